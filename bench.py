@@ -5,6 +5,8 @@ Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N > 1 it
 torch.distributed.run with one rank per GPU (RCCL).  A "step" is one pass of the hot path over
 one resident batch per GPU -- fp32 NHWC crops in HBM -> poses [B, Jout, 3] in HBM -- plus, for
 N > 1, the one all-gather of the pose outputs.  Weak scaling: the per-GPU batch is fixed.
+`--dump-outputs DIR` writes the poses of the last timed step to DIR/poses.npy (float32; for N > 1 the gathered
+poses of all ranks), so that two builds can be compared output for output on the same seeded inputs.
 
 Workload (BASELINE.json configs[1], the config the metric is quoted on): ResNet-50, stride 16,
 17 H36M joints, batch 64 per GPU, fp16 compute (the reference's default dtype, options.py:73),
@@ -140,7 +142,13 @@ def parse_args():
                          'the step is from the power budget that sets the clock (MI355X_MICROARCH.md, DVFS give-back)')
     ap.add_argument('--no-extras', action='store_true',
                     help='skip the accuracy / parity-mode / batch-256 legs (profiling runs)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', type=str, default=None, metavar='DIR',
+                    help='write what the last timed step returned to its caller as DIR/<name>.npy (float32): the poses, '
+                         'all-gathered over the ranks for N > 1; the seeded inputs make runs with the same arguments comparable')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def kernels_sha16() -> str:
@@ -529,6 +537,11 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # the last timed step's result as its caller holds it, copied before the legs below reuse `local` as an output buffer
+        poses = gatherer.result(step_no[0] - 1) if world > 1 else local
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'poses.npy'), poses.cpu().numpy().astype(np.float32))
     if not torch.isfinite(local).all():
         print('bench.py: non-finite poses', file=sys.stderr)
         sys.exit(3)
