@@ -333,6 +333,41 @@ int  metro_prep_input_f16(const float* d_images, int32_t n, int32_t side, void* 
 int  metro_warp_crop_u8(const uint8_t* d_image, int32_t h, int32_t w, int32_t row_stride,
                         const float* d_homographies, int32_t n, int32_t side, float* d_out, void* stream);
 
+/* Crops from MANY uint8 HWC RGB frames in one launch, with or without lens distortion of the original camera (the full
+ * camera path of reference src/cameralib.py:265-324 reproject_image + src/improc.py:56-61 normalize01).
+ * frames: HOST array of n_frames <= METRO_MAX_FRAMES entries (copied into the kernel arguments); frames may differ in size and
+ * be separate allocations; h, w <= 32767 (cv2.remap's short coordinates), row_stride >= 3 w.
+ * d_crops: DEVICE array of n MetroCropWarp records.  Crop i samples frame d_crops[i].frame (a crop whose index is outside
+ * [0, n_frames) comes out as the border value 0: the index is device data, the host binding checks it) in one of two modes:
+ *   METRO_WARP_HOMOGRAPHY  reproject_image_fast (cameralib.py:406-429): fp32 homography, the coordinate chain of
+ *                          metro_warp_crop_u8 (bit for bit the same bytes for the same homography);
+ *   METRO_WARP_DISTORTED   reproject_image case 2 (cameralib.py:294-312) for an original camera WITH distortion coefficients:
+ *                          ray = partial (x, y, 1) in fp64 (the fp32 grid against the fp64 partial_homography, :297-306,
+ *                          evaluated rn(rn(rn(P0 x) + rn(P1 y)) + P2)), cast to fp32, then project_points' fp32 chain in its
+ *                          statement order (cameralib.py:375-397: r2, r4, r6, the distorter k1 k2 k3 1 p2 p1, the in-place
+ *                          multiply-adds, K[:2,:2] and K[:2,2]); a ray with z <= 0 (or NaN) samples nothing (the border
+ *                          value 0) -- the reference would project it through the origin.
+ * Both modes then sample with cv2.remap's 8-bit rule exactly like metro_warp_crop_u8.  d_out: fp32 NHWC [n, side, side, 3],
+ * the input contract of metro_forward. */
+#define METRO_MAX_FRAMES 64
+#define METRO_WARP_HOMOGRAPHY 0
+#define METRO_WARP_DISTORTED 1
+typedef struct MetroFrame {
+    const uint8_t* data;        /* device pointer to row 0, pixel 0 */
+    int32_t h, w, row_stride;   /* row_stride in bytes */
+    int32_t reserved;
+} MetroFrame;                   /* 24 bytes */
+typedef struct MetroCropWarp {
+    int32_t frame;              /* index into the frame table */
+    int32_t mode;               /* METRO_WARP_HOMOGRAPHY | METRO_WARP_DISTORTED */
+    double partial[9];          /* DISTORTED: row-major fp64 partial_homography = old.R inv(new.R) inv(new.K) */
+    float homography[9];        /* HOMOGRAPHY: row-major, maps output pixel (x, y, 1) to source pixel coordinates */
+    float intrinsics[6];        /* DISTORTED: the original camera's K[0,0] K[0,1] K[0,2] K[1,0] K[1,1] K[1,2] */
+    float distortion[5];        /* DISTORTED: k1 k2 p1 p2 k3 (OpenCV order) */
+} MetroCropWarp;                /* 160 bytes */
+int  metro_warp_crops_frames_u8(const MetroFrame* frames, int32_t n_frames, const MetroCropWarp* d_crops, int32_t n,
+                                int32_t side, float* d_out, void* stream);
+
 /* 3x3 stride-2 max-pool over a ZERO-padded (1,1) input (reference resnet_utils.py:177-185).
  * dtype METRO_F16 / METRO_F32 / METRO_F64; c % 8 == 0 (f16), c % 4 == 0 (f32), c % 2 == 0 (f64). */
 int  metro_maxpool3x3s2_zeropad(const void* d_in, void* d_out, int32_t n, int32_t h_in,

@@ -59,6 +59,20 @@ class MetroConvDesc(C.Structure):
                 ('in_dtype', C.c_int32)]
 
 
+METRO_MAX_FRAMES = 64
+METRO_WARP_HOMOGRAPHY, METRO_WARP_DISTORTED = 0, 1
+
+
+class MetroFrame(C.Structure):
+    _fields_ = [('data', C.c_void_p), ('h', C.c_int32), ('w', C.c_int32), ('row_stride', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
+class MetroCropWarp(C.Structure):
+    _fields_ = [('frame', C.c_int32), ('mode', C.c_int32), ('partial', C.c_double * 9), ('homography', C.c_float * 9),
+                ('intrinsics', C.c_float * 6), ('distortion', C.c_float * 5)]
+
+
 # symbol -> (restype, argtypes); must list every function include/metro_hip.h declares
 _P = C.c_void_p
 SIGNATURES = {
@@ -95,6 +109,7 @@ SIGNATURES = {
     'metro_stem_pool_f32in': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     'metro_prep_input_f16': (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P]),
     'metro_warp_crop_u8': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
+    'metro_warp_crops_frames_u8': (C.c_int, [C.POINTER(MetroFrame), C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
     'metro_eval_metrics': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_float, _P, _P, _P, _P]),
     'metro_maxpool3x3s2_zeropad': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_int32, _P]),

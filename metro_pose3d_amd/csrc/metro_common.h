@@ -339,6 +339,9 @@ int launch_conv_f64acc(const MetroConvDesc& d, const void* in, const double* w, 
 int launch_conv_f32m(const MetroConvDesc& d, const void* in, const float* w, const float* bias, const float* pro_scale,
                      const float* pro_shift, const void* residual, void* out, hipStream_t stream);
 int launch_prep_input_f16(const float* images, int n, int side, void* out, hipStream_t stream);
+struct FrameTable { MetroFrame f[METRO_MAX_FRAMES]; };
+int launch_warp_crops_frames_u8(const FrameTable& frames, int n_frames, const MetroCropWarp* crops, int n, int side,
+                                float* out, hipStream_t stream);
 int launch_warp_crop_u8(const unsigned char* img, int h, int w, int row_stride, const float* homs, float* out,
                         int n, int side, hipStream_t stream);
 int launch_eval_metrics(const float* pred, const float* truth, const unsigned char* valid, int n, int nj,

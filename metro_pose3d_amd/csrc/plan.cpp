@@ -1187,6 +1187,25 @@ int metro_warp_crop_u8(const uint8_t* d_image, int32_t h, int32_t w, int32_t row
     return launch_warp_crop_u8(d_image, h, w, row_stride, d_homographies, d_out, n, side, static_cast<hipStream_t>(stream));
 }
 
+int metro_warp_crops_frames_u8(const MetroFrame* frames, int32_t n_frames, const MetroCropWarp* d_crops, int32_t n,
+                               int32_t side, float* d_out, void* stream) {
+    METRO_CHECK_ARG(frames && d_crops && d_out, "warp_crops_frames_u8: NULL pointer");
+    METRO_CHECK_ARG(n_frames > 0 && n_frames <= METRO_MAX_FRAMES, "warp_crops_frames_u8: %d frames (1 to %d per launch)",
+                    n_frames, METRO_MAX_FRAMES);
+    METRO_CHECK_ARG(n > 0 && side > 0, "warp_crops_frames_u8: bad geometry (n %d side %d)", n, side);
+    metro::FrameTable table = {};
+    for (int i = 0; i < n_frames; ++i) {
+        const MetroFrame& f = frames[i];
+        METRO_CHECK_ARG(f.data, "warp_crops_frames_u8: frame %d: NULL data pointer", i);
+        METRO_CHECK_ARG(f.h <= 32767 && f.w <= 32767, "warp_crops_frames_u8: frame %d: frames larger than 32767 pixels a side "
+                        "are outside cv2.remap's short coordinates (h %d w %d)", i, f.h, f.w);
+        METRO_CHECK_ARG(f.h > 0 && f.w > 0 && f.row_stride >= 3 * f.w,
+                        "warp_crops_frames_u8: frame %d: bad geometry (h %d w %d stride %d)", i, f.h, f.w, f.row_stride);
+        table.f[i] = f;
+    }
+    return launch_warp_crops_frames_u8(table, n_frames, d_crops, n, side, d_out, static_cast<hipStream_t>(stream));
+}
+
 int metro_eval_metrics(const float* d_pred, const float* d_true, const uint8_t* d_valid, int32_t n, int32_t n_joints,
                        float threshold_mm, float* d_dist, float* d_dist_aligned, double* d_sums, void* stream) {
     METRO_CHECK_ARG(d_pred && d_true && d_valid && d_dist && d_dist_aligned && d_sums, "eval_metrics: NULL pointer");

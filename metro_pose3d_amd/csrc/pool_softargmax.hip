@@ -64,6 +64,41 @@ __device__ __forceinline__ int cv_round_x86(float v) {
     return (fabsf(v) < 2147483648.f) ? __float2int_rn(v) : (int)0x80000000;
 }
 
+// Source coordinates of output pixel (x, y) through homography H (see above).
+__device__ __forceinline__ void homography_coords(const float* H, float fx, float fy, float& u, float& v) {
+    const float cx = __fmaf_rn(H[2], 1.f, __fmaf_rn(H[1], fy, __fmul_rn(H[0], fx)));
+    const float cy = __fmaf_rn(H[5], 1.f, __fmaf_rn(H[4], fy, __fmul_rn(H[3], fx)));
+    const float cw = __fmaf_rn(H[8], 1.f, __fmaf_rn(H[7], fy, __fmul_rn(H[6], fx)));
+    u = __fdiv_rn(cx, cw);
+    v = __fdiv_rn(cy, cw);
+}
+
+// cv2.remap's 8-bit INTER_LINEAR / BORDER_CONSTANT 0 sample of the uint8 HWC frame at (u, v), then normalize01, into o[0..2].
+// h, w <= 32767: a coordinate saturated to the short range (or INT_MIN >> 5 from a NaN / huge value) is outside the frame.
+__device__ __forceinline__ void sample_u8_normalized(const unsigned char* __restrict__ img, int h, int w, int row_stride,
+                                                     float u, float v, float* __restrict__ o) {
+    const int sx = cv_round_x86(__fmul_rn(u, 32.f)), sy = cv_round_x86(__fmul_rn(v, 32.f));
+    const int ax = sx & 31, ay = sy & 31;
+    int x0 = sx >> 5, y0 = sy >> 5;
+    x0 = x0 < -32768 ? -32768 : (x0 > 32767 ? 32767 : x0);          // saturate_cast<short>
+    y0 = y0 < -32768 ? -32768 : (y0 > 32767 ? 32767 : y0);
+    const int wgt[4] = {32 * (32 - ay) * (32 - ax), 32 * (32 - ay) * ax, 32 * ay * (32 - ax), 32 * ay * ax};
+    int acc[3] = {0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int xx = x0 + (k & 1), yy = y0 + (k >> 1);
+        if ((unsigned)xx < (unsigned)w && (unsigned)yy < (unsigned)h) {
+            const unsigned char* s = img + (size_t)yy * row_stride + (size_t)xx * 3;
+            acc[0] += wgt[k] * (int)s[0]; acc[1] += wgt[k] * (int)s[1]; acc[2] += wgt[k] * (int)s[2];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int byte = (acc[c] + (1 << 14)) >> 15;                  // <= 255: the weights sum to 2^15
+        o[c] = fminf(fmaxf(__fdiv_rn((float)byte, 255.f), -1.f), 1.f);
+    }
+}
+
 __global__ __launch_bounds__(256) void warp_crop_u8_kernel(const unsigned char* __restrict__ img, int h, int w,
                                                            int row_stride, const float* __restrict__ homs,
                                                            float* __restrict__ out, int n, int side) {
@@ -73,33 +108,9 @@ __global__ __launch_bounds__(256) void warp_crop_u8_kernel(const unsigned char* 
         const long t = p / side;
         const int y = (int)(t % side);
         const int i = (int)(t / side);
-        const float* H = homs + i * 9;
-        const float fx = (float)x, fy = (float)y;
-        const float cx = __fmaf_rn(H[2], 1.f, __fmaf_rn(H[1], fy, __fmul_rn(H[0], fx)));
-        const float cy = __fmaf_rn(H[5], 1.f, __fmaf_rn(H[4], fy, __fmul_rn(H[3], fx)));
-        const float cw = __fmaf_rn(H[8], 1.f, __fmaf_rn(H[7], fy, __fmul_rn(H[6], fx)));
-        const float u = __fdiv_rn(cx, cw), v = __fdiv_rn(cy, cw);
-        const int sx = cv_round_x86(__fmul_rn(u, 32.f)), sy = cv_round_x86(__fmul_rn(v, 32.f));
-        const int ax = sx & 31, ay = sy & 31;
-        int x0 = sx >> 5, y0 = sy >> 5;
-        x0 = x0 < -32768 ? -32768 : (x0 > 32767 ? 32767 : x0);          // saturate_cast<short>
-        y0 = y0 < -32768 ? -32768 : (y0 > 32767 ? 32767 : y0);
-        const int wgt[4] = {32 * (32 - ay) * (32 - ax), 32 * (32 - ay) * ax, 32 * ay * (32 - ax), 32 * ay * ax};
-        int acc[3] = {0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int xx = x0 + (k & 1), yy = y0 + (k >> 1);
-            if ((unsigned)xx < (unsigned)w && (unsigned)yy < (unsigned)h) {
-                const unsigned char* s = img + (size_t)yy * row_stride + (size_t)xx * 3;
-                acc[0] += wgt[k] * (int)s[0]; acc[1] += wgt[k] * (int)s[1]; acc[2] += wgt[k] * (int)s[2];
-            }
-        }
-        float* o = out + p * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int byte = (acc[c] + (1 << 14)) >> 15;                  // <= 255: the weights sum to 2^15
-            o[c] = fminf(fmaxf(__fdiv_rn((float)byte, 255.f), -1.f), 1.f);
-        }
+        float u, v;
+        homography_coords(homs + i * 9, (float)x, (float)y, u, v);
+        sample_u8_normalized(img, h, w, row_stride, u, v, out + p * 3);
     }
 }
 
@@ -109,6 +120,77 @@ int launch_warp_crop_u8(const unsigned char* img, int h, int w, int row_stride, 
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
     hipLaunchKernelGGL(warp_crop_u8_kernel, dim3(blocks), dim3(256), 0, stream, img, h, w, row_stride, homs, out, n, side);
     return launch_status("warp_crop_u8");
+}
+
+// ---------------------------------------------------------------------------------------------
+// Crops from many frames in one launch (metro_warp_crops_frames_u8, include/metro_hip.h).  Same thread layout and sampling
+// as warp_crop_u8_kernel; the crop's record selects the frame and the coordinate chain.  Every lane of a wave reads the same
+// record unless the wave straddles two crops (side * side not a multiple of 64).
+// DISTORTED: reference cameralib.py:297-312 (fp64 ray of the fp32 grid) and :375-397 (project_points, fp32).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void distorted_coords(const MetroCropWarp& c, float fx, float fy, float& u, float& v) {
+    // every product and sum rounded on its own, as NumPy evaluates them: no contraction into fma in this function
+    // (plain operators: the pragma does not reach the bodies of the __fmul_rn-style helpers)
+#pragma clang fp contract(off)
+    const double* P = c.partial;
+    const double dx = (double)fx, dy = (double)fy;
+    const float rx = (float)((P[0] * dx + P[1] * dy) + P[2]);
+    const float ry = (float)((P[3] * dx + P[4] * dy) + P[5]);
+    const float rz = (float)((P[6] * dx + P[7] * dy) + P[8]);
+    if (!(rz > 0.f)) {                          // behind the camera (or NaN): cv_round_x86(NaN) = INT_MIN -> border
+        u = v = __builtin_nanf("");
+        return;
+    }
+    const float* d = c.distortion;              // k1 k2 p1 p2 k3
+    float px = rx / rz, py = ry / rz;
+    const float r2 = px * px + py * py;
+    const float r4 = r2 * r2;
+    float dist = d[0] * r2;
+    dist += d[1] * r4;
+    const float r6 = r4 * r2;
+    dist += d[4] * r6;
+    dist += 1.f;
+    dist += px * (2.f * d[3]);
+    dist += py * (2.f * d[2]);
+    px = px * dist + r2 * d[3];
+    py = py * dist + r2 * d[2];
+    const float* K = c.intrinsics;              // K00 K01 K02 K10 K11 K12; [N,2] @ K[:2,:2].T + K[:2,2] like the matmul above
+    u = __fmaf_rn(py, K[1], px * K[0]) + K[2];
+    v = __fmaf_rn(py, K[4], px * K[3]) + K[5];
+}
+
+__global__ __launch_bounds__(256) void warp_crops_frames_u8_kernel(const FrameTable frames, int n_frames,
+                                                                   const MetroCropWarp* __restrict__ crops,
+                                                                   float* __restrict__ out, int n, int side) {
+    const long total = (long)n * side * side;
+    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(p % side);
+        const long t = p / side;
+        const int y = (int)(t % side);
+        const MetroCropWarp& c = crops[t / side];
+        const int fi = c.frame;
+        float* o = out + p * 3;
+        if ((unsigned)fi >= (unsigned)n_frames) {
+            o[0] = o[1] = o[2] = 0.f;
+            continue;
+        }
+        const MetroFrame& f = frames.f[fi];
+        float u, v;
+        if (c.mode == METRO_WARP_DISTORTED)
+            distorted_coords(c, (float)x, (float)y, u, v);
+        else
+            homography_coords(c.homography, (float)x, (float)y, u, v);
+        sample_u8_normalized(f.data, f.h, f.w, f.row_stride, u, v, o);
+    }
+}
+
+int launch_warp_crops_frames_u8(const FrameTable& frames, int n_frames, const MetroCropWarp* crops, int n, int side,
+                                float* out, hipStream_t stream) {
+    const long total = (long)n * side * side;
+    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    hipLaunchKernelGGL(warp_crops_frames_u8_kernel, dim3(blocks), dim3(256), 0, stream, frames, n_frames, crops, out, n,
+                       side);
+    return launch_status("warp_crops_frames_u8");
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,0 +1,335 @@
+"""Pose estimation on full camera frames: person boxes and (optionally calibrated, lens-distorted) cameras in, poses out.
+
+The reference's test path (src/data/data_loading.py:33-58, 107-111) builds a virtual camera per person box that turns towards
+the box centre, drops the lens distortion, squares the pixels and zooms so the box fills the crop; `cameralib.reproject_image`
+(src/cameralib.py:265-324) warps the uint8 frame into it; after the net `volumetric.to_orig_cam` (src/model/volumetric.py:
+204-216, 277-281) rotates the poses back into the original camera or the world.  Here:
+
+  Camera, undistort_points, look_at_box   host geometry, the reference's camera restated in its dtypes (fp32 R, K, t)
+  crop_params                             per-crop warp mode + matrices and the rotations back (data_loading.py:110-111)
+  warp_frames                             one HIP launch (metro_warp_crops_frames_u8) for the crops of many frames
+  estimate_pose_in_frames                 the whole chain on one device, enqueued on the current stream
+
+Divergences from the reference, on purpose:
+  * a Camera built from intrinsics alone (no R, no t) defaults to world_up = (0, -1, 0), not the reference's (0, 0, 1): with
+    R = I and t = 0, `turn_towards` takes cross(new_z, (0, 0, 1)), which vanishes for a box near the optical axis;
+  * reproject_image's case 1 (cameralib.py:282-293: an all-zero coefficient array whose virtual R is allclose to the original
+    goes to cv2.warpAffine, with INTER_AREA when zooming out) is not reproduced: any coefficient array takes the general mode;
+  * a general-mode ray that points behind the camera (z <= 0) samples the border value 0; the reference projects it through
+    the origin.
+"""
+from __future__ import annotations
+
+import copy
+import ctypes as C
+import os
+from typing import NamedTuple, Optional, Sequence
+
+import numpy as np
+import torch
+
+from metro_pose3d_amd import _lib
+from metro_pose3d_amd._lib import check
+from metro_pose3d_amd.preprocess import box_homography
+
+UNDISTORT_ITERATIONS = 5
+
+
+def undistort_points(points, intrinsic_matrix, distortion_coeffs) -> np.ndarray:
+    """cv2.undistortPoints(points, K, D) with R = P = None -> float32 [N, 2] normalised camera coordinates.
+
+    OpenCV is absent here, so this is restated from its published source, modules/imgproc/src/undistort.cpp
+    (cvUndistortPoints / cvUndistortPointsInternal, 3.x): K and D converted to double; fx, fy, cx, cy only (a skew term is
+    ignored); x = (u - cx) * (1 / fx); with coefficients, the fixed-point iteration
+        icdist = 1 / (1 + ((k3 r2 + k2) r2 + k1) r2),  x = (x0 - dx) icdist
+    run for the fixed count of the default criteria, TermCriteria(COUNT, 5, 0.01) (`iters = 5` in the older 3.x form), then
+    the result is stored as float32 like the float32 input.  PARITY UNPINNED against cv2 itself (no OpenCV to execute)."""
+    p = np.asarray(points, np.float32).reshape(-1, 2).astype(np.float64)
+    a = np.asarray(intrinsic_matrix, np.float64)
+    fx, fy, cx, cy = a[0, 0], a[1, 1], a[0, 2], a[1, 2]
+    ifx, ify = 1. / fx, 1. / fy
+    x = (p[:, 0] - cx) * ifx
+    y = (p[:, 1] - cy) * ify
+    if distortion_coeffs is not None:
+        k = np.zeros(14)
+        d = np.asarray(distortion_coeffs, np.float64).ravel()
+        k[:len(d)] = d
+        x0, y0 = x, y
+        for _ in range(UNDISTORT_ITERATIONS):
+            r2 = x * x + y * y
+            icdist = (1 + ((k[7] * r2 + k[6]) * r2 + k[5]) * r2) / (1 + ((k[4] * r2 + k[1]) * r2 + k[0]) * r2)
+            delta_x = 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x) + k[8] * r2 + k[9] * r2 * r2
+            delta_y = k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y + k[10] * r2 + k[11] * r2 * r2
+            x = (x0 - delta_x) * icdist
+            y = (y0 - delta_y) * icdist
+    return np.stack([x, y], axis=-1).astype(np.float32)
+
+
+class Camera:
+    """The parts of the reference's cameralib.Camera (src/cameralib.py:25-84) the frame pipeline needs, in its dtypes:
+    R (world -> camera rotation), t (optical centre in world coordinates) and the intrinsic matrix are float32, the
+    distortion coefficients (k1, k2, p1, p2, k3; OpenCV order) float32 or None.
+
+    world_up defaults to (0, 0, 1) like the reference when R or t is given; a camera built from intrinsics alone defaults to
+    (0, -1, 0) (image y points down, so "up" is -y): the reference default degenerates there (module docstring)."""
+
+    def __init__(self, intrinsic_matrix, distortion_coeffs=None, R=None, t=None, world_up=None):
+        if world_up is None:
+            world_up = (0, -1, 0) if R is None and t is None else (0, 0, 1)
+        self.R = np.asarray(np.eye(3) if R is None else R, np.float32)
+        self.t = np.asarray(np.zeros(3) if t is None else t, np.float32)
+        self.intrinsic_matrix = np.asarray(intrinsic_matrix, np.float32)
+        self.distortion_coeffs = None if distortion_coeffs is None else np.asarray(distortion_coeffs, np.float32)
+        self.world_up = np.asarray(world_up)
+        if self.R.shape != (3, 3) or self.t.shape != (3,) or self.intrinsic_matrix.shape != (3, 3):
+            raise ValueError('R and intrinsic_matrix must be 3x3, t a 3-vector')
+        if not np.allclose(self.intrinsic_matrix[2, :], [0, 0, 1]):
+            raise ValueError(f'bottom row of the intrinsic matrix must be (0, 0, 1), got {self.intrinsic_matrix[2, :]}')
+        if self.distortion_coeffs is not None and self.distortion_coeffs.shape != (5,):
+            raise ValueError(f'distortion_coeffs must be None or 5 values (k1, k2, p1, p2, k3), got '
+                             f'{self.distortion_coeffs.shape}')
+
+    def copy(self) -> 'Camera':
+        return copy.deepcopy(self)
+
+    # cameralib.py:133-156
+    def world_to_camera(self, points):
+        return (np.asarray(points, np.float32) - self.t) @ self.R.T
+
+    def camera_to_world(self, points):
+        return np.asarray(points, np.float32) @ np.linalg.inv(self.R).T + self.t
+
+    def camera_to_image_undistorted(self, points):
+        """camera_to_image (:126-131) of a camera without distortion coefficients."""
+        assert self.distortion_coeffs is None
+        projected = points[:, :2] / points[:, 2:]
+        return projected @ self.intrinsic_matrix[:2, :2].T + self.intrinsic_matrix[:2, 2]
+
+    def image_to_camera(self, points):
+        p = undistort_points(points, self.intrinsic_matrix, self.distortion_coeffs)
+        return np.concatenate([p, np.ones_like(p[:, :1])], axis=1)        # convertPointsToHomogeneous, depth 1
+
+    def image_to_world(self, points):
+        return self.camera_to_world(self.image_to_camera(points))
+
+    # cameralib.py:167-228
+    def turn_towards(self, target_image_point):
+        target_world_point = self.image_to_world(np.asarray([target_image_point], np.float64))[0]
+        new_z = target_world_point - self.t
+        new_z = new_z / np.linalg.norm(new_z)
+        new_x = np.cross(new_z, self.world_up)
+        new_x = new_x / np.linalg.norm(new_x)
+        new_y = np.cross(new_z, new_x)
+        self.R = np.vstack([new_x, new_y, new_z]).astype(np.float32)
+
+    def undistort(self):
+        self.distortion_coeffs = None
+
+    def square_pixels(self):
+        fx, fy = self.intrinsic_matrix[0, 0], self.intrinsic_matrix[1, 1]
+        fmean = 0.5 * (fx + fy)
+        multiplier = np.array([[fmean / fx, 0, 0], [0, fmean / fy, 0], [0, 0, 1]])     # float64, so K becomes float64
+        self.intrinsic_matrix = multiplier @ self.intrinsic_matrix
+
+    def zoom(self, factor):
+        self.intrinsic_matrix[:2, :2] *= np.expand_dims(factor, -1)
+
+    def center_principal_point(self, imshape):
+        self.intrinsic_matrix[:2, 2] = [imshape[1] / 2, imshape[0] / 2]
+
+
+def look_at_box(camera: Camera, box: Sequence[float], side: int = 256) -> Camera:
+    """The virtual camera of a crop: reference cameralib.look_at_box (src/cameralib.py:337-358), step by step -- turn towards
+    the box centre, undistort, square the pixels, zoom so that the box's longer side (measured between the two side midpoints,
+    through the world) spans `side` pixels, centre the principal point.  This is the reference's stand-alone helper; the
+    training loader's variant (data_loading.py:33-58: the norm of the side-point difference, a 1.05 box expansion for 3DHP,
+    augmentation flags) is not what is restated here."""
+    cam = camera.copy()
+    box = np.asarray(box, np.float64)
+    center_point = box[:2] + box[2:] / 2
+    delta_x = np.array([box[2] / 2, 0])
+    delta_y = np.array([0, box[3] / 2])
+    if box[2] < box[3]:
+        sidepoints = np.stack([center_point - delta_y, center_point + delta_y])
+    else:
+        sidepoints = np.stack([center_point - delta_x, center_point + delta_x])
+    world_sidepoints = camera.image_to_world(sidepoints)
+    cam.turn_towards(center_point)
+    cam.undistort()
+    cam.square_pixels()
+    cam_sidepoints = cam.camera_to_image_undistorted(cam.world_to_camera(world_sidepoints))
+    if box[2] < box[3]:
+        crop_side = np.abs(cam_sidepoints[0, 1] - cam_sidepoints[1, 1])
+    else:
+        crop_side = np.abs(cam_sidepoints[0, 0] - cam_sidepoints[1, 0])
+    cam.zoom(side / crop_side)
+    cam.center_principal_point((side, side))
+    return cam
+
+
+class CropParams(NamedTuple):
+    """Per-crop warp parameters (the fields of MetroCropWarp, include/metro_hip.h) and the rotations back."""
+    mode: np.ndarray             # int32 [n]: _lib.METRO_WARP_HOMOGRAPHY | METRO_WARP_DISTORTED
+    homography: np.ndarray       # float32 [n, 3, 3]
+    partial: np.ndarray          # float64 [n, 3, 3]
+    intrinsics: np.ndarray       # float32 [n, 3, 3] (the original camera's K)
+    distortion: np.ndarray       # float32 [n, 5]
+    rot_to_orig_cam: np.ndarray  # float32 [n, 3, 3]
+    rot_to_world: np.ndarray     # float32 [n, 3, 3]
+
+
+def _camera_of(cameras, f: int) -> Camera:
+    if isinstance(cameras, Camera):
+        return cameras
+    return cameras[f]
+
+
+def crop_params(cameras, boxes, frame_index, side: int = 256) -> CropParams:
+    """Warp parameters of n crops.  `cameras`: None, one Camera for every frame, or a list with one Camera per frame.
+
+    A camera with distortion_coeffs None takes the homography mode (reproject_image_fast, cameralib.py:406-412: K R of both
+    cameras, solve, cast to float32); any coefficient array, even all zeros, takes the general mode (reproject_image case 2,
+    :294-306: partial_homography = old.R inv(new.R) inv(new.K), float64), as the test at :272 sends it there.
+    rot_to_orig_cam = orig.R virt.R^T and rot_to_world = virt.R^T (data_loading.py:110-111).
+    cameras=None: the axis-aligned square crop of preprocess.box_homography, rotations I."""
+    boxes = np.asarray(boxes, np.float64).reshape(-1, 4)
+    n = len(boxes)
+    fi = np.asarray(frame_index, np.int64).reshape(n)
+    p = CropParams(np.zeros(n, np.int32), np.zeros((n, 3, 3), np.float32), np.zeros((n, 3, 3)),
+                   np.zeros((n, 3, 3), np.float32), np.zeros((n, 5), np.float32),
+                   np.tile(np.eye(3, dtype=np.float32), (n, 1, 1)), np.tile(np.eye(3, dtype=np.float32), (n, 1, 1)))
+    for i, box in enumerate(boxes):
+        if cameras is None:
+            p.homography[i] = box_homography(box, side)
+            continue
+        orig = _camera_of(cameras, int(fi[i]))
+        virt = look_at_box(orig, box, side)
+        if orig.distortion_coeffs is None:
+            old_matrix = orig.intrinsic_matrix @ orig.R                         # float32, as cameralib.py:410
+            new_matrix = virt.intrinsic_matrix @ virt.R                         # float64 (square_pixels made K float64)
+            p.homography[i] = np.linalg.solve(new_matrix.T, old_matrix.T).T.astype(np.float32)
+        else:
+            p.mode[i] = _lib.METRO_WARP_DISTORTED
+            p.partial[i] = orig.R @ np.linalg.inv(virt.R) @ np.linalg.inv(virt.intrinsic_matrix)
+            p.intrinsics[i] = orig.intrinsic_matrix
+            p.distortion[i] = orig.distortion_coeffs
+        p.rot_to_orig_cam[i] = (orig.R @ virt.R.T).astype(np.float32)
+        p.rot_to_world[i] = virt.R.T.astype(np.float32)
+    return p
+
+
+def pack_crops(params: CropParams, frame_index) -> np.ndarray:
+    """The MetroCropWarp records (include/metro_hip.h) of `params` as a byte array [n, 160]."""
+    n = len(params.mode)
+    rec = (_lib.MetroCropWarp * n)()
+    k = params.intrinsics
+    for i in range(n):
+        r = rec[i]
+        r.frame, r.mode = int(frame_index[i]), int(params.mode[i])
+        r.partial[:] = params.partial[i].ravel().tolist()
+        r.homography[:] = params.homography[i].ravel().tolist()
+        r.intrinsics[:] = [float(v) for v in (k[i, 0, 0], k[i, 0, 1], k[i, 0, 2], k[i, 1, 0], k[i, 1, 1], k[i, 1, 2])]
+        r.distortion[:] = params.distortion[i].tolist()
+    return np.frombuffer(bytearray(rec), np.uint8).reshape(n, C.sizeof(_lib.MetroCropWarp))
+
+
+def _upload(a: np.ndarray, device: torch.device) -> torch.Tensor:
+    """Host array -> device tensor without a host synchronisation (pinned staging, non-blocking copy)."""
+    return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(device, non_blocking=True)
+
+
+def _device_frames(frames, device: torch.device):
+    if isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 3:
+        frames = [frames]
+    out = []
+    for k, f in enumerate(frames):
+        if isinstance(f, np.ndarray):
+            f = torch.from_numpy(f)
+        if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3:
+            raise ValueError(f'frame {k} must be a uint8 [H, W, 3] tensor or array, got '
+                             f'{getattr(f, "dtype", type(f))} {tuple(getattr(f, "shape", ()))}')
+        if f.is_cuda and f.device != device:
+            raise ValueError(f'frame {k} is on {f.device}, the call runs on {device}')
+        if not f.is_cuda:
+            f = _upload(f.numpy(), device)
+        if f.stride(2) != 1 or f.stride(1) != 3 or f.stride(0) < 3 * f.shape[1]:
+            f = f.contiguous()
+        out.append(f)
+    if not out:
+        raise ValueError('no frames')
+    if len(out) > _lib.METRO_MAX_FRAMES:
+        raise ValueError(f'{len(out)} frames: at most {_lib.METRO_MAX_FRAMES} per call')
+    return out
+
+
+def warp_frames(frames, params: CropParams, frame_index, side: int = 256, device: Optional[torch.device] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [H, W, 3] frames (a tensor or a list; host or device; sizes may differ) + per-crop parameters -> fp32 NHWC
+    [n, side, side, 3] crops in [0, 1] on the device, in ONE launch on the current stream."""
+    if device is None:
+        first = frames if isinstance(frames, torch.Tensor) else frames[0] if isinstance(frames, (list, tuple)) and frames else None
+        device = first.device if isinstance(first, torch.Tensor) and first.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    dev_frames = _device_frames(frames, device)
+    n = len(params.mode)
+    fi = np.asarray(frame_index, np.int64).reshape(n)
+    if n and (fi.min() < 0 or fi.max() >= len(dev_frames)):
+        raise ValueError(f'frame_index must lie in [0, {len(dev_frames)}), got [{fi.min()}, {fi.max()}]')
+    if out is None:
+        out = torch.empty((n, side, side, 3), dtype=torch.float32, device=device)
+    if n == 0:
+        return out
+    table = (_lib.MetroFrame * len(dev_frames))()
+    for k, f in enumerate(dev_frames):
+        table[k].data, table[k].h, table[k].w, table[k].row_stride = f.data_ptr(), f.shape[0], f.shape[1], f.stride(0)
+    crops = _upload(pack_crops(params, fi), device)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    check(_lib.load().metro_warp_crops_frames_u8(table, len(dev_frames), C.c_void_p(crops.data_ptr()), n, side,
+                                                 C.c_void_p(out.data_ptr()), C.c_void_p(stream)), 'metro_warp_crops_frames_u8')
+    return out
+
+
+def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index=None, coords: str = 'camera',
+                            precision: Optional[str] = None, check_finite: Optional[bool] = None):
+    """uint8 frames + person boxes [n, 4] (x, y, w, h) -> (poses [n, Jout, 3] mm, joint_edges, joint_names) like estimate_pose.
+
+    frames: a uint8 [H, W, 3] tensor / array or a list of them (host or device, sizes may differ, at most 64);
+    frame_index [n]: the frame of each box (default: every box on frame 0); cameras: None (axis-aligned square crops, what
+    preprocess.box_homography gives), one Camera for all frames, or one Camera per frame.
+    The poses are root-relative, in `coords`:
+      'crop'    the virtual camera of each crop: what estimate_pose returns for the crops;
+      'camera'  the original camera (volumetric.py:204-205, 277-281: rotation by rot_to_orig_cam, mirrored joints when
+                det <= 0);
+      'world'   rotation by rot_to_world only (root-relative poses carry no translation; volumetric.py:206-208 adds cam_loc
+                to absolute ones).
+    One enqueue chain on the current stream of the local device: frame and parameter uploads (pinned, non-blocking), one warp
+    launch, estimate_pose's forward in <= 256-crop chunks on its cached engine with its finite screen (its one stream
+    synchronisation), then metro_to_orig_cam.  Runs on the local device only (estimate_pose's shard=False): sharding across
+    ranks is not supported here."""
+    from metro_pose3d_amd.inference import _engine_for, _resolve_device, estimate_pose
+    if coords not in ('crop', 'camera', 'world'):
+        raise ValueError(f"coords must be 'crop', 'camera' or 'world', got {coords!r}")
+    if precision is None:
+        precision = os.environ.get('METRO_PRECISION', 'f16')
+    boxes = np.asarray(boxes, np.float64)
+    if boxes.ndim != 2 or boxes.shape[1] != 4:
+        raise ValueError(f'boxes must be [n, 4] (x, y, w, h), got {boxes.shape}')
+    n = len(boxes)
+    fi = np.zeros(n, np.int64) if frame_index is None else np.asarray(frame_index, np.int64).reshape(n)
+    first = frames if isinstance(frames, torch.Tensor) else frames[0] if isinstance(frames, (list, tuple)) and frames else None
+    device = _resolve_device(first if isinstance(first, torch.Tensor) else torch.empty(0))
+    with torch.cuda.device(device):
+        side = _engine_for(model_path, precision, device, max(n, 1)).spec.proc_side
+        params = crop_params(cameras, boxes, fi, side)
+        crops = warp_frames(frames, params, fi, side, device=device)
+        poses, edges, names = estimate_pose(crops, model_path, precision=precision, check_finite=check_finite, shard=False)
+        if coords == 'crop' or n == 0:
+            return poses, edges, names
+        sk = _engine_for(model_path, precision, device, max(n, 1)).spec.skeleton
+        rot = _upload((params.rot_to_orig_cam if coords == 'camera' else params.rot_to_world).reshape(n, 9), device)
+        mirror = _upload(np.asarray(sk.out_mirror, np.int32), device)
+        out = torch.empty_like(poses)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        check(_lib.load().metro_to_orig_cam(C.c_void_p(poses.data_ptr()), C.c_void_p(rot.data_ptr()),
+                                            C.c_void_p(mirror.data_ptr()), C.c_void_p(out.data_ptr()), n, sk.n_out,
+                                            C.c_void_p(stream)), 'metro_to_orig_cam')
+    return out, edges, names

@@ -233,7 +233,16 @@ def main(argv=None):
                         help='.npy file with a [256,256,3] float image in [0,1]; default: seeded noise')
     parser.add_argument('--precision', type=str, default=None, choices=['f16', 'f32', 'f32m', 'f64'])
     parser.add_argument('--plot', type=str, default=None, help='write the stick-figure plot to this file')
+    parser.add_argument('--frame', type=str, default=None,
+                        help='.npy file with a uint8 [H,W,3] RGB frame: poses of the --box persons in it (frames.py)')
+    parser.add_argument('--box', type=str, action='append', default=[], help='x,y,w,h of a person box in --frame (repeatable)')
+    parser.add_argument('--intrinsics', type=str, default=None, help='fx,fy,cx,cy of the --frame camera')
+    parser.add_argument('--distortion', type=str, default=None, help='k1,k2,p1,p2,k3 of the --frame camera (needs --intrinsics)')
     opts = parser.parse_args(argv)
+    if opts.frame:
+        return _main_frame(opts)
+    if opts.box or opts.intrinsics or opts.distortion:
+        parser.error('--box, --intrinsics and --distortion go with --frame')
     if opts.image:
         img = np.load(opts.image).astype(np.float32)
     else:
@@ -246,6 +255,33 @@ def main(argv=None):
         print(f'{name.decode():>10s}  {p[0]:9.2f} {p[1]:9.2f} {p[2]:9.2f}')
     if opts.plot:
         visualize_pose(img, poses[0], edges).savefig(opts.plot)
+
+
+def _floats(text, n, flag):
+    v = [float(t) for t in text.split(',')]
+    if len(v) != n:
+        raise SystemExit(f'{flag} takes {n} comma-separated numbers, got {text!r}')
+    return v
+
+
+def _main_frame(opts):
+    from metro_pose3d_amd.frames import Camera, estimate_pose_in_frames
+    frame = np.load(opts.frame)
+    if not opts.box:
+        raise SystemExit('--frame needs at least one --box x,y,w,h')
+    boxes = np.array([_floats(b, 4, '--box') for b in opts.box])
+    camera = None
+    if opts.intrinsics:
+        fx, fy, cx, cy = _floats(opts.intrinsics, 4, '--intrinsics')
+        dist = _floats(opts.distortion, 5, '--distortion') if opts.distortion else None
+        camera = Camera(np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]]), dist)
+    elif opts.distortion:
+        raise SystemExit('--distortion needs --intrinsics')
+    poses, edges, names = estimate_pose_in_frames(frame, boxes, opts.model_path, cameras=camera, precision=opts.precision)
+    for k, pose in enumerate(poses.cpu().numpy()):
+        print(f'box {k} {opts.box[k]} (camera frame, root-relative mm)')
+        for name, p in zip(names, pose):
+            print(f'{name.decode():>10s}  {p[0]:9.2f} {p[1]:9.2f} {p[2]:9.2f}')
 
 
 if __name__ == '__main__':

@@ -45,6 +45,17 @@ class Skeleton:
         return tuple(idx[other(n)] for n in self.head_names)
 
     @property
+    def out_mirror(self) -> Tuple[int, ...]:
+        """head_mirror in OUTPUT order: row i's opposite-side joint as an output row (to_orig_cam on exported poses).
+        Raises when an output joint's mirror is not exported."""
+        position_of = {h: i for i, h in enumerate(self.permutation)}
+        mirror = self.head_mirror
+        missing = [self.names[i] for i, h in enumerate(self.permutation) if mirror[h] not in position_of]
+        if missing:
+            raise ValueError(f'the mirror joints of {missing} are not among the exported joints')
+        return tuple(position_of[mirror[h]] for h in self.permutation)
+
+    @property
     def n_head(self) -> int:
         return len(self.head_names)
 
