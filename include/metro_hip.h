@@ -217,12 +217,13 @@ typedef struct MetroConvDesc {
     int32_t has_residual;
     int32_t res_h, res_w;       /* spatial dims of the residual tensor [n,res_h,res_w,c_out] */
     int32_t res_stride, res_offset; /* residual pixel = (ho*res_stride+res_offset, wo*...)  */
-    int32_t out_dtype;          /* MetroDType of output AND residual: F16/F32 (fast kernel), F32/F64 (precise kernel) */
+    int32_t out_dtype;          /* MetroDType of output AND residual: F16/F32 (fast kernel; F32 without residual), F32/F64 (precise kernel) */
     int32_t in_dtype;           /* MetroDType of the input: F16 (fast kernel), F32/F64 (precise kernel) */
 } MetroConvDesc;
 
 /* fp16 operands, fp32 MFMA accumulate (v_mfma_f32_32x32x16_f16).  Weights [c_out][kh*kw*c_in]
- * fp16, bias fp32[c_out], prologue scale/shift fp16[c_in], residual fp16. c_in % 8 == 0. */
+ * fp16, bias fp32[c_out], prologue scale/shift fp16[c_in], residual fp16 (F16 output only: F32 output with a
+ * residual is rejected).  c_in % 8 == 0, c_in <= 2048, c_out % 4 == 0 (% 8 with a residual). */
 int  metro_conv_f16(const MetroConvDesc* d, const void* d_in, const void* d_w, const float* d_bias,
                     const void* d_pro_scale, const void* d_pro_shift, const void* d_residual,
                     void* d_out, void* stream);

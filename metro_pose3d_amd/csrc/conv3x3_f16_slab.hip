@@ -464,6 +464,59 @@ static int slab_subgrid_rate(const MetroConvDesc& d) {
     return r;
 }
 
+// The configuration launch_conv3x3_slab runs a layer on.  The predicate and the launcher share this one choice and its
+// capacity: a slab of SLAB_ROWS rows for a tile of TN pixels holds (SLAB_ROWS - TN) / 2 rows of halo on either side, and a
+// layer whose halo exceeds what its configuration holds is not a slab layer (it falls to the generic ring kernel).
+enum SlabPick { SP_64R320B1, SP_64R384B1, SP_64R320T3, SP_64R320, SP_64R384, SP_64R512, SP_128P512, SP_128R320, SP_128R384 };
+
+template <class Cfg>
+constexpr int slab_halo_cap() { return (Cfg::SLAB_ROWS - Cfg::TN) / 2; }
+
+static int slab_pick_halo_cap(SlabPick p) {
+    switch (p) {
+        case SP_64R320B1: return slab_halo_cap<Slab64r320b1>();
+        case SP_64R384B1: return slab_halo_cap<Slab64r384b1>();
+        case SP_64R320T3: return slab_halo_cap<Slab64r320t3>();
+        case SP_64R320: return slab_halo_cap<Slab64r320>();
+        case SP_64R384: return slab_halo_cap<Slab64r384>();
+        case SP_64R512: return slab_halo_cap<Slab64r512>();
+        case SP_128P512: return slab_halo_cap<Slab128p512>();
+        case SP_128R320: return slab_halo_cap<Slab128r320>();
+        case SP_128R384: return slab_halo_cap<Slab128r384>();
+    }
+    return 0;
+}
+
+// halo rows of a layer's slab: sub-grid order runs a rate-1 layer on (W / d)-wide sub-images
+static int slab_halo(const MetroConvDesc& d, int sgd) { return sgd ? d.w_out / sgd : d.dilation * d.w_out; }
+
+static SlabPick slab_pick(const MetroConvDesc& d, int halo, int sgd) {
+    const long m_total = (long)d.n * d.h_out * d.w_out;
+    // 64-cout tiles when 128-cout tiles would leave CUs without a block (256 CUs)
+    const long blocks128 = (long)((d.c_out + 127) / 128) * ((m_total + 255) / 256);
+    if (d.c_out <= 64 || blocks128 < 256) {
+        if (d.c_in == 64 && halo <= 32) return SP_64R320B1;
+        if (d.c_in == 64 && halo <= 64) return SP_64R384B1;
+        static const int t3 = tuning_knob("METRO_SLAB_T3", 1);
+        if (t3 && halo <= 32) return SP_64R320T3;
+        if (halo <= 32) return SP_64R320;
+        if (halo <= 64) return SP_64R384;
+        return SP_64R512;
+    }
+    // 512-pixel tiles (half the weight stream per pixel) once they still give every CU a tile (A/B: 256 beats 512 as the
+    // threshold at batch 128 and 256)
+    static const int min512 = tuning_knob("METRO_SLAB512_MIN_TILES", 256);
+    const long blocks512 = (long)((d.c_out + 127) / 128) * ((m_total + 511) / 512);
+    // (sub-grid layers -- strides 4 and 8 -- reach 256 such tiles at 16 / 32 crops, the per-GPU shards of BASELINE.json configs[4] /
+    // [3]; same-box A/B, profiles/r06_ab_subgrid_shards.txt: with 256-pixel tiles the sub-grid order is +1.0 % / +0.2 % SLOWER
+    // than the ring kernel it replaces, with 512-pixel tiles -1.3 % / -0.6 % faster.  METRO_SLAB_SG512_MIN_N raises the batch from
+    // which they may take them: the 32-channel chunks are another fp32 summation order)
+    static const int sg512_min_n = tuning_knob("METRO_SLAB_SG512_MIN_N", 1);
+    if (blocks512 >= min512 && (sgd == 0 || d.n >= sg512_min_n)) return SP_128P512;
+    if (halo <= 32) return SP_128R320;
+    return SP_128R384;
+}
+
 bool conv3x3_slab_supported(const MetroConvDesc& d) {
     static const int enabled = tuning_knob("METRO_CONV_SLAB", 1);
     if (!enabled) return false;
@@ -474,40 +527,34 @@ bool conv3x3_slab_supported(const MetroConvDesc& d) {
         return false;
     const long m = (long)d.n * d.h_out * d.w_out;
     if (m < 256) return false;
-    return slab_subgrid_rate(d) > 0 || slab_plain_ok(d);
+    const int sgd = slab_subgrid_rate(d);
+    if (!(sgd > 0 || slab_plain_ok(d))) return false;
+    const int halo = slab_halo(d, sgd);
+    return halo <= slab_pick_halo_cap(slab_pick(d, halo, sgd));
 }
 
 int launch_conv3x3_slab(const MetroConvDesc& d, const void* in_, const void* w_, const float* bias,
                         void* out_, hipStream_t stream) {
+    if (!conv3x3_slab_supported(d)) { set_error("conv3x3_f16_slab: unsupported layer"); return METRO_ERR_UNSUPPORTED; }
     const ConvArgs a = make_conv_args(d);
     const half_t* in = static_cast<const half_t*>(in_);
     const half_t* w = static_cast<const half_t*>(w_);
     half_t* out = static_cast<half_t*>(out_);
     const int sgd = slab_subgrid_rate(d);
-    const int halo = sgd ? d.w_out / sgd : d.dilation * d.w_out;       // sub-grid order: a rate-1 layer on (W / d)-wide sub-images
-    // 64-cout tiles when 128-cout tiles would leave CUs without a block (256 CUs)
-    const long blocks128 = (long)((d.c_out + 127) / 128) * ((a.m_total + 255) / 256);
-    if (d.c_out <= 64 || blocks128 < 256) {
-        if (d.c_in == 64 && halo <= 32) return launch_slab_cfg<Slab64r320b1>(a, in, w, bias, out, halo, stream, sgd);
-        if (d.c_in == 64 && halo <= 64) return launch_slab_cfg<Slab64r384b1>(a, in, w, bias, out, halo, stream, sgd);
-        static const int t3 = tuning_knob("METRO_SLAB_T3", 1);
-        if (t3 && halo <= 32) return launch_slab_cfg<Slab64r320t3>(a, in, w, bias, out, halo, stream, sgd);
-        if (halo <= 32) return launch_slab_cfg<Slab64r320>(a, in, w, bias, out, halo, stream, sgd);
-        if (halo <= 64) return launch_slab_cfg<Slab64r384>(a, in, w, bias, out, halo, stream, sgd);
-        return launch_slab_cfg<Slab64r512>(a, in, w, bias, out, halo, stream, sgd);
+    const int halo = slab_halo(d, sgd);
+    switch (slab_pick(d, halo, sgd)) {
+        case SP_64R320B1: return launch_slab_cfg<Slab64r320b1>(a, in, w, bias, out, halo, stream, sgd);
+        case SP_64R384B1: return launch_slab_cfg<Slab64r384b1>(a, in, w, bias, out, halo, stream, sgd);
+        case SP_64R320T3: return launch_slab_cfg<Slab64r320t3>(a, in, w, bias, out, halo, stream, sgd);
+        case SP_64R320: return launch_slab_cfg<Slab64r320>(a, in, w, bias, out, halo, stream, sgd);
+        case SP_64R384: return launch_slab_cfg<Slab64r384>(a, in, w, bias, out, halo, stream, sgd);
+        case SP_64R512: return launch_slab_cfg<Slab64r512>(a, in, w, bias, out, halo, stream, sgd);
+        case SP_128P512: return launch_slab_cfg<Slab128p512>(a, in, w, bias, out, halo, stream, sgd);
+        case SP_128R320: return launch_slab_cfg<Slab128r320>(a, in, w, bias, out, halo, stream, sgd);
+        case SP_128R384: return launch_slab_cfg<Slab128r384>(a, in, w, bias, out, halo, stream, sgd);
     }
-    // 512-pixel tiles (half the weight stream per pixel) once they still give every CU a tile (A/B: 256 beats 512 as the
-    // threshold at batch 128 and 256)
-    static const int min512 = tuning_knob("METRO_SLAB512_MIN_TILES", 256);
-    const long blocks512 = (long)((d.c_out + 127) / 128) * ((a.m_total + 511) / 512);
-    // (sub-grid layers -- strides 4 and 8 -- reach 256 such tiles at 16 / 32 crops, the per-GPU shards of BASELINE.json configs[4] /
-    // [3]; same-box A/B, profiles/r06_ab_subgrid_shards.txt: with 256-pixel tiles the sub-grid order is +1.0 % / +0.2 % SLOWER
-    // than the ring kernel it replaces, with 512-pixel tiles -1.3 % / -0.6 % faster.  METRO_SLAB_SG512_MIN_N raises the batch from
-    // which they may take them: the 32-channel chunks are another fp32 summation order)
-    static const int sg512_min_n = tuning_knob("METRO_SLAB_SG512_MIN_N", 1);
-    if (blocks512 >= min512 && (sgd == 0 || d.n >= sg512_min_n)) return launch_slab_cfg<Slab128p512>(a, in, w, bias, out, halo, stream, sgd);
-    if (halo <= 32) return launch_slab_cfg<Slab128r320>(a, in, w, bias, out, halo, stream, sgd);
-    return launch_slab_cfg<Slab128r384>(a, in, w, bias, out, halo, stream, sgd);
+    set_error("conv3x3_f16_slab: no configuration");
+    return METRO_ERR_UNSUPPORTED;
 }
 
 }  // namespace metro

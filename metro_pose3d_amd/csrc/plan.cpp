@@ -1009,9 +1009,11 @@ int metro_conv_f16(const MetroConvDesc* d, const void* d_in, const void* d_w, co
     int st = validate_conv_desc(d);
     if (st) return st;
     METRO_CHECK_ARG(d->c_in % 8 == 0 && d->in_pix_stride % 4 == 0, "conv_f16: c_in must be a multiple of 8 (got %d) and in_pix_stride of 4", d->c_in);
+    METRO_CHECK_ARG(d->c_in <= 2048, "conv_f16: c_in must be <= 2048 (got %d)", d->c_in);
     METRO_CHECK_ARG(d->c_out % 4 == 0, "conv_f16: c_out must be a multiple of 4 (got %d)", d->c_out);
     METRO_CHECK_ARG(d->out_dtype == METRO_F16 || d->out_dtype == METRO_F32, "conv_f16: out_dtype must be F16 or F32");
     METRO_CHECK_ARG(d->in_dtype == METRO_F16, "conv_f16: in_dtype must be F16");
+    METRO_CHECK_ARG(!(d->has_residual && d->out_dtype == METRO_F32), "conv_f16: a residual needs F16 output (F32 output has no residual epilogue)");
     METRO_CHECK_ARG(d_in && d_w && d_bias && d_out, "conv_f16: NULL tensor pointer");
     METRO_CHECK_ARG(!d->has_prologue || (d_pro_scale && d_pro_shift), "conv_f16: prologue tensors missing");
     METRO_CHECK_ARG(!d->has_residual || d_residual, "conv_f16: residual tensor missing");

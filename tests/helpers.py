@@ -16,7 +16,8 @@ def ptr(t):
 
 def conv_desc(n, h_in, c_in, h_out, c_out, k, stride=1, dil=1, pad=0, prologue=False, relu=False,
               residual=False, res_h=0, res_stride=1, res_offset=0, out_dtype=_lib.METRO_F16,
-              w_in=None, w_out=None, in_pix_stride=None, kh=None, kw=None, in_dtype=None):
+              w_in=None, w_out=None, in_pix_stride=None, kh=None, kw=None, in_dtype=None,
+              pad_top=None, pad_left=None, res_w=None):
     d = _lib.MetroConvDesc()
     d.n = n
     d.h_in = h_in
@@ -31,10 +32,15 @@ def conv_desc(n, h_in, c_in, h_out, c_out, k, stride=1, dil=1, pad=0, prologue=F
     d.stride = stride
     d.dilation = dil
     d.pad_top = d.pad_left = pad
+    if pad_top is not None:
+        d.pad_top = pad_top
+    if pad_left is not None:
+        d.pad_left = pad_left
     d.has_prologue = int(prologue)
     d.relu = int(relu)
     d.has_residual = int(residual)
-    d.res_h = d.res_w = res_h
+    d.res_h = res_h
+    d.res_w = res_w if res_w is not None else res_h
     d.res_stride = res_stride
     d.res_offset = res_offset
     d.out_dtype = out_dtype
@@ -73,6 +79,57 @@ def ref_conv_nhwc(x, w_ok, bias, stride, dil, pad, h_out, pro=None, relu=False, 
         r = torch.as_tensor(res, dtype=torch.float64)
         y = y + r[:, res_offset::res_stride, res_offset::res_stride][:, :h_out, :h_out]
     return y
+
+
+def ref_conv_desc(d, x, w_ok, bias, pro=None, pro_round=np.float16, res=None):
+    """fp64 tap-sum restatement of one MetroConvDesc `d`, for any geometry the descriptor can state.
+
+    x: [n, h_in, w_in, P] with P >= d.c_in -- the input pixels as the kernel sees them (P = d.in_pix_stride for a strided
+    buffer); channels [0, c_in) are read.  w_ok [c_out, kh, kw, c_in] (the packed layout), bias [c_out].
+    Tap (r, s) of output (ho, wo) reads input row ho*stride - pad_top + r*dilation, column wo*stride - pad_left + s*dilation;
+    a tap outside the input reads zero.  pro = (scale, shift): the input becomes relu(x*scale + shift), rounded ONCE to
+    `pro_round` (fp16 for the fp16 kernels; None = kept in fp64).  Then bias, ReLU (if d.relu) and the residual
+    res [n, res_h, res_w, c_out] at pixel (ho*res_stride + res_offset, wo*res_stride + res_offset).
+
+    Returns (y, a): y the exact result, a = sum|w*x| + |bias| (+ |res|), the absolute condition sum of every output element
+    (what bounds the error of any summation order of the same terms)."""
+    c_in = d.c_in
+    x = np.asarray(x, dtype=np.float64)[..., :c_in]
+    assert x.shape == (d.n, d.h_in, d.w_in, c_in), (x.shape, (d.n, d.h_in, d.w_in, c_in))
+    w = np.asarray(w_ok, dtype=np.float64)
+    assert w.shape == (d.c_out, d.kh, d.kw, c_in), w.shape
+    if pro is not None:
+        x = x * np.asarray(pro[0], np.float64) + np.asarray(pro[1], np.float64)
+        if pro_round is not None:
+            x = x.astype(pro_round).astype(np.float64)
+        x = np.maximum(x, 0.0)
+    ho = np.arange(d.h_out) * d.stride - d.pad_top
+    wo = np.arange(d.w_out) * d.stride - d.pad_left
+    y = np.zeros((d.n, d.h_out, d.w_out, d.c_out))
+    a = np.zeros_like(y)
+    for r in range(d.kh):
+        rows = ho + r * d.dilation
+        rok = (rows >= 0) & (rows < d.h_in)
+        for s in range(d.kw):
+            cols = wo + s * d.dilation
+            cok = (cols >= 0) & (cols < d.w_in)
+            xt = x[:, np.clip(rows, 0, d.h_in - 1)][:, :, np.clip(cols, 0, d.w_in - 1)]
+            xt = xt * (rok[:, None] & cok[None, :])[None, :, :, None]
+            wt = w[:, r, s, :].T
+            y += xt @ wt
+            a += np.abs(xt) @ np.abs(wt)
+    b = np.asarray(bias, np.float64)
+    y += b
+    a += np.abs(b)
+    if d.relu:
+        y = np.maximum(y, 0.0)
+    if d.has_residual:
+        rr = np.arange(d.h_out) * d.res_stride + d.res_offset
+        rc = np.arange(d.w_out) * d.res_stride + d.res_offset
+        rg = np.asarray(res, np.float64)[:, rr][:, :, rc]
+        y += rg
+        a += np.abs(rg)
+    return y, a
 
 
 def run_conv_f16(lib, dev, d, x, w, bias, pro=None, res=None):
