@@ -381,16 +381,13 @@ static int launch_b1(B1Args a, hipStream_t stream) {
     return launch_status("conv_b1_chain");
 }
 
-// d: the conv3 layer (1x1, 64 -> 256, no prologue, no residual tensor); psc, f2 as for conv_pw64's mode 3; rb: rebuild / output mode
+// d: the conv3 layer (1x1, 64 -> 256, no prologue, no residual tensor) of a NextProj / NextRebuild launch that conv_pw64 hands over
+// (whole 64-pixel tiles, map width a power of two >= 16); f.rb.out_mode 1 (NextProj) / 2 (NextRebuild) or 0
 int launch_conv_b1_chain(const MetroConvDesc& d, const void* in, const void* w, const float* bias, void* out, hipStream_t stream,
-                         const ConvFuse2& f2, const ConvProjSc& psc, const ConvRebuild& rb) {
-    const int hw = d.h_out * d.w_out;
-    if (!(d.kh == 1 && d.kw == 1 && d.stride == 1 && d.c_in == 64 && d.c_out == 256 && d.in_pix_stride == 64 && !d.has_prologue &&
-          !d.has_residual && !d.relu && d.in_dtype == METRO_F16 && d.out_dtype == METRO_F16 && f2.c2 == 64 && hw % 64 == 0 &&
-          d.w_out >= 16 && (d.w_out & (d.w_out - 1)) == 0)) {
-        set_error("conv_b1_chain: built for the conv3 + next conv1 launches of block1 (1x1, 64 -> 256 -> 64, whole 64-pixel tiles, map width a power of two >= 16)");
-        return METRO_ERR_UNSUPPORTED;
-    }
+                         const ConvFused& f) {
+    const ConvFuse2& f2 = f.next;
+    const ConvProjSc& psc = f.psc;
+    const ConvRebuild& rb = f.rb;
     B1Args a;
     a.in = static_cast<const half_t*>(in); a.w = static_cast<const half_t*>(w); a.bias = bias;
     a.x_sc = static_cast<const half_t*>(psc.x); a.w_sc = static_cast<const half_t*>(psc.w_sc); a.bias_sc = psc.bias_sc;
@@ -399,21 +396,12 @@ int launch_conv_b1_chain(const MetroConvDesc& d, const void* in, const void* w, 
     a.w2 = static_cast<const half_t*>(f2.w2); a.bias2 = f2.bias2;
     a.scale2 = static_cast<const half_t*>(f2.scale2); a.shift2 = static_cast<const half_t*>(f2.shift2);
     a.out = static_cast<half_t*>(out); a.out_sub = static_cast<half_t*>(rb.out_sub); a.out2 = static_cast<half_t*>(f2.out2);
-    a.m_total = d.n * hw; a.n_tiles = 0;
+    a.m_total = d.n * d.h_out * d.w_out; a.n_tiles = 0;
     a.h_out = d.h_out; a.w_out = d.w_out; a.lw_out = 0;
     while ((1 << a.lw_out) < d.w_out) ++a.lw_out;
     a.sub_off = rb.sub_off; a.h_sub = rb.h_sub; a.w_sub = rb.w_sub;
-    const bool reb = rb.t2_prev != nullptr;
-    if (reb) {
-        if (rb.out_mode == 2) return launch_b1<true, 2>(a, stream);
-        if (rb.out_mode == 0) return launch_b1<true, 0>(a, stream);
-        set_error("conv_b1_chain: a rebuilt residual whose sum is neither stored nor sub-sampled has no consumer");
-        return METRO_ERR_INVALID_ARG;
-    }
-    if (rb.out_mode == 1) return launch_b1<false, 1>(a, stream);
-    if (rb.out_mode == 0) return launch_b1<false, 0>(a, stream);
-    set_error("conv_b1_chain: the sub-sampled copy exists with the rebuilt residual only");
-    return METRO_ERR_INVALID_ARG;
+    if (f.form == ConvForm::NextRebuild) return rb.out_mode == 2 ? launch_b1<true, 2>(a, stream) : launch_b1<true, 0>(a, stream);
+    return rb.out_mode == 1 ? launch_b1<false, 1>(a, stream) : launch_b1<false, 0>(a, stream);
 }
 
 }  // namespace metro

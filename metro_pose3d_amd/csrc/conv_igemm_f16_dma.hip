@@ -646,18 +646,12 @@ __global__ __launch_bounds__(Cfg::NT) void conv_igemm_f16_fuse2_kernel(
     conv_dma_body<Cfg, false, true, true>(a, in, w, bias, nullptr, nullptr, residual, out, 0, 1, nullptr, f2);
 }
 
-static int env_int(const char* name, int dflt) { return tuning_knob(name, dflt); }
-
-static thread_local void* g_out2 = nullptr;   // second output of a fused pair (set by launch_conv_f16_dma)
-
+// out2: the second output of a fused pair (a.split > 0), else NULL
 template <class Cfg, bool PROLOGUE, bool FASTK>
 static int launch_dma_cfg2(const ConvArgs& a, const half_t* in, const half_t* w, const float* bias,
-                           const half_t* ps, const half_t* pb, const half_t* res, void* out, int out_f32,
+                           const half_t* ps, const half_t* pb, const half_t* res, void* out, int out_f32, void* out2,
                            hipStream_t stream) {
-    if (a.split > 0 && (a.split % Cfg::TM) != 0) {
-        set_error("conv_igemm_f16_dma: split %d is not a multiple of the %d-wide cout tile", a.split, Cfg::TM);
-        return METRO_ERR_INVALID_ARG;
-    }
+    static_assert(256 % Cfg::TM == 0, "a pair splits on a 256-row boundary (conv_form_supported): whole cout tiles");
     if (note_kernel("conv_igemm_f16_dma<%dx%d,bk%d,s%d%s%s>%s%s%s", Cfg::TM, Cfg::TN, Cfg::BK, Cfg::STAGES, PROLOGUE ? ",pro" : "",
                     FASTK ? "" : ",ktail", res ? "+res" : "", a.split > 0 ? "+pair" : "", out_f32 ? "+f32out" : ""))
         return METRO_OK;
@@ -668,18 +662,18 @@ static int launch_dma_cfg2(const ConvArgs& a, const half_t* in, const half_t* w,
     const int tiles_m = (a.c_out + Cfg::TM - 1) / Cfg::TM;
     const int tiles_n = (a.m_total + Cfg::TN - 1) / Cfg::TN;
     hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(Cfg::NT), lds, stream, a, in, w, bias, ps, pb,
-                       res, out, out_f32, tiles_m, g_out2);
+                       res, out, out_f32, tiles_m, out2);
     return launch_status("conv_igemm_f16_dma");
 }
 
 template <class Cfg, bool PROLOGUE>
 static int launch_dma_cfg(const ConvArgs& a, const half_t* in, const half_t* w, const float* bias,
-                          const half_t* ps, const half_t* pb, const half_t* res, void* out, int out_f32,
+                          const half_t* ps, const half_t* pb, const half_t* res, void* out, int out_f32, void* out2,
                           hipStream_t stream) {
     // FASTK needs whole K steps per tap and 16-byte-aligned weight rows for the running pointers
     if (a.c_in % Cfg::BK == 0)
-        return launch_dma_cfg2<Cfg, PROLOGUE, true>(a, in, w, bias, ps, pb, res, out, out_f32, stream);
-    return launch_dma_cfg2<Cfg, PROLOGUE, false>(a, in, w, bias, ps, pb, res, out, out_f32, stream);
+        return launch_dma_cfg2<Cfg, PROLOGUE, true>(a, in, w, bias, ps, pb, res, out, out_f32, out2, stream);
+    return launch_dma_cfg2<Cfg, PROLOGUE, false>(a, in, w, bias, ps, pb, res, out, out_f32, out2, stream);
 }
 
 //                        WAVES_M WAVES_N WM WN STAGES BK   tile (cout x pixels), waves, LDS
@@ -696,7 +690,7 @@ using Dma64x128s3k32 = DmaCfg<1, 4, 2, 1, 3, 32>;  //  64 x 128, 4 waves, BK 32 
 using DmaFuse256x64 = DmaCfg<4, 2, 2, 1, 1>;       // 256 cout x 64 px, 8 waves (wave 64 x 32), one K step: conv3 + next conv1
 
 bool conv_f16_fuse2_supported(const MetroConvDesc& d, int c2) {
-    static const int enabled = env_int("METRO_FUSE2", 1);
+    static const int enabled = tuning_knob("METRO_FUSE2", 1);
     return enabled && d.c_out == DmaFuse256x64::TM && c2 == 64 && d.kh == 1 && d.kw == 1 && d.c_in == 64 &&
            d.in_pix_stride == 64 && d.stride == 1 && d.pad_top == 0 && d.pad_left == 0 && !d.has_prologue &&
            d.out_dtype == METRO_F16 && d.in_dtype == METRO_F16 && d.h_in == d.h_out && d.w_in == d.w_out;
@@ -723,48 +717,56 @@ bool conv_f16_dma_supported(const MetroConvDesc& d) {
            (!d.has_residual || d.c_out % 8 == 0) && (d.in_pix_stride % 8 == 0 || !d.has_prologue);
 }
 
+bool conv_form_supported(const MetroConvDesc& d, const ConvFused& f) {
+    const ConvSplit& s = f.pair;
+    const ConvRebuild& rb = f.rb;
+    switch (f.form) {
+        case ConvForm::Plain:
+            return true;          // plain layers: launch_conv_f16's kernel predicates
+        case ConvForm::Pair:      // the ring kernel's pair, which holds every pair conv_pw64 and conv_gemm4w run
+            return d.kh == 1 && d.kw == 1 && d.stride == 1 && d.has_prologue && !d.has_residual && !d.relu && d.in_dtype == METRO_F16 &&
+                   d.out_dtype == METRO_F16 && d.c_in % 64 == 0 && s.split > 0 && s.c_out2 > 0 && s.split + s.c_out2 == d.c_out &&
+                   s.split % 256 == 0 && s.c_out2 % 8 == 0;
+        case ConvForm::Next:
+            return conv_f16_fuse2_supported(d, f.next.c2) || conv_pw64_supported(d, f);
+        case ConvForm::NextProj:  // out_mode 1: the sum only feeds the next conv1 in the launch
+            return conv_pw64_supported(d, f) && (rb.out_mode == 0 || rb.out_mode == 1);
+        case ConvForm::NextRebuild:   // out_mode 2: only the sub-sampled compact copy of the sum is stored
+            return conv_pw64_supported(d, f) &&
+                   (rb.out_mode == 0 || (rb.out_mode == 2 && rb.out_sub != nullptr && (rb.sub_off == 0 || rb.sub_off == 1) && rb.h_sub > 0 &&
+                                         rb.w_sub > 0));
+    }
+    return false;
+}
+
+// `f` has passed conv_form_supported (the planner, the C entries)
 int launch_conv_f16_dma(const MetroConvDesc& d, const void* in_, const void* w_, const float* bias,
-                        const void* ps_, const void* pb_, const void* res_, void* out, hipStream_t stream,
-                        const ConvSplit* split, const ConvFuse2* fuse2, const ConvProjSc* psc, const ConvRebuild* rebuild) {
+                        const void* ps_, const void* pb_, const void* res_, void* out, hipStream_t stream, const ConvFused& f) {
     ConvArgs a = make_conv_args(d);
-    g_out2 = nullptr;
-    if (psc != nullptr && psc->x != nullptr) {        // projection shortcut computed in the launch: the persistent kernel only
-        const bool rb = rebuild != nullptr && rebuild->t2_prev != nullptr;
-        if (fuse2 != nullptr && fuse2->w2 != nullptr && fuse2->c2 == 64 && conv_pw64_supported(d, rb ? 4 : 3))
-            return launch_conv_pw64(d, in_, w_, bias, nullptr, nullptr, nullptr, out, stream, nullptr, fuse2, psc, rebuild);
-        set_error("conv3 with an in-launch projection shortcut: built for 1x1 stride-1 64 -> 256 + next conv1 (block1/unit_1) only");
-        return METRO_ERR_UNSUPPORTED;
-    }
-    if (!(fuse2 != nullptr && fuse2->w2 != nullptr) && !(split != nullptr && split->split > 0) && conv_pws_supported(d))
-        return launch_conv_pws(d, in_, w_, bias, res_, out, stream);
-    {
-        const int mode = (fuse2 != nullptr && fuse2->w2 != nullptr) ? 2 : (split != nullptr && split->split > 0) ? 1 : 0;
-        if (conv_pw64_supported(d, mode) && (mode != 1 || (split->relu2 == 1 && ((split->split == 256 && split->c_out2 == 64) || (split->split == 512 && split->c_out2 == 128)))) &&
-            (mode != 2 || fuse2->c2 == (d.c_in == 128 ? 128 : 64)))
-            return launch_conv_pw64(d, in_, w_, bias, ps_, pb_, res_, out, stream, split, fuse2);
-    }
-    // deep-K pre-activated 1x1 layers with at least one 256 x 256 tile per CU: the four-wave GEMM (128 x 128 wave tiles,
-    // register-staged operands, the pre-activation applied once per element on its way into LDS).  Two other forms of this GEMM
-    // (8-phase two-wave-group LDS-DMA, round 2; four waves with both operands by LDS-DMA, round 4) give the same bits and
-    // measured the same inside the forward: they live in csrc/experimental/ (libmetro_experimental.so), not in the product.
-    if (!(fuse2 != nullptr && fuse2->w2 != nullptr) && conv_gemm4w_supported(d, split))
-        return launch_conv_gemm4w(d, in_, w_, bias, ps_, pb_, res_, out, stream, split);
-    if (fuse2 != nullptr && fuse2->w2 != nullptr) {
-        if (!conv_f16_fuse2_supported(d, fuse2->c2)) { set_error("conv fuse2: unsupported layer shape (c_out %d c2 %d k %dx%d c_in %d pix_stride %d stride %d pad %d,%d pro %d dt %d/%d hw %dx%d -> %dx%d)",
-                                                                 d.c_out, fuse2->c2, d.kh, d.kw, d.c_in, d.in_pix_stride, d.stride, d.pad_top, d.pad_left, d.has_prologue,
-                                                                 d.in_dtype, d.out_dtype, d.h_in, d.w_in, d.h_out, d.w_out); return METRO_ERR_INVALID_ARG; }
-        return launch_fuse2(a, static_cast<const half_t*>(in_), static_cast<const half_t*>(w_), bias,
-                            d.has_residual ? static_cast<const half_t*>(res_) : nullptr, out, *fuse2, stream);
-    }
-    if (split != nullptr && split->split > 0) {
-        if (d.has_residual || d.out_dtype != METRO_F16 || split->split + split->c_out2 != d.c_out ||
-            split->split % 256 != 0 || split->c_out2 % 8 != 0) {
-            set_error("conv_igemm_f16_dma: unsupported fused pair (split %d + %d vs c_out %d)", split->split,
-                      split->c_out2, d.c_out);
-            return METRO_ERR_INVALID_ARG;
-        }
-        a.split = split->split; a.c_out2 = split->c_out2; a.relu2 = split->relu2;
-        g_out2 = split->out2;
+    void* out2 = nullptr;
+    switch (f.form) {
+        case ConvForm::NextProj:
+        case ConvForm::NextRebuild:       // the persistent kernel only
+            return launch_conv_pw64(d, in_, w_, bias, nullptr, nullptr, nullptr, out, stream, f);
+        case ConvForm::Next:
+            if (conv_pw64_supported(d, f)) return launch_conv_pw64(d, in_, w_, bias, ps_, pb_, res_, out, stream, f);
+            return launch_fuse2(a, static_cast<const half_t*>(in_), static_cast<const half_t*>(w_), bias,
+                                d.has_residual ? static_cast<const half_t*>(res_) : nullptr, out, f.next, stream);
+        case ConvForm::Pair:
+            if (conv_pw64_supported(d, f)) return launch_conv_pw64(d, in_, w_, bias, ps_, pb_, res_, out, stream, f);
+            if (conv_gemm4w_supported(d, &f.pair)) return launch_conv_gemm4w(d, in_, w_, bias, ps_, pb_, res_, out, stream, &f.pair);
+            a.split = f.pair.split; a.c_out2 = f.pair.c_out2; a.relu2 = f.pair.relu2;
+            out2 = f.pair.out2;
+            break;
+        case ConvForm::Plain:
+            if (conv_pws_supported(d)) return launch_conv_pws(d, in_, w_, bias, res_, out, stream);
+            if (conv_pw64_supported(d, f)) return launch_conv_pw64(d, in_, w_, bias, ps_, pb_, res_, out, stream, f);
+            // deep-K pre-activated 1x1 layers with at least one 256 x 256 tile per CU: the four-wave GEMM (128 x 128 wave tiles,
+            // register-staged operands, the pre-activation applied once per element on its way into LDS).  Two other forms of this
+            // GEMM (8-phase two-wave-group LDS-DMA, round 2; four waves with both operands by LDS-DMA, round 4) give the same bits and
+            // measured the same inside the forward: they live in csrc/experimental/ (libmetro_experimental.so), not in the product.
+            if (conv_gemm4w_supported(d, nullptr)) return launch_conv_gemm4w(d, in_, w_, bias, ps_, pb_, res_, out, stream, nullptr);
+            break;
     }
     const half_t* in = static_cast<const half_t*>(in_);
     const half_t* w = static_cast<const half_t*>(w_);
@@ -775,17 +777,17 @@ int launch_conv_f16_dma(const MetroConvDesc& d, const void* in_, const void* w_,
     const bool pro = d.has_prologue != 0;
     const int tiles128 = (d.c_out + 127) / 128;
     // tuning knobs (A/B runs): K-steps up to which the 1-stage / 2-stage 128x128 configs are used
-    static const int nk_s1 = env_int("METRO_NK_S1", 2);
-    static const int nk_s2 = env_int("METRO_NK_S2", 8);
-#define METRO_DMA(CFG)                                                                         \
-    return pro ? launch_dma_cfg<CFG, true>(a, in, w, bias, ps, pb, res, out, out_f32, stream)  \
-               : launch_dma_cfg<CFG, false>(a, in, w, bias, ps, pb, res, out, out_f32, stream)
+    static const int nk_s1 = tuning_knob("METRO_NK_S1", 2);
+    static const int nk_s2 = tuning_knob("METRO_NK_S2", 8);
+#define METRO_DMA(CFG)                                                                               \
+    return pro ? launch_dma_cfg<CFG, true>(a, in, w, bias, ps, pb, res, out, out_f32, out2, stream)  \
+               : launch_dma_cfg<CFG, false>(a, in, w, bias, ps, pb, res, out, out_f32, out2, stream)
     if (d.c_in <= 32 && !pro) {
-        return launch_dma_cfg<Dma64x128s3k32, false>(a, in, w, bias, ps, pb, res, out, out_f32, stream);
+        return launch_dma_cfg<Dma64x128s3k32, false>(a, in, w, bias, ps, pb, res, out, out_f32, out2, stream);
     }
     const int nk = d.kh * d.kw * ((d.c_in + 63) / 64);
     // 64-cout tiles: narrow layers, and heads whose width wastes most of a second 128-tile (136 = 8*17)
-    static const int head64 = env_int("METRO_DMA_HEAD64", 1);
+    static const int head64 = tuning_knob("METRO_DMA_HEAD64", 1);
     const bool narrow = d.c_out <= 64 || (head64 && d.c_out < 256 && d.c_out % 128 != 0 && (d.c_out % 128) <= 64 &&
                                           d.c_out / 128 <= 1);
     if (narrow) {
@@ -793,7 +795,7 @@ int launch_conv_f16_dma(const MetroConvDesc& d, const void* in_, const void* w_,
         METRO_DMA(Dma64x128s3);
     }
     if (nk <= nk_s1) { METRO_DMA(Dma128x128s1); }
-    static const int k32 = env_int("METRO_DMA_K32", 8);
+    static const int k32 = tuning_knob("METRO_DMA_K32", 8);
     {
         const long b256 = (long)tiles128 * ((a.m_total + 255) / 256);
         if (k32 && nk <= k32 && b256 >= 512) { METRO_DMA(Dma128x256s3k32); }
@@ -801,12 +803,12 @@ int launch_conv_f16_dma(const MetroConvDesc& d, const void* in_, const void* w_,
     if (nk <= nk_s2) { METRO_DMA(Dma128x128s2); }
     // 256-pixel tiles only when they still give every CU a block
     const long blocks256 = (long)tiles128 * ((a.m_total + 255) / 256);
-    static const int big = env_int("METRO_DMA_BIG", 2);
+    static const int big = tuning_knob("METRO_DMA_BIG", 2);
     if (big && d.c_out % 256 == 0 && blocks256 / 2 >= 256) { METRO_DMA(Dma256x256s4k32); }
     if (blocks256 >= 256) { METRO_DMA(Dma128x256s3); }
     // deep-K layers whose 128 x 128 tiles leave CUs idle (block2/unit_4's strided 3x3 at batch 64: 128 tiles on 256 CUs): 64-cout
     // tiles double the blocks (same pixel gather per block, half the weight rows and MFMAs per K step); same bits
-    static const int half_tiles = env_int("METRO_DMA_HALF_TILES", 1);
+    static const int half_tiles = tuning_knob("METRO_DMA_HALF_TILES", 1);
     const long blocks128 = (long)tiles128 * ((a.m_total + 127) / 128);
     if (half_tiles && d.c_out % 64 == 0 && blocks128 >= 64 && blocks128 < 224 && a.split == 0) { METRO_DMA(Dma64x128s3); }
     METRO_DMA(Dma128x128s4);

@@ -660,15 +660,18 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
     }
 }
 
-static int pw_env_int(const char* name, int dflt) { return tuning_knob(name, dflt); }
-
 static bool pw_enabled() {
-    static const int v = pw_env_int("METRO_PW64", 1);
+    static const int v = tuning_knob("METRO_PW64", 1);
     return v != 0;
 }
 
-// mode: 0 plain, 1 shortcut + conv1 pair (desc.c_out = 320 = 256 + 64 concatenated rows), 2 conv3 + next conv1
-bool conv_pw64_supported(const MetroConvDesc& d, int mode) {
+// the maps the rebuilt residual and conv_b1.hip's producer / consumer form are built for: whole 64-pixel tiles, width a power of
+// two >= 16 (the sub-sampled copy's pixel arithmetic)
+static bool b1_map_ok(const MetroConvDesc& d) {
+    return (d.h_out * d.w_out) % 64 == 0 && d.w_out >= 16 && (d.w_out & (d.w_out - 1)) == 0;
+}
+
+bool conv_pw64_supported(const MetroConvDesc& d, const ConvFused& f) {
     if (!pw_enabled()) return false;
     if (!(d.kh == 1 && d.kw == 1 && d.stride == 1 && d.pad_top == 0 && d.pad_left == 0 && d.in_pix_stride == d.c_in &&
           d.h_in == d.h_out && d.w_in == d.w_out && d.relu == 0 && d.out_dtype == METRO_F16 && d.in_dtype == METRO_F16))
@@ -677,28 +680,31 @@ bool conv_pw64_supported(const MetroConvDesc& d, int mode) {
     // sub-sampled shortcut of the stride-2 units: every addressed shortcut pixel must exist
     const bool res_sub = d.res_stride == 2 && d.res_offset >= 0 && d.res_offset + 2 * (d.h_out - 1) < d.res_h &&
                          d.res_offset + 2 * (d.w_out - 1) < d.res_w;
-    if (d.has_residual && !res_plain && !(mode == 0 && res_sub && d.c_in <= 128)) return false;
+    if (d.has_residual && !res_plain && !(f.form == ConvForm::Plain && res_sub && d.c_in <= 128)) return false;
     // built combinations: prologue without shortcut (projection shortcut, pair) / shortcut without prologue (conv3)
-    if (mode == 1) {
-        // block1's pair (64 -> 256 + 64) and, round 5, block2's (256 -> 512 + 128: all 640 weight rows register-resident in one block)
-        static const int pair256 = pw_env_int("METRO_PW_PAIR256", 1);
-        // (under the test switch metro_conv_b1_form(1) the 256-channel pair stays on the ring kernel it replaced: same bits, tested)
-        return ((d.c_in == 64 && d.c_out == 320) || (pair256 && !classic_forms_forced() && d.c_in == 256 && d.c_out == 640)) &&
-               d.has_prologue && !d.has_residual;
-    }
-    if (mode == 2) {
-        static const int next128 = pw_env_int("METRO_PW_NEXT128", 1);
-        return ((d.c_in == 64 && d.c_out == 256) || (next128 && d.c_in == 128 && d.c_out == 512 && res_plain)) && !d.has_prologue && d.has_residual;
-    }
-    if (mode == 3) return d.c_in == 64 && d.c_out == 256 && !d.has_prologue && !d.has_residual;    // + in-launch projection shortcut
-    if (mode == 4) {           // + the residual rebuilt from the previous unit's conv2 output (and optionally kept on chip)
-        const int hw = d.h_out * d.w_out;
-        return d.c_in == 64 && d.c_out == 256 && !d.has_prologue && !d.has_residual && hw % 64 == 0 && d.w_out >= 16 &&
-               (d.w_out & (d.w_out - 1)) == 0;
+    switch (f.form) {
+        case ConvForm::Pair: {
+            // block1's pair (64 -> 256 + 64) and, round 5, block2's (256 -> 512 + 128: all 640 weight rows register-resident in one block)
+            static const int pair256 = tuning_knob("METRO_PW_PAIR256", 1);
+            // (under the test switch metro_conv_b1_form(1) the 256-channel pair stays on the ring kernel it replaced: same bits, tested)
+            return ((d.c_in == 64 && d.c_out == 320) || (pair256 && !classic_forms_forced() && d.c_in == 256 && d.c_out == 640)) &&
+                   d.has_prologue && !d.has_residual && f.pair.relu2 == 1 && 5 * f.pair.c_out2 == d.c_out && f.pair.split == 4 * f.pair.c_out2;
+        }
+        case ConvForm::Next: {         // c2 = the next unit's conv1 width: 64 (block1), 128 (block2)
+            static const int next128 = tuning_knob("METRO_PW_NEXT128", 1);
+            return ((d.c_in == 64 && d.c_out == 256 && f.next.c2 == 64) ||
+                    (next128 && d.c_in == 128 && d.c_out == 512 && res_plain && f.next.c2 == 128)) && !d.has_prologue && d.has_residual;
+        }
+        case ConvForm::NextProj:       // the projection shortcut computed in the launch
+        case ConvForm::NextRebuild:    // ... and the residual rebuilt from the previous unit's conv2 output (and optionally kept on chip)
+            return d.c_in == 64 && d.c_out == 256 && !d.has_prologue && !d.has_residual && f.next.c2 == 64 &&
+                   (f.form == ConvForm::NextProj || b1_map_ok(d));
+        case ConvForm::Plain:
+            break;
     }
     if (d.c_in == 64 && d.c_out == 256) return (d.has_prologue != 0) != (d.has_residual != 0);
     // conv3 (+ shortcut) of blocks 2-4: c_out = 4 * c_in in 256-channel slabs (METRO_PW_MAXK caps c_in for A/B runs)
-    static const int maxk = pw_env_int("METRO_PW_MAXK", 512);
+    static const int maxk = tuning_knob("METRO_PW_MAXK", 512);
     return (d.c_in == 128 || d.c_in == 256 || d.c_in == 512) && d.c_in <= maxk && d.c_out == 4 * d.c_in &&
            !d.has_prologue && d.has_residual;
 }
@@ -715,7 +721,7 @@ static int launch_pw(Pw64Args a, hipStream_t stream) {
     static PerDeviceInt cap;
     int grid_cap = 0;
     if (const int st = ensure_dyn_lds_and_grid_cap(reinterpret_cast<const void*>(kern), pw::NT, lds, cap, "conv_pw64",
-                                                   pw_env_int("METRO_PW64_BPC", 0) /* blocks per CU, 0 = what fits */, &grid_cap))
+                                                   tuning_knob("METRO_PW64_BPC", 0) /* blocks per CU, 0 = what fits */, &grid_cap))
         return st;
     const int halves = a.c_out / CB;
     int grid = a.n_tiles * halves < grid_cap ? a.n_tiles * halves : grid_cap;
@@ -724,29 +730,14 @@ static int launch_pw(Pw64Args a, hipStream_t stream) {
     return launch_status("conv_pw64");
 }
 
+// `f` has passed conv_form_supported and conv_pw64_supported
 int launch_conv_pw64(const MetroConvDesc& d, const void* in, const void* w, const float* bias, const void* ps,
-                     const void* pb, const void* res, void* out, hipStream_t stream, const ConvSplit* split,
-                     const ConvFuse2* f2, const ConvProjSc* psc, const ConvRebuild* rb) {
-    const bool proj = psc != nullptr && psc->x != nullptr;
-    const bool reb = rb != nullptr && rb->t2_prev != nullptr;
-    const int outm = rb != nullptr ? rb->out_mode : 0;
-    const int mode = (f2 != nullptr && f2->w2 != nullptr) ? (proj ? (reb ? 4 : 3) : 2) : (split != nullptr && split->split > 0) ? 1 : 0;
-    if (proj && mode < 3) { set_error("conv_pw64: the in-launch projection shortcut exists for conv3 + next conv1 only"); return METRO_ERR_INVALID_ARG; }
-    if ((reb || outm != 0) && mode < 3) { set_error("conv_pw64: rebuilt residual / on-chip output exist on top of the in-launch projection shortcut only"); return METRO_ERR_INVALID_ARG; }
-    if (outm < 0 || outm > 2 || (outm == 2 && !(reb && rb->out_sub != nullptr && rb->sub_off >= 0 && rb->sub_off <= 1 && rb->h_sub > 0 && rb->w_sub > 0)) ||
-        (outm == 0 && out == nullptr)) {
-        set_error("conv_pw64: bad output mode %d (2 = sub-sampled copy: needs the rebuilt residual, out_sub, sub_off 0|1 and the sub-sampled map size)", outm);
-        return METRO_ERR_INVALID_ARG;
-    }
-    if (!conv_pw64_supported(d, mode) || (mode == 1 && !(split->relu2 == 1 && ((d.c_in == 64 && split->split == 256 && split->c_out2 == 64) ||
-                                                                      (d.c_in == 256 && split->split == 512 && split->c_out2 == 128)))) ||
-        (mode >= 2 && f2->c2 != (d.c_in == 128 ? 128 : 64))) {
-        set_error("conv_pw64: unsupported layer");
-        return METRO_ERR_INVALID_ARG;
-    }
+                     const void* pb, const void* res, void* out, hipStream_t stream, const ConvFused& f) {
+    const ConvRebuild& rb = f.rb;
     // the launches whose sum stays on chip (or is rebuilt): the producer / consumer form, unless the classic one is asked for
-    if (mode >= 3 && rb != nullptr && !rb->classic && (reb || outm == 1) && conv_b1_chain_preferred() && conv_pw64_supported(d, 4))
-        return launch_conv_b1_chain(d, in, w, bias, out, stream, *f2, *psc, *rb);
+    if ((f.form == ConvForm::NextRebuild || (f.form == ConvForm::NextProj && rb.out_mode == 1)) && !rb.classic &&
+        conv_b1_chain_preferred() && b1_map_ok(d))
+        return launch_conv_b1_chain(d, in, w, bias, out, stream, f);
     Pw64Args a;
     a.in = static_cast<const half_t*>(in);
     a.w = static_cast<const half_t*>(w);
@@ -760,34 +751,32 @@ int launch_conv_pw64(const MetroConvDesc& d, const void* in, const void* w, cons
     a.in_b = nullptr; a.w_b = nullptr; a.bias_b = nullptr; a.out_sub = nullptr; a.sub_off = 0; a.h_sub = 0; a.w_sub = 0; a.lw_out = 0;
     a.m_total = d.n * d.h_out * d.w_out;
     a.n_tiles = 0;
-    a.c_out = mode == 1 ? split->split : d.c_out;
+    a.c_out = f.form == ConvForm::Pair ? f.pair.split : d.c_out;
     a.res_stride = d.res_stride; a.res_off = d.res_offset; a.res_h = d.res_h; a.res_w = d.res_w;
     a.h_out = d.h_out; a.w_out = d.w_out;
     const bool rsub = d.has_residual && d.res_stride == 2;
-    if (mode == 1) {
-        a.w2 = a.w + (size_t)split->split * d.c_in; a.bias2 = bias + split->split; a.out2 = static_cast<half_t*>(split->out2);
+    if (f.form == ConvForm::Pair) {
+        a.w2 = a.w + (size_t)f.pair.split * d.c_in; a.bias2 = bias + f.pair.split; a.out2 = static_cast<half_t*>(f.pair.out2);
         if (d.c_in == 256) return launch_pw<256, 8, true, false, 1, false, false, 512>(a, stream);
         return launch_pw<64, 4, true, false, 1>(a, stream);
     }
-    if (mode >= 2) {
-        a.w2 = static_cast<const half_t*>(f2->w2); a.bias2 = f2->bias2;
-        a.scale2 = static_cast<const half_t*>(f2->scale2); a.shift2 = static_cast<const half_t*>(f2->shift2);
-        a.out2 = static_cast<half_t*>(f2->out2);
-        if (mode >= 3) {
-            a.x_sc = static_cast<const half_t*>(psc->x); a.w_sc = static_cast<const half_t*>(psc->w_sc); a.bias_sc = psc->bias_sc;
-            a.pro_scale = static_cast<const half_t*>(psc->pro_scale); a.pro_shift = static_cast<const half_t*>(psc->pro_shift);
-            if (reb) {
-                a.in_b = static_cast<const half_t*>(rb->t2_prev); a.w_b = static_cast<const half_t*>(rb->w3_prev); a.bias_b = rb->bias3_prev;
-                if (a.w_b == nullptr || a.bias_b == nullptr) { set_error("conv_pw64: rebuilt residual without the previous unit's conv3 parameters"); return METRO_ERR_INVALID_ARG; }
-                if (outm == 2) {
-                    a.out_sub = static_cast<half_t*>(rb->out_sub); a.sub_off = rb->sub_off; a.h_sub = rb->h_sub; a.w_sub = rb->w_sub;
+    if (f.form != ConvForm::Plain) {
+        a.w2 = static_cast<const half_t*>(f.next.w2); a.bias2 = f.next.bias2;
+        a.scale2 = static_cast<const half_t*>(f.next.scale2); a.shift2 = static_cast<const half_t*>(f.next.shift2);
+        a.out2 = static_cast<half_t*>(f.next.out2);
+        if (f.form != ConvForm::Next) {
+            a.x_sc = static_cast<const half_t*>(f.psc.x); a.w_sc = static_cast<const half_t*>(f.psc.w_sc); a.bias_sc = f.psc.bias_sc;
+            a.pro_scale = static_cast<const half_t*>(f.psc.pro_scale); a.pro_shift = static_cast<const half_t*>(f.psc.pro_shift);
+            if (f.form == ConvForm::NextRebuild) {
+                a.in_b = static_cast<const half_t*>(rb.t2_prev); a.w_b = static_cast<const half_t*>(rb.w3_prev); a.bias_b = rb.bias3_prev;
+                if (rb.out_mode == 2) {
+                    a.out_sub = static_cast<half_t*>(rb.out_sub); a.sub_off = rb.sub_off; a.h_sub = rb.h_sub; a.w_sub = rb.w_sub;
                     while ((1 << a.lw_out) < d.w_out) ++a.lw_out;
                     return launch_pw<64, 4, false, false, 2, false, true, 256, true, 2>(a, stream);
                 }
-                if (outm == 1) { set_error("conv_pw64: a rebuilt residual whose sum is neither stored nor sub-sampled has no consumer"); return METRO_ERR_INVALID_ARG; }
                 return launch_pw<64, 4, false, false, 2, false, true, 256, true, 0>(a, stream);
             }
-            if (outm == 1) return launch_pw<64, 4, false, false, 2, false, true, 256, false, 1>(a, stream);
+            if (rb.out_mode == 1) return launch_pw<64, 4, false, false, 2, false, true, 256, false, 1>(a, stream);
             return launch_pw<64, 4, false, false, 2, false, true>(a, stream);
         }
         if (d.c_in == 128) return launch_pw<128, 8, false, true, 2, false, false, 512>(a, stream);

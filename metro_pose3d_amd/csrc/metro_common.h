@@ -193,7 +193,6 @@ inline int launch_status(const char* what) {
     return METRO_OK;
 }
 
-// device-side view of MetroConvDesc plus derived values
 // Two convolutions over the same input fused into one launch: weight/bias rows [0, split) belong
 // to the first output (desc.c_out == split + c_out2 rows in total), rows [split, ...) to `out2`
 // (NHWC with c_out2 channels, its own ReLU flag).  split must be a multiple of the cout tile.
@@ -255,6 +254,25 @@ struct ConvRebuild {
                                        // would be dispatched (metro_forward_upto stopping at the layer: an independent second form)
 };
 
+// The shape of a fused conv launch (one launch that does more than one convolution), decided once -- by the planner or a C entry,
+// checked with conv_form_supported -- and read by every launcher on the way to the kernel:
+//   Plain        one convolution
+//   Pair         the projection shortcut + conv1 of a unit over concatenated weight rows (`pair`)
+//   Next         conv3 of a unit + conv1 of the next unit (`next`)
+//   NextProj     Next with the unit's projection shortcut computed in the launch (`psc`; block1/unit_1); rb.out_mode 0 | 1
+//   NextRebuild  NextProj on top of the unit's identity shortcut rebuilt in the launch (`rb`; block1/unit_2); rb.out_mode 0 | 2
+// (ConvPre1, conv1 in front of the 64-channel 3x3, belongs to conv3x3_c64.hip's family and is not one of them.)
+enum class ConvForm { Plain, Pair, Next, NextProj, NextRebuild };
+
+struct ConvFused {
+    ConvForm form = ConvForm::Plain;
+    ConvSplit pair;
+    ConvFuse2 next;
+    ConvProjSc psc;
+    ConvRebuild rb;    // out_mode and classic apply to NextProj too
+};
+
+// device-side view of MetroConvDesc plus derived values
 struct ConvArgs {
     int split, c_out2, relu2;   // see ConvSplit (0 = plain convolution)
     int n, h_in, w_in, c_in, in_pix_stride;
@@ -285,12 +303,14 @@ int validate_conv_desc(const MetroConvDesc* d);
 int launch_conv_f16(const MetroConvDesc& d, const void* in, const void* w, const float* bias,
                     const void* pro_scale, const void* pro_shift, const void* residual, void* out,
                     hipStream_t stream);
-// LDS-DMA ring kernel (coalesced epilogue)
+// LDS-DMA ring kernel (coalesced epilogue); also the dispatcher of the fused forms, which reads `f.form` (checked)
 bool conv_f16_dma_supported(const MetroConvDesc& d);
 int launch_conv_f16_dma(const MetroConvDesc& d, const void* in, const void* w, const float* bias,
                         const void* pro_scale, const void* pro_shift, const void* residual, void* out,
-                        hipStream_t stream, const ConvSplit* split = nullptr, const ConvFuse2* fuse2 = nullptr,
-                        const ConvProjSc* psc = nullptr, const ConvRebuild* rebuild = nullptr);
+                        hipStream_t stream, const ConvFused& f = ConvFused{});
+// whether `d` with the parts of `f` can run as one launch of form f.form: the one shape rule of each form (the pair's split, the
+// second GEMM's c2, the rebuilt residual's map and output mode), read by the planner, the C entries and the dispatch
+bool conv_form_supported(const MetroConvDesc& d, const ConvFused& f);
 bool conv_f16_fuse2_supported(const MetroConvDesc& d, int c2);
 // 256 x 256 x 64 GEMM, four waves of 128 x 128, register-staged operands (conv_gemm4w.hip): the pre-activated deep-K 1x1 layers
 // (conv1, projection shortcut, shortcut + conv1 pair of blocks 3-4) with at least one tile per CU
@@ -298,15 +318,12 @@ bool conv_gemm4w_shape_ok(const MetroConvDesc& d, const ConvSplit* split);      
 bool conv_gemm4w_supported(const MetroConvDesc& d, const ConvSplit* split);     // ... and when the dispatcher prefers it
 int launch_conv_gemm4w(const MetroConvDesc& d, const void* in, const void* w, const float* bias, const void* pro_scale,
                        const void* pro_shift, const void* residual, void* out, hipStream_t stream, const ConvSplit* split);
-// persistent pipelined kernel for block1's 64-channel 1x1 convolutions (conv_pw64.hip); mode: 0 plain,
-// 1 projection shortcut + conv1 pair (c_out = 256 + 64 concatenated rows), 2 conv3 + the next unit's conv1, 3 = 2 with the projection
-// shortcut computed in the launch, 4 = 3 with the residual rebuilt / the sum kept on chip (ConvRebuild)
-bool conv_pw64_supported(const MetroConvDesc& d, int mode);
+// persistent pipelined kernel for block1's 64-channel 1x1 convolutions and the conv3 layers of blocks 2-4 (conv_pw64.hip): whether it
+// runs `d` in form f.form with f's parts
+bool conv_pw64_supported(const MetroConvDesc& d, const ConvFused& f);
 int launch_conv_pw64(const MetroConvDesc& d, const void* in, const void* w, const float* bias, const void* pro_scale,
-                     const void* pro_shift, const void* residual, void* out, hipStream_t stream,
-                     const ConvSplit* split, const ConvFuse2* fuse2, const ConvProjSc* psc = nullptr,
-                     const ConvRebuild* rebuild = nullptr);
-// producer / consumer form of the conv3 + next conv1 launches of block1 whose sum stays on chip (conv_b1.hip)
+                     const void* pro_shift, const void* residual, void* out, hipStream_t stream, const ConvFused& f);
+// producer / consumer form of the NextProj / NextRebuild launches of block1 whose sum stays on chip (conv_b1.hip)
 bool conv_b1_chain_preferred();
 void conv_b1_set_form(int classic);      // thread-local test switch: 1 = never dispatch it (nor conv_pws.hip's kernel)
 bool classic_forms_forced();
@@ -314,7 +331,7 @@ bool classic_forms_forced();
 bool conv_pws_supported(const MetroConvDesc& d);
 int launch_conv_pws(const MetroConvDesc& d, const void* in, const void* w, const float* bias, const void* res, void* out, hipStream_t stream);
 int launch_conv_b1_chain(const MetroConvDesc& d, const void* in, const void* w, const float* bias, void* out, hipStream_t stream,
-                         const ConvFuse2& f2, const ConvProjSc& psc, const ConvRebuild& rb);
+                         const ConvFused& f);
 // stem 7x7/2 conv + zero-padded 3x3/2 max-pool in one persistent kernel (stem_pool_f16.hip); input is the
 // bordered 4-channel fp16 image of launch_prep_input_f16, weights packed [64][7][8][4]
 bool stem_pool_f16_supported(int side, int base_width);

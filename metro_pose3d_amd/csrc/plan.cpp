@@ -83,30 +83,32 @@ namespace {
 enum LayerKind { LK_PREP = 0, LK_CONV = 1, LK_POOL = 2, LK_SOFTARGMAX = 3 };
 enum Slot { S_IMAGES = -2, S_NONE = -1, S_PREP = 0, S_STEM, S_X0, S_X1, S_T1, S_T2, S_T2B, S_SC, S_LOGITS, S_PART, S_STATUS, S_COUNT };
 
+// parameter indices of one convolution's tensors in the blob, -1 = none
+struct ConvParams {
+    int w = -1, bias = -1, scale = -1, shift = -1;
+};
+
+// What a conv layer's launch does; launch_layer switches on it.  Pair ... NextRebuild are the fused conv forms (ConvForm).
+enum class LayerForm { Plain, Pair, Next, NextProj, NextRebuild, Conv1Conv2, StemPool, StemPoolF32In, Head };
+
 struct Layer {
+    Layer() { memset(&info, 0, sizeof(info)); }   // with the public struct's padding (metro_plan_layer_info copies it out)
     MetroLayerInfo info;
-    int kind;
-    MetroConvDesc cd;     // cd.n is filled per call
-    int in_slot, out_slot, res_slot;
-    int p_w, p_bias, p_scale, p_shift;
-    // fused pair (projection shortcut + conv1 of the same unit, same pre-activated input):
-    int split, c_out2, relu2, out2_slot;
-    // conv3 of unit u + conv1 of unit u+1 (ConvFuse2): parameter indices of the second GEMM, -1 = none
-    int f2_w, f2_bias, f2_scale, f2_shift, f2_c2;
-    // block1/unit_1 in two launches (round 3): conv1 fused in FRONT of conv2 (conv3x3_c64 PRE1: parameter indices of conv1 and of the
-    // unit's pre-activation, -1 = none) and the projection shortcut computed INSIDE the conv3 launch (conv_pw64 PSC: its
-    // parameters and the slot of the unit's input)
-    int p1_w, p1_bias, p1_scale, p1_shift;
-    int psc_w, psc_bias, psc_scale, psc_shift, psc_slot;
-    // block1 without its 256-channel residual stream in HBM (round 5, conv_pw64 REB / OUTM): parameters and slot of the PREVIOUS
-    // unit's conv3 (the shortcut is rebuilt from them + psc_*), what metro_forward does with the launch's sum (0 store, 1 keep on
-    // chip, 2 sub-sampled compact copy into sub_slot only) and the geometry of that copy
-    int reb_w, reb_bias, reb_slot;
-    int out_mode, sub_slot, sub_off, sub_side;
-    int stem_pool;        // stem conv + max-pool in one launch (the layer's output is the pooled tensor)
-    int head_c_in;        // soft-argmax layer of a fused head: input channels of the logits GEMM (which head kernel ran)
-    int head_fused;       // logits layer: GEMM + per-joint softmax statistics in one launch (head_f16.hip); the
-                          // soft-argmax layer behind it then only finalizes
+    int kind = LK_CONV;
+    LayerForm form = LayerForm::Plain;  // Head: also the soft-argmax layer behind a fused head, which then only finalizes
+    MetroConvDesc cd{};                 // cd.n is filled per call
+    int in_slot = S_NONE, out_slot = S_NONE, res_slot = S_NONE;
+    ConvParams main;      // the layer's convolution (Pair: the shortcut rows, which conv1's rows follow in the blob)
+    ConvParams conv1;     // conv1 of the unit inside the launch: a Pair's second row block, or in front of conv2 (Conv1Conv2, on the unit's input)
+    ConvParams next;      // conv1 of the NEXT unit on the launch's output (Next...)
+    ConvParams psc;       // the projection shortcut computed in the launch (NextProj, NextRebuild) from the unit input in psc_slot
+    ConvParams reb;       // the PREVIOUS unit's conv3 (w, bias; NextRebuild), whose output in reb_slot rebuilds the identity shortcut
+    int c2 = 0, out2_slot = S_NONE;   // the second output (Pair, Next...): channels, slot
+    int psc_slot = S_NONE, reb_slot = S_NONE;
+    // block1 without its 256-channel residual stream in HBM (round 5): what metro_forward does with the launch's sum (0 store, 1 keep
+    // on chip, 2 sub-sampled compact copy into sub_slot only) and the geometry of that copy
+    int out_mode = 0, sub_slot = S_NONE, sub_off = 0, sub_side = 0;
+    int head_c_in = 0;    // soft-argmax layer of a fused head: input channels of the logits GEMM (which head kernel ran)
 };
 
 }  // namespace
@@ -181,9 +183,6 @@ struct Builder {
                   int pad_beg, bool relu, int res_side, int res_stride, int res_offset,
                   int out_dtype, int in_dtype) {
         Layer L;
-        memset(&L, 0, sizeof(L));
-        L.f2_w = L.f2_bias = L.f2_scale = L.f2_shift = -1; L.p1_w = L.p1_bias = L.p1_scale = L.p1_shift = -1; L.psc_w = L.psc_bias = L.psc_scale = L.psc_shift = -1; L.psc_slot = S_NONE; L.reb_w = L.reb_bias = -1; L.reb_slot = L.sub_slot = S_NONE;
-        L.kind = LK_CONV;
         const bool fast = p->fast;
         const bool f32m = p->spec.precision == METRO_PREC_F32M;
         const int wdt = fast ? METRO_F16 : f32m ? METRO_F32 : METRO_F64;
@@ -202,15 +201,14 @@ struct Builder {
         cd.in_dtype = in_dtype;
         const std::string conv_var = root + "/" + scope;
         const std::string bn_var = bn_fold.empty() ? "" : root + "/" + bn_fold;
-        L.p_w = add_param(lname + "/W", METRO_PARAM_CONV_W, conv_var, bn_var, wdt, c_out, k, k, c_in, k, c_in);
-        L.p_bias = add_param(lname + "/bias", METRO_PARAM_BIAS, conv_var, bn_var, bdt, c_out, 1, 1, 1, 1, 1);
-        L.p_scale = L.p_shift = -1;
+        L.main.w = add_param(lname + "/W", METRO_PARAM_CONV_W, conv_var, bn_var, wdt, c_out, k, k, c_in, k, c_in);
+        L.main.bias = add_param(lname + "/bias", METRO_PARAM_BIAS, conv_var, bn_var, bdt, c_out, 1, 1, 1, 1, 1);
         if (cd.has_prologue) {
             const std::string pv = root + "/" + prologue_bn;
-            L.p_scale = add_param(lname + "/pro_scale", METRO_PARAM_PRO_SCALE, "", pv, wdt, c_in, 1, 1, 1, 1, 1);
-            L.p_shift = add_param(lname + "/pro_shift", METRO_PARAM_PRO_SHIFT, "", pv, wdt, c_in, 1, 1, 1, 1, 1);
+            L.main.scale = add_param(lname + "/pro_scale", METRO_PARAM_PRO_SCALE, "", pv, wdt, c_in, 1, 1, 1, 1, 1);
+            L.main.shift = add_param(lname + "/pro_shift", METRO_PARAM_PRO_SHIFT, "", pv, wdt, c_in, 1, 1, 1, 1, 1);
         }
-        L.in_slot = in_slot; L.out_slot = out_slot; L.res_slot = res_slot; L.out2_slot = S_NONE;
+        L.in_slot = in_slot; L.out_slot = out_slot; L.res_slot = res_slot;
         const int64_t out_es = out_dtype == METRO_F16 ? 2 : out_dtype == METRO_F32 ? 4 : 8;
         need(out_slot, (int64_t)side_out * side_out * c_out * out_es);
         fill_info(L, lname, (double)2.0 * side_out * side_out * c_out * k * k * c_in);
@@ -224,9 +222,7 @@ struct Builder {
     int add_shortcut_conv1_pair(const std::string& un, const std::string& sc, int in_slot, int side, int c_in,
                                 int c_sc, int cb, int adt) {
         Layer L;
-        memset(&L, 0, sizeof(L));
-        L.f2_w = L.f2_bias = L.f2_scale = L.f2_shift = -1; L.p1_w = L.p1_bias = L.p1_scale = L.p1_shift = -1; L.psc_w = L.psc_bias = L.psc_scale = L.psc_shift = -1; L.psc_slot = S_NONE; L.reb_w = L.reb_bias = -1; L.reb_slot = L.sub_slot = S_NONE;
-        L.kind = LK_CONV;
+        L.form = LayerForm::Pair;
         MetroConvDesc& cd = L.cd;
         cd.h_in = cd.w_in = side; cd.c_in = c_in; cd.in_pix_stride = c_in;
         cd.h_out = cd.w_out = side; cd.c_out = c_sc + cb;
@@ -234,22 +230,22 @@ struct Builder {
         cd.has_prologue = 1; cd.relu = 0; cd.has_residual = 0; cd.res_stride = 1;
         cd.out_dtype = adt; cd.in_dtype = adt;
         const std::string pre = root + "/" + sc + "/preact";
-        L.p_w = add_param(un + "/shortcut/W", METRO_PARAM_CONV_W, root + "/" + sc + "/shortcut", "", METRO_F16, c_sc, 1, 1, c_in, 1, c_in);
-        const int w2 = add_param(un + "/conv1/W", METRO_PARAM_CONV_W, root + "/" + sc + "/conv1", root + "/" + sc + "/conv1/BatchNorm",
-                                 METRO_F16, cb, 1, 1, c_in, 1, c_in);
-        L.p_bias = add_param(un + "/shortcut/bias", METRO_PARAM_BIAS, root + "/" + sc + "/shortcut", "", METRO_F32, c_sc, 1, 1, 1, 1, 1);
-        const int b2 = add_param(un + "/conv1/bias", METRO_PARAM_BIAS, root + "/" + sc + "/conv1", root + "/" + sc + "/conv1/BatchNorm",
+        L.main.w = add_param(un + "/shortcut/W", METRO_PARAM_CONV_W, root + "/" + sc + "/shortcut", "", METRO_F16, c_sc, 1, 1, c_in, 1, c_in);
+        L.conv1.w = add_param(un + "/conv1/W", METRO_PARAM_CONV_W, root + "/" + sc + "/conv1", root + "/" + sc + "/conv1/BatchNorm",
+                              METRO_F16, cb, 1, 1, c_in, 1, c_in);
+        L.main.bias = add_param(un + "/shortcut/bias", METRO_PARAM_BIAS, root + "/" + sc + "/shortcut", "", METRO_F32, c_sc, 1, 1, 1, 1, 1);
+        L.conv1.bias = add_param(un + "/conv1/bias", METRO_PARAM_BIAS, root + "/" + sc + "/conv1", root + "/" + sc + "/conv1/BatchNorm",
                                  METRO_F32, cb, 1, 1, 1, 1, 1);
         // contiguity (sizes are multiples of the 256-byte blob alignment for c_sc % 256 == 0, c_in % 64 == 0)
-        if (p->params[w2].offset != p->params[L.p_w].offset + p->params[L.p_w].bytes ||
-            p->params[b2].offset != p->params[L.p_bias].offset + p->params[L.p_bias].bytes) {
+        if (p->params[L.conv1.w].offset != p->params[L.main.w].offset + p->params[L.main.w].bytes ||
+            p->params[L.conv1.bias].offset != p->params[L.main.bias].offset + p->params[L.main.bias].bytes) {
             set_error("internal: fused pair parameters of %s are not contiguous in the blob", un.c_str());
             return METRO_ERR_STATE;       // the kernel reads conv1's rows at w + c_sc * c_in: never launch on a broken layout
         }
-        L.p_scale = add_param(un + "/shortcut/pro_scale", METRO_PARAM_PRO_SCALE, "", pre, METRO_F16, c_in, 1, 1, 1, 1, 1);
-        L.p_shift = add_param(un + "/shortcut/pro_shift", METRO_PARAM_PRO_SHIFT, "", pre, METRO_F16, c_in, 1, 1, 1, 1, 1);
-        L.in_slot = in_slot; L.out_slot = S_SC; L.res_slot = S_NONE;
-        L.split = c_sc; L.c_out2 = cb; L.relu2 = 1; L.out2_slot = S_T1;
+        L.main.scale = add_param(un + "/shortcut/pro_scale", METRO_PARAM_PRO_SCALE, "", pre, METRO_F16, c_in, 1, 1, 1, 1, 1);
+        L.main.shift = add_param(un + "/shortcut/pro_shift", METRO_PARAM_PRO_SHIFT, "", pre, METRO_F16, c_in, 1, 1, 1, 1, 1);
+        L.in_slot = in_slot; L.out_slot = S_SC;
+        L.c2 = cb; L.out2_slot = S_T1;
         need(S_SC, (int64_t)side * side * c_sc * 2);
         need(S_T1, (int64_t)side * side * cb * 2);
         fill_info(L, un + "/shortcut+conv1", 2.0 * side * side * (double)(c_sc + cb) * c_in);
@@ -267,11 +263,12 @@ struct Builder {
         const std::string bn_var = conv_var + "/BatchNorm";
         const std::string pv = root + "/" + sc_next + "/preact";
         const std::string ln = un_next + "/conv1";
-        L.f2_w = add_param(ln + "/W", METRO_PARAM_CONV_W, conv_var, bn_var, METRO_F16, cb, 1, 1, c_in, 1, c_in);
-        L.f2_bias = add_param(ln + "/bias", METRO_PARAM_BIAS, conv_var, bn_var, METRO_F32, cb, 1, 1, 1, 1, 1);
-        L.f2_scale = add_param(ln + "/pro_scale", METRO_PARAM_PRO_SCALE, "", pv, METRO_F16, c_in, 1, 1, 1, 1, 1);
-        L.f2_shift = add_param(ln + "/pro_shift", METRO_PARAM_PRO_SHIFT, "", pv, METRO_F16, c_in, 1, 1, 1, 1, 1);
-        L.f2_c2 = cb; L.out2_slot = S_T1;
+        L.next.w = add_param(ln + "/W", METRO_PARAM_CONV_W, conv_var, bn_var, METRO_F16, cb, 1, 1, c_in, 1, c_in);
+        L.next.bias = add_param(ln + "/bias", METRO_PARAM_BIAS, conv_var, bn_var, METRO_F32, cb, 1, 1, 1, 1, 1);
+        L.next.scale = add_param(ln + "/pro_scale", METRO_PARAM_PRO_SCALE, "", pv, METRO_F16, c_in, 1, 1, 1, 1, 1);
+        L.next.shift = add_param(ln + "/pro_shift", METRO_PARAM_PRO_SHIFT, "", pv, METRO_F16, c_in, 1, 1, 1, 1, 1);
+        L.c2 = cb; L.out2_slot = S_T1;
+        if (L.form == LayerForm::Plain) L.form = LayerForm::Next;      // NextProj / NextRebuild: set by the shortcut fusions before
         need(S_T1, (int64_t)side * side * cb * 2);
         const double flops = 2.0 * side * side * (double)cb * c_in;
         const std::string name = std::string(L.info.name) + "+" + un_next.substr(un_next.find('/') + 1) + "/conv1";
@@ -287,10 +284,11 @@ struct Builder {
         const std::string conv_var = root + "/" + sc + "/conv1";
         const std::string bn_var = conv_var + "/BatchNorm";
         const std::string pv = root + "/" + sc + "/preact";
-        L.p1_w = add_param(un + "/conv1/W", METRO_PARAM_CONV_W, conv_var, bn_var, METRO_F16, cb, 1, 1, c_in, 1, c_in);
-        L.p1_bias = add_param(un + "/conv1/bias", METRO_PARAM_BIAS, conv_var, bn_var, METRO_F32, cb, 1, 1, 1, 1, 1);
-        L.p1_scale = add_param(un + "/conv1/pro_scale", METRO_PARAM_PRO_SCALE, "", pv, METRO_F16, c_in, 1, 1, 1, 1, 1);
-        L.p1_shift = add_param(un + "/conv1/pro_shift", METRO_PARAM_PRO_SHIFT, "", pv, METRO_F16, c_in, 1, 1, 1, 1, 1);
+        L.conv1.w = add_param(un + "/conv1/W", METRO_PARAM_CONV_W, conv_var, bn_var, METRO_F16, cb, 1, 1, c_in, 1, c_in);
+        L.conv1.bias = add_param(un + "/conv1/bias", METRO_PARAM_BIAS, conv_var, bn_var, METRO_F32, cb, 1, 1, 1, 1, 1);
+        L.conv1.scale = add_param(un + "/conv1/pro_scale", METRO_PARAM_PRO_SCALE, "", pv, METRO_F16, c_in, 1, 1, 1, 1, 1);
+        L.conv1.shift = add_param(un + "/conv1/pro_shift", METRO_PARAM_PRO_SHIFT, "", pv, METRO_F16, c_in, 1, 1, 1, 1, 1);
+        L.form = LayerForm::Conv1Conv2;
         L.in_slot = in_slot;
         const double flops = 2.0 * side * side * (double)cb * c_in;
         snprintf(L.info.name, sizeof(L.info.name), "%s/conv1+conv2", un.c_str());
@@ -305,10 +303,11 @@ struct Builder {
         Layer& L = p->layers.back();
         const std::string conv_var = root + "/" + sc + "/shortcut";
         const std::string pv = root + "/" + sc + "/preact";
-        L.psc_w = add_param(un + "/shortcut/W", METRO_PARAM_CONV_W, conv_var, "", METRO_F16, c_out, 1, 1, c_in, 1, c_in);
-        L.psc_bias = add_param(un + "/shortcut/bias", METRO_PARAM_BIAS, conv_var, "", METRO_F32, c_out, 1, 1, 1, 1, 1);
-        L.psc_scale = add_param(un + "/shortcut/pro_scale", METRO_PARAM_PRO_SCALE, "", pv, METRO_F16, c_in, 1, 1, 1, 1, 1);
-        L.psc_shift = add_param(un + "/shortcut/pro_shift", METRO_PARAM_PRO_SHIFT, "", pv, METRO_F16, c_in, 1, 1, 1, 1, 1);
+        L.psc.w = add_param(un + "/shortcut/W", METRO_PARAM_CONV_W, conv_var, "", METRO_F16, c_out, 1, 1, c_in, 1, c_in);
+        L.psc.bias = add_param(un + "/shortcut/bias", METRO_PARAM_BIAS, conv_var, "", METRO_F32, c_out, 1, 1, 1, 1, 1);
+        L.psc.scale = add_param(un + "/shortcut/pro_scale", METRO_PARAM_PRO_SCALE, "", pv, METRO_F16, c_in, 1, 1, 1, 1, 1);
+        L.psc.shift = add_param(un + "/shortcut/pro_shift", METRO_PARAM_PRO_SHIFT, "", pv, METRO_F16, c_in, 1, 1, 1, 1, 1);
+        L.form = LayerForm::NextProj;
         L.psc_slot = x_slot;
         const double flops = 2.0 * side * side * (double)c_out * c_in;
         L.info.flops_per_image += flops;
@@ -339,6 +338,25 @@ int tf_same_pad_beg(int in, int k_eff, int s) {
     return total / 2;
 }
 
+// A batch-1 fp16 stride-1 SAME k x k convolution on a side x side map: what the planner asks the kernel predicates about a layer
+// before adding it.  The choice must hold for EVERY batch the plan may run (the layer list is fixed): probed at n = 1.
+MetroConvDesc probe_desc(int side, int c_in, int c_out, int k, bool prologue, bool relu) {
+    MetroConvDesc d{};
+    d.n = 1; d.h_in = d.w_in = d.h_out = d.w_out = side; d.c_in = d.in_pix_stride = c_in; d.c_out = c_out;
+    d.kh = d.kw = k; d.stride = 1; d.dilation = 1; d.pad_top = d.pad_left = k / 2;
+    d.has_prologue = prologue; d.relu = relu; d.res_stride = 1;
+    d.out_dtype = d.in_dtype = METRO_F16;
+    return d;
+}
+
+// a fused form with the shape of its parts only (no tensors): probes of conv_form_supported / conv_pw64_supported
+ConvFused form_probe(ConvForm form, int c2) {
+    ConvFused f;
+    f.form = form;
+    f.next.c2 = c2;
+    return f;
+}
+
 int build_plan(MetroPlan* p) {
     const MetroSpec& sp = p->spec;
     Builder B{p, std::string("MainPart/resnet_v2_") + std::to_string(sp.arch)};
@@ -357,13 +375,10 @@ int build_plan(MetroPlan* p) {
     const bool raw_stem = fast && stem_pool_f32in_supported(side, bw);
     if (fast) {
         Layer L;
-        memset(&L, 0, sizeof(L));
-        L.f2_w = L.f2_bias = L.f2_scale = L.f2_shift = -1; L.p1_w = L.p1_bias = L.p1_scale = L.p1_shift = -1; L.psc_w = L.psc_bias = L.psc_scale = L.psc_shift = -1; L.psc_slot = S_NONE; L.reb_w = L.reb_bias = -1; L.reb_slot = L.sub_slot = S_NONE;
         L.kind = LK_PREP;
         L.cd.h_in = L.cd.w_in = side; L.cd.c_in = 3;
         L.cd.h_out = side + 6; L.cd.w_out = side + 8; L.cd.c_out = 4; L.cd.out_dtype = METRO_F16;
-        L.in_slot = S_IMAGES; L.out_slot = S_PREP; L.res_slot = S_NONE;
-        L.p_w = L.p_bias = L.p_scale = L.p_shift = -1;
+        L.in_slot = S_IMAGES; L.out_slot = S_PREP;
         if (!raw_stem) {
             B.need(S_PREP, (int64_t)(side + 6) * (side + 8) * 4 * 2);
             B.fill_info(L, "prep_input", 0.0);
@@ -374,23 +389,19 @@ int build_plan(MetroPlan* p) {
         // pixels x 4 channels = 32 contiguous fp16; weights packed [c_out][7][8][4] (zeros in
         // the 8th pixel and the 4th channel).
         Layer S;
-        memset(&S, 0, sizeof(S));
-        S.f2_w = S.f2_bias = S.f2_scale = S.f2_shift = -1; S.p1_w = S.p1_bias = S.p1_scale = S.p1_shift = -1; S.psc_w = S.psc_bias = S.psc_scale = S.psc_shift = -1; S.psc_slot = S_NONE; S.reb_w = S.reb_bias = -1; S.reb_slot = S.sub_slot = S_NONE;
-        S.kind = LK_CONV;
         MetroConvDesc& cd = S.cd;
         cd.h_in = side + 6; cd.w_in = side + 8; cd.c_in = 32; cd.in_pix_stride = 4;
         cd.h_out = cd.w_out = s2; cd.c_out = bw;
         cd.kh = 7; cd.kw = 1; cd.stride = 2; cd.dilation = 1; cd.pad_top = cd.pad_left = 0;
         cd.out_dtype = adt; cd.in_dtype = METRO_F16;
         const std::string cv = B.root + "/conv1";
-        S.p_w = B.add_param("conv1/W", METRO_PARAM_CONV_W, cv, "", METRO_F16, bw, 7, 7, 3, 8, 4);
-        S.p_bias = B.add_param("conv1/bias", METRO_PARAM_BIAS, cv, "", METRO_F32, bw, 1, 1, 1, 1, 1);
-        S.p_scale = S.p_shift = -1;
-        S.in_slot = S_PREP; S.out_slot = S_STEM; S.res_slot = S_NONE;
+        S.main.w = B.add_param("conv1/W", METRO_PARAM_CONV_W, cv, "", METRO_F16, bw, 7, 7, 3, 8, 4);
+        S.main.bias = B.add_param("conv1/bias", METRO_PARAM_BIAS, cv, "", METRO_F32, bw, 1, 1, 1, 1, 1);
+        S.in_slot = S_PREP; S.out_slot = S_STEM;
         if (stem_pool_f16_supported(side, bw)) {
             // reference resnet_v2.py:219-224: the pooled tensor is the only thing block1 reads
             fused_stem_pool = true;
-            S.stem_pool = raw_stem ? 2 : 1;
+            S.form = raw_stem ? LayerForm::StemPoolF32In : LayerForm::StemPool;
             if (raw_stem) S.in_slot = S_IMAGES;
             S.out_slot = S_X0;
             const int s4f = (s2 + 2 - 3) / 2 + 1;
@@ -410,14 +421,11 @@ int build_plan(MetroPlan* p) {
     const int s4 = (s2 + 2 - 3) / 2 + 1;     // 64
     if (!fused_stem_pool) {
         Layer L;
-        memset(&L, 0, sizeof(L));
-        L.f2_w = L.f2_bias = L.f2_scale = L.f2_shift = -1; L.p1_w = L.p1_bias = L.p1_scale = L.p1_shift = -1; L.psc_w = L.psc_bias = L.psc_scale = L.psc_shift = -1; L.psc_slot = S_NONE; L.reb_w = L.reb_bias = -1; L.reb_slot = L.sub_slot = S_NONE;
         L.kind = LK_POOL;
         L.cd.h_in = L.cd.w_in = s2; L.cd.c_in = bw; L.cd.h_out = L.cd.w_out = s4; L.cd.c_out = bw;
         L.cd.kh = L.cd.kw = 3; L.cd.stride = 2; L.cd.dilation = 1; L.cd.pad_top = L.cd.pad_left = 1;
         L.cd.out_dtype = adt;
-        L.in_slot = S_STEM; L.out_slot = S_X0; L.res_slot = S_NONE;
-        L.p_w = L.p_bias = L.p_scale = L.p_shift = -1;
+        L.in_slot = S_STEM; L.out_slot = S_X0;
         B.need(S_X0, (int64_t)s4 * s4 * bw * aes);
         B.fill_info(L, "pool1", 0.0);
         p->layers.push_back(L);
@@ -472,38 +480,20 @@ int build_plan(MetroPlan* p) {
             // block1 (cb = 64: a half-empty tile in the tiled kernel) pairs only in the persistent kernel
             bool pw_pair = false;
             if (fast && project && s == 1 && cur_c == 64 && cout == 256 && cb == 64) {
-                MetroConvDesc probe;
-                memset(&probe, 0, sizeof(probe));
-                probe.n = 1; probe.h_in = probe.w_in = probe.h_out = probe.w_out = cur_side;
-                probe.c_in = probe.in_pix_stride = cur_c; probe.c_out = cout + cb;
-                probe.kh = probe.kw = 1; probe.stride = 1; probe.dilation = 1; probe.has_prologue = 1;
-                probe.out_dtype = probe.in_dtype = METRO_F16; probe.res_stride = 1;
-                pw_pair = conv_pw64_supported(probe, 1);
+                ConvFused pair = form_probe(ConvForm::Pair, 0);
+                pair.pair.split = cout; pair.pair.c_out2 = cb; pair.pair.relu2 = 1;
+                pw_pair = conv_pw64_supported(probe_desc(cur_side, cur_c, cout + cb, 1, true, false), pair);
             }
             // block1/unit_1 (64-channel input): conv1 in front of conv2 inside the weight-resident 3x3 kernel, the projection
-            // shortcut inside the conv3 (+ next conv1) launch: two launches, no shortcut / t1 tensors.  The choice must hold for
-            // EVERY batch the plan may run (the layer list is fixed): probed at n = 1.
-            bool unit_fused = false;
-            if (fast && project && s == 1 && r == 1 && cur_c == 64 && cb == 64 && cout == 256 && u < n_units[b] && !conv1_done &&
-                tuning_knob("METRO_UNIT1_FUSED", 1)) {
-                MetroConvDesc c2, c3;
-                memset(&c2, 0, sizeof(c2));
-                c2.n = 1; c2.h_in = c2.w_in = c2.h_out = c2.w_out = cur_side; c2.c_in = c2.in_pix_stride = c2.c_out = 64;
-                c2.kh = c2.kw = 3; c2.stride = 1; c2.dilation = 1; c2.pad_top = c2.pad_left = 1; c2.relu = 1;
-                c2.out_dtype = c2.in_dtype = METRO_F16; c2.res_stride = 1;
-                c3 = c2;
-                c3.kh = c3.kw = 1; c3.pad_top = c3.pad_left = 0; c3.relu = 0; c3.c_out = 256;
-                unit_fused = conv3x3_c64_supported(c2) && conv_pw64_supported(c3, 3);
-            }
+            // shortcut inside the conv3 (+ next conv1) launch: two launches, no shortcut / t1 tensors
+            const MetroConvDesc conv3 = probe_desc(cur_side, 64, 256, 1, false, false);
+            const bool unit_fused = fast && project && s == 1 && r == 1 && cur_c == 64 && cb == 64 && cout == 256 && u < n_units[b] &&
+                                    !conv1_done && tuning_knob("METRO_UNIT1_FUSED", 1) &&
+                                    conv3x3_c64_supported(probe_desc(cur_side, 64, 64, 3, false, true)) &&
+                                    conv_form_supported(conv3, form_probe(ConvForm::NextProj, cb));
             // ... and none of the block's 256-channel sums in HBM (conv_pw64 REB / OUTM): three units, the second one plain
-            bool chain_start = false;
-            if (unit_fused && u == 1 && n_units[b] == 3 && tuning_knob("METRO_B1_REBUILD", 1)) {
-                MetroConvDesc c3;
-                memset(&c3, 0, sizeof(c3));
-                c3.n = 1; c3.h_in = c3.w_in = c3.h_out = c3.w_out = cur_side; c3.c_in = c3.in_pix_stride = 64; c3.c_out = 256;
-                c3.kh = c3.kw = 1; c3.stride = 1; c3.dilation = 1; c3.out_dtype = c3.in_dtype = METRO_F16; c3.res_stride = 1;
-                chain_start = conv_pw64_supported(c3, 4);
-            }
+            const bool chain_start = unit_fused && u == 1 && n_units[b] == 3 && tuning_knob("METRO_B1_REBUILD", 1) &&
+                                     conv_form_supported(conv3, form_probe(ConvForm::NextRebuild, cb));
             const bool chain_mid = chain == 1 && u == 2 && conv1_done && !project && s == 1 && r == 1;
             if (chain == 1 && !chain_mid) { set_error("internal: block1 rebuild chain planned for a unit 2 that is not plain"); return METRO_ERR_STATE; }
             const int nxt_slot = chain_mid ? S_X1 : nxt;      // unit 2 of the chain: S_X0 still holds x0, which its launch reads
@@ -556,8 +546,9 @@ int build_plan(MetroPlan* p) {
                 const Layer& L1 = p->layers[chain_l1];
                 L3.info.has_residual = 1; L3.info.res_stride = 1; L3.info.res_offset = 0;    // the reference's shortcut, as for any unit
                 L3.info.fused_flags |= METRO_FUSED_REBUILT_SHORTCUT;
-                L3.reb_w = L1.p_w; L3.reb_bias = L1.p_bias; L3.reb_slot = L1.in_slot;
-                L3.psc_w = L1.psc_w; L3.psc_bias = L1.psc_bias; L3.psc_scale = L1.psc_scale; L3.psc_shift = L1.psc_shift; L3.psc_slot = chain_x0;
+                L3.form = LayerForm::NextRebuild;
+                L3.reb.w = L1.main.w; L3.reb.bias = L1.main.bias; L3.reb_slot = L1.in_slot;
+                L3.psc = L1.psc; L3.psc_slot = chain_x0;
                 // what the last unit reads of this sum: every pixel (it runs at stride 1: stride-4 nets), or every second one
                 const bool next_strided = (double)current_stride != output_stride;      // resnet_utils.py:325-333 for unit 3
                 if (next_strided) {
@@ -589,12 +580,12 @@ int build_plan(MetroPlan* p) {
             if (fast && u < n_units[b] && s == 1) {
                 MetroConvDesc probe = p->layers.back().cd;
                 probe.n = 1;
-                // block2 (128 -> 512 on 32-wide maps): the persistent kernel with all 512 channels of a pixel tile in one block
-                const bool pw_next = probe.c_in == 128 && cb == 128 && conv_pw64_supported(probe, 2);
-                // chain_mid: unit 2 of block1's rebuild chain has no residual tensor to read -- its identity shortcut exists only
-                // inside the fused conv3 + next-conv1 launch (conv_pw64 REB), so the fusion is not optional there (METRO_FUSE2=0
-                // used to drop the shortcut silently: ADVICE r5)
-                if (conv_f16_fuse2_supported(probe, cb) || unit_fused || chain_mid || pw_next) {
+                // block1: the ring kernel's fusion (METRO_FUSE2); block2 (128 -> 512 on 32-wide maps): the persistent kernel with all
+                // 512 channels of a pixel tile in one block.  The NextProj / NextRebuild layers (unit_fused, chain_mid) are fused
+                // launches by form: unit 2 of the rebuild chain has no residual tensor to read at all
+                const bool next = probe.c_in == 128 ? conv_form_supported(probe, form_probe(ConvForm::Next, cb))
+                                                    : conv_f16_fuse2_supported(probe, cb);
+                if (next || unit_fused || chain_mid) {
                     const std::string un2 = "block" + std::to_string(b + 1) + "/unit_" + std::to_string(u + 1);
                     B.fuse_next_conv1(un2, un2 + "/bottleneck_v2", side_out, cout, cb);
                     conv1_done = true;
@@ -613,19 +604,16 @@ int build_plan(MetroPlan* p) {
                c_head, 1, 1, 1, 0, false, 0, 1, 0, ldt, adt);
     // fp16 mode: the logits stay on chip (volumetric.py:227-235 starts in the GEMM's epilogue)
     const bool head_fused = fast && head_f16_supported(cur_c, c_head, sp.n_joints_head, sp.depth, cur_side);
-    p->layers.back().head_fused = head_fused ? 1 : 0;
+    if (head_fused) p->layers.back().form = LayerForm::Head;
 
     // ---- soft-argmax + decode ---------------------------------------------------------------
     {
         Layer L;
-        memset(&L, 0, sizeof(L));
-        L.f2_w = L.f2_bias = L.f2_scale = L.f2_shift = -1; L.p1_w = L.p1_bias = L.p1_scale = L.p1_shift = -1; L.psc_w = L.psc_bias = L.psc_scale = L.psc_shift = -1; L.psc_slot = S_NONE; L.reb_w = L.reb_bias = -1; L.reb_slot = L.sub_slot = S_NONE;
         L.kind = LK_SOFTARGMAX;
         L.cd.h_in = L.cd.w_in = cur_side; L.cd.c_in = c_head; L.cd.h_out = 1; L.cd.w_out = sp.n_joints_out;
         L.cd.c_out = 3; L.cd.out_dtype = METRO_F32;
-        L.in_slot = S_LOGITS; L.out_slot = S_NONE; L.res_slot = S_NONE;
-        L.p_w = L.p_bias = L.p_scale = L.p_shift = -1;
-        L.head_fused = head_fused ? 1 : 0;
+        L.in_slot = S_LOGITS;
+        L.form = head_fused ? LayerForm::Head : LayerForm::Plain;
         L.head_c_in = cur_c;
         B.fill_info(L, "softargmax", 0.0);
         p->layers.push_back(L);
@@ -654,13 +642,13 @@ int build_plan(MetroPlan* p) {
         L.info.out_sub_side = L.out_mode == 2 ? L.sub_side : 0;
         L.info.out_sub_off = L.out_mode == 2 ? L.sub_off : 0;
         const int64_t es = L.cd.out_dtype == METRO_F16 ? 2 : L.cd.out_dtype == METRO_F32 ? 4 : 8;
-        L.info.out_bytes_per_image = (int64_t)L.cd.h_out * L.cd.w_out * (L.split > 0 ? L.split : L.cd.c_out) * es;
-        const bool two = L.kind == LK_CONV && (L.split > 0 || L.f2_w >= 0);
+        L.info.out_bytes_per_image = (int64_t)L.cd.h_out * L.cd.w_out * (L.form == LayerForm::Pair ? L.cd.c_out - L.c2 : L.cd.c_out) * es;
+        const bool two = L.out2_slot != S_NONE;
         L.info.out2_offset = two ? p->slot_offset[L.out2_slot] : -1;
-        L.info.out2_channels = two ? (L.split > 0 ? L.c_out2 : L.f2_c2) : 0;
-        if (L.p1_w >= 0) {      // conv1+conv2: conv1's output is a DUMP-ONLY second tensor (metro_forward_upto stopping here), not traffic
+        L.info.out2_channels = two ? L.c2 : 0;
+        if (L.form == LayerForm::Conv1Conv2) {  // conv1's output is a DUMP-ONLY second tensor (metro_forward_upto stopping here), not traffic
             L.info.out2_offset = p->slot_offset[S_T1];
-            L.info.out2_channels = p->params[L.p1_w].c_out;
+            L.info.out2_channels = p->params[L.conv1.w].c_out;
         }
         // algorithmic bytes: every tensor the launch touches, once
         const int64_t in_es = L.in_slot == S_IMAGES ? 4 : (L.kind == LK_SOFTARGMAX ? (sp.precision == METRO_PREC_F64 ? 8 : 4)
@@ -672,21 +660,20 @@ int build_plan(MetroPlan* p) {
         if (L.kind == LK_SOFTARGMAX) act += (int64_t)sp.n_joints_out * 3 * 4;
         else if (L.out_mode == 0) act += L.info.out_bytes_per_image;
         else if (L.out_mode == 2) act += (int64_t)L.sub_side * L.sub_side * L.cd.c_out * es;     // the sub-sampled copy only
-        if (L.reb_w >= 0) act += (int64_t)L.cd.h_out * L.cd.w_out * p->params[L.reb_w].c_in * es;  // the previous unit's conv2 output
+        if (L.reb.w >= 0) act += (int64_t)L.cd.h_out * L.cd.w_out * p->params[L.reb.w].c_in * es;  // the previous unit's conv2 output
         if (two) act += (int64_t)L.cd.h_out * L.cd.w_out * L.info.out2_channels * es;
         if (L.kind == LK_CONV && L.cd.has_residual) act += (int64_t)L.cd.h_out * L.cd.w_out * L.cd.c_out * es;
-        if (L.psc_w >= 0) act += (int64_t)L.cd.h_out * L.cd.w_out * p->params[L.psc_w].c_in * es;      // the unit input, read for the shortcut
-        if (L.head_fused) {       // logits never reach HBM: the launch writes / the finalize reads the per-slab statistics
+        if (L.psc.w >= 0) act += (int64_t)L.cd.h_out * L.cd.w_out * p->params[L.psc.w].c_in * es;      // the unit input, read for the shortcut
+        if (L.form == LayerForm::Head) {       // logits never reach HBM: the launch writes / the finalize reads the per-slab statistics
             const int64_t part = (int64_t)head_f16_slabs(sp.proc_side / sp.stride) * sp.n_joints_head * 5 * 4;
             if (L.kind == LK_CONV) act = (int64_t)L.cd.h_in * L.cd.w_in * L.cd.c_in * 2 + part;
             else act = part + (int64_t)sp.n_joints_out * 3 * 4;
         }
         L.info.algo_act_bytes_per_image = act;
         int64_t pb = 0;
-        for (int idx : {L.p_w, L.p_bias, L.p_scale, L.p_shift, L.f2_w, L.f2_bias, L.f2_scale, L.f2_shift, L.p1_w, L.p1_bias, L.p1_scale,
-                        L.p1_shift, L.psc_w, L.psc_bias, L.psc_scale, L.psc_shift, L.reb_w, L.reb_bias})
-            if (idx >= 0) pb += p->params[idx].bytes;
-        if (L.split > 0) pb += p->params[L.p_w + 1].bytes + p->params[L.p_bias + 1].bytes;   // conv1 rows of a fused pair
+        for (const ConvParams& g : {L.main, L.conv1, L.next, L.psc, L.reb})
+            for (int idx : {g.w, g.bias, g.scale, g.shift})
+                if (idx >= 0) pb += p->params[idx].bytes;
         L.info.algo_param_bytes = pb;
     }
     return METRO_OK;
@@ -710,75 +697,65 @@ int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* 
         case LK_CONV: {
             MetroConvDesc cd = L.cd;
             cd.n = n;
-            if (p->fast && L.head_fused) {
-                float* logits_dump = dump ? static_cast<float*>(slot_ptr(L.out_slot)) : nullptr;
-                return launch_head_f16(slot_ptr(L.in_slot), prm(L.p_w), static_cast<const float*>(prm(L.p_bias)), prm(L.p_scale),
-                                       prm(L.p_shift), n, L.cd.c_in, L.cd.c_out, p->spec.n_joints_head, p->spec.depth, L.cd.h_in,
-                                       static_cast<float*>(slot_ptr(S_PART)), logits_dump, stream);
-            }
-            if (p->fast && L.stem_pool == 2)
-                return launch_stem_pool_f32in(images, prm(L.p_w), static_cast<const float*>(prm(L.p_bias)), slot_ptr(L.out_slot), n,
-                                              p->spec.proc_side, stream);
-            if (p->fast && L.stem_pool)
-                return launch_stem_pool_f16(slot_ptr(L.in_slot), prm(L.p_w), static_cast<const float*>(prm(L.p_bias)),
-                                            slot_ptr(L.out_slot), n, p->spec.proc_side, stream);
-            if (p->fast && L.split > 0) {
-                ConvSplit sp;
-                sp.split = L.split; sp.c_out2 = L.c_out2; sp.relu2 = L.relu2; sp.out2 = slot_ptr(L.out2_slot);
-                return launch_conv_f16_dma(cd, slot_ptr(L.in_slot), prm(L.p_w), static_cast<const float*>(prm(L.p_bias)),
-                                           prm(L.p_scale), prm(L.p_shift), nullptr, slot_ptr(L.out_slot), stream, &sp);
-            }
-            if (p->fast && L.f2_w >= 0) {
-                ConvFuse2 f2;
-                f2.w2 = prm(L.f2_w); f2.bias2 = static_cast<const float*>(prm(L.f2_bias));
-                f2.scale2 = prm(L.f2_scale); f2.shift2 = prm(L.f2_shift);
-                f2.out2 = slot_ptr(L.out2_slot); f2.c2 = L.f2_c2;
-                ConvProjSc ps;
-                if (L.psc_w >= 0) {
-                    ps.x = slot_ptr(L.psc_slot); ps.w_sc = prm(L.psc_w); ps.bias_sc = static_cast<const float*>(prm(L.psc_bias));
-                    ps.pro_scale = prm(L.psc_scale); ps.pro_shift = prm(L.psc_shift);
+            auto fprm = [&](int idx) { return static_cast<const float*>(prm(idx)); };
+            void* in = slot_ptr(L.in_slot);
+            void* out = slot_ptr(L.out_slot);
+            const void* w = prm(L.main.w);
+            const float* bias = fprm(L.main.bias);
+            ConvFused f;
+            switch (L.form) {
+                case LayerForm::Head: {
+                    float* logits_dump = dump ? static_cast<float*>(out) : nullptr;
+                    return launch_head_f16(in, w, bias, prm(L.main.scale), prm(L.main.shift), n, L.cd.c_in, L.cd.c_out, p->spec.n_joints_head,
+                                           p->spec.depth, L.cd.h_in, static_cast<float*>(slot_ptr(S_PART)), logits_dump, stream);
                 }
-                // block1 without its residual stream in HBM: metro_forward_upto stopping here (dump) stores the sum in full
-                ConvRebuild rb;
-                const bool has_rb = L.reb_w >= 0 || L.out_mode != 0;
-                if (L.reb_w >= 0) {
-                    rb.t2_prev = slot_ptr(L.reb_slot); rb.w3_prev = prm(L.reb_w); rb.bias3_prev = static_cast<const float*>(prm(L.reb_bias));
+                case LayerForm::StemPoolF32In:
+                    return launch_stem_pool_f32in(images, w, bias, out, n, p->spec.proc_side, stream);
+                case LayerForm::StemPool:
+                    return launch_stem_pool_f16(in, w, bias, out, n, p->spec.proc_side, stream);
+                case LayerForm::Conv1Conv2: {
+                    ConvPre1 p1;
+                    p1.w1 = prm(L.conv1.w); p1.bias1 = fprm(L.conv1.bias);
+                    p1.pro_scale = prm(L.conv1.scale); p1.pro_shift = prm(L.conv1.shift);
+                    p1.t1_dump = dump ? slot_ptr(S_T1) : nullptr;        // conv1's output exists in LDS only; layer dumps get a copy
+                    return launch_conv3x3_c64(cd, in, w, bias, out, stream, &p1);
                 }
-                rb.out_mode = dump ? 0 : L.out_mode;
-                rb.classic = dump ? 1 : 0;
-                if (rb.out_mode == 2) { rb.out_sub = slot_ptr(L.sub_slot); rb.sub_off = L.sub_off; rb.h_sub = rb.w_sub = L.sub_side; }
-                return launch_conv_f16_dma(cd, slot_ptr(L.in_slot), prm(L.p_w), static_cast<const float*>(prm(L.p_bias)),
-                                           nullptr, nullptr, slot_ptr(L.res_slot), slot_ptr(L.out_slot), stream, nullptr, &f2,
-                                           L.psc_w >= 0 ? &ps : nullptr, has_rb ? &rb : nullptr);
+                case LayerForm::Plain:
+                    if (p->fast)
+                        return launch_conv_f16(cd, in, w, bias, prm(L.main.scale), prm(L.main.shift), slot_ptr(L.res_slot), out, stream);
+                    if (p->spec.precision == METRO_PREC_F32M)
+                        return launch_conv_f32m(cd, in, static_cast<const float*>(w), bias, fprm(L.main.scale), fprm(L.main.shift),
+                                                slot_ptr(L.res_slot), out, stream);
+                    return launch_conv_f64acc(cd, in, static_cast<const double*>(w), static_cast<const double*>(prm(L.main.bias)),
+                                              static_cast<const double*>(prm(L.main.scale)), static_cast<const double*>(prm(L.main.shift)),
+                                              slot_ptr(L.res_slot), out, stream);
+                case LayerForm::Pair:
+                    f.form = ConvForm::Pair;
+                    f.pair = {L.cd.c_out - L.c2, L.c2, 1, slot_ptr(L.out2_slot)};
+                    return launch_conv_f16_dma(cd, in, w, bias, prm(L.main.scale), prm(L.main.shift), nullptr, out, stream, f);
+                case LayerForm::Next:
+                case LayerForm::NextProj:
+                case LayerForm::NextRebuild:
+                    f.form = L.form == LayerForm::Next ? ConvForm::Next : L.form == LayerForm::NextProj ? ConvForm::NextProj : ConvForm::NextRebuild;
+                    f.next = {prm(L.next.w), fprm(L.next.bias), prm(L.next.scale), prm(L.next.shift), slot_ptr(L.out2_slot), L.c2};
+                    if (f.form != ConvForm::Next)
+                        f.psc = {slot_ptr(L.psc_slot), prm(L.psc.w), fprm(L.psc.bias), prm(L.psc.scale), prm(L.psc.shift)};
+                    if (f.form == ConvForm::NextRebuild) {
+                        f.rb.t2_prev = slot_ptr(L.reb_slot); f.rb.w3_prev = prm(L.reb.w); f.rb.bias3_prev = fprm(L.reb.bias);
+                    }
+                    // block1 without its residual stream in HBM: metro_forward_upto stopping here (dump) stores the sum in full, on the
+                    // classic kernel
+                    f.rb.out_mode = dump ? 0 : L.out_mode;
+                    f.rb.classic = dump ? 1 : 0;
+                    if (f.rb.out_mode == 2) { f.rb.out_sub = slot_ptr(L.sub_slot); f.rb.sub_off = L.sub_off; f.rb.h_sub = f.rb.w_sub = L.sub_side; }
+                    return launch_conv_f16_dma(cd, in, w, bias, nullptr, nullptr, slot_ptr(L.res_slot), out, stream, f);
             }
-            if (L.reb_w >= 0 || L.out_mode != 0) {
-                // only the fused conv3 + next-conv1 launch above reads the rebuild data; any other path would drop the shortcut
-                set_error("internal: layer %d carries block1 rebuild data (reb_w %d, out_mode %d) but no fused next-conv1 launch", li, L.reb_w, L.out_mode);
-                return METRO_ERR_STATE;
-            }
-            if (p->fast && L.p1_w >= 0) {
-                ConvPre1 p1;
-                p1.w1 = prm(L.p1_w); p1.bias1 = static_cast<const float*>(prm(L.p1_bias));
-                p1.pro_scale = prm(L.p1_scale); p1.pro_shift = prm(L.p1_shift);
-                p1.t1_dump = dump ? slot_ptr(S_T1) : nullptr;        // conv1's output exists in LDS only; layer dumps get a copy
-                return launch_conv3x3_c64(cd, slot_ptr(L.in_slot), prm(L.p_w), static_cast<const float*>(prm(L.p_bias)),
-                                          slot_ptr(L.out_slot), stream, &p1);
-            }
-            if (p->fast)
-                return launch_conv_f16(cd, slot_ptr(L.in_slot), prm(L.p_w), static_cast<const float*>(prm(L.p_bias)),
-                                       prm(L.p_scale), prm(L.p_shift), slot_ptr(L.res_slot), slot_ptr(L.out_slot), stream);
-            if (p->spec.precision == METRO_PREC_F32M)
-                return launch_conv_f32m(cd, slot_ptr(L.in_slot), static_cast<const float*>(prm(L.p_w)), static_cast<const float*>(prm(L.p_bias)),
-                                        static_cast<const float*>(prm(L.p_scale)), static_cast<const float*>(prm(L.p_shift)),
-                                        slot_ptr(L.res_slot), slot_ptr(L.out_slot), stream);
-            return launch_conv_f64acc(cd, slot_ptr(L.in_slot), static_cast<const double*>(prm(L.p_w)),
-                                      static_cast<const double*>(prm(L.p_bias)), static_cast<const double*>(prm(L.p_scale)),
-                                      static_cast<const double*>(prm(L.p_shift)), slot_ptr(L.res_slot), slot_ptr(L.out_slot), stream);
+            break;
         }
         case LK_SOFTARGMAX: {
             if (poses == nullptr) { set_error("metro_forward: poses_out is NULL"); return METRO_ERR_INVALID_ARG; }
             const SoftArgmaxArgs a = make_softargmax_args(p->spec, n);
-            if (L.head_fused)
+            if (L.form == LayerForm::Head)
                 return launch_softargmax_finalize(static_cast<const float*>(slot_ptr(S_PART)), a,
                                                   head_f16_records(n, L.head_c_in, a.depth * a.n_joints_head, a.side), poses, stream, nullptr,
                                                   static_cast<int32_t*>(slot_ptr(S_STATUS)));
@@ -1026,16 +1003,13 @@ int metro_conv_f16_pair(const MetroConvDesc* d, const void* d_in, const void* d_
                         void* d_out2, void* stream) {
     int st = validate_conv_desc(d);
     if (st) return st;
-    METRO_CHECK_ARG(d->in_dtype == METRO_F16 && d->out_dtype == METRO_F16, "conv_f16_pair: fp16 tensors only");
-    METRO_CHECK_ARG(d->kh == 1 && d->kw == 1 && d->stride == 1 && d->has_prologue && !d->has_residual && !d->relu,
-                    "conv_f16_pair: 1x1 stride-1 convolution with prologue, without residual/ReLU on the first output");
     METRO_CHECK_ARG(d_in && d_w && d_bias && d_out && d_out2 && d_pro_scale && d_pro_shift, "conv_f16_pair: NULL tensor pointer");
-    METRO_CHECK_ARG(split > 0 && split < d->c_out && split % 256 == 0 && (d->c_out - split) % 8 == 0 && d->c_in % 64 == 0,
-                    "conv_f16_pair: split %d of c_out %d (split %% 256, rest %% 8, c_in %% 64 required)", split, d->c_out);
-    ConvSplit sp;
-    sp.split = split; sp.c_out2 = d->c_out - split; sp.relu2 = 1; sp.out2 = d_out2;
-    return launch_conv_f16_dma(*d, d_in, d_w, d_bias, d_pro_scale, d_pro_shift, nullptr, d_out,
-                               static_cast<hipStream_t>(stream), &sp);
+    ConvFused f;
+    f.form = ConvForm::Pair;
+    f.pair = {split, d->c_out - split, 1, d_out2};
+    METRO_CHECK_ARG(conv_form_supported(*d, f), "conv_f16_pair: fp16 1x1 stride-1 convolution with prologue, without residual / ReLU on the "
+                    "first output, c_in %% 64; split %d of c_out %d (split %% 256, rest %% 8)", split, d->c_out);
+    return launch_conv_f16_dma(*d, d_in, d_w, d_bias, d_pro_scale, d_pro_shift, nullptr, d_out, static_cast<hipStream_t>(stream), f);
 }
 
 int metro_conv_f16_next(const MetroConvDesc* d, const void* d_in, const void* d_w, const float* d_bias,
@@ -1046,12 +1020,12 @@ int metro_conv_f16_next(const MetroConvDesc* d, const void* d_in, const void* d_
     METRO_CHECK_ARG(d_in && d_w && d_bias && d_out && d_w2 && d_bias2 && d_scale2 && d_shift2 && d_out2,
                     "conv_f16_next: NULL tensor pointer");
     METRO_CHECK_ARG(!d->has_residual || d_residual, "conv_f16_next: residual tensor missing");
-    METRO_CHECK_ARG(conv_f16_fuse2_supported(*d, c2) || (conv_pw64_supported(*d, 2) && c2 == (d->c_in == 128 ? 128 : 64)),
+    ConvFused f;
+    f.form = ConvForm::Next;
+    f.next = {d_w2, d_bias2, d_scale2, d_shift2, d_out2, c2};
+    METRO_CHECK_ARG(conv_form_supported(*d, f),
                     "conv_f16_next: built for 1x1 stride-1 64 -> 256 with c2 = 64 (block1) and 128 -> 512 with c2 = 128 (block2), fp16");
-    ConvFuse2 f2;
-    f2.w2 = d_w2; f2.bias2 = d_bias2; f2.scale2 = d_scale2; f2.shift2 = d_shift2; f2.out2 = d_out2; f2.c2 = c2;
-    return launch_conv_f16_dma(*d, d_in, d_w, d_bias, nullptr, nullptr, d_residual, d_out,
-                               static_cast<hipStream_t>(stream), nullptr, &f2);
+    return launch_conv_f16_dma(*d, d_in, d_w, d_bias, nullptr, nullptr, d_residual, d_out, static_cast<hipStream_t>(stream), f);
 }
 
 int metro_conv_f16_conv1_conv2(const MetroConvDesc* d, const void* d_x, const void* d_w1, const float* d_bias1, const void* d_pro_scale,
@@ -1074,16 +1048,14 @@ int metro_conv_f16_next_proj(const MetroConvDesc* d, const void* d_in, const voi
     if (st) return st;
     METRO_CHECK_ARG(d_in && d_w && d_bias && d_x && d_w_sc && d_bias_sc && d_pro_scale && d_pro_shift && d_w2 && d_bias2 &&
                         d_scale2 && d_shift2 && d_out2, "conv_f16_next_proj: NULL tensor pointer");
-    METRO_CHECK_ARG(conv_pw64_supported(*d, 3) && c2 == 64, "conv_f16_next_proj: built for 1x1 stride-1 64 -> 256 without prologue / residual, "
+    ConvFused f;
+    f.form = ConvForm::NextProj;
+    f.next = {d_w2, d_bias2, d_scale2, d_shift2, d_out2, c2};
+    f.psc = {d_x, d_w_sc, d_bias_sc, d_pro_scale, d_pro_shift};
+    f.rb.out_mode = d_out == nullptr ? 1 : 0;          // d_out == NULL: the sum stays on chip (it only feeds the second GEMM)
+    METRO_CHECK_ARG(conv_form_supported(*d, f), "conv_f16_next_proj: built for 1x1 stride-1 64 -> 256 without prologue / residual, "
                     "c2 = 64 (block1/unit_1), fp16");
-    ConvFuse2 f2;
-    f2.w2 = d_w2; f2.bias2 = d_bias2; f2.scale2 = d_scale2; f2.shift2 = d_shift2; f2.out2 = d_out2; f2.c2 = c2;
-    ConvProjSc ps;
-    ps.x = d_x; ps.w_sc = d_w_sc; ps.bias_sc = d_bias_sc; ps.pro_scale = d_pro_scale; ps.pro_shift = d_pro_shift;
-    ConvRebuild rb;
-    rb.out_mode = d_out == nullptr ? 1 : 0;          // d_out == NULL: the sum stays on chip (it only feeds the second GEMM)
-    return launch_conv_f16_dma(*d, d_in, d_w, d_bias, nullptr, nullptr, nullptr, d_out, static_cast<hipStream_t>(stream), nullptr, &f2, &ps,
-                               d_out == nullptr ? &rb : nullptr);
+    return launch_conv_f16_dma(*d, d_in, d_w, d_bias, nullptr, nullptr, nullptr, d_out, static_cast<hipStream_t>(stream), f);
 }
 
 int metro_conv_f16_next_rebuild(const MetroConvDesc* d, const void* d_in, const void* d_w, const float* d_bias, const void* d_x,
@@ -1098,19 +1070,19 @@ int metro_conv_f16_next_rebuild(const MetroConvDesc* d, const void* d_in, const 
     METRO_CHECK_ARG((d_out != nullptr) != (d_out_sub != nullptr), "conv_f16_next_rebuild: exactly one of d_out (the whole sum) and d_out_sub (its "
                     "sub-sampled compact copy) must be given");
     METRO_CHECK_ARG(sub_off == 0 || sub_off == 1, "conv_f16_next_rebuild: sub_off %d must be 0 or 1", sub_off);
-    METRO_CHECK_ARG(conv_pw64_supported(*d, 4) && c2 == 64, "conv_f16_next_rebuild: built for 1x1 stride-1 64 -> 256 without prologue / residual on maps "
-                    "whose width is a power of two >= 16 and whose pixel count is a multiple of 64, c2 = 64 (block1/unit_2), fp16");
-    ConvFuse2 f2;
-    f2.w2 = d_w2; f2.bias2 = d_bias2; f2.scale2 = d_scale2; f2.shift2 = d_shift2; f2.out2 = d_out2; f2.c2 = c2;
-    ConvProjSc ps;
-    ps.x = d_x; ps.w_sc = d_w_sc; ps.bias_sc = d_bias_sc; ps.pro_scale = d_pro_scale; ps.pro_shift = d_pro_shift;
-    ConvRebuild rb;
+    ConvFused f;
+    f.form = ConvForm::NextRebuild;
+    f.next = {d_w2, d_bias2, d_scale2, d_shift2, d_out2, c2};
+    f.psc = {d_x, d_w_sc, d_bias_sc, d_pro_scale, d_pro_shift};
+    ConvRebuild& rb = f.rb;
     rb.t2_prev = d_t2_prev; rb.w3_prev = d_w3_prev; rb.bias3_prev = d_bias3_prev;
     if (d_out_sub != nullptr) {
         rb.out_mode = 2; rb.out_sub = d_out_sub; rb.sub_off = sub_off;
         rb.h_sub = (d->h_out - sub_off + 1) / 2; rb.w_sub = (d->w_out - sub_off + 1) / 2;
     }
-    return launch_conv_f16_dma(*d, d_in, d_w, d_bias, nullptr, nullptr, nullptr, d_out, static_cast<hipStream_t>(stream), nullptr, &f2, &ps, &rb);
+    METRO_CHECK_ARG(conv_form_supported(*d, f), "conv_f16_next_rebuild: built for 1x1 stride-1 64 -> 256 without prologue / residual on maps "
+                    "whose width is a power of two >= 16 and whose pixel count is a multiple of 64, c2 = 64 (block1/unit_2), fp16");
+    return launch_conv_f16_dma(*d, d_in, d_w, d_bias, nullptr, nullptr, nullptr, d_out, static_cast<hipStream_t>(stream), f);
 }
 
 int metro_conv_b1_form(int32_t classic) {

@@ -267,3 +267,98 @@ def test_gpu_contract_sweep_dispatches_to_its_families(dry):
         assert st == 0 and kid.startswith(case.family), (case.name, st, kid, dry.metro_last_error())
         fit = _slab_fits(case.desc(), kid)
         assert fit is None or fit[0] <= fit[1], (case.name, kid, fit)
+
+
+# ---- the fused entry points by dry runs ---------------------------------------------------------------------------------
+# metro_conv_f16_pair / _next / _next_proj / _next_rebuild / _gemm4w: each accepted form reaches its kernel, and a layer one
+# step off a shape rule (pair split, c2, map width of the rebuilt residual, sub_off, whole gemm4w tiles) is refused with its
+# status and without a launch
+
+def _fused(lib, entry, d, split=0, c2=64, out=True, out_sub=False, sub_off=0, classic=False):
+    """(status, kernel id) of one fused entry point on `d` without launching; classic = under metro_conv_b1_form(1)."""
+    p, o = _P, (_P if out else None)
+    lib.metro_kernel_notes(2)
+    lib.metro_conv_b1_form(int(classic))
+    try:
+        if entry == 'pair':
+            st = lib.metro_conv_f16_pair(C.byref(d), p, p, p, p, p, o, split, p, None)
+        elif entry == 'next':
+            st = lib.metro_conv_f16_next(C.byref(d), p, p, p, p, o, p, p, p, p, p, c2, None)
+        elif entry == 'next_proj':
+            st = lib.metro_conv_f16_next_proj(C.byref(d), p, p, p, p, p, p, p, p, o, p, p, p, p, p, c2, None)
+        elif entry == 'next_rebuild':
+            st = lib.metro_conv_f16_next_rebuild(C.byref(d), p, p, p, p, p, p, p, p, p, p, p, o, _P if out_sub else None, sub_off,
+                                                 p, p, p, p, p, c2, None)
+        else:
+            st = lib.metro_conv_f16_gemm4w(C.byref(d), p, p, p, p, p, p, o, split, _P if split else None, None)
+    finally:
+        lib.metro_conv_b1_form(0)
+    return st, lib.metro_last_kernel_id().decode()
+
+
+def _pw(n, side, c_in, c_out, w=None, **kw):
+    """A 1x1 stride-1 fp16 layer on an n x side x w map."""
+    return H.conv_desc(n, side, c_in, side, c_out, 1, w_in=w, w_out=w, in_dtype=F16, **kw)
+
+
+_RES = dict(residual=True, res_h=16)
+
+# (name, entry, desc, call arguments, kernel id)
+FUSED_ACCEPTED = [
+    ('pair block1', 'pair', _pw(2, 16, 64, 320, prologue=True), dict(split=256), 'conv_pw64<k64,wm4,pro,pair>'),
+    ('pair block2', 'pair', _pw(2, 16, 256, 640, prologue=True), dict(split=512), 'conv_pw64<k256,wm8,cb512,pro,pair>'),
+    ('pair block2 classic', 'pair', _pw(2, 16, 256, 640, prologue=True), dict(split=512, classic=True),
+     'conv_igemm_f16_dma<128x128,bk64,s2,pro>+pair'),
+    ('pair block3', 'pair', _pw(2, 16, 512, 1280, prologue=True), dict(split=1024), 'conv_igemm_f16_dma<128x128,bk64,s2,pro>+pair'),
+    ('pair block4 batch 128', 'pair', _pw(128, 8, 1024, 2560, prologue=True), dict(split=2048), 'conv_gemm4w<256x256,pro>+pair'),
+    ('pair 256 + 72', 'pair', _pw(2, 16, 64, 328, prologue=True), dict(split=256), 'conv_igemm_f16_dma<128x128,bk64,s1,pro>+pair'),
+    ('next block1', 'next', _pw(2, 16, 64, 256, **_RES), dict(c2=64), 'conv_pw64<k64,wm4,res,next>'),
+    ('next block2', 'next', _pw(2, 16, 128, 512, **_RES), dict(c2=128), 'conv_pw64<k128,wm8,cb512,res,next>'),
+    ('next without residual', 'next', _pw(2, 16, 64, 256), dict(c2=64), 'conv_igemm_f16_fuse2<256x64>'),
+    ('next_proj', 'next_proj', _pw(2, 16, 64, 256), dict(), 'conv_pw64<k64,wm4,next,projsc>'),
+    ('next_proj on chip', 'next_proj', _pw(2, 16, 64, 256), dict(out=False), 'conv_b1_chain<projsc,noout>'),
+    ('next_proj on chip classic', 'next_proj', _pw(2, 16, 64, 256), dict(out=False, classic=True),
+     'conv_pw64<k64,wm4,next,projsc,noout>'),
+    ('next_proj on chip width 8', 'next_proj', _pw(2, 8, 64, 256), dict(out=False), 'conv_pw64<k64,wm4,next,projsc,noout>'),
+    ('next_rebuild', 'next_rebuild', _pw(2, 16, 64, 256), dict(), 'conv_b1_chain<rebuild>'),
+    ('next_rebuild sub', 'next_rebuild', _pw(2, 16, 64, 256), dict(out=False, out_sub=True), 'conv_b1_chain<rebuild,subout>'),
+    ('next_rebuild sub 1', 'next_rebuild', _pw(2, 16, 64, 256), dict(out=False, out_sub=True, sub_off=1), 'conv_b1_chain<rebuild,subout>'),
+    ('next_rebuild classic', 'next_rebuild', _pw(2, 16, 64, 256), dict(classic=True), 'conv_pw64<k64,wm4,next,projsc,rebuild>'),
+    ('next_rebuild sub classic', 'next_rebuild', _pw(2, 16, 64, 256), dict(out=False, out_sub=True, classic=True),
+     'conv_pw64<k64,wm4,next,projsc,rebuild,subout>'),
+    ('gemm4w', 'gemm4w', _pw(2, 16, 512, 256, prologue=True), dict(), 'conv_gemm4w<256x256,pro>'),
+    ('gemm4w pair', 'gemm4w', _pw(2, 16, 1024, 2560, prologue=True), dict(split=2048), 'conv_gemm4w<256x256,pro>+pair'),
+]
+
+# (name, entry, desc, call arguments, status): each one step off an accepted case above
+FUSED_REJECTED = [
+    ('pair split % 256', 'pair', _pw(2, 16, 64, 320, prologue=True), dict(split=100), -1),
+    ('pair second output % 8', 'pair', _pw(2, 16, 64, 324, prologue=True), dict(split=256), -1),
+    ('pair with residual', 'pair', _pw(2, 16, 64, 320, prologue=True, **_RES), dict(split=256), -1),
+    ('next block1 c2 128', 'next', _pw(2, 16, 64, 256, **_RES), dict(c2=128), -1),
+    ('next block2 c2 64', 'next', _pw(2, 16, 128, 512, **_RES), dict(c2=64), -1),
+    ('next c_out 128', 'next', _pw(2, 16, 64, 128, **_RES), dict(c2=64), -1),
+    ('next_proj c2 128', 'next_proj', _pw(2, 16, 64, 256), dict(c2=128), -1),
+    ('next_proj with residual', 'next_proj', _pw(2, 16, 64, 256, **_RES), dict(), -1),
+    ('next_rebuild width 24', 'next_rebuild', _pw(2, 16, 64, 256, w=24), dict(), -1),
+    ('next_rebuild width 8', 'next_rebuild', _pw(2, 8, 64, 256), dict(), -1),
+    ('next_rebuild c2 128', 'next_rebuild', _pw(2, 16, 64, 256), dict(c2=128), -1),
+    ('next_rebuild sub_off 2', 'next_rebuild', _pw(2, 16, 64, 256), dict(out=False, out_sub=True, sub_off=2), -1),
+    ('next_rebuild both outputs', 'next_rebuild', _pw(2, 16, 64, 256), dict(out_sub=True), -1),
+    ('next_rebuild no output', 'next_rebuild', _pw(2, 16, 64, 256), dict(out=False), -1),
+    ('gemm4w partial tile', 'gemm4w', _pw(1, 8, 512, 256), dict(), -2),
+    ('gemm4w pair second output % 256', 'gemm4w', _pw(2, 16, 1024, 2176, prologue=True), dict(split=2048), -2),
+]
+
+
+@pytest.mark.parametrize('name,entry,d,kw,kid', FUSED_ACCEPTED, ids=[c[0] for c in FUSED_ACCEPTED])
+def test_fused_entries_reach_their_kernels(dry, name, entry, d, kw, kid):
+    st, got = _fused(dry, entry, d, **kw)
+    assert (st, got) == (0, kid), (name, st, got, dry.metro_last_error())
+
+
+@pytest.mark.parametrize('name,entry,d,kw,status', FUSED_REJECTED, ids=[c[0] for c in FUSED_REJECTED])
+def test_fused_entries_reject_shapes_one_step_off(dry, name, entry, d, kw, status):
+    st, got = _fused(dry, entry, d, **kw)
+    assert (st, got) == (status, ''), (name, st, got)
+    assert dry.metro_last_error().decode(), name
