@@ -19,7 +19,7 @@ EXPERIMENTAL_SOURCES = [os.path.join('experimental', f) for f in ('conv_gemm8p.h
 EXPERIMENTAL_HEADERS = [os.path.join('experimental', 'metro_experimental.h')]
 PROBE_SRC = os.path.normpath(os.path.join(HERE, '..', 'tools', 'peak_probe.hip'))
 PROBE_LIB_PATH = os.path.normpath(os.path.join(HERE, '..', 'tools', 'libmetro_probe.so'))
-HEADERS = ['metro_common.h', os.path.join('..', '..', 'include', 'metro_hip.h')]
+HEADERS = ['metro_common.h', 'gfx950_prims.h', os.path.join('..', '..', 'include', 'metro_hip.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-x', 'hip', '-Wall',
          '-Wno-unused-function'] + os.environ.get('METRO_EXTRA_HIPCC_FLAGS', '').split()
 

@@ -24,16 +24,9 @@
 // shortcut + conv1 pair -> nothing; the shortcut moves into the conv3 launch, conv_pw64.hip PSC) and 1152 of its 2304
 // bytes per pixel.  Same arithmetic as the separate launches: one fp16 rounding per tensor (oracle/f16emu.py unit_conv1).
 #include "metro_common.h"
+#include "gfx950_prims.h"
 
 namespace metro {
-
-typedef _Float16 half_t;
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-__device__ __attribute__((aligned(16))) unsigned int g_zero_page_c64[4];   // zero-initialised
 
 namespace c64 {
 constexpr int C = 64, TN = 128, NW = 8, NT = 512;
@@ -51,17 +44,6 @@ constexpr int LDS_BYTES = OUT_OFF + TN * OUT_ROW;        // 157,952 B
 constexpr int STORES = TN * (C / 8) / NT;                // row-wise 16-byte stores per thread per tile: 2
 static_assert(LDS_BYTES <= 160 * 1024 && ZERO_OFF % 256 == 0, "LDS budget / zero-area alignment");
 }  // namespace c64
-
-typedef __attribute__((address_space(3))) void c64_lds_void_t;
-
-__device__ __forceinline__ void c64_dma16(const void* gsrc, unsigned lds_addr) {
-    asm volatile(
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %0, off"
-        :
-        : "v"(gsrc), "s"(lds_addr));
-}
 
 struct C64Args {
     const half_t* in;      // [m_total][64]
@@ -90,8 +72,8 @@ __global__ __launch_bounds__(c64::NT) void conv3x3_c64_kernel(C64Args a) {
     int t_end = t_begin + a.tiles_per_block;
     if (t_end > a.n_tiles) t_end = a.n_tiles;
     if (t_begin >= t_end) return;
-    const half_t* zero = reinterpret_cast<const half_t*>(g_zero_page_c64);
-    const unsigned smem_base = (unsigned)(size_t)(c64_lds_void_t*)smem;
+    const half_t* zero = reinterpret_cast<const half_t*>(g_zero_page);
+    const unsigned smem_base = lds_offset_of(smem);
     const int halo = a.w_map;                             // one map row above and below
     const int hw = a.h * a.w_map;
 
@@ -103,8 +85,8 @@ __global__ __launch_bounds__(c64::NT) void conv3x3_c64_kernel(C64Args a) {
     for (int i = 0; i < WI; ++i) {
         const int grp = i * NW + wave;                    // 72 groups of 8 rows: tap = grp / 8, cout rows (grp % 8) * 8 ..
         const int tap = grp >> 3, row = (grp & 7) * 8 + lrow;
-        const half_t* src = a.w + (size_t)row * (9 * C) + tap * C + ((lch ^ ((row >> 1) & 7)) * 8);
-        c64_dma16(src, __builtin_amdgcn_readfirstlane(smem_base + W_OFF + grp * 1024));
+        const half_t* src = a.w + (size_t)row * (9 * C) + tap * C + ((lch ^ swz<64>(row)) * 8);
+        dma16(src, __builtin_amdgcn_readfirstlane(smem_base + W_OFF + grp * 1024));
     }
     // ---- slab DMA of a tile: flattened pixel rows [m0 - halo, m0 + TN + halo) (zero page outside the tensor) ----
     auto issue_slab = [&](int tile, int buf) {
@@ -114,15 +96,15 @@ __global__ __launch_bounds__(c64::NT) void conv3x3_c64_kernel(C64Args a) {
             const int srow = (i * NW + wave) * 8 + lrow;
             const int g = m0 - halo + srow;
             const bool ok = g >= 0 && g < a.m_total && srow < TN + 2 * halo;
-            const half_t* src = ok ? a.in + (size_t)g * C + ((lch ^ ((srow >> 1) & 7)) * 8) : zero;
-            c64_dma16(src, __builtin_amdgcn_readfirstlane(smem_base + SLAB_OFF + buf * SLAB_BYTES + (i * NW + wave) * 1024));
+            const half_t* src = ok ? a.in + (size_t)g * C + ((lch ^ swz<64>(srow)) * 8) : zero;
+            dma16(src, __builtin_amdgcn_readfirstlane(smem_base + SLAB_OFF + buf * SLAB_BYTES + (i * NW + wave) * 1024));
         }
     };
     issue_slab(t_begin, 0);
 
     // per-lane A (weight) fragment base: row * 128 + swizzle bits; tap adds 8192, k step kk is an XOR with kk << 5
     const int arow = wm * 32 + frag_row;
-    const int a_base = W_OFF + arow * 128 + ((frag_half ^ ((arow >> 1) & 7)) << 4);
+    const int a_base = W_OFF + arow * 128 + ((frag_half ^ swz<64>(arow)) << 4);
     float bias_v[4][4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -152,7 +134,7 @@ __global__ __launch_bounds__(c64::NT) void conv3x3_c64_kernel(C64Args a) {
             pb1[kk] = *reinterpret_cast<const half8_t*>(a.pro_shift + kk * 16 + frag_half * 8);
         }
     }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");     // weights + first slab + zero area
+    wait_vm_and_barrier<0>();     // weights + first slab + zero area
 
     for (int t = t_begin; t < t_end; ++t) {
         const int buf = (t - t_begin) & 1;
@@ -167,7 +149,7 @@ __global__ __launch_bounds__(c64::NT) void conv3x3_c64_kernel(C64Args a) {
             //      its 64 output channels are written, nobody else touches these rows before the barrier below ----
             char* sp = smem + SLAB_OFF + buf * SLAB_BYTES;
             const int srow = wave * 32 + frag_row;
-            const int r_base = srow * 128 + ((frag_half ^ ((srow >> 1) & 7)) << 4);
+            const int r_base = srow * 128 + ((frag_half ^ swz<64>(srow)) << 4);
             floatx16 a1[2];
 #pragma unroll
             for (int e = 0; e < 16; ++e) { a1[0][e] = 0.f; a1[1][e] = 0.f; }
@@ -187,11 +169,11 @@ __global__ __launch_bounds__(c64::NT) void conv3x3_c64_kernel(C64Args a) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) hv[e] = (half_t)fmaxf(a1[i][4 * q + e] + bias1_v[i][q][e], 0.f);
                     // channels i*32 + 8q + 4 half ..+3 = 16-byte chunk (4i + q), byte 8 * half inside it
-                    *reinterpret_cast<half4_t*>(sp + srow * 128 + ((((4 * i + q) ^ ((srow >> 1) & 7)) << 4) | (frag_half << 3))) = hv;
+                    *reinterpret_cast<half4_t*>(sp + srow * 128 + ((((4 * i + q) ^ swz<64>(srow)) << 4) | (frag_half << 3))) = hv;
                     if (a.t1_dump != nullptr && srow >= halo && srow < halo + TN)      // the tile's own rows, once
                         *reinterpret_cast<half4_t*>(a.t1_dump + (size_t)(t * TN + srow - halo) * C + i * 32 + 8 * q + 4 * frag_half) = hv;
                 }
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            wait_lgkm_and_barrier();
         }
         // ---- per-lane tap rows of this tile (slab row, or the zero area for taps outside the image) ----
         const int m0 = t * TN;
@@ -207,7 +189,7 @@ __global__ __launch_bounds__(c64::NT) void conv3x3_c64_kernel(C64Args a) {
             const int dr = tap / 3 - 1, ds = tap % 3 - 1;
             const bool ok = (unsigned)(py + dr) < (unsigned)a.h && (unsigned)(px + ds) < (unsigned)a.w_map;
             const int srow = halo + tl + dr * a.w_map + ds;
-            const int b_base = ok ? sl + srow * 128 + ((frag_half ^ ((srow >> 1) & 7)) << 4) : ZERO_OFF;
+            const int b_base = ok ? sl + srow * 128 + ((frag_half ^ swz<64>(srow)) << 4) : ZERO_OFF;
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
                 const half8_t af = *reinterpret_cast<const half8_t*>(smem + tap * 8192 + (a_base ^ (kk << 5)));
@@ -228,7 +210,7 @@ __global__ __launch_bounds__(c64::NT) void conv3x3_c64_kernel(C64Args a) {
             }
             *reinterpret_cast<half4_t*>(ol + tl * OUT_ROW + (wm * 32 + 8 * q + 4 * frag_half) * 2) = hv;
         }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        wait_lgkm_and_barrier();
 #pragma unroll
         for (int r = 0; r < STORES; ++r) {
             const int idx = tid + r * NT;

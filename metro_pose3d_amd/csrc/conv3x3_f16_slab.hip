@@ -22,33 +22,9 @@
 #include <type_traits>
 
 #include "metro_common.h"
+#include "gfx950_prims.h"
 
 namespace metro {
-
-typedef _Float16 half_t;
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-// (no relocatable device code: every translation unit keeps its own zero page)
-__device__ __attribute__((aligned(16))) unsigned int g_zero_page_slab[4];
-
-typedef __attribute__((address_space(3))) void lds_void3_t;
-
-__device__ __forceinline__ void slab_dma16(const void* gsrc, unsigned lds_addr) {
-    asm volatile(
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %0, off"
-        :
-        : "v"(gsrc), "s"(lds_addr));
-}
-
-template <int N>
-__device__ __forceinline__ void slab_wait_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 // WM: 32-row cout tiles per wave (TM = WAVES_M*WM*32); pixels: TN = WAVES_N * WN * 32 (256 or 512)
 // TPS: taps per K step.  1 = one (chunk, tap) per barrier; 3 = one kernel ROW (3 taps) per barrier for the
@@ -90,19 +66,8 @@ struct SlabCfg {
     static_assert(SLAB_ROWS % (RPI * NW) == 0 && TM % (RPI * NW) == 0, "loader mismatch");
     static_assert(W_STAGES >= 3 && W_STAGES - 2 <= NSTEPS - 1, "ring depth");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-    // swizzle of the 16-byte chunk index inside a row (conflict-free ds_read_b128 for 32 consecutive rows at any
-    // alignment: the 16 rows one LDS cycle serves cover the 256-byte bank span exactly once)
-    __device__ static __forceinline__ int swz(int row) { return KC == 64 ? (row >> 1) & 7 : (row >> 2) & 3; }
     // the epilogue tile overlays slabs + zero area + weight ring (all idle by then)
 };
-
-template <int I, int N, class F>
-__device__ __forceinline__ void slab_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        slab_static_for<I + 1, N>(f);
-    }
-}
 
 // One tile: cout [n0, n0 + TM) of pixels [m0, m0 + TN).
 template <class Cfg>
@@ -137,8 +102,8 @@ __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __res
         const int sy = sub / sgd, sx = sub - sy * sgd;
         return ((size_t)img * a.h_out + (vy * sgd + sy)) * a.w_out + (vx * sgd + sx);
     };
-    const half_t* zero = reinterpret_cast<const half_t*>(g_zero_page_slab);
-    const unsigned smem_base = (unsigned)(size_t)(lds_void3_t*)smem;
+    const half_t* zero = reinterpret_cast<const half_t*>(g_zero_page);
+    const unsigned smem_base = lds_offset_of(smem);
 
     // zero area (read by taps that fall outside the image)
     if (tid < 16) reinterpret_cast<uint4*>(smem + Cfg::ZERO_OFF)[tid] = make_uint4(0, 0, 0, 0);
@@ -157,7 +122,7 @@ __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __res
         // rows past the tile's own halo (a configuration's slab is sized for the largest halo it serves) come from the zero page
         svalid[i] = g >= 0 && g < a.m_total && srow < Cfg::TN + 2 * halo;
         ssrc[i] = in + pixel_of(svalid[i] ? g : 0) * c_in;
-        skoff[i] = (lch ^ Cfg::swz(srow)) * 8;
+        skoff[i] = (lch ^ swz<Cfg::KC>(srow)) * 8;
     }
     const half_t* wsrc[Cfg::WI];
     int wkoff[Cfg::WI];
@@ -168,7 +133,7 @@ __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __res
         const int co = n0 + row;
         wvalid[i] = co < a.c_out;
         wsrc[i] = w + (size_t)(wvalid[i] ? co : 0) * k_total;
-        wkoff[i] = (lch ^ Cfg::swz(row)) * 8;
+        wkoff[i] = (lch ^ swz<Cfg::KC>(row)) * 8;
     }
 
     // running DMA pointers (c_in % 64 == 0 is required by the launcher): the slab advances KC
@@ -187,7 +152,7 @@ __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __res
 #pragma unroll
         for (int i = 0; i < Cfg::SI; ++i) {
             if (i % Cfg::NKK != part) continue;
-            slab_dma16(sptr[i], base + i * NW * 1024);
+            dma16(sptr[i], base + i * NW * 1024);
             sptr[i] += svalid[i] ? Cfg::KC : 0;
         }
         (void)last_part;
@@ -200,7 +165,7 @@ __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __res
 #pragma unroll
         for (int i = 0; i < Cfg::WI; ++i) {
             if (i % Cfg::NKK != part) continue;
-            slab_dma16(wptr[i] + (wvalid[i] ? tt * w_tap_inc : 0), base + i * NW * 1024);
+            dma16(wptr[i] + (wvalid[i] ? tt * w_tap_inc : 0), base + i * NW * 1024);
             if (tt == Cfg::TPS - 1)
                 wptr[i] += wvalid[i] ? (t_issue + Cfg::TPS == 9 ? w_chunk_inc + (Cfg::TPS - 1) * w_tap_inc : Cfg::TPS * w_tap_inc) : 0;
         }
@@ -237,7 +202,7 @@ __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __res
 #pragma unroll
     for (int i = 0; i < Cfg::WM; ++i) {
         const int row = (wave_m * Cfg::WM + i) * 32 + frag_row;
-        arow[i] = row * Cfg::ROW_BYTES + ((frag_half ^ Cfg::swz(row)) << 4);
+        arow[i] = row * Cfg::ROW_BYTES + ((frag_half ^ swz<Cfg::KC>(row)) << 4);
     }
 
     floatx16 acc[Cfg::WM][Cfg::WN];
@@ -278,7 +243,7 @@ __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __res
                 bo = bbase[j] + toff;
                 ok = (bmask[j] >> TAP) & 1u;
             }
-            pb[j] = ok ? sl + bo + ((frag_half ^ Cfg::swz(bo / Cfg::ROW_BYTES)) << 4) : (unsigned)Cfg::ZERO_OFF;
+            pb[j] = ok ? sl + bo + ((frag_half ^ swz<Cfg::KC>(bo / Cfg::ROW_BYTES)) << 4) : (unsigned)Cfg::ZERO_OFF;
         }
     };
 
@@ -298,7 +263,7 @@ __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __res
     // for the 3-deep ring (9 taps = 3 turns), a rotating scalar for deeper ones.
     auto step = [&](auto tap_c, auto issue_slab_c, auto issue_w_c, auto wait_c, int slab_buf, int wslot) {
         constexpr int TAP0 = decltype(tap_c)::value;             // first tap of the step
-        slab_wait_barrier<decltype(wait_c)::value>();
+        wait_vm_and_barrier<decltype(wait_c)::value>();
         const int islot = wslot == 0 ? WS - 1 : wslot - 1;     // slot of step q+WS-1 == slot of step q-1
 #pragma unroll
         for (int tt = 0; tt < Cfg::TPS; ++tt) {
@@ -324,7 +289,7 @@ __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __res
         }
     };
     auto chunk_main = [&](int slab_buf) {       // not the last chunk: slab(c+1) during the first step, W always
-        slab_static_for<0, NSTEPS>([&](auto jc) {
+        static_for<NSTEPS>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             constexpr int wait = (WS - 2) * WSI + ((j >= 1 && j <= WS - 2) ? Cfg::SI : 0);
             step(std::integral_constant<int, j * Cfg::TPS>{}, std::integral_constant<bool, j == 0>{}, std::true_type{},
@@ -333,7 +298,7 @@ __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __res
         advance_ring();
     };
     auto chunk_last = [&](int slab_buf) {       // last chunk: no slab, W stops WS-1 steps before the end
-        slab_static_for<0, NSTEPS>([&](auto jc) {
+        static_for<NSTEPS>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             constexpr int left = NSTEPS - 1 - j;
             constexpr int wait = (left < WS - 2 ? left : WS - 2) * WSI;

@@ -24,14 +24,9 @@
 // Arithmetic (MFMA shapes, k order, fp16 rounding points) is conv_pw64_kernel's: the two forms give the same bits
 // (tests/test_kernel_coverage.py compares them); metro_forward_upto stopping at such a layer runs the classic form.
 #include "metro_common.h"
+#include "gfx950_prims.h"
 
 namespace metro {
-
-typedef _Float16 half_t;
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 namespace b1 {
 constexpr int NPROD = 8, NCONS = 4, NT = 64 * (NPROD + NCONS), TN = 64, K = 64, CB = 256, C2 = 64, NBUF = 3;
@@ -78,49 +73,13 @@ struct B1Args {
     int h_out, w_out, lw_out, sub_off, h_sub, w_sub;
 };
 
-__device__ __forceinline__ int b1_swz(int row) { return (row >> 1) & 7; }
-__device__ __forceinline__ void b1_dma16(const void* gsrc, unsigned lds_addr) {
-    asm volatile(
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %0, off"
-        :
-        : "v"(gsrc), "s"(lds_addr));
-}
-template <int N>
-__device__ __forceinline__ void b1_wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// fp16(a + bias) for four accumulators as two v_cvt_pk_f16_f32 (round to nearest even, like the (half_t) casts of conv_pw64.hip).
-// Written out because the launch is INSTRUCTION-ISSUE bound (SQ counters: ~3 200 wave instructions per 64-pixel tile, the SIMDs
-// issuing 70 % of the time, matrix pipe 32 % busy): hipcc's SLP pass turned the element-wise form into v_pk_add_f32 on shuffled
-// register pairs + single v_cvt_f16_f32 + v_pack_b32_f16 / v_alignbit_b32 -- 313 instructions per producer tile instead of ~200.
-typedef unsigned int b1_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ half4_t b1_cvt4(float a0, float a1, float a2, float a3) {
-    b1_u32x2 r;
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r.x) : "v"(a0), "v"(a1));
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r.y) : "v"(a2), "v"(a3));
-    return __builtin_bit_cast(half4_t, r);
-}
-typedef float b1_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ half4_t b1_bias_cvt(const floatx16& acc, int q, const floatx4& bv) {
-    // two v_pk_add_f32 on the accumulator's own (even-aligned) register pairs, two v_cvt_pk_f16_f32: 4 issue slots per 4 outputs
-    b1_f32x2 lo = {acc[4 * q], acc[4 * q + 1]}, hi = {acc[4 * q + 2], acc[4 * q + 3]};
-    const b1_f32x2 blo = {bv[0], bv[1]}, bhi = {bv[2], bv[3]};
-    asm("v_pk_add_f32 %0, %1, %2" : "=v"(lo) : "v"(lo), "v"(blo));
-    asm("v_pk_add_f32 %0, %1, %2" : "=v"(hi) : "v"(hi), "v"(bhi));
-    return b1_cvt4(lo.x, lo.y, hi.x, hi.y);
-}
-__device__ __forceinline__ void b1_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 template <bool REB, int OUTM>
 __global__ __launch_bounds__(b1::NT) void conv_b1_chain_kernel(B1Args a) {
     using namespace b1;
     using L = Lay<REB>;
     constexpr int NIN = L::NIN;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef __attribute__((address_space(3))) void lds_void_t;
-    const unsigned smem_base = (unsigned)(size_t)(lds_void_t*)smem;
+    const unsigned smem_base = lds_offset_of(smem);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -178,22 +137,22 @@ __global__ __launch_bounds__(b1::NT) void conv_b1_chain_kernel(B1Args a) {
         }
         // an input tile = 8 LDS-DMA instructions of 8 rows x 128 B: producer w issues instruction w of every input
         const int xrow = wave * 8 + (lane >> 3);
-        const int xoff = xrow * K + (((lane & 7) ^ b1_swz(xrow)) * 8);
+        const int xoff = xrow * K + (((lane & 7) ^ swz<64>(xrow)) * 8);
         auto issue_tile = [&](int tile, int slot) {           // whole tiles only (the launcher checks h * w % 64 == 0): no zero page
             const size_t m0 = (size_t)tile * TN;
             const unsigned dst = smem_base + L::X_OFF + slot * NIN * X_BYTES + wave * 1024;
-            b1_dma16(a.in + m0 * K + xoff, __builtin_amdgcn_readfirstlane(dst));
-            b1_dma16(a.x_sc + m0 * K + xoff, __builtin_amdgcn_readfirstlane(dst + X_BYTES));
-            if constexpr (REB) b1_dma16(a.in_b + m0 * K + xoff, __builtin_amdgcn_readfirstlane(dst + 2 * X_BYTES));
+            dma16(a.in + m0 * K + xoff, __builtin_amdgcn_readfirstlane(dst));
+            dma16(a.x_sc + m0 * K + xoff, __builtin_amdgcn_readfirstlane(dst + X_BYTES));
+            if constexpr (REB) dma16(a.in_b + m0 * K + xoff, __builtin_amdgcn_readfirstlane(dst + 2 * X_BYTES));
         };
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");     // parameters in LDS, weights in registers
+        wait_vm_and_barrier<0>();     // parameters in LDS, weights in registers
         // The block's pre-activation (resnet_v2.py:119) is applied to the x0 tile ONCE, in place, by the wave whose LDS-DMA
         // brought the rows in (lane l's 16 bytes: row 8 w + (l >> 3), logical chunk (l & 7) ^ swizzle), right behind its own
         // vmcnt wait and in front of the tile's barrier -- not by every producer on every fragment it reads (eight waves repeating
         // the same 64 packed operations per tile: a quarter of the launch's VALU work, which is what bounds it).
         half8_t pre_s, pre_b;
         {
-            const int ch = ((lane & 7) ^ b1_swz(xrow)) * 8;
+            const int ch = ((lane & 7) ^ swz<64>(xrow)) * 8;
             pre_s = *reinterpret_cast<const half8_t*>(par + L::PRO + ch * 2);
             pre_b = *reinterpret_cast<const half8_t*>(par + L::PRO + 128 + ch * 2);
         }
@@ -208,21 +167,21 @@ __global__ __launch_bounds__(b1::NT) void conv_b1_chain_kernel(B1Args a) {
         const float* bias_b_l = reinterpret_cast<const float*>(par + L::BB);
         // fragment address of pixel half p (32 pixels), k step kk: row p * 32 + frag_row, chunk 2 kk + frag_half, swizzled (the swizzle
         // (row >> 1) & 7 does not see bit 5 of the row: the two halves differ by 32 rows x 128 B)
-        const int boff0 = frag_row * 128 + ((frag_half ^ b1_swz(frag_row)) << 4);
+        const int boff0 = frag_row * 128 + ((frag_half ^ swz<64>(frag_row)) << 4);
         int slot = 0;                                       // ring slot of tile j
         for (int j = 0; j <= T; ++j) {
             // tile j's operands have landed (this wave's share; the barrier makes it every producer's) and the consumers are done
             // with the LDS tile of j - 2, which tile j overwrites
             if (j < T) {
-                if (j + 1 < T) b1_wait_vm<NIN>();            // tile j + 1's requests may stay in flight
-                else b1_wait_vm<0>();
+                if (j + 1 < T) wait_vm<NIN>();               // tile j + 1's requests may stay in flight
+                else wait_vm<0>();
             }
             if (j < T) {
                 half8_t* mine = reinterpret_cast<half8_t*>(smem + L::X_OFF + (slot * NIN + 1) * X_BYTES + wave * 1024 + lane * 16);
                 const half8_t z = {};
                 *mine = __builtin_elementwise_max(*mine * pre_s + pre_b, z);
             }
-            b1_barrier();
+            wait_lgkm_and_barrier();
             if (j + 2 < T) issue_tile(t0 + (j + 2) * G, slot >= 1 ? slot - 1 : 2);       // slot of j + 2 = (slot + 2) % 3
             if (j < T) {
                 const char* xs = smem + L::X_OFF + slot * NIN * X_BYTES;
@@ -245,7 +204,7 @@ __global__ __launch_bounds__(b1::NT) void conv_b1_chain_kernel(B1Args a) {
                 for (int q = 0; q < 4; ++q) {
                     const floatx4 bv = *reinterpret_cast<const floatx4*>(bias_sc_l + wave * 32 + 8 * q + 4 * frag_half);
 #pragma unroll
-                    for (int p = 0; p < 2; ++p) xsum[p][q] = b1_bias_cvt(acc[p], q, bv);
+                    for (int p = 0; p < 2; ++p) xsum[p][q] = bias_cvt(acc[p], q, bv);
                 }
                 // ---- REB: + fp16(W3_prev . t2_prev + b3_prev): the previous unit's sum x_prev (its own fp16 Add, resnet_v2.py:138) ----
                 if constexpr (REB) {
@@ -264,7 +223,7 @@ __global__ __launch_bounds__(b1::NT) void conv_b1_chain_kernel(B1Args a) {
                     for (int q = 0; q < 4; ++q) {
                         const floatx4 bv = *reinterpret_cast<const floatx4*>(bias_b_l + wave * 32 + 8 * q + 4 * frag_half);
 #pragma unroll
-                        for (int p = 0; p < 2; ++p) xsum[p][q] = b1_bias_cvt(acc[p], q, bv) + xsum[p][q];
+                        for (int p = 0; p < 2; ++p) xsum[p][q] = bias_cvt(acc[p], q, bv) + xsum[p][q];
                     }
                 }
                 // ---- conv3 of this unit + its fp16 Add, into the LDS tile -------------------------------------------------------
@@ -284,7 +243,7 @@ __global__ __launch_bounds__(b1::NT) void conv_b1_chain_kernel(B1Args a) {
                     const int col = wave * 32 + 8 * q + 4 * frag_half;
 #pragma unroll
                     for (int p = 0; p < 2; ++p)
-                        *reinterpret_cast<half4_t*>(ot + (p * 32 + frag_row) * OUT_ROW + col * 2) = b1_bias_cvt(acc[p], q, b3_r[q]) + xsum[p][q];
+                        *reinterpret_cast<half4_t*>(ot + (p * 32 + frag_row) * OUT_ROW + col * 2) = bias_cvt(acc[p], q, b3_r[q]) + xsum[p][q];
                 }
             }
             slot = slot == 2 ? 0 : slot + 1;
@@ -292,7 +251,7 @@ __global__ __launch_bounds__(b1::NT) void conv_b1_chain_kernel(B1Args a) {
     } else {
         // W1 of the next unit over K = 256 as 16x16x32 A fragments: rows 0 .. 47 in registers, rows 48 .. 63 in LDS (above)
         half8_t w2r[3][8];
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");     // parameters and W1's stage in LDS
+        wait_vm_and_barrier<0>();     // parameters and W1's stage in LDS
         // (read before this wave's first loop barrier; the producers overwrite the stage behind their second one)
 #pragma unroll
         for (int mt = 0; mt < 3; ++mt)
@@ -304,7 +263,7 @@ __global__ __launch_bounds__(b1::NT) void conv_b1_chain_kernel(B1Args a) {
         const int wb = wave - NPROD;
         const int px = wb * 16 + (lane & 15), kg = lane >> 4;
         for (int j = 0; j <= T; ++j) {
-            b1_barrier();                                   // tile j - 1's sum is complete in its LDS tile
+            wait_lgkm_and_barrier();     // tile j - 1's sum is complete in its LDS tile
             if (j == 0) continue;
             // ---- 16 pixels of tile j - 1 x all channels: store | pre-activate | conv1 of the next unit -------------------------------
             const int tile = t0 + (j - 1) * G;

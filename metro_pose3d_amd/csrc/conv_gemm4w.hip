@@ -19,15 +19,9 @@
 #include <type_traits>
 
 #include "metro_common.h"
+#include "gfx950_prims.h"
 
 namespace metro {
-
-typedef _Float16 half_t;
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 namespace g4 {
 constexpr int TM = 256, TN = 256, BK = 64, NT = 256;
@@ -41,10 +35,6 @@ constexpr int MAIN_BYTES = OUT_BYTES > RING_BYTES ? OUT_BYTES : RING_BYTES;
 constexpr int PRO_BYTES = 2 * 2048 * 2;            // scale | shift, c_in <= 2048
 constexpr int PIECES = 8;                          // 16-byte loads per lane per operand per K tile (256 rows x 128 B / 256 lanes / 16 B)
 }  // namespace g4
-
-__device__ __forceinline__ int g4_swz(int row) { return (row >> 1) & 7; }
-typedef float g4_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int g4_u32x2 __attribute__((ext_vector_type(2)));
 
 // NJ: 32-pixel fragments per wave.  4 = the 256 x 256 tile (wave 128 x 128); 2 (round 6) = a 256 cout x 128 pixel HALF tile (wave
 // 128 x 64) for the deep-K layers of batch 64 that have only 128 whole tiles (block4 conv1: 2048 -> 512 on 16 384 pixels; the
@@ -95,7 +85,7 @@ __device__ __forceinline__ void conv_gemm4w_body(
     // ---- staging coordinates: piece e of an operand = rows 32 e + 8 wave + (lane >> 3), 16-byte chunk lane & 7 ------
     const int lrow = lane >> 3, lch = lane & 7;
     const int srow = wave * 8 + lrow;                                  // row of piece 0; piece e adds 32 e (same swizzle)
-    const unsigned st_off = (unsigned)(srow * ROW_BYTES + ((lch ^ g4_swz(srow)) << 4));   // LDS byte offset inside an operand image
+    const unsigned st_off = (unsigned)(srow * ROW_BYTES + ((lch ^ swz<BK>(srow)) << 4));  // LDS byte offset inside an operand image
     // buffer loads: wave-uniform descriptor of the tile's operand rows + ONE per-lane 32-bit offset for both operands (the piece
     // and the K tile go into the scalar offset): no 64-bit address arithmetic in the loop, no address registers
     const auto wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(w + (size_t)n0 * K), 0, 256 * K * 2, 0x00020000);
@@ -154,12 +144,12 @@ __device__ __forceinline__ void conv_gemm4w_body(
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int row = wr * 128 + i * 32 + frag_row;
-        a_base[i] = A_OFF + row * ROW_BYTES + ((frag_half ^ g4_swz(row)) << 4);
+        a_base[i] = A_OFF + row * ROW_BYTES + ((frag_half ^ swz<BK>(row)) << 4);
     }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int row = wc * (NJ * 32) + j * 32 + frag_row;
-        b_base[j] = B_OFF + row * ROW_BYTES + ((frag_half ^ g4_swz(row)) << 4);
+        b_base[j] = B_OFF + row * ROW_BYTES + ((frag_half ^ swz<BK>(row)) << 4);
     }
 
     // ---- prologue: table, tile 0 -> LDS buffer 0, tile 1 -> registers -----------------------------------------------
@@ -263,7 +253,7 @@ __device__ __forceinline__ void conv_gemm4w_body(
         step(std::integral_constant<int, 0>{});
         step(std::integral_constant<int, 1>{});
         step(std::integral_constant<int, 2>{});
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        wait_lgkm_and_barrier();
         load_frags(0, BUF ^ 1, 0);
         mma(1);                                  // k step 3: fragments read before the barrier
 #pragma unroll
@@ -303,17 +293,10 @@ __device__ __forceinline__ void conv_gemm4w_body(
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int col = wr * 128 + i * 32 + 8 * q + 4 * frag_half;
-                const g4_f32x2 blo = {bvq[i][q][0], bvq[i][q][1]}, bhi = {bvq[i][q][2], bvq[i][q][3]};
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
                     const int prow = wc * (NJ * 32) + j * 32 + frag_row;
-                    g4_f32x2 lo = {acc[i][j][4 * q], acc[i][j][4 * q + 1]}, hi = {acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
-                    asm("v_pk_add_f32 %0, %1, %2" : "=v"(lo) : "v"(lo), "v"(blo));
-                    asm("v_pk_add_f32 %0, %1, %2" : "=v"(hi) : "v"(hi), "v"(bhi));
-                    g4_u32x2 r;
-                    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r.x) : "v"(lo.x), "v"(lo.y));
-                    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r.y) : "v"(hi.x), "v"(hi.y));
-                    half4_t hv = __builtin_bit_cast(half4_t, r);
+                    half4_t hv = bias_cvt(acc[i][j], q, bvq[i][q]);
                     if constexpr (decltype(relu_c)::value) {
                         const half4_t z = {};
                         hv = __builtin_elementwise_max(hv, z);

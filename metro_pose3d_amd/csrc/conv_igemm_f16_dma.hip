@@ -20,17 +20,9 @@
 #include <type_traits>
 
 #include "metro_common.h"
+#include "gfx950_prims.h"
 
 namespace metro {
-
-typedef _Float16 half_t;
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-__device__ __attribute__((aligned(16))) unsigned int g_zero_page[4];   // zero-initialised
 
 template <int WAVES_M_, int WAVES_N_, int WM_, int WN_, int STAGES_, int BK_ = 64>
 struct DmaCfg {
@@ -56,39 +48,6 @@ struct DmaCfg {
     static_assert(BK == 64 || BK == 32, "BK must be 32 or 64");
     static_assert(STAGES >= 1 && STAGES <= 6, "ring depth 1..6");
 };
-
-// chunk swizzle so that ds_read_b128 of 32 rows x one chunk hits 16 distinct 16-byte slots per
-// 16-lane group: BK=64 (128-byte rows, 2 per bank row): (row>>1)&7; BK=32 (64-byte rows): (row>>2)&3
-template <int BK>
-__device__ __forceinline__ int swzk(int row) { return BK == 64 ? (row >> 1) & 7 : (row >> 2) & 3; }
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void glb_void_t;
-
-// One LDS-DMA wave-instruction: 64 lanes x 16 bytes, lane l lands at lds_addr + 16*l.
-// Inline asm on purpose: hipcc tracks the builtin form as an LDS write that may alias every
-// later ds_read and drains it with s_waitcnt vmcnt(0), which serialises the ring.  The asm form
-// is invisible to its bookkeeping; completion is ordered by the counted waits below.
-// lds_addr must be wave-uniform (it goes through M0, saved/restored around the instruction).
-__device__ __forceinline__ void dma16(const void* gsrc, unsigned lds_addr) {
-    // M0 is written in the same statement that consumes it and is not preserved: nothing else in
-    // these kernels uses M0 (gfx9+ LDS instructions do not need it).
-    asm volatile(
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %0, off"
-        :
-        : "v"(gsrc), "s"(lds_addr));   // no "memory" clobber: ordering is carried by the barrier asm
-}
-
-__device__ __forceinline__ unsigned lds_offset_of(const void* p) {
-    return (unsigned)(size_t)(lds_void_t*)p;
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm_and_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 struct Fuse2Args {
     const half_t* w2; const float* bias2; const half_t* scale2; const half_t* shift2; half_t* out2; int c2;
@@ -151,7 +110,7 @@ __device__ __forceinline__ void conv_dma_body(
         const int row = (i * NW + wave) * RPI + lrow;
         const int co = n0 + row;
         wvalid[i] = co < a.c_out;
-        wkoff[i] = (lch ^ swzk<BK>(row)) * 8;
+        wkoff[i] = (lch ^ swz<BK>(row)) * 8;
         const half_t* base = w + (size_t)(wvalid[i] ? co : 0) * k_total;
         // weight rows are contiguous across taps: with c_in % BK == 0 every step is +BK elements
         wsrc[i] = FASTK ? (wvalid[i] ? base + wkoff[i] : zero) : base;
@@ -173,7 +132,7 @@ __device__ __forceinline__ void conv_dma_body(
         xh[i] = ho * a.stride - a.pad_top;
         xw[i] = wo * a.stride - a.pad_left;
         xn[i] = img * a.h_in * a.w_in;
-        xkoff[i] = (lch ^ swzk<BK>(row)) * 8;
+        xkoff[i] = (lch ^ swz<BK>(row)) * 8;
         xptr[i] = zero;
         xinc[i] = 0;
     }
@@ -272,12 +231,12 @@ __device__ __forceinline__ void conv_dma_body(
 #pragma unroll
             for (int i = 0; i < Cfg::WM; ++i) {
                 const int row = (wave_m * Cfg::WM + i) * 32 + frag_row;
-                af[i] = *reinterpret_cast<const half8_t*>(wl + row * Cfg::ROW_BYTES + ((chunk ^ swzk<BK>(row)) << 4));
+                af[i] = *reinterpret_cast<const half8_t*>(wl + row * Cfg::ROW_BYTES + ((chunk ^ swz<BK>(row)) << 4));
             }
 #pragma unroll
             for (int j = 0; j < Cfg::WN; ++j) {
                 const int row = (wave_n * Cfg::WN + j) * 32 + frag_row;
-                bf[j] = *reinterpret_cast<const half8_t*>(xl + row * Cfg::ROW_BYTES + ((chunk ^ swzk<BK>(row)) << 4));
+                bf[j] = *reinterpret_cast<const half8_t*>(xl + row * Cfg::ROW_BYTES + ((chunk ^ swz<BK>(row)) << 4));
             }
             if (PROLOGUE) {
                 const half8_t sc = *reinterpret_cast<const half8_t*>(pro_lds + c0 + chunk * 8);
@@ -380,7 +339,7 @@ __device__ __forceinline__ void conv_dma_body(
         for (int i = 0; i < F2_W_BYTES / 1024 / NW; ++i) {
             const int vrow = (i * NW + wave) * 8 + (lane >> 3);          // row of the [TM/64 * 64][64] image
             const int kc = vrow >> 6, r = vrow & 63;
-            const half_t* src = f2.w2 + (size_t)r * Cfg::TM + kc * 64 + (((lane & 7) ^ swzk<64>(r)) * 8);
+            const half_t* src = f2.w2 + (size_t)r * Cfg::TM + kc * 64 + (((lane & 7) ^ swz<64>(r)) * 8);
             dma16(src, __builtin_amdgcn_readfirstlane(smem_base + F2_W_OFF + (i * NW + wave) * 1024));
         }
         half_t* p2 = reinterpret_cast<half_t*>(smem + F2_P_OFF);
@@ -604,7 +563,7 @@ __device__ __forceinline__ void conv_dma_body(
             for (int ks = 0; ks < F2_KSTEPS; ++ks) {
                 const int k0 = ks * 16 + frag_half * 8;
                 const half8_t af = *reinterpret_cast<const half8_t*>(
-                    w2l + (ks >> 2) * 8192 + ((((ks & 3) * 2 + frag_half) ^ swzk<64>(arow)) << 4));
+                    w2l + (ks >> 2) * 8192 + ((((ks & 3) * 2 + frag_half) ^ swz<64>(arow)) << 4));
                 half8_t bf = *reinterpret_cast<const half8_t*>(smem + prow2 * Cfg::OUT_ROW_BYTES + k0 * 2);
                 const half8_t sc = *reinterpret_cast<const half8_t*>(p2 + k0);
                 const half8_t sh = *reinterpret_cast<const half8_t*>(p2 + Cfg::TM + k0);

@@ -14,10 +14,9 @@
 // by the fp32 matrix pipe (157 TFLOP/s peak).  The gathers of step s+1 are issued before the MFMAs of step s (registers),
 // written to the other LDS buffer behind them: one barrier per step.
 #include "metro_common.h"
+#include "gfx950_prims.h"
 
 namespace metro {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 namespace f32m {
 #ifndef METRO_F32M_BK
@@ -176,7 +175,6 @@ __global__ __launch_bounds__(f32m::NT) void conv_igemm_f32_kernel(
 
     // epilogue: D[row = cout 8 q + 4 (lane >> 5) + e][col = pixel lane & 31] per 32 x 32 tile: a lane owns FOUR consecutive output
     // channels of a pixel per (i, q) -> 16-byte stores (and shortcut loads, all issued before the first use) when c_out % 4 == 0
-    typedef float floatx4 __attribute__((ext_vector_type(4)));
     const bool vec = (a.c_out & 3) == 0;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {

@@ -14,6 +14,7 @@
 //   A: lane l holds X[pixel = l&15][k = l>>4]      B: lane l holds W[k = l>>4][cout = l&15]
 //   D: reg r of lane l = D[pixel = (l>>4) + 4r][cout = l&15]
 #include "metro_common.h"
+#include "gfx950_prims.h"
 
 namespace metro {
 

@@ -42,17 +42,9 @@
 #include <type_traits>
 
 #include "metro_common.h"
+#include "gfx950_prims.h"
 
 namespace metro {
-
-typedef _Float16 half_t;
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-__device__ __attribute__((aligned(16))) unsigned int g_zero_page_pw[4];   // zero-initialised
 
 struct Pw64Args {
     const half_t* in;          // [m_total][64]
@@ -120,39 +112,17 @@ constexpr int lds_bytes() {
 }
 }  // namespace pw
 
-__device__ __forceinline__ int pw_swz(int row) { return (row >> 1) & 7; }
-
-__device__ __forceinline__ void pw_dma16(const void* gsrc, unsigned lds_addr) {
-    asm volatile(
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %0, off"
-        :
-        : "v"(gsrc), "s"(lds_addr));
-}
-template <int N>
-__device__ __forceinline__ void pw_wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 // vmcnt(BASE + extra), extra in [0, MAXX] wave-uniform: the wait count is an immediate
 template <int BASE, int MAXX>
 __device__ __forceinline__ void pw_wait_vm_plus(int extra) {
     if constexpr (MAXX == 0) {
-        pw_wait_vm<BASE>();
+        wait_vm<BASE>();
     } else {
-        if (extra >= MAXX) pw_wait_vm<BASE + MAXX>();
+        if (extra >= MAXX) wait_vm<BASE + MAXX>();
         else pw_wait_vm_plus<BASE, MAXX - 1>(extra);
     }
 }
-// s_waitcnt lgkmcnt(n), n a compile-time value after unrolling, tied to the register(s) the wait is for
-__device__ __forceinline__ void pw_wait_lgkm(half8_t& r, int n) {
-    switch (n) {
-        case 0: asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r)); break;
-        case 1: asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r)); break;
-        case 2: asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r)); break;
-        default: asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(r)); break;
-    }
-}
+// s_waitcnt lgkmcnt(n) tied to two registers, n a compile-time value after unrolling
 __device__ __forceinline__ void pw_wait_lgkm2(half8_t& r, half8_t& r2, int n) {
     switch (n) {
         case 0: asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r), "+v"(r2)); break;
@@ -160,9 +130,6 @@ __device__ __forceinline__ void pw_wait_lgkm2(half8_t& r, half8_t& r2, int n) {
         case 4: asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(r), "+v"(r2)); break;
         default: asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(r), "+v"(r2)); break;
     }
-}
-__device__ __forceinline__ void pw_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
 template <int K, int WM, bool PRO, bool RES, int MODE2, bool RSUB = false, bool PSC = false, int CB = 256, bool REB = false, int OUTM = 0>
@@ -182,8 +149,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
     constexpr int X_BYTES = L::X_BYTES, X_OFF = L::X_OFF, OUT_OFF = L::OUT_OFF, PAR_OFF = L::PAR_OFF, RES_OFF = L::RES_OFF,
                   RES_BYTES = L::RES_BYTES, SL_BYTES = L::SL_BYTES, OUT_ROW = L::OUT_ROW, CPR = L::CPR, C2 = L::C2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef __attribute__((address_space(3))) void lds_void_t;
-    const unsigned smem_base = (unsigned)(size_t)(lds_void_t*)smem;
+    const unsigned smem_base = lds_offset_of(smem);
     constexpr int XS_OFF = RES_OFF;                          // PSC: two buffers of the unit-input tile where the shortcut rows would be
     constexpr int XB_OFF = XS_OFF + 2 * X_BYTES;             // REB: two buffers of the previous unit's conv2 output tile
 
@@ -212,7 +178,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
     a.out += half * CB;
     if (RES) a.residual += half * CB;
     const int ldo = a.c_out;
-    const half_t* zero = reinterpret_cast<const half_t*>(g_zero_page_pw);
+    const half_t* zero = reinterpret_cast<const half_t*>(g_zero_page);
 
     // ---- launch-resident operands ------------------------------------------------------------
     half8_t wf[NI][KK];
@@ -310,21 +276,21 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
     for (int i = 0; i < XI; ++i) {
         const int q = i * NW + wave;
         xrow[i] = (q % (TN / 8)) * 8 + (lane >> 3);
-        xoff[i] = xrow[i] * K + (q / (TN / 8)) * 64 + (((lane & 7) ^ pw_swz(xrow[i])) * 8);
+        xoff[i] = xrow[i] * K + (q / (TN / 8)) * 64 + (((lane & 7) ^ swz<64>(xrow[i])) * 8);
     }
     auto issue_tile = [&](int tile, int buf) {
         const int m0 = tile * TN;
 #pragma unroll
         for (int i = 0; i < XI; ++i) {
             const half_t* xs = (m0 + xrow[i] < a.m_total) ? a.in + (size_t)m0 * K + xoff[i] : zero;
-            pw_dma16(xs, __builtin_amdgcn_readfirstlane(smem_base + X_OFF + buf * X_BYTES + (i * NW + wave) * 1024));
+            dma16(xs, __builtin_amdgcn_readfirstlane(smem_base + X_OFF + buf * X_BYTES + (i * NW + wave) * 1024));
             if constexpr (PSC) {
                 const half_t* ss = (m0 + xrow[i] < a.m_total) ? a.x_sc + (size_t)m0 * K + xoff[i] : zero;
-                pw_dma16(ss, __builtin_amdgcn_readfirstlane(smem_base + XS_OFF + buf * X_BYTES + (i * NW + wave) * 1024));
+                dma16(ss, __builtin_amdgcn_readfirstlane(smem_base + XS_OFF + buf * X_BYTES + (i * NW + wave) * 1024));
             }
             if constexpr (REB) {
                 const half_t* sb = (m0 + xrow[i] < a.m_total) ? a.in_b + (size_t)m0 * K + xoff[i] : zero;
-                pw_dma16(sb, __builtin_amdgcn_readfirstlane(smem_base + XB_OFF + buf * X_BYTES + (i * NW + wave) * 1024));
+                dma16(sb, __builtin_amdgcn_readfirstlane(smem_base + XB_OFF + buf * X_BYTES + (i * NW + wave) * 1024));
             }
         }
         if constexpr (RES) {
@@ -342,7 +308,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
                     rrow = ((size_t)img * a.res_h + a.res_off + a.res_stride * ho) * a.res_w + a.res_off + a.res_stride * wo;
                 }
                 const half_t* rs = m < a.m_total ? a.residual + rrow * ldo + (c & (CPR - 1)) * 8 : zero;
-                pw_dma16(rs, __builtin_amdgcn_readfirstlane(smem_base + RES_OFF + buf * RES_BYTES + it * 8192 + wave * 1024));
+                dma16(rs, __builtin_amdgcn_readfirstlane(smem_base + RES_OFF + buf * RES_BYTES + it * 8192 + wave * 1024));
             }
         }
     };
@@ -359,11 +325,11 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
         const int buf = it & 1;
         const int m0 = t * TN;
         // ---- the tile's loads have landed (for this wave), then for every wave -----------------
-        if (it == 0 || !prev_full) pw_wait_vm<0>();
+        if (it == 0 || !prev_full) wait_vm<0>();
         else if constexpr (OUTM == 2) pw_wait_vm_plus<S2, RI>(prev_sub);
-        else if (two) pw_wait_vm<RS + S2>();
-        else pw_wait_vm<RS>();
-        pw_barrier();
+        else if (two) wait_vm<RS + S2>();
+        else wait_vm<RS>();
+        wait_lgkm_and_barrier();
         if (t + G < a.n_tiles) issue_tile(t + G, buf ^ 1);
         prev_full = m0 + TN <= a.m_total;
 
@@ -376,12 +342,12 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int sl = (wave >> 2) + 2 * h;
-                half8_t* xp = reinterpret_cast<half8_t*>(smem + X_OFF + buf * X_BYTES + sl * SL_BYTES + prow * 128 + ((c8 ^ pw_swz(prow)) << 4));
+                half8_t* xp = reinterpret_cast<half8_t*>(smem + X_OFF + buf * X_BYTES + sl * SL_BYTES + prow * 128 + ((c8 ^ swz<64>(prow)) << 4));
                 const half8_t sc = *reinterpret_cast<const half8_t*>(pro_l + sl * 64 + c8 * 8);
                 const half8_t sh = *reinterpret_cast<const half8_t*>(pro_l + K + sl * 64 + c8 * 8);
                 *xp = __builtin_elementwise_max(*xp * sc + sh, z);
             }
-            pw_barrier();
+            wait_lgkm_and_barrier();
         }
         // ---- GEMM 1: [256 x 64] x [64 x 64 pixels] ---------------------------------------------
         floatx16 acc[NI], acc2, accs[NI];
@@ -401,7 +367,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
 #pragma unroll
             for (int kk = 0; kk < KK; ++kk) {
                 const int chunk = (kk & 3) * 2 + frag_half;
-                half8_t bs = *reinterpret_cast<const half8_t*>(smem + XS_OFF + buf * X_BYTES + (kk >> 2) * SL_BYTES + brow * 128 + ((chunk ^ pw_swz(brow)) << 4));
+                half8_t bs = *reinterpret_cast<const half8_t*>(smem + XS_OFF + buf * X_BYTES + (kk >> 2) * SL_BYTES + brow * 128 + ((chunk ^ swz<64>(brow)) << 4));
                 const half8_t s = *reinterpret_cast<const half8_t*>(pro_l + kk * 16 + frag_half * 8);
                 const half8_t b = *reinterpret_cast<const half8_t*>(pro_l + K + kk * 16 + frag_half * 8);
                 const half8_t z = {};
@@ -425,7 +391,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
 #pragma unroll
             for (int kk = 0; kk < KK; ++kk) {
                 const int chunk = (kk & 3) * 2 + frag_half;
-                const half8_t bb = *reinterpret_cast<const half8_t*>(smem + XB_OFF + buf * X_BYTES + (kk >> 2) * SL_BYTES + brow * 128 + ((chunk ^ pw_swz(brow)) << 4));
+                const half8_t bb = *reinterpret_cast<const half8_t*>(smem + XB_OFF + buf * X_BYTES + (kk >> 2) * SL_BYTES + brow * 128 + ((chunk ^ swz<64>(brow)) << 4));
 #pragma unroll
                 for (int i = 0; i < NI; ++i) accb[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wbf[i][kk], bb, accb[i], 0, 0, 0);
             }
@@ -448,7 +414,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
             unsigned fbase[4];
 #pragma unroll
             for (int c = 0; c < 4; ++c)
-                fbase[c] = smem_base + X_OFF + buf * X_BYTES + brow * 128 + (((2 * c + frag_half) ^ pw_swz(brow)) << 4);
+                fbase[c] = smem_base + X_OFF + buf * X_BYTES + brow * 128 + (((2 * c + frag_half) ^ swz<64>(brow)) << 4);
             const unsigned f2base = smem_base + W2_OFF + (wm * 32 + frag_row) * W2_ROW + frag_half * 16;
             auto gemm = [&](auto has2_c) {
                 constexpr bool HAS2 = decltype(has2_c)::value;
@@ -464,7 +430,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
                     constexpr int D1 = DEPTH - 1;
                     const int younger = (KK - 1 - kk < D1 ? KK - 1 - kk : D1) * PER;     // a constant after unrolling
                     if constexpr (HAS2) pw_wait_lgkm2(fr[kk % DEPTH], f2[kk % DEPTH], younger);
-                    else pw_wait_lgkm(fr[kk % DEPTH], younger);
+                    else wait_lgkm_dyn(fr[kk % DEPTH], younger);
 #pragma unroll
                     for (int i = 0; i < NI; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[i][kk], fr[kk % DEPTH], acc[i], 0, 0, 0);
                     if constexpr (HAS2) acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(f2[kk % DEPTH], fr[kk % DEPTH], acc2, 0, 0, 0);
@@ -480,7 +446,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
 #pragma unroll
         for (int kk = 0; kk < KK; ++kk) {
             const int chunk = (kk & 3) * 2 + frag_half;
-            half8_t bf = *reinterpret_cast<const half8_t*>(xl + (kk >> 2) * SL_BYTES + brow * 128 + ((chunk ^ pw_swz(brow)) << 4));
+            half8_t bf = *reinterpret_cast<const half8_t*>(xl + (kk >> 2) * SL_BYTES + brow * 128 + ((chunk ^ swz<64>(brow)) << 4));
             if constexpr (PRO && !PREPASS) {
                 const half8_t s = *reinterpret_cast<const half8_t*>(pro_l + kk * 16 + frag_half * 8);
                 const half8_t b = *reinterpret_cast<const half8_t*>(pro_l + K + kk * 16 + frag_half * 8);
@@ -497,7 +463,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
             }
             if constexpr (PSC && !REB) {
                 // projection shortcut on the pre-activated unit input (same pixels, same k step)
-                half8_t bs = *reinterpret_cast<const half8_t*>(smem + XS_OFF + buf * X_BYTES + (kk >> 2) * SL_BYTES + brow * 128 + ((chunk ^ pw_swz(brow)) << 4));
+                half8_t bs = *reinterpret_cast<const half8_t*>(smem + XS_OFF + buf * X_BYTES + (kk >> 2) * SL_BYTES + brow * 128 + ((chunk ^ swz<64>(brow)) << 4));
                 const half8_t s = *reinterpret_cast<const half8_t*>(pro_l + kk * 16 + frag_half * 8);
                 const half8_t b = *reinterpret_cast<const half8_t*>(pro_l + K + kk * 16 + frag_half * 8);
                 const half8_t z = {};
@@ -556,7 +522,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
                 *reinterpret_cast<half4_t*>(ol + brow * OUT_ROW + col * 2) = hv;
             }
         }
-        pw_barrier();
+        wait_lgkm_and_barrier();
         // ---- row-wise: 16 bytes per lane, + shortcut, full-row stores ---------------------------
         const char* rl = smem + RES_OFF + buf * RES_BYTES;
         // OUTM = 2: which of the RI row-wise instructions of this tile hold pixels the next (strided) unit's shortcut reads.  A
@@ -628,7 +594,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
             if (m0 + prow2 < a.m_total) store_out16<1>(a.out2 + (size_t)(m0 + prow2) * C2 + ch2 * 8, v2);
         }
         if constexpr (MODE2 == 2) {
-            pw_barrier();
+            wait_lgkm_and_barrier();
             // ---- GEMM 2: [C2 x CB] x [CB x TN pixels] from the tile: v_mfma_f32_16x16x32_f16, A[i][k] lane (i = lane & 15, k group =
             //      lane >> 4), B likewise by pixel, D[i][j] lane (j = lane & 15 -> pixel, rows 4 (lane >> 4) .. + 3)
             floatx4 dacc[NTW];

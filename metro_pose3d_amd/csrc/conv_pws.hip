@@ -20,14 +20,9 @@
 // Arithmetic is conv_pw64's (fp32 accumulation in ascending k on one accumulator, fp16(conv + bias), then the fp16 shortcut add:
 // reference resnet_v2.py:134-138): the same bits.
 #include "metro_common.h"
+#include "gfx950_prims.h"
 
 namespace metro {
-
-typedef _Float16 half_t;
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 struct PwsArgs {
     const half_t* in;          // [m_total][K]
@@ -57,56 +52,13 @@ struct Lay {
 };
 }  // namespace pws
 
-__device__ __forceinline__ int pws_swz(int row) { return (row >> 1) & 7; }
-__device__ __forceinline__ void pws_dma16(const void* gsrc, unsigned lds_addr) {
-    asm volatile(
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %0, off"
-        :
-        : "v"(gsrc), "s"(lds_addr));
-}
-template <int N>
-__device__ __forceinline__ void pws_wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void pws_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// s_waitcnt lgkmcnt(n), n a compile-time value after unrolling (0 .. 6), tied to the register the wait is for
-__device__ __forceinline__ void pws_wait_lgkm_dyn(half8_t& r, int n) {
-    switch (n) {
-        case 0: asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r)); break;
-        case 1: asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r)); break;
-        case 2: asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r)); break;
-        case 3: asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(r)); break;
-        case 4: asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(r)); break;
-        case 5: asm volatile("s_waitcnt lgkmcnt(5)" : "+v"(r)); break;
-        default: asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(r)); break;
-    }
-}
-
-typedef unsigned int pws_u32x2 __attribute__((ext_vector_type(2)));
-typedef float pws_f32x2 __attribute__((ext_vector_type(2)));
-// fp16(acc + bias) for four accumulators: two v_pk_add_f32 on the accumulator's own register pairs, two v_cvt_pk_f16_f32 (RNE)
-__device__ __forceinline__ half4_t pws_bias_cvt(const floatx16& acc, int q, const floatx4& bv) {
-    pws_f32x2 lo = {acc[4 * q], acc[4 * q + 1]}, hi = {acc[4 * q + 2], acc[4 * q + 3]};
-    const pws_f32x2 blo = {bv[0], bv[1]}, bhi = {bv[2], bv[3]};
-    asm("v_pk_add_f32 %0, %1, %2" : "=v"(lo) : "v"(lo), "v"(blo));
-    asm("v_pk_add_f32 %0, %1, %2" : "=v"(hi) : "v"(hi), "v"(bhi));
-    pws_u32x2 r;
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r.x) : "v"(lo.x), "v"(lo.y));
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r.y) : "v"(hi.x), "v"(hi.y));
-    return __builtin_bit_cast(half4_t, r);
-}
-
 template <int K>
 __global__ __launch_bounds__(pws::NT) void conv_pws_kernel(PwsArgs a) {
     using namespace pws;
     using L = Lay<K>;
     constexpr int KK = K / 16, NX = L::NX, X_BYTES = L::X_BYTES, SL_BYTES = L::SL_BYTES;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef __attribute__((address_space(3))) void lds_void_t;
-    const unsigned smem_base = (unsigned)(size_t)(lds_void_t*)smem;
+    const unsigned smem_base = lds_offset_of(smem);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -148,13 +100,13 @@ __global__ __launch_bounds__(pws::NT) void conv_pws_kernel(PwsArgs a) {
     for (int i = 0; i < NX; ++i) {
         const int q = i * NW + wave;
         const int row = (q & 3) * 8 + (lane >> 3);
-        xoff[i] = row * K + (q >> 2) * 64 + (((lane & 7) ^ pws_swz(row)) * 8);
+        xoff[i] = row * K + (q >> 2) * 64 + (((lane & 7) ^ swz<64>(row)) * 8);
     }
     auto issue_x = [&](int tile, int slot) {
         const half_t* src = a.in + (size_t)tile * TN * K;
 #pragma unroll
         for (int i = 0; i < NX; ++i)
-            pws_dma16(src + xoff[i], __builtin_amdgcn_readfirstlane(smem_base + L::X_OFF + slot * X_BYTES + (i * NW + wave) * 1024));
+            dma16(src + xoff[i], __builtin_amdgcn_readfirstlane(smem_base + L::X_OFF + slot * X_BYTES + (i * NW + wave) * 1024));
     };
     // shortcut rows / stores: lane l <-> pixel (l >> 2) + 16 it, 16-byte piece l & 3 of the wave's 64-byte row piece
     char* tw = smem + L::T_OFF + wave * (T_BYTES + R_BYTES);
@@ -162,29 +114,29 @@ __global__ __launch_bounds__(pws::NT) void conv_pws_kernel(PwsArgs a) {
     const int rpx = lane >> 2, rch = lane & 3;
     auto issue_res = [&](int tile) {
         const half_t* src = a.residual + ((size_t)tile * TN + rpx) * ldo + co0 + rch * 8;
-        pws_dma16(src, __builtin_amdgcn_readfirstlane(rw_lds));
-        pws_dma16(src + (size_t)16 * ldo, __builtin_amdgcn_readfirstlane(rw_lds + 1024));
+        dma16(src, __builtin_amdgcn_readfirstlane(rw_lds));
+        dma16(src + (size_t)16 * ldo, __builtin_amdgcn_readfirstlane(rw_lds + 1024));
     };
     // B fragment of k step kk: slice kk >> 2, row frag_row, chunk (2 (kk & 3) + frag_half) ^ swizzle
-    const int boff0 = frag_row * 128 + ((frag_half ^ pws_swz(frag_row)) << 4);
+    const int boff0 = frag_row * 128 + ((frag_half ^ swz<64>(frag_row)) << 4);
 
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");     // bias in LDS, weights in registers
+    wait_vm_and_barrier<0>();     // bias in LDS, weights in registers
     floatx4 bv[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) bv[q] = *reinterpret_cast<const floatx4*>(bias_l + wave * 32 + 8 * q + 4 * frag_half);
     issue_x(t0, 0);
     if (T > 1) issue_x(t0 + G, 1);
     // this wave's share of tile 0 has landed BEFORE its first barrier (waves 0-3 multiply tile 0 right behind it)
-    if (T > 1) pws_wait_vm<NX>();
-    else pws_wait_vm<0>();
-    if (wave >= 4) pws_barrier();        // waves 4-7 run one phase behind waves 0-3 from here on
+    if (T > 1) wait_vm<NX>();
+    else wait_vm<0>();
+    if (wave >= 4) wait_lgkm_and_barrier();  // waves 4-7 run one phase behind waves 0-3 from here on
 
     int slot = 0;
     for (int j = 0; j < T; ++j) {
         const int tile = t0 + j * G;
         // ---- phase 1: every wave's share of tile j has landed (each waited for its own: above for tile 0, behind the GEMM of tile
         //      j - 1 otherwise -- in both wave groups that wait lies in front of the barrier the OTHER group starts tile j behind) ----
-        pws_barrier();
+        wait_lgkm_and_barrier();
         issue_res(tile);                                         // consumed in this tile's epilogue
         if (j + 2 < T) issue_x(t0 + (j + 2) * G, slot >= 1 ? slot - 1 : 2);
         floatx16 acc;
@@ -206,20 +158,20 @@ __global__ __launch_bounds__(pws::NT) void conv_pws_kernel(PwsArgs a) {
         for (int kk = 0; kk < KK; ++kk) {
             // fragment kk has landed: at most min(DEPTH - 1, KK - 1 - kk) younger reads are still in flight
             if (KK - 1 - kk >= DEPTH - 1) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(fr[kk % DEPTH]) : "n"(DEPTH - 1));
-            else pws_wait_lgkm_dyn(fr[kk % DEPTH], KK - 1 - kk);
+            else wait_lgkm_dyn(fr[kk % DEPTH], KK - 1 - kk);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[kk], fr[kk % DEPTH], acc, 0, 0, 0);
             if (kk + DEPTH < KK)
                 asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fr[kk % DEPTH]) : "v"(fbase[(kk + DEPTH) & 3]), "n"(((kk + DEPTH) >> 2) * SL_BYTES));
         }
         // the shortcut rows of this tile (and every older request: the operand tile j + 1 among them) have landed; the operand
         // requests of tile j + 2 stay in flight
-        if (j + 2 < T) pws_wait_vm<NX>();
-        else pws_wait_vm<0>();
+        if (j + 2 < T) wait_vm<NX>();
+        else wait_vm<0>();
         // ---- phase 2 (the other wave of this SIMD is in its phase 1 now) --------------------------------------------------------------
-        pws_barrier();
+        wait_lgkm_and_barrier();
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-            *reinterpret_cast<half4_t*>(tw + frag_row * T_ROW + (8 * q + 4 * frag_half) * 2) = pws_bias_cvt(acc, q, bv[q]);
+            *reinterpret_cast<half4_t*>(tw + frag_row * T_ROW + (8 * q + 4 * frag_half) * 2) = bias_cvt(acc, q, bv[q]);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the wave's own tile: no barrier
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
@@ -232,7 +184,7 @@ __global__ __launch_bounds__(pws::NT) void conv_pws_kernel(PwsArgs a) {
         }
         slot = slot == 2 ? 0 : slot + 1;
     }
-    if (wave < 4) pws_barrier();         // every wave executes 2 T + 1 barriers
+    if (wave < 4) wait_lgkm_and_barrier();  // every wave executes 2 T + 1 barriers
 }
 
 bool conv_pws_supported(const MetroConvDesc& d) {

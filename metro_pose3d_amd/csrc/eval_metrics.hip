@@ -9,6 +9,7 @@
 // valid joints, A = X0^T Y0, SVD by cyclic Jacobi on A^T A, T = V U^T with the last singular
 // direction flipped when det(T) < 0.  A second kernel reduces over poses per joint (fp64 sums).
 #include "metro_common.h"
+#include "gfx950_prims.h"
 
 namespace metro {
 

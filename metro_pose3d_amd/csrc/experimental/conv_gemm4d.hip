@@ -27,16 +27,10 @@
 #include <type_traits>
 
 #include "../metro_common.h"
+#include "../gfx950_prims.h"
 #include "metro_experimental.h"
 
 namespace metro {
-
-typedef _Float16 half_t;
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 namespace g4d {
 constexpr int BK = 64, NT = 256;
@@ -59,33 +53,9 @@ struct Geo {
 };
 }  // namespace g4d
 
-__device__ __forceinline__ int g4d_swz(int row) { return (row >> 1) & 7; }
-
-typedef __attribute__((address_space(3))) void g4d_lds_void_t;
-
-// one LDS-DMA wave-instruction: lane l's 16 bytes land at (lds_base + LDS_IMM) + 16 l.  Inline asm: hipcc treats the builtin as a
-// may-alias LDS write and drains it with vmcnt(0) before every ds_read.  M0 is written in the statement that reads it.
-template <int LDS_IMM>
-__device__ __forceinline__ void g4d_dma16(const void* sbase, unsigned voff, unsigned lds_base) {
-    asm volatile(
-        "s_add_u32 m0, %2, %3\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %0, %1"
-        :
-        : "v"(voff), "s"(sbase), "s"(lds_base), "n"(LDS_IMM)
-        : "scc");
-}
 template <int N>
 __device__ __forceinline__ void g4d_wait_vm_barrier() {
     asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-// f(integral_constant<0>) ... f(integral_constant<N - 1>)
-template <int N, typename F>
-__device__ __forceinline__ void g4d_for(F&& f) {
-    if constexpr (N > 0) {
-        g4d_for<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
 }
 
 // INPLACE (round 5, experiment): the pre-activation is applied ONCE per element, in place in the landed pixel image, by the wave whose
@@ -122,7 +92,7 @@ __global__ __launch_bounds__(g4d::NT, (MI * NJ <= 4 ? 2 : 1)) void conv_gemm4d_k
     const int n0 = tile_m * TM;
     const int K = a.c_in;
     const int nk = K / BK;               // even (the launcher guarantees c_in % 128 == 0)
-    const unsigned smem_base = (unsigned)(size_t)(g4d_lds_void_t*)smem;
+    const unsigned smem_base = lds_offset_of(smem);
     half_t* pro_lds = reinterpret_cast<half_t*>(smem + G::MAIN_BYTES);
 
     // ---- LDS-DMA sources.  One instruction = 8 rows x 128 B (lane l: row l >> 3, physical chunk l & 7 = logical chunk ^ swz(row)).
@@ -133,7 +103,7 @@ __global__ __launch_bounds__(g4d::NT, (MI * NJ <= 4 ? 2 : 1)) void conv_gemm4d_k
 #pragma unroll
     for (int e = 0; e < RMAX; ++e) {
         const int row = (4 * e + wave) * 8 + lrow;
-        voff[e] = (unsigned)(row * K + ((lch ^ g4d_swz(row)) * 8)) * 2u;
+        voff[e] = (unsigned)(row * K + ((lch ^ swz<64>(row)) * 8)) * 2u;
     }
     const unsigned lds_a = __builtin_amdgcn_readfirstlane(smem_base + wave * 8 * ROW_BYTES);            // group e adds e * 4 KiB
     const unsigned lds_b = lds_a + G::B_BASE;
@@ -148,8 +118,8 @@ __global__ __launch_bounds__(g4d::NT, (MI * NJ <= 4 ? 2 : 1)) void conv_gemm4d_k
     auto req = [&](auto buf_c, auto g_c, int kt) {
         constexpr int BUF = decltype(buf_c)::value, GI = decltype(g_c)::value;
 #ifndef METRO_DBG_G4D_NO_DMA
-        if constexpr (GI < G::RB) g4d_dma16<BUF * G::OPER_B + GI * 4096>(xbase + kt * BK, voff[GI], lds_b);
-        else if constexpr (GI < G::R) g4d_dma16<BUF * G::OPER_A + (GI - G::RB) * 4096>(wbase + kt * BK, voff[GI - G::RB], lds_a);
+        if constexpr (GI < G::RB) dma16s<BUF * G::OPER_B + GI * 4096>(xbase + kt * BK, voff[GI], lds_b);
+        else if constexpr (GI < G::R) dma16s<BUF * G::OPER_A + (GI - G::RB) * 4096>(wbase + kt * BK, voff[GI - G::RB], lds_a);
 #endif
     };
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
@@ -168,12 +138,12 @@ __global__ __launch_bounds__(g4d::NT, (MI * NJ <= 4 ? 2 : 1)) void conv_gemm4d_k
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
         const int row = wr * (TM / 2) + i * 32 + frag_row;
-        a_base[i] = row * ROW_BYTES + ((frag_half ^ g4d_swz(row)) << 4);
+        a_base[i] = row * ROW_BYTES + ((frag_half ^ swz<64>(row)) << 4);
     }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int row = wc * (TN / 2) + j * 32 + frag_row;
-        b_base[j] = G::B_BASE + row * ROW_BYTES + ((frag_half ^ g4d_swz(row)) << 4);
+        b_base[j] = G::B_BASE + row * ROW_BYTES + ((frag_half ^ swz<64>(row)) << 4);
     }
 
     // INPLACE: this wave's own pixel pieces of a K tile (piece g: rows 32 g + 8 wave + (lane >> 3), physical chunk lane & 7 -- the
@@ -198,15 +168,15 @@ __global__ __launch_bounds__(g4d::NT, (MI * NJ <= 4 ? 2 : 1)) void conv_gemm4d_k
         const int idx = wave * 512 + lane * 8;
         if (wave * 512 < K) {
             const unsigned dst = __builtin_amdgcn_readfirstlane(smem_base + G::MAIN_BYTES + wave * 1024);
-            g4d_dma16<0>(pro_scale, (unsigned)((idx < K ? idx : 0) * 2), dst);
-            g4d_dma16<4096>(pro_shift, (unsigned)((idx < K ? idx : 0) * 2), dst);
+            dma16s<0>(pro_scale, (unsigned)((idx < K ? idx : 0) * 2), dst);
+            dma16s<4096>(pro_shift, (unsigned)((idx < K ? idx : 0) * 2), dst);
         }
     }
-    g4d_for<G::R>([&](auto g_c) { req(I0{}, g_c, 0); });
+    static_for<G::R>([&](auto g_c) { req(I0{}, g_c, 0); });
     constexpr int HEAD = 2 * G::Q < G::R ? 2 * G::Q : G::R;       // requests of a tile that k steps 2 and 3 issue
     {
         const int k1 = nk > 1 ? 1 : 0;
-        g4d_for<HEAD>([&](auto g_c) { req(I1{}, g_c, k1); });
+        static_for<HEAD>([&](auto g_c) { req(I1{}, g_c, k1); });
     }
 #ifdef METRO_DBG_G4D_NO_DMA
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
@@ -219,7 +189,7 @@ __global__ __launch_bounds__(g4d::NT, (MI * NJ <= 4 ? 2 : 1)) void conv_gemm4d_k
         for (int g = 0; g < G::RB; ++g) rmw_read(0, g);
 #pragma unroll
         for (int g = 0; g < G::RB; ++g) rmw_write(0, g);
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        wait_lgkm_and_barrier();
     }
 
     // FOUR fragment sets, one per k step of a K tile: while the MFMAs of k step kk run on set kk, the pixel fragments of set kk + 1
@@ -282,7 +252,7 @@ __global__ __launch_bounds__(g4d::NT, (MI * NJ <= 4 ? 2 : 1)) void conv_gemm4d_k
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::RA) : "memory");              // own pixel pieces landed; the cout requests may fly
             rmw_pro(rmw_kt);
         }
-        g4d_for<MI>([&](auto i_c) {
+        static_for<MI>([&](auto i_c) {
             constexpr int I = decltype(i_c)::value;
             if constexpr (RMW) {
                 rmw_read(NB, 2 * I); rmw_read(NB, 2 * I + 1);
@@ -358,7 +328,7 @@ __global__ __launch_bounds__(g4d::NT, (MI * NJ <= 4 ? 2 : 1)) void conv_gemm4d_k
         ktile(I0{}, t);
         ktile(I1{}, t + 1);
     }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // every wave's re-requested tail has landed: the
+    wait_vm_and_barrier<0>();     // every wave's re-requested tail has landed: the
                                                                                  // epilogue tile overlays the ring
 
     // ---- epilogue: accumulators (+bias, ReLU) -> LDS [pixel][cout] fp16 -> full-line stores (+ shortcut) ----

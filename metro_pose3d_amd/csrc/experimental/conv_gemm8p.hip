@@ -21,16 +21,10 @@
 #include <type_traits>
 
 #include "../metro_common.h"
+#include "../gfx950_prims.h"
 #include "metro_experimental.h"
 
 namespace metro {
-
-typedef _Float16 half_t;
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 namespace g8 {
 constexpr int TM = 256, TN = 256, BK = 64, NT = 512;
@@ -47,12 +41,8 @@ constexpr int MAIN_BYTES = OUT_BYTES > RING_BYTES ? OUT_BYTES : RING_BYTES;
 constexpr int PRO_BYTES = 2 * 2048 * 2;            // scale | shift, c_in <= 2048
 }  // namespace g8
 
-__device__ __forceinline__ int g8_swz(int row) { return (row >> 1) & 7; }
-
-typedef __attribute__((address_space(3))) void g8_lds_void_t;
-
 // one LDS-DMA wave-instruction (64 lanes x 16 B, lane l lands at lds_addr + 16*l); inline asm so that hipcc does
-// not drain it with vmcnt(0) before every ds_read (see conv_igemm_f16_dma.hip).  Source = wave-uniform base
+// not drain it with vmcnt(0) before every ds_read (see gfx950_prims.h).  Source = wave-uniform base
 // (SGPR pair, advanced per K tile by scalar adds) + per-lane 32-bit byte offset: 1 VGPR per instruction stream.
 __device__ __forceinline__ void g8_dma16(const void* sbase, unsigned voff, unsigned lds_addr) {
     asm volatile(
@@ -62,12 +52,7 @@ __device__ __forceinline__ void g8_dma16(const void* sbase, unsigned voff, unsig
         :
         : "v"(voff), "s"(sbase), "s"(lds_addr));
 }
-template <int N>
-__device__ __forceinline__ void g8_wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 __device__ __forceinline__ void g8_barrier() { asm volatile("s_barrier" ::: "memory"); }
-__device__ __forceinline__ void g8_wait_lgkm_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <bool PROLOGUE>
 __global__ __launch_bounds__(g8::NT) void conv_gemm8p_kernel(
@@ -97,7 +82,7 @@ __global__ __launch_bounds__(g8::NT) void conv_gemm8p_kernel(
     const int n0 = tile_m * TM;
     const int K = a.c_in;
     const int nk = K / BK;
-    const unsigned smem_base = (unsigned)(size_t)(g8_lds_void_t*)smem;
+    const unsigned smem_base = lds_offset_of(smem);
     half_t* pro_lds = reinterpret_cast<half_t*>(smem + MAIN_BYTES);
 
     // ---- LDS-DMA sources.  Half-tiles (what ONE phase stages = what every wave reads in one later phase):
@@ -115,7 +100,7 @@ __global__ __launch_bounds__(g8::NT) void conv_gemm8p_kernel(
             const int grp = (i * 16) + h * 8 + wave;            // rows [8*grp, 8*grp+8): i = wave row, h = half
             const int row = grp * 8 + lrow;
             const int e = h * 2 + i;
-            voff[e] = (unsigned)(row * K + ((lch ^ g8_swz(row)) * 8)) * 2u;
+            voff[e] = (unsigned)(row * K + ((lch ^ swz<64>(row)) * 8)) * 2u;
             ldsoff[e] = grp * 8 * ROW_BYTES;
         }
     }
@@ -127,7 +112,7 @@ __global__ __launch_bounds__(g8::NT) void conv_gemm8p_kernel(
             const int grp = (q >> 2) * 8 + h * 4 + (q & 3);      // rows 64c + 32h + 8g ..
             const int row = grp * 8 + lrow;
             const int e = 4 + h * 2 + i;
-            voff[e] = (unsigned)(row * K + ((lch ^ g8_swz(row)) * 8)) * 2u;
+            voff[e] = (unsigned)(row * K + ((lch ^ swz<64>(row)) * 8)) * 2u;
             ldsoff[e] = B_BASE + grp * 8 * ROW_BYTES;
         }
     }
@@ -158,12 +143,12 @@ __global__ __launch_bounds__(g8::NT) void conv_gemm8p_kernel(
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int row = wr * 128 + i * 32 + frag_row;
-        a_base[i] = row * ROW_BYTES + ((frag_half ^ g8_swz(row)) << 4);
+        a_base[i] = row * ROW_BYTES + ((frag_half ^ swz<64>(row)) << 4);
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int row = wc * 64 + j * 32 + frag_row;
-        b_base[j] = B_BASE + row * ROW_BYTES + ((frag_half ^ g8_swz(row)) << 4);
+        b_base[j] = B_BASE + row * ROW_BYTES + ((frag_half ^ swz<64>(row)) << 4);
     }
 
     // ---- prologue: K tile 0 (all four half-tiles), pre-activation table, then the stagger ------------------
@@ -175,7 +160,7 @@ __global__ __launch_bounds__(g8::NT) void conv_gemm8p_kernel(
             *reinterpret_cast<uint4*>(pro_lds + 2048 + c) = *reinterpret_cast<const uint4*>(pro_shift + c);
         }
     }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // tile 0 landed, table visible
+    wait_vm_and_barrier<0>();     // tile 0 landed, table visible
     if (wr == 1) g8_barrier();                                                  // waves 4-7 run one barrier behind
 
     half8_t af[2][4], bf0[4], bf1[4];
@@ -229,26 +214,26 @@ __global__ __launch_bounds__(g8::NT) void conv_gemm8p_kernel(
         load_a(buf, 0);
         load_b(buf, 0, bf0, k0);
         stage(0, BUF ^ 1, kn);            // HA0 of tile t+1 (slot last read in phase 1 of tile t-1)
-        g8_wait_vm<6>();                  // retires HB1 of THIS tile (read in phase 2); three half-tiles stay in flight
-        g8_wait_lgkm_barrier();
+        wait_vm<6>();                     // retires HB1 of THIS tile (read in phase 2); three half-tiles stay in flight
+        wait_lgkm_and_barrier();
         mma(0, 0, bf0);
         g8_barrier();
         // ---- phase 2: quadrant (m 0-1, n 1) ----
         load_b(buf, 1, bf1, k0);
         stage(3, BUF ^ 1, kn);            // HB1 of tile t+1
-        g8_wait_vm<6>();                  // retires HA1 of this tile (read in phase 3)
-        g8_wait_lgkm_barrier();
+        wait_vm<6>();                     // retires HA1 of this tile (read in phase 3)
+        wait_lgkm_and_barrier();
         mma(0, 1, bf1);
         g8_barrier();
         // ---- phase 3: quadrant (m 2-3, n 1) ----
         load_a(buf, 1);
         stage(1, BUF ^ 1, kn);            // HA1 of tile t+1
-        g8_wait_lgkm_barrier();
+        wait_lgkm_and_barrier();
         mma(1, 1, bf1);
         g8_barrier();
         // ---- phase 4: quadrant (m 2-3, n 0): both fragments are in registers ----
         stage(2, BUF, kn2);               // HB0 of tile t+2 into THIS buffer (its B0 was read in phase 1 only)
-        g8_wait_vm<6>();                  // retires HB0 + HA0 of tile t+1 (read in its phase 1)
+        wait_vm<6>();                     // retires HB0 + HA0 of tile t+1 (read in its phase 1)
         g8_barrier();
         mma(1, 0, bf0);
         g8_barrier();
@@ -257,7 +242,7 @@ __global__ __launch_bounds__(g8::NT) void conv_gemm8p_kernel(
         ktile(std::integral_constant<int, 0>{}, t);
         ktile(std::integral_constant<int, 1>{}, t + 1);
     }
-    g8_wait_vm<0>();                      // this wave's re-staged last tile has landed ...
+    wait_vm<0>();                         // this wave's re-staged last tile has landed ...
     if (wr == 0) g8_barrier();            // re-align the two groups: every wave is done reading the ring
     g8_barrier();                         // ... and so has EVERY wave's (group 1 leaves its last loop barrier with up to six
                                           // LDS-DMAs in flight; vmcnt orders only a wave's own): nobody writes the epilogue

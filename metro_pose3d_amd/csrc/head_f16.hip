@@ -20,15 +20,9 @@
 //     and gathers the exported order, as for the two-launch path.
 // The logits never exist in HBM.  Arithmetic: fp16 operands, fp32 accumulate, fp32 bias add, fp32 soft-argmax.
 #include "metro_common.h"
+#include "gfx950_prims.h"
 
 namespace metro {
-
-typedef _Float16 half_t;
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-__device__ __attribute__((aligned(16))) unsigned int g_zero_page_head[4];   // zero-initialised
 
 namespace hd {
 constexpr int TM = 160, MT = 5, TN = 64, BK = 64, NW = 8, NT = 512, STAGES = 5;
@@ -43,22 +37,6 @@ constexpr int LDS_BYTES = RING_BYTES + PRO_BYTES;
 constexpr int LPS_A = 5, LPS_B = 2;                    // DMA instructions per K step: waves 0-3 (weights) / 4-7 (pixels)
 static_assert(LOGITS_BYTES <= RING_BYTES, "logits tile must fit the ring");
 }  // namespace hd
-
-__device__ __forceinline__ int hd_swz(int row) { return (row >> 1) & 7; }
-typedef __attribute__((address_space(3))) void hd_lds_void_t;
-
-__device__ __forceinline__ void hd_dma16(const void* gsrc, unsigned lds_addr) {
-    asm volatile(
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %0, off"
-        :
-        : "v"(gsrc), "s"(lds_addr));
-}
-template <int N>
-__device__ __forceinline__ void hd_wait_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 struct HeadArgs {
     const half_t* x;          // [n * pixels][K] fp16, raw residual stream
@@ -86,8 +64,8 @@ __global__ __launch_bounds__(hd::NT) void head_f16_kernel(HeadArgs a) {
     const int slab = blockIdx.x, img = blockIdx.y;
     const int m0 = img * a.pixels + slab * TN;    // first pixel row of the tile
     const int K = a.K, nk = K / BK;
-    const half_t* zero = reinterpret_cast<const half_t*>(g_zero_page_head);
-    const unsigned smem_base = (unsigned)(size_t)(hd_lds_void_t*)smem;
+    const half_t* zero = reinterpret_cast<const half_t*>(g_zero_page);
+    const unsigned smem_base = lds_offset_of(smem);
     half_t* pro_lds = reinterpret_cast<half_t*>(smem + RING_BYTES);
 
     // ---- DMA sources: waves 0-3 bring the 160 weight rows (20 groups of 8 rows, 5 per wave), waves 4-7 the 64 pixel rows
@@ -101,13 +79,13 @@ __global__ __launch_bounds__(hd::NT) void head_f16_kernel(HeadArgs a) {
         if (wave < 4) {
             const int row = (i * 4 + wave) * 8 + lrow;
             const bool ok = row < a.C;
-            src[i] = ok ? a.w + (size_t)row * K + ((lch ^ hd_swz(row)) * 8) : zero;
+            src[i] = ok ? a.w + (size_t)row * K + ((lch ^ swz<64>(row)) * 8) : zero;
             inc[i] = ok ? BK : 0;
             ldsoff[i] = (i * 4 + wave) * 8 * ROW_BYTES;
         } else {
             const int g = (i * 4 + (wave - 4)) & 7;              // 8 groups of 8 pixel rows, 2 per wave
             const int row = g * 8 + lrow;
-            src[i] = a.x + (size_t)(m0 + row) * K + ((lch ^ hd_swz(row)) * 8);
+            src[i] = a.x + (size_t)(m0 + row) * K + ((lch ^ swz<64>(row)) * 8);
             inc[i] = BK;
             ldsoff[i] = TM * ROW_BYTES + g * 8 * ROW_BYTES;
         }
@@ -117,7 +95,7 @@ __global__ __launch_bounds__(hd::NT) void head_f16_kernel(HeadArgs a) {
 #pragma unroll
         for (int i = 0; i < LPS_A; ++i) {
             if (i < nld) {                        // wave-uniform: the pixel waves issue 2, the weight waves 5
-                hd_dma16(src[i], base + ldsoff[i]);
+                dma16(src[i], base + ldsoff[i]);
                 src[i] += inc[i];
             }
         }
@@ -142,7 +120,7 @@ __global__ __launch_bounds__(hd::NT) void head_f16_kernel(HeadArgs a) {
 
     const int brow = wn * 32 + frag_row;
     const int b_off = TM * ROW_BYTES + brow * ROW_BYTES;
-    const int b_sw = hd_swz(brow);
+    const int b_sw = swz<64>(brow);
     auto compute_step = [&](int slot, int k0) {
         const char* wl = smem + slot * STAGE_BYTES;
         {
@@ -156,7 +134,7 @@ __global__ __launch_bounds__(hd::NT) void head_f16_kernel(HeadArgs a) {
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 const int row = i * 32 + frag_row;
-                const half8_t af = *reinterpret_cast<const half8_t*>(wl + row * ROW_BYTES + ((chunk ^ hd_swz(row)) << 4));
+                const half8_t af = *reinterpret_cast<const half8_t*>(wl + row * ROW_BYTES + ((chunk ^ swz<64>(row)) << 4));
                 acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, acc[i], 0, 0, 0);
             }
         }
@@ -165,7 +143,7 @@ __global__ __launch_bounds__(hd::NT) void head_f16_kernel(HeadArgs a) {
     const int n_main = nk - (STAGES - 1);
     int slot = 0, islot = STAGES - 1;
     for (int k = 0; k < n_main; ++k) {
-        if (wave < 4) hd_wait_barrier<(STAGES - 2) * LPS_A>(); else hd_wait_barrier<(STAGES - 2) * LPS_B>();
+        if (wave < 4) wait_vm_and_barrier<(STAGES - 2) * LPS_A>(); else wait_vm_and_barrier<(STAGES - 2) * LPS_B>();
         issue_step(islot);
         compute_step(slot, k * BK);
         slot = slot + 1 == STAGES ? 0 : slot + 1;
@@ -173,10 +151,10 @@ __global__ __launch_bounds__(hd::NT) void head_f16_kernel(HeadArgs a) {
     }
     for (int k = n_main < 0 ? 0 : n_main; k < nk; ++k) {      // drain
         const int ahead = nk - 1 - k;
-        if (ahead >= 3) { if (wave < 4) hd_wait_barrier<3 * LPS_A>(); else hd_wait_barrier<3 * LPS_B>(); }
-        else if (ahead == 2) { if (wave < 4) hd_wait_barrier<2 * LPS_A>(); else hd_wait_barrier<2 * LPS_B>(); }
-        else if (ahead == 1) { if (wave < 4) hd_wait_barrier<LPS_A>(); else hd_wait_barrier<LPS_B>(); }
-        else hd_wait_barrier<0>();
+        if (ahead >= 3) { if (wave < 4) wait_vm_and_barrier<3 * LPS_A>(); else wait_vm_and_barrier<3 * LPS_B>(); }
+        else if (ahead == 2) { if (wave < 4) wait_vm_and_barrier<2 * LPS_A>(); else wait_vm_and_barrier<2 * LPS_B>(); }
+        else if (ahead == 1) { if (wave < 4) wait_vm_and_barrier<LPS_A>(); else wait_vm_and_barrier<LPS_B>(); }
+        else wait_vm_and_barrier<0>();
         compute_step(slot, k * BK);
         slot = slot + 1 == STAGES ? 0 : slot + 1;
     }
@@ -344,8 +322,6 @@ constexpr int WTILE_BYTES = 4 * 32 * LROW * 4;           // four wave-private [3
 static_assert(LDS_BYTES <= 160 * 1024 && LOGITS_BYTES <= RING_BYTES && WTILE_BYTES <= RING_BYTES && GA <= 2 * NW && GB == 2 * NW, "LDS / loader split");
 }  // namespace hd2
 
-__device__ __forceinline__ int hd2_swz(int row) { return (row >> 2) & 3; }
-
 __global__ __launch_bounds__(hd2::NT) void head_f16_kernel256(HeadArgs a) {
     using namespace hd2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -355,8 +331,8 @@ __global__ __launch_bounds__(hd2::NT) void head_f16_kernel256(HeadArgs a) {
     const int tile = blockIdx.x, img = blockIdx.y;
     const int m0 = img * a.pixels + tile * TN;
     const int K = a.K, nk = K / BK;
-    const half_t* zero = reinterpret_cast<const half_t*>(g_zero_page_head);
-    const unsigned smem_base = (unsigned)(size_t)(hd_lds_void_t*)smem;
+    const half_t* zero = reinterpret_cast<const half_t*>(g_zero_page);
+    const unsigned smem_base = lds_offset_of(smem);
     half_t* pro_lds = reinterpret_cast<half_t*>(smem + PRO_OFF);
 
     // ---- DMA sources per K step (one instruction = 16 rows x 64 B): weight groups g = wave, wave + 8 (< 10), pixel groups
@@ -370,20 +346,20 @@ __global__ __launch_bounds__(hd2::NT) void head_f16_kernel256(HeadArgs a) {
     for (int i = 0; i < 2; ++i) {
         const int row = (wave + NW * i) * 16 + lrow;
         const bool ok = row < a.C;
-        srcw[i] = ok ? a.w + (size_t)row * K + ((lch ^ hd2_swz(row)) * 8) : zero;
+        srcw[i] = ok ? a.w + (size_t)row * K + ((lch ^ swz<32>(row)) * 8) : zero;
         incw[i] = ok ? BK : 0;
         const int prow = (wave + NW * i) * 16 + lrow;
-        srcx[i] = a.x + (size_t)(m0 + prow) * K + ((lch ^ hd2_swz(prow)) * 8);
+        srcx[i] = a.x + (size_t)(m0 + prow) * K + ((lch ^ swz<32>(prow)) * 8);
     }
     auto issue_step = [&](int slot) {
         const unsigned base = __builtin_amdgcn_readfirstlane(smem_base + slot * STAGE_BYTES);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             if (i < na) {
-                hd_dma16(srcw[i], base + (wave + NW * i) * 16 * ROW_BYTES);
+                dma16(srcw[i], base + (wave + NW * i) * 16 * ROW_BYTES);
                 srcw[i] += incw[i];
             }
-            hd_dma16(srcx[i], base + TM * ROW_BYTES + (wave + NW * i) * 16 * ROW_BYTES);
+            dma16(srcx[i], base + TM * ROW_BYTES + (wave + NW * i) * 16 * ROW_BYTES);
             srcx[i] += BK;
         }
     };
@@ -406,7 +382,7 @@ __global__ __launch_bounds__(hd2::NT) void head_f16_kernel256(HeadArgs a) {
 
     const int brow = wave * 32 + frag_row;
     const int b_off = TM * ROW_BYTES + brow * ROW_BYTES;
-    const int b_sw = hd2_swz(brow);
+    const int b_sw = swz<32>(brow);
     auto compute_step = [&](int slot, int k0) {
         const char* wl = smem + slot * STAGE_BYTES;
 #pragma unroll
@@ -420,7 +396,7 @@ __global__ __launch_bounds__(hd2::NT) void head_f16_kernel256(HeadArgs a) {
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 const int row = i * 32 + frag_row;
-                const half8_t af = *reinterpret_cast<const half8_t*>(wl + row * ROW_BYTES + ((chunk ^ hd2_swz(row)) << 4));
+                const half8_t af = *reinterpret_cast<const half8_t*>(wl + row * ROW_BYTES + ((chunk ^ swz<32>(row)) << 4));
                 acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, acc[i], 0, 0, 0);
             }
         }
@@ -429,7 +405,7 @@ __global__ __launch_bounds__(hd2::NT) void head_f16_kernel256(HeadArgs a) {
     const int n_main = nk - (STAGES - 1);
     int slot = 0, islot = STAGES - 1;
     for (int k = 0; k < n_main; ++k) {
-        if (na == 2) hd_wait_barrier<3 * 4>(); else hd_wait_barrier<3 * 3>();
+        if (na == 2) wait_vm_and_barrier<3 * 4>(); else wait_vm_and_barrier<3 * 3>();
         issue_step(islot);
         compute_step(slot, k * BK);
         slot = slot + 1 == STAGES ? 0 : slot + 1;
@@ -437,10 +413,10 @@ __global__ __launch_bounds__(hd2::NT) void head_f16_kernel256(HeadArgs a) {
     }
     for (int k = n_main < 0 ? 0 : n_main; k < nk; ++k) {      // drain
         const int ahead = nk - 1 - k;
-        if (ahead >= 3) { if (na == 2) hd_wait_barrier<12>(); else hd_wait_barrier<9>(); }
-        else if (ahead == 2) { if (na == 2) hd_wait_barrier<8>(); else hd_wait_barrier<6>(); }
-        else if (ahead == 1) { if (na == 2) hd_wait_barrier<4>(); else hd_wait_barrier<3>(); }
-        else hd_wait_barrier<0>();
+        if (ahead >= 3) { if (na == 2) wait_vm_and_barrier<12>(); else wait_vm_and_barrier<9>(); }
+        else if (ahead == 2) { if (na == 2) wait_vm_and_barrier<8>(); else wait_vm_and_barrier<6>(); }
+        else if (ahead == 1) { if (na == 2) wait_vm_and_barrier<4>(); else wait_vm_and_barrier<3>(); }
+        else wait_vm_and_barrier<0>();
         compute_step(slot, k * BK);
         slot = slot + 1 == STAGES ? 0 : slot + 1;
     }
@@ -532,17 +508,6 @@ struct HeadRing {
                   NA_HI <= 3 && NB >= 1 && NB <= 4 && GB % NW == 0 && WROWS % 8 == 0, "head ring geometry");
 };
 
-// one LDS-DMA wave-instruction, source = wave-uniform base + per-lane byte offset, destination (lds_base + LDS_IMM) + 16 l
-template <int LDS_IMM>
-__device__ __forceinline__ void hd_dma16s(const void* sbase, unsigned voff, unsigned lds_base) {
-    asm volatile(
-        "s_add_u32 m0, %2, %3\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %0, %1"
-        :
-        : "v"(voff), "s"(sbase), "s"(lds_base), "n"(LDS_IMM)
-        : "scc");
-}
 // the emitted order of a segment: its LDS reads, then its MFMAs with the VALU work between them
 template <int NREAD, int NMFMA, int NVALU>
 __device__ __forceinline__ void hd_pin() {
@@ -569,7 +534,7 @@ __global__ __launch_bounds__(512, 2) void head_f16_ring_kernel(HeadArgs a) {
     const int tile = blockIdx.x, img = blockIdx.y;
     const int m0 = img * a.pixels + tile * TN;
     const int K = a.K, nk = K / BK;
-    const unsigned smem_base = (unsigned)(size_t)(hd_lds_void_t*)smem;
+    const unsigned smem_base = lds_offset_of(smem);
     half_t* pro_lds = reinterpret_cast<half_t*>(smem + G::PRO_OFF);
     // joint group of this block: joints j0 .. j0 + jg - 1, sub-head rows c' = d * jg + j' <-> weight / bias row d * J + j0 + j'
     const int j0 = a.JG > 0 ? (int)blockIdx.z * a.JG : 0;
@@ -594,12 +559,12 @@ __global__ __launch_bounds__(512, 2) void head_f16_ring_kernel(HeadArgs a) {
     for (int i = 0; i < 3; ++i) {
         const int row = (wave + NW * i) * 8 + lrow;
         const int srow = src_row(row < cg ? row : cg - 1);
-        voffw[i] = (unsigned)(srow * K + ((lch ^ hd_swz(row)) * 8)) * 2u;
+        voffw[i] = (unsigned)(srow * K + ((lch ^ swz<64>(row)) * 8)) * 2u;
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int prow = ((wave + NW * i) * 8 + lrow) & (TN - 1);
-        voffx[i] = (unsigned)(prow * K + ((lch ^ hd_swz(prow)) * 8)) * 2u;
+        voffx[i] = (unsigned)(prow * K + ((lch ^ swz<64>(prow)) * 8)) * 2u;
     }
     const half_t* xbase = a.x + (size_t)m0 * K;
     const unsigned lds_wave = __builtin_amdgcn_readfirstlane(smem_base + wave * 8 * ROW_BYTES);
@@ -607,13 +572,13 @@ __global__ __launch_bounds__(512, 2) void head_f16_ring_kernel(HeadArgs a) {
         const unsigned base = lds_wave + slot_off;
         const half_t* xs = xbase + kt * BK;
         const half_t* ws = a.w + kt * BK;
-        hd_dma16s<WROWS * ROW_BYTES + 0 * 8192>(xs, voffx[0], base);      // the pixel rows first: first touch from HBM
-        if constexpr (G::NB > 1) hd_dma16s<WROWS * ROW_BYTES + 1 * 8192>(xs, voffx[1], base);
-        if constexpr (G::NB > 2) hd_dma16s<WROWS * ROW_BYTES + 2 * 8192>(xs, voffx[2], base);
-        if constexpr (G::NB > 3) hd_dma16s<WROWS * ROW_BYTES + 3 * 8192>(xs, voffx[3], base);
-        hd_dma16s<0 * 8192>(ws, voffw[0], base);
-        hd_dma16s<1 * 8192>(ws, voffw[1], base);
-        if (na == 3) hd_dma16s<2 * 8192>(ws, voffw[2], base);
+        dma16s<WROWS * ROW_BYTES + 0 * 8192>(xs, voffx[0], base);         // the pixel rows first: first touch from HBM
+        if constexpr (G::NB > 1) dma16s<WROWS * ROW_BYTES + 1 * 8192>(xs, voffx[1], base);
+        if constexpr (G::NB > 2) dma16s<WROWS * ROW_BYTES + 2 * 8192>(xs, voffx[2], base);
+        if constexpr (G::NB > 3) dma16s<WROWS * ROW_BYTES + 3 * 8192>(xs, voffx[3], base);
+        dma16s<0 * 8192>(ws, voffw[0], base);
+        dma16s<1 * 8192>(ws, voffw[1], base);
+        if (na == 3) dma16s<2 * 8192>(ws, voffw[2], base);
     };
     static_assert(G::NA_LO == 2, "two weight groups per wave at least, a third for the first GA % 8 waves");
     constexpr int NW_LO = G::NA_LO + G::NB, NW_HI = G::NA_HI + G::NB;     // DMA instructions per wave and K step
@@ -633,8 +598,8 @@ __global__ __launch_bounds__(512, 2) void head_f16_ring_kernel(HeadArgs a) {
     {
         const int idx = (wave & 3) * 512 + lane * 8;
         const unsigned dst = __builtin_amdgcn_readfirstlane(smem_base + G::PRO_OFF + (wave >> 2) * 4096 + (wave & 3) * 1024);
-        hd_dma16s<0>(wave < 4 ? a.pro_scale : a.pro_shift, (unsigned)((idx < K ? idx : 0) * 2), dst);
-        if (a.JG == 0) hd_dma16s<0>(a.bias, (unsigned)((lane * 4 < a.C ? lane * 4 : 0) * 4), smem_base + G::BIAS_OFF);
+        dma16s<0>(wave < 4 ? a.pro_scale : a.pro_shift, (unsigned)((idx < K ? idx : 0) * 2), dst);
+        if (a.JG == 0) dma16s<0>(a.bias, (unsigned)((lane * 4 < a.C ? lane * 4 : 0) * 4), smem_base + G::BIAS_OFF);
     }
 #pragma unroll
     for (int st = 0; st < STAGES; ++st) issue_step(st * STAGE_BYTES, st < nk ? st : nk - 1);
@@ -650,12 +615,12 @@ __global__ __launch_bounds__(512, 2) void head_f16_ring_kernel(HeadArgs a) {
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             const int row = i * 32 + frag_row;
-            a_addr[ph][i] = row * ROW_BYTES + ((chunk ^ hd_swz(row)) << 4);
+            a_addr[ph][i] = row * ROW_BYTES + ((chunk ^ swz<64>(row)) << 4);
         }
 #pragma unroll
         for (int t = 0; t < PT; ++t) {
             const int brow = (pg * PT + t) * 32 + frag_row;
-            b_addr[ph][t] = WROWS * ROW_BYTES + brow * ROW_BYTES + ((chunk ^ hd_swz(brow)) << 4);
+            b_addr[ph][t] = WROWS * ROW_BYTES + brow * ROW_BYTES + ((chunk ^ swz<64>(brow)) << 4);
         }
     }
     // A wave's work is a chain of PHASES (K step k, ph): 5 PT MFMAs = five weight fragments against its PT pixel fragments.  The
@@ -710,7 +675,7 @@ __global__ __launch_bounds__(512, 2) void head_f16_ring_kernel(HeadArgs a) {
         mma(par_c, I2{});
         hd_pin<1, PT, 4>();
         if constexpr (LAST) {
-            if (na_hi) hd_wait_barrier<(STAGES - 2) * NW_HI>(); else hd_wait_barrier<(STAGES - 2) * NW_LO>();
+            if (na_hi) wait_vm_and_barrier<(STAGES - 2) * NW_HI>(); else wait_vm_and_barrier<(STAGES - 2) * NW_LO>();
             issue_step(cur, k + STAGES < nk ? k + STAGES : nk - 1);
         }
         rd_a(PQ{}, I0{}, noff, NPH{});
@@ -750,7 +715,7 @@ __global__ __launch_bounds__(512, 2) void head_f16_ring_kernel(HeadArgs a) {
             cur = nxt2;
         }
     }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the re-requested tail has landed everywhere: the
+    wait_vm_and_barrier<0>();     // the re-requested tail has landed everywhere: the
                                                                                  // logits tiles overlay the ring
 
     // ---- K-parts -> fp32 logits (+ bias) of the group's 32 pixels, then the per-joint statistics, 32 pixels at a time ----

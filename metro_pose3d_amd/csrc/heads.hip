@@ -14,6 +14,7 @@
 // tensors TF hands to the py_func: no FMA contraction anywhere in this file.
 // One thread per pose (E, J <= 64): the work is a few hundred flops per pose, the point is parity, not speed.
 #include "metro_common.h"
+#include "gfx950_prims.h"
 
 #pragma clang fp contract(off)
 

@@ -1,12 +1,9 @@
 // HBM-bound kernels of the path: input preparation, zero-padded max-pool, and the
 // softmax-over-volume + expectation soft-argmax with mm decode.
 #include "metro_common.h"
+#include "gfx950_prims.h"
 
 namespace metro {
-
-typedef _Float16 half_t;
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------
 // fp32 NHWC [n,side,side,3] -> fp16 [n,side+6,side+8,4], zero border (3 top/left, 3/5
@@ -241,8 +238,6 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_zeropad_kernel(const VecT* _
     }
 }
 
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef double doublex2 __attribute__((ext_vector_type(2)));
 
 int launch_maxpool(const void* in, void* out, int n, int h_in, int w_in, int c, int dtype,

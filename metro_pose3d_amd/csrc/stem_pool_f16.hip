@@ -16,16 +16,9 @@
 #include <type_traits>
 
 #include "metro_common.h"
+#include "gfx950_prims.h"
 
 namespace metro {
-
-typedef _Float16 half_t;
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-__device__ __attribute__((aligned(16))) unsigned int g_zero_page_sp[4];   // zero-initialised
 
 namespace sp {
 constexpr int MG = 4;                         // wave groups over the pixel tiles (tiles mg, mg+4, mg+8)
@@ -61,34 +54,19 @@ struct StemPoolArgs {
     int n_patches;
 };
 
-__device__ __forceinline__ void sp_dma16(const void* gsrc, unsigned lds_addr) {
-    asm volatile(
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %0, off"
-        :
-        : "v"(gsrc), "s"(lds_addr));
-}
-template <int N>
-__device__ __forceinline__ void sp_wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 // wave-uniform n in [0, 8]
 __device__ __forceinline__ void sp_wait_vm_dyn(int n) {
     switch (n) {
-        case 0: sp_wait_vm<0>(); break;
-        case 1: sp_wait_vm<1>(); break;
-        case 2: sp_wait_vm<2>(); break;
-        case 3: sp_wait_vm<3>(); break;
-        case 4: sp_wait_vm<4>(); break;
-        case 5: sp_wait_vm<5>(); break;
-        case 6: sp_wait_vm<6>(); break;
-        case 7: sp_wait_vm<7>(); break;
-        default: sp_wait_vm<8>(); break;
+        case 0: wait_vm<0>(); break;
+        case 1: wait_vm<1>(); break;
+        case 2: wait_vm<2>(); break;
+        case 3: wait_vm<3>(); break;
+        case 4: wait_vm<4>(); break;
+        case 5: wait_vm<5>(); break;
+        case 6: wait_vm<6>(); break;
+        case 7: wait_vm<7>(); break;
+        default: wait_vm<8>(); break;
     }
-}
-__device__ __forceinline__ void sp_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
 // NSPLIT = 1: 4 waves, each holds both 32-cout weight tiles (112 VGPRs) and reuses every pixel fragment twice;
@@ -102,8 +80,7 @@ __global__ __launch_bounds__(64 * sp::MG * NSPLIT, 2 * NSPLIT) void stem_pool_f1
     constexpr int NW = MG * NSPLIT, NT = 64 * NW, CT = 2 / NSPLIT;
     constexpr int PS = 512 / NT;                  // pooled stores per wave per patch
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef __attribute__((address_space(3))) void lds_void_t;
-    const unsigned smem_base = (unsigned)(size_t)(lds_void_t*)smem;
+    const unsigned smem_base = lds_offset_of(smem);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -111,7 +88,7 @@ __global__ __launch_bounds__(64 * sp::MG * NSPLIT, 2 * NSPLIT) void stem_pool_f1
     const int G = gridDim.x;
     int p = blockIdx.x;
     if (p >= a.n_patches) return;
-    const half_t* zero = reinterpret_cast<const half_t*>(g_zero_page_sp);
+    const half_t* zero = reinterpret_cast<const half_t*>(g_zero_page);
     const int hp = a.side + 6, wp = a.side + 8;          // bordered image
     const int ps = a.side / 4;                           // pooled side
     const int ppr = ps / PP;                             // patches per row
@@ -143,7 +120,7 @@ __global__ __launch_bounds__(64 * sp::MG * NSPLIT, 2 * NSPLIT) void stem_pool_f1
                 const int wr = c / (WIN_C / 2), wc = (c - wr * (WIN_C / 2)) * 2;
                 const int y = r0 + wr, x = c0 + wc;
                 const bool ok = c < WIN_CHUNKS && (unsigned)y < (unsigned)hp && (unsigned)x < (unsigned)wp;
-                sp_dma16(ok ? base + ((size_t)y * wp + x) * 4 : zero,
+                dma16(ok ? base + ((size_t)y * wp + x) * 4 : zero,
                          __builtin_amdgcn_readfirstlane(smem_base + WIN_OFF + buf * WIN_BYTES + q * 1024));
             }
         }
@@ -195,7 +172,7 @@ __global__ __launch_bounds__(64 * sp::MG * NSPLIT, 2 * NSPLIT) void stem_pool_f1
             const int next_dma = p + G < a.n_patches ? nw : 0;
             sp_wait_vm_dyn((it == 0 ? 0 : it == 1 ? PS : 2 * PS) + next_dma);
         }
-        sp_barrier();
+        wait_lgkm_and_barrier();
         if constexpr (RAW) {
             if (p + G < a.n_patches) raw_fetch(p + G);
         } else {
@@ -269,7 +246,7 @@ __global__ __launch_bounds__(64 * sp::MG * NSPLIT, 2 * NSPLIT) void stem_pool_f1
             }
             }
         }
-        sp_barrier();
+        wait_lgkm_and_barrier();
         // ---- pool: (pooled pixel, 8-channel chunk) items, zero where the conv position is outside -------
 #pragma unroll
         for (int r = 0; r < PS; ++r) {
@@ -350,8 +327,6 @@ constexpr int LDS_BYTES = EDGE_OFF + EDGE_BYTES;          // 81 536: two blocks 
 static_assert(2 * LDS_BYTES <= 160 * 1024, "two blocks per CU");
 }  // namespace sp2
 
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-
 // packed fp16 max as the instruction (the builtin canonicalises both operands first: a third of the pooling's VALU work)
 __device__ __forceinline__ half2_t sp2_max(half2_t a, half2_t b) {
     half2_t r;
@@ -379,8 +354,7 @@ __device__ __forceinline__ half2_t sp2_xchg32(half2_t v) {          // the value
 __global__ __launch_bounds__(sp2::NT, 2) void stem_pool_rows_kernel(StemPoolArgs a) {
     using namespace sp2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef __attribute__((address_space(3))) void lds_void_t;
-    const unsigned smem_base = (unsigned)(size_t)(lds_void_t*)smem;
+    const unsigned smem_base = lds_offset_of(smem);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // x-tile: conv columns 32 w ..., pooled columns 16 w ...
@@ -394,7 +368,7 @@ __global__ __launch_bounds__(sp2::NT, 2) void stem_pool_rows_kernel(StemPoolArgs
         if (wave < 3) {
             const int ic = i < 0 ? 0 : i > SIDE - 1 ? SIDE - 1 : i;
             const float* src = crop + (size_t)ic * SIDE * 3 + wave * 256 + lane * 4;
-            sp_dma16(src, __builtin_amdgcn_readfirstlane(smem_base + STG_OFF + slot * SROW + wave * 1024));
+            dma16(src, __builtin_amdgcn_readfirstlane(smem_base + STG_OFF + slot * SROW + wave * 1024));
         }
     };
     // window row p (bordered: crop row p - 3) from a staging slot: thread = pixel.  Read and write are separate steps: the steady
@@ -450,21 +424,21 @@ __global__ __launch_bounds__(sp2::NT, 2) void stem_pool_rows_kernel(StemPoolArgs
     // zero window (the borders stay zero: the cast only writes the 256 interior pixels of a row); the -inf row of the edge table
     for (int i = tid; i < NWR * WROW / 16; i += NT) reinterpret_cast<uint4*>(smem + WIN_OFF)[i] = make_uint4(0, 0, 0, 0);
     if (tid < 32) reinterpret_cast<unsigned*>(smem + EDGE_OFF + NW * 128)[tid] = 0xfc00fc00u;
-    sp_wait_vm<0>();
+    wait_vm<0>();
     // every ordinary load is waited for HERE: a compiler-placed wait at the first use inside the row loop would be a vmcnt(0) per row
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int kk = 0; kk < KK; ++kk) asm volatile("" : "+v"(wf[i][kk]));
     asm volatile("" : "+v"(bias_l[0]), "+v"(bias_l[1]));
-    sp_barrier();
+    wait_lgkm_and_barrier();
 #pragma unroll
     for (int r = 0; r < 11; ++r) {
         half4_t v;
         cast_read(plo + r, r, v);
         cast_write(plo + r, v);
     }
-    sp_barrier();            // the staging slots are free again, the window rows visible
+    wait_lgkm_and_barrier();  // the staging slots are free again, the window rows visible
     issue_group(0);
     issue_group(1);
 
@@ -645,8 +619,8 @@ __global__ __launch_bounds__(sp2::NT, 2) void stem_pool_rows_kernel(StemPoolArgs
         // the crop rows cast in this iteration were requested two iterations ago: one iteration of requests (4) is younger.  The
         // pooled-row stores in between are not counted: requests land in order among themselves, so "at most 4 operations
         // outstanding" implies this group has landed whatever the stores do
-        if (wave < 3) sp_wait_vm<4>();
-        sp_barrier();            // ... and everybody's share has landed; the last pooled row's tile is complete
+        if (wave < 3) wait_vm<4>();
+        wait_lgkm_and_barrier();  // ... and everybody's share has landed; the last pooled row's tile is complete
         SP2_CLK(1);
         half8_t sv[2];
         half4_t cv[4];
@@ -665,7 +639,7 @@ __global__ __launch_bounds__(sp2::NT, 2) void stem_pool_rows_kernel(StemPoolArgs
         SP2_CLK(4);
         // vertical 3-max; lane n holds (X, X + 1) of channel n: the lane pair (n, n ^ 1) swaps one column so that the even lane
         // writes column X of channels (n, n + 1) and the odd lane column X + 1 of (n - 1, n): one 4-byte write per quad
-        sp_barrier();            // every wave has read the last pooled row out of the tile (at the top of this iteration)
+        wait_lgkm_and_barrier();  // every wave has read the last pooled row out of the tile (at the top of this iteration)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -682,7 +656,7 @@ __global__ __launch_bounds__(sp2::NT, 2) void stem_pool_rows_kernel(StemPoolArgs
         }
         SP2_CLK(5);
     }
-    sp_barrier();
+    wait_lgkm_and_barrier();
     {
         half8_t sv[2];
         store_read(sv);
