@@ -434,6 +434,49 @@ int  metro_heatmap_to_25d(const float* d_coords01, int32_t n, const MetroSpec* s
 int  metro_to_orig_cam(const float* d_coords, const float* d_rot, const int32_t* d_mirror, float* d_out, int32_t n,
                        int32_t n_joints, void* stream);
 
+/* ---- absolute poses and frame keypoints of crops cut from full frames (the reference's test path with a calibrated camera:
+ *      src/data/data_loading.py:110-112 hands each crop's virtual camera to src/model/volumetric.py:171-216) ---- */
+/* metro_forward that ALSO writes the soft-argmax coordinates in [0,1] (what metro_softargmax01 returns: head joint order,
+ * (x, y, z); volumetric.py:234-235) to d_coords01_out fp32 [n, n_joints_head, 3], from the finalize launch the forward runs
+ * anyway (every precision; no extra launch).  d_poses_out gets the bits metro_forward writes.  Captured forwards
+ * (metro_plan_set_graph_max_batch) are keyed on d_coords01_out too. */
+int  metro_forward_coords01(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out,
+                            float* d_coords01_out, void* d_workspace, void* stream);
+/* One record per crop (host code: frames.placement_params): the crop's virtual camera and the way back to its frame. */
+typedef struct MetroPlacement {
+    int32_t keypoint_mode;      /* METRO_WARP_HOMOGRAPHY: keypoints through `homography`; METRO_WARP_DISTORTED: through
+                                 * rot_to_orig_cam, intrinsics and distortion (an original camera with coefficients) */
+    int32_t reserved;
+    float inv_intrinsics[9];    /* row-major inverse K of the virtual camera, fp32 (data_loading.py:112)                   */
+    float rot_to_orig_cam[9];   /* orig.R virt.R^T (data_loading.py:110)                                                   */
+    float rot_to_world[9];      /* virt.R^T (data_loading.py:111)                                                          */
+    float cam_loc[3];           /* the camera centre in world coordinates, virt.t = orig.t (volumetric.py:206-208)         */
+    float homography[9];        /* HOMOGRAPHY: row-major, crop pixel (x, y, 1) -> frame pixel (the warp's matrix)           */
+    float intrinsics[6];        /* DISTORTED: the original camera's K[0,0] K[0,1] K[0,2] K[1,0] K[1,1] K[1,2]              */
+    float distortion[5];        /* DISTORTED: k1 k2 p1 p2 k3 (OpenCV order)                                                 */
+} MetroPlacement;               /* 208 bytes */
+#define METRO_SCALE_METRO 0             /* root-relative: the engine's poses (--scale-recovery=metro)                       */
+#define METRO_SCALE_BONE_LENGTHS 1      /* --scale-recovery=bone-lengths (volumetric.py:171-191)                            */
+#define METRO_SCALE_TRUE_ROOT_DEPTH 2   /* --scale-recovery=true-root-depth (volumetric.py:192-199)                         */
+#define METRO_COORDS_CROP 0             /* the crop's virtual camera                                                        */
+#define METRO_COORDS_CAMERA 1           /* the original camera: to_orig_cam(x, rot_to_orig_cam) (volumetric.py:204-205)     */
+#define METRO_COORDS_WORLD 2            /* to_orig_cam(x, rot_to_world) (+ cam_loc for absolute poses, volumetric.py:206-208) */
+/* n crops in one launch.  d_coords01 fp32 [n, n_joints_head, 3] (metro_forward_coords01); d_poses the engine's fp32
+ * [n, n_joints_out, 3] (read in METRO_SCALE_METRO only, else may be NULL); d_records DEVICE array of n MetroPlacement.
+ * scale_recovery METRO_SCALE_*:
+ *   BONE_LENGTHS     d_bone_lengths fp64 [n_edges] or [n, n_edges] (per_pose_lengths != 0), d_edges int32 [n_edges, 2] head
+ *                    joint indices; the z offset of metro_backproject_bone_lengths (same operations, same bits);
+ *   TRUE_ROOT_DEPTH  d_root_depth fp32 [n]: the root's z in mm in the virtual camera;
+ *   METRO            the engine's root-relative poses, rotated as metro_to_orig_cam does.
+ * coords METRO_COORDS_*; d_mirror int32 [n_joints_out] output-order mirror joints (to_orig_cam when det R <= 0).
+ * d_poses_out fp32 [n, n_joints_out, 3] (output joint order; BONE_LENGTHS in CROP coords = metro_backproject_bone_lengths
+ * with root_relative 0, permute 1); d_keypoints_out fp32 [n, n_joints_out, 2] frame pixels of heatmap_to_image(coords01.xy)
+ * (NaN where the ray lies behind the original camera) or NULL; d_z_offset_out fp32 [n] (absolute modes) or NULL. */
+int  metro_place_poses(const float* d_coords01, const float* d_poses, const MetroPlacement* d_records, int32_t n,
+                       const MetroSpec* spec, int32_t scale_recovery, const double* d_bone_lengths, int32_t per_pose_lengths,
+                       const float* d_root_depth, const int32_t* d_edges, int32_t n_edges, const int32_t* d_mirror,
+                       int32_t coords, float* d_poses_out, float* d_keypoints_out, float* d_z_offset_out, void* stream);
+
 const char* metro_last_error(void);
 int32_t metro_abi_version(void);
 

@@ -73,6 +73,16 @@ class MetroCropWarp(C.Structure):
                 ('intrinsics', C.c_float * 6), ('distortion', C.c_float * 5)]
 
 
+METRO_SCALE_METRO, METRO_SCALE_BONE_LENGTHS, METRO_SCALE_TRUE_ROOT_DEPTH = 0, 1, 2
+METRO_COORDS_CROP, METRO_COORDS_CAMERA, METRO_COORDS_WORLD = 0, 1, 2
+
+
+class MetroPlacement(C.Structure):
+    _fields_ = [('keypoint_mode', C.c_int32), ('reserved', C.c_int32), ('inv_intrinsics', C.c_float * 9),
+                ('rot_to_orig_cam', C.c_float * 9), ('rot_to_world', C.c_float * 9), ('cam_loc', C.c_float * 3),
+                ('homography', C.c_float * 9), ('intrinsics', C.c_float * 6), ('distortion', C.c_float * 5)]
+
+
 # symbol -> (restype, argtypes); must list every function include/metro_hip.h declares
 _P = C.c_void_p
 SIGNATURES = {
@@ -91,6 +101,7 @@ SIGNATURES = {
     'metro_last_kernel_id': (C.c_char_p, []),
     'metro_plan_set_graph_max_batch': (C.c_int, [_P, C.c_int32]),
     'metro_forward': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
+    'metro_forward_coords01': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     'metro_forward_status': (C.c_int, [_P, _P, C.c_int32, _P, C.POINTER(C.c_int32)]),
     'metro_plan_status_offset': (C.c_int64, [_P]),
     'metro_forward_upto': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32]),
@@ -119,6 +130,8 @@ SIGNATURES = {
                                                  C.c_int32, C.c_int32, _P, _P, _P]),
     'metro_backproject_root_depth': (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(MetroSpec), C.c_int32, C.c_int32, _P, _P]),
     'metro_to_orig_cam': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
+    'metro_place_poses': (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(MetroSpec), C.c_int32, _P, C.c_int32, _P, _P, C.c_int32,
+                                    _P, C.c_int32, _P, _P, _P, _P]),
     'metro_heatmap_to_25d': (C.c_int, [_P, C.c_int32, C.POINTER(MetroSpec), _P, _P]),
     'metro_head_f16_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     'metro_head_f16': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(MetroSpec), _P, _P, _P, _P]),

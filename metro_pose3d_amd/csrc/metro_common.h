@@ -394,6 +394,10 @@ int launch_backproject(const float* coords01, const float* inv_k, const double* 
                        int root_relative, int permute, float* out, float* z_out, hipStream_t stream);
 int launch_heatmap_to_25d(const float* coords01, float* out, int n, const MetroSpec& spec, hipStream_t stream);
 int launch_to_orig_cam(const float* x, const float* rot, const int* mirror, float* out, int n, int nj, hipStream_t stream);
+// absolute poses + frame keypoints of frame crops (place_poses.hip)
+int launch_place_poses(const float* coords01, const float* poses, const MetroPlacement* rec, int n, const MetroSpec& spec,
+                       int scale, const double* targets, int per_pose_targets, const float* root_z, const int* edges, int ne,
+                       const int* mirror, int coords, float* out, float* keypoints, float* z_out, hipStream_t stream);
 SoftArgmaxArgs make_softargmax_args(const MetroSpec& spec, int n);
 
 }  // namespace metro

@@ -118,6 +118,7 @@ struct GraphEntry {
     int n;
     const void* images;
     const void* poses;
+    const void* coords01;    // metro_forward_coords01's output (NULL for metro_forward): baked into the finalize launch
     const void* ws;
     hipStream_t stream;
     hipGraphExec_t exec;
@@ -681,7 +682,9 @@ int build_plan(MetroPlan* p) {
 
 // One layer of the plan at batch n.  `dump` (metro_forward_upto stopping at this layer): launches whose intermediate tensors live on
 // chip also write them out -- the fp32 logits of the one-launch head, conv1's output of a conv1+conv2 launch.
-int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* images, int n, float* poses, char* ws, hipStream_t stream, bool dump) {
+// `coords01` (optional): the finalize launch also writes the soft-argmax coordinates in [0,1] there (metro_forward_coords01).
+int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* images, int n, float* poses, char* ws, hipStream_t stream, bool dump,
+                 float* coords01 = nullptr) {
     const Layer& L = p->layers[li];
     auto slot_ptr = [&](int slot) -> void* {
         if (slot == S_IMAGES) return const_cast<float*>(images);
@@ -757,11 +760,11 @@ int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* 
             const SoftArgmaxArgs a = make_softargmax_args(p->spec, n);
             if (L.form == LayerForm::Head)
                 return launch_softargmax_finalize(static_cast<const float*>(slot_ptr(S_PART)), a,
-                                                  head_f16_records(n, L.head_c_in, a.depth * a.n_joints_head, a.side), poses, stream, nullptr,
+                                                  head_f16_records(n, L.head_c_in, a.depth * a.n_joints_head, a.side), poses, stream, coords01,
                                                   static_cast<int32_t*>(slot_ptr(S_STATUS)));
             // precise: 0 fp32 / fp32, 1 fp32 logits + fp64 accumulators (F32 and F32M modes), 2 fp64 / fp64
             return launch_softargmax(slot_ptr(L.in_slot), a, p->spec.precision == METRO_PREC_F32M ? 1 : p->spec.precision, slot_ptr(S_PART), poses, stream,
-                                     nullptr, static_cast<int32_t*>(slot_ptr(S_STATUS)));
+                                     coords01, static_cast<int32_t*>(slot_ptr(S_STATUS)));
         }
     }
     set_error("internal: layer %d has unknown kind %d", li, L.kind);
@@ -769,7 +772,7 @@ int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* 
 }
 
 int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_, hipStream_t stream,
-               int last_layer, float* ms_out) {
+               int last_layer, float* ms_out, float* coords01 = nullptr) {
     METRO_CHECK_ARG(p != nullptr, "plan is NULL");
     METRO_CHECK_ARG(n > 0 && n <= p->max_batch, "batch %d outside [1, %d]", n, p->max_batch);
     METRO_CHECK_ARG(images != nullptr && ws_ != nullptr, "NULL images/workspace pointer");
@@ -786,7 +789,7 @@ int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_
     int st = METRO_OK;
     for (int li = 0; li <= last_layer && st == METRO_OK; ++li) {
         if (ms_out) METRO_HIP_CHECK(hipEventRecord(ev[2 * li], stream));
-        st = launch_layer(p, p->d_params, li, images, n, poses, ws, stream, li == last_layer && li + 1 < nl);
+        st = launch_layer(p, p->d_params, li, images, n, poses, ws, stream, li == last_layer && li + 1 < nl, coords01);
         if (ms_out) METRO_HIP_CHECK(hipEventRecord(ev[2 * li + 1], stream));
     }
     if (ms_out) {
@@ -910,33 +913,33 @@ int metro_plan_set_graph_max_batch(MetroPlan* plan, int32_t max_batch_for_graphs
     return METRO_OK;
 }
 
-int metro_forward(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out,
-                  void* d_workspace, void* stream_) {
+static int forward_impl(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out, float* d_coords01,
+                        void* d_workspace, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (plan == nullptr || n > plan->graph_max_batch || n < 1)
-        return run_layers(plan, d_images_nhwc, n, d_poses_out, d_workspace, stream, -1, nullptr);
+        return run_layers(plan, d_images_nhwc, n, d_poses_out, d_workspace, stream, -1, nullptr, d_coords01);
     // small batches are launch-latency bound (57 dependent launches): replay a captured hipGraph
     GraphEntry* hit = nullptr;
     for (GraphEntry& g : plan->graphs)
-        if (g.n == n && g.images == d_images_nhwc && g.poses == d_poses_out && g.ws == d_workspace)
+        if (g.n == n && g.images == d_images_nhwc && g.poses == d_poses_out && g.coords01 == d_coords01 && g.ws == d_workspace)
             hit = &g;
     if (hit == nullptr) {
         if (plan->graphs.size() >= 16) {            // bounded cache: drop the oldest capture
             if (plan->graphs.front().exec) (void)hipGraphExecDestroy(plan->graphs.front().exec);
             plan->graphs.erase(plan->graphs.begin());
         }
-        plan->graphs.push_back(GraphEntry{n, d_images_nhwc, d_poses_out, d_workspace, stream, nullptr, 0});
+        plan->graphs.push_back(GraphEntry{n, d_images_nhwc, d_poses_out, d_coords01, d_workspace, stream, nullptr, 0});
         hit = &plan->graphs.back();
     }
     if (hit->exec == nullptr) {
         if (hit->eager_runs == 0) {                  // first sight of this key: plain launches (sets kernel attributes)
             hit->eager_runs = 1;
-            return run_layers(plan, d_images_nhwc, n, d_poses_out, d_workspace, stream, -1, nullptr);
+            return run_layers(plan, d_images_nhwc, n, d_poses_out, d_workspace, stream, -1, nullptr, d_coords01);
         }
         hipGraph_t graph = nullptr;
         if (plan->cap_stream == nullptr) METRO_HIP_CHECK(hipStreamCreateWithFlags(&plan->cap_stream, hipStreamNonBlocking));
         METRO_HIP_CHECK(hipStreamBeginCapture(plan->cap_stream, hipStreamCaptureModeThreadLocal));
-        const int st = run_layers(plan, d_images_nhwc, n, d_poses_out, d_workspace, plan->cap_stream, -1, nullptr);
+        const int st = run_layers(plan, d_images_nhwc, n, d_poses_out, d_workspace, plan->cap_stream, -1, nullptr, d_coords01);
         const hipError_t e = hipStreamEndCapture(plan->cap_stream, &graph);
         if (st != METRO_OK) { if (graph) (void)hipGraphDestroy(graph); return st; }
         if (e != hipSuccess) { set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return METRO_ERR_HIP; }
@@ -946,6 +949,17 @@ int metro_forward(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float*
     }
     METRO_HIP_CHECK(hipGraphLaunch(hit->exec, stream));
     return METRO_OK;
+}
+
+int metro_forward(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out,
+                  void* d_workspace, void* stream) {
+    return forward_impl(plan, d_images_nhwc, n, d_poses_out, nullptr, d_workspace, stream);
+}
+
+int metro_forward_coords01(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out,
+                           float* d_coords01_out, void* d_workspace, void* stream) {
+    METRO_CHECK_ARG(d_coords01_out != nullptr && d_poses_out != nullptr, "metro_forward_coords01: NULL poses / coords01 pointer");
+    return forward_impl(plan, d_images_nhwc, n, d_poses_out, d_coords01_out, d_workspace, stream);
 }
 
 int metro_forward_status(const MetroPlan* plan, const void* d_workspace, int32_t n, void* stream_, int32_t* n_nonfinite_out) {
@@ -1286,6 +1300,27 @@ int metro_to_orig_cam(const float* d_coords, const float* d_rot, const int32_t* 
     METRO_CHECK_ARG(d_coords && d_rot && d_mirror && d_out && n > 0 && n_joints >= 1 && n_joints <= 64,
                     "to_orig_cam: bad argument (1 <= joints <= 64)");
     return launch_to_orig_cam(d_coords, d_rot, d_mirror, d_out, n, n_joints, static_cast<hipStream_t>(stream));
+}
+
+int metro_place_poses(const float* d_coords01, const float* d_poses, const MetroPlacement* d_records, int32_t n,
+                      const MetroSpec* spec, int32_t scale_recovery, const double* d_bone_lengths, int32_t per_pose_lengths,
+                      const float* d_root_depth, const int32_t* d_edges, int32_t n_edges, const int32_t* d_mirror,
+                      int32_t coords, float* d_poses_out, float* d_keypoints_out, float* d_z_offset_out, void* stream) {
+    const bool bones = scale_recovery == METRO_SCALE_BONE_LENGTHS;
+    int st = check_head_args(spec, n, bones ? n_edges : 0, "place_poses");
+    if (st) return st;
+    METRO_CHECK_ARG(scale_recovery >= METRO_SCALE_METRO && scale_recovery <= METRO_SCALE_TRUE_ROOT_DEPTH,
+                    "place_poses: scale_recovery must be METRO_SCALE_METRO, _BONE_LENGTHS or _TRUE_ROOT_DEPTH (got %d)", scale_recovery);
+    METRO_CHECK_ARG(coords >= METRO_COORDS_CROP && coords <= METRO_COORDS_WORLD,
+                    "place_poses: coords must be METRO_COORDS_CROP, _CAMERA or _WORLD (got %d)", coords);
+    METRO_CHECK_ARG(d_coords01 && d_records && d_poses_out && (coords == METRO_COORDS_CROP || d_mirror),
+                    "place_poses: NULL coords01 / records / poses_out / mirror pointer");
+    METRO_CHECK_ARG(scale_recovery != METRO_SCALE_METRO || d_poses, "place_poses: METRO_SCALE_METRO reads the engine's poses: NULL");
+    METRO_CHECK_ARG(!bones || (d_bone_lengths && d_edges && n_edges >= 1), "place_poses: bone-lengths needs lengths and >= 1 edge");
+    METRO_CHECK_ARG(scale_recovery != METRO_SCALE_TRUE_ROOT_DEPTH || d_root_depth, "place_poses: true-root-depth needs root depths");
+    return launch_place_poses(d_coords01, d_poses, d_records, n, *spec, scale_recovery, d_bone_lengths, per_pose_lengths != 0,
+                              d_root_depth, d_edges, bones ? n_edges : 0, d_mirror, coords, d_poses_out, d_keypoints_out,
+                              d_z_offset_out, static_cast<hipStream_t>(stream));
 }
 
 const char* metro_last_error(void) { return metro::get_error(); }

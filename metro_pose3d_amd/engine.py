@@ -170,17 +170,29 @@ class Engine:
             raise ValueError(f'batch {images.shape[0]} outside [1, {self.max_batch}]')
         return images.contiguous()
 
-    def forward(self, images: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward(self, images: torch.Tensor, out: Optional[torch.Tensor] = None,
+                coords01: Optional[torch.Tensor] = None) -> torch.Tensor:
         """images fp32 [n,256,256,3] on the plan's device -> poses fp32 [n,Jout,3] (mm).  Enqueued
-        on torch's current stream; no synchronisation."""
+        on torch's current stream; no synchronisation.  `coords01`: an fp32 [n, J_head, 3] device tensor that also receives
+        the soft-argmax coordinates in [0,1] (head order; metro_forward_coords01: the same poses, from the same launches)."""
         images = self._check_images(images)
         n = images.shape[0]
         if out is None:
             out = torch.empty((n, self.spec.skeleton.n_out, 3), dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        check(self.lib.metro_forward(self._plan, C.c_void_p(images.data_ptr()), n,
-                                     C.c_void_p(out.data_ptr()), C.c_void_p(self._ws.data_ptr()),
-                                     C.c_void_p(stream)), 'metro_forward')
+        if coords01 is None:
+            check(self.lib.metro_forward(self._plan, C.c_void_p(images.data_ptr()), n,
+                                         C.c_void_p(out.data_ptr()), C.c_void_p(self._ws.data_ptr()),
+                                         C.c_void_p(stream)), 'metro_forward')
+            return out
+        shape = (n, self.spec.skeleton.n_head, 3)
+        if (not isinstance(coords01, torch.Tensor) or coords01.dtype != torch.float32 or tuple(coords01.shape) != shape
+                or coords01.device != self.device or not coords01.is_contiguous()):
+            raise ValueError(f'coords01 must be a contiguous float32 {list(shape)} tensor on {self.device}, got '
+                             f'{getattr(coords01, "dtype", type(coords01))} {tuple(getattr(coords01, "shape", ()))}')
+        check(self.lib.metro_forward_coords01(self._plan, C.c_void_p(images.data_ptr()), n, C.c_void_p(out.data_ptr()),
+                                              C.c_void_p(coords01.data_ptr()), C.c_void_p(self._ws.data_ptr()),
+                                              C.c_void_p(stream)), 'metro_forward_coords01')
         return out
 
     def check_finite(self, n: int) -> None:

@@ -9,6 +9,10 @@ the box centre, drops the lens distortion, squares the pixels and zooms so the b
   crop_params                             per-crop warp mode + matrices and the rotations back (data_loading.py:110-111)
   warp_frames                             one HIP launch (metro_warp_crops_frames_u8) for the crops of many frames
   estimate_pose_in_frames                 the whole chain on one device, enqueued on the current stream
+  placement_params                        per-crop virtual camera (inverse K, rotations, camera centre) and the way back to the
+                                          frame's pixels (MetroPlacement records)
+  locate_poses_in_frames                  absolute poses (bone-lengths / true-root-depth scale recovery, volumetric.py:171-208)
+                                          and 2D frame keypoints, one metro_place_poses launch after the forward
 
 Divergences from the reference, on purpose:
   * a Camera built from intrinsics alone (no R, no t) defaults to world_up = (0, -1, 0), not the reference's (0, 0, 1): with
@@ -16,14 +20,21 @@ Divergences from the reference, on purpose:
   * reproject_image's case 1 (cameralib.py:282-293: an all-zero coefficient array whose virtual R is allclose to the original
     goes to cv2.warpAffine, with INTER_AREA when zooming out) is not reproduced: any coefficient array takes the general mode;
   * a general-mode ray that points behind the camera (z <= 0) samples the border value 0; the reference projects it through
-    the origin.
+    the origin;
+  * likewise a keypoint whose ray lies behind the original camera (z <= 0; w <= 0 after the crop -> frame homography) comes
+    out of locate_poses_in_frames as NaN; the reference's reproject_image_points projects it through the origin;
+  * keypoints of undistorted cameras go through the crop -> frame homography, the mapping the reference's general branch
+    `orig.world_to_image(virt.image_to_world(p))` computes; its dispatcher would send them to reproject_image_points_fast
+    (cameralib.py:432-438), which maps in the OPPOSITE direction to its docstring (H = old new^-1, i.e. frame -> crop when
+    called as (points, virtual, original)): that inverted fast path is not reproduced.
 """
 from __future__ import annotations
 
 import copy
 import ctypes as C
 import os
-from typing import NamedTuple, Optional, Sequence
+from collections import OrderedDict
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -192,12 +203,41 @@ def crop_params(cameras, boxes, frame_index, side: int = 256) -> CropParams:
     :294-306: partial_homography = old.R inv(new.R) inv(new.K), float64), as the test at :272 sends it there.
     rot_to_orig_cam = orig.R virt.R^T and rot_to_world = virt.R^T (data_loading.py:110-111).
     cameras=None: the axis-aligned square crop of preprocess.box_homography, rotations I."""
+    return _frame_params(cameras, boxes, frame_index, side)[0]
+
+
+class PlacementParams(NamedTuple):
+    """Per-crop placement records (the fields of MetroPlacement, include/metro_hip.h): the crop's virtual camera and the way
+    back to its frame."""
+    keypoint_mode: np.ndarray    # int32 [n]: _lib.METRO_WARP_HOMOGRAPHY | METRO_WARP_DISTORTED
+    inv_intrinsics: np.ndarray   # float32 [n, 3, 3]: inv(virt.K) (data_loading.py:112); zero without a camera
+    rot_to_orig_cam: np.ndarray  # float32 [n, 3, 3]
+    rot_to_world: np.ndarray     # float32 [n, 3, 3]
+    cam_loc: np.ndarray          # float32 [n, 3]: virt.t = orig.t
+    homography: np.ndarray       # float32 [n, 3, 3]: crop pixel -> frame pixel (HOMOGRAPHY mode)
+    intrinsics: np.ndarray       # float32 [n, 3, 3]: the original camera's K (DISTORTED mode)
+    distortion: np.ndarray       # float32 [n, 5]
+
+
+def placement_params(cameras, boxes, frame_index, side: int = 256) -> PlacementParams:
+    """MetroPlacement records of n crops (`cameras` as for crop_params): inv_intrinsics = inv(virt.K) cast to float32,
+    rot_to_orig_cam, rot_to_world and cam_loc = virt.t as the reference's loader returns them (data_loading.py:110-112, 119);
+    the keypoint mode follows the warp mode (an undistorted camera or cameras=None: the crop's warp homography, which maps crop
+    pixels to frame pixels; a camera with coefficients: its K and distortion for project_points).  cameras=None has no
+    virtual camera: inv_intrinsics is zero (no metric placement) and the rotations are I."""
+    return _frame_params(cameras, boxes, frame_index, side)[1]
+
+
+def _frame_params(cameras, boxes, frame_index, side: int):
+    """(CropParams, PlacementParams) of n crops, each virtual camera computed once."""
     boxes = np.asarray(boxes, np.float64).reshape(-1, 4)
     n = len(boxes)
     fi = np.asarray(frame_index, np.int64).reshape(n)
     p = CropParams(np.zeros(n, np.int32), np.zeros((n, 3, 3), np.float32), np.zeros((n, 3, 3)),
                    np.zeros((n, 3, 3), np.float32), np.zeros((n, 5), np.float32),
                    np.tile(np.eye(3, dtype=np.float32), (n, 1, 1)), np.tile(np.eye(3, dtype=np.float32), (n, 1, 1)))
+    q = PlacementParams(p.mode, np.zeros((n, 3, 3), np.float32), p.rot_to_orig_cam, p.rot_to_world, np.zeros((n, 3), np.float32),
+                        p.homography, p.intrinsics, p.distortion)
     for i, box in enumerate(boxes):
         if cameras is None:
             p.homography[i] = box_homography(box, side)
@@ -215,7 +255,9 @@ def crop_params(cameras, boxes, frame_index, side: int = 256) -> CropParams:
             p.distortion[i] = orig.distortion_coeffs
         p.rot_to_orig_cam[i] = (orig.R @ virt.R.T).astype(np.float32)
         p.rot_to_world[i] = virt.R.T.astype(np.float32)
-    return p
+        q.inv_intrinsics[i] = np.linalg.inv(virt.intrinsic_matrix).astype(np.float32)
+        q.cam_loc[i] = virt.t
+    return p, q
 
 
 def pack_crops(params: CropParams, frame_index) -> np.ndarray:
@@ -231,6 +273,24 @@ def pack_crops(params: CropParams, frame_index) -> np.ndarray:
         r.intrinsics[:] = [float(v) for v in (k[i, 0, 0], k[i, 0, 1], k[i, 0, 2], k[i, 1, 0], k[i, 1, 1], k[i, 1, 2])]
         r.distortion[:] = params.distortion[i].tolist()
     return np.frombuffer(bytearray(rec), np.uint8).reshape(n, C.sizeof(_lib.MetroCropWarp))
+
+
+def pack_placements(params: PlacementParams) -> np.ndarray:
+    """The MetroPlacement records (include/metro_hip.h) of `params` as a byte array [n, 208]."""
+    n = len(params.keypoint_mode)
+    rec = (_lib.MetroPlacement * n)()
+    k = params.intrinsics
+    for i in range(n):
+        r = rec[i]
+        r.keypoint_mode = int(params.keypoint_mode[i])
+        r.inv_intrinsics[:] = params.inv_intrinsics[i].ravel().tolist()
+        r.rot_to_orig_cam[:] = params.rot_to_orig_cam[i].ravel().tolist()
+        r.rot_to_world[:] = params.rot_to_world[i].ravel().tolist()
+        r.cam_loc[:] = params.cam_loc[i].tolist()
+        r.homography[:] = params.homography[i].ravel().tolist()
+        r.intrinsics[:] = [float(v) for v in (k[i, 0, 0], k[i, 0, 1], k[i, 0, 2], k[i, 1, 0], k[i, 1, 1], k[i, 1, 2])]
+        r.distortion[:] = params.distortion[i].tolist()
+    return np.frombuffer(bytearray(rec), np.uint8).reshape(n, C.sizeof(_lib.MetroPlacement))
 
 
 def _upload(a: np.ndarray, device: torch.device) -> torch.Tensor:
@@ -333,3 +393,163 @@ def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index
                                             C.c_void_p(mirror.data_ptr()), C.c_void_p(out.data_ptr()), n, sk.n_out,
                                             C.c_void_p(stream)), 'metro_to_orig_cam')
     return out, edges, names
+
+
+class FramePoses(NamedTuple):
+    """What locate_poses_in_frames returns."""
+    poses: torch.Tensor                  # float32 [n, Jout, 3] mm on the device, in the requested coords
+    keypoints2d: torch.Tensor            # float32 [n, Jout, 2] frame pixels on the device (NaN: behind the original camera)
+    z_offset: Optional[torch.Tensor]     # float32 [n] mm (absolute modes: the root's depth in the virtual camera), else None
+    joint_edges: np.ndarray
+    joint_names: np.ndarray
+
+
+SCALE_RECOVERY = {'metro': _lib.METRO_SCALE_METRO, 'bone-lengths': _lib.METRO_SCALE_BONE_LENGTHS,
+                  'true-root-depth': _lib.METRO_SCALE_TRUE_ROOT_DEPTH}
+COORDS = {'crop': _lib.METRO_COORDS_CROP, 'camera': _lib.METRO_COORDS_CAMERA, 'world': _lib.METRO_COORDS_WORLD}
+
+
+# Skeletons of the model files seen so far, keyed like inference._engine_for (absolute path, mtime): a frozen GraphDef has no
+# spec entry and is decoded whole to learn it, which must happen once per file, not once per call.
+MAX_CACHED_SKELETONS = 16
+_SKELETONS: 'OrderedDict[Tuple[str, float], object]' = OrderedDict()
+
+
+def _model_skeleton(model_path):
+    """The skeleton of a model file, read once per (path, mtime): the .npz spec entry alone, or a .pb decoded whole."""
+    from metro_pose3d_amd.modelfile import SPEC_KEY, load_model
+    from metro_pose3d_amd.spec import ModelSpec
+    path = os.path.abspath(model_path)
+    key = (path, os.path.getmtime(path))
+    sk = _SKELETONS.get(key)
+    if sk is not None:
+        _SKELETONS.move_to_end(key)
+        return sk
+    with open(path, 'rb') as f:
+        is_zip = f.read(2) == b'PK'
+    sk = None
+    if is_zip:
+        with np.load(path, allow_pickle=False) as z:
+            if SPEC_KEY in z.files:
+                sk = ModelSpec.from_json(bytes(z[SPEC_KEY]).decode()).skeleton
+    if sk is None:
+        sk = load_model(path)[0].skeleton
+    _SKELETONS[key] = sk
+    while len(_SKELETONS) > MAX_CACHED_SKELETONS:
+        _SKELETONS.popitem(last=False)
+    return sk
+
+
+def _placement_targets(scale_recovery, cameras, n, n_edges, bone_lengths, root_depth):
+    """Checks the scale-recovery arguments; returns (bone lengths float64 [E] or [n, E], per-pose flag, root depths float32 [n])."""
+    if scale_recovery not in SCALE_RECOVERY:
+        raise ValueError(f"scale_recovery must be 'metro', 'bone-lengths' or 'true-root-depth', got {scale_recovery!r}")
+    if scale_recovery == 'metro':
+        if bone_lengths is not None or root_depth is not None:
+            raise ValueError("bone_lengths / root_depth go with scale_recovery='bone-lengths' / 'true-root-depth'")
+        return None, 0, None
+    if cameras is None:
+        raise ValueError(f"scale_recovery={scale_recovery!r} places poses metrically and needs calibrated cameras (their intrinsics): "
+                         "cameras=None has none (2D keypoints and root-relative poses: scale_recovery='metro')")
+    if scale_recovery == 'bone-lengths':
+        if root_depth is not None:
+            raise ValueError("root_depth goes with scale_recovery='true-root-depth'")
+        if bone_lengths is None:
+            raise ValueError(f"scale_recovery='bone-lengths' needs bone_lengths in mm, [E] or [n, E] over the model's {n_edges} "
+                             'head edges (spec.skeleton.head_edges); no default table ships with the package')
+        b = np.asarray(bone_lengths, np.float64)
+        if b.shape not in ((n_edges,), (n, n_edges)):
+            raise ValueError(f'bone_lengths must be [{n_edges}] or [{n}, {n_edges}] (mm over spec.skeleton.head_edges), got {b.shape}')
+        if not (np.isfinite(b).all() and (b > 0).all()):
+            raise ValueError('bone_lengths must be finite and positive (mm)')
+        return np.ascontiguousarray(b), int(b.ndim == 2), None
+    if bone_lengths is not None:
+        raise ValueError("bone_lengths go with scale_recovery='bone-lengths'")
+    if root_depth is None:
+        raise ValueError("scale_recovery='true-root-depth' needs root_depth [n] in mm")
+    r = np.asarray(root_depth, np.float64)
+    if r.shape != (n,):
+        raise ValueError(f'root_depth must be [{n}] (mm, one per box), got {r.shape}')
+    if not (np.isfinite(r).all() and (r > 0).all()):
+        raise ValueError('root_depth must be finite and positive (mm)')
+    return None, 0, r.astype(np.float32)
+
+
+def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=None, scale_recovery: str = 'bone-lengths',
+                           bone_lengths=None, root_depth=None, coords: str = 'camera', precision: Optional[str] = None,
+                           check_finite: Optional[bool] = None) -> FramePoses:
+    """uint8 frames + person boxes -> FramePoses(poses, keypoints2d, z_offset, joint_edges, joint_names): where each person is
+    in 3D and where each joint lands in its frame's pixels.  frames, boxes, frame_index, cameras, precision and check_finite as
+    for estimate_pose_in_frames.
+
+    scale_recovery (the reference's --scale-recovery names, volumetric.py:171-201):
+      'metro'            root-relative poses: the bits of estimate_pose_in_frames(..., coords=coords); z_offset None;
+      'bone-lengths'     needs cameras and bone_lengths in mm, [E] or [n, E] over spec.skeleton.head_edges: rays through each
+                         crop's virtual camera, the reference's Levenberg-Marquardt z offset (metro_backproject_bone_lengths'
+                         arithmetic), back_project;
+      'true-root-depth'  needs cameras and root_depth [n] in mm: the root's z in the crop's virtual camera (the reference's
+                         coords3d_true[:, -1, 2]).
+    coords: 'crop' (the virtual camera), 'camera' (the original one: to_orig_cam, volumetric.py:204-205, 277-281) or 'world'
+    (to_orig_cam(x, rot_to_world) + cam_loc for absolute poses, :206-208; rotation only in 'metro' mode).
+    keypoints2d: heatmap_to_image(coords01.xy) mapped into the frame (cameralib.reproject_image_points, cameralib.py:241-262):
+    through the crop's warp homography (cameras=None or an undistorted camera), or through rot_to_orig_cam and the original
+    camera's project_points (a camera with coefficients).  NaN where the ray points behind the original camera.
+    One enqueue chain on the current stream of the local device: uploads, one warp launch, metro_forward_coords01 in <= 256-crop
+    chunks with the finite screen folded on the device, one metro_place_poses launch, then the call's one stream
+    synchronisation (the screen).  No default bone-length table ships: the reference's come from its training data."""
+    from metro_pose3d_amd.inference import _engine_for, _resolve_device
+    if coords not in COORDS:
+        raise ValueError(f"coords must be 'crop', 'camera' or 'world', got {coords!r}")
+    if precision is None:
+        precision = os.environ.get('METRO_PRECISION', 'f16')
+    if check_finite is None:
+        check_finite = os.environ.get('METRO_CHECK_FINITE', '1') != '0'
+    boxes = np.asarray(boxes, np.float64)
+    if boxes.ndim != 2 or boxes.shape[1] != 4:
+        raise ValueError(f'boxes must be [n, 4] (x, y, w, h), got {boxes.shape}')
+    n = len(boxes)
+    fi = np.zeros(n, np.int64) if frame_index is None else np.asarray(frame_index, np.int64).reshape(n)
+    sk = _model_skeleton(model_path)
+    targets, per_pose, root_z = _placement_targets(scale_recovery, cameras, n, len(sk.head_edges), bone_lengths, root_depth)
+    first = frames if isinstance(frames, torch.Tensor) else frames[0] if isinstance(frames, (list, tuple)) and frames else None
+    device = _resolve_device(first if isinstance(first, torch.Tensor) else torch.empty(0))
+    names = np.empty(sk.n_out, dtype=object)
+    names[:] = sk.names_bytes()
+    with torch.cuda.device(device):
+        eng = _engine_for(model_path, precision, device, max(n, 1))
+        spec = eng.spec
+        poses = torch.empty((n, sk.n_out, 3), dtype=torch.float32, device=device)
+        keypoints = torch.empty((n, sk.n_out, 2), dtype=torch.float32, device=device)
+        z_offset = torch.empty(n, dtype=torch.float32, device=device) if scale_recovery != 'metro' else None
+        if n == 0:
+            return FramePoses(poses, keypoints, z_offset, sk.edges_array(), names)
+        side = spec.proc_side
+        crop_p, place_p = _frame_params(cameras, boxes, fi, side)
+        crops = warp_frames(frames, crop_p, fi, side, device=device)
+        rel = torch.empty((n, sk.n_out, 3), dtype=torch.float32, device=device)
+        coords01 = torch.empty((n, sk.n_head, 3), dtype=torch.float32, device=device)
+        bad = None
+        for i in range(0, n, eng.max_batch):
+            k = min(eng.max_batch, n - i)
+            eng.forward(crops[i:i + k], out=rel[i:i + k], coords01=coords01[i:i + k])
+            if check_finite:       # folded on the device after every chunk: ONE synchronisation per call, below
+                cnt = eng.status_words(k).ne(0).sum()
+                bad = cnt if bad is None else bad + cnt
+        recs = _upload(pack_placements(place_p), device)
+        mirror = _upload(np.asarray(sk.out_mirror, np.int32), device)
+        d_targets = _upload(targets, device) if targets is not None else None
+        d_root = _upload(root_z, device) if root_z is not None else None
+        d_edges = _upload(np.asarray(sk.head_edges, np.int32).reshape(-1, 2), device) if targets is not None else None
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        check(_lib.load().metro_place_poses(ptr(coords01), ptr(rel), ptr(recs), n, C.byref(eng.cspec), SCALE_RECOVERY[scale_recovery],
+                                            ptr(d_targets), per_pose, ptr(d_root), ptr(d_edges), len(sk.head_edges),
+                                            ptr(mirror), COORDS[coords], ptr(poses), ptr(keypoints), ptr(z_offset),
+                                            C.c_void_p(stream)), 'metro_place_poses')
+        n_bad = int(bad.item()) if bad is not None else 0              # the call's one stream synchronisation
+        if n_bad:
+            raise _lib.NonFiniteError(
+                f'{spec.arch_name} stride {spec.stride} in precision {precision!r}: {n_bad} of {n} crops reached the '
+                'soft-argmax with non-finite statistics' +
+                (' (fp16 storage overflows at 65504: run this model with precision f32m or f64)' if precision == 'f16' else ''))
+    return FramePoses(poses, keypoints, z_offset, sk.edges_array(), names)

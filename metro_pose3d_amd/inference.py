@@ -238,11 +238,17 @@ def main(argv=None):
     parser.add_argument('--box', type=str, action='append', default=[], help='x,y,w,h of a person box in --frame (repeatable)')
     parser.add_argument('--intrinsics', type=str, default=None, help='fx,fy,cx,cy of the --frame camera')
     parser.add_argument('--distortion', type=str, default=None, help='k1,k2,p1,p2,k3 of the --frame camera (needs --intrinsics)')
+    parser.add_argument('--bone-lengths', type=str, default=None,
+                        help='.npy with the bone lengths in mm over the model\'s head edges ([E] or [boxes, E]): absolute '
+                             'camera-frame poses and frame pixels of the --box persons (needs --intrinsics)')
+    parser.add_argument('--root-depth', type=str, default=None,
+                        help='MM[,MM...]: root depth of every --box person in its crop\'s virtual camera (true-root-depth '
+                             'scale recovery; needs --intrinsics)')
     opts = parser.parse_args(argv)
     if opts.frame:
         return _main_frame(opts)
-    if opts.box or opts.intrinsics or opts.distortion:
-        parser.error('--box, --intrinsics and --distortion go with --frame')
+    if opts.box or opts.intrinsics or opts.distortion or opts.bone_lengths or opts.root_depth:
+        parser.error('--box, --intrinsics, --distortion, --bone-lengths and --root-depth go with --frame')
     if opts.image:
         img = np.load(opts.image).astype(np.float32)
     else:
@@ -277,11 +283,34 @@ def _main_frame(opts):
         camera = Camera(np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]]), dist)
     elif opts.distortion:
         raise SystemExit('--distortion needs --intrinsics')
+    if opts.bone_lengths or opts.root_depth:
+        return _main_locate(opts, frame, boxes, camera)
     poses, edges, names = estimate_pose_in_frames(frame, boxes, opts.model_path, cameras=camera, precision=opts.precision)
     for k, pose in enumerate(poses.cpu().numpy()):
         print(f'box {k} {opts.box[k]} (camera frame, root-relative mm)')
         for name, p in zip(names, pose):
             print(f'{name.decode():>10s}  {p[0]:9.2f} {p[1]:9.2f} {p[2]:9.2f}')
+
+
+def _main_locate(opts, frame, boxes, camera):
+    from metro_pose3d_amd.frames import locate_poses_in_frames
+    if opts.bone_lengths and opts.root_depth:
+        raise SystemExit('--bone-lengths and --root-depth are two scale recoveries: pick one')
+    if camera is None:
+        raise SystemExit('--bone-lengths / --root-depth place the poses metrically: they need --intrinsics')
+    if opts.bone_lengths:
+        kw = dict(scale_recovery='bone-lengths', bone_lengths=np.load(opts.bone_lengths))
+    else:
+        kw = dict(scale_recovery='true-root-depth', root_depth=_floats(opts.root_depth, len(boxes), '--root-depth'))
+    try:
+        res = locate_poses_in_frames(frame, boxes, opts.model_path, cameras=camera, precision=opts.precision, **kw)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    poses, kp, z = res.poses.cpu().numpy(), res.keypoints2d.cpu().numpy(), res.z_offset.cpu().numpy()
+    for k in range(len(boxes)):
+        print(f'box {k} {opts.box[k]} (camera frame, absolute mm; frame pixels); root depth {z[k]:.1f} mm')
+        for name, p, q in zip(res.joint_names, poses[k], kp[k]):
+            print(f'{name.decode():>10s}  {p[0]:9.2f} {p[1]:9.2f} {p[2]:9.2f}   px {q[0]:8.2f} {q[1]:8.2f}')
 
 
 if __name__ == '__main__':

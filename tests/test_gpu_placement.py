@@ -1,0 +1,223 @@
+"""metro_place_poses, metro_forward_coords01 and locate_poses_in_frames on the MI355X: the placement launch against the
+reference's outputs (tests/golden/ref_placement_v1.npz), bit equality with the existing head kernels, the forward's coords01
+against metro_forward / metro_softargmax01, and the whole call against the oracle."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from metro_pose3d_amd import ModelSpec, _lib
+from metro_pose3d_amd._lib import check
+from metro_pose3d_amd.frames import SCALE_RECOVERY, COORDS, pack_placements
+from tests import oracle_placement as OPL
+from tests.test_placement import fixture_params
+
+pytestmark = pytest.mark.gpu
+
+SPEC = ModelSpec(50, 32, 'h36m')             # the fixture's constants: stride 32, 256 px crops, 2200 mm box, centred
+SK = SPEC.skeleton
+
+
+def _dev(a, cuda, dtype=None):
+    return torch.from_numpy(np.ascontiguousarray(a if dtype is None else np.asarray(a, dtype))).to(cuda)
+
+
+def _place(cuda, spec, coords01, params, scale, coords, poses=None, bones=None, root=None):
+    """One metro_place_poses launch -> (poses [n, Jout, 3], keypoints [n, Jout, 2], z_offset [n]) as host arrays."""
+    sk = spec.skeleton
+    n = len(coords01)
+    c01 = _dev(coords01, cuda, np.float32)
+    rel = _dev(poses, cuda, np.float32) if poses is not None else None
+    recs = _dev(pack_placements(params), cuda)
+    t = _dev(bones, cuda, np.float64) if bones is not None else None
+    rz = _dev(root, cuda, np.float32) if root is not None else None
+    edges = _dev(np.asarray(sk.head_edges, np.int32), cuda)
+    mirror = _dev(np.asarray(sk.out_mirror, np.int32), cuda)
+    out = torch.full((n, sk.n_out, 3), 12345.0, device=cuda)
+    kp = torch.full((n, sk.n_out, 2), 12345.0, device=cuda)
+    z = torch.full((n,), 12345.0, device=cuda)
+    p = lambda x: C.c_void_p(x.data_ptr() if x is not None else 0)
+    cs = spec.to_c(0)
+    check(_lib.load().metro_place_poses(p(c01), p(rel), p(recs), n, C.byref(cs), SCALE_RECOVERY[scale], p(t),
+                                        int(t is not None and t.dim() == 2), p(rz), p(edges), len(sk.head_edges), p(mirror),
+                                        COORDS[coords], p(out), p(kp), p(z), C.c_void_p(torch.cuda.current_stream(cuda).cuda_stream)),
+          'metro_place_poses')
+    return out.cpu().numpy(), kp.cpu().numpy(), z.cpu().numpy()
+
+
+@pytest.mark.parametrize('scale', OPL.SCALES)
+def test_place_poses_matches_the_reference(cuda, scale):
+    """3 cameras x 3 scale recoveries x 3 coordinate frames against the reference's outputs.
+    Bounds (fp32 derivation): the kernel evaluates the reference's fp32 formulas; what can differ is (a) K^-1, whose entries
+    agree with the reference's to a few ulp (our look_at_box, tests/test_frames.py: rtol 1e-6 on K), (b) the einsum's summation
+    order (1 ulp per ray component), (c) the z offset, whose fp64 solve on fp32 coefficients carries (a)-(b) through the bone
+    fit.  A 3D point is a ray times a depth of 3-6 m: 3-4 fp32 roundings of 6e-8 -> ~3e-7 relative, so the issue's 1e-4 is
+    loose; measured on the MI355X: 0 (every value bit-equal to the reference's), bound 1e-6 relative.  Keypoints: the
+    reference's general branch in fp32 (at camera_depth 4000 mm) vs our fp32 ray through the rounded rotation: ~1e-7 relative
+    of a 1000-2000 px focal length, 1e-4..1e-3 px; measured 2.4e-4 px, bound 1e-3 px (the issue's 1e-2 tightened)."""
+    d, q = fixture_params()
+    perm = list(SK.permutation)
+    key = scale.replace('-', '_')
+    worst3, worstkp = 0.0, 0.0
+    for coords in OPL.COORDS:
+        got, kp, z = _place(cuda, SPEC, d['coords01'], q, scale, coords, poses=d['metro_crop'][:, perm],
+                            bones=d['bone_targets'] if scale == 'bone-lengths' else None,
+                            root=d['root_depth'] if scale == 'true-root-depth' else None)
+        want = d[f'{key}_{coords}'][:, perm]
+        rel = np.abs(got - want).max() / np.abs(want).max()
+        worst3 = max(worst3, rel)
+        assert rel <= 1e-6, (coords, rel)
+        if scale != 'metro':
+            assert np.abs(z - d[f'{key}_z_offset']).max() <= 1e-6 * np.abs(d[f'{key}_z_offset']).max()
+        worstkp = max(worstkp, np.abs(kp - d['keypoints'][:, perm]).max())
+        assert worstkp <= 1e-3, (coords, worstkp)
+    print(f'{scale}: worst 3D relative error {worst3:.2e}, worst keypoint error {worstkp:.2e} px')
+
+
+def test_place_poses_is_bit_identical_to_the_head_kernels(cuda):
+    from metro_pose3d_amd import heads as MH
+    d, q = fixture_params()
+    got, _, z = _place(cuda, SPEC, d['coords01'], q, 'bone-lengths', 'crop', bones=d['bone_targets'])
+    ref, zref = MH.backproject_bone_lengths(_dev(d['coords01'], cuda), q.inv_intrinsics, d['bone_targets'], SPEC,
+                                            root_relative=False, permute=True)
+    assert np.array_equal(got, ref.cpu().numpy()) and np.array_equal(z, zref.cpu().numpy())
+    shared = d['bone_targets'].mean(axis=0)
+    got, _, z = _place(cuda, SPEC, d['coords01'], q, 'bone-lengths', 'crop', bones=shared)
+    ref, zref = MH.backproject_bone_lengths(_dev(d['coords01'], cuda), q.inv_intrinsics, shared, SPEC, permute=True)
+    assert np.array_equal(got, ref.cpu().numpy()) and np.array_equal(z, zref.cpu().numpy())
+    rel = d['metro_crop'][:, list(SK.permutation)]
+    for coords, rot in (('camera', q.rot_to_orig_cam), ('world', q.rot_to_world)):
+        got, _, _ = _place(cuda, SPEC, d['coords01'], q, 'metro', coords, poses=rel)
+        ref = MH.to_orig_cam(_dev(rel, cuda), rot, SK.out_mirror).cpu().numpy()
+        assert np.array_equal(got, ref), coords
+    # a reflection (det < 0) mirrors the joints in both kernels alike
+    q2 = q._replace(rot_to_orig_cam=-q.rot_to_orig_cam)
+    got, _, _ = _place(cuda, SPEC, d['coords01'], q2, 'metro', 'camera', poses=rel)
+    assert np.array_equal(got, MH.to_orig_cam(_dev(rel, cuda), q2.rot_to_orig_cam, SK.out_mirror).cpu().numpy())
+    # absolute modes, proper and improper rotations (half the crops reflected): back-projection of the mirror joint equals
+    # metro_backproject_bone_lengths followed by metro_to_orig_cam (+ cam_loc for world)
+    sign = np.where(np.arange(len(q.rot_to_orig_cam)) % 2, -1, 1).astype(np.float32)[:, None, None]
+    q3 = q._replace(rot_to_orig_cam=q.rot_to_orig_cam * sign, rot_to_world=q.rot_to_world * sign)
+    assert (np.linalg.det(q3.rot_to_orig_cam[1::2].astype(np.float64)) < 0).all()
+    crop, _ = MH.backproject_bone_lengths(_dev(d['coords01'], cuda), q.inv_intrinsics, d['bone_targets'], SPEC,
+                                          root_relative=False, permute=True)
+    for coords, rot in (('camera', q3.rot_to_orig_cam), ('world', q3.rot_to_world)):
+        got, _, _ = _place(cuda, SPEC, d['coords01'], q3, 'bone-lengths', coords, bones=d['bone_targets'])
+        ref = MH.to_orig_cam(crop, rot, SK.out_mirror).cpu().numpy()
+        if coords == 'world':
+            ref = ref + q3.cam_loc[:, None]
+        assert np.array_equal(got, ref), coords
+
+
+def test_keypoints_behind_the_camera_are_nan(cuda):
+    d, q = fixture_params()
+    q = q._replace(homography=q.homography.copy(), rot_to_orig_cam=q.rot_to_orig_cam.copy())
+    q.homography[19] = np.diag([1., 1., -1.]).astype(np.float32)          # undistorted camera: w < 0
+    q.rot_to_orig_cam[0] = np.diag([1., -1., -1.]).astype(np.float32)     # distorted camera: z < 0 (a proper rotation)
+    _, kp, _ = _place(cuda, SPEC, d['coords01'], q, 'metro', 'crop', poses=d['metro_crop'][:, list(SK.permutation)])
+    assert np.isnan(kp[19]).all() and np.isnan(kp[0]).all() and np.isfinite(kp[1:19]).all()
+
+
+def _toy_engine_model(tmp_path):
+    from metro_pose3d_amd import save_model, synth
+    spec = ModelSpec(50, 32, 'h36m', base_width=8)
+    params = synth.make_params(50, spec.n_head_channels, 8, seed=1, logit_gain=0.84)
+    path = str(tmp_path / 'toy.npz')
+    save_model(path, spec, params)
+    return spec, params, path
+
+
+@pytest.mark.parametrize('precision', ['f16', 'f32m', 'f64'])
+def test_forward_coords01_matches_forward(cuda, tmp_path, precision):
+    from metro_pose3d_amd import heads as MH, synth
+    from metro_pose3d_amd.engine import Engine
+    spec, params, _ = _toy_engine_model(tmp_path)
+    eng = Engine(spec, params, precision, max_batch=130, device=cuda)
+    images = torch.from_numpy(synth.make_images(130, spec.proc_side, seed=3)).to(cuda)
+    for graphs in (0, 130):
+        check(eng.lib.metro_plan_set_graph_max_batch(eng._plan, graphs), 'metro_plan_set_graph_max_batch')
+        for n in (1, 64, 130):
+            x = images[:n]
+            base = eng.forward(x).clone()
+            bufs = [torch.empty((n, spec.skeleton.n_head, 3), device=cuda) for _ in range(2)]
+            ref = None
+            for b, c01 in enumerate(bufs):
+                for rep in range(3):                  # graphs on: first sight runs eagerly, then capture, then replay
+                    for other in bufs:
+                        other.fill_(-7.0)
+                    poses = eng.forward(x, coords01=c01)
+                    assert torch.equal(poses, base), (graphs, n, b, rep)
+                    assert ((c01 >= 0) & (c01 <= 1)).all(), (graphs, n, b, rep)     # written: expectations in [0, 1]
+                    ref = c01.clone() if ref is None else ref
+                    assert torch.equal(c01, ref), (graphs, n, b, rep)
+                    # the other buffer is a different graph key: nothing may land there
+                    assert (bufs[1 - b] == -7.0).all(), (graphs, n, b, rep)
+            assert torch.equal(eng.forward(x), base)
+    n = 64
+    x = images[:n]
+    c01 = torch.full((n, spec.skeleton.n_head, 3), -7.0, device=cuda)
+    poses = eng.forward(x, coords01=c01)
+    assert ((c01 >= 0) & (c01 <= 1)).all()
+    if precision == 'f64':
+        li = [i for i, l in enumerate(eng.layer_infos()) if l.name.decode() == 'logits'][0]
+        logits = eng.forward_upto(x, li)
+        ref = MH.coords01_from_logits(logits, spec, precise=2)
+        assert (c01 - ref).abs().max().item() <= 1e-6
+    # heatmap_to_metric + root-relative + permutation of coords01 reproduces the poses: in fp32, the finalize's arithmetic, for
+    # f16; in fp64 for f32m / f64, whose finalize decodes the fp64 expectation that coords01 holds rounded to fp32
+    # (2200 mm x 6e-8 = 1.3e-4 mm per coordinate)
+    dt = np.float32 if precision == 'f16' else np.float64
+    c = c01.cpu().numpy().astype(dt)
+    last = spec.proc_side - 1
+    lrc, half = dt(last - last % spec.stride - 1), dt(spec.stride // 2)
+    box, side = dt(spec.box_size_mm), dt(spec.proc_side)
+    mm = np.concatenate([(c[..., :2] * lrc + half) * box / side, c[..., 2:] * box], -1)
+    rel = (mm - mm[:, -1:])[:, list(spec.skeleton.permutation)]
+    assert np.abs(rel - poses.cpu().numpy()).max() <= 1e-3, precision
+    with pytest.raises(ValueError, match='coords01 must be'):
+        eng.forward(x, coords01=torch.empty((n, 3, 3), device=cuda))
+    eng.close()
+
+
+def test_locate_poses_in_frames_f64_matches_the_oracle(cuda, tmp_path):
+    from metro_pose3d_amd.frames import crop_params, estimate_pose_in_frames, locate_poses_in_frames, placement_params
+    from oracle import forward as OF
+    from tests import helpers as H
+    from tests.test_gpu_frames import _cameras, _frame, _oracle_crops
+    spec, params, path = _toy_engine_model(tmp_path)
+    d, cams = _cameras()
+    cams[2].distortion_coeffs = None                                   # one undistorted camera: the homography keypoints
+    frames = [_frame(*d[f'cam{i}_frame_hw'], seed=50 + i) for i in range(3)]
+    sel = [0, 2, 8, 11, 14, 16, 19]
+    boxes, fi = d['boxes'][sel], d['box_camera'][sel]
+    n = len(sel)
+    rng = np.random.default_rng(11)
+    bones = rng.uniform(200, 450, len(spec.skeleton.head_edges))
+    root = rng.uniform(3000, 5000, n)
+    p = crop_params(cams, boxes, fi, 256)
+    q = placement_params(cams, boxes, fi, 256)
+    collect = {}
+    OF.forward(H.oracle_spec(spec), params, _oracle_crops(frames, p, fi, 256), torch.float64, collect=collect)
+    c01 = collect['coords01'].numpy().astype(np.float32)
+    perm, mirror = spec.skeleton.permutation, spec.skeleton.out_mirror
+    for scale, kw in (('bone-lengths', dict(bone_lengths=bones)), ('true-root-depth', dict(root_depth=root))):
+        for coords in OPL.COORDS:
+            got = locate_poses_in_frames(frames, boxes, path, cameras=cams, frame_index=fi, scale_recovery=scale,
+                                         coords=coords, precision='f64', **kw)
+            ref, kp, z = OPL.place(c01, q, spec.stride, scale, coords, perm, mirror, edges=spec.skeleton.head_edges,
+                                   bone_lengths=bones, root_depth=root)
+            assert got.poses.shape == (n, 17, 3) and got.keypoints2d.shape == (n, 17, 2) and got.z_offset.shape == (n,)
+            assert np.abs(got.poses.cpu().numpy() - ref).max() <= 1e-2, (scale, coords)
+            assert np.abs(got.keypoints2d.cpu().numpy() - kp).max() <= 1e-3, (scale, coords)
+            assert np.abs(got.z_offset.cpu().numpy() - z).max() <= 1e-2
+            assert got.joint_names[0] == b'pelv' and got.joint_edges.shape == (16, 2)
+    for coords in OPL.COORDS:
+        got = locate_poses_in_frames(frames, boxes, path, cameras=cams, frame_index=fi, scale_recovery='metro', coords=coords,
+                                     precision='f64')
+        base = estimate_pose_in_frames(frames, boxes, path, cameras=cams, frame_index=fi, coords=coords, precision='f64')[0]
+        assert torch.equal(got.poses, base) and got.z_offset is None, coords
+    # no cameras: keypoints through the square crops' homographies, 'metro' only
+    got = locate_poses_in_frames(frames[0], boxes[:3], path, scale_recovery='metro', precision='f16')
+    base = estimate_pose_in_frames(frames[0], boxes[:3], path, precision='f16')[0]
+    assert torch.equal(got.poses, base) and torch.isfinite(got.keypoints2d).all()
