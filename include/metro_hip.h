@@ -477,6 +477,59 @@ int  metro_place_poses(const float* d_coords01, const float* d_poses, const Metr
                        const float* d_root_depth, const int32_t* d_edges, int32_t n_edges, const int32_t* d_mirror,
                        int32_t coords, float* d_poses_out, float* d_keypoints_out, float* d_z_offset_out, void* stream);
 
+/* ---- test-time augmentation of frame crops: several views per person box (the reference's --test-aug geometry,
+ *      src/data/data_loading.py:60-68, 77-79, 110-112) ---- */
+/* One record per box (host code: frames.view_bases): the box's camera, its look_at_box camera and the records of the box
+ * itself (what frames.crop_params / placement_params give it), from which metro_expand_views derives every view. */
+typedef struct MetroViewBase {
+    int32_t frame;              /* index into the frame table                                                             */
+    int32_t mode;               /* METRO_WARP_HOMOGRAPHY | METRO_WARP_DISTORTED                                          */
+    int32_t has_camera;         /* 0: cameras=None, the axis-aligned square crop of `homography`                         */
+    int32_t reserved;
+    double old_matrix[9];       /* HOMOGRAPHY with a camera: the original camera's K R as the host's fp32 product         */
+    double orig_r[9];           /* the original camera's R (fp32 values)                                                 */
+    double virt_k[9];           /* the look_at_box camera's K (fp64)                                                     */
+    double virt_r[9];           /* the look_at_box camera's R (fp32 values)                                              */
+    double partial[9];          /* the identity view's MetroCropWarp.partial                                              */
+    float homography[9];        /* the identity view's homography (cameras=None: the square crop's, crop -> frame)        */
+    float inv_intrinsics[9];    /* the identity view's MetroPlacement fields, and cam_loc = the original camera's t        */
+    float rot_to_orig_cam[9];
+    float rot_to_world[9];
+    float cam_loc[3];
+    float intrinsics[6];        /* the original camera's K[0,0] K[0,1] K[0,2] K[1,0] K[1,1] K[1,2]                        */
+    float distortion[5];        /* k1 k2 p1 p2 k3 (OpenCV order)                                                          */
+} MetroViewBase;                /* 576 bytes */
+/* One view: the look_at_box camera zoomed by `zoom` about the principal point (cameralib.py:167-170), rolled about the optical
+ * axis (R <- Rz(roll)^T R, cameralib.py:95-98; cos / sin computed on the host) and, if flip, mirrored (R[0] *= -1,
+ * cameralib.py:191-192), in that order (data_loading.py:66-67, 77).  cos 1, sin 0, zoom 1, no flip is the identity view. */
+#define METRO_MAX_VIEWS 32
+typedef struct MetroView {
+    double cos_roll, sin_roll, zoom;
+    int32_t flip;
+    int32_t reserved;
+} MetroView;                    /* 32 bytes */
+/* d_bases: DEVICE array of n MetroViewBase; views: HOST array of n_views <= METRO_MAX_VIEWS (copied into the kernel
+ * arguments).  Writes n * n_views MetroCropWarp (metro_warp_crops_frames_u8's input) and MetroPlacement (metro_place_poses')
+ * records, box-major (row i * n_views + v), one thread per (box, view) in fp64 with closed-form 3x3 inverses, following
+ * frames._frame_params with the view camera in place of the look_at_box one (homography = old_matrix inv(K R) cast to fp32,
+ * partial = orig.R inv(R) inv(K), rot_to_orig_cam = orig.R R^T, rot_to_world = R^T, inv_intrinsics = inv(K), all cast to
+ * fp32).  cameras=None: the crop is a camera with principal point (side/2, side/2) whose frame is the square crop: the
+ * view's homography is the square's times the image-plane similarity of the view, the rotations back are R^T of the view,
+ * inv_intrinsics stays 0.  The identity view copies the box's own records: the bits of the call without views. */
+int  metro_expand_views(const MetroViewBase* d_bases, int32_t n, const MetroView* views, int32_t n_views, int32_t side,
+                        MetroCropWarp* d_crops_out, MetroPlacement* d_placements_out, void* stream);
+/* Fuses the n_views rows of each of n boxes (box-major, row i * n_views + v).  d_poses fp32 [n * n_views, n_joints, 3] in the
+ * requested coords with joints already mirrored (metro_place_poses / metro_to_orig_cam); d_keypoints fp32
+ * [n * n_views, n_joints, 2] frame pixels (unmirrored, as metro_place_poses writes them) or NULL; d_z_offset fp32
+ * [n * n_views] or NULL; d_records the views' MetroPlacement (a view with det(rot_to_orig_cam) <= 0 contributes its mirror
+ * joint's keypoint; d_mirror int32 [n_joints] output order).  Outputs: d_poses_out [n, n_joints, 3] the mean over the views;
+ * d_keypoints_out [n, n_joints, 2] the mean over the views whose keypoint is finite (NaN if none); d_z_offset_out [n] the
+ * mean; d_spread_out [n, n_joints] (or NULL) the RMS 3D distance of the views from their mean.  fp64 sums in view order,
+ * one rounding to fp32: n_views copies of one view give its bits and a spread of 0. */
+int  metro_merge_views(const float* d_poses, const float* d_keypoints, const float* d_z_offset,
+                       const MetroPlacement* d_records, const int32_t* d_mirror, int32_t n, int32_t n_views, int32_t n_joints,
+                       float* d_poses_out, float* d_keypoints_out, float* d_z_offset_out, float* d_spread_out, void* stream);
+
 const char* metro_last_error(void);
 int32_t metro_abi_version(void);
 

@@ -83,6 +83,22 @@ class MetroPlacement(C.Structure):
                 ('homography', C.c_float * 9), ('intrinsics', C.c_float * 6), ('distortion', C.c_float * 5)]
 
 
+METRO_MAX_VIEWS = 32
+
+
+class MetroViewBase(C.Structure):
+    _fields_ = [('frame', C.c_int32), ('mode', C.c_int32), ('has_camera', C.c_int32), ('reserved', C.c_int32),
+                ('old_matrix', C.c_double * 9), ('orig_r', C.c_double * 9), ('virt_k', C.c_double * 9),
+                ('virt_r', C.c_double * 9), ('partial', C.c_double * 9), ('homography', C.c_float * 9),
+                ('inv_intrinsics', C.c_float * 9), ('rot_to_orig_cam', C.c_float * 9), ('rot_to_world', C.c_float * 9),
+                ('cam_loc', C.c_float * 3), ('intrinsics', C.c_float * 6), ('distortion', C.c_float * 5)]
+
+
+class MetroView(C.Structure):
+    _fields_ = [('cos_roll', C.c_double), ('sin_roll', C.c_double), ('zoom', C.c_double), ('flip', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
 # symbol -> (restype, argtypes); must list every function include/metro_hip.h declares
 _P = C.c_void_p
 SIGNATURES = {
@@ -132,6 +148,8 @@ SIGNATURES = {
     'metro_to_orig_cam': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     'metro_place_poses': (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(MetroSpec), C.c_int32, _P, C.c_int32, _P, _P, C.c_int32,
                                     _P, C.c_int32, _P, _P, _P, _P]),
+    'metro_expand_views': (C.c_int, [_P, C.c_int32, C.POINTER(MetroView), C.c_int32, C.c_int32, _P, _P, _P]),
+    'metro_merge_views': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     'metro_heatmap_to_25d': (C.c_int, [_P, C.c_int32, C.POINTER(MetroSpec), _P, _P]),
     'metro_head_f16_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     'metro_head_f16': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(MetroSpec), _P, _P, _P, _P]),

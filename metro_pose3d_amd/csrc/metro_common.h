@@ -399,5 +399,11 @@ int launch_place_poses(const float* coords01, const float* poses, const MetroPla
                        int scale, const double* targets, int per_pose_targets, const float* root_z, const int* edges, int ne,
                        const int* mirror, int coords, float* out, float* keypoints, float* z_out, hipStream_t stream);
 SoftArgmaxArgs make_softargmax_args(const MetroSpec& spec, int n);
+// test-time augmentation views of frame crops (views.hip)
+int launch_expand_views(const MetroViewBase* bases, int n, const MetroView* views, int n_views, int side, MetroCropWarp* crops,
+                        MetroPlacement* places, hipStream_t stream);
+int launch_merge_views(const float* poses, const float* keypoints, const float* z, const MetroPlacement* rec, const int* mirror,
+                       int n, int n_views, int nj, float* poses_out, float* keypoints_out, float* z_out, float* spread_out,
+                       hipStream_t stream);
 
 }  // namespace metro

@@ -1323,6 +1323,38 @@ int metro_place_poses(const float* d_coords01, const float* d_poses, const Metro
                               d_z_offset_out, static_cast<hipStream_t>(stream));
 }
 
+int metro_expand_views(const MetroViewBase* d_bases, int32_t n, const MetroView* views, int32_t n_views, int32_t side,
+                       MetroCropWarp* d_crops_out, MetroPlacement* d_placements_out, void* stream) {
+    METRO_CHECK_ARG(d_bases && views && d_crops_out && d_placements_out, "expand_views: NULL pointer");
+    METRO_CHECK_ARG(n > 0 && side > 0, "expand_views: bad geometry (n %d side %d)", n, side);
+    METRO_CHECK_ARG(n_views >= 1 && n_views <= METRO_MAX_VIEWS, "expand_views: %d views (1 to %d per launch)", n_views,
+                    METRO_MAX_VIEWS);
+    METRO_CHECK_ARG((int64_t)n * n_views <= INT32_MAX, "expand_views: %d boxes x %d views overflow int32", n, n_views);
+    for (int v = 0; v < n_views; ++v) {
+        const MetroView& w = views[v];
+        METRO_CHECK_ARG(std::isfinite(w.cos_roll) && std::isfinite(w.sin_roll) && std::isfinite(w.zoom) && w.zoom > 0.0,
+                        "expand_views: view %d: cos / sin of the roll must be finite and the zoom finite and > 0", v);
+        METRO_CHECK_ARG(w.flip == 0 || w.flip == 1, "expand_views: view %d: flip must be 0 or 1 (got %d)", v, w.flip);
+    }
+    return launch_expand_views(d_bases, n, views, n_views, side, d_crops_out, d_placements_out, static_cast<hipStream_t>(stream));
+}
+
+int metro_merge_views(const float* d_poses, const float* d_keypoints, const float* d_z_offset, const MetroPlacement* d_records,
+                      const int32_t* d_mirror, int32_t n, int32_t n_views, int32_t n_joints, float* d_poses_out,
+                      float* d_keypoints_out, float* d_z_offset_out, float* d_spread_out, void* stream) {
+    METRO_CHECK_ARG(d_poses && d_poses_out, "merge_views: NULL poses / poses_out pointer");
+    METRO_CHECK_ARG(!d_keypoints == !d_keypoints_out, "merge_views: keypoints and keypoints_out go together");
+    METRO_CHECK_ARG(!d_z_offset == !d_z_offset_out, "merge_views: z_offset and z_offset_out go together");
+    METRO_CHECK_ARG(!d_keypoints || (d_records && d_mirror), "merge_views: keypoints need the records and the mirror table");
+    METRO_CHECK_ARG(n > 0 && n_joints >= 1 && n_joints <= METRO_MAX_JOINTS, "merge_views: bad sizes (n %d, joints %d; 1 <= joints <= %d)",
+                    n, n_joints, METRO_MAX_JOINTS);
+    METRO_CHECK_ARG(n_views >= 1 && n_views <= METRO_MAX_VIEWS, "merge_views: %d views (1 to %d)", n_views, METRO_MAX_VIEWS);
+    METRO_CHECK_ARG((int64_t)n * n_views * n_joints * 3 <= INT32_MAX && (int64_t)n * n_joints <= INT32_MAX,
+                    "merge_views: %d boxes x %d views overflow int32", n, n_views);
+    return launch_merge_views(d_poses, d_keypoints, d_z_offset, d_records, d_mirror, n, n_views, n_joints, d_poses_out,
+                              d_keypoints_out, d_z_offset_out, d_spread_out, static_cast<hipStream_t>(stream));
+}
+
 const char* metro_last_error(void) { return metro::get_error(); }
 int32_t metro_abi_version(void) { return METRO_ABI_VERSION; }
 

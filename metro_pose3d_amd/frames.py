@@ -13,6 +13,9 @@ the box centre, drops the lens distortion, squares the pixels and zooms so the b
                                           frame's pixels (MetroPlacement records)
   locate_poses_in_frames                  absolute poses (bone-lengths / true-root-depth scale recovery, volumetric.py:171-208)
                                           and 2D frame keypoints, one metro_place_poses launch after the forward
+  view_set, pack_view_bases, view_params test-time augmentation (`views=`): V rolled / zoomed / flipped views per box
+                                          (data_loading.py:60-68, 77-79), expanded on the device (metro_expand_views) from one
+                                          record per box and fused per box after the placement (metro_merge_views)
 
 Divergences from the reference, on purpose:
   * a Camera built from intrinsics alone (no R, no t) defaults to world_up = (0, -1, 0), not the reference's (0, 0, 1): with
@@ -26,12 +29,16 @@ Divergences from the reference, on purpose:
   * keypoints of undistorted cameras go through the crop -> frame homography, the mapping the reference's general branch
     `orig.world_to_image(virt.image_to_world(p))` computes; its dispatcher would send them to reproject_image_points_fast
     (cameralib.py:432-438), which maps in the OPPOSITE direction to its docstring (H = old new^-1, i.e. frame -> crop when
-    called as (points, virtual, original)): that inverted fast path is not reproduced.
+    called as (points, virtual, original)): that inverted fast path is not reproduced;
+  * test-time views are deterministic (view_set), not the loader's random draws; the loader's `shift_aug_by_rot` centre shift
+    is not offered (it would need a look_at_box per view); a flip mirrors about x = side/2, the principal point that
+    center_principal_point sets, not about the pixel grid's centre (side - 1)/2.
 """
 from __future__ import annotations
 
 import copy
 import ctypes as C
+import math
 import os
 from collections import OrderedDict
 from typing import NamedTuple, Optional, Sequence, Tuple
@@ -148,6 +155,39 @@ class Camera:
     def center_principal_point(self, imshape):
         self.intrinsic_matrix[:2, 2] = [imshape[1] / 2, imshape[0] / 2]
 
+    # cameralib.py:95-98, 191-192
+    def rotate(self, yaw=0, pitch=0, roll=0):
+        """R <- euler2mat(yaw, pitch, roll, 'ryxz')^T R (angles in radians): the camera turns by yaw about its y axis, then
+        pitch about its new x axis, then roll about its new optical axis.  R becomes float64, as in the reference."""
+        self.R = euler2mat_ryxz(yaw, pitch, roll).T @ self.R
+
+    def horizontal_flip(self):
+        self.R[0] *= -1
+
+
+def euler2mat_ryxz(yaw, pitch, roll) -> np.ndarray:
+    """transforms3d.euler.euler2mat(yaw, pitch, roll, 'ryxz') (transforms3d is not a dependency), float64 [3, 3].
+
+    'ryxz' is the rotating-frame convention with axes y, x, z: the matrix is Ry(yaw) @ Rx(pitch) @ Rz(roll) with the
+    right-handed elementary rotations Rx(a) = [[1, 0, 0], [0, c, -s], [0, s, c]], Ry(a) = [[c, 0, s], [0, 1, 0], [-s, 0, c]],
+    Rz(a) = [[c, -s, 0], [s, c, 0], [0, 0, 1]].  Its entries are written as transforms3d's euler2mat writes them for this axis
+    code (first axis z, no parity, no repetition, rotating frame: i, j, k = 2, 0, 1 with the first and last angle swapped),
+    so roll alone gives exactly cos(roll) and sin(roll)."""
+    si, sj, sk = math.sin(roll), math.sin(pitch), math.sin(yaw)
+    ci, cj, ck = math.cos(roll), math.cos(pitch), math.cos(yaw)
+    cc, cs, sc, ss = ci * ck, ci * sk, si * ck, si * sk
+    m = np.eye(3)
+    m[2, 2] = cj * ck
+    m[2, 0] = sj * sc - cs
+    m[2, 1] = sj * cc + ss
+    m[0, 2] = cj * sk
+    m[0, 0] = sj * ss + cc
+    m[0, 1] = sj * cs - sc
+    m[1, 2] = -sj
+    m[1, 0] = cj * si
+    m[1, 1] = cj * ci
+    return m
+
 
 def look_at_box(camera: Camera, box: Sequence[float], side: int = 256) -> Camera:
     """The virtual camera of a crop: reference cameralib.look_at_box (src/cameralib.py:337-358), step by step -- turn towards
@@ -230,6 +270,11 @@ def placement_params(cameras, boxes, frame_index, side: int = 256) -> PlacementP
 
 def _frame_params(cameras, boxes, frame_index, side: int):
     """(CropParams, PlacementParams) of n crops, each virtual camera computed once."""
+    return _frame_params_and_cameras(cameras, boxes, frame_index, side)[:2]
+
+
+def _frame_params_and_cameras(cameras, boxes, frame_index, side: int):
+    """(CropParams, PlacementParams, the look_at_box camera of every crop (None without cameras))."""
     boxes = np.asarray(boxes, np.float64).reshape(-1, 4)
     n = len(boxes)
     fi = np.asarray(frame_index, np.int64).reshape(n)
@@ -238,12 +283,13 @@ def _frame_params(cameras, boxes, frame_index, side: int):
                    np.tile(np.eye(3, dtype=np.float32), (n, 1, 1)), np.tile(np.eye(3, dtype=np.float32), (n, 1, 1)))
     q = PlacementParams(p.mode, np.zeros((n, 3, 3), np.float32), p.rot_to_orig_cam, p.rot_to_world, np.zeros((n, 3), np.float32),
                         p.homography, p.intrinsics, p.distortion)
+    virts = [None] * n
     for i, box in enumerate(boxes):
         if cameras is None:
             p.homography[i] = box_homography(box, side)
             continue
         orig = _camera_of(cameras, int(fi[i]))
-        virt = look_at_box(orig, box, side)
+        virt = virts[i] = look_at_box(orig, box, side)
         if orig.distortion_coeffs is None:
             old_matrix = orig.intrinsic_matrix @ orig.R                         # float32, as cameralib.py:410
             new_matrix = virt.intrinsic_matrix @ virt.R                         # float64 (square_pixels made K float64)
@@ -257,7 +303,7 @@ def _frame_params(cameras, boxes, frame_index, side: int):
         p.rot_to_world[i] = virt.R.T.astype(np.float32)
         q.inv_intrinsics[i] = np.linalg.inv(virt.intrinsic_matrix).astype(np.float32)
         q.cam_loc[i] = virt.t
-    return p, q
+    return p, q, virts
 
 
 def pack_crops(params: CropParams, frame_index) -> np.ndarray:
@@ -338,18 +384,229 @@ def warp_frames(frames, params: CropParams, frame_index, side: int = 256, device
         out = torch.empty((n, side, side, 3), dtype=torch.float32, device=device)
     if n == 0:
         return out
-    table = (_lib.MetroFrame * len(dev_frames))()
-    for k, f in enumerate(dev_frames):
-        table[k].data, table[k].h, table[k].w, table[k].row_stride = f.data_ptr(), f.shape[0], f.shape[1], f.stride(0)
-    crops = _upload(pack_crops(params, fi), device)
-    stream = torch.cuda.current_stream(device).cuda_stream
-    check(_lib.load().metro_warp_crops_frames_u8(table, len(dev_frames), C.c_void_p(crops.data_ptr()), n, side,
-                                                 C.c_void_p(out.data_ptr()), C.c_void_p(stream)), 'metro_warp_crops_frames_u8')
+    _launch_warp(dev_frames, _upload(pack_crops(params, fi), device), n, side, out, device)
     return out
 
 
+def _launch_warp(dev_frames, crops: torch.Tensor, n: int, side: int, out: torch.Tensor, device: torch.device) -> None:
+    """One metro_warp_crops_frames_u8 launch on the current stream: n MetroCropWarp records already on the device."""
+    table = (_lib.MetroFrame * len(dev_frames))()
+    for k, f in enumerate(dev_frames):
+        table[k].data, table[k].h, table[k].w, table[k].row_stride = f.data_ptr(), f.shape[0], f.shape[1], f.stride(0)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    check(_lib.load().metro_warp_crops_frames_u8(table, len(dev_frames), C.c_void_p(crops.data_ptr()), n, side,
+                                                 C.c_void_p(out.data_ptr()), C.c_void_p(stream)), 'metro_warp_crops_frames_u8')
+
+
+MAX_VIEWS = _lib.METRO_MAX_VIEWS
+DEFAULT_ROLL_DEG = 20.0              # the reference's --rot-aug default (options.py:48-49)
+
+
+class Views(NamedTuple):
+    """A set of test-time views: view v is the look_at_box camera zoomed by zoom[v], rolled by roll_deg[v] about the optical
+    axis and, if flip[v], mirrored horizontally -- in that order (data_loading.py:66-67, 77)."""
+    roll_deg: np.ndarray         # float64 [V]
+    zoom: np.ndarray             # float64 [V]
+    flip: np.ndarray             # bool [V]
+
+
+def view_set(views) -> Views:
+    """`views` of estimate_pose_in_frames / locate_poses_in_frames -> Views.
+
+    An int V (1 <= V <= 32) selects the default set: rolls linspace(-20, +20, V) degrees (the reference's --rot-aug range),
+    zoom 1, a horizontal flip on the odd-indexed views; V = 1 is the identity view (roll 0, zoom 1, no flip).  E.g. V = 5:
+    (-20, 1, False), (-10, 1, True), (0, 1, False), (10, 1, True), (20, 1, False).  Otherwise a sequence of 1 to 32
+    (roll_deg, zoom, flip) triples: roll finite (degrees, positive turns the camera counter-clockwise about its optical axis,
+    cameralib.Camera.rotate), zoom finite and > 0 (> 1 magnifies, about the principal point), flip a bool."""
+    if isinstance(views, (bool, np.bool_)):
+        raise ValueError(f'views must be an int (the default set) or (roll_deg, zoom, flip) triples, got {views!r}')
+    if isinstance(views, (int, np.integer)):
+        v = int(views)
+        if not 1 <= v <= MAX_VIEWS:
+            raise ValueError(f'views must lie in [1, {MAX_VIEWS}], got {v}')
+        roll = np.linspace(-DEFAULT_ROLL_DEG, DEFAULT_ROLL_DEG, v) if v > 1 else np.zeros(1)
+        return Views(roll, np.ones(v), np.arange(v) % 2 == 1)
+    if isinstance(views, (str, bytes)) or not hasattr(views, '__len__'):
+        raise ValueError(f'views must be an int (the default set) or (roll_deg, zoom, flip) triples, got {views!r}')
+    if not 1 <= len(views) <= MAX_VIEWS:
+        raise ValueError(f'views must hold 1 to {MAX_VIEWS} (roll_deg, zoom, flip) triples, got {len(views)}')
+    roll, zoom, flip = np.zeros(len(views)), np.ones(len(views)), np.zeros(len(views), bool)
+    for k, t in enumerate(views):
+        if isinstance(t, (str, bytes)) or not hasattr(t, '__len__') or len(t) != 3:
+            raise ValueError(f'view {k} must be a (roll_deg, zoom, flip) triple, got {t!r}')
+        r, z, f = t
+        if isinstance(r, (bool, np.bool_)) or not isinstance(r, (int, float, np.integer, np.floating)) or not math.isfinite(r):
+            raise ValueError(f'view {k}: roll_deg must be a finite number, got {r!r}')
+        if (isinstance(z, (bool, np.bool_)) or not isinstance(z, (int, float, np.integer, np.floating)) or not math.isfinite(z)
+                or not z > 0):
+            raise ValueError(f'view {k}: zoom must be a finite number > 0, got {z!r}')
+        if not isinstance(f, (bool, np.bool_)):
+            raise ValueError(f'view {k}: flip must be a bool, got {f!r}')
+        roll[k], zoom[k], flip[k] = float(r), float(z), bool(f)
+    return Views(roll, zoom, flip)
+
+
+def _roll_rad(roll_deg: float) -> float:
+    return float(roll_deg) * math.pi / 180
+
+
+def _is_identity(vs: Views, v: int) -> bool:
+    return vs.roll_deg[v] == 0 and vs.zoom[v] == 1 and not vs.flip[v]
+
+
+def view_camera(camera: Camera, roll_deg: float, zoom: float, flip: bool) -> Camera:
+    """A view of a look_at_box camera, as the reference's loader builds it under --test-aug (data_loading.py:60-68, 77):
+    cam.zoom(zoom), cam.rotate(roll=roll), then cam.horizontal_flip() when flip."""
+    cam = camera.copy()
+    cam.zoom(zoom)
+    cam.rotate(roll=_roll_rad(roll_deg))
+    if flip:
+        cam.horizontal_flip()
+    return cam
+
+
+def _square_crop_camera(side: int) -> Camera:
+    """cameras=None: the square crop as a camera of principal point (side/2, side/2), unit focal length (roll, zoom and flip
+    are image-plane similarities about that point whatever the focal length), R = I, K in float64 like look_at_box's."""
+    cam = Camera(np.eye(3))
+    cam.intrinsic_matrix = np.array([[1., 0, side / 2], [0, 1., side / 2], [0, 0, 1]])
+    return cam
+
+
+def view_params(cameras, boxes, frame_index, views, side: int = 256):
+    """(CropParams, PlacementParams) of n * V crops, box-major (row i * V + v): the host restatement of metro_expand_views,
+    _frame_params' formulas with each view camera (view_camera of the box's look_at_box camera) in place of the look_at_box
+    one.  The identity view keeps the box's own records (its bits without views).  cameras=None: _square_crop_camera is the
+    look_at_box camera and the square crop's homography its frame: homography = square's . K_base inv(K R), the rotations
+    back R^T of the view, inv_intrinsics 0.  Tests use it as the reference of the device expansion; the product path does
+    not call it."""
+    vs = view_set(views)
+    boxes = np.asarray(boxes, np.float64).reshape(-1, 4)
+    n, nv = len(boxes), len(vs.zoom)
+    fi = np.asarray(frame_index, np.int64).reshape(n)
+    p0, q0, virts = _frame_params_and_cameras(cameras, boxes, fi, side)
+    rows = np.repeat(np.arange(n), nv)
+    p = CropParams(*(np.array(a[rows]) for a in p0))
+    q = PlacementParams(p.mode, q0.inv_intrinsics[rows], p.rot_to_orig_cam, p.rot_to_world, q0.cam_loc[rows], p.homography,
+                        p.intrinsics, p.distortion)
+    f32 = np.float32
+    for i in range(n):
+        base = _square_crop_camera(side) if cameras is None else virts[i]
+        orig = None if cameras is None else _camera_of(cameras, int(fi[i]))
+        for v in range(nv):
+            if _is_identity(vs, v):
+                continue
+            r = i * nv + v
+            view = view_camera(base, vs.roll_deg[v], vs.zoom[v], bool(vs.flip[v]))
+            vk, vr = view.intrinsic_matrix, view.R
+            if cameras is None:
+                g = np.linalg.solve((vk @ vr).T, base.intrinsic_matrix.T).T
+                p.homography[r] = (p0.homography[i].astype(np.float64) @ g).astype(f32)
+                p.rot_to_orig_cam[r] = vr.T.astype(f32)
+                p.rot_to_world[r] = vr.T.astype(f32)
+                continue
+            if orig.distortion_coeffs is None:
+                old_matrix = orig.intrinsic_matrix @ orig.R                         # float32, as cameralib.py:410
+                p.homography[r] = np.linalg.solve((vk @ vr).T, old_matrix.T).T.astype(f32)
+            else:
+                p.partial[r] = orig.R @ np.linalg.inv(vr) @ np.linalg.inv(vk)
+            p.rot_to_orig_cam[r] = (orig.R @ vr.T).astype(f32)
+            p.rot_to_world[r] = vr.T.astype(f32)
+            q.inv_intrinsics[r] = np.linalg.inv(vk).astype(f32)
+    return p, q
+
+
+VIEW_BASE_DTYPE = np.dtype(_lib.MetroViewBase)
+
+
+def pack_view_bases(cameras, boxes, frame_index, side: int = 256) -> np.ndarray:
+    """The MetroViewBase records (include/metro_hip.h) of n boxes as a byte array [n, 576]: one look_at_box per box (through
+    _frame_params, whose records are the identity view's), the rest filled column-wise, without a per-record ctypes loop."""
+    boxes = np.asarray(boxes, np.float64).reshape(-1, 4)
+    n = len(boxes)
+    fi = np.asarray(frame_index, np.int64).reshape(n)
+    p, q, virts = _frame_params_and_cameras(cameras, boxes, fi, side)
+    rec = np.zeros(n, VIEW_BASE_DTYPE)
+    rec['frame'] = fi
+    rec['mode'] = p.mode
+    rec['has_camera'] = int(cameras is not None)
+    rec['partial'] = p.partial.reshape(n, 9)
+    rec['homography'] = p.homography.reshape(n, 9)
+    rec['inv_intrinsics'] = q.inv_intrinsics.reshape(n, 9)
+    rec['rot_to_orig_cam'] = q.rot_to_orig_cam.reshape(n, 9)
+    rec['rot_to_world'] = q.rot_to_world.reshape(n, 9)
+    rec['cam_loc'] = q.cam_loc
+    rec['intrinsics'] = p.intrinsics.reshape(n, 9)[:, :6]
+    rec['distortion'] = p.distortion
+    if cameras is not None and n:
+        cams = [cameras] if isinstance(cameras, Camera) else list(cameras)
+        slot = np.zeros(n, np.int64) if isinstance(cameras, Camera) else fi
+        old = np.stack([(c.intrinsic_matrix @ c.R).astype(np.float64) for c in cams])   # float32 products, as cameralib.py:410
+        rec['old_matrix'] = old.reshape(-1, 9)[slot]
+        rec['orig_r'] = np.stack([c.R.astype(np.float64) for c in cams]).reshape(-1, 9)[slot]
+        rec['virt_k'] = np.stack([np.asarray(v.intrinsic_matrix, np.float64) for v in virts]).reshape(n, 9)
+        rec['virt_r'] = np.stack([np.asarray(v.R, np.float64) for v in virts]).reshape(n, 9)
+    return rec.view(np.uint8).reshape(n, VIEW_BASE_DTYPE.itemsize)
+
+
+def view_table(vs: Views):
+    """The MetroView array of a view set: cos / sin of each roll computed here, once, in the arithmetic euler2mat_ryxz uses."""
+    table = (_lib.MetroView * len(vs.zoom))()
+    for v in range(len(vs.zoom)):
+        a = _roll_rad(vs.roll_deg[v])
+        table[v].cos_roll, table[v].sin_roll = math.cos(a), math.sin(a)
+        table[v].zoom, table[v].flip = float(vs.zoom[v]), int(bool(vs.flip[v]))
+    return table
+
+
+def _expand_views(bases: np.ndarray, vs: Views, side: int, device: torch.device):
+    """One base-record upload and one metro_expand_views launch -> (MetroCropWarp [n V, 160], MetroPlacement [n V, 208]) uint8
+    device tensors."""
+    n, nv = len(bases), len(vs.zoom)
+    d_bases = _upload(bases, device)
+    crops = torch.empty((n * nv, C.sizeof(_lib.MetroCropWarp)), dtype=torch.uint8, device=device)
+    places = torch.empty((n * nv, C.sizeof(_lib.MetroPlacement)), dtype=torch.uint8, device=device)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    check(_lib.load().metro_expand_views(C.c_void_p(d_bases.data_ptr()), n, view_table(vs), nv, side,
+                                         C.c_void_p(crops.data_ptr()), C.c_void_p(places.data_ptr()), C.c_void_p(stream)),
+          'metro_expand_views')
+    return crops, places
+
+
+def _warp_views(frames, cameras, boxes, fi, vs: Views, side: int, device: torch.device):
+    """Per-box host geometry, the expansion and ONE warp launch of the n V crops -> (crops [n V, side, side, 3], placement
+    records [n V, 208])."""
+    dev_frames = _device_frames(frames, device)
+    n = len(boxes)
+    if n and (fi.min() < 0 or fi.max() >= len(dev_frames)):
+        raise ValueError(f'frame_index must lie in [0, {len(dev_frames)}), got [{fi.min()}, {fi.max()}]')
+    crop_recs, places = _expand_views(pack_view_bases(cameras, boxes, fi, side), vs, side, device)
+    crops = torch.empty((n * len(vs.zoom), side, side, 3), dtype=torch.float32, device=device)
+    _launch_warp(dev_frames, crop_recs, len(crops), side, crops, device)
+    return crops, places
+
+
+def _merge_views(poses, keypoints, z, places, mirror, n: int, nv: int, spread: bool):
+    """One metro_merge_views launch -> (poses [n, J, 3], keypoints [n, J, 2] or None, z [n] or None, spread [n, J] or None)."""
+    nj = poses.shape[1]
+    dev = poses.device
+    out = torch.empty((n, nj, 3), dtype=torch.float32, device=dev)
+    kp = torch.empty((n, nj, 2), dtype=torch.float32, device=dev) if keypoints is not None else None
+    zo = torch.empty(n, dtype=torch.float32, device=dev) if z is not None else None
+    sp = torch.empty((n, nj), dtype=torch.float32, device=dev) if spread else None
+    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    check(_lib.load().metro_merge_views(ptr(poses), ptr(keypoints), ptr(z), ptr(places), ptr(mirror), n, nv, nj, ptr(out),
+                                        ptr(kp), ptr(zo), ptr(sp), C.c_void_p(stream)), 'metro_merge_views')
+    return out, kp, zo, sp
+
+
+_ROT_TO_ORIG_CAM = _lib.MetroPlacement.rot_to_orig_cam.offset // 4      # float index of the field in a MetroPlacement
+_ROT_TO_WORLD = _lib.MetroPlacement.rot_to_world.offset // 4
+
+
 def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index=None, coords: str = 'camera',
-                            precision: Optional[str] = None, check_finite: Optional[bool] = None):
+                            precision: Optional[str] = None, check_finite: Optional[bool] = None, views=None):
     """uint8 frames + person boxes [n, 4] (x, y, w, h) -> (poses [n, Jout, 3] mm, joint_edges, joint_names) like estimate_pose.
 
     frames: a uint8 [H, W, 3] tensor / array or a list of them (host or device, sizes may differ, at most 64);
@@ -364,10 +621,18 @@ def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index
     One enqueue chain on the current stream of the local device: frame and parameter uploads (pinned, non-blocking), one warp
     launch, estimate_pose's forward in <= 256-crop chunks on its cached engine with its finite screen (its one stream
     synchronisation), then metro_to_orig_cam.  Runs on the local device only (estimate_pose's shard=False): sharding across
-    ranks is not supported here."""
+    ranks is not supported here.
+    views: None (one crop per box, the path above) or test-time views (view_set: an int V for the default set, or
+    (roll_deg, zoom, flip) triples): the host geometry stays per box, metro_expand_views derives the n V crop records on the
+    device, one warp launch cuts them, estimate_pose runs on the n V crops, metro_to_orig_cam rotates each view back (mirroring
+    flipped views' joints) and metro_merge_views averages the views of each box.  coords='crop' takes one view only (the views
+    have different virtual cameras); views=1 returns the bits of views=None."""
     from metro_pose3d_amd.inference import _engine_for, _resolve_device, estimate_pose
     if coords not in ('crop', 'camera', 'world'):
         raise ValueError(f"coords must be 'crop', 'camera' or 'world', got {coords!r}")
+    vs = None if views is None else view_set(views)
+    if vs is not None and coords == 'crop' and len(vs.zoom) > 1:
+        raise ValueError(f"coords='crop' takes one view: the {len(vs.zoom)} views have different virtual cameras")
     if precision is None:
         precision = os.environ.get('METRO_PRECISION', 'f16')
     boxes = np.asarray(boxes, np.float64)
@@ -377,6 +642,8 @@ def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index
     fi = np.zeros(n, np.int64) if frame_index is None else np.asarray(frame_index, np.int64).reshape(n)
     first = frames if isinstance(frames, torch.Tensor) else frames[0] if isinstance(frames, (list, tuple)) and frames else None
     device = _resolve_device(first if isinstance(first, torch.Tensor) else torch.empty(0))
+    if vs is not None and n:
+        return _estimate_pose_views(frames, boxes, model_path, cameras, fi, coords, precision, check_finite, vs, device)
     with torch.cuda.device(device):
         side = _engine_for(model_path, precision, device, max(n, 1)).spec.proc_side
         params = crop_params(cameras, boxes, fi, side)
@@ -392,6 +659,28 @@ def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index
         check(_lib.load().metro_to_orig_cam(C.c_void_p(poses.data_ptr()), C.c_void_p(rot.data_ptr()),
                                             C.c_void_p(mirror.data_ptr()), C.c_void_p(out.data_ptr()), n, sk.n_out,
                                             C.c_void_p(stream)), 'metro_to_orig_cam')
+    return out, edges, names
+
+
+def _estimate_pose_views(frames, boxes, model_path, cameras, fi, coords, precision, check_finite, vs: Views, device):
+    from metro_pose3d_amd.inference import _engine_for, estimate_pose
+    n, nv = len(boxes), len(vs.zoom)
+    with torch.cuda.device(device):
+        side = _engine_for(model_path, precision, device, n * nv).spec.proc_side
+        crops, places = _warp_views(frames, cameras, boxes, fi, vs, side, device)
+        poses, edges, names = estimate_pose(crops, model_path, precision=precision, check_finite=check_finite, shard=False)
+        if coords == 'crop':                                           # one view (checked by the caller)
+            return poses, edges, names
+        sk = _engine_for(model_path, precision, device, n * nv).spec.skeleton
+        at = _ROT_TO_ORIG_CAM if coords == 'camera' else _ROT_TO_WORLD
+        rot = places.view(torch.float32)[:, at:at + 9].contiguous()
+        mirror = _upload(np.asarray(sk.out_mirror, np.int32), device)
+        placed = torch.empty_like(poses)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        check(_lib.load().metro_to_orig_cam(C.c_void_p(poses.data_ptr()), C.c_void_p(rot.data_ptr()),
+                                            C.c_void_p(mirror.data_ptr()), C.c_void_p(placed.data_ptr()), n * nv, sk.n_out,
+                                            C.c_void_p(stream)), 'metro_to_orig_cam')
+        out = _merge_views(placed, None, None, places, mirror, n, nv, spread=False)[0]
     return out, edges, names
 
 
@@ -477,7 +766,7 @@ def _placement_targets(scale_recovery, cameras, n, n_edges, bone_lengths, root_d
 
 def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=None, scale_recovery: str = 'bone-lengths',
                            bone_lengths=None, root_depth=None, coords: str = 'camera', precision: Optional[str] = None,
-                           check_finite: Optional[bool] = None) -> FramePoses:
+                           check_finite: Optional[bool] = None, views=None, return_spread: bool = False):
     """uint8 frames + person boxes -> FramePoses(poses, keypoints2d, z_offset, joint_edges, joint_names): where each person is
     in 3D and where each joint lands in its frame's pixels.  frames, boxes, frame_index, cameras, precision and check_finite as
     for estimate_pose_in_frames.
@@ -496,10 +785,19 @@ def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=
     camera's project_points (a camera with coefficients).  NaN where the ray points behind the original camera.
     One enqueue chain on the current stream of the local device: uploads, one warp launch, metro_forward_coords01 in <= 256-crop
     chunks with the finite screen folded on the device, one metro_place_poses launch, then the call's one stream
-    synchronisation (the screen).  No default bone-length table ships: the reference's come from its training data."""
+    synchronisation (the screen).  No default bone-length table ships: the reference's come from its training data.
+    views: None (one crop per box) or test-time views as for estimate_pose_in_frames: n V crops through the same chain
+    (bone lengths and root depths repeated per view), each view placed by metro_place_poses in `coords` (flipped views'
+    joints mirrored), then metro_merge_views: poses and z offsets averaged over the views, keypoints over the views whose
+    keypoint is finite (a flipped view contributes its mirror joint's), NaN if none.  views=1 returns the bits of
+    views=None.  return_spread=True returns (FramePoses, spread [n, Jout]): per joint, the RMS 3D distance in mm of the
+    views from their mean (zeros with one view), a cheap agreement score."""
     from metro_pose3d_amd.inference import _engine_for, _resolve_device
     if coords not in COORDS:
         raise ValueError(f"coords must be 'crop', 'camera' or 'world', got {coords!r}")
+    vs = None if views is None else view_set(views)
+    if vs is not None and coords == 'crop' and len(vs.zoom) > 1:
+        raise ValueError(f"coords='crop' takes one view: the {len(vs.zoom)} views have different virtual cameras")
     if precision is None:
         precision = os.environ.get('METRO_PRECISION', 'f16')
     if check_finite is None:
@@ -515,6 +813,21 @@ def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=
     device = _resolve_device(first if isinstance(first, torch.Tensor) else torch.empty(0))
     names = np.empty(sk.n_out, dtype=object)
     names[:] = sk.names_bytes()
+    if vs is not None and n:
+        res = _locate_poses_views(frames, boxes, model_path, cameras, fi, scale_recovery, targets, per_pose, root_z, coords,
+                                  precision, check_finite, vs, sk, names, device)
+        return res if return_spread else res[0]
+    res = _locate_poses(frames, boxes, model_path, cameras, fi, scale_recovery, targets, per_pose, root_z, coords, precision,
+                        check_finite, sk, names, device)
+    if return_spread:
+        return res, torch.zeros((n, sk.n_out), dtype=torch.float32, device=device)
+    return res
+
+
+def _locate_poses(frames, boxes, model_path, cameras, fi, scale_recovery, targets, per_pose, root_z, coords, precision,
+                  check_finite, sk, names, device) -> FramePoses:
+    from metro_pose3d_amd.inference import _engine_for
+    n = len(boxes)
     with torch.cuda.device(device):
         eng = _engine_for(model_path, precision, device, max(n, 1))
         spec = eng.spec
@@ -553,3 +866,50 @@ def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=
                 'soft-argmax with non-finite statistics' +
                 (' (fp16 storage overflows at 65504: run this model with precision f32m or f64)' if precision == 'f16' else ''))
     return FramePoses(poses, keypoints, z_offset, sk.edges_array(), names)
+
+
+def _locate_poses_views(frames, boxes, model_path, cameras, fi, scale_recovery, targets, per_pose, root_z, coords, precision,
+                        check_finite, vs: Views, sk, names, device):
+    """locate_poses_in_frames with views: -> (FramePoses, spread [n, Jout])."""
+    from metro_pose3d_amd.inference import _engine_for
+    n, nv = len(boxes), len(vs.zoom)
+    m = n * nv
+    if per_pose:                                    # per-box targets, repeated per view by index (box-major rows)
+        targets = np.repeat(targets, nv, axis=0)
+    if root_z is not None:
+        root_z = np.repeat(root_z, nv)
+    with torch.cuda.device(device):
+        eng = _engine_for(model_path, precision, device, m)
+        spec = eng.spec
+        side = spec.proc_side
+        crops, places = _warp_views(frames, cameras, boxes, fi, vs, side, device)
+        rel = torch.empty((m, sk.n_out, 3), dtype=torch.float32, device=device)
+        coords01 = torch.empty((m, sk.n_head, 3), dtype=torch.float32, device=device)
+        bad = None
+        for i in range(0, m, eng.max_batch):
+            k = min(eng.max_batch, m - i)
+            eng.forward(crops[i:i + k], out=rel[i:i + k], coords01=coords01[i:i + k])
+            if check_finite:       # folded on the device after every chunk: ONE synchronisation per call, below
+                cnt = eng.status_words(k).ne(0).sum()
+                bad = cnt if bad is None else bad + cnt
+        poses_v = torch.empty((m, sk.n_out, 3), dtype=torch.float32, device=device)
+        keypoints_v = torch.empty((m, sk.n_out, 2), dtype=torch.float32, device=device)
+        z_v = torch.empty(m, dtype=torch.float32, device=device) if scale_recovery != 'metro' else None
+        mirror = _upload(np.asarray(sk.out_mirror, np.int32), device)
+        d_targets = _upload(targets, device) if targets is not None else None
+        d_root = _upload(root_z, device) if root_z is not None else None
+        d_edges = _upload(np.asarray(sk.head_edges, np.int32).reshape(-1, 2), device) if targets is not None else None
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        check(_lib.load().metro_place_poses(ptr(coords01), ptr(rel), ptr(places), m, C.byref(eng.cspec), SCALE_RECOVERY[scale_recovery],
+                                            ptr(d_targets), per_pose, ptr(d_root), ptr(d_edges), len(sk.head_edges),
+                                            ptr(mirror), COORDS[coords], ptr(poses_v), ptr(keypoints_v), ptr(z_v),
+                                            C.c_void_p(stream)), 'metro_place_poses')
+        poses, keypoints, z_offset, spread = _merge_views(poses_v, keypoints_v, z_v, places, mirror, n, nv, spread=True)
+        n_bad = int(bad.item()) if bad is not None else 0              # the call's one stream synchronisation
+        if n_bad:
+            raise _lib.NonFiniteError(
+                f'{spec.arch_name} stride {spec.stride} in precision {precision!r}: {n_bad} of {m} view crops reached the '
+                'soft-argmax with non-finite statistics' +
+                (' (fp16 storage overflows at 65504: run this model with precision f32m or f64)' if precision == 'f16' else ''))
+    return FramePoses(poses, keypoints, z_offset, sk.edges_array(), names), spread

@@ -244,11 +244,14 @@ def main(argv=None):
     parser.add_argument('--root-depth', type=str, default=None,
                         help='MM[,MM...]: root depth of every --box person in its crop\'s virtual camera (true-root-depth '
                              'scale recovery; needs --intrinsics)')
+    parser.add_argument('--views', type=int, default=None,
+                        help='N: test-time augmentation, N rolled / flipped views per --box averaged (the default view set of '
+                             'frames.view_set: rolls -20..+20 degrees, flips on odd views; 1 to 32)')
     opts = parser.parse_args(argv)
     if opts.frame:
         return _main_frame(opts)
-    if opts.box or opts.intrinsics or opts.distortion or opts.bone_lengths or opts.root_depth:
-        parser.error('--box, --intrinsics, --distortion, --bone-lengths and --root-depth go with --frame')
+    if opts.box or opts.intrinsics or opts.distortion or opts.bone_lengths or opts.root_depth or opts.views is not None:
+        parser.error('--box, --intrinsics, --distortion, --bone-lengths, --root-depth and --views go with --frame')
     if opts.image:
         img = np.load(opts.image).astype(np.float32)
     else:
@@ -285,7 +288,11 @@ def _main_frame(opts):
         raise SystemExit('--distortion needs --intrinsics')
     if opts.bone_lengths or opts.root_depth:
         return _main_locate(opts, frame, boxes, camera)
-    poses, edges, names = estimate_pose_in_frames(frame, boxes, opts.model_path, cameras=camera, precision=opts.precision)
+    try:
+        poses, edges, names = estimate_pose_in_frames(frame, boxes, opts.model_path, cameras=camera, precision=opts.precision,
+                                                      views=opts.views)
+    except ValueError as e:
+        raise SystemExit(str(e))
     for k, pose in enumerate(poses.cpu().numpy()):
         print(f'box {k} {opts.box[k]} (camera frame, root-relative mm)')
         for name, p in zip(names, pose):
@@ -303,7 +310,8 @@ def _main_locate(opts, frame, boxes, camera):
     else:
         kw = dict(scale_recovery='true-root-depth', root_depth=_floats(opts.root_depth, len(boxes), '--root-depth'))
     try:
-        res = locate_poses_in_frames(frame, boxes, opts.model_path, cameras=camera, precision=opts.precision, **kw)
+        res = locate_poses_in_frames(frame, boxes, opts.model_path, cameras=camera, precision=opts.precision, views=opts.views,
+                                     **kw)
     except ValueError as e:
         raise SystemExit(str(e))
     poses, kp, z = res.poses.cpu().numpy(), res.keypoints2d.cpu().numpy(), res.z_offset.cpu().numpy()

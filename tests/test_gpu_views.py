@@ -1,0 +1,212 @@
+"""Test-time views on the MI355X (metro_expand_views, metro_merge_views, `views=` of estimate_pose_in_frames and
+locate_poses_in_frames): one view reproduces the call without views bit for bit, copies of one view merge to its bits, the
+device-expanded records against their host restatement (frames.view_params) and the crops cut through them, the whole call
+against the oracle forward and the NumPy merge, and the mirror swap of a flipped view."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from metro_pose3d_amd import _lib, frames as FR
+from metro_pose3d_amd._lib import check
+from metro_pose3d_amd.frames import (COORDS, SCALE_RECOVERY, estimate_pose_in_frames, locate_poses_in_frames, view_params,
+                                     view_set)
+from tests import oracle_placement as OPL, oracle_views as OV
+from tests.test_gpu_frames import _cameras, _frame, _oracle_crops
+from tests.test_gpu_placement import _toy_engine_model
+
+pytestmark = pytest.mark.gpu
+
+SEL = [0, 8, 11, 16, 19]          # boxes of the frames fixture: distorted cameras 0 and 1, the undistorted camera 2
+
+
+def _scene(undistorted_last=True):
+    d, cams = _cameras()
+    if undistorted_last:
+        cams[2].distortion_coeffs = None                  # the homography mode next to the distorted one
+    frames = [_frame(*d[f'cam{i}_frame_hw'], seed=70 + i) for i in range(3)]
+    return cams, frames, d['boxes'][SEL], d['box_camera'][SEL].astype(np.int64)
+
+
+def _np(t):
+    return None if t is None else t.cpu().numpy()
+
+
+def _fields(raw, struct):
+    """uint8 [m, sizeof] records -> {field: array [m, ...]}."""
+    dt = np.dtype(struct)
+    rec = np.ascontiguousarray(raw).view(dt).ravel()
+    return {f: rec[f] for f in dt.names}
+
+
+@pytest.mark.parametrize('precision', ['f16', 'f64'])
+def test_one_view_is_bit_identical_to_no_views(cuda, tmp_path, precision):
+    spec, _, path = _toy_engine_model(tmp_path)
+    cams, frames, boxes, fi = _scene()
+    bones = np.random.default_rng(2).uniform(200, 450, len(spec.skeleton.head_edges))
+    for cameras in (cams, None):
+        base = estimate_pose_in_frames(frames, boxes, path, cameras=cameras, frame_index=fi, precision=precision)[0]
+        scale = dict(bone_lengths=bones) if cameras is not None else dict(scale_recovery='metro')
+        ref = locate_poses_in_frames(frames, boxes, path, cameras=cameras, frame_index=fi, precision=precision, **scale)
+        for views in (1, [(0, 1, False)], [(0.0, 1.0, np.bool_(False))]):
+            got = estimate_pose_in_frames(frames, boxes, path, cameras=cameras, frame_index=fi, precision=precision, views=views)[0]
+            assert torch.equal(got, base), (cameras is None, views)
+            loc, spread = locate_poses_in_frames(frames, boxes, path, cameras=cameras, frame_index=fi, precision=precision,
+                                                 views=views, return_spread=True, **scale)
+            assert torch.equal(loc.poses, ref.poses) and (cameras is None or torch.equal(loc.z_offset, ref.z_offset))
+            assert np.array_equal(_np(loc.keypoints2d), _np(ref.keypoints2d), equal_nan=True)
+            assert (spread == 0).all() and spread.shape == (len(boxes), spec.skeleton.n_out)
+        if cameras is None:
+            crop = estimate_pose_in_frames(frames, boxes, path, frame_index=fi, precision=precision, coords='crop')[0]
+            got = estimate_pose_in_frames(frames, boxes, path, frame_index=fi, precision=precision, coords='crop', views=1)[0]
+            assert torch.equal(got, crop)
+
+
+def test_copies_of_one_view_merge_to_its_bits(cuda, tmp_path):
+    """V copies of a rolled, zoomed, flipped view: the merge of V equal rows is that row (fp64 sums of <= 32 equal fp32 values
+    are exact) and the spread is exactly 0.  f64: its forward gives a crop the same bits at any batch size."""
+    spec, _, path = _toy_engine_model(tmp_path)
+    cams, frames, boxes, fi = _scene()
+    bones = np.random.default_rng(3).uniform(200, 450, len(spec.skeleton.head_edges))
+    view = (12.5, 1.15, True)
+    for cameras, scale in ((cams, dict(bone_lengths=bones)), (None, dict(scale_recovery='metro'))):
+        one, s1 = locate_poses_in_frames(frames, boxes, path, cameras=cameras, frame_index=fi, precision='f64', views=[view],
+                                         return_spread=True, **scale)
+        many, s4 = locate_poses_in_frames(frames, boxes, path, cameras=cameras, frame_index=fi, precision='f64',
+                                          views=[view] * 4, return_spread=True, **scale)
+        assert torch.equal(one.poses, many.poses) and (s4 == 0).all() and (s1 == 0).all()
+        assert np.array_equal(_np(one.keypoints2d), _np(many.keypoints2d), equal_nan=True)
+        if cameras is not None:
+            assert torch.equal(one.z_offset, many.z_offset)
+        rel1 = estimate_pose_in_frames(frames, boxes, path, cameras=cameras, frame_index=fi, precision='f64', views=[view])[0]
+        rel4 = estimate_pose_in_frames(frames, boxes, path, cameras=cameras, frame_index=fi, precision='f64', views=[view] * 4)[0]
+        assert torch.equal(rel1, rel4)
+
+
+def _ulps(a, b, scale, dt):
+    return np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64)) / np.spacing(np.asarray(scale, dt)).astype(np.float64)
+
+
+def test_expanded_records_match_the_host_restatement(cuda):
+    """metro_expand_views' records against frames.view_params: fp32 fields within 1 ulp, the fp64 partial homography within 4
+    ulp.  A 3x3 entry's ulp is that of the largest entry of its column: a column multiplies one homogeneous coordinate, and
+    entries that are 0 in exact arithmetic come out of LAPACK's solve as ~1e-20 where the closed-form inverse gives 0 (the
+    homography's bottom row).  Crops cut through the device records are byte-identical to crops cut through the host records on
+    every view whose records are bit-identical."""
+    for undistorted in (True, False):
+        cams, frames, boxes, fi = _scene(undistorted)
+        views = [(0, 1, False), (-20, 1, False), (-7.5, 1.2, True), (20, 0.8, True), (3, 1, False), (0, 1.3, True)]
+        vs = view_set(views)
+        nv = len(views)
+        for cameras in (cams, None):
+            p, q = view_params(cameras, boxes, fi, views, 256)
+            bases = FR.pack_view_bases(cameras, boxes, fi, 256)
+            crops_raw, places_raw = FR._expand_views(bases, vs, 256, cuda)
+            c, pl = _fields(_np(crops_raw), _lib.MetroCropWarp), _fields(_np(places_raw), _lib.MetroPlacement)
+            m = len(boxes) * nv
+            assert (c['frame'] == np.repeat(fi, nv)).all() and (c['mode'] == p.mode).all() and (pl['keypoint_mode'] == p.mode).all()
+            f32 = [(c['homography'], p.homography), (pl['homography'], p.homography), (pl['inv_intrinsics'], q.inv_intrinsics),
+                   (pl['rot_to_orig_cam'], q.rot_to_orig_cam), (pl['rot_to_world'], q.rot_to_world), (pl['cam_loc'], q.cam_loc),
+                   (c['intrinsics'], p.intrinsics.reshape(m, 9)[:, :6]), (c['distortion'], p.distortion)]
+            same = np.ones(m, bool)
+            for got, want in f32:
+                got, want = got.reshape(m, -1), np.asarray(want, np.float32).reshape(m, -1)
+                scale = np.maximum(np.abs(got), np.abs(want))
+                if got.shape[1] == 9:
+                    scale = np.tile(scale.reshape(m, 3, 3).max(axis=1), (1, 3))
+                u = _ulps(got, want, scale, np.float32)
+                assert u.max() <= 1, u.max()
+                same &= (got == want).all(axis=1)
+            got, want = c['partial'].reshape(m, 3, 3), p.partial
+            col = np.maximum(np.abs(got), np.abs(want)).max(axis=1, keepdims=True)
+            assert _ulps(got, want, col, np.float64).max() <= 4
+            same &= (got == want).all(axis=(1, 2))
+            ident = np.tile([v == (0, 1, False) for v in views], len(boxes))
+            assert same[ident].all()                                  # the identity view copies the box's records
+            dev = torch.empty((m, 256, 256, 3), dtype=torch.float32, device=cuda)
+            FR._launch_warp(FR._device_frames(frames, cuda), crops_raw, m, 256, dev, cuda)
+            rows = np.flatnonzero(same)
+            host = FR.warp_frames(frames, FR.CropParams(*(a[rows] for a in p)), np.repeat(fi, nv)[rows], 256, device=cuda)
+            assert torch.equal(dev[rows], host)
+            print(f'undistorted camera 2 {undistorted}, cameras {cameras is not None}: {len(rows)} of {m} views bit-identical '
+                  f'records (byte-identical crops)')
+
+
+def test_views_match_the_oracle_f64(cuda, tmp_path):
+    """V = 5 (rolls, zooms other than 1, flips), distorted and undistorted cameras, every scale recovery: the merged call
+    against the NumPy merge of per-view oracle placements, each view's crop cut by tests/oracle_frames.py from the host
+    restatement's records and run through the oracle forward in fp64.  Poses within 1e-3 mm, keypoints within 1e-3 px."""
+    from oracle import forward as OF
+    from tests import helpers as H
+    spec, params, path = _toy_engine_model(tmp_path)
+    cams, frames, boxes, fi = _scene()
+    views = [(-20, 1, False), (-8, 1.2, True), (0, 1, False), (9, 0.85, True), (20, 1.1, False)]
+    nv, n = len(views), len(boxes)
+    p, q = view_params(cams, boxes, fi, views, 256)
+    fir = np.repeat(fi, nv)
+    collect = {}
+    rel = OF.forward(H.oracle_spec(spec), params, _oracle_crops(frames, p, fir, 256), torch.float64, collect=collect)
+    c01 = collect['coords01'].numpy().astype(np.float32)
+    rel = np.asarray(rel.numpy() if isinstance(rel, torch.Tensor) else rel, np.float32)
+    perm, mirror = spec.skeleton.permutation, spec.skeleton.out_mirror
+    rng = np.random.default_rng(5)
+    bones = rng.uniform(200, 450, (n, len(spec.skeleton.head_edges)))
+    root = rng.uniform(3000, 5000, n)
+    worst3, worstkp = 0.0, 0.0
+    for scale, kw in (('metro', {}), ('bone-lengths', dict(bone_lengths=bones)), ('true-root-depth', dict(root_depth=root))):
+        for coords in ('camera', 'world'):
+            got, spread = locate_poses_in_frames(frames, boxes, path, cameras=cams, frame_index=fi, scale_recovery=scale,
+                                                 coords=coords, precision='f64', views=views, return_spread=True, **kw)
+            pv, kv, zv = OPL.place(c01, q, spec.stride, scale, coords, perm, mirror, edges=spec.skeleton.head_edges,
+                                   bone_lengths=np.repeat(bones, nv, axis=0), root_depth=np.repeat(root, nv), poses_rel=rel)
+            rot = q.rot_to_orig_cam
+            want, wkp, wz, wsp = OV.merge(pv, kv, zv, rot, mirror, nv)
+            e3 = np.abs(_np(got.poses) - want).max()
+            ekp = np.nanmax(np.abs(_np(got.keypoints2d) - wkp))
+            assert np.array_equal(np.isnan(_np(got.keypoints2d)), np.isnan(wkp))
+            worst3, worstkp = max(worst3, e3), max(worstkp, ekp)
+            assert e3 <= 1e-3, (scale, coords, e3)
+            assert ekp <= 1e-3, (scale, coords, ekp)
+            assert np.abs(_np(spread) - wsp).max() <= 1e-3
+            if scale != 'metro':
+                assert np.abs(_np(got.z_offset) - wz).max() <= 1e-3
+            else:
+                assert got.z_offset is None
+    print(f'views vs oracle: worst 3D {worst3:.2e} mm, worst keypoint {worstkp:.2e} px')
+
+
+def test_flipped_view_swaps_mirror_joints(cuda, tmp_path):
+    """A flipped view in metro mode against the single-view machinery on the same crop (its device records, the engine's
+    forward, one metro_place_poses launch): the merge carries the 3D poses as placed (joint j = R . crop pose of mirror[j])
+    and takes keypoint j from the mirror joint's frame pixel."""
+    from metro_pose3d_amd.inference import _engine_for
+    spec, _, path = _toy_engine_model(tmp_path)
+    cams, frames, boxes, fi = _scene()
+    sk = spec.skeleton
+    mirror = np.asarray(sk.out_mirror)
+    assert (mirror != np.arange(sk.n_out)).any()
+    vs = view_set([(0, 1, True)])
+    got = locate_poses_in_frames(frames, boxes, path, cameras=cams, frame_index=fi, scale_recovery='metro', precision='f32m',
+                                 views=[(0, 1, True)])
+    n = len(boxes)
+    with torch.cuda.device(cuda):
+        eng = _engine_for(path, 'f32m', cuda, n)
+        crops, places = FR._warp_views(frames, cams, boxes, fi, vs, 256, cuda)
+        rel = torch.empty((n, sk.n_out, 3), device=cuda)
+        c01 = torch.empty((n, sk.n_head, 3), device=cuda)
+        eng.forward(crops, out=rel, coords01=c01)
+        out = torch.empty((n, sk.n_out, 3), device=cuda)
+        kp = torch.empty((n, sk.n_out, 2), device=cuda)
+        d_mirror = torch.from_numpy(mirror.astype(np.int32)).to(cuda)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        check(_lib.load().metro_place_poses(ptr(c01), ptr(rel), ptr(places), n, C.byref(eng.cspec), SCALE_RECOVERY['metro'],
+                                            None, 0, None, None, 0, ptr(d_mirror), COORDS['camera'], ptr(out), ptr(kp), None,
+                                            C.c_void_p(torch.cuda.current_stream(cuda).cuda_stream)), 'metro_place_poses')
+    rot = _fields(_np(places), _lib.MetroPlacement)['rot_to_orig_cam'].reshape(n, 3, 3)
+    assert (np.linalg.det(rot.astype(np.float64)) < 0).all()
+    assert torch.equal(got.poses, out)
+    expect = np.einsum('nij,nkj->nki', rot.astype(np.float64), _np(rel).astype(np.float64)[:, mirror])
+    assert np.abs(_np(out) - expect).max() <= 1e-3
+    assert np.array_equal(_np(got.keypoints2d), _np(kp)[:, mirror], equal_nan=True)
+    assert not np.allclose(_np(kp)[:, mirror], _np(kp), equal_nan=True)       # the swap moves the keypoints
