@@ -479,7 +479,7 @@ int  metro_place_poses(const float* d_coords01, const float* d_poses, const Metr
 
 /* ---- test-time augmentation of frame crops: several views per person box (the reference's --test-aug geometry,
  *      src/data/data_loading.py:60-68, 77-79, 110-112) ---- */
-/* One record per box (host code: frames.view_bases): the box's camera, its look_at_box camera and the records of the box
+/* One record per box (host code: frames.pack_view_bases; device: metro_look_at_boxes): the box's camera, its look_at_box camera and the records of the box
  * itself (what frames.crop_params / placement_params give it), from which metro_expand_views derives every view. */
 typedef struct MetroViewBase {
     int32_t frame;              /* index into the frame table                                                             */
@@ -518,6 +518,34 @@ typedef struct MetroView {
  * inv_intrinsics stays 0.  The identity view copies the box's own records: the bits of the call without views. */
 int  metro_expand_views(const MetroViewBase* d_bases, int32_t n, const MetroView* views, int32_t n_views, int32_t side,
                         MetroCropWarp* d_crops_out, MetroPlacement* d_placements_out, void* stream);
+/* One calibrated camera of a frame (host code: frames.pack_frame_cameras, column-wise from frames.Camera).  r_inv and
+ * old_matrix are per-frame products the host takes once with NumPy (np.linalg.inv(R) as Camera.camera_to_world uses it, and
+ * K R as pack_view_bases stores it), so that the device works from the host's own bits for them. */
+typedef struct MetroFrameCamera {
+    float intrinsics[9];        /* K, row-major fp32; fx K[0], fy K[4], cx K[2], cy K[5] (a skew K[1] rides along)         */
+    float r[9];                 /* world -> camera rotation, row-major fp32                                                */
+    float r_inv[9];             /* np.linalg.inv(R) in fp32 (camera_to_world's matrix)                                     */
+    float t[3];                 /* optical centre in world coordinates, fp32                                               */
+    float distortion[5];        /* k1 k2 p1 p2 k3 (OpenCV order); read when has_distortion                                 */
+    int32_t has_distortion;     /* 0: distortion_coeffs None (homography mode); 1: any coefficient array, zeros included  */
+    double world_up[3];         /* turn_towards' up vector                                                                 */
+    double old_matrix[9];       /* K R as the host's fp32 product (MetroViewBase.old_matrix)                               */
+} MetroFrameCamera;             /* 240 bytes */
+/* The MetroViewBase of n person boxes on the device, one thread per box in fp64: frames.pack_view_bases without the host.
+ * d_boxes fp64 [n, 4] (x, y, w, h); d_frame_index int32 [n], each in [0, n_frames) (n_frames <= METRO_MAX_FRAMES): the frame
+ * of each box.  d_cameras: NULL (cameras=None: preprocess.box_homography's square crop, has_camera 0, rotations I,
+ * inv_intrinsics 0; n_cameras 0) or a DEVICE table of n_cameras == 1 (one camera for every frame) or n_cameras == n_frames
+ * entries (camera of frame f at f).  With a camera each record follows frames.look_at_box step by step in the host's dtypes
+ * (side points and centre rounded to fp32, undistort_points' 5 fixed iterations in fp64, camera_to_world / world_to_camera
+ * and the new R in fp32, square_pixels' K in fp64, zoom, centre_principal_point) and then _frame_params_and_cameras
+ * (homography = old_matrix inv(K R) cast to fp32; partial = fp32(orig.R fp32(inv R)) inv(K); rot_to_orig_cam, rot_to_world,
+ * inv_intrinsics = inv(K) cast to fp32; cam_loc = t), 3x3 inverses in closed form: within a few fp32 ulp of the host, not
+ * its LAPACK bits.  A frame index outside [0, n_frames) is clamped into it (the record's `frame` too, so nothing downstream
+ * reads outside the tables) and counted: d_status (one int32, overwritten) receives the number of such boxes, which the
+ * caller must treat as an error. */
+int  metro_look_at_boxes(const double* d_boxes, const int32_t* d_frame_index, int32_t n, int32_t n_frames,
+                         const MetroFrameCamera* d_cameras, int32_t n_cameras, int32_t side, MetroViewBase* d_bases_out,
+                         int32_t* d_status, void* stream);
 /* Fuses the n_views rows of each of n boxes (box-major, row i * n_views + v).  d_poses fp32 [n * n_views, n_joints, 3] in the
  * requested coords with joints already mirrored (metro_place_poses / metro_to_orig_cam); d_keypoints fp32
  * [n * n_views, n_joints, 2] frame pixels (unmirrored, as metro_place_poses writes them) or NULL; d_z_offset fp32

@@ -94,6 +94,12 @@ class MetroViewBase(C.Structure):
                 ('cam_loc', C.c_float * 3), ('intrinsics', C.c_float * 6), ('distortion', C.c_float * 5)]
 
 
+class MetroFrameCamera(C.Structure):
+    _fields_ = [('intrinsics', C.c_float * 9), ('r', C.c_float * 9), ('r_inv', C.c_float * 9), ('t', C.c_float * 3),
+                ('distortion', C.c_float * 5), ('has_distortion', C.c_int32), ('world_up', C.c_double * 3),
+                ('old_matrix', C.c_double * 9)]
+
+
 class MetroView(C.Structure):
     _fields_ = [('cos_roll', C.c_double), ('sin_roll', C.c_double), ('zoom', C.c_double), ('flip', C.c_int32),
                 ('reserved', C.c_int32)]
@@ -149,6 +155,7 @@ SIGNATURES = {
     'metro_place_poses': (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(MetroSpec), C.c_int32, _P, C.c_int32, _P, _P, C.c_int32,
                                     _P, C.c_int32, _P, _P, _P, _P]),
     'metro_expand_views': (C.c_int, [_P, C.c_int32, C.POINTER(MetroView), C.c_int32, C.c_int32, _P, _P, _P]),
+    'metro_look_at_boxes': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     'metro_merge_views': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     'metro_heatmap_to_25d': (C.c_int, [_P, C.c_int32, C.POINTER(MetroSpec), _P, _P]),
     'metro_head_f16_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

@@ -405,5 +405,8 @@ int launch_expand_views(const MetroViewBase* bases, int n, const MetroView* view
 int launch_merge_views(const float* poses, const float* keypoints, const float* z, const MetroPlacement* rec, const int* mirror,
                        int n, int n_views, int nj, float* poses_out, float* keypoints_out, float* z_out, float* spread_out,
                        hipStream_t stream);
+// per-box crop geometry of full frames (look_at_boxes.hip)
+int launch_look_at_boxes(const double* boxes, const int32_t* frame_index, int n, int n_frames, const MetroFrameCamera* cameras,
+                         int n_cameras, int side, MetroViewBase* out, int32_t* status, hipStream_t stream);
 
 }  // namespace metro

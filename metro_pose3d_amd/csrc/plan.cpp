@@ -1339,6 +1339,21 @@ int metro_expand_views(const MetroViewBase* d_bases, int32_t n, const MetroView*
     return launch_expand_views(d_bases, n, views, n_views, side, d_crops_out, d_placements_out, static_cast<hipStream_t>(stream));
 }
 
+int metro_look_at_boxes(const double* d_boxes, const int32_t* d_frame_index, int32_t n, int32_t n_frames,
+                        const MetroFrameCamera* d_cameras, int32_t n_cameras, int32_t side, MetroViewBase* d_bases_out,
+                        int32_t* d_status, void* stream) {
+    METRO_CHECK_ARG(d_boxes && d_frame_index && d_bases_out && d_status, "look_at_boxes: NULL boxes / frame_index / bases_out / "
+                    "status pointer");
+    METRO_CHECK_ARG(n > 0 && side > 0, "look_at_boxes: bad geometry (n %d side %d)", n, side);
+    METRO_CHECK_ARG(n_frames >= 1 && n_frames <= METRO_MAX_FRAMES, "look_at_boxes: %d frames (1 to %d per launch)", n_frames,
+                    METRO_MAX_FRAMES);
+    METRO_CHECK_ARG(d_cameras ? (n_cameras == 1 || n_cameras == n_frames) : n_cameras == 0,
+                    "look_at_boxes: %d cameras for %d frames (one for every frame, one per frame, or none with a NULL table)",
+                    n_cameras, n_frames);
+    return launch_look_at_boxes(d_boxes, d_frame_index, n, n_frames, d_cameras, n_cameras, side, d_bases_out, d_status,
+                                static_cast<hipStream_t>(stream));
+}
+
 int metro_merge_views(const float* d_poses, const float* d_keypoints, const float* d_z_offset, const MetroPlacement* d_records,
                       const int32_t* d_mirror, int32_t n, int32_t n_views, int32_t n_joints, float* d_poses_out,
                       float* d_keypoints_out, float* d_z_offset_out, float* d_spread_out, void* stream) {

@@ -16,6 +16,10 @@ the box centre, drops the lens distortion, squares the pixels and zooms so the b
   view_set, pack_view_bases, view_params test-time augmentation (`views=`): V rolled / zoomed / flipped views per box
                                           (data_loading.py:60-68, 77-79), expanded on the device (metro_expand_views) from one
                                           record per box and fused per box after the placement (metro_merge_views)
+  look_at_boxes, pack_frame_cameras       the per-box records on the device (metro_look_at_boxes, `geometry='device'`, the
+                                          default for CUDA boxes): look_at_box and pack_view_bases restated per thread from a
+                                          per-frame camera table, so boxes from a GPU detector stay on the GPU and the call does
+                                          no per-box host work ('host' keeps the NumPy geometry and its bits)
 
 Divergences from the reference, on purpose:
   * a Camera built from intrinsics alone (no R, no t) defaults to world_up = (0, -1, 0), not the reference's (0, 0, 1): with
@@ -32,7 +36,11 @@ Divergences from the reference, on purpose:
     called as (points, virtual, original)): that inverted fast path is not reproduced;
   * test-time views are deterministic (view_set), not the loader's random draws; the loader's `shift_aug_by_rot` centre shift
     is not offered (it would need a look_at_box per view); a flip mirrors about x = side/2, the principal point that
-    center_principal_point sets, not about the pixel grid's centre (side - 1)/2.
+    center_principal_point sets, not about the pixel grid's centre (side - 1)/2;
+  * the device geometry (geometry='device') inverts 3x3 matrices in closed form, not with LAPACK's pivoted solves: its records
+    are within one fp32 ulp of the host's (most of them bit-identical), not always the host's bits.  The host geometry, the
+    default for host boxes, costs ~0.2 ms of NumPy per box and bounds the call there (profiles/frames_probe.json); the
+    device geometry takes one ~6 us launch for 64 boxes (profiles/device_geometry_probe.json).
 """
 from __future__ import annotations
 
@@ -559,11 +567,11 @@ def view_table(vs: Views):
     return table
 
 
-def _expand_views(bases: np.ndarray, vs: Views, side: int, device: torch.device):
-    """One base-record upload and one metro_expand_views launch -> (MetroCropWarp [n V, 160], MetroPlacement [n V, 208]) uint8
-    device tensors."""
+def _expand_views(bases, vs: Views, side: int, device: torch.device):
+    """One base-record upload (host records; device records, e.g. metro_look_at_boxes', are used in place) and one
+    metro_expand_views launch -> (MetroCropWarp [n V, 160], MetroPlacement [n V, 208]) uint8 device tensors."""
     n, nv = len(bases), len(vs.zoom)
-    d_bases = _upload(bases, device)
+    d_bases = bases if isinstance(bases, torch.Tensor) else _upload(bases, device)
     crops = torch.empty((n * nv, C.sizeof(_lib.MetroCropWarp)), dtype=torch.uint8, device=device)
     places = torch.empty((n * nv, C.sizeof(_lib.MetroPlacement)), dtype=torch.uint8, device=device)
     stream = torch.cuda.current_stream(device).cuda_stream
@@ -586,6 +594,163 @@ def _warp_views(frames, cameras, boxes, fi, vs: Views, side: int, device: torch.
     return crops, places
 
 
+# ---- device geometry: the MetroViewBase records of the boxes computed on the GPU (metro_look_at_boxes) ----
+
+GEOMETRY = ('host', 'device', 'auto')
+FRAME_CAMERA_DTYPE = np.dtype(_lib.MetroFrameCamera)
+
+
+def _geometry_of(geometry, boxes) -> str:
+    """`geometry` of estimate_pose_in_frames / locate_poses_in_frames -> 'host' or 'device' ('auto': 'device' for CUDA boxes)."""
+    if not isinstance(geometry, str) or geometry not in GEOMETRY:
+        raise ValueError(f"geometry must be 'host', 'device' or 'auto', got {geometry!r}")
+    if geometry == 'auto':
+        return 'device' if isinstance(boxes, torch.Tensor) and boxes.is_cuda else 'host'
+    return geometry
+
+
+def _host_array(a):
+    """Host data as given (a torch tensor, on the device or not, is copied to a NumPy array)."""
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
+
+
+def pack_frame_cameras(cameras, n_frames: Optional[int] = None) -> np.ndarray:
+    """The MetroFrameCamera table (include/metro_hip.h) of `cameras` as a structured array: one entry for a single Camera (every
+    frame), else one per frame (the first n_frames of the list, which must hold that many).  Filled column-wise, per frame:
+    K, R, t and the distortion coefficients in fp32, the world-up vector in fp64, and the two per-frame products the host takes
+    with NumPy, inv(R) as Camera.camera_to_world uses it and K R as pack_view_bases stores it."""
+    cams = [cameras] if isinstance(cameras, Camera) else list(cameras)
+    if not isinstance(cameras, Camera) and n_frames is not None:
+        if len(cams) < n_frames:
+            raise ValueError(f'cameras: {len(cams)} Camera objects for {n_frames} frames (one Camera, or one per frame)')
+        cams = cams[:n_frames]
+    if not 1 <= len(cams) <= _lib.METRO_MAX_FRAMES:
+        raise ValueError(f'cameras: {len(cams)} entries (1 to {_lib.METRO_MAX_FRAMES})')
+    for k, c in enumerate(cams):
+        if not isinstance(c, Camera):
+            raise ValueError(f'cameras[{k}] must be a frames.Camera, got {type(c)}')
+    rec = np.zeros(len(cams), FRAME_CAMERA_DTYPE)
+    rec['intrinsics'] = np.stack([c.intrinsic_matrix for c in cams]).reshape(-1, 9)
+    rec['r'] = np.stack([c.R for c in cams]).reshape(-1, 9)
+    rec['r_inv'] = np.stack([np.linalg.inv(c.R) for c in cams]).reshape(-1, 9)
+    rec['t'] = np.stack([c.t for c in cams])
+    rec['has_distortion'] = [c.distortion_coeffs is not None for c in cams]
+    rec['distortion'] = np.stack([np.zeros(5, np.float32) if c.distortion_coeffs is None else c.distortion_coeffs for c in cams])
+    rec['world_up'] = np.stack([np.asarray(c.world_up, np.float64).reshape(3) for c in cams])
+    rec['old_matrix'] = np.stack([(c.intrinsic_matrix @ c.R).astype(np.float64) for c in cams]).reshape(-1, 9)
+    return rec
+
+
+class _DeviceBoxes:
+    """Boxes on the device for metro_look_at_boxes: fp64 [n, 4], and the frame indices either as host int64 [n] (checked
+    against the frame count before any launch) or as a device int32 [n] tensor (checked by the kernel's status)."""
+    __slots__ = ('boxes', 'host_fi', 'device_fi')
+
+    def __init__(self, boxes: torch.Tensor, host_fi: Optional[np.ndarray], device_fi: Optional[torch.Tensor]):
+        self.boxes, self.host_fi, self.device_fi = boxes, host_fi, device_fi
+
+    def __len__(self) -> int:
+        return int(self.boxes.shape[0])
+
+
+def _device_boxes(boxes, frame_index, device: torch.device) -> _DeviceBoxes:
+    """boxes (a float32 / float64 CUDA tensor [n, 4], or host data that is uploaded once) and frame_index (None, host data or a
+    CUDA integer tensor) -> _DeviceBoxes, without a synchronisation."""
+    if isinstance(boxes, torch.Tensor) and boxes.is_cuda:
+        if boxes.device != device:
+            raise ValueError(f'boxes are on {boxes.device}, the call runs on {device}')
+        if boxes.dtype not in (torch.float32, torch.float64) or boxes.dim() != 2 or boxes.shape[1] != 4:
+            raise ValueError(f'boxes must be a float32 or float64 [n, 4] (x, y, w, h) tensor, got {boxes.dtype} '
+                             f'{tuple(boxes.shape)}')
+        d_boxes = boxes.to(torch.float64).contiguous()
+    else:
+        b = np.asarray(_host_array(boxes), np.float64)
+        if b.ndim != 2 or b.shape[1] != 4:
+            raise ValueError(f'boxes must be [n, 4] (x, y, w, h), got {b.shape}')
+        d_boxes = _upload(b, device)
+    n = int(d_boxes.shape[0])
+    if isinstance(frame_index, torch.Tensor) and frame_index.is_cuda:
+        if frame_index.device != device:
+            raise ValueError(f'frame_index is on {frame_index.device}, the call runs on {device}')
+        if frame_index.is_floating_point() or frame_index.is_complex() or frame_index.dtype == torch.bool:
+            raise ValueError(f'frame_index must hold integers, got {frame_index.dtype}')
+        if frame_index.numel() != n:
+            raise ValueError(f'frame_index must hold {n} values (one per box), got {frame_index.numel()}')
+        fi = frame_index.reshape(n)
+        if fi.dtype != torch.int32:         # out-of-range values stay out of range through the cast
+            fi = fi.to(torch.int64).clamp(-1, _lib.METRO_MAX_FRAMES).to(torch.int32)
+        return _DeviceBoxes(d_boxes, None, fi.contiguous())
+    fi = np.zeros(n, np.int64) if frame_index is None else np.asarray(_host_array(frame_index), np.int64).reshape(n)
+    return _DeviceBoxes(d_boxes, fi, None)
+
+
+def _look_at_boxes(cameras, d_boxes: torch.Tensor, d_fi: torch.Tensor, n_frames: int, side: int, device: torch.device):
+    """One camera-table upload (none for cameras=None) and one metro_look_at_boxes launch -> (MetroViewBase [n, 576] uint8,
+    status int32 [1]: the number of frame indices outside [0, n_frames)) device tensors.  n >= 1."""
+    n = int(d_boxes.shape[0])
+    bases = torch.empty((n, VIEW_BASE_DTYPE.itemsize), dtype=torch.uint8, device=device)
+    status = torch.empty(1, dtype=torch.int32, device=device)
+    table, n_cameras = None, 0
+    if cameras is not None:
+        rec = pack_frame_cameras(cameras, n_frames)
+        table, n_cameras = _upload(rec.view(np.uint8), device), len(rec)
+    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    check(_lib.load().metro_look_at_boxes(ptr(d_boxes), ptr(d_fi), n, n_frames, ptr(table), n_cameras, side, ptr(bases),
+                                          ptr(status), C.c_void_p(stream)), 'metro_look_at_boxes')
+    return bases, status
+
+
+def look_at_boxes(cameras, boxes, frame_index=None, side: int = 256, n_frames: Optional[int] = None,
+                  device: Optional[torch.device] = None) -> torch.Tensor:
+    """The device twin of pack_view_bases: the MetroViewBase records of n boxes computed by metro_look_at_boxes, as a uint8
+    device tensor [n, 576].  boxes: a float32 / float64 CUDA tensor [n, 4] or host data; frame_index: None (frame 0), host
+    data or a CUDA integer tensor; cameras: None, one Camera, or one Camera per frame.  n_frames (default: len(cameras) for
+    a list, else METRO_MAX_FRAMES) bounds the frame indices; one outside [0, n_frames) raises ValueError (this reads the
+    kernel's status: one synchronisation)."""
+    if device is None:
+        device = boxes.device if isinstance(boxes, torch.Tensor) and boxes.is_cuda else \
+            torch.device('cuda', torch.cuda.current_device())
+    if n_frames is None:
+        n_frames = len(cameras) if isinstance(cameras, (list, tuple)) else _lib.METRO_MAX_FRAMES
+    db = _device_boxes(boxes, frame_index, device)
+    n = len(db)
+    if n == 0:
+        return torch.empty((0, VIEW_BASE_DTYPE.itemsize), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        bases, status = _look_at_boxes(cameras, db.boxes, _checked_device_fi(db, n_frames, device), n_frames, side, device)
+        _raise_on_bad_frames(int(status.item()), n, n_frames)
+    return bases
+
+
+def _checked_device_fi(db: _DeviceBoxes, n_frames: int, device: torch.device) -> torch.Tensor:
+    """The device frame indices of db; host indices are checked here, before any launch, and uploaded."""
+    if db.device_fi is not None:
+        return db.device_fi
+    fi = db.host_fi
+    if len(fi) and (fi.min() < 0 or fi.max() >= n_frames):
+        raise ValueError(f'frame_index must lie in [0, {n_frames}), got [{fi.min()}, {fi.max()}]')
+    return _upload(fi.astype(np.int32), device)
+
+
+def _raise_on_bad_frames(n_out: int, n: int, n_frames: int) -> None:
+    if n_out:
+        raise ValueError(f'frame_index must lie in [0, {n_frames}): {n_out} of {n} device frame indices lie outside')
+
+
+def _warp_device_boxes(frames, cameras, db: _DeviceBoxes, vs: Views, side: int, device: torch.device):
+    """_warp_views with the geometry on the device: metro_look_at_boxes, the expansion and ONE warp launch, no per-box host
+    work -> (crops [n V, side, side, 3], placement records [n V, 208], (status int32 [1], n_frames)).  The status is read by
+    the caller after its synchronisation (_raise_on_bad_frames)."""
+    dev_frames = _device_frames(frames, device)
+    n_frames = len(dev_frames)
+    bases, status = _look_at_boxes(cameras, db.boxes, _checked_device_fi(db, n_frames, device), n_frames, side, device)
+    crop_recs, places = _expand_views(bases, vs, side, device)
+    crops = torch.empty((len(db) * len(vs.zoom), side, side, 3), dtype=torch.float32, device=device)
+    _launch_warp(dev_frames, crop_recs, len(crops), side, crops, device)
+    return crops, places, (status, n_frames)
+
+
 def _merge_views(poses, keypoints, z, places, mirror, n: int, nv: int, spread: bool):
     """One metro_merge_views launch -> (poses [n, J, 3], keypoints [n, J, 2] or None, z [n] or None, spread [n, J] or None)."""
     nj = poses.shape[1]
@@ -606,7 +771,8 @@ _ROT_TO_WORLD = _lib.MetroPlacement.rot_to_world.offset // 4
 
 
 def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index=None, coords: str = 'camera',
-                            precision: Optional[str] = None, check_finite: Optional[bool] = None, views=None):
+                            precision: Optional[str] = None, check_finite: Optional[bool] = None, views=None,
+                            geometry: str = 'auto'):
     """uint8 frames + person boxes [n, 4] (x, y, w, h) -> (poses [n, Jout, 3] mm, joint_edges, joint_names) like estimate_pose.
 
     frames: a uint8 [H, W, 3] tensor / array or a list of them (host or device, sizes may differ, at most 64);
@@ -626,8 +792,16 @@ def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index
     (roll_deg, zoom, flip) triples): the host geometry stays per box, metro_expand_views derives the n V crop records on the
     device, one warp launch cuts them, estimate_pose runs on the n V crops, metro_to_orig_cam rotates each view back (mirroring
     flipped views' joints) and metro_merge_views averages the views of each box.  coords='crop' takes one view only (the views
-    have different virtual cameras); views=1 returns the bits of views=None."""
+    have different virtual cameras); views=1 returns the bits of views=None.
+    geometry: where the per-box crop geometry is computed.  'host': look_at_box in NumPy per box (boxes are host data);
+    'device': one metro_look_at_boxes launch writes the per-box records on the GPU (boxes a float32 / float64 CUDA tensor
+    [n, 4], or host boxes uploaded once; frame_index host data or a CUDA integer tensor), then metro_expand_views with the
+    identity view when views=None: no per-box host work and no synchronisation before the forward; the records agree with the
+    host's to a few fp32 ulp (include/metro_hip.h).  'auto' (default): 'device' for CUDA boxes, else 'host'.  With device
+    boxes the call runs on the boxes' device; a device frame index outside [0, n_frames) raises ValueError (read from the
+    kernel's status after the call's synchronisation)."""
     from metro_pose3d_amd.inference import _engine_for, _resolve_device, estimate_pose
+    geo = _geometry_of(geometry, boxes)
     if coords not in ('crop', 'camera', 'world'):
         raise ValueError(f"coords must be 'crop', 'camera' or 'world', got {coords!r}")
     vs = None if views is None else view_set(views)
@@ -635,12 +809,19 @@ def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index
         raise ValueError(f"coords='crop' takes one view: the {len(vs.zoom)} views have different virtual cameras")
     if precision is None:
         precision = os.environ.get('METRO_PRECISION', 'f16')
-    boxes = np.asarray(boxes, np.float64)
+    first = frames if isinstance(frames, torch.Tensor) else frames[0] if isinstance(frames, (list, tuple)) and frames else None
+    if geo == 'device':
+        device = _geometry_device(boxes, first)
+        db = _device_boxes(boxes, frame_index, device)
+        if len(db):
+            return _estimate_pose_views(frames, db, model_path, cameras, None, coords, precision, check_finite,
+                                        vs if vs is not None else view_set(1), device)
+        boxes, frame_index = np.zeros((0, 4)), None
+    boxes = np.asarray(_host_array(boxes), np.float64)
     if boxes.ndim != 2 or boxes.shape[1] != 4:
         raise ValueError(f'boxes must be [n, 4] (x, y, w, h), got {boxes.shape}')
     n = len(boxes)
-    fi = np.zeros(n, np.int64) if frame_index is None else np.asarray(frame_index, np.int64).reshape(n)
-    first = frames if isinstance(frames, torch.Tensor) else frames[0] if isinstance(frames, (list, tuple)) and frames else None
+    fi = np.zeros(n, np.int64) if frame_index is None else np.asarray(_host_array(frame_index), np.int64).reshape(n)
     device = _resolve_device(first if isinstance(first, torch.Tensor) else torch.empty(0))
     if vs is not None and n:
         return _estimate_pose_views(frames, boxes, model_path, cameras, fi, coords, precision, check_finite, vs, device)
@@ -662,13 +843,28 @@ def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index
     return out, edges, names
 
 
+def _geometry_device(boxes, first) -> torch.device:
+    """The device of a call with device geometry: the boxes' for CUDA boxes, else the frames' (or the current one)."""
+    from metro_pose3d_amd.inference import _resolve_device
+    if isinstance(boxes, torch.Tensor) and boxes.is_cuda:
+        return _resolve_device(boxes)
+    return _resolve_device(first if isinstance(first, torch.Tensor) else torch.empty(0))
+
+
 def _estimate_pose_views(frames, boxes, model_path, cameras, fi, coords, precision, check_finite, vs: Views, device):
+    """boxes: host boxes with their frame indices fi, or _DeviceBoxes (fi None: the geometry runs on the device)."""
     from metro_pose3d_amd.inference import _engine_for, estimate_pose
     n, nv = len(boxes), len(vs.zoom)
     with torch.cuda.device(device):
         side = _engine_for(model_path, precision, device, n * nv).spec.proc_side
-        crops, places = _warp_views(frames, cameras, boxes, fi, vs, side, device)
+        if isinstance(boxes, _DeviceBoxes):
+            crops, places, (status, n_frames) = _warp_device_boxes(frames, cameras, boxes, vs, side, device)
+        else:
+            crops, places = _warp_views(frames, cameras, boxes, fi, vs, side, device)
+            status = None
         poses, edges, names = estimate_pose(crops, model_path, precision=precision, check_finite=check_finite, shard=False)
+        if status is not None:            # after estimate_pose's synchronisation (its finite screen), or the call's one read
+            _raise_on_bad_frames(int(status.item()), n, n_frames)
         if coords == 'crop':                                           # one view (checked by the caller)
             return poses, edges, names
         sk = _engine_for(model_path, precision, device, n * nv).spec.skeleton
@@ -766,7 +962,8 @@ def _placement_targets(scale_recovery, cameras, n, n_edges, bone_lengths, root_d
 
 def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=None, scale_recovery: str = 'bone-lengths',
                            bone_lengths=None, root_depth=None, coords: str = 'camera', precision: Optional[str] = None,
-                           check_finite: Optional[bool] = None, views=None, return_spread: bool = False):
+                           check_finite: Optional[bool] = None, views=None, return_spread: bool = False,
+                           geometry: str = 'auto'):
     """uint8 frames + person boxes -> FramePoses(poses, keypoints2d, z_offset, joint_edges, joint_names): where each person is
     in 3D and where each joint lands in its frame's pixels.  frames, boxes, frame_index, cameras, precision and check_finite as
     for estimate_pose_in_frames.
@@ -791,8 +988,12 @@ def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=
     joints mirrored), then metro_merge_views: poses and z offsets averaged over the views, keypoints over the views whose
     keypoint is finite (a flipped view contributes its mirror joint's), NaN if none.  views=1 returns the bits of
     views=None.  return_spread=True returns (FramePoses, spread [n, Jout]): per joint, the RMS 3D distance in mm of the
-    views from their mean (zeros with one view), a cheap agreement score."""
+    views from their mean (zeros with one view), a cheap agreement score.
+    geometry: 'host', 'device' or 'auto' as for estimate_pose_in_frames (device boxes: metro_look_at_boxes, then the views
+    chain with the identity view when views=None; bone_lengths and root_depth stay host data); a device frame index outside
+    [0, n_frames) raises ValueError, read together with the finite screen in the call's one synchronisation."""
     from metro_pose3d_amd.inference import _engine_for, _resolve_device
+    geo = _geometry_of(geometry, boxes)
     if coords not in COORDS:
         raise ValueError(f"coords must be 'crop', 'camera' or 'world', got {coords!r}")
     vs = None if views is None else view_set(views)
@@ -802,14 +1003,28 @@ def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=
         precision = os.environ.get('METRO_PRECISION', 'f16')
     if check_finite is None:
         check_finite = os.environ.get('METRO_CHECK_FINITE', '1') != '0'
-    boxes = np.asarray(boxes, np.float64)
+    first = frames if isinstance(frames, torch.Tensor) else frames[0] if isinstance(frames, (list, tuple)) and frames else None
+    if geo == 'device':
+        device = _geometry_device(boxes, first)
+        db = _device_boxes(boxes, frame_index, device)
+        n = len(db)
+        if n:
+            sk = _model_skeleton(model_path)
+            targets, per_pose, root_z = _placement_targets(scale_recovery, cameras, n, len(sk.head_edges), bone_lengths,
+                                                           root_depth)
+            names = np.empty(sk.n_out, dtype=object)
+            names[:] = sk.names_bytes()
+            res = _locate_poses_views(frames, db, model_path, cameras, None, scale_recovery, targets, per_pose, root_z, coords,
+                                      precision, check_finite, vs if vs is not None else view_set(1), sk, names, device)
+            return res if return_spread else res[0]
+        boxes, frame_index = np.zeros((0, 4)), None
+    boxes = np.asarray(_host_array(boxes), np.float64)
     if boxes.ndim != 2 or boxes.shape[1] != 4:
         raise ValueError(f'boxes must be [n, 4] (x, y, w, h), got {boxes.shape}')
     n = len(boxes)
-    fi = np.zeros(n, np.int64) if frame_index is None else np.asarray(frame_index, np.int64).reshape(n)
+    fi = np.zeros(n, np.int64) if frame_index is None else np.asarray(_host_array(frame_index), np.int64).reshape(n)
     sk = _model_skeleton(model_path)
     targets, per_pose, root_z = _placement_targets(scale_recovery, cameras, n, len(sk.head_edges), bone_lengths, root_depth)
-    first = frames if isinstance(frames, torch.Tensor) else frames[0] if isinstance(frames, (list, tuple)) and frames else None
     device = _resolve_device(first if isinstance(first, torch.Tensor) else torch.empty(0))
     names = np.empty(sk.n_out, dtype=object)
     names[:] = sk.names_bytes()
@@ -870,7 +1085,8 @@ def _locate_poses(frames, boxes, model_path, cameras, fi, scale_recovery, target
 
 def _locate_poses_views(frames, boxes, model_path, cameras, fi, scale_recovery, targets, per_pose, root_z, coords, precision,
                         check_finite, vs: Views, sk, names, device):
-    """locate_poses_in_frames with views: -> (FramePoses, spread [n, Jout])."""
+    """locate_poses_in_frames with views: -> (FramePoses, spread [n, Jout]).  boxes: host boxes with their frame indices fi,
+    or _DeviceBoxes (fi None: the geometry runs on the device)."""
     from metro_pose3d_amd.inference import _engine_for
     n, nv = len(boxes), len(vs.zoom)
     m = n * nv
@@ -882,7 +1098,11 @@ def _locate_poses_views(frames, boxes, model_path, cameras, fi, scale_recovery, 
         eng = _engine_for(model_path, precision, device, m)
         spec = eng.spec
         side = spec.proc_side
-        crops, places = _warp_views(frames, cameras, boxes, fi, vs, side, device)
+        if isinstance(boxes, _DeviceBoxes):
+            crops, places, (status, n_frames) = _warp_device_boxes(frames, cameras, boxes, vs, side, device)
+        else:
+            crops, places = _warp_views(frames, cameras, boxes, fi, vs, side, device)
+            status = None
         rel = torch.empty((m, sk.n_out, 3), dtype=torch.float32, device=device)
         coords01 = torch.empty((m, sk.n_head, 3), dtype=torch.float32, device=device)
         bad = None
@@ -906,7 +1126,13 @@ def _locate_poses_views(frames, boxes, model_path, cameras, fi, scale_recovery, 
                                             ptr(mirror), COORDS[coords], ptr(poses_v), ptr(keypoints_v), ptr(z_v),
                                             C.c_void_p(stream)), 'metro_place_poses')
         poses, keypoints, z_offset, spread = _merge_views(poses_v, keypoints_v, z_v, places, mirror, n, nv, spread=True)
-        n_bad = int(bad.item()) if bad is not None else 0              # the call's one stream synchronisation
+        if status is None:
+            n_bad = int(bad.item()) if bad is not None else 0          # the call's one stream synchronisation
+        else:                                # the screen and the frame-index status in the call's one synchronisation
+            words = status[0].to(torch.int64) if bad is None else torch.stack([status[0].to(torch.int64), bad.reshape(())])
+            words = words.reshape(-1).tolist()
+            n_bad = words[1] if len(words) > 1 else 0
+            _raise_on_bad_frames(words[0], n, n_frames)
         if n_bad:
             raise _lib.NonFiniteError(
                 f'{spec.arch_name} stride {spec.stride} in precision {precision!r}: {n_bad} of {m} view crops reached the '
