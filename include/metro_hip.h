@@ -369,6 +369,40 @@ typedef struct MetroCropWarp {
 int  metro_warp_crops_frames_u8(const MetroFrame* frames, int32_t n_frames, const MetroCropWarp* d_crops, int32_t n,
                                 int32_t side, float* d_out, void* stream);
 
+/* metro_warp_crops_frames_u8 for frames in other pixel formats, as a decoder leaves them; the same MetroCropWarp records, modes,
+ * frame-index rule and output, and frames of different formats may share one launch.  The colour conversion happens per tap
+ * as the warp reads it; no RGB frame is written.
+ * frames: HOST array of n_frames <= METRO_MAX_FRAMES descriptors (copied into the kernel arguments):
+ *   METRO_PIX_RGB   plane[0] packed uint8 HWC RGB, stride[0] >= 3 w: the bytes of metro_warp_crops_frames_u8;
+ *   METRO_PIX_BGR   the same with the channels reversed (OpenCV's order);
+ *   METRO_PIX_NV12  plane[0] Y (stride[0] >= w), plane[1] interleaved UV at half resolution (stride[1] >= w); h, w even;
+ *   METRO_PIX_I420  plane[0] Y (stride[0] >= w), plane[1] U and plane[2] V at half resolution (stride[1] >= w / 2, one
+ *                   stride for both); h, w even.
+ * A YUV frame is the RGB image of OpenCV's integer cvtColor(COLOR_YUV2RGB_NV12 / _I420) rule (limited range, chroma of the
+ * 2x2 block replicated, no interpolation): u = U - 128, v = V - 128, y = max(0, Y - 16) CY,
+ *   R = clamp((y + 2^19 + CVR v) >> 20), G = clamp((y + 2^19 + CVG v + CUG u) >> 20), B = clamp((y + 2^19 + CUB u) >> 20)
+ * (arithmetic shifts, clamp to [0, 255]) with round(c 2^20) of the three-decimal coefficients
+ *   METRO_YUV_BT601 (OpenCV's, the default)  CY 1220542  CVR 1673527  CVG -852492  CUG -409993  CUB 2116026
+ *   METRO_YUV_BT709                          CY 1220542  CVR 1880097  CVG -558891  CUG -223347  CUB 2214593
+ * and the warp samples that image with the remap rule above; a tap outside the frame is the border value 0 in RGB (black,
+ * not YUV (0, 0, 0)).  So every crop is byte for byte metro_warp_crops_frames_u8 of the converted RGB frame.  ffmpeg's
+ * swscale conversion rounds differently and is not reproduced.  matrix is ignored for RGB and BGR.
+ * Checks: known format and matrix, the planes the format needs non-NULL, 0 < h, w <= 32767, the stride bounds above. */
+#define METRO_PIX_RGB  0
+#define METRO_PIX_BGR  1
+#define METRO_PIX_NV12 2
+#define METRO_PIX_I420 3
+#define METRO_YUV_BT601 0
+#define METRO_YUV_BT709 1
+typedef struct MetroFramePlanes {
+    const uint8_t* plane[3];    /* device pointers to row 0; RGB/BGR: [0] packed HWC; NV12: [0] Y, [1] UV; I420: [0] Y, [1] U, [2] V */
+    int32_t h, w;               /* pixels; NV12 / I420: both even */
+    int32_t stride[2];          /* bytes per row: [0] of plane 0, [1] of the chroma plane(s) */
+    int32_t format, matrix;     /* METRO_PIX_*, METRO_YUV_* */
+} MetroFramePlanes;             /* 48 bytes */
+int  metro_warp_crops_frames_planes(const MetroFramePlanes* frames, int32_t n_frames, const MetroCropWarp* d_crops,
+                                    int32_t n, int32_t side, float* d_out, void* stream);
+
 /* 3x3 stride-2 max-pool over a ZERO-padded (1,1) input (reference resnet_utils.py:177-185).
  * dtype METRO_F16 / METRO_F32 / METRO_F64; c % 8 == 0 (f16), c % 4 == 0 (f32), c % 2 == 0 (f64). */
 int  metro_maxpool3x3s2_zeropad(const void* d_in, void* d_out, int32_t n, int32_t h_in,

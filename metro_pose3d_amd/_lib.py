@@ -68,6 +68,15 @@ class MetroFrame(C.Structure):
                 ('reserved', C.c_int32)]
 
 
+METRO_PIX_RGB, METRO_PIX_BGR, METRO_PIX_NV12, METRO_PIX_I420 = 0, 1, 2, 3
+METRO_YUV_BT601, METRO_YUV_BT709 = 0, 1
+
+
+class MetroFramePlanes(C.Structure):
+    _fields_ = [('plane', C.c_void_p * 3), ('h', C.c_int32), ('w', C.c_int32), ('stride', C.c_int32 * 2),
+                ('format', C.c_int32), ('matrix', C.c_int32)]
+
+
 class MetroCropWarp(C.Structure):
     _fields_ = [('frame', C.c_int32), ('mode', C.c_int32), ('partial', C.c_double * 9), ('homography', C.c_float * 9),
                 ('intrinsics', C.c_float * 6), ('distortion', C.c_float * 5)]
@@ -143,6 +152,8 @@ SIGNATURES = {
     'metro_prep_input_f16': (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P]),
     'metro_warp_crop_u8': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
     'metro_warp_crops_frames_u8': (C.c_int, [C.POINTER(MetroFrame), C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
+    'metro_warp_crops_frames_planes': (C.c_int, [C.POINTER(MetroFramePlanes), C.c_int32, _P, C.c_int32, C.c_int32, _P,
+                                                 _P]),
     'metro_eval_metrics': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_float, _P, _P, _P, _P]),
     'metro_maxpool3x3s2_zeropad': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_int32, _P]),

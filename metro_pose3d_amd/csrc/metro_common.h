@@ -359,6 +359,10 @@ int launch_prep_input_f16(const float* images, int n, int side, void* out, hipSt
 struct FrameTable { MetroFrame f[METRO_MAX_FRAMES]; };
 int launch_warp_crops_frames_u8(const FrameTable& frames, int n_frames, const MetroCropWarp* crops, int n, int side,
                                 float* out, hipStream_t stream);
+// 64 x 48 bytes: passed by value, inside the 4 KiB of kernel arguments
+struct FramePlanesTable { MetroFramePlanes f[METRO_MAX_FRAMES]; };
+int launch_warp_crops_frames_planes(const FramePlanesTable& frames, int n_frames, const MetroCropWarp* crops, int n,
+                                    int side, float* out, hipStream_t stream);
 int launch_warp_crop_u8(const unsigned char* img, int h, int w, int row_stride, const float* homs, float* out,
                         int n, int side, hipStream_t stream);
 int launch_eval_metrics(const float* pred, const float* truth, const unsigned char* valid, int n, int nj,

@@ -1194,6 +1194,40 @@ int metro_warp_crops_frames_u8(const MetroFrame* frames, int32_t n_frames, const
     return launch_warp_crops_frames_u8(table, n_frames, d_crops, n, side, d_out, static_cast<hipStream_t>(stream));
 }
 
+int metro_warp_crops_frames_planes(const MetroFramePlanes* frames, int32_t n_frames, const MetroCropWarp* d_crops,
+                                   int32_t n, int32_t side, float* d_out, void* stream) {
+    METRO_CHECK_ARG(frames && d_crops && d_out, "warp_crops_frames_planes: NULL pointer");
+    METRO_CHECK_ARG(n_frames > 0 && n_frames <= METRO_MAX_FRAMES, "warp_crops_frames_planes: %d frames (1 to %d per launch)",
+                    n_frames, METRO_MAX_FRAMES);
+    METRO_CHECK_ARG(n > 0 && side > 0, "warp_crops_frames_planes: bad geometry (n %d side %d)", n, side);
+    metro::FramePlanesTable table = {};
+    for (int i = 0; i < n_frames; ++i) {
+        const MetroFramePlanes& f = frames[i];
+        METRO_CHECK_ARG(f.format >= METRO_PIX_RGB && f.format <= METRO_PIX_I420,
+                        "warp_crops_frames_planes: frame %d: unknown pixel format %d", i, f.format);
+        METRO_CHECK_ARG(f.matrix == METRO_YUV_BT601 || f.matrix == METRO_YUV_BT709,
+                        "warp_crops_frames_planes: frame %d: unknown colour matrix %d", i, f.matrix);
+        const bool yuv = f.format == METRO_PIX_NV12 || f.format == METRO_PIX_I420;
+        const int n_planes = f.format == METRO_PIX_I420 ? 3 : f.format == METRO_PIX_NV12 ? 2 : 1;
+        for (int k = 0; k < n_planes; ++k)
+            METRO_CHECK_ARG(f.plane[k], "warp_crops_frames_planes: frame %d: NULL plane %d", i, k);
+        METRO_CHECK_ARG(f.h > 0 && f.w > 0 && f.h <= 32767 && f.w <= 32767, "warp_crops_frames_planes: frame %d: h %d w %d "
+                        "outside [1, 32767] (cv2.remap's short coordinates)", i, f.h, f.w);
+        METRO_CHECK_ARG(!yuv || (f.h % 2 == 0 && f.w % 2 == 0),
+                        "warp_crops_frames_planes: frame %d: 4:2:0 frames need an even h and w (h %d w %d)", i, f.h, f.w);
+        const int min_stride0 = yuv ? f.w : 3 * f.w;
+        METRO_CHECK_ARG(f.stride[0] >= min_stride0, "warp_crops_frames_planes: frame %d: stride[0] %d < %d", i, f.stride[0],
+                        min_stride0);
+        if (yuv) {
+            const int min_stride1 = f.format == METRO_PIX_NV12 ? f.w : f.w / 2;
+            METRO_CHECK_ARG(f.stride[1] >= min_stride1, "warp_crops_frames_planes: frame %d: stride[1] %d < %d", i,
+                            f.stride[1], min_stride1);
+        }
+        table.f[i] = f;
+    }
+    return launch_warp_crops_frames_planes(table, n_frames, d_crops, n, side, d_out, static_cast<hipStream_t>(stream));
+}
+
 int metro_eval_metrics(const float* d_pred, const float* d_true, const uint8_t* d_valid, int32_t n, int32_t n_joints,
                        float threshold_mm, float* d_dist, float* d_dist_aligned, double* d_sums, void* stream) {
     METRO_CHECK_ARG(d_pred && d_true && d_valid && d_dist && d_dist_aligned && d_sums, "eval_metrics: NULL pointer");

@@ -70,10 +70,24 @@ __device__ __forceinline__ void homography_coords(const float* H, float fx, floa
     v = __fdiv_rn(cy, cw);
 }
 
-// cv2.remap's 8-bit INTER_LINEAR / BORDER_CONSTANT 0 sample of the uint8 HWC frame at (u, v), then normalize01, into o[0..2].
-// h, w <= 32767: a coordinate saturated to the short range (or INT_MIN >> 5 from a NaN / huge value) is outside the frame.
-__device__ __forceinline__ void sample_u8_normalized(const unsigned char* __restrict__ img, int h, int w, int row_stride,
-                                                     float u, float v, float* __restrict__ o) {
+// One tap's fetch for sample_taps_normalized: adds weight wk times the R, G, B bytes of the in-frame pixel (xx, yy) to
+// acc[0..2].  Packed uint8 HWC; BGR reverses the channels on read.
+template <bool BGR>
+struct PackedFetch {
+    const unsigned char* img;
+    int row_stride;
+    __device__ __forceinline__ void operator()(int xx, int yy, int wk, int acc[3]) const {
+        const unsigned char* s = img + (size_t)yy * row_stride + (size_t)xx * 3;
+        acc[BGR ? 2 : 0] += wk * (int)s[0]; acc[1] += wk * (int)s[1]; acc[BGR ? 0 : 2] += wk * (int)s[2];
+    }
+};
+
+// cv2.remap's 8-bit INTER_LINEAR / BORDER_CONSTANT 0 sample at (u, v) of the RGB image whose pixels `fetch` reads, then
+// normalize01, into o[0..2].  h, w <= 32767: a coordinate saturated to the short range (or INT_MIN >> 5 from a NaN / huge
+// value) is outside the frame, and fetch is called for in-frame taps only.
+template <typename Fetch>
+__device__ __forceinline__ void sample_taps_normalized(const Fetch& fetch, int h, int w, float u, float v,
+                                                       float* __restrict__ o) {
     const int sx = cv_round_x86(__fmul_rn(u, 32.f)), sy = cv_round_x86(__fmul_rn(v, 32.f));
     const int ax = sx & 31, ay = sy & 31;
     int x0 = sx >> 5, y0 = sy >> 5;
@@ -84,16 +98,19 @@ __device__ __forceinline__ void sample_u8_normalized(const unsigned char* __rest
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int xx = x0 + (k & 1), yy = y0 + (k >> 1);
-        if ((unsigned)xx < (unsigned)w && (unsigned)yy < (unsigned)h) {
-            const unsigned char* s = img + (size_t)yy * row_stride + (size_t)xx * 3;
-            acc[0] += wgt[k] * (int)s[0]; acc[1] += wgt[k] * (int)s[1]; acc[2] += wgt[k] * (int)s[2];
-        }
+        if ((unsigned)xx < (unsigned)w && (unsigned)yy < (unsigned)h) fetch(xx, yy, wgt[k], acc);
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const int byte = (acc[c] + (1 << 14)) >> 15;                  // <= 255: the weights sum to 2^15
         o[c] = fminf(fmaxf(__fdiv_rn((float)byte, 255.f), -1.f), 1.f);
     }
+}
+
+// The sample of a uint8 HWC RGB frame (row_stride bytes per row).
+__device__ __forceinline__ void sample_u8_normalized(const unsigned char* __restrict__ img, int h, int w, int row_stride,
+                                                     float u, float v, float* __restrict__ o) {
+    sample_taps_normalized(PackedFetch<false>{img, row_stride}, h, w, u, v, o);
 }
 
 __global__ __launch_bounds__(256) void warp_crop_u8_kernel(const unsigned char* __restrict__ img, int h, int w,
@@ -188,6 +205,96 @@ int launch_warp_crops_frames_u8(const FrameTable& frames, int n_frames, const Me
     hipLaunchKernelGGL(warp_crops_frames_u8_kernel, dim3(blocks), dim3(256), 0, stream, frames, n_frames, crops, out, n,
                        side);
     return launch_status("warp_crops_frames_u8");
+}
+
+// ---------------------------------------------------------------------------------------------
+// Crops from frames in several pixel formats in one launch (metro_warp_crops_frames_planes, include/metro_hip.h).  The thread
+// layout, both coordinate chains and the remap weights and rounding of warp_crops_frames_u8_kernel; only the per-tap fetch
+// differs, chosen per frame (uniform over a wave wherever the wave covers one crop).  A YUV 4:2:0 frame is the RGB image of
+// OpenCV's integer cvtColor(COLOR_YUV2RGB_NV12 / _I420) rule (its scalar yuv42xxp2RGB8 path): each in-frame tap reads its Y
+// byte and the U, V bytes of its 2x2 block and converts them; out-of-frame taps stay the RGB border 0.
+// ---------------------------------------------------------------------------------------------
+struct YuvCoeffs { int cy, cvr, cvg, cug, cub; };
+
+// round(c * 2^20) of the three-decimal limited-range coefficients (BT.601: OpenCV's own constants)
+__device__ __forceinline__ YuvCoeffs yuv_coeffs(int matrix) {
+    return matrix == METRO_YUV_BT709 ? YuvCoeffs{1220542, 1880097, -558891, -223347, 2214593}
+                                     : YuvCoeffs{1220542, 1673527, -852492, -409993, 2116026};
+}
+
+__device__ __forceinline__ int clamp_u8(int x) { return x < 0 ? 0 : (x > 255 ? 255 : x); }
+
+// NV12 (one interleaved UV plane, the pair read as one 16-bit load) and I420 (separate U and V planes): y_stride / c_stride
+// bytes per row.
+template <bool NV12>
+struct Yuv420Fetch {
+    const unsigned char* y;
+    const unsigned char* u;
+    const unsigned char* v;
+    int y_stride, c_stride;
+    YuvCoeffs m;
+    __device__ __forceinline__ void operator()(int xx, int yy, int wk, int acc[3]) const {
+        int cu, cv;
+        if (NV12) {
+            unsigned short uv;
+            __builtin_memcpy(&uv, u + (size_t)(yy >> 1) * c_stride + (size_t)((xx >> 1) * 2), 2);
+            cu = (int)(uv & 0xff) - 128;
+            cv = (int)(uv >> 8) - 128;
+        } else {
+            const size_t c = (size_t)(yy >> 1) * c_stride + (size_t)(xx >> 1);
+            cu = (int)u[c] - 128;
+            cv = (int)v[c] - 128;
+        }
+        const int ly = (int)y[(size_t)yy * y_stride + xx] - 16;
+        const int yv = (ly > 0 ? ly : 0) * m.cy + (1 << 19);       // every intermediate fits in int32
+        acc[0] += wk * clamp_u8((yv + m.cvr * cv) >> 20);
+        acc[1] += wk * clamp_u8((yv + m.cvg * cv + m.cug * cu) >> 20);
+        acc[2] += wk * clamp_u8((yv + m.cub * cu) >> 20);
+    }
+};
+
+__global__ __launch_bounds__(256) void warp_crops_frames_planes_kernel(const FramePlanesTable frames, int n_frames,
+                                                                       const MetroCropWarp* __restrict__ crops,
+                                                                       float* __restrict__ out, int n, int side) {
+    const long total = (long)n * side * side;
+    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(p % side);
+        const long t = p / side;
+        const int y = (int)(t % side);
+        const MetroCropWarp& c = crops[t / side];
+        const int fi = c.frame;
+        float* o = out + p * 3;
+        if ((unsigned)fi >= (unsigned)n_frames) {
+            o[0] = o[1] = o[2] = 0.f;
+            continue;
+        }
+        const MetroFramePlanes& f = frames.f[fi];
+        float u, v;
+        if (c.mode == METRO_WARP_DISTORTED)
+            distorted_coords(c, (float)x, (float)y, u, v);
+        else
+            homography_coords(c.homography, (float)x, (float)y, u, v);
+        if (f.format == METRO_PIX_RGB) {
+            sample_taps_normalized(PackedFetch<false>{f.plane[0], f.stride[0]}, f.h, f.w, u, v, o);
+        } else if (f.format == METRO_PIX_BGR) {
+            sample_taps_normalized(PackedFetch<true>{f.plane[0], f.stride[0]}, f.h, f.w, u, v, o);
+        } else if (f.format == METRO_PIX_NV12) {
+            const Yuv420Fetch<true> fetch{f.plane[0], f.plane[1], nullptr, f.stride[0], f.stride[1], yuv_coeffs(f.matrix)};
+            sample_taps_normalized(fetch, f.h, f.w, u, v, o);
+        } else {
+            const Yuv420Fetch<false> fetch{f.plane[0], f.plane[1], f.plane[2], f.stride[0], f.stride[1], yuv_coeffs(f.matrix)};
+            sample_taps_normalized(fetch, f.h, f.w, u, v, o);
+        }
+    }
+}
+
+int launch_warp_crops_frames_planes(const FramePlanesTable& frames, int n_frames, const MetroCropWarp* crops, int n,
+                                    int side, float* out, hipStream_t stream) {
+    const long total = (long)n * side * side;
+    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    hipLaunchKernelGGL(warp_crops_frames_planes_kernel, dim3(blocks), dim3(256), 0, stream, frames, n_frames, crops, out,
+                       n, side);
+    return launch_status("warp_crops_frames_planes");
 }
 
 // ---------------------------------------------------------------------------------------------

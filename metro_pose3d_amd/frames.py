@@ -8,6 +8,9 @@ the box centre, drops the lens distortion, squares the pixels and zooms so the b
   Camera, undistort_points, look_at_box   host geometry, the reference's camera restated in its dtypes (fp32 R, K, t)
   crop_params                             per-crop warp mode + matrices and the rotations back (data_loading.py:110-111)
   warp_frames                             one HIP launch (metro_warp_crops_frames_u8) for the crops of many frames
+  pixel_format, color_matrix              frames as decoders leave them: 'bgr' (OpenCV), 'nv12' (hardware decoders), 'i420'
+                                          (libavcodec's yuv420p), converted per tap inside the warp by
+                                          metro_warp_crops_frames_planes; 'rgb' (the default) keeps metro_warp_crops_frames_u8
   estimate_pose_in_frames                 the whole chain on one device, enqueued on the current stream
   placement_params                        per-crop virtual camera (inverse K, rotations, camera centre) and the way back to the
                                           frame's pixels (MetroPlacement records)
@@ -40,7 +43,10 @@ Divergences from the reference, on purpose:
   * the device geometry (geometry='device') inverts 3x3 matrices in closed form, not with LAPACK's pivoted solves: its records
     are within one fp32 ulp of the host's (most of them bit-identical), not always the host's bits.  The host geometry, the
     default for host boxes, costs ~0.2 ms of NumPy per box and bounds the call there (profiles/frames_probe.json); the
-    device geometry takes one ~6 us launch for 64 boxes (profiles/device_geometry_probe.json).
+    device geometry takes one ~6 us launch for 64 boxes (profiles/device_geometry_probe.json);
+  * a YUV frame ('nv12', 'i420') is the RGB image of OpenCV's integer cvtColor(COLOR_YUV2RGB_NV12 / _I420) rule (limited
+    range, BT.601 by default or BT.709, the chroma of each 2x2 block replicated; include/metro_hip.h), not of ffmpeg's
+    swscale, which rounds differently; a tap outside the frame is black (RGB 0), not YUV (0, 0, 0).
 """
 from __future__ import annotations
 
@@ -352,7 +358,154 @@ def _upload(a: np.ndarray, device: torch.device) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(device, non_blocking=True)
 
 
+# ---- frames in other pixel formats: metro_warp_crops_frames_planes converts each tap as the warp reads it ----
+
+PIXEL_FORMATS = {'rgb': _lib.METRO_PIX_RGB, 'bgr': _lib.METRO_PIX_BGR, 'nv12': _lib.METRO_PIX_NV12,
+                 'i420': _lib.METRO_PIX_I420}
+COLOR_MATRICES = {'bt601': _lib.METRO_YUV_BT601, 'bt709': _lib.METRO_YUV_BT709}
+_LAYOUTS = {
+    'rgb': 'a uint8 [H, W, 3] tensor or array',
+    'bgr': 'a uint8 [H, W, 3] tensor or array',
+    'nv12': 'a uint8 [H*3/2, W] tensor or array (Y rows, then interleaved UV rows) or a tuple (Y [H, W], UV [H/2, W/2, 2] '
+            'or [H/2, W]), H and W even, rows of element stride 1',
+    'i420': 'a contiguous uint8 [H*3/2, W] tensor or array (Y, then U and V at W/2 bytes per row) or a tuple (Y [H, W], '
+            'U [H/2, W/2], V [H/2, W/2]) whose U and V share one row stride, H and W even, rows of element stride 1',
+}
+
+
+class _Planar(NamedTuple):
+    """One frame for metro_warp_crops_frames_planes: its plane views (host or device) and the descriptor's fields."""
+    planes: Tuple[torch.Tensor, ...]
+    h: int
+    w: int
+    stride: Tuple[int, int]
+    format: int
+    matrix: int
+
+
+class _FrameSet(NamedTuple):
+    """Frames in a pixel format other than 'rgb' whose layouts are checked, as given (host or device data)."""
+    items: list
+    pixel_format: str
+    color_matrix: str
+
+
+def _frame_set(frames, pixel_format: str = 'rgb', color_matrix: str = 'bt601'):
+    """Checks pixel_format and color_matrix and, for any format but 'rgb', the layout of every frame, before any device work.
+    'rgb' frames come back as given, for the unchanged metro_warp_crops_frames_u8 path; the others as a _FrameSet.
+    A YUV frame is one tensor / array (2-D) or a tuple of its planes; a list holds many frames."""
+    if isinstance(frames, _FrameSet):
+        return frames
+    if pixel_format not in PIXEL_FORMATS:
+        raise ValueError(f"pixel_format must be 'rgb', 'bgr', 'nv12' or 'i420', got {pixel_format!r}")
+    if color_matrix not in COLOR_MATRICES:
+        raise ValueError(f"color_matrix must be 'bt601' or 'bt709', got {color_matrix!r}")
+    if pixel_format in ('rgb', 'bgr') and color_matrix != 'bt601':
+        raise ValueError(f"color_matrix={color_matrix!r} applies to 'nv12' and 'i420' frames, not to {pixel_format!r} ones")
+    if pixel_format == 'rgb':
+        return frames
+    if pixel_format == 'bgr':
+        single = isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 3
+    else:
+        single = isinstance(frames, (torch.Tensor, np.ndarray, tuple))
+    items = [frames] if single else list(frames)
+    if not items:
+        raise ValueError('no frames')
+    if len(items) > _lib.METRO_MAX_FRAMES:
+        raise ValueError(f'{len(items)} frames: at most {_lib.METRO_MAX_FRAMES} per call')
+    for k, f in enumerate(items):
+        _planar(k, f, pixel_format, color_matrix)
+    return _FrameSet(items, pixel_format, color_matrix)
+
+
+def _planar(k: int, f, pixel_format: str, color_matrix: str) -> _Planar:
+    """The plane views and descriptor fields of frame k (metadata only: no copy, no device work); ValueError on a bad layout."""
+    def bad(what):
+        return ValueError(f'frame {k}: {what}; pixel_format={pixel_format!r} takes {_LAYOUTS[pixel_format]}')
+
+    def plane(t, name, ndim):
+        t = torch.from_numpy(t) if isinstance(t, np.ndarray) else t
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != ndim:
+            raise bad(f'{name} is {getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))}')
+        if pixel_format != 'bgr' and (t.stride(-1) != 1 or (ndim >= 2 and t.stride(0) < t.shape[1] * t.stride(1))):
+            raise bad(f'{name} has strides {t.stride()}')
+        return t
+
+    def even(h, w):
+        if h % 2 or w % 2:
+            raise bad(f'{h} x {w} pixels (4:2:0 frames have an even height and width)')
+
+    fmt, matrix = PIXEL_FORMATS[pixel_format], COLOR_MATRICES[color_matrix]
+    if pixel_format == 'bgr':
+        t = plane(f, 'the frame', 3)
+        if t.shape[2] != 3:
+            raise bad(f'the frame is {tuple(t.shape)}')
+        return _Planar((t,), t.shape[0], t.shape[1], (t.stride(0), 0), fmt, matrix)
+    n_planes = 2 if pixel_format == 'nv12' else 3
+    if isinstance(f, tuple):
+        if len(f) != n_planes:
+            raise bad(f'a tuple of {len(f)} planes')
+        y = plane(f[0], 'the Y plane', 2)
+        h, w = y.shape
+        even(h, w)
+        if pixel_format == 'nv12':
+            uv = f[1]
+            uv = plane(uv, 'the UV plane', getattr(uv, 'ndim', 2))
+            if tuple(uv.shape) not in ((h // 2, w // 2, 2), (h // 2, w)) or (uv.dim() == 3 and uv.stride(1) != 2):
+                raise bad(f'the UV plane is {tuple(uv.shape)} with strides {uv.stride()} for a {h} x {w} Y plane')
+            planes = (y, uv)
+        else:
+            u, v = plane(f[1], 'the U plane', 2), plane(f[2], 'the V plane', 2)
+            if tuple(u.shape) != (h // 2, w // 2) or tuple(v.shape) != (h // 2, w // 2) or u.stride(0) != v.stride(0):
+                raise bad(f'the U and V planes are {tuple(u.shape)} and {tuple(v.shape)} with row strides {u.stride(0)} and '
+                          f'{v.stride(0)} for a {h} x {w} Y plane')
+            planes = (y, u, v)
+        if len({p.device for p in planes}) != 1:
+            raise bad(f'the planes lie on {sorted({str(p.device) for p in planes})}')
+        return _Planar(planes, h, w, (y.stride(0), planes[1].stride(0)), fmt, matrix)
+    t = plane(f, 'the frame', 2)
+    rows, w = t.shape
+    if rows % 3:
+        raise bad(f'the frame is {tuple(t.shape)}: {rows} rows are not H*3/2')
+    h = rows * 2 // 3
+    even(h, w)
+    if pixel_format == 'nv12':
+        return _Planar((t[:h], t[h:]), h, w, (t.stride(0), t.stride(0)), fmt, matrix)
+    if not t.is_contiguous():
+        raise bad(f'the frame has strides {t.stride()}')
+    flat, q = t.reshape(-1), h * w // 4
+    return _Planar((t[:h], flat[h * w:h * w + q].view(h // 2, w // 2), flat[h * w + q:].view(h // 2, w // 2)), h, w,
+                   (w, w // 2), fmt, matrix)
+
+
+def _device_frame_set(fs: _FrameSet, device: torch.device):
+    """-> [_Planar] on the device: device frames as they are (a BGR one packed if it is not), host frames uploaded (pinned,
+    non-blocking) at their own byte size."""
+    def to_device(k, a):
+        if isinstance(a, tuple):
+            return tuple(to_device(k, p) for p in a)
+        t = torch.from_numpy(a) if isinstance(a, np.ndarray) else a
+        if not t.is_cuda:
+            return _upload(t.numpy(), device)
+        if t.device != device:
+            raise ValueError(f'frame {k} is on {t.device}, the call runs on {device}')
+        if fs.pixel_format == 'bgr' and (t.stride(2) != 1 or t.stride(1) != 3 or t.stride(0) < 3 * t.shape[1]):
+            t = t.contiguous()
+        return t
+    return [_planar(k, to_device(k, f), fs.pixel_format, fs.color_matrix) for k, f in enumerate(fs.items)]
+
+
+def _first_frame(frames):
+    """The first frame (or plane) of `frames`, from which a call without device boxes takes its device."""
+    f = frames.items if isinstance(frames, _FrameSet) else frames
+    while isinstance(f, (list, tuple)) and f:
+        f = f[0]
+    return f if isinstance(f, (torch.Tensor, np.ndarray)) else None
+
+
 def _device_frames(frames, device: torch.device):
+    if isinstance(frames, _FrameSet):
+        return _device_frame_set(frames, device)
     if isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 3:
         frames = [frames]
     out = []
@@ -377,11 +530,22 @@ def _device_frames(frames, device: torch.device):
 
 
 def warp_frames(frames, params: CropParams, frame_index, side: int = 256, device: Optional[torch.device] = None,
-                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                out: Optional[torch.Tensor] = None, pixel_format: str = 'rgb', color_matrix: str = 'bt601') -> torch.Tensor:
     """uint8 [H, W, 3] frames (a tensor or a list; host or device; sizes may differ) + per-crop parameters -> fp32 NHWC
-    [n, side, side, 3] crops in [0, 1] on the device, in ONE launch on the current stream."""
+    [n, side, side, 3] crops in [0, 1] on the device, in ONE launch on the current stream.
+    pixel_format 'rgb' (metro_warp_crops_frames_u8), or 'bgr', 'nv12', 'i420' (metro_warp_crops_frames_planes: the bytes of
+    'rgb' on the converted frame); color_matrix 'bt601' or 'bt709' for the YUV formats.  Frame layouts:
+      'rgb', 'bgr'  uint8 [H, W, 3];
+      'nv12'        uint8 [H*3/2, W] (Y rows then UV rows, as `ffmpeg -pix_fmt nv12 -f rawvideo` writes them; the row stride
+                    is the tensor's), or a tuple (Y [H, W], UV [H/2, W/2, 2] or [H/2, W]), e.g. views into a pitched decoder
+                    surface whose UV plane starts at an aligned offset;
+      'i420'        contiguous uint8 [H*3/2, W] (Y, then U and V at W/2 bytes per row from offsets H W and H W 5/4), or a tuple
+                    (Y [H, W], U [H/2, W/2], V [H/2, W/2]).
+    A YUV frame is one tensor / array (2-D) or a tuple of planes; a list holds many frames.  H and W are even; rows have element
+    stride 1; anything else raises ValueError naming the frame and the layout."""
+    frames = _frame_set(frames, pixel_format, color_matrix)
     if device is None:
-        first = frames if isinstance(frames, torch.Tensor) else frames[0] if isinstance(frames, (list, tuple)) and frames else None
+        first = _first_frame(frames)
         device = first.device if isinstance(first, torch.Tensor) and first.is_cuda else torch.device('cuda', torch.cuda.current_device())
     dev_frames = _device_frames(frames, device)
     n = len(params.mode)
@@ -397,11 +561,24 @@ def warp_frames(frames, params: CropParams, frame_index, side: int = 256, device
 
 
 def _launch_warp(dev_frames, crops: torch.Tensor, n: int, side: int, out: torch.Tensor, device: torch.device) -> None:
-    """One metro_warp_crops_frames_u8 launch on the current stream: n MetroCropWarp records already on the device."""
+    """One metro_warp_crops_frames_u8 launch ('rgb' frames: tensors) or one metro_warp_crops_frames_planes launch (_Planar
+    frames) on the current stream: n MetroCropWarp records already on the device."""
+    stream = torch.cuda.current_stream(device).cuda_stream
+    if dev_frames and isinstance(dev_frames[0], _Planar):
+        ptable = (_lib.MetroFramePlanes * len(dev_frames))()
+        for k, f in enumerate(dev_frames):
+            r = ptable[k]
+            for i, p in enumerate(f.planes):
+                r.plane[i] = p.data_ptr()
+            r.h, r.w, r.format, r.matrix = f.h, f.w, f.format, f.matrix
+            r.stride[0], r.stride[1] = f.stride
+        check(_lib.load().metro_warp_crops_frames_planes(ptable, len(dev_frames), C.c_void_p(crops.data_ptr()), n, side,
+                                                         C.c_void_p(out.data_ptr()), C.c_void_p(stream)),
+              'metro_warp_crops_frames_planes')
+        return
     table = (_lib.MetroFrame * len(dev_frames))()
     for k, f in enumerate(dev_frames):
         table[k].data, table[k].h, table[k].w, table[k].row_stride = f.data_ptr(), f.shape[0], f.shape[1], f.stride(0)
-    stream = torch.cuda.current_stream(device).cuda_stream
     check(_lib.load().metro_warp_crops_frames_u8(table, len(dev_frames), C.c_void_p(crops.data_ptr()), n, side,
                                                  C.c_void_p(out.data_ptr()), C.c_void_p(stream)), 'metro_warp_crops_frames_u8')
 
@@ -772,10 +949,11 @@ _ROT_TO_WORLD = _lib.MetroPlacement.rot_to_world.offset // 4
 
 def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index=None, coords: str = 'camera',
                             precision: Optional[str] = None, check_finite: Optional[bool] = None, views=None,
-                            geometry: str = 'auto'):
+                            geometry: str = 'auto', pixel_format: str = 'rgb', color_matrix: str = 'bt601'):
     """uint8 frames + person boxes [n, 4] (x, y, w, h) -> (poses [n, Jout, 3] mm, joint_edges, joint_names) like estimate_pose.
 
-    frames: a uint8 [H, W, 3] tensor / array or a list of them (host or device, sizes may differ, at most 64);
+    frames: a uint8 [H, W, 3] tensor / array or a list of them (host or device, sizes may differ, at most 64), or frames in
+    `pixel_format` (below);
     frame_index [n]: the frame of each box (default: every box on frame 0); cameras: None (axis-aligned square crops, what
     preprocess.box_homography gives), one Camera for all frames, or one Camera per frame.
     The poses are root-relative, in `coords`:
@@ -799,8 +977,14 @@ def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index
     identity view when views=None: no per-box host work and no synchronisation before the forward; the records agree with the
     host's to a few fp32 ulp (include/metro_hip.h).  'auto' (default): 'device' for CUDA boxes, else 'host'.  With device
     boxes the call runs on the boxes' device; a device frame index outside [0, n_frames) raises ValueError (read from the
-    kernel's status after the call's synchronisation)."""
+    kernel's status after the call's synchronisation).
+    pixel_format: 'rgb' (default), 'bgr', 'nv12' or 'i420', with color_matrix 'bt601' (default) or 'bt709' for the YUV
+    formats; the layouts are warp_frames'.  Frames other than 'rgb' go through metro_warp_crops_frames_planes, which
+    converts each tap as the warp reads it: the crops are byte for byte those of the RGB frame that OpenCV's integer
+    cvtColor(COLOR_YUV2RGB_NV12 / _I420) rule gives (not ffmpeg's swscale, which rounds differently), with a black border;
+    no RGB frame is written, and host frames upload at their own size (1.5 bytes per pixel for YUV)."""
     from metro_pose3d_amd.inference import _engine_for, _resolve_device, estimate_pose
+    frames = _frame_set(frames, pixel_format, color_matrix)
     geo = _geometry_of(geometry, boxes)
     if coords not in ('crop', 'camera', 'world'):
         raise ValueError(f"coords must be 'crop', 'camera' or 'world', got {coords!r}")
@@ -809,7 +993,7 @@ def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index
         raise ValueError(f"coords='crop' takes one view: the {len(vs.zoom)} views have different virtual cameras")
     if precision is None:
         precision = os.environ.get('METRO_PRECISION', 'f16')
-    first = frames if isinstance(frames, torch.Tensor) else frames[0] if isinstance(frames, (list, tuple)) and frames else None
+    first = _first_frame(frames)
     if geo == 'device':
         device = _geometry_device(boxes, first)
         db = _device_boxes(boxes, frame_index, device)
@@ -963,7 +1147,7 @@ def _placement_targets(scale_recovery, cameras, n, n_edges, bone_lengths, root_d
 def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=None, scale_recovery: str = 'bone-lengths',
                            bone_lengths=None, root_depth=None, coords: str = 'camera', precision: Optional[str] = None,
                            check_finite: Optional[bool] = None, views=None, return_spread: bool = False,
-                           geometry: str = 'auto'):
+                           geometry: str = 'auto', pixel_format: str = 'rgb', color_matrix: str = 'bt601'):
     """uint8 frames + person boxes -> FramePoses(poses, keypoints2d, z_offset, joint_edges, joint_names): where each person is
     in 3D and where each joint lands in its frame's pixels.  frames, boxes, frame_index, cameras, precision and check_finite as
     for estimate_pose_in_frames.
@@ -991,8 +1175,11 @@ def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=
     views from their mean (zeros with one view), a cheap agreement score.
     geometry: 'host', 'device' or 'auto' as for estimate_pose_in_frames (device boxes: metro_look_at_boxes, then the views
     chain with the identity view when views=None; bone_lengths and root_depth stay host data); a device frame index outside
-    [0, n_frames) raises ValueError, read together with the finite screen in the call's one synchronisation."""
+    [0, n_frames) raises ValueError, read together with the finite screen in the call's one synchronisation.
+    pixel_format, color_matrix: as for estimate_pose_in_frames ('bgr', 'nv12', 'i420' frames converted per tap in the warp,
+    OpenCV's integer YUV rule, black border)."""
     from metro_pose3d_amd.inference import _engine_for, _resolve_device
+    frames = _frame_set(frames, pixel_format, color_matrix)
     geo = _geometry_of(geometry, boxes)
     if coords not in COORDS:
         raise ValueError(f"coords must be 'crop', 'camera' or 'world', got {coords!r}")
@@ -1003,7 +1190,7 @@ def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=
         precision = os.environ.get('METRO_PRECISION', 'f16')
     if check_finite is None:
         check_finite = os.environ.get('METRO_CHECK_FINITE', '1') != '0'
-    first = frames if isinstance(frames, torch.Tensor) else frames[0] if isinstance(frames, (list, tuple)) and frames else None
+    first = _first_frame(frames)
     if geo == 'device':
         device = _geometry_device(boxes, first)
         db = _device_boxes(boxes, frame_index, device)

@@ -234,7 +234,8 @@ def main(argv=None):
     parser.add_argument('--precision', type=str, default=None, choices=['f16', 'f32', 'f32m', 'f64'])
     parser.add_argument('--plot', type=str, default=None, help='write the stick-figure plot to this file')
     parser.add_argument('--frame', type=str, default=None,
-                        help='.npy file with a uint8 [H,W,3] RGB frame: poses of the --box persons in it (frames.py)')
+                        help='.npy file with a uint8 [H,W,3] RGB frame (or --pixel-format): poses of the --box persons in it '
+                             '(frames.py)')
     parser.add_argument('--box', type=str, action='append', default=[], help='x,y,w,h of a person box in --frame (repeatable)')
     parser.add_argument('--intrinsics', type=str, default=None, help='fx,fy,cx,cy of the --frame camera')
     parser.add_argument('--distortion', type=str, default=None, help='k1,k2,p1,p2,k3 of the --frame camera (needs --intrinsics)')
@@ -247,11 +248,18 @@ def main(argv=None):
     parser.add_argument('--views', type=int, default=None,
                         help='N: test-time augmentation, N rolled / flipped views per --box averaged (the default view set of '
                              'frames.view_set: rolls -20..+20 degrees, flips on odd views; 1 to 32)')
+    parser.add_argument('--pixel-format', type=str, default=None, choices=['rgb', 'bgr', 'nv12', 'i420'],
+                        help='layout of --frame: rgb / bgr uint8 [H,W,3] (default rgb), nv12 / i420 uint8 [H*3/2,W] (Y rows, '
+                             'then the chroma rows as ffmpeg -f rawvideo writes them); converted per tap in the warp')
+    parser.add_argument('--color-matrix', type=str, default=None, choices=['bt601', 'bt709'],
+                        help='YUV matrix of an nv12 / i420 --frame (limited range; default bt601, OpenCV\'s)')
     opts = parser.parse_args(argv)
     if opts.frame:
         return _main_frame(opts)
     if opts.box or opts.intrinsics or opts.distortion or opts.bone_lengths or opts.root_depth or opts.views is not None:
         parser.error('--box, --intrinsics, --distortion, --bone-lengths, --root-depth and --views go with --frame')
+    if opts.pixel_format or opts.color_matrix:
+        parser.error('--pixel-format and --color-matrix go with --frame')
     if opts.image:
         img = np.load(opts.image).astype(np.float32)
     else:
@@ -286,11 +294,12 @@ def _main_frame(opts):
         camera = Camera(np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]]), dist)
     elif opts.distortion:
         raise SystemExit('--distortion needs --intrinsics')
+    fmt = dict(pixel_format=opts.pixel_format or 'rgb', color_matrix=opts.color_matrix or 'bt601')
     if opts.bone_lengths or opts.root_depth:
-        return _main_locate(opts, frame, boxes, camera)
+        return _main_locate(opts, frame, boxes, camera, fmt)
     try:
         poses, edges, names = estimate_pose_in_frames(frame, boxes, opts.model_path, cameras=camera, precision=opts.precision,
-                                                      views=opts.views)
+                                                      views=opts.views, **fmt)
     except ValueError as e:
         raise SystemExit(str(e))
     for k, pose in enumerate(poses.cpu().numpy()):
@@ -299,7 +308,7 @@ def _main_frame(opts):
             print(f'{name.decode():>10s}  {p[0]:9.2f} {p[1]:9.2f} {p[2]:9.2f}')
 
 
-def _main_locate(opts, frame, boxes, camera):
+def _main_locate(opts, frame, boxes, camera, fmt):
     from metro_pose3d_amd.frames import locate_poses_in_frames
     if opts.bone_lengths and opts.root_depth:
         raise SystemExit('--bone-lengths and --root-depth are two scale recoveries: pick one')
@@ -311,7 +320,7 @@ def _main_locate(opts, frame, boxes, camera):
         kw = dict(scale_recovery='true-root-depth', root_depth=_floats(opts.root_depth, len(boxes), '--root-depth'))
     try:
         res = locate_poses_in_frames(frame, boxes, opts.model_path, cameras=camera, precision=opts.precision, views=opts.views,
-                                     **kw)
+                                     **kw, **fmt)
     except ValueError as e:
         raise SystemExit(str(e))
     poses, kp, z = res.poses.cpu().numpy(), res.keypoints2d.cpu().numpy(), res.z_offset.cpu().numpy()
