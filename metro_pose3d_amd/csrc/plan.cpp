@@ -818,6 +818,9 @@ int metro_plan_create(const MetroSpec* spec, int32_t max_batch, MetroPlan** out_
     METRO_CHECK_ARG(spec->stride == 4 || spec->stride == 8 || spec->stride == 16 || spec->stride == 32,
                     "unsupported stride %d (4|8|16|32)", spec->stride);
     METRO_CHECK_ARG(spec->proc_side > 0 && spec->proc_side % 32 == 0, "proc_side %d must be a positive multiple of 32", spec->proc_side);
+    // the soft-argmax places pixel i at i / (side - 1): a 1 x 1 heat map has no coordinate
+    METRO_CHECK_ARG(spec->proc_side / spec->stride >= 2, "heat-map side %d (proc_side %d / stride %d) must be >= 2",
+                    spec->proc_side / spec->stride, spec->proc_side, spec->stride);
     METRO_CHECK_ARG(spec->depth >= 2 && spec->depth <= 64, "depth %d out of range", spec->depth);
     METRO_CHECK_ARG(spec->n_joints_head >= 1 && spec->n_joints_head <= METRO_MAX_JOINTS, "n_joints_head %d out of range", spec->n_joints_head);
     METRO_CHECK_ARG(spec->n_joints_out >= 1 && spec->n_joints_out <= METRO_MAX_JOINTS, "n_joints_out %d out of range", spec->n_joints_out);

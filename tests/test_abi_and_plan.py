@@ -174,6 +174,18 @@ def test_plan_rejects_bad_specs(lib):
         assert lib.metro_plan_create(C.byref(cs), 4, C.byref(plan)) == -1
         assert needle in lib.metro_last_error()
     assert lib.metro_plan_create(C.byref(good), 0, C.byref(plan)) == -1
+    # proc_side 32 at stride 32 is a 1 x 1 heat map: the soft-argmax step 1 / (side - 1) would be infinite
+    for prec in (_lib.METRO_PREC_F16, _lib.METRO_PREC_F64):
+        one = ModelSpec(50, 32, 'h36m', proc_side=32).to_c(prec)
+        assert lib.metro_plan_create(C.byref(one), 1, C.byref(plan)) == -1
+        assert b'heat-map side 1' in lib.metro_last_error(), lib.metro_last_error()
+    with pytest.raises(ValueError, match='heat-map side 1'):
+        Engine(ModelSpec(50, 32, 'h36m', proc_side=32), None, 'f16', max_batch=1)
+    # the smallest heat map the soft-argmax takes (2 x 2) still plans
+    for stride, side in ((32, 64), (16, 32)):
+        ok = ModelSpec(50, stride, 'h36m', proc_side=side).to_c(_lib.METRO_PREC_F16)
+        assert lib.metro_plan_create(C.byref(ok), 1, C.byref(plan)) == 0, lib.metro_last_error()
+        lib.metro_plan_destroy(plan)
     # the one-launch head entry validates the head width itself (its bias comes in 16-byte pieces): no launch, no GPU needed
     odd = ModelSpec(50, 16, 'h36m', depth=2).to_c(_lib.METRO_PREC_F16)              # 2 x 17 = 34 channels
     p = C.c_void_p(256)

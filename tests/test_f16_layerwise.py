@@ -53,8 +53,17 @@ CASES = [(ModelSpec(50, 32, 'h36m'), 2), (ModelSpec(50, 16, 'h36m'), 3), (ModelS
          (ModelSpec(50, 16, 'h36m'), 1, {'res_gain': 1.0}),
          # the dispatch of calls with >= 128 crops (512-pixel 3x3 tiles, more layers on the 256 x 256 GEMM, from 256 crops the
          # 256-pixel head): every launch at its REAL batch, the oracle on the first and the last crop of the call
-         (ModelSpec(50, 16, 'h36m'), 2, {'batch': 130}), (ModelSpec(50, 16, 'h36m'), 2, {'batch': 256})]
-_id = lambda c: (f'rn{c[0].arch}-s{c[0].stride}-{c[0].dataset}-n{c[1]}' + ('' if c[0].centered_stride else '-nc') +
+         (ModelSpec(50, 16, 'h36m'), 2, {'batch': 130}), (ModelSpec(50, 16, 'h36m'), 2, {'batch': 256}),
+         # crop sides other than 256 (the model file's proc_side): 56/28/14/7-wide maps and a 7 x 7 head on the fp32-output GEMM +
+         # two-launch soft-argmax (224); an 18 x 18 head of 424 channels (288); 96/48/24-wide maps (384); RN101-s8 on 80/40-wide
+         # maps (320); block1 on 128-wide maps and a 16 x 16 head (512)
+         (ModelSpec(50, 32, 'h36m', proc_side=224), 2), (ModelSpec(50, 16, 'merged', proc_side=288), 1),
+         (ModelSpec(50, 16, 'h36m', proc_side=384), 1), (ModelSpec(101, 8, 'many19', proc_side=320), 1),
+         (ModelSpec(50, 32, 'h36m', proc_side=512), 1),
+         # the 256-pixel head tiles on an 80 x 80 heat map (stride 4 at 320): the real batch 16, the oracle on its first and last crop
+         (ModelSpec(50, 4, 'h36m', proc_side=320), 2, {'batch': 16})]
+_id = lambda c: (f'rn{c[0].arch}-s{c[0].stride}-{c[0].dataset}-n{c[1]}' + ('' if c[0].proc_side == 256 else f'-side{c[0].proc_side}') +
+                 ('' if c[0].centered_stride else '-nc') +
                  ('-undamped' if len(c) > 2 and 'res_gain' in c[2] else '') + (f'-of-batch{c[2]["batch"]}' if len(c) > 2 and 'batch' in c[2] else ''))
 
 

@@ -503,9 +503,25 @@ def test_maxpool_zeropad(lib, cuda, dtype):
 
 SA_SPECS = [ModelSpec(50, 32, 'h36m'), ModelSpec(50, 16, 'h36m'), ModelSpec(50, 16, 'many19'),
             ModelSpec(101, 8, 'merged'), ModelSpec(50, 4, 'h36m')]
+# ragged heat maps of crop sides other than 256: pixel counts that are not whole 32- or 64-pixel slabs.  Pixel lanes per
+# partials block = 256 threads / (channels / 4): 7 for the 136-channel head (= the width of a 7 x 7 map), 6 for 152, 2 for the
+# 424-channel one, 15 for the depth-4 head of 68 channels
+SA_RAGGED = [ModelSpec(50, 32, 'h36m', proc_side=224), ModelSpec(50, 32, 'merged', proc_side=288),
+             ModelSpec(50, 32, 'many19', proc_side=320), ModelSpec(50, 16, 'merged', proc_side=288),
+             ModelSpec(50, 16, 'h36m', depth=4, proc_side=352)]
+_sa_id = lambda s: f'rn{s.arch}-s{s.stride}-{s.dataset}' + ('' if s.depth == 8 else f'-D{s.depth}') + \
+    ('' if s.proc_side == 256 else f'-side{s.proc_side}')
 
 
-@pytest.mark.parametrize('spec', SA_SPECS, ids=lambda s: f'rn{s.arch}-s{s.stride}-{s.dataset}')
+def sa_slabs(side):
+    """The partials launch's slab split (pool_softargmax.hip softargmax_slabs): pixels // 32 slabs, 1..64; slab k covers
+    pixels [pixels * k // slabs, pixels * (k + 1) // slabs)."""
+    pixels = side * side
+    slabs = min(64, max(1, pixels // 32))
+    return [(pixels * k // slabs, pixels * (k + 1) // slabs) for k in range(slabs)]
+
+
+@pytest.mark.parametrize('spec', SA_SPECS + SA_RAGGED, ids=_sa_id)
 @pytest.mark.parametrize('precise', [0, 1, 2])
 def test_softargmax_random(lib, cuda, spec, precise):
     from oracle.forward import logits_to_output
@@ -543,6 +559,35 @@ def test_softargmax_known_answers(lib, cuda):
         shifted = H.run_softargmax(lib, cuda, spec, logits + 7.5, precise)
         assert np.abs(shifted - got).max() < 1e-3
     assert (got[:, 0, :] == 0).all()                        # h36m: output row 0 is the root (KA10)
+
+
+@pytest.mark.parametrize('spec', SA_RAGGED, ids=_sa_id)
+def test_softargmax_ragged_known_answers(lib, cuda, spec):
+    """One-hot peaks (60 over a -50 floor) on the first and the last pixel of every slab, along the last row and in the four
+    corners: each joint's coordinate is exactly its peak's voxel (i / (side - 1) in fp32), in every precision.  A pixel a slab
+    drops, reads twice, or places in the wrong row moves the joint to the centre of the map or off by a row."""
+    from metro_pose3d_amd import heads as MH
+    from oracle.forward import coords01_to_output
+    s, dd, j = spec.heatmap_side, spec.depth, spec.skeleton.n_head
+    spots = {0, s - 1, s * (s - 1), s * s - 1} | {p for a, b in sa_slabs(s) for p in (a, b - 1)} | set(range(s * (s - 1), s * s))
+    spots = sorted(spots)
+    n = -(-len(spots) // j)                                  # every spot is some (image, joint)'s peak
+    rng = np.random.default_rng(s * 1000 + j)
+    logits = np.full((n, s, s, dd * j), -50.0, np.float32)
+    want = np.zeros((n, j, 3), np.float64)
+    step, step_d = np.float32(1) / np.float32(s - 1), np.float32(1) / np.float32(dd - 1)
+    for k in range(n * j):
+        i, jj = divmod(k, j)
+        p = spots[k] if k < len(spots) else int(rng.integers(0, s * s))
+        h, w, d = p // s, p % s, int(rng.integers(0, dd))
+        logits[i, h, w, d * j + jj] = 60.0                   # channel d * J + j (volumetric.py:231)
+        want[i, jj] = (np.float32(w) * step, np.float32(h) * step, np.float32(d) * step_d)
+    exp_poses = coords01_to_output(H.oracle_spec(spec), torch.from_numpy(want)).numpy()
+    for precise in (0, 1, 2):
+        c01 = MH.coords01_from_logits(torch.from_numpy(logits).to(cuda), spec, precise=precise).cpu().numpy()
+        assert np.abs(c01 - want).max() <= 1e-6, (precise, np.abs(c01 - want).max())
+        got = H.run_softargmax(lib, cuda, spec, logits, precise)
+        assert np.abs(got - exp_poses).max() <= 1e-3, (precise, np.abs(got - exp_poses).max())
 
 
 def test_softargmax_online_rescale_branch(lib, cuda):

@@ -119,9 +119,9 @@ def test_keypoints_behind_the_camera_are_nan(cuda):
     assert np.isnan(kp[19]).all() and np.isnan(kp[0]).all() and np.isfinite(kp[1:19]).all()
 
 
-def _toy_engine_model(tmp_path):
+def _toy_engine_model(tmp_path, proc_side=256):
     from metro_pose3d_amd import save_model, synth
-    spec = ModelSpec(50, 32, 'h36m', base_width=8)
+    spec = ModelSpec(50, 32, 'h36m', base_width=8, proc_side=proc_side)
     params = synth.make_params(50, spec.n_head_channels, 8, seed=1, logit_gain=0.84)
     path = str(tmp_path / 'toy.npz')
     save_model(path, spec, params)
@@ -180,12 +180,14 @@ def test_forward_coords01_matches_forward(cuda, tmp_path, precision):
     eng.close()
 
 
-def test_locate_poses_in_frames_f64_matches_the_oracle(cuda, tmp_path):
+@pytest.mark.parametrize('proc_side', [256, 384])
+def test_locate_poses_in_frames_f64_matches_the_oracle(cuda, tmp_path, proc_side):
+    """The model file's crop side reaches the crop, the forward and the placement: the oracle warps, runs and places at it."""
     from metro_pose3d_amd.frames import crop_params, estimate_pose_in_frames, locate_poses_in_frames, placement_params
     from oracle import forward as OF
     from tests import helpers as H
     from tests.test_gpu_frames import _cameras, _frame, _oracle_crops
-    spec, params, path = _toy_engine_model(tmp_path)
+    spec, params, path = _toy_engine_model(tmp_path, proc_side)
     d, cams = _cameras()
     cams[2].distortion_coeffs = None                                   # one undistorted camera: the homography keypoints
     frames = [_frame(*d[f'cam{i}_frame_hw'], seed=50 + i) for i in range(3)]
@@ -195,10 +197,10 @@ def test_locate_poses_in_frames_f64_matches_the_oracle(cuda, tmp_path):
     rng = np.random.default_rng(11)
     bones = rng.uniform(200, 450, len(spec.skeleton.head_edges))
     root = rng.uniform(3000, 5000, n)
-    p = crop_params(cams, boxes, fi, 256)
-    q = placement_params(cams, boxes, fi, 256)
+    p = crop_params(cams, boxes, fi, proc_side)
+    q = placement_params(cams, boxes, fi, proc_side)
     collect = {}
-    OF.forward(H.oracle_spec(spec), params, _oracle_crops(frames, p, fi, 256), torch.float64, collect=collect)
+    OF.forward(H.oracle_spec(spec), params, _oracle_crops(frames, p, fi, proc_side), torch.float64, collect=collect)
     c01 = collect['coords01'].numpy().astype(np.float32)
     perm, mirror = spec.skeleton.permutation, spec.skeleton.out_mirror
     for scale, kw in (('bone-lengths', dict(bone_lengths=bones)), ('true-root-depth', dict(root_depth=root))):
@@ -206,7 +208,7 @@ def test_locate_poses_in_frames_f64_matches_the_oracle(cuda, tmp_path):
             got = locate_poses_in_frames(frames, boxes, path, cameras=cams, frame_index=fi, scale_recovery=scale,
                                          coords=coords, precision='f64', **kw)
             ref, kp, z = OPL.place(c01, q, spec.stride, scale, coords, perm, mirror, edges=spec.skeleton.head_edges,
-                                   bone_lengths=bones, root_depth=root)
+                                   bone_lengths=bones, root_depth=root, proc_side=proc_side)
             assert got.poses.shape == (n, 17, 3) and got.keypoints2d.shape == (n, 17, 2) and got.z_offset.shape == (n,)
             assert np.abs(got.poses.cpu().numpy() - ref).max() <= 1e-2, (scale, coords)
             assert np.abs(got.keypoints2d.cpu().numpy() - kp).max() <= 1e-3, (scale, coords)

@@ -93,8 +93,9 @@ def test_skeleton_tables_agree_with_oracle():
 
 # ---------------------------------------------------------------------------------------------- GPU
 @pytest.mark.gpu
-@pytest.mark.parametrize('spec', [ModelSpec(50, 16, 'h36m'), ModelSpec(50, 8, 'many19'), ModelSpec(50, 32, 'h36m', centered_stride=False)],
-                         ids=['h36m-s16', 'many19-s8', 'h36m-s32-nc'])
+@pytest.mark.parametrize('spec', [ModelSpec(50, 16, 'h36m'), ModelSpec(50, 8, 'many19'), ModelSpec(50, 32, 'h36m', centered_stride=False),
+                                  ModelSpec(50, 16, 'h36m', proc_side=384), ModelSpec(50, 32, 'many19', proc_side=224, centered_stride=False)],
+                         ids=['h36m-s16', 'many19-s8', 'h36m-s32-nc', 'h36m-s16-side384', 'many19-s32-nc-side224'])
 def test_gpu_bone_length_head(cuda, spec):
     import torch
     from metro_pose3d_amd import heads as MH
@@ -133,6 +134,30 @@ def test_gpu_coords01_and_to_orig_cam(cuda):
     assert np.abs(got - ref).max() <= 1e-6
     c01 = rng.uniform(0, 1, (7, 17, 3)).astype(np.float32)
     assert np.array_equal(MH.heatmap_to_25d(torch.from_numpy(c01).to(cuda), spec).cpu().numpy(), OH.heatmap_to_25d(c01, spec.stride))
+    # the last image pixel (and so the scale of a heat-map coordinate) follows the model's crop side
+    for sp in (ModelSpec(50, 16, 'h36m', proc_side=384), ModelSpec(50, 32, 'h36m', proc_side=224, centered_stride=False),
+               ModelSpec(50, 8, 'h36m', proc_side=320)):
+        got25 = MH.heatmap_to_25d(torch.from_numpy(c01).to(cuda), sp).cpu().numpy()
+        assert np.array_equal(got25, OH.heatmap_to_25d(c01, sp.stride, sp.proc_side, sp.centered_stride)), sp
+        assert not np.array_equal(got25, OH.heatmap_to_25d(c01, sp.stride, 256, sp.centered_stride))
+    # an 18 x 18 heat map (crop side 288): 324 pixels, not whole 32-pixel slabs
+    sp = ModelSpec(50, 16, 'h36m', proc_side=288)
+    lg = (rng.standard_normal((3, 18, 18, sp.n_head_channels)) * 4).astype(np.float32)
+    got = MH.coords01_from_logits(torch.from_numpy(lg).to(cuda), sp, precise=1).cpu().numpy()
+    ref = soft_argmax01(torch.from_numpy(lg).permute(0, 3, 1, 2).double(), sp.skeleton.n_head, sp.depth)[1].numpy()
+    assert np.abs(got - ref).max() <= 1e-6
+    # the last image pixel (and so the scale of a heat-map coordinate) follows the model's crop side
+    for sp in (ModelSpec(50, 16, 'h36m', proc_side=384), ModelSpec(50, 32, 'h36m', proc_side=224, centered_stride=False),
+               ModelSpec(50, 8, 'h36m', proc_side=320)):
+        got25 = MH.heatmap_to_25d(torch.from_numpy(c01).to(cuda), sp).cpu().numpy()
+        assert np.array_equal(got25, OH.heatmap_to_25d(c01, sp.stride, sp.proc_side, sp.centered_stride)), sp
+        assert not np.array_equal(got25, OH.heatmap_to_25d(c01, sp.stride, 256, sp.centered_stride))
+    # an 18 x 18 heat map (crop side 288): 324 pixels, not whole 32-pixel slabs
+    sp = ModelSpec(50, 16, 'h36m', proc_side=288)
+    lg = (rng.standard_normal((3, 18, 18, sp.n_head_channels)) * 4).astype(np.float32)
+    got = MH.coords01_from_logits(torch.from_numpy(lg).to(cuda), sp, precise=1).cpu().numpy()
+    ref = soft_argmax01(torch.from_numpy(lg).permute(0, 3, 1, 2).double(), sp.skeleton.n_head, sp.depth)[1].numpy()
+    assert np.abs(got - ref).max() <= 1e-6
     ji = head_joint_info('h36m')
     x = rng.normal(0, 500, (6, 17, 3)).astype(np.float32)
     q, _ = np.linalg.qr(rng.normal(size=(6, 3, 3)))

@@ -44,8 +44,36 @@ CONFIGS = {
     # in three joint groups on the ring head (round 5), 64- and 128-pixel tiles
     'X-rn50-s16-merged53-b64': (ModelSpec(50, 16, 'merged'), 64),
     'X-rn101-s8-merged53-b32': (ModelSpec(101, 8, 'merged'), 32),
+    # estimate_pose's batch-256 bucket at stride 32: block3/unit_6/conv3 on the 128 x 256 ring tiles with a residual
+    'X-rn50-s32-J17-b256': (ModelSpec(50, 32, 'h36m'), 256),
+    # ---- crop sides other than 256 (the model file's proc_side): maps that are not powers of two, heads that are not whole tiles
+    # 224: 56/28/14/7-wide maps; the 7 x 7 head is not whole 64-pixel tiles -> the f32out GEMM and the two-launch soft-argmax
+    'X-rn50-s32-J17-side224-b64': (ModelSpec(50, 32, 'h36m', proc_side=224), 64),
+    # 288: an 18 x 18 heat map of the 424-channel head (2 pixel lanes per soft-argmax block)
+    'X-rn50-s16-merged53-side288-b64': (ModelSpec(50, 16, 'merged', proc_side=288), 64),
+    # 384: 96/48/24-wide maps, the one-launch head on a 24 x 24 heat map (32-pixel slabs cross image rows)
+    'X-rn50-s16-J17-side384-b64': (ModelSpec(50, 16, 'h36m', proc_side=384), 64),
+    # 320: 80/40-wide maps; the 256-pixel head on an 80 x 80 heat map, and RN101-s8's 40 x 40 head
+    'X-rn101-s8-J19-side320-b32': (ModelSpec(101, 8, 'many19', proc_side=320), 32),
+    'X-rn50-s4-J17-side320-b16': (ModelSpec(50, 4, 'h36m', proc_side=320), 16),
+    # 512: block1 on 128-wide maps (the 512-row slab of the tap-reuse 3x3), and at stride 4 its sub-grid form on a 128 x 128 head
+    'X-rn50-s32-J17-side512-b1': (ModelSpec(50, 32, 'h36m', proc_side=512), 1),
+    'X-rn50-s4-J17-side512-b1': (ModelSpec(50, 4, 'h36m', proc_side=512), 1),
+    # the cheapest shapes of the remaining instantiations: 64 px (16-wide block1, a 4 x 4 head of 424 channels: 128 x 128 f32out
+    # GEMM, block4's conv3 on the weight-resident 1x1), 416 px at stride 8 (block4 on 52-wide maps: the 256 x 256 ring pair, the
+    # 128 x 256 deep-K conv1)
+    'X-rn50-s16-merged53-side64-b1': (ModelSpec(50, 16, 'merged', proc_side=64), 1),
+    'X-rn50-s8-J17-side416-b8': (ModelSpec(50, 8, 'h36m', proc_side=416), 8),
 }
 PERIOD = 4
+
+# The supported range of the f16 path (test_dispatch_closure): every plan of this grid dispatches only instantiations that a GPU
+# test launches at some shape
+GRID_SIDES = range(64, 513, 32)
+GRID_ARCHS = (50, 101)
+GRID_STRIDES = (4, 8, 16, 32)
+GRID_DATASETS = ('h36m', 'many19', 'merged')
+GRID_BATCHES = (1, 8, 16, 32, 64, 128, 256)
 
 
 def dispatch_table(spec, n):
@@ -114,6 +142,62 @@ def test_every_layer_names_its_kernel_without_a_gpu():
     k32 = Engine(ModelSpec(50, 16, 'h36m'), None, 'f32m', max_batch=2).layer_kernels(2)
     assert k32[0] == 'conv_igemm_f32<64x128,bk32>' and k32[3].startswith('conv_igemm_f32<') and ',v4' in k32[3]
     assert k32[-1] == 'softargmax_partial<acc64,logits32> & softargmax_finalize<acc64>'
+    # crop sides other than 256: a 56-wide 3x3 takes neither the tap-reuse slab kernel (256 % W) nor conv3x3_c64 (128 % W)
+    s224 = ids['X-rn50-s32-J17-side224-b64']
+    for name in ('block1/unit_1/conv2', 'block1/unit_2/conv2', 'block1/unit_3/conv2'):
+        assert s224[name].startswith('conv_igemm_f16_dma<'), (name, s224[name])
+    # a 7 x 7 head is not whole 64-pixel tiles: the fp32-output GEMM, then the two-launch soft-argmax
+    assert s224['logits'] == 'conv_igemm_f16_dma<64x128,bk64,s3,pro>+f32out'
+    assert s224['softargmax'] == 'softargmax_partial<acc32,logits32> & softargmax_finalize<acc32>'
+    assert ids['X-rn50-s16-merged53-side288-b64']['logits'] == 'conv_igemm_f16_dma<128x256,bk64,s3,pro>+f32out'
+    assert ids['X-rn50-s16-merged53-side64-b1']['logits'] == 'conv_igemm_f16_dma<128x128,bk64,s4,pro>+f32out'
+    # ... a 24 x 24 one is 9 tiles: the one-launch head, as is 80 x 80 on 256-pixel tiles and 40 x 40 on 128-pixel ones
+    assert ids['X-rn50-s16-J17-side384-b64']['logits'] == 'head_f16<144x64,k4>'
+    assert ids['X-rn50-s16-J17-side384-b64']['softargmax'] == 'softargmax_finalize<acc32>'
+    assert ids['X-rn50-s4-J17-side320-b16']['logits'] == 'head_f16<144x256,k2>'
+    assert ids['X-rn101-s8-J19-side320-b32']['logits'].startswith('head_f16<160x')
+    # 128-wide block1 maps: the 512-row slab of the tap-reuse 3x3; at stride 4 the rate-2 block3 on its sub-grid form
+    assert ids['X-rn50-s32-J17-side512-b1']['block1/unit_1/conv2'] == 'conv3x3_f16_slab<64x256,rows512,bufs2,tps1,kc64,ws3>'
+    assert ids['X-rn50-s4-J17-side512-b1']['block1/unit_1/conv2'] == 'conv3x3_f16_slab<64x256,rows512,bufs2,tps1,kc64,ws3>'
+    # the stem of any side but 256 reads its fp32 image without the side-256 specialisation
+    assert all(ids[c]['conv1+pool1'] == 'stem_pool_f16<split2,f32in>' for c in ids if '-side' in c)
+
+
+def _gpu_tested_ids():
+    """Every kernel id a GPU test launches: the CONFIGS above (this file) and the layer-by-layer cases of test_f16_layerwise.py,
+    each at its real batch."""
+    from tests.test_f16_layerwise import CASES
+    out = {}
+    runs = [(c, s, n) for c, (s, n) in CONFIGS.items()]
+    runs += [(f'test_f16_layerwise[{i}]', c[0], c[2].get('batch', c[1]) if len(c) > 2 else c[1]) for i, c in enumerate(CASES)]
+    for who, spec, n in runs:
+        for k in Engine(spec, None, 'f16', max_batch=n).layer_kernels(n):
+            out.setdefault(k, who)
+    return out
+
+
+def test_dispatch_closure():
+    """The supported range of the f16 path is the grid
+
+        proc_side 64, 96, ..., 512  x  ResNet-v2 50 / 101  x  stride 4 / 8 / 16 / 32  x  h36m / many19 / merged heads
+        x  batch 1, 8, 16, 32, 64, 128, 256
+
+    (a dry run of the dispatch: no device).  Every kernel instantiation a plan of this grid dispatches must be launched by a
+    GPU-tested configuration -- CONFIGS, or a test_f16_layerwise case at its real batch -- so no shape of the range reaches a
+    kernel no test has held to the fp64 reference."""
+    tested = _gpu_tested_ids()
+    untested = {}
+    for side in GRID_SIDES:
+        for arch in GRID_ARCHS:
+            for stride in GRID_STRIDES:
+                for ds in GRID_DATASETS:
+                    spec = ModelSpec(arch, stride, ds, proc_side=side)
+                    for n in GRID_BATCHES:
+                        for k in Engine(spec, None, 'f16', max_batch=n).layer_kernels(n):
+                            if k not in tested:
+                                untested.setdefault(k, f'rn{arch}-s{stride}-{ds} at proc_side {side}, batch {n}')
+    assert not untested, 'dispatched by the supported grid but launched by no GPU test (first plan that reaches it):\n' + \
+        '\n'.join(f'  {k}: {w}' for k, w in sorted(untested.items()))
 
 
 @pytest.mark.parametrize('nb', [3, 8], ids=['64-pixel-tiles', '256-pixel-tiles'])
@@ -181,9 +265,11 @@ def test_production_dispatch_against_fp64_reference(lib, cuda, cname, layer, kid
     p = min(PERIOD, n)
     check(lib.metro_kernel_notes(1), 'metro_kernel_notes')
     try:
-        if name == 'softargmax':
+        if name == 'softargmax' and kid == 'softargmax_finalize<acc32>':
             pytest.skip('launched (and compared) together with the head: see the logits case of this configuration')
-        if name == 'conv1+pool1':
+        if name == 'softargmax':
+            _softargmax(lib, cuda, spec, n, gen, rng, kid)
+        elif name == 'conv1+pool1':
             _stem(lib, cuda, li, n, gen, rng, dev, kid)
         elif name == 'logits' and kid.startswith('head_f16'):
             _head(lib, cuda, spec, li, n, gen, rng, dev, kid)
@@ -243,6 +329,34 @@ def _head(lib, cuda, spec, li, n, gen, rng, dev, kid):
     want = logits_to_output(H.oracle_spec(spec), ref).numpy()
     d = np.abs(poses[:p].cpu().numpy() - want).max()
     assert d <= 2e-3, f'{kid}: poses {d} mm from the exact soft-argmax of the exact logits'
+
+
+def _softargmax(lib, cuda, spec, n, gen, rng, kid):
+    """The two-launch soft-argmax behind a head that is not whole tiles, on fp32 logits at the layer's real side and batch:
+    N(0, 4) plus one planted peak per (image, joint) at a random voxel, so no pose is the map centre."""
+    from oracle.forward import logits_to_output
+    side, j, dd = spec.heatmap_side, spec.skeleton.n_head, spec.depth
+    p = min(PERIOD, n)
+    base = torch.randn((p, side, side, dd * j), generator=gen, device=cuda, dtype=torch.float32) * 4.0
+    for i in range(p):
+        for jj in range(j):
+            h, w, d = (int(v) for v in rng.integers(0, (side, side, dd)))
+            base[i, h, w, d * j + jj] += 12.0
+    logits = base.repeat(((n + p - 1) // p, 1, 1, 1))[:n].contiguous()
+    cs = spec.to_c(_lib.METRO_PREC_F16)
+    scratch = torch.empty(lib.metro_softargmax_scratch_bytes(n, side, j), dtype=torch.uint8, device=cuda)
+    poses = torch.full((n, spec.skeleton.n_out, 3), float('nan'), dtype=torch.float32, device=cuda)
+    check(lib.metro_softargmax(H.ptr(logits), n, C.byref(cs), _lib.METRO_PREC_F16, H.ptr(scratch), H.ptr(poses), None), 'metro_softargmax')
+    torch.cuda.synchronize()
+    assert _noted(lib) == kid.split(' & '), f'the entry point launched {_noted(lib)}, the plan names {kid}'
+    _assert_periodic(poses, n, kid)
+    want = logits_to_output(H.oracle_spec(spec), base.cpu().double().numpy()).numpy()
+    got = poses[:p].cpu().numpy()
+    assert np.isfinite(got).all(), kid
+    d = np.abs(got - want).max()
+    assert d <= 2e-3, f'{kid}: poses {d} mm from the exact soft-argmax of the same logits'
+    # the planted peaks pull the joints off the centre: the comparison is not of two maps' centres
+    assert np.abs(want).max() > 50.0, np.abs(want).max()
 
 
 def _conv(lib, cuda, li, n, gen, rng, dev, kid, name):
