@@ -113,6 +113,18 @@ __global__ __launch_bounds__(64) void eval_pose_kernel(const float* __restrict__
             for (int c = 0; c < 3; ++c) acc += A[r][c] * Vs[c][k];
             U[r][k] = acc / s[k];
         }
+    // a singular value that is exactly 0 (A = 0; rank-1 fits: points on a line) leaves its left vector free, and A v / 0 is
+    // 0 / 0: take the first axis, then a unit vector orthogonal to the first left vector, as LAPACK returns SOME completion
+    if (!(s[0] > 0.0)) { U[0][0] = 1.0; U[1][0] = 0.0; U[2][0] = 0.0; }
+    if (!(s[1] > 0.0)) {
+        int ax = 0;
+        for (int r = 1; r < 3; ++r)
+            if (fabs(U[r][0]) < fabs(U[ax][0])) ax = r;
+        double u[3], nn = 0;
+        for (int r = 0; r < 3; ++r) { u[r] = (r == ax ? 1.0 : 0.0) - U[ax][0] * U[r][0]; nn += u[r] * u[r]; }
+        nn = sqrt(nn);
+        for (int r = 0; r < 3; ++r) U[r][1] = u[r] / nn;
+    }
     // third left vector: from A v3 / s3 when well conditioned, else the cross product (rank-2 fits)
     {
         double u3[3];
@@ -132,9 +144,18 @@ __global__ __launch_bounds__(64) void eval_pose_kernel(const float* __restrict__
             for (int c = 0; c < 3; ++c) T[r][c] -= 2.0 * Vs[r][2] * U[c][2];
         trace -= 2.0 * s[2];
     }
-    const double bsc = trace * normx / normy;                                  // scaling=True (procrustes.py:82)
+    double bsc = trace * normx / normy;                                        // scaling=True (procrustes.py:82)
     double cvec[3];
     for (int c = 0; c < 3; ++c) { double acc = 0; for (int k = 0; k < 3; ++k) acc += muy[k] * T[k][c]; cvec[c] = mux[c] - bsc * acc; }
+    // a point set of zero norm (fewer than two distinct valid joints) makes A 0 / 0: the reference's SVD raises LinAlgError
+    // on it and rigid_align returns the prediction as it is (util3d.py:152-154)
+    if (!(normx > 0.0 && normy > 0.0)) {
+        bsc = 1.0;
+        for (int r = 0; r < 3; ++r) {
+            cvec[r] = 0.0;
+            for (int c = 0; c < 3; ++c) T[r][c] = r == c ? 1.0 : 0.0;
+        }
+    }
     // aligned = b * pred @ T + c for ALL joints (util3d.py:156-159), then root-relative distance
     double ar[3];
     {

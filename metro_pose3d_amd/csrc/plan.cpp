@@ -1296,9 +1296,11 @@ int metro_softargmax01(const void* d_logits, int32_t n, const MetroSpec* spec, i
 
 static int check_head_args(const MetroSpec* spec, int32_t n, int32_t n_edges, const char* what) {
     METRO_CHECK_ARG(spec != nullptr && n > 0, "%s: bad argument", what);
-    METRO_CHECK_ARG(spec->n_joints_head >= 1 && spec->n_joints_head <= 64 && spec->n_joints_out >= 1 &&
-                        spec->n_joints_out <= 64, "%s: joint counts out of range (<= 64)", what);
-    METRO_CHECK_ARG(n_edges >= 0 && n_edges <= 64, "%s: at most 64 stick-figure edges (got %d)", what, n_edges);
+    // METRO_MAX_JOINTS is the length of the kernels' per-lane joint and edge arrays (HEAD_MAX, backproject.h)
+    METRO_CHECK_ARG(spec->n_joints_head >= 1 && spec->n_joints_head <= METRO_MAX_JOINTS && spec->n_joints_out >= 1 &&
+                        spec->n_joints_out <= METRO_MAX_JOINTS, "%s: joint counts out of range (<= %d)", what, METRO_MAX_JOINTS);
+    METRO_CHECK_ARG(n_edges >= 0 && n_edges <= METRO_MAX_JOINTS, "%s: at most %d stick-figure edges (got %d)", what,
+                    METRO_MAX_JOINTS, n_edges);
     return METRO_OK;
 }
 
@@ -1334,8 +1336,8 @@ int metro_heatmap_to_25d(const float* d_coords01, int32_t n, const MetroSpec* sp
 
 int metro_to_orig_cam(const float* d_coords, const float* d_rot, const int32_t* d_mirror, float* d_out, int32_t n,
                       int32_t n_joints, void* stream) {
-    METRO_CHECK_ARG(d_coords && d_rot && d_mirror && d_out && n > 0 && n_joints >= 1 && n_joints <= 64,
-                    "to_orig_cam: bad argument (1 <= joints <= 64)");
+    METRO_CHECK_ARG(d_coords && d_rot && d_mirror && d_out && n > 0 && n_joints >= 1 && n_joints <= METRO_MAX_JOINTS,
+                    "to_orig_cam: bad argument (1 <= joints <= %d)", METRO_MAX_JOINTS);
     return launch_to_orig_cam(d_coords, d_rot, d_mirror, d_out, n, n_joints, static_cast<hipStream_t>(stream));
 }
 

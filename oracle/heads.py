@@ -69,6 +69,37 @@ def optimize_z_offset_by_bones_single(x, delta_z, target_bone_lengths, edges, in
     return float(solution.x[0])
 
 
+def edge_coefficients(x, delta_z, edges):
+    """c, d, e of optimize_z_offset_by_bones_single (its first five lines), fp32 as it forms them: tests perturb them by an
+    ulp to see how far the solution moves."""
+    a = np.asarray([x[i] - x[j] for i, j in edges])
+    y = x * np.expand_dims(delta_z, -1)
+    b = np.asarray([y[i] - y[j] for i, j in edges])
+    return np.sum(a ** 2, axis=1), np.sum(2 * a * b, axis=1), np.sum(b ** 2, axis=1)
+
+
+def z_offset_from_coefficients(c, d, e, target_bone_lengths, initial_guess=2000, half_d_jacobian=False):
+    """The rest of optimize_z_offset_by_bones_single on given coefficients: the same residual, the same (inexact) Jacobian
+    and the same scipy call.  NaN where scipy refuses the problem (a residual that is not finite at the initial guess).
+    half_d_jacobian=True is the derivative the reference did NOT write, (z c + d/2) / len: tests show that it gives other
+    answers, so that a device solver 'corrected' to it would be caught."""
+    def reconstruct_bone_lengths(z):
+        return np.sqrt(z ** 2 * c + z * d + e)
+
+    def fn(z):
+        return reconstruct_bone_lengths(z) - target_bone_lengths
+
+    def jacobian(z):
+        return ((z * c + (d / 2 if half_d_jacobian else d)) / reconstruct_bone_lengths(z)).reshape([-1, 1])
+
+    try:
+        with np.errstate(invalid='ignore', divide='ignore'):
+            solution = scipy.optimize.least_squares(fn, jac=jacobian, x0=initial_guess, method='lm')
+    except ValueError:
+        return float('nan')
+    return float(solution.x[0])
+
+
 def back_project(camcoords2d_homog, delta_z, z_offset):
     return (camcoords2d_homog * np.expand_dims(delta_z + np.expand_dims(z_offset, -1), -1)).astype(np.float32)
 

@@ -21,8 +21,13 @@ def enorm(v):
         s += float(t) * float(t)
     return math.sqrt(s)
 
-def lmder1(fn, jac, x0, ftol=1e-8, xtol=1e-8, gtol=1e-8, maxfev=100, factor=100.0, diag=1.0):
-    """MINPACK lmder for ONE unknown, mode = 2 (diag given), restated step by step."""
+def lmder1(fn, jac, x0, ftol=1e-8, xtol=1e-8, gtol=1e-8, maxfev=100, factor=100.0, diag=1.0, stats=None):
+    """MINPACK lmder for ONE unknown, mode = 2 (diag given), restated step by step.
+    stats: an optional dict that counts the branches taken ('givens_cotan' / 'givens_tan': the two rotations of qrsolv,
+    'lmpar_iterations': passes of lmpar's loop), for tests that must know which paths their problems reach."""
+    def count(key):
+        if stats is not None:
+            stats[key] = stats.get(key, 0) + 1
     x = float(x0)
     fvec = np.asarray(fn(x), dtype=np.float64); nfev = 1; njev = 0
     fnorm = enorm(fvec)
@@ -97,6 +102,7 @@ def lmder1(fn, jac, x0, ftol=1e-8, xtol=1e-8, gtol=1e-8, maxfev=100, factor=100.
                     par_l = gn / dxnorm
                 while True:
                     liter += 1
+                    count('lmpar_iterations')
                     if par_l == 0.0:
                         par_l = max(DWARF, 0.001 * paru)
                     temp = math.sqrt(par_l)
@@ -105,10 +111,12 @@ def lmder1(fn, jac, x0, ftol=1e-8, xtol=1e-8, gtol=1e-8, maxfev=100, factor=100.
                     rr = r; wa = qtf; qtbpj = 0.0
                     if sd != 0.0:
                         if abs(rr) < abs(sd):
+                            count('givens_cotan')
                             cotan = rr / sd
                             sin = 0.5 / math.sqrt(0.25 + 0.25 * cotan * cotan)
                             cos = sin * cotan
                         else:
+                            count('givens_tan')
                             tan = sd / rr
                             cos = 0.5 / math.sqrt(0.25 + 0.25 * tan * tan)
                             sin = cos * tan

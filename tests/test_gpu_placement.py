@@ -223,3 +223,147 @@ def test_locate_poses_in_frames_f64_matches_the_oracle(cuda, tmp_path, proc_side
     got = locate_poses_in_frames(frames[0], boxes[:3], path, scale_recovery='metro', precision='f16')
     base = estimate_pose_in_frames(frames[0], boxes[:3], path, precision='f16')[0]
     assert torch.equal(got.poses, base) and torch.isfinite(got.keypoints2d).all()
+
+
+# ---- the bone-length solve inside the placement launch, on the hard corpus ----------------------------------------------
+
+def _random_rotations(rng, n, improper):
+    """fp32 [n, 3, 3] orthogonal matrices; improper[i]: det -1 (a mirrored view)."""
+    q, _ = np.linalg.qr(rng.normal(size=(n, 3, 3)))
+    q *= (np.where(improper, -1.0, 1.0) * np.sign(np.linalg.det(q)))[:, None, None]
+    return q.astype(np.float32)
+
+
+def _synthetic_records(rng, inv_k):
+    """PlacementParams around given K^-1: random rotations (every other one improper), camera positions metres away,
+    identity keypoint homographies."""
+    from metro_pose3d_amd.frames import PlacementParams
+    n = len(inv_k)
+    improper = np.arange(n) % 2 == 1
+    eye = np.tile(np.eye(3, dtype=np.float32), (n, 1, 1))
+    return PlacementParams(np.zeros(n, np.int32), np.asarray(inv_k, np.float32), _random_rotations(rng, n, improper),
+                           _random_rotations(rng, n, improper), rng.uniform(-5000, 5000, (n, 3)).astype(np.float32), eye,
+                           eye.copy(), np.zeros((n, 5), np.float32))
+
+
+@pytest.mark.parametrize('family', ['friendly', 'noisy', 'mis-scaled', 'collapsed'])
+@pytest.mark.parametrize('dataset', ['h36m', 'many19', 'merged'])
+def test_place_poses_bone_lengths_on_the_hard_corpus(cuda, dataset, family):
+    """metro_place_poses, bone-lengths, in the three coordinate frames on the corpus of tests/test_heads.py (130 crops, every
+    other rotation improper, shared and per-pose targets): z_offset within the corpus tolerance of scipy's (tests/helpers.py
+    BoneCase: max(1e-3 mm, k ulp32(|z|)), k from the oracle's own sensitivity to an ulp of its fp32 coefficients), no NaN
+    where scipy is finite, poses against the oracle's placement of scipy's z, and every bit equal to
+    metro_backproject_bone_lengths (+ metro_to_orig_cam + cam_loc) on the same inputs.
+    Measured on the MI355X: z offsets and poses bit-equal to the oracle's in every family and frame."""
+    from metro_pose3d_amd import heads as MH
+    from tests import helpers as H
+    for per_pose in (False, True):
+        case = H.bone_case(dataset, family, per_pose)
+        spec, sk = case.spec, case.spec.skeleton
+        what = f'{dataset} {family} {"per-pose" if per_pose else "shared"}'
+        q = _synthetic_records(np.random.default_rng(sk.n_head + per_pose), case.inv_k)
+        crop, zhead = MH.backproject_bone_lengths(_dev(case.c01, cuda), case.inv_k, case.targets, spec, permute=True)
+        for coords in OPL.COORDS:
+            got, _, z = _place(cuda, spec, case.c01, q, 'bone-lengths', coords, bones=case.targets)
+            assert np.array_equal(z, zhead.cpu().numpy()), (what, coords)
+            same = crop
+            if coords != 'crop':
+                same = MH.to_orig_cam(crop, q.rot_to_orig_cam if coords == 'camera' else q.rot_to_world, sk.out_mirror)
+            same = same.cpu().numpy() + (q.cam_loc[:, None] if coords == 'world' else np.float32(0))
+            assert np.array_equal(got, same), (what, coords)
+            case.check_z(z, f'{what} {coords}')
+            ref, _, _ = OPL.place(case.c01, q, spec.stride, 'true-root-depth', coords, sk.permutation, sk.out_mirror,
+                                  root_depth=case.z32, proc_side=spec.proc_side, centered=spec.centered_stride,
+                                  box_size_mm=spec.box_size_mm)
+            case.check_poses(got, ref, f'{what} {coords}')
+
+
+# ---- placement outside the fixture: strides, centring, crop sides, skeletons, ragged n ----------------------------------
+
+GRID = [('h36m', 4, True, 256), ('h36m', 8, False, 224), ('h36m', 16, True, 384), ('h36m', 32, False, 256),
+        ('many19', 4, False, 384), ('many19', 8, True, 256), ('many19', 16, False, 224), ('many19', 32, True, 384),
+        ('merged', 4, True, 224), ('merged', 8, False, 384), ('merged', 16, True, 256), ('merged', 32, False, 224)]
+
+
+def _grid_case(dataset, stride, centered, side, n=200):
+    """n synthetic crops of the fixture's three cameras (two distorted, one not: the keypoint modes alternate from crop to crop)
+    with the virtual cameras of random person boxes; every other crop's rotations improper (a reflection that keeps rays in
+    front of the camera), crops 4, 70 and 133 (distorted) and 8, 64 (homography) looking away from the camera.  coords01 are
+    those of a pose 3 to 6 m in front of the virtual camera."""
+    from metro_pose3d_amd.frames import placement_params
+    from tests.test_frames import FIX as FRAMES_FIX, fixture_cameras
+    fr = np.load(FRAMES_FIX)
+    cams = fixture_cameras(fr)
+    spec = ModelSpec(50, stride, dataset, centered_stride=centered, proc_side=side)
+    sk = spec.skeleton
+    rng = np.random.default_rng([stride, side, sk.n_head])
+    fi = np.arange(n) % 3
+    fi[64] = 2
+    hw = np.array([fr[f'cam{i}_frame_hw'] for i in range(3)], np.float64)[fi]
+    wh = rng.uniform(150, 500, (n, 2))
+    xy = rng.uniform(0, 1, (n, 2)) * (hw[:, ::-1] - wh)
+    q = placement_params(cams, np.concatenate([xy, wh], 1), fi, side)
+    flip = np.diag([-1., 1., 1.]).astype(np.float32)
+    back = np.diag([1., -1., -1.]).astype(np.float32)
+    rc, rw, hm = q.rot_to_orig_cam.copy(), q.rot_to_world.copy(), q.homography.copy()
+    rc[1::2] = rc[1::2] @ flip
+    rw[1::2] = rw[1::2] @ flip
+    for i in (4, 70, 133):
+        assert q.keypoint_mode[i] == _lib.METRO_WARP_DISTORTED
+        rc[i] = rc[i] @ back
+    for i in (8, 64):
+        assert q.keypoint_mode[i] == _lib.METRO_WARP_HOMOGRAPHY
+        hm[i] = -hm[i]
+    q = q._replace(rot_to_orig_cam=rc, rot_to_world=rw, homography=hm)
+    assert (np.linalg.det(rc[1::2].astype(np.float64)) < 0).all() and (np.linalg.det(rc[0::2].astype(np.float64)) > 0).all()
+    # a pose in front of each virtual camera and its soft-argmax coordinates
+    j = sk.n_head
+    p = rng.normal(0, 150, (n, j, 3))
+    p[..., 2] += rng.uniform(3000, 6000, (n, 1))
+    kk = np.linalg.inv(q.inv_intrinsics.astype(np.float64))
+    uv = np.einsum('nij,ncj->nci', kk, p / p[..., 2:3])[..., :2]
+    lrc = (side - 1) - ((side - 1) % stride) - 1
+    c01 = np.empty((n, j, 3), np.float32)
+    c01[..., :2] = (uv - (stride // 2 if centered else 0)) / lrc
+    c01[..., 2] = (p[..., 2] - p[:, -1:, 2]) / spec.box_size_mm + 0.5 + rng.normal(0, 0.01, (n, j))
+    edges = np.asarray(sk.head_edges)
+    bones = np.linalg.norm(p[:, edges[:, 0]] - p[:, edges[:, 1]], axis=-1)
+    rel = rng.normal(0, 300, (n, sk.n_out, 3)).astype(np.float32)
+    return spec, q, c01, bones, p[:, -1, 2].astype(np.float32), rel
+
+
+@pytest.mark.parametrize('dataset,stride,centered,side', GRID, ids=[f'{d}-s{s}-{"c" if c else "nc"}-{p}' for d, s, c, p in GRID])
+def test_place_poses_outside_the_fixture(cuda, dataset, stride, centered, side):
+    """metro_place_poses against tests/oracle_placement.py away from the reference fixture's one configuration: every stride
+    with every skeleton, both centrings and crop sides 224 / 256 / 384 with every skeleton, n = 1, 64, 65 and 200, homography
+    and distorted keypoints alternating inside a wave, every other rotation improper, five crops behind the camera (NaN
+    keypoints exactly where the oracle has them).  All three scale recoveries in all three frames (bone-lengths: shared
+    targets in one frame, per-pose targets in the two others).
+    Bounds: those of test_place_poses_matches_the_reference, 1e-6 relative on 3D and on z, 1e-3 px on keypoints.
+    Measured on the MI355X: 3D, z and keypoints bit-equal to the oracle's in all twelve configurations."""
+    spec, q, c01, bones, root, rel = _grid_case(dataset, stride, centered, side)
+    sk = spec.skeleton
+    worst3 = worstkp = 0.0
+    for k, n in enumerate((1, 64, 65, 200)):
+        qn = type(q)(*(a[:n] for a in q))
+        for s, scale in enumerate(OPL.SCALES):
+            for c, coords in enumerate(OPL.COORDS):
+                shared = (k + c) % 3 == 0
+                t = (bones[:n].mean(axis=0) * 0.97 if shared else bones[:n]) if scale == 'bone-lengths' else None
+                got, kp, z = _place(cuda, spec, c01[:n], qn, scale, coords, poses=rel[:n] if scale == 'metro' else None, bones=t,
+                                    root=root[:n] if scale == 'true-root-depth' else None)
+                want, wkp, wz = OPL.place(c01[:n], qn, stride, scale, coords, sk.permutation, sk.out_mirror, edges=sk.head_edges,
+                                          bone_lengths=t, root_depth=root[:n], poses_rel=rel[:n], proc_side=side,
+                                          centered=centered, box_size_mm=spec.box_size_mm)
+                e3 = np.abs(got - want).max() / np.abs(want).max()
+                assert e3 <= 1e-6, (n, scale, coords, e3)
+                if scale != 'metro':
+                    assert np.abs(z - wz).max() <= 1e-6 * np.abs(wz).max(), (n, scale, coords)
+                assert np.array_equal(np.isnan(kp), np.isnan(wkp)), (n, scale, coords)
+                behind = [i for i in (4, 8, 64, 70, 133) if i < n]
+                assert np.isnan(wkp[behind]).all() and np.isnan(wkp).all(axis=(1, 2)).sum() == len(behind)
+                ekp = np.nanmax(np.abs(kp - wkp)) if n > len(behind) else 0.0
+                assert ekp <= 1e-3, (n, scale, coords, ekp)
+                worst3, worstkp = max(worst3, e3), max(worstkp, ekp)
+    print(f'{dataset} stride {stride} centred {centered} side {side}: worst 3D relative error {worst3:.2e}, worst keypoint '
+          f'error {worstkp:.2e} px')

@@ -210,3 +210,99 @@ def test_flipped_view_swaps_mirror_joints(cuda, tmp_path):
     assert np.abs(_np(out) - expect).max() <= 1e-3
     assert np.array_equal(_np(got.keypoints2d), _np(kp)[:, mirror], equal_nan=True)
     assert not np.allclose(_np(kp)[:, mirror], _np(kp), equal_nan=True)       # the swap moves the keypoints
+
+
+# ---- metro_merge_views on its own against fp64 ----------------------------------------------------------------------------
+
+def _merge_reference(poses, kps, z, rot, mirror, nv):
+    """Plain fp64: per box and joint the mean over the views, the RMS distance of the views from it, the mean of the finite
+    keypoints (a view with det <= 0 contributes its mirror joint's), the mean z offset."""
+    p = poses.astype(np.float64).reshape(-1, nv, *poses.shape[1:])
+    mean = p.sum(axis=1) / nv
+    spread = np.sqrt(((p - mean[:, None]) ** 2).sum(axis=-1).sum(axis=1) / nv)
+    k = kps.astype(np.float64).reshape(-1, nv, *kps.shape[1:])
+    mirrored = ~(np.linalg.det(rot.astype(np.float64)) > 0).reshape(-1, nv)
+    k = np.where(mirrored[:, :, None, None], k[:, :, list(mirror)], k)
+    ok = np.isfinite(k).all(axis=-1, keepdims=True)
+    cnt = ok.sum(axis=1)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        kp = np.where(cnt > 0, np.where(ok, k, 0.0).sum(axis=1) / cnt, np.nan)
+    return mean, spread, kp, z.astype(np.float64).reshape(-1, nv).sum(axis=1) / nv
+
+
+def _within_one_ulp(got, want64):
+    """got fp32 against the fp64 result rounded to fp32: equal, or one float32 spacing apart."""
+    want = want64.astype(np.float32)
+    assert np.array_equal(np.isnan(got), np.isnan(want))
+    d = np.abs(got.astype(np.float64) - want.astype(np.float64))
+    ok = ~np.isnan(want)
+    return (d[ok] <= np.spacing(np.abs(want[ok])).astype(np.float64)).all(), int((got[ok] != want[ok]).sum())
+
+
+@pytest.mark.parametrize('nj', [17, 19, 53])
+@pytest.mark.parametrize('nv', [1, 2, 5, 32])
+def test_merge_views_matches_fp64(cuda, lib, nv, nj):
+    """metro_merge_views called directly, V = 1 / 2 / 5 / 32 views of 17 / 19 / 53 joints, n such that n x joints crosses one
+    and two 256-thread blocks.  Views 1, 4, 7, ... are mirrored (det -1: keypoint j comes from joint mirror[j]), one record has
+    det exactly 0 (counts as mirrored, as metro_place_poses decides it).  Planted among the keypoints: NaN or +-inf in ONE
+    coordinate (the view drops out of both), every view of a joint and of its mirror joint non-finite (NaN out), and boxes
+    with none.  The kernel accumulates in fp64 in view order, so poses, spread, keypoints and z are expected bit-equal to the
+    fp64 reference rounded to fp32; asserted: within one float32 ulp of it, and the NaN pattern identical.  Outputs that
+    are not asked for (no spread; no keypoints and z) change nothing else, and a guard row behind every output stays as it
+    was.  Measured on the MI355X: every value bit-equal."""
+    from metro_pose3d_amd.frames import PlacementParams, pack_placements
+    from metro_pose3d_amd.joints import skeleton
+    from tests.test_gpu_placement import _random_rotations
+    sk = skeleton({17: 'h36m', 19: 'many19', 53: 'merged'}[nj])
+    mirror = np.asarray(sk.head_mirror if nj == 53 else sk.out_mirror, np.int32)
+    assert len(mirror) == nj and (mirror != np.arange(nj)).any()
+    differ = 0
+    for n in (256 // nj + 1, 512 // nj + 1):
+        assert (n - 1) * nj <= 256 * ((n * nj - 1) // 256) < n * nj            # the last box spills into one more block
+        rng = np.random.default_rng([nv, nj, n])
+        m = n * nv
+        poses = (rng.normal(0, 400, (m, nj, 3)) + rng.uniform(-5000, 5000, (m, 1, 3))).astype(np.float32)
+        kps = rng.uniform(-200, 2200, (m, nj, 2)).astype(np.float32)
+        z = rng.uniform(2000, 7000, m).astype(np.float32)
+        rot = _random_rotations(rng, m, np.arange(m) % 3 == 1)
+        rot[m // 2] = np.diag([1., 1., 0.]).astype(np.float32)                  # det exactly 0
+        bad = np.array([np.nan, np.inf, -np.inf], np.float32)
+        for i in range(0, m, 3):                                               # one coordinate of one joint of a view
+            kps[i, rng.integers(nj), rng.integers(2)] = bad[i % 3]
+        for box in range(0, n, 4):                                             # every view of a joint and of its mirror joint
+            j = int(rng.integers(nj))
+            kps[box * nv:(box + 1) * nv, [j, mirror[j]], rng.integers(2)] = bad[box % 3]
+        eye = np.tile(np.eye(3, dtype=np.float32), (m, 1, 1))
+        recs = pack_placements(PlacementParams(np.zeros(m, np.int32), eye, rot, eye, np.zeros((m, 3), np.float32), eye, eye,
+                                               np.zeros((m, 5), np.float32)))
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
+        d_p, d_k, d_z, d_r, d_m = dev(poses), dev(kps), dev(z), dev(recs), dev(mirror)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+
+        def run(with_kp, with_z, with_spread):
+            """-> host arrays (None where not asked for), each allocated with a guard row that must stay 12345."""
+            outs = [torch.full(s, 12345.0, device=cuda) for s in ((n + 1, nj, 3), (n + 1, nj, 2), (n + 1,), (n + 1, nj))]
+            use = [True, with_kp, with_z, with_spread]
+            o = [t if u else None for t, u in zip(outs, use)]
+            check(lib.metro_merge_views(ptr(d_p), ptr(d_k if with_kp else None), ptr(d_z if with_z else None), ptr(d_r), ptr(d_m),
+                                        n, nv, nj, ptr(o[0]), ptr(o[1]), ptr(o[2]), ptr(o[3]),
+                                        C.c_void_p(torch.cuda.current_stream(cuda).cuda_stream)), 'metro_merge_views')
+            for t in outs:
+                assert (t[n:] == 12345.0).all()
+            return [t[:n].cpu().numpy() if u else None for t, u in zip(outs, use)]
+
+        want = _merge_reference(poses, kps, z, rot, mirror, nv)
+        got = run(True, True, True)
+        assert np.isnan(want[2]).any() and np.isfinite(want[2]).any()
+        for name, g, w in zip(('poses', 'keypoints', 'z', 'spread'), (got[0], got[1], got[2], got[3]),
+                              (want[0], want[2], want[3], want[1])):
+            ok, ne = _within_one_ulp(g, w)
+            differ += ne
+            assert ok, (n, name)
+        if nv == 1:
+            assert (got[3] == 0).all() and np.array_equal(got[0], poses)
+        bare = run(False, False, False)
+        assert np.array_equal(bare[0], got[0]) and bare[1] is None
+        some = run(True, False, False)
+        assert np.array_equal(some[0], got[0]) and np.array_equal(some[1], got[1], equal_nan=True)
+    print(f'V {nv}, {nj} joints: {differ} values differ from the rounded fp64 reference')
