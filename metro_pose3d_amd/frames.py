@@ -5,28 +5,30 @@ the box centre, drops the lens distortion, squares the pixels and zooms so the b
 (src/cameralib.py:265-324) warps the uint8 frame into it; after the net `volumetric.to_orig_cam` (src/model/volumetric.py:
 204-216, 277-281) rotates the poses back into the original camera or the world.  Here:
 
-  Camera, undistort_points, look_at_box   host geometry, the reference's camera restated in its dtypes (fp32 R, K, t)
+  Camera, undistort_points, look_at_box   host geometry, the reference's camera restated in its dtypes (camera.py)
+  pixel_format, color_matrix              frames as decoders leave them, 'rgb' (the default), 'bgr', 'nv12', 'i420', converted
+                                          per tap inside the warp (frame_formats.py)
   crop_params                             per-crop warp mode + matrices and the rotations back (data_loading.py:110-111)
-  warp_frames                             one HIP launch (metro_warp_crops_frames_u8) for the crops of many frames
-  pixel_format, color_matrix              frames as decoders leave them: 'bgr' (OpenCV), 'nv12' (hardware decoders), 'i420'
-                                          (libavcodec's yuv420p), converted per tap inside the warp by
-                                          metro_warp_crops_frames_planes; 'rgb' (the default) keeps metro_warp_crops_frames_u8
-  estimate_pose_in_frames                 the whole chain on one device, enqueued on the current stream
   placement_params                        per-crop virtual camera (inverse K, rotations, camera centre) and the way back to the
                                           frame's pixels (MetroPlacement records)
-  locate_poses_in_frames                  absolute poses (bone-lengths / true-root-depth scale recovery, volumetric.py:171-208)
-                                          and 2D frame keypoints, one metro_place_poses launch after the forward
-  view_set, pack_view_bases, view_params test-time augmentation (`views=`): V rolled / zoomed / flipped views per box
+  pack_crops, pack_placements,            the host restatement of the records the device writes: what tests and tools compare
+  view_params, warp_frames                against, and one warp launch over host-packed records; not on the product path
+  view_set, pack_view_bases               test-time augmentation (`views=`): V rolled / zoomed / flipped views per box
                                           (data_loading.py:60-68, 77-79), expanded on the device (metro_expand_views) from one
                                           record per box and fused per box after the placement (metro_merge_views)
   look_at_boxes, pack_frame_cameras       the per-box records on the device (metro_look_at_boxes, `geometry='device'`, the
                                           default for CUDA boxes): look_at_box and pack_view_bases restated per thread from a
                                           per-frame camera table, so boxes from a GPU detector stay on the GPU and the call does
                                           no per-box host work ('host' keeps the NumPy geometry and its bits)
+  estimate_pose_in_frames                 root-relative poses: ONE chain on one device, enqueued on the current stream, for
+                                          host boxes, device boxes and views (views=None is the identity view): per-box
+                                          records, metro_expand_views, one warp launch, the forward, metro_to_orig_cam,
+                                          metro_merge_views
+  locate_poses_in_frames                  absolute poses (bone-lengths / true-root-depth scale recovery, volumetric.py:171-208)
+                                          and 2D frame keypoints: the same chain with one metro_place_poses launch after the
+                                          forward
 
-Divergences from the reference, on purpose:
-  * a Camera built from intrinsics alone (no R, no t) defaults to world_up = (0, -1, 0), not the reference's (0, 0, 1): with
-    R = I and t = 0, `turn_towards` takes cross(new_z, (0, 0, 1)), which vanishes for a box near the optical axis;
+Divergences from the reference, on purpose (camera.py and frame_formats.py list their own):
   * reproject_image's case 1 (cameralib.py:282-293: an all-zero coefficient array whose virtual R is allclose to the original
     goes to cv2.warpAffine, with INTER_AREA when zooming out) is not reproduced: any coefficient array takes the general mode;
   * a general-mode ray that points behind the camera (z <= 0) samples the border value 0; the reference projects it through
@@ -43,193 +45,26 @@ Divergences from the reference, on purpose:
   * the device geometry (geometry='device') inverts 3x3 matrices in closed form, not with LAPACK's pivoted solves: its records
     are within one fp32 ulp of the host's (most of them bit-identical), not always the host's bits.  The host geometry, the
     default for host boxes, costs ~0.2 ms of NumPy per box and bounds the call there (profiles/frames_probe.json); the
-    device geometry takes one ~6 us launch for 64 boxes (profiles/device_geometry_probe.json);
-  * a YUV frame ('nv12', 'i420') is the RGB image of OpenCV's integer cvtColor(COLOR_YUV2RGB_NV12 / _I420) rule (limited
-    range, BT.601 by default or BT.709, the chroma of each 2x2 block replicated; include/metro_hip.h), not of ffmpeg's
-    swscale, which rounds differently; a tap outside the frame is black (RGB 0), not YUV (0, 0, 0).
+    device geometry takes one ~6 us launch for 64 boxes (profiles/device_geometry_probe.json).
 """
 from __future__ import annotations
 
-import copy
 import ctypes as C
 import math
 import os
 from collections import OrderedDict
-from typing import NamedTuple, Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
 
 from metro_pose3d_amd import _lib
 from metro_pose3d_amd._lib import check
+from metro_pose3d_amd.camera import (UNDISTORT_ITERATIONS, Camera, _roll_rad, _square_crop_camera,  # noqa: F401 -- the public
+                                     euler2mat_ryxz, look_at_box, undistort_points, view_camera)    # names of this module
+from metro_pose3d_amd.frame_formats import (COLOR_MATRICES, PIXEL_FORMATS, _LAYOUTS, _FrameSet, _Planar,  # noqa: F401
+                                            _device_frames, _first_frame, _frame_set, _planar, _upload)
 from metro_pose3d_amd.preprocess import box_homography
-
-UNDISTORT_ITERATIONS = 5
-
-
-def undistort_points(points, intrinsic_matrix, distortion_coeffs) -> np.ndarray:
-    """cv2.undistortPoints(points, K, D) with R = P = None -> float32 [N, 2] normalised camera coordinates.
-
-    OpenCV is absent here, so this is restated from its published source, modules/imgproc/src/undistort.cpp
-    (cvUndistortPoints / cvUndistortPointsInternal, 3.x): K and D converted to double; fx, fy, cx, cy only (a skew term is
-    ignored); x = (u - cx) * (1 / fx); with coefficients, the fixed-point iteration
-        icdist = 1 / (1 + ((k3 r2 + k2) r2 + k1) r2),  x = (x0 - dx) icdist
-    run for the fixed count of the default criteria, TermCriteria(COUNT, 5, 0.01) (`iters = 5` in the older 3.x form), then
-    the result is stored as float32 like the float32 input.  PARITY UNPINNED against cv2 itself (no OpenCV to execute)."""
-    p = np.asarray(points, np.float32).reshape(-1, 2).astype(np.float64)
-    a = np.asarray(intrinsic_matrix, np.float64)
-    fx, fy, cx, cy = a[0, 0], a[1, 1], a[0, 2], a[1, 2]
-    ifx, ify = 1. / fx, 1. / fy
-    x = (p[:, 0] - cx) * ifx
-    y = (p[:, 1] - cy) * ify
-    if distortion_coeffs is not None:
-        k = np.zeros(14)
-        d = np.asarray(distortion_coeffs, np.float64).ravel()
-        k[:len(d)] = d
-        x0, y0 = x, y
-        for _ in range(UNDISTORT_ITERATIONS):
-            r2 = x * x + y * y
-            icdist = (1 + ((k[7] * r2 + k[6]) * r2 + k[5]) * r2) / (1 + ((k[4] * r2 + k[1]) * r2 + k[0]) * r2)
-            delta_x = 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x) + k[8] * r2 + k[9] * r2 * r2
-            delta_y = k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y + k[10] * r2 + k[11] * r2 * r2
-            x = (x0 - delta_x) * icdist
-            y = (y0 - delta_y) * icdist
-    return np.stack([x, y], axis=-1).astype(np.float32)
-
-
-class Camera:
-    """The parts of the reference's cameralib.Camera (src/cameralib.py:25-84) the frame pipeline needs, in its dtypes:
-    R (world -> camera rotation), t (optical centre in world coordinates) and the intrinsic matrix are float32, the
-    distortion coefficients (k1, k2, p1, p2, k3; OpenCV order) float32 or None.
-
-    world_up defaults to (0, 0, 1) like the reference when R or t is given; a camera built from intrinsics alone defaults to
-    (0, -1, 0) (image y points down, so "up" is -y): the reference default degenerates there (module docstring)."""
-
-    def __init__(self, intrinsic_matrix, distortion_coeffs=None, R=None, t=None, world_up=None):
-        if world_up is None:
-            world_up = (0, -1, 0) if R is None and t is None else (0, 0, 1)
-        self.R = np.asarray(np.eye(3) if R is None else R, np.float32)
-        self.t = np.asarray(np.zeros(3) if t is None else t, np.float32)
-        self.intrinsic_matrix = np.asarray(intrinsic_matrix, np.float32)
-        self.distortion_coeffs = None if distortion_coeffs is None else np.asarray(distortion_coeffs, np.float32)
-        self.world_up = np.asarray(world_up)
-        if self.R.shape != (3, 3) or self.t.shape != (3,) or self.intrinsic_matrix.shape != (3, 3):
-            raise ValueError('R and intrinsic_matrix must be 3x3, t a 3-vector')
-        if not np.allclose(self.intrinsic_matrix[2, :], [0, 0, 1]):
-            raise ValueError(f'bottom row of the intrinsic matrix must be (0, 0, 1), got {self.intrinsic_matrix[2, :]}')
-        if self.distortion_coeffs is not None and self.distortion_coeffs.shape != (5,):
-            raise ValueError(f'distortion_coeffs must be None or 5 values (k1, k2, p1, p2, k3), got '
-                             f'{self.distortion_coeffs.shape}')
-
-    def copy(self) -> 'Camera':
-        return copy.deepcopy(self)
-
-    # cameralib.py:133-156
-    def world_to_camera(self, points):
-        return (np.asarray(points, np.float32) - self.t) @ self.R.T
-
-    def camera_to_world(self, points):
-        return np.asarray(points, np.float32) @ np.linalg.inv(self.R).T + self.t
-
-    def camera_to_image_undistorted(self, points):
-        """camera_to_image (:126-131) of a camera without distortion coefficients."""
-        assert self.distortion_coeffs is None
-        projected = points[:, :2] / points[:, 2:]
-        return projected @ self.intrinsic_matrix[:2, :2].T + self.intrinsic_matrix[:2, 2]
-
-    def image_to_camera(self, points):
-        p = undistort_points(points, self.intrinsic_matrix, self.distortion_coeffs)
-        return np.concatenate([p, np.ones_like(p[:, :1])], axis=1)        # convertPointsToHomogeneous, depth 1
-
-    def image_to_world(self, points):
-        return self.camera_to_world(self.image_to_camera(points))
-
-    # cameralib.py:167-228
-    def turn_towards(self, target_image_point):
-        target_world_point = self.image_to_world(np.asarray([target_image_point], np.float64))[0]
-        new_z = target_world_point - self.t
-        new_z = new_z / np.linalg.norm(new_z)
-        new_x = np.cross(new_z, self.world_up)
-        new_x = new_x / np.linalg.norm(new_x)
-        new_y = np.cross(new_z, new_x)
-        self.R = np.vstack([new_x, new_y, new_z]).astype(np.float32)
-
-    def undistort(self):
-        self.distortion_coeffs = None
-
-    def square_pixels(self):
-        fx, fy = self.intrinsic_matrix[0, 0], self.intrinsic_matrix[1, 1]
-        fmean = 0.5 * (fx + fy)
-        multiplier = np.array([[fmean / fx, 0, 0], [0, fmean / fy, 0], [0, 0, 1]])     # float64, so K becomes float64
-        self.intrinsic_matrix = multiplier @ self.intrinsic_matrix
-
-    def zoom(self, factor):
-        self.intrinsic_matrix[:2, :2] *= np.expand_dims(factor, -1)
-
-    def center_principal_point(self, imshape):
-        self.intrinsic_matrix[:2, 2] = [imshape[1] / 2, imshape[0] / 2]
-
-    # cameralib.py:95-98, 191-192
-    def rotate(self, yaw=0, pitch=0, roll=0):
-        """R <- euler2mat(yaw, pitch, roll, 'ryxz')^T R (angles in radians): the camera turns by yaw about its y axis, then
-        pitch about its new x axis, then roll about its new optical axis.  R becomes float64, as in the reference."""
-        self.R = euler2mat_ryxz(yaw, pitch, roll).T @ self.R
-
-    def horizontal_flip(self):
-        self.R[0] *= -1
-
-
-def euler2mat_ryxz(yaw, pitch, roll) -> np.ndarray:
-    """transforms3d.euler.euler2mat(yaw, pitch, roll, 'ryxz') (transforms3d is not a dependency), float64 [3, 3].
-
-    'ryxz' is the rotating-frame convention with axes y, x, z: the matrix is Ry(yaw) @ Rx(pitch) @ Rz(roll) with the
-    right-handed elementary rotations Rx(a) = [[1, 0, 0], [0, c, -s], [0, s, c]], Ry(a) = [[c, 0, s], [0, 1, 0], [-s, 0, c]],
-    Rz(a) = [[c, -s, 0], [s, c, 0], [0, 0, 1]].  Its entries are written as transforms3d's euler2mat writes them for this axis
-    code (first axis z, no parity, no repetition, rotating frame: i, j, k = 2, 0, 1 with the first and last angle swapped),
-    so roll alone gives exactly cos(roll) and sin(roll)."""
-    si, sj, sk = math.sin(roll), math.sin(pitch), math.sin(yaw)
-    ci, cj, ck = math.cos(roll), math.cos(pitch), math.cos(yaw)
-    cc, cs, sc, ss = ci * ck, ci * sk, si * ck, si * sk
-    m = np.eye(3)
-    m[2, 2] = cj * ck
-    m[2, 0] = sj * sc - cs
-    m[2, 1] = sj * cc + ss
-    m[0, 2] = cj * sk
-    m[0, 0] = sj * ss + cc
-    m[0, 1] = sj * cs - sc
-    m[1, 2] = -sj
-    m[1, 0] = cj * si
-    m[1, 1] = cj * ci
-    return m
-
-
-def look_at_box(camera: Camera, box: Sequence[float], side: int = 256) -> Camera:
-    """The virtual camera of a crop: reference cameralib.look_at_box (src/cameralib.py:337-358), step by step -- turn towards
-    the box centre, undistort, square the pixels, zoom so that the box's longer side (measured between the two side midpoints,
-    through the world) spans `side` pixels, centre the principal point.  This is the reference's stand-alone helper; the
-    training loader's variant (data_loading.py:33-58: the norm of the side-point difference, a 1.05 box expansion for 3DHP,
-    augmentation flags) is not what is restated here."""
-    cam = camera.copy()
-    box = np.asarray(box, np.float64)
-    center_point = box[:2] + box[2:] / 2
-    delta_x = np.array([box[2] / 2, 0])
-    delta_y = np.array([0, box[3] / 2])
-    if box[2] < box[3]:
-        sidepoints = np.stack([center_point - delta_y, center_point + delta_y])
-    else:
-        sidepoints = np.stack([center_point - delta_x, center_point + delta_x])
-    world_sidepoints = camera.image_to_world(sidepoints)
-    cam.turn_towards(center_point)
-    cam.undistort()
-    cam.square_pixels()
-    cam_sidepoints = cam.camera_to_image_undistorted(cam.world_to_camera(world_sidepoints))
-    if box[2] < box[3]:
-        crop_side = np.abs(cam_sidepoints[0, 1] - cam_sidepoints[1, 1])
-    else:
-        crop_side = np.abs(cam_sidepoints[0, 0] - cam_sidepoints[1, 0])
-    cam.zoom(side / crop_side)
-    cam.center_principal_point((side, side))
-    return cam
 
 
 class CropParams(NamedTuple):
@@ -257,7 +92,7 @@ def crop_params(cameras, boxes, frame_index, side: int = 256) -> CropParams:
     :294-306: partial_homography = old.R inv(new.R) inv(new.K), float64), as the test at :272 sends it there.
     rot_to_orig_cam = orig.R virt.R^T and rot_to_world = virt.R^T (data_loading.py:110-111).
     cameras=None: the axis-aligned square crop of preprocess.box_homography, rotations I."""
-    return _frame_params(cameras, boxes, frame_index, side)[0]
+    return _frame_params_and_cameras(cameras, boxes, frame_index, side)[0]
 
 
 class PlacementParams(NamedTuple):
@@ -279,16 +114,12 @@ def placement_params(cameras, boxes, frame_index, side: int = 256) -> PlacementP
     the keypoint mode follows the warp mode (an undistorted camera or cameras=None: the crop's warp homography, which maps crop
     pixels to frame pixels; a camera with coefficients: its K and distortion for project_points).  cameras=None has no
     virtual camera: inv_intrinsics is zero (no metric placement) and the rotations are I."""
-    return _frame_params(cameras, boxes, frame_index, side)[1]
-
-
-def _frame_params(cameras, boxes, frame_index, side: int):
-    """(CropParams, PlacementParams) of n crops, each virtual camera computed once."""
-    return _frame_params_and_cameras(cameras, boxes, frame_index, side)[:2]
+    return _frame_params_and_cameras(cameras, boxes, frame_index, side)[1]
 
 
 def _frame_params_and_cameras(cameras, boxes, frame_index, side: int):
-    """(CropParams, PlacementParams, the look_at_box camera of every crop (None without cameras))."""
+    """(CropParams, PlacementParams, the look_at_box camera of every crop (None without cameras)) of n crops, each virtual
+    camera computed once."""
     boxes = np.asarray(boxes, np.float64).reshape(-1, 4)
     n = len(boxes)
     fi = np.asarray(frame_index, np.int64).reshape(n)
@@ -353,180 +184,10 @@ def pack_placements(params: PlacementParams) -> np.ndarray:
     return np.frombuffer(bytearray(rec), np.uint8).reshape(n, C.sizeof(_lib.MetroPlacement))
 
 
-def _upload(a: np.ndarray, device: torch.device) -> torch.Tensor:
-    """Host array -> device tensor without a host synchronisation (pinned staging, non-blocking copy)."""
-    return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(device, non_blocking=True)
-
-
-# ---- frames in other pixel formats: metro_warp_crops_frames_planes converts each tap as the warp reads it ----
-
-PIXEL_FORMATS = {'rgb': _lib.METRO_PIX_RGB, 'bgr': _lib.METRO_PIX_BGR, 'nv12': _lib.METRO_PIX_NV12,
-                 'i420': _lib.METRO_PIX_I420}
-COLOR_MATRICES = {'bt601': _lib.METRO_YUV_BT601, 'bt709': _lib.METRO_YUV_BT709}
-_LAYOUTS = {
-    'rgb': 'a uint8 [H, W, 3] tensor or array',
-    'bgr': 'a uint8 [H, W, 3] tensor or array',
-    'nv12': 'a uint8 [H*3/2, W] tensor or array (Y rows, then interleaved UV rows) or a tuple (Y [H, W], UV [H/2, W/2, 2] '
-            'or [H/2, W]), H and W even, rows of element stride 1',
-    'i420': 'a contiguous uint8 [H*3/2, W] tensor or array (Y, then U and V at W/2 bytes per row) or a tuple (Y [H, W], '
-            'U [H/2, W/2], V [H/2, W/2]) whose U and V share one row stride, H and W even, rows of element stride 1',
-}
-
-
-class _Planar(NamedTuple):
-    """One frame for metro_warp_crops_frames_planes: its plane views (host or device) and the descriptor's fields."""
-    planes: Tuple[torch.Tensor, ...]
-    h: int
-    w: int
-    stride: Tuple[int, int]
-    format: int
-    matrix: int
-
-
-class _FrameSet(NamedTuple):
-    """Frames in a pixel format other than 'rgb' whose layouts are checked, as given (host or device data)."""
-    items: list
-    pixel_format: str
-    color_matrix: str
-
-
-def _frame_set(frames, pixel_format: str = 'rgb', color_matrix: str = 'bt601'):
-    """Checks pixel_format and color_matrix and, for any format but 'rgb', the layout of every frame, before any device work.
-    'rgb' frames come back as given, for the unchanged metro_warp_crops_frames_u8 path; the others as a _FrameSet.
-    A YUV frame is one tensor / array (2-D) or a tuple of its planes; a list holds many frames."""
-    if isinstance(frames, _FrameSet):
-        return frames
-    if pixel_format not in PIXEL_FORMATS:
-        raise ValueError(f"pixel_format must be 'rgb', 'bgr', 'nv12' or 'i420', got {pixel_format!r}")
-    if color_matrix not in COLOR_MATRICES:
-        raise ValueError(f"color_matrix must be 'bt601' or 'bt709', got {color_matrix!r}")
-    if pixel_format in ('rgb', 'bgr') and color_matrix != 'bt601':
-        raise ValueError(f"color_matrix={color_matrix!r} applies to 'nv12' and 'i420' frames, not to {pixel_format!r} ones")
-    if pixel_format == 'rgb':
-        return frames
-    if pixel_format == 'bgr':
-        single = isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 3
-    else:
-        single = isinstance(frames, (torch.Tensor, np.ndarray, tuple))
-    items = [frames] if single else list(frames)
-    if not items:
-        raise ValueError('no frames')
-    if len(items) > _lib.METRO_MAX_FRAMES:
-        raise ValueError(f'{len(items)} frames: at most {_lib.METRO_MAX_FRAMES} per call')
-    for k, f in enumerate(items):
-        _planar(k, f, pixel_format, color_matrix)
-    return _FrameSet(items, pixel_format, color_matrix)
-
-
-def _planar(k: int, f, pixel_format: str, color_matrix: str) -> _Planar:
-    """The plane views and descriptor fields of frame k (metadata only: no copy, no device work); ValueError on a bad layout."""
-    def bad(what):
-        return ValueError(f'frame {k}: {what}; pixel_format={pixel_format!r} takes {_LAYOUTS[pixel_format]}')
-
-    def plane(t, name, ndim):
-        t = torch.from_numpy(t) if isinstance(t, np.ndarray) else t
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != ndim:
-            raise bad(f'{name} is {getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))}')
-        if pixel_format != 'bgr' and (t.stride(-1) != 1 or (ndim >= 2 and t.stride(0) < t.shape[1] * t.stride(1))):
-            raise bad(f'{name} has strides {t.stride()}')
-        return t
-
-    def even(h, w):
-        if h % 2 or w % 2:
-            raise bad(f'{h} x {w} pixels (4:2:0 frames have an even height and width)')
-
-    fmt, matrix = PIXEL_FORMATS[pixel_format], COLOR_MATRICES[color_matrix]
-    if pixel_format == 'bgr':
-        t = plane(f, 'the frame', 3)
-        if t.shape[2] != 3:
-            raise bad(f'the frame is {tuple(t.shape)}')
-        return _Planar((t,), t.shape[0], t.shape[1], (t.stride(0), 0), fmt, matrix)
-    n_planes = 2 if pixel_format == 'nv12' else 3
-    if isinstance(f, tuple):
-        if len(f) != n_planes:
-            raise bad(f'a tuple of {len(f)} planes')
-        y = plane(f[0], 'the Y plane', 2)
-        h, w = y.shape
-        even(h, w)
-        if pixel_format == 'nv12':
-            uv = f[1]
-            uv = plane(uv, 'the UV plane', getattr(uv, 'ndim', 2))
-            if tuple(uv.shape) not in ((h // 2, w // 2, 2), (h // 2, w)) or (uv.dim() == 3 and uv.stride(1) != 2):
-                raise bad(f'the UV plane is {tuple(uv.shape)} with strides {uv.stride()} for a {h} x {w} Y plane')
-            planes = (y, uv)
-        else:
-            u, v = plane(f[1], 'the U plane', 2), plane(f[2], 'the V plane', 2)
-            if tuple(u.shape) != (h // 2, w // 2) or tuple(v.shape) != (h // 2, w // 2) or u.stride(0) != v.stride(0):
-                raise bad(f'the U and V planes are {tuple(u.shape)} and {tuple(v.shape)} with row strides {u.stride(0)} and '
-                          f'{v.stride(0)} for a {h} x {w} Y plane')
-            planes = (y, u, v)
-        if len({p.device for p in planes}) != 1:
-            raise bad(f'the planes lie on {sorted({str(p.device) for p in planes})}')
-        return _Planar(planes, h, w, (y.stride(0), planes[1].stride(0)), fmt, matrix)
-    t = plane(f, 'the frame', 2)
-    rows, w = t.shape
-    if rows % 3:
-        raise bad(f'the frame is {tuple(t.shape)}: {rows} rows are not H*3/2')
-    h = rows * 2 // 3
-    even(h, w)
-    if pixel_format == 'nv12':
-        return _Planar((t[:h], t[h:]), h, w, (t.stride(0), t.stride(0)), fmt, matrix)
-    if not t.is_contiguous():
-        raise bad(f'the frame has strides {t.stride()}')
-    flat, q = t.reshape(-1), h * w // 4
-    return _Planar((t[:h], flat[h * w:h * w + q].view(h // 2, w // 2), flat[h * w + q:].view(h // 2, w // 2)), h, w,
-                   (w, w // 2), fmt, matrix)
-
-
-def _device_frame_set(fs: _FrameSet, device: torch.device):
-    """-> [_Planar] on the device: device frames as they are (a BGR one packed if it is not), host frames uploaded (pinned,
-    non-blocking) at their own byte size."""
-    def to_device(k, a):
-        if isinstance(a, tuple):
-            return tuple(to_device(k, p) for p in a)
-        t = torch.from_numpy(a) if isinstance(a, np.ndarray) else a
-        if not t.is_cuda:
-            return _upload(t.numpy(), device)
-        if t.device != device:
-            raise ValueError(f'frame {k} is on {t.device}, the call runs on {device}')
-        if fs.pixel_format == 'bgr' and (t.stride(2) != 1 or t.stride(1) != 3 or t.stride(0) < 3 * t.shape[1]):
-            t = t.contiguous()
-        return t
-    return [_planar(k, to_device(k, f), fs.pixel_format, fs.color_matrix) for k, f in enumerate(fs.items)]
-
-
-def _first_frame(frames):
-    """The first frame (or plane) of `frames`, from which a call without device boxes takes its device."""
-    f = frames.items if isinstance(frames, _FrameSet) else frames
-    while isinstance(f, (list, tuple)) and f:
-        f = f[0]
-    return f if isinstance(f, (torch.Tensor, np.ndarray)) else None
-
-
-def _device_frames(frames, device: torch.device):
-    if isinstance(frames, _FrameSet):
-        return _device_frame_set(frames, device)
-    if isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 3:
-        frames = [frames]
-    out = []
-    for k, f in enumerate(frames):
-        if isinstance(f, np.ndarray):
-            f = torch.from_numpy(f)
-        if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3:
-            raise ValueError(f'frame {k} must be a uint8 [H, W, 3] tensor or array, got '
-                             f'{getattr(f, "dtype", type(f))} {tuple(getattr(f, "shape", ()))}')
-        if f.is_cuda and f.device != device:
-            raise ValueError(f'frame {k} is on {f.device}, the call runs on {device}')
-        if not f.is_cuda:
-            f = _upload(f.numpy(), device)
-        if f.stride(2) != 1 or f.stride(1) != 3 or f.stride(0) < 3 * f.shape[1]:
-            f = f.contiguous()
-        out.append(f)
-    if not out:
-        raise ValueError('no frames')
-    if len(out) > _lib.METRO_MAX_FRAMES:
-        raise ValueError(f'{len(out)} frames: at most {_lib.METRO_MAX_FRAMES} per call')
-    return out
+def _check_frame_index(fi: np.ndarray, n_frames: int) -> None:
+    """Host frame indices against the frame count, before any launch."""
+    if len(fi) and (fi.min() < 0 or fi.max() >= n_frames):
+        raise ValueError(f'frame_index must lie in [0, {n_frames}), got [{fi.min()}, {fi.max()}]')
 
 
 def warp_frames(frames, params: CropParams, frame_index, side: int = 256, device: Optional[torch.device] = None,
@@ -550,8 +211,7 @@ def warp_frames(frames, params: CropParams, frame_index, side: int = 256, device
     dev_frames = _device_frames(frames, device)
     n = len(params.mode)
     fi = np.asarray(frame_index, np.int64).reshape(n)
-    if n and (fi.min() < 0 or fi.max() >= len(dev_frames)):
-        raise ValueError(f'frame_index must lie in [0, {len(dev_frames)}), got [{fi.min()}, {fi.max()}]')
+    _check_frame_index(fi, len(dev_frames))
     if out is None:
         out = torch.empty((n, side, side, 3), dtype=torch.float32, device=device)
     if n == 0:
@@ -631,36 +291,13 @@ def view_set(views) -> Views:
     return Views(roll, zoom, flip)
 
 
-def _roll_rad(roll_deg: float) -> float:
-    return float(roll_deg) * math.pi / 180
-
-
 def _is_identity(vs: Views, v: int) -> bool:
     return vs.roll_deg[v] == 0 and vs.zoom[v] == 1 and not vs.flip[v]
 
 
-def view_camera(camera: Camera, roll_deg: float, zoom: float, flip: bool) -> Camera:
-    """A view of a look_at_box camera, as the reference's loader builds it under --test-aug (data_loading.py:60-68, 77):
-    cam.zoom(zoom), cam.rotate(roll=roll), then cam.horizontal_flip() when flip."""
-    cam = camera.copy()
-    cam.zoom(zoom)
-    cam.rotate(roll=_roll_rad(roll_deg))
-    if flip:
-        cam.horizontal_flip()
-    return cam
-
-
-def _square_crop_camera(side: int) -> Camera:
-    """cameras=None: the square crop as a camera of principal point (side/2, side/2), unit focal length (roll, zoom and flip
-    are image-plane similarities about that point whatever the focal length), R = I, K in float64 like look_at_box's."""
-    cam = Camera(np.eye(3))
-    cam.intrinsic_matrix = np.array([[1., 0, side / 2], [0, 1., side / 2], [0, 0, 1]])
-    return cam
-
-
 def view_params(cameras, boxes, frame_index, views, side: int = 256):
     """(CropParams, PlacementParams) of n * V crops, box-major (row i * V + v): the host restatement of metro_expand_views,
-    _frame_params' formulas with each view camera (view_camera of the box's look_at_box camera) in place of the look_at_box
+    _frame_params_and_cameras' formulas with each view camera (view_camera of the box's look_at_box camera) in place of the look_at_box
     one.  The identity view keeps the box's own records (its bits without views).  cameras=None: _square_crop_camera is the
     look_at_box camera and the square crop's homography its frame: homography = square's . K_base inv(K R), the rotations
     back R^T of the view, inv_intrinsics 0.  Tests use it as the reference of the device expansion; the product path does
@@ -706,7 +343,7 @@ VIEW_BASE_DTYPE = np.dtype(_lib.MetroViewBase)
 
 def pack_view_bases(cameras, boxes, frame_index, side: int = 256) -> np.ndarray:
     """The MetroViewBase records (include/metro_hip.h) of n boxes as a byte array [n, 576]: one look_at_box per box (through
-    _frame_params, whose records are the identity view's), the rest filled column-wise, without a per-record ctypes loop."""
+    _frame_params_and_cameras, whose records are the identity view's), the rest filled column-wise, without a per-record ctypes loop."""
     boxes = np.asarray(boxes, np.float64).reshape(-1, 4)
     n = len(boxes)
     fi = np.asarray(frame_index, np.int64).reshape(n)
@@ -755,19 +392,6 @@ def _expand_views(bases, vs: Views, side: int, device: torch.device):
     check(_lib.load().metro_expand_views(C.c_void_p(d_bases.data_ptr()), n, view_table(vs), nv, side,
                                          C.c_void_p(crops.data_ptr()), C.c_void_p(places.data_ptr()), C.c_void_p(stream)),
           'metro_expand_views')
-    return crops, places
-
-
-def _warp_views(frames, cameras, boxes, fi, vs: Views, side: int, device: torch.device):
-    """Per-box host geometry, the expansion and ONE warp launch of the n V crops -> (crops [n V, side, side, 3], placement
-    records [n V, 208])."""
-    dev_frames = _device_frames(frames, device)
-    n = len(boxes)
-    if n and (fi.min() < 0 or fi.max() >= len(dev_frames)):
-        raise ValueError(f'frame_index must lie in [0, {len(dev_frames)}), got [{fi.min()}, {fi.max()}]')
-    crop_recs, places = _expand_views(pack_view_bases(cameras, boxes, fi, side), vs, side, device)
-    crops = torch.empty((n * len(vs.zoom), side, side, 3), dtype=torch.float32, device=device)
-    _launch_warp(dev_frames, crop_recs, len(crops), side, crops, device)
     return crops, places
 
 
@@ -820,11 +444,13 @@ def pack_frame_cameras(cameras, n_frames: Optional[int] = None) -> np.ndarray:
 
 class _DeviceBoxes:
     """Boxes on the device for metro_look_at_boxes: fp64 [n, 4], and the frame indices either as host int64 [n] (checked
-    against the frame count before any launch) or as a device int32 [n] tensor (checked by the kernel's status)."""
-    __slots__ = ('boxes', 'host_fi', 'device_fi')
+    against the frame count before any launch) or as a device int32 [n] tensor (checked by the kernel's status).
+    frame_status: None until _warp_views launched metro_look_at_boxes on these boxes, then (status int32 [1], n_frames),
+    which the call reads in its synchronisation (_synchronise)."""
+    __slots__ = ('boxes', 'host_fi', 'device_fi', 'frame_status')
 
     def __init__(self, boxes: torch.Tensor, host_fi: Optional[np.ndarray], device_fi: Optional[torch.Tensor]):
-        self.boxes, self.host_fi, self.device_fi = boxes, host_fi, device_fi
+        self.boxes, self.host_fi, self.device_fi, self.frame_status = boxes, host_fi, device_fi, None
 
     def __len__(self) -> int:
         return int(self.boxes.shape[0])
@@ -904,28 +530,13 @@ def _checked_device_fi(db: _DeviceBoxes, n_frames: int, device: torch.device) ->
     """The device frame indices of db; host indices are checked here, before any launch, and uploaded."""
     if db.device_fi is not None:
         return db.device_fi
-    fi = db.host_fi
-    if len(fi) and (fi.min() < 0 or fi.max() >= n_frames):
-        raise ValueError(f'frame_index must lie in [0, {n_frames}), got [{fi.min()}, {fi.max()}]')
-    return _upload(fi.astype(np.int32), device)
+    _check_frame_index(db.host_fi, n_frames)
+    return _upload(db.host_fi.astype(np.int32), device)
 
 
 def _raise_on_bad_frames(n_out: int, n: int, n_frames: int) -> None:
     if n_out:
         raise ValueError(f'frame_index must lie in [0, {n_frames}): {n_out} of {n} device frame indices lie outside')
-
-
-def _warp_device_boxes(frames, cameras, db: _DeviceBoxes, vs: Views, side: int, device: torch.device):
-    """_warp_views with the geometry on the device: metro_look_at_boxes, the expansion and ONE warp launch, no per-box host
-    work -> (crops [n V, side, side, 3], placement records [n V, 208], (status int32 [1], n_frames)).  The status is read by
-    the caller after its synchronisation (_raise_on_bad_frames)."""
-    dev_frames = _device_frames(frames, device)
-    n_frames = len(dev_frames)
-    bases, status = _look_at_boxes(cameras, db.boxes, _checked_device_fi(db, n_frames, device), n_frames, side, device)
-    crop_recs, places = _expand_views(bases, vs, side, device)
-    crops = torch.empty((len(db) * len(vs.zoom), side, side, 3), dtype=torch.float32, device=device)
-    _launch_warp(dev_frames, crop_recs, len(crops), side, crops, device)
-    return crops, places, (status, n_frames)
 
 
 def _merge_views(poses, keypoints, z, places, mirror, n: int, nv: int, spread: bool):
@@ -947,6 +558,89 @@ _ROT_TO_ORIG_CAM = _lib.MetroPlacement.rot_to_orig_cam.offset // 4      # float 
 _ROT_TO_WORLD = _lib.MetroPlacement.rot_to_world.offset // 4
 
 
+def _warp_views(frames, cameras, boxes, fi, vs: Views, side: int, device: torch.device):
+    """The frames on the device, one MetroViewBase record per box (host boxes with their frame indices fi: pack_view_bases,
+    NumPy per box; _DeviceBoxes, fi None: metro_look_at_boxes, no per-box host work), the expansion and ONE warp launch of the
+    n V crops -> (crops [n V, side, side, 3], placement records [n V, 208]).  Host frame indices are checked here, before
+    any launch; metro_look_at_boxes' check of device ones is left in boxes.frame_status.  No launch for n = 0."""
+    dev_frames = _device_frames(frames, device)
+    n, n_frames = len(boxes), len(dev_frames)
+    if n == 0:
+        return (torch.empty((0, side, side, 3), dtype=torch.float32, device=device),
+                torch.empty((0, C.sizeof(_lib.MetroPlacement)), dtype=torch.uint8, device=device))
+    if isinstance(boxes, _DeviceBoxes):
+        bases, status = _look_at_boxes(cameras, boxes.boxes, _checked_device_fi(boxes, n_frames, device), n_frames, side, device)
+        boxes.frame_status = (status, n_frames)
+    else:
+        _check_frame_index(fi, n_frames)
+        bases = pack_view_bases(cameras, boxes, fi, side)
+    crop_recs, places = _expand_views(bases, vs, side, device)
+    crops = torch.empty((n * len(vs.zoom), side, side, 3), dtype=torch.float32, device=device)
+    _launch_warp(dev_frames, crop_recs, len(crops), side, crops, device)
+    return crops, places
+
+
+def _synchronise(bad: Optional[torch.Tensor], boxes) -> int:
+    """The one read of a call, after everything is enqueued: the finite screen folded on the device (`bad`; None: not asked for)
+    and, for _DeviceBoxes, their frame status in one transfer -> the number of non-finite crops.  ValueError for a device
+    frame index outside its range.  Host boxes and no screen: nothing to read, no synchronisation."""
+    if not isinstance(boxes, _DeviceBoxes):
+        return int(bad.item()) if bad is not None else 0
+    status, n_frames = boxes.frame_status
+    words = status.to(torch.int64) if bad is None else torch.cat([status.to(torch.int64), bad.reshape(1)])
+    words = words.tolist()
+    _raise_on_bad_frames(words[0], len(boxes), n_frames)
+    return words[1] if bad is not None else 0
+
+
+class _Call(NamedTuple):
+    """The arguments estimate_pose_in_frames and locate_poses_in_frames share, checked."""
+    frames: object               # as _frame_set returns them
+    boxes: object                # host boxes float64 [n, 4], or _DeviceBoxes (device geometry, n >= 1)
+    fi: Optional[np.ndarray]     # int64 [n]: the frame of each host box; None with _DeviceBoxes, which hold their own
+    vs: Views                    # views=None: the identity view
+    precision: str
+    check_finite: bool
+
+
+def _checked_call(frames, boxes, frame_index, coords, views, geometry, precision, check_finite, pixel_format,
+                  color_matrix) -> _Call:
+    """Every check that needs neither the model file nor, for host boxes, a device; the environment's defaults."""
+    frames = _frame_set(frames, pixel_format, color_matrix)
+    geo = _geometry_of(geometry, boxes)
+    if coords not in COORDS:
+        raise ValueError(f"coords must be 'crop', 'camera' or 'world', got {coords!r}")
+    vs = view_set(1 if views is None else views)
+    if coords == 'crop' and len(vs.zoom) > 1:
+        raise ValueError(f"coords='crop' takes one view: the {len(vs.zoom)} views have different virtual cameras")
+    if precision is None:
+        precision = os.environ.get('METRO_PRECISION', 'f16')
+    if check_finite is None:
+        check_finite = os.environ.get('METRO_CHECK_FINITE', '1') != '0'
+    if geo == 'device':
+        db = _device_boxes(boxes, frame_index, _call_device(boxes, frames))
+        if len(db):
+            return _Call(frames, db, None, vs, precision, check_finite)
+        boxes, frame_index = np.zeros((0, 4)), None
+    boxes = np.asarray(_host_array(boxes), np.float64)
+    if boxes.ndim != 2 or boxes.shape[1] != 4:
+        raise ValueError(f'boxes must be [n, 4] (x, y, w, h), got {boxes.shape}')
+    n = len(boxes)
+    fi = np.zeros(n, np.int64) if frame_index is None else np.asarray(_host_array(frame_index), np.int64).reshape(n)
+    return _Call(frames, boxes, fi, vs, precision, check_finite)
+
+
+def _call_device(boxes, frames) -> torch.device:
+    """The device of a call: the boxes' for CUDA boxes and _DeviceBoxes, else the first frame's (or the current one)."""
+    from metro_pose3d_amd.inference import _resolve_device
+    if isinstance(boxes, _DeviceBoxes):
+        boxes = boxes.boxes
+    if isinstance(boxes, torch.Tensor) and boxes.is_cuda:
+        return _resolve_device(boxes)
+    first = _first_frame(frames)
+    return _resolve_device(first if isinstance(first, torch.Tensor) else torch.empty(0))
+
+
 def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index=None, coords: str = 'camera',
                             precision: Optional[str] = None, check_finite: Optional[bool] = None, views=None,
                             geometry: str = 'auto', pixel_format: str = 'rgb', color_matrix: str = 'bt601'):
@@ -962,96 +656,45 @@ def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index
                 det <= 0);
       'world'   rotation by rot_to_world only (root-relative poses carry no translation; volumetric.py:206-208 adds cam_loc
                 to absolute ones).
-    One enqueue chain on the current stream of the local device: frame and parameter uploads (pinned, non-blocking), one warp
-    launch, estimate_pose's forward in <= 256-crop chunks on its cached engine with its finite screen (its one stream
-    synchronisation), then metro_to_orig_cam.  Runs on the local device only (estimate_pose's shard=False): sharding across
-    ranks is not supported here.
-    views: None (one crop per box, the path above) or test-time views (view_set: an int V for the default set, or
-    (roll_deg, zoom, flip) triples): the host geometry stays per box, metro_expand_views derives the n V crop records on the
-    device, one warp launch cuts them, estimate_pose runs on the n V crops, metro_to_orig_cam rotates each view back (mirroring
-    flipped views' joints) and metro_merge_views averages the views of each box.  coords='crop' takes one view only (the views
-    have different virtual cameras); views=1 returns the bits of views=None.
-    geometry: where the per-box crop geometry is computed.  'host': look_at_box in NumPy per box (boxes are host data);
+    One enqueue chain on the current stream of the local device, the same for every kind of call: frame uploads (pinned,
+    non-blocking), one record per box, metro_expand_views (the n V crop and placement records, written on the device), one
+    warp launch, estimate_pose's forward on the n V crops in <= 256-crop chunks on its cached engine with its finite screen (its
+    one stream synchronisation), metro_to_orig_cam on each view (mirroring flipped views' joints), then metro_merge_views,
+    which averages the views of each box.  Runs on the local device only (estimate_pose's shard=False): sharding across ranks
+    is not supported here.
+    views: None (one crop per box: the identity view, whose records metro_expand_views copies and whose merge is the view
+    itself, so views=None and views=1 are one path and one answer) or test-time views (view_set: an int V for the default
+    set, or (roll_deg, zoom, flip) triples).  coords='crop' takes one view only (the views have different virtual cameras)
+    and returns the forward's poses as they are.
+    geometry: where the per-box record is computed.  'host': look_at_box in NumPy per box (boxes are host data), one upload;
     'device': one metro_look_at_boxes launch writes the per-box records on the GPU (boxes a float32 / float64 CUDA tensor
-    [n, 4], or host boxes uploaded once; frame_index host data or a CUDA integer tensor), then metro_expand_views with the
-    identity view when views=None: no per-box host work and no synchronisation before the forward; the records agree with the
-    host's to a few fp32 ulp (include/metro_hip.h).  'auto' (default): 'device' for CUDA boxes, else 'host'.  With device
-    boxes the call runs on the boxes' device; a device frame index outside [0, n_frames) raises ValueError (read from the
-    kernel's status after the call's synchronisation).
+    [n, 4], or host boxes uploaded once; frame_index host data or a CUDA integer tensor): no per-box host work and no
+    synchronisation before the forward; the records agree with the host's to a few fp32 ulp (include/metro_hip.h).  'auto'
+    (default): 'device' for CUDA boxes, else 'host'.  With device boxes the call runs on the boxes' device; a device frame
+    index outside [0, n_frames) raises ValueError (read from the kernel's status after the call's synchronisation).
     pixel_format: 'rgb' (default), 'bgr', 'nv12' or 'i420', with color_matrix 'bt601' (default) or 'bt709' for the YUV
     formats; the layouts are warp_frames'.  Frames other than 'rgb' go through metro_warp_crops_frames_planes, which
     converts each tap as the warp reads it: the crops are byte for byte those of the RGB frame that OpenCV's integer
     cvtColor(COLOR_YUV2RGB_NV12 / _I420) rule gives (not ffmpeg's swscale, which rounds differently), with a black border;
     no RGB frame is written, and host frames upload at their own size (1.5 bytes per pixel for YUV)."""
-    from metro_pose3d_amd.inference import _engine_for, _resolve_device, estimate_pose
-    frames = _frame_set(frames, pixel_format, color_matrix)
-    geo = _geometry_of(geometry, boxes)
-    if coords not in ('crop', 'camera', 'world'):
-        raise ValueError(f"coords must be 'crop', 'camera' or 'world', got {coords!r}")
-    vs = None if views is None else view_set(views)
-    if vs is not None and coords == 'crop' and len(vs.zoom) > 1:
-        raise ValueError(f"coords='crop' takes one view: the {len(vs.zoom)} views have different virtual cameras")
-    if precision is None:
-        precision = os.environ.get('METRO_PRECISION', 'f16')
-    first = _first_frame(frames)
-    if geo == 'device':
-        device = _geometry_device(boxes, first)
-        db = _device_boxes(boxes, frame_index, device)
-        if len(db):
-            return _estimate_pose_views(frames, db, model_path, cameras, None, coords, precision, check_finite,
-                                        vs if vs is not None else view_set(1), device)
-        boxes, frame_index = np.zeros((0, 4)), None
-    boxes = np.asarray(_host_array(boxes), np.float64)
-    if boxes.ndim != 2 or boxes.shape[1] != 4:
-        raise ValueError(f'boxes must be [n, 4] (x, y, w, h), got {boxes.shape}')
-    n = len(boxes)
-    fi = np.zeros(n, np.int64) if frame_index is None else np.asarray(_host_array(frame_index), np.int64).reshape(n)
-    device = _resolve_device(first if isinstance(first, torch.Tensor) else torch.empty(0))
-    if vs is not None and n:
-        return _estimate_pose_views(frames, boxes, model_path, cameras, fi, coords, precision, check_finite, vs, device)
-    with torch.cuda.device(device):
-        side = _engine_for(model_path, precision, device, max(n, 1)).spec.proc_side
-        params = crop_params(cameras, boxes, fi, side)
-        crops = warp_frames(frames, params, fi, side, device=device)
-        poses, edges, names = estimate_pose(crops, model_path, precision=precision, check_finite=check_finite, shard=False)
-        if coords == 'crop' or n == 0:
-            return poses, edges, names
-        sk = _engine_for(model_path, precision, device, max(n, 1)).spec.skeleton
-        rot = _upload((params.rot_to_orig_cam if coords == 'camera' else params.rot_to_world).reshape(n, 9), device)
-        mirror = _upload(np.asarray(sk.out_mirror, np.int32), device)
-        out = torch.empty_like(poses)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        check(_lib.load().metro_to_orig_cam(C.c_void_p(poses.data_ptr()), C.c_void_p(rot.data_ptr()),
-                                            C.c_void_p(mirror.data_ptr()), C.c_void_p(out.data_ptr()), n, sk.n_out,
-                                            C.c_void_p(stream)), 'metro_to_orig_cam')
-    return out, edges, names
+    call = _checked_call(frames, boxes, frame_index, coords, views, geometry, precision, check_finite, pixel_format,
+                         color_matrix)
+    return _estimate_pose_views(call, model_path, cameras, coords)
 
 
-def _geometry_device(boxes, first) -> torch.device:
-    """The device of a call with device geometry: the boxes' for CUDA boxes, else the frames' (or the current one)."""
-    from metro_pose3d_amd.inference import _resolve_device
-    if isinstance(boxes, torch.Tensor) and boxes.is_cuda:
-        return _resolve_device(boxes)
-    return _resolve_device(first if isinstance(first, torch.Tensor) else torch.empty(0))
-
-
-def _estimate_pose_views(frames, boxes, model_path, cameras, fi, coords, precision, check_finite, vs: Views, device):
-    """boxes: host boxes with their frame indices fi, or _DeviceBoxes (fi None: the geometry runs on the device)."""
+def _estimate_pose_views(call: _Call, model_path, cameras, coords):
     from metro_pose3d_amd.inference import _engine_for, estimate_pose
-    n, nv = len(boxes), len(vs.zoom)
+    n, nv = len(call.boxes), len(call.vs.zoom)
+    device = _call_device(call.boxes, call.frames)
     with torch.cuda.device(device):
-        side = _engine_for(model_path, precision, device, n * nv).spec.proc_side
-        if isinstance(boxes, _DeviceBoxes):
-            crops, places, (status, n_frames) = _warp_device_boxes(frames, cameras, boxes, vs, side, device)
-        else:
-            crops, places = _warp_views(frames, cameras, boxes, fi, vs, side, device)
-            status = None
-        poses, edges, names = estimate_pose(crops, model_path, precision=precision, check_finite=check_finite, shard=False)
-        if status is not None:            # after estimate_pose's synchronisation (its finite screen), or the call's one read
-            _raise_on_bad_frames(int(status.item()), n, n_frames)
-        if coords == 'crop':                                           # one view (checked by the caller)
+        spec = _engine_for(model_path, call.precision, device, max(n * nv, 1)).spec
+        crops, places = _warp_views(call.frames, cameras, call.boxes, call.fi, call.vs, spec.proc_side, device)
+        poses, edges, names = estimate_pose(crops, model_path, precision=call.precision, check_finite=call.check_finite,
+                                            shard=False)
+        _synchronise(None, call.boxes)         # after estimate_pose's synchronisation (its finite screen), or the call's one
+        if coords == 'crop' or n == 0:         # one view (_checked_call)
             return poses, edges, names
-        sk = _engine_for(model_path, precision, device, n * nv).spec.skeleton
+        sk = spec.skeleton
         at = _ROT_TO_ORIG_CAM if coords == 'camera' else _ROT_TO_WORLD
         rot = places.view(torch.float32)[:, at:at + 9].contiguous()
         mirror = _upload(np.asarray(sk.out_mirror, np.int32), device)
@@ -1164,147 +807,72 @@ def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=
     keypoints2d: heatmap_to_image(coords01.xy) mapped into the frame (cameralib.reproject_image_points, cameralib.py:241-262):
     through the crop's warp homography (cameras=None or an undistorted camera), or through rot_to_orig_cam and the original
     camera's project_points (a camera with coefficients).  NaN where the ray points behind the original camera.
-    One enqueue chain on the current stream of the local device: uploads, one warp launch, metro_forward_coords01 in <= 256-crop
-    chunks with the finite screen folded on the device, one metro_place_poses launch, then the call's one stream
-    synchronisation (the screen).  No default bone-length table ships: the reference's come from its training data.
-    views: None (one crop per box) or test-time views as for estimate_pose_in_frames: n V crops through the same chain
-    (bone lengths and root depths repeated per view), each view placed by metro_place_poses in `coords` (flipped views'
-    joints mirrored), then metro_merge_views: poses and z offsets averaged over the views, keypoints over the views whose
-    keypoint is finite (a flipped view contributes its mirror joint's), NaN if none.  views=1 returns the bits of
-    views=None.  return_spread=True returns (FramePoses, spread [n, Jout]): per joint, the RMS 3D distance in mm of the
-    views from their mean (zeros with one view), a cheap agreement score.
-    geometry: 'host', 'device' or 'auto' as for estimate_pose_in_frames (device boxes: metro_look_at_boxes, then the views
-    chain with the identity view when views=None; bone_lengths and root_depth stay host data); a device frame index outside
-    [0, n_frames) raises ValueError, read together with the finite screen in the call's one synchronisation.
+    One enqueue chain on the current stream of the local device, estimate_pose_in_frames' up to the warp: uploads, one record
+    per box, metro_expand_views, one warp launch; then metro_forward_coords01 in <= 256-crop chunks with the finite screen
+    folded on the device, one metro_place_poses launch, metro_merge_views, then the call's one stream synchronisation (the
+    screen).  No default bone-length table ships: the reference's come from its training data.
+    views: None (one crop per box: the identity view) or test-time views as for estimate_pose_in_frames: n V crops (bone
+    lengths and root depths repeated per view), each view placed by metro_place_poses in `coords` (flipped views' joints
+    mirrored), then metro_merge_views: poses and z offsets averaged over the views, keypoints over the views whose keypoint
+    is finite (a view whose rot_to_orig_cam has det <= 0 contributes its mirror joint's), NaN if none.  Every call runs the
+    merge, so a camera whose own R is improper (det R <= 0) has its keypoints swapped to the mirror joints with or without
+    views, on host and on device boxes alike.  return_spread=True returns (FramePoses, spread [n, Jout]): per joint, the RMS
+    3D distance in mm of the views from their mean (zeros with one view), a cheap agreement score.
+    geometry: 'host', 'device' or 'auto' as for estimate_pose_in_frames (bone_lengths and root_depth stay host data); a
+    device frame index outside [0, n_frames) raises ValueError, read together with the finite screen in the call's one
+    synchronisation.
     pixel_format, color_matrix: as for estimate_pose_in_frames ('bgr', 'nv12', 'i420' frames converted per tap in the warp,
     OpenCV's integer YUV rule, black border)."""
-    from metro_pose3d_amd.inference import _engine_for, _resolve_device
-    frames = _frame_set(frames, pixel_format, color_matrix)
-    geo = _geometry_of(geometry, boxes)
-    if coords not in COORDS:
-        raise ValueError(f"coords must be 'crop', 'camera' or 'world', got {coords!r}")
-    vs = None if views is None else view_set(views)
-    if vs is not None and coords == 'crop' and len(vs.zoom) > 1:
-        raise ValueError(f"coords='crop' takes one view: the {len(vs.zoom)} views have different virtual cameras")
-    if precision is None:
-        precision = os.environ.get('METRO_PRECISION', 'f16')
-    if check_finite is None:
-        check_finite = os.environ.get('METRO_CHECK_FINITE', '1') != '0'
-    first = _first_frame(frames)
-    if geo == 'device':
-        device = _geometry_device(boxes, first)
-        db = _device_boxes(boxes, frame_index, device)
-        n = len(db)
-        if n:
-            sk = _model_skeleton(model_path)
-            targets, per_pose, root_z = _placement_targets(scale_recovery, cameras, n, len(sk.head_edges), bone_lengths,
-                                                           root_depth)
-            names = np.empty(sk.n_out, dtype=object)
-            names[:] = sk.names_bytes()
-            res = _locate_poses_views(frames, db, model_path, cameras, None, scale_recovery, targets, per_pose, root_z, coords,
-                                      precision, check_finite, vs if vs is not None else view_set(1), sk, names, device)
-            return res if return_spread else res[0]
-        boxes, frame_index = np.zeros((0, 4)), None
-    boxes = np.asarray(_host_array(boxes), np.float64)
-    if boxes.ndim != 2 or boxes.shape[1] != 4:
-        raise ValueError(f'boxes must be [n, 4] (x, y, w, h), got {boxes.shape}')
-    n = len(boxes)
-    fi = np.zeros(n, np.int64) if frame_index is None else np.asarray(_host_array(frame_index), np.int64).reshape(n)
+    call = _checked_call(frames, boxes, frame_index, coords, views, geometry, precision, check_finite, pixel_format,
+                         color_matrix)
     sk = _model_skeleton(model_path)
-    targets, per_pose, root_z = _placement_targets(scale_recovery, cameras, n, len(sk.head_edges), bone_lengths, root_depth)
-    device = _resolve_device(first if isinstance(first, torch.Tensor) else torch.empty(0))
+    targets, per_pose, root_z = _placement_targets(scale_recovery, cameras, len(call.boxes), len(sk.head_edges), bone_lengths,
+                                                   root_depth)
+    res = _locate_poses_views(call, model_path, cameras, scale_recovery, targets, per_pose, root_z, coords, sk)
+    return res if return_spread else res[0]
+
+
+def _forward_coords01(eng, crops: torch.Tensor, check_finite: bool):
+    """metro_forward_coords01 in chunks of the engine's batch -> (root-relative poses [m, Jout, 3], coords01 [m, Jhead, 3],
+    the number of crops with non-finite statistics as a device scalar, or None without check_finite: folded on the device
+    after every chunk, read by the caller's one synchronisation)."""
+    sk = eng.spec.skeleton
+    m = len(crops)
+    rel = torch.empty((m, sk.n_out, 3), dtype=torch.float32, device=crops.device)
+    coords01 = torch.empty((m, sk.n_head, 3), dtype=torch.float32, device=crops.device)
+    bad = None
+    for i in range(0, m, eng.max_batch):
+        k = min(eng.max_batch, m - i)
+        eng.forward(crops[i:i + k], out=rel[i:i + k], coords01=coords01[i:i + k])
+        if check_finite:
+            cnt = eng.status_words(k).ne(0).sum()
+            bad = cnt if bad is None else bad + cnt
+    return rel, coords01, bad
+
+
+def _locate_poses_views(call: _Call, model_path, cameras, scale_recovery, targets, per_pose, root_z, coords, sk):
+    """-> (FramePoses, spread [n, Jout])."""
+    from metro_pose3d_amd.inference import _engine_for
+    n, nv = len(call.boxes), len(call.vs.zoom)
+    m = n * nv
+    device = _call_device(call.boxes, call.frames)
     names = np.empty(sk.n_out, dtype=object)
     names[:] = sk.names_bytes()
-    if vs is not None and n:
-        res = _locate_poses_views(frames, boxes, model_path, cameras, fi, scale_recovery, targets, per_pose, root_z, coords,
-                                  precision, check_finite, vs, sk, names, device)
-        return res if return_spread else res[0]
-    res = _locate_poses(frames, boxes, model_path, cameras, fi, scale_recovery, targets, per_pose, root_z, coords, precision,
-                        check_finite, sk, names, device)
-    if return_spread:
-        return res, torch.zeros((n, sk.n_out), dtype=torch.float32, device=device)
-    return res
-
-
-def _locate_poses(frames, boxes, model_path, cameras, fi, scale_recovery, targets, per_pose, root_z, coords, precision,
-                  check_finite, sk, names, device) -> FramePoses:
-    from metro_pose3d_amd.inference import _engine_for
-    n = len(boxes)
+    absolute = scale_recovery != 'metro'
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
     with torch.cuda.device(device):
-        eng = _engine_for(model_path, precision, device, max(n, 1))
-        spec = eng.spec
-        poses = torch.empty((n, sk.n_out, 3), dtype=torch.float32, device=device)
-        keypoints = torch.empty((n, sk.n_out, 2), dtype=torch.float32, device=device)
-        z_offset = torch.empty(n, dtype=torch.float32, device=device) if scale_recovery != 'metro' else None
+        eng = _engine_for(model_path, call.precision, device, max(m, 1))
         if n == 0:
-            return FramePoses(poses, keypoints, z_offset, sk.edges_array(), names)
-        side = spec.proc_side
-        crop_p, place_p = _frame_params(cameras, boxes, fi, side)
-        crops = warp_frames(frames, crop_p, fi, side, device=device)
-        rel = torch.empty((n, sk.n_out, 3), dtype=torch.float32, device=device)
-        coords01 = torch.empty((n, sk.n_head, 3), dtype=torch.float32, device=device)
-        bad = None
-        for i in range(0, n, eng.max_batch):
-            k = min(eng.max_batch, n - i)
-            eng.forward(crops[i:i + k], out=rel[i:i + k], coords01=coords01[i:i + k])
-            if check_finite:       # folded on the device after every chunk: ONE synchronisation per call, below
-                cnt = eng.status_words(k).ne(0).sum()
-                bad = cnt if bad is None else bad + cnt
-        recs = _upload(pack_placements(place_p), device)
+            return (FramePoses(f32(0, sk.n_out, 3), f32(0, sk.n_out, 2), f32(0) if absolute else None, sk.edges_array(), names),
+                    torch.zeros((0, sk.n_out), dtype=torch.float32, device=device))
+        crops, places = _warp_views(call.frames, cameras, call.boxes, call.fi, call.vs, eng.spec.proc_side, device)
+        rel, coords01, bad = _forward_coords01(eng, crops, call.check_finite)
+        if per_pose:                                    # per-box targets, repeated per view by index (box-major rows)
+            targets = np.repeat(targets, nv, axis=0)
+        poses_v, keypoints_v, z_v = f32(m, sk.n_out, 3), f32(m, sk.n_out, 2), f32(m) if absolute else None
         mirror = _upload(np.asarray(sk.out_mirror, np.int32), device)
         d_targets = _upload(targets, device) if targets is not None else None
-        d_root = _upload(root_z, device) if root_z is not None else None
-        d_edges = _upload(np.asarray(sk.head_edges, np.int32).reshape(-1, 2), device) if targets is not None else None
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        check(_lib.load().metro_place_poses(ptr(coords01), ptr(rel), ptr(recs), n, C.byref(eng.cspec), SCALE_RECOVERY[scale_recovery],
-                                            ptr(d_targets), per_pose, ptr(d_root), ptr(d_edges), len(sk.head_edges),
-                                            ptr(mirror), COORDS[coords], ptr(poses), ptr(keypoints), ptr(z_offset),
-                                            C.c_void_p(stream)), 'metro_place_poses')
-        n_bad = int(bad.item()) if bad is not None else 0              # the call's one stream synchronisation
-        if n_bad:
-            raise _lib.NonFiniteError(
-                f'{spec.arch_name} stride {spec.stride} in precision {precision!r}: {n_bad} of {n} crops reached the '
-                'soft-argmax with non-finite statistics' +
-                (' (fp16 storage overflows at 65504: run this model with precision f32m or f64)' if precision == 'f16' else ''))
-    return FramePoses(poses, keypoints, z_offset, sk.edges_array(), names)
-
-
-def _locate_poses_views(frames, boxes, model_path, cameras, fi, scale_recovery, targets, per_pose, root_z, coords, precision,
-                        check_finite, vs: Views, sk, names, device):
-    """locate_poses_in_frames with views: -> (FramePoses, spread [n, Jout]).  boxes: host boxes with their frame indices fi,
-    or _DeviceBoxes (fi None: the geometry runs on the device)."""
-    from metro_pose3d_amd.inference import _engine_for
-    n, nv = len(boxes), len(vs.zoom)
-    m = n * nv
-    if per_pose:                                    # per-box targets, repeated per view by index (box-major rows)
-        targets = np.repeat(targets, nv, axis=0)
-    if root_z is not None:
-        root_z = np.repeat(root_z, nv)
-    with torch.cuda.device(device):
-        eng = _engine_for(model_path, precision, device, m)
-        spec = eng.spec
-        side = spec.proc_side
-        if isinstance(boxes, _DeviceBoxes):
-            crops, places, (status, n_frames) = _warp_device_boxes(frames, cameras, boxes, vs, side, device)
-        else:
-            crops, places = _warp_views(frames, cameras, boxes, fi, vs, side, device)
-            status = None
-        rel = torch.empty((m, sk.n_out, 3), dtype=torch.float32, device=device)
-        coords01 = torch.empty((m, sk.n_head, 3), dtype=torch.float32, device=device)
-        bad = None
-        for i in range(0, m, eng.max_batch):
-            k = min(eng.max_batch, m - i)
-            eng.forward(crops[i:i + k], out=rel[i:i + k], coords01=coords01[i:i + k])
-            if check_finite:       # folded on the device after every chunk: ONE synchronisation per call, below
-                cnt = eng.status_words(k).ne(0).sum()
-                bad = cnt if bad is None else bad + cnt
-        poses_v = torch.empty((m, sk.n_out, 3), dtype=torch.float32, device=device)
-        keypoints_v = torch.empty((m, sk.n_out, 2), dtype=torch.float32, device=device)
-        z_v = torch.empty(m, dtype=torch.float32, device=device) if scale_recovery != 'metro' else None
-        mirror = _upload(np.asarray(sk.out_mirror, np.int32), device)
-        d_targets = _upload(targets, device) if targets is not None else None
-        d_root = _upload(root_z, device) if root_z is not None else None
+        d_root = _upload(np.repeat(root_z, nv), device) if root_z is not None else None
         d_edges = _upload(np.asarray(sk.head_edges, np.int32).reshape(-1, 2), device) if targets is not None else None
         ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
         stream = torch.cuda.current_stream(device).cuda_stream
@@ -1313,16 +881,11 @@ def _locate_poses_views(frames, boxes, model_path, cameras, fi, scale_recovery, 
                                             ptr(mirror), COORDS[coords], ptr(poses_v), ptr(keypoints_v), ptr(z_v),
                                             C.c_void_p(stream)), 'metro_place_poses')
         poses, keypoints, z_offset, spread = _merge_views(poses_v, keypoints_v, z_v, places, mirror, n, nv, spread=True)
-        if status is None:
-            n_bad = int(bad.item()) if bad is not None else 0          # the call's one stream synchronisation
-        else:                                # the screen and the frame-index status in the call's one synchronisation
-            words = status[0].to(torch.int64) if bad is None else torch.stack([status[0].to(torch.int64), bad.reshape(())])
-            words = words.reshape(-1).tolist()
-            n_bad = words[1] if len(words) > 1 else 0
-            _raise_on_bad_frames(words[0], n, n_frames)
+        n_bad = _synchronise(bad, call.boxes)                          # the call's one stream synchronisation
         if n_bad:
+            spec = eng.spec
             raise _lib.NonFiniteError(
-                f'{spec.arch_name} stride {spec.stride} in precision {precision!r}: {n_bad} of {m} view crops reached the '
+                f'{spec.arch_name} stride {spec.stride} in precision {call.precision!r}: {n_bad} of {m} crops reached the '
                 'soft-argmax with non-finite statistics' +
-                (' (fp16 storage overflows at 65504: run this model with precision f32m or f64)' if precision == 'f16' else ''))
+                (' (fp16 storage overflows at 65504: run this model with precision f32m or f64)' if call.precision == 'f16' else ''))
     return FramePoses(poses, keypoints, z_offset, sk.edges_array(), names), spread

@@ -63,6 +63,59 @@ def test_one_view_is_bit_identical_to_no_views(cuda, tmp_path, precision):
             assert torch.equal(got, crop)
 
 
+def test_no_views_is_the_identity_view_chain(cuda, tmp_path):
+    """views=None is views=1 on host boxes and on device boxes, with and without cameras: no path skips the expansion or the
+    merge.  f64: its forward gives a crop the same bits in any call."""
+    spec, _, path = _toy_engine_model(tmp_path)
+    cams, frames, boxes, fi = _scene()
+    bones = np.random.default_rng(2).uniform(200, 450, len(spec.skeleton.head_edges))
+    for cameras in (cams, None):
+        scale = dict(bone_lengths=bones) if cameras is not None else dict(scale_recovery='metro')
+        for geometry in ('host', 'device'):
+            kw = dict(cameras=cameras, frame_index=fi, precision='f64', geometry=geometry)
+            (none, s0), (one, s1) = (locate_poses_in_frames(frames, boxes, path, views=views, return_spread=True, **scale, **kw)
+                                     for views in (None, 1))
+            assert torch.equal(none.poses, one.poses), (cameras is None, geometry)
+            if cameras is None:
+                assert none.z_offset is None and one.z_offset is None
+            else:
+                assert torch.equal(none.z_offset, one.z_offset)
+            assert np.array_equal(_np(none.keypoints2d), _np(one.keypoints2d), equal_nan=True)
+            assert s0.shape == (len(boxes), spec.skeleton.n_out) and (s0 == 0).all() and torch.equal(s0, s1)
+            rel = [estimate_pose_in_frames(frames, boxes, path, views=views, **kw)[0] for views in (None, 1)]
+            assert torch.equal(rel[0], rel[1])
+
+
+def test_improper_camera_rotation_is_one_answer(cuda, tmp_path):
+    """A camera whose R has det -1: look_at_box builds a proper virtual R, so the identity view's rot_to_orig_cam has det -1
+    and metro_merge_views takes keypoint j from joint mirror[j].  Host boxes with views=None, with views=1, and device boxes
+    with views=None give one answer.  Before the chains were merged, host boxes with views=None never ran the merge: on these
+    two boxes they returned the poses of the other two paths but the unswapped keypoints (row j of the others = their row
+    mirror[j], up to 43.5 px apart), in 'metro' and 'bone-lengths' mode alike; views=1 and device boxes agreed bit for bit.
+    The two boxes are camera 1's; the placement oracle puts every heat-map position of their crops in front of the camera, so
+    the keypoints compared are finite."""
+    spec, _, path = _toy_engine_model(tmp_path)
+    sk = spec.skeleton
+    cams, frames, boxes, fi = _scene()
+    cams[1].R[0] *= -1
+    boxes, fi = boxes[1:3], fi[1:3]
+    assert (fi == 1).all() and np.linalg.det(cams[1].R.astype(np.float64)) < 0
+    _, q = view_params(cams, boxes, fi, 1, 256)
+    assert (np.linalg.det(q.rot_to_orig_cam.astype(np.float64)) < 0).all()
+    c01 = np.random.default_rng(0).uniform(0, 1, (len(boxes), sk.n_head, 3)).astype(np.float32)
+    assert np.isfinite(OPL.keypoints(c01, q, spec.stride, sk.permutation)).all()
+    bones = np.random.default_rng(2).uniform(200, 450, len(sk.head_edges))
+    for scale in (dict(scale_recovery='metro'), dict(scale_recovery='bone-lengths', bone_lengths=bones)):
+        call = lambda **kw: locate_poses_in_frames(frames, boxes, path, cameras=cams, frame_index=fi, precision='f64',
+                                                   **scale, **kw)
+        host, one, device = call(), call(views=1), call(geometry='device')
+        kp = _np(host.keypoints2d)
+        assert np.isfinite(kp).all(axis=-1).mean() >= 0.5
+        for other in (one, device):
+            assert torch.equal(host.poses, other.poses), scale['scale_recovery']
+            assert np.array_equal(kp, _np(other.keypoints2d), equal_nan=True), scale['scale_recovery']
+
+
 def test_copies_of_one_view_merge_to_its_bits(cuda, tmp_path):
     """V copies of a rolled, zoomed, flipped view: the merge of V equal rows is that row (fp64 sums of <= 32 equal fp32 values
     are exact) and the spread is exactly 0.  f64: its forward gives a crop the same bits at any batch size."""

@@ -105,7 +105,7 @@ def test_identity_view_keeps_the_records_of_the_box():
     fr = np.load(FRAMES_FIX)
     cams = fixture_cameras(fr)
     for cameras in (cams, None):
-        p0, q0 = frames._frame_params(cameras, fr['boxes'], fr['box_camera'], 256)
+        p0, q0, _ = frames._frame_params_and_cameras(cameras, fr['boxes'], fr['box_camera'], 256)
         p, q = view_params(cameras, fr['boxes'], fr['box_camera'], [(0, 1, False), (5, 1, False)], 256)
         for a, b in zip(p0 + q0, p + q):
             assert np.array_equal(a, b[0::2])
@@ -221,8 +221,8 @@ class _Stop(Exception):
 
 @pytest.mark.parametrize('cameras', ['fixture', None])
 def test_host_work_is_per_box_not_per_view(monkeypatch, cameras):
-    """The views chain's host phase (_warp_views up to the expansion launch): look_at_box and the record packing run once per
-    box whatever V is; no per-crop record is packed on the host (the device writes them)."""
+    """The chain's host phase (_warp_views up to the expansion launch): look_at_box and the record packing run once per
+    box whatever V is, views=None included; no per-crop record is packed on the host (the device writes them)."""
     fr = np.load(FRAMES_FIX)
     cams = fixture_cameras(fr) if cameras else None
     calls = {'look_at_box': 0, 'pack_crops': 0, 'pack_placements': 0, 'bases_rows': []}
@@ -250,6 +250,30 @@ def test_host_work_is_per_box_not_per_view(monkeypatch, cameras):
             frames._warp_views(None, cams, fr['boxes'], fr['box_camera'].astype(np.int64), view_set(nv), 256, None)
         assert calls['look_at_box'] == (n if cameras else 0)
         assert calls['bases_rows'][-1] == (n, nv, nv)
+    assert calls['pack_crops'] == 0 and calls['pack_placements'] == 0
+    # views=None is the same chain with the identity view: the public calls up to the expansion, the engine and the device
+    # stubbed (no model file, no GPU)
+    import contextlib
+    import types
+
+    import torch
+    from metro_pose3d_amd import inference
+    engine = types.SimpleNamespace(spec=types.SimpleNamespace(proc_side=256))
+    monkeypatch.setattr(inference, '_engine_for', lambda *a, **kw: engine)
+    monkeypatch.setattr(inference, '_resolve_device', lambda t: None)
+    monkeypatch.setattr(torch.cuda, 'device', lambda device: contextlib.nullcontext())
+    monkeypatch.setattr(frames, '_model_skeleton', lambda path: SK)
+    frame = [np.zeros((8, 8, 3), np.uint8)] * 3
+    for call in (lambda **kw: estimate_pose_in_frames(frame, fr['boxes'], 'no-such-model.npz', cameras=cams,
+                                                      frame_index=fr['box_camera'], **kw),
+                 lambda **kw: locate_poses_in_frames(frame, fr['boxes'], 'no-such-model.npz', cameras=cams,
+                                                     frame_index=fr['box_camera'], scale_recovery='metro', **kw)):
+        for views, nv in ((None, 1), (1, 1), (5, 5)):
+            calls['look_at_box'] = 0
+            with pytest.raises(_Stop):
+                call(views=views)
+            assert calls['look_at_box'] == (n if cameras else 0)
+            assert calls['bases_rows'][-1] == (n, nv, nv)
     assert calls['pack_crops'] == 0 and calls['pack_placements'] == 0
 
 
