@@ -56,6 +56,16 @@ def to_rgb(frame, pixel_format, matrix='bt601'):
     return yuv420_to_rgb(*planes, matrix)
 
 
+def random_frame(h, w, pixel_format, matrix='bt601', seed=0):
+    """-> (a random one-array frame in pixel_format, the RGB uint8 [H, W, 3] frame it stands for).  The packed formats draw
+    bytes from 1..255, so a pixel whose three channels are 0 is a border pixel of the warp, never a frame pixel."""
+    if pixel_format in ('rgb', 'bgr'):
+        src = np.random.default_rng(seed).integers(1, 256, (h, w, 3), dtype=np.uint8)
+    else:
+        src = (nv12_frame if pixel_format == 'nv12' else i420_frame)(*random_planes(h, w, seed))
+    return src, to_rgb(src, pixel_format, matrix)
+
+
 def random_planes(h, w, seed):
     """Random Y [H, W], U, V [H/2, W/2] planes over the whole byte range (every clamp of the rule is reached)."""
     rng = np.random.default_rng(seed)
