@@ -18,7 +18,7 @@
 
 namespace metro {
 
-constexpr int HEAD_MAX = METRO_MAX_JOINTS;      // what check_head_args (plan.cpp) admits: joints and edges per pose
+constexpr int HEAD_MAX = METRO_MAX_JOINTS;      // what check_head_args (entries.cpp) admits: joints and edges per pose
 
 struct LmProblem {
     const double* c; const double* d; const double* e; const double* t; int m;

@@ -1,0 +1,496 @@
+// The per-kernel C entries of libmetro_hip.so (include/metro_hip.h): argument checks in front of a launch_*, plus the
+// thread-local error and dispatch-note state every translation unit reports through.
+#include <cmath>
+#include <cstring>
+
+#include "metro_common.h"
+
+namespace metro {
+
+static thread_local char g_err[512] = "";
+
+void set_error(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+}
+const char* get_error() { return g_err; }
+
+static thread_local KernelNotes g_notes = {0, ""};
+KernelNotes& kernel_notes() { return g_notes; }
+bool note_kernel(const char* fmt, ...) {
+    if (g_notes.mode == 0) return false;
+    // Mode 1 accumulates until metro_kernel_notes() is called again; an id that does not fit the 1 KiB string is replaced by a
+    // trailing " ..." so a truncated string can never pass for an id (a whole metro_forward of ~46 launches does not fit: mode 1
+    // is meant for ONE single-kernel entry-point call at a time).
+    const size_t cap = sizeof(g_notes.ids) - 5;           // room for " ..."
+    const size_t used = strlen(g_notes.ids);
+    if (used >= 4 && strcmp(g_notes.ids + used - 4, " ...") == 0) return g_notes.mode == 2;
+    char one[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(one, sizeof(one), fmt, ap);
+    va_end(ap);
+    const size_t need = strlen(one) + (used ? 3 : 0);
+    if (used + need > cap) { memcpy(g_notes.ids + used, " ...", 5); return g_notes.mode == 2; }
+    if (used) memcpy(g_notes.ids + used, " & ", 3);       // several kernels: a & b
+    memcpy(g_notes.ids + used + (used ? 3 : 0), one, strlen(one) + 1);
+    return g_notes.mode == 2;
+}
+
+int validate_conv_desc(const MetroConvDesc* d) {
+    METRO_CHECK_ARG(d != nullptr, "conv desc is NULL");
+    METRO_CHECK_ARG(d->n > 0 && d->h_in > 0 && d->w_in > 0 && d->c_in > 0 && d->h_out > 0 &&
+                        d->w_out > 0 && d->c_out > 0,
+                    "conv desc: non-positive dimension");
+    METRO_CHECK_ARG(d->kh > 0 && d->kw > 0 && d->stride > 0 && d->dilation > 0, "conv desc: bad kernel geometry");
+    METRO_CHECK_ARG(d->in_pix_stride > 0, "conv desc: in_pix_stride must be positive");
+    METRO_CHECK_ARG((long)d->n * d->h_out * d->w_out < (1L << 31), "conv desc: too many output pixels");
+    METRO_CHECK_ARG((long)d->n * d->h_in * d->w_in < (1L << 31), "conv desc: too many input pixels");
+    if (d->has_prologue) {
+        METRO_CHECK_ARG(d->kh == 1 && d->kw == 1, "conv desc: prologue requires a 1x1 kernel");
+        const long last_h = (long)(d->h_out - 1) * d->stride - d->pad_top;
+        const long last_w = (long)(d->w_out - 1) * d->stride - d->pad_left;
+        METRO_CHECK_ARG(d->pad_top <= 0 && d->pad_left <= 0 && last_h < d->h_in && last_w < d->w_in,
+                        "conv desc: prologue requires every tap to be in bounds (no padding)");
+    }
+    if (d->has_residual) {
+        METRO_CHECK_ARG(d->res_stride > 0 && d->res_offset >= 0, "conv desc: bad residual gather");
+        METRO_CHECK_ARG((d->h_out - 1) * d->res_stride + d->res_offset < d->res_h &&
+                            (d->w_out - 1) * d->res_stride + d->res_offset < d->res_w,
+                        "conv desc: residual gather out of bounds");
+    }
+    return METRO_OK;
+}
+
+}  // namespace metro
+
+using namespace metro;
+
+extern "C" {
+
+int metro_kernel_notes(int32_t mode) {
+    METRO_CHECK_ARG(mode >= 0 && mode <= 2, "metro_kernel_notes: mode must be 0 (off), 1 (record) or 2 (dry run)");
+    KernelNotes& kn = kernel_notes();
+    kn.mode = mode; kn.ids[0] = 0;
+    return METRO_OK;
+}
+const char* metro_last_kernel_id(void) { return kernel_notes().ids; }
+
+int metro_conv_f16(const MetroConvDesc* d, const void* d_in, const void* d_w, const float* d_bias,
+                   const void* d_pro_scale, const void* d_pro_shift, const void* d_residual,
+                   void* d_out, void* stream) {
+    int st = validate_conv_desc(d);
+    if (st) return st;
+    METRO_CHECK_ARG(d->c_in % 8 == 0 && d->in_pix_stride % 4 == 0, "conv_f16: c_in must be a multiple of 8 (got %d) and in_pix_stride of 4", d->c_in);
+    METRO_CHECK_ARG(d->c_in <= 2048, "conv_f16: c_in must be <= 2048 (got %d)", d->c_in);
+    METRO_CHECK_ARG(d->c_out % 4 == 0, "conv_f16: c_out must be a multiple of 4 (got %d)", d->c_out);
+    METRO_CHECK_ARG(d->out_dtype == METRO_F16 || d->out_dtype == METRO_F32, "conv_f16: out_dtype must be F16 or F32");
+    METRO_CHECK_ARG(d->in_dtype == METRO_F16, "conv_f16: in_dtype must be F16");
+    METRO_CHECK_ARG(!(d->has_residual && d->out_dtype == METRO_F32), "conv_f16: a residual needs F16 output (F32 output has no residual epilogue)");
+    METRO_CHECK_ARG(d_in && d_w && d_bias && d_out, "conv_f16: NULL tensor pointer");
+    METRO_CHECK_ARG(!d->has_prologue || (d_pro_scale && d_pro_shift), "conv_f16: prologue tensors missing");
+    METRO_CHECK_ARG(!d->has_residual || d_residual, "conv_f16: residual tensor missing");
+    return launch_conv_f16(*d, d_in, d_w, d_bias, d_pro_scale, d_pro_shift, d_residual, d_out,
+                           static_cast<hipStream_t>(stream));
+}
+
+int metro_conv_f16_pair(const MetroConvDesc* d, const void* d_in, const void* d_w, const float* d_bias,
+                        const void* d_pro_scale, const void* d_pro_shift, void* d_out, int32_t split,
+                        void* d_out2, void* stream) {
+    int st = validate_conv_desc(d);
+    if (st) return st;
+    METRO_CHECK_ARG(d_in && d_w && d_bias && d_out && d_out2 && d_pro_scale && d_pro_shift, "conv_f16_pair: NULL tensor pointer");
+    ConvFused f;
+    f.form = ConvForm::Pair;
+    f.pair = {split, d->c_out - split, 1, d_out2};
+    METRO_CHECK_ARG(conv_form_supported(*d, f), "conv_f16_pair: fp16 1x1 stride-1 convolution with prologue, without residual / ReLU on the "
+                    "first output, c_in %% 64; split %d of c_out %d (split %% 256, rest %% 8)", split, d->c_out);
+    return launch_conv_f16_dma(*d, d_in, d_w, d_bias, d_pro_scale, d_pro_shift, nullptr, d_out, static_cast<hipStream_t>(stream), f);
+}
+
+int metro_conv_f16_next(const MetroConvDesc* d, const void* d_in, const void* d_w, const float* d_bias,
+                        const void* d_residual, void* d_out, const void* d_w2, const float* d_bias2,
+                        const void* d_scale2, const void* d_shift2, void* d_out2, int32_t c2, void* stream) {
+    int st = validate_conv_desc(d);
+    if (st) return st;
+    METRO_CHECK_ARG(d_in && d_w && d_bias && d_out && d_w2 && d_bias2 && d_scale2 && d_shift2 && d_out2,
+                    "conv_f16_next: NULL tensor pointer");
+    METRO_CHECK_ARG(!d->has_residual || d_residual, "conv_f16_next: residual tensor missing");
+    ConvFused f;
+    f.form = ConvForm::Next;
+    f.next = {d_w2, d_bias2, d_scale2, d_shift2, d_out2, c2};
+    METRO_CHECK_ARG(conv_form_supported(*d, f),
+                    "conv_f16_next: built for 1x1 stride-1 64 -> 256 with c2 = 64 (block1) and 128 -> 512 with c2 = 128 (block2), fp16");
+    return launch_conv_f16_dma(*d, d_in, d_w, d_bias, nullptr, nullptr, d_residual, d_out, static_cast<hipStream_t>(stream), f);
+}
+
+int metro_conv_f16_conv1_conv2(const MetroConvDesc* d, const void* d_x, const void* d_w1, const float* d_bias1, const void* d_pro_scale,
+                               const void* d_pro_shift, const void* d_w2, const float* d_bias2, void* d_out, void* stream) {
+    int st = validate_conv_desc(d);
+    if (st) return st;
+    METRO_CHECK_ARG(d_x && d_w1 && d_bias1 && d_pro_scale && d_pro_shift && d_w2 && d_bias2 && d_out, "conv_f16_conv1_conv2: NULL tensor pointer");
+    METRO_CHECK_ARG(conv3x3_c64_supported(*d), "conv_f16_conv1_conv2: built for 3x3 stride-1 SAME 64 -> 64 on maps of <= 64 columns that tile into "
+                    "128-pixel row pairs (block1 of the 256-pixel nets)");
+    ConvPre1 p1;
+    p1.w1 = d_w1; p1.bias1 = d_bias1; p1.pro_scale = d_pro_scale; p1.pro_shift = d_pro_shift;
+    return launch_conv3x3_c64(*d, d_x, d_w2, d_bias2, d_out, static_cast<hipStream_t>(stream), &p1);
+}
+
+int metro_conv_f16_next_proj(const MetroConvDesc* d, const void* d_in, const void* d_w, const float* d_bias, const void* d_x,
+                             const void* d_w_sc, const float* d_bias_sc, const void* d_pro_scale, const void* d_pro_shift, void* d_out,
+                             const void* d_w2, const float* d_bias2, const void* d_scale2, const void* d_shift2, void* d_out2,
+                             int32_t c2, void* stream) {
+    int st = validate_conv_desc(d);
+    if (st) return st;
+    METRO_CHECK_ARG(d_in && d_w && d_bias && d_x && d_w_sc && d_bias_sc && d_pro_scale && d_pro_shift && d_w2 && d_bias2 &&
+                        d_scale2 && d_shift2 && d_out2, "conv_f16_next_proj: NULL tensor pointer");
+    ConvFused f;
+    f.form = ConvForm::NextProj;
+    f.next = {d_w2, d_bias2, d_scale2, d_shift2, d_out2, c2};
+    f.psc = {d_x, d_w_sc, d_bias_sc, d_pro_scale, d_pro_shift};
+    f.rb.out_mode = d_out == nullptr ? 1 : 0;          // d_out == NULL: the sum stays on chip (it only feeds the second GEMM)
+    METRO_CHECK_ARG(conv_form_supported(*d, f), "conv_f16_next_proj: built for 1x1 stride-1 64 -> 256 without prologue / residual, "
+                    "c2 = 64 (block1/unit_1), fp16");
+    return launch_conv_f16_dma(*d, d_in, d_w, d_bias, nullptr, nullptr, nullptr, d_out, static_cast<hipStream_t>(stream), f);
+}
+
+int metro_conv_f16_next_rebuild(const MetroConvDesc* d, const void* d_in, const void* d_w, const float* d_bias, const void* d_x,
+                                const void* d_w_sc, const float* d_bias_sc, const void* d_pro_scale, const void* d_pro_shift,
+                                const void* d_t2_prev, const void* d_w3_prev, const float* d_bias3_prev, void* d_out, void* d_out_sub,
+                                int32_t sub_off, const void* d_w2, const float* d_bias2, const void* d_scale2, const void* d_shift2,
+                                void* d_out2, int32_t c2, void* stream) {
+    int st = validate_conv_desc(d);
+    if (st) return st;
+    METRO_CHECK_ARG(d_in && d_w && d_bias && d_x && d_w_sc && d_bias_sc && d_pro_scale && d_pro_shift && d_t2_prev && d_w3_prev && d_bias3_prev &&
+                        d_w2 && d_bias2 && d_scale2 && d_shift2 && d_out2, "conv_f16_next_rebuild: NULL tensor pointer");
+    METRO_CHECK_ARG((d_out != nullptr) != (d_out_sub != nullptr), "conv_f16_next_rebuild: exactly one of d_out (the whole sum) and d_out_sub (its "
+                    "sub-sampled compact copy) must be given");
+    METRO_CHECK_ARG(sub_off == 0 || sub_off == 1, "conv_f16_next_rebuild: sub_off %d must be 0 or 1", sub_off);
+    ConvFused f;
+    f.form = ConvForm::NextRebuild;
+    f.next = {d_w2, d_bias2, d_scale2, d_shift2, d_out2, c2};
+    f.psc = {d_x, d_w_sc, d_bias_sc, d_pro_scale, d_pro_shift};
+    ConvRebuild& rb = f.rb;
+    rb.t2_prev = d_t2_prev; rb.w3_prev = d_w3_prev; rb.bias3_prev = d_bias3_prev;
+    if (d_out_sub != nullptr) {
+        rb.out_mode = 2; rb.out_sub = d_out_sub; rb.sub_off = sub_off;
+        rb.h_sub = (d->h_out - sub_off + 1) / 2; rb.w_sub = (d->w_out - sub_off + 1) / 2;
+    }
+    METRO_CHECK_ARG(conv_form_supported(*d, f), "conv_f16_next_rebuild: built for 1x1 stride-1 64 -> 256 without prologue / residual on maps "
+                    "whose width is a power of two >= 16 and whose pixel count is a multiple of 64, c2 = 64 (block1/unit_2), fp16");
+    return launch_conv_f16_dma(*d, d_in, d_w, d_bias, nullptr, nullptr, nullptr, d_out, static_cast<hipStream_t>(stream), f);
+}
+
+int metro_conv_b1_form(int32_t classic) {
+    METRO_CHECK_ARG(classic == 0 || classic == 1, "metro_conv_b1_form: 0 (default dispatch) or 1 (classic single-role kernel)");
+    conv_b1_set_form(classic);
+    return METRO_OK;
+}
+
+int metro_conv_f16_gemm4w(const MetroConvDesc* d, const void* d_in, const void* d_w, const float* d_bias,
+                          const void* d_pro_scale, const void* d_pro_shift, const void* d_residual, void* d_out,
+                          int32_t split, void* d_out2, void* stream) {
+    int st = validate_conv_desc(d);
+    if (st) return st;
+    METRO_CHECK_ARG(d_in && d_w && d_bias && d_out, "conv_f16_gemm4w: NULL tensor pointer");
+    METRO_CHECK_ARG(!d->has_prologue || (d_pro_scale && d_pro_shift), "conv_f16_gemm4w: prologue tensors missing");
+    METRO_CHECK_ARG(!d->has_residual || d_residual, "conv_f16_gemm4w: residual tensor missing");
+    METRO_CHECK_ARG(split >= 0 && split < d->c_out && (split == 0 || d_out2), "conv_f16_gemm4w: bad split %d / missing second output", split);
+    ConvSplit sp;
+    sp.split = split; sp.c_out2 = d->c_out - split; sp.relu2 = 1; sp.out2 = d_out2;
+    return launch_conv_gemm4w(*d, d_in, d_w, d_bias, d_pro_scale, d_pro_shift, d_residual, d_out,
+                              static_cast<hipStream_t>(stream), split > 0 ? &sp : nullptr);
+}
+
+int metro_stem_pool_f16(const void* d_prepped, const void* d_w, const float* d_bias, void* d_out, int32_t n,
+                        int32_t side, void* stream) {
+    METRO_CHECK_ARG(d_prepped && d_w && d_bias && d_out, "stem_pool_f16: NULL tensor pointer");
+    METRO_CHECK_ARG(n > 0, "stem_pool_f16: n = %d", n);
+    METRO_CHECK_ARG(stem_pool_f16_supported(side, 64), "stem_pool_f16: side %d must be a multiple of 32 (and METRO_STEM_POOL != 0)", side);
+    return launch_stem_pool_f16(d_prepped, d_w, d_bias, d_out, n, side, static_cast<hipStream_t>(stream));
+}
+
+int metro_stem_pool_f32in(const float* d_images, const void* d_w, const float* d_bias, void* d_out, int32_t n,
+                          int32_t side, void* stream) {
+    METRO_CHECK_ARG(d_images && d_w && d_bias && d_out, "stem_pool_f32in: NULL tensor pointer");
+    METRO_CHECK_ARG(n > 0, "stem_pool_f32in: n = %d", n);
+    METRO_CHECK_ARG(stem_pool_f32in_supported(side, 64), "stem_pool_f32in: side %d must be a multiple of 32 (and METRO_STEM_POOL / METRO_STEM_RAW != 0)", side);
+    return launch_stem_pool_f32in(d_images, d_w, d_bias, d_out, n, side, static_cast<hipStream_t>(stream));
+}
+
+int metro_conv_f64acc(const MetroConvDesc* d, const void* d_in, const double* d_w, const double* d_bias,
+                      const double* d_pro_scale, const double* d_pro_shift, const void* d_residual,
+                      void* d_out, void* stream) {
+    int st = validate_conv_desc(d);
+    if (st) return st;
+    METRO_CHECK_ARG((d->in_dtype == METRO_F32 || d->in_dtype == METRO_F64) && (d->out_dtype == METRO_F32 || d->out_dtype == METRO_F64) &&
+                        !(d->in_dtype == METRO_F64 && d->out_dtype == METRO_F32),
+                    "conv_f64acc: in/out dtypes must be F32/F32, F32/F64 or F64/F64");
+    METRO_CHECK_ARG(d_in && d_w && d_bias && d_out, "conv_f64acc: NULL tensor pointer");
+    METRO_CHECK_ARG(!d->has_prologue || (d_pro_scale && d_pro_shift), "conv_f64acc: prologue tensors missing");
+    METRO_CHECK_ARG(!d->has_residual || d_residual, "conv_f64acc: residual tensor missing");
+    return launch_conv_f64acc(*d, d_in, d_w, d_bias, d_pro_scale, d_pro_shift, d_residual, d_out,
+                              static_cast<hipStream_t>(stream));
+}
+
+int metro_conv_f32m(const MetroConvDesc* d, const void* d_in, const float* d_w, const float* d_bias, const float* d_pro_scale,
+                    const float* d_pro_shift, const void* d_residual, void* d_out, void* stream) {
+    int st = validate_conv_desc(d);
+    if (st) return st;
+    METRO_CHECK_ARG(d->in_dtype == METRO_F32 && d->out_dtype == METRO_F32, "conv_f32m: in/out dtypes must be F32");
+    METRO_CHECK_ARG(d_in && d_w && d_bias && d_out, "conv_f32m: NULL tensor pointer");
+    METRO_CHECK_ARG(!d->has_prologue || (d_pro_scale && d_pro_shift), "conv_f32m: prologue tensors missing");
+    METRO_CHECK_ARG(!d->has_residual || d_residual, "conv_f32m: residual tensor missing");
+    return launch_conv_f32m(*d, d_in, d_w, d_bias, d_pro_scale, d_pro_shift, d_residual, d_out, static_cast<hipStream_t>(stream));
+}
+
+int metro_prep_input_f16(const float* d_images, int32_t n, int32_t side, void* d_out, void* stream) {
+    METRO_CHECK_ARG(d_images && d_out && n > 0 && side > 0, "prep_input_f16: bad argument");
+    return launch_prep_input_f16(d_images, n, side, d_out, static_cast<hipStream_t>(stream));
+}
+
+int metro_warp_crop_u8(const uint8_t* d_image, int32_t h, int32_t w, int32_t row_stride, const float* d_homographies,
+                       int32_t n, int32_t side, float* d_out, void* stream) {
+    METRO_CHECK_ARG(d_image && d_homographies && d_out, "warp_crop_u8: NULL pointer");
+    METRO_CHECK_ARG(h > 0 && w > 0 && n > 0 && side > 0 && row_stride >= 3 * w, "warp_crop_u8: bad geometry (h %d w %d stride %d n %d side %d)", h, w, row_stride, n, side);
+    METRO_CHECK_ARG(h <= 32767 && w <= 32767, "warp_crop_u8: frames larger than 32767 pixels a side are outside cv2.remap's short coordinates (h %d w %d)", h, w);
+    return launch_warp_crop_u8(d_image, h, w, row_stride, d_homographies, d_out, n, side, static_cast<hipStream_t>(stream));
+}
+
+int metro_warp_crops_frames_u8(const MetroFrame* frames, int32_t n_frames, const MetroCropWarp* d_crops, int32_t n,
+                               int32_t side, float* d_out, void* stream) {
+    METRO_CHECK_ARG(frames && d_crops && d_out, "warp_crops_frames_u8: NULL pointer");
+    METRO_CHECK_ARG(n_frames > 0 && n_frames <= METRO_MAX_FRAMES, "warp_crops_frames_u8: %d frames (1 to %d per launch)",
+                    n_frames, METRO_MAX_FRAMES);
+    METRO_CHECK_ARG(n > 0 && side > 0, "warp_crops_frames_u8: bad geometry (n %d side %d)", n, side);
+    metro::FrameTable table = {};
+    for (int i = 0; i < n_frames; ++i) {
+        const MetroFrame& f = frames[i];
+        METRO_CHECK_ARG(f.data, "warp_crops_frames_u8: frame %d: NULL data pointer", i);
+        METRO_CHECK_ARG(f.h <= 32767 && f.w <= 32767, "warp_crops_frames_u8: frame %d: frames larger than 32767 pixels a side "
+                        "are outside cv2.remap's short coordinates (h %d w %d)", i, f.h, f.w);
+        METRO_CHECK_ARG(f.h > 0 && f.w > 0 && f.row_stride >= 3 * f.w,
+                        "warp_crops_frames_u8: frame %d: bad geometry (h %d w %d stride %d)", i, f.h, f.w, f.row_stride);
+        table.f[i] = f;
+    }
+    return launch_warp_crops_frames_u8(table, n_frames, d_crops, n, side, d_out, static_cast<hipStream_t>(stream));
+}
+
+int metro_warp_crops_frames_planes(const MetroFramePlanes* frames, int32_t n_frames, const MetroCropWarp* d_crops,
+                                   int32_t n, int32_t side, float* d_out, void* stream) {
+    METRO_CHECK_ARG(frames && d_crops && d_out, "warp_crops_frames_planes: NULL pointer");
+    METRO_CHECK_ARG(n_frames > 0 && n_frames <= METRO_MAX_FRAMES, "warp_crops_frames_planes: %d frames (1 to %d per launch)",
+                    n_frames, METRO_MAX_FRAMES);
+    METRO_CHECK_ARG(n > 0 && side > 0, "warp_crops_frames_planes: bad geometry (n %d side %d)", n, side);
+    metro::FramePlanesTable table = {};
+    for (int i = 0; i < n_frames; ++i) {
+        const MetroFramePlanes& f = frames[i];
+        METRO_CHECK_ARG(f.format >= METRO_PIX_RGB && f.format <= METRO_PIX_I420,
+                        "warp_crops_frames_planes: frame %d: unknown pixel format %d", i, f.format);
+        METRO_CHECK_ARG(f.matrix == METRO_YUV_BT601 || f.matrix == METRO_YUV_BT709,
+                        "warp_crops_frames_planes: frame %d: unknown colour matrix %d", i, f.matrix);
+        const bool yuv = f.format == METRO_PIX_NV12 || f.format == METRO_PIX_I420;
+        const int n_planes = f.format == METRO_PIX_I420 ? 3 : f.format == METRO_PIX_NV12 ? 2 : 1;
+        for (int k = 0; k < n_planes; ++k)
+            METRO_CHECK_ARG(f.plane[k], "warp_crops_frames_planes: frame %d: NULL plane %d", i, k);
+        METRO_CHECK_ARG(f.h > 0 && f.w > 0 && f.h <= 32767 && f.w <= 32767, "warp_crops_frames_planes: frame %d: h %d w %d "
+                        "outside [1, 32767] (cv2.remap's short coordinates)", i, f.h, f.w);
+        METRO_CHECK_ARG(!yuv || (f.h % 2 == 0 && f.w % 2 == 0),
+                        "warp_crops_frames_planes: frame %d: 4:2:0 frames need an even h and w (h %d w %d)", i, f.h, f.w);
+        const int min_stride0 = yuv ? f.w : 3 * f.w;
+        METRO_CHECK_ARG(f.stride[0] >= min_stride0, "warp_crops_frames_planes: frame %d: stride[0] %d < %d", i, f.stride[0],
+                        min_stride0);
+        if (yuv) {
+            const int min_stride1 = f.format == METRO_PIX_NV12 ? f.w : f.w / 2;
+            METRO_CHECK_ARG(f.stride[1] >= min_stride1, "warp_crops_frames_planes: frame %d: stride[1] %d < %d", i,
+                            f.stride[1], min_stride1);
+        }
+        table.f[i] = f;
+    }
+    return launch_warp_crops_frames_planes(table, n_frames, d_crops, n, side, d_out, static_cast<hipStream_t>(stream));
+}
+
+int metro_eval_metrics(const float* d_pred, const float* d_true, const uint8_t* d_valid, int32_t n, int32_t n_joints,
+                       float threshold_mm, float* d_dist, float* d_dist_aligned, double* d_sums, void* stream) {
+    METRO_CHECK_ARG(d_pred && d_true && d_valid && d_dist && d_dist_aligned && d_sums, "eval_metrics: NULL pointer");
+    METRO_CHECK_ARG(n > 0 && n_joints >= 3 && n_joints <= 1024 && threshold_mm > 0.f, "eval_metrics: bad sizes (n %d, joints %d)", n, n_joints);
+    return launch_eval_metrics(d_pred, d_true, d_valid, n, n_joints, threshold_mm, d_dist, d_dist_aligned, d_sums,
+                               static_cast<hipStream_t>(stream));
+}
+
+int metro_maxpool3x3s2_zeropad(const void* d_in, void* d_out, int32_t n, int32_t h_in, int32_t w_in,
+                               int32_t c, int32_t dtype, void* stream) {
+    METRO_CHECK_ARG(d_in && d_out && n > 0 && h_in > 0 && w_in > 0 && c > 0, "maxpool: bad argument");
+    return launch_maxpool(d_in, d_out, n, h_in, w_in, c, dtype, static_cast<hipStream_t>(stream));
+}
+
+int64_t metro_softargmax_scratch_bytes(int32_t n, int32_t side, int32_t n_joints_head) {
+    if (n <= 0 || side <= 1 || n_joints_head <= 0) return -1;
+    return softargmax_scratch_bytes(n, side, n_joints_head);
+}
+
+int metro_softargmax(const void* d_logits, int32_t n, const MetroSpec* spec, int32_t precise,
+                     void* d_partials, float* d_poses_out, void* stream) {
+    METRO_CHECK_ARG(d_logits && spec && d_partials && d_poses_out && n > 0, "softargmax: bad argument");
+    METRO_CHECK_ARG(spec->n_joints_head >= 1 && spec->n_joints_head <= METRO_MAX_JOINTS &&
+                        spec->n_joints_out >= 1 && spec->n_joints_out <= METRO_MAX_JOINTS,
+                    "softargmax: joint counts out of range");
+    METRO_CHECK_ARG(spec->proc_side / spec->stride >= 2, "softargmax: heat-map side must be >= 2");
+    const SoftArgmaxArgs a = make_softargmax_args(*spec, n);
+    return launch_softargmax(d_logits, a, precise, d_partials, d_poses_out, static_cast<hipStream_t>(stream));
+}
+
+int64_t metro_head_f16_scratch_bytes(int32_t n, int32_t side, int32_t n_joints_head) {
+    if (n <= 0 || side <= 1 || n_joints_head <= 0) return -1;
+    return (int64_t)n * head_f16_slabs(side) * n_joints_head * 5 * (int64_t)sizeof(float);
+}
+
+int metro_head_f16(const void* d_x, const void* d_w, const float* d_bias, const void* d_pro_scale, const void* d_pro_shift,
+                   int32_t n, int32_t c_in, const MetroSpec* spec, void* d_partials, float* d_logits_out, float* d_poses_out,
+                   void* stream) {
+    METRO_CHECK_ARG(d_x && d_w && d_bias && d_pro_scale && d_pro_shift && spec && d_partials && d_poses_out && n > 0,
+                    "head_f16: bad argument");
+    METRO_CHECK_ARG(spec->n_joints_head >= 1 && spec->n_joints_head <= METRO_MAX_JOINTS && spec->n_joints_out >= 1 &&
+                        spec->n_joints_out <= METRO_MAX_JOINTS, "head_f16: joint counts out of range");
+    METRO_CHECK_ARG((spec->depth * spec->n_joints_head) % 4 == 0, "head_f16: depth*n_joints_head must be a multiple of 4");
+    const int side = spec->proc_side / spec->stride;
+    const SoftArgmaxArgs a = make_softargmax_args(*spec, n);
+    int st = launch_head_f16(d_x, d_w, d_bias, d_pro_scale, d_pro_shift, n, c_in, spec->depth * spec->n_joints_head,
+                             spec->n_joints_head, spec->depth, side, static_cast<float*>(d_partials), d_logits_out,
+                             static_cast<hipStream_t>(stream));
+    if (st) return st;
+    return launch_softargmax_finalize(static_cast<const float*>(d_partials), a,
+                                      head_f16_records(n, c_in, spec->depth * spec->n_joints_head, side), d_poses_out,
+                                      static_cast<hipStream_t>(stream));
+}
+
+int metro_softargmax01(const void* d_logits, int32_t n, const MetroSpec* spec, int32_t precise, void* d_partials,
+                       float* d_coords01_out, void* stream) {
+    METRO_CHECK_ARG(d_logits && spec && d_partials && d_coords01_out && n > 0, "softargmax01: bad argument");
+    METRO_CHECK_ARG(spec->n_joints_head >= 1 && spec->n_joints_head <= METRO_MAX_JOINTS, "softargmax01: joint count out of range");
+    METRO_CHECK_ARG(spec->proc_side / spec->stride >= 2, "softargmax01: heat-map side must be >= 2");
+    const SoftArgmaxArgs a = make_softargmax_args(*spec, n);
+    return launch_softargmax(d_logits, a, precise, d_partials, nullptr, static_cast<hipStream_t>(stream), d_coords01_out);
+}
+
+static int check_head_args(const MetroSpec* spec, int32_t n, int32_t n_edges, const char* what) {
+    METRO_CHECK_ARG(spec != nullptr && n > 0, "%s: bad argument", what);
+    // METRO_MAX_JOINTS is the length of the kernels' per-lane joint and edge arrays (HEAD_MAX, backproject.h)
+    METRO_CHECK_ARG(spec->n_joints_head >= 1 && spec->n_joints_head <= METRO_MAX_JOINTS && spec->n_joints_out >= 1 &&
+                        spec->n_joints_out <= METRO_MAX_JOINTS, "%s: joint counts out of range (<= %d)", what, METRO_MAX_JOINTS);
+    METRO_CHECK_ARG(n_edges >= 0 && n_edges <= METRO_MAX_JOINTS, "%s: at most %d stick-figure edges (got %d)", what,
+                    METRO_MAX_JOINTS, n_edges);
+    return METRO_OK;
+}
+
+int metro_backproject_bone_lengths(const float* d_coords01, const float* d_inv_intrinsics, const double* d_bone_lengths,
+                                   int32_t per_pose_lengths, const int32_t* d_edges, int32_t n_edges, int32_t n,
+                                   const MetroSpec* spec, int32_t root_relative, int32_t permute, float* d_coords3d_out,
+                                   float* d_z_offset_out, void* stream) {
+    int st = check_head_args(spec, n, n_edges, "backproject_bone_lengths");
+    if (st) return st;
+    METRO_CHECK_ARG(d_coords01 && d_inv_intrinsics && d_bone_lengths && d_edges && d_coords3d_out && n_edges >= 1,
+                    "backproject_bone_lengths: NULL tensor pointer or no edges");
+    return launch_backproject(d_coords01, d_inv_intrinsics, d_bone_lengths, per_pose_lengths != 0, nullptr, d_edges, n,
+                              spec->n_joints_head, n_edges, *spec, root_relative, permute, d_coords3d_out, d_z_offset_out,
+                              static_cast<hipStream_t>(stream));
+}
+
+int metro_backproject_root_depth(const float* d_coords01, const float* d_inv_intrinsics, const float* d_root_z, int32_t n,
+                                 const MetroSpec* spec, int32_t root_relative, int32_t permute, float* d_coords3d_out,
+                                 void* stream) {
+    int st = check_head_args(spec, n, 0, "backproject_root_depth");
+    if (st) return st;
+    METRO_CHECK_ARG(d_coords01 && d_inv_intrinsics && d_root_z && d_coords3d_out, "backproject_root_depth: NULL tensor pointer");
+    return launch_backproject(d_coords01, d_inv_intrinsics, nullptr, 0, d_root_z, nullptr, n, spec->n_joints_head, 0, *spec,
+                              root_relative, permute, d_coords3d_out, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int metro_heatmap_to_25d(const float* d_coords01, int32_t n, const MetroSpec* spec, float* d_out, void* stream) {
+    int st = check_head_args(spec, n, 0, "heatmap_to_25d");
+    if (st) return st;
+    METRO_CHECK_ARG(d_coords01 && d_out, "heatmap_to_25d: NULL tensor pointer");
+    return launch_heatmap_to_25d(d_coords01, d_out, n, *spec, static_cast<hipStream_t>(stream));
+}
+
+int metro_to_orig_cam(const float* d_coords, const float* d_rot, const int32_t* d_mirror, float* d_out, int32_t n,
+                      int32_t n_joints, void* stream) {
+    METRO_CHECK_ARG(d_coords && d_rot && d_mirror && d_out && n > 0 && n_joints >= 1 && n_joints <= METRO_MAX_JOINTS,
+                    "to_orig_cam: bad argument (1 <= joints <= %d)", METRO_MAX_JOINTS);
+    return launch_to_orig_cam(d_coords, d_rot, d_mirror, d_out, n, n_joints, static_cast<hipStream_t>(stream));
+}
+
+int metro_place_poses(const float* d_coords01, const float* d_poses, const MetroPlacement* d_records, int32_t n,
+                      const MetroSpec* spec, int32_t scale_recovery, const double* d_bone_lengths, int32_t per_pose_lengths,
+                      const float* d_root_depth, const int32_t* d_edges, int32_t n_edges, const int32_t* d_mirror,
+                      int32_t coords, float* d_poses_out, float* d_keypoints_out, float* d_z_offset_out, void* stream) {
+    const bool bones = scale_recovery == METRO_SCALE_BONE_LENGTHS;
+    int st = check_head_args(spec, n, bones ? n_edges : 0, "place_poses");
+    if (st) return st;
+    METRO_CHECK_ARG(scale_recovery >= METRO_SCALE_METRO && scale_recovery <= METRO_SCALE_TRUE_ROOT_DEPTH,
+                    "place_poses: scale_recovery must be METRO_SCALE_METRO, _BONE_LENGTHS or _TRUE_ROOT_DEPTH (got %d)", scale_recovery);
+    METRO_CHECK_ARG(coords >= METRO_COORDS_CROP && coords <= METRO_COORDS_WORLD,
+                    "place_poses: coords must be METRO_COORDS_CROP, _CAMERA or _WORLD (got %d)", coords);
+    METRO_CHECK_ARG(d_coords01 && d_records && d_poses_out && (coords == METRO_COORDS_CROP || d_mirror),
+                    "place_poses: NULL coords01 / records / poses_out / mirror pointer");
+    METRO_CHECK_ARG(scale_recovery != METRO_SCALE_METRO || d_poses, "place_poses: METRO_SCALE_METRO reads the engine's poses: NULL");
+    METRO_CHECK_ARG(!bones || (d_bone_lengths && d_edges && n_edges >= 1), "place_poses: bone-lengths needs lengths and >= 1 edge");
+    METRO_CHECK_ARG(scale_recovery != METRO_SCALE_TRUE_ROOT_DEPTH || d_root_depth, "place_poses: true-root-depth needs root depths");
+    return launch_place_poses(d_coords01, d_poses, d_records, n, *spec, scale_recovery, d_bone_lengths, per_pose_lengths != 0,
+                              d_root_depth, d_edges, bones ? n_edges : 0, d_mirror, coords, d_poses_out, d_keypoints_out,
+                              d_z_offset_out, static_cast<hipStream_t>(stream));
+}
+
+int metro_expand_views(const MetroViewBase* d_bases, int32_t n, const MetroView* views, int32_t n_views, int32_t side,
+                       MetroCropWarp* d_crops_out, MetroPlacement* d_placements_out, void* stream) {
+    METRO_CHECK_ARG(d_bases && views && d_crops_out && d_placements_out, "expand_views: NULL pointer");
+    METRO_CHECK_ARG(n > 0 && side > 0, "expand_views: bad geometry (n %d side %d)", n, side);
+    METRO_CHECK_ARG(n_views >= 1 && n_views <= METRO_MAX_VIEWS, "expand_views: %d views (1 to %d per launch)", n_views,
+                    METRO_MAX_VIEWS);
+    METRO_CHECK_ARG((int64_t)n * n_views <= INT32_MAX, "expand_views: %d boxes x %d views overflow int32", n, n_views);
+    for (int v = 0; v < n_views; ++v) {
+        const MetroView& w = views[v];
+        METRO_CHECK_ARG(std::isfinite(w.cos_roll) && std::isfinite(w.sin_roll) && std::isfinite(w.zoom) && w.zoom > 0.0,
+                        "expand_views: view %d: cos / sin of the roll must be finite and the zoom finite and > 0", v);
+        METRO_CHECK_ARG(w.flip == 0 || w.flip == 1, "expand_views: view %d: flip must be 0 or 1 (got %d)", v, w.flip);
+    }
+    return launch_expand_views(d_bases, n, views, n_views, side, d_crops_out, d_placements_out, static_cast<hipStream_t>(stream));
+}
+
+int metro_look_at_boxes(const double* d_boxes, const int32_t* d_frame_index, int32_t n, int32_t n_frames,
+                        const MetroFrameCamera* d_cameras, int32_t n_cameras, int32_t side, MetroViewBase* d_bases_out,
+                        int32_t* d_status, void* stream) {
+    METRO_CHECK_ARG(d_boxes && d_frame_index && d_bases_out && d_status, "look_at_boxes: NULL boxes / frame_index / bases_out / "
+                    "status pointer");
+    METRO_CHECK_ARG(n > 0 && side > 0, "look_at_boxes: bad geometry (n %d side %d)", n, side);
+    METRO_CHECK_ARG(n_frames >= 1 && n_frames <= METRO_MAX_FRAMES, "look_at_boxes: %d frames (1 to %d per launch)", n_frames,
+                    METRO_MAX_FRAMES);
+    METRO_CHECK_ARG(d_cameras ? (n_cameras == 1 || n_cameras == n_frames) : n_cameras == 0,
+                    "look_at_boxes: %d cameras for %d frames (one for every frame, one per frame, or none with a NULL table)",
+                    n_cameras, n_frames);
+    return launch_look_at_boxes(d_boxes, d_frame_index, n, n_frames, d_cameras, n_cameras, side, d_bases_out, d_status,
+                                static_cast<hipStream_t>(stream));
+}
+
+int metro_merge_views(const float* d_poses, const float* d_keypoints, const float* d_z_offset, const MetroPlacement* d_records,
+                      const int32_t* d_mirror, int32_t n, int32_t n_views, int32_t n_joints, float* d_poses_out,
+                      float* d_keypoints_out, float* d_z_offset_out, float* d_spread_out, void* stream) {
+    METRO_CHECK_ARG(d_poses && d_poses_out, "merge_views: NULL poses / poses_out pointer");
+    METRO_CHECK_ARG(!d_keypoints == !d_keypoints_out, "merge_views: keypoints and keypoints_out go together");
+    METRO_CHECK_ARG(!d_z_offset == !d_z_offset_out, "merge_views: z_offset and z_offset_out go together");
+    METRO_CHECK_ARG(!d_keypoints || (d_records && d_mirror), "merge_views: keypoints need the records and the mirror table");
+    METRO_CHECK_ARG(n > 0 && n_joints >= 1 && n_joints <= METRO_MAX_JOINTS, "merge_views: bad sizes (n %d, joints %d; 1 <= joints <= %d)",
+                    n, n_joints, METRO_MAX_JOINTS);
+    METRO_CHECK_ARG(n_views >= 1 && n_views <= METRO_MAX_VIEWS, "merge_views: %d views (1 to %d)", n_views, METRO_MAX_VIEWS);
+    METRO_CHECK_ARG((int64_t)n * n_views * n_joints * 3 <= INT32_MAX && (int64_t)n * n_joints <= INT32_MAX,
+                    "merge_views: %d boxes x %d views overflow int32", n, n_views);
+    return launch_merge_views(d_poses, d_keypoints, d_z_offset, d_records, d_mirror, n, n_views, n_joints, d_poses_out,
+                              d_keypoints_out, d_z_offset_out, d_spread_out, static_cast<hipStream_t>(stream));
+}
+
+const char* metro_last_error(void) { return metro::get_error(); }
+int32_t metro_abi_version(void) { return METRO_ABI_VERSION; }
+
+}  // extern "C"

@@ -1,0 +1,254 @@
+// Executor of libmetro_hip.so: runs the layer list planner.cpp built -- one launch per layer, eagerly or as a captured hipGraph.
+#include <vector>
+
+#include "plan.h"
+
+using namespace metro;
+
+namespace {
+
+// One layer of the plan at batch n.  `dump` (metro_forward_upto stopping at this layer): launches whose intermediate tensors live on
+// chip also write them out -- the fp32 logits of the one-launch head, conv1's output of a conv1+conv2 launch.
+// `coords01` (optional): the finalize launch also writes the soft-argmax coordinates in [0,1] there (metro_forward_coords01).
+int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* images, int n, float* poses, char* ws, hipStream_t stream, bool dump,
+                 float* coords01 = nullptr) {
+    const Layer& L = p->layers[li];
+    auto slot_ptr = [&](int slot) -> void* {
+        if (slot == S_IMAGES) return const_cast<float*>(images);
+        if (slot < 0) return nullptr;
+        return ws + p->slot_offset[slot];
+    };
+    auto prm = [&](int idx) -> const void* { return idx < 0 ? nullptr : d_params + p->params[idx].offset; };
+    switch (L.kind) {
+        case LK_PREP:
+            return launch_prep_input_f16(images, n, p->spec.proc_side, slot_ptr(L.out_slot), stream);
+        case LK_POOL:
+            return launch_maxpool(slot_ptr(L.in_slot), slot_ptr(L.out_slot), n, L.cd.h_in, L.cd.w_in, L.cd.c_in, p->act_dtype, stream);
+        case LK_CONV: {
+            MetroConvDesc cd = L.cd;
+            cd.n = n;
+            auto fprm = [&](int idx) { return static_cast<const float*>(prm(idx)); };
+            void* in = slot_ptr(L.in_slot);
+            void* out = slot_ptr(L.out_slot);
+            const void* w = prm(L.main.w);
+            const float* bias = fprm(L.main.bias);
+            ConvFused f;
+            switch (L.form) {
+                case LayerForm::Head: {
+                    float* logits_dump = dump ? static_cast<float*>(out) : nullptr;
+                    return launch_head_f16(in, w, bias, prm(L.main.scale), prm(L.main.shift), n, L.cd.c_in, L.cd.c_out, p->spec.n_joints_head,
+                                           p->spec.depth, L.cd.h_in, static_cast<float*>(slot_ptr(S_PART)), logits_dump, stream);
+                }
+                case LayerForm::StemPoolF32In:
+                    return launch_stem_pool_f32in(images, w, bias, out, n, p->spec.proc_side, stream);
+                case LayerForm::StemPool:
+                    return launch_stem_pool_f16(in, w, bias, out, n, p->spec.proc_side, stream);
+                case LayerForm::Conv1Conv2: {
+                    ConvPre1 p1;
+                    p1.w1 = prm(L.conv1.w); p1.bias1 = fprm(L.conv1.bias);
+                    p1.pro_scale = prm(L.conv1.scale); p1.pro_shift = prm(L.conv1.shift);
+                    p1.t1_dump = dump ? slot_ptr(S_T1) : nullptr;        // conv1's output exists in LDS only; layer dumps get a copy
+                    return launch_conv3x3_c64(cd, in, w, bias, out, stream, &p1);
+                }
+                case LayerForm::Plain:
+                    if (p->fast)
+                        return launch_conv_f16(cd, in, w, bias, prm(L.main.scale), prm(L.main.shift), slot_ptr(L.res_slot), out, stream);
+                    if (p->spec.precision == METRO_PREC_F32M)
+                        return launch_conv_f32m(cd, in, static_cast<const float*>(w), bias, fprm(L.main.scale), fprm(L.main.shift),
+                                                slot_ptr(L.res_slot), out, stream);
+                    return launch_conv_f64acc(cd, in, static_cast<const double*>(w), static_cast<const double*>(prm(L.main.bias)),
+                                              static_cast<const double*>(prm(L.main.scale)), static_cast<const double*>(prm(L.main.shift)),
+                                              slot_ptr(L.res_slot), out, stream);
+                case LayerForm::Pair:
+                    f.form = ConvForm::Pair;
+                    f.pair = {L.cd.c_out - L.c2, L.c2, 1, slot_ptr(L.out2_slot)};
+                    return launch_conv_f16_dma(cd, in, w, bias, prm(L.main.scale), prm(L.main.shift), nullptr, out, stream, f);
+                case LayerForm::Next:
+                case LayerForm::NextProj:
+                case LayerForm::NextRebuild:
+                    f.form = conv_form(L.form);
+                    f.next = {prm(L.next.w), fprm(L.next.bias), prm(L.next.scale), prm(L.next.shift), slot_ptr(L.out2_slot), L.c2};
+                    if (f.form != ConvForm::Next)
+                        f.psc = {slot_ptr(L.psc_slot), prm(L.psc.w), fprm(L.psc.bias), prm(L.psc.scale), prm(L.psc.shift)};
+                    if (f.form == ConvForm::NextRebuild) {
+                        f.rb.t2_prev = slot_ptr(L.reb_slot); f.rb.w3_prev = prm(L.reb.w); f.rb.bias3_prev = fprm(L.reb.bias);
+                    }
+                    // block1 without its residual stream in HBM: metro_forward_upto stopping here (dump) stores the sum in full, on the
+                    // classic kernel
+                    f.rb.out_mode = dump ? 0 : L.out_mode;
+                    f.rb.classic = dump ? 1 : 0;
+                    if (f.rb.out_mode == 2) { f.rb.out_sub = slot_ptr(L.sub_slot); f.rb.sub_off = L.sub_off; f.rb.h_sub = f.rb.w_sub = L.sub_side; }
+                    return launch_conv_f16_dma(cd, in, w, bias, nullptr, nullptr, slot_ptr(L.res_slot), out, stream, f);
+            }
+            break;
+        }
+        case LK_SOFTARGMAX: {
+            if (poses == nullptr) { set_error("metro_forward: poses_out is NULL"); return METRO_ERR_INVALID_ARG; }
+            const SoftArgmaxArgs a = make_softargmax_args(p->spec, n);
+            if (L.form == LayerForm::Head)
+                return launch_softargmax_finalize(static_cast<const float*>(slot_ptr(S_PART)), a,
+                                                  head_f16_records(n, L.head_c_in, a.depth * a.n_joints_head, a.side), poses, stream, coords01,
+                                                  static_cast<int32_t*>(slot_ptr(S_STATUS)));
+            // precise: 0 fp32 / fp32, 1 fp32 logits + fp64 accumulators (F32 and F32M modes), 2 fp64 / fp64
+            return launch_softargmax(slot_ptr(L.in_slot), a, p->spec.precision == METRO_PREC_F32M ? 1 : p->spec.precision, slot_ptr(S_PART), poses, stream,
+                                     coords01, static_cast<int32_t*>(slot_ptr(S_STATUS)));
+        }
+    }
+    set_error("internal: layer %d has unknown kind %d", li, L.kind);
+    return METRO_ERR_STATE;
+}
+
+int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_, hipStream_t stream,
+               int last_layer, float* ms_out, float* coords01 = nullptr) {
+    METRO_CHECK_ARG(p != nullptr, "plan is NULL");
+    METRO_CHECK_ARG(n > 0 && n <= p->max_batch, "batch %d outside [1, %d]", n, p->max_batch);
+    METRO_CHECK_ARG(images != nullptr && ws_ != nullptr, "NULL images/workspace pointer");
+    if (p->d_params == nullptr) { set_error("metro_forward: parameters not bound (metro_plan_bind_params)"); return METRO_ERR_STATE; }
+    char* ws = static_cast<char*>(ws_);
+    const int nl = (int)p->layers.size();
+    if (last_layer < 0 || last_layer >= nl) last_layer = nl - 1;
+
+    std::vector<hipEvent_t> ev;
+    if (ms_out) {
+        ev.resize(2 * (last_layer + 1));
+        for (auto& e : ev) METRO_HIP_CHECK(hipEventCreate(&e));
+    }
+    int st = METRO_OK;
+    for (int li = 0; li <= last_layer && st == METRO_OK; ++li) {
+        if (ms_out) METRO_HIP_CHECK(hipEventRecord(ev[2 * li], stream));
+        st = launch_layer(p, p->d_params, li, images, n, poses, ws, stream, li == last_layer && li + 1 < nl, coords01);
+        if (ms_out) METRO_HIP_CHECK(hipEventRecord(ev[2 * li + 1], stream));
+    }
+    if (ms_out) {
+        if (st == METRO_OK) {
+            METRO_HIP_CHECK(hipEventSynchronize(ev.back()));
+            for (int li = 0; li <= last_layer; ++li) {
+                float ms = 0.f;
+                METRO_HIP_CHECK(hipEventElapsedTime(&ms, ev[2 * li], ev[2 * li + 1]));
+                ms_out[li] += ms;
+            }
+        }
+        for (auto& e : ev) (void)hipEventDestroy(e);
+    }
+    return st;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------
+extern "C" {
+
+int metro_plan_layer_kernel(const MetroPlan* plan, int32_t index, int32_t n, char* buf, int32_t buf_len) {
+    METRO_CHECK_ARG(plan && buf && buf_len > 1 && index >= 0 && index < (int)plan->layers.size(), "metro_plan_layer_kernel: bad argument");
+    METRO_CHECK_ARG(n > 0 && n <= plan->max_batch, "metro_plan_layer_kernel: batch %d outside [1, %d]", n, plan->max_batch);
+    // dry run of the layer's dispatch: the leaf launcher records the instantiation it would launch and returns
+    KernelNotes& kn = kernel_notes();
+    const KernelNotes saved = kn;
+    kn.mode = 2; kn.ids[0] = 0;
+    static const char fake = 0;                       // pointers are never dereferenced in a dry run (launch_status asserts it)
+    float dummy_poses = 0.f;
+    const int st = launch_layer(plan, &fake, index, reinterpret_cast<const float*>(&fake), n, &dummy_poses,
+                                const_cast<char*>(&fake), nullptr, false);
+    snprintf(buf, (size_t)buf_len, "%s", kn.ids);
+    kn = saved;
+    return st;
+}
+
+int metro_plan_bind_params(MetroPlan* plan, const void* d_param_blob) {
+    METRO_CHECK_ARG(plan && d_param_blob, "metro_plan_bind_params: NULL argument");
+    METRO_CHECK_ARG(((uintptr_t)d_param_blob & 255) == 0, "parameter blob must be 256-byte aligned");
+    plan->d_params = static_cast<const char*>(d_param_blob);
+    // captured forwards bake the OLD blob's pointers into their kernel arguments: drop them
+    for (GraphEntry& g : plan->graphs)
+        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    plan->graphs.clear();
+    return METRO_OK;
+}
+
+int metro_plan_set_graph_max_batch(MetroPlan* plan, int32_t max_batch_for_graphs) {
+    METRO_CHECK_ARG(plan != nullptr && max_batch_for_graphs >= 0, "metro_plan_set_graph_max_batch: bad argument");
+    plan->graph_max_batch = max_batch_for_graphs;
+    return METRO_OK;
+}
+
+static int forward_impl(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out, float* d_coords01,
+                        void* d_workspace, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (plan == nullptr || n > plan->graph_max_batch || n < 1)
+        return run_layers(plan, d_images_nhwc, n, d_poses_out, d_workspace, stream, -1, nullptr, d_coords01);
+    // small batches are launch-latency bound (57 dependent launches): replay a captured hipGraph
+    GraphEntry* hit = nullptr;
+    for (GraphEntry& g : plan->graphs)
+        if (g.n == n && g.images == d_images_nhwc && g.poses == d_poses_out && g.coords01 == d_coords01 && g.ws == d_workspace)
+            hit = &g;
+    if (hit == nullptr) {
+        if (plan->graphs.size() >= 16) {            // bounded cache: drop the oldest capture
+            if (plan->graphs.front().exec) (void)hipGraphExecDestroy(plan->graphs.front().exec);
+            plan->graphs.erase(plan->graphs.begin());
+        }
+        plan->graphs.push_back(GraphEntry{n, d_images_nhwc, d_poses_out, d_coords01, d_workspace, stream, nullptr, 0});
+        hit = &plan->graphs.back();
+    }
+    if (hit->exec == nullptr) {
+        if (hit->eager_runs == 0) {                  // first sight of this key: plain launches (sets kernel attributes)
+            hit->eager_runs = 1;
+            return run_layers(plan, d_images_nhwc, n, d_poses_out, d_workspace, stream, -1, nullptr, d_coords01);
+        }
+        hipGraph_t graph = nullptr;
+        if (plan->cap_stream == nullptr) METRO_HIP_CHECK(hipStreamCreateWithFlags(&plan->cap_stream, hipStreamNonBlocking));
+        METRO_HIP_CHECK(hipStreamBeginCapture(plan->cap_stream, hipStreamCaptureModeThreadLocal));
+        const int st = run_layers(plan, d_images_nhwc, n, d_poses_out, d_workspace, plan->cap_stream, -1, nullptr, d_coords01);
+        const hipError_t e = hipStreamEndCapture(plan->cap_stream, &graph);
+        if (st != METRO_OK) { if (graph) (void)hipGraphDestroy(graph); return st; }
+        if (e != hipSuccess) { set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return METRO_ERR_HIP; }
+        const hipError_t ei = hipGraphInstantiate(&hit->exec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        if (ei != hipSuccess) { hit->exec = nullptr; set_error("hipGraphInstantiate: %s", hipGetErrorString(ei)); return METRO_ERR_HIP; }
+    }
+    METRO_HIP_CHECK(hipGraphLaunch(hit->exec, stream));
+    return METRO_OK;
+}
+
+int metro_forward(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out,
+                  void* d_workspace, void* stream) {
+    return forward_impl(plan, d_images_nhwc, n, d_poses_out, nullptr, d_workspace, stream);
+}
+
+int metro_forward_coords01(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out,
+                           float* d_coords01_out, void* d_workspace, void* stream) {
+    METRO_CHECK_ARG(d_coords01_out != nullptr && d_poses_out != nullptr, "metro_forward_coords01: NULL poses / coords01 pointer");
+    return forward_impl(plan, d_images_nhwc, n, d_poses_out, d_coords01_out, d_workspace, stream);
+}
+
+int metro_forward_status(const MetroPlan* plan, const void* d_workspace, int32_t n, void* stream_, int32_t* n_nonfinite_out) {
+    METRO_CHECK_ARG(plan && d_workspace && n_nonfinite_out, "metro_forward_status: NULL argument");
+    METRO_CHECK_ARG(n > 0 && n <= plan->max_batch, "metro_forward_status: batch %d outside [1, %d]", n, plan->max_batch);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    std::vector<int32_t> host((size_t)n);
+    METRO_HIP_CHECK(hipMemcpyAsync(host.data(), static_cast<const char*>(d_workspace) + plan->slot_offset[S_STATUS], (size_t)n * 4,
+                                   hipMemcpyDeviceToHost, stream));
+    METRO_HIP_CHECK(hipStreamSynchronize(stream));
+    int32_t bad = 0;
+    for (int32_t v : host) bad += v != 0;
+    *n_nonfinite_out = bad;
+    if (bad) {
+        set_error("%d of %d crops reached the soft-argmax with non-finite statistics%s", bad, n,
+                  plan->spec.precision == METRO_PREC_F16 ? " (fp16 storage overflows at 65504: run this model with precision f32m or f64)" : "");
+        return METRO_ERR_NONFINITE;
+    }
+    return METRO_OK;
+}
+
+
+int metro_forward_upto(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out,
+                       void* d_workspace, void* stream, int32_t last_layer) {
+    return run_layers(plan, d_images_nhwc, n, d_poses_out, d_workspace, static_cast<hipStream_t>(stream), last_layer, nullptr);
+}
+
+int metro_forward_timed(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out,
+                        void* d_workspace, void* stream, float* ms_out) {
+    METRO_CHECK_ARG(ms_out != nullptr, "metro_forward_timed: ms_out is NULL");
+    return run_layers(plan, d_images_nhwc, n, d_poses_out, d_workspace, static_cast<hipStream_t>(stream), -1, ms_out);
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 """Model spec, unit schedule, decode constants and joint tables of the exported graph.
 
 TEST INFRASTRUCTURE (see oracle/__init__.py).  Restates, independently of the product's C++
-planner (metro_pose3d_amd/csrc/plan.cpp), the control flow of:
+planner (metro_pose3d_amd/csrc/planner.cpp), the control flow of:
   * reference src/model/resnet_v2.py:272-312   (block tables, which unit is "centered")
   * reference src/model/resnet_utils.py:307-348 (stack_blocks_dense: stride/rate schedule)
   * reference src/model/volumetric.py:288-295   (decode constants)

@@ -27,7 +27,7 @@ TensorFlow is ABSENT.  What stands in for it, and therefore what this file does 
   -> (in - k_eff) // stride + 1).  No arithmetic is pinned by part A.  What is: which ops the reference creates, in which
   order, wired to which tensors, with which stride / rate / padding mode / explicit pad amounts / normalizer / activation /
   bias, for every (architecture, stride, centered_stride) -- i.e. KA6, KA8, KA9, KA12 of SURVEY section 8(c) as REFERENCE
-  outputs, and the unit table `oracle/spec.schedule` and `csrc/plan.cpp` are each held to (tests/test_ref_schedule.py).
+  outputs, and the unit table `oracle/spec.schedule` and `csrc/planner.cpp` are each held to (tests/test_ref_schedule.py).
 
   PART B (decode) -- NumPy under TensorFlow's names.  `tf.reshape / transpose / reduce_max / exp / reduce_sum / linspace / cast /
   squeeze / stack / concat / identity / gather` are bound to the NumPy function of the same meaning and the reference's lines

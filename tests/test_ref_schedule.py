@@ -1,5 +1,5 @@
 """The oracle's restatement of the graph's control flow (oracle/spec.py, oracle/forward.py) AND the product's planner
-(csrc/plan.cpp through metro_plan_layer_info) are each held to what the REFERENCE'S OWN Python produced when its
+(csrc/planner.cpp through metro_plan_layer_info) are each held to what the REFERENCE'S OWN Python produced when its
 graph-building functions were executed in the build container (tests/golden/make_ref_schedule.py ->
 tests/golden/ref_schedule_v1.npz: resnet_v2_50/101, resnet_v2_block, bottleneck, stack_blocks_dense, conv2d_same,
 max_pool2d_same, architectures.resnet on a recording tape; build_inference_model, net_output_to_heatmap_and_coords,
@@ -121,7 +121,7 @@ def test_oracle_schedule_equals_reference_tape(ref, cfg):
 @pytest.mark.parametrize('cfg', CONFIGS, ids=ids)
 @pytest.mark.parametrize('prec', ['f16', 'f64'])
 def test_planner_equals_reference_tape(ref, cfg, prec):
-    """csrc/plan.cpp (metro_plan_layer_info) against the reference's tape directly -- not through oracle/spec.py."""
+    """csrc/planner.cpp (metro_plan_layer_info) against the reference's tape directly -- not through oracle/spec.py."""
     arch, stride, centered = cfg
     key, runits = ref_units(ref, arch, stride, centered)
     layers = {li.name.decode(): li for li in Engine(ModelSpec(arch, stride, 'h36m', centered_stride=centered), None, prec, max_batch=1).layer_infos()}
