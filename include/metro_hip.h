@@ -307,6 +307,12 @@ int  metro_stem_pool_f16(const void* d_prepped, const void* d_w, const float* d_
  * src/model/architectures.py:29) and the stem's zero border happen on the way into LDS. */
 int  metro_stem_pool_f32in(const float* d_images, const void* d_w, const float* d_bias, void* d_out, int32_t n,
                            int32_t side, void* stream);
+/* The twin of metro_stem_pool_f32in for uint8 NHWC crops [n,side,side,3]: byte b stands for the fp32 value b / 255 (IEEE
+ * divide; normalize01, reference src/improc.py:56-61 -- what metro_warp_crop_u8 writes), so d_out has the bits of
+ * metro_stem_pool_f32in on float(b) / 255.  The same sides.  d_images must be 16-byte aligned (the 256-pixel kernel fetches
+ * whole 768-byte crop rows by LDS-DMA; every crop is a multiple of 16 bytes): METRO_ERR_INVALID_ARG otherwise. */
+int  metro_stem_pool_u8in(const uint8_t* d_images, const void* d_w, const float* d_bias, void* d_out, int32_t n,
+                          int32_t side, void* stream);
 /* fp32 or fp64 activations (in_dtype / out_dtype), fp64 weights/bias/prologue,
  * v_mfma_f64_16x16x4_f64 accumulate, one rounding to out_dtype. */
 int  metro_conv_f64acc(const MetroConvDesc* d, const void* d_in, const double* d_w,
@@ -322,6 +328,10 @@ int  metro_conv_f32m(const MetroConvDesc* d, const void* d_in, const float* d_w,
 /* fp32 NHWC [n,side,side,3] -> zero-bordered fp16 [n,side+6,side+8,4] (the stem's explicit
  * pad-3 of reference resnet_utils.py:125-135 materialised once; channel 3 is zero). */
 int  metro_prep_input_f16(const float* d_images, int32_t n, int32_t side, void* d_out, void* stream);
+/* count uint8 image values -> fp32: d_out[i] = clip(float(d_in[i]) / 255, -1, 1) with an IEEE divide (normalize01, reference
+ * src/improc.py:56-61), one elementwise launch.  The fp32 image metro_forward_u8 stands for; the way uint8 crops enter the
+ * two parity precisions (f32m, f64), whose metro_forward takes fp32. */
+int  metro_images_u8_to_f32(const uint8_t* d_in, int64_t count, float* d_out, void* stream);
 
 /* Crop pre-processing, the step before the path: n crops of one uint8
  * HWC RGB frame [h, w, 3] (row_stride bytes per row), crop i sampled through the 3x3 homography
@@ -368,6 +378,11 @@ typedef struct MetroCropWarp {
 } MetroCropWarp;                /* 160 bytes */
 int  metro_warp_crops_frames_u8(const MetroFrame* frames, int32_t n_frames, const MetroCropWarp* d_crops, int32_t n,
                                 int32_t side, float* d_out, void* stream);
+/* The same launch writing the remapped BYTE ((sum of taps * weights + 2^14) >> 15, before normalize01) instead of byte / 255:
+ * d_out uint8 NHWC [n, side, side, 3], the input contract of metro_forward_u8; 0 for a frame index outside [0, n_frames).
+ * float(d_out) / 255 is metro_warp_crops_frames_u8's output bit for bit, at a quarter of the bytes. */
+int  metro_warp_crops_frames_u8_to_u8(const MetroFrame* frames, int32_t n_frames, const MetroCropWarp* d_crops, int32_t n,
+                                      int32_t side, uint8_t* d_out, void* stream);
 
 /* metro_warp_crops_frames_u8 for frames in other pixel formats, as a decoder leaves them; the same MetroCropWarp records, modes,
  * frame-index rule and output, and frames of different formats may share one launch.  The colour conversion happens per tap
@@ -402,6 +417,9 @@ typedef struct MetroFramePlanes {
 } MetroFramePlanes;             /* 48 bytes */
 int  metro_warp_crops_frames_planes(const MetroFramePlanes* frames, int32_t n_frames, const MetroCropWarp* d_crops,
                                     int32_t n, int32_t side, float* d_out, void* stream);
+/* metro_warp_crops_frames_planes writing the remapped byte: uint8 crops as metro_warp_crops_frames_u8_to_u8 writes them. */
+int  metro_warp_crops_frames_planes_to_u8(const MetroFramePlanes* frames, int32_t n_frames, const MetroCropWarp* d_crops,
+                                          int32_t n, int32_t side, uint8_t* d_out, void* stream);
 
 /* 3x3 stride-2 max-pool over a ZERO-padded (1,1) input (reference resnet_utils.py:177-185).
  * dtype METRO_F16 / METRO_F32 / METRO_F64; c % 8 == 0 (f16), c % 4 == 0 (f32), c % 2 == 0 (f64). */
@@ -476,6 +494,17 @@ int  metro_to_orig_cam(const float* d_coords, const float* d_rot, const int32_t*
  * (metro_plan_set_graph_max_batch) are keyed on d_coords01_out too. */
 int  metro_forward_coords01(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out,
                             float* d_coords01_out, void* d_workspace, void* stream);
+/* metro_forward / metro_forward_coords01 (d_coords01_out may be NULL) on uint8 crops: d_images_nhwc uint8 [n,side,side,3],
+ * 16-byte aligned, byte b standing for the fp32 value b / 255 (IEEE divide, clipped to [-1, 1]: normalize01, reference
+ * src/improc.py:56-61; what the crop warps write), which the stem rounds to fp16 as it rounds an fp32 image value
+ * (architectures.py:29).  Poses, coords01 and status words have the bits of metro_forward_coords01 on float(b) / 255.
+ * METRO_PREC_F16 plans only: uint8 is a property of the call, the plan, its layer table, parameter blob and workspace are
+ * those of metro_forward; the first layer runs the uint8 form of its kernel (metro_stem_pool_u8in, or prep_input_f16 reading
+ * bytes where that stem is not supported) and every later launch is the same.  A plan of another precision returns
+ * METRO_ERR_INVALID_ARG: expand the crops with metro_images_u8_to_f32 and call metro_forward.  Always plain launches: the
+ * hipGraph cache of metro_plan_set_graph_max_batch does not serve this entry. */
+int  metro_forward_u8(MetroPlan* plan, const uint8_t* d_images_nhwc, int32_t n, float* d_poses_out,
+                      float* d_coords01_out, void* d_workspace, void* stream);
 /* One record per crop (host code: frames.placement_params): the crop's virtual camera and the way back to its frame. */
 typedef struct MetroPlacement {
     int32_t keypoint_mode;      /* METRO_WARP_HOMOGRAPHY: keypoints through `homography`; METRO_WARP_DISTORTED: through

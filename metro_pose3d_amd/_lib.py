@@ -133,6 +133,7 @@ SIGNATURES = {
     'metro_plan_set_graph_max_batch': (C.c_int, [_P, C.c_int32]),
     'metro_forward': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
     'metro_forward_coords01': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
+    'metro_forward_u8': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     'metro_forward_status': (C.c_int, [_P, _P, C.c_int32, _P, C.POINTER(C.c_int32)]),
     'metro_plan_status_offset': (C.c_int64, [_P]),
     'metro_forward_upto': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32]),
@@ -149,11 +150,16 @@ SIGNATURES = {
     'metro_conv_f16_next': (C.c_int, [C.POINTER(MetroConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P]),
     'metro_stem_pool_f16': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     'metro_stem_pool_f32in': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
+    'metro_stem_pool_u8in': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     'metro_prep_input_f16': (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P]),
+    'metro_images_u8_to_f32': (C.c_int, [_P, C.c_int64, _P, _P]),
     'metro_warp_crop_u8': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
     'metro_warp_crops_frames_u8': (C.c_int, [C.POINTER(MetroFrame), C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
     'metro_warp_crops_frames_planes': (C.c_int, [C.POINTER(MetroFramePlanes), C.c_int32, _P, C.c_int32, C.c_int32, _P,
                                                  _P]),
+    'metro_warp_crops_frames_u8_to_u8': (C.c_int, [C.POINTER(MetroFrame), C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
+    'metro_warp_crops_frames_planes_to_u8': (C.c_int, [C.POINTER(MetroFramePlanes), C.c_int32, _P, C.c_int32, C.c_int32, _P,
+                                                       _P]),
     'metro_eval_metrics': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_float, _P, _P, _P, _P]),
     'metro_maxpool3x3s2_zeropad': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_int32, _P]),

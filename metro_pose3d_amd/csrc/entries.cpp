@@ -220,6 +220,20 @@ int metro_stem_pool_f32in(const float* d_images, const void* d_w, const float* d
     return launch_stem_pool_f32in(d_images, d_w, d_bias, d_out, n, side, static_cast<hipStream_t>(stream));
 }
 
+int metro_stem_pool_u8in(const uint8_t* d_images, const void* d_w, const float* d_bias, void* d_out, int32_t n,
+                         int32_t side, void* stream) {
+    METRO_CHECK_ARG(d_images && d_w && d_bias && d_out, "stem_pool_u8in: NULL tensor pointer");
+    METRO_CHECK_ARG(n > 0, "stem_pool_u8in: n = %d", n);
+    METRO_CHECK_ARG(stem_pool_f32in_supported(side, 64), "stem_pool_u8in: side %d must be a multiple of 32 (and METRO_STEM_POOL / METRO_STEM_RAW != 0)", side);
+    return launch_stem_pool_u8in(d_images, d_w, d_bias, d_out, n, side, static_cast<hipStream_t>(stream));
+}
+
+int metro_images_u8_to_f32(const uint8_t* d_in, int64_t count, float* d_out, void* stream) {
+    METRO_CHECK_ARG(d_in && d_out, "images_u8_to_f32: NULL pointer");
+    METRO_CHECK_ARG(count > 0, "images_u8_to_f32: count = %lld", (long long)count);
+    return launch_images_u8_to_f32(d_in, (long)count, d_out, static_cast<hipStream_t>(stream));
+}
+
 int metro_conv_f64acc(const MetroConvDesc* d, const void* d_in, const double* d_w, const double* d_bias,
                       const double* d_pro_scale, const double* d_pro_shift, const void* d_residual,
                       void* d_out, void* stream) {
@@ -259,57 +273,84 @@ int metro_warp_crop_u8(const uint8_t* d_image, int32_t h, int32_t w, int32_t row
     return launch_warp_crop_u8(d_image, h, w, row_stride, d_homographies, d_out, n, side, static_cast<hipStream_t>(stream));
 }
 
-int metro_warp_crops_frames_u8(const MetroFrame* frames, int32_t n_frames, const MetroCropWarp* d_crops, int32_t n,
-                               int32_t side, float* d_out, void* stream) {
-    METRO_CHECK_ARG(frames && d_crops && d_out, "warp_crops_frames_u8: NULL pointer");
-    METRO_CHECK_ARG(n_frames > 0 && n_frames <= METRO_MAX_FRAMES, "warp_crops_frames_u8: %d frames (1 to %d per launch)",
+}  // extern "C"
+
+// who: the entry's name in its messages; OutT: float crops or the remapped bytes
+template <typename OutT>
+static int warp_crops_frames_entry(const char* who, const MetroFrame* frames, int32_t n_frames, const MetroCropWarp* d_crops, int32_t n,
+                                   int32_t side, OutT* d_out, void* stream) {
+    METRO_CHECK_ARG(frames && d_crops && d_out, "%s: NULL pointer", who);
+    METRO_CHECK_ARG(n_frames > 0 && n_frames <= METRO_MAX_FRAMES, "%s: %d frames (1 to %d per launch)", who,
                     n_frames, METRO_MAX_FRAMES);
-    METRO_CHECK_ARG(n > 0 && side > 0, "warp_crops_frames_u8: bad geometry (n %d side %d)", n, side);
+    METRO_CHECK_ARG(n > 0 && side > 0, "%s: bad geometry (n %d side %d)", who, n, side);
     metro::FrameTable table = {};
     for (int i = 0; i < n_frames; ++i) {
         const MetroFrame& f = frames[i];
-        METRO_CHECK_ARG(f.data, "warp_crops_frames_u8: frame %d: NULL data pointer", i);
-        METRO_CHECK_ARG(f.h <= 32767 && f.w <= 32767, "warp_crops_frames_u8: frame %d: frames larger than 32767 pixels a side "
-                        "are outside cv2.remap's short coordinates (h %d w %d)", i, f.h, f.w);
+        METRO_CHECK_ARG(f.data, "%s: frame %d: NULL data pointer", who, i);
+        METRO_CHECK_ARG(f.h <= 32767 && f.w <= 32767, "%s: frame %d: frames larger than 32767 pixels a side "
+                        "are outside cv2.remap's short coordinates (h %d w %d)", who, i, f.h, f.w);
         METRO_CHECK_ARG(f.h > 0 && f.w > 0 && f.row_stride >= 3 * f.w,
-                        "warp_crops_frames_u8: frame %d: bad geometry (h %d w %d stride %d)", i, f.h, f.w, f.row_stride);
+                        "%s: frame %d: bad geometry (h %d w %d stride %d)", who, i, f.h, f.w, f.row_stride);
         table.f[i] = f;
     }
     return launch_warp_crops_frames_u8(table, n_frames, d_crops, n, side, d_out, static_cast<hipStream_t>(stream));
 }
 
-int metro_warp_crops_frames_planes(const MetroFramePlanes* frames, int32_t n_frames, const MetroCropWarp* d_crops,
-                                   int32_t n, int32_t side, float* d_out, void* stream) {
-    METRO_CHECK_ARG(frames && d_crops && d_out, "warp_crops_frames_planes: NULL pointer");
-    METRO_CHECK_ARG(n_frames > 0 && n_frames <= METRO_MAX_FRAMES, "warp_crops_frames_planes: %d frames (1 to %d per launch)",
+template <typename OutT>
+static int warp_crops_frames_planes_entry(const char* who, const MetroFramePlanes* frames, int32_t n_frames, const MetroCropWarp* d_crops,
+                                          int32_t n, int32_t side, OutT* d_out, void* stream) {
+    METRO_CHECK_ARG(frames && d_crops && d_out, "%s: NULL pointer", who);
+    METRO_CHECK_ARG(n_frames > 0 && n_frames <= METRO_MAX_FRAMES, "%s: %d frames (1 to %d per launch)", who,
                     n_frames, METRO_MAX_FRAMES);
-    METRO_CHECK_ARG(n > 0 && side > 0, "warp_crops_frames_planes: bad geometry (n %d side %d)", n, side);
+    METRO_CHECK_ARG(n > 0 && side > 0, "%s: bad geometry (n %d side %d)", who, n, side);
     metro::FramePlanesTable table = {};
     for (int i = 0; i < n_frames; ++i) {
         const MetroFramePlanes& f = frames[i];
         METRO_CHECK_ARG(f.format >= METRO_PIX_RGB && f.format <= METRO_PIX_I420,
-                        "warp_crops_frames_planes: frame %d: unknown pixel format %d", i, f.format);
+                        "%s: frame %d: unknown pixel format %d", who, i, f.format);
         METRO_CHECK_ARG(f.matrix == METRO_YUV_BT601 || f.matrix == METRO_YUV_BT709,
-                        "warp_crops_frames_planes: frame %d: unknown colour matrix %d", i, f.matrix);
+                        "%s: frame %d: unknown colour matrix %d", who, i, f.matrix);
         const bool yuv = f.format == METRO_PIX_NV12 || f.format == METRO_PIX_I420;
         const int n_planes = f.format == METRO_PIX_I420 ? 3 : f.format == METRO_PIX_NV12 ? 2 : 1;
         for (int k = 0; k < n_planes; ++k)
-            METRO_CHECK_ARG(f.plane[k], "warp_crops_frames_planes: frame %d: NULL plane %d", i, k);
-        METRO_CHECK_ARG(f.h > 0 && f.w > 0 && f.h <= 32767 && f.w <= 32767, "warp_crops_frames_planes: frame %d: h %d w %d "
-                        "outside [1, 32767] (cv2.remap's short coordinates)", i, f.h, f.w);
+            METRO_CHECK_ARG(f.plane[k], "%s: frame %d: NULL plane %d", who, i, k);
+        METRO_CHECK_ARG(f.h > 0 && f.w > 0 && f.h <= 32767 && f.w <= 32767, "%s: frame %d: h %d w %d "
+                        "outside [1, 32767] (cv2.remap's short coordinates)", who, i, f.h, f.w);
         METRO_CHECK_ARG(!yuv || (f.h % 2 == 0 && f.w % 2 == 0),
-                        "warp_crops_frames_planes: frame %d: 4:2:0 frames need an even h and w (h %d w %d)", i, f.h, f.w);
+                        "%s: frame %d: 4:2:0 frames need an even h and w (h %d w %d)", who, i, f.h, f.w);
         const int min_stride0 = yuv ? f.w : 3 * f.w;
-        METRO_CHECK_ARG(f.stride[0] >= min_stride0, "warp_crops_frames_planes: frame %d: stride[0] %d < %d", i, f.stride[0],
+        METRO_CHECK_ARG(f.stride[0] >= min_stride0, "%s: frame %d: stride[0] %d < %d", who, i, f.stride[0],
                         min_stride0);
         if (yuv) {
             const int min_stride1 = f.format == METRO_PIX_NV12 ? f.w : f.w / 2;
-            METRO_CHECK_ARG(f.stride[1] >= min_stride1, "warp_crops_frames_planes: frame %d: stride[1] %d < %d", i,
+            METRO_CHECK_ARG(f.stride[1] >= min_stride1, "%s: frame %d: stride[1] %d < %d", who, i,
                             f.stride[1], min_stride1);
         }
         table.f[i] = f;
     }
     return launch_warp_crops_frames_planes(table, n_frames, d_crops, n, side, d_out, static_cast<hipStream_t>(stream));
+}
+
+extern "C" {
+
+int metro_warp_crops_frames_u8(const MetroFrame* frames, int32_t n_frames, const MetroCropWarp* d_crops, int32_t n,
+                               int32_t side, float* d_out, void* stream) {
+    return warp_crops_frames_entry("warp_crops_frames_u8", frames, n_frames, d_crops, n, side, d_out, stream);
+}
+
+int metro_warp_crops_frames_u8_to_u8(const MetroFrame* frames, int32_t n_frames, const MetroCropWarp* d_crops, int32_t n,
+                                     int32_t side, uint8_t* d_out, void* stream) {
+    return warp_crops_frames_entry("warp_crops_frames_u8_to_u8", frames, n_frames, d_crops, n, side, d_out, stream);
+}
+
+int metro_warp_crops_frames_planes(const MetroFramePlanes* frames, int32_t n_frames, const MetroCropWarp* d_crops,
+                                   int32_t n, int32_t side, float* d_out, void* stream) {
+    return warp_crops_frames_planes_entry("warp_crops_frames_planes", frames, n_frames, d_crops, n, side, d_out, stream);
+}
+
+int metro_warp_crops_frames_planes_to_u8(const MetroFramePlanes* frames, int32_t n_frames, const MetroCropWarp* d_crops,
+                                         int32_t n, int32_t side, uint8_t* d_out, void* stream) {
+    return warp_crops_frames_planes_entry("warp_crops_frames_planes_to_u8", frames, n_frames, d_crops, n, side, d_out, stream);
 }
 
 int metro_eval_metrics(const float* d_pred, const float* d_true, const uint8_t* d_valid, int32_t n, int32_t n_joints,

@@ -10,8 +10,9 @@ namespace {
 // One layer of the plan at batch n.  `dump` (metro_forward_upto stopping at this layer): launches whose intermediate tensors live on
 // chip also write them out -- the fp32 logits of the one-launch head, conv1's output of a conv1+conv2 launch.
 // `coords01` (optional): the finalize launch also writes the soft-argmax coordinates in [0,1] there (metro_forward_coords01).
+// `images_u8` (metro_forward_u8): `images` points to uint8 crops; the layer that reads them runs the uint8 form of its kernel.
 int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* images, int n, float* poses, char* ws, hipStream_t stream, bool dump,
-                 float* coords01 = nullptr) {
+                 float* coords01 = nullptr, bool images_u8 = false) {
     const Layer& L = p->layers[li];
     auto slot_ptr = [&](int slot) -> void* {
         if (slot == S_IMAGES) return const_cast<float*>(images);
@@ -21,6 +22,8 @@ int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* 
     auto prm = [&](int idx) -> const void* { return idx < 0 ? nullptr : d_params + p->params[idx].offset; };
     switch (L.kind) {
         case LK_PREP:
+            if (images_u8)
+                return launch_prep_input_u8_f16(reinterpret_cast<const unsigned char*>(images), n, p->spec.proc_side, slot_ptr(L.out_slot), stream);
             return launch_prep_input_f16(images, n, p->spec.proc_side, slot_ptr(L.out_slot), stream);
         case LK_POOL:
             return launch_maxpool(slot_ptr(L.in_slot), slot_ptr(L.out_slot), n, L.cd.h_in, L.cd.w_in, L.cd.c_in, p->act_dtype, stream);
@@ -40,6 +43,8 @@ int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* 
                                            p->spec.depth, L.cd.h_in, static_cast<float*>(slot_ptr(S_PART)), logits_dump, stream);
                 }
                 case LayerForm::StemPoolF32In:
+                    if (images_u8)
+                        return launch_stem_pool_u8in(reinterpret_cast<const unsigned char*>(images), w, bias, out, n, p->spec.proc_side, stream);
                     return launch_stem_pool_f32in(images, w, bias, out, n, p->spec.proc_side, stream);
                 case LayerForm::StemPool:
                     return launch_stem_pool_f16(in, w, bias, out, n, p->spec.proc_side, stream);
@@ -99,7 +104,7 @@ int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* 
 }
 
 int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_, hipStream_t stream,
-               int last_layer, float* ms_out, float* coords01 = nullptr) {
+               int last_layer, float* ms_out, float* coords01 = nullptr, bool images_u8 = false) {
     METRO_CHECK_ARG(p != nullptr, "plan is NULL");
     METRO_CHECK_ARG(n > 0 && n <= p->max_batch, "batch %d outside [1, %d]", n, p->max_batch);
     METRO_CHECK_ARG(images != nullptr && ws_ != nullptr, "NULL images/workspace pointer");
@@ -116,7 +121,7 @@ int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_
     int st = METRO_OK;
     for (int li = 0; li <= last_layer && st == METRO_OK; ++li) {
         if (ms_out) METRO_HIP_CHECK(hipEventRecord(ev[2 * li], stream));
-        st = launch_layer(p, p->d_params, li, images, n, poses, ws, stream, li == last_layer && li + 1 < nl, coords01);
+        st = launch_layer(p, p->d_params, li, images, n, poses, ws, stream, li == last_layer && li + 1 < nl, coords01, images_u8);
         if (ms_out) METRO_HIP_CHECK(hipEventRecord(ev[2 * li + 1], stream));
     }
     if (ms_out) {
@@ -218,6 +223,20 @@ int metro_forward_coords01(MetroPlan* plan, const float* d_images_nhwc, int32_t 
                            float* d_coords01_out, void* d_workspace, void* stream) {
     METRO_CHECK_ARG(d_coords01_out != nullptr && d_poses_out != nullptr, "metro_forward_coords01: NULL poses / coords01 pointer");
     return forward_impl(plan, d_images_nhwc, n, d_poses_out, d_coords01_out, d_workspace, stream);
+}
+
+int metro_forward_u8(MetroPlan* plan, const uint8_t* d_images_nhwc, int32_t n, float* d_poses_out, float* d_coords01_out,
+                     void* d_workspace, void* stream) {
+    METRO_CHECK_ARG(plan != nullptr, "metro_forward_u8: plan is NULL");
+    METRO_CHECK_ARG(plan->spec.precision == METRO_PREC_F16,
+                    "metro_forward_u8: uint8 crops run on f16 plans only; for this precision expand them with metro_images_u8_to_f32 "
+                    "and call metro_forward");
+    METRO_CHECK_ARG(d_poses_out != nullptr, "metro_forward_u8: NULL poses pointer");
+    METRO_CHECK_ARG(((uintptr_t)d_images_nhwc & 15) == 0, "metro_forward_u8: uint8 crops must start at a 16-byte aligned address (got %p)",
+                    (const void*)d_images_nhwc);
+    // eager: the captured-forward cache is keyed for metro_forward's fp32 images only
+    return run_layers(plan, reinterpret_cast<const float*>(d_images_nhwc), n, d_poses_out, d_workspace, static_cast<hipStream_t>(stream), -1,
+                      nullptr, d_coords01_out, true);
 }
 
 int metro_forward_status(const MetroPlan* plan, const void* d_workspace, int32_t n, void* stream_, int32_t* n_nonfinite_out) {

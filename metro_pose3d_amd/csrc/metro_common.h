@@ -341,6 +341,9 @@ int launch_stem_pool_f16(const void* prepped, const void* w, const float* bias, 
 bool stem_pool_f32in_supported(int side, int base_width);
 int launch_stem_pool_f32in(const float* images, const void* w, const float* bias, void* out, int n, int side,
                            hipStream_t stream);
+// same, reading uint8 NHWC3 crops (16-byte aligned; byte b = fp32 b / 255): where stem_pool_f32in_supported
+int launch_stem_pool_u8in(const unsigned char* images, const void* w, const float* bias, void* out, int n, int side,
+                          hipStream_t stream);
 // persistent weight-resident 3x3 for the 64 -> 64 channel layers (conv3x3_c64.hip)
 bool conv3x3_c64_supported(const MetroConvDesc& d);
 int launch_conv3x3_c64(const MetroConvDesc& d, const void* in, const void* w, const float* bias, void* out, hipStream_t stream,
@@ -356,14 +359,20 @@ int launch_conv_f64acc(const MetroConvDesc& d, const void* in, const double* w, 
 int launch_conv_f32m(const MetroConvDesc& d, const void* in, const float* w, const float* bias, const float* pro_scale,
                      const float* pro_shift, const void* residual, void* out, hipStream_t stream);
 int launch_prep_input_f16(const float* images, int n, int side, void* out, hipStream_t stream);
+int launch_prep_input_u8_f16(const unsigned char* images, int n, int side, void* out, hipStream_t stream);
+int launch_images_u8_to_f32(const unsigned char* in, long count, float* out, hipStream_t stream);
+// the warp launchers: OutT = float (crops in [0, 1]) or unsigned char (the remapped byte itself)
 struct FrameTable { MetroFrame f[METRO_MAX_FRAMES]; };
+template <typename OutT>
 int launch_warp_crops_frames_u8(const FrameTable& frames, int n_frames, const MetroCropWarp* crops, int n, int side,
-                                float* out, hipStream_t stream);
+                                OutT* out, hipStream_t stream);
 // 64 x 48 bytes: passed by value, inside the 4 KiB of kernel arguments
 struct FramePlanesTable { MetroFramePlanes f[METRO_MAX_FRAMES]; };
+template <typename OutT>
 int launch_warp_crops_frames_planes(const FramePlanesTable& frames, int n_frames, const MetroCropWarp* crops, int n,
-                                    int side, float* out, hipStream_t stream);
-int launch_warp_crop_u8(const unsigned char* img, int h, int w, int row_stride, const float* homs, float* out,
+                                    int side, OutT* out, hipStream_t stream);
+template <typename OutT>
+int launch_warp_crop_u8(const unsigned char* img, int h, int w, int row_stride, const float* homs, OutT* out,
                         int n, int side, hipStream_t stream);
 int launch_eval_metrics(const float* pred, const float* truth, const unsigned char* valid, int n, int nj,
                         float threshold, float* dist, float* dist_pa, double* sums, hipStream_t stream);

@@ -43,6 +43,57 @@ int launch_prep_input_f16(const float* images, int n, int side, void* out, hipSt
 }
 
 // ---------------------------------------------------------------------------------------------
+// uint8 crops (metro_forward_u8, include/metro_hip.h): byte b stands for the fp32 value fdiv_rn(float(b), 255) clipped to
+// [-1, 1] -- normalize01 (reference src/improc.py:56-61), what the crop warp below writes -- and each precision then treats it
+// as it treats an fp32 image value.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float u8_unit(unsigned b) { return fminf(fmaxf(__fdiv_rn((float)b, 255.f), -1.f), 1.f); }
+
+// prep_input_f16 from uint8 NHWC [n,side,side,3]: the bits of prep_input_f16 on the fp32 image of the bytes
+__global__ __launch_bounds__(256) void prep_input_u8_f16_kernel(const unsigned char* __restrict__ img,
+                                                                half4_t* __restrict__ out, int n, int side) {
+    const int hp = side + 6, wp = side + 8;
+    const long total = (long)n * hp * wp;
+    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total;
+         p += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(p % wp);
+        const long t = p / wp;
+        const int y = (int)(t % hp);
+        const int im = (int)(t / hp);
+        half4_t v = {(half_t)0, (half_t)0, (half_t)0, (half_t)0};
+        const int yi = y - 3, xi = x - 3;
+        if ((unsigned)yi < (unsigned)side && (unsigned)xi < (unsigned)side) {
+            const unsigned char* s = img + ((size_t)(im * side + yi) * side + xi) * 3;
+            v[0] = (half_t)u8_unit(s[0]); v[1] = (half_t)u8_unit(s[1]); v[2] = (half_t)u8_unit(s[2]);
+        }
+        out[p] = v;
+    }
+}
+
+int launch_prep_input_u8_f16(const unsigned char* images, int n, int side, void* out, hipStream_t stream) {
+    if (note_kernel("prep_input_f16<u8in>")) return METRO_OK;
+    const long total = (long)n * (side + 6) * (side + 8);
+    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL(prep_input_u8_f16_kernel, dim3(blocks), dim3(256), 0, stream, images,
+                       static_cast<half4_t*>(out), n, side);
+    return launch_status("prep_input_f16<u8in>");
+}
+
+// count bytes -> count fp32 values (metro_images_u8_to_f32): the input of the two parity precisions
+__global__ __launch_bounds__(256) void images_u8_to_f32_kernel(const unsigned char* __restrict__ in, float* __restrict__ out,
+                                                               long count) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (long)gridDim.x * blockDim.x)
+        out[i] = u8_unit(in[i]);
+}
+
+int launch_images_u8_to_f32(const unsigned char* in, long count, float* out, hipStream_t stream) {
+    if (note_kernel("images_u8_to_f32")) return METRO_OK;
+    const int blocks = (int)((count + 255) / 256 < 8192 ? (count + 255) / 256 : 8192);
+    hipLaunchKernelGGL(images_u8_to_f32_kernel, dim3(blocks), dim3(256), 0, stream, in, out, count);
+    return launch_status("images_u8_to_f32");
+}
+
+// ---------------------------------------------------------------------------------------------
 // Crop pre-processing (the step BEFORE the path): for every output pixel (x, y) of crop i, source
 // coords = H_i * [x, y, 1] (fp32, perspective divide), cv2.remap(INTER_LINEAR, BORDER_CONSTANT 0) of the UINT8 HWC frame, then
 // /255 and clip to [-1, 1]: reference src/cameralib.py:406-429 (reproject_image_fast) + src/improc.py:56-61 (normalize01).
@@ -83,11 +134,17 @@ struct PackedFetch {
 };
 
 // cv2.remap's 8-bit INTER_LINEAR / BORDER_CONSTANT 0 sample at (u, v) of the RGB image whose pixels `fetch` reads, then
-// normalize01, into o[0..2].  h, w <= 32767: a coordinate saturated to the short range (or INT_MIN >> 5 from a NaN / huge
+// normalize01, into o[0..2] -- or, for uint8 crops (OutT = unsigned char), the remapped byte itself: the value normalize01
+// would have divided, which metro_forward_u8 reads by the same rule.  h, w <= 32767: a coordinate saturated to the short range (or INT_MIN >> 5 from a NaN / huge
 // value) is outside the frame, and fetch is called for in-frame taps only.
-template <typename Fetch>
+__device__ __forceinline__ void store_sample(float* o, int c, int byte) {
+    o[c] = fminf(fmaxf(__fdiv_rn((float)byte, 255.f), -1.f), 1.f);
+}
+__device__ __forceinline__ void store_sample(unsigned char* o, int c, int byte) { o[c] = (unsigned char)byte; }
+
+template <typename Fetch, typename OutT>
 __device__ __forceinline__ void sample_taps_normalized(const Fetch& fetch, int h, int w, float u, float v,
-                                                       float* __restrict__ o) {
+                                                       OutT* __restrict__ o) {
     const int sx = cv_round_x86(__fmul_rn(u, 32.f)), sy = cv_round_x86(__fmul_rn(v, 32.f));
     const int ax = sx & 31, ay = sy & 31;
     int x0 = sx >> 5, y0 = sy >> 5;
@@ -103,19 +160,21 @@ __device__ __forceinline__ void sample_taps_normalized(const Fetch& fetch, int h
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const int byte = (acc[c] + (1 << 14)) >> 15;                  // <= 255: the weights sum to 2^15
-        o[c] = fminf(fmaxf(__fdiv_rn((float)byte, 255.f), -1.f), 1.f);
+        store_sample(o, c, byte);
     }
 }
 
 // The sample of a uint8 HWC RGB frame (row_stride bytes per row).
+template <typename OutT>
 __device__ __forceinline__ void sample_u8_normalized(const unsigned char* __restrict__ img, int h, int w, int row_stride,
-                                                     float u, float v, float* __restrict__ o) {
+                                                     float u, float v, OutT* __restrict__ o) {
     sample_taps_normalized(PackedFetch<false>{img, row_stride}, h, w, u, v, o);
 }
 
+template <typename OutT>
 __global__ __launch_bounds__(256) void warp_crop_u8_kernel(const unsigned char* __restrict__ img, int h, int w,
                                                            int row_stride, const float* __restrict__ homs,
-                                                           float* __restrict__ out, int n, int side) {
+                                                           OutT* __restrict__ out, int n, int side) {
     const long total = (long)n * side * side;
     for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
         const int x = (int)(p % side);
@@ -128,13 +187,16 @@ __global__ __launch_bounds__(256) void warp_crop_u8_kernel(const unsigned char* 
     }
 }
 
-int launch_warp_crop_u8(const unsigned char* img, int h, int w, int row_stride, const float* homs, float* out,
+template <typename OutT>
+int launch_warp_crop_u8(const unsigned char* img, int h, int w, int row_stride, const float* homs, OutT* out,
                         int n, int side, hipStream_t stream) {
     const long total = (long)n * side * side;
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(warp_crop_u8_kernel, dim3(blocks), dim3(256), 0, stream, img, h, w, row_stride, homs, out, n, side);
+    hipLaunchKernelGGL(warp_crop_u8_kernel<OutT>, dim3(blocks), dim3(256), 0, stream, img, h, w, row_stride, homs, out, n, side);
     return launch_status("warp_crop_u8");
 }
+template int launch_warp_crop_u8<float>(const unsigned char*, int, int, int, const float*, float*, int, int, hipStream_t);
+template int launch_warp_crop_u8<unsigned char>(const unsigned char*, int, int, int, const float*, unsigned char*, int, int, hipStream_t);
 
 // ---------------------------------------------------------------------------------------------
 // Crops from many frames in one launch (metro_warp_crops_frames_u8, include/metro_hip.h).  Same thread layout and sampling
@@ -173,9 +235,10 @@ __device__ __forceinline__ void distorted_coords(const MetroCropWarp& c, float f
     v = __fmaf_rn(py, K[4], px * K[3]) + K[5];
 }
 
+template <typename OutT>
 __global__ __launch_bounds__(256) void warp_crops_frames_u8_kernel(const FrameTable frames, int n_frames,
                                                                    const MetroCropWarp* __restrict__ crops,
-                                                                   float* __restrict__ out, int n, int side) {
+                                                                   OutT* __restrict__ out, int n, int side) {
     const long total = (long)n * side * side;
     for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
         const int x = (int)(p % side);
@@ -183,9 +246,9 @@ __global__ __launch_bounds__(256) void warp_crops_frames_u8_kernel(const FrameTa
         const int y = (int)(t % side);
         const MetroCropWarp& c = crops[t / side];
         const int fi = c.frame;
-        float* o = out + p * 3;
+        OutT* o = out + p * 3;
         if ((unsigned)fi >= (unsigned)n_frames) {
-            o[0] = o[1] = o[2] = 0.f;
+            o[0] = o[1] = o[2] = OutT(0);
             continue;
         }
         const MetroFrame& f = frames.f[fi];
@@ -198,14 +261,17 @@ __global__ __launch_bounds__(256) void warp_crops_frames_u8_kernel(const FrameTa
     }
 }
 
+template <typename OutT>
 int launch_warp_crops_frames_u8(const FrameTable& frames, int n_frames, const MetroCropWarp* crops, int n, int side,
-                                float* out, hipStream_t stream) {
+                                OutT* out, hipStream_t stream) {
     const long total = (long)n * side * side;
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(warp_crops_frames_u8_kernel, dim3(blocks), dim3(256), 0, stream, frames, n_frames, crops, out, n,
+    hipLaunchKernelGGL(warp_crops_frames_u8_kernel<OutT>, dim3(blocks), dim3(256), 0, stream, frames, n_frames, crops, out, n,
                        side);
     return launch_status("warp_crops_frames_u8");
 }
+template int launch_warp_crops_frames_u8<float>(const FrameTable&, int, const MetroCropWarp*, int, int, float*, hipStream_t);
+template int launch_warp_crops_frames_u8<unsigned char>(const FrameTable&, int, const MetroCropWarp*, int, int, unsigned char*, hipStream_t);
 
 // ---------------------------------------------------------------------------------------------
 // Crops from frames in several pixel formats in one launch (metro_warp_crops_frames_planes, include/metro_hip.h).  The thread
@@ -253,9 +319,10 @@ struct Yuv420Fetch {
     }
 };
 
+template <typename OutT>
 __global__ __launch_bounds__(256) void warp_crops_frames_planes_kernel(const FramePlanesTable frames, int n_frames,
                                                                        const MetroCropWarp* __restrict__ crops,
-                                                                       float* __restrict__ out, int n, int side) {
+                                                                       OutT* __restrict__ out, int n, int side) {
     const long total = (long)n * side * side;
     for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
         const int x = (int)(p % side);
@@ -263,9 +330,9 @@ __global__ __launch_bounds__(256) void warp_crops_frames_planes_kernel(const Fra
         const int y = (int)(t % side);
         const MetroCropWarp& c = crops[t / side];
         const int fi = c.frame;
-        float* o = out + p * 3;
+        OutT* o = out + p * 3;
         if ((unsigned)fi >= (unsigned)n_frames) {
-            o[0] = o[1] = o[2] = 0.f;
+            o[0] = o[1] = o[2] = OutT(0);
             continue;
         }
         const MetroFramePlanes& f = frames.f[fi];
@@ -288,14 +355,17 @@ __global__ __launch_bounds__(256) void warp_crops_frames_planes_kernel(const Fra
     }
 }
 
+template <typename OutT>
 int launch_warp_crops_frames_planes(const FramePlanesTable& frames, int n_frames, const MetroCropWarp* crops, int n,
-                                    int side, float* out, hipStream_t stream) {
+                                    int side, OutT* out, hipStream_t stream) {
     const long total = (long)n * side * side;
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(warp_crops_frames_planes_kernel, dim3(blocks), dim3(256), 0, stream, frames, n_frames, crops, out,
+    hipLaunchKernelGGL(warp_crops_frames_planes_kernel<OutT>, dim3(blocks), dim3(256), 0, stream, frames, n_frames, crops, out,
                        n, side);
     return launch_status("warp_crops_frames_planes");
 }
+template int launch_warp_crops_frames_planes<float>(const FramePlanesTable&, int, const MetroCropWarp*, int, int, float*, hipStream_t);
+template int launch_warp_crops_frames_planes<unsigned char>(const FramePlanesTable&, int, const MetroCropWarp*, int, int, unsigned char*, hipStream_t);
 
 // ---------------------------------------------------------------------------------------------
 // 3x3 stride-2 max-pool over an input ZERO-padded by (1,1) (reference resnet_utils.py:177-185:

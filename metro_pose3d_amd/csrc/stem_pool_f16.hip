@@ -46,6 +46,7 @@ constexpr int KK = 14;                        // 7 tap rows x 2 k-steps of 16
 
 struct StemPoolArgs {
     const float* img_f32;  // RAW: [n][side][side][3] fp32, cast + bordered on the way into LDS (architectures.py:29)
+    const unsigned char* img_u8;  // RAW_U8: [n][side][side][3] uint8, byte b = the fp32 value b / 255 (improc.py:56-61), 16-byte aligned
     const half_t* img;     // [n][side+6][side+8][4] fp16 (prep_input_f16)
     const half_t* w;       // [64][7][8][4] fp16
     const float* bias;     // [64]
@@ -69,15 +70,28 @@ __device__ __forceinline__ void sp_wait_vm_dyn(int n) {
     }
 }
 
+// A uint8 crop value b stands for the fp32 value fdiv_rn(float(b), 255) (normalize01, improc.py:56-61: what the crop warp
+// writes), which the stem then rounds to fp16 (architectures.py:29).  For every one of the 256 bytes
+// fp16(rn(float(b) * rn(1 / 255))) is that same fp16 value: the product is within one fp32 ulp of the quotient and no quotient
+// lies that close to a tie of the 11-bit fp16 grid (tests/test_u8_input.py walks all 256; the GPU twin test compares the
+// kernels on all 256 with the fp32-input ones).  One multiply instead of an IEEE divide per channel.
+constexpr float U8_UNIT = 1.0f / 255.0f;
+__device__ __forceinline__ half_t u8_to_f16(unsigned b) { return (half_t)__fmul_rn((float)b, U8_UNIT); }
+
+// input of the kernels below: the bordered fp16 image of prep_input_f16, or the raw NHWC3 crops as fp32 or as uint8
+constexpr int IN_PREPPED = 0, IN_F32 = 1, IN_U8 = 2;
+
 // NSPLIT = 1: 4 waves, each holds both 32-cout weight tiles (112 VGPRs) and reuses every pixel fragment twice;
 // NSPLIT = 2: 8 waves, a wave holds one cout tile (56 VGPRs): twice the waves per CU to overlap the phases
 // RAW: the fp32 NHWC3 crops are read directly (prep_input_f16 fused away): every thread fetches ~3 window pixels
 // of the NEXT patch into registers at the top of an iteration and writes them to the other window buffer as
-// zero-bordered 4-channel fp16 at the end of it (ordinary loads: the compiler places their waits).
-template <int NSPLIT, bool RAW>
+// zero-bordered 4-channel fp16 at the end of it (ordinary loads: the compiler places their waits).  INPUT = IN_U8: the same
+// with three byte loads per pixel, kept as the fp32 product u8_to_f16 rounds.
+template <int NSPLIT, int INPUT>
 __global__ __launch_bounds__(64 * sp::MG * NSPLIT, 2 * NSPLIT) void stem_pool_f16_kernel(StemPoolArgs a) {
     using namespace sp;
     constexpr int NW = MG * NSPLIT, NT = 64 * NW, CT = 2 / NSPLIT;
+    constexpr bool RAW = INPUT != IN_PREPPED;
     constexpr int PS = 512 / NT;                  // pooled stores per wave per patch
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned smem_base = lds_offset_of(smem);
@@ -133,15 +147,22 @@ __global__ __launch_bounds__(64 * sp::MG * NSPLIT, 2 * NSPLIT) void stem_pool_f1
         const int img = patch / (ppr * ppr);
         const int rem = patch - img * ppr * ppr;
         const int r0 = 4 * PP * (rem / ppr) - 2 - 3, c0 = 4 * PP * (rem % ppr) - 2 - 3;   // window origin in the IMAGE
-        const float* base = a.img_f32 + (size_t)img * a.side * a.side * 3;
+        const size_t img_off = (size_t)img * a.side * a.side * 3;
 #pragma unroll
         for (int k = 0; k < RK; ++k) {
             const int idx = k * NT + tid;
             const int wr = idx / WIN_C, wc = idx - wr * WIN_C;
             const int y = r0 + wr, x = c0 + wc;
             const bool ok = idx < WIN_R * WIN_C && (unsigned)y < (unsigned)a.side && (unsigned)x < (unsigned)a.side;
-            const float* s3 = base + ((size_t)(ok ? y : 0) * a.side + (ok ? x : 0)) * 3;
-            rawpx[k][0] = ok ? s3[0] : 0.f; rawpx[k][1] = ok ? s3[1] : 0.f; rawpx[k][2] = ok ? s3[2] : 0.f;
+            const size_t px_off = img_off + ((size_t)(ok ? y : 0) * a.side + (ok ? x : 0)) * 3;
+            if constexpr (INPUT == IN_U8) {
+                const unsigned char* s3 = a.img_u8 + px_off;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) rawpx[k][c] = ok ? __fmul_rn((float)s3[c], U8_UNIT) : 0.f;
+            } else {
+                const float* s3 = a.img_f32 + px_off;
+                rawpx[k][0] = ok ? s3[0] : 0.f; rawpx[k][1] = ok ? s3[1] : 0.f; rawpx[k][2] = ok ? s3[2] : 0.f;
+            }
         }
     };
     auto raw_commit = [&](int buf) {
@@ -325,6 +346,10 @@ constexpr int OUT_OFF = STG_OFF + NSR * SROW;
 constexpr int EDGE_OFF = OUT_OFF + OUT_BYTES;
 constexpr int LDS_BYTES = EDGE_OFF + EDGE_BYTES;          // 81 536: two blocks per CU, to the byte
 static_assert(2 * LDS_BYTES <= 160 * 1024, "two blocks per CU");
+// uint8 crops: a crop row is 768 bytes = ONE LDS-DMA instruction (48 lanes of crop bytes; the other 16 lanes fetch the zero
+// page, since a lane cannot be masked out of an LDS-DMA), so a staging slot is the instruction's 1 KiB and the ring 12 KiB
+constexpr int SROW_U8 = 1024;
+constexpr int LDS_BYTES_U8 = LDS_BYTES - NSR * (SROW - SROW_U8);          // 56 960
 }  // namespace sp2
 
 // packed fp16 max as the instruction (the builtin canonicalises both operands first: a third of the pooling's VALU work)
@@ -351,8 +376,17 @@ __device__ __forceinline__ half2_t sp2_xchg32(half2_t v) {          // the value
     return __builtin_bit_cast(half2_t, __shfl_xor(i, 32, 64));
 }
 
-__global__ __launch_bounds__(sp2::NT, 2) void stem_pool_rows_kernel(StemPoolArgs a) {
+// U8: the crops are uint8 (StemPoolArgs::img_u8).  Only the staging ring and the cast differ: a crop row is one LDS-DMA
+// instruction, issued by wave 3 (the wave without requests in the fp32 form), and cast_read turns the three bytes at
+// tid * 3 into the fp16 window pixel by u8_to_f16.  Window ring, MFMAs, pooling and stores are the same code.
+template <bool U8>
+__device__ __forceinline__ void stem_pool_rows_body(const StemPoolArgs& a) {
     using namespace sp2;
+    // the areas behind the staging ring move up with it (these hide sp2's)
+    constexpr int SROW = U8 ? SROW_U8 : sp2::SROW;
+    constexpr int OUT_OFF = STG_OFF + NSR * SROW;
+    constexpr int EDGE_OFF = OUT_OFF + OUT_BYTES;
+    static_assert(EDGE_OFF + EDGE_BYTES == (U8 ? LDS_BYTES_U8 : LDS_BYTES), "LDS layout");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned smem_base = lds_offset_of(smem);
     const int tid = threadIdx.x;
@@ -362,23 +396,41 @@ __global__ __launch_bounds__(sp2::NT, 2) void stem_pool_rows_kernel(StemPoolArgs
     const int img = blockIdx.x / (PS / PY), band = blockIdx.x % (PS / PY);
     const int Y0 = band * PY;
 
+    const unsigned char* crop_u8 = a.img_u8 + (size_t)img * SIDE * SIDE * 3;
     const float* crop = a.img_f32 + (size_t)img * SIDE * SIDE * 3;
     // crop row i (clamped: rows outside the crop are cast to zeros whatever arrived) -> a staging slot: waves 0-2 a KiB each
     auto issue_row = [&](int i, int slot) {
         if (wave < 3) {
             const int ic = i < 0 ? 0 : i > SIDE - 1 ? SIDE - 1 : i;
             const float* src = crop + (size_t)ic * SIDE * 3 + wave * 256 + lane * 4;
-            dma16(src, __builtin_amdgcn_readfirstlane(smem_base + STG_OFF + slot * SROW + wave * 1024));
+            if constexpr (!U8) dma16(src, __builtin_amdgcn_readfirstlane(smem_base + STG_OFF + slot * SROW + wave * 1024));
+        }
+        if constexpr (U8) {      // wave 3 the whole row: 48 lanes of crop bytes, lanes 48-63 zeros behind them
+            if (wave == 3) {
+                const int ic = i < 0 ? 0 : i > SIDE - 1 ? SIDE - 1 : i;
+                const void* src = lane < 48 ? static_cast<const void*>(crop_u8 + (size_t)ic * SIDE * 3 + lane * 16)
+                                            : static_cast<const void*>(g_zero_page);
+                dma16(src, __builtin_amdgcn_readfirstlane(smem_base + STG_OFF + slot * SROW));
+            }
         }
     };
     // window row p (bordered: crop row p - 3) from a staging slot: thread = pixel.  Read and write are separate steps: the steady
     // state reads at the top of an iteration and writes at its end (an LDS latency and a half otherwise sit on the critical path);
     // no branch around a read (a branch is a wait per read)
     auto cast_read = [&](int p, int slot, half4_t& v) {
-        const float* s3 = reinterpret_cast<const float*>(smem + STG_OFF + slot * SROW) + tid * 3;
         const bool ok = (unsigned)(p - 3) < (unsigned)SIDE;
-        const float r = s3[0], g = s3[1], b = s3[2];
-        v = half4_t{(half_t)(ok ? r : 0.f), (half_t)(ok ? g : 0.f), (half_t)(ok ? b : 0.f), (half_t)0};
+        if constexpr (U8) {
+            // the two dwords that hold bytes tid * 3 ... + 2 (the last pixel's second dword lies in the slot's zero tail),
+            // shifted so that the pixel starts at byte 0: no sub-dword LDS reads
+            const unsigned* s = reinterpret_cast<const unsigned*>(smem + STG_OFF + slot * SROW) + ((tid * 3) >> 2);
+            const unsigned lo = s[0], hi = s[1];
+            const unsigned px = ok ? __builtin_amdgcn_alignbyte(hi, lo, (unsigned)(tid * 3) & 3u) : 0u;
+            v = half4_t{u8_to_f16(px & 0xffu), u8_to_f16((px >> 8) & 0xffu), u8_to_f16((px >> 16) & 0xffu), (half_t)0};
+        } else {
+            const float* s3 = reinterpret_cast<const float*>(smem + STG_OFF + slot * SROW) + tid * 3;
+            const float r = s3[0], g = s3[1], b = s3[2];
+            v = half4_t{(half_t)(ok ? r : 0.f), (half_t)(ok ? g : 0.f), (half_t)(ok ? b : 0.f), (half_t)0};
+        }
     };
     auto cast_write = [&](int p, const half4_t& v) {
         *reinterpret_cast<half4_t*>(smem + WIN_OFF + (p & (NWR - 1)) * WROW + (tid + 3) * 8) = v;
@@ -619,7 +671,7 @@ __global__ __launch_bounds__(sp2::NT, 2) void stem_pool_rows_kernel(StemPoolArgs
         // the crop rows cast in this iteration were requested two iterations ago: one iteration of requests (4) is younger.  The
         // pooled-row stores in between are not counted: requests land in order among themselves, so "at most 4 operations
         // outstanding" implies this group has landed whatever the stores do
-        if (wave < 3) wait_vm<4>();
+        if (U8 ? wave == 3 : wave < 3) wait_vm<4>();
         wait_lgkm_and_barrier();  // ... and everybody's share has landed; the last pooled row's tile is complete
         SP2_CLK(1);
         half8_t sv[2];
@@ -665,6 +717,9 @@ __global__ __launch_bounds__(sp2::NT, 2) void stem_pool_rows_kernel(StemPoolArgs
 #undef SP2_CLK
 }
 
+__global__ __launch_bounds__(sp2::NT, 2) void stem_pool_rows_kernel(StemPoolArgs a) { stem_pool_rows_body<false>(a); }
+__global__ __launch_bounds__(sp2::NT, 2) void stem_pool_rows_u8_kernel(StemPoolArgs a) { stem_pool_rows_body<true>(a); }
+
 static int sp_env_int(const char* name, int dflt) { return tuning_knob(name, dflt); }
 
 bool stem_pool_f16_supported(int side, int base_width) {
@@ -672,7 +727,7 @@ bool stem_pool_f16_supported(int side, int base_width) {
     return enabled && base_width == 64 && side % 32 == 0 && side >= 32;
 }
 
-template <int NSPLIT, bool RAW>
+template <int NSPLIT, int INPUT>
 static int launch_sp(const StemPoolArgs& a, hipStream_t stream);
 
 int launch_stem_pool_f16(const void* prepped, const void* w, const float* bias, void* out, int n, int side,
@@ -687,9 +742,10 @@ int launch_stem_pool_f16(const void* prepped, const void* w, const float* bias, 
     const int ppr = side / 4 / sp::PP;
     a.n_patches = n * ppr * ppr;
     a.img_f32 = nullptr;
+    a.img_u8 = nullptr;
     static const int split = sp_env_int("METRO_STEM_SPLIT", 2);
-    if (split == 2) return launch_sp<2, false>(a, stream);
-    return launch_sp<1, false>(a, stream);
+    if (split == 2) return launch_sp<2, IN_PREPPED>(a, stream);
+    return launch_sp<1, IN_PREPPED>(a, stream);
 }
 
 bool stem_pool_f32in_supported(int side, int base_width) {
@@ -703,6 +759,7 @@ int launch_stem_pool_f32in(const float* images, const void* w, const float* bias
     StemPoolArgs a;
     a.img_f32 = images;
     a.img = nullptr;
+    a.img_u8 = nullptr;
     a.w = static_cast<const half_t*>(w);
     a.bias = bias;
     a.out = static_cast<half_t*>(out);
@@ -719,14 +776,47 @@ int launch_stem_pool_f32in(const float* images, const void* w, const float* bias
         return launch_status("stem_pool_f16<rows>");
     }
     static const int split = sp_env_int("METRO_STEM_RAW_SPLIT", 2);
-    if (split == 1) return launch_sp<1, true>(a, stream);
-    return launch_sp<2, true>(a, stream);
+    if (split == 1) return launch_sp<1, IN_F32>(a, stream);
+    return launch_sp<2, IN_F32>(a, stream);
 }
 
-template <int NSPLIT, bool RAW>
+// The twin of launch_stem_pool_f32in for uint8 crops: the same sides, the same switches, the same choice of kernel.
+int launch_stem_pool_u8in(const unsigned char* images, const void* w, const float* bias, void* out, int n, int side,
+                          hipStream_t stream) {
+    if (!stem_pool_f32in_supported(side, 64)) { set_error("stem_pool_u8in: unsupported shape (side %d)", side); return METRO_ERR_INVALID_ARG; }
+    // the rows kernel fetches whole 16-byte pieces of a crop row by LDS-DMA; a crop is a multiple of 16 bytes at every supported side
+    if (((uintptr_t)images & 15) != 0) {
+        set_error("stem_pool_u8in: uint8 crops must start at a 16-byte aligned address (got %p): copy the view once", (const void*)images);
+        return METRO_ERR_INVALID_ARG;
+    }
+    StemPoolArgs a;
+    a.img_u8 = images;
+    a.img_f32 = nullptr;
+    a.img = nullptr;
+    a.w = static_cast<const half_t*>(w);
+    a.bias = bias;
+    a.out = static_cast<half_t*>(out);
+    a.n = n; a.side = side;
+    const int ppr = side / 4 / sp::PP;
+    a.n_patches = n * ppr * ppr;
+    static const int rows = sp_env_int("METRO_STEM_ROWS", 1);
+    if (rows && side == sp2::SIDE) {
+        if (note_kernel("stem_pool_f16<rows,u8in>")) return METRO_OK;
+        static PerDeviceInt cap;
+        int grid_cap = 0;
+        if (const int st = ensure_dyn_lds_and_grid_cap(reinterpret_cast<const void*>(stem_pool_rows_u8_kernel), sp2::NT, sp2::LDS_BYTES_U8, cap, "stem_pool_f16<rows,u8in>", 0, &grid_cap)) return st;
+        hipLaunchKernelGGL(stem_pool_rows_u8_kernel, dim3(n * (sp2::PS / sp2::PY)), dim3(sp2::NT), sp2::LDS_BYTES_U8, stream, a);
+        return launch_status("stem_pool_f16<rows,u8in>");
+    }
+    static const int split = sp_env_int("METRO_STEM_RAW_SPLIT", 2);
+    if (split == 1) return launch_sp<1, IN_U8>(a, stream);
+    return launch_sp<2, IN_U8>(a, stream);
+}
+
+template <int NSPLIT, int INPUT>
 static int launch_sp(const StemPoolArgs& a, hipStream_t stream) {
-    if (note_kernel("stem_pool_f16<split%d%s>", NSPLIT, RAW ? ",f32in" : "")) return METRO_OK;
-    auto kern = stem_pool_f16_kernel<NSPLIT, RAW>;
+    if (note_kernel("stem_pool_f16<split%d%s>", NSPLIT, INPUT == IN_F32 ? ",f32in" : INPUT == IN_U8 ? ",u8in" : "")) return METRO_OK;
+    auto kern = stem_pool_f16_kernel<NSPLIT, INPUT>;
     constexpr int NT = 64 * sp::MG * NSPLIT;
     static PerDeviceInt cap;
     int grid_cap = 0;

@@ -86,6 +86,7 @@ class Engine:
         self.device = None
         self._blob = None
         self._ws = None
+        self._u8_f32 = None
         if params is not None:
             if device is None:
                 if not torch.cuda.is_available():
@@ -162,38 +163,66 @@ class Engine:
             raise ValueError('images must be a torch.Tensor on the GPU')
         if images.dim() != 4 or tuple(images.shape[1:]) != (s, s, 3):
             raise ValueError(f'images must be [N,{s},{s},3] NHWC, got {tuple(images.shape)}')
-        if images.dtype != torch.float32:
-            raise ValueError(f'images must be float32 in [0,1], got {images.dtype}')
+        if images.dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f'images must be float32 in [0,1] or uint8 (byte b = b / 255), got {images.dtype}')
         if images.device != self.device:
             raise ValueError(f'images are on {images.device}, the plan is on {self.device}')
         if images.shape[0] < 1 or images.shape[0] > self.max_batch:
             raise ValueError(f'batch {images.shape[0]} outside [1, {self.max_batch}]')
-        return images.contiguous()
+        images = images.contiguous()
+        if images.dtype == torch.uint8 and images.data_ptr() % 16:
+            images = images.clone()         # metro_forward_u8 fetches 16-byte pieces: a misaligned view is copied once
+        return images
+
+    def _as_float32(self, images: torch.Tensor) -> torch.Tensor:
+        """uint8 crops -> the fp32 image they stand for (metro_images_u8_to_f32: byte / 255, an IEEE divide), in a buffer the
+        engine owns (allocated on first use, max_batch crops): what the parity precisions, whose forward takes fp32, run on."""
+        n, s = images.shape[0], self.spec.proc_side
+        if self._u8_f32 is None:
+            self._u8_f32 = torch.empty((self.max_batch, s, s, 3), dtype=torch.float32, device=self.device)
+        out = self._u8_f32[:n]
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        check(self.lib.metro_images_u8_to_f32(C.c_void_p(images.data_ptr()), images.numel(), C.c_void_p(out.data_ptr()),
+                                              C.c_void_p(stream)), 'metro_images_u8_to_f32')
+        return out
 
     def forward(self, images: torch.Tensor, out: Optional[torch.Tensor] = None,
                 coords01: Optional[torch.Tensor] = None) -> torch.Tensor:
         """images fp32 [n,256,256,3] on the plan's device -> poses fp32 [n,Jout,3] (mm).  Enqueued
         on torch's current stream; no synchronisation.  `coords01`: an fp32 [n, J_head, 3] device tensor that also receives
-        the soft-argmax coordinates in [0,1] (head order; metro_forward_coords01: the same poses, from the same launches)."""
+        the soft-argmax coordinates in [0,1] (head order; metro_forward_coords01: the same poses, from the same launches).
+        uint8 images (byte b = the fp32 value b / 255) give the bits of the fp32 call on those values: precision 'f16' reads
+        the bytes in its first kernel (metro_forward_u8), the others expand them once (metro_images_u8_to_f32)."""
         images = self._check_images(images)
         n = images.shape[0]
         if out is None:
             out = torch.empty((n, self.spec.skeleton.n_out, 3), dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
+        if coords01 is not None:
+            self._check_coords01(coords01, n)
+        if images.dtype == torch.uint8:
+            if self.precision == 'f16':
+                check(self.lib.metro_forward_u8(self._plan, C.c_void_p(images.data_ptr()), n, C.c_void_p(out.data_ptr()),
+                                                C.c_void_p(coords01.data_ptr() if coords01 is not None else 0),
+                                                C.c_void_p(self._ws.data_ptr()), C.c_void_p(stream)), 'metro_forward_u8')
+                return out
+            images = self._as_float32(images)
         if coords01 is None:
             check(self.lib.metro_forward(self._plan, C.c_void_p(images.data_ptr()), n,
                                          C.c_void_p(out.data_ptr()), C.c_void_p(self._ws.data_ptr()),
                                          C.c_void_p(stream)), 'metro_forward')
             return out
+        check(self.lib.metro_forward_coords01(self._plan, C.c_void_p(images.data_ptr()), n, C.c_void_p(out.data_ptr()),
+                                              C.c_void_p(coords01.data_ptr()), C.c_void_p(self._ws.data_ptr()),
+                                              C.c_void_p(stream)), 'metro_forward_coords01')
+        return out
+
+    def _check_coords01(self, coords01, n: int) -> None:
         shape = (n, self.spec.skeleton.n_head, 3)
         if (not isinstance(coords01, torch.Tensor) or coords01.dtype != torch.float32 or tuple(coords01.shape) != shape
                 or coords01.device != self.device or not coords01.is_contiguous()):
             raise ValueError(f'coords01 must be a contiguous float32 {list(shape)} tensor on {self.device}, got '
                              f'{getattr(coords01, "dtype", type(coords01))} {tuple(getattr(coords01, "shape", ()))}')
-        check(self.lib.metro_forward_coords01(self._plan, C.c_void_p(images.data_ptr()), n, C.c_void_p(out.data_ptr()),
-                                              C.c_void_p(coords01.data_ptr()), C.c_void_p(self._ws.data_ptr()),
-                                              C.c_void_p(stream)), 'metro_forward_coords01')
-        return out
 
     def check_finite(self, n: int) -> None:
         """Non-finite screen of the last forward(n) on this engine: raises _lib.NonFiniteError when activations overflowed
@@ -213,6 +242,8 @@ class Engine:
         """Runs layers [0..layer] and returns that layer's output tensor [n,h,w,c] (a copy); `second` selects
         the second output of a fused launch (MetroLayerInfo.out2_offset)."""
         images = self._check_images(images)
+        if images.dtype == torch.uint8:      # layer dumps and timings take the fp32 image the bytes stand for
+            images = self._as_float32(images)
         n = images.shape[0]
         li = self.layer_infos()[layer]
         poses = torch.empty((n, self.spec.skeleton.n_out, 3), dtype=torch.float32, device=self.device)
@@ -237,6 +268,8 @@ class Engine:
     def forward_timed(self, images: torch.Tensor, reps: int = 1) -> np.ndarray:
         """Per-layer milliseconds (HIP events on the launch stream), averaged over `reps`."""
         images = self._check_images(images)
+        if images.dtype == torch.uint8:
+            images = self._as_float32(images)
         n = images.shape[0]
         nl = self.lib.metro_plan_num_layers(self._plan)
         ms = (C.c_float * nl)()

@@ -190,10 +190,22 @@ def _check_frame_index(fi: np.ndarray, n_frames: int) -> None:
         raise ValueError(f'frame_index must lie in [0, {n_frames}), got [{fi.min()}, {fi.max()}]')
 
 
+CROP_DTYPES = {'float32': torch.float32, 'uint8': torch.uint8}
+
+
+def _crop_dtype(crop_dtype) -> torch.dtype:
+    if crop_dtype not in CROP_DTYPES:
+        raise ValueError(f"crop_dtype must be 'float32' or 'uint8', got {crop_dtype!r}")
+    return CROP_DTYPES[crop_dtype]
+
+
 def warp_frames(frames, params: CropParams, frame_index, side: int = 256, device: Optional[torch.device] = None,
-                out: Optional[torch.Tensor] = None, pixel_format: str = 'rgb', color_matrix: str = 'bt601') -> torch.Tensor:
+                out: Optional[torch.Tensor] = None, pixel_format: str = 'rgb', color_matrix: str = 'bt601',
+                crop_dtype: str = 'float32') -> torch.Tensor:
     """uint8 [H, W, 3] frames (a tensor or a list; host or device; sizes may differ) + per-crop parameters -> fp32 NHWC
     [n, side, side, 3] crops in [0, 1] on the device, in ONE launch on the current stream.
+    crop_dtype 'uint8': the crops are the remapped bytes themselves (metro_warp_crops_frames_u8_to_u8 / _planes_to_u8), uint8
+    [n, side, side, 3]: float32(byte) / 255 is the 'float32' crop bit for bit, and estimate_pose takes them as they are.
     pixel_format 'rgb' (metro_warp_crops_frames_u8), or 'bgr', 'nv12', 'i420' (metro_warp_crops_frames_planes: the bytes of
     'rgb' on the converted frame); color_matrix 'bt601' or 'bt709' for the YUV formats.  Frame layouts:
       'rgb', 'bgr'  uint8 [H, W, 3];
@@ -204,6 +216,7 @@ def warp_frames(frames, params: CropParams, frame_index, side: int = 256, device
                     (Y [H, W], U [H/2, W/2], V [H/2, W/2]).
     A YUV frame is one tensor / array (2-D) or a tuple of planes; a list holds many frames.  H and W are even; rows have element
     stride 1; anything else raises ValueError naming the frame and the layout."""
+    dtype = _crop_dtype(crop_dtype)
     frames = _frame_set(frames, pixel_format, color_matrix)
     if device is None:
         first = _first_frame(frames)
@@ -213,7 +226,9 @@ def warp_frames(frames, params: CropParams, frame_index, side: int = 256, device
     fi = np.asarray(frame_index, np.int64).reshape(n)
     _check_frame_index(fi, len(dev_frames))
     if out is None:
-        out = torch.empty((n, side, side, 3), dtype=torch.float32, device=device)
+        out = torch.empty((n, side, side, 3), dtype=dtype, device=device)
+    elif out.dtype != dtype:
+        raise ValueError(f'out is {out.dtype}, crop_dtype is {crop_dtype!r}')
     if n == 0:
         return out
     _launch_warp(dev_frames, _upload(pack_crops(params, fi), device), n, side, out, device)
@@ -222,8 +237,10 @@ def warp_frames(frames, params: CropParams, frame_index, side: int = 256, device
 
 def _launch_warp(dev_frames, crops: torch.Tensor, n: int, side: int, out: torch.Tensor, device: torch.device) -> None:
     """One metro_warp_crops_frames_u8 launch ('rgb' frames: tensors) or one metro_warp_crops_frames_planes launch (_Planar
-    frames) on the current stream: n MetroCropWarp records already on the device."""
+    frames) on the current stream: n MetroCropWarp records already on the device.  A uint8 `out` takes the entries that write
+    the remapped byte (metro_warp_crops_frames_u8_to_u8, metro_warp_crops_frames_planes_to_u8)."""
     stream = torch.cuda.current_stream(device).cuda_stream
+    lib, u8 = _lib.load(), out.dtype == torch.uint8
     if dev_frames and isinstance(dev_frames[0], _Planar):
         ptable = (_lib.MetroFramePlanes * len(dev_frames))()
         for k, f in enumerate(dev_frames):
@@ -232,15 +249,16 @@ def _launch_warp(dev_frames, crops: torch.Tensor, n: int, side: int, out: torch.
                 r.plane[i] = p.data_ptr()
             r.h, r.w, r.format, r.matrix = f.h, f.w, f.format, f.matrix
             r.stride[0], r.stride[1] = f.stride
-        check(_lib.load().metro_warp_crops_frames_planes(ptable, len(dev_frames), C.c_void_p(crops.data_ptr()), n, side,
-                                                         C.c_void_p(out.data_ptr()), C.c_void_p(stream)),
-              'metro_warp_crops_frames_planes')
+        entry = 'metro_warp_crops_frames_planes_to_u8' if u8 else 'metro_warp_crops_frames_planes'
+        check(getattr(lib, entry)(ptable, len(dev_frames), C.c_void_p(crops.data_ptr()), n, side,
+                                  C.c_void_p(out.data_ptr()), C.c_void_p(stream)), entry)
         return
     table = (_lib.MetroFrame * len(dev_frames))()
     for k, f in enumerate(dev_frames):
         table[k].data, table[k].h, table[k].w, table[k].row_stride = f.data_ptr(), f.shape[0], f.shape[1], f.stride(0)
-    check(_lib.load().metro_warp_crops_frames_u8(table, len(dev_frames), C.c_void_p(crops.data_ptr()), n, side,
-                                                 C.c_void_p(out.data_ptr()), C.c_void_p(stream)), 'metro_warp_crops_frames_u8')
+    entry = 'metro_warp_crops_frames_u8_to_u8' if u8 else 'metro_warp_crops_frames_u8'
+    check(getattr(lib, entry)(table, len(dev_frames), C.c_void_p(crops.data_ptr()), n, side,
+                              C.c_void_p(out.data_ptr()), C.c_void_p(stream)), entry)
 
 
 MAX_VIEWS = _lib.METRO_MAX_VIEWS
@@ -558,15 +576,17 @@ _ROT_TO_ORIG_CAM = _lib.MetroPlacement.rot_to_orig_cam.offset // 4      # float 
 _ROT_TO_WORLD = _lib.MetroPlacement.rot_to_world.offset // 4
 
 
-def _warp_views(frames, cameras, boxes, fi, vs: Views, side: int, device: torch.device):
+def _warp_views(frames, cameras, boxes, fi, vs: Views, side: int, device: torch.device, crop_dtype: str = 'float32'):
     """The frames on the device, one MetroViewBase record per box (host boxes with their frame indices fi: pack_view_bases,
     NumPy per box; _DeviceBoxes, fi None: metro_look_at_boxes, no per-box host work), the expansion and ONE warp launch of the
     n V crops -> (crops [n V, side, side, 3], placement records [n V, 208]).  Host frame indices are checked here, before
-    any launch; metro_look_at_boxes' check of device ones is left in boxes.frame_status.  No launch for n = 0."""
+    any launch; metro_look_at_boxes' check of device ones is left in boxes.frame_status.  No launch for n = 0.
+    crop_dtype 'uint8': uint8 crops (the remapped bytes), which the forward reads as they are."""
+    dtype = _crop_dtype(crop_dtype)
     dev_frames = _device_frames(frames, device)
     n, n_frames = len(boxes), len(dev_frames)
     if n == 0:
-        return (torch.empty((0, side, side, 3), dtype=torch.float32, device=device),
+        return (torch.empty((0, side, side, 3), dtype=dtype, device=device),
                 torch.empty((0, C.sizeof(_lib.MetroPlacement)), dtype=torch.uint8, device=device))
     if isinstance(boxes, _DeviceBoxes):
         bases, status = _look_at_boxes(cameras, boxes.boxes, _checked_device_fi(boxes, n_frames, device), n_frames, side, device)
@@ -575,7 +595,7 @@ def _warp_views(frames, cameras, boxes, fi, vs: Views, side: int, device: torch.
         _check_frame_index(fi, n_frames)
         bases = pack_view_bases(cameras, boxes, fi, side)
     crop_recs, places = _expand_views(bases, vs, side, device)
-    crops = torch.empty((n * len(vs.zoom), side, side, 3), dtype=torch.float32, device=device)
+    crops = torch.empty((n * len(vs.zoom), side, side, 3), dtype=dtype, device=device)
     _launch_warp(dev_frames, crop_recs, len(crops), side, crops, device)
     return crops, places
 
@@ -601,11 +621,13 @@ class _Call(NamedTuple):
     vs: Views                    # views=None: the identity view
     precision: str
     check_finite: bool
+    crop_dtype: str = 'float32'  # dtype of the crops between the warp and the forward: 'float32' | 'uint8'
 
 
 def _checked_call(frames, boxes, frame_index, coords, views, geometry, precision, check_finite, pixel_format,
-                  color_matrix) -> _Call:
+                  color_matrix, crop_dtype: str = 'float32') -> _Call:
     """Every check that needs neither the model file nor, for host boxes, a device; the environment's defaults."""
+    _crop_dtype(crop_dtype)
     frames = _frame_set(frames, pixel_format, color_matrix)
     geo = _geometry_of(geometry, boxes)
     if coords not in COORDS:
@@ -620,14 +642,14 @@ def _checked_call(frames, boxes, frame_index, coords, views, geometry, precision
     if geo == 'device':
         db = _device_boxes(boxes, frame_index, _call_device(boxes, frames))
         if len(db):
-            return _Call(frames, db, None, vs, precision, check_finite)
+            return _Call(frames, db, None, vs, precision, check_finite, crop_dtype)
         boxes, frame_index = np.zeros((0, 4)), None
     boxes = np.asarray(_host_array(boxes), np.float64)
     if boxes.ndim != 2 or boxes.shape[1] != 4:
         raise ValueError(f'boxes must be [n, 4] (x, y, w, h), got {boxes.shape}')
     n = len(boxes)
     fi = np.zeros(n, np.int64) if frame_index is None else np.asarray(_host_array(frame_index), np.int64).reshape(n)
-    return _Call(frames, boxes, fi, vs, precision, check_finite)
+    return _Call(frames, boxes, fi, vs, precision, check_finite, crop_dtype)
 
 
 def _call_device(boxes, frames) -> torch.device:
@@ -643,7 +665,8 @@ def _call_device(boxes, frames) -> torch.device:
 
 def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index=None, coords: str = 'camera',
                             precision: Optional[str] = None, check_finite: Optional[bool] = None, views=None,
-                            geometry: str = 'auto', pixel_format: str = 'rgb', color_matrix: str = 'bt601'):
+                            geometry: str = 'auto', pixel_format: str = 'rgb', color_matrix: str = 'bt601',
+                            crop_dtype: str = 'float32'):
     """uint8 frames + person boxes [n, 4] (x, y, w, h) -> (poses [n, Jout, 3] mm, joint_edges, joint_names) like estimate_pose.
 
     frames: a uint8 [H, W, 3] tensor / array or a list of them (host or device, sizes may differ, at most 64), or frames in
@@ -676,9 +699,12 @@ def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index
     formats; the layouts are warp_frames'.  Frames other than 'rgb' go through metro_warp_crops_frames_planes, which
     converts each tap as the warp reads it: the crops are byte for byte those of the RGB frame that OpenCV's integer
     cvtColor(COLOR_YUV2RGB_NV12 / _I420) rule gives (not ffmpeg's swscale, which rounds differently), with a black border;
-    no RGB frame is written, and host frames upload at their own size (1.5 bytes per pixel for YUV)."""
+    no RGB frame is written, and host frames upload at their own size (1.5 bytes per pixel for YUV).
+    crop_dtype: what the warp hands the network.  'float32' (default): byte / 255 as fp32, 12 bytes per pixel.  'uint8': the
+    remapped byte itself, 3 bytes per pixel, which the forward reads by the same rule (metro_forward_u8; the parity
+    precisions expand it first): the same poses bit for bit."""
     call = _checked_call(frames, boxes, frame_index, coords, views, geometry, precision, check_finite, pixel_format,
-                         color_matrix)
+                         color_matrix, crop_dtype)
     return _estimate_pose_views(call, model_path, cameras, coords)
 
 
@@ -688,7 +714,7 @@ def _estimate_pose_views(call: _Call, model_path, cameras, coords):
     device = _call_device(call.boxes, call.frames)
     with torch.cuda.device(device):
         spec = _engine_for(model_path, call.precision, device, max(n * nv, 1)).spec
-        crops, places = _warp_views(call.frames, cameras, call.boxes, call.fi, call.vs, spec.proc_side, device)
+        crops, places = _warp_views(call.frames, cameras, call.boxes, call.fi, call.vs, spec.proc_side, device, call.crop_dtype)
         poses, edges, names = estimate_pose(crops, model_path, precision=call.precision, check_finite=call.check_finite,
                                             shard=False)
         _synchronise(None, call.boxes)         # after estimate_pose's synchronisation (its finite screen), or the call's one
@@ -790,7 +816,8 @@ def _placement_targets(scale_recovery, cameras, n, n_edges, bone_lengths, root_d
 def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=None, scale_recovery: str = 'bone-lengths',
                            bone_lengths=None, root_depth=None, coords: str = 'camera', precision: Optional[str] = None,
                            check_finite: Optional[bool] = None, views=None, return_spread: bool = False,
-                           geometry: str = 'auto', pixel_format: str = 'rgb', color_matrix: str = 'bt601'):
+                           geometry: str = 'auto', pixel_format: str = 'rgb', color_matrix: str = 'bt601',
+                           crop_dtype: str = 'float32'):
     """uint8 frames + person boxes -> FramePoses(poses, keypoints2d, z_offset, joint_edges, joint_names): where each person is
     in 3D and where each joint lands in its frame's pixels.  frames, boxes, frame_index, cameras, precision and check_finite as
     for estimate_pose_in_frames.
@@ -822,9 +849,10 @@ def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=
     device frame index outside [0, n_frames) raises ValueError, read together with the finite screen in the call's one
     synchronisation.
     pixel_format, color_matrix: as for estimate_pose_in_frames ('bgr', 'nv12', 'i420' frames converted per tap in the warp,
-    OpenCV's integer YUV rule, black border)."""
+    OpenCV's integer YUV rule, black border); crop_dtype 'float32' | 'uint8' likewise (the same bits from a quarter of the
+    crop bytes)."""
     call = _checked_call(frames, boxes, frame_index, coords, views, geometry, precision, check_finite, pixel_format,
-                         color_matrix)
+                         color_matrix, crop_dtype)
     sk = _model_skeleton(model_path)
     targets, per_pose, root_z = _placement_targets(scale_recovery, cameras, len(call.boxes), len(sk.head_edges), bone_lengths,
                                                    root_depth)
@@ -865,7 +893,7 @@ def _locate_poses_views(call: _Call, model_path, cameras, scale_recovery, target
         if n == 0:
             return (FramePoses(f32(0, sk.n_out, 3), f32(0, sk.n_out, 2), f32(0) if absolute else None, sk.edges_array(), names),
                     torch.zeros((0, sk.n_out), dtype=torch.float32, device=device))
-        crops, places = _warp_views(call.frames, cameras, call.boxes, call.fi, call.vs, eng.spec.proc_side, device)
+        crops, places = _warp_views(call.frames, cameras, call.boxes, call.fi, call.vs, eng.spec.proc_side, device, call.crop_dtype)
         rel, coords01, bad = _forward_coords01(eng, crops, call.check_finite)
         if per_pose:                                    # per-box targets, repeated per view by index (box-major rows)
             targets = np.repeat(targets, nv, axis=0)

@@ -14,7 +14,8 @@ same CLI flag `--model-path`.  Differences that follow from not being TensorFlow
     128- / 256-pixel tiles once it has 256 of them), so results are not bit-stable ACROSS call sizes >= 128 at stride 16
     (estimate_pose docstring);
   * one process per GPU under torch.distributed: the same call shards the batch by image and all-gathers the poses.
-Input contract (inference.py:17-18, main.py:109-110): float32 NHWC [N,256,256,3], RGB in [0,1].
+Input contract (inference.py:17-18, main.py:109-110): float32 NHWC [N,256,256,3], RGB in [0,1]; or the uint8 RGB bytes such
+an image was divided from (byte b = b / 255: the same bits).
 The arithmetic mode defaults to fp16, the reference's default compute dtype (options.py:73);
 pass precision='f64' (or METRO_PRECISION=f64) for the parity mode (fp64 arithmetic inside).
 """
@@ -97,6 +98,11 @@ def estimate_pose(images_tensor, model_path, precision: Optional[str] = None, ch
                   shard: Optional[bool] = None, group=None):
     """images [N,256,256,3] float32 in [0,1] -> (poses [N,Jout,3] mm, joint_edges, joint_names).
 
+    uint8 images (RGB bytes, as a JPEG decoder or the crop warp leaves them) are accepted as they are: byte b stands for the
+    float32 value b / 255 (normalize01, reference improc.py:56-61) and the result has the bits of the float32 call on those
+    values, in every precision.  A quarter of the bytes are uploaded; precision 'f16' reads the bytes in its first kernel
+    (metro_forward_u8), the parity precisions expand them on the device first (metro_images_u8_to_f32).
+
     Multi-GPU (BASELINE.json north star; the reference's call has no such notion): when `torch.distributed` is initialised with
     more than one rank (one process per GPU), EVERY rank makes this same call with the same N images; rank r computes the
     contiguous shard dist.shard_range(N, r, world) on its own GPU and all ranks return the full [N,Jout,3] after ONE all-gather
@@ -126,8 +132,8 @@ def estimate_pose(images_tensor, model_path, precision: Optional[str] = None, ch
         images_tensor = torch.from_numpy(images_tensor)
     if not isinstance(images_tensor, torch.Tensor):
         raise ValueError(f'images must be a torch.Tensor or numpy array, got {type(images_tensor)}')
-    if images_tensor.dtype != torch.float32:
-        raise ValueError(f'images must be float32 in [0,1] (reference inference.py:18), got {images_tensor.dtype}')
+    if images_tensor.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f'images must be float32 in [0,1] (reference inference.py:18) or uint8 RGB bytes, got {images_tensor.dtype}')
     device = _resolve_device(images_tensor)
     n = int(images_tensor.shape[0]) if images_tensor.dim() == 4 else 0
     rank, world = 0, 1
@@ -253,9 +259,14 @@ def main(argv=None):
                              'then the chroma rows as ffmpeg -f rawvideo writes them); converted per tap in the warp')
     parser.add_argument('--color-matrix', type=str, default=None, choices=['bt601', 'bt709'],
                         help='YUV matrix of an nv12 / i420 --frame (limited range; default bt601, OpenCV\'s)')
+    parser.add_argument('--crop-dtype', type=str, default=None, choices=['float32', 'uint8'],
+                        help="dtype of the crops the warp cuts from --frame: 'float32' (default) or 'uint8' (the remapped bytes, "
+                             'read by the network as they are: the same poses from a quarter of the crop bytes)')
     opts = parser.parse_args(argv)
     if opts.frame:
         return _main_frame(opts)
+    if opts.crop_dtype:
+        parser.error('--crop-dtype goes with --frame')
     if opts.box or opts.intrinsics or opts.distortion or opts.bone_lengths or opts.root_depth or opts.views is not None:
         parser.error('--box, --intrinsics, --distortion, --bone-lengths, --root-depth and --views go with --frame')
     if opts.pixel_format or opts.color_matrix:
@@ -294,7 +305,8 @@ def _main_frame(opts):
         camera = Camera(np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]]), dist)
     elif opts.distortion:
         raise SystemExit('--distortion needs --intrinsics')
-    fmt = dict(pixel_format=opts.pixel_format or 'rgb', color_matrix=opts.color_matrix or 'bt601')
+    fmt = dict(pixel_format=opts.pixel_format or 'rgb', color_matrix=opts.color_matrix or 'bt601',
+               crop_dtype=opts.crop_dtype or 'float32')
     if opts.bone_lengths or opts.root_depth:
         return _main_locate(opts, frame, boxes, camera, fmt)
     try:
