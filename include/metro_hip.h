@@ -621,6 +621,45 @@ int  metro_merge_views(const float* d_poses, const float* d_keypoints, const flo
                        const MetroPlacement* d_records, const int32_t* d_mirror, int32_t n, int32_t n_views, int32_t n_joints,
                        float* d_poses_out, float* d_keypoints_out, float* d_z_offset_out, float* d_spread_out, void* stream);
 
+/* ---- per-joint heat-map covariance and peak confidence ----
+ * Every joint's output is a softmax distribution p over its S x S x D volume and the pose is only its mean.  With the voxel
+ * coordinates c = (x01, y01, z01) the soft-argmax uses (fp32 linspace(0,1,.)) and mu = sum p c (= coords01):
+ *   Cov01 = sum p (c - mu)(c - mu)^T     stored as six fp32 words xx, yy, zz, xy, xz, yz;      peak = max p.
+ * This is the spread of the joint's OWN heat-map in the crop's virtual-camera axes -- not of the root-relative difference the
+ * poses are.  The statistics are centred at every step (each record about its own mean, merged with the parallel-axis
+ * update): variances are sums of non-negative terms and a one-hot heat-map gives exactly 0.
+ * d_moments_scratch: caller's device buffer of metro_moments_scratch_bytes(spec, n) bytes, 16-byte aligned (the plan's
+ * workspace is not touched by it: its size and layout are those of metro_forward). */
+int64_t metro_moments_scratch_bytes(const MetroSpec* spec, int32_t n);
+/* metro_forward_coords01 (images_u8 == 0: d_images_nhwc fp32) or metro_forward_u8 (images_u8 == 1: uint8, f16 plans only)
+ * that ALSO writes d_cov01_out fp32 [n, n_joints_head, 6] and d_peak_out fp32 [n, n_joints_head] (head joint order), from the
+ * MOMENTS instantiations of the same head / soft-argmax launches: same launch count; poses, coords01 and status words have
+ * the bits of those entries on the same input.  d_coords01_out may be NULL; d_cov01_out, d_peak_out and d_moments_scratch go
+ * together (all NULL: the plain forward, eagerly).  Always plain launches: the hipGraph cache does not serve this entry. */
+int  metro_forward_moments(MetroPlan* plan, const void* d_images_nhwc, int32_t images_u8, int32_t n, float* d_poses_out,
+                           float* d_coords01_out, float* d_cov01_out, float* d_peak_out, void* d_moments_scratch,
+                           void* d_workspace, void* stream);
+/* metro_head_f16 with the moments: d_coords01_out (optional), d_cov01_out, d_peak_out as above; d_poses_out optional. */
+int  metro_head_f16_moments(const void* d_x, const void* d_w, const float* d_bias, const void* d_pro_scale,
+                            const void* d_pro_shift, int32_t n, int32_t c_in, const MetroSpec* spec, void* d_partials,
+                            void* d_moments_scratch, float* d_logits_out, float* d_poses_out, float* d_coords01_out,
+                            float* d_cov01_out, float* d_peak_out, void* stream);
+/* metro_softargmax01 with the moments (precise 0 / 1 / 2 as there; the records are in the accumulator type). */
+int  metro_softargmax01_moments(const void* d_logits, int32_t n, const MetroSpec* spec, int32_t precise, void* d_scratch,
+                                void* d_moments_scratch, float* d_coords01_out, float* d_cov01_out, float* d_peak_out,
+                                void* stream);
+/* Covariances in mm^2, output joint order, requested coordinates, one launch, one thread per (box, output joint).
+ * d_cov01 / d_peak: [n * n_views, n_joints_head, 6] / [n * n_views, n_joints_head] (box-major rows i * n_views + v).
+ * Gathers spec->permutation; Cov_mm = diag(s) Cov01 diag(s) with the linear part of heatmap_to_metric,
+ * s = (lrc box_size_mm / proc_side, the same, box_size_mm) (volumetric.py:288-306; the half stride does not enter);
+ * coords CAMERA / WORLD: R Cov R^T with the row's rot_to_orig_cam / rot_to_world of d_records (n * n_views MetroPlacement),
+ * taking the mirror joint's covariance (d_mirror int32 [n_joints_out]) when det R <= 0 as metro_to_orig_cam does; CROP reads
+ * neither.  Views are averaged (covariances after rotation, and peaks).  MeTRo's metric scale, whatever scale recovery
+ * placed the poses.  d_cov_out fp32 [n, n_joints_out, 9] (row-major symmetric 3x3); d_peak_out fp32 [n, n_joints_out]. */
+int  metro_place_covariances(const float* d_cov01, const float* d_peak, const MetroPlacement* d_records, int32_t n,
+                             int32_t n_views, const MetroSpec* spec, const int32_t* d_mirror, int32_t coords,
+                             float* d_cov_out, float* d_peak_out, void* stream);
+
 const char* metro_last_error(void);
 int32_t metro_abi_version(void);
 

@@ -178,6 +178,11 @@ SIGNATURES = {
     'metro_head_f16_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     'metro_head_f16': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(MetroSpec), _P, _P, _P, _P]),
     'metro_softargmax': (C.c_int, [_P, C.c_int32, C.POINTER(MetroSpec), C.c_int32, _P, _P, _P]),
+    'metro_moments_scratch_bytes': (C.c_int64, [C.POINTER(MetroSpec), C.c_int32]),
+    'metro_forward_moments': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    'metro_head_f16_moments': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(MetroSpec)] + [_P] * 8),
+    'metro_softargmax01_moments': (C.c_int, [_P, C.c_int32, C.POINTER(MetroSpec), C.c_int32, _P, _P, _P, _P, _P, _P]),
+    'metro_place_covariances': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(MetroSpec), _P, C.c_int32, _P, _P, _P]),
     'metro_last_error': (C.c_char_p, []),
     'metro_abi_version': (C.c_int32, []),
 }

@@ -407,6 +407,60 @@ int metro_head_f16(const void* d_x, const void* d_w, const float* d_bias, const 
                                       static_cast<hipStream_t>(stream));
 }
 
+static int check_head_args(const MetroSpec* spec, int32_t n, int32_t n_edges, const char* what);
+
+int metro_head_f16_moments(const void* d_x, const void* d_w, const float* d_bias, const void* d_pro_scale, const void* d_pro_shift,
+                           int32_t n, int32_t c_in, const MetroSpec* spec, void* d_partials, void* d_moments_scratch,
+                           float* d_logits_out, float* d_poses_out, float* d_coords01_out, float* d_cov01_out, float* d_peak_out,
+                           void* stream) {
+    METRO_CHECK_ARG(d_x && d_w && d_bias && d_pro_scale && d_pro_shift && spec && d_partials && d_moments_scratch && d_cov01_out &&
+                        d_peak_out && n > 0, "head_f16_moments: bad argument");
+    METRO_CHECK_ARG(spec->n_joints_head >= 1 && spec->n_joints_head <= METRO_MAX_JOINTS && spec->n_joints_out >= 1 &&
+                        spec->n_joints_out <= METRO_MAX_JOINTS, "head_f16_moments: joint counts out of range");
+    METRO_CHECK_ARG((spec->depth * spec->n_joints_head) % 4 == 0, "head_f16_moments: depth*n_joints_head must be a multiple of 4");
+    const int side = spec->proc_side / spec->stride;
+    const SoftArgmaxArgs a = make_softargmax_args(*spec, n);
+    MomentsOut mo;
+    mo.scratch = d_moments_scratch; mo.cov01 = d_cov01_out; mo.peak = d_peak_out;
+    int st = launch_head_f16(d_x, d_w, d_bias, d_pro_scale, d_pro_shift, n, c_in, spec->depth * spec->n_joints_head,
+                             spec->n_joints_head, spec->depth, side, static_cast<float*>(d_partials), d_logits_out,
+                             static_cast<hipStream_t>(stream), static_cast<float*>(d_moments_scratch));
+    if (st) return st;
+    return launch_softargmax_finalize(static_cast<const float*>(d_partials), a,
+                                      head_f16_records(n, c_in, spec->depth * spec->n_joints_head, side), d_poses_out,
+                                      static_cast<hipStream_t>(stream), d_coords01_out, nullptr, mo);
+}
+
+int metro_softargmax01_moments(const void* d_logits, int32_t n, const MetroSpec* spec, int32_t precise, void* d_partials,
+                               void* d_moments_scratch, float* d_coords01_out, float* d_cov01_out, float* d_peak_out,
+                               void* stream) {
+    METRO_CHECK_ARG(d_logits && spec && d_partials && d_moments_scratch && d_cov01_out && d_peak_out && n > 0,
+                    "softargmax01_moments: bad argument");
+    METRO_CHECK_ARG(spec->n_joints_head >= 1 && spec->n_joints_head <= METRO_MAX_JOINTS, "softargmax01_moments: joint count out of range");
+    METRO_CHECK_ARG(spec->proc_side / spec->stride >= 2, "softargmax01_moments: heat-map side must be >= 2");
+    const SoftArgmaxArgs a = make_softargmax_args(*spec, n);
+    MomentsOut mo;
+    mo.scratch = d_moments_scratch; mo.cov01 = d_cov01_out; mo.peak = d_peak_out;
+    return launch_softargmax(d_logits, a, precise, d_partials, nullptr, static_cast<hipStream_t>(stream), d_coords01_out, nullptr, mo);
+}
+
+int metro_place_covariances(const float* d_cov01, const float* d_peak, const MetroPlacement* d_records, int32_t n, int32_t n_views,
+                            const MetroSpec* spec, const int32_t* d_mirror, int32_t coords, float* d_cov_out, float* d_peak_out,
+                            void* stream) {
+    int st = check_head_args(spec, n, 0, "place_covariances");
+    if (st) return st;
+    METRO_CHECK_ARG(coords >= METRO_COORDS_CROP && coords <= METRO_COORDS_WORLD,
+                    "place_covariances: coords must be METRO_COORDS_CROP, _CAMERA or _WORLD (got %d)", coords);
+    METRO_CHECK_ARG(d_cov01 && d_peak && d_cov_out && d_peak_out, "place_covariances: NULL cov01 / peak / output pointer");
+    METRO_CHECK_ARG(coords == METRO_COORDS_CROP || (d_records && d_mirror), "place_covariances: camera / world coords need the records "
+                    "and the mirror table");
+    METRO_CHECK_ARG(n_views >= 1 && n_views <= METRO_MAX_VIEWS, "place_covariances: %d views (1 to %d)", n_views, METRO_MAX_VIEWS);
+    METRO_CHECK_ARG((int64_t)n * n_views * spec->n_joints_head * 6 <= INT32_MAX, "place_covariances: %d boxes x %d views overflow int32",
+                    n, n_views);
+    return launch_place_covariances(d_cov01, d_peak, d_records, n, n_views, *spec, d_mirror, coords, d_cov_out, d_peak_out,
+                                    static_cast<hipStream_t>(stream));
+}
+
 int metro_softargmax01(const void* d_logits, int32_t n, const MetroSpec* spec, int32_t precise, void* d_partials,
                        float* d_coords01_out, void* stream) {
     METRO_CHECK_ARG(d_logits && spec && d_partials && d_coords01_out && n > 0, "softargmax01: bad argument");

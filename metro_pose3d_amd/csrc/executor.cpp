@@ -11,8 +11,9 @@ namespace {
 // chip also write them out -- the fp32 logits of the one-launch head, conv1's output of a conv1+conv2 launch.
 // `coords01` (optional): the finalize launch also writes the soft-argmax coordinates in [0,1] there (metro_forward_coords01).
 // `images_u8` (metro_forward_u8): `images` points to uint8 crops; the layer that reads them runs the uint8 form of its kernel.
+// `mo` (metro_forward_moments): its scratch selects the MOMENTS instantiations of the head / soft-argmax launches.
 int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* images, int n, float* poses, char* ws, hipStream_t stream, bool dump,
-                 float* coords01 = nullptr, bool images_u8 = false) {
+                 float* coords01 = nullptr, bool images_u8 = false, const MomentsOut& mo = MomentsOut{}) {
     const Layer& L = p->layers[li];
     auto slot_ptr = [&](int slot) -> void* {
         if (slot == S_IMAGES) return const_cast<float*>(images);
@@ -40,7 +41,8 @@ int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* 
                 case LayerForm::Head: {
                     float* logits_dump = dump ? static_cast<float*>(out) : nullptr;
                     return launch_head_f16(in, w, bias, prm(L.main.scale), prm(L.main.shift), n, L.cd.c_in, L.cd.c_out, p->spec.n_joints_head,
-                                           p->spec.depth, L.cd.h_in, static_cast<float*>(slot_ptr(S_PART)), logits_dump, stream);
+                                           p->spec.depth, L.cd.h_in, static_cast<float*>(slot_ptr(S_PART)), logits_dump, stream,
+                                           static_cast<float*>(mo.scratch));
                 }
                 case LayerForm::StemPoolF32In:
                     if (images_u8)
@@ -93,10 +95,10 @@ int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* 
             if (L.form == LayerForm::Head)
                 return launch_softargmax_finalize(static_cast<const float*>(slot_ptr(S_PART)), a,
                                                   head_f16_records(n, L.head_c_in, a.depth * a.n_joints_head, a.side), poses, stream, coords01,
-                                                  static_cast<int32_t*>(slot_ptr(S_STATUS)));
+                                                  static_cast<int32_t*>(slot_ptr(S_STATUS)), mo);
             // precise: 0 fp32 / fp32, 1 fp32 logits + fp64 accumulators (F32 and F32M modes), 2 fp64 / fp64
             return launch_softargmax(slot_ptr(L.in_slot), a, p->spec.precision == METRO_PREC_F32M ? 1 : p->spec.precision, slot_ptr(S_PART), poses, stream,
-                                     coords01, static_cast<int32_t*>(slot_ptr(S_STATUS)));
+                                     coords01, static_cast<int32_t*>(slot_ptr(S_STATUS)), mo);
         }
     }
     set_error("internal: layer %d has unknown kind %d", li, L.kind);
@@ -104,7 +106,7 @@ int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* 
 }
 
 int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_, hipStream_t stream,
-               int last_layer, float* ms_out, float* coords01 = nullptr, bool images_u8 = false) {
+               int last_layer, float* ms_out, float* coords01 = nullptr, bool images_u8 = false, const MomentsOut& mo = MomentsOut{}) {
     METRO_CHECK_ARG(p != nullptr, "plan is NULL");
     METRO_CHECK_ARG(n > 0 && n <= p->max_batch, "batch %d outside [1, %d]", n, p->max_batch);
     METRO_CHECK_ARG(images != nullptr && ws_ != nullptr, "NULL images/workspace pointer");
@@ -121,7 +123,7 @@ int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_
     int st = METRO_OK;
     for (int li = 0; li <= last_layer && st == METRO_OK; ++li) {
         if (ms_out) METRO_HIP_CHECK(hipEventRecord(ev[2 * li], stream));
-        st = launch_layer(p, p->d_params, li, images, n, poses, ws, stream, li == last_layer && li + 1 < nl, coords01, images_u8);
+        st = launch_layer(p, p->d_params, li, images, n, poses, ws, stream, li == last_layer && li + 1 < nl, coords01, images_u8, mo);
         if (ms_out) METRO_HIP_CHECK(hipEventRecord(ev[2 * li + 1], stream));
     }
     if (ms_out) {
@@ -237,6 +239,32 @@ int metro_forward_u8(MetroPlan* plan, const uint8_t* d_images_nhwc, int32_t n, f
     // eager: the captured-forward cache is keyed for metro_forward's fp32 images only
     return run_layers(plan, reinterpret_cast<const float*>(d_images_nhwc), n, d_poses_out, d_workspace, static_cast<hipStream_t>(stream), -1,
                       nullptr, d_coords01_out, true);
+}
+
+int64_t metro_moments_scratch_bytes(const MetroSpec* spec, int32_t n) {
+    if (spec == nullptr || n <= 0 || spec->stride <= 0 || spec->proc_side / spec->stride < 2 || spec->n_joints_head <= 0) return -1;
+    return moments_scratch_bytes(n, spec->proc_side / spec->stride, spec->n_joints_head);
+}
+
+int metro_forward_moments(MetroPlan* plan, const void* d_images_nhwc, int32_t images_u8, int32_t n, float* d_poses_out,
+                          float* d_coords01_out, float* d_cov01_out, float* d_peak_out, void* d_moments_scratch,
+                          void* d_workspace, void* stream) {
+    METRO_CHECK_ARG(plan != nullptr, "metro_forward_moments: plan is NULL");
+    METRO_CHECK_ARG(d_poses_out != nullptr, "metro_forward_moments: NULL poses pointer");
+    METRO_CHECK_ARG(images_u8 == 0 || images_u8 == 1, "metro_forward_moments: images_u8 must be 0 or 1 (got %d)", images_u8);
+    METRO_CHECK_ARG(!images_u8 || plan->spec.precision == METRO_PREC_F16,
+                    "metro_forward_moments: uint8 crops run on f16 plans only; for this precision expand them with "
+                    "metro_images_u8_to_f32");
+    METRO_CHECK_ARG(!images_u8 || ((uintptr_t)d_images_nhwc & 15) == 0,
+                    "metro_forward_moments: uint8 crops must start at a 16-byte aligned address (got %p)", d_images_nhwc);
+    METRO_CHECK_ARG((d_cov01_out != nullptr) == (d_peak_out != nullptr) && (d_cov01_out != nullptr) == (d_moments_scratch != nullptr),
+                    "metro_forward_moments: cov01_out, peak_out and the moments scratch go together (all three or none)");
+    METRO_CHECK_ARG(((uintptr_t)d_moments_scratch & 15) == 0, "metro_forward_moments: the moments scratch must be 16-byte aligned");
+    MomentsOut mo;
+    mo.scratch = d_moments_scratch; mo.cov01 = d_cov01_out; mo.peak = d_peak_out;
+    // eager, like metro_forward_u8: the captured-forward cache is keyed for metro_forward / metro_forward_coords01 only
+    return run_layers(plan, static_cast<const float*>(d_images_nhwc), n, d_poses_out, d_workspace, static_cast<hipStream_t>(stream), -1,
+                      nullptr, d_coords01_out, images_u8 != 0, mo);
 }
 
 int metro_forward_status(const MetroPlan* plan, const void* d_workspace, int32_t n, void* stream_, int32_t* n_nonfinite_out) {

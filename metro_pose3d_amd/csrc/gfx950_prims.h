@@ -109,6 +109,15 @@ __device__ __forceinline__ half4_t bias_cvt(const floatx16& acc, int q, const fl
     return __builtin_bit_cast(half4_t, r);
 }
 
+// A copy of a register value the optimiser knows nothing about (no instruction).  The MOMENTS instantiations of the head and
+// soft-argmax kernels take their inputs through it: code added behind the default path then shares no expression with it -- a
+// product that gains a second use is no longer contracted into an fma with its sum, which moved the default results by an ulp.
+template <typename T>
+__device__ __forceinline__ T opaque_copy(T v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
 // f(integral_constant<0>) ... f(integral_constant<N - 1>), in that order
 template <int N, int I = 0, class F>
 __device__ __forceinline__ void static_for(F&& f) {

@@ -46,6 +46,8 @@ struct HeadArgs {
     const half_t* pro_shift;
     float* partials;          // [n][slabs][J][5]: m, S, Sx, Sy, Sz
     float* logits_out;        // optional fp32 NHWC logits [n * pixels][C] (tests / layer dumps); NULL in the product path
+    float* moments;           // MOMENTS instantiations: [n][slabs][J][6] second central moments of each record about ITS OWN mean,
+                              // weighted like S (xx, yy, zz, xy, xz, yz); NULL otherwise
     int K, C, J, D, side, pixels, slabs;
     // Heads wider than 160 channels (the 53-joint `merged` export: 424, reference data/datasets.py:142-154, main.py:119-127) run the
     // ring kernel once per GROUP of JG joints (blockIdx.z): a group's sub-head is the D * jg rows d * J + j0 + j' of the weight
@@ -54,6 +56,7 @@ struct HeadArgs {
     int JG;
 };
 
+template <bool MOMENTS>
 __global__ __launch_bounds__(hd::NT) void head_f16_kernel(HeadArgs a) {
     using namespace hd;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -218,6 +221,28 @@ __global__ __launch_bounds__(hd::NT) void head_f16_kernel(HeadArgs a) {
             float* o5 = a.partials + (((size_t)img * a.slabs + slab) * a.J + j) * 5;
             o5[0] = m; o5[1] = s; o5[2] = sx; o5[3] = sy; o5[4] = sz;
         }
+        if constexpr (MOMENTS) {
+            // second central moments of the slab about the slab's own mean (every lane holds the folded sums): one more pass over
+            // the lane's D values, one more fold.  Sums of non-negative terms on the diagonal: nothing cancels on a sharp peak.
+            const float inv = 1.0f / opaque_copy(s), mo = opaque_copy(m), sdo = opaque_copy(step_d);
+            const float dx = opaque_copy(cx) - opaque_copy(sx) * inv, dy = opaque_copy(cy) - opaque_copy(sy) * inv, mz = opaque_copy(sz) * inv;
+            float sl = 0.f, z1 = 0.f, z2 = 0.f;
+            for (int d = 0; d < a.D; ++d) {
+                const float e = __expf(opaque_copy(lt[lane * LROW + d * a.J + j]) - mo);
+                const float dz = opaque_copy((float)d * sdo) - mz;      // the ROUNDED coordinate of the first pass: no fma into the difference
+                sl += e; z1 += e * dz; z2 += e * dz * dz;
+            }
+            float c[6] = {sl * dx * dx, sl * dy * dy, z2, sl * dx * dy, dx * z1, dy * z1};
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1)
+#pragma unroll
+                for (int k = 0; k < 6; ++k) c[k] += __shfl_xor(c[k], o, 64);
+            if (lane == 0) {
+                float* o6 = a.moments + (((size_t)img * a.slabs + slab) * a.J + j) * 6;
+#pragma unroll
+                for (int k = 0; k < 6; ++k) o6[k] = c[k];
+            }
+        }
     }
 }
 
@@ -226,14 +251,19 @@ __global__ __launch_bounds__(hd::NT) void head_f16_kernel(HeadArgs a) {
 // with xor butterflies 16 .. 1 (ds_swizzle: no address arithmetic, never crossing halves).  Depth 8 (every BASELINE config): the
 // D logits of FIVE joints are read at once and their five reductions run side by side -- the serial form (a dependent LDS read per
 // depth, a dependent shuffle per fold step, one joint at a time) cost 17 of the 69 us of the 256-pixel head.
+constexpr int HD_NJM = 5;      // joints at a time of the MOMENTS instantiations (register counts: NOTES_dead_ends.md)
 template <int O>
 __device__ __forceinline__ float hd_xor32(float v) {
     return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), (O << 10) | 0x1F));
 }
-template <typename F>
+// MOMENTS: every record is followed by record_m(j, c[6]) -- the six second central moments of the tile's voxels about the tile's
+// OWN mean (sx / s, sy / s, sz / s, which every lane holds after the fold), weighted like s, in the order xx, yy, zz, xy, xz, yz:
+// one more pass over the lane's D values (the exponentials are taken again rather than kept: D registers per joint) and one more
+// butterfly fold.  softargmax_finalize merges the tiles with the parallel-axis update.
+template <bool MOMENTS, int NJM, typename F, typename G>
 __device__ __forceinline__ void hd_tile_stats(const float* row, int J, int D, int j0, int js, float cx, float cy, float step_d,
-                                              bool writer, F&& record) {
-    constexpr int NJ = 5;
+                                              bool writer, F&& record, G&& record_m) {
+    constexpr int NJ = MOMENTS ? NJM : 5;
     if (D == 8) {
         for (int jb = j0; jb < J; jb += NJ * js) {
             float v[NJ][8], m[NJ], s[NJ], sx[NJ], sy[NJ], sz[NJ];
@@ -276,6 +306,34 @@ __device__ __forceinline__ void hd_tile_stats(const float* row, int J, int D, in
                 for (int q = 0; q < NJ; ++q)
                     if (jb + q * js < J) record(jb + q * js, m[q], s[q], sx[q], sy[q], sz[q]);
             }
+            if constexpr (MOMENTS) {
+                float c[NJ][6];
+#pragma unroll
+                for (int q = 0; q < NJ; ++q) {
+                    const float inv = 1.0f / opaque_copy(s[q]), mo = opaque_copy(m[q]), sdo = opaque_copy(step_d);
+                    const float dx = opaque_copy(cx) - opaque_copy(sx[q]) * inv, dy = opaque_copy(cy) - opaque_copy(sy[q]) * inv;
+                    const float mz = opaque_copy(sz[q]) * inv;
+                    float sl = 0.f, z1 = 0.f, z2 = 0.f;
+#pragma unroll
+                    for (int d = 0; d < 8; ++d) {
+                        const float e = __expf(opaque_copy(v[q][d]) - mo);
+                        const float dz = opaque_copy((float)d * sdo) - mz;      // the ROUNDED coordinate of the first pass: no fma into the difference
+                        sl += e; z1 += e * dz; z2 += e * dz * dz;
+                    }
+                    c[q][0] = sl * dx * dx; c[q][1] = sl * dy * dy; c[q][2] = z2;
+                    c[q][3] = sl * dx * dy; c[q][4] = dx * z1; c[q][5] = dy * z1;
+                }
+#define HD_FOLD_MOM(O)                                                        \
+    _Pragma("unroll") for (int q = 0; q < NJ; ++q)                            \
+        _Pragma("unroll") for (int k = 0; k < 6; ++k) c[q][k] += hd_xor32<O>(c[q][k])
+                HD_FOLD_MOM(16); HD_FOLD_MOM(8); HD_FOLD_MOM(4); HD_FOLD_MOM(2); HD_FOLD_MOM(1);
+#undef HD_FOLD_MOM
+                if (writer) {
+#pragma unroll
+                    for (int q = 0; q < NJ; ++q)
+                        if (jb + q * js < J) record_m(jb + q * js, c[q]);
+                }
+            }
         }
         return;
     }
@@ -295,6 +353,23 @@ __device__ __forceinline__ void hd_tile_stats(const float* row, int J, int D, in
         HD_FOLD1(16); HD_FOLD1(8); HD_FOLD1(4); HD_FOLD1(2); HD_FOLD1(1);
 #undef HD_FOLD1
         if (writer) record(j, m, s, sx, sy, sz);
+        if constexpr (MOMENTS) {
+            const float inv = 1.0f / opaque_copy(s), mo = opaque_copy(m), sdo = opaque_copy(step_d);
+            const float dx = opaque_copy(cx) - opaque_copy(sx) * inv, dy = opaque_copy(cy) - opaque_copy(sy) * inv, mz = opaque_copy(sz) * inv;
+            float sl = 0.f, z1 = 0.f, z2 = 0.f;
+            for (int d = 0; d < D; ++d) {
+                const float e = __expf(opaque_copy(row[d * J + j]) - mo);
+                const float dz = opaque_copy((float)d * sdo) - mz;      // the ROUNDED coordinate of the first pass: no fma into the difference
+                sl += e; z1 += e * dz; z2 += e * dz * dz;
+            }
+            float c[6] = {sl * dx * dx, sl * dy * dy, z2, sl * dx * dy, dx * z1, dy * z1};
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                c[k] += hd_xor32<16>(c[k]); c[k] += hd_xor32<8>(c[k]); c[k] += hd_xor32<4>(c[k]);
+                c[k] += hd_xor32<2>(c[k]); c[k] += hd_xor32<1>(c[k]);
+            }
+            if (writer) record_m(j, c);
+        }
     }
 }
 
@@ -322,6 +397,7 @@ constexpr int WTILE_BYTES = 4 * 32 * LROW * 4;           // four wave-private [3
 static_assert(LDS_BYTES <= 160 * 1024 && LOGITS_BYTES <= RING_BYTES && WTILE_BYTES <= RING_BYTES && GA <= 2 * NW && GB == 2 * NW, "LDS / loader split");
 }  // namespace hd2
 
+template <bool MOMENTS>
 __global__ __launch_bounds__(hd2::NT) void head_f16_kernel256(HeadArgs a) {
     using namespace hd2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -456,10 +532,16 @@ __global__ __launch_bounds__(hd2::NT) void head_f16_kernel256(HeadArgs a) {
             const float cx = (float)px * step_s, cy = (float)py * step_s;
             const int slab = tile * (TN / 32) + wave;
             float* rec = a.partials + ((size_t)img * a.slabs + slab) * a.J * 5;
-            hd_tile_stats(lt + frag_row * LROW, a.J, a.D, frag_half, 2, cx, cy, step_d, frag_row == 0,
+            float* recm = MOMENTS ? a.moments + ((size_t)img * a.slabs + slab) * a.J * 6 : nullptr;
+            hd_tile_stats<MOMENTS, HD_NJM>(lt + frag_row * LROW, a.J, a.D, frag_half, 2, cx, cy, step_d, frag_row == 0,
                           [&](int j, float m, float s_, float sx, float sy, float sz) {
                               float* o5 = rec + j * 5;
                               o5[0] = m; o5[1] = s_; o5[2] = sx; o5[3] = sy; o5[4] = sz;
+                          },
+                          [&](int j, const float* c) {
+                              float* o6 = recm + j * 6;
+#pragma unroll
+                              for (int k = 0; k < 6; ++k) o6[k] = c[k];
                           });
         }
         __syncthreads();
@@ -521,7 +603,7 @@ __device__ __forceinline__ void hd_pin() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
-template <int TN_, int KSPLIT_, int WROWS_>
+template <int TN_, int KSPLIT_, int WROWS_, bool MOMENTS>
 __global__ __launch_bounds__(512, 2) void head_f16_ring_kernel(HeadArgs a) {
     using G = HeadRing<TN_, KSPLIT_, WROWS_>;
     constexpr int TN = G::TN, KSPLIT = G::KSPLIT, WROWS = G::WROWS, MT = G::MT, BK = G::BK, NW = G::NW, PT = G::PT, NP = G::NP;
@@ -765,10 +847,16 @@ __global__ __launch_bounds__(512, 2) void head_f16_ring_kernel(HeadArgs a) {
         const float cx = (float)px * step_s, cy = (float)py * step_s;
         const int slab = tile * (TN / 32) + pg * PT + t;
         float* rec = a.partials + (((size_t)img * a.slabs + slab) * a.J + j0) * 5;
-        hd_tile_stats(lt0 + frag_row * LROW, jg, a.D, h * 2 + frag_half, 2 * KSPLIT, cx, cy, step_d, frag_row == 0,
+        float* recm = MOMENTS ? a.moments + (((size_t)img * a.slabs + slab) * a.J + j0) * 6 : nullptr;
+        hd_tile_stats<MOMENTS, HD_NJM>(lt0 + frag_row * LROW, jg, a.D, h * 2 + frag_half, 2 * KSPLIT, cx, cy, step_d, frag_row == 0,
                       [&](int j, float m, float s_, float sx, float sy, float sz) {
                           float* o5 = rec + j * 5;
                           o5[0] = m; o5[1] = s_; o5[2] = sx; o5[3] = sy; o5[4] = sz;
+                      },
+                      [&](int j, const float* c) {
+                          float* o6 = recm + j * 6;
+#pragma unroll
+                          for (int k = 0; k < 6; ++k) o6[k] = c[k];
                       });
         if (t + 1 < PT) __syncthreads();                          // the tiles are rewritten in the next round
     }
@@ -813,20 +901,38 @@ int head_f16_records(int n, int c_in, int c_head, int side) {
     return head_f16_variant(n, c_in, c_head, side) == 0 ? side * side / hd::TN : side * side / 32;
 }
 
-template <int TN, int KSPLIT, int WROWS>
-static int launch_head_ring(const HeadArgs& a, int n, int side, hipStream_t stream) {
+template <int TN, int KSPLIT, int WROWS, bool MOMENTS>
+static int launch_head_ring_t(const HeadArgs& a, int n, int side, hipStream_t stream) {
     using G = HeadRing<TN, KSPLIT, WROWS>;
-    auto kern = head_f16_ring_kernel<TN, KSPLIT, WROWS>;
+    auto kern = head_f16_ring_kernel<TN, KSPLIT, WROWS, MOMENTS>;
     static PerDeviceInt done;
     if (const int st = ensure_dyn_lds(reinterpret_cast<const void*>(kern), G::LDS_BYTES, done, "head_f16<ring>")) return st;
     const int groups = a.JG > 0 ? (a.J + a.JG - 1) / a.JG : 1;
     hipLaunchKernelGGL(kern, dim3(side * side / TN, n, groups), dim3(G::NT), G::LDS_BYTES, stream, a);
     return launch_status("head_f16<ring>");
 }
+template <int TN, int KSPLIT, int WROWS>
+static int launch_head_ring(const HeadArgs& a, int n, int side, hipStream_t stream) {
+    return a.moments ? launch_head_ring_t<TN, KSPLIT, WROWS, true>(a, n, side, stream)
+                     : launch_head_ring_t<TN, KSPLIT, WROWS, false>(a, n, side, stream);
+}
+template <bool MOMENTS>
+static int launch_head_plain(const HeadArgs& a, int n, int side, int variant, hipStream_t stream) {
+    if (variant == 1) {
+        static PerDeviceInt done2;
+        if (const int st = ensure_dyn_lds(reinterpret_cast<const void*>(head_f16_kernel256<MOMENTS>), hd2::LDS_BYTES, done2, "head_f16<256>")) return st;
+        hipLaunchKernelGGL(head_f16_kernel256<MOMENTS>, dim3(side * side / hd2::TN, n), dim3(hd2::NT), hd2::LDS_BYTES, stream, a);
+        return launch_status("head_f16<256>");
+    }
+    static PerDeviceInt done;
+    if (const int st = ensure_dyn_lds(reinterpret_cast<const void*>(head_f16_kernel<MOMENTS>), hd::LDS_BYTES, done, "head_f16")) return st;
+    hipLaunchKernelGGL(head_f16_kernel<MOMENTS>, dim3(a.slabs, n), dim3(hd::NT), hd::LDS_BYTES, stream, a);
+    return launch_status("head_f16");
+}
 
 int launch_head_f16(const void* x, const void* w, const float* bias, const void* pro_scale, const void* pro_shift,
                     int n, int c_in, int c_head, int n_joints, int depth, int side, float* partials, float* logits_out,
-                    hipStream_t stream) {
+                    hipStream_t stream, float* moments) {
     if (!head_f16_supported(c_in, c_head, n_joints, depth, side)) {
         set_error("head_f16: unsupported head (c_in %d, %d channels = %d joints x depth %d, side %d)", c_in, c_head, n_joints, depth, side);
         return METRO_ERR_UNSUPPORTED;
@@ -836,29 +942,21 @@ int launch_head_f16(const void* x, const void* w, const float* bias, const void*
     const int wrows = jgrp > 0 ? 160 : c_head <= 144 ? 144 : 160;
     char grp[16] = "";
     if (jgrp > 0) snprintf(grp, sizeof(grp), ",g%d", (n_joints + jgrp - 1) / jgrp);
-    if (variant >= 2 ? note_kernel("head_f16<%dx%d,k%d%s>", wrows, variant == 2 ? 256 : variant == 3 ? 128 : 64, variant == 2 ? 2 : 4, grp)
-                     : note_kernel(variant == 1 ? "head_f16<160x256>" : "head_f16<160x64>"))
+    const char* mom = moments ? ",moments" : "";
+    if (variant >= 2 ? note_kernel("head_f16<%dx%d,k%d%s%s>", wrows, variant == 2 ? 256 : variant == 3 ? 128 : 64, variant == 2 ? 2 : 4, grp, mom)
+                     : note_kernel(variant == 1 ? "head_f16<160x256%s>" : "head_f16<160x64%s>", mom))
         return METRO_OK;
     HeadArgs a;
     a.x = static_cast<const half_t*>(x); a.w = static_cast<const half_t*>(w); a.bias = bias;
     a.pro_scale = static_cast<const half_t*>(pro_scale); a.pro_shift = static_cast<const half_t*>(pro_shift);
-    a.partials = partials; a.logits_out = logits_out;
+    a.partials = partials; a.logits_out = logits_out; a.moments = moments;
     a.K = c_in; a.C = c_head; a.J = n_joints; a.D = depth; a.side = side; a.pixels = side * side;
     a.slabs = head_f16_records(n, c_in, c_head, side);
     a.JG = jgrp;
     if (variant == 2) return launch_head_ring<256, 2, 144>(a, n, side, stream);
     if (variant == 3) return wrows == 144 ? launch_head_ring<128, 4, 144>(a, n, side, stream) : launch_head_ring<128, 4, 160>(a, n, side, stream);
     if (variant == 4) return wrows == 144 ? launch_head_ring<64, 4, 144>(a, n, side, stream) : launch_head_ring<64, 4, 160>(a, n, side, stream);
-    if (variant == 1) {
-        static PerDeviceInt done2;
-        if (const int st = ensure_dyn_lds(reinterpret_cast<const void*>(head_f16_kernel256), hd2::LDS_BYTES, done2, "head_f16<256>")) return st;
-        hipLaunchKernelGGL(head_f16_kernel256, dim3(side * side / hd2::TN, n), dim3(hd2::NT), hd2::LDS_BYTES, stream, a);
-        return launch_status("head_f16<256>");
-    }
-    static PerDeviceInt done;
-    if (const int st = ensure_dyn_lds(reinterpret_cast<const void*>(head_f16_kernel), hd::LDS_BYTES, done, "head_f16")) return st;
-    hipLaunchKernelGGL(head_f16_kernel, dim3(a.slabs, n), dim3(hd::NT), hd::LDS_BYTES, stream, a);
-    return launch_status("head_f16");
+    return moments ? launch_head_plain<true>(a, n, side, variant, stream) : launch_head_plain<false>(a, n, side, variant, stream);
 }
 
 }  // namespace metro

@@ -386,21 +386,34 @@ struct SoftArgmaxArgs {
     int proc_side;
     int perm[METRO_MAX_JOINTS];
 };
+// Heat-map moments (metro_forward_moments and the kernel-level *_moments entries): `scratch` non-NULL selects the MOMENTS
+// instantiations, which write one record of six second central moments per (image, slab, joint) there (moments_scratch_bytes;
+// in the accumulator type of the launch) and fold them into cov01 fp32 [n][J_head][6] (xx, yy, zz, xy, xz, yz) and peak [n][J_head].
+struct MomentsOut {
+    void* scratch = nullptr;
+    float* cov01 = nullptr;
+    float* peak = nullptr;
+};
+int64_t moments_scratch_bytes(int n, int side, int n_joints_head);
 int softargmax_slabs(int n, int side);
 int64_t softargmax_scratch_bytes(int n, int side, int n_joints_head);
 int launch_softargmax(const void* logits, const SoftArgmaxArgs& a, int precise, void* partials,
-                      float* poses_out, hipStream_t stream, float* coords01_out = nullptr, int32_t* status = nullptr);
+                      float* poses_out, hipStream_t stream, float* coords01_out = nullptr, int32_t* status = nullptr,
+                      const MomentsOut& mo = MomentsOut{});
 // `status` (optional, int32 [n]): 1 where an image's soft-argmax statistics were not finite (fp16 overflow upstream), else 0
 // finalize only (slabs folded, mm decode, root-relative, permutation) on fp32 partials written by another kernel
 int launch_softargmax_finalize(const float* partials, const SoftArgmaxArgs& a, int slabs, float* poses_out,
-                               hipStream_t stream, float* coords01_out = nullptr, int32_t* status = nullptr);
+                               hipStream_t stream, float* coords01_out = nullptr, int32_t* status = nullptr,
+                               const MomentsOut& mo = MomentsOut{});
 // the volumetric head in one launch (head_f16.hip): postnorm prologue + logits GEMM + per-joint softmax statistics
 bool head_f16_supported(int c_in, int c_head, int n_joints, int depth, int side);
 int head_f16_slabs(int side);               // records per image the partials slot must hold
 int head_f16_records(int n, int c_in, int c_head, int side);      // records per image a launch at batch n writes
 int launch_head_f16(const void* x, const void* w, const float* bias, const void* pro_scale, const void* pro_shift,
                     int n, int c_in, int c_head, int n_joints, int depth, int side, float* partials, float* logits_out,
-                    hipStream_t stream);
+                    hipStream_t stream, float* moments = nullptr);
+// `moments` (optional, fp32 [n][records][J][6]): the MOMENTS instantiation of the same kernel also writes every record's second
+// central moments (launch_softargmax_finalize folds them into cov01)
 // alternative decode heads (heads.hip): root_z != NULL selects true-root-depth, else the bone-length solve
 int launch_backproject(const float* coords01, const float* inv_k, const double* targets, int per_pose_targets,
                        const float* root_z, const int* edges, int n, int nj, int ne, const MetroSpec& spec,
@@ -418,6 +431,10 @@ int launch_expand_views(const MetroViewBase* bases, int n, const MetroView* view
 int launch_merge_views(const float* poses, const float* keypoints, const float* z, const MetroPlacement* rec, const int* mirror,
                        int n, int n_views, int nj, float* poses_out, float* keypoints_out, float* z_out, float* spread_out,
                        hipStream_t stream);
+// per-joint covariances of frame crops in the requested coordinates (covariances.hip)
+int launch_place_covariances(const float* cov01, const float* peak, const MetroPlacement* rec, int n, int n_views,
+                             const MetroSpec& spec, const int* mirror, int coords, float* cov_out, float* peak_out,
+                             hipStream_t stream);
 // per-box crop geometry of full frames (look_at_boxes.hip)
 int launch_look_at_boxes(const double* boxes, const int32_t* frame_index, int n, int n_frames, const MetroFrameCamera* cameras,
                          int n_cameras, int side, MetroViewBase* out, int32_t* status, hipStream_t stream);

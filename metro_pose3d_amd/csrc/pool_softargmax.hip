@@ -487,12 +487,18 @@ __device__ __forceinline__ AccT acc_exp(AccT x);
 template <> __device__ __forceinline__ float acc_exp<float>(float x) { return __expf(x); }
 template <> __device__ __forceinline__ double acc_exp<double>(double x) { return exp(x); }
 
-template <typename AccT, typename LogitT>
+// MOMENTS: every record is followed, in `moments` [n][slabs][J][6], by its six second central moments about ITS OWN mean
+// (xx, yy, zz, xy, xz, yz, weighted like S).  Centred from the first step: a pixel lane takes its channel's (xx, yy, xy) about
+// its own mean in a second walk over its pixels (the slab is L2-resident: it was streamed a moment ago) -- an online update of
+// centred sums needs a division per logit, raw sums E[x^2] - E[x]^2 cancel on a sharp peak -- and the two folds merge with the
+// parallel-axis update, rescaled by the same factor f as the sums: every diagonal term is a sum of non-negative numbers.
+template <typename AccT, typename LogitT, bool MOMENTS>
 __global__ __launch_bounds__(SA_NT) void softargmax_partial_kernel(
     const LogitT* __restrict__ logits, AccT* __restrict__ partials, int side, int depth, int nj,
-    int slabs) {
+    int slabs, AccT* __restrict__ moments) {
     extern __shared__ __attribute__((aligned(16))) char sa_smem[];
-    AccT* red = reinterpret_cast<AccT*>(sa_smem);   // [ppb][C][4]: m, s, sx, sy
+    constexpr int RS = MOMENTS ? 7 : 4;
+    AccT* red = reinterpret_cast<AccT*>(sa_smem);   // [ppb][C][RS]: m, s, sx, sy (MOMENTS: + xx, yy, xy)
 
     const int C = depth * nj;
     const int quads = C / 4;
@@ -554,10 +560,36 @@ __global__ __launch_bounds__(SA_NT) void softargmax_partial_kernel(
                 m[e] = mx; s[e] = s_; sx[e] = sx_; sy[e] = sy_;
             }
         }
+        AccT cxx[4] = {0, 0, 0, 0}, cyy[4] = {0, 0, 0, 0}, cxy[4] = {0, 0, 0, 0};
+        if constexpr (MOMENTS) {
+            AccT mux[4], muy[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const AccT so = opaque_copy(s[e]);
+                mux[e] = so > 0 ? opaque_copy(sx[e]) / so : (AccT)0;
+                muy[e] = so > 0 ? opaque_copy(sy[e]) / so : (AccT)0;
+            }
+            AccT mo[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) mo[e] = opaque_copy(m[e]);
+            const float sso = opaque_copy(step_s);
+            for (int p = p_begin + pp; p < p_end; p += ppb) {
+                const logit4 v = *reinterpret_cast<const logit4*>(base + (size_t)p * C);
+                const int qh = p / side, qw = p - qh * side;
+                const AccT px = (AccT)opaque_copy((float)qw * sso), py = (AccT)opaque_copy((float)qh * sso);      // the ROUNDED coordinates of the first pass: no fma into dx
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const AccT ex = acc_exp<AccT>((AccT)v[e] - mo[e]);
+                    const AccT dx = px - mux[e], dy = py - muy[e];
+                    cxx[e] += ex * dx * dx; cyy[e] += ex * dy * dy; cxy[e] += ex * dx * dy;
+                }
+            }
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            AccT* r = red + ((size_t)pp * C + q * 4 + e) * 4;
+            AccT* r = red + ((size_t)pp * C + q * 4 + e) * RS;
             r[0] = m[e]; r[1] = s[e]; r[2] = sx[e]; r[3] = sy[e];
+            if constexpr (MOMENTS) { r[4] = cxx[e]; r[5] = cyy[e]; r[6] = cxy[e]; }
         }
     }
     __syncthreads();
@@ -567,19 +599,33 @@ __global__ __launch_bounds__(SA_NT) void softargmax_partial_kernel(
     for (int c = tid; c < C; c += SA_NT) {               // C > 256 for the 53-joint head
         AccT M = (AccT)-INFINITY;
         for (int l = 0; l < ppb; ++l) {
-            const AccT mv = red[((size_t)l * C + c) * 4];
+            const AccT mv = red[((size_t)l * C + c) * RS];
             M = mv > M ? mv : M;
         }
         AccT S = 0, SX = 0, SY = 0;
         for (int l = 0; l < ppb; ++l) {
-            const AccT* r = red + ((size_t)l * C + c) * 4;
+            const AccT* r = red + ((size_t)l * C + c) * RS;
             if (r[1] > 0) {
                 const AccT f = acc_exp<AccT>(r[0] - M);
                 S += r[1] * f; SX += r[2] * f; SY += r[3] * f;
             } else if (r[1] != r[1]) S = r[1];           // a NaN sum must reach the finalize launch's non-finite screen
         }
-        AccT* r0 = red + (size_t)c * 4;                  // lane 0's record of this channel: read above by this thread only
+        AccT XX = 0, YY = 0, XY = 0;
+        if constexpr (MOMENTS) {
+            const AccT So = opaque_copy(S), Mo = opaque_copy(M);
+            const AccT mux = opaque_copy(SX) / So, muy = opaque_copy(SY) / So;
+            for (int l = 0; l < ppb; ++l) {
+                const AccT* r = red + ((size_t)l * C + c) * RS;
+                if (r[1] > 0) {
+                    const AccT f = acc_exp<AccT>(opaque_copy(r[0]) - Mo);
+                    const AccT w = r[1] * f, lx = r[2] / r[1] - mux, ly = r[3] / r[1] - muy;
+                    XX += f * r[4] + w * lx * lx; YY += f * r[5] + w * ly * ly; XY += f * r[6] + w * lx * ly;
+                }
+            }
+        }
+        AccT* r0 = red + (size_t)c * RS;                 // lane 0's record of this channel: read above by this thread only
         r0[0] = M; r0[1] = S; r0[2] = SX; r0[3] = SY;
+        if constexpr (MOMENTS) { r0[4] = XX; r0[5] = YY; r0[6] = XY; }
     }
     __syncthreads();
     // stage 2: one thread per joint folds its `depth` channels (c = d * nj + j, volumetric.py:231)
@@ -588,12 +634,12 @@ __global__ __launch_bounds__(SA_NT) void softargmax_partial_kernel(
         const float step_d = 1.0f / (float)(depth - 1);
         AccT M = (AccT)-INFINITY;
         for (int d = 0; d < depth; ++d) {
-            const AccT mv = red[(size_t)(d * nj + j) * 4];
+            const AccT mv = red[(size_t)(d * nj + j) * RS];
             M = mv > M ? mv : M;
         }
         AccT S = 0, SX = 0, SY = 0, SZ = 0;
         for (int d = 0; d < depth; ++d) {
-            const AccT* r = red + (size_t)(d * nj + j) * 4;
+            const AccT* r = red + (size_t)(d * nj + j) * RS;
             if (r[1] > 0) {
                 const AccT f = acc_exp<AccT>(r[0] - M);
                 const AccT cz = (AccT)((float)d * step_d);
@@ -602,6 +648,25 @@ __global__ __launch_bounds__(SA_NT) void softargmax_partial_kernel(
         }
         AccT* o = partials + (((size_t)img * slabs + slab) * nj + j) * 5;
         o[0] = M; o[1] = S; o[2] = SX; o[3] = SY; o[4] = SZ;
+        if constexpr (MOMENTS) {
+            const AccT So = opaque_copy(S), Mo = opaque_copy(M);
+            const AccT mux = opaque_copy(SX) / So, muy = opaque_copy(SY) / So, muz = opaque_copy(SZ) / So;
+            const float sdo = opaque_copy(step_d);
+            AccT c[6] = {0, 0, 0, 0, 0, 0};
+            for (int d = 0; d < depth; ++d) {
+                const AccT* r = red + (size_t)(d * nj + j) * RS;
+                if (r[1] > 0) {
+                    const AccT f = acc_exp<AccT>(opaque_copy(r[0]) - Mo);
+                    const AccT w = r[1] * f, lx = r[2] / r[1] - mux, ly = r[3] / r[1] - muy;
+                    const AccT lz = (AccT)opaque_copy((float)d * sdo) - muz;
+                    c[0] += f * r[4] + w * lx * lx; c[1] += f * r[5] + w * ly * ly; c[2] += w * lz * lz;
+                    c[3] += f * r[6] + w * lx * ly; c[4] += w * lx * lz; c[5] += w * ly * lz;
+                }
+            }
+            AccT* om = moments + (((size_t)img * slabs + slab) * nj + j) * 6;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) om[k] = c[k];
+        }
     }
 }
 
@@ -615,12 +680,18 @@ __device__ __forceinline__ AccT sa_wave_sum(AccT v) {
     return v;
 }
 
-template <typename AccT>
+// MOMENTS: also folds the records' second central moments (`moments` [n][slabs][J][6], each about its record's own mean
+// mu_i = (SX_i, SY_i, SZ_i) / S_i) with the parallel-axis update, scaled by exp(m_i - M) as the sums are:
+//   Cov01 = sum_i f_i (C_i + S_i (mu_i - mu)(mu_i - mu)^T) / S,   mu = the coords01 of the joint,
+// into cov01 fp32 [n][J][6] (xx, yy, zz, xy, xz, yz; head order) and peak [n][J] = max p = exp(M - M) / S = 1 / S.
+template <typename AccT, bool MOMENTS>
 __global__ __launch_bounds__(1024) void softargmax_finalize_kernel(const AccT* __restrict__ partials,
                                                                   float* __restrict__ poses,
                                                                   SoftArgmaxArgs a, int slabs,
                                                                   float* __restrict__ coords01,
-                                                                  int32_t* __restrict__ status) {
+                                                                  int32_t* __restrict__ status,
+                                                                  const AccT* __restrict__ moments,
+                                                                  float* __restrict__ cov01, float* __restrict__ peak) {
     __shared__ AccT mm[METRO_MAX_JOINTS][3];
     // Non-finite screen (status[img] = 1): a record whose sum is NaN, a non-finite maximum or normaliser.  fp16 storage overflows
     // at 65 504: an Inf in the residual stream reaches every logit of its pixel (reference tfu.py:426-440 keeps fp32 variables
@@ -664,6 +735,26 @@ __global__ __launch_bounds__(1024) void softargmax_finalize_kernel(const AccT* _
             mm[j][0] = (x01 * (AccT)a.lrc + (AccT)a.half_off) * (AccT)a.box_size_mm / (AccT)a.proc_side;
             mm[j][1] = (y01 * (AccT)a.lrc + (AccT)a.half_off) * (AccT)a.box_size_mm / (AccT)a.proc_side;
             mm[j][2] = z01 * (AccT)a.box_size_mm;
+            if constexpr (MOMENTS) {
+                const AccT Mo = opaque_copy(M), So = opaque_copy(S);
+                const AccT xo = opaque_copy(x01), yo = opaque_copy(y01), zo = opaque_copy(z01);
+                AccT c[6] = {0, 0, 0, 0, 0, 0};
+                for (int sl = 0; sl < slabs; ++sl) {
+                    const AccT* r = partials + (((size_t)img * slabs + sl) * nj + j) * 5;
+                    const AccT* q = moments + (((size_t)img * slabs + sl) * nj + j) * 6;
+                    const AccT r0 = opaque_copy(r[0]), r1 = opaque_copy(r[1]), r2 = opaque_copy(r[2]), r3 = opaque_copy(r[3]), r4 = opaque_copy(r[4]);
+                    if (r1 > 0) {
+                        const AccT f = acc_exp<AccT>(r0 - Mo);
+                        const AccT w = r1 * f, lx = r2 / r1 - xo, ly = r3 / r1 - yo, lz = r4 / r1 - zo;
+                        c[0] += f * q[0] + w * lx * lx; c[1] += f * q[1] + w * ly * ly; c[2] += f * q[2] + w * lz * lz;
+                        c[3] += f * q[3] + w * lx * ly; c[4] += f * q[4] + w * lx * lz; c[5] += f * q[5] + w * ly * lz;
+                    }
+                }
+                float* co = cov01 + ((size_t)img * nj + j) * 6;
+#pragma unroll
+                for (int k = 0; k < 6; ++k) co[k] = (float)(c[k] / So);
+                peak[(size_t)img * nj + j] = (float)((AccT)1 / So);
+            }
         }
     } else
     for (int j = wave; j < nj; j += (int)(blockDim.x >> 6)) {      // many records per joint: a wave per joint (16 waves: one or two rounds)
@@ -700,6 +791,30 @@ __global__ __launch_bounds__(1024) void softargmax_finalize_kernel(const AccT* _
             mm[j][1] = (y01 * (AccT)a.lrc + (AccT)a.half_off) * (AccT)a.box_size_mm / (AccT)a.proc_side;
             mm[j][2] = z01 * (AccT)a.box_size_mm;
         }
+        if constexpr (MOMENTS) {
+            const AccT So = opaque_copy(S), Mo = opaque_copy(M);      // every lane holds the folded sums
+            const AccT x01 = opaque_copy(SX) / So, y01 = opaque_copy(SY) / So, z01 = opaque_copy(SZ) / So;
+            AccT c[6] = {0, 0, 0, 0, 0, 0};
+            for (int sl = lane; sl < slabs; sl += 64) {
+                const AccT* r = partials + (((size_t)img * slabs + sl) * nj + j) * 5;
+                const AccT* q = moments + (((size_t)img * slabs + sl) * nj + j) * 6;
+                const AccT r0 = opaque_copy(r[0]), r1 = opaque_copy(r[1]), r2 = opaque_copy(r[2]), r3 = opaque_copy(r[3]), r4 = opaque_copy(r[4]);
+                if (r1 > 0) {
+                    const AccT f = acc_exp<AccT>(r0 - Mo);
+                    const AccT w = r1 * f, lx = r2 / r1 - x01, ly = r3 / r1 - y01, lz = r4 / r1 - z01;
+                    c[0] += f * q[0] + w * lx * lx; c[1] += f * q[1] + w * ly * ly; c[2] += f * q[2] + w * lz * lz;
+                    c[3] += f * q[3] + w * lx * ly; c[4] += f * q[4] + w * lx * lz; c[5] += f * q[5] + w * ly * lz;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 6; ++k) c[k] = sa_wave_sum(c[k]);
+            if (lane == 0) {
+                float* co = cov01 + ((size_t)img * nj + j) * 6;
+#pragma unroll
+                for (int k = 0; k < 6; ++k) co[k] = (float)(c[k] / So);
+                peak[(size_t)img * nj + j] = (float)((AccT)1 / So);
+            }
+        }
     }
     if (bad) atomicOr(&s_bad, 1);
     __syncthreads();
@@ -729,48 +844,69 @@ SoftArgmaxArgs make_softargmax_args(const MetroSpec& spec, int n) {
     return a;
 }
 
-template <typename AccT, typename LogitT>
+int64_t moments_scratch_bytes(int n, int side, int n_joints_head) {
+    // one record of six sums per (image, 32-pixel slab, joint): the most any head or soft-argmax launch writes, as fp64
+    const int slabs = side * side / 32 > 0 ? side * side / 32 : 1;
+    return (int64_t)n * slabs * n_joints_head * 6 * (int64_t)sizeof(double);
+}
+
+template <typename AccT, typename LogitT, bool MOMENTS>
 static int launch_softargmax_t(const void* logits, const SoftArgmaxArgs& a, void* partials,
-                               float* poses, float* coords01, hipStream_t stream, int32_t* status) {
+                               float* poses, float* coords01, hipStream_t stream, int32_t* status, const MomentsOut& mo) {
     const int C = a.depth * a.n_joints_head;
     const int quads = C / 4;
     const int ppb = SA_NT / quads;
     const int slabs = softargmax_slabs(a.n, a.side);
-    const size_t lds = (size_t)ppb * C * 4 * sizeof(AccT);
-    if (note_kernel("softargmax_partial<acc%d,logits%d> & softargmax_finalize<acc%d>", (int)sizeof(AccT) * 8, (int)sizeof(LogitT) * 8,
-                    (int)sizeof(AccT) * 8))
+    const size_t lds = (size_t)ppb * C * (MOMENTS ? 7 : 4) * sizeof(AccT);
+    if (note_kernel(MOMENTS ? "softargmax_partial<acc%d,logits%d,moments> & softargmax_finalize<acc%d,moments>"
+                            : "softargmax_partial<acc%d,logits%d> & softargmax_finalize<acc%d>", (int)sizeof(AccT) * 8,
+                    (int)sizeof(LogitT) * 8, (int)sizeof(AccT) * 8))
         return METRO_OK;
-    auto kern = softargmax_partial_kernel<AccT, LogitT>;
+    auto kern = softargmax_partial_kernel<AccT, LogitT, MOMENTS>;
     if (lds > 64 * 1024) {
         static PerDeviceInt attr_done;
         if (const int st = ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done, "softargmax_partial")) return st;
     }
     hipLaunchKernelGGL(kern, dim3(slabs, a.n), dim3(SA_NT), lds, stream, static_cast<const LogitT*>(logits),
-                       static_cast<AccT*>(partials), a.side, a.depth, a.n_joints_head, slabs);
+                       static_cast<AccT*>(partials), a.side, a.depth, a.n_joints_head, slabs, static_cast<AccT*>(mo.scratch));
     int st = launch_status("softargmax_partial");
     if (st) return st;
-    hipLaunchKernelGGL(softargmax_finalize_kernel<AccT>, dim3(a.n), dim3(slabs > 16 ? 1024 : 256), 0, stream,
-                       static_cast<const AccT*>(partials), poses, a, slabs, coords01, status);
+    hipLaunchKernelGGL((softargmax_finalize_kernel<AccT, MOMENTS>), dim3(a.n), dim3(slabs > 16 ? 1024 : 256), 0, stream,
+                       static_cast<const AccT*>(partials), poses, a, slabs, coords01, status,
+                       static_cast<const AccT*>(mo.scratch), mo.cov01, mo.peak);
     return launch_status("softargmax_finalize");
 }
 
 int launch_softargmax_finalize(const float* partials, const SoftArgmaxArgs& a, int slabs, float* poses_out,
-                               hipStream_t stream, float* coords01_out, int32_t* status) {
+                               hipStream_t stream, float* coords01_out, int32_t* status, const MomentsOut& mo) {
+    if (mo.scratch != nullptr) {
+        if (note_kernel("softargmax_finalize<acc32,moments>")) return METRO_OK;
+        hipLaunchKernelGGL((softargmax_finalize_kernel<float, true>), dim3(a.n), dim3(slabs > 16 ? 1024 : 256), 0, stream, partials,
+                           poses_out, a, slabs, coords01_out, status, static_cast<const float*>(mo.scratch), mo.cov01, mo.peak);
+        return launch_status("softargmax_finalize");
+    }
     if (note_kernel("softargmax_finalize<acc32>")) return METRO_OK;
-    hipLaunchKernelGGL(softargmax_finalize_kernel<float>, dim3(a.n), dim3(slabs > 16 ? 1024 : 256), 0, stream, partials, poses_out, a, slabs, coords01_out, status);
+    hipLaunchKernelGGL((softargmax_finalize_kernel<float, false>), dim3(a.n), dim3(slabs > 16 ? 1024 : 256), 0, stream, partials,
+                       poses_out, a, slabs, coords01_out, status, nullptr, nullptr, nullptr);
     return launch_status("softargmax_finalize");
 }
 
 int launch_softargmax(const void* logits, const SoftArgmaxArgs& a, int precise, void* partials,
-                      float* poses_out, hipStream_t stream, float* coords01_out, int32_t* status) {
+                      float* poses_out, hipStream_t stream, float* coords01_out, int32_t* status, const MomentsOut& mo) {
     const int C = a.depth * a.n_joints_head;
     if (C % 4 || C / 4 > SA_NT || a.n_joints_head > METRO_MAX_JOINTS || a.n_joints_out > 64) {
         set_error("softargmax: unsupported head (depth %d, joints %d)", a.depth, a.n_joints_head);
         return METRO_ERR_UNSUPPORTED;
     }
-    if (precise == 0) return launch_softargmax_t<float, float>(logits, a, partials, poses_out, coords01_out, stream, status);
-    if (precise == 1) return launch_softargmax_t<double, float>(logits, a, partials, poses_out, coords01_out, stream, status);
-    if (precise == 2) return launch_softargmax_t<double, double>(logits, a, partials, poses_out, coords01_out, stream, status);
+    if (mo.scratch != nullptr) {
+        if (precise == 0) return launch_softargmax_t<float, float, true>(logits, a, partials, poses_out, coords01_out, stream, status, mo);
+        if (precise == 1) return launch_softargmax_t<double, float, true>(logits, a, partials, poses_out, coords01_out, stream, status, mo);
+        if (precise == 2) return launch_softargmax_t<double, double, true>(logits, a, partials, poses_out, coords01_out, stream, status, mo);
+    } else {
+        if (precise == 0) return launch_softargmax_t<float, float, false>(logits, a, partials, poses_out, coords01_out, stream, status, mo);
+        if (precise == 1) return launch_softargmax_t<double, float, false>(logits, a, partials, poses_out, coords01_out, stream, status, mo);
+        if (precise == 2) return launch_softargmax_t<double, double, false>(logits, a, partials, poses_out, coords01_out, stream, status, mo);
+    }
     set_error("softargmax: precise must be 0, 1 or 2 (got %d)", precise);
     return METRO_ERR_INVALID_ARG;
 }

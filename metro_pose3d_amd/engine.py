@@ -87,6 +87,7 @@ class Engine:
         self._blob = None
         self._ws = None
         self._u8_f32 = None
+        self._moments = None
         if params is not None:
             if device is None:
                 if not torch.cuda.is_available():
@@ -187,19 +188,43 @@ class Engine:
         return out
 
     def forward(self, images: torch.Tensor, out: Optional[torch.Tensor] = None,
-                coords01: Optional[torch.Tensor] = None) -> torch.Tensor:
+                coords01: Optional[torch.Tensor] = None, cov01: Optional[torch.Tensor] = None,
+                peak: Optional[torch.Tensor] = None) -> torch.Tensor:
         """images fp32 [n,256,256,3] on the plan's device -> poses fp32 [n,Jout,3] (mm).  Enqueued
         on torch's current stream; no synchronisation.  `coords01`: an fp32 [n, J_head, 3] device tensor that also receives
         the soft-argmax coordinates in [0,1] (head order; metro_forward_coords01: the same poses, from the same launches).
         uint8 images (byte b = the fp32 value b / 255) give the bits of the fp32 call on those values: precision 'f16' reads
-        the bytes in its first kernel (metro_forward_u8), the others expand them once (metro_images_u8_to_f32)."""
+        the bytes in its first kernel (metro_forward_u8), the others expand them once (metro_images_u8_to_f32).
+        `cov01` / `peak` (together): fp32 [n, J_head, 6] and [n, J_head] device tensors that receive every joint's heat-map
+        covariance (xx, yy, zz, xy, xz, yz in the units of coords01) and peak probability, head order -- the spread of the
+        joint's own softmax distribution in the crop's virtual-camera axes, not of the root-relative pose
+        (metro_forward_moments: the same launch count, the same poses and coords01).  With both None the call goes to the
+        entries it always went to."""
         images = self._check_images(images)
         n = images.shape[0]
+        if (cov01 is None) != (peak is None):
+            raise ValueError('cov01 and peak go together: pass both or neither')
+        if cov01 is not None:
+            self._check_out('cov01', cov01, (n, self.spec.skeleton.n_head, 6))
+            self._check_out('peak', peak, (n, self.spec.skeleton.n_head))
         if out is None:
             out = torch.empty((n, self.spec.skeleton.n_out, 3), dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         if coords01 is not None:
             self._check_coords01(coords01, n)
+        if cov01 is not None:
+            u8 = images.dtype == torch.uint8 and self.precision == 'f16'
+            if images.dtype == torch.uint8 and not u8:
+                images = self._as_float32(images)
+            if self._moments is None:
+                nb = int(self.lib.metro_moments_scratch_bytes(C.byref(self.cspec), self.max_batch))
+                self._moments = torch.empty(nb, dtype=torch.uint8, device=self.device)
+            check(self.lib.metro_forward_moments(self._plan, C.c_void_p(images.data_ptr()), int(u8), n, C.c_void_p(out.data_ptr()),
+                                                 C.c_void_p(coords01.data_ptr() if coords01 is not None else 0),
+                                                 C.c_void_p(cov01.data_ptr()), C.c_void_p(peak.data_ptr()),
+                                                 C.c_void_p(self._moments.data_ptr()), C.c_void_p(self._ws.data_ptr()),
+                                                 C.c_void_p(stream)), 'metro_forward_moments')
+            return out
         if images.dtype == torch.uint8:
             if self.precision == 'f16':
                 check(self.lib.metro_forward_u8(self._plan, C.c_void_p(images.data_ptr()), n, C.c_void_p(out.data_ptr()),
@@ -223,6 +248,12 @@ class Engine:
                 or coords01.device != self.device or not coords01.is_contiguous()):
             raise ValueError(f'coords01 must be a contiguous float32 {list(shape)} tensor on {self.device}, got '
                              f'{getattr(coords01, "dtype", type(coords01))} {tuple(getattr(coords01, "shape", ()))}')
+
+    def _check_out(self, name: str, t, shape) -> None:
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape)
+                or t.device != self.device or not t.is_contiguous()):
+            raise ValueError(f'{name} must be a contiguous float32 {list(shape)} tensor on {self.device}, got '
+                             f'{getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))}')
 
     def check_finite(self, n: int) -> None:
         """Non-finite screen of the last forward(n) on this engine: raises _lib.NonFiniteError when activations overflowed

@@ -666,8 +666,13 @@ def _call_device(boxes, frames) -> torch.device:
 def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index=None, coords: str = 'camera',
                             precision: Optional[str] = None, check_finite: Optional[bool] = None, views=None,
                             geometry: str = 'auto', pixel_format: str = 'rgb', color_matrix: str = 'bt601',
-                            crop_dtype: str = 'float32'):
+                            crop_dtype: str = 'float32', return_uncertainty: bool = False):
     """uint8 frames + person boxes [n, 4] (x, y, w, h) -> (poses [n, Jout, 3] mm, joint_edges, joint_names) like estimate_pose.
+
+    return_uncertainty=True adds a fourth element, inference.PoseUncertainty(covariance [n, Jout, 3, 3] mm^2, peak [n, Jout]):
+    the covariance of each joint's own heat-map (estimate_pose), rotated into `coords` as R Cov R^T with the crop's
+    rot_to_orig_cam / rot_to_world (mirror joints swapped where det R <= 0, as for the poses) and averaged over the views,
+    as are the peaks (one metro_place_covariances launch).  It stays in MeTRo's metric scale.
 
     frames: a uint8 [H, W, 3] tensor / array or a list of them (host or device, sizes may differ, at most 64), or frames in
     `pixel_format` (below);
@@ -705,21 +710,34 @@ def estimate_pose_in_frames(frames, boxes, model_path, cameras=None, frame_index
     precisions expand it first): the same poses bit for bit."""
     call = _checked_call(frames, boxes, frame_index, coords, views, geometry, precision, check_finite, pixel_format,
                          color_matrix, crop_dtype)
-    return _estimate_pose_views(call, model_path, cameras, coords)
+    res = _estimate_pose_views(call, model_path, cameras, coords, return_uncertainty)
+    return res if return_uncertainty else res[:3]
 
 
-def _estimate_pose_views(call: _Call, model_path, cameras, coords):
-    from metro_pose3d_amd.inference import _engine_for, estimate_pose
+def _place_covariances(spec, cov01, peak, places, coords: str, n: int, nv: int):
+    """One metro_place_covariances launch -> inference.PoseUncertainty of the n boxes (empty without a launch for n = 0)."""
+    from metro_pose3d_amd.heads import place_covariances
+    from metro_pose3d_amd.inference import PoseUncertainty
+    if n == 0:
+        n_out = spec.skeleton.n_out
+        return PoseUncertainty(peak.new_empty((0, n_out, 3, 3)), peak.new_empty((0, n_out)))
+    return PoseUncertainty(*place_covariances(cov01, peak, spec, coords, places.reshape(-1) if coords != 'crop' else None, nv))
+
+
+def _estimate_pose_views(call: _Call, model_path, cameras, coords, uncertainty: bool = False):
+    """-> (poses, joint_edges, joint_names, PoseUncertainty or None)."""
+    from metro_pose3d_amd.inference import _engine_for, _estimate_pose
     n, nv = len(call.boxes), len(call.vs.zoom)
     device = _call_device(call.boxes, call.frames)
     with torch.cuda.device(device):
         spec = _engine_for(model_path, call.precision, device, max(n * nv, 1)).spec
         crops, places = _warp_views(call.frames, cameras, call.boxes, call.fi, call.vs, spec.proc_side, device, call.crop_dtype)
-        poses, edges, names = estimate_pose(crops, model_path, precision=call.precision, check_finite=call.check_finite,
-                                            shard=False)
+        poses, edges, names, mom = _estimate_pose(crops, model_path, call.precision, call.check_finite, False, None,
+                                                  'head' if uncertainty else None)
         _synchronise(None, call.boxes)         # after estimate_pose's synchronisation (its finite screen), or the call's one
+        unc = _place_covariances(spec, mom[0], mom[1], places, coords, n, nv) if uncertainty else None
         if coords == 'crop' or n == 0:         # one view (_checked_call)
-            return poses, edges, names
+            return poses, edges, names, unc
         sk = spec.skeleton
         at = _ROT_TO_ORIG_CAM if coords == 'camera' else _ROT_TO_WORLD
         rot = places.view(torch.float32)[:, at:at + 9].contiguous()
@@ -730,7 +748,7 @@ def _estimate_pose_views(call: _Call, model_path, cameras, coords):
                                             C.c_void_p(mirror.data_ptr()), C.c_void_p(placed.data_ptr()), n * nv, sk.n_out,
                                             C.c_void_p(stream)), 'metro_to_orig_cam')
         out = _merge_views(placed, None, None, places, mirror, n, nv, spread=False)[0]
-    return out, edges, names
+    return out, edges, names, unc
 
 
 class FramePoses(NamedTuple):
@@ -740,6 +758,8 @@ class FramePoses(NamedTuple):
     z_offset: Optional[torch.Tensor]     # float32 [n] mm (absolute modes: the root's depth in the virtual camera), else None
     joint_edges: np.ndarray
     joint_names: np.ndarray
+    covariance: Optional[torch.Tensor] = None   # return_uncertainty: float32 [n, Jout, 3, 3] mm^2 in the requested coords, else None
+    peak: Optional[torch.Tensor] = None         # return_uncertainty: float32 [n, Jout] largest heat-map probability, else None
 
 
 SCALE_RECOVERY = {'metro': _lib.METRO_SCALE_METRO, 'bone-lengths': _lib.METRO_SCALE_BONE_LENGTHS,
@@ -817,7 +837,7 @@ def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=
                            bone_lengths=None, root_depth=None, coords: str = 'camera', precision: Optional[str] = None,
                            check_finite: Optional[bool] = None, views=None, return_spread: bool = False,
                            geometry: str = 'auto', pixel_format: str = 'rgb', color_matrix: str = 'bt601',
-                           crop_dtype: str = 'float32'):
+                           crop_dtype: str = 'float32', return_uncertainty: bool = False):
     """uint8 frames + person boxes -> FramePoses(poses, keypoints2d, z_offset, joint_edges, joint_names): where each person is
     in 3D and where each joint lands in its frame's pixels.  frames, boxes, frame_index, cameras, precision and check_finite as
     for estimate_pose_in_frames.
@@ -850,35 +870,47 @@ def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=
     synchronisation.
     pixel_format, color_matrix: as for estimate_pose_in_frames ('bgr', 'nv12', 'i420' frames converted per tap in the warp,
     OpenCV's integer YUV rule, black border); crop_dtype 'float32' | 'uint8' likewise (the same bits from a quarter of the
-    crop bytes)."""
+    crop bytes).
+    return_uncertainty=True fills FramePoses.covariance [n, Jout, 3, 3] (mm^2) and .peak [n, Jout] (None otherwise): the
+    covariance of each joint's own heat-map (its softmax over the S x S x D volume; estimate_pose) in the requested coords --
+    R Cov R^T per view, mirror joints swapped where det R <= 0, views averaged; one metro_place_covariances launch -- and the
+    heat-map's largest probability.  The covariance stays in MeTRo's metric scale (the linear part of heatmap_to_metric) under
+    every scale_recovery: bone lengths and root depths move and rescale the pose, they are not applied to it."""
     call = _checked_call(frames, boxes, frame_index, coords, views, geometry, precision, check_finite, pixel_format,
                          color_matrix, crop_dtype)
     sk = _model_skeleton(model_path)
     targets, per_pose, root_z = _placement_targets(scale_recovery, cameras, len(call.boxes), len(sk.head_edges), bone_lengths,
                                                    root_depth)
-    res = _locate_poses_views(call, model_path, cameras, scale_recovery, targets, per_pose, root_z, coords, sk)
+    res = _locate_poses_views(call, model_path, cameras, scale_recovery, targets, per_pose, root_z, coords, sk, return_uncertainty)
     return res if return_spread else res[0]
 
 
-def _forward_coords01(eng, crops: torch.Tensor, check_finite: bool):
+def _forward_coords01(eng, crops: torch.Tensor, check_finite: bool, moments: bool = False):
     """metro_forward_coords01 in chunks of the engine's batch -> (root-relative poses [m, Jout, 3], coords01 [m, Jhead, 3],
     the number of crops with non-finite statistics as a device scalar, or None without check_finite: folded on the device
-    after every chunk, read by the caller's one synchronisation)."""
+    after every chunk, read by the caller's one synchronisation); `moments`: a fourth element (cov01 [m, Jhead, 6], peak
+    [m, Jhead]) from the same launches."""
     sk = eng.spec.skeleton
     m = len(crops)
     rel = torch.empty((m, sk.n_out, 3), dtype=torch.float32, device=crops.device)
     coords01 = torch.empty((m, sk.n_head, 3), dtype=torch.float32, device=crops.device)
+    cov01 = torch.empty((m, sk.n_head, 6), dtype=torch.float32, device=crops.device) if moments else None
+    peak = torch.empty((m, sk.n_head), dtype=torch.float32, device=crops.device) if moments else None
     bad = None
     for i in range(0, m, eng.max_batch):
         k = min(eng.max_batch, m - i)
-        eng.forward(crops[i:i + k], out=rel[i:i + k], coords01=coords01[i:i + k])
+        if moments:
+            eng.forward(crops[i:i + k], out=rel[i:i + k], coords01=coords01[i:i + k], cov01=cov01[i:i + k], peak=peak[i:i + k])
+        else:
+            eng.forward(crops[i:i + k], out=rel[i:i + k], coords01=coords01[i:i + k])
         if check_finite:
             cnt = eng.status_words(k).ne(0).sum()
             bad = cnt if bad is None else bad + cnt
-    return rel, coords01, bad
+    return (rel, coords01, bad, (cov01, peak)) if moments else (rel, coords01, bad)
 
 
-def _locate_poses_views(call: _Call, model_path, cameras, scale_recovery, targets, per_pose, root_z, coords, sk):
+def _locate_poses_views(call: _Call, model_path, cameras, scale_recovery, targets, per_pose, root_z, coords, sk,
+                        uncertainty: bool = False):
     """-> (FramePoses, spread [n, Jout])."""
     from metro_pose3d_amd.inference import _engine_for
     n, nv = len(call.boxes), len(call.vs.zoom)
@@ -891,10 +923,11 @@ def _locate_poses_views(call: _Call, model_path, cameras, scale_recovery, target
     with torch.cuda.device(device):
         eng = _engine_for(model_path, call.precision, device, max(m, 1))
         if n == 0:
-            return (FramePoses(f32(0, sk.n_out, 3), f32(0, sk.n_out, 2), f32(0) if absolute else None, sk.edges_array(), names),
+            unc = (f32(0, sk.n_out, 3, 3), f32(0, sk.n_out)) if uncertainty else (None, None)
+            return (FramePoses(f32(0, sk.n_out, 3), f32(0, sk.n_out, 2), f32(0) if absolute else None, sk.edges_array(), names, *unc),
                     torch.zeros((0, sk.n_out), dtype=torch.float32, device=device))
         crops, places = _warp_views(call.frames, cameras, call.boxes, call.fi, call.vs, eng.spec.proc_side, device, call.crop_dtype)
-        rel, coords01, bad = _forward_coords01(eng, crops, call.check_finite)
+        rel, coords01, bad, *mom = _forward_coords01(eng, crops, call.check_finite, uncertainty)
         if per_pose:                                    # per-box targets, repeated per view by index (box-major rows)
             targets = np.repeat(targets, nv, axis=0)
         poses_v, keypoints_v, z_v = f32(m, sk.n_out, 3), f32(m, sk.n_out, 2), f32(m) if absolute else None
@@ -909,6 +942,7 @@ def _locate_poses_views(call: _Call, model_path, cameras, scale_recovery, target
                                             ptr(mirror), COORDS[coords], ptr(poses_v), ptr(keypoints_v), ptr(z_v),
                                             C.c_void_p(stream)), 'metro_place_poses')
         poses, keypoints, z_offset, spread = _merge_views(poses_v, keypoints_v, z_v, places, mirror, n, nv, spread=True)
+        unc = tuple(_place_covariances(eng.spec, mom[0][0], mom[0][1], places, coords, n, nv)) if uncertainty else (None, None)
         n_bad = _synchronise(bad, call.boxes)                          # the call's one stream synchronisation
         if n_bad:
             spec = eng.spec
@@ -916,4 +950,4 @@ def _locate_poses_views(call: _Call, model_path, cameras, scale_recovery, target
                 f'{spec.arch_name} stride {spec.stride} in precision {call.precision!r}: {n_bad} of {m} crops reached the '
                 'soft-argmax with non-finite statistics' +
                 (' (fp16 storage overflows at 65504: run this model with precision f32m or f64)' if call.precision == 'f16' else ''))
-    return FramePoses(poses, keypoints, z_offset, sk.edges_array(), names), spread
+    return FramePoses(poses, keypoints, z_offset, sk.edges_array(), names, *unc), spread

@@ -2,6 +2,9 @@
 through the C ABI (csrc/heads.hip).  Names and argument meaning follow the reference:
 
   coords01_from_logits      net_output_to_heatmap_and_coords          src/model/volumetric.py:227-235
+  moments_from_logits       the same + covariance and peak of every joint's softmax volume (the graph's unused by-product
+                            `heatmap_pred_z`, volumetric.py:165, is a marginal of it)
+  place_covariances         Cov01 -> mm^2 in output order and crop / camera / world axes, views averaged
   backproject_bone_lengths  scale_recovery 'bone-lengths' / '-true'   volumetric.py:171-191,
                             optimize_z_offset_by_bones(_tensor)       src/model/bone_length_based_backproj.py:15-62
   backproject_root_depth    scale_recovery 'true-root-depth'          volumetric.py:192-199
@@ -52,6 +55,70 @@ def coords01_from_logits(logits: torch.Tensor, spec: ModelSpec, precise: int = 1
     check(lib.metro_softargmax01(_p(logits), n, C.byref(cs), int(precise), _p(scratch), _p(out), _stream(logits.device)),
           'metro_softargmax01')
     return out
+
+
+def cov6_to_3x3(cov6: torch.Tensor) -> torch.Tensor:
+    """[..., 6] (xx, yy, zz, xy, xz, yz) -> symmetric [..., 3, 3]."""
+    idx = torch.tensor([0, 3, 4, 3, 1, 5, 4, 5, 2], device=cov6.device)
+    return cov6[..., idx].reshape(*cov6.shape[:-1], 3, 3)
+
+
+def moments_from_logits(logits: torch.Tensor, spec: ModelSpec, precise: int = 1):
+    """fp32 (precise 0/1) or fp64 (precise 2) NHWC logits [N,S,S,D*J] -> (coords01 [N,J,3], cov01 [N,J,3,3], peak [N,J]), head
+    order.  Per joint, with p its softmax over the S*S*D voxels and c their linspace(0,1,.) coordinates: coords01 = sum p c,
+    cov01 = sum p (c - coords01)(c - coords01)^T, peak = max p.  The covariance of the joint's OWN heat-map in the crop's
+    virtual-camera axes (units of coords01), not of the root-relative difference."""
+    lib = _lib.load()
+    if logits.dim() != 4 or logits.shape[1] != spec.heatmap_side or logits.shape[3] != spec.n_head_channels:
+        raise ValueError(f'logits must be [N,{spec.heatmap_side},{spec.heatmap_side},{spec.n_head_channels}]')
+    if precise not in (0, 1, 2):
+        raise ValueError(f'precise must be 0, 1 or 2, got {precise!r}')
+    logits = logits.to(torch.float64 if precise == 2 else torch.float32).contiguous()
+    n, nj, dev = logits.shape[0], spec.skeleton.n_head, logits.device
+    cs = spec.to_c(int(precise))
+    scratch = torch.empty(lib.metro_softargmax_scratch_bytes(n, spec.heatmap_side, nj), dtype=torch.uint8, device=dev)
+    mscratch = torch.empty(lib.metro_moments_scratch_bytes(C.byref(cs), n), dtype=torch.uint8, device=dev)
+    c01 = torch.empty((n, nj, 3), dtype=torch.float32, device=dev)
+    cov = torch.empty((n, nj, 6), dtype=torch.float32, device=dev)
+    peak = torch.empty((n, nj), dtype=torch.float32, device=dev)
+    check(lib.metro_softargmax01_moments(_p(logits), n, C.byref(cs), int(precise), _p(scratch), _p(mscratch), _p(c01), _p(cov),
+                                         _p(peak), _stream(dev)), 'metro_softargmax01_moments')
+    return c01, cov6_to_3x3(cov), peak
+
+
+_COORDS = {'crop': _lib.METRO_COORDS_CROP, 'camera': _lib.METRO_COORDS_CAMERA, 'world': _lib.METRO_COORDS_WORLD}
+
+
+def place_covariances(cov01: torch.Tensor, peak: torch.Tensor, spec: ModelSpec, coords: str = 'crop',
+                      records: Optional[torch.Tensor] = None, n_views: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """cov01 [R,J_head,6] + peak [R,J_head] of R = n * n_views crops (box-major rows) -> (covariance [n,Jout,3,3] mm^2,
+    peak [n,Jout]) in output joint order: diag(s) Cov01 diag(s) with s = (lrc box / proc_side, the same, box) -- the linear part
+    of heatmap_to_metric -- then, for coords 'camera' / 'world', R Cov R^T with the rotation of each row's MetroPlacement in
+    `records` (a uint8 device tensor of R records), mirror joints swapped where det R <= 0; the mean over the views."""
+    lib = _lib.load()
+    if coords not in _COORDS:
+        raise ValueError(f"coords must be 'crop', 'camera' or 'world', got {coords!r}")
+    nj = spec.skeleton.n_head
+    if cov01.dim() != 3 or tuple(cov01.shape[1:]) != (nj, 6) or tuple(peak.shape) != tuple(cov01.shape[:2]):
+        raise ValueError(f'cov01 must be [R,{nj},6] and peak [R,{nj}], got {tuple(cov01.shape)} and {tuple(peak.shape)}')
+    n_views = int(n_views)
+    if n_views < 1 or n_views > _lib.METRO_MAX_VIEWS or cov01.shape[0] % n_views:
+        raise ValueError(f'{cov01.shape[0]} rows are not a whole number of boxes of {n_views} views (1 to {_lib.METRO_MAX_VIEWS})')
+    if coords != 'crop':
+        need = cov01.shape[0] * C.sizeof(_lib.MetroPlacement)
+        if records is None or records.dtype != torch.uint8 or records.numel() != need:
+            raise ValueError(f"coords {coords!r} needs `records`: a uint8 tensor of {cov01.shape[0]} MetroPlacement ({need} bytes)")
+    dev = cov01.device
+    cov01 = cov01.to(torch.float32).contiguous()
+    peak = peak.to(torch.float32).contiguous()
+    n = cov01.shape[0] // n_views
+    cs = spec.to_c(1)
+    mirror = torch.from_numpy(np.asarray(spec.skeleton.out_mirror, dtype=np.int32)).to(dev) if coords != 'crop' else None
+    out = torch.empty((n, spec.skeleton.n_out, 9), dtype=torch.float32, device=dev)
+    pk = torch.empty((n, spec.skeleton.n_out), dtype=torch.float32, device=dev)
+    check(lib.metro_place_covariances(_p(cov01), _p(peak), _p(records if coords != 'crop' else None), n, n_views, C.byref(cs),
+                                      _p(mirror), _COORDS[coords], _p(out), _p(pk), _stream(dev)), 'metro_place_covariances')
+    return out.view(n, spec.skeleton.n_out, 3, 3), pk
 
 
 def backproject_bone_lengths(coords01: torch.Tensor, inv_intrinsics, bone_lengths, spec: ModelSpec,

@@ -25,7 +25,7 @@ import argparse
 import contextlib
 import os
 from collections import OrderedDict
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -94,9 +94,23 @@ def _gather_shards(local: torch.Tensor, n_total: int, group, status: int = 0):
     return out.to(local.device), st
 
 
+class PoseUncertainty(NamedTuple):
+    """Per-joint confidence read off the heat-maps (estimate_pose(..., return_uncertainty=True)), output joint order."""
+    covariance: torch.Tensor     # float32 [n, Jout, 3, 3] mm^2: covariance of each joint's softmax volume
+    peak: torch.Tensor           # float32 [n, Jout]: its largest voxel probability, in (0, 1]
+
+
 def estimate_pose(images_tensor, model_path, precision: Optional[str] = None, check_finite: Optional[bool] = None,
-                  shard: Optional[bool] = None, group=None):
+                  shard: Optional[bool] = None, group=None, return_uncertainty: bool = False):
     """images [N,256,256,3] float32 in [0,1] -> (poses [N,Jout,3] mm, joint_edges, joint_names).
+
+    return_uncertainty=True adds a fourth element, PoseUncertainty(covariance [N,Jout,3,3] mm^2, peak [N,Jout]): every joint's
+    output is a softmax distribution over its S x S x D volume and the pose is only its mean; the covariance is that
+    distribution's spread (large for an occluded or out-of-crop joint, small for a well-seen one) and peak its largest
+    probability.  It is the covariance of the joint's OWN heat-map in the crop's virtual-camera axes, scaled to mm by the linear
+    part of heatmap_to_metric -- not the covariance of the root-relative difference the poses are.  Computed by the same
+    launches as the poses (metro_forward_moments: the logits never reach HBM), which stay bit for bit those of the plain
+    call; sharded calls gather it with the poses in the same collective.
 
     uint8 images (RGB bytes, as a JPEG decoder or the crop warp leaves them) are accepted as they are: byte b stands for the
     float32 value b / 255 (normalize01, reference improc.py:56-61) and the result has the bits of the float32 call on those
@@ -124,6 +138,15 @@ def estimate_pose(images_tensor, model_path, precision: Optional[str] = None, ch
     row per rank), so an overflow or an exception on one rank raises on every rank instead of leaving the others blocked in
     the collective.  The screen reads the words of the immediately preceding forward on the engine's workspace and stream: one
     caller per cached engine at a time (an Engine is not thread-safe, like the C plan it wraps)."""
+    res = _estimate_pose(images_tensor, model_path, precision, check_finite, shard, group,
+                         'placed' if return_uncertainty else None)
+    return res if return_uncertainty else res[:3]
+
+
+def _estimate_pose(images_tensor, model_path, precision, check_finite, shard, group, uncertainty):
+    """estimate_pose's body -> (poses, joint_edges, joint_names, uncertainty): None, PoseUncertainty ('placed'), or, for the
+    frames chain, which rotates and averages them itself, the forward's own (cov01 [N,J_head,6], peak [N,J_head]) ('head':
+    local calls only)."""
     if precision is None:
         precision = os.environ.get('METRO_PRECISION', 'f16')
     if check_finite is None:
@@ -154,6 +177,8 @@ def estimate_pose(images_tensor, model_path, precision: Optional[str] = None, ch
     # collective), a wrong image shape (ValueError on every rank alike), or a sticky HIP error after which no device tensor can
     # be allocated under backend `nccl` (the process group's own timeout ends the other ranks).
     status, err, eng, poses, n_out = 0, None, None, None, None
+    cov01 = peak = None
+    width = 13 if uncertainty == 'placed' else 3          # gathered row: pose (3) + covariance (9) + peak (1)
     with (torch.cuda.device(device) if device.type == 'cuda' else contextlib.nullcontext()):
         try:
             eng = _engine_for(model_path, precision, device, max(end - begin, 1))
@@ -164,13 +189,26 @@ def estimate_pose(images_tensor, model_path, precision: Optional[str] = None, ch
                                   f'{tuple(images_tensor.shape)}')
             images = images_tensor[begin:end].to(device, non_blocking=True).contiguous()      # only this rank's shard goes to its GPU
             poses = torch.empty((end - begin, n_out, 3), dtype=torch.float32, device=device)
+            if uncertainty:
+                cov01 = torch.empty((end - begin, eng.spec.skeleton.n_head, 6), dtype=torch.float32, device=device)
+                peak = torch.empty((end - begin, eng.spec.skeleton.n_head), dtype=torch.float32, device=device)
             bad = None
             for i in range(0, end - begin, eng.max_batch):
                 k = min(eng.max_batch, end - begin - i)
-                eng.forward(images[i:i + k], out=poses[i:i + k])
+                if uncertainty:
+                    eng.forward(images[i:i + k], out=poses[i:i + k], cov01=cov01[i:i + k], peak=peak[i:i + k])
+                else:
+                    eng.forward(images[i:i + k], out=poses[i:i + k])
                 if check_finite:       # folded on the device after every chunk: ONE synchronisation per call, below
                     cnt = eng.status_words(k).ne(0).sum()
                     bad = cnt if bad is None else bad + cnt
+            if uncertainty == 'placed':
+                from metro_pose3d_amd.heads import place_covariances
+                if end > begin:
+                    cov, pk = place_covariances(cov01, peak, eng.spec)
+                else:
+                    cov, pk = poses.new_empty((0, n_out, 3, 3)), poses.new_empty((0, n_out))
+                poses = torch.cat([poses, cov.reshape(-1, n_out, 9), pk[..., None]], dim=2)
             if bad is not None:
                 status = int(bad.item())                                 # the call's one stream synchronisation
         except _ShapeError:
@@ -184,7 +222,7 @@ def estimate_pose(images_tensor, model_path, precision: Optional[str] = None, ch
                     if n_out is None:
                         n_out = load_model(model_path)[0].skeleton.n_out       # raises if the file is unreadable (every rank alike)
                     on_host = torch.distributed.get_backend(group) != 'nccl'
-                    poses = torch.zeros((end - begin, n_out, 3), dtype=torch.float32, device='cpu' if on_host else device)
+                    poses = torch.zeros((end - begin, n_out, width), dtype=torch.float32, device='cpu' if on_host else device)
                 poses, statuses = _gather_shards(poses, n, group, status)
             except Exception:
                 if err is not None:
@@ -204,7 +242,13 @@ def estimate_pose(images_tensor, model_path, precision: Optional[str] = None, ch
     sk = eng.spec.skeleton
     names = np.empty(sk.n_out, dtype=object)
     names[:] = sk.names_bytes()
-    return poses, sk.edges_array(), names
+    unc = None
+    if uncertainty == 'placed':
+        unc = PoseUncertainty(poses[..., 3:12].reshape(-1, sk.n_out, 3, 3).contiguous(), poses[..., 12].contiguous())
+        poses = poses[..., :3].contiguous()
+    elif uncertainty == 'head':
+        unc = (cov01, peak)
+    return poses, sk.edges_array(), names, unc
 
 
 def visualize_pose(image, coords, edges):
@@ -262,6 +306,9 @@ def main(argv=None):
     parser.add_argument('--crop-dtype', type=str, default=None, choices=['float32', 'uint8'],
                         help="dtype of the crops the warp cuts from --frame: 'float32' (default) or 'uint8' (the remapped bytes, "
                              'read by the network as they are: the same poses from a quarter of the crop bytes)')
+    parser.add_argument('--uncertainty', action='store_true',
+                        help='also print, per joint, the standard deviations in mm of its heat-map along the three axes and its '
+                             'peak probability')
     opts = parser.parse_args(argv)
     if opts.frame:
         return _main_frame(opts)
@@ -277,12 +324,21 @@ def main(argv=None):
         from metro_pose3d_amd.synth import make_images
         img = make_images(1)[0]
     images = torch.from_numpy(img[None])
-    poses, edges, names = estimate_pose(images, opts.model_path, precision=opts.precision)
+    poses, edges, names, *unc = estimate_pose(images, opts.model_path, precision=opts.precision,
+                                              return_uncertainty=opts.uncertainty)
     poses = poses.cpu().numpy()
-    for name, p in zip(names, poses[0]):
-        print(f'{name.decode():>10s}  {p[0]:9.2f} {p[1]:9.2f} {p[2]:9.2f}')
+    tails = _uncertainty_columns(unc[0], 0) if unc else [''] * len(names)
+    for name, p, tail in zip(names, poses[0], tails):
+        print(f'{name.decode():>10s}  {p[0]:9.2f} {p[1]:9.2f} {p[2]:9.2f}{tail}')
     if opts.plot:
         visualize_pose(img, poses[0], edges).savefig(opts.plot)
+
+
+def _uncertainty_columns(unc, k):
+    """Per joint of pose k: '   sd x y z mm   peak p' from a PoseUncertainty-like (covariance, peak)."""
+    cov, peak = unc[0][k].cpu().numpy(), unc[1][k].cpu().numpy()
+    sd = np.sqrt(np.maximum(np.diagonal(cov, axis1=-2, axis2=-1), 0.0))
+    return [f'   sd {s[0]:7.2f} {s[1]:7.2f} {s[2]:7.2f} mm   peak {p:6.4f}' for s, p in zip(sd, peak)]
 
 
 def _floats(text, n, flag):
@@ -310,14 +366,16 @@ def _main_frame(opts):
     if opts.bone_lengths or opts.root_depth:
         return _main_locate(opts, frame, boxes, camera, fmt)
     try:
-        poses, edges, names = estimate_pose_in_frames(frame, boxes, opts.model_path, cameras=camera, precision=opts.precision,
-                                                      views=opts.views, **fmt)
+        poses, edges, names, *unc = estimate_pose_in_frames(frame, boxes, opts.model_path, cameras=camera,
+                                                            precision=opts.precision, views=opts.views,
+                                                            return_uncertainty=opts.uncertainty, **fmt)
     except ValueError as e:
         raise SystemExit(str(e))
     for k, pose in enumerate(poses.cpu().numpy()):
         print(f'box {k} {opts.box[k]} (camera frame, root-relative mm)')
-        for name, p in zip(names, pose):
-            print(f'{name.decode():>10s}  {p[0]:9.2f} {p[1]:9.2f} {p[2]:9.2f}')
+        tails = _uncertainty_columns(unc[0], k) if unc else [''] * len(names)
+        for name, p, tail in zip(names, pose, tails):
+            print(f'{name.decode():>10s}  {p[0]:9.2f} {p[1]:9.2f} {p[2]:9.2f}{tail}')
 
 
 def _main_locate(opts, frame, boxes, camera, fmt):
@@ -332,14 +390,15 @@ def _main_locate(opts, frame, boxes, camera, fmt):
         kw = dict(scale_recovery='true-root-depth', root_depth=_floats(opts.root_depth, len(boxes), '--root-depth'))
     try:
         res = locate_poses_in_frames(frame, boxes, opts.model_path, cameras=camera, precision=opts.precision, views=opts.views,
-                                     **kw, **fmt)
+                                     return_uncertainty=opts.uncertainty, **kw, **fmt)
     except ValueError as e:
         raise SystemExit(str(e))
     poses, kp, z = res.poses.cpu().numpy(), res.keypoints2d.cpu().numpy(), res.z_offset.cpu().numpy()
     for k in range(len(boxes)):
         print(f'box {k} {opts.box[k]} (camera frame, absolute mm; frame pixels); root depth {z[k]:.1f} mm')
-        for name, p, q in zip(res.joint_names, poses[k], kp[k]):
-            print(f'{name.decode():>10s}  {p[0]:9.2f} {p[1]:9.2f} {p[2]:9.2f}   px {q[0]:8.2f} {q[1]:8.2f}')
+        tails = _uncertainty_columns((res.covariance, res.peak), k) if opts.uncertainty else [''] * len(res.joint_names)
+        for name, p, q, tail in zip(res.joint_names, poses[k], kp[k], tails):
+            print(f'{name.decode():>10s}  {p[0]:9.2f} {p[1]:9.2f} {p[2]:9.2f}   px {q[0]:8.2f} {q[1]:8.2f}{tail}')
 
 
 if __name__ == '__main__':
