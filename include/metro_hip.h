@@ -660,6 +660,37 @@ int  metro_place_covariances(const float* d_cov01, const float* d_peak, const Me
                              int32_t n_views, const MetroSpec* spec, const int32_t* d_mirror, int32_t coords,
                              float* d_cov_out, float* d_peak_out, void* stream);
 
+/* ---- world poses of persons seen by several calibrated cameras ----
+ * Nothing in the reference: its examples have one camera each.  Every crop row that shows a person gives one ray per joint,
+ * from the crop's undistorted virtual camera (MetroPlacement.inv_intrinsics, rot_to_world, cam_loc: no undistortion needed);
+ * the joint is the point nearest to its rays, X = (sum w (I - d d^T))^-1 sum w (I - d d^T) o.  One launch, one thread per
+ * (person, output joint), fp64 arithmetic on the fp32 inputs, one rounding to fp32 per output.
+ * d_coords01 fp32 [m, n_joints_head, 3] (metro_forward_coords01); d_cov01 fp32 [m, n_joints_head, 6] (metro_forward_moments;
+ * read by METRO_TRI_COVARIANCE only, else may be NULL); d_records DEVICE array of m MetroPlacement.
+ * Grouping (CSR): person p owns the crop rows d_rows[d_starts[p] : d_starts[p + 1]], d_rows int32 [n_rows] indices into the m
+ * rows, d_starts int32 [n_persons + 1] non-decreasing from 0 to n_rows.  A group may be empty.  An index of d_rows outside
+ * [0, m) gives no ray and d_starts is clamped to [0, n_rows]: the kernel reads nothing out of bounds.  With n_rows == 0 the
+ * four row inputs are not read and may be NULL.
+ * Ray of row i and output joint r: head joint spec->permutation[mirrored ? d_mirror[r] : r], mirrored = !(det rot_to_world >
+ * 0) (a flipped test-time view; metro_place_poses' rule); (u, v) = heatmap_to_image(coords01); d = rot_to_world .
+ * (inv_intrinsics . (u, v, 1)) normalised; o = cam_loc.  A ray with a non-finite component is skipped.
+ * weights METRO_TRI_UNIFORM: w = 1.  METRO_TRI_COVARIANCE: a second solve with w = 1 / (sigma^2 z^2), z = d . (X0 - o) the
+ * ray's depth at the uniform solution X0 and sigma^2 = (cov01_xx + cov01_yy) / 2 . lrc^2 . inv_intrinsics[0]^2 (lrc: the
+ * heat-map-to-pixel factor of heatmap_to_image), floored at 1e-12 lrc^2 inv_intrinsics[0]^2; a ray with z <= 0 or a
+ * non-finite w is dropped.
+ * Determinacy: with A~ = sum w (I - d d^T) / sum w, a joint with fewer than 2 rays or det A~ < min_det is undetermined:
+ * point and residual NaN, n_rays the number of usable rays.  Two rays at angle t have det A~ = sin^2 t / 4, so
+ * min_det = sin^2(min_angle) / 4 rejects (anti-)parallel rays, and any bundle of rays from one optical centre.
+ * d_points_out fp32 [n_persons, n_joints_out, 3] world mm; d_n_rays_out int32 [n_persons, n_joints_out] rays in the final
+ * solve; d_residual_out fp32 [n_persons, n_joints_out] = sqrt(sum w |(I - d d^T)(X - o)|^2 / sum w), the weighted RMS
+ * distance of the point from its rays in mm.  n_persons == 0 launches nothing. */
+#define METRO_TRI_UNIFORM 0
+#define METRO_TRI_COVARIANCE 1
+int  metro_triangulate_joints(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records, int32_t m,
+                              const int32_t* d_rows, int32_t n_rows, const int32_t* d_starts, int32_t n_persons,
+                              const MetroSpec* spec, const int32_t* d_mirror, int32_t weights, double min_det,
+                              float* d_points_out, int32_t* d_n_rays_out, float* d_residual_out, void* stream);
+
 const char* metro_last_error(void);
 int32_t metro_abi_version(void);
 

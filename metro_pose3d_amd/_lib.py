@@ -93,6 +93,7 @@ class MetroPlacement(C.Structure):
 
 
 METRO_MAX_VIEWS = 32
+METRO_TRI_UNIFORM, METRO_TRI_COVARIANCE = 0, 1
 
 
 class MetroViewBase(C.Structure):
@@ -183,6 +184,8 @@ SIGNATURES = {
     'metro_head_f16_moments': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(MetroSpec)] + [_P] * 8),
     'metro_softargmax01_moments': (C.c_int, [_P, C.c_int32, C.POINTER(MetroSpec), C.c_int32, _P, _P, _P, _P, _P, _P]),
     'metro_place_covariances': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(MetroSpec), _P, C.c_int32, _P, _P, _P]),
+    'metro_triangulate_joints': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.POINTER(MetroSpec), _P, C.c_int32,
+                                           C.c_double, _P, _P, _P, _P]),
     'metro_last_error': (C.c_char_p, []),
     'metro_abi_version': (C.c_int32, []),
 }

@@ -240,7 +240,7 @@ __device__ inline float z_offset_by_bones(const float (*cam)[3], const float* dz
 }
 
 // det of a row-major fp32 3x3 evaluated in fp64: tf.linalg.det's sign is what to_orig_cam tests (volumetric.py:279-281)
-__device__ inline double det3_f64(const float* r) {
+__host__ __device__ inline double det3_f64(const float* r) {
     return (double)r[0] * ((double)r[4] * r[8] - (double)r[5] * r[7]) -
            (double)r[1] * ((double)r[3] * r[8] - (double)r[5] * r[6]) +
            (double)r[2] * ((double)r[3] * r[7] - (double)r[4] * r[6]);
@@ -249,6 +249,21 @@ __device__ inline double det3_f64(const float* r) {
 // R . p, evaluated ((r0 p0 + r1 p1) + r2 p2) per row (matmul_joint_coords in to_orig_cam, volumetric.py:277-278)
 __device__ inline void rotate3(const float* r, const float* p, float* o) {
     for (int i = 0; i < 3; ++i) o[i] = (r[i * 3 + 0] * p[0] + r[i * 3 + 1] * p[1]) + r[i * 3 + 2] * p[2];
+}
+
+// crop_pixel, ray_through and rotate3 on the same fp32 inputs with every product and sum in fp64, in the same order
+// (triangulate.hip, whose reference is an fp64 restatement of the fp32 records; __host__ too: its test runs them on the CPU)
+__host__ __device__ inline void crop_pixel_f64(const float* c01j, float lrc, float half_off, double& u, double& v) {
+    u = (double)c01j[0] * (double)lrc; v = (double)c01j[1] * (double)lrc;
+    u = u + (double)half_off; v = v + (double)half_off;
+}
+
+__host__ __device__ inline void ray_through_f64(const float* k, double u, double v, double* cam) {
+    for (int i = 0; i < 3; ++i) cam[i] = ((double)k[i * 3 + 0] * u + (double)k[i * 3 + 1] * v) + (double)k[i * 3 + 2] * 1.0;
+}
+
+__host__ __device__ inline void rotate3_f64(const float* r, const double* p, double* o) {
+    for (int i = 0; i < 3; ++i) o[i] = ((double)r[i * 3 + 0] * p[0] + (double)r[i * 3 + 1] * p[1]) + (double)r[i * 3 + 2] * p[2];
 }
 
 }  // namespace metro

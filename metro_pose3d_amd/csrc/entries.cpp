@@ -585,6 +585,29 @@ int metro_merge_views(const float* d_poses, const float* d_keypoints, const floa
                               d_keypoints_out, d_z_offset_out, d_spread_out, static_cast<hipStream_t>(stream));
 }
 
+int metro_triangulate_joints(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records, int32_t m,
+                             const int32_t* d_rows, int32_t n_rows, const int32_t* d_starts, int32_t n_persons,
+                             const MetroSpec* spec, const int32_t* d_mirror, int32_t weights, double min_det, float* d_points_out,
+                             int32_t* d_n_rays_out, float* d_residual_out, void* stream) {
+    METRO_CHECK_ARG(spec != nullptr, "triangulate_joints: NULL spec");
+    METRO_CHECK_ARG(spec->n_joints_head >= 1 && spec->n_joints_head <= METRO_MAX_JOINTS && spec->n_joints_out >= 1 &&
+                        spec->n_joints_out <= METRO_MAX_JOINTS, "triangulate_joints: joint counts out of range (<= %d)", METRO_MAX_JOINTS);
+    METRO_CHECK_ARG(weights == METRO_TRI_UNIFORM || weights == METRO_TRI_COVARIANCE,
+                    "triangulate_joints: weights must be METRO_TRI_UNIFORM or METRO_TRI_COVARIANCE (got %d)", weights);
+    METRO_CHECK_ARG(n_persons >= 0 && m >= 0 && n_rows >= 0, "triangulate_joints: negative size (persons %d, crop rows %d, "
+                    "group rows %d)", n_persons, m, n_rows);
+    METRO_CHECK_ARG((int64_t)n_persons * spec->n_joints_out <= INT32_MAX, "triangulate_joints: %d persons overflow int32", n_persons);
+    if (n_persons == 0) return METRO_OK;
+    METRO_CHECK_ARG(d_starts && d_mirror && d_points_out && d_n_rays_out && d_residual_out,
+                    "triangulate_joints: NULL starts / mirror / output pointer");
+    METRO_CHECK_ARG(n_rows == 0 || (d_coords01 && d_records && d_rows && m > 0),
+                    "triangulate_joints: %d group rows need coords01, records, rows and m > 0", n_rows);
+    METRO_CHECK_ARG(weights != METRO_TRI_COVARIANCE || n_rows == 0 || d_cov01,
+                    "triangulate_joints: METRO_TRI_COVARIANCE reads cov01: NULL");
+    return launch_triangulate_joints(d_coords01, d_cov01, d_records, m, d_rows, n_rows, d_starts, n_persons, *spec, d_mirror, weights,
+                                     min_det, d_points_out, d_n_rays_out, d_residual_out, static_cast<hipStream_t>(stream));
+}
+
 const char* metro_last_error(void) { return metro::get_error(); }
 int32_t metro_abi_version(void) { return METRO_ABI_VERSION; }
 

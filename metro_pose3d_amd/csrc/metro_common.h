@@ -435,6 +435,10 @@ int launch_merge_views(const float* poses, const float* keypoints, const float* 
 int launch_place_covariances(const float* cov01, const float* peak, const MetroPlacement* rec, int n, int n_views,
                              const MetroSpec& spec, const int* mirror, int coords, float* cov_out, float* peak_out,
                              hipStream_t stream);
+// world joints of persons seen by several cameras, from the rays of their crop rows (triangulate.hip)
+int launch_triangulate_joints(const float* coords01, const float* cov01, const MetroPlacement* rec, int m, const int* rows,
+                              int n_rows, const int* starts, int n_persons, const MetroSpec& spec, const int* mirror, int weights,
+                              double min_det, float* points, int* n_rays, float* residual, hipStream_t stream);
 // per-box crop geometry of full frames (look_at_boxes.hip)
 int launch_look_at_boxes(const double* boxes, const int32_t* frame_index, int n, int n_frames, const MetroFrameCamera* cameras,
                          int n_cameras, int side, MetroViewBase* out, int32_t* status, hipStream_t stream);

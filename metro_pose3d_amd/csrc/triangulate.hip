@@ -1,0 +1,196 @@
+// World positions of the joints of persons seen by several calibrated cameras, in ONE launch (metro_triangulate_joints,
+// include/metro_hip.h).  Nothing in the reference to restate: its examples have one camera each.  The inputs are what the
+// frames chain holds on the device after the forward: coords01 [m][J_head][3], the MetroPlacement record of every crop (the
+// undistorted, square-pixel virtual camera: inv_intrinsics, rot_to_world, cam_loc -- no undistortion is needed) and, for the
+// covariance weights, cov01 [m][J_head][6] of the MOMENTS forward.  The crop rows of person p are rows[starts[p] : starts[p+1]].
+// Per (person, output joint r), every row i of the group gives one ray:
+//   * the head joint is perm[mirrored ? mirror[r] : r] with mirrored = !(det rot_to_world > 0), metro_place_poses' rule: a
+//     flipped test-time view reports the left joint where the right one is;
+//   * (u, v) = heatmap_to_image(coords01) (crop_pixel), d = rot_to_world . (inv_intrinsics . (u, v, 1)) normalised, o = cam_loc;
+//   * a ray with a non-finite component, or a row index outside [0, m), is skipped.
+// The point nearest to the rays in the least-squares sense solves  (sum w (I - d d^T)) X = sum w (I - d d^T) o:
+//   pass 1   w = 1;
+//   pass 2   (METRO_TRI_COVARIANCE) w = 1 / (sigma^2 z^2) with z = d . (X0 - o) the ray's depth at the pass-1 point and
+//            sigma^2 = (cov01_xx + cov01_yy) / 2 . lrc^2 . inv_intrinsics[0]^2 the isotropic variance of the ray in normalised
+//            image units (floored at 1e-12 lrc^2 inv_intrinsics[0]^2: a one-hot heat-map gets a large finite weight): w is the
+//            inverse variance of the ray's lateral position at the joint, in mm^-2.  z <= 0 or a non-finite w drops the ray.
+// The 3x3 system is solved by its cofactors.  With A~ = A / sum w (eigenvalues in [0, 1]) a joint is undetermined when fewer
+// than 2 rays remain or det A~ < min_det: two rays at angle t have det A~ = sin^2 t / 4, and rays from one optical centre
+// have det A~ -> 0 however many they are.  Undetermined: point and residual NaN, n_rays the count of usable rays.
+// residual = sqrt(sum w |(I - d d^T)(X - o)|^2 / sum w): the weighted RMS distance of the point from its rays, mm.
+// One thread per (person, output joint); rays are recomputed in each pass rather than stored (a group has no upper size).
+// fp64 arithmetic on the fp32 inputs, no FMA contraction (backproject.h), one rounding to fp32 per output.
+#include "metro_common.h"
+#include "backproject.h"
+
+#pragma clang fp contract(off)
+
+namespace metro {
+
+struct TriArgs {
+    const float* coords01;            // [m][nj][3] head order
+    const float* cov01;               // [m][nj][6] (METRO_TRI_COVARIANCE)
+    const MetroPlacement* rec;        // [m]
+    const int* rows;                  // [n_rows] indices into the m crop rows
+    const int* starts;                // [n_persons + 1]
+    const int* mirror;                // [n_out] output-order mirror joints
+    float* points;                    // [n_persons][n_out][3]
+    int* n_rays;                      // [n_persons][n_out]
+    float* residual;                  // [n_persons][n_out]
+    int m, n_rows, n_persons, nj, n_out, weights;
+    double min_det;
+    float lrc, half_off;
+    int perm[HEAD_MAX];
+};
+
+struct TriRay { double d[3], o[3], sigma2; };
+struct TriSystem { double a[6], b[3], sw; int cnt; };       // a: xx, yy, zz, xy, xz, yz of sum w (I - d d^T)
+
+__host__ __device__ inline bool tri_finite3(const double* v) {
+    return __builtin_isfinite(v[0]) && __builtin_isfinite(v[1]) && __builtin_isfinite(v[2]);
+}
+
+// the ray of output joint r in crop row `row`; false: no usable ray
+__host__ __device__ inline bool tri_ray(const TriArgs& a, int row, int r, TriRay& ray) {
+    if ((unsigned)row >= (unsigned)a.m) return false;
+    const MetroPlacement& rec = a.rec[row];
+    const bool mirrored = !(det3_f64(rec.rot_to_world) > 0.0);
+    const int ro = mirrored ? a.mirror[r] : r;
+    if ((unsigned)ro >= (unsigned)a.n_out) return false;
+    const int j = a.perm[ro];
+    if ((unsigned)j >= (unsigned)a.nj) return false;
+    double u, v, cam[3];
+    crop_pixel_f64(a.coords01 + ((size_t)row * a.nj + j) * 3, a.lrc, a.half_off, u, v);
+    ray_through_f64(rec.inv_intrinsics, u, v, cam);
+    rotate3_f64(rec.rot_to_world, cam, ray.d);
+    const double len = sqrt((ray.d[0] * ray.d[0] + ray.d[1] * ray.d[1]) + ray.d[2] * ray.d[2]);
+    for (int t = 0; t < 3; ++t) {
+        ray.d[t] = ray.d[t] / len;
+        ray.o[t] = (double)rec.cam_loc[t];
+    }
+    ray.sigma2 = 0.0;
+    if (a.weights == METRO_TRI_COVARIANCE) {
+        const float* c6 = a.cov01 + ((size_t)row * a.nj + j) * 6;
+        const double k0 = (double)rec.inv_intrinsics[0];
+        const double scale = ((double)a.lrc * (double)a.lrc) * (k0 * k0);
+        const double floor2 = 1e-12 * scale;
+        ray.sigma2 = (0.5 * ((double)c6[0] + (double)c6[1])) * scale;
+        if (ray.sigma2 < floor2) ray.sigma2 = floor2;          // a NaN covariance stays NaN: the ray drops in tri_weight
+    }
+    return tri_finite3(ray.d) && tri_finite3(ray.o);
+}
+
+// pass-2 weight of a ray given the pass-1 point; < 0: the ray is dropped
+__host__ __device__ inline double tri_weight(const TriRay& ray, const double* x0) {
+    const double z = (ray.d[0] * (x0[0] - ray.o[0]) + ray.d[1] * (x0[1] - ray.o[1])) + ray.d[2] * (x0[2] - ray.o[2]);
+    if (!(z > 0.0)) return -1.0;
+    const double w = 1.0 / (ray.sigma2 * (z * z));
+    return __builtin_isfinite(w) ? w : -1.0;
+}
+
+__host__ __device__ inline void tri_add(TriSystem& s, const TriRay& ray, double w) {
+    const double* d = ray.d;
+    const double* o = ray.o;
+    const double m[6] = {1.0 - d[0] * d[0], 1.0 - d[1] * d[1], 1.0 - d[2] * d[2], -(d[0] * d[1]), -(d[0] * d[2]), -(d[1] * d[2])};
+    for (int k = 0; k < 6; ++k) s.a[k] += w * m[k];
+    s.b[0] += w * ((m[0] * o[0] + m[3] * o[1]) + m[4] * o[2]);
+    s.b[1] += w * ((m[3] * o[0] + m[1] * o[1]) + m[5] * o[2]);
+    s.b[2] += w * ((m[4] * o[0] + m[5] * o[1]) + m[2] * o[2]);
+    s.sw += w;
+    ++s.cnt;
+}
+
+// X = A~^-1 b~ by the cofactors of the symmetric A~ = A / sum w; false: undetermined
+__host__ __device__ inline bool tri_solve(const TriSystem& s, double min_det, double* x) {
+    if (s.cnt < 2) return false;
+    const double xx = s.a[0] / s.sw, yy = s.a[1] / s.sw, zz = s.a[2] / s.sw, xy = s.a[3] / s.sw, xz = s.a[4] / s.sw, yz = s.a[5] / s.sw;
+    const double b0 = s.b[0] / s.sw, b1 = s.b[1] / s.sw, b2 = s.b[2] / s.sw;
+    const double c00 = yy * zz - yz * yz, c01 = xz * yz - xy * zz, c02 = xy * yz - xz * yy;
+    const double det = (xx * c00 + xy * c01) + xz * c02;
+    if (!(det >= min_det)) return false;
+    const double c11 = xx * zz - xz * xz, c12 = xy * xz - xx * yz, c22 = xx * yy - xy * xy;
+    x[0] = ((c00 * b0 + c01 * b1) + c02 * b2) / det;
+    x[1] = ((c01 * b0 + c11 * b1) + c12 * b2) / det;
+    x[2] = ((c02 * b0 + c12 * b1) + c22 * b2) / det;
+    return true;
+}
+
+// one (person, output joint): what a thread of the kernel runs, and what tests/test_triangulation.py runs on the host
+__host__ __device__ inline void triangulate_joint(const TriArgs& a, int idx) {
+    const int person = idx / a.n_out, r = idx - person * a.n_out;
+    int first = a.starts[person], last = a.starts[person + 1];
+    if (first < 0) first = 0;
+    if (last > a.n_rows) last = a.n_rows;
+    const bool weighted = a.weights == METRO_TRI_COVARIANCE;
+    TriRay ray;
+    TriSystem sys = {{0, 0, 0, 0, 0, 0}, {0, 0, 0}, 0.0, 0};
+    for (int k = first; k < last; ++k)
+        if (tri_ray(a, a.rows[k], r, ray)) tri_add(sys, ray, 1.0);
+    double x0[3] = {0, 0, 0}, x[3] = {0, 0, 0};
+    bool ok = tri_solve(sys, a.min_det, x0);
+    if (ok && weighted) {
+        sys = {{0, 0, 0, 0, 0, 0}, {0, 0, 0}, 0.0, 0};
+        for (int k = first; k < last; ++k) {
+            if (!tri_ray(a, a.rows[k], r, ray)) continue;
+            const double w = tri_weight(ray, x0);
+            if (w > 0.0) tri_add(sys, ray, w);
+        }
+        ok = tri_solve(sys, a.min_det, x);
+    } else {
+        for (int t = 0; t < 3; ++t) x[t] = x0[t];
+    }
+    float* out = a.points + (size_t)idx * 3;
+    a.n_rays[idx] = sys.cnt;
+    if (!ok) {
+        const float nan = __builtin_nanf("");
+        out[0] = out[1] = out[2] = nan;
+        a.residual[idx] = nan;
+        return;
+    }
+    double acc = 0.0;
+    for (int k = first; k < last; ++k) {
+        if (!tri_ray(a, a.rows[k], r, ray)) continue;
+        const double w = weighted ? tri_weight(ray, x0) : 1.0;
+        if (!(w > 0.0)) continue;
+        const double v[3] = {x[0] - ray.o[0], x[1] - ray.o[1], x[2] - ray.o[2]};
+        const double along = (ray.d[0] * v[0] + ray.d[1] * v[1]) + ray.d[2] * v[2];
+        const double p[3] = {v[0] - ray.d[0] * along, v[1] - ray.d[1] * along, v[2] - ray.d[2] * along};
+        acc += w * ((p[0] * p[0] + p[1] * p[1]) + p[2] * p[2]);
+    }
+    for (int t = 0; t < 3; ++t) out[t] = (float)x[t];
+    a.residual[idx] = (float)sqrt(acc / sys.sw);
+}
+
+__global__ __launch_bounds__(64) void triangulate_joints_kernel(TriArgs a) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < a.n_persons * a.n_out) triangulate_joint(a, idx);
+}
+
+// the launch's arguments from the entry's (the pixel scale of heatmap_to_image, volumetric.py:288-295, as place_poses.hip)
+inline TriArgs make_tri_args(const float* coords01, const float* cov01, const MetroPlacement* rec, int m, const int* rows,
+                             int n_rows, const int* starts, int n_persons, const MetroSpec& spec, const int* mirror, int weights,
+                             double min_det, float* points, int* n_rays, float* residual) {
+    TriArgs a;
+    a.coords01 = coords01; a.cov01 = cov01; a.rec = rec; a.rows = rows; a.starts = starts; a.mirror = mirror;
+    a.points = points; a.n_rays = n_rays; a.residual = residual;
+    a.m = m; a.n_rows = n_rows; a.n_persons = n_persons; a.nj = spec.n_joints_head; a.n_out = spec.n_joints_out;
+    a.weights = weights; a.min_det = min_det;
+    const int last = spec.proc_side - 1;
+    a.lrc = (float)(last - (last % spec.stride) - 1);
+    a.half_off = spec.centered_stride ? (float)(spec.stride / 2) : 0.0f;
+    for (int i = 0; i < HEAD_MAX; ++i) a.perm[i] = i < spec.n_joints_out ? spec.permutation[i] : 0;
+    return a;
+}
+
+int launch_triangulate_joints(const float* coords01, const float* cov01, const MetroPlacement* rec, int m, const int* rows,
+                              int n_rows, const int* starts, int n_persons, const MetroSpec& spec, const int* mirror, int weights,
+                              double min_det, float* points, int* n_rays, float* residual, hipStream_t stream) {
+    if (note_kernel("triangulate_joints")) return METRO_OK;
+    const TriArgs a = make_tri_args(coords01, cov01, rec, m, rows, n_rows, starts, n_persons, spec, mirror, weights, min_det, points,
+                                    n_rays, residual);
+    const int total = n_persons * spec.n_joints_out;
+    hipLaunchKernelGGL(triangulate_joints_kernel, dim3((total + 63) / 64), dim3(64), 0, stream, a);
+    return launch_status("triangulate_joints");
+}
+
+}  // namespace metro

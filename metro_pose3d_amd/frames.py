@@ -27,6 +27,12 @@ the box centre, drops the lens distortion, squares the pixels and zooms so the b
   locate_poses_in_frames                  absolute poses (bone-lengths / true-root-depth scale recovery, volumetric.py:171-208)
                                           and 2D frame keypoints: the same chain with one metro_place_poses launch after the
                                           forward
+  triangulate_poses_in_frames             world poses of persons seen by several calibrated cameras: the same chain up to the
+                                          forward (with the heat-map moments for the covariance weights), then ONE
+                                          metro_triangulate_joints launch that intersects, per person and joint, the rays of
+                                          all the crops that show the person (person_groups: the CSR grouping of the crop
+                                          rows); no bone lengths and no root depth needed.  Nothing in the reference (one
+                                          camera per example)
 
 Divergences from the reference, on purpose (camera.py and frame_formats.py list their own):
   * reproject_image's case 1 (cameralib.py:282-293: an all-zero coefficient array whose virtual R is allclose to the original
@@ -943,11 +949,126 @@ def _locate_poses_views(call: _Call, model_path, cameras, scale_recovery, target
                                             C.c_void_p(stream)), 'metro_place_poses')
         poses, keypoints, z_offset, spread = _merge_views(poses_v, keypoints_v, z_v, places, mirror, n, nv, spread=True)
         unc = tuple(_place_covariances(eng.spec, mom[0][0], mom[0][1], places, coords, n, nv)) if uncertainty else (None, None)
-        n_bad = _synchronise(bad, call.boxes)                          # the call's one stream synchronisation
-        if n_bad:
-            spec = eng.spec
-            raise _lib.NonFiniteError(
-                f'{spec.arch_name} stride {spec.stride} in precision {call.precision!r}: {n_bad} of {m} crops reached the '
-                'soft-argmax with non-finite statistics' +
-                (' (fp16 storage overflows at 65504: run this model with precision f32m or f64)' if call.precision == 'f16' else ''))
+        _raise_on_non_finite(eng.spec, call.precision, _synchronise(bad, call.boxes), m)    # the call's one stream synchronisation
     return FramePoses(poses, keypoints, z_offset, sk.edges_array(), names, *unc), spread
+
+
+def _raise_on_non_finite(spec, precision: str, n_bad: int, m: int) -> None:
+    if n_bad:
+        raise _lib.NonFiniteError(
+            f'{spec.arch_name} stride {spec.stride} in precision {precision!r}: {n_bad} of {m} crops reached the '
+            'soft-argmax with non-finite statistics' +
+            (' (fp16 storage overflows at 65504: run this model with precision f32m or f64)' if precision == 'f16' else ''))
+
+
+# ---- several calibrated cameras per person: triangulated world poses (metro_triangulate_joints) ----
+
+class WorldPoses(NamedTuple):
+    """What triangulate_poses_in_frames returns."""
+    poses: torch.Tensor                  # float32 [P, Jout, 3] world mm on the device; NaN where a joint is undetermined
+    n_rays: torch.Tensor                 # int32 [P, Jout]: the rays in the joint's final solve (usable rays if undetermined)
+    residual: torch.Tensor               # float32 [P, Jout] mm: weighted RMS distance of the joint from its rays
+    keypoints2d: torch.Tensor            # float32 [n, Jout, 2] frame pixels of every box, as locate_poses_in_frames gives them
+    joint_edges: np.ndarray
+    joint_names: np.ndarray
+
+
+def person_groups(person_index, frame_index, n_views: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+    """The CSR grouping metro_triangulate_joints reads, built on the host: (rows int32 [R], starts int32 [P + 1]) with
+    P = max(person_index) + 1, person p owning rows[starts[p]:starts[p+1]] -- the crop rows i * n_views + v (box-major) of
+    its boxes i, boxes in their given order (a stable sort by person).  A person index no box carries, and a person whose
+    boxes all lie on ONE frame (one camera: its rays share an optical centre and fix no depth), get an empty group."""
+    pi = np.asarray(person_index, np.int64).reshape(-1)
+    fi = np.asarray(frame_index, np.int64).reshape(-1)
+    if len(pi) != len(fi):
+        raise ValueError(f'person_index holds {len(pi)} values, frame_index {len(fi)}')
+    if len(pi) and pi.min() < 0:
+        raise ValueError(f'person_index must not be negative, got {pi.min()}')
+    n_persons = int(pi.max()) + 1 if len(pi) else 0
+    pairs = np.unique(np.stack([pi, fi], axis=1), axis=0) if len(pi) else np.zeros((0, 2), np.int64)
+    n_frames_of = np.bincount(pairs[:, 0], minlength=n_persons)
+    order = np.argsort(pi, kind='stable')
+    order = order[n_frames_of[pi[order]] >= 2]
+    counts = np.bincount(pi[order], minlength=n_persons) * int(n_views)
+    starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    rows = (order[:, None] * int(n_views) + np.arange(int(n_views))[None, :]).reshape(-1).astype(np.int32)
+    return rows, starts
+
+
+def triangulate_poses_in_frames(frames, boxes, model_path, cameras, person_index, frame_index, weights: str = 'covariance',
+                                min_angle_deg: float = 2.0, views=None, precision: Optional[str] = None,
+                                check_finite: Optional[bool] = None, geometry: str = 'auto', pixel_format: str = 'rgb',
+                                color_matrix: str = 'bt601', crop_dtype: str = 'float32') -> WorldPoses:
+    """uint8 frames of several calibrated cameras + person boxes -> WorldPoses(poses [P, Jout, 3], n_rays, residual,
+    keypoints2d [n, Jout, 2], joint_edges, joint_names): the absolute world pose of every person from two or more views of
+    it, with neither bone lengths nor a root depth.  frames, boxes, precision, check_finite, views, geometry, pixel_format,
+    color_matrix and crop_dtype as for locate_poses_in_frames.
+
+    cameras: a list with one Camera per frame, each with its own R and t (and distortion coefficients or None);
+    frame_index [n]: the frame (camera) of each box; person_index [n]: whom each box shows, P = max(person_index) + 1.  Both
+    are host integers.  Every box gives one ray per joint (V rays with views=V) from its crop's undistorted virtual camera,
+    d = rot_to_world . K^-1 . heatmap_to_image(coords01) from cam_loc; joint r of person p is the point nearest to the rays
+    of p's boxes (flipped views contribute their mirror joint, as in metro_place_poses).
+    weights 'uniform': every ray counts alike.  'covariance' (default): a second solve in which a ray counts by
+    1 / (sigma^2 z^2), sigma^2 the variance of the joint's own heat-map (the forward's moments, return_uncertainty's
+    statistic) in normalised image units and z the ray's depth at the uniform solution: a joint one camera sees badly
+    (occluded, at the crop's edge) leans on the cameras that see it well.
+    A joint is undetermined -- NaN pose and residual, n_rays the usable rays -- with fewer than two rays, or when its rays are
+    within min_angle_deg (in (0, 90], default 2 degrees) of parallel: the determinant of the normalised system is below
+    sin^2(min_angle) / 4.  A person whose boxes all lie on one frame has rays from one optical centre only and is not
+    solved: NaN pose, n_rays 0.  residual is the weighted RMS distance of the joint from its rays in mm: large where the
+    views disagree (a wrong person association, a bad calibration).
+    One enqueue chain on the current stream of the local device, locate_poses_in_frames' up to the forward (which also writes
+    the heat-map moments in 'covariance' mode, from the same launches), then one metro_triangulate_joints launch over all
+    n V crop rows, the keypoints by metro_place_poses and metro_merge_views, and the call's one synchronisation (the finite
+    screen; NonFiniteError).  No boxes: empty tensors, no launch.  ValueError before any launch for cameras=None or one Camera
+    for several frames, a negative person index, index lengths other than the number of boxes, an unknown `weights`, and
+    min_angle_deg outside (0, 90]."""
+    from metro_pose3d_amd.heads import triangulate_joints, triangulation_min_det
+    from metro_pose3d_amd.inference import _engine_for
+    triangulation_min_det(weights, min_angle_deg)
+    n_boxes = int(boxes.shape[0]) if isinstance(boxes, torch.Tensor) else len(np.asarray(boxes, np.float64).reshape(-1, 4))
+    pi = np.asarray(_host_array(person_index), np.int64).reshape(-1)
+    fi = np.asarray(_host_array(frame_index), np.int64).reshape(-1)
+    if len(pi) != n_boxes or len(fi) != n_boxes:
+        raise ValueError(f'person_index and frame_index must hold one value per box ({n_boxes}), got {len(pi)} and {len(fi)}')
+    if n_boxes and pi.min() < 0:
+        raise ValueError(f'person_index must not be negative, got {pi.min()}')
+    if cameras is None:
+        raise ValueError('triangulation needs calibrated cameras, one Camera per frame (cameras=None has none)')
+    if isinstance(cameras, Camera):
+        if n_boxes and (fi != fi[0]).any():
+            raise ValueError('one Camera for several frames: triangulation needs one Camera per frame, each with its own R and t')
+    elif n_boxes and (fi.min() < 0 or fi.max() >= len(cameras)):
+        raise ValueError(f'frame_index must lie in [0, {len(cameras)}) (one Camera per frame), got [{fi.min()}, {fi.max()}]')
+    call = _checked_call(frames, boxes, fi, 'world', views, geometry, precision, check_finite, pixel_format, color_matrix,
+                         crop_dtype)
+    sk = _model_skeleton(model_path)
+    n, nv = len(call.boxes), len(call.vs.zoom)
+    m = n * nv
+    rows, starts = person_groups(pi, fi, nv)
+    device = _call_device(call.boxes, call.frames)
+    names = np.empty(sk.n_out, dtype=object)
+    names[:] = sk.names_bytes()
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
+    if n == 0:
+        return WorldPoses(f32(0, sk.n_out, 3), torch.empty((0, sk.n_out), dtype=torch.int32, device=device), f32(0, sk.n_out),
+                          f32(0, sk.n_out, 2), sk.edges_array(), names)
+    moments = weights == 'covariance'
+    with torch.cuda.device(device):
+        eng = _engine_for(model_path, call.precision, device, m)
+        crops, places = _warp_views(call.frames, cameras, call.boxes, call.fi, call.vs, eng.spec.proc_side, device, call.crop_dtype)
+        rel, coords01, bad, *mom = _forward_coords01(eng, crops, call.check_finite, moments)
+        poses, n_rays, residual = triangulate_joints(coords01, mom[0][0] if moments else None, places.reshape(-1),
+                                                     _upload(rows, device), _upload(starts, device), eng.spec, weights,
+                                                     min_angle_deg)
+        poses_v, keypoints_v = f32(m, sk.n_out, 3), f32(m, sk.n_out, 2)
+        mirror = _upload(np.asarray(sk.out_mirror, np.int32), device)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        check(_lib.load().metro_place_poses(ptr(coords01), ptr(rel), ptr(places), m, C.byref(eng.cspec), SCALE_RECOVERY['metro'],
+                                            None, 0, None, None, len(sk.head_edges), ptr(mirror), COORDS['world'], ptr(poses_v),
+                                            ptr(keypoints_v), None, C.c_void_p(stream)), 'metro_place_poses')
+        keypoints = _merge_views(poses_v, keypoints_v, None, places, mirror, n, nv, spread=False)[1]
+        _raise_on_non_finite(eng.spec, call.precision, _synchronise(bad, call.boxes), m)    # the call's one stream synchronisation
+    return WorldPoses(poses, n_rays, residual, keypoints, sk.edges_array(), names)

@@ -5,6 +5,8 @@ through the C ABI (csrc/heads.hip).  Names and argument meaning follow the refer
   moments_from_logits       the same + covariance and peak of every joint's softmax volume (the graph's unused by-product
                             `heatmap_pred_z`, volumetric.py:165, is a marginal of it)
   place_covariances         Cov01 -> mm^2 in output order and crop / camera / world axes, views averaged
+  triangulate_joints        world joints of persons seen by several calibrated cameras: the point nearest to the rays of
+                            their crops, uniform or heat-map-covariance weights (nothing in the reference: one camera each)
   backproject_bone_lengths  scale_recovery 'bone-lengths' / '-true'   volumetric.py:171-191,
                             optimize_z_offset_by_bones(_tensor)       src/model/bone_length_based_backproj.py:15-62
   backproject_root_depth    scale_recovery 'true-root-depth'          volumetric.py:192-199
@@ -119,6 +121,67 @@ def place_covariances(cov01: torch.Tensor, peak: torch.Tensor, spec: ModelSpec, 
     check(lib.metro_place_covariances(_p(cov01), _p(peak), _p(records if coords != 'crop' else None), n, n_views, C.byref(cs),
                                       _p(mirror), _COORDS[coords], _p(out), _p(pk), _stream(dev)), 'metro_place_covariances')
     return out.view(n, spec.skeleton.n_out, 3, 3), pk
+
+
+TRI_WEIGHTS = {'uniform': _lib.METRO_TRI_UNIFORM, 'covariance': _lib.METRO_TRI_COVARIANCE}
+
+
+def triangulation_min_det(weights, min_angle_deg) -> float:
+    """Checks `weights` and `min_angle_deg` of the triangulation calls; returns min_det = sin^2(min_angle) / 4, the determinant
+    of the normalised system of two rays at that angle (metro_triangulate_joints)."""
+    if not isinstance(weights, str) or weights not in TRI_WEIGHTS:
+        raise ValueError(f"weights must be 'uniform' or 'covariance', got {weights!r}")
+    if (isinstance(min_angle_deg, (bool, np.bool_)) or not isinstance(min_angle_deg, (int, float, np.integer, np.floating))
+            or not 0 < min_angle_deg <= 90):
+        raise ValueError(f'min_angle_deg must lie in (0, 90] degrees, got {min_angle_deg!r}')
+    return float(np.sin(np.radians(float(min_angle_deg))) ** 2 / 4.0)
+
+
+def _i32(x, dev) -> torch.Tensor:
+    if isinstance(x, torch.Tensor):
+        return x.to(device=dev, dtype=torch.int32).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(x).astype(np.int32))).to(dev)
+
+
+def triangulate_joints(coords01: torch.Tensor, cov01: Optional[torch.Tensor], places: torch.Tensor, rows, starts,
+                       spec: ModelSpec, weights: str = 'covariance', min_angle_deg: float = 2.0):
+    """World joints of P persons from the rays of their crop rows, one metro_triangulate_joints launch.
+    coords01 [m,J_head,3] and (weights 'covariance') cov01 [m,J_head,6] as the forward writes them, `places` a uint8 device
+    tensor of m MetroPlacement records (the crops' virtual cameras), person p owning the crop rows rows[starts[p]:starts[p+1]]
+    (int arrays or tensors; starts [P+1], from 0 to len(rows), a group may be empty).  -> (points [P,Jout,3] world mm,
+    n_rays int32 [P,Jout], residual [P,Jout] mm) on the device.  'uniform': the point nearest to the rays; 'covariance': a
+    second solve that weights each ray by 1 / (sigma^2 z^2), its heat-map's variance carried to the joint's depth.  A joint
+    seen by fewer than two rays, or whose rays are within min_angle_deg of parallel (det of the normalised system below
+    sin^2(min_angle) / 4), is NaN; n_rays still counts its usable rays."""
+    min_det = triangulation_min_det(weights, min_angle_deg)
+    nj, n_out = spec.skeleton.n_head, spec.skeleton.n_out
+    if coords01.dim() != 3 or tuple(coords01.shape[1:]) != (nj, 3):
+        raise ValueError(f'coords01 must be [m,{nj},3], got {tuple(coords01.shape)}')
+    m = coords01.shape[0]
+    if weights == 'covariance' and (cov01 is None or tuple(cov01.shape) != (m, nj, 6)):
+        raise ValueError(f"weights='covariance' needs cov01 [{m},{nj},6], got {None if cov01 is None else tuple(cov01.shape)}")
+    need = m * C.sizeof(_lib.MetroPlacement)
+    if not isinstance(places, torch.Tensor) or places.dtype != torch.uint8 or places.numel() != need:
+        raise ValueError(f'places must be a uint8 tensor of {m} MetroPlacement records ({need} bytes)')
+    dev = coords01.device
+    rows, starts = _i32(rows, dev).reshape(-1), _i32(starts, dev).reshape(-1)
+    if starts.numel() < 1:
+        raise ValueError('starts must hold P + 1 offsets (P >= 0)')
+    n_persons = starts.numel() - 1
+    lib = _lib.load()
+    coords01, places = coords01.to(torch.float32).contiguous(), places.contiguous()
+    cov01 = cov01.to(torch.float32).contiguous() if weights == 'covariance' else None
+    points = torch.empty((n_persons, n_out, 3), dtype=torch.float32, device=dev)
+    n_rays = torch.empty((n_persons, n_out), dtype=torch.int32, device=dev)
+    residual = torch.empty((n_persons, n_out), dtype=torch.float32, device=dev)
+    if n_persons == 0:
+        return points, n_rays, residual
+    cs = spec.to_c(1)
+    mirror = torch.from_numpy(np.asarray(spec.skeleton.out_mirror, dtype=np.int32)).to(dev)
+    check(lib.metro_triangulate_joints(_p(coords01), _p(cov01), _p(places), m, _p(rows), rows.numel(), _p(starts),
+                                       n_persons, C.byref(cs), _p(mirror), TRI_WEIGHTS[weights], min_det, _p(points), _p(n_rays),
+                                       _p(residual), _stream(dev)), 'metro_triangulate_joints')
+    return points, n_rays, residual
 
 
 def backproject_bone_lengths(coords01: torch.Tensor, inv_intrinsics, bone_lengths, spec: ModelSpec,
