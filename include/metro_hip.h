@@ -19,6 +19,7 @@
 #ifndef METRO_HIP_H
 #define METRO_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -690,6 +691,56 @@ int  metro_triangulate_joints(const float* d_coords01, const float* d_cov01, con
                               const int32_t* d_rows, int32_t n_rows, const int32_t* d_starts, int32_t n_persons,
                               const MetroSpec* spec, const int32_t* d_mirror, int32_t weights, double min_det,
                               float* d_points_out, int32_t* d_n_rays_out, float* d_residual_out, void* stream);
+
+/* ---- poses of tracked persons smoothed over time: constant-velocity Kalman filter + Rauch-Tung-Striebel pass ----
+ * Nothing in the reference: one example is one image.  One launch, one thread per (track, output joint), fp64 arithmetic on
+ * the fp32 inputs, one rounding to fp32 per output.  J = spec->n_joints_out (nothing else of the spec is read).
+ * d_poses fp32 [n, J, 3] mm, the measurements (metro_place_poses / metro_merge_views); d_cov fp32 [n, J, 9] mm^2, row-major
+ * 3x3 per joint (metro_place_covariances), of which the upper triangle is read; read by METRO_SMOOTH_COVARIANCE only, else
+ * may be NULL; d_times fp64 [n] seconds.
+ * Grouping (CSR): track t owns the rows d_rows[d_starts[t] : d_starts[t + 1]] IN TIME ORDER (the host sorts them), d_rows
+ * int32 [n_rows] indices into the n rows, d_starts int32 [n_tracks + 1] non-decreasing from 0 to n_rows.  A group may be
+ * empty.  An index of d_rows outside [0, n) is skipped as if it were not listed, and d_starts is clamped to [0, n_rows]: the
+ * kernel reads nothing out of bounds.
+ * Per joint the state is x = (p, v) in R^6, mm and mm/s, with the symmetric 6x6 covariance P.
+ * Measurement of row k: z = d_poses[row, joint], H = [I 0], R = r_floor^2 I (METRO_SMOOTH_ISOTROPIC) or
+ * cov_scale Cov + r_floor^2 I (METRO_SMOOTH_COVARIANCE).  z is MISSING if a component is non-finite or, in covariance mode,
+ * if R has a non-finite entry or is not positive definite (leading minors R00, R00 R11 - R01^2, det R all > 0).
+ * Start: with d_state NULL or the slot's t_last NaN, rows before the track's first non-missing measurement get NaN in every
+ * float output and used = 0; that measurement sets x = (z, 0), P = diag(R, v0^2 I), used = 1.
+ * Every later row, and every row of a track with a carried state: dt = t_k - t_prev (t_prev the time of the previous listed
+ * row, or t_last of the carried state), 0 unless dt > 0; F = [[I, dt I], [0, I]], Q = q [[dt^3/3 I, dt^2/2 I], [dt^2/2 I, dt I]]
+ * (white-noise acceleration of spectral density q, mm^2/s^3); x- = F x, P- = F P F^T + Q.  Unless z is missing:
+ * nu = z - H x-, S = P-_pp + R; with gate > 0 the measurement is GATED if nu^T S^-1 nu > gate (gate == 0: never); otherwise
+ * K = P- H^T S^-1, x = x- + K nu, P = (I - K H) P- (I - K H)^T + K R K^T (Joseph form), used = 1.  A missing or gated
+ * row is predict-only: x = x-, P = P-, used = 0.
+ * mode METRO_SMOOTH_FILTER: the outputs of row k are x_k and P_k.  METRO_SMOOTH_RTS: from the track's last listed row of
+ * this call (whose smoothed value is its filtered one) back to its first row with a state, C = P_k F_{k+1}^T (P-_{k+1})^-1,
+ * x^s_k = x_k + C (x^s_{k+1} - x-_{k+1}), P^s_k = P_k + C (P^s_{k+1} - P-_{k+1}) C^T, the 6x6 system solved by an
+ * unpivoted LDL^T; if a pivot is not > 0 row k keeps its filtered value, which the pass continues from.  The outputs of
+ * row k are x^s_k and P^s_k.
+ * d_workspace: metro_smooth_tracks_workspace_bytes(n_rows, J) bytes = n_rows J 54 fp64 (x_k, P_k, x-_k, P-_k per listed row
+ * and joint); written and read by METRO_SMOOTH_RTS only, else may be NULL.
+ * d_state fp64 [n_tracks, J, 28] or NULL: x (6), the upper triangle of P row by row (21), t_last.  A track with at least one
+ * listed row in [0, n) and a state by its last row has the FILTER state of that row and the row's time written back, in both
+ * modes (never smoothed values); every other slot is left untouched.
+ * Outputs, written only for rows listed in some group: d_poses_out fp32 [n, J, 3] (p); optional (NULL: not written)
+ * d_velocity_out fp32 [n, J, 3] mm/s (v), d_cov_out fp32 [n, J, 9] mm^2 (the position block of P, symmetric),
+ * d_used_out uint8 [n, J].
+ * -1 before any launch for a NULL spec, J outside [1, METRO_MAX_JOINTS], a bad mode or measurement, negative n / n_rows /
+ * n_tracks, q <= 0, r_floor <= 0, v0 <= 0, cov_scale < 0, gate < 0 (or any of them NaN), and, with n_tracks > 0 and
+ * n_rows > 0, NULL d_poses, d_times, d_rows, d_starts or d_poses_out, NULL d_cov in covariance mode, NULL d_workspace in RTS
+ * mode.  n_tracks == 0 or n_rows == 0 launches nothing and returns 0. */
+#define METRO_SMOOTH_FILTER 0
+#define METRO_SMOOTH_RTS 1
+#define METRO_SMOOTH_ISOTROPIC 0
+#define METRO_SMOOTH_COVARIANCE 1
+size_t metro_smooth_tracks_workspace_bytes(int32_t n_rows, int32_t n_joints_out);
+int  metro_smooth_tracks(const float* d_poses, const float* d_cov, const double* d_times, int32_t n, const int32_t* d_rows,
+                         int32_t n_rows, const int32_t* d_starts, int32_t n_tracks, const MetroSpec* spec, int32_t mode,
+                         int32_t measurement, double q, double r_floor, double cov_scale, double v0, double gate,
+                         double* d_state, void* d_workspace, float* d_poses_out, float* d_velocity_out, float* d_cov_out,
+                         uint8_t* d_used_out, void* stream);
 
 const char* metro_last_error(void);
 int32_t metro_abi_version(void);

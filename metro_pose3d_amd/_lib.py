@@ -94,6 +94,8 @@ class MetroPlacement(C.Structure):
 
 METRO_MAX_VIEWS = 32
 METRO_TRI_UNIFORM, METRO_TRI_COVARIANCE = 0, 1
+METRO_SMOOTH_FILTER, METRO_SMOOTH_RTS = 0, 1
+METRO_SMOOTH_ISOTROPIC, METRO_SMOOTH_COVARIANCE = 0, 1
 
 
 class MetroViewBase(C.Structure):
@@ -186,6 +188,9 @@ SIGNATURES = {
     'metro_place_covariances': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(MetroSpec), _P, C.c_int32, _P, _P, _P]),
     'metro_triangulate_joints': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.POINTER(MetroSpec), _P, C.c_int32,
                                            C.c_double, _P, _P, _P, _P]),
+    'metro_smooth_tracks_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
+    'metro_smooth_tracks': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.POINTER(MetroSpec), C.c_int32, C.c_int32,
+                                      C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, _P]),
     'metro_last_error': (C.c_char_p, []),
     'metro_abi_version': (C.c_int32, []),
 }

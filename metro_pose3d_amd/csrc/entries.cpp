@@ -608,6 +608,40 @@ int metro_triangulate_joints(const float* d_coords01, const float* d_cov01, cons
                                      min_det, d_points_out, d_n_rays_out, d_residual_out, static_cast<hipStream_t>(stream));
 }
 
+size_t metro_smooth_tracks_workspace_bytes(int32_t n_rows, int32_t n_joints_out) {
+    return smooth_tracks_workspace_bytes(n_rows, n_joints_out);
+}
+
+int metro_smooth_tracks(const float* d_poses, const float* d_cov, const double* d_times, int32_t n, const int32_t* d_rows,
+                        int32_t n_rows, const int32_t* d_starts, int32_t n_tracks, const MetroSpec* spec, int32_t mode,
+                        int32_t measurement, double q, double r_floor, double cov_scale, double v0, double gate, double* d_state,
+                        void* d_workspace, float* d_poses_out, float* d_velocity_out, float* d_cov_out, uint8_t* d_used_out,
+                        void* stream) {
+    METRO_CHECK_ARG(spec != nullptr, "smooth_tracks: NULL spec");
+    METRO_CHECK_ARG(spec->n_joints_out >= 1 && spec->n_joints_out <= METRO_MAX_JOINTS,
+                    "smooth_tracks: n_joints_out %d out of range [1, %d]", spec->n_joints_out, METRO_MAX_JOINTS);
+    METRO_CHECK_ARG(mode == METRO_SMOOTH_FILTER || mode == METRO_SMOOTH_RTS,
+                    "smooth_tracks: mode must be METRO_SMOOTH_FILTER or METRO_SMOOTH_RTS (got %d)", mode);
+    METRO_CHECK_ARG(measurement == METRO_SMOOTH_ISOTROPIC || measurement == METRO_SMOOTH_COVARIANCE,
+                    "smooth_tracks: measurement must be METRO_SMOOTH_ISOTROPIC or METRO_SMOOTH_COVARIANCE (got %d)", measurement);
+    METRO_CHECK_ARG(n_tracks >= 0 && n >= 0 && n_rows >= 0, "smooth_tracks: negative size (tracks %d, pose rows %d, group rows %d)",
+                    n_tracks, n, n_rows);
+    METRO_CHECK_ARG(q > 0.0, "smooth_tracks: q must be > 0 (got %g)", q);
+    METRO_CHECK_ARG(r_floor > 0.0, "smooth_tracks: r_floor must be > 0 (got %g)", r_floor);
+    METRO_CHECK_ARG(v0 > 0.0, "smooth_tracks: v0 must be > 0 (got %g)", v0);
+    METRO_CHECK_ARG(cov_scale >= 0.0, "smooth_tracks: cov_scale must be >= 0 (got %g)", cov_scale);
+    METRO_CHECK_ARG(gate >= 0.0, "smooth_tracks: gate must be >= 0, 0 for none (got %g)", gate);
+    METRO_CHECK_ARG((int64_t)n_tracks * spec->n_joints_out <= INT32_MAX, "smooth_tracks: %d tracks overflow int32", n_tracks);
+    if (n_tracks == 0 || n_rows == 0) return METRO_OK;
+    METRO_CHECK_ARG(d_poses && d_times && d_rows && d_starts && d_poses_out,
+                    "smooth_tracks: NULL poses / times / rows / starts / poses_out pointer");
+    METRO_CHECK_ARG(measurement != METRO_SMOOTH_COVARIANCE || d_cov, "smooth_tracks: METRO_SMOOTH_COVARIANCE reads the covariance: NULL");
+    METRO_CHECK_ARG(mode != METRO_SMOOTH_RTS || d_workspace, "smooth_tracks: METRO_SMOOTH_RTS needs the workspace: NULL");
+    return launch_smooth_tracks(d_poses, d_cov, d_times, n, d_rows, n_rows, d_starts, n_tracks, spec->n_joints_out, mode, measurement,
+                                q, r_floor, cov_scale, v0, gate, d_state, d_workspace, d_poses_out, d_velocity_out, d_cov_out,
+                                d_used_out, static_cast<hipStream_t>(stream));
+}
+
 const char* metro_last_error(void) { return metro::get_error(); }
 int32_t metro_abi_version(void) { return METRO_ABI_VERSION; }
 

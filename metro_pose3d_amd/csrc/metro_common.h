@@ -439,6 +439,12 @@ int launch_place_covariances(const float* cov01, const float* peak, const MetroP
 int launch_triangulate_joints(const float* coords01, const float* cov01, const MetroPlacement* rec, int m, const int* rows,
                               int n_rows, const int* starts, int n_persons, const MetroSpec& spec, const int* mirror, int weights,
                               double min_det, float* points, int* n_rays, float* residual, hipStream_t stream);
+// tracked poses smoothed over time: Kalman filter + RTS pass per (track, joint) (smooth_tracks.hip)
+size_t smooth_tracks_workspace_bytes(int n_rows, int n_out);
+int launch_smooth_tracks(const float* poses, const float* cov, const double* times, int n, const int* rows, int n_rows,
+                         const int* starts, int n_tracks, int n_out, int mode, int measurement, double q, double r_floor,
+                         double cov_scale, double v0, double gate, double* state, void* workspace, float* poses_out,
+                         float* velocity_out, float* cov_out, unsigned char* used_out, hipStream_t stream);
 // per-box crop geometry of full frames (look_at_boxes.hip)
 int launch_look_at_boxes(const double* boxes, const int32_t* frame_index, int n, int n_frames, const MetroFrameCamera* cameras,
                          int n_cameras, int side, MetroViewBase* out, int32_t* status, hipStream_t stream);

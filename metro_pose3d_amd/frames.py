@@ -33,6 +33,13 @@ the box centre, drops the lens distortion, squares the pixels and zooms so the b
                                           all the crops that show the person (person_groups: the CSR grouping of the crop
                                           rows); no bone lengths and no root depth needed.  Nothing in the reference (one
                                           camera per example)
+  track_poses_in_frames                   poses of tracked persons smoothed over the frames of a video:
+                                          locate_poses_in_frames(return_uncertainty=True) unchanged, then ONE
+                                          metro_smooth_tracks launch: per track and joint a constant-velocity Kalman filter
+                                          and Rauch-Tung-Striebel pass over the track's boxes in time order, each weighted
+                                          by its heat-map covariance (track_groups: the CSR grouping; new_track_state: the
+                                          filter state carried from call to call).  Nothing in the reference (one image
+                                          per example)
 
 Divergences from the reference, on purpose (camera.py and frame_formats.py list their own):
   * reproject_image's case 1 (cameralib.py:282-293: an all-zero coefficient array whose virtual R is allclose to the original
@@ -1072,3 +1079,127 @@ def triangulate_poses_in_frames(frames, boxes, model_path, cameras, person_index
         keypoints = _merge_views(poses_v, keypoints_v, None, places, mirror, n, nv, spread=False)[1]
         _raise_on_non_finite(eng.spec, call.precision, _synchronise(bad, call.boxes), m)    # the call's one stream synchronisation
     return WorldPoses(poses, n_rays, residual, keypoints, sk.edges_array(), names)
+
+
+# ---- one camera over time: tracked poses smoothed by a Kalman filter / RTS pass (metro_smooth_tracks) ----
+
+class TrackPoses(NamedTuple):
+    """What track_poses_in_frames returns."""
+    poses: torch.Tensor                  # float32 [n, Jout, 3] mm: the filtered / smoothed pose of every box (untracked boxes: raw.poses)
+    velocity: torch.Tensor               # float32 [n, Jout, 3] mm/s (NaN for untracked boxes)
+    covariance: torch.Tensor             # float32 [n, Jout, 3, 3] mm^2 of the position estimate (untracked boxes: their R)
+    used: torch.Tensor                   # uint8 [n, Jout]: 1 where the box's measurement entered the update
+    raw: FramePoses                      # locate_poses_in_frames(..., return_uncertainty=True) of the same call, untouched
+    state: torch.Tensor                  # float64 [T, Jout, 28]: the filter state after this call (pass it to the next)
+    joint_edges: np.ndarray
+    joint_names: np.ndarray
+
+
+def track_groups(track_index, timestamps) -> Tuple[np.ndarray, np.ndarray]:
+    """The CSR grouping metro_smooth_tracks reads, built on the host: (rows int32 [R], starts int32 [T + 1]) with
+    T = max(track_index) + 1, track t owning rows[starts[t]:starts[t+1]], its rows in time order (a stable sort by track,
+    then time).  track_index -1 means untracked: the row is in no group.  ValueError for other negative indices, for
+    lengths that differ, for non-finite times and for two rows of one track at the same time."""
+    ti = np.asarray(track_index, np.int64).reshape(-1)
+    ts = np.asarray(timestamps, np.float64).reshape(-1)
+    if len(ti) != len(ts):
+        raise ValueError(f'track_index holds {len(ti)} values, timestamps {len(ts)}')
+    if len(ti) and ti.min() < -1:
+        raise ValueError(f'track_index must be a track (>= 0) or -1 for untracked, got {ti.min()}')
+    if not np.isfinite(ts).all():
+        raise ValueError('timestamps must be finite (seconds)')
+    n_tracks = int(ti.max()) + 1 if len(ti) else 0
+    order = np.lexsort((ts, ti))                           # by track, then time; stable
+    order = order[ti[order] >= 0]
+    same = (ti[order][1:] == ti[order][:-1]) & (ts[order][1:] == ts[order][:-1])
+    if same.any():
+        k = int(np.flatnonzero(same)[0])
+        raise ValueError(f'track {ti[order][k]} has two rows at the same time {ts[order][k]!r} ({order[k]} and {order[k + 1]})')
+    starts = np.concatenate([[0], np.cumsum(np.bincount(ti[order], minlength=n_tracks))]).astype(np.int32)
+    return order.astype(np.int32), starts
+
+
+def new_track_state(n_tracks: int, n_joints_out: int, device) -> torch.Tensor:
+    """A float64 [n_tracks, n_joints_out, 28] filter state with no prior (t_last = NaN) for track_poses_in_frames /
+    heads.smooth_tracks: per track and joint x (6), the upper triangle of P (21), t_last."""
+    state = torch.zeros((int(n_tracks), int(n_joints_out), 28), dtype=torch.float64, device=device)
+    state[..., 27] = float('nan')
+    return state
+
+
+def _box_times(timestamps, fi: np.ndarray, n: int) -> np.ndarray:
+    """timestamps -> one float64 per box: n values are read per box (boxes of one frame must then agree), any other length per
+    frame through frame_index."""
+    ts = np.asarray(_host_array(timestamps), np.float64).reshape(-1)
+    if not np.isfinite(ts).all():
+        raise ValueError('timestamps must be finite (seconds)')
+    if len(ts) != n:
+        if n and (fi.min() < 0 or fi.max() >= len(ts)):
+            raise ValueError(f'timestamps must hold one value per box ({n}) or one per frame: {len(ts)} values do not cover '
+                             f'frame_index [{fi.min()}, {fi.max()}]')
+        ts = ts[fi]
+    else:
+        first = {}
+        for f, t in zip(fi.tolist(), ts.tolist()):
+            if first.setdefault(f, t) != t:
+                raise ValueError(f'timestamps: boxes on frame {f} carry different times ({first[f]!r} and {t!r}); pass one value per '
+                                 'box, equal within a frame, or one per frame')
+    return ts
+
+
+def track_poses_in_frames(frames, boxes, model_path, cameras, track_index, frame_index, timestamps, state=None,
+                          mode: str = 'smooth', measurement: str = 'covariance', accel_psd: float = 4e6,
+                          sigma_floor_mm: float = 1.0, cov_scale: float = 1.0, initial_speed_mm_s: float = 2000.0, gate=None,
+                          scale_recovery: str = 'bone-lengths', bone_lengths=None, root_depth=None, coords: str = 'camera',
+                          precision: Optional[str] = None, check_finite: Optional[bool] = None, views=None,
+                          geometry: str = 'auto', pixel_format: str = 'rgb', color_matrix: str = 'bt601',
+                          crop_dtype: str = 'float32') -> TrackPoses:
+    """uint8 frames of a video + person boxes with a track each -> TrackPoses(poses, velocity, covariance, used, raw, state,
+    joint_edges, joint_names): locate_poses_in_frames(..., return_uncertainty=True), untouched (`raw`), then one
+    metro_smooth_tracks launch that runs, per track and joint, a constant-velocity Kalman filter over the track's boxes in
+    time order and (mode 'smooth') the Rauch-Tung-Striebel backward pass.  frames, boxes, cameras, frame_index and every
+    keyword from scale_recovery on are locate_poses_in_frames'.
+
+    track_index [n]: the track of each box (host integers; -1: untracked, the box comes back as `raw` has it with NaN
+    velocity and used 0); associating boxes with tracks is the caller's.  timestamps: seconds, one value per box, or one per
+    frame looked up through frame_index (n values are read per box); host data.  Two boxes of one track at one time are a
+    ValueError.
+    Each box's pose is a measurement with noise R = cov_scale * raw.covariance + sigma_floor_mm^2 I (measurement
+    'isotropic': sigma_floor_mm^2 I): a joint whose heat-map is wide in some direction counts for less in that direction.
+    A non-finite pose, or an R that is not positive definite, is bridged by the motion model (used 0); so is a measurement
+    whose squared Mahalanobis innovation exceeds `gate` (None: no gate).  mode 'filter' returns the causal estimates.
+    accel_psd (mm^2/s^3, white-noise acceleration), sigma_floor_mm and initial_speed_mm_s are design choices, not
+    measurements (heads.smooth_tracks).
+    state: None (every track starts at its first usable box; a fresh state for max(track_index) + 1 tracks is returned) or
+    the state a previous call returned (new_track_state for more tracks than this call names): tracks continue from it, and
+    it is updated in place with the FILTER state at each track's last box, so a stream cut into 64-frame calls with
+    mode='filter' gives what one long call gives.  In mode 'smooth' a call smooths within itself; its last box per track is
+    the filtered value.
+    keypoints2d stay raw.keypoints2d: 2D smoothing is not offered."""
+    from metro_pose3d_amd.heads import TRACK_STATE_DOUBLES, smooth_tracks, smoothing_params
+    smoothing_params(mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate)
+    n_boxes = int(boxes.shape[0]) if isinstance(boxes, torch.Tensor) else len(np.asarray(boxes, np.float64).reshape(-1, 4))
+    ti = np.asarray(_host_array(track_index), np.int64).reshape(-1)
+    fi = np.zeros(n_boxes, np.int64) if frame_index is None else np.asarray(_host_array(frame_index), np.int64).reshape(-1)
+    if len(ti) != n_boxes or len(fi) != n_boxes:
+        raise ValueError(f'track_index and frame_index must hold one value per box ({n_boxes}), got {len(ti)} and {len(fi)}')
+    times = _box_times(timestamps, fi, n_boxes)
+    rows, starts = track_groups(ti, times)
+    n_tracks = len(starts) - 1
+    if state is not None:
+        if (not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or state.dim() != 3
+                or state.shape[2] != TRACK_STATE_DOUBLES or state.shape[0] < n_tracks or not state.is_contiguous()):
+            raise ValueError(f'state must be a contiguous float64 tensor [T, Jout, {TRACK_STATE_DOUBLES}] with T >= {n_tracks} '
+                             '(new_track_state, or the state of a previous call)')
+        starts = np.concatenate([starts, np.full(state.shape[0] - n_tracks, starts[-1], np.int32)])
+    raw = locate_poses_in_frames(frames, boxes, model_path, cameras=cameras, frame_index=frame_index, scale_recovery=scale_recovery,
+                                 bone_lengths=bone_lengths, root_depth=root_depth, coords=coords, precision=precision,
+                                 check_finite=check_finite, views=views, geometry=geometry, pixel_format=pixel_format,
+                                 color_matrix=color_matrix, crop_dtype=crop_dtype, return_uncertainty=True)
+    device = raw.poses.device
+    if state is None:
+        state = new_track_state(n_tracks, raw.poses.shape[1], device)
+    with torch.cuda.device(device):
+        poses, velocity, covariance, used = smooth_tracks(raw.poses, raw.covariance, times, rows, starts, mode, measurement, accel_psd,
+                                                          sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, state)
+    return TrackPoses(poses, velocity, covariance, used, raw, state, raw.joint_edges, raw.joint_names)

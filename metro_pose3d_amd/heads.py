@@ -7,6 +7,8 @@ through the C ABI (csrc/heads.hip).  Names and argument meaning follow the refer
   place_covariances         Cov01 -> mm^2 in output order and crop / camera / world axes, views averaged
   triangulate_joints        world joints of persons seen by several calibrated cameras: the point nearest to the rays of
                             their crops, uniform or heat-map-covariance weights (nothing in the reference: one camera each)
+  smooth_tracks             poses of tracked persons over time: constant-velocity Kalman filter / RTS smoother per track and
+                            joint, each row weighted by its heat-map covariance (nothing in the reference: one image each)
   backproject_bone_lengths  scale_recovery 'bone-lengths' / '-true'   volumetric.py:171-191,
                             optimize_z_offset_by_bones(_tensor)       src/model/bone_length_based_backproj.py:15-62
   backproject_root_depth    scale_recovery 'true-root-depth'          volumetric.py:192-199
@@ -182,6 +184,94 @@ def triangulate_joints(coords01: torch.Tensor, cov01: Optional[torch.Tensor], pl
                                        n_persons, C.byref(cs), _p(mirror), TRI_WEIGHTS[weights], min_det, _p(points), _p(n_rays),
                                        _p(residual), _stream(dev)), 'metro_triangulate_joints')
     return points, n_rays, residual
+
+
+SMOOTH_MODES = {'filter': _lib.METRO_SMOOTH_FILTER, 'smooth': _lib.METRO_SMOOTH_RTS}
+SMOOTH_MEASUREMENTS = {'isotropic': _lib.METRO_SMOOTH_ISOTROPIC, 'covariance': _lib.METRO_SMOOTH_COVARIANCE}
+TRACK_STATE_DOUBLES = 28             # per (track, joint): x (6), the upper triangle of P (21), t_last
+
+
+def _positive(name, v, zero_ok=False) -> float:
+    ok = not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
+    if not ok or v < 0 or (v == 0 and not zero_ok):
+        raise ValueError(f"{name} must be a finite number {'>= 0' if zero_ok else '> 0'}, got {v!r}")
+    return float(v)
+
+
+def smoothing_params(mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate):
+    """Checks the smoothing keywords of smooth_tracks / frames.track_poses_in_frames; -> metro_smooth_tracks' (mode,
+    measurement, q, r_floor, cov_scale, v0, gate), gate None as 0."""
+    if not isinstance(mode, str) or mode not in SMOOTH_MODES:
+        raise ValueError(f"mode must be 'smooth' or 'filter', got {mode!r}")
+    if not isinstance(measurement, str) or measurement not in SMOOTH_MEASUREMENTS:
+        raise ValueError(f"measurement must be 'covariance' or 'isotropic', got {measurement!r}")
+    return (SMOOTH_MODES[mode], SMOOTH_MEASUREMENTS[measurement], _positive('accel_psd', accel_psd),
+            _positive('sigma_floor_mm', sigma_floor_mm), _positive('cov_scale', cov_scale, zero_ok=True),
+            _positive('initial_speed_mm_s', initial_speed_mm_s), 0.0 if gate is None else _positive('gate', gate))
+
+
+def smooth_tracks(poses: torch.Tensor, covariance: Optional[torch.Tensor], times, rows, starts, mode: str = 'smooth',
+                  measurement: str = 'covariance', accel_psd: float = 4e6, sigma_floor_mm: float = 1.0, cov_scale: float = 1.0,
+                  initial_speed_mm_s: float = 2000.0, gate: Optional[float] = None, state: Optional[torch.Tensor] = None):
+    """Poses of tracked persons filtered over time, one metro_smooth_tracks launch (include/metro_hip.h has the model).
+    poses [n,J,3] mm and (measurement 'covariance') covariance [n,J,3,3] or [n,J,9] mm^2 on the device, as
+    locate_poses_in_frames(return_uncertainty=True) returns them; times [n] seconds (host values or a tensor); track t owns
+    the rows rows[starts[t]:starts[t+1]] in time order (frames.track_groups; int arrays or tensors, starts [T+1]).
+    -> (poses [n,J,3], velocity [n,J,3] mm/s, covariance [n,J,3,3] mm^2 of the position, used uint8 [n,J]).
+    Per track and joint a constant-velocity Kalman filter reads each row's pose as a measurement with noise
+    R = cov_scale * covariance + sigma_floor_mm^2 I ('isotropic': sigma_floor_mm^2 I); mode 'filter' returns the causal
+    estimates, 'smooth' (default) the Rauch-Tung-Striebel smoothed ones.  A row whose pose is non-finite, or whose R is not
+    positive definite, is bridged by the prediction (used 0), as is one whose innovation exceeds `gate` (a squared
+    Mahalanobis distance, chi-square with 3 degrees of freedom; None: no gate); rows before a track's first usable
+    measurement are NaN.  Rows in no group come back as given: their pose, NaN velocity, their R, used 0.
+    The defaults are design choices, not measurements: accel_psd = 4e6 mm^2/s^3 is the white-noise acceleration density
+    that roughly 2 m/s^2 sustained over a second amounts to; sigma_floor_mm = 1 keeps R positive definite without
+    outweighing any real heat-map; initial_speed_mm_s = 2000 is the prior spread of the unknown first velocity.
+    state: None, or a float64 [T,J,28] device tensor (frames.new_track_state) carried from call to call: a track whose slot
+    holds a state continues from it, and every track with rows in this call gets the FILTER state of its last row written
+    back in place (in both modes), so a stream cut into calls is filtered as one."""
+    params = smoothing_params(mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate)
+    if not isinstance(poses, torch.Tensor) or poses.dim() != 3 or poses.shape[2] != 3 or not 1 <= poses.shape[1] <= _lib.METRO_MAX_JOINTS:
+        raise ValueError(f'poses must be a tensor [n,J,3] with J <= {_lib.METRO_MAX_JOINTS}, got {tuple(getattr(poses, "shape", ()))}')
+    n, nj = int(poses.shape[0]), int(poses.shape[1])
+    with_cov = measurement == 'covariance'
+    if with_cov and (covariance is None or tuple(covariance.shape) not in ((n, nj, 3, 3), (n, nj, 9))):
+        raise ValueError(f"measurement='covariance' needs covariance [{n},{nj},3,3], got "
+                         f'{None if covariance is None else tuple(covariance.shape)}')
+    dev = poses.device
+    if not isinstance(times, torch.Tensor):
+        times = torch.from_numpy(np.ascontiguousarray(np.asarray(times, np.float64).reshape(-1)))
+    if times.numel() != n:
+        raise ValueError(f'times must hold one value per pose row ({n}), got {times.numel()}')
+    n_rows = int(rows.numel() if isinstance(rows, torch.Tensor) else np.asarray(rows).size)
+    n_starts = int(starts.numel() if isinstance(starts, torch.Tensor) else np.asarray(starts).size)
+    if n_starts < 1:
+        raise ValueError('starts must hold T + 1 offsets (T >= 0)')
+    n_tracks = n_starts - 1
+    if state is not None and (not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or state.device != dev
+                              or tuple(state.shape) != (n_tracks, nj, TRACK_STATE_DOUBLES) or not state.is_contiguous()):
+        raise ValueError(f'state must be a contiguous float64 tensor [{n_tracks},{nj},{TRACK_STATE_DOUBLES}] on {dev} '
+                         '(frames.new_track_state)')
+    lib = _lib.load()
+    times = times.to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+    rows, starts = _i32(rows, dev).reshape(-1), _i32(starts, dev).reshape(-1)
+    poses = poses.to(torch.float32).contiguous()
+    cov = covariance.to(torch.float32).reshape(n, nj, 9).contiguous() if with_cov else None
+    # what the launch leaves alone: rows in no group keep their pose, a NaN velocity, their R and used = 0
+    out = poses.clone()
+    velocity = torch.full_like(poses, float('nan'))
+    r = torch.eye(3, dtype=torch.float32, device=dev).mul(params[3] ** 2).expand(n, nj, 3, 3)
+    if with_cov:
+        upper = cov.view(n, nj, 3, 3).triu()
+        r = r + params[4] * (upper + upper.triu(1).transpose(-1, -2))
+    cov_out = r.reshape(n, nj, 9).contiguous()
+    used = torch.zeros((n, nj), dtype=torch.uint8, device=dev)
+    ws = torch.empty(lib.metro_smooth_tracks_workspace_bytes(n_rows, nj) if mode == 'smooth' else 0, dtype=torch.uint8, device=dev)
+    cs = _lib.MetroSpec(n_joints_out=nj)
+    check(lib.metro_smooth_tracks(_p(poses), _p(cov), _p(times), n, _p(rows), n_rows, _p(starts), n_tracks, C.byref(cs), *params,
+                                  _p(state), _p(ws), _p(out), _p(velocity), _p(cov_out), _p(used), _stream(dev)),
+          'metro_smooth_tracks')
+    return out, velocity, cov_out.view(n, nj, 3, 3), used
 
 
 def backproject_bone_lengths(coords01: torch.Tensor, inv_intrinsics, bone_lengths, spec: ModelSpec,
