@@ -692,6 +692,43 @@ int  metro_triangulate_joints(const float* d_coords01, const float* d_cov01, con
                               const MetroSpec* spec, const int32_t* d_mirror, int32_t weights, double min_det,
                               float* d_points_out, int32_t* d_n_rays_out, float* d_residual_out, void* stream);
 
+/* ---- which boxes of several calibrated cameras show the same person: cross-view association on the device ----
+ * Nothing in the reference: its examples have one camera each, and a person detector gives boxes per camera with no shared
+ * identity.  Two launches between the forward and metro_triangulate_joints, no host work in between.
+ * metro_view_affinity: how close the per-joint rays of every two boxes pass.  Inputs as metro_triangulate_joints reads them:
+ * d_coords01 fp32 [m, n_joints_head, 3], d_cov01 fp32 [m, n_joints_head, 6] (METRO_TRI_COVARIANCE only, else may be NULL),
+ * d_records m MetroPlacement, d_mirror int32 [n_joints_out], with m = n * n_views crop rows, box-major (row i * n_views + v);
+ * d_frame_index int32 [n], the frame (camera) of each box.  Rays as there: the mirror joint for a flipped view, a non-finite
+ * ray skipped, sigma^2 the same variance.  Per pair of boxes a < b on different frames, per view v and output joint r, with
+ * the unit directions da, db from oa, ob and c = da . db: the ray pair is skipped if a ray is unusable or
+ * 1 - c^2 < min_sin2 (within min_angle of parallel, min_sin2 = sin^2(min_angle) in (0, 1]); the lines are closest at the
+ * parameters ta, tb at the distance dist; with ta <= 0 or tb <= 0 (they meet behind a camera) the pair counts with
+ * dist = clip_mm, else with min(dist, clip_mm).  weights METRO_TRI_UNIFORM: w = 1; METRO_TRI_COVARIANCE:
+ * w = 1 / (sigma_a^2 ta^2 + sigma_b^2 tb^2), a pair whose w is not finite and positive is skipped.
+ * d_cost_out fp32 [n, n] = sqrt(sum w dist^2 / sum w) in mm over the counted pairs, symmetric; d_n_pairs_out int32 [n, n]
+ * their number.  +inf where n_pairs < min_pairs, for two boxes on one frame (n_pairs 0: a person appears once per camera)
+ * and on the diagonal (n_pairs 0).  One thread per entry of the n x n index space, the one with a < b writes [a][b] and
+ * [b][a]; fp64 arithmetic on the fp32 inputs, one rounding to fp32 per output.
+ * metro_cluster_views: constrained complete-linkage clustering of the boxes, one workgroup, the working matrix in LDS.
+ * d_cost fp32 [n, n] is read as C = max(cost, cost^T) with NaN as +inf.  Every box starts as its own cluster, named by its
+ * lowest box.  Repeat: among the clusters a < b take the smallest C[a][b] (ties: the smallest a, then the smallest b); unless
+ * it is < max_cost stop; else b merges into a, C[a][k] = C[k][a] = max(C[a][k], C[b][k]) for all k.  +inf propagates through
+ * the max, so no person gets two boxes of one frame.  d_person_index_out int32 [n]: persons numbered by their lowest box (box
+ * 0 is in person 0); d_n_persons_out int32 [1]; the CSR grouping metro_triangulate_joints reads with n as its person count:
+ * d_starts_out int32 [n + 1], d_rows_out int32 [n * n_views].  A person with several boxes owns the crop rows
+ * i * n_views + v of its boxes in ascending box order; a person with one box (one optical centre: no depth) and the persons
+ * >= n_persons have empty groups; the entries of d_rows_out from d_starts_out[n] on are -1.
+ * -1 before any launch for a NULL pointer (d_cov01 only with METRO_TRI_COVARIANCE), a negative n, n > METRO_MATCH_MAX_BOXES,
+ * n_views outside [1, METRO_MAX_VIEWS], unknown weights, joint counts out of range, min_sin2 outside (0, 1], clip_mm or
+ * max_cost not > 0 (or NaN) and min_pairs < 1.  n == 0 launches nothing and returns 0. */
+#define METRO_MATCH_MAX_BOXES 128
+int  metro_view_affinity(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records, const MetroSpec* spec,
+                         const int32_t* d_mirror, const int32_t* d_frame_index, int32_t n, int32_t n_views, int32_t weights,
+                         double min_sin2, double clip_mm, int32_t min_pairs, float* d_cost_out, int32_t* d_n_pairs_out,
+                         void* stream);
+int  metro_cluster_views(const float* d_cost, int32_t n, int32_t n_views, float max_cost, int32_t* d_person_index_out,
+                         int32_t* d_n_persons_out, int32_t* d_rows_out, int32_t* d_starts_out, void* stream);
+
 /* ---- poses of tracked persons smoothed over time: constant-velocity Kalman filter + Rauch-Tung-Striebel pass ----
  * Nothing in the reference: one example is one image.  One launch, one thread per (track, output joint), fp64 arithmetic on
  * the fp32 inputs, one rounding to fp32 per output.  J = spec->n_joints_out (nothing else of the spec is read).

@@ -94,6 +94,7 @@ class MetroPlacement(C.Structure):
 
 METRO_MAX_VIEWS = 32
 METRO_TRI_UNIFORM, METRO_TRI_COVARIANCE = 0, 1
+METRO_MATCH_MAX_BOXES = 128
 METRO_SMOOTH_FILTER, METRO_SMOOTH_RTS = 0, 1
 METRO_SMOOTH_ISOTROPIC, METRO_SMOOTH_COVARIANCE = 0, 1
 
@@ -188,6 +189,9 @@ SIGNATURES = {
     'metro_place_covariances': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(MetroSpec), _P, C.c_int32, _P, _P, _P]),
     'metro_triangulate_joints': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.POINTER(MetroSpec), _P, C.c_int32,
                                            C.c_double, _P, _P, _P, _P]),
+    'metro_view_affinity': (C.c_int, [_P, _P, _P, C.POINTER(MetroSpec), _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                      C.c_int32, _P, _P, _P]),
+    'metro_cluster_views': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_float, _P, _P, _P, _P, _P]),
     'metro_smooth_tracks_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
     'metro_smooth_tracks': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.POINTER(MetroSpec), C.c_int32, C.c_int32,
                                       C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, _P]),

@@ -608,6 +608,42 @@ int metro_triangulate_joints(const float* d_coords01, const float* d_cov01, cons
                                      min_det, d_points_out, d_n_rays_out, d_residual_out, static_cast<hipStream_t>(stream));
 }
 
+int metro_view_affinity(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records, const MetroSpec* spec,
+                        const int32_t* d_mirror, const int32_t* d_frame_index, int32_t n, int32_t n_views, int32_t weights,
+                        double min_sin2, double clip_mm, int32_t min_pairs, float* d_cost_out, int32_t* d_n_pairs_out,
+                        void* stream) {
+    METRO_CHECK_ARG(spec != nullptr, "view_affinity: NULL spec");
+    METRO_CHECK_ARG(spec->n_joints_head >= 1 && spec->n_joints_head <= METRO_MAX_JOINTS && spec->n_joints_out >= 1 &&
+                        spec->n_joints_out <= METRO_MAX_JOINTS, "view_affinity: joint counts out of range (<= %d)", METRO_MAX_JOINTS);
+    METRO_CHECK_ARG(weights == METRO_TRI_UNIFORM || weights == METRO_TRI_COVARIANCE,
+                    "view_affinity: weights must be METRO_TRI_UNIFORM or METRO_TRI_COVARIANCE (got %d)", weights);
+    METRO_CHECK_ARG(n >= 0, "view_affinity: negative size (%d boxes)", n);
+    METRO_CHECK_ARG(n <= METRO_MATCH_MAX_BOXES, "view_affinity: %d boxes (at most %d)", n, METRO_MATCH_MAX_BOXES);
+    METRO_CHECK_ARG(n_views >= 1 && n_views <= METRO_MAX_VIEWS, "view_affinity: %d views (1 to %d)", n_views, METRO_MAX_VIEWS);
+    METRO_CHECK_ARG(min_sin2 > 0.0 && min_sin2 <= 1.0, "view_affinity: min_sin2 must lie in (0, 1] (got %g)", min_sin2);
+    METRO_CHECK_ARG(clip_mm > 0.0, "view_affinity: clip_mm must be > 0 (got %g)", clip_mm);
+    METRO_CHECK_ARG(min_pairs >= 1, "view_affinity: min_pairs must be >= 1 (got %d)", min_pairs);
+    if (n == 0) return METRO_OK;
+    METRO_CHECK_ARG(d_coords01 && d_records && d_mirror && d_frame_index && d_cost_out && d_n_pairs_out,
+                    "view_affinity: NULL coords01 / records / mirror / frame_index / output pointer");
+    METRO_CHECK_ARG(weights != METRO_TRI_COVARIANCE || d_cov01, "view_affinity: METRO_TRI_COVARIANCE reads cov01: NULL");
+    return launch_view_affinity(d_coords01, d_cov01, d_records, *spec, d_mirror, d_frame_index, n, n_views, weights, min_sin2,
+                                clip_mm, min_pairs, d_cost_out, d_n_pairs_out, static_cast<hipStream_t>(stream));
+}
+
+int metro_cluster_views(const float* d_cost, int32_t n, int32_t n_views, float max_cost, int32_t* d_person_index_out,
+                        int32_t* d_n_persons_out, int32_t* d_rows_out, int32_t* d_starts_out, void* stream) {
+    METRO_CHECK_ARG(n >= 0, "cluster_views: negative size (%d boxes)", n);
+    METRO_CHECK_ARG(n <= METRO_MATCH_MAX_BOXES, "cluster_views: %d boxes (at most %d)", n, METRO_MATCH_MAX_BOXES);
+    METRO_CHECK_ARG(n_views >= 1 && n_views <= METRO_MAX_VIEWS, "cluster_views: %d views (1 to %d)", n_views, METRO_MAX_VIEWS);
+    METRO_CHECK_ARG(max_cost > 0.0f, "cluster_views: max_cost must be > 0 (got %g)", (double)max_cost);
+    if (n == 0) return METRO_OK;
+    METRO_CHECK_ARG(d_cost && d_person_index_out && d_n_persons_out && d_rows_out && d_starts_out,
+                    "cluster_views: NULL cost / output pointer");
+    return launch_cluster_views(d_cost, n, n_views, max_cost, d_person_index_out, d_n_persons_out, d_rows_out, d_starts_out,
+                                static_cast<hipStream_t>(stream));
+}
+
 size_t metro_smooth_tracks_workspace_bytes(int32_t n_rows, int32_t n_joints_out) {
     return smooth_tracks_workspace_bytes(n_rows, n_joints_out);
 }

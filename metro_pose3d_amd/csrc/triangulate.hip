@@ -22,6 +22,7 @@
 // fp64 arithmetic on the fp32 inputs, no FMA contraction (backproject.h), one rounding to fp32 per output.
 #include "metro_common.h"
 #include "backproject.h"
+#include "tri_ray.h"
 
 #pragma clang fp contract(off)
 
@@ -43,42 +44,7 @@ struct TriArgs {
     int perm[HEAD_MAX];
 };
 
-struct TriRay { double d[3], o[3], sigma2; };
 struct TriSystem { double a[6], b[3], sw; int cnt; };       // a: xx, yy, zz, xy, xz, yz of sum w (I - d d^T)
-
-__host__ __device__ inline bool tri_finite3(const double* v) {
-    return __builtin_isfinite(v[0]) && __builtin_isfinite(v[1]) && __builtin_isfinite(v[2]);
-}
-
-// the ray of output joint r in crop row `row`; false: no usable ray
-__host__ __device__ inline bool tri_ray(const TriArgs& a, int row, int r, TriRay& ray) {
-    if ((unsigned)row >= (unsigned)a.m) return false;
-    const MetroPlacement& rec = a.rec[row];
-    const bool mirrored = !(det3_f64(rec.rot_to_world) > 0.0);
-    const int ro = mirrored ? a.mirror[r] : r;
-    if ((unsigned)ro >= (unsigned)a.n_out) return false;
-    const int j = a.perm[ro];
-    if ((unsigned)j >= (unsigned)a.nj) return false;
-    double u, v, cam[3];
-    crop_pixel_f64(a.coords01 + ((size_t)row * a.nj + j) * 3, a.lrc, a.half_off, u, v);
-    ray_through_f64(rec.inv_intrinsics, u, v, cam);
-    rotate3_f64(rec.rot_to_world, cam, ray.d);
-    const double len = sqrt((ray.d[0] * ray.d[0] + ray.d[1] * ray.d[1]) + ray.d[2] * ray.d[2]);
-    for (int t = 0; t < 3; ++t) {
-        ray.d[t] = ray.d[t] / len;
-        ray.o[t] = (double)rec.cam_loc[t];
-    }
-    ray.sigma2 = 0.0;
-    if (a.weights == METRO_TRI_COVARIANCE) {
-        const float* c6 = a.cov01 + ((size_t)row * a.nj + j) * 6;
-        const double k0 = (double)rec.inv_intrinsics[0];
-        const double scale = ((double)a.lrc * (double)a.lrc) * (k0 * k0);
-        const double floor2 = 1e-12 * scale;
-        ray.sigma2 = (0.5 * ((double)c6[0] + (double)c6[1])) * scale;
-        if (ray.sigma2 < floor2) ray.sigma2 = floor2;          // a NaN covariance stays NaN: the ray drops in tri_weight
-    }
-    return tri_finite3(ray.d) && tri_finite3(ray.o);
-}
 
 // pass-2 weight of a ray given the pass-1 point; < 0: the ray is dropped
 __host__ __device__ inline double tri_weight(const TriRay& ray, const double* x0) {
@@ -166,19 +132,16 @@ __global__ __launch_bounds__(64) void triangulate_joints_kernel(TriArgs a) {
     if (idx < a.n_persons * a.n_out) triangulate_joint(a, idx);
 }
 
-// the launch's arguments from the entry's (the pixel scale of heatmap_to_image, volumetric.py:288-295, as place_poses.hip)
+// the launch's arguments from the entry's
 inline TriArgs make_tri_args(const float* coords01, const float* cov01, const MetroPlacement* rec, int m, const int* rows,
                              int n_rows, const int* starts, int n_persons, const MetroSpec& spec, const int* mirror, int weights,
                              double min_det, float* points, int* n_rays, float* residual) {
     TriArgs a;
     a.coords01 = coords01; a.cov01 = cov01; a.rec = rec; a.rows = rows; a.starts = starts; a.mirror = mirror;
     a.points = points; a.n_rays = n_rays; a.residual = residual;
-    a.m = m; a.n_rows = n_rows; a.n_persons = n_persons; a.nj = spec.n_joints_head; a.n_out = spec.n_joints_out;
+    a.m = m; a.n_rows = n_rows; a.n_persons = n_persons;
     a.weights = weights; a.min_det = min_det;
-    const int last = spec.proc_side - 1;
-    a.lrc = (float)(last - (last % spec.stride) - 1);
-    a.half_off = spec.centered_stride ? (float)(spec.stride / 2) : 0.0f;
-    for (int i = 0; i < HEAD_MAX; ++i) a.perm[i] = i < spec.n_joints_out ? spec.permutation[i] : 0;
+    tri_ray_fields(a, spec);
     return a;
 }
 

@@ -33,6 +33,10 @@ the box centre, drops the lens distortion, squares the pixels and zooms so the b
                                           all the crops that show the person (person_groups: the CSR grouping of the crop
                                           rows); no bone lengths and no root depth needed.  Nothing in the reference (one
                                           camera per example)
+  match_poses_in_frames                   the same without a person_index: one metro_view_affinity launch (how close the
+                                          per-joint rays of every two boxes pass) and one metro_cluster_views launch
+                                          (complete-linkage clustering in one workgroup, which writes the CSR grouping on the
+                                          device) between the forward and metro_triangulate_joints.  Nothing in the reference
   track_poses_in_frames                   poses of tracked persons smoothed over the frames of a video:
                                           locate_poses_in_frames(return_uncertainty=True) unchanged, then ONE
                                           metro_smooth_tracks launch: per track and joint a constant-velocity Kalman filter
@@ -613,17 +617,21 @@ def _warp_views(frames, cameras, boxes, fi, vs: Views, side: int, device: torch.
     return crops, places
 
 
-def _synchronise(bad: Optional[torch.Tensor], boxes) -> int:
+def _synchronise(bad: Optional[torch.Tensor], boxes, also: Optional[torch.Tensor] = None):
     """The one read of a call, after everything is enqueued: the finite screen folded on the device (`bad`; None: not asked for)
     and, for _DeviceBoxes, their frame status in one transfer -> the number of non-finite crops.  ValueError for a device
-    frame index outside its range.  Host boxes and no screen: nothing to read, no synchronisation."""
-    if not isinstance(boxes, _DeviceBoxes):
+    frame index outside its range.  Host boxes and no screen: nothing to read, no synchronisation.
+    also: one more device integer the caller needs on the host (the persons metro_cluster_views found), read in the same
+    transfer -> (the number of non-finite crops, that integer or None)."""
+    if also is None and not isinstance(boxes, _DeviceBoxes):
         return int(bad.item()) if bad is not None else 0
-    status, n_frames = boxes.frame_status
-    words = status.to(torch.int64) if bad is None else torch.cat([status.to(torch.int64), bad.reshape(1)])
-    words = words.tolist()
-    _raise_on_bad_frames(words[0], len(boxes), n_frames)
-    return words[1] if bad is not None else 0
+    words = [t.reshape(-1)[:1].to(torch.int64) for t in (boxes.frame_status[0] if isinstance(boxes, _DeviceBoxes) else None, bad, also)
+             if t is not None]
+    words = torch.cat(words).tolist()
+    if isinstance(boxes, _DeviceBoxes):
+        _raise_on_bad_frames(words.pop(0), len(boxes), boxes.frame_status[1])
+    n_bad = words.pop(0) if bad is not None else 0
+    return n_bad if also is None else (n_bad, words.pop(0))
 
 
 class _Call(NamedTuple):
@@ -1031,16 +1039,27 @@ def triangulate_poses_in_frames(frames, boxes, model_path, cameras, person_index
     screen; NonFiniteError).  No boxes: empty tensors, no launch.  ValueError before any launch for cameras=None or one Camera
     for several frames, a negative person index, index lengths other than the number of boxes, an unknown `weights`, and
     min_angle_deg outside (0, 90]."""
-    from metro_pose3d_amd.heads import triangulate_joints, triangulation_min_det
-    from metro_pose3d_amd.inference import _engine_for
+    from metro_pose3d_amd.heads import triangulation_min_det
     triangulation_min_det(weights, min_angle_deg)
-    n_boxes = int(boxes.shape[0]) if isinstance(boxes, torch.Tensor) else len(np.asarray(boxes, np.float64).reshape(-1, 4))
+    n_boxes = _n_boxes(boxes)
     pi = np.asarray(_host_array(person_index), np.int64).reshape(-1)
     fi = np.asarray(_host_array(frame_index), np.int64).reshape(-1)
     if len(pi) != n_boxes or len(fi) != n_boxes:
         raise ValueError(f'person_index and frame_index must hold one value per box ({n_boxes}), got {len(pi)} and {len(fi)}')
     if n_boxes and pi.min() < 0:
         raise ValueError(f'person_index must not be negative, got {pi.min()}')
+    _check_rig(cameras, fi, n_boxes)
+    call = _checked_call(frames, boxes, fi, 'world', views, geometry, precision, check_finite, pixel_format, color_matrix,
+                         crop_dtype)
+    return _world_poses(call, model_path, cameras, fi, weights, min_angle_deg, person_index=pi)[0]
+
+
+def _n_boxes(boxes) -> int:
+    return int(boxes.shape[0]) if isinstance(boxes, torch.Tensor) else len(np.asarray(boxes, np.float64).reshape(-1, 4))
+
+
+def _check_rig(cameras, fi: np.ndarray, n_boxes: int) -> None:
+    """Several cameras need one calibrated Camera per frame, and every box a frame that has one."""
     if cameras is None:
         raise ValueError('triangulation needs calibrated cameras, one Camera per frame (cameras=None has none)')
     if isinstance(cameras, Camera):
@@ -1048,26 +1067,44 @@ def triangulate_poses_in_frames(frames, boxes, model_path, cameras, person_index
             raise ValueError('one Camera for several frames: triangulation needs one Camera per frame, each with its own R and t')
     elif n_boxes and (fi.min() < 0 or fi.max() >= len(cameras)):
         raise ValueError(f'frame_index must lie in [0, {len(cameras)}) (one Camera per frame), got [{fi.min()}, {fi.max()}]')
-    call = _checked_call(frames, boxes, fi, 'world', views, geometry, precision, check_finite, pixel_format, color_matrix,
-                         crop_dtype)
+
+
+def _world_poses(call: _Call, model_path, cameras, fi: np.ndarray, weights: str, min_angle_deg: float, person_index=None,
+                 match=None):
+    """The chain triangulate_poses_in_frames and match_poses_in_frames share -> (WorldPoses, None or (person_index, cost,
+    n_pairs)).  The persons' crop rows come from the host (person_index: person_groups, uploaded) or, with
+    match = (max_cost_mm, clip_mm, min_joints), from metro_view_affinity and metro_cluster_views on the forward's outputs; the
+    triangulation launch then runs over the upper bound of n persons and the count is read in the call's synchronisation."""
+    from metro_pose3d_amd.heads import cluster_views, triangulate_joints, view_affinity
+    from metro_pose3d_amd.inference import _engine_for
     sk = _model_skeleton(model_path)
     n, nv = len(call.boxes), len(call.vs.zoom)
     m = n * nv
-    rows, starts = person_groups(pi, fi, nv)
+    if match is not None and match[2] is not None and match[2] > sk.n_out:
+        raise ValueError(f'min_joints must be at most the {sk.n_out} output joints of the model, got {match[2]!r}')
     device = _call_device(call.boxes, call.frames)
     names = np.empty(sk.n_out, dtype=object)
     names[:] = sk.names_bytes()
     f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=device)
     if n == 0:
-        return WorldPoses(f32(0, sk.n_out, 3), torch.empty((0, sk.n_out), dtype=torch.int32, device=device), f32(0, sk.n_out),
-                          f32(0, sk.n_out, 2), sk.edges_array(), names)
+        return (WorldPoses(f32(0, sk.n_out, 3), i32(0, sk.n_out), f32(0, sk.n_out), f32(0, sk.n_out, 2), sk.edges_array(), names),
+                None if match is None else (i32(0), f32(0, 0), i32(0, 0)))
     moments = weights == 'covariance'
+    matched = n_persons = None
     with torch.cuda.device(device):
         eng = _engine_for(model_path, call.precision, device, m)
         crops, places = _warp_views(call.frames, cameras, call.boxes, call.fi, call.vs, eng.spec.proc_side, device, call.crop_dtype)
         rel, coords01, bad, *mom = _forward_coords01(eng, crops, call.check_finite, moments)
-        poses, n_rays, residual = triangulate_joints(coords01, mom[0][0] if moments else None, places.reshape(-1),
-                                                     _upload(rows, device), _upload(starts, device), eng.spec, weights,
+        cov01 = mom[0][0] if moments else None
+        if match is None:
+            rows, starts = (_upload(a, device) for a in person_groups(person_index, fi, nv))
+        else:
+            cost, n_pairs = view_affinity(coords01, cov01, places.reshape(-1), _upload(fi.astype(np.int32), device), eng.spec, nv,
+                                          weights, min_angle_deg, match[1], match[2])
+            labels, n_persons, rows, starts = cluster_views(cost, match[0], nv)
+            matched = (labels, cost, n_pairs)
+        poses, n_rays, residual = triangulate_joints(coords01, cov01, places.reshape(-1), rows, starts, eng.spec, weights,
                                                      min_angle_deg)
         poses_v, keypoints_v = f32(m, sk.n_out, 3), f32(m, sk.n_out, 2)
         mirror = _upload(np.asarray(sk.out_mirror, np.int32), device)
@@ -1077,8 +1114,66 @@ def triangulate_poses_in_frames(frames, boxes, model_path, cameras, person_index
                                             None, 0, None, None, len(sk.head_edges), ptr(mirror), COORDS['world'], ptr(poses_v),
                                             ptr(keypoints_v), None, C.c_void_p(stream)), 'metro_place_poses')
         keypoints = _merge_views(poses_v, keypoints_v, None, places, mirror, n, nv, spread=False)[1]
-        _raise_on_non_finite(eng.spec, call.precision, _synchronise(bad, call.boxes), m)    # the call's one stream synchronisation
-    return WorldPoses(poses, n_rays, residual, keypoints, sk.edges_array(), names)
+        n_bad = _synchronise(bad, call.boxes, n_persons)                                    # the call's one stream synchronisation
+        if match is not None:
+            n_bad, count = n_bad
+            poses, n_rays, residual = poses[:count], n_rays[:count], residual[:count]
+        _raise_on_non_finite(eng.spec, call.precision, n_bad, m)
+    return WorldPoses(poses, n_rays, residual, keypoints, sk.edges_array(), names), matched
+
+
+# ---- the same, with the persons found on the device: cross-view association (metro_view_affinity, metro_cluster_views) ----
+
+class MatchedPoses(NamedTuple):
+    """What match_poses_in_frames returns."""
+    person_index: torch.Tensor           # int32 [n] on the device: the person of every box, numbered by their lowest box
+    cost: torch.Tensor                   # float32 [n, n] mm: RMS distance between the rays of every two boxes (+inf: no match)
+    n_pairs: torch.Tensor                # int32 [n, n]: the ray pairs behind each cost
+    world: WorldPoses                    # triangulate_poses_in_frames' result for that person_index, P = the persons found
+
+
+def match_poses_in_frames(frames, boxes, model_path, cameras, frame_index, max_cost_mm: float = 200.0, clip_mm: float = 500.0,
+                          min_joints: Optional[int] = None, weights: str = 'covariance', min_angle_deg: float = 2.0, views=None,
+                          precision: Optional[str] = None, check_finite: Optional[bool] = None, geometry: str = 'auto',
+                          pixel_format: str = 'rgb', color_matrix: str = 'bt601', crop_dtype: str = 'float32') -> MatchedPoses:
+    """triangulate_poses_in_frames without a person_index: which boxes show the same person is decided on the device, from the
+    forward's own outputs, between the forward and the triangulation launch -> MatchedPoses(person_index int32 [n], cost
+    [n, n], n_pairs [n, n], world: WorldPoses with one row per person found).  Every other argument as there; a person
+    detector's boxes per camera, in any order, are enough.  At most 128 boxes.
+
+    Two boxes of different frames show the same person when their per-joint rays pass close to each other: cost[a][b] is the
+    RMS distance in mm between the rays of the same joint (heads.view_affinity: ray pairs within min_angle_deg of parallel
+    left out, each distance capped at clip_mm, a pair that meets behind a camera counted as clip_mm; weights 'covariance'
+    weighs each pair by its heat-maps' variances, and the moments are not requested in 'uniform' mode).  A cost from fewer
+    than min_joints joints (per view; None: half the output joints, rounded up) is +inf, as is that of two boxes on one
+    frame.  The boxes are then clustered (heads.cluster_views): the closest two clusters merge while their cost is below
+    max_cost_mm, the cost between clusters being the largest between their boxes (complete linkage), so every two boxes of
+    a person agree and no person has two boxes of one camera.  Persons are numbered by their lowest box.  A person seen by
+    one camera only is a person with NaN poses and n_rays 0, as in triangulate_poses_in_frames.  The merge order is greedy,
+    not an optimal assignment across cameras.
+    max_cost_mm = 200, clip_mm = 500 and the min_joints default are design choices, not measurements: 200 mm is below the
+    distance between two persons standing next to each other and above what calibration and heat-map error amount to at a
+    few metres; 500 mm keeps one wild joint from deciding a pair; half the joints keeps a cost from resting on a few.
+    One enqueue chain: triangulate_poses_in_frames' own, with one metro_view_affinity and one metro_cluster_views launch
+    between the forward and metro_triangulate_joints, which runs over n persons (the upper bound; the groups past the persons
+    found are empty); the call's one synchronisation stays the finite screen, which also brings the number of persons.
+    ValueError before any launch for cameras=None or one Camera for several frames, a frame_index out of range or not one
+    per box, more than 128 boxes, max_cost_mm, clip_mm, min_angle_deg or min_joints out of range and an unknown `weights`."""
+    from metro_pose3d_amd.heads import MATCH_MAX_BOXES, matching_params, triangulation_min_det
+    triangulation_min_det(weights, min_angle_deg)
+    matching_params(clip_mm, min_joints, max_cost_mm)
+    n_boxes = _n_boxes(boxes)
+    fi = np.asarray(_host_array(frame_index), np.int64).reshape(-1)
+    if len(fi) != n_boxes:
+        raise ValueError(f'frame_index must hold one value per box ({n_boxes}), got {len(fi)}')
+    if n_boxes > MATCH_MAX_BOXES:
+        raise ValueError(f'{n_boxes} boxes: matching takes at most {MATCH_MAX_BOXES} per call')
+    _check_rig(cameras, fi, n_boxes)
+    call = _checked_call(frames, boxes, fi, 'world', views, geometry, precision, check_finite, pixel_format, color_matrix,
+                         crop_dtype)
+    world, matched = _world_poses(call, model_path, cameras, fi, weights, min_angle_deg,
+                                  match=(float(max_cost_mm), float(clip_mm), None if min_joints is None else int(min_joints)))
+    return MatchedPoses(*matched, world)
 
 
 # ---- one camera over time: tracked poses smoothed by a Kalman filter / RTS pass (metro_smooth_tracks) ----

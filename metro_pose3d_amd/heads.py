@@ -7,6 +7,10 @@ through the C ABI (csrc/heads.hip).  Names and argument meaning follow the refer
   place_covariances         Cov01 -> mm^2 in output order and crop / camera / world axes, views averaged
   triangulate_joints        world joints of persons seen by several calibrated cameras: the point nearest to the rays of
                             their crops, uniform or heat-map-covariance weights (nothing in the reference: one camera each)
+  view_affinity             how close the per-joint rays of every two boxes of several cameras pass: the cost matrix of
+                            cross-view association (nothing in the reference: one camera each)
+  cluster_views             constrained complete-linkage clustering of that matrix: person_index and the CSR grouping
+                            triangulate_joints reads, all on the device
   smooth_tracks             poses of tracked persons over time: constant-velocity Kalman filter / RTS smoother per track and
                             joint, each row weighted by its heat-map covariance (nothing in the reference: one image each)
   backproject_bone_lengths  scale_recovery 'bone-lengths' / '-true'   volumetric.py:171-191,
@@ -184,6 +188,115 @@ def triangulate_joints(coords01: torch.Tensor, cov01: Optional[torch.Tensor], pl
                                        n_persons, C.byref(cs), _p(mirror), TRI_WEIGHTS[weights], min_det, _p(points), _p(n_rays),
                                        _p(residual), _stream(dev)), 'metro_triangulate_joints')
     return points, n_rays, residual
+
+
+MATCH_MAX_BOXES = _lib.METRO_MATCH_MAX_BOXES
+
+
+def _is_number(v) -> bool:
+    return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def matching_params(clip_mm, min_joints, *max_cost_mm):
+    """Checks `clip_mm`, `min_joints` (None, or an integer >= 1) and, if given, `max_cost_mm` of the matching calls."""
+    for name, v in (('clip_mm', clip_mm),) + tuple(('max_cost_mm', v) for v in max_cost_mm):
+        if not _is_number(v) or not np.isfinite(v) or not v > 0:
+            raise ValueError(f'{name} must be a finite number > 0 (mm), got {v!r}')
+    if min_joints is not None and (isinstance(min_joints, (bool, np.bool_)) or not isinstance(min_joints, (int, np.integer))
+                                   or min_joints < 1):
+        raise ValueError(f'min_joints must be None or an integer >= 1, got {min_joints!r}')
+
+
+def _check_n_views(n_views, rows: int) -> int:
+    if isinstance(n_views, (bool, np.bool_)) or not isinstance(n_views, (int, np.integer)) or not 1 <= n_views <= _lib.METRO_MAX_VIEWS:
+        raise ValueError(f'n_views must be an integer from 1 to {_lib.METRO_MAX_VIEWS}, got {n_views!r}')
+    if rows % int(n_views):
+        raise ValueError(f'{rows} rows are not a whole number of boxes of {n_views} views')
+    return int(n_views)
+
+
+def view_affinity(coords01: torch.Tensor, cov01: Optional[torch.Tensor], places: torch.Tensor, frame_index, spec: ModelSpec,
+                  n_views: int = 1, weights: str = 'covariance', min_angle_deg: float = 2.0, clip_mm: float = 500.0,
+                  min_joints: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """How close the per-joint rays of every two boxes pass, one metro_view_affinity launch: the cost of calling two boxes
+    of different cameras the same person.  coords01 [m,J_head,3], cov01 [m,J_head,6] (weights 'covariance') and `places`
+    (m MetroPlacement records, uint8) as triangulate_joints reads them, m = n * n_views crop rows, box-major; frame_index [n]
+    (ints or a tensor): the frame (camera) of each box.  -> (cost float32 [n,n] mm, n_pairs int32 [n,n]) on the device.
+    Per pair of boxes, every (view, output joint) gives one pair of rays -- triangulate_joints' rays, the mirror joint for a
+    flipped view -- and the distance at which their lines pass; pairs within min_angle_deg of parallel are left out, pairs
+    that meet behind a camera count with clip_mm, every distance is capped at clip_mm.  cost is the RMS of these distances,
+    each weighted ('covariance') by 1 / (sigma_a^2 t_a^2 + sigma_b^2 t_b^2), the heat-map variances carried to where the rays
+    pass.  +inf on the diagonal, for two boxes on one frame (a person appears once per camera) and where fewer than
+    min_joints * n_views ray pairs count (min_joints None: (Jout + 1) // 2).  At most 128 boxes."""
+    triangulation_min_det(weights, min_angle_deg)
+    matching_params(clip_mm, min_joints)
+    nj, n_out = spec.skeleton.n_head, spec.skeleton.n_out
+    if not isinstance(coords01, torch.Tensor) or coords01.dim() != 3 or tuple(coords01.shape[1:]) != (nj, 3):
+        raise ValueError(f'coords01 must be a tensor [m,{nj},3], got {tuple(getattr(coords01, "shape", ()))}')
+    m = coords01.shape[0]
+    n_views = _check_n_views(n_views, m)
+    n = m // n_views
+    if n > MATCH_MAX_BOXES:
+        raise ValueError(f'{n} boxes: matching takes at most {MATCH_MAX_BOXES}')
+    if min_joints is None:
+        min_joints = (n_out + 1) // 2
+    if min_joints > n_out:
+        raise ValueError(f'min_joints must be at most the {n_out} output joints, got {min_joints!r}')
+    if weights == 'covariance' and (cov01 is None or tuple(cov01.shape) != (m, nj, 6)):
+        raise ValueError(f"weights='covariance' needs cov01 [{m},{nj},6], got {None if cov01 is None else tuple(cov01.shape)}")
+    need = m * C.sizeof(_lib.MetroPlacement)
+    if not isinstance(places, torch.Tensor) or places.dtype != torch.uint8 or places.numel() != need:
+        raise ValueError(f'places must be a uint8 tensor of {m} MetroPlacement records ({need} bytes)')
+    n_fi = int(frame_index.numel() if isinstance(frame_index, torch.Tensor) else np.asarray(frame_index).size)
+    if n_fi != n:
+        raise ValueError(f'frame_index must hold one value per box ({n}), got {n_fi}')
+    dev = coords01.device
+    cost = torch.empty((n, n), dtype=torch.float32, device=dev)
+    n_pairs = torch.empty((n, n), dtype=torch.int32, device=dev)
+    if n == 0:
+        return cost, n_pairs
+    lib = _lib.load()
+    fi = _i32(frame_index, dev).reshape(-1)
+    coords01, places = coords01.to(torch.float32).contiguous(), places.contiguous()
+    cov01 = cov01.to(torch.float32).contiguous() if weights == 'covariance' else None
+    cs = spec.to_c(1)
+    mirror = torch.from_numpy(np.asarray(spec.skeleton.out_mirror, dtype=np.int32)).to(dev)
+    min_sin2 = float(np.sin(np.radians(float(min_angle_deg))) ** 2)
+    check(lib.metro_view_affinity(_p(coords01), _p(cov01), _p(places), C.byref(cs), _p(mirror), _p(fi), n, n_views,
+                                  TRI_WEIGHTS[weights], min_sin2, float(clip_mm), int(min_joints) * n_views, _p(cost), _p(n_pairs),
+                                  _stream(dev)), 'metro_view_affinity')
+    return cost, n_pairs
+
+
+def cluster_views(cost: torch.Tensor, max_cost_mm: float, n_views: int = 1):
+    """Boxes -> persons by constrained complete-linkage clustering of view_affinity's cost, one metro_cluster_views launch (one
+    workgroup, the matrix in LDS).  cost [n,n] on the device is read as max(cost, cost^T) with NaN as +inf.  Every box starts
+    as its own cluster; the two clusters with the smallest cost merge (ties: the lowest box index of the first, then of the
+    second) while that cost is < max_cost_mm, the cost between clusters being the LARGEST cost between their boxes: every two
+    boxes of a person agree, and since two boxes of one frame cost +inf a person never gets two boxes of one camera.
+    -> (person_index int32 [n], persons numbered by their lowest box; n_persons int32 [1]; rows int32 [n * n_views] and
+    starts int32 [n + 1]: the CSR grouping triangulate_joints reads, with n as its person count), all on the device.  A person
+    with several boxes owns the crop rows i * n_views + v of its boxes in ascending order; a person with one box, and the
+    persons >= n_persons, have empty groups; rows past starts[n] are -1.  At most 128 boxes."""
+    if not _is_number(max_cost_mm) or not max_cost_mm > 0:
+        raise ValueError(f'max_cost_mm must be a number > 0 (mm), got {max_cost_mm!r}')
+    if not isinstance(cost, torch.Tensor) or cost.dim() != 2 or cost.shape[0] != cost.shape[1]:
+        raise ValueError(f'cost must be a square tensor [n,n], got {tuple(getattr(cost, "shape", ()))}')
+    n = int(cost.shape[0])
+    if n > MATCH_MAX_BOXES:
+        raise ValueError(f'{n} boxes: matching takes at most {MATCH_MAX_BOXES}')
+    n_views = _check_n_views(n_views, 0)
+    dev = cost.device
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    person_index, n_persons, rows, starts = i32(n), i32(1), i32(n * n_views), i32(n + 1)
+    if n == 0:
+        n_persons.zero_()
+        starts.zero_()
+        return person_index, n_persons, rows, starts
+    cost = cost.to(torch.float32).contiguous()
+    check(_lib.load().metro_cluster_views(_p(cost), n, n_views, float(max_cost_mm), _p(person_index), _p(n_persons), _p(rows),
+                                          _p(starts), _stream(dev)), 'metro_cluster_views')
+    return person_index, n_persons, rows, starts
 
 
 SMOOTH_MODES = {'filter': _lib.METRO_SMOOTH_FILTER, 'smooth': _lib.METRO_SMOOTH_RTS}
