@@ -779,6 +779,63 @@ int  metro_smooth_tracks(const float* d_poses, const float* d_cov, const double*
                          double* d_state, void* d_workspace, float* d_poses_out, float* d_velocity_out, float* d_cov_out,
                          uint8_t* d_used_out, void* stream);
 
+/* ---- which box of a video continues which track: frame-to-frame association on the device ----
+ * Nothing in the reference: one example is one image, and a person detector gives boxes per frame, unordered, with no
+ * identity from one frame to the next.  One launch of one workgroup (256 threads, the cost matrix in LDS) between the forward
+ * and metro_smooth_tracks, no host work in between; fp64 arithmetic on the fp32 inputs.  J = spec->n_joints_out (nothing else
+ * of the spec is read).
+ * d_poses fp32 [n, J, 3] mm, ABSOLUTE (root-relative poses of different persons coincide); d_cov fp32 [n, J, 9] mm^2, read by
+ * METRO_SMOOTH_COVARIANCE only, else may be NULL; d_times fp64 [n] seconds: metro_smooth_tracks' inputs.
+ * Time steps (CSR, built on the host): step s owns the boxes d_step_rows[d_step_starts[s] : d_step_starts[s + 1]],
+ * d_step_rows int32 [n_step_rows] indices into the n rows, d_step_starts int32 [n_steps + 1]; the steps are in ascending
+ * time and all boxes of one timestamp form one step; every row is listed at most once.  The time t_s of a step is that of its
+ * first listed row in [0, n); a step without one is skipped.  An index outside [0, n) is skipped as if it were not listed
+ * (it keeps its position in the step), d_step_starts is clamped to [0, n_step_rows], and of a step with more than
+ * METRO_ASSOC_MAX positions only the first METRO_ASSOC_MAX are read: the kernel reads and writes nothing out of bounds.  A
+ * row in no step, or past that limit, is untracked and counted nowhere.
+ * Track table, n_tracks = T <= METRO_ASSOC_MAX slots: d_state fp64 [T, J, 28], metro_smooth_tracks' carried state;
+ * d_ids int32 [T], the persistent id of the track in each slot, -1: the slot is free; d_next_id int32 [1], the next id to
+ * give.  A slot is LIVE iff some joint's t_last is not NaN; its last-seen time is the largest such t_last.
+ * d_workspace: metro_associate_tracks_workspace_bytes(T, J) bytes = T J 28 fp64, the WORKING state: a copy of d_state made
+ * at the start of the launch that the launch advances and leaves behind; it is exchanged only within the workgroup.
+ * At the start: a live slot whose last-seen time is < t_first - max_age_s (t_first the time of the first step that has one)
+ * is RETIRED: every joint's t_last becomes NaN in d_state and in the working state, and its id -1.  This is the only write
+ * to d_state; it makes the smoothing launch that follows start a reborn slot afresh.  A slot that is not live is free: its
+ * id becomes -1.  No slot is retired inside a call, so a slot never holds two tracks within one group of the CSR below.
+ * Then per step, in order:
+ * 1. cost[t][b] of slot t continuing in box b: over the joints j whose working t_last[j] is not NaN and whose measurement
+ *    z = d_poses[b, j] is finite, with dt = max(t_s - t_last[j], 0) and the working x = (p, v):
+ *    d_j = min(|z - (p + dt v)|, clip_mm); cost = sqrt(mean d_j^2), rounded once to fp32.  +inf with fewer than min_joints
+ *    such joints, or if the slot's last-seen time is < t_s - max_age_s (a free slot has no such joint).
+ * 2. Greedy one-to-one assignment on the fp32 costs: take the smallest remaining cost -- ties go to the lowest slot, then
+ *    to the lowest position in the step -- and unless it is < max_cost_mm stop; else that box continues that slot, and the
+ *    slot's row and the box's column are struck out.
+ * 3. Births: the unassigned boxes that have at least one finite joint, in step order, take the free slots in ascending
+ *    order, each with ids[slot] = next_id++.  A box for which no free slot is left, or without a finite joint, is UNTRACKED.
+ * 4. Filter: every slot that received a box advances its working state, per joint, by exactly the per-row step of
+ *    metro_smooth_tracks (start, predict, update, missing, gated; measurement, q, r_floor, cov_scale, v0 and gate as there;
+ *    t_prev the joint's t_last, the row's time its d_times).  A joint with no state and an unusable measurement stays as it is.
+ * Outputs: d_track_index_out int32 [n] the slot of each box, -1 untracked; d_track_id_out int32 [n] the id, -1 untracked;
+ * d_cost_out fp32 [n] the accepted cost of a box that continues a track, NaN for births and untracked boxes; the CSR grouping
+ * metro_smooth_tracks reads with T as its track count and n as its n_rows: d_starts_out int32 [T + 1], d_rows_out int32 [n],
+ * slot t owning its boxes in time order, the entries from d_starts_out[T] on -1; d_n_new_out int32 [1] the births,
+ * d_n_dropped_out int32 [1] the untracked boxes of the steps; d_ids and d_next_id updated in place.  Running
+ * metro_smooth_tracks (either mode) on that CSR with d_state leaves in d_state, bit for bit, the working state.
+ * -1 before any launch for a NULL spec, J outside [1, METRO_MAX_JOINTS], a bad measurement, negative n / n_step_rows /
+ * n_steps, n_tracks outside [1, METRO_ASSOC_MAX], q <= 0, r_floor <= 0, v0 <= 0, cov_scale < 0, gate < 0, max_cost_mm <= 0,
+ * clip_mm <= 0, max_age_s < 0 (or any of them NaN), min_joints outside [1, J], and, with n, n_step_rows and n_steps all > 0,
+ * a NULL pointer (d_cov only in covariance mode).  n == 0, n_step_rows == 0 or n_steps == 0 launches nothing, writes nothing
+ * and returns 0. */
+#define METRO_ASSOC_MAX 128
+size_t metro_associate_tracks_workspace_bytes(int32_t n_tracks, int32_t n_joints_out);
+int  metro_associate_tracks(const float* d_poses, const float* d_cov, const double* d_times, int32_t n,
+                            const int32_t* d_step_rows, int32_t n_step_rows, const int32_t* d_step_starts, int32_t n_steps,
+                            const MetroSpec* spec, int32_t measurement, double q, double r_floor, double cov_scale, double v0,
+                            double gate, float max_cost_mm, double clip_mm, int32_t min_joints, double max_age_s,
+                            double* d_state, int32_t n_tracks, int32_t* d_ids, int32_t* d_next_id, void* d_workspace,
+                            int32_t* d_track_index_out, int32_t* d_track_id_out, float* d_cost_out, int32_t* d_rows_out,
+                            int32_t* d_starts_out, int32_t* d_n_new_out, int32_t* d_n_dropped_out, void* stream);
+
 const char* metro_last_error(void);
 int32_t metro_abi_version(void);
 

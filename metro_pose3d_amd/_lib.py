@@ -97,6 +97,7 @@ METRO_TRI_UNIFORM, METRO_TRI_COVARIANCE = 0, 1
 METRO_MATCH_MAX_BOXES = 128
 METRO_SMOOTH_FILTER, METRO_SMOOTH_RTS = 0, 1
 METRO_SMOOTH_ISOTROPIC, METRO_SMOOTH_COVARIANCE = 0, 1
+METRO_ASSOC_MAX = 128
 
 
 class MetroViewBase(C.Structure):
@@ -195,6 +196,10 @@ SIGNATURES = {
     'metro_smooth_tracks_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
     'metro_smooth_tracks': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.POINTER(MetroSpec), C.c_int32, C.c_int32,
                                       C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, _P]),
+    'metro_associate_tracks_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
+    'metro_associate_tracks': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.POINTER(MetroSpec), C.c_int32,
+                                         C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float, C.c_double, C.c_int32,
+                                         C.c_double, _P, C.c_int32] + [_P] * 11),
     'metro_last_error': (C.c_char_p, []),
     'metro_abi_version': (C.c_int32, []),
 }

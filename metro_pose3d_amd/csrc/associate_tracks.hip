@@ -1,0 +1,421 @@
+// Which box of a video continues which track, decided on the device between the forward and metro_smooth_tracks, in ONE launch
+// of ONE workgroup (metro_associate_tracks, include/metro_hip.h, which is the specification).  Nothing in the reference to
+// restate: one example is one image, and a person detector gives boxes per frame with no identity from frame to frame.
+// The launch walks the call's boxes step by step (all boxes of one timestamp are one step, the CSR of the steps is built on
+// the host, frames.time_steps) over a table of T <= 128 track slots whose filter state is the smoother's own [T][J][28]:
+//   begin     a working copy of the state goes to the caller's workspace; a live slot last seen before
+//             t_first - max_age is retired (t_last = NaN in the state and the copy, id -1), a slot that is not live is free
+//   cost      per (slot, box of the step): the RMS over the joints of min(|z - (p + dt v)|, clip), one rounding to fp32;
+//             +inf with fewer than min_joints joints or a slot last seen before t_step - max_age
+//   assign    greedy one-to-one: the smallest remaining cost (ties: lowest slot, then lowest position in the step) while it
+//             is < max_cost; its row and its column of the matrix become +inf
+//   births    the unassigned boxes with a finite joint, in step order, take the lowest free slots and the next ids
+//   filter    every slot that received a box advances its working state by smooth_filter_row (smooth_step.h), the per-row
+//             step of smooth_tracks.hip
+// and then writes the CSR per slot that metro_smooth_tracks reads.  The cost matrix lives in LDS: 128 rows of 129 floats
+// (64.5 KiB of the CU's 160 KiB; the odd row stride keeps the column walk of the strike off a single bank).  The working
+// state lives in global memory and is exchanged only within the workgroup, across __syncthreads().
+// The steps below take (tid, nt): thread tid of nt covers the items tid, tid + nt, ...  The kernel calls them with its 256
+// threads and a workgroup barrier between steps; tests/test_follow_tracks.py runs the same steps on the host with one thread.
+// fp64 arithmetic on the fp32 inputs, no FMA contraction.
+#include "metro_common.h"
+#include "smooth_step.h"
+
+#pragma clang fp contract(off)
+
+namespace metro {
+
+constexpr int ASSOC_MAX = METRO_ASSOC_MAX;               // boxes per step, and track slots
+constexpr int ASSOC_LD = ASSOC_MAX + 1;                  // row stride of the cost matrix, in floats
+constexpr int ASSOC_THREADS = 256;
+
+struct AssocArgs {
+    const float* poses;      // [n][J][3] mm, absolute
+    const float* cov;        // [n][J][9] mm^2 (METRO_SMOOTH_COVARIANCE)
+    const double* times;     // [n] s
+    const int* step_rows;    // [n_step_rows] indices into the n pose rows
+    const int* step_starts;  // [n_steps + 1]
+    double* state;           // [T][J][28]: only the retirement writes it
+    int* ids;                // [T]
+    int* next_id;            // [1]
+    double* ws;              // [T][J][28] working copy of the state
+    int* track_index;        // [n]
+    int* track_id;           // [n]
+    float* cost_out;         // [n]
+    int* rows_out;           // [n]
+    int* starts_out;         // [T + 1]
+    int* n_new;              // [1]
+    int* n_dropped;          // [1]
+    int n, n_step_rows, n_steps, n_tracks, n_out, measurement, min_joints;
+    double q, r2, cov_scale, v02, gate, clip, max_age;
+    float max_cost;
+};
+
+struct AssocCand { float v; int idx; };                  // idx = slot * ASSOC_LD + position: its order is (slot, position)'s
+
+// what the workgroup keeps in LDS (the host test keeps it on its heap)
+struct AssocLds {
+    float c[ASSOC_MAX * ASSOC_LD];                       // cost[slot][position in the step]
+    float box_cost[ASSOC_MAX];                           // the accepted cost of a matched box, else NaN
+    int box_row[ASSOC_MAX];                              // the pose row of a position, -1: not in [0, n)
+    int box_any[ASSOC_MAX];                              // the box has a finite joint
+    int box_slot[ASSOC_MAX];                             // the slot of the box, -1: none (yet)
+    int born_slot[ASSOC_MAX], born_id[ASSOC_MAX];        // births decided, not yet applied
+    int ids[ASSOC_MAX], count[ASSOC_MAX], fill[ASSOC_MAX], start[ASSOC_MAX + 1];
+    int next_id, n_new, n_dropped;
+};
+
+__host__ __device__ inline bool assoc_cand_less(const AssocCand& x, const AssocCand& y) {
+    return x.v < y.v || (x.v == y.v && x.idx < y.idx);
+}
+
+// step s owns the positions lo .. lo + m - 1 of step_rows: the starts clamped to [0, n_step_rows], at most 128 positions
+__host__ __device__ inline void assoc_step_range(const AssocArgs& a, int s, int& lo, int& m) {
+    lo = a.step_starts[s];
+    int hi = a.step_starts[s + 1];
+    if (lo < 0) lo = 0;
+    if (hi > a.n_step_rows) hi = a.n_step_rows;
+    m = hi - lo;
+    if (m < 0) m = 0;
+    if (m > ASSOC_MAX) m = ASSOC_MAX;
+}
+
+// the time of a step is that of its first row in [0, n); false: it has none, the step is skipped
+__host__ __device__ inline bool assoc_step_time(const AssocArgs& a, int lo, int m, double& t) {
+    for (int k = 0; k < m; ++k) {
+        const int row = a.step_rows[lo + k];
+        if ((unsigned)row < (unsigned)a.n) {
+            t = a.times[row];
+            return true;
+        }
+    }
+    return false;
+}
+
+__host__ __device__ inline bool assoc_first_time(const AssocArgs& a, double& t) {
+    for (int s = 0; s < a.n_steps; ++s) {
+        int lo, m;
+        assoc_step_range(a, s, lo, m);
+        if (assoc_step_time(a, lo, m, t)) return true;
+    }
+    return false;
+}
+
+__host__ __device__ inline double* assoc_slot_state(const AssocArgs& a, double* base, int slot, int j) {
+    return base + ((size_t)slot * a.n_out + j) * SMOOTH_STATE_DOUBLES;
+}
+
+// the working copy of the state, every box untracked until a step says otherwise, the table into LDS
+__host__ __device__ inline void assoc_begin(const AssocArgs& a, AssocLds& l, int tid, int nt) {
+    const size_t total = (size_t)a.n_tracks * a.n_out * SMOOTH_STATE_DOUBLES;
+    for (size_t i = tid; i < total; i += nt) a.ws[i] = a.state[i];
+    for (int i = tid; i < a.n; i += nt) {
+        a.track_index[i] = -1;
+        a.track_id[i] = -1;
+        a.cost_out[i] = __builtin_nanf("");
+    }
+    for (int t = tid; t < a.n_tracks; t += nt) {
+        l.ids[t] = a.ids[t];
+        l.count[t] = 0;
+        l.fill[t] = 0;
+    }
+    if (tid == 0) {
+        l.next_id = a.next_id[0];
+        l.n_new = 0;
+        l.n_dropped = 0;
+    }
+}
+
+// a live slot last seen before t_first - max_age is retired; a slot that is not live is free
+__host__ __device__ inline void assoc_retire(const AssocArgs& a, AssocLds& l, bool have_first, double t_first, int tid, int nt) {
+    for (int t = tid; t < a.n_tracks; t += nt) {
+        bool live = false;
+        double seen = -__builtin_inf();
+        for (int j = 0; j < a.n_out; ++j) {
+            const double tl = assoc_slot_state(a, a.ws, t, j)[27];
+            if (tl != tl) continue;
+            live = true;
+            if (tl > seen) seen = tl;
+        }
+        if (live && have_first && seen < t_first - a.max_age) {
+            for (int j = 0; j < a.n_out; ++j)
+                assoc_slot_state(a, a.ws, t, j)[27] = assoc_slot_state(a, a.state, t, j)[27] = __builtin_nan("");
+            live = false;
+        }
+        if (!live) l.ids[t] = -1;
+    }
+}
+
+// the boxes of the step: their rows, whether a joint is finite, nobody assigned
+__host__ __device__ inline void assoc_step_boxes(const AssocArgs& a, AssocLds& l, int lo, int m, int tid, int nt) {
+    for (int k = tid; k < m; k += nt) {
+        const int row = a.step_rows[lo + k];
+        const bool valid = (unsigned)row < (unsigned)a.n;
+        int any = 0;
+        if (valid) {
+            const float* z = a.poses + (size_t)row * a.n_out * 3;
+            for (int j = 0; j < a.n_out; ++j)
+                any |= __builtin_isfinite(z[j * 3]) && __builtin_isfinite(z[j * 3 + 1]) && __builtin_isfinite(z[j * 3 + 2]);
+        }
+        l.box_row[k] = valid ? row : -1;
+        l.box_any[k] = any;
+        l.box_slot[k] = -1;
+        l.box_cost[k] = __builtin_nanf("");
+    }
+}
+
+// the cost of slot `slot` continuing in pose row `row` at the step's time
+__host__ __device__ inline float assoc_pair_cost(const AssocArgs& a, int slot, int row, double t_step) {
+    double sum = 0.0, seen = -__builtin_inf();
+    int cnt = 0;
+    for (int j = 0; j < a.n_out; ++j) {
+        const double* st = assoc_slot_state(a, a.ws, slot, j);
+        const double tl = st[27];
+        if (tl != tl) continue;
+        if (tl > seen) seen = tl;
+        const float* z = a.poses + ((size_t)row * a.n_out + j) * 3;
+        if (!(__builtin_isfinite(z[0]) && __builtin_isfinite(z[1]) && __builtin_isfinite(z[2]))) continue;
+        double dt = t_step - tl;
+        if (!(dt > 0.0)) dt = 0.0;
+        const double e0 = (double)z[0] - (st[0] + dt * st[3]), e1 = (double)z[1] - (st[1] + dt * st[4]),
+                     e2 = (double)z[2] - (st[2] + dt * st[5]);
+        double d = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
+        if (!(d <= a.clip)) d = a.clip;
+        sum += d * d;
+        ++cnt;
+    }
+    if (cnt < a.min_joints || cnt < 1 || seen < t_step - a.max_age) return __builtin_inff();
+    return (float)sqrt(sum / (double)cnt);
+}
+
+__host__ __device__ inline void assoc_costs(const AssocArgs& a, AssocLds& l, int m, double t_step, int tid, int nt) {
+    const int dq = nt / m, dr = nt - dq * m;
+    int t = tid / m, k = tid - t * m;
+    while (t < a.n_tracks) {
+        l.c[t * ASSOC_LD + k] = l.box_row[k] >= 0 ? assoc_pair_cost(a, t, l.box_row[k], t_step) : __builtin_inff();
+        t += dq;
+        k += dr;
+        if (k >= m) { k -= m; ++t; }
+    }
+}
+
+// this thread's smallest (value, slot, position)
+__host__ __device__ inline AssocCand assoc_scan(const AssocLds& l, int n_tracks, int m, int tid, int nt) {
+    AssocCand best = {__builtin_inff(), 0x7fffffff};
+    const int dq = nt / m, dr = nt - dq * m;
+    int t = tid / m, k = tid - t * m;
+    while (t < n_tracks) {
+        const AssocCand x = {l.c[t * ASSOC_LD + k], t * ASSOC_LD + k};
+        if (assoc_cand_less(x, best)) best = x;
+        t += dq;
+        k += dr;
+        if (k >= m) { k -= m; ++t; }
+    }
+    return best;
+}
+
+// the pick (slot t, position k): the box is the slot's, its row and its column leave the matrix
+__host__ __device__ inline void assoc_strike(AssocLds& l, int n_tracks, int m, AssocCand best, int tid, int nt) {
+    const int t = best.idx / ASSOC_LD, k = best.idx - t * ASSOC_LD;
+    const int span = n_tracks > m ? n_tracks : m;
+    for (int i = tid; i < span; i += nt) {
+        if (i < m) l.c[t * ASSOC_LD + i] = __builtin_inff();
+        if (i < n_tracks) l.c[i * ASSOC_LD + k] = __builtin_inff();
+    }
+    if (tid == 0) {
+        l.box_slot[k] = t;
+        l.box_cost[k] = best.v;
+    }
+}
+
+// the r-th unassigned box with a finite joint takes the r-th free slot and the id next_id + r
+__host__ __device__ inline void assoc_births(const AssocArgs& a, AssocLds& l, int m, int tid, int nt) {
+    for (int k = tid; k < m; k += nt) {
+        l.born_slot[k] = -1;
+        l.born_id[k] = -1;
+        if (l.box_row[k] < 0 || l.box_slot[k] >= 0 || !l.box_any[k]) continue;
+        int r = 0;
+        for (int i = 0; i < k; ++i) r += l.box_row[i] >= 0 && l.box_slot[i] < 0 && l.box_any[i];
+        int free_seen = 0;
+        for (int t = 0; t < a.n_tracks; ++t) {
+            if (l.ids[t] >= 0) continue;
+            if (free_seen == r) {
+                l.born_slot[k] = t;
+                l.born_id[k] = l.next_id + r;
+                break;
+            }
+            ++free_seen;
+        }
+    }
+}
+
+// the births into the table, the counters, and the step's outputs per box
+__host__ __device__ inline void assoc_apply(const AssocArgs& a, AssocLds& l, int m, int tid, int nt) {
+    if (tid == 0) {                                        // reads only what this step no longer writes
+        int born = 0, untracked = 0;
+        for (int k = 0; k < m; ++k) {
+            if (l.box_row[k] < 0) continue;
+            const bool matched = l.box_cost[k] == l.box_cost[k];
+            born += l.born_slot[k] >= 0;
+            untracked += !matched && l.born_slot[k] < 0;
+        }
+        l.next_id += born;
+        l.n_new += born;
+        l.n_dropped += untracked;
+    }
+    for (int k = tid; k < m; k += nt) {
+        const int row = l.box_row[k];
+        if (row < 0) continue;
+        int slot = l.box_slot[k];
+        if (l.born_slot[k] >= 0) {
+            slot = l.born_slot[k];
+            l.box_slot[k] = slot;
+            l.ids[slot] = l.born_id[k];
+        }
+        if (slot < 0) continue;                            // untracked: as assoc_begin left it
+        a.track_index[row] = slot;
+        a.track_id[row] = l.ids[slot];
+        a.cost_out[row] = l.box_cost[k];
+        l.count[slot] += 1;                                // one box per slot and step: no other thread is here
+    }
+}
+
+// every slot that received a box advances its working state, one (box, joint) per item
+__host__ __device__ inline void assoc_filter(const AssocArgs& a, const AssocLds& l, int m, int tid, int nt) {
+    for (int i = tid; i < m * a.n_out; i += nt) {
+        const int k = i / a.n_out, j = i - k * a.n_out;
+        const int slot = l.box_slot[k], row = l.box_row[k];
+        if (slot < 0 || row < 0) continue;
+        double* st = assoc_slot_state(a, a.ws, slot, j);
+        SmoothKf s, pred;
+        double t_prev = 0.0;
+        bool have = smooth_state_load(st, s, t_prev), used;
+        if (smooth_filter_row(a, (size_t)row * a.n_out + j, a.times[row], s, pred, t_prev, have, used)) smooth_state_store(st, s, t_prev);
+    }
+}
+
+// the CSR offsets from the boxes each slot received
+__host__ __device__ inline void assoc_starts(const AssocArgs& a, AssocLds& l, int tid, int nt) {
+    if (tid != 0) return;
+    int at = 0;
+    for (int t = 0; t < a.n_tracks; ++t) {
+        l.start[t] = a.starts_out[t] = at;
+        at += l.count[t];
+    }
+    l.start[a.n_tracks] = a.starts_out[a.n_tracks] = at;
+}
+
+// the step's tracked boxes into their slots' groups: steps come in time order, so every group is time-sorted
+__host__ __device__ inline void assoc_group_step(const AssocArgs& a, AssocLds& l, int lo, int m, int tid, int nt) {
+    for (int k = tid; k < m; k += nt) {
+        const int row = a.step_rows[lo + k];
+        if ((unsigned)row >= (unsigned)a.n) continue;
+        const int slot = a.track_index[row];
+        if ((unsigned)slot >= (unsigned)a.n_tracks) continue;
+        const int at = l.start[slot] + l.fill[slot];
+        if (at < l.start[slot + 1] && at < a.n) a.rows_out[at] = row;
+        l.fill[slot] += 1;
+    }
+}
+
+__host__ __device__ inline void assoc_finish(const AssocArgs& a, const AssocLds& l, int tid, int nt) {
+    for (int i = l.start[a.n_tracks] + tid; i < a.n; i += nt) a.rows_out[i] = -1;
+    for (int t = tid; t < a.n_tracks; t += nt) a.ids[t] = l.ids[t];
+    if (tid == 0) {
+        a.next_id[0] = l.next_id;
+        a.n_new[0] = l.n_new;
+        a.n_dropped[0] = l.n_dropped;
+    }
+}
+
+__global__ __launch_bounds__(ASSOC_THREADS) void associate_tracks_kernel(AssocArgs a) {
+    __shared__ AssocLds l;
+    __shared__ AssocCand wave_best[ASSOC_THREADS / 64];
+    const int tid = threadIdx.x, nt = ASSOC_THREADS;
+    assoc_begin(a, l, tid, nt);
+    __syncthreads();
+    double t_first = 0.0;
+    const bool have_first = assoc_first_time(a, t_first);
+    assoc_retire(a, l, have_first, t_first, tid, nt);
+    __syncthreads();
+    for (int s = 0; s < a.n_steps; ++s) {                  // every branch below is taken by all threads or by none
+        int lo, m;
+        double t_step;
+        assoc_step_range(a, s, lo, m);
+        if (!assoc_step_time(a, lo, m, t_step)) continue;
+        assoc_step_boxes(a, l, lo, m, tid, nt);
+        __syncthreads();
+        assoc_costs(a, l, m, t_step, tid, nt);
+        __syncthreads();
+        const int rounds = a.n_tracks < m ? a.n_tracks : m;
+        for (int round = 0; round < rounds; ++round) {
+            AssocCand best = assoc_scan(l, a.n_tracks, m, tid, nt);
+            for (int off = 32; off > 0; off >>= 1) {
+                const AssocCand other = {__shfl_xor(best.v, off), __shfl_xor(best.idx, off)};
+                if (assoc_cand_less(other, best)) best = other;
+            }
+            if ((tid & 63) == 0) wave_best[tid >> 6] = best;
+            __syncthreads();
+            best = wave_best[0];
+            for (int w = 1; w < ASSOC_THREADS / 64; ++w)
+                if (assoc_cand_less(wave_best[w], best)) best = wave_best[w];
+            if (!(best.v < a.max_cost)) break;             // the same value in every thread
+            assoc_strike(l, a.n_tracks, m, best, tid, nt);
+            __syncthreads();                               // also: wave_best is read before it is written again
+        }
+        assoc_births(a, l, m, tid, nt);
+        __syncthreads();
+        assoc_apply(a, l, m, tid, nt);
+        __syncthreads();
+        assoc_filter(a, l, m, tid, nt);
+        __syncthreads();                                   // the working state and the box arrays, before the next step
+    }
+    assoc_starts(a, l, tid, nt);
+    __syncthreads();
+    for (int s = 0; s < a.n_steps; ++s) {
+        int lo, m;
+        assoc_step_range(a, s, lo, m);
+        if (m == 0) continue;
+        assoc_group_step(a, l, lo, m, tid, nt);
+        __syncthreads();
+    }
+    assoc_finish(a, l, tid, nt);
+}
+
+AssocArgs make_assoc_args(const float* poses, const float* cov, const double* times, int n, const int* step_rows, int n_step_rows,
+                          const int* step_starts, int n_steps, int n_out, int measurement, double q, double r_floor, double cov_scale,
+                          double v0, double gate, float max_cost_mm, double clip_mm, int min_joints, double max_age_s, double* state,
+                          int n_tracks, int* ids, int* next_id, double* ws, int* track_index, int* track_id, float* cost_out,
+                          int* rows_out, int* starts_out, int* n_new, int* n_dropped) {
+    AssocArgs a;
+    a.poses = poses; a.cov = cov; a.times = times; a.step_rows = step_rows; a.step_starts = step_starts;
+    a.state = state; a.ids = ids; a.next_id = next_id; a.ws = ws;
+    a.track_index = track_index; a.track_id = track_id; a.cost_out = cost_out; a.rows_out = rows_out; a.starts_out = starts_out;
+    a.n_new = n_new; a.n_dropped = n_dropped;
+    a.n = n; a.n_step_rows = n_step_rows; a.n_steps = n_steps; a.n_tracks = n_tracks; a.n_out = n_out;
+    a.measurement = measurement; a.min_joints = min_joints;
+    a.q = q; a.r2 = r_floor * r_floor; a.cov_scale = cov_scale; a.v02 = v0 * v0; a.gate = gate;
+    a.clip = clip_mm; a.max_age = max_age_s; a.max_cost = max_cost_mm;
+    return a;
+}
+
+size_t associate_tracks_workspace_bytes(int n_tracks, int n_out) {
+    return (size_t)(n_tracks > 0 ? n_tracks : 0) * (size_t)(n_out > 0 ? n_out : 0) * SMOOTH_STATE_DOUBLES * sizeof(double);
+}
+
+int launch_associate_tracks(const float* poses, const float* cov, const double* times, int n, const int* step_rows, int n_step_rows,
+                            const int* step_starts, int n_steps, int n_out, int measurement, double q, double r_floor,
+                            double cov_scale, double v0, double gate, float max_cost_mm, double clip_mm, int min_joints,
+                            double max_age_s, double* state, int n_tracks, int* ids, int* next_id, void* workspace, int* track_index,
+                            int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new, int* n_dropped,
+                            hipStream_t stream) {
+    if (note_kernel("associate_tracks")) return METRO_OK;
+    const AssocArgs a = make_assoc_args(poses, cov, times, n, step_rows, n_step_rows, step_starts, n_steps, n_out, measurement, q,
+                                        r_floor, cov_scale, v0, gate, max_cost_mm, clip_mm, min_joints, max_age_s, state, n_tracks,
+                                        ids, next_id, static_cast<double*>(workspace), track_index, track_id, cost_out, rows_out,
+                                        starts_out, n_new, n_dropped);
+    hipLaunchKernelGGL(associate_tracks_kernel, dim3(1), dim3(ASSOC_THREADS), 0, stream, a);
+    return launch_status("associate_tracks");
+}
+
+}  // namespace metro

@@ -678,6 +678,49 @@ int metro_smooth_tracks(const float* d_poses, const float* d_cov, const double* 
                                 d_used_out, static_cast<hipStream_t>(stream));
 }
 
+size_t metro_associate_tracks_workspace_bytes(int32_t n_tracks, int32_t n_joints_out) {
+    return associate_tracks_workspace_bytes(n_tracks, n_joints_out);
+}
+
+int metro_associate_tracks(const float* d_poses, const float* d_cov, const double* d_times, int32_t n,
+                           const int32_t* d_step_rows, int32_t n_step_rows, const int32_t* d_step_starts, int32_t n_steps,
+                           const MetroSpec* spec, int32_t measurement, double q, double r_floor, double cov_scale, double v0,
+                           double gate, float max_cost_mm, double clip_mm, int32_t min_joints, double max_age_s, double* d_state,
+                           int32_t n_tracks, int32_t* d_ids, int32_t* d_next_id, void* d_workspace, int32_t* d_track_index_out,
+                           int32_t* d_track_id_out, float* d_cost_out, int32_t* d_rows_out, int32_t* d_starts_out,
+                           int32_t* d_n_new_out, int32_t* d_n_dropped_out, void* stream) {
+    METRO_CHECK_ARG(spec != nullptr, "associate_tracks: NULL spec");
+    METRO_CHECK_ARG(spec->n_joints_out >= 1 && spec->n_joints_out <= METRO_MAX_JOINTS,
+                    "associate_tracks: n_joints_out %d out of range [1, %d]", spec->n_joints_out, METRO_MAX_JOINTS);
+    METRO_CHECK_ARG(measurement == METRO_SMOOTH_ISOTROPIC || measurement == METRO_SMOOTH_COVARIANCE,
+                    "associate_tracks: measurement must be METRO_SMOOTH_ISOTROPIC or METRO_SMOOTH_COVARIANCE (got %d)", measurement);
+    METRO_CHECK_ARG(n >= 0 && n_step_rows >= 0 && n_steps >= 0,
+                    "associate_tracks: negative size (pose rows %d, step rows %d, steps %d)", n, n_step_rows, n_steps);
+    METRO_CHECK_ARG(n_tracks >= 1 && n_tracks <= METRO_ASSOC_MAX, "associate_tracks: %d track slots (1 to %d)", n_tracks,
+                    METRO_ASSOC_MAX);
+    METRO_CHECK_ARG(q > 0.0, "associate_tracks: q must be > 0 (got %g)", q);
+    METRO_CHECK_ARG(r_floor > 0.0, "associate_tracks: r_floor must be > 0 (got %g)", r_floor);
+    METRO_CHECK_ARG(v0 > 0.0, "associate_tracks: v0 must be > 0 (got %g)", v0);
+    METRO_CHECK_ARG(cov_scale >= 0.0, "associate_tracks: cov_scale must be >= 0 (got %g)", cov_scale);
+    METRO_CHECK_ARG(gate >= 0.0, "associate_tracks: gate must be >= 0, 0 for none (got %g)", gate);
+    METRO_CHECK_ARG(max_cost_mm > 0.0f, "associate_tracks: max_cost_mm must be > 0 (got %g)", (double)max_cost_mm);
+    METRO_CHECK_ARG(clip_mm > 0.0, "associate_tracks: clip_mm must be > 0 (got %g)", clip_mm);
+    METRO_CHECK_ARG(max_age_s >= 0.0, "associate_tracks: max_age_s must be >= 0 (got %g)", max_age_s);
+    METRO_CHECK_ARG(min_joints >= 1 && min_joints <= spec->n_joints_out, "associate_tracks: min_joints %d outside [1, %d]",
+                    min_joints, spec->n_joints_out);
+    if (n == 0 || n_step_rows == 0 || n_steps == 0) return METRO_OK;
+    METRO_CHECK_ARG(d_poses && d_times && d_step_rows && d_step_starts && d_state && d_ids && d_next_id && d_workspace &&
+                        d_track_index_out && d_track_id_out && d_cost_out && d_rows_out && d_starts_out && d_n_new_out &&
+                        d_n_dropped_out,
+                    "associate_tracks: NULL poses / times / steps / table / workspace / output pointer");
+    METRO_CHECK_ARG(measurement != METRO_SMOOTH_COVARIANCE || d_cov,
+                    "associate_tracks: METRO_SMOOTH_COVARIANCE reads the covariance: NULL");
+    return launch_associate_tracks(d_poses, d_cov, d_times, n, d_step_rows, n_step_rows, d_step_starts, n_steps, spec->n_joints_out,
+                                   measurement, q, r_floor, cov_scale, v0, gate, max_cost_mm, clip_mm, min_joints, max_age_s, d_state,
+                                   n_tracks, d_ids, d_next_id, d_workspace, d_track_index_out, d_track_id_out, d_cost_out, d_rows_out,
+                                   d_starts_out, d_n_new_out, d_n_dropped_out, static_cast<hipStream_t>(stream));
+}
+
 const char* metro_last_error(void) { return metro::get_error(); }
 int32_t metro_abi_version(void) { return METRO_ABI_VERSION; }
 

@@ -451,6 +451,14 @@ int launch_smooth_tracks(const float* poses, const float* cov, const double* tim
                          const int* starts, int n_tracks, int n_out, int mode, int measurement, double q, double r_floor,
                          double cov_scale, double v0, double gate, double* state, void* workspace, float* poses_out,
                          float* velocity_out, float* cov_out, unsigned char* used_out, hipStream_t stream);
+// which box of a video continues which track: one workgroup over the steps of the call (associate_tracks.hip)
+size_t associate_tracks_workspace_bytes(int n_tracks, int n_out);
+int launch_associate_tracks(const float* poses, const float* cov, const double* times, int n, const int* step_rows, int n_step_rows,
+                            const int* step_starts, int n_steps, int n_out, int measurement, double q, double r_floor,
+                            double cov_scale, double v0, double gate, float max_cost_mm, double clip_mm, int min_joints,
+                            double max_age_s, double* state, int n_tracks, int* ids, int* next_id, void* workspace, int* track_index,
+                            int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new, int* n_dropped,
+                            hipStream_t stream);
 // per-box crop geometry of full frames (look_at_boxes.hip)
 int launch_look_at_boxes(const double* boxes, const int32_t* frame_index, int n, int n_frames, const MetroFrameCamera* cameras,
                          int n_cameras, int side, MetroViewBase* out, int32_t* status, hipStream_t stream);

@@ -17,13 +17,13 @@
 // the indices are compile-time constants and P lives in registers: the code object reports no scratch.
 // One thread per (track, output joint); fp64 arithmetic on the fp32 inputs, no FMA contraction, one rounding to fp32 per output.
 #include "metro_common.h"
+#include "smooth_step.h"
 
 #pragma clang fp contract(off)
 
 namespace metro {
 
 constexpr int SMOOTH_WS_DOUBLES = 54;     // per (group row, joint): x 6, P 21, x- 6, P- 21
-constexpr int SMOOTH_STATE_DOUBLES = 28;  // per (track, joint): x 6, P 21, t_last
 
 struct SmoothArgs {
     const float* poses;      // [n][J][3] mm
@@ -40,88 +40,6 @@ struct SmoothArgs {
     int n, n_rows, n_tracks, n_out, mode, measurement;
     double q, r2, cov_scale, v02, gate;
 };
-
-// index of P(i, j) in the packed upper triangle
-__host__ __device__ constexpr int smooth_tri(int i, int j) {
-    return i <= j ? i * (13 - i) / 2 + (j - i) : j * (13 - j) / 2 + (i - j);
-}
-#define SMOOTH_P(p, i, j) (p)[smooth_tri((i), (j))]
-
-struct SmoothKf { double x[6], p[21]; };
-
-__host__ __device__ inline void smooth_predict(const SmoothKf& s, double dt, double q, SmoothKf& m) {
-    const double dt2 = dt * dt, qa = q * (dt2 * dt / 3.0), qb = q * (dt2 / 2.0), qd = q * dt;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        m.x[a] = s.x[a] + dt * s.x[3 + a];
-        m.x[3 + a] = s.x[3 + a];
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {
-            const double pv = SMOOTH_P(s.p, a, 3 + b), vv = SMOOTH_P(s.p, 3 + a, 3 + b);
-            if (a <= b) {
-                SMOOTH_P(m.p, a, b) = ((SMOOTH_P(s.p, a, b) + dt * (pv + SMOOTH_P(s.p, b, 3 + a))) + dt2 * vv) + (a == b ? qa : 0.0);
-                SMOOTH_P(m.p, 3 + a, 3 + b) = vv + (a == b ? qd : 0.0);
-            }
-            SMOOTH_P(m.p, a, 3 + b) = (pv + dt * vv) + (a == b ? qb : 0.0);
-        }
-    }
-}
-
-// r: xx, xy, xz, yy, yz, zz.  Positive definite by its leading minors, all entries finite.
-__host__ __device__ inline bool smooth_pd3(const double* r) {
-    bool fin = true;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) fin = fin && __builtin_isfinite(r[k]);
-    const double m2 = r[0] * r[3] - r[1] * r[1];
-    const double det = (r[0] * (r[3] * r[5] - r[4] * r[4]) - r[1] * (r[1] * r[5] - r[4] * r[2])) + r[2] * (r[1] * r[4] - r[3] * r[2]);
-    return fin && r[0] > 0.0 && m2 > 0.0 && det > 0.0;
-}
-
-// the measurement update of (m = x-, P-) with z and R (sym6) into s; false: gated, s untouched
-__host__ __device__ inline bool smooth_update(const SmoothKf& m, const double* z, const double* r, double gate, SmoothKf& s) {
-    const double sxx = m.p[smooth_tri(0, 0)] + r[0], sxy = m.p[smooth_tri(0, 1)] + r[1], sxz = m.p[smooth_tri(0, 2)] + r[2];
-    const double syy = m.p[smooth_tri(1, 1)] + r[3], syz = m.p[smooth_tri(1, 2)] + r[4], szz = m.p[smooth_tri(2, 2)] + r[5];
-    const double c00 = syy * szz - syz * syz, c01 = sxz * syz - sxy * szz, c02 = sxy * syz - sxz * syy;
-    const double c11 = sxx * szz - sxz * sxz, c12 = sxy * sxz - sxx * syz, c22 = sxx * syy - sxy * sxy;
-    const double det = (sxx * c00 + sxy * c01) + sxz * c02;
-    const double si[3][3] = {{c00 / det, c01 / det, c02 / det}, {c01 / det, c11 / det, c12 / det}, {c02 / det, c12 / det, c22 / det}};
-    const double nu[3] = {z[0] - m.x[0], z[1] - m.x[1], z[2] - m.x[2]};
-    double t[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) t[a] = (si[a][0] * nu[0] + si[a][1] * nu[1]) + si[a][2] * nu[2];
-    const double d2 = (nu[0] * t[0] + nu[1] * t[1]) + nu[2] * t[2];
-    if (gate > 0.0 && d2 > gate) return false;
-    const double rr[3][3] = {{r[0], r[1], r[2]}, {r[1], r[3], r[4]}, {r[2], r[4], r[5]}};
-    double k[6][3], kr[6][3], tm[6][3];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-            k[i][a] = (SMOOTH_P(m.p, i, 0) * si[0][a] + SMOOTH_P(m.p, i, 1) * si[1][a]) + SMOOTH_P(m.p, i, 2) * si[2][a];
-        s.x[i] = m.x[i] + ((k[i][0] * nu[0] + k[i][1] * nu[1]) + k[i][2] * nu[2]);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) kr[i][a] = (k[i][0] * rr[0][a] + k[i][1] * rr[1][a]) + k[i][2] * rr[2][a];
-    }
-    // T = (I - KH) P-: T(i, j) = P-(i, j) - sum_l K(i, l) P-(l, j); only its first three columns meet (I - KH)^T's K
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-            tm[i][a] = SMOOTH_P(m.p, i, a) - ((k[i][0] * SMOOTH_P(m.p, 0, a) + k[i][1] * SMOOTH_P(m.p, 1, a)) + k[i][2] * SMOOTH_P(m.p, 2, a));
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = i; j < 6; ++j) {
-            const double tij = SMOOTH_P(m.p, i, j) - ((k[i][0] * SMOOTH_P(m.p, 0, j) + k[i][1] * SMOOTH_P(m.p, 1, j)) + k[i][2] * SMOOTH_P(m.p, 2, j));
-            const double tk = (tm[i][0] * k[j][0] + tm[i][1] * k[j][1]) + tm[i][2] * k[j][2];
-            const double krk = (kr[i][0] * k[j][0] + kr[i][1] * k[j][1]) + kr[i][2] * k[j][2];
-            SMOOTH_P(s.p, i, j) = (tij - tk) + krk;
-        }
-    return true;
-}
 
 // one RTS step: (xs, ps) = smoothed k+1 on entry, smoothed k on return.  f = filtered k, m = predicted k+1, dt = t_{k+1} - t_k.
 // false: a pivot of P-_{k+1} was not positive, (xs, ps) = f
@@ -252,60 +170,19 @@ __host__ __device__ inline void smooth_track_joint(const SmoothArgs& a, int idx)
     double t_prev = 0.0;
     bool have = false;
     double* st = a.state ? a.state + (size_t)idx * SMOOTH_STATE_DOUBLES : nullptr;
-    if (st && !(st[27] != st[27])) {
-#pragma unroll
-        for (int e = 0; e < 6; ++e) s.x[e] = st[e];
-#pragma unroll
-        for (int e = 0; e < 21; ++e) s.p[e] = st[6 + e];
-        t_prev = st[27];
-        have = true;
-    }
+    if (st) have = smooth_state_load(st, s, t_prev);
     int k_first = -1, k_last = -1;            // the first and the last group row with a filter state
     for (int k = first; k < last; ++k) {
         const int row = a.rows[k];
         if ((unsigned)row >= (unsigned)a.n) continue;
         const size_t at = (size_t)row * a.n_out + j;
         const double t = a.times[row];
-        const double z[3] = {(double)a.poses[at * 3], (double)a.poses[at * 3 + 1], (double)a.poses[at * 3 + 2]};
-        double r[6] = {a.r2, 0.0, 0.0, a.r2, 0.0, a.r2};
-        bool usable = __builtin_isfinite(z[0]) && __builtin_isfinite(z[1]) && __builtin_isfinite(z[2]);
-        if (a.measurement == METRO_SMOOTH_COVARIANCE) {
-            const float* c9 = a.cov + at * 9;
-            r[0] = a.cov_scale * (double)c9[0] + a.r2;
-            r[1] = a.cov_scale * (double)c9[1];
-            r[2] = a.cov_scale * (double)c9[2];
-            r[3] = a.cov_scale * (double)c9[4] + a.r2;
-            r[4] = a.cov_scale * (double)c9[5];
-            r[5] = a.cov_scale * (double)c9[8] + a.r2;
-            usable = usable && smooth_pd3(r);
+        bool used;
+        if (!smooth_filter_row(a, at, t, s, m, t_prev, have, used)) {
+            smooth_write_nan(a, at);
+            if (a.used_out) a.used_out[at] = 0;
+            continue;
         }
-        bool used = false;
-        if (!have) {
-            if (!usable) {
-                smooth_write_nan(a, at);
-                if (a.used_out) a.used_out[at] = 0;
-                continue;
-            }
-#pragma unroll
-            for (int e = 0; e < 21; ++e) s.p[e] = 0.0;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                s.x[c] = z[c];
-                s.x[3 + c] = 0.0;
-                SMOOTH_P(s.p, 3 + c, 3 + c) = a.v02;
-            }
-            SMOOTH_P(s.p, 0, 0) = r[0]; SMOOTH_P(s.p, 0, 1) = r[1]; SMOOTH_P(s.p, 0, 2) = r[2];
-            SMOOTH_P(s.p, 1, 1) = r[3]; SMOOTH_P(s.p, 1, 2) = r[4]; SMOOTH_P(s.p, 2, 2) = r[5];
-            m = s;
-            have = used = true;
-        } else {
-            double dt = t - t_prev;
-            if (!(dt > 0.0)) dt = 0.0;
-            smooth_predict(s, dt, a.q, m);
-            used = usable && smooth_update(m, z, r, a.gate, s);
-            if (!used) s = m;
-        }
-        t_prev = t;
         if (rts) {
             smooth_ws_store(a, 0, k, j, s);
             smooth_ws_store(a, 27, k, j, m);
@@ -316,13 +193,7 @@ __host__ __device__ inline void smooth_track_joint(const SmoothArgs& a, int idx)
         k_last = k;
     }
     if (k_last < 0) return;
-    if (st) {
-#pragma unroll
-        for (int e = 0; e < 6; ++e) st[e] = s.x[e];
-#pragma unroll
-        for (int e = 0; e < 21; ++e) st[6 + e] = s.p[e];
-        st[27] = t_prev;
-    }
+    if (st) smooth_state_store(st, s, t_prev);
     if (!rts) return;
     // backward: s holds the smoothed row k_next (the last row's smoothed value is its filtered one)
     int k_next = k_last;

@@ -44,6 +44,12 @@ the box centre, drops the lens distortion, squares the pixels and zooms so the b
                                           by its heat-map covariance (track_groups: the CSR grouping; new_track_state: the
                                           filter state carried from call to call).  Nothing in the reference (one image
                                           per example)
+  follow_poses_in_frames                  the same without a track_index: ONE metro_associate_tracks launch between the
+                                          forward and metro_smooth_tracks walks the boxes in time order over a table of
+                                          track slots (greedy assignment on the filter's predicted poses, births, persistent
+                                          ids) and writes the CSR grouping on the device (time_steps: the CSR of the time
+                                          steps; new_track_table: the tracks carried from call to call).  Nothing in the
+                                          reference
 
 Divergences from the reference, on purpose (camera.py and frame_formats.py list their own):
   * reproject_image's case 1 (cameralib.py:282-293: an all-zero coefficient array whose virtual R is allclose to the original
@@ -1256,8 +1262,8 @@ def track_poses_in_frames(frames, boxes, model_path, cameras, track_index, frame
     keyword from scale_recovery on are locate_poses_in_frames'.
 
     track_index [n]: the track of each box (host integers; -1: untracked, the box comes back as `raw` has it with NaN
-    velocity and used 0); associating boxes with tracks is the caller's.  timestamps: seconds, one value per box, or one per
-    frame looked up through frame_index (n values are read per box); host data.  Two boxes of one track at one time are a
+    velocity and used 0); associating boxes with tracks is the caller's here (follow_poses_in_frames does it on the device).
+    timestamps: seconds, one value per box, or one per frame looked up through frame_index (n values are read per box); host data.  Two boxes of one track at one time are a
     ValueError.
     Each box's pose is a measurement with noise R = cov_scale * raw.covariance + sigma_floor_mm^2 I (measurement
     'isotropic': sigma_floor_mm^2 I): a joint whose heat-map is wide in some direction counts for less in that direction.
@@ -1298,3 +1304,137 @@ def track_poses_in_frames(frames, boxes, model_path, cameras, track_index, frame
         poses, velocity, covariance, used = smooth_tracks(raw.poses, raw.covariance, times, rows, starts, mode, measurement, accel_psd,
                                                           sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, state)
     return TrackPoses(poses, velocity, covariance, used, raw, state, raw.joint_edges, raw.joint_names)
+
+
+# ---- the same, with the tracks found on the device: frame-to-frame association (metro_associate_tracks) ----
+
+class TrackTable(NamedTuple):
+    """The tracks follow_poses_in_frames carries from call to call, on the device (new_track_table)."""
+    state: torch.Tensor                  # float64 [T, Jout, 28]: the filter state per slot (track_poses_in_frames' `state`)
+    ids: torch.Tensor                    # int32 [T]: the persistent id of the track in each slot, -1: the slot is free
+    next_id: torch.Tensor                # int32 [1]: the next id to give
+
+
+class FollowedPoses(NamedTuple):
+    """What follow_poses_in_frames returns."""
+    track_index: torch.Tensor            # int32 [n] on the device: the slot of every box, -1 untracked
+    track_id: torch.Tensor               # int32 [n] on the device: the persistent id of its track, -1 untracked
+    cost: torch.Tensor                   # float32 [n] mm: the cost at which a box continued its track (NaN: born here, or untracked)
+    n_new: torch.Tensor                  # int32 [1] on the device: tracks born in this call
+    n_dropped: torch.Tensor              # int32 [1] on the device: boxes left untracked (no free slot, or no finite joint)
+    tracks: TrackTable                   # the table after this call (pass it to the next)
+    smoothed: TrackPoses                 # track_poses_in_frames' result for that track_index; its state is tracks.state
+
+
+def time_steps(timestamps) -> Tuple[np.ndarray, np.ndarray]:
+    """The time-step CSR metro_associate_tracks reads, built on the host from one time per box: (step_rows int32 [n],
+    step_starts int32 [S + 1]), step s owning the boxes step_rows[step_starts[s]:step_starts[s+1]] (in box order), the steps
+    in ascending time, all boxes of one timestamp in one step.  ValueError for non-finite times and for more than 128 boxes
+    on one timestamp."""
+    from metro_pose3d_amd.heads import ASSOC_MAX
+    ts = np.asarray(timestamps, np.float64).reshape(-1)
+    if not np.isfinite(ts).all():
+        raise ValueError('timestamps must be finite (seconds)')
+    order = np.argsort(ts, kind='stable')
+    new = np.concatenate([[True], ts[order][1:] != ts[order][:-1]]) if len(ts) else np.zeros(0, bool)
+    starts = np.concatenate([np.flatnonzero(new), [len(ts)]]).astype(np.int32)
+    sizes = np.diff(starts)
+    if len(sizes) and sizes.max() > ASSOC_MAX:
+        s = int(np.argmax(sizes))
+        raise ValueError(f'{int(sizes[s])} boxes at time {ts[order][starts[s]]!r}: association takes at most {ASSOC_MAX} per '
+                         'timestamp')
+    return order.astype(np.int32), starts
+
+
+def new_track_table(capacity: int, n_joints_out: int, device) -> TrackTable:
+    """An empty table of `capacity` (1 to 128) track slots for follow_poses_in_frames / heads.associate_tracks: no state
+    (new_track_state), every slot free (id -1), the first id to give 0."""
+    from metro_pose3d_amd.heads import ASSOC_MAX
+    if isinstance(capacity, (bool, np.bool_)) or not isinstance(capacity, (int, np.integer)) or not 1 <= capacity <= ASSOC_MAX:
+        raise ValueError(f'capacity must be an integer from 1 to {ASSOC_MAX} (track slots), got {capacity!r}')
+    return TrackTable(new_track_state(int(capacity), n_joints_out, device),
+                      torch.full((int(capacity),), -1, dtype=torch.int32, device=device),
+                      torch.zeros((1,), dtype=torch.int32, device=device))
+
+
+def _check_track_table(tracks, capacity):
+    from metro_pose3d_amd.heads import ASSOC_MAX, TRACK_STATE_DOUBLES
+    ok = (isinstance(tracks, tuple) and len(tracks) == 3 and all(isinstance(t, torch.Tensor) for t in tracks)
+          and tracks[0].dtype == torch.float64 and tracks[0].dim() == 3 and tracks[0].shape[2] == TRACK_STATE_DOUBLES
+          and 1 <= tracks[0].shape[0] <= ASSOC_MAX and tracks[0].is_contiguous()
+          and tracks[1].dtype == torch.int32 and tuple(tracks[1].shape) == (tracks[0].shape[0],) and tracks[1].is_contiguous()
+          and tracks[2].dtype == torch.int32 and tracks[2].numel() == 1)
+    if not ok:
+        raise ValueError(f'tracks must be a TrackTable(state float64 [T, Jout, {TRACK_STATE_DOUBLES}], ids int32 [T], next_id int32 '
+                         f'[1]) with 1 <= T <= {ASSOC_MAX} (new_track_table, or the table of a previous call)')
+    del capacity
+
+
+def follow_poses_in_frames(frames, boxes, model_path, cameras, frame_index, timestamps, tracks: Optional[TrackTable] = None,
+                           capacity: int = 64, max_cost_mm: float = 300.0, clip_mm: float = 600.0,
+                           min_joints: Optional[int] = None, max_age_s: float = 1.0, mode: str = 'smooth',
+                           measurement: str = 'covariance', accel_psd: float = 4e6, sigma_floor_mm: float = 1.0,
+                           cov_scale: float = 1.0, initial_speed_mm_s: float = 2000.0, gate=None,
+                           scale_recovery: str = 'bone-lengths', bone_lengths=None, root_depth=None, coords: str = 'camera',
+                           precision: Optional[str] = None, check_finite: Optional[bool] = None, views=None,
+                           geometry: str = 'auto', pixel_format: str = 'rgb', color_matrix: str = 'bt601',
+                           crop_dtype: str = 'float32') -> FollowedPoses:
+    """track_poses_in_frames without a track_index: which box continues which track is decided on the device, from the
+    forward's own outputs, between the forward and the smoothing launch -> FollowedPoses(track_index int32 [n], track_id
+    int32 [n], cost [n], n_new [1], n_dropped [1], tracks: TrackTable, smoothed: TrackPoses).  Every other argument as there;
+    a person detector's boxes per frame, in any order, are enough.  At most 128 boxes per timestamp and 128 track slots.
+
+    The boxes are walked in time order over a table of track slots (heads.associate_tracks): at each timestamp the cost of a
+    slot continuing in a box is the RMS distance in mm between the box's joints and the slot's constant-velocity prediction
+    (the filter state advanced to the box's time), each joint capped at clip_mm, +inf from fewer than min_joints joints
+    (None: half the output joints, rounded up) and for a slot last seen more than max_age_s before; slots and boxes are
+    paired greedily, the smallest cost first, while it is below max_cost_mm (one box per slot, one slot per box); a box left
+    over starts a new track in the lowest free slot, under the next id; with no slot free it stays untracked (-1, counted in
+    n_dropped), as does a box with no finite joint.  The pairing is greedy, not an optimal assignment.  track_index is the
+    slot (what track_poses_in_frames calls a track), track_id the identity that persists when slots are reused.
+    max_cost_mm = 300, clip_mm = 600, max_age_s = 1 and the min_joints default are design choices, not measurements
+    (heads.associate_tracks has the reasoning).
+    tracks: None (a fresh table of `capacity` slots) or the table a previous call returned: tracks continue from it, a slot
+    last seen more than max_age_s before this call's first box is retired first and free again, and the table is updated in
+    place -- its ids, and its state with the FILTER state at each track's last box -- so a stream cut into calls gets the
+    ids one long call gives.  `capacity` is read only when tracks is None.
+    The poses must be absolute: scale_recovery 'metro' returns root-relative poses, in which all persons coincide, and is
+    refused.
+    One enqueue chain: track_poses_in_frames' own, with one metro_associate_tracks launch between the forward and
+    metro_smooth_tracks, which reads the device CSR that launch wrote and tracks.state; track_index is never read on the
+    host, and the call's one synchronisation stays the finite screen.
+    ValueError before any launch for more than 128 boxes on one timestamp, capacity outside [1, 128], a tracks that is no
+    table, scale_recovery 'metro', max_cost_mm, clip_mm, min_joints or max_age_s out of range, and whatever
+    track_poses_in_frames refuses."""
+    from metro_pose3d_amd.heads import associate_tracks, association_params, smooth_tracks, smoothing_params
+    smoothing_params(mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate)
+    association_params(max_cost_mm, clip_mm, min_joints, max_age_s)
+    if scale_recovery == 'metro':
+        raise ValueError("scale_recovery='metro' returns root-relative poses, in which all persons coincide: following needs "
+                         "absolute poses ('bone-lengths' or 'true-root-depth')")
+    n_boxes = _n_boxes(boxes)
+    fi = np.zeros(n_boxes, np.int64) if frame_index is None else np.asarray(_host_array(frame_index), np.int64).reshape(-1)
+    if len(fi) != n_boxes:
+        raise ValueError(f'frame_index must hold one value per box ({n_boxes}), got {len(fi)}')
+    times = _box_times(timestamps, fi, n_boxes)
+    step_rows, step_starts = time_steps(times)
+    if tracks is None:
+        new_track_table(capacity, 1, 'cpu')                 # the capacity check, before any launch
+    else:
+        _check_track_table(tracks, capacity)
+    raw = locate_poses_in_frames(frames, boxes, model_path, cameras=cameras, frame_index=frame_index, scale_recovery=scale_recovery,
+                                 bone_lengths=bone_lengths, root_depth=root_depth, coords=coords, precision=precision,
+                                 check_finite=check_finite, views=views, geometry=geometry, pixel_format=pixel_format,
+                                 color_matrix=color_matrix, crop_dtype=crop_dtype, return_uncertainty=True)
+    device = raw.poses.device
+    if tracks is None:
+        tracks = new_track_table(capacity, raw.poses.shape[1], device)
+    tracks = TrackTable(*tracks)
+    with torch.cuda.device(device):
+        found = associate_tracks(raw.poses, raw.covariance, times, step_rows, step_starts, tracks.state, tracks.ids, tracks.next_id,
+                                 max_cost_mm, clip_mm, min_joints, max_age_s, measurement, accel_psd, sigma_floor_mm, cov_scale,
+                                 initial_speed_mm_s, gate)
+        poses, velocity, covariance, used = smooth_tracks(raw.poses, raw.covariance, times, found.rows, found.starts, mode, measurement,
+                                                          accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, tracks.state)
+    smoothed = TrackPoses(poses, velocity, covariance, used, raw, tracks.state, raw.joint_edges, raw.joint_names)
+    return FollowedPoses(found.track_index, found.track_id, found.cost, found.n_new, found.n_dropped, tracks, smoothed)

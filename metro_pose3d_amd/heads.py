@@ -11,6 +11,8 @@ through the C ABI (csrc/heads.hip).  Names and argument meaning follow the refer
                             cross-view association (nothing in the reference: one camera each)
   cluster_views             constrained complete-linkage clustering of that matrix: person_index and the CSR grouping
                             triangulate_joints reads, all on the device
+  associate_tracks          which box of a video continues which track: greedy assignment on predicted poses, births and the
+                            CSR grouping smooth_tracks reads, one workgroup
   smooth_tracks             poses of tracked persons over time: constant-velocity Kalman filter / RTS smoother per track and
                             joint, each row weighted by its heat-map covariance (nothing in the reference: one image each)
   backproject_bone_lengths  scale_recovery 'bone-lengths' / '-true'   volumetric.py:171-191,
@@ -24,7 +26,7 @@ There is no CPU fallback: without the HIP library these raise MetroError."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -385,6 +387,108 @@ def smooth_tracks(poses: torch.Tensor, covariance: Optional[torch.Tensor], times
                                   _p(state), _p(ws), _p(out), _p(velocity), _p(cov_out), _p(used), _stream(dev)),
           'metro_smooth_tracks')
     return out, velocity, cov_out.view(n, nj, 3, 3), used
+
+
+ASSOC_MAX = _lib.METRO_ASSOC_MAX       # boxes per time step, and track slots, of associate_tracks
+
+
+class AssociatedTracks(NamedTuple):
+    """What associate_tracks returns, all on the device."""
+    track_index: torch.Tensor            # int32 [n]: the slot of every box, -1 untracked
+    track_id: torch.Tensor               # int32 [n]: the persistent id of its track, -1 untracked
+    cost: torch.Tensor                   # float32 [n] mm: the accepted cost of a box that continues a track, NaN for births / untracked
+    rows: torch.Tensor                   # int32 [n] and
+    starts: torch.Tensor                 # int32 [T + 1]: the CSR per slot in time order that smooth_tracks reads; rows past starts[T] are -1
+    n_new: torch.Tensor                  # int32 [1]: tracks born in this call
+    n_dropped: torch.Tensor              # int32 [1]: boxes left untracked (no free slot, or no finite joint)
+    working_state: torch.Tensor          # float64 [T, J, 28]: the state as the launch advanced it (what smooth_tracks will leave in `state`)
+
+
+def association_params(max_cost_mm, clip_mm, min_joints, max_age_s):
+    """Checks the association keywords of associate_tracks / frames.follow_poses_in_frames."""
+    matching_params(clip_mm, min_joints, max_cost_mm)
+    ok = not isinstance(max_age_s, (bool, np.bool_)) and isinstance(max_age_s, (int, float, np.integer, np.floating))
+    if not ok or np.isnan(max_age_s) or max_age_s < 0:
+        raise ValueError(f'max_age_s must be a number >= 0 (seconds), got {max_age_s!r}')
+
+
+def associate_tracks(poses: torch.Tensor, covariance: Optional[torch.Tensor], times, step_rows, step_starts, state: torch.Tensor,
+                     ids: torch.Tensor, next_id: torch.Tensor, max_cost_mm: float = 300.0, clip_mm: float = 600.0,
+                     min_joints: Optional[int] = None, max_age_s: float = 1.0, measurement: str = 'covariance',
+                     accel_psd: float = 4e6, sigma_floor_mm: float = 1.0, cov_scale: float = 1.0,
+                     initial_speed_mm_s: float = 2000.0, gate: Optional[float] = None) -> AssociatedTracks:
+    """Which box of a video continues which track, one metro_associate_tracks launch (one workgroup, the cost matrix in LDS;
+    include/metro_hip.h has the model).  poses [n,J,3] mm ABSOLUTE, covariance and times as smooth_tracks reads them;
+    step s owns the boxes step_rows[step_starts[s]:step_starts[s+1]], the steps in ascending time, all boxes of one
+    timestamp in one step (frames.time_steps; at most 128 boxes per step).  The track table (frames.new_track_table) is
+    state float64 [T,J,28] (smooth_tracks' carried state), ids int32 [T] (-1: free) and next_id int32 [1], T <= 128, all on
+    the device of `poses`; ids and next_id are updated in place, and of `state` only the t_last of slots retired at the
+    start (last seen more than max_age_s before the call's first box).
+    Per step: the cost of a slot continuing in a box is the RMS over the joints of the distance between the box's joint and
+    the slot's constant-velocity prediction, each capped at clip_mm (+inf from fewer than min_joints joints -- None:
+    (J + 1) // 2 -- or for a slot last seen more than max_age_s ago); boxes and slots are paired greedily, smallest cost
+    first, while it is below max_cost_mm; the remaining boxes start new tracks in the lowest free slots; every slot that got
+    a box advances a working copy of the state by smooth_tracks' filter step, with the same measurement, accel_psd,
+    sigma_floor_mm, cov_scale, initial_speed_mm_s and gate.  The pairing is greedy, not an optimal assignment.
+    max_cost_mm = 300, clip_mm = 600, max_age_s = 1 and the min_joints default are design choices, not measurements: 300 mm
+    is below the distance between two persons side by side and above what a person's joints move against a constant-velocity
+    prediction within a few frames; 600 mm keeps one wild joint from deciding a pair; one second bridges a short occlusion
+    without handing a long-gone track's slot history to a newcomer; half the joints keeps a cost from resting on a few.
+    -> AssociatedTracks; its rows / starts and `state` go to smooth_tracks unchanged.  No boxes or no steps: no launch."""
+    params = smoothing_params('filter', measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate)
+    association_params(max_cost_mm, clip_mm, min_joints, max_age_s)
+    if not isinstance(poses, torch.Tensor) or poses.dim() != 3 or poses.shape[2] != 3 or not 1 <= poses.shape[1] <= _lib.METRO_MAX_JOINTS:
+        raise ValueError(f'poses must be a tensor [n,J,3] with J <= {_lib.METRO_MAX_JOINTS}, got {tuple(getattr(poses, "shape", ()))}')
+    n, nj = int(poses.shape[0]), int(poses.shape[1])
+    if min_joints is None:
+        min_joints = (nj + 1) // 2
+    if min_joints > nj:
+        raise ValueError(f'min_joints must be at most the {nj} joints, got {min_joints!r}')
+    with_cov = measurement == 'covariance'
+    if with_cov and (covariance is None or tuple(covariance.shape) not in ((n, nj, 3, 3), (n, nj, 9))):
+        raise ValueError(f"measurement='covariance' needs covariance [{n},{nj},3,3], got "
+                         f'{None if covariance is None else tuple(covariance.shape)}')
+    dev = poses.device
+    if not isinstance(times, torch.Tensor):
+        times = torch.from_numpy(np.ascontiguousarray(np.asarray(times, np.float64).reshape(-1)))
+    if times.numel() != n:
+        raise ValueError(f'times must hold one value per pose row ({n}), got {times.numel()}')
+    n_step_rows = int(step_rows.numel() if isinstance(step_rows, torch.Tensor) else np.asarray(step_rows).size)
+    n_starts = int(step_starts.numel() if isinstance(step_starts, torch.Tensor) else np.asarray(step_starts).size)
+    if n_starts < 1:
+        raise ValueError('step_starts must hold S + 1 offsets (S >= 0)')
+    if not isinstance(step_starts, torch.Tensor):
+        sizes = np.diff(np.asarray(step_starts, np.int64).reshape(-1))
+        if len(sizes) and sizes.max() > ASSOC_MAX:
+            raise ValueError(f'{int(sizes.max())} boxes in one time step: association takes at most {ASSOC_MAX}')
+    if (not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or state.dim() != 3 or state.device != dev
+            or tuple(state.shape[1:]) != (nj, TRACK_STATE_DOUBLES) or not state.is_contiguous() or not 1 <= state.shape[0] <= ASSOC_MAX):
+        raise ValueError(f'state must be a contiguous float64 tensor [T,{nj},{TRACK_STATE_DOUBLES}] on {dev} with 1 <= T <= {ASSOC_MAX} '
+                         '(frames.new_track_table)')
+    n_tracks = int(state.shape[0])
+    for name, t, size in (('ids', ids, n_tracks), ('next_id', next_id, 1)):
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != dev or t.numel() != size or not t.is_contiguous()):
+            raise ValueError(f'{name} must be a contiguous int32 tensor of {size} on {dev} (frames.new_track_table)')
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    track_index, track_id, rows, starts, n_new, n_dropped = i32(n), i32(n), i32(n), i32(n_tracks + 1), i32(1), i32(1)
+    cost = torch.empty((n,), dtype=torch.float32, device=dev)
+    if n == 0 or n_step_rows == 0 or n_starts == 1:        # nothing to decide: no launch
+        track_index.fill_(-1), track_id.fill_(-1), rows.fill_(-1), cost.fill_(float('nan'))
+        starts.zero_(), n_new.zero_(), n_dropped.zero_()
+        return AssociatedTracks(track_index, track_id, cost, rows, starts, n_new, n_dropped, state.clone())
+    lib = _lib.load()
+    times = times.to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+    step_rows, step_starts = _i32(step_rows, dev).reshape(-1), _i32(step_starts, dev).reshape(-1)
+    poses = poses.to(torch.float32).contiguous()
+    cov = covariance.to(torch.float32).reshape(n, nj, 9).contiguous() if with_cov else None
+    ws = torch.empty(lib.metro_associate_tracks_workspace_bytes(n_tracks, nj), dtype=torch.uint8, device=dev)
+    cs = _lib.MetroSpec(n_joints_out=nj)
+    check(lib.metro_associate_tracks(_p(poses), _p(cov), _p(times), n, _p(step_rows), n_step_rows, _p(step_starts), n_starts - 1,
+                                     C.byref(cs), *params[1:], float(max_cost_mm), float(clip_mm), int(min_joints), float(max_age_s),
+                                     _p(state), n_tracks, _p(ids), _p(next_id), _p(ws), _p(track_index), _p(track_id), _p(cost), _p(rows),
+                                     _p(starts), _p(n_new), _p(n_dropped), _stream(dev)), 'metro_associate_tracks')
+    return AssociatedTracks(track_index, track_id, cost, rows, starts, n_new, n_dropped,
+                            ws.view(torch.float64).view(n_tracks, nj, TRACK_STATE_DOUBLES))
 
 
 def backproject_bone_lengths(coords01: torch.Tensor, inv_intrinsics, bone_lengths, spec: ModelSpec,
