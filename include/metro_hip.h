@@ -684,13 +684,25 @@ int  metro_place_covariances(const float* d_cov01, const float* d_peak, const Me
  * min_det = sin^2(min_angle) / 4 rejects (anti-)parallel rays, and any bundle of rays from one optical centre.
  * d_points_out fp32 [n_persons, n_joints_out, 3] world mm; d_n_rays_out int32 [n_persons, n_joints_out] rays in the final
  * solve; d_residual_out fp32 [n_persons, n_joints_out] = sqrt(sum w |(I - d d^T)(X - o)|^2 / sum w), the weighted RMS
- * distance of the point from its rays in mm.  n_persons == 0 launches nothing. */
+ * distance of the point from its rays in mm.  n_persons == 0 launches nothing.
+ * metro_triangulate_joints_cov: the same launch (points, n_rays and residual bit for bit those of the plain entry) that also
+ * writes d_cov_out fp32 [n_persons, n_joints_out, 9], the covariance of the point in mm^2, row-major symmetric 3x3 (the layout
+ * metro_smooth_tracks and metro_associate_tracks read), from the cofactors of the final solve.  METRO_TRI_COVARIANCE:
+ * Cov = A^-1 with A = sum w (I - d d^T) of the second solve (w is an inverse variance in mm^-2).  METRO_TRI_UNIFORM:
+ * Cov = s^2 A^-1 with A = sum (I - d d^T) and s^2 = sum |p|^2 / (2 k - 3), |p| the distances of the point from its k rays that
+ * the residual sums (two constraints per ray, three unknowns; exactly meeting rays give Cov = 0).  An undetermined joint gets
+ * a NaN block.  -1 also for a NULL d_cov_out. */
 #define METRO_TRI_UNIFORM 0
 #define METRO_TRI_COVARIANCE 1
 int  metro_triangulate_joints(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records, int32_t m,
                               const int32_t* d_rows, int32_t n_rows, const int32_t* d_starts, int32_t n_persons,
                               const MetroSpec* spec, const int32_t* d_mirror, int32_t weights, double min_det,
                               float* d_points_out, int32_t* d_n_rays_out, float* d_residual_out, void* stream);
+int  metro_triangulate_joints_cov(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records, int32_t m,
+                                  const int32_t* d_rows, int32_t n_rows, const int32_t* d_starts, int32_t n_persons,
+                                  const MetroSpec* spec, const int32_t* d_mirror, int32_t weights, double min_det,
+                                  float* d_points_out, int32_t* d_n_rays_out, float* d_residual_out, float* d_cov_out,
+                                  void* stream);
 
 /* ---- which boxes of several calibrated cameras show the same person: cross-view association on the device ----
  * Nothing in the reference: its examples have one camera each, and a person detector gives boxes per camera with no shared
@@ -709,6 +721,9 @@ int  metro_triangulate_joints(const float* d_coords01, const float* d_cov01, con
  * their number.  +inf where n_pairs < min_pairs, for two boxes on one frame (n_pairs 0: a person appears once per camera)
  * and on the diagonal (n_pairs 0).  One thread per entry of the n x n index space, the one with a < b writes [a][b] and
  * [b][a]; fp64 arithmetic on the fp32 inputs, one rounding to fp32 per output.
+ * metro_view_affinity_steps: the same kernel with d_step_index int32 [n], the time step (one exposure of the rig) of each box:
+ * two boxes of different steps get +inf and n_pairs 0, as two boxes of one frame do, every other entry has the bits the plain
+ * entry gives.  +inf survives the complete-linkage maximum, so no cluster of metro_cluster_views spans two steps.
  * metro_cluster_views: constrained complete-linkage clustering of the boxes, one workgroup, the working matrix in LDS.
  * d_cost fp32 [n, n] is read as C = max(cost, cost^T) with NaN as +inf.  Every box starts as its own cluster, named by its
  * lowest box.  Repeat: among the clusters a < b take the smallest C[a][b] (ties: the smallest a, then the smallest b); unless
@@ -720,14 +735,36 @@ int  metro_triangulate_joints(const float* d_coords01, const float* d_cov01, con
  * >= n_persons have empty groups; the entries of d_rows_out from d_starts_out[n] on are -1.
  * -1 before any launch for a NULL pointer (d_cov01 only with METRO_TRI_COVARIANCE), a negative n, n > METRO_MATCH_MAX_BOXES,
  * n_views outside [1, METRO_MAX_VIEWS], unknown weights, joint counts out of range, min_sin2 outside (0, 1], clip_mm or
- * max_cost not > 0 (or NaN) and min_pairs < 1.  n == 0 launches nothing and returns 0. */
+ * max_cost not > 0 (or NaN) and min_pairs < 1.  n == 0 launches nothing and returns 0.
+ * metro_person_steps: the time step of every person metro_cluster_views found and the persons as the time-step CSR
+ * metro_associate_tracks reads, one workgroup of 128 threads (thread p = person p) between the triangulation and the association
+ * launch.  Inputs: the cluster CSR d_rows int32 [n_rows], d_starts int32 [n + 1] and d_n_persons int32 [1] as
+ * metro_cluster_views wrote them, n <= METRO_MATCH_MAX_BOXES the upper bound of the persons; d_box_step int32 [n_boxes], the
+ * step of each box (box = crop row / n_views); d_step_times fp64 [n_steps] seconds, ascending.
+ * d_person_step_out int32 [n]: the smallest step among the boxes of the person's group (a gated cluster has one; ungated
+ * clusters take the earliest); -1 for the persons >= d_n_persons[0] and for an empty group (a person seen by one camera).  A
+ * row outside [0, n_boxes n_views) and a step outside [0, n_steps) are skipped, never read; d_starts is clamped to [0, n_rows].
+ * d_person_times_out fp64 [n]: d_step_times of that step, NaN where it is -1.  d_step_rows_out int32 [n]: the persons that
+ * have a step sorted by (step, person), the entries past their number -1.  d_step_starts_out int32 [n_steps + 1]: step s owns
+ * d_step_rows_out[d_step_starts_out[s] : d_step_starts_out[s + 1]]; d_step_starts_out[n_steps] is the number of persons that
+ * have a step.  -1 before any launch for a negative size, n > METRO_MATCH_MAX_BOXES, n_views outside [1, METRO_MAX_VIEWS] and,
+ * with n > 0, a NULL pointer (d_rows and d_box_step only with n_rows > 0, d_step_times only with n_steps > 0).  n == 0 launches
+ * nothing and returns 0. */
 #define METRO_MATCH_MAX_BOXES 128
 int  metro_view_affinity(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records, const MetroSpec* spec,
                          const int32_t* d_mirror, const int32_t* d_frame_index, int32_t n, int32_t n_views, int32_t weights,
                          double min_sin2, double clip_mm, int32_t min_pairs, float* d_cost_out, int32_t* d_n_pairs_out,
                          void* stream);
+int  metro_view_affinity_steps(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records,
+                               const MetroSpec* spec, const int32_t* d_mirror, const int32_t* d_frame_index,
+                               const int32_t* d_step_index, int32_t n, int32_t n_views, int32_t weights, double min_sin2,
+                               double clip_mm, int32_t min_pairs, float* d_cost_out, int32_t* d_n_pairs_out, void* stream);
 int  metro_cluster_views(const float* d_cost, int32_t n, int32_t n_views, float max_cost, int32_t* d_person_index_out,
                          int32_t* d_n_persons_out, int32_t* d_rows_out, int32_t* d_starts_out, void* stream);
+int  metro_person_steps(const int32_t* d_rows, int32_t n_rows, const int32_t* d_starts, const int32_t* d_n_persons, int32_t n,
+                        int32_t n_views, const int32_t* d_box_step, int32_t n_boxes, const double* d_step_times, int32_t n_steps,
+                        int32_t* d_person_step_out, double* d_person_times_out, int32_t* d_step_rows_out,
+                        int32_t* d_step_starts_out, void* stream);
 
 /* ---- poses of tracked persons smoothed over time: constant-velocity Kalman filter + Rauch-Tung-Striebel pass ----
  * Nothing in the reference: one example is one image.  One launch, one thread per (track, output joint), fp64 arithmetic on

@@ -12,13 +12,15 @@ Public surface (mirrors reference inference.py):
         persons smoothed over the frames of a video (Kalman filter / RTS smoother weighted by the heat-map covariances)
     follow_poses_in_frames(frames, boxes, model_path, cameras, frame_index, timestamps) -> the same without a track_index:
         the boxes are assigned to tracks on the device, frame by frame, under ids that persist from call to call
+    follow_world_poses_in_frames(frames, boxes, model_path, cameras, frame_index, timestamps) -> a calibrated rig's video:
+        boxes matched across cameras per exposure, triangulated with covariance, followed and smoothed in the world
 plus the pieces under it: ModelSpec, Engine (plan + forward over libmetro_hip.so), the model
 container (save_model / load_model) and batch sharding over the GPUs of a node (dist).
 """
 from metro_pose3d_amd.spec import ModelSpec  # noqa: F401
 from metro_pose3d_amd.modelfile import load_model, save_model  # noqa: F401
 
-__all__ = ['ModelSpec', 'load_model', 'save_model', 'Engine', 'estimate_pose', 'estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'Camera']
+__all__ = ['ModelSpec', 'load_model', 'save_model', 'Engine', 'estimate_pose', 'estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'Camera']
 
 
 def __getattr__(name):
@@ -29,7 +31,7 @@ def __getattr__(name):
     if name == 'estimate_pose':
         from metro_pose3d_amd.inference import estimate_pose
         return estimate_pose
-    if name in ('estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'Camera'):
+    if name in ('estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'Camera'):
         from metro_pose3d_amd import frames
         return getattr(frames, name)
     raise AttributeError(name)

@@ -192,6 +192,11 @@ SIGNATURES = {
                                            C.c_double, _P, _P, _P, _P]),
     'metro_view_affinity': (C.c_int, [_P, _P, _P, C.POINTER(MetroSpec), _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                       C.c_int32, _P, _P, _P]),
+    'metro_triangulate_joints_cov': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.POINTER(MetroSpec), _P, C.c_int32,
+                                               C.c_double, _P, _P, _P, _P, _P]),
+    'metro_view_affinity_steps': (C.c_int, [_P, _P, _P, C.POINTER(MetroSpec), _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                            C.c_double, C.c_int32, _P, _P, _P]),
+    'metro_person_steps': (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P]),
     'metro_cluster_views': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_float, _P, _P, _P, _P, _P]),
     'metro_smooth_tracks_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
     'metro_smooth_tracks': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.POINTER(MetroSpec), C.c_int32, C.c_int32,

@@ -585,10 +585,12 @@ int metro_merge_views(const float* d_poses, const float* d_keypoints, const floa
                               d_keypoints_out, d_z_offset_out, d_spread_out, static_cast<hipStream_t>(stream));
 }
 
-int metro_triangulate_joints(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records, int32_t m,
-                             const int32_t* d_rows, int32_t n_rows, const int32_t* d_starts, int32_t n_persons,
-                             const MetroSpec* spec, const int32_t* d_mirror, int32_t weights, double min_det, float* d_points_out,
-                             int32_t* d_n_rays_out, float* d_residual_out, void* stream) {
+// metro_triangulate_joints and metro_triangulate_joints_cov: the second also writes d_cov_out
+static int triangulate_joints_entry(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records, int32_t m,
+                                    const int32_t* d_rows, int32_t n_rows, const int32_t* d_starts, int32_t n_persons,
+                                    const MetroSpec* spec, const int32_t* d_mirror, int32_t weights, double min_det,
+                                    float* d_points_out, int32_t* d_n_rays_out, float* d_residual_out, bool with_cov,
+                                    float* d_cov_out, void* stream) {
     METRO_CHECK_ARG(spec != nullptr, "triangulate_joints: NULL spec");
     METRO_CHECK_ARG(spec->n_joints_head >= 1 && spec->n_joints_head <= METRO_MAX_JOINTS && spec->n_joints_out >= 1 &&
                         spec->n_joints_out <= METRO_MAX_JOINTS, "triangulate_joints: joint counts out of range (<= %d)", METRO_MAX_JOINTS);
@@ -596,7 +598,8 @@ int metro_triangulate_joints(const float* d_coords01, const float* d_cov01, cons
                     "triangulate_joints: weights must be METRO_TRI_UNIFORM or METRO_TRI_COVARIANCE (got %d)", weights);
     METRO_CHECK_ARG(n_persons >= 0 && m >= 0 && n_rows >= 0, "triangulate_joints: negative size (persons %d, crop rows %d, "
                     "group rows %d)", n_persons, m, n_rows);
-    METRO_CHECK_ARG((int64_t)n_persons * spec->n_joints_out <= INT32_MAX, "triangulate_joints: %d persons overflow int32", n_persons);
+    METRO_CHECK_ARG((int64_t)n_persons * spec->n_joints_out * (with_cov ? 9 : 1) <= INT32_MAX,
+                    "triangulate_joints: %d persons overflow int32", n_persons);
     if (n_persons == 0) return METRO_OK;
     METRO_CHECK_ARG(d_starts && d_mirror && d_points_out && d_n_rays_out && d_residual_out,
                     "triangulate_joints: NULL starts / mirror / output pointer");
@@ -604,14 +607,33 @@ int metro_triangulate_joints(const float* d_coords01, const float* d_cov01, cons
                     "triangulate_joints: %d group rows need coords01, records, rows and m > 0", n_rows);
     METRO_CHECK_ARG(weights != METRO_TRI_COVARIANCE || n_rows == 0 || d_cov01,
                     "triangulate_joints: METRO_TRI_COVARIANCE reads cov01: NULL");
+    METRO_CHECK_ARG(!with_cov || d_cov_out, "triangulate_joints_cov: NULL cov_out pointer");
     return launch_triangulate_joints(d_coords01, d_cov01, d_records, m, d_rows, n_rows, d_starts, n_persons, *spec, d_mirror, weights,
-                                     min_det, d_points_out, d_n_rays_out, d_residual_out, static_cast<hipStream_t>(stream));
+                                     min_det, d_points_out, d_n_rays_out, d_residual_out, with_cov ? d_cov_out : nullptr,
+                                     static_cast<hipStream_t>(stream));
 }
 
-int metro_view_affinity(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records, const MetroSpec* spec,
-                        const int32_t* d_mirror, const int32_t* d_frame_index, int32_t n, int32_t n_views, int32_t weights,
-                        double min_sin2, double clip_mm, int32_t min_pairs, float* d_cost_out, int32_t* d_n_pairs_out,
-                        void* stream) {
+int metro_triangulate_joints(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records, int32_t m,
+                             const int32_t* d_rows, int32_t n_rows, const int32_t* d_starts, int32_t n_persons,
+                             const MetroSpec* spec, const int32_t* d_mirror, int32_t weights, double min_det, float* d_points_out,
+                             int32_t* d_n_rays_out, float* d_residual_out, void* stream) {
+    return triangulate_joints_entry(d_coords01, d_cov01, d_records, m, d_rows, n_rows, d_starts, n_persons, spec, d_mirror, weights,
+                                    min_det, d_points_out, d_n_rays_out, d_residual_out, false, nullptr, stream);
+}
+
+int metro_triangulate_joints_cov(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records, int32_t m,
+                                 const int32_t* d_rows, int32_t n_rows, const int32_t* d_starts, int32_t n_persons,
+                                 const MetroSpec* spec, const int32_t* d_mirror, int32_t weights, double min_det,
+                                 float* d_points_out, int32_t* d_n_rays_out, float* d_residual_out, float* d_cov_out, void* stream) {
+    return triangulate_joints_entry(d_coords01, d_cov01, d_records, m, d_rows, n_rows, d_starts, n_persons, spec, d_mirror, weights,
+                                    min_det, d_points_out, d_n_rays_out, d_residual_out, true, d_cov_out, stream);
+}
+
+// metro_view_affinity and metro_view_affinity_steps: the second also reads d_step_index
+static int view_affinity_entry(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records, const MetroSpec* spec,
+                               const int32_t* d_mirror, const int32_t* d_frame_index, bool with_steps, const int32_t* d_step_index,
+                               int32_t n, int32_t n_views, int32_t weights, double min_sin2, double clip_mm, int32_t min_pairs,
+                               float* d_cost_out, int32_t* d_n_pairs_out, void* stream) {
     METRO_CHECK_ARG(spec != nullptr, "view_affinity: NULL spec");
     METRO_CHECK_ARG(spec->n_joints_head >= 1 && spec->n_joints_head <= METRO_MAX_JOINTS && spec->n_joints_out >= 1 &&
                         spec->n_joints_out <= METRO_MAX_JOINTS, "view_affinity: joint counts out of range (<= %d)", METRO_MAX_JOINTS);
@@ -627,8 +649,26 @@ int metro_view_affinity(const float* d_coords01, const float* d_cov01, const Met
     METRO_CHECK_ARG(d_coords01 && d_records && d_mirror && d_frame_index && d_cost_out && d_n_pairs_out,
                     "view_affinity: NULL coords01 / records / mirror / frame_index / output pointer");
     METRO_CHECK_ARG(weights != METRO_TRI_COVARIANCE || d_cov01, "view_affinity: METRO_TRI_COVARIANCE reads cov01: NULL");
-    return launch_view_affinity(d_coords01, d_cov01, d_records, *spec, d_mirror, d_frame_index, n, n_views, weights, min_sin2,
-                                clip_mm, min_pairs, d_cost_out, d_n_pairs_out, static_cast<hipStream_t>(stream));
+    METRO_CHECK_ARG(!with_steps || d_step_index, "view_affinity_steps: NULL step_index pointer");
+    return launch_view_affinity(d_coords01, d_cov01, d_records, *spec, d_mirror, d_frame_index, with_steps ? d_step_index : nullptr, n,
+                                n_views, weights, min_sin2, clip_mm, min_pairs, d_cost_out, d_n_pairs_out,
+                                static_cast<hipStream_t>(stream));
+}
+
+int metro_view_affinity(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records, const MetroSpec* spec,
+                        const int32_t* d_mirror, const int32_t* d_frame_index, int32_t n, int32_t n_views, int32_t weights,
+                        double min_sin2, double clip_mm, int32_t min_pairs, float* d_cost_out, int32_t* d_n_pairs_out,
+                        void* stream) {
+    return view_affinity_entry(d_coords01, d_cov01, d_records, spec, d_mirror, d_frame_index, false, nullptr, n, n_views, weights,
+                               min_sin2, clip_mm, min_pairs, d_cost_out, d_n_pairs_out, stream);
+}
+
+int metro_view_affinity_steps(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records, const MetroSpec* spec,
+                              const int32_t* d_mirror, const int32_t* d_frame_index, const int32_t* d_step_index, int32_t n,
+                              int32_t n_views, int32_t weights, double min_sin2, double clip_mm, int32_t min_pairs,
+                              float* d_cost_out, int32_t* d_n_pairs_out, void* stream) {
+    return view_affinity_entry(d_coords01, d_cov01, d_records, spec, d_mirror, d_frame_index, true, d_step_index, n, n_views, weights,
+                               min_sin2, clip_mm, min_pairs, d_cost_out, d_n_pairs_out, stream);
 }
 
 int metro_cluster_views(const float* d_cost, int32_t n, int32_t n_views, float max_cost, int32_t* d_person_index_out,
@@ -642,6 +682,24 @@ int metro_cluster_views(const float* d_cost, int32_t n, int32_t n_views, float m
                     "cluster_views: NULL cost / output pointer");
     return launch_cluster_views(d_cost, n, n_views, max_cost, d_person_index_out, d_n_persons_out, d_rows_out, d_starts_out,
                                 static_cast<hipStream_t>(stream));
+}
+
+int metro_person_steps(const int32_t* d_rows, int32_t n_rows, const int32_t* d_starts, const int32_t* d_n_persons, int32_t n,
+                       int32_t n_views, const int32_t* d_box_step, int32_t n_boxes, const double* d_step_times, int32_t n_steps,
+                       int32_t* d_person_step_out, double* d_person_times_out, int32_t* d_step_rows_out, int32_t* d_step_starts_out,
+                       void* stream) {
+    METRO_CHECK_ARG(n >= 0 && n_rows >= 0 && n_boxes >= 0 && n_steps >= 0,
+                    "person_steps: negative size (persons %d, group rows %d, boxes %d, steps %d)", n, n_rows, n_boxes, n_steps);
+    METRO_CHECK_ARG(n <= METRO_MATCH_MAX_BOXES, "person_steps: %d persons (at most %d)", n, METRO_MATCH_MAX_BOXES);
+    METRO_CHECK_ARG(n_views >= 1 && n_views <= METRO_MAX_VIEWS, "person_steps: %d views (1 to %d)", n_views, METRO_MAX_VIEWS);
+    if (n == 0) return METRO_OK;
+    METRO_CHECK_ARG(d_starts && d_n_persons && d_person_step_out && d_person_times_out && d_step_rows_out && d_step_starts_out,
+                    "person_steps: NULL starts / n_persons / output pointer");
+    METRO_CHECK_ARG(n_rows == 0 || (d_rows && d_box_step), "person_steps: %d group rows need rows and box_step", n_rows);
+    METRO_CHECK_ARG(n_steps == 0 || d_step_times, "person_steps: %d steps need step_times", n_steps);
+    return launch_person_steps(d_rows, n_rows, d_starts, d_n_persons, n, n_views, d_box_step, n_boxes, d_step_times, n_steps,
+                               d_person_step_out, d_person_times_out, d_step_rows_out, d_step_starts_out,
+                               static_cast<hipStream_t>(stream));
 }
 
 size_t metro_smooth_tracks_workspace_bytes(int32_t n_rows, int32_t n_joints_out) {

@@ -12,6 +12,8 @@
 // rays' lateral positions where they pass, mm^-2; a pair whose w is not finite and positive is skipped.
 // cost = sqrt(sum w dist^2 / sum w) over the counted pairs, n_pairs their number; +inf with fewer than min_pairs, for two
 // boxes on one frame (a person appears once per camera; n_pairs 0) and on the diagonal.
+// metro_view_affinity_steps: the same with step_index [n], the exposure of the rig each box belongs to: two boxes of different
+// steps are +inf with n_pairs 0 as two boxes of one frame are, every other pair is computed as above (step_index NULL: no gate).
 // Threads over the n x n index space: the one with a < b runs the serial loop over (v, r) and writes [a][b] and [b][a], the
 // ones with a == b write the diagonal.  fp64 arithmetic on the fp32 inputs, no FMA contraction, one rounding per output.
 //
@@ -41,6 +43,7 @@ struct MatchArgs {
     const MetroPlacement* rec;        // [m]
     const int* mirror;                // [n_out] output-order mirror joints
     const int* frame_index;           // [n]
+    const int* step_index;            // [n] or NULL: pairs across two steps are not compared
     float* cost;                      // [n][n]
     int* n_pairs;                     // [n][n]
     int m, n, n_views, nj, n_out, weights, min_pairs;
@@ -57,7 +60,8 @@ __host__ __device__ inline double match_dot3(const double* x, const double* y) {
 __host__ __device__ inline void view_affinity_pair(const MatchArgs& a, int ia, int ib) {
     float cost = __builtin_inff();
     int cnt = 0;
-    if (a.frame_index[ia] != a.frame_index[ib]) {
+    const bool same_step = !a.step_index || a.step_index[ia] == a.step_index[ib];
+    if (same_step && a.frame_index[ia] != a.frame_index[ib]) {
         const bool weighted = a.weights == METRO_TRI_COVARIANCE;
         double sw = 0.0, swd = 0.0;
         TriRay ra, rb;
@@ -113,6 +117,7 @@ inline MatchArgs make_match_args(const float* coords01, const float* cov01, cons
                                  double clip_mm, int min_pairs, float* cost, int* n_pairs) {
     MatchArgs a;
     a.coords01 = coords01; a.cov01 = cov01; a.rec = rec; a.mirror = mirror; a.frame_index = frame_index;
+    a.step_index = nullptr;
     a.cost = cost; a.n_pairs = n_pairs;
     a.m = n * n_views; a.n = n; a.n_views = n_views; a.weights = weights; a.min_pairs = min_pairs;
     a.min_sin2 = min_sin2; a.clip = clip_mm;
@@ -121,11 +126,12 @@ inline MatchArgs make_match_args(const float* coords01, const float* cov01, cons
 }
 
 int launch_view_affinity(const float* coords01, const float* cov01, const MetroPlacement* rec, const MetroSpec& spec,
-                         const int* mirror, const int* frame_index, int n, int n_views, int weights, double min_sin2,
-                         double clip_mm, int min_pairs, float* cost, int* n_pairs, hipStream_t stream) {
+                         const int* mirror, const int* frame_index, const int* step_index, int n, int n_views, int weights,
+                         double min_sin2, double clip_mm, int min_pairs, float* cost, int* n_pairs, hipStream_t stream) {
     if (note_kernel("view_affinity")) return METRO_OK;
-    const MatchArgs a = make_match_args(coords01, cov01, rec, spec, mirror, frame_index, n, n_views, weights, min_sin2, clip_mm,
+    MatchArgs a = make_match_args(coords01, cov01, rec, spec, mirror, frame_index, n, n_views, weights, min_sin2, clip_mm,
                                         min_pairs, cost, n_pairs);
+    a.step_index = step_index;
     hipLaunchKernelGGL(view_affinity_kernel, dim3((n * n + 63) / 64), dim3(64), 0, stream, a);
     return launch_status("view_affinity");
 }

@@ -438,13 +438,17 @@ int launch_place_covariances(const float* cov01, const float* peak, const MetroP
 // world joints of persons seen by several cameras, from the rays of their crop rows (triangulate.hip)
 int launch_triangulate_joints(const float* coords01, const float* cov01, const MetroPlacement* rec, int m, const int* rows,
                               int n_rows, const int* starts, int n_persons, const MetroSpec& spec, const int* mirror, int weights,
-                              double min_det, float* points, int* n_rays, float* residual, hipStream_t stream);
+                              double min_det, float* points, int* n_rays, float* residual, float* cov, hipStream_t stream);
 // cross-view association: pairwise ray distance of boxes and their complete-linkage clustering (match_views.hip)
 int launch_view_affinity(const float* coords01, const float* cov01, const MetroPlacement* rec, const MetroSpec& spec,
-                         const int* mirror, const int* frame_index, int n, int n_views, int weights, double min_sin2,
-                         double clip_mm, int min_pairs, float* cost, int* n_pairs, hipStream_t stream);
+                         const int* mirror, const int* frame_index, const int* step_index, int n, int n_views, int weights,
+                         double min_sin2, double clip_mm, int min_pairs, float* cost, int* n_pairs, hipStream_t stream);
 int launch_cluster_views(const float* cost, int n, int n_views, float max_cost, int* person_index, int* n_persons, int* rows,
                          int* starts, hipStream_t stream);
+// the time step of every person metro_cluster_views found and the time-step CSR of the persons (world_tracks.hip)
+int launch_person_steps(const int* rows, int n_rows, const int* starts, const int* n_persons, int n, int n_views, const int* box_step,
+                        int n_boxes, const double* step_times, int n_steps, int* person_step, double* person_times, int* step_rows,
+                        int* step_starts, hipStream_t stream);
 // tracked poses smoothed over time: Kalman filter + RTS pass per (track, joint) (smooth_tracks.hip)
 size_t smooth_tracks_workspace_bytes(int n_rows, int n_out);
 int launch_smooth_tracks(const float* poses, const float* cov, const double* times, int n, const int* rows, int n_rows,

@@ -18,6 +18,10 @@
 // than 2 rays remain or det A~ < min_det: two rays at angle t have det A~ = sin^2 t / 4, and rays from one optical centre
 // have det A~ -> 0 however many they are.  Undetermined: point and residual NaN, n_rays the count of usable rays.
 // residual = sqrt(sum w |(I - d d^T)(X - o)|^2 / sum w): the weighted RMS distance of the point from its rays, mm.
+// metro_triangulate_joints_cov also writes the covariance of the point, mm^2, row-major symmetric 3x3, from the final solve's
+// cofactors: METRO_TRI_COVARIANCE  Cov = A^-1 = cof(A~) / det A~ / sum w (w is an inverse variance in mm^-2);  METRO_TRI_UNIFORM
+// Cov = s^2 A^-1 with s^2 = sum |p|^2 / (2 k - 3), |p| the distances the residual sums and k the rays (two constraints per ray,
+// three unknowns); NaN where the joint is undetermined.  The plain kernel is compiled without the write.
 // One thread per (person, output joint); rays are recomputed in each pass rather than stored (a group has no upper size).
 // fp64 arithmetic on the fp32 inputs, no FMA contraction (backproject.h), one rounding to fp32 per output.
 #include "metro_common.h"
@@ -38,6 +42,7 @@ struct TriArgs {
     float* points;                    // [n_persons][n_out][3]
     int* n_rays;                      // [n_persons][n_out]
     float* residual;                  // [n_persons][n_out]
+    float* cov;                       // [n_persons][n_out][9] mm^2 (triangulate_joints_cov_kernel only)
     int m, n_rows, n_persons, nj, n_out, weights;
     double min_det;
     float lrc, half_off;
@@ -66,8 +71,9 @@ __host__ __device__ inline void tri_add(TriSystem& s, const TriRay& ray, double 
     ++s.cnt;
 }
 
-// X = A~^-1 b~ by the cofactors of the symmetric A~ = A / sum w; false: undetermined
-__host__ __device__ inline bool tri_solve(const TriSystem& s, double min_det, double* x) {
+// X = A~^-1 b~ by the cofactors of the symmetric A~ = A / sum w; false: undetermined.  inv (if given): A~^-1 as xx, yy, zz, xy,
+// xz, yz
+__host__ __device__ inline bool tri_solve(const TriSystem& s, double min_det, double* x, double* inv = nullptr) {
     if (s.cnt < 2) return false;
     const double xx = s.a[0] / s.sw, yy = s.a[1] / s.sw, zz = s.a[2] / s.sw, xy = s.a[3] / s.sw, xz = s.a[4] / s.sw, yz = s.a[5] / s.sw;
     const double b0 = s.b[0] / s.sw, b1 = s.b[1] / s.sw, b2 = s.b[2] / s.sw;
@@ -78,11 +84,16 @@ __host__ __device__ inline bool tri_solve(const TriSystem& s, double min_det, do
     x[0] = ((c00 * b0 + c01 * b1) + c02 * b2) / det;
     x[1] = ((c01 * b0 + c11 * b1) + c12 * b2) / det;
     x[2] = ((c02 * b0 + c12 * b1) + c22 * b2) / det;
+    if (inv) {
+        inv[0] = c00 / det; inv[1] = c11 / det; inv[2] = c22 / det;
+        inv[3] = c01 / det; inv[4] = c02 / det; inv[5] = c12 / det;
+    }
     return true;
 }
 
 // one (person, output joint): what a thread of the kernel runs, and what tests/test_triangulation.py runs on the host
-__host__ __device__ inline void triangulate_joint(const TriArgs& a, int idx) {
+template <bool COV>
+__host__ __device__ inline void triangulate_joint_t(const TriArgs& a, int idx) {
     const int person = idx / a.n_out, r = idx - person * a.n_out;
     int first = a.starts[person], last = a.starts[person + 1];
     if (first < 0) first = 0;
@@ -92,8 +103,8 @@ __host__ __device__ inline void triangulate_joint(const TriArgs& a, int idx) {
     TriSystem sys = {{0, 0, 0, 0, 0, 0}, {0, 0, 0}, 0.0, 0};
     for (int k = first; k < last; ++k)
         if (tri_ray(a, a.rows[k], r, ray)) tri_add(sys, ray, 1.0);
-    double x0[3] = {0, 0, 0}, x[3] = {0, 0, 0};
-    bool ok = tri_solve(sys, a.min_det, x0);
+    double x0[3] = {0, 0, 0}, x[3] = {0, 0, 0}, inv[6];
+    bool ok = tri_solve(sys, a.min_det, x0, COV ? inv : nullptr);
     if (ok && weighted) {
         sys = {{0, 0, 0, 0, 0, 0}, {0, 0, 0}, 0.0, 0};
         for (int k = first; k < last; ++k) {
@@ -101,7 +112,7 @@ __host__ __device__ inline void triangulate_joint(const TriArgs& a, int idx) {
             const double w = tri_weight(ray, x0);
             if (w > 0.0) tri_add(sys, ray, w);
         }
-        ok = tri_solve(sys, a.min_det, x);
+        ok = tri_solve(sys, a.min_det, x, COV ? inv : nullptr);
     } else {
         for (int t = 0; t < 3; ++t) x[t] = x0[t];
     }
@@ -111,6 +122,8 @@ __host__ __device__ inline void triangulate_joint(const TriArgs& a, int idx) {
         const float nan = __builtin_nanf("");
         out[0] = out[1] = out[2] = nan;
         a.residual[idx] = nan;
+        if (COV)
+            for (int t = 0; t < 9; ++t) a.cov[(size_t)idx * 9 + t] = nan;
         return;
     }
     double acc = 0.0;
@@ -125,11 +138,28 @@ __host__ __device__ inline void triangulate_joint(const TriArgs& a, int idx) {
     }
     for (int t = 0; t < 3; ++t) out[t] = (float)x[t];
     a.residual[idx] = (float)sqrt(acc / sys.sw);
+    if (COV) {
+        // inv = (A / sum w)^-1, so A^-1 = inv / sum w; uniform weights: times the variance of a ray's distance from the point
+        const double s2 = weighted ? 1.0 : acc / (double)(2 * sys.cnt - 3);
+        float c6[6];
+        for (int t = 0; t < 6; ++t) c6[t] = (float)(s2 * (inv[t] / sys.sw));
+        float* c9 = a.cov + (size_t)idx * 9;
+        c9[0] = c6[0]; c9[1] = c6[3]; c9[2] = c6[4];
+        c9[3] = c6[3]; c9[4] = c6[1]; c9[5] = c6[5];
+        c9[6] = c6[4]; c9[7] = c6[5]; c9[8] = c6[2];
+    }
 }
+
+__host__ __device__ inline void triangulate_joint(const TriArgs& a, int idx) { triangulate_joint_t<false>(a, idx); }
 
 __global__ __launch_bounds__(64) void triangulate_joints_kernel(TriArgs a) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < a.n_persons * a.n_out) triangulate_joint(a, idx);
+}
+
+__global__ __launch_bounds__(64) void triangulate_joints_cov_kernel(TriArgs a) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < a.n_persons * a.n_out) triangulate_joint_t<true>(a, idx);
 }
 
 // the launch's arguments from the entry's
@@ -138,7 +168,7 @@ inline TriArgs make_tri_args(const float* coords01, const float* cov01, const Me
                              double min_det, float* points, int* n_rays, float* residual) {
     TriArgs a;
     a.coords01 = coords01; a.cov01 = cov01; a.rec = rec; a.rows = rows; a.starts = starts; a.mirror = mirror;
-    a.points = points; a.n_rays = n_rays; a.residual = residual;
+    a.points = points; a.n_rays = n_rays; a.residual = residual; a.cov = nullptr;
     a.m = m; a.n_rows = n_rows; a.n_persons = n_persons;
     a.weights = weights; a.min_det = min_det;
     tri_ray_fields(a, spec);
@@ -147,11 +177,16 @@ inline TriArgs make_tri_args(const float* coords01, const float* cov01, const Me
 
 int launch_triangulate_joints(const float* coords01, const float* cov01, const MetroPlacement* rec, int m, const int* rows,
                               int n_rows, const int* starts, int n_persons, const MetroSpec& spec, const int* mirror, int weights,
-                              double min_det, float* points, int* n_rays, float* residual, hipStream_t stream) {
-    if (note_kernel("triangulate_joints")) return METRO_OK;
-    const TriArgs a = make_tri_args(coords01, cov01, rec, m, rows, n_rows, starts, n_persons, spec, mirror, weights, min_det, points,
+                              double min_det, float* points, int* n_rays, float* residual, float* cov, hipStream_t stream) {
+    if (note_kernel("%s", cov ? "triangulate_joints_cov" : "triangulate_joints")) return METRO_OK;
+    TriArgs a = make_tri_args(coords01, cov01, rec, m, rows, n_rows, starts, n_persons, spec, mirror, weights, min_det, points,
                                     n_rays, residual);
     const int total = n_persons * spec.n_joints_out;
+    a.cov = cov;
+    if (cov) {
+        hipLaunchKernelGGL(triangulate_joints_cov_kernel, dim3((total + 63) / 64), dim3(64), 0, stream, a);
+        return launch_status("triangulate_joints_cov");
+    }
     hipLaunchKernelGGL(triangulate_joints_kernel, dim3((total + 63) / 64), dim3(64), 0, stream, a);
     return launch_status("triangulate_joints");
 }

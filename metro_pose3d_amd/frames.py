@@ -1076,12 +1076,16 @@ def _check_rig(cameras, fi: np.ndarray, n_boxes: int) -> None:
 
 
 def _world_poses(call: _Call, model_path, cameras, fi: np.ndarray, weights: str, min_angle_deg: float, person_index=None,
-                 match=None):
-    """The chain triangulate_poses_in_frames and match_poses_in_frames share -> (WorldPoses, None or (person_index, cost,
-    n_pairs)).  The persons' crop rows come from the host (person_index: person_groups, uploaded) or, with
-    match = (max_cost_mm, clip_mm, min_joints), from metro_view_affinity and metro_cluster_views on the forward's outputs; the
-    triangulation launch then runs over the upper bound of n persons and the count is read in the call's synchronisation."""
-    from metro_pose3d_amd.heads import cluster_views, triangulate_joints, view_affinity
+                 match=None, step_index=None, covariance: bool = False, then=None):
+    """The chain triangulate_poses_in_frames, match_poses_in_frames and follow_world_poses_in_frames share -> (WorldPoses,
+    None or (person_index, cost, n_pairs), None or (covariance [P, Jout, 9], what `then` returned)).  The persons' crop rows
+    come from the host (person_index: person_groups, uploaded) or, with match = (max_cost_mm, clip_mm, min_joints), from
+    metro_view_affinity and metro_cluster_views on the forward's outputs; the triangulation launch then runs over the upper
+    bound of n persons and the count is read in the call's synchronisation.
+    step_index (host int32 [n], with match): the affinity is gated by time step.  covariance: the triangulation launch also
+    writes the covariance of every joint.  then(spec, n_views, poses, covariance, rows, starts, n_persons): enqueued after the
+    triangulation, before the synchronisation, on the unsliced outputs over the n persons (with match and covariance)."""
+    from metro_pose3d_amd.heads import cluster_views, triangulate_joints, view_affinity_steps
     from metro_pose3d_amd.inference import _engine_for
     sk = _model_skeleton(model_path)
     n, nv = len(call.boxes), len(call.vs.zoom)
@@ -1095,9 +1099,9 @@ def _world_poses(call: _Call, model_path, cameras, fi: np.ndarray, weights: str,
     i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=device)
     if n == 0:
         return (WorldPoses(f32(0, sk.n_out, 3), i32(0, sk.n_out), f32(0, sk.n_out), f32(0, sk.n_out, 2), sk.edges_array(), names),
-                None if match is None else (i32(0), f32(0, 0), i32(0, 0)))
+                None if match is None else (i32(0), f32(0, 0), i32(0, 0)), (f32(0, sk.n_out, 9), None) if covariance else None)
     moments = weights == 'covariance'
-    matched = n_persons = None
+    matched = n_persons = more = None
     with torch.cuda.device(device):
         eng = _engine_for(model_path, call.precision, device, m)
         crops, places = _warp_views(call.frames, cameras, call.boxes, call.fi, call.vs, eng.spec.proc_side, device, call.crop_dtype)
@@ -1106,12 +1110,15 @@ def _world_poses(call: _Call, model_path, cameras, fi: np.ndarray, weights: str,
         if match is None:
             rows, starts = (_upload(a, device) for a in person_groups(person_index, fi, nv))
         else:
-            cost, n_pairs = view_affinity(coords01, cov01, places.reshape(-1), _upload(fi.astype(np.int32), device), eng.spec, nv,
-                                          weights, min_angle_deg, match[1], match[2])
+            cost, n_pairs = view_affinity_steps(coords01, cov01, places.reshape(-1), _upload(fi.astype(np.int32), device),
+                                                None if step_index is None else _upload(np.asarray(step_index, np.int32), device),
+                                                eng.spec, nv, weights, min_angle_deg, match[1], match[2])
             labels, n_persons, rows, starts = cluster_views(cost, match[0], nv)
             matched = (labels, cost, n_pairs)
-        poses, n_rays, residual = triangulate_joints(coords01, cov01, places.reshape(-1), rows, starts, eng.spec, weights,
-                                                     min_angle_deg)
+        poses, n_rays, residual, *cov = triangulate_joints(coords01, cov01, places.reshape(-1), rows, starts, eng.spec, weights,
+                                                           min_angle_deg, covariance)
+        if covariance:
+            more = (cov[0], then(eng.spec, nv, poses, cov[0], rows, starts, n_persons) if then is not None else None)
         poses_v, keypoints_v = f32(m, sk.n_out, 3), f32(m, sk.n_out, 2)
         mirror = _upload(np.asarray(sk.out_mirror, np.int32), device)
         ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
@@ -1124,8 +1131,10 @@ def _world_poses(call: _Call, model_path, cameras, fi: np.ndarray, weights: str,
         if match is not None:
             n_bad, count = n_bad
             poses, n_rays, residual = poses[:count], n_rays[:count], residual[:count]
+            if covariance:
+                more = (more[0][:count], more[1])
         _raise_on_non_finite(eng.spec, call.precision, n_bad, m)
-    return WorldPoses(poses, n_rays, residual, keypoints, sk.edges_array(), names), matched
+    return WorldPoses(poses, n_rays, residual, keypoints, sk.edges_array(), names), matched, more
 
 
 # ---- the same, with the persons found on the device: cross-view association (metro_view_affinity, metro_cluster_views) ----
@@ -1177,8 +1186,8 @@ def match_poses_in_frames(frames, boxes, model_path, cameras, frame_index, max_c
     _check_rig(cameras, fi, n_boxes)
     call = _checked_call(frames, boxes, fi, 'world', views, geometry, precision, check_finite, pixel_format, color_matrix,
                          crop_dtype)
-    world, matched = _world_poses(call, model_path, cameras, fi, weights, min_angle_deg,
-                                  match=(float(max_cost_mm), float(clip_mm), None if min_joints is None else int(min_joints)))
+    world, matched, _ = _world_poses(call, model_path, cameras, fi, weights, min_angle_deg,
+                                     match=(float(max_cost_mm), float(clip_mm), None if min_joints is None else int(min_joints)))
     return MatchedPoses(*matched, world)
 
 
@@ -1438,3 +1447,127 @@ def follow_poses_in_frames(frames, boxes, model_path, cameras, frame_index, time
                                                           accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, tracks.state)
     smoothed = TrackPoses(poses, velocity, covariance, used, raw, tracks.state, raw.joint_edges, raw.joint_names)
     return FollowedPoses(found.track_index, found.track_id, found.cost, found.n_new, found.n_dropped, tracks, smoothed)
+
+
+# ---- several calibrated cameras over time: persons matched across cameras, triangulated, followed and smoothed in the world ----
+
+MAX_WORLD_FRAMES = 64                # frames (camera exposures) of one follow_world_poses_in_frames call
+
+
+class SmoothedWorldPoses(NamedTuple):
+    """The smoothing launch's outputs in FollowedWorldPoses, one row per person found."""
+    poses: torch.Tensor                  # float32 [P, Jout, 3] world mm: filtered / smoothed (untracked persons: world.poses)
+    velocity: torch.Tensor               # float32 [P, Jout, 3] mm/s (NaN for untracked persons)
+    covariance: torch.Tensor             # float32 [P, Jout, 3, 3] mm^2 of the position estimate (untracked persons: their R)
+    used: torch.Tensor                   # uint8 [P, Jout]: 1 where the person's joint entered the update
+    state: torch.Tensor                  # float64 [T, Jout, 28]: tracks.state
+
+
+class FollowedWorldPoses(NamedTuple):
+    """What follow_world_poses_in_frames returns; P = the persons found (one per person and time step)."""
+    person_index: torch.Tensor           # int32 [n] on the device: the person of every box, numbered by their lowest box
+    cost: torch.Tensor                   # float32 [n, n] mm: match_poses_in_frames' cost, +inf also across time steps
+    n_pairs: torch.Tensor                # int32 [n, n]
+    world: WorldPoses                    # the triangulated poses, one row per person found
+    world_covariance: torch.Tensor       # float32 [P, Jout, 9] mm^2: covariance of every triangulated joint, NaN where the joint is
+    person_step: torch.Tensor            # int32 [P]: the time step of the person (index into the sorted distinct timestamps), -1: none
+    track_index: torch.Tensor            # int32 [P]: the slot of every person, -1 untracked
+    track_id: torch.Tensor               # int32 [P]: the persistent id of its track, -1 untracked
+    track_cost: torch.Tensor             # float32 [P] mm: the cost at which a person continued its track (NaN: born here, or untracked)
+    n_new: torch.Tensor                  # int32 [1]: tracks born in this call
+    n_dropped: torch.Tensor              # int32 [1]: persons of the steps left untracked (no free slot, or no finite joint)
+    tracks: TrackTable                   # the table after this call (pass it to the next)
+    smoothed: SmoothedWorldPoses
+
+
+def follow_world_poses_in_frames(frames, boxes, model_path, cameras, frame_index, timestamps, tracks: Optional[TrackTable] = None,
+                                 capacity: int = 64, match_max_cost_mm: float = 200.0, match_clip_mm: float = 500.0,
+                                 match_min_joints: Optional[int] = None, weights: str = 'covariance', min_angle_deg: float = 2.0,
+                                 max_cost_mm: float = 300.0, clip_mm: float = 600.0, min_joints: Optional[int] = None,
+                                 max_age_s: float = 1.0, mode: str = 'smooth', measurement: str = 'covariance',
+                                 accel_psd: float = 4e6, sigma_floor_mm: float = 1.0, cov_scale: float = 1.0,
+                                 initial_speed_mm_s: float = 2000.0, gate=None, views=None, precision: Optional[str] = None,
+                                 check_finite: Optional[bool] = None, geometry: str = 'auto', pixel_format: str = 'rgb',
+                                 color_matrix: str = 'bt601', crop_dtype: str = 'float32') -> FollowedWorldPoses:
+    """A calibrated rig's video: a person detector's boxes per camera and per exposure, unordered and without identity ->
+    FollowedWorldPoses: the boxes matched across the cameras of each exposure (match_poses_in_frames), every person found
+    triangulated in the world with the covariance of each joint, the persons followed from exposure to exposure under ids that
+    persist (follow_poses_in_frames' association, here on world poses: neither bone lengths nor a root depth are needed) and
+    smoothed by the Kalman / RTS launch with the triangulation's covariance as measurement noise.
+
+    frames: the exposures of all cameras, one frame each; cameras: a list with one Camera per frame (a camera's Camera repeats
+    for each of its exposures); frame_index [n]: the frame of each box, host integers.  timestamps: seconds, one per frame or
+    one per box (follow_poses_in_frames' rule); the frames that share a timestamp form one time step, one exposure of the rig.
+    At most 128 boxes and 64 frames per call.
+    match_max_cost_mm, match_clip_mm, match_min_joints, weights and min_angle_deg are match_poses_in_frames' max_cost_mm,
+    clip_mm, min_joints, weights and min_angle_deg; max_cost_mm, clip_mm, min_joints, max_age_s, mode, measurement, accel_psd,
+    sigma_floor_mm, cov_scale, initial_speed_mm_s and gate are follow_poses_in_frames'; all keep their defaults there, which
+    are design choices, not measurements (heads.view_affinity, heads.associate_tracks and heads.smooth_tracks have the
+    reasoning).  tracks and capacity as in follow_poses_in_frames: the table carries over between calls, so a stream cut into
+    calls at step boundaries gets the ids and filter states one long call gives.
+    Two boxes of different time steps are never matched (their cost is +inf, as for two boxes of one frame), so a person found
+    lives in one step: P counts persons per step.  With weights 'uniform' exactly meeting rays give a zero covariance;
+    sigma_floor_mm keeps the measurement noise positive definite.
+    A person seen by one camera only has NaN world joints and no step (person_step -1): it is in no step of the association,
+    stays untracked (track_index -1) and its track is bridged by the motion model until max_age_s.  A person seen by several
+    cameras none of whose joints could be triangulated is in its step, untracked and counted in n_dropped.
+    One enqueue chain: match_poses_in_frames' own up to the forward, then, with no host work in between and all over the upper
+    bound of n persons, metro_view_affinity_steps, metro_cluster_views, metro_triangulate_joints_cov, metro_person_steps,
+    metro_associate_tracks and metro_smooth_tracks; the call's one synchronisation stays the finite screen, which also brings
+    the number of persons, to which the per-person outputs are sliced.
+    ValueError before any launch for more than 128 boxes or 64 frames, cameras=None, timestamps that are not finite or match
+    neither frames nor boxes, capacity outside [1, 128], a tracks that is no table or has another joint count than the model,
+    and whatever match_poses_in_frames and follow_poses_in_frames refuse of their keywords."""
+    from metro_pose3d_amd.heads import (MATCH_MAX_BOXES, associate_tracks, association_params, matching_params, person_steps,
+                                        smooth_tracks, smoothing_params, triangulation_min_det)
+    triangulation_min_det(weights, min_angle_deg)
+    matching_params(match_clip_mm, match_min_joints, match_max_cost_mm)
+    smoothing_params(mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate)
+    association_params(max_cost_mm, clip_mm, min_joints, max_age_s)
+    n_boxes = _n_boxes(boxes)
+    fi = np.asarray(_host_array(frame_index), np.int64).reshape(-1)
+    if len(fi) != n_boxes:
+        raise ValueError(f'frame_index must hold one value per box ({n_boxes}), got {len(fi)}')
+    if n_boxes > MATCH_MAX_BOXES:
+        raise ValueError(f'{n_boxes} boxes: matching takes at most {MATCH_MAX_BOXES} per call')
+    if len(np.unique(fi)) > MAX_WORLD_FRAMES:
+        raise ValueError(f'{len(np.unique(fi))} frames: at most {MAX_WORLD_FRAMES} per call')
+    _check_rig(cameras, fi, n_boxes)
+    times = _box_times(timestamps, fi, n_boxes)
+    step_times, box_step = np.unique(times, return_inverse=True)
+    if tracks is None:
+        new_track_table(capacity, 1, 'cpu')                 # the capacity check, before any launch
+    else:
+        _check_track_table(tracks, capacity)
+    call = _checked_call(frames, boxes, fi, 'world', views, geometry, precision, check_finite, pixel_format, color_matrix,
+                         crop_dtype)
+    sk = _model_skeleton(model_path)
+    if min_joints is not None and min_joints > sk.n_out:
+        raise ValueError(f'min_joints must be at most the {sk.n_out} output joints of the model, got {min_joints!r}')
+    if tracks is not None and tracks[0].shape[1] != sk.n_out:
+        raise ValueError(f'tracks.state holds {tracks[0].shape[1]} joints, the model has {sk.n_out}')
+    device = _call_device(call.boxes, call.frames)
+    tracks = new_track_table(capacity, sk.n_out, device) if tracks is None else TrackTable(*tracks)
+
+    def then(spec, n_views, poses, cov, rows, starts, n_persons):
+        person_step, person_times, step_rows, step_starts = person_steps(rows, starts, n_persons, box_step, step_times, n_views)
+        found = associate_tracks(poses, cov, person_times, step_rows, step_starts, tracks.state, tracks.ids, tracks.next_id,
+                                 max_cost_mm, clip_mm, min_joints, max_age_s, measurement, accel_psd, sigma_floor_mm, cov_scale,
+                                 initial_speed_mm_s, gate)
+        return person_step, found, smooth_tracks(poses, cov, person_times, found.rows, found.starts, mode, measurement, accel_psd,
+                                                 sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, tracks.state)
+
+    match = (float(match_max_cost_mm), float(match_clip_mm), None if match_min_joints is None else int(match_min_joints))
+    world, matched, (cov, followed) = _world_poses(call, model_path, cameras, fi, weights, min_angle_deg, match=match,
+                                                   step_index=box_step, covariance=True, then=then)
+    p = len(world.poses)
+    if followed is None:                                    # no boxes: no launch
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=device)
+        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=device)
+        smoothed = SmoothedWorldPoses(f32(0, sk.n_out, 3), f32(0, sk.n_out, 3), f32(0, sk.n_out, 3, 3),
+                                      torch.zeros((0, sk.n_out), dtype=torch.uint8, device=device), tracks.state)
+        return FollowedWorldPoses(*matched, world, cov, i32(0), i32(0), i32(0), f32(0), i32(1), i32(1), tracks, smoothed)
+    person_step, found, (poses, velocity, covariance, used) = followed
+    smoothed = SmoothedWorldPoses(poses[:p], velocity[:p], covariance[:p], used[:p], tracks.state)
+    return FollowedWorldPoses(*matched, world, cov, person_step[:p], found.track_index[:p], found.track_id[:p], found.cost[:p],
+                              found.n_new, found.n_dropped, tracks, smoothed)

@@ -9,8 +9,11 @@ through the C ABI (csrc/heads.hip).  Names and argument meaning follow the refer
                             their crops, uniform or heat-map-covariance weights (nothing in the reference: one camera each)
   view_affinity             how close the per-joint rays of every two boxes of several cameras pass: the cost matrix of
                             cross-view association (nothing in the reference: one camera each)
+  view_affinity_steps       the same gated by time step: boxes of different exposures of the rig are never compared
   cluster_views             constrained complete-linkage clustering of that matrix: person_index and the CSR grouping
                             triangulate_joints reads, all on the device
+  person_steps              the time step of every person cluster_views found and the time-step CSR associate_tracks reads,
+                            on the device
   associate_tracks          which box of a video continues which track: greedy assignment on predicted poses, births and the
                             CSR grouping smooth_tracks reads, one workgroup
   smooth_tracks             poses of tracked persons over time: constant-velocity Kalman filter / RTS smoother per track and
@@ -152,7 +155,8 @@ def _i32(x, dev) -> torch.Tensor:
 
 
 def triangulate_joints(coords01: torch.Tensor, cov01: Optional[torch.Tensor], places: torch.Tensor, rows, starts,
-                       spec: ModelSpec, weights: str = 'covariance', min_angle_deg: float = 2.0):
+                       spec: ModelSpec, weights: str = 'covariance', min_angle_deg: float = 2.0,
+                       return_covariance: bool = False):
     """World joints of P persons from the rays of their crop rows, one metro_triangulate_joints launch.
     coords01 [m,J_head,3] and (weights 'covariance') cov01 [m,J_head,6] as the forward writes them, `places` a uint8 device
     tensor of m MetroPlacement records (the crops' virtual cameras), person p owning the crop rows rows[starts[p]:starts[p+1]]
@@ -160,7 +164,12 @@ def triangulate_joints(coords01: torch.Tensor, cov01: Optional[torch.Tensor], pl
     n_rays int32 [P,Jout], residual [P,Jout] mm) on the device.  'uniform': the point nearest to the rays; 'covariance': a
     second solve that weights each ray by 1 / (sigma^2 z^2), its heat-map's variance carried to the joint's depth.  A joint
     seen by fewer than two rays, or whose rays are within min_angle_deg of parallel (det of the normalised system below
-    sin^2(min_angle) / 4), is NaN; n_rays still counts its usable rays."""
+    sin^2(min_angle) / 4), is NaN; n_rays still counts its usable rays.
+    return_covariance=True: one metro_triangulate_joints_cov launch instead, the same three outputs bit for bit and a fourth,
+    covariance [P,Jout,9] mm^2 (row-major symmetric 3x3, what smooth_tracks and associate_tracks read): the inverse of the
+    final solve's system, 'covariance': (sum w (I - d d^T))^-1, w being an inverse variance; 'uniform':
+    s^2 (sum (I - d d^T))^-1 with s^2 = sum |p|^2 / (2 k - 3) from the distances of the point to its k rays; NaN where the
+    joint is."""
     min_det = triangulation_min_det(weights, min_angle_deg)
     nj, n_out = spec.skeleton.n_head, spec.skeleton.n_out
     if coords01.dim() != 3 or tuple(coords01.shape[1:]) != (nj, 3):
@@ -182,10 +191,16 @@ def triangulate_joints(coords01: torch.Tensor, cov01: Optional[torch.Tensor], pl
     points = torch.empty((n_persons, n_out, 3), dtype=torch.float32, device=dev)
     n_rays = torch.empty((n_persons, n_out), dtype=torch.int32, device=dev)
     residual = torch.empty((n_persons, n_out), dtype=torch.float32, device=dev)
+    cov = torch.empty((n_persons, n_out, 9), dtype=torch.float32, device=dev) if return_covariance else None
     if n_persons == 0:
-        return points, n_rays, residual
+        return (points, n_rays, residual, cov) if return_covariance else (points, n_rays, residual)
     cs = spec.to_c(1)
     mirror = torch.from_numpy(np.asarray(spec.skeleton.out_mirror, dtype=np.int32)).to(dev)
+    if return_covariance:
+        check(lib.metro_triangulate_joints_cov(_p(coords01), _p(cov01), _p(places), m, _p(rows), rows.numel(), _p(starts),
+                                               n_persons, C.byref(cs), _p(mirror), TRI_WEIGHTS[weights], min_det, _p(points),
+                                               _p(n_rays), _p(residual), _p(cov), _stream(dev)), 'metro_triangulate_joints_cov')
+        return points, n_rays, residual, cov
     check(lib.metro_triangulate_joints(_p(coords01), _p(cov01), _p(places), m, _p(rows), rows.numel(), _p(starts),
                                        n_persons, C.byref(cs), _p(mirror), TRI_WEIGHTS[weights], min_det, _p(points), _p(n_rays),
                                        _p(residual), _stream(dev)), 'metro_triangulate_joints')
@@ -230,6 +245,20 @@ def view_affinity(coords01: torch.Tensor, cov01: Optional[torch.Tensor], places:
     each weighted ('covariance') by 1 / (sigma_a^2 t_a^2 + sigma_b^2 t_b^2), the heat-map variances carried to where the rays
     pass.  +inf on the diagonal, for two boxes on one frame (a person appears once per camera) and where fewer than
     min_joints * n_views ray pairs count (min_joints None: (Jout + 1) // 2).  At most 128 boxes."""
+    return _view_affinity(coords01, cov01, places, frame_index, None, spec, n_views, weights, min_angle_deg, clip_mm, min_joints)
+
+
+def view_affinity_steps(coords01: torch.Tensor, cov01: Optional[torch.Tensor], places: torch.Tensor, frame_index, step_index,
+                        spec: ModelSpec, n_views: int = 1, weights: str = 'covariance', min_angle_deg: float = 2.0,
+                        clip_mm: float = 500.0, min_joints: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """view_affinity gated by time step, one metro_view_affinity_steps launch.  step_index [n] (ints or a tensor): the time step
+    of each box, one exposure of the rig; two boxes of different steps cost +inf with n_pairs 0, as two boxes of one frame do;
+    every other entry has view_affinity's bits.  step_index None is view_affinity.  (A function of its own: view_affinity's
+    parameter list is pinned.)"""
+    return _view_affinity(coords01, cov01, places, frame_index, step_index, spec, n_views, weights, min_angle_deg, clip_mm, min_joints)
+
+
+def _view_affinity(coords01, cov01, places, frame_index, step_index, spec, n_views, weights, min_angle_deg, clip_mm, min_joints):
     triangulation_min_det(weights, min_angle_deg)
     matching_params(clip_mm, min_joints)
     nj, n_out = spec.skeleton.n_head, spec.skeleton.n_out
@@ -252,6 +281,10 @@ def view_affinity(coords01: torch.Tensor, cov01: Optional[torch.Tensor], places:
     n_fi = int(frame_index.numel() if isinstance(frame_index, torch.Tensor) else np.asarray(frame_index).size)
     if n_fi != n:
         raise ValueError(f'frame_index must hold one value per box ({n}), got {n_fi}')
+    if step_index is not None:
+        n_si = int(step_index.numel() if isinstance(step_index, torch.Tensor) else np.asarray(step_index).size)
+        if n_si != n:
+            raise ValueError(f'step_index must hold one value per box ({n}), got {n_si}')
     dev = coords01.device
     cost = torch.empty((n, n), dtype=torch.float32, device=dev)
     n_pairs = torch.empty((n, n), dtype=torch.int32, device=dev)
@@ -264,6 +297,12 @@ def view_affinity(coords01: torch.Tensor, cov01: Optional[torch.Tensor], places:
     cs = spec.to_c(1)
     mirror = torch.from_numpy(np.asarray(spec.skeleton.out_mirror, dtype=np.int32)).to(dev)
     min_sin2 = float(np.sin(np.radians(float(min_angle_deg))) ** 2)
+    if step_index is not None:
+        si = _i32(step_index, dev).reshape(-1)
+        check(lib.metro_view_affinity_steps(_p(coords01), _p(cov01), _p(places), C.byref(cs), _p(mirror), _p(fi), _p(si), n, n_views,
+                                            TRI_WEIGHTS[weights], min_sin2, float(clip_mm), int(min_joints) * n_views, _p(cost),
+                                            _p(n_pairs), _stream(dev)), 'metro_view_affinity_steps')
+        return cost, n_pairs
     check(lib.metro_view_affinity(_p(coords01), _p(cov01), _p(places), C.byref(cs), _p(mirror), _p(fi), n, n_views,
                                   TRI_WEIGHTS[weights], min_sin2, float(clip_mm), int(min_joints) * n_views, _p(cost), _p(n_pairs),
                                   _stream(dev)), 'metro_view_affinity')
@@ -299,6 +338,43 @@ def cluster_views(cost: torch.Tensor, max_cost_mm: float, n_views: int = 1):
     check(_lib.load().metro_cluster_views(_p(cost), n, n_views, float(max_cost_mm), _p(person_index), _p(n_persons), _p(rows),
                                           _p(starts), _stream(dev)), 'metro_cluster_views')
     return person_index, n_persons, rows, starts
+
+
+def person_steps(rows, starts, n_persons, box_step, step_times, n_views: int = 1):
+    """The time step of every person cluster_views found, and the persons as the time-step CSR associate_tracks reads, one
+    metro_person_steps launch (one workgroup): no host work between clustering and association.  rows, starts [n + 1] and
+    n_persons [1]: cluster_views' CSR and count, device tensors, n <= 128 the upper bound of the persons; box_step [n_boxes]
+    (ints or a tensor): the step of each box; step_times [S] seconds, ascending (host values or a tensor).
+    -> (person_step int32 [n]: the smallest step among the boxes of the person's group, -1 for persons at or past the count
+    and for empty groups (a person seen by one camera); person_times float64 [n]: step_times of that step, NaN where it is
+    -1; step_rows int32 [n]: the persons with a step sorted by (step, person), -1 past their number; step_starts int32
+    [S + 1], step_starts[S] the number of persons with a step), all on the device.  Row and step values out of range are
+    skipped.  associate_tracks takes person_times, step_rows and step_starts as they are."""
+    if not isinstance(starts, torch.Tensor) or not isinstance(rows, torch.Tensor) or not isinstance(n_persons, torch.Tensor):
+        raise ValueError('rows, starts and n_persons must be the device tensors cluster_views returned')
+    if starts.numel() < 1 or n_persons.numel() != 1:
+        raise ValueError(f'starts must hold n + 1 offsets and n_persons one count, got {starts.numel()} and {n_persons.numel()}')
+    n = int(starts.numel()) - 1
+    if n > MATCH_MAX_BOXES:
+        raise ValueError(f'{n} persons: matching takes at most {MATCH_MAX_BOXES}')
+    n_views = _check_n_views(n_views, int(rows.numel()))
+    dev = starts.device
+    rows, starts, n_persons = _i32(rows, dev).reshape(-1), _i32(starts, dev).reshape(-1), _i32(n_persons, dev).reshape(-1)
+    box_step = _i32(box_step, dev).reshape(-1)
+    if not isinstance(step_times, torch.Tensor):
+        step_times = torch.from_numpy(np.ascontiguousarray(np.asarray(step_times, np.float64).reshape(-1)))
+    step_times = step_times.to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+    n_steps = int(step_times.numel())
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    person_step, step_rows, step_starts = i32(n), i32(n), i32(n_steps + 1)
+    person_times = torch.empty((n,), dtype=torch.float64, device=dev)
+    if n == 0:
+        step_starts.zero_()
+        return person_step, person_times, step_rows, step_starts
+    check(_lib.load().metro_person_steps(_p(rows), rows.numel(), _p(starts), _p(n_persons), n, n_views, _p(box_step), box_step.numel(),
+                                         _p(step_times), n_steps, _p(person_step), _p(person_times), _p(step_rows), _p(step_starts),
+                                         _stream(dev)), 'metro_person_steps')
+    return person_step, person_times, step_rows, step_starts
 
 
 SMOOTH_MODES = {'filter': _lib.METRO_SMOOTH_FILTER, 'smooth': _lib.METRO_SMOOTH_RTS}
