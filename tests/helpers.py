@@ -185,6 +185,98 @@ def run_softargmax(lib, dev, spec, logits, precise):
     return out.cpu().numpy()
 
 
+# ---- batches of twins: a call of n crops built from p oracle-checked images, every position held through its twin ------------------
+
+TWIN_GROUPS = (2, 4, 8, 16)     # images per tile / per block round the kernels walk in: aligned groups of these sizes
+
+
+def _assignment_faults(a, p):
+    """What keeps `a` from being a crop assignment (crop_assignment's conditions); None if nothing does."""
+    n = len(a)
+    if not np.array_equal(a[:p], np.arange(p)) or a[n - 1] != p - 1:
+        return 'the first p positions are not 0..p-1, or the last is not p - 1'
+    for s in range(1, n):
+        if np.array_equal(a[:n - s], a[s:]):
+            return f'a shift by {s} images maps the sequence onto itself'
+    for g in TWIN_GROUPS:
+        groups = a[:n // g * g].reshape(-1, g)
+        same = np.flatnonzero((groups[:-1] == groups[1:]).all(axis=1)) if 2 * g <= n else []
+        if len(same):
+            return f'the aligned groups of {g} images at {same[0] * g} and {(same[0] + 1) * g} have the same pattern'
+    at = np.arange(n)
+    for s in range(1, n):                   # out[i] = table[a[(i + s) % n]]: the twin check sees it iff out[i] != out[a[i]] somewhere
+        if np.array_equal(a[(at + s) % n], a[(a + s) % n]):
+            return f'a rotation of the batch by {s} images passes the twin check'
+    return None
+
+
+def crop_assignment(n, p, seed):
+    """int64 [n]: position i of a call of n crops holds base image assign[i] of p -- the layout of a batch whose first p
+    positions are compared with an oracle and whose other positions must carry the bits of their twin (assert_twins).
+
+    Unlike `i % p` the sequence has no symmetry a misplaced tile could hide behind (each is asserted here):
+      * assign[:p] is 0..p-1 and, for n > p, assign[n-1] == p - 1: the first and the last position of the call are anchored to
+        different oracle-checked images, and every base image occurs;
+      * no shift maps the sequence onto itself: for every s in 1..n-1 some assign[i] != assign[i + s];
+      * for g in 2, 4, 8, 16 with 2 g <= n no two adjacent aligned groups of g images have the same pattern, so a swap of two
+        such groups (two blocks exchanging tiles, a tile stored into the next tile's slot) always moves some image onto a
+        different one.  g = 1 cannot be had: with n > p some neighbours are equal, and a swap of two equal neighbours changes
+        nothing in the inputs either -- it is undetectable by construction;
+      * no rotation of the batch by 1..n-1 images passes assert_twins on its own (a rotated output whose first p positions still
+        look like p distinct images to the gather).
+    n <= p gives the identity.  Deterministic: the middle is drawn from np.random.default_rng([seed, n, p]), an element that
+    would complete a repeated group is redrawn among the values that do not (with none left, the 16 positions in front are drawn
+    again), and the seed is stepped until everything holds (n > p needs p >= 2)."""
+    if n <= p:
+        return np.arange(n)
+    if p < 2:
+        raise ValueError('a batch of twins needs at least two base images')
+    for step in range(1000):
+        rng = np.random.default_rng([seed + step, n, p])
+        a = rng.integers(0, p, n)
+        a[:p] = np.arange(p)
+        a[n - 1] = p - 1
+        i, redraws = p, 0
+        while i < n and redraws < 100:
+            # the values that would make the aligned group ending at i a copy of the group in front of it
+            bad = {a[i - g] for g in TWIN_GROUPS if (i + 1) % g == 0 and i + 1 >= 2 * g and np.array_equal(a[i - g + 1:i], a[i - 2 * g + 1:i - g])}
+            free = [v for v in ([p - 1] if i == n - 1 else range(p)) if v not in bad]
+            if a[i] in free:
+                i += 1
+            elif free:
+                a[i] = free[rng.integers(len(free))]
+                i += 1
+            else:                                   # no value is left (p = 2): draw the last 16 positions again
+                back = max(p, i - 16)
+                a[back:min(i + 1, n - 1)] = rng.integers(0, p, min(i + 1, n - 1) - back)
+                i, redraws = back, redraws + 1
+        if i == n and _assignment_faults(a, p) is None:
+            break
+    fault = _assignment_faults(a, p)
+    assert fault is None, f'crop_assignment({n}, {p}, {seed}): {fault}'
+    return a
+
+
+def lay_out_twins(base, assign):
+    """The batch base[assign]: [n, ...] from the p base images, a device tensor or a numpy array like `base`."""
+    if isinstance(base, np.ndarray):
+        return np.ascontiguousarray(base[assign])
+    return base[torch.as_tensor(assign, device=base.device)].contiguous()
+
+
+def assert_twins(out, assign, p, what):
+    """Every position of `out` [n, ...] carries the bits of its base image's first occurrence: out == out[:p][assign], one
+    gather on out's device (on the bit patterns of float tensors: NaN equals NaN)."""
+    assert out.shape[0] == len(assign), (what, out.shape, len(assign))
+    if out.is_floating_point():
+        out = out.contiguous().view({2: torch.int16, 4: torch.int32, 8: torch.int64}[out.element_size()])
+    want = out[:p][torch.as_tensor(assign, device=out.device)]
+    if torch.equal(out, want):
+        return
+    i = int((out != want).reshape(len(assign), -1).any(dim=1).nonzero()[0])
+    raise AssertionError(f'{what}: position {i} of {len(assign)} differs from its twin, position {int(assign[i])} (base image {int(assign[i])})')
+
+
 def oracle_spec(spec):
     """metro_pose3d_amd.ModelSpec -> oracle.spec.OracleSpec (same field names by design)."""
     from oracle.spec import OracleSpec

@@ -344,7 +344,10 @@ def test_batch_independence_of_the_other_baseline_configs(cuda, arch, stride, da
     per-GPU batch (BASELINE.json configs[2..4] sharded 8 ways) other kernel instantiations run (tests/test_kernel_coverage.py
     checks each of them on its own).  This transfers the n = 1 parity to the real batch END TO END: while every tile shape
     accumulates in the same order (stride 16: below 128 crops) the batch and its split 1 + (n - 1) must give the same BITS, layer
-    outputs included; strides 4 and 8 change tile shape exactly at their shard size (below)."""
+    outputs included; strides 4 and 8 change tile shape exactly at their shard size (below), and from the first such layer on this
+    test compares no bits: there the real-batch cases of tests/test_f16_layerwise.py take over (rn101-s8-many19-n2-of-batch32 for
+    C4, rn50-s4-h36m-n2-of-batch16 for C5), which hold EVERY launch of the chain at this batch to the fp16 oracle on the launch's
+    own inputs, and every crop of the call to the bits of its oracle-checked twin."""
     spec = ModelSpec(arch, stride, dataset)
     params, images = _setup(spec, n, gain=synth.logit_gain_for(arch, stride))
     x = torch.from_numpy(images).to(cuda)
@@ -360,7 +363,9 @@ def test_batch_independence_of_the_other_baseline_configs(cuda, arch, stride, da
     # tiles (32-channel chunks: another fp32 summation order) exactly at these per-GPU batches -- 16 crops at stride 4, 32 at
     # stride 8 -- while n - 1 crops stay on 256-pixel tiles.  Up to the first such layer the bits must not depend on the batch;
     # AT it the two tile shapes see the same inputs and may differ by rounding flips only; behind it the two chains are two fp16
-    # realisations of one graph, each held to exact math by the accuracy criterion of the f16 mode.
+    # realisations of one graph, each held to exact math by the accuracy criterion of the f16 mode -- here on crops 0 and n - 1 only,
+    # and loosely.  What holds the layers behind it (and the head) at this batch, launch by launch and for every crop of the call,
+    # are the {'batch': n} cases of tests/test_f16_layerwise.py named in the docstring, not this test.
     kern_m = eng.layer_kernels(n - 1)
     chunk = lambda k: 'kc32' in k
     first = next((i for i in range(len(names)) if chunk(kern_n[i]) != chunk(kern_1[i]) or chunk(kern_n[i]) != chunk(kern_m[i])), None)

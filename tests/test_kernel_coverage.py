@@ -9,9 +9,13 @@ instantiation (a dry run of the dispatch, no device needed), so this file can
     real shape at the configuration's real batch through the single-kernel C-ABI entry point, check that the entry
     point launched exactly the instantiation the plan names (`metro_last_kernel_id`), and compare with the fp64 reference
     on the same fp16 operands (2e-3 of the layer maximum = fp16 output rounding; reference resnet_v2.py:119-138,219-236,
-    resnet_utils.py:82-135, volumetric.py:227-235).  The batch is PERIODIC (image i = image i mod 4): the reference is
-    computed for one period and every other image must carry the same bits as its twin, so each tile position of the
-    launch is held to the oracle at the cost of four images.
+    resnet_utils.py:82-135, volumetric.py:227-235).  The batch is built from FOUR images: the reference is computed for
+    them, at positions 0..3, and every other position must carry the same bits as its twin.  Which image a position holds
+    is drawn so that no shift of the sequence, no rotation of the batch and no swap of two adjacent aligned groups of 2, 4,
+    8 or 16 images maps the layout onto itself (tests/helpers.py: crop_assignment; tests/test_crop_assignment.py plants such
+    faults): a launch that stores whole tiles into other tiles' slots -- with image i = image i mod 4 it would give every
+    position "its twin's bits" whenever it moves results by a multiple of four images -- fails the twin check, so each tile
+    position of the launch is held to the oracle at the cost of four images.
 """
 import ctypes as C
 import zlib
@@ -65,7 +69,7 @@ CONFIGS = {
     'X-rn50-s16-merged53-side64-b1': (ModelSpec(50, 16, 'merged', proc_side=64), 1),
     'X-rn50-s8-J17-side416-b8': (ModelSpec(50, 8, 'h36m', proc_side=416), 8),
 }
-PERIOD = 4
+BASE_IMAGES = 4                 # distinct images of a batch: the oracle's cost per case
 
 # The supported range of the f16 path (test_dispatch_closure): every plan of this grid dispatches only instantiations that a GPU
 # test launches at some shape
@@ -221,22 +225,19 @@ def test_head_partials_slot_covers_large_heat_maps(lib, nb):
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------
-def _periodic(gen, n, shape, cuda, scale=1.0, relu=False):
-    """fp16 [n, *shape] on the device with image i == image i % PERIOD."""
-    p = min(PERIOD, n)
+def _assignment(n, what):
+    """Which of the min(BASE_IMAGES, n) base images each position of the batch holds (H.crop_assignment), seeded by the case."""
+    return H.crop_assignment(n, min(BASE_IMAGES, n), zlib.crc32(what.encode()))
+
+
+def _twins(gen, assign, shape, cuda, scale=1.0, relu=False):
+    """fp16 [n, *shape] on the device with image i == base image assign[i], and the base images as numpy."""
+    p = min(BASE_IMAGES, len(assign))
     base = torch.randn((p,) + tuple(shape), generator=gen, device=cuda, dtype=torch.float32) * scale
     if relu:
         base = base.clamp_min(0)
     base = base.half()
-    reps = (n + p - 1) // p
-    return base.repeat((reps,) + (1,) * len(shape))[:n].contiguous(), base.cpu().numpy()
-
-
-def _assert_periodic(out, n, what):
-    p = min(PERIOD, n)
-    for i in range(p, n, p):
-        k = min(p, n - i)
-        assert torch.equal(out[i:i + k], out[:k]), f'{what}: images {i}..{i + k - 1} differ from their twins 0..{k - 1}'
+    return H.lay_out_twins(base, assign), base.cpu().numpy()
 
 
 def _noted(lib):
@@ -262,28 +263,29 @@ def test_production_dispatch_against_fp64_reference(lib, cuda, cname, layer, kid
     gen.manual_seed(zlib.crc32(f'{cname}/{name}'.encode()))
     rng = np.random.default_rng(zlib.crc32(f'{cname}/{name}/w'.encode()))
     dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(dt))).to(cuda)
-    p = min(PERIOD, n)
+    assign = _assignment(n, f'{cname}/{name}')
     check(lib.metro_kernel_notes(1), 'metro_kernel_notes')
     try:
         if name == 'softargmax' and kid == 'softargmax_finalize<acc32>':
             pytest.skip('launched (and compared) together with the head: see the logits case of this configuration')
         if name == 'softargmax':
-            _softargmax(lib, cuda, spec, n, gen, rng, kid)
+            _softargmax(lib, cuda, spec, assign, gen, rng, kid)
         elif name == 'conv1+pool1':
-            _stem(lib, cuda, li, n, gen, rng, dev, kid)
+            _stem(lib, cuda, li, assign, gen, rng, dev, kid)
         elif name == 'logits' and kid.startswith('head_f16'):
-            _head(lib, cuda, spec, li, n, gen, rng, dev, kid)
+            _head(lib, cuda, spec, li, assign, gen, rng, dev, kid)
         else:
-            _conv(lib, cuda, li, n, gen, rng, dev, kid, name)
+            _conv(lib, cuda, li, assign, gen, rng, dev, kid, name)
     finally:
         lib.metro_kernel_notes(0)
 
 
-def _stem(lib, cuda, li, n, gen, rng, dev, kid):
+def _stem(lib, cuda, li, assign, gen, rng, dev, kid):
     side = 4 * li.h_out
-    p = min(PERIOD, n)
+    n = len(assign)
+    p = min(BASE_IMAGES, n)
     base = torch.rand((p, side, side, 3), generator=gen, device=cuda, dtype=torch.float32)
-    img = base.repeat(((n + p - 1) // p, 1, 1, 1))[:n].contiguous()
+    img = H.lay_out_twins(base, assign)
     w = (rng.standard_normal((64, 7, 7, 3)) * np.sqrt(2.0 / 147)).astype(np.float16)
     b = (rng.standard_normal(64) * 0.5).astype(np.float32)
     wp = np.zeros((64, 7, 8, 4), np.float16)
@@ -293,7 +295,7 @@ def _stem(lib, cuda, li, n, gen, rng, dev, kid):
     check(lib.metro_stem_pool_f32in(H.ptr(img), H.ptr(tw), H.ptr(tb), H.ptr(out), n, side, None), 'metro_stem_pool_f32in')
     torch.cuda.synchronize()
     assert _noted(lib) == [kid], (_noted(lib), kid)
-    _assert_periodic(out, n, kid)
+    H.assert_twins(out, assign, p, kid)
     xi = torch.from_numpy(base.cpu().numpy().astype(np.float16).astype(np.float64)).permute(0, 3, 1, 2)
     conv = torch.nn.functional.conv2d(torch.nn.functional.pad(xi, (3, 3, 3, 3)), torch.from_numpy(w.astype(np.float64)).permute(0, 3, 1, 2),
                                       torch.from_numpy(b.astype(np.float64)), stride=2).half().double()
@@ -301,10 +303,11 @@ def _stem(lib, cuda, li, n, gen, rng, dev, kid):
     _close(out[:p].cpu().numpy(), want, kid)
 
 
-def _head(lib, cuda, spec, li, n, gen, rng, dev, kid):
+def _head(lib, cuda, spec, li, assign, gen, rng, dev, kid):
     from oracle.forward import logits_to_output
     side, k, c = li.h_in, li.c_in, li.c_out
-    x, xb = _periodic(gen, n, (side, side, k), cuda)
+    n = len(assign)
+    x, xb = _twins(gen, assign, (side, side, k), cuda)
     w = (rng.standard_normal((c, k)) * np.sqrt(2.0 / k) * 2.0).astype(np.float16)
     b = (rng.standard_normal(c) * 0.1).astype(np.float32)
     sc = rng.uniform(0.5, 1.5, k).astype(np.float16)
@@ -318,9 +321,9 @@ def _head(lib, cuda, spec, li, n, gen, rng, dev, kid):
                              H.ptr(poses), None), 'metro_head_f16')
     torch.cuda.synchronize()
     assert _noted(lib) == [kid, 'softargmax_finalize<acc32>'], _noted(lib)
-    _assert_periodic(logits, n, kid)
-    _assert_periodic(poses, n, kid)
     p = xb.shape[0]
+    H.assert_twins(logits, assign, p, kid)
+    H.assert_twins(poses, assign, p, kid + ' (poses)')
     xin = np.maximum((xb.astype(np.float64) * sc.astype(np.float64) + sh.astype(np.float64)).astype(np.float16).astype(np.float64), 0)
     ref = xin.reshape(-1, k) @ w.astype(np.float64).T + b.astype(np.float64)
     ref = ref.reshape(p, side, side, c)
@@ -331,25 +334,26 @@ def _head(lib, cuda, spec, li, n, gen, rng, dev, kid):
     assert d <= 2e-3, f'{kid}: poses {d} mm from the exact soft-argmax of the exact logits'
 
 
-def _softargmax(lib, cuda, spec, n, gen, rng, kid):
+def _softargmax(lib, cuda, spec, assign, gen, rng, kid):
     """The two-launch soft-argmax behind a head that is not whole tiles, on fp32 logits at the layer's real side and batch:
     N(0, 4) plus one planted peak per (image, joint) at a random voxel, so no pose is the map centre."""
     from oracle.forward import logits_to_output
     side, j, dd = spec.heatmap_side, spec.skeleton.n_head, spec.depth
-    p = min(PERIOD, n)
+    n = len(assign)
+    p = min(BASE_IMAGES, n)
     base = torch.randn((p, side, side, dd * j), generator=gen, device=cuda, dtype=torch.float32) * 4.0
     for i in range(p):
         for jj in range(j):
             h, w, d = (int(v) for v in rng.integers(0, (side, side, dd)))
             base[i, h, w, d * j + jj] += 12.0
-    logits = base.repeat(((n + p - 1) // p, 1, 1, 1))[:n].contiguous()
+    logits = H.lay_out_twins(base, assign)
     cs = spec.to_c(_lib.METRO_PREC_F16)
     scratch = torch.empty(lib.metro_softargmax_scratch_bytes(n, side, j), dtype=torch.uint8, device=cuda)
     poses = torch.full((n, spec.skeleton.n_out, 3), float('nan'), dtype=torch.float32, device=cuda)
     check(lib.metro_softargmax(H.ptr(logits), n, C.byref(cs), _lib.METRO_PREC_F16, H.ptr(scratch), H.ptr(poses), None), 'metro_softargmax')
     torch.cuda.synchronize()
     assert _noted(lib) == kid.split(' & '), f'the entry point launched {_noted(lib)}, the plan names {kid}'
-    _assert_periodic(poses, n, kid)
+    H.assert_twins(poses, assign, p, kid)
     want = logits_to_output(H.oracle_spec(spec), base.cpu().double().numpy()).numpy()
     got = poses[:p].cpu().numpy()
     assert np.isfinite(got).all(), kid
@@ -359,7 +363,8 @@ def _softargmax(lib, cuda, spec, n, gen, rng, kid):
     assert np.abs(want).max() > 50.0, np.abs(want).max()
 
 
-def _conv(lib, cuda, li, n, gen, rng, dev, kid, name):
+def _conv(lib, cuda, li, assign, gen, rng, dev, kid, name):
+    n = len(assign)
     pair = name.endswith('/shortcut+conv1')
     nxt = '/conv3+' in name
     c_in, c1 = li.c_in, li.c_out
@@ -375,7 +380,7 @@ def _conv(lib, cuda, li, n, gen, rng, dev, kid, name):
     d = H.conv_desc(n, h_in, c_in, h_out, c_out, k, li.stride, li.dilation, li.pad_top, prologue=bool(li.has_prologue),
                     relu=bool(li.relu), residual=has_res, res_h=res_h, res_stride=res_stride,
                     res_offset=res_offset, out_dtype=_lib.METRO_F32 if f32out else _lib.METRO_F16, in_dtype=_lib.METRO_F16)
-    x, xb = _periodic(gen, n, (h_in, h_in, c_in), cuda, relu=not li.has_prologue and k == 3)
+    x, xb = _twins(gen, assign, (h_in, h_in, c_in), cuda, relu=not li.has_prologue and k == 3)
     w = (rng.standard_normal((c_out, k, k, c_in)) * np.sqrt(2.0 / (k * k * c_in))).astype(np.float16)
     b = (rng.standard_normal(c_out) * 0.1).astype(np.float32)
     tw, tb = dev(w, np.float16), dev(b, np.float32)
@@ -386,16 +391,16 @@ def _conv(lib, cuda, li, n, gen, rng, dev, kid, name):
         ts, tsh = dev(pro[0], np.float16), dev(pro[1], np.float16)
     rb = None
     if has_res:
-        tr, rb = _periodic(gen, n, (res_h, res_h, c_out), cuda)
+        tr, rb = _twins(gen, assign, (res_h, res_h, c_out), cuda)
     out = torch.full((n, h_out, h_out, c1), float('nan'), dtype=torch.float32 if f32out else torch.float16, device=cuda)
     out2 = None
     if li.fused_flags & _lib.FUSED_CONV1_IN_FRONT:
-        return _conv1_conv2(lib, cuda, li, n, d, x, xb, tw, tb, w, b, out, rng, dev, kid)
+        return _conv1_conv2(lib, cuda, li, assign, d, x, xb, tw, tb, w, b, out, rng, dev, kid)
     psc = None
     if li.fused_flags & (_lib.FUSED_PROJECTION_SHORTCUT | _lib.FUSED_REBUILT_SHORTCUT):
         assert nxt, 'the in-launch projection shortcut exists in the conv3 + next conv1 launch only'
         cx = 64                                   # the unit's raw input (block1/unit_1: the pooled stem output)
-        xs, xsb = _periodic(gen, n, (h_out, h_out, cx), cuda)
+        xs, xsb = _twins(gen, assign, (h_out, h_out, cx), cuda)
         wsc = (rng.standard_normal((c1, cx)) * np.sqrt(2.0 / cx)).astype(np.float16)
         bsc = (rng.standard_normal(c1) * 0.1).astype(np.float32)
         psc_s = rng.uniform(0.5, 1.5, cx).astype(np.float16)
@@ -434,7 +439,7 @@ def _conv(lib, cuda, li, n, gen, rng, dev, kid, name):
             # block1/unit_2: x_1 = fp16(W3_prev . t2_prev + b) + fp16(Wsc . pre(x0) + bsc) is rebuilt in the launch.  The storing form
             # (what metro_forward_upto runs) gives `out`; the form the plan names must give the SAME second output, and its
             # sub-sampled copy must be those pixels of `out`
-            tp, tpb = _periodic(gen, n, (h_out, h_out, 64), cuda, relu=True)
+            tp, tpb = _twins(gen, assign, (h_out, h_out, 64), cuda, relu=True)
             w3p = (rng.standard_normal((c1, 64)) * np.sqrt(2.0 / 64)).astype(np.float16)
             b3p = (rng.standard_normal(c1) * 0.1).astype(np.float32)
             prev = [tp, dev(w3p, np.float16), dev(b3p, np.float32)]
@@ -526,10 +531,10 @@ def _conv(lib, cuda, li, n, gen, rng, dev, kid, name):
             check(lib.metro_conv_f16(C.byref(d), H.ptr(x), H.ptr(tw), H.ptr(tb), H.ptr(ts), H.ptr(tsh), H.ptr(tr), H.ptr(out), None), 'metro_conv_f16')
     torch.cuda.synchronize()
     assert _noted(lib) == kid.split(' & '), f'the entry point launched {_noted(lib)}, the plan names {kid}'     # (a layer may be two launches)
-    _assert_periodic(out, n, kid)
-    if out2 is not None:
-        _assert_periodic(out2, n, kid + ' (second output)')
     p = xb.shape[0]
+    H.assert_twins(out, assign, p, kid)
+    if out2 is not None:
+        H.assert_twins(out2, assign, p, kid + ' (second output)')
     xin = xb.astype(np.float64)
     if pro is not None:       # fp16 FMA + ReLU, one rounding (v_pk_fma_f16)
         xin = np.maximum((xin * pro[0].astype(np.float64) + pro[1].astype(np.float64)).astype(np.float16).astype(np.float64), 0)
@@ -556,7 +561,7 @@ def _conv(lib, cuda, li, n, gen, rng, dev, kid, name):
         _close(out2[:p].cpu().numpy(), want2, kid + ' (second output)')
 
 
-def _conv1_conv2(lib, cuda, li, n, d, x, xb, tw2, tb2, w2, b2, out, rng, dev, kid):
+def _conv1_conv2(lib, cuda, li, assign, d, x, xb, tw2, tb2, w2, b2, out, rng, dev, kid):
     """conv1 (1x1 on the pre-activated input, folded BN + ReLU) fused in front of the 3x3: t1 is rounded to fp16 once (in LDS)."""
     c = li.c_in
     w1 = (rng.standard_normal((li.c_out, c)) * np.sqrt(2.0 / c)).astype(np.float16)
@@ -568,7 +573,7 @@ def _conv1_conv2(lib, cuda, li, n, d, x, xb, tw2, tb2, w2, b2, out, rng, dev, ki
                                          H.ptr(out), None), 'metro_conv_f16_conv1_conv2')
     torch.cuda.synchronize()
     assert _noted(lib) == kid.split(' & '), f'the entry point launched {_noted(lib)}, the plan names {kid}'     # (a layer may be two launches)
-    _assert_periodic(out, n, kid)
+    H.assert_twins(out, assign, xb.shape[0], kid)
     xin = np.maximum((xb.astype(np.float64) * ps.astype(np.float64) + pb.astype(np.float64)).astype(np.float16).astype(np.float64), 0)
     t1 = np.maximum(xin @ w1.astype(np.float64).T + b1.astype(np.float64), 0).astype(np.float16)
     ref = H.ref_conv_nhwc(t1, w2, b2, 1, 1, 1, li.h_out, relu=True).numpy()
