@@ -873,6 +873,56 @@ int  metro_associate_tracks(const float* d_poses, const float* d_cov, const doub
                             int32_t* d_track_index_out, int32_t* d_track_id_out, float* d_cost_out, int32_t* d_rows_out,
                             int32_t* d_starts_out, int32_t* d_n_new_out, int32_t* d_n_dropped_out, void* stream);
 
+/* ---- next-frame person boxes from the track table: crops between the key frames of a detector ----
+ * Nothing in the reference: one example is one image and its box is given.  Two launches on `stream`, no host work in
+ * between: one thread per (frame, slot) writes dense tables, one workgroup compacts them into rows and appends the
+ * detector's boxes that no predicted box covers.  The table is READ, never written.
+ * Track table as metro_associate_tracks has it: d_state fp64 [T, J, 28], d_ids int32 [T] (-1: free), T = n_tracks in
+ * [1, METRO_ASSOC_MAX], J = n_joints_out in [1, METRO_MAX_JOINTS]; the positions are absolute mm in the frame's camera
+ * (coords METRO_COORDS_CAMERA: r and t of the camera table are not read) or in the world (METRO_COORDS_WORLD).
+ * d_cameras: DEVICE table of n_cameras == 1 (every frame) or n_cameras == n_frames entries; frame_sizes int32 [F, 2] (W, H)
+ * and frame_times fp64 [F] seconds are HOST arrays, copied into the kernel arguments (F = n_frames in [1, METRO_MAX_FRAMES]).
+ * Per (frame f, slot s):
+ * 1. d_ids[s] < 0, no joint with a state (t_last NaN), or frame_times[f] - (the newest t_last of the slot) > max_age_s:
+ *    no box, joint count -1.
+ * 2. Every joint with a state is advanced by dt = max(frame_times[f] - t_last, 0) with the prediction step of
+ *    metro_smooth_tracks (white-noise acceleration q): the position metro_associate_tracks compares a box against, and its P.
+ * 3. Camera point: METRO_COORDS_WORLD R (p - t) (Camera.world_to_camera) from the fp32 entries, in fp64; else p itself.  The
+ *    joint is VISIBLE iff the point is finite, z >= near_mm and, with has_distortion and r2 = (x/z)^2 + (y/z)^2,
+ *    1 + 3 k1 r2 + 5 k2 r2^2 + 7 k3 r2^3 > 0 (the radial polynomial still grows: beyond, it folds a far joint back into the
+ *    image), and its pixel is finite.
+ * 4. Pixel (u, v): the point rounded to fp32, then project_points' fp32 chain in its statement order with has_distortion
+ *    (metro_place_poses' keypoints), else K (x/z, y/z, 1) in fp32.
+ * 5. Margin, fp64: sigma = min(sqrt(max(Pxx, Pyy, Pzz, 0)), max_sigma_mm), mg = n_sigma sigma sqrt(|fx fy|) / z; the joint
+ *    contributes [u - mg, u + mg] x [v - mg, v + mg].
+ * 6. Box, fp64: the union over the visible joints; their count goes to d_joints_dense; fewer than min_joints: no box.  The
+ *    union is scaled about its centre by expand, intersected with [0, W_f] x [0, H_f] when clip != 0, and dropped if then
+ *    narrower or lower than min_side_px.  d_boxes_dense fp64 [F, T, 4] (x, y, w, h), all NaN where there is no box;
+ *    d_joints_dense int32 [F, T].
+ * Rows, capacity F T + n_detections (d_boxes_out fp64 [., 4], d_frame_out, d_slot_out, d_id_out, d_detection_out,
+ * d_n_joints_out int32 [.]): first the boxes present, frame-major then by slot, with their frame, slot, d_ids[slot],
+ * detection -1 and joint count; then the detections (d_det_boxes fp64 [m, 4], d_det_frame int32 [m], both NULL with
+ * n_detections == 0, m <= METRO_PREDICT_MAX_DETECTIONS) in their given order with slot -1, id -1, detection = their index and
+ * joint count -1.  A detection whose frame lies outside [0, F) is dropped and counted in d_counts[4], which the caller must
+ * treat as an error; else one with a non-finite coordinate or w <= 0 or h <= 0 is dropped and counted in d_counts[3]; else
+ * one whose intersection over union with ANY predicted box of its frame is >= iou_max is suppressed and counted in
+ * d_counts[2].  d_counts int32 [5]: rows written, predicted rows, suppressed, bad detections, bad frame indices; rows past
+ * d_counts[0] are not written.
+ * -1 before any launch for J, T, F or n_detections out of range, coords other than METRO_COORDS_CAMERA / _WORLD, a
+ * non-finite or out-of-range q (> 0), max_age_s (>= 0), expand (>= 1), n_sigma (>= 0), max_sigma_mm (>= 0), near_mm (> 0),
+ * min_side_px (>= 0) or iou_max (in (0, 1]), min_joints outside [1, J], n_cameras neither 1 nor F, a NULL pointer, a frame
+ * size < 1 and a non-finite frame time.  With T F == 0 rows and no detections there is nothing to do: no launch, nothing
+ * written, 0. */
+#define METRO_PREDICT_MAX_DETECTIONS 4096
+int  metro_predict_boxes(const double* d_state, const int32_t* d_ids, int32_t n_tracks, int32_t n_joints_out,
+                         const MetroFrameCamera* d_cameras, int32_t n_cameras, const int32_t* frame_sizes,
+                         const double* frame_times, int32_t n_frames, int32_t coords, double q, double max_age_s,
+                         double expand, double n_sigma, double max_sigma_mm, double near_mm, double min_side_px,
+                         int32_t min_joints, int32_t clip, const double* d_det_boxes, const int32_t* d_det_frame,
+                         int32_t n_detections, double iou_max, double* d_boxes_dense, int32_t* d_joints_dense,
+                         double* d_boxes_out, int32_t* d_frame_out, int32_t* d_slot_out, int32_t* d_id_out,
+                         int32_t* d_detection_out, int32_t* d_n_joints_out, int32_t* d_counts, void* stream);
+
 const char* metro_last_error(void);
 int32_t metro_abi_version(void);
 

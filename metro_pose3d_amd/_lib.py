@@ -98,6 +98,7 @@ METRO_MATCH_MAX_BOXES = 128
 METRO_SMOOTH_FILTER, METRO_SMOOTH_RTS = 0, 1
 METRO_SMOOTH_ISOTROPIC, METRO_SMOOTH_COVARIANCE = 0, 1
 METRO_ASSOC_MAX = 128
+METRO_PREDICT_MAX_DETECTIONS = 4096
 
 
 class MetroViewBase(C.Structure):
@@ -205,6 +206,8 @@ SIGNATURES = {
     'metro_associate_tracks': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.POINTER(MetroSpec), C.c_int32,
                                          C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float, C.c_double, C.c_int32,
                                          C.c_double, _P, C.c_int32] + [_P] * 11),
+    'metro_predict_boxes': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32] + [C.c_double] * 7 +
+                            [C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_double] + [_P] * 10),
     'metro_last_error': (C.c_char_p, []),
     'metro_abi_version': (C.c_int32, []),
 }

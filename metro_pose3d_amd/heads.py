@@ -16,6 +16,8 @@ through the C ABI (csrc/heads.hip).  Names and argument meaning follow the refer
                             on the device
   associate_tracks          which box of a video continues which track: greedy assignment on predicted poses, births and the
                             CSR grouping smooth_tracks reads, one workgroup
+  predict_boxes             next-frame person boxes from the track table: the filter's prediction of every live track through
+                            the frames' calibrated cameras, compacted on the device and fused with a detector's boxes
   smooth_tracks             poses of tracked persons over time: constant-velocity Kalman filter / RTS smoother per track and
                             joint, each row weighted by its heat-map covariance (nothing in the reference: one image each)
   backproject_bone_lengths  scale_recovery 'bone-lengths' / '-true'   volumetric.py:171-191,
@@ -565,6 +567,155 @@ def associate_tracks(poses: torch.Tensor, covariance: Optional[torch.Tensor], ti
                                      _p(starts), _p(n_new), _p(n_dropped), _stream(dev)), 'metro_associate_tracks')
     return AssociatedTracks(track_index, track_id, cost, rows, starts, n_new, n_dropped,
                             ws.view(torch.float64).view(n_tracks, nj, TRACK_STATE_DOUBLES))
+
+
+PREDICT_MAX_DETECTIONS = _lib.METRO_PREDICT_MAX_DETECTIONS
+FRAME_CAMERA_BYTES = C.sizeof(_lib.MetroFrameCamera)
+
+
+class PredictedBoxRows(NamedTuple):
+    """What predict_boxes returns, all on the device and unsliced: the first counts[0] rows hold the boxes."""
+    boxes: torch.Tensor                  # float64 [F T + m, 4] (x, y, w, h)
+    frame_index: torch.Tensor            # int32 [F T + m]
+    track_index: torch.Tensor            # int32 [F T + m]: the slot of a predicted box, -1 for a detection
+    track_id: torch.Tensor               # int32 [F T + m]: its id, -1 for a detection
+    detection: torch.Tensor              # int32 [F T + m]: the index of a detection, -1 for a predicted box
+    n_joints: torch.Tensor               # int32 [F T + m]: the visible joints of a predicted box, -1 for a detection
+    dense_boxes: torch.Tensor            # float64 [F, T, 4]: the box of every (frame, slot), NaN where there is none
+    dense_joints: torch.Tensor           # int32 [F, T]: its visible joints, -1: the slot is free or older than max_age_s
+    counts: torch.Tensor                 # int32 [5]: rows, predicted rows, suppressed, bad detections, bad frame indices
+
+
+def _finite(name, v, low, low_ok, high=None) -> float:
+    ok = not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
+    if not ok or v < low or (v == low and not low_ok) or (high is not None and v > high):
+        rng = f"{'>=' if low_ok else '>'} {low:g}" + ('' if high is None else f' and <= {high:g}')
+        raise ValueError(f'{name} must be a finite number {rng}, got {v!r}')
+    return float(v)
+
+
+def prediction_params(expand, n_sigma, max_sigma_mm, min_joints, max_age_s, near_mm, min_side_px, iou_max, accel_psd):
+    """Checks the prediction keywords of predict_boxes / frames.predict_boxes_in_frames; -> metro_predict_boxes' (q, max_age_s,
+    expand, n_sigma, max_sigma_mm, near_mm, min_side_px) as floats, then iou_max.  min_joints: None or an integer >= 1."""
+    if min_joints is not None and (isinstance(min_joints, (bool, np.bool_)) or not isinstance(min_joints, (int, np.integer))
+                                   or min_joints < 1):
+        raise ValueError(f'min_joints must be None or an integer >= 1, got {min_joints!r}')
+    return (_finite('accel_psd', accel_psd, 0, False), _finite('max_age_s', max_age_s, 0, True), _finite('expand', expand, 1, True),
+            _finite('n_sigma', n_sigma, 0, True), _finite('max_sigma_mm', max_sigma_mm, 0, True), _finite('near_mm', near_mm, 0, False),
+            _finite('min_side_px', min_side_px, 0, True)), _finite('iou_max', iou_max, 0, False, 1)
+
+
+def predict_boxes(state: torch.Tensor, ids: torch.Tensor, cameras, frame_sizes, times, coords: str = 'camera', detections=None,
+                  detection_frame_index=None, expand: float = 1.25, n_sigma: float = 2.0, max_sigma_mm: float = 300.0,
+                  min_joints: Optional[int] = None, max_age_s: float = 1.0, near_mm: float = 100.0, min_side_px: float = 8.0,
+                  iou_max: float = 0.3, accel_psd: float = 4e6, clip: bool = True) -> PredictedBoxRows:
+    """Next-frame person boxes from the track table, the two launches of metro_predict_boxes on the current stream and no
+    synchronisation (include/metro_hip.h has the model).  state float64 [T,J,28] and ids int32 [T] are the table
+    associate_tracks walks (frames.new_track_table), on a CUDA device, and are only read.  cameras: the MetroFrameCamera
+    table of 1 or F entries (frames.pack_frame_cameras' structured array, uploaded here, or its bytes as a uint8 CUDA tensor
+    [n, 240]); frame_sizes int [F,2] (W, H) and times [F] seconds, host values, one per frame, F <= 64.
+    coords 'camera' (the state is in each frame's camera; R and t are not read) or 'world'.
+    Per (frame, slot): a free slot, or one last seen more than max_age_s before the frame's time, has no box; else every joint
+    with a state is advanced to the frame's time by the filter's own prediction (accel_psd as smooth_tracks has it) -- the
+    position associate_tracks will compare the next box against -- and projected through the frame's lens-distorted camera.
+    A joint counts if it is finite, at least near_mm in front of the camera and inside the monotonic range of the lens model;
+    around its pixel it claims a margin of n_sigma standard deviations of its predicted position (at most max_sigma_mm),
+    seen at its depth.  The box is the union of those squares, scaled about its centre by expand, cut to the frame (clip),
+    and dropped with fewer than min_joints joints (None: (J + 1) // 2) or a side below min_side_px.
+    detections float [m,4] (x, y, w, h) with detection_frame_index [m] (None: frame 0), host data or CUDA tensors, m <= 4096:
+    a detector's boxes of the same frames, appended after the predicted ones unless their intersection over union with a
+    predicted box of their frame reaches iou_max (the tracked person keeps its predicted box) or they are not boxes
+    (non-finite, w or h <= 0); suppression among the detections is the detector's own.
+    The defaults expand = 1.25, n_sigma = 2, max_sigma_mm = 300, near_mm = 100, min_side_px = 8 and iou_max = 0.3 are
+    design choices, not measurements: a quarter more than the joints' extent leaves room for head, hands and feet beyond the outermost joints;
+    two standard deviations cover a coasting joint 95 times in 100 per axis; 300 mm keeps a long-unseen track from claiming
+    the whole frame; nothing nearer than 100 mm is a person in front of a lens; a crop of fewer than 8 pixels holds no pose;
+    two boxes of one person overlap far more than 0.3, two persons side by side less.
+    -> PredictedBoxRows, unsliced: counts[0] says how many rows are written, counts[4] > 0 (a detection frame index outside
+    [0, F)) is the caller's error to raise.  An empty call (no detections and T F == 0) launches nothing."""
+    if coords not in ('camera', 'world'):
+        raise ValueError(f"coords must be 'camera' or 'world' (a crop has no calibrated camera to project through), got {coords!r}")
+    params, iou = prediction_params(expand, n_sigma, max_sigma_mm, min_joints, max_age_s, near_mm, min_side_px, iou_max, accel_psd)
+    if (not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or state.dim() != 3 or state.shape[2] != TRACK_STATE_DOUBLES
+            or not 1 <= state.shape[0] <= ASSOC_MAX or not 1 <= state.shape[1] <= _lib.METRO_MAX_JOINTS or not state.is_contiguous()):
+        raise ValueError(f'state must be a contiguous float64 tensor [T,J,{TRACK_STATE_DOUBLES}] with 1 <= T <= {ASSOC_MAX} and '
+                         f'J <= {_lib.METRO_MAX_JOINTS} (frames.new_track_table)')
+    dev, n_tracks, nj = state.device, int(state.shape[0]), int(state.shape[1])
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.device != dev or ids.numel() != n_tracks or not ids.is_contiguous():
+        raise ValueError(f'ids must be a contiguous int32 tensor of {n_tracks} on {dev} (frames.new_track_table)')
+    if min_joints is None:
+        min_joints = (nj + 1) // 2
+    if min_joints > nj:
+        raise ValueError(f'min_joints must be at most the {nj} joints, got {min_joints!r}')
+    sizes = np.ascontiguousarray(np.asarray(frame_sizes.cpu() if isinstance(frame_sizes, torch.Tensor) else frame_sizes))
+    if sizes.ndim != 2 or sizes.shape[1] != 2 or sizes.dtype.kind not in 'iu' or not 1 <= len(sizes) <= _lib.METRO_MAX_FRAMES:
+        raise ValueError(f'frame_sizes must be integers [F, 2] (W, H) with 1 <= F <= {_lib.METRO_MAX_FRAMES} (frames.frame_sizes), got '
+                         f'{sizes.dtype} {sizes.shape}')
+    if sizes.min() < 1 or sizes.max() > np.iinfo(np.int32).max:
+        raise ValueError(f'frame_sizes must be >= 1 pixel, got a frame of {sizes[np.argmin(sizes.min(axis=1))].tolist()}')
+    sizes = np.ascontiguousarray(sizes, np.int32)
+    n_frames = len(sizes)
+    ts = np.ascontiguousarray(np.asarray(times.cpu() if isinstance(times, torch.Tensor) else times, np.float64).reshape(-1))
+    if len(ts) != n_frames or not np.isfinite(ts).all():
+        raise ValueError(f'times must hold one finite value per frame ({n_frames}), got {len(ts)}')
+    if isinstance(cameras, torch.Tensor):
+        if cameras.dtype != torch.uint8 or cameras.device != dev or cameras.dim() != 2 or cameras.shape[1] != FRAME_CAMERA_BYTES \
+                or not cameras.is_contiguous():
+            raise ValueError(f'cameras must be a contiguous uint8 tensor [n, {FRAME_CAMERA_BYTES}] on {dev} (frames.pack_frame_cameras)')
+        n_cameras = int(cameras.shape[0])
+    else:
+        if not isinstance(cameras, np.ndarray) or cameras.dtype.itemsize != FRAME_CAMERA_BYTES or cameras.ndim != 1:
+            raise ValueError('cameras must be the structured array frames.pack_frame_cameras returns, or its bytes on the device')
+        n_cameras = len(cameras)
+    if n_cameras not in (1, n_frames):
+        raise ValueError(f'cameras: {n_cameras} entries for {n_frames} frames (one for every frame, or one per frame)')
+    det, det_fi, m = None, None, 0
+    if detections is not None:
+        if isinstance(detections, torch.Tensor) and detections.is_cuda:
+            det = detections
+        else:
+            det = torch.from_numpy(np.ascontiguousarray(np.asarray(detections.cpu() if isinstance(detections, torch.Tensor) else detections,
+                                                                   np.float64)))
+        if det.dim() != 2 or det.shape[1] != 4 or not det.is_floating_point():
+            raise ValueError(f'detections must be floating point [m, 4] (x, y, w, h), got {det.dtype} {tuple(det.shape)}')
+        m = int(det.shape[0])
+        if m > PREDICT_MAX_DETECTIONS:
+            raise ValueError(f'{m} detections: at most {PREDICT_MAX_DETECTIONS} per call')
+        if detection_frame_index is None:
+            det_fi = torch.zeros(m, dtype=torch.int32)
+        else:
+            det_fi = detection_frame_index if isinstance(detection_frame_index, torch.Tensor) else \
+                torch.from_numpy(np.ascontiguousarray(np.asarray(detection_frame_index).reshape(-1)))
+            if det_fi.is_floating_point() or det_fi.is_complex() or det_fi.dtype == torch.bool or det_fi.numel() != m:
+                raise ValueError(f'detection_frame_index must hold {m} integers (one per detection), got {det_fi.dtype} '
+                                 f'{tuple(det_fi.shape)}')
+        if (det.is_cuda and det.device != dev) or (det_fi.is_cuda and det_fi.device != dev):
+            raise ValueError(f'detections and detection_frame_index must be host data or on {dev}')
+    if dev.type != 'cuda':
+        raise ValueError(f'the track table must be on a CUDA device, got {dev}: there is no CPU path')
+    from metro_pose3d_amd.frame_formats import _upload
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        if not isinstance(cameras, torch.Tensor):
+            cameras = _upload(np.ascontiguousarray(cameras).view(np.uint8).reshape(n_cameras, FRAME_CAMERA_BYTES), dev)
+        if m:
+            det = (det if det.is_cuda else det.pin_memory().to(dev, non_blocking=True)).to(torch.float64).contiguous()
+            det_fi = det_fi.reshape(-1) if det_fi.is_cuda else det_fi.reshape(-1).pin_memory().to(dev, non_blocking=True)
+            if det_fi.dtype != torch.int32:                 # out-of-range values stay out of range through the cast
+                det_fi = det_fi.to(torch.int64).clamp(-1, _lib.METRO_MAX_FRAMES).to(torch.int32)
+            det_fi = det_fi.contiguous()
+        cap = n_frames * n_tracks + m
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        boxes = torch.empty((cap, 4), dtype=torch.float64, device=dev)
+        frame, slot, tid, detection, joints = i32(cap), i32(cap), i32(cap), i32(cap), i32(cap)
+        dense = torch.empty((n_frames, n_tracks, 4), dtype=torch.float64, device=dev)
+        dense_joints, counts = i32(n_frames, n_tracks), i32(5)
+        check(lib.metro_predict_boxes(_p(state), _p(ids), n_tracks, nj, _p(cameras), n_cameras, C.c_void_p(sizes.ctypes.data),
+                                      C.c_void_p(ts.ctypes.data), n_frames, _COORDS[coords], *params, int(min_joints), int(bool(clip)),
+                                      _p(det if m else None), _p(det_fi if m else None), m, iou, _p(dense), _p(dense_joints), _p(boxes),
+                                      _p(frame), _p(slot), _p(tid), _p(detection), _p(joints), _p(counts), _stream(dev)),
+              'metro_predict_boxes')
+    return PredictedBoxRows(boxes, frame, slot, tid, detection, joints, dense, dense_joints, counts)
 
 
 def backproject_bone_lengths(coords01: torch.Tensor, inv_intrinsics, bone_lengths, spec: ModelSpec,
