@@ -206,7 +206,15 @@ int  metro_forward_timed(MetroPlan* plan, const float* d_images_nhwc, int32_t n,
  * reference resnet_v2.py:123-136,219-220,233-236; resnet_utils.py:82-135).  Generic over
  * kernel size, stride, dilation and asymmetric TF padding; optional per-input-channel
  * scale/shift+ReLU prologue (pre-activation BN, resnet_v2.py:119,229) and
- * bias / ReLU / strided-shifted residual epilogue (resnet_v2.py:113-121,138). */
+ * bias / ReLU / strided-shifted residual epilogue (resnet_v2.py:113-121,138).
+ *
+ * Non-finite values.  Every ReLU of the library -- the `relu` epilogue, the prologue's, those inside the fused launches and the
+ * head's, in every precision -- is IEEE-754-2019 maximum(v, 0): relu(NaN) = NaN, relu(+Inf) = +Inf, relu(-Inf) = 0 (the value
+ * behind a -Inf is hugely negative: zero is its ReLU).  A store rounds to the output type as IEEE does: |y| past the largest
+ * fp16 (65 504) is stored as +-Inf.  A non-finite input element therefore reaches exactly the outputs it is a term of, as IEEE
+ * arithmetic on the fp64 restatement of the layer gives them, and no other element of the launch: nothing outside the tensors
+ * the descriptor states is ever a term of an output, whatever its bits.  That is what lets the finalize launch's screen
+ * (metro_forward_status) see an overflow that began several units in front of the head. */
 typedef struct MetroConvDesc {
     int32_t n, h_in, w_in, c_in;
     int32_t in_pix_stride;      /* elements between consecutive input pixels (>= c_in)      */

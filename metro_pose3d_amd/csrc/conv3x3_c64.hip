@@ -153,11 +153,10 @@ __global__ __launch_bounds__(c64::NT) void conv3x3_c64_kernel(C64Args a) {
             floatx16 a1[2];
 #pragma unroll
             for (int e = 0; e < 16; ++e) { a1[0][e] = 0.f; a1[1][e] = 0.f; }
-            const half8_t z = {};
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
                 half8_t bf = *reinterpret_cast<const half8_t*>(sp + (r_base ^ (kk << 5)));
-                bf = __builtin_elementwise_max(bf * ps1[kk] + pb1[kk], z);            // fp16 FMA + ReLU, one rounding
+                bf = relu(bf * ps1[kk] + pb1[kk]);            // fp16 FMA + ReLU, one rounding
                 a1[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1f[0][kk], bf, a1[0], 0, 0, 0);
                 a1[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1f[1][kk], bf, a1[1], 0, 0, 0);
             }
@@ -167,7 +166,7 @@ __global__ __launch_bounds__(c64::NT) void conv3x3_c64_kernel(C64Args a) {
                 for (int q = 0; q < 4; ++q) {
                     half4_t hv;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) hv[e] = (half_t)fmaxf(a1[i][4 * q + e] + bias1_v[i][q][e], 0.f);
+                    for (int e = 0; e < 4; ++e) hv[e] = (half_t)relu(a1[i][4 * q + e] + bias1_v[i][q][e]);
                     // channels i*32 + 8q + 4 half ..+3 = 16-byte chunk (4i + q), byte 8 * half inside it
                     *reinterpret_cast<half4_t*>(sp + srow * 128 + ((((4 * i + q) ^ swz<64>(srow)) << 4) | (frag_half << 3))) = hv;
                     if (a.t1_dump != nullptr && srow >= halo && srow < halo + TN)      // the tile's own rows, once
@@ -205,7 +204,7 @@ __global__ __launch_bounds__(c64::NT) void conv3x3_c64_kernel(C64Args a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float v = acc[4 * q + e] + bias_v[q][e];
-                if (a.relu) v = fmaxf(v, 0.f);
+                if (a.relu) v = relu(v);
                 hv[e] = (half_t)v;
             }
             *reinterpret_cast<half4_t*>(ol + tl * OUT_ROW + (wm * 32 + 8 * q + 4 * frag_half) * 2) = hv;

@@ -326,7 +326,7 @@ __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __res
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float v = acc[i][j][4 * qd + e] + bv[e];
-                    if (a.relu) v = fmaxf(v, 0.f);
+                    if (a.relu) v = relu(v);
                     hv[e] = (half_t)v;
                 }
                 *reinterpret_cast<half4_t*>(smem + prow * Cfg::OUT_ROW_BYTES + col * 2) = hv;

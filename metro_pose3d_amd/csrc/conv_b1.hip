@@ -178,8 +178,7 @@ __global__ __launch_bounds__(b1::NT) void conv_b1_chain_kernel(B1Args a) {
             }
             if (j < T) {
                 half8_t* mine = reinterpret_cast<half8_t*>(smem + L::X_OFF + (slot * NIN + 1) * X_BYTES + wave * 1024 + lane * 16);
-                const half8_t z = {};
-                *mine = __builtin_elementwise_max(*mine * pre_s + pre_b, z);
+                *mine = relu(*mine * pre_s + pre_b);
             }
             wait_lgkm_and_barrier();
             if (j + 2 < T) issue_tile(t0 + (j + 2) * G, slot >= 1 ? slot - 1 : 2);       // slot of j + 2 = (slot + 2) % 3
@@ -293,9 +292,8 @@ __global__ __launch_bounds__(b1::NT) void conv_b1_chain_kernel(B1Args a) {
                 }
                 const half8_t s = *reinterpret_cast<const half8_t*>(par + L::SC2 + (ks * 32 + kg * 8) * 2);
                 const half8_t b = *reinterpret_cast<const half8_t*>(par + L::SH2 + (ks * 32 + kg * 8) * 2);
-                const half8_t z = {};
                 half8_t pv = *reinterpret_cast<const half8_t*>(&v);
-                pv = __builtin_elementwise_max(pv * s + b, z);        // the next unit's pre-activation (fp16 BN + ReLU, one rounding)
+                pv = relu(pv * s + b);        // the next unit's pre-activation (fp16 BN + ReLU, one rounding)
                 const half8_t w3 = *reinterpret_cast<const half8_t*>(smem + L::W1T_OFF + (ks * 64 + lane) * 16);
 #pragma unroll
                 for (int mt = 0; mt < 3; ++mt) dacc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w2r[mt][ks], pv, dacc[mt], 0, 0, 0);
@@ -307,7 +305,7 @@ __global__ __launch_bounds__(b1::NT) void conv_b1_chain_kernel(B1Args a) {
                 const floatx4 bv = *reinterpret_cast<const floatx4*>(par + L::B2 + co * 4);
                 half4_t hv;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) hv[e] = (half_t)fmaxf(dacc[mt][e] + bv[e], 0.f);
+                for (int e = 0; e < 4; ++e) hv[e] = (half_t)relu(dacc[mt][e] + bv[e]);
                 *reinterpret_cast<half4_t*>(a.out2 + m * C2 + co) = hv;
             }
         }

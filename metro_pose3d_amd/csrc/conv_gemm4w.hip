@@ -122,9 +122,8 @@ __device__ __forceinline__ void conv_gemm4w_body(
         const int eb = bpiece(e);
         if (eb < 0) return;
         if constexpr (PROLOGUE) {
-            const half8_t z = {};
             half8_t x = *reinterpret_cast<const half8_t*>(&rb[set][eb]);
-            x = __builtin_elementwise_max(x * pro_sc + pro_sh, z);
+            x = relu(x * pro_sc + pro_sh);
             *reinterpret_cast<half8_t*>(smem + B_OFF + buf * OPER_BYTES + st_off + eb * 32 * ROW_BYTES) = x;
         } else {
             *reinterpret_cast<u32x4*>(smem + B_OFF + buf * OPER_BYTES + st_off + eb * 32 * ROW_BYTES) = rb[set][eb];
@@ -298,8 +297,7 @@ __device__ __forceinline__ void conv_gemm4w_body(
                     const int prow = wc * (NJ * 32) + j * 32 + frag_row;
                     half4_t hv = bias_cvt(acc[i][j], q, bvq[i][q]);
                     if constexpr (decltype(relu_c)::value) {
-                        const half4_t z = {};
-                        hv = __builtin_elementwise_max(hv, z);
+                        hv = relu(hv);
                     }
                     *reinterpret_cast<half4_t*>(smem + prow * OUT_ROW_BYTES + col * 2) = hv;
                 }

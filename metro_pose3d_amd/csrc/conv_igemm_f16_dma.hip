@@ -241,9 +241,8 @@ __device__ __forceinline__ void conv_dma_body(
             if (PROLOGUE) {
                 const half8_t sc = *reinterpret_cast<const half8_t*>(pro_lds + c0 + chunk * 8);
                 const half8_t sh = *reinterpret_cast<const half8_t*>(pro_lds + 2048 + c0 + chunk * 8);
-                const half8_t z = {};
 #pragma unroll
-                for (int j = 0; j < Cfg::WN; ++j) bf[j] = __builtin_elementwise_max(bf[j] * sc + sh, z);
+                for (int j = 0; j < Cfg::WN; ++j) bf[j] = relu(bf[j] * sc + sh);
             }
 #ifdef METRO_SETPRIO
             __builtin_amdgcn_s_setprio(1);
@@ -449,7 +448,7 @@ __device__ __forceinline__ void conv_dma_body(
                     for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e] + bv[e];
                     if (a.relu) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+                        for (int e = 0; e < 4; ++e) v[e] = relu(v[e]);
                     }
                     *reinterpret_cast<floatx4*>(reinterpret_cast<float*>(out) + (size_t)m * a.c_out + co) = v;
                 }
@@ -475,7 +474,7 @@ __device__ __forceinline__ void conv_dma_body(
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float v = acc[i][j][4 * q + e] + bv[e];
-                    if (o_relu) v = fmaxf(v, 0.f);
+                    if (o_relu) v = relu(v);
                     hv[e] = (half_t)v;
                 }
                 *reinterpret_cast<half4_t*>(smem + prow * Cfg::OUT_ROW_BYTES + col * 2) = hv;
@@ -567,8 +566,7 @@ __device__ __forceinline__ void conv_dma_body(
                 half8_t bf = *reinterpret_cast<const half8_t*>(smem + prow2 * Cfg::OUT_ROW_BYTES + k0 * 2);
                 const half8_t sc = *reinterpret_cast<const half8_t*>(p2 + k0);
                 const half8_t sh = *reinterpret_cast<const half8_t*>(p2 + Cfg::TM + k0);
-                const half8_t z = {};
-                bf = __builtin_elementwise_max(bf * sc + sh, z);
+                bf = relu(bf * sc + sh);
                 acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, acc2, 0, 0, 0);
             }
             const int m = m0 + prow2;
@@ -579,7 +577,7 @@ __device__ __forceinline__ void conv_dma_body(
                     const floatx4 bv = *reinterpret_cast<const floatx4*>(f2.bias2 + co);
                     half4_t hv;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) hv[e] = (half_t)fmaxf(acc2[4 * q + e] + bv[e], 0.f);
+                    for (int e = 0; e < 4; ++e) hv[e] = (half_t)relu(acc2[4 * q + e] + bv[e]);
                     *reinterpret_cast<half4_t*>(f2.out2 + (size_t)m * f2.c2 + co) = hv;
                 }
             }

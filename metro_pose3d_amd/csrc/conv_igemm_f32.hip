@@ -131,7 +131,7 @@ __global__ __launch_bounds__(f32m::NT) void conv_igemm_f32_kernel(
 #pragma unroll
             for (int e = 0; e < V; ++e) {
                 float v = xv[i][e];
-                if (PROLOGUE) v = fmaxf(fmaf(v, g_sc[e], g_sh[e]), 0.f);      // pre-activation BN + ReLU (resnet_v2.py:119,229), one rounding
+                if (PROLOGUE) v = relu(fmaf(v, g_sc[e], g_sh[e]));      // pre-activation BN + ReLU (resnet_v2.py:119,229), one rounding
                 xs[buf][(lrow + KR * i) * LD + kcol + e] = xok[i] ? v : 0.f;
             }
 #pragma unroll
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(f32m::NT) void conv_igemm_f32_kernel(
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float t = acc[i][j][4 * q + e] + bv[e];
-                        if (a.relu) t = fmaxf(t, 0.f);
+                        if (a.relu) t = relu(t);
                         v[e] = t + rv[i][q][e];
                     }
                     if (mok && co < a.c_out) *reinterpret_cast<floatx4*>(out + (size_t)m * a.c_out + co) = v;
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(f32m::NT) void conv_igemm_f32_kernel(
                         const int co = n0 + wave_m * (TM / 2) + i * 32 + 8 * q + 4 * frag_k + e;
                         if (co >= a.c_out) continue;
                         float v = acc[i][j][4 * q + e] + bias[co];
-                        if (a.relu) v = fmaxf(v, 0.f);
+                        if (a.relu) v = relu(v);
                         if (residual != nullptr) v += residual[res_pix * a.c_out + co];
                         out[(size_t)m * a.c_out + co] = v;
                     }

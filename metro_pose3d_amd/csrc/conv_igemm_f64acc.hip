@@ -140,7 +140,7 @@ __global__ __launch_bounds__(f64k::NT, 2) void conv_igemm_f64acc_kernel(
 #pragma unroll
             for (int e = 0; e < V; ++e) {
                 double v = (double)xv[i][e];
-                if (PROLOGUE) v = fmax(fma(v, g_sc[e], g_sh[e]), 0.0);     // pre-activation BN + ReLU (resnet_v2.py:119,229) in fp64
+                if (PROLOGUE) v = relu(fma(v, g_sc[e], g_sh[e]));     // pre-activation BN + ReLU (resnet_v2.py:119,229) in fp64
                 xs[buf][(lrow + KR * i) * LD + kcol + e] = xok[i] ? v : 0.0;
             }
 #pragma unroll
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(f64k::NT, 2) void conv_igemm_f64acc_kernel(
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 double v = acc[i][j][rr] + bv[j];
-                if (a.relu) v = fmax(v, 0.0);
+                if (a.relu) v = relu(v);
                 v += (double)rv[rr][j];
                 if (mok[rr] && cov[j] < a.c_out) out[(size_t)mrow[rr] * a.c_out + cov[j]] = (TAct)v;
             }

@@ -338,14 +338,13 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
         if constexpr (PREPASS) {
             static_assert(X_BYTES / 16 == 2 * NT, "two 16-byte chunks of the input tile per thread");
             const int c8 = lane & 7, prow = (wave & 3) * 8 + (lane >> 3);
-            const half8_t z = {};
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int sl = (wave >> 2) + 2 * h;
                 half8_t* xp = reinterpret_cast<half8_t*>(smem + X_OFF + buf * X_BYTES + sl * SL_BYTES + prow * 128 + ((c8 ^ swz<64>(prow)) << 4));
                 const half8_t sc = *reinterpret_cast<const half8_t*>(pro_l + sl * 64 + c8 * 8);
                 const half8_t sh = *reinterpret_cast<const half8_t*>(pro_l + K + sl * 64 + c8 * 8);
-                *xp = __builtin_elementwise_max(*xp * sc + sh, z);
+                *xp = relu(*xp * sc + sh);
             }
             wait_lgkm_and_barrier();
         }
@@ -370,8 +369,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
                 half8_t bs = *reinterpret_cast<const half8_t*>(smem + XS_OFF + buf * X_BYTES + (kk >> 2) * SL_BYTES + brow * 128 + ((chunk ^ swz<64>(brow)) << 4));
                 const half8_t s = *reinterpret_cast<const half8_t*>(pro_l + kk * 16 + frag_half * 8);
                 const half8_t b = *reinterpret_cast<const half8_t*>(pro_l + K + kk * 16 + frag_half * 8);
-                const half8_t z = {};
-                bs = __builtin_elementwise_max(bs * s + b, z);
+                bs = relu(bs * s + b);
 #pragma unroll
                 for (int i = 0; i < NI; ++i) accs[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wsf[i][kk], bs, accs[i], 0, 0, 0);
             }
@@ -450,8 +448,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
             if constexpr (PRO && !PREPASS) {
                 const half8_t s = *reinterpret_cast<const half8_t*>(pro_l + kk * 16 + frag_half * 8);
                 const half8_t b = *reinterpret_cast<const half8_t*>(pro_l + K + kk * 16 + frag_half * 8);
-                const half8_t z = {};
-                bf = __builtin_elementwise_max(bf * s + b, z);
+                bf = relu(bf * s + b);
             }
 #pragma unroll
             for (int i = 0; i < NI; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[i][kk], bf, acc[i], 0, 0, 0);
@@ -466,8 +463,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
                 half8_t bs = *reinterpret_cast<const half8_t*>(smem + XS_OFF + buf * X_BYTES + (kk >> 2) * SL_BYTES + brow * 128 + ((chunk ^ swz<64>(brow)) << 4));
                 const half8_t s = *reinterpret_cast<const half8_t*>(pro_l + kk * 16 + frag_half * 8);
                 const half8_t b = *reinterpret_cast<const half8_t*>(pro_l + K + kk * 16 + frag_half * 8);
-                const half8_t z = {};
-                bs = __builtin_elementwise_max(bs * s + b, z);
+                bs = relu(bs * s + b);
 #pragma unroll
                 for (int i = 0; i < NI; ++i) accs[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wsf[i][kk], bs, accs[i], 0, 0, 0);
             }
@@ -484,7 +480,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
                         const floatx4 bv = *reinterpret_cast<const floatx4*>(bias2_l + co);
                         half4_t hv;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) hv[e] = (half_t)fmaxf(acc2[4 * q + e] + bv[e], 0.f);
+                        for (int e = 0; e < 4; ++e) hv[e] = (half_t)relu(acc2[4 * q + e] + bv[e]);
                         if constexpr (W2_LDS) *reinterpret_cast<half4_t*>(smem + O2_OFF + (wn * 32 + frag_row) * O2_ROW + co * 2) = hv;   // full rows below
                         else *reinterpret_cast<half4_t*>(a.out2 + (size_t)m * C2 + co) = hv;
                     }
@@ -580,9 +576,8 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
             }
             if constexpr (MODE2 == 2) {
                 // next unit's pre-activation (fp16 BN + ReLU) goes back into the tile for the second GEMM
-                const half8_t z = {};
                 half8_t p = *reinterpret_cast<const half8_t*>(&v);
-                p = __builtin_elementwise_max(p * sc2 + sh2, z);
+                p = relu(p * sc2 + sh2);
                 *reinterpret_cast<half8_t*>(ol + prow * OUT_ROW + ch * 16) = p;
             }
         }
@@ -617,7 +612,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
                 const int m = m0 + px0 + j * 16 + (lane & 15);
                 half4_t hv;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) hv[e] = (half_t)fmaxf(dacc[j][e] + bv[e], 0.f);
+                for (int e = 0; e < 4; ++e) hv[e] = (half_t)relu(dacc[j][e] + bv[e]);
                 if (m < a.m_total) *reinterpret_cast<half4_t*>(a.out2 + (size_t)m * C2 + co) = hv;
             }
         }

@@ -158,8 +158,7 @@ __global__ __launch_bounds__(g4d::NT, (MI * NJ <= 4 ? 2 : 1)) void conv_gemm4d_k
     auto rmw_addr = [&](int buf, int g) { return smem + G::B_BASE + buf * G::OPER_B + g * 4096 + wave * 1024 + lane * 16; };
     auto rmw_read = [&](int buf, int g) { rp[g] = *reinterpret_cast<const half8_t*>(rmw_addr(buf, g)); };
     auto rmw_write = [&](int buf, int g) {
-        const half8_t z = {};
-        *reinterpret_cast<half8_t*>(rmw_addr(buf, g)) = __builtin_elementwise_max(rp[g] * prs + prh, z);
+        *reinterpret_cast<half8_t*>(rmw_addr(buf, g)) = relu(rp[g] * prs + prh);
     };
     // ---- prologue: the table, K tile 0, and of tile 1 what the loop would have requested by now; tile 0 landed --------------------
     if (PROLOGUE) {
@@ -217,8 +216,7 @@ __global__ __launch_bounds__(g4d::NT, (MI * NJ <= 4 ? 2 : 1)) void conv_gemm4d_k
         constexpr int KK = decltype(kk_c)::value;
 #ifndef METRO_DBG_G4D_NO_PRO
         if constexpr (PROLOGUE && !INPLACE) {
-            const half8_t z = {};
-            bf[KK][j] = __builtin_elementwise_max(bf[KK][j] * sc[KK] + sh[KK], z);
+            bf[KK][j] = relu(bf[KK][j] * sc[KK] + sh[KK]);
         }
 #endif
     };
@@ -350,7 +348,7 @@ __global__ __launch_bounds__(g4d::NT, (MI * NJ <= 4 ? 2 : 1)) void conv_gemm4d_k
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float v = acc[i][j][4 * q + e] + bv[e];
-                    if (o_relu) v = fmaxf(v, 0.f);
+                    if (o_relu) v = relu(v);
                     hv[e] = (half_t)v;
                 }
                 *reinterpret_cast<half4_t*>(smem + prow * G::OUT_ROW_BYTES + col * 2) = hv;

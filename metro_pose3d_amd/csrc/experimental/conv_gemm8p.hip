@@ -177,12 +177,11 @@ __global__ __launch_bounds__(g8::NT) void conv_gemm8p_kernel(
             bf[kk] = *reinterpret_cast<const half8_t*>(buf + (b_base[j] ^ (kk << 5)));
         if (PROLOGUE) {
             // pre-activation BN + ReLU on the pixel fragment (fp16 FMA, one rounding: resnet_v2.py:119)
-            const half8_t z = {};
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
                 const half8_t sc = *reinterpret_cast<const half8_t*>(pro_lds + k0 + kk * 16 + frag_half * 8);
                 const half8_t sh = *reinterpret_cast<const half8_t*>(pro_lds + 2048 + k0 + kk * 16 + frag_half * 8);
-                bf[kk] = __builtin_elementwise_max(bf[kk] * sc + sh, z);
+                bf[kk] = relu(bf[kk] * sc + sh);
             }
             // keep this VALU work in the load interval: volatile asm statements stay ordered with the barrier asm,
             // so the values must exist before it (otherwise hipcc sinks half of it behind the barrier, in front of
@@ -269,7 +268,7 @@ __global__ __launch_bounds__(g8::NT) void conv_gemm8p_kernel(
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float v = acc[i][j][4 * q + e] + bv[e];
-                    if (o_relu) v = fmaxf(v, 0.f);
+                    if (o_relu) v = relu(v);
                     hv[e] = (half_t)v;
                 }
                 *reinterpret_cast<half4_t*>(smem + prow * OUT_ROW_BYTES + col * 2) = hv;

@@ -109,6 +109,16 @@ __device__ __forceinline__ half4_t bias_cvt(const floatx16& acc, int q, const fl
     return __builtin_bit_cast(half4_t, r);
 }
 
+// The ReLU of every kernel, scalar or packed: IEEE-754-2019 maximum(v, 0), NOT fmaxf / __builtin_elementwise_max (maxNum, which
+// answers max(NaN, 0) = 0).  NaN stays NaN and +Inf stays +Inf, so a value that overflowed fp16 storage keeps travelling down the
+// residual stream to the soft-argmax screen (pool_softargmax.hip, finalize) instead of becoming a plausible zero; -Inf -> 0 is
+// right, the true value behind it is hugely negative.  One instruction where the maxNum form was one: v_maximum3_f32 v, v, 0, 0 /
+// v_pk_maximum3_f16 (fp64, the parity kernels only: v_max_f64 + a NaN select).
+template <typename T>
+__device__ __forceinline__ T relu(T v) {
+    return __builtin_elementwise_maximum(v, T{});
+}
+
 // A copy of a register value the optimiser knows nothing about (no instruction).  The MOMENTS instantiations of the head and
 // soft-argmax kernels take their inputs through it: code added behind the default path then shares no expression with it -- a
 // product that gains a second use is no longer contracted into an fma with its sum, which moved the default results by an ulp.

@@ -132,8 +132,7 @@ __global__ __launch_bounds__(hd::NT) void head_f16_kernel(HeadArgs a) {
             half8_t bf = *reinterpret_cast<const half8_t*>(wl + b_off + ((chunk ^ b_sw) << 4));
             const half8_t sc = *reinterpret_cast<const half8_t*>(pro_lds + k0 + chunk * 8);
             const half8_t sh = *reinterpret_cast<const half8_t*>(pro_lds + 2048 + k0 + chunk * 8);
-            const half8_t z = {};
-            bf = __builtin_elementwise_max(bf * sc + sh, z);      // postnorm BN + ReLU, fp16 FMA (resnet_v2.py:229)
+            bf = relu(bf * sc + sh);      // postnorm BN + ReLU, fp16 FMA (resnet_v2.py:229)
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 const int row = i * 32 + frag_row;
@@ -467,8 +466,7 @@ __global__ __launch_bounds__(hd2::NT) void head_f16_kernel256(HeadArgs a) {
             half8_t bf = *reinterpret_cast<const half8_t*>(wl + b_off + ((chunk ^ b_sw) << 4));
             const half8_t sc = *reinterpret_cast<const half8_t*>(pro_lds + k0 + chunk * 8);
             const half8_t sh = *reinterpret_cast<const half8_t*>(pro_lds + 2048 + k0 + chunk * 8);
-            const half8_t z = {};
-            bf = __builtin_elementwise_max(bf * sc + sh, z);      // postnorm BN + ReLU, fp16 FMA (resnet_v2.py:229)
+            bf = relu(bf * sc + sh);      // postnorm BN + ReLU, fp16 FMA (resnet_v2.py:229)
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 const int row = i * 32 + frag_row;
@@ -723,8 +721,7 @@ __global__ __launch_bounds__(512, 2) void head_f16_ring_kernel(HeadArgs a) {
         sh = *reinterpret_cast<const half8_t*>(pro_lds + 2048 + k0 + chunk * 8);
     };
     auto act = [&](auto par_c, int t) {                  // postnorm BN + ReLU, fp16 FMA, one rounding (resnet_v2.py:229)
-        const half8_t z = {};
-        bq[decltype(par_c)::value][t] = __builtin_elementwise_max(braw[t] * sc + sh, z);
+        bq[decltype(par_c)::value][t] = relu(braw[t] * sc + sh);
     };
     auto mma = [&](auto par_c, auto i_c) {
         constexpr int P = decltype(par_c)::value, I = decltype(i_c)::value;

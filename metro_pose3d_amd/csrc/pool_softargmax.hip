@@ -550,11 +550,14 @@ __global__ __launch_bounds__(SA_NT) void softargmax_partial_kernel(
                 AccT mx = m[e];
 #pragma unroll
                 for (int u = 0; u < UNR; ++u) mx = (AccT)v[u][e] > mx ? (AccT)v[u][e] : mx;
-                const AccT f = acc_exp<AccT>(m[e] - mx);          // exp(-inf) = 0 on first touch
+                // a channel that has held nothing but -Inf so far (a voxel of weight zero: a -Inf logits bias) keeps m = -Inf and
+                // s = 0: the exponents are taken about 0 then, -Inf - -Inf would be NaN.  Any other mx is its own reference.
+                const AccT mr = mx == (AccT)-INFINITY ? (AccT)0 : mx;
+                const AccT f = acc_exp<AccT>(m[e] - mr);          // exp(-inf) = 0 on first touch
                 AccT s_ = s[e] * f, sx_ = sx[e] * f, sy_ = sy[e] * f;
 #pragma unroll
                 for (int u = 0; u < UNR; ++u) {
-                    const AccT ex = acc_exp<AccT>((AccT)v[u][e] - mx);
+                    const AccT ex = acc_exp<AccT>((AccT)v[u][e] - mr);
                     s_ += ex; sx_ += ex * cx[u]; sy_ += ex * cy[u];
                 }
                 m[e] = mx; s[e] = s_; sx[e] = sx_; sy[e] = sy_;
@@ -694,8 +697,13 @@ __global__ __launch_bounds__(1024) void softargmax_finalize_kernel(const AccT* _
                                                                   float* __restrict__ cov01, float* __restrict__ peak) {
     __shared__ AccT mm[METRO_MAX_JOINTS][3];
     // Non-finite screen (status[img] = 1): a record whose sum is NaN, a non-finite maximum or normaliser.  fp16 storage overflows
-    // at 65 504: an Inf in the residual stream reaches every logit of its pixel (reference tfu.py:426-440 keeps fp32 variables
-    // for the same reason); `r[1] > 0` alone would silently DROP a NaN record and return a finite, wrong pose.
+    // at 65 504 (reference tfu.py:426-440 keeps fp32 variables for the same reason).  What carries an overflow to this screen: the
+    // identity shortcuts keep a +-Inf (or the NaN of Inf - Inf) in the residual stream, every ReLU of the library is the
+    // NaN-propagating metro::relu (gfx950_prims.h: a maxNum ReLU turned the NaN pixels into zeros in the next pre-activation, and
+    // a projection shortcut, which reads only the pre-activated stream, then made the stream finite again), so the head's
+    // pre-activation hands NaN / +Inf to every logit of that pixel, whose exp(l - max) is NaN in its record's sum.  A -Inf that
+    // a ReLU turns into 0 is the right value, not a lost flag.  A NaN record is never dropped from the sums: its joint (every
+    // joint, if it is the root's) is returned as NaN, not as the finite, wrong pose of the other slabs.
     __shared__ int s_bad;
     if (threadIdx.x == 0) s_bad = 0;
     __syncthreads();
@@ -721,10 +729,11 @@ __global__ __launch_bounds__(1024) void softargmax_finalize_kernel(const AccT* _
             for (int sl = 0; sl < slabs; ++sl) {
                 const AccT* r = partials + (((size_t)img * slabs + sl) * nj + j) * 5;
                 const AccT r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3], r4 = r[4];
-                if (r1 > 0) {
-                    const AccT f = acc_exp<AccT>(r0 - M);
-                    S += r1 * f; SX += r2 * f; SY += r3 * f; SZ += r4 * f;
-                } else bad = true;
+                // a record that is not a sum of exponentials (NaN: a NaN or +Inf logit in its slab) is added like any other, so
+                // its joint comes out NaN, as the exact soft-argmax of those logits does, and the image is flagged
+                const AccT f = acc_exp<AccT>(r0 - M);
+                S += r1 * f; SX += r2 * f; SY += r3 * f; SZ += r4 * f;
+                if (!(r1 > 0)) bad = true;
             }
             bad = bad || !(M - M == (AccT)0) || !(S - S == (AccT)0) || !(SX - SX == (AccT)0) || !(SY - SY == (AccT)0) || !(SZ - SZ == (AccT)0);
             const AccT x01 = SX / S, y01 = SY / S, z01 = SZ / S;
@@ -773,10 +782,9 @@ __global__ __launch_bounds__(1024) void softargmax_finalize_kernel(const AccT* _
         for (int sl = lane; sl < slabs; sl += 64) {
             const AccT* r = partials + (((size_t)img * slabs + sl) * nj + j) * 5;
             const AccT r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3], r4 = r[4];      // all five before the test: one latency, not two
-            if (r1 > 0) {
-                const AccT f = acc_exp<AccT>(r0 - M);
-                S += r1 * f; SX += r2 * f; SY += r3 * f; SZ += r4 * f;
-            } else bad = true;
+            const AccT f = acc_exp<AccT>(r0 - M);
+            S += r1 * f; SX += r2 * f; SY += r3 * f; SZ += r4 * f;
+            if (!(r1 > 0)) bad = true;
         }
         S = sa_wave_sum(S); SX = sa_wave_sum(SX); SY = sa_wave_sum(SY); SZ = sa_wave_sum(SZ);
         bad = bad || !(M - M == (AccT)0) || !(S - S == (AccT)0) || !(SX - SX == (AccT)0) || !(SY - SY == (AccT)0) || !(SZ - SZ == (AccT)0);

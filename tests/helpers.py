@@ -114,7 +114,8 @@ def ref_conv_desc(d, x, w_ok, bias, pro=None, pro_round=np.float16, res=None):
             cols = wo + s * d.dilation
             cok = (cols >= 0) & (cols < d.w_in)
             xt = x[:, np.clip(rows, 0, d.h_in - 1)][:, :, np.clip(cols, 0, d.w_in - 1)]
-            xt = xt * (rok[:, None] & cok[None, :])[None, :, :, None]
+            # (a select, not a product: a tap outside the input reads zero even where the clipped gather found Inf or NaN)
+            xt = np.where((rok[:, None] & cok[None, :])[None, :, :, None], xt, 0.0)
             wt = w[:, r, s, :].T
             y += xt @ wt
             a += np.abs(xt) @ np.abs(wt)

@@ -204,6 +204,32 @@ def test_dispatch_closure():
         '\n'.join(f'  {k}: {w}' for k, w in sorted(untested.items()))
 
 
+def test_every_kernel_has_a_nonfinite_case(lib):
+    """Every kernel a configuration dispatches must be LAUNCHED by a case of tests/test_gpu_nonfinite_kernels.py (IEEE special
+    values, store overflow and poisoned surroundings, one kernel at a time): a new kernel cannot enter the plans without one.
+    A kernel is the id's family -- the text in front of '<' -- and, where one family holds several __global__ kernels with a ReLU
+    of their own (head_f16: ring / 256-pixel / plain; stem_pool_f16: rows / patch), which of them (kernel_of).  What a case
+    launches is taken from a dry run of its launches (metro_kernel_notes(2): nothing is launched), not from the name it states;
+    and the dry run must note exactly the ids the case names."""
+    from tests.test_gpu_nonfinite_kernels import NF_CASES, dry_run_ids, ids_match, kernel_of
+    noted = {c.id: dry_run_ids(lib, c) for c in NF_CASES}
+    wrong = {c.id: noted[c.id] for c in NF_CASES if not ids_match(noted[c.id], c.families)}
+    assert not wrong, 'non-finite cases that do not reach the kernels they name:\n' + \
+        '\n'.join(f'  {k}: launches {v}' for k, v in sorted(wrong.items()))
+    launched = {kernel_of(k) for ids in noted.values() for k in ids}
+    missing = {}
+    for cname, (spec, n) in CONFIGS.items():
+        for _, li, kid in dispatch_table(spec, n):
+            for part in kid.split(' & '):
+                if kernel_of(part) not in launched:
+                    missing.setdefault(kernel_of(part), f'{cname}: {li.name.decode()} ({kid})')
+    assert not missing, 'kernels without a non-finite case (first layer that dispatches each):\n' + \
+        '\n'.join(f'  {k}: {w}' for k, w in sorted(missing.items()))
+    # the key tells the kernels of one family apart
+    assert len({kernel_of(k) for k in ('head_f16<144x256,k2>', 'head_f16<160x256>', 'head_f16<160x64>')}) == 3
+    assert kernel_of('stem_pool_f16<rows,f32in>') != kernel_of('stem_pool_f16<split2,f32in>')
+
+
 @pytest.mark.parametrize('nb', [3, 8], ids=['64-pixel-tiles', '256-pixel-tiles'])
 def test_head_partials_slot_covers_large_heat_maps(lib, nb):
     """The one-launch head writes one fp32 record per (image, slab, joint): one per 64 pixels, and one per 32 pixels once the
