@@ -23,6 +23,9 @@
 // read the zero area: conv2d_same pads t1, not x).  t1 never exists in HBM: the unit loses a launch (projection
 // shortcut + conv1 pair -> nothing; the shortcut moves into the conv3 launch, conv_pw64.hip PSC) and 1152 of its 2304
 // bytes per pixel.  Same arithmetic as the separate launches: one fp16 rounding per tensor (oracle/f16emu.py unit_conv1).
+#ifndef METRO_WT_STORES
+#define METRO_WT_STORES 1      // epilogue stores write through the L2 (metro_common.h: store_out16; A/B in NOTES_dead_ends.md)
+#endif
 #include "metro_common.h"
 #include "gfx950_prims.h"
 
@@ -215,7 +218,7 @@ __global__ __launch_bounds__(c64::NT) void conv3x3_c64_kernel(C64Args a) {
             const int idx = tid + r * NT;
             const int prow = idx >> 3, ch = idx & 7;
             const uint4 v = *reinterpret_cast<const uint4*>(ol + prow * OUT_ROW + ch * 16);
-            store_out16<1>(a.out + (size_t)(m0 + prow) * C + ch * 8, v);
+            store_out16(a.out + (size_t)(m0 + prow) * C + ch * 8, v);
         }
     }
 }

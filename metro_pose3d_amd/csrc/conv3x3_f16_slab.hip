@@ -21,6 +21,9 @@
 #include <cstdlib>
 #include <type_traits>
 
+#ifndef METRO_WT_STORES
+#define METRO_WT_STORES 1      // epilogue stores write through the L2 (metro_common.h: store_out16; A/B in NOTES_dead_ends.md)
+#endif
 #include "metro_common.h"
 #include "gfx950_prims.h"
 
@@ -344,7 +347,7 @@ __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __res
         const uint4 v = *reinterpret_cast<const uint4*>(smem + prow * Cfg::OUT_ROW_BYTES + ch * 16);
         const size_t mo = pixel_of(m);
         if (co + 8 <= a.c_out) {
-            store_out16<2>(out + mo * a.c_out + co, v);
+            store_out16(out + mo * a.c_out + co, v);
         } else {
             const half8_t x = *reinterpret_cast<const half8_t*>(&v);
 #pragma unroll

@@ -23,6 +23,9 @@
 //   * ONE s_barrier per tile hands tile j from the producers to the consumers and tile j - 2's LDS tile back.
 // Arithmetic (MFMA shapes, k order, fp16 rounding points) is conv_pw64_kernel's: the two forms give the same bits
 // (tests/test_kernel_coverage.py compares them); metro_forward_upto stopping at such a layer runs the classic form.
+#ifndef METRO_WT_STORES
+#define METRO_WT_STORES 1      // epilogue stores write through the L2 (metro_common.h: store_out16; A/B in NOTES_dead_ends.md)
+#endif
 #include "metro_common.h"
 #include "gfx950_prims.h"
 
@@ -286,9 +289,9 @@ __global__ __launch_bounds__(b1::NT) void conv_b1_chain_kernel(B1Args a) {
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks) {
                 const uint4 v = *reinterpret_cast<const uint4*>(ot + px * OUT_ROW + ks * 64 + kg * 16);
-                if constexpr (OUTM == 0) store_out16<1>(a.out + m * CB + ks * 32 + kg * 8, v);
+                if constexpr (OUTM == 0) store_out16(a.out + m * CB + ks * 32 + kg * 8, v);
                 if constexpr (OUTM == 2) {
-                    if (sub_ok) store_out16<1>(a.out_sub + sub_row * CB + ks * 32 + kg * 8, v);
+                    if (sub_ok) store_out16(a.out_sub + sub_row * CB + ks * 32 + kg * 8, v);
                 }
                 const half8_t s = *reinterpret_cast<const half8_t*>(par + L::SC2 + (ks * 32 + kg * 8) * 2);
                 const half8_t b = *reinterpret_cast<const half8_t*>(par + L::SH2 + (ks * 32 + kg * 8) * 2);

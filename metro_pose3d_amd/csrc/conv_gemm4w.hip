@@ -18,6 +18,9 @@
 //     one fp32 accumulator per output): bit-identical results.
 #include <type_traits>
 
+#ifndef METRO_WT_STORES
+#define METRO_WT_STORES 1      // epilogue stores write through the L2 (metro_common.h: store_out16; A/B in NOTES_dead_ends.md)
+#endif
 #include "metro_common.h"
 #include "gfx950_prims.h"
 
@@ -324,7 +327,7 @@ __device__ __forceinline__ void conv_gemm4w_body(
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int u = 0; u < 8; ++u)
-                store_out16<2>(o_ptr + (size_t)(m0 + pr0 + (it0 + u) * (NT / CPRO)) * o_c + o_n0 + ch * 8, vv[u]);
+                store_out16(o_ptr + (size_t)(m0 + pr0 + (it0 + u) * (NT / CPRO)) * o_c + o_n0 + ch * 8, vv[u]);
         }
         return;
     }
@@ -352,7 +355,7 @@ __device__ __forceinline__ void conv_gemm4w_body(
 #pragma unroll
             for (int e = 0; e < 4; ++e) x[e] = x[e] + r[e];    // fp16 Add, like the reference graph
         }
-        store_out16<2>(o_ptr + (size_t)m * o_c + co, v);
+        store_out16(o_ptr + (size_t)m * o_c + co, v);
     }
 }
 

@@ -19,6 +19,9 @@
 #include <cstdlib>
 #include <type_traits>
 
+#ifndef METRO_WT_STORES
+#define METRO_WT_STORES 1      // epilogue stores write through the L2 (metro_common.h: store_out16; A/B in NOTES_dead_ends.md)
+#endif
 #include "metro_common.h"
 #include "gfx950_prims.h"
 
@@ -515,7 +518,7 @@ __device__ __forceinline__ void conv_dma_body(
 #pragma unroll
                     for (int e = 0; e < 4; ++e) x[e] = x[e] + r[e];    // fp16 Add, like the reference graph
                 }
-                store_out16<2>(outh + (size_t)(m0 + prow) * o_c + o_n0 + ch * 8, v);
+                store_out16(outh + (size_t)(m0 + prow) * o_c + o_n0 + ch * 8, v);
                 if constexpr (FUSE2) *reinterpret_cast<uint4*>(smem + prow * Cfg::OUT_ROW_BYTES + ch * 16) = v;
             }
         }
@@ -536,7 +539,7 @@ __device__ __forceinline__ void conv_dma_body(
 #pragma unroll
                 for (int e = 0; e < 4; ++e) x[e] = x[e] + r[e];    // fp16 Add, like the reference graph
             }
-            store_out16<2>(outh + (size_t)m * o_c + co, v);
+            store_out16(outh + (size_t)m * o_c + co, v);
             if constexpr (FUSE2) *reinterpret_cast<uint4*>(smem + prow * Cfg::OUT_ROW_BYTES + ch * 16) = v;
         } else {
             // ragged channel tail (c_out % 8 != 0 never carries a residual: see conv_f16_dma_supported)

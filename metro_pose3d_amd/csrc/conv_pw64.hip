@@ -41,6 +41,9 @@
 #include <cstdlib>
 #include <type_traits>
 
+#ifndef METRO_WT_STORES
+#define METRO_WT_STORES 1      // epilogue stores write through the L2 (metro_common.h: store_out16; A/B in NOTES_dead_ends.md)
+#endif
 #include "metro_common.h"
 #include "gfx950_prims.h"
 
@@ -562,8 +565,8 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
                 for (int e = 0; e < 4; ++e) x[e] = x[e] + rr[e];       // fp16 Add, like the reference graph
             }
             if constexpr (OUTM == 0) {
-                if (inside) store_out16<1>(a.out + (size_t)m * ldo + ch * 8, v);
-                else if (m < a.m_total) store_out16<1>(a.out + (size_t)m * ldo + ch * 8, v);
+                if (inside) store_out16(a.out + (size_t)m * ldo + ch * 8, v);
+                else if (m < a.m_total) store_out16(a.out + (size_t)m * ldo + ch * 8, v);
             }
             if constexpr (OUTM == 2) {
                 const int hr = ((rem0 + 16 * r) >> a.lw_out) - a.sub_off;         // wave-uniform: map row of this instruction's pixels
@@ -571,7 +574,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
                     ++now_sub;
                     const int wo = ((rem0 + prow) & (a.w_out - 1)) - a.sub_off;
                     if (wo >= 0 && (wo & 1) == 0 && (wo >> 1) < a.w_sub)
-                        store_out16<1>(a.out_sub + (((size_t)img0 * a.h_sub + (hr >> 1)) * a.w_sub + (wo >> 1)) * CB + ch * 8, v);
+                        store_out16(a.out_sub + (((size_t)img0 * a.h_sub + (hr >> 1)) * a.w_sub + (wo >> 1)) * CB + ch * 8, v);
                 }
             }
             if constexpr (MODE2 == 2) {
@@ -586,7 +589,7 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
             static_assert(TN * (C2 / 8) == NT, "one 16-byte chunk of the second output per thread");
             const int prow2 = tid / (C2 / 8), ch2 = tid % (C2 / 8);
             const uint4 v2 = *reinterpret_cast<const uint4*>(smem + O2_OFF + prow2 * O2_ROW + ch2 * 16);
-            if (m0 + prow2 < a.m_total) store_out16<1>(a.out2 + (size_t)(m0 + prow2) * C2 + ch2 * 8, v2);
+            if (m0 + prow2 < a.m_total) store_out16(a.out2 + (size_t)(m0 + prow2) * C2 + ch2 * 8, v2);
         }
         if constexpr (MODE2 == 2) {
             wait_lgkm_and_barrier();

@@ -19,6 +19,9 @@
 //     waits ONCE, with a counted vmcnt that leaves the operand requests in flight.
 // Arithmetic is conv_pw64's (fp32 accumulation in ascending k on one accumulator, fp16(conv + bias), then the fp16 shortcut add:
 // reference resnet_v2.py:134-138): the same bits.
+// METRO_WT_STORES stays 0 here (plain stores; metro_common.h: store_out16).  A tile's two stores are OLDER than the operand requests
+// the next tile's counted wait leaves in flight, so that wait also waits for them, one GEMM phase after they were issued: a
+// write-through store is acknowledged later than that, and each K = 256 launch took 2.6 - 3.1 us longer (NOTES_dead_ends.md).
 #include "metro_common.h"
 #include "gfx950_prims.h"
 
@@ -180,7 +183,7 @@ __global__ __launch_bounds__(pws::NT) void conv_pws_kernel(PwsArgs a) {
             const uint4 rv = *reinterpret_cast<const uint4*>(tw + T_BYTES + it * 1024 + lane * 16);
             half8_t x = __builtin_bit_cast(half8_t, v);
             x = x + __builtin_bit_cast(half8_t, rv);             // the fp16 Add of the reference graph (resnet_v2.py:138)
-            store_out16<1>(a.out + ((size_t)tile * TN + px) * ldo + co0 + rch * 8, __builtin_bit_cast(uint4, x));
+            store_out16(a.out + ((size_t)tile * TN + px) * ldo + co0 + rch * 8, __builtin_bit_cast(uint4, x));
         }
         slot = slot == 2 ? 0 : slot + 1;
     }

@@ -384,7 +384,7 @@ __global__ __launch_bounds__(g4d::NT, (MI * NJ <= 4 ? 2 : 1)) void conv_gemm4d_k
 #pragma unroll
             for (int e = 0; e < 4; ++e) x[e] = x[e] + r[e];    // fp16 Add, like the reference graph
         }
-        store_out16<2>(o_ptr + (size_t)m * o_c + co, v);
+        store_out16(o_ptr + (size_t)m * o_c + co, v);
     }
 }
 

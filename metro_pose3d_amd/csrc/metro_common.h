@@ -54,19 +54,30 @@ struct KernelNotes { int mode; char ids[1024]; };   // a string that did not fit
 KernelNotes& kernel_notes();
 bool note_kernel(const char* fmt, ...) __attribute__((format(printf, 1, 2)));   // true = dry run: skip the launch
 
-// 16-byte activation store of an epilogue.  METRO_NT_STORES (A/B builds only) marks them non-temporal:
-//   1 = the streaming kernels whose outputs exceed the L2 (stem, conv_pw64, conv3x3_c64), 2 = every conv kernel.
+// 16-byte activation store of an epilogue, in the form its translation unit chose with METRO_WT_STORES:
+//   0  plain: the line stays DIRTY in the writing XCD's L2 (the eight L2s are not coherent), and the release at the end of the
+//      launch writes every dirty line back, with no wave running, before the next launch may start.
+//   1  write-through (sc1): the bytes go to memory while the kernel runs and the line is dropped from the L2, so the launch ends
+//      clean.  The consumer loses nothing: every launch fetches its input from beyond the L2 anyway (profiles/*_pmc_layers.tsv).
+// A kernel file that ships write-through defines METRO_WT_STORES 1 above its includes (unless the command line set it:
+// tools/build_variant.sh <name> "-DMETRO_WT_STORES=0|1" <file>.hip flips one family); NOTES_dead_ends.md has the A/B per family.
+// Inline asm, not __builtin_amdgcn_raw_buffer_store_b128(.., aux 16), which hipcc would count: the builtin wants a wave-uniform
+// descriptor and a 32-bit offset, the 17 call sites hold per-lane 64-bit pointers into tensors of up to 537 MB, and a per-lane
+// descriptor costs a waterfall loop.  hipcc does not model the asm: `s_nop 1` keeps the data registers from being rewritten while
+// the store reads them, and the store is absent from the compiler's vmcnt bookkeeping -- compiler-placed waits count fewer
+// younger operations than there are (longer waits, never shorter); A CALLER WITH A HAND-COUNTED WAIT COUNTS THESE STORES ITSELF
+// (one instruction each, as before).  No "memory" clobber: no kernel reads back what it stores here; volatile asm keeps its order.
 typedef unsigned int metro_u32x4 __attribute__((ext_vector_type(4)));
-template <int LEVEL = 1>
-__device__ __forceinline__ void store_out16(void* p, uint4 v) {
-#if defined(METRO_NT_STORES)
-    if constexpr (METRO_NT_STORES >= LEVEL) {
-        metro_u32x4 w = {v.x, v.y, v.z, v.w};
-        __builtin_nontemporal_store(w, reinterpret_cast<metro_u32x4*>(p));
-        return;
-    }
+#ifndef METRO_WT_STORES
+#define METRO_WT_STORES 0
 #endif
+__device__ __forceinline__ void store_out16(void* p, uint4 v) {
+#if METRO_WT_STORES
+    const metro_u32x4 w = {v.x, v.y, v.z, v.w};
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(w));
+#else
     *reinterpret_cast<uint4*>(p) = v;
+#endif
 }
 
 // ---- launch-resident weight fragments of the persistent (weight-stationary) kernels -------------------------------------------

@@ -15,6 +15,9 @@
 #include <cstdlib>
 #include <type_traits>
 
+#ifndef METRO_WT_STORES
+#define METRO_WT_STORES 1      // epilogue stores write through the L2 (metro_common.h: store_out16; A/B in NOTES_dead_ends.md)
+#endif
 #include "metro_common.h"
 #include "gfx950_prims.h"
 
@@ -296,7 +299,7 @@ __global__ __launch_bounds__(64 * sp::MG * NSPLIT, 2 * NSPLIT) void stem_pool_f1
                     }
                 }
             }
-            store_out16<1>(a.out + (((size_t)img * ps + py0 + ppy) * ps + px0 + ppx) * 64 + c8 * 8, *reinterpret_cast<const uint4*>(&best));
+            store_out16(a.out + (((size_t)img * ps + py0 + ppy) * ps + px0 + ppx) * 64 + c8 * 8, *reinterpret_cast<const uint4*>(&best));
         }
         if (p + G >= a.n_patches) break;
         buf = buf + 1 == NBUF ? 0 : buf + 1;
@@ -645,7 +648,7 @@ __device__ __forceinline__ void stem_pool_rows_body(const StemPoolArgs& a) {
         for (int r = 0; r < 2; ++r) {
             const int c = tid + r * NT;
             const int X = c >> 3, c8 = c & 7;
-            store_out16<1>(a.out + (((size_t)img * PS + Y) * PS + X) * 64 + c8 * 8, *reinterpret_cast<const uint4*>(&v[r]));
+            store_out16(a.out + (((size_t)img * PS + Y) * PS + X) * 64 + c8 * 8, *reinterpret_cast<const uint4*>(&v[r]));
         }
     };
 

@@ -2,6 +2,7 @@
 # A/B library build with extra hipcc flags on SOME translation units (the rest as the product builds them):
 #   tools/build_variant.sh <name> "<flags>" file1.hip file2.hip ...   ->  metro_pose3d_amd/ab/libmetro_<name>.so
 #   tools/build_variant.sh agpr_slab "-DMETRO_AGPR_ACC=1" conv3x3_f16_slab.hip
+#   tools/build_variant.sh plain_slab "-DMETRO_WT_STORES=0" conv3x3_f16_slab.hip      (the store form of one family: metro_common.h)
 # then: tools/ab_libs.sh 64 3 metro_pose3d_amd/libmetro_hip.so metro_pose3d_amd/ab/libmetro_agpr_slab.so
 set -e
 name=$1; flags=$2; shift 2
