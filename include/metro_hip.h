@@ -881,6 +881,31 @@ int  metro_associate_tracks(const float* d_poses, const float* d_cov, const doub
                             int32_t* d_track_index_out, int32_t* d_track_id_out, float* d_cost_out, int32_t* d_rows_out,
                             int32_t* d_starts_out, int32_t* d_n_new_out, int32_t* d_n_dropped_out, void* stream);
 
+/* ---- the same walk with the OPTIMAL assignment of a step's boxes to the slots ----
+ * metro_associate_tracks_optimal is metro_associate_tracks -- parameters, argument checks, workspace
+ * (metro_associate_tracks_workspace_bytes), one launch of one workgroup, every step, output and return value -- except for step 2
+ * of a time step, which becomes, with c = cost[t][b] as step 1 writes it (fp32) and g = max_cost_mm (fp32):
+ * 2'. A pair is ADMISSIBLE if c < g.  The assignment is the one-to-one set M of admissible pairs that minimises
+ *    sum over M of (c - g), i.e. maximises the total gain sum (g - c): the linear assignment problem on min(c, g) in which a
+ *    pair at g means "unmatched" (the m x (T + m) problem with m dummy columns at cost g).  It is not a maximum-cardinality
+ *    matching: one pair at 10 mm beats two pairs at 299 mm each (gains 290 against 1 + 1, with g = 300).  The greedy rule of
+ *    step 2 can miss it: with slots A, B and boxes p, q at costs A-p 100, A-q 120, B-p 130, B-q 350 it takes A-p, after which
+ *    B has no admissible box left (B bridges, q is born under a new id); the optimum A-q + B-p keeps both tracks.
+ *    The sums (dual potentials, path lengths of the shortest augmenting paths) are fp64 over the fp32 costs.  The boxes are
+ *    augmented in step order and every minimum takes the lowest index among equals (a slot before "unmatched"), so the result
+ *    does not depend on the number of threads; which of several exactly equal optima is returned is otherwise not specified.
+ *    Every loop is bounded by the sizes alone: one search per box, at most T + 1 column visits per search, at most T steps
+ *    back along a path; a cost that is not a number is not admissible.
+ * d_cost_out holds the cost c of each accepted pair, as there.  The ABI version is unchanged: the entry is an addition. */
+int  metro_associate_tracks_optimal(const float* d_poses, const float* d_cov, const double* d_times, int32_t n,
+                                    const int32_t* d_step_rows, int32_t n_step_rows, const int32_t* d_step_starts,
+                                    int32_t n_steps, const MetroSpec* spec, int32_t measurement, double q, double r_floor,
+                                    double cov_scale, double v0, double gate, float max_cost_mm, double clip_mm,
+                                    int32_t min_joints, double max_age_s, double* d_state, int32_t n_tracks, int32_t* d_ids,
+                                    int32_t* d_next_id, void* d_workspace, int32_t* d_track_index_out, int32_t* d_track_id_out,
+                                    float* d_cost_out, int32_t* d_rows_out, int32_t* d_starts_out, int32_t* d_n_new_out,
+                                    int32_t* d_n_dropped_out, void* stream);
+
 /* ---- next-frame person boxes from the track table: crops between the key frames of a detector ----
  * Nothing in the reference: one example is one image and its box is given.  Two launches on `stream`, no host work in
  * between: one thread per (frame, slot) writes dense tables, one workgroup compacts them into rows and appends the

@@ -16,13 +16,15 @@ Public surface (mirrors reference inference.py):
         boxes matched across cameras per exposure, triangulated with covariance, followed and smoothed in the world
     predict_boxes_in_frames(tracks, cameras, frame_sizes, timestamps) -> the person boxes of the next frames from the
         table of tracks those two return (frame_sizes(frames): their sizes), for the frames a detector does not see
+    Follower(model_path, cameras, world=False, assignment='greedy', ...) -> one of the two follow calls with its keywords
+        and its table of tracks kept from call to call: .follow(frames, boxes, frame_index, timestamps), .predict(...)
 plus the pieces under it: ModelSpec, Engine (plan + forward over libmetro_hip.so), the model
 container (save_model / load_model) and batch sharding over the GPUs of a node (dist).
 """
 from metro_pose3d_amd.spec import ModelSpec  # noqa: F401
 from metro_pose3d_amd.modelfile import load_model, save_model  # noqa: F401
 
-__all__ = ['ModelSpec', 'load_model', 'save_model', 'Engine', 'estimate_pose', 'estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'predict_boxes_in_frames', 'frame_sizes', 'Camera']
+__all__ = ['ModelSpec', 'load_model', 'save_model', 'Engine', 'estimate_pose', 'estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'predict_boxes_in_frames', 'frame_sizes', 'Follower', 'Camera']
 
 
 def __getattr__(name):
@@ -33,7 +35,7 @@ def __getattr__(name):
     if name == 'estimate_pose':
         from metro_pose3d_amd.inference import estimate_pose
         return estimate_pose
-    if name in ('estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'predict_boxes_in_frames', 'frame_sizes', 'Camera'):
+    if name in ('estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'predict_boxes_in_frames', 'frame_sizes', 'Follower', 'Camera'):
         from metro_pose3d_amd import frames
         return getattr(frames, name)
     raise AttributeError(name)

@@ -206,6 +206,9 @@ SIGNATURES = {
     'metro_associate_tracks': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.POINTER(MetroSpec), C.c_int32,
                                          C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float, C.c_double, C.c_int32,
                                          C.c_double, _P, C.c_int32] + [_P] * 11),
+    'metro_associate_tracks_optimal': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.POINTER(MetroSpec), C.c_int32,
+                                                 C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float, C.c_double,
+                                                 C.c_int32, C.c_double, _P, C.c_int32] + [_P] * 11),
     'metro_predict_boxes': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32] + [C.c_double] * 7 +
                             [C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_double] + [_P] * 10),
     'metro_last_error': (C.c_char_p, []),

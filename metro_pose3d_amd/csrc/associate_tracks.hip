@@ -8,7 +8,8 @@
 //   cost      per (slot, box of the step): the RMS over the joints of min(|z - (p + dt v)|, clip), one rounding to fp32;
 //             +inf with fewer than min_joints joints or a slot last seen before t_step - max_age
 //   assign    greedy one-to-one: the smallest remaining cost (ties: lowest slot, then lowest position in the step) while it
-//             is < max_cost; its row and its column of the matrix become +inf
+//             is < max_cost; its row and its column of the matrix become +inf.  metro_associate_tracks_optimal: the admissible
+//             pairs of the largest total gain max_cost - cost instead, by shortest augmenting paths (further down)
 //   births    the unassigned boxes with a finite joint, in step order, take the lowest free slots and the next ids
 //   filter    every slot that received a box advances its working state by smooth_filter_row (smooth_step.h), the per-row
 //             step of smooth_tracks.hip
@@ -382,6 +383,202 @@ __global__ __launch_bounds__(ASSOC_THREADS) void associate_tracks_kernel(AssocAr
     assoc_finish(a, l, tid, nt);
 }
 
+// ---- the optimal assignment (metro_associate_tracks_optimal): the block between assoc_costs and assoc_births ----
+// The one-to-one set of admissible pairs (c < max_cost) of the largest total gain sum (max_cost - c): the linear assignment
+// problem with one extra column of unlimited capacity at cost max_cost that means "unmatched".  Shortest augmenting paths
+// (Jonker-Volgenant): one Dijkstra per box, in step order, over the T slot columns and that sink, on the costs reduced by the
+// dual potentials u (boxes) and v (slots; the sink's stays 0); potentials and path lengths in fp64 on the fp32 costs.  A visit
+// relaxes the columns from the box of the column reached last and takes the nearest unvisited one (ties: the lowest slot; a
+// slot before the sink).  The search ends at a free slot or at the sink; a box that went to the sink is never searched
+// through again (its way out, the sink, stays the cheapest).  Every thread keeps its own copy of the search (AssocPath), equal
+// in all of them; thread t owns column t of dist / way / used.  At most T + 1 visits per box, T steps back along a path.
+
+struct AssocOptLds {
+    double u[ASSOC_MAX];                                 // potential of the box at a position
+    double v[ASSOC_MAX];                                 // potential of a slot, <= 0
+    double dist[ASSOC_MAX];                              // length of the shortest path found so far to a slot
+    int way[ASSOC_MAX];                                  // the slot before it on that path, -1: the searching box itself
+    int used[ASSOC_MAX];                                 // the slot was visited in this search
+    int slot_box[ASSOC_MAX];                             // the position matched to a slot, -1: free
+};
+
+struct AssocCandD { double v; int idx; };
+
+struct AssocPath {
+    int row;                                             // the box whose costs the next visit relaxes
+    int col;                                             // the slot reached last, -1: none yet
+    double base;                                         // its distance
+    double sink;                                         // the shortest way into the sink so far
+    int sink_from;                                       // the slot it leaves from, -1: the searching box itself
+    int end;                                             // -2: searching, -1: ended in the sink, >= 0: ended in this free slot
+};
+
+__host__ __device__ inline bool assoc_candd_less(const AssocCandD& x, const AssocCandD& y) {
+    return x.v < y.v || (x.v == y.v && x.idx < y.idx);
+}
+
+__host__ __device__ inline void assoc_opt_begin(const AssocArgs& a, AssocOptLds& o, int m, int tid, int nt) {
+    const int span = a.n_tracks > m ? a.n_tracks : m;
+    for (int i = tid; i < span; i += nt) {
+        if (i < m) o.u[i] = 0.0;
+        if (i < a.n_tracks) {
+            o.v[i] = 0.0;
+            o.slot_box[i] = -1;
+        }
+    }
+}
+
+// the search of box k starts: no column reached
+__host__ __device__ inline AssocPath assoc_opt_root(const AssocArgs& a, AssocOptLds& o, int k, int tid, int nt) {
+    for (int t = tid; t < a.n_tracks; t += nt) {
+        o.dist[t] = __builtin_inf();
+        o.way[t] = -1;
+        o.used[t] = 0;
+    }
+    const AssocPath p = {k, -1, 0.0, __builtin_inf(), -1, -2};
+    return p;
+}
+
+// one visit: the column reached last is marked, the others and the sink are relaxed from the path's box
+// -> this thread's nearest unvisited column
+__host__ __device__ inline AssocCandD assoc_opt_relax(const AssocArgs& a, const AssocLds& l, AssocOptLds& o, AssocPath& p, int tid, int nt) {
+    const double ur = o.u[p.row];
+    const double to_sink = (p.base + (double)a.max_cost) - ur;
+    if (to_sink < p.sink) {
+        p.sink = to_sink;
+        p.sink_from = p.col;
+    }
+    AssocCandD best = {__builtin_inf(), 0x7fffffff};
+    for (int t = tid; t < a.n_tracks; t += nt) {
+        if (t == p.col) o.used[t] = 1;
+        if (o.used[t]) continue;
+        const float c = l.c[t * ASSOC_LD + p.row];
+        if (c < a.max_cost) {
+            const double nd = ((p.base + (double)c) - ur) - o.v[t];
+            if (nd < o.dist[t]) {
+                o.dist[t] = nd;
+                o.way[t] = p.col;
+            }
+        }
+        const AssocCandD x = {o.dist[t], t};
+        if (assoc_candd_less(x, best)) best = x;
+    }
+    return best;
+}
+
+// the workgroup's nearest unvisited column against the sink; the same in every thread
+__host__ __device__ inline void assoc_opt_advance(const AssocArgs& a, const AssocOptLds& o, AssocPath& p, AssocCandD best) {
+    if (!((unsigned)best.idx < (unsigned)a.n_tracks) || !(best.v <= p.sink)) {
+        p.end = -1;
+        return;
+    }
+    p.col = best.idx;
+    p.base = best.v;
+    const int k = o.slot_box[best.idx];
+    if ((unsigned)k < (unsigned)ASSOC_MAX) p.row = k;
+    else p.end = best.idx;
+}
+
+// the potentials after a search that ended at distance p.end's: visited columns and their boxes move by what the path to
+// them was shorter; a search that found no end (a matrix without sense) changes nothing
+__host__ __device__ inline void assoc_opt_duals(const AssocArgs& a, AssocOptLds& o, const AssocPath& p, int k, int tid, int nt) {
+    if (p.end == -2) return;
+    const double d_end = p.end >= 0 ? p.base : p.sink;
+    for (int t = tid; t < a.n_tracks; t += nt) {
+        if (!o.used[t]) continue;
+        const double d = d_end - o.dist[t];
+        o.v[t] -= d;
+        const int kb = o.slot_box[t];
+        if ((unsigned)kb < (unsigned)ASSOC_MAX) o.u[kb] += d;
+    }
+    if (tid == 0) o.u[k] += d_end;
+}
+
+// the path back from its end to box k: every slot on it takes the box of the slot before it, the first one box k
+__host__ __device__ inline void assoc_opt_augment(const AssocArgs& a, AssocOptLds& o, const AssocPath& p, int k, int tid) {
+    if (tid != 0 || p.end == -2) return;
+    int t = p.end >= 0 ? p.end : p.sink_from;
+    for (int hop = 0; hop < a.n_tracks && (unsigned)t < (unsigned)a.n_tracks; ++hop) {
+        const int before = o.way[t];
+        o.slot_box[t] = (unsigned)before < (unsigned)a.n_tracks ? o.slot_box[before] : k;
+        t = before;
+    }
+}
+
+// box_slot and box_cost as assoc_strike leaves them
+__host__ __device__ inline void assoc_opt_pairs(const AssocArgs& a, AssocLds& l, const AssocOptLds& o, int m, int tid, int nt) {
+    for (int t = tid; t < a.n_tracks; t += nt) {
+        const int k = o.slot_box[t];
+        if ((unsigned)k >= (unsigned)m) continue;
+        l.box_slot[k] = t;
+        l.box_cost[k] = l.c[t * ASSOC_LD + k];
+    }
+}
+
+__global__ __launch_bounds__(ASSOC_THREADS) void associate_tracks_optimal_kernel(AssocArgs a) {
+    __shared__ AssocLds l;
+    __shared__ AssocOptLds o;
+    __shared__ AssocCandD wave_best[2][ASSOC_THREADS / 64];   // two sets in turn: one barrier per visit
+    const int tid = threadIdx.x, nt = ASSOC_THREADS;
+    assoc_begin(a, l, tid, nt);
+    __syncthreads();
+    double t_first = 0.0;
+    const bool have_first = assoc_first_time(a, t_first);
+    assoc_retire(a, l, have_first, t_first, tid, nt);
+    __syncthreads();
+    int turn = 0;
+    for (int s = 0; s < a.n_steps; ++s) {                  // every branch below is taken by all threads or by none
+        int lo, m;
+        double t_step;
+        assoc_step_range(a, s, lo, m);
+        if (!assoc_step_time(a, lo, m, t_step)) continue;
+        assoc_step_boxes(a, l, lo, m, tid, nt);
+        assoc_opt_begin(a, o, m, tid, nt);
+        __syncthreads();
+        assoc_costs(a, l, m, t_step, tid, nt);
+        __syncthreads();
+        for (int k = 0; k < m; ++k) {
+            AssocPath p = assoc_opt_root(a, o, k, tid, nt);
+            for (int visit = 0; visit <= a.n_tracks && p.end == -2; ++visit) {
+                AssocCandD best = assoc_opt_relax(a, l, o, p, tid, nt);
+                for (int off = 32; off > 0; off >>= 1) {
+                    const AssocCandD other = {__shfl_xor(best.v, off), __shfl_xor(best.idx, off)};
+                    if (assoc_candd_less(other, best)) best = other;
+                }
+                if ((tid & 63) == 0) wave_best[turn][tid >> 6] = best;
+                __syncthreads();
+                best = wave_best[turn][0];
+                for (int w = 1; w < ASSOC_THREADS / 64; ++w)
+                    if (assoc_candd_less(wave_best[turn][w], best)) best = wave_best[turn][w];
+                turn ^= 1;
+                assoc_opt_advance(a, o, p, best);          // the same value in every thread
+            }
+            assoc_opt_duals(a, o, p, k, tid, nt);
+            __syncthreads();                               // the duals read slot_box before the path rewrites it
+            assoc_opt_augment(a, o, p, k, tid);
+            __syncthreads();
+        }
+        assoc_opt_pairs(a, l, o, m, tid, nt);
+        __syncthreads();
+        assoc_births(a, l, m, tid, nt);
+        __syncthreads();
+        assoc_apply(a, l, m, tid, nt);
+        __syncthreads();
+        assoc_filter(a, l, m, tid, nt);
+        __syncthreads();                                   // the working state and the box arrays, before the next step
+    }
+    assoc_starts(a, l, tid, nt);
+    __syncthreads();
+    for (int s = 0; s < a.n_steps; ++s) {
+        int lo, m;
+        assoc_step_range(a, s, lo, m);
+        if (m == 0) continue;
+        assoc_group_step(a, l, lo, m, tid, nt);
+        __syncthreads();
+    }
+    assoc_finish(a, l, tid, nt);
+}
+
 AssocArgs make_assoc_args(const float* poses, const float* cov, const double* times, int n, const int* step_rows, int n_step_rows,
                           const int* step_starts, int n_steps, int n_out, int measurement, double q, double r_floor, double cov_scale,
                           double v0, double gate, float max_cost_mm, double clip_mm, int min_joints, double max_age_s, double* state,
@@ -416,6 +613,21 @@ int launch_associate_tracks(const float* poses, const float* cov, const double* 
                                         starts_out, n_new, n_dropped);
     hipLaunchKernelGGL(associate_tracks_kernel, dim3(1), dim3(ASSOC_THREADS), 0, stream, a);
     return launch_status("associate_tracks");
+}
+
+int launch_associate_tracks_optimal(const float* poses, const float* cov, const double* times, int n, const int* step_rows, int n_step_rows,
+                                    const int* step_starts, int n_steps, int n_out, int measurement, double q, double r_floor,
+                                    double cov_scale, double v0, double gate, float max_cost_mm, double clip_mm, int min_joints,
+                                    double max_age_s, double* state, int n_tracks, int* ids, int* next_id, void* workspace, int* track_index,
+                                    int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new, int* n_dropped,
+                                    hipStream_t stream) {
+    if (note_kernel("associate_tracks_optimal")) return METRO_OK;
+    const AssocArgs a = make_assoc_args(poses, cov, times, n, step_rows, n_step_rows, step_starts, n_steps, n_out, measurement, q,
+                                                r_floor, cov_scale, v0, gate, max_cost_mm, clip_mm, min_joints, max_age_s, state, n_tracks,
+                                                ids, next_id, static_cast<double*>(workspace), track_index, track_id, cost_out, rows_out,
+                                                starts_out, n_new, n_dropped);
+    hipLaunchKernelGGL(associate_tracks_optimal_kernel, dim3(1), dim3(ASSOC_THREADS), 0, stream, a);
+    return launch_status("associate_tracks_optimal");
 }
 
 }  // namespace metro

@@ -736,17 +736,14 @@ int metro_smooth_tracks(const float* d_poses, const float* d_cov, const double* 
                                 d_used_out, static_cast<hipStream_t>(stream));
 }
 
-size_t metro_associate_tracks_workspace_bytes(int32_t n_tracks, int32_t n_joints_out) {
-    return associate_tracks_workspace_bytes(n_tracks, n_joints_out);
-}
-
-int metro_associate_tracks(const float* d_poses, const float* d_cov, const double* d_times, int32_t n,
-                           const int32_t* d_step_rows, int32_t n_step_rows, const int32_t* d_step_starts, int32_t n_steps,
-                           const MetroSpec* spec, int32_t measurement, double q, double r_floor, double cov_scale, double v0,
-                           double gate, float max_cost_mm, double clip_mm, int32_t min_joints, double max_age_s, double* d_state,
-                           int32_t n_tracks, int32_t* d_ids, int32_t* d_next_id, void* d_workspace, int32_t* d_track_index_out,
-                           int32_t* d_track_id_out, float* d_cost_out, int32_t* d_rows_out, int32_t* d_starts_out,
-                           int32_t* d_n_new_out, int32_t* d_n_dropped_out, void* stream) {
+// the argument checks of both association entries, then the launch of one
+static int associate_tracks_entry(bool optimal, const float* d_poses, const float* d_cov, const double* d_times, int32_t n,
+                                  const int32_t* d_step_rows, int32_t n_step_rows, const int32_t* d_step_starts, int32_t n_steps,
+                                  const MetroSpec* spec, int32_t measurement, double q, double r_floor, double cov_scale,
+                                  double v0, double gate, float max_cost_mm, double clip_mm, int32_t min_joints, double max_age_s,
+                                  double* d_state, int32_t n_tracks, int32_t* d_ids, int32_t* d_next_id, void* d_workspace,
+                                  int32_t* d_track_index_out, int32_t* d_track_id_out, float* d_cost_out, int32_t* d_rows_out,
+                                  int32_t* d_starts_out, int32_t* d_n_new_out, int32_t* d_n_dropped_out, void* stream) {
     METRO_CHECK_ARG(spec != nullptr, "associate_tracks: NULL spec");
     METRO_CHECK_ARG(spec->n_joints_out >= 1 && spec->n_joints_out <= METRO_MAX_JOINTS,
                     "associate_tracks: n_joints_out %d out of range [1, %d]", spec->n_joints_out, METRO_MAX_JOINTS);
@@ -773,10 +770,41 @@ int metro_associate_tracks(const float* d_poses, const float* d_cov, const doubl
                     "associate_tracks: NULL poses / times / steps / table / workspace / output pointer");
     METRO_CHECK_ARG(measurement != METRO_SMOOTH_COVARIANCE || d_cov,
                     "associate_tracks: METRO_SMOOTH_COVARIANCE reads the covariance: NULL");
-    return launch_associate_tracks(d_poses, d_cov, d_times, n, d_step_rows, n_step_rows, d_step_starts, n_steps, spec->n_joints_out,
-                                   measurement, q, r_floor, cov_scale, v0, gate, max_cost_mm, clip_mm, min_joints, max_age_s, d_state,
-                                   n_tracks, d_ids, d_next_id, d_workspace, d_track_index_out, d_track_id_out, d_cost_out, d_rows_out,
-                                   d_starts_out, d_n_new_out, d_n_dropped_out, static_cast<hipStream_t>(stream));
+    const auto launch = optimal ? launch_associate_tracks_optimal : launch_associate_tracks;
+    return launch(d_poses, d_cov, d_times, n, d_step_rows, n_step_rows, d_step_starts, n_steps, spec->n_joints_out, measurement, q,
+                  r_floor, cov_scale, v0, gate, max_cost_mm, clip_mm, min_joints, max_age_s, d_state, n_tracks, d_ids, d_next_id,
+                  d_workspace, d_track_index_out, d_track_id_out, d_cost_out, d_rows_out, d_starts_out, d_n_new_out, d_n_dropped_out,
+                  static_cast<hipStream_t>(stream));
+}
+
+size_t metro_associate_tracks_workspace_bytes(int32_t n_tracks, int32_t n_joints_out) {
+    return associate_tracks_workspace_bytes(n_tracks, n_joints_out);
+}
+
+int metro_associate_tracks(const float* d_poses, const float* d_cov, const double* d_times, int32_t n,
+                           const int32_t* d_step_rows, int32_t n_step_rows, const int32_t* d_step_starts, int32_t n_steps,
+                           const MetroSpec* spec, int32_t measurement, double q, double r_floor, double cov_scale, double v0,
+                           double gate, float max_cost_mm, double clip_mm, int32_t min_joints, double max_age_s, double* d_state,
+                           int32_t n_tracks, int32_t* d_ids, int32_t* d_next_id, void* d_workspace, int32_t* d_track_index_out,
+                           int32_t* d_track_id_out, float* d_cost_out, int32_t* d_rows_out, int32_t* d_starts_out,
+                           int32_t* d_n_new_out, int32_t* d_n_dropped_out, void* stream) {
+    return associate_tracks_entry(false, d_poses, d_cov, d_times, n, d_step_rows, n_step_rows, d_step_starts, n_steps, spec,
+                                  measurement, q, r_floor, cov_scale, v0, gate, max_cost_mm, clip_mm, min_joints, max_age_s, d_state,
+                                  n_tracks, d_ids, d_next_id, d_workspace, d_track_index_out, d_track_id_out, d_cost_out, d_rows_out,
+                                  d_starts_out, d_n_new_out, d_n_dropped_out, stream);
+}
+
+int metro_associate_tracks_optimal(const float* d_poses, const float* d_cov, const double* d_times, int32_t n,
+                                   const int32_t* d_step_rows, int32_t n_step_rows, const int32_t* d_step_starts, int32_t n_steps,
+                                   const MetroSpec* spec, int32_t measurement, double q, double r_floor, double cov_scale, double v0,
+                                   double gate, float max_cost_mm, double clip_mm, int32_t min_joints, double max_age_s, double* d_state,
+                                   int32_t n_tracks, int32_t* d_ids, int32_t* d_next_id, void* d_workspace, int32_t* d_track_index_out,
+                                   int32_t* d_track_id_out, float* d_cost_out, int32_t* d_rows_out, int32_t* d_starts_out,
+                                   int32_t* d_n_new_out, int32_t* d_n_dropped_out, void* stream) {
+    return associate_tracks_entry(true, d_poses, d_cov, d_times, n, d_step_rows, n_step_rows, d_step_starts, n_steps, spec,
+                                  measurement, q, r_floor, cov_scale, v0, gate, max_cost_mm, clip_mm, min_joints, max_age_s, d_state,
+                                  n_tracks, d_ids, d_next_id, d_workspace, d_track_index_out, d_track_id_out, d_cost_out, d_rows_out,
+                                  d_starts_out, d_n_new_out, d_n_dropped_out, stream);
 }
 
 const char* metro_last_error(void) { return metro::get_error(); }

@@ -474,6 +474,13 @@ int launch_associate_tracks(const float* poses, const float* cov, const double* 
                             double max_age_s, double* state, int n_tracks, int* ids, int* next_id, void* workspace, int* track_index,
                             int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new, int* n_dropped,
                             hipStream_t stream);
+// the same walk with the optimal assignment in place of the greedy one (associate_tracks.hip)
+int launch_associate_tracks_optimal(const float* poses, const float* cov, const double* times, int n, const int* step_rows, int n_step_rows,
+                                    const int* step_starts, int n_steps, int n_out, int measurement, double q, double r_floor,
+                                    double cov_scale, double v0, double gate, float max_cost_mm, double clip_mm, int min_joints,
+                                    double max_age_s, double* state, int n_tracks, int* ids, int* next_id, void* workspace, int* track_index,
+                                    int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new, int* n_dropped,
+                                    hipStream_t stream);
 // per-box crop geometry of full frames (look_at_boxes.hip)
 int launch_look_at_boxes(const double* boxes, const int32_t* frame_index, int n, int n_frames, const MetroFrameCamera* cameras,
                          int n_cameras, int side, MetroViewBase* out, int32_t* status, hipStream_t stream);

@@ -56,6 +56,9 @@ the box centre, drops the lens distortion, squares the pixels and zooms so the b
                                           the frame's calibrated camera and writes one box per (frame, track), compacted on
                                           the device and fused with whatever boxes a detector did give; the rows go into the
                                           calls above as they are.  Nothing in the reference
+  Follower                                one followed stream: follow_poses_in_frames or follow_world_poses_in_frames with the
+                                          keywords checked once, the assignment rule chosen ('greedy', or 'optimal':
+                                          metro_associate_tracks_optimal) and the table of tracks kept between calls
 
 Divergences from the reference, on purpose (camera.py and frame_formats.py list their own):
   * reproject_image's case 1 (cameralib.py:282-293: an all-zero coefficient array whose virtual R is allclose to the original
@@ -1405,7 +1408,8 @@ def follow_poses_in_frames(frames, boxes, model_path, cameras, frame_index, time
     (None: half the output joints, rounded up) and for a slot last seen more than max_age_s before; slots and boxes are
     paired greedily, the smallest cost first, while it is below max_cost_mm (one box per slot, one slot per box); a box left
     over starts a new track in the lowest free slot, under the next id; with no slot free it stays untracked (-1, counted in
-    n_dropped), as does a box with no finite joint.  The pairing is greedy, not an optimal assignment.  track_index is the
+    n_dropped), as does a box with no finite joint.  The pairing is greedy, not an optimal assignment (Follower and
+    follow_world_poses_in_frames take assignment='optimal'; heads.associate_tracks has both rules).  track_index is the
     slot (what track_poses_in_frames calls a track), track_id the identity that persists when slots are reused.
     max_cost_mm = 300, clip_mm = 600, max_age_s = 1 and the min_joints default are design choices, not measurements
     (heads.associate_tracks has the reasoning).
@@ -1421,7 +1425,19 @@ def follow_poses_in_frames(frames, boxes, model_path, cameras, frame_index, time
     ValueError before any launch for more than 128 boxes on one timestamp, capacity outside [1, 128], a tracks that is no
     table, scale_recovery 'metro', max_cost_mm, clip_mm, min_joints or max_age_s out of range, and whatever
     track_poses_in_frames refuses."""
-    from metro_pose3d_amd.heads import associate_tracks, association_params, smooth_tracks, smoothing_params
+    return _follow_poses(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity, max_cost_mm, clip_mm, min_joints,
+                         max_age_s, mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, scale_recovery,
+                         bone_lengths, root_depth, coords, precision, check_finite, views, geometry, pixel_format, color_matrix,
+                         crop_dtype, 'greedy')
+
+
+def _follow_poses(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity, max_cost_mm, clip_mm, min_joints,
+                  max_age_s, mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, scale_recovery,
+                  bone_lengths, root_depth, coords, precision, check_finite, views, geometry, pixel_format, color_matrix, crop_dtype,
+                  assignment):
+    """follow_poses_in_frames with the assignment rule of heads.associate_tracks chosen ('greedy' there; Follower passes its own)."""
+    from metro_pose3d_amd.heads import associate_tracks, association_params, assignment_rule, smooth_tracks, smoothing_params
+    assignment_rule(assignment)
     smoothing_params(mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate)
     association_params(max_cost_mm, clip_mm, min_joints, max_age_s)
     if scale_recovery == 'metro':
@@ -1448,7 +1464,7 @@ def follow_poses_in_frames(frames, boxes, model_path, cameras, frame_index, time
     with torch.cuda.device(device):
         found = associate_tracks(raw.poses, raw.covariance, times, step_rows, step_starts, tracks.state, tracks.ids, tracks.next_id,
                                  max_cost_mm, clip_mm, min_joints, max_age_s, measurement, accel_psd, sigma_floor_mm, cov_scale,
-                                 initial_speed_mm_s, gate)
+                                 initial_speed_mm_s, gate, assignment)
         poses, velocity, covariance, used = smooth_tracks(raw.poses, raw.covariance, times, found.rows, found.starts, mode, measurement,
                                                           accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, tracks.state)
     smoothed = TrackPoses(poses, velocity, covariance, used, raw, tracks.state, raw.joint_edges, raw.joint_names)
@@ -1494,7 +1510,8 @@ def follow_world_poses_in_frames(frames, boxes, model_path, cameras, frame_index
                                  accel_psd: float = 4e6, sigma_floor_mm: float = 1.0, cov_scale: float = 1.0,
                                  initial_speed_mm_s: float = 2000.0, gate=None, views=None, precision: Optional[str] = None,
                                  check_finite: Optional[bool] = None, geometry: str = 'auto', pixel_format: str = 'rgb',
-                                 color_matrix: str = 'bt601', crop_dtype: str = 'float32') -> FollowedWorldPoses:
+                                 color_matrix: str = 'bt601', crop_dtype: str = 'float32',
+                                 assignment: str = 'greedy') -> FollowedWorldPoses:
     """A calibrated rig's video: a person detector's boxes per camera and per exposure, unordered and without identity ->
     FollowedWorldPoses: the boxes matched across the cameras of each exposure (match_poses_in_frames), every person found
     triangulated in the world with the covariance of each joint, the persons followed from exposure to exposure under ids that
@@ -1511,6 +1528,8 @@ def follow_world_poses_in_frames(frames, boxes, model_path, cameras, frame_index
     are design choices, not measurements (heads.view_affinity, heads.associate_tracks and heads.smooth_tracks have the
     reasoning).  tracks and capacity as in follow_poses_in_frames: the table carries over between calls, so a stream cut into
     calls at step boundaries gets the ids and filter states one long call gives.
+    assignment: 'greedy' (the default: the smallest cost first) or 'optimal' (the admissible pairs of the largest total gain
+    max_cost_mm - cost, which keeps the ids of persons close together where greedy swaps them), heads.associate_tracks' rule.
     Two boxes of different time steps are never matched (their cost is +inf, as for two boxes of one frame), so a person found
     lives in one step: P counts persons per step.  With weights 'uniform' exactly meeting rays give a zero covariance;
     sigma_floor_mm keeps the measurement noise positive definite.
@@ -1524,8 +1543,9 @@ def follow_world_poses_in_frames(frames, boxes, model_path, cameras, frame_index
     ValueError before any launch for more than 128 boxes or 64 frames, cameras=None, timestamps that are not finite or match
     neither frames nor boxes, capacity outside [1, 128], a tracks that is no table or has another joint count than the model,
     and whatever match_poses_in_frames and follow_poses_in_frames refuse of their keywords."""
-    from metro_pose3d_amd.heads import (MATCH_MAX_BOXES, associate_tracks, association_params, matching_params, person_steps,
-                                        smooth_tracks, smoothing_params, triangulation_min_det)
+    from metro_pose3d_amd.heads import (MATCH_MAX_BOXES, associate_tracks, association_params, assignment_rule, matching_params,
+                                        person_steps, smooth_tracks, smoothing_params, triangulation_min_det)
+    assignment_rule(assignment)
     triangulation_min_det(weights, min_angle_deg)
     matching_params(match_clip_mm, match_min_joints, match_max_cost_mm)
     smoothing_params(mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate)
@@ -1559,7 +1579,7 @@ def follow_world_poses_in_frames(frames, boxes, model_path, cameras, frame_index
         person_step, person_times, step_rows, step_starts = person_steps(rows, starts, n_persons, box_step, step_times, n_views)
         found = associate_tracks(poses, cov, person_times, step_rows, step_starts, tracks.state, tracks.ids, tracks.next_id,
                                  max_cost_mm, clip_mm, min_joints, max_age_s, measurement, accel_psd, sigma_floor_mm, cov_scale,
-                                 initial_speed_mm_s, gate)
+                                 initial_speed_mm_s, gate, assignment)
         return person_step, found, smooth_tracks(poses, cov, person_times, found.rows, found.starts, mode, measurement, accel_psd,
                                                  sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, tracks.state)
 
@@ -1657,3 +1677,75 @@ def predict_boxes_in_frames(tracks: TrackTable, cameras, frame_sizes, timestamps
     _raise_on_bad_frames(n_bad_frames, 0 if detections is None else len(detections), len(sizes))
     return PredictedBoxes(rows.boxes[:n], rows.frame_index[:n], rows.track_index[:n], rows.track_id[:n], rows.detection[:n],
                           rows.n_joints[:n], n_predicted, n_suppressed, n_bad, rows.dense_boxes, rows.dense_joints)
+
+
+# ---- one object per followed stream: the keywords checked once, the table of tracks carried from call to call ----
+
+_FOLLOWER_GIVEN = ('frames', 'boxes', 'model_path', 'cameras', 'frame_index', 'timestamps', 'tracks', 'capacity', 'assignment')
+
+
+class Follower:
+    """A followed stream: follow_poses_in_frames (world=False: one calibrated camera, tracks in its frame or, with
+    coords='world', in the world) or follow_world_poses_in_frames (world=True: a calibrated rig) with the model, the
+    cameras, the assignment rule and every keyword fixed at construction, and the table of tracks kept between calls.
+
+    Follower(model_path, cameras, world=False, assignment='greedy', capacity=64, **keywords): `keywords` are those of the
+    chosen call other than frames, boxes, model_path, cameras, frame_index, timestamps, tracks and capacity; an unknown name
+    is a TypeError here, and the values are checked here by the calls' own validators (heads.association_params,
+    heads.smoothing_params and, with world=True, heads.matching_params and heads.triangulation_min_det), so a bad keyword
+    fails before the first frame.  assignment: 'greedy' or 'optimal', heads.associate_tracks' rule.
+    .follow(frames, boxes, frame_index, timestamps) -> FollowedPoses / FollowedWorldPoses of these boxes, continuing
+    .tracks (None before the first call: a fresh table of `capacity` slots), which then is the table the call returned.
+    .predict(frame_sizes, timestamps, **keywords) -> predict_boxes_in_frames on .tracks with the follower's cameras and
+    coordinates.  .reset() drops the table: the next call starts new tracks from id 0."""
+
+    def __init__(self, model_path, cameras, world: bool = False, assignment: str = 'greedy', capacity: int = 64, **keywords):
+        import inspect
+        from metro_pose3d_amd.heads import (association_params, assignment_rule, matching_params, smoothing_params,
+                                            triangulation_min_det)
+        if not isinstance(world, (bool, np.bool_)):
+            raise ValueError(f'world must be True or False, got {world!r}')
+        params = inspect.signature(follow_world_poses_in_frames if world else follow_poses_in_frames).parameters
+        defaults = {k: p.default for k, p in params.items() if k not in _FOLLOWER_GIVEN}
+        unknown = [k for k in keywords if k not in defaults]
+        if unknown:
+            raise TypeError(f"Follower(world={bool(world)}) got an unexpected keyword {unknown[0]!r}: it takes "
+                            f"{', '.join(defaults)}")
+        kw = dict(defaults, **keywords)
+        assignment_rule(assignment)
+        new_track_table(capacity, 1, 'cpu')                 # the capacity check
+        association_params(kw['max_cost_mm'], kw['clip_mm'], kw['min_joints'], kw['max_age_s'])
+        smoothing_params(kw['mode'], kw['measurement'], kw['accel_psd'], kw['sigma_floor_mm'], kw['cov_scale'],
+                         kw['initial_speed_mm_s'], kw['gate'])
+        if world:
+            matching_params(kw['match_clip_mm'], kw['match_min_joints'], kw['match_max_cost_mm'])
+            triangulation_min_det(kw['weights'], kw['min_angle_deg'])
+            if cameras is None:
+                raise ValueError('cameras: following in the world needs the calibrated cameras of the rig')
+        elif kw['scale_recovery'] == 'metro':
+            raise ValueError("scale_recovery='metro' returns root-relative poses, in which all persons coincide: following needs "
+                             "absolute poses ('bone-lengths' or 'true-root-depth')")
+        self.model_path, self.cameras, self.world = model_path, cameras, bool(world)
+        self.assignment, self.capacity, self.keywords = assignment, int(capacity), kw
+        self.tracks: Optional[TrackTable] = None
+
+    def follow(self, frames, boxes, frame_index, timestamps):
+        if self.world:
+            out = follow_world_poses_in_frames(frames, boxes, self.model_path, self.cameras, frame_index, timestamps, tracks=self.tracks,
+                                               capacity=self.capacity, assignment=self.assignment, **self.keywords)
+        else:
+            out = _follow_poses(frames, boxes, self.model_path, self.cameras, frame_index, timestamps, self.tracks, self.capacity,
+                                assignment=self.assignment, **self.keywords)
+        self.tracks = out.tracks
+        return out
+
+    def predict(self, frame_sizes, timestamps, **keywords) -> PredictedBoxes:
+        if self.tracks is None:
+            raise ValueError('Follower.predict: no table of tracks yet (call follow first)')
+        if 'coords' in keywords:
+            raise TypeError("Follower.predict: coords is the follower's own")
+        coords = 'world' if self.world else self.keywords['coords']
+        return predict_boxes_in_frames(self.tracks, self.cameras, frame_sizes, timestamps, coords=coords, **keywords)
+
+    def reset(self):
+        self.tracks = None

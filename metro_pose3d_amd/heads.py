@@ -14,7 +14,7 @@ through the C ABI (csrc/heads.hip).  Names and argument meaning follow the refer
                             triangulate_joints reads, all on the device
   person_steps              the time step of every person cluster_views found and the time-step CSR associate_tracks reads,
                             on the device
-  associate_tracks          which box of a video continues which track: greedy assignment on predicted poses, births and the
+  associate_tracks          which box of a video continues which track: greedy or optimal assignment on predicted poses, births and the
                             CSR grouping smooth_tracks reads, one workgroup
   predict_boxes             next-frame person boxes from the track table: the filter's prediction of every live track through
                             the frames' calibrated cameras, compacted on the device and fused with a detector's boxes
@@ -490,11 +490,21 @@ def association_params(max_cost_mm, clip_mm, min_joints, max_age_s):
         raise ValueError(f'max_age_s must be a number >= 0 (seconds), got {max_age_s!r}')
 
 
+ASSIGNMENTS = ('greedy', 'optimal')
+
+
+def assignment_rule(assignment):
+    """Checks the `assignment` keyword of associate_tracks, frames.follow_world_poses_in_frames and frames.Follower."""
+    if not isinstance(assignment, str) or assignment not in ASSIGNMENTS:
+        raise ValueError(f"assignment must be 'greedy' or 'optimal', got {assignment!r}")
+
+
 def associate_tracks(poses: torch.Tensor, covariance: Optional[torch.Tensor], times, step_rows, step_starts, state: torch.Tensor,
                      ids: torch.Tensor, next_id: torch.Tensor, max_cost_mm: float = 300.0, clip_mm: float = 600.0,
                      min_joints: Optional[int] = None, max_age_s: float = 1.0, measurement: str = 'covariance',
                      accel_psd: float = 4e6, sigma_floor_mm: float = 1.0, cov_scale: float = 1.0,
-                     initial_speed_mm_s: float = 2000.0, gate: Optional[float] = None) -> AssociatedTracks:
+                     initial_speed_mm_s: float = 2000.0, gate: Optional[float] = None,
+                     assignment: str = 'greedy') -> AssociatedTracks:
     """Which box of a video continues which track, one metro_associate_tracks launch (one workgroup, the cost matrix in LDS;
     include/metro_hip.h has the model).  poses [n,J,3] mm ABSOLUTE, covariance and times as smooth_tracks reads them;
     step s owns the boxes step_rows[step_starts[s]:step_starts[s+1]], the steps in ascending time, all boxes of one
@@ -507,12 +517,22 @@ def associate_tracks(poses: torch.Tensor, covariance: Optional[torch.Tensor], ti
     (J + 1) // 2 -- or for a slot last seen more than max_age_s ago); boxes and slots are paired greedily, smallest cost
     first, while it is below max_cost_mm; the remaining boxes start new tracks in the lowest free slots; every slot that got
     a box advances a working copy of the state by smooth_tracks' filter step, with the same measurement, accel_psd,
-    sigma_floor_mm, cov_scale, initial_speed_mm_s and gate.  The pairing is greedy, not an optimal assignment.
+    sigma_floor_mm, cov_scale, initial_speed_mm_s and gate.
+    assignment 'greedy' (the default): that pairing, which is not an optimal assignment -- with tracks A at x = 0 and B at
+    x = 230 mm and boxes at -120 and +100 it takes A-(+100) at 100 mm, after which B has no box within max_cost_mm: A continues
+    in B's box, A's own box is born under a new id and B is bridged.  assignment 'optimal' (one
+    metro_associate_tracks_optimal launch, the same workgroup and cost matrix): with g = max_cost_mm a pair is admissible if
+    its cost c < g, and the pairing is the one-to-one set of admissible pairs that minimises the sum of (c - g), i.e.
+    maximises the total gain sum (g - c) -- the linear assignment problem on min(c, g) in which a pair at g means
+    "unmatched", solved exactly by shortest augmenting paths in fp64; above it keeps both ids, at 120 + 130 mm.  This is
+    not a maximum-cardinality matching: one pair at 10 mm beats two at 299 mm each.  Costs, births, n_dropped, the filter
+    step and the CSR are the same code under both rules.
     max_cost_mm = 300, clip_mm = 600, max_age_s = 1 and the min_joints default are design choices, not measurements: 300 mm
     is below the distance between two persons side by side and above what a person's joints move against a constant-velocity
     prediction within a few frames; 600 mm keeps one wild joint from deciding a pair; one second bridges a short occlusion
     without handing a long-gone track's slot history to a newcomer; half the joints keeps a cost from resting on a few.
     -> AssociatedTracks; its rows / starts and `state` go to smooth_tracks unchanged.  No boxes or no steps: no launch."""
+    assignment_rule(assignment)
     params = smoothing_params('filter', measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate)
     association_params(max_cost_mm, clip_mm, min_joints, max_age_s)
     if not isinstance(poses, torch.Tensor) or poses.dim() != 3 or poses.shape[2] != 3 or not 1 <= poses.shape[1] <= _lib.METRO_MAX_JOINTS:
@@ -561,10 +581,11 @@ def associate_tracks(poses: torch.Tensor, covariance: Optional[torch.Tensor], ti
     cov = covariance.to(torch.float32).reshape(n, nj, 9).contiguous() if with_cov else None
     ws = torch.empty(lib.metro_associate_tracks_workspace_bytes(n_tracks, nj), dtype=torch.uint8, device=dev)
     cs = _lib.MetroSpec(n_joints_out=nj)
-    check(lib.metro_associate_tracks(_p(poses), _p(cov), _p(times), n, _p(step_rows), n_step_rows, _p(step_starts), n_starts - 1,
-                                     C.byref(cs), *params[1:], float(max_cost_mm), float(clip_mm), int(min_joints), float(max_age_s),
-                                     _p(state), n_tracks, _p(ids), _p(next_id), _p(ws), _p(track_index), _p(track_id), _p(cost), _p(rows),
-                                     _p(starts), _p(n_new), _p(n_dropped), _stream(dev)), 'metro_associate_tracks')
+    entry = 'metro_associate_tracks_optimal' if assignment == 'optimal' else 'metro_associate_tracks'
+    check(getattr(lib, entry)(_p(poses), _p(cov), _p(times), n, _p(step_rows), n_step_rows, _p(step_starts), n_starts - 1,
+                              C.byref(cs), *params[1:], float(max_cost_mm), float(clip_mm), int(min_joints), float(max_age_s),
+                              _p(state), n_tracks, _p(ids), _p(next_id), _p(ws), _p(track_index), _p(track_id), _p(cost), _p(rows),
+                              _p(starts), _p(n_new), _p(n_dropped), _stream(dev)), entry)
     return AssociatedTracks(track_index, track_id, cost, rows, starts, n_new, n_dropped,
                             ws.view(torch.float64).view(n_tracks, nj, TRACK_STATE_DOUBLES))
 
