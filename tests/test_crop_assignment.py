@@ -13,8 +13,9 @@ import torch
 from tests import helpers as H
 
 # (n, p): test_kernel_coverage.py's batches at p = min(4, n), and the real-batch cases of test_f16_layerwise.py (two oracle crops)
-COVERAGE_BATCHES = (1, 8, 16, 32, 64, 130, 256)
-PAIRS = [(n, min(4, n)) for n in COVERAGE_BATCHES] + [(16, 2), (32, 2), (64, 2), (130, 2), (256, 2)]
+# (+ odd call sizes of the single launches and the ragged real-batch cases)
+COVERAGE_BATCHES = (1, 8, 16, 32, 64, 130, 256, 13, 31, 49, 63, 101, 135, 253)
+PAIRS = [(n, min(4, n)) for n in COVERAGE_BATCHES] + [(16, 2), (32, 2), (64, 2), (130, 2), (256, 2), (5, 2), (13, 2), (63, 2)]
 SEEDS = (0, 1, zlib.crc32(b'C4-rn101-s8-J19-b32/block3/unit_2/conv2'))
 ROTATIONS = (1, 2, 4, 8, 16)
 

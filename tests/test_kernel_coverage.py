@@ -16,6 +16,9 @@ instantiation (a dry run of the dispatch, no device needed), so this file can
     faults): a launch that stores whole tiles into other tiles' slots -- with image i = image i mod 4 it would give every
     position "its twin's bits" whenever it moves results by a multiple of four images -- fails the twin check, so each tile
     position of the launch is held to the oracle at the cost of four images.
+  * (`-m gpu`) the same for single launches (spec, batch, layer): the instantiations that only call sizes off the powers of two
+    reach (SINGLE_LAUNCHES), and every (kernel id, layer shape) pair of the released models' crop side that the cases above do
+    not launch -- the list comes from the dry run over every call size 1 .. 256 that the two CPU closure tests make.
 """
 import ctypes as C
 import zlib
@@ -77,13 +80,62 @@ GRID_SIDES = range(64, 513, 32)
 GRID_ARCHS = (50, 101)
 GRID_STRIDES = (4, 8, 16, 32)
 GRID_DATASETS = ('h36m', 'many19', 'merged')
-GRID_BATCHES = (1, 8, 16, 32, 64, 128, 256)
+GRID_BATCHES = range(1, 257)    # every call size: estimate_pose forwards what it is given, the frames chain calls with boxes x views crops
+
+# Single launches away from proc_side 256: (spec, batch, layer) at the cheapest shape of the grid that reaches an instantiation
+# no configuration above and no test_f16_layerwise case dispatches -- both are reached at call sizes off the powers of two only.
+# (Not CONFIGS entries: a configuration adds a case per id it dispatches, and at 4 crops of side 512 those are fifteen more
+# launches on 128 x 128 maps, ~490 GFLOP of fp64 reference for ids that are held elsewhere.)
+SINGLE_LAUNCHES = [
+    # conv_igemm_f16_dma<256x256,bk32,s4,pro>: the conv1 layers of block3 / block4 (1024 -> 256, 2048 -> 512) once the call has
+    # ~250 tiles of 256 pixels, e.g. RN50-s4 at side 224 from 11 crops on.  Here 135 crops of 22 x 22 maps: 65 340 pixels, the last
+    # of 256 tiles holds 60 of them
+    (ModelSpec(50, 16, 'h36m', proc_side=352), 135, 'block3/unit_2/conv1'),
+    # conv3x3_f16_slab<128x256,rows384,...>+subgrid: block2's rate-2 3x3 at stride 4 on 128 x 128 maps, at 4..7 crops only
+    # (fewer: 64-cout tiles; more: 512-pixel tiles).  4 crops: all four positions held to fp64 themselves
+    (ModelSpec(50, 4, 'h36m', proc_side=512), 4, 'block2/unit_1/conv2'),
+]
+
+# The (kernel id, layer shape) closure (test_pair_closure): the released models' crop side, every arch / stride / head, every call size
+PAIR_SPECS = [ModelSpec(a, s, d) for a in GRID_ARCHS for s in GRID_STRIDES for d in GRID_DATASETS]
+# what a launch's runtime arguments (K-loop length, halo, dilation, map side, residual form, fused outputs) are made of
+SHAPE_KEY = ('kind', 'c_in', 'c_out', 'h_in', 'h_out', 'kh', 'stride', 'dilation', 'relu', 'has_residual', 'res_stride', 'res_offset',
+             'has_prologue', 'out_dtype', 'fused_flags', 'out2_channels')
+
+
+def shape_key(li):
+    return tuple(getattr(li, f) for f in SHAPE_KEY)
+
+
+def spec_name(spec):
+    return f'rn{spec.arch}-s{spec.stride}-{spec.dataset}' + ('' if spec.proc_side == 256 else f'-side{spec.proc_side}')
 
 
 def dispatch_table(spec, n):
     """[(layer index, MetroLayerInfo, kernel id)] of an f16 plan at batch n -- no GPU needed."""
     eng = Engine(spec, None, 'f16', max_batch=n)
     return list(zip(range(10 ** 6), eng.layer_infos(), eng.layer_kernels(n)))
+
+
+class DryRun:
+    """The dispatch of one spec at every batch up to max_batch from ONE plan (max_batch sizes the workspace slots and nothing else
+    of a plan; test_dispatch_closure holds that against dispatch_table for every configuration).  kernels(n, layers): the ids of
+    the given layer indices (all by default)."""
+
+    def __init__(self, spec, max_batch=256):
+        self.spec = spec
+        self.eng = Engine(spec, None, 'f16', max_batch=max_batch)
+        self.infos = self.eng.layer_infos()
+        self.names = [li.name.decode() for li in self.infos]
+        self.keys = [shape_key(li) for li in self.infos]
+        self._buf = C.create_string_buffer(1024)
+
+    def kernels(self, n, layers=None):
+        out = []
+        for i in range(len(self.infos)) if layers is None else layers:
+            check(self.eng.lib.metro_plan_layer_kernel(self.eng._plan, i, int(n), self._buf, len(self._buf)), 'metro_plan_layer_kernel')
+            out.append(self._buf.value.decode())
+        return out
 
 
 def _first_layers_by_id():
@@ -97,10 +149,92 @@ def _first_layers_by_id():
     return out
 
 
+def _layerwise_runs():
+    """(who, spec, batch) of every test_f16_layerwise case: each launches every layer of its plan at its real batch."""
+    from tests.test_f16_layerwise import CASES
+    return [(f'test_f16_layerwise[{i}]', c[0], c[2].get('batch', c[1]) if len(c) > 2 else c[1]) for i, c in enumerate(CASES)]
+
+
+def _launched_by(table, layer):
+    """The layers of a dispatch table that a case on `layer` launches: the one-launch head takes its finalize with it (_head)."""
+    _, li, kid = table[layer]
+    both = li.name == b'logits' and kid.startswith('head_f16')
+    return [layer, layer + 1] if both else [layer]
+
+
+def launched_pairs(config_cases, single_cases):
+    """{(kernel id, shape key): who} of what the GPU cases launch: of every configuration the layers its cases name (the first per
+    id, not the whole plan), every layer of the test_f16_layerwise cases, and the single launches (spec, batch, layer index)."""
+    out = {}
+    tables = {}
+    for p in config_cases:
+        cname, layer, _ = p.values
+        if cname not in tables:
+            tables[cname] = dispatch_table(*CONFIGS[cname])
+        for i in _launched_by(tables[cname], layer):
+            out.setdefault((tables[cname][i][2], shape_key(tables[cname][i][1])), cname)
+    for who, spec, n in _layerwise_runs():
+        for _, li, kid in dispatch_table(spec, n):
+            out.setdefault((kid, shape_key(li)), who)
+    for p in single_cases:
+        spec, n, layer, _ = p.values
+        table = dispatch_table(spec, n)
+        for i in _launched_by(table, layer):
+            out.setdefault((table[i][2], shape_key(table[i][1])), p.id)
+    return out
+
+
+_UNIVERSE = {}
+
+
+def pair_universe():
+    """{(kernel id, shape key): (spec, n, layer index)} over PAIR_SPECS x GRID_BATCHES: the point with the smallest n (then the
+    first spec) that reaches each pair.  One dry run per process, shared by the case list below and test_pair_closure."""
+    if not _UNIVERSE:
+        for spec in PAIR_SPECS:
+            run = DryRun(spec)
+            for n in GRID_BATCHES:
+                for i, kid in enumerate(run.kernels(n)):
+                    at = _UNIVERSE.get((kid, run.keys[i]))
+                    if at is None or n < at[1]:
+                        _UNIVERSE[(kid, run.keys[i])] = (spec, n, i)
+    return _UNIVERSE
+
+
+def _single_param(spec, n, layer, kid, name):
+    return pytest.param(spec, n, layer, kid, id=f'{spec_name(spec)}-b{n}:{name}:{kid}')
+
+
+def _single_launches():
+    """SINGLE_LAUNCHES, then for every pair of the universe that no configuration case and no test_f16_layerwise case launches the
+    (spec, smallest n, layer) that reaches it.  A head's finalize launch comes with the head case of the same (spec, n)."""
+    out = []
+    for spec, n, name in SINGLE_LAUNCHES:
+        table = dispatch_table(spec, n)
+        i = [li.name.decode() for _, li, _ in table].index(name)
+        out.append(_single_param(spec, n, i, table[i][2], name))
+    have = launched_pairs(_CASES, out)
+    todo = sorted(((spec_name(spec), n, i), pair) for pair, (spec, n, i) in pair_universe().items() if pair not in have)
+    specs = {spec_name(s): s for s in PAIR_SPECS}
+    for (sname, n, i), pair in todo:        # in (spec, n, layer) order: a head in front of its finalize
+        if pair in have:
+            continue
+        spec = specs[sname]
+        table = dispatch_table(spec, n)
+        if table[i][1].name == b'softargmax' and pair[0] == 'softargmax_finalize<acc32>':
+            i -= 1                          # launched by the head in front of it
+        out.append(_single_param(spec, n, i, table[i][2], table[i][1].name.decode()))
+        for k in _launched_by(table, i):
+            have.setdefault((table[k][2], shape_key(table[k][1])), out[-1].id)
+    return out
+
+
 try:
     _CASES = _first_layers_by_id()
+    _SINGLE_CASES = _single_launches()
 except Exception as e:  # noqa: BLE001  (library not built: the CPU test below reports it)
     _CASES = [pytest.param(None, -1, str(e), id='library-missing')]
+    _SINGLE_CASES = [pytest.param(None, 0, -1, str(e), id='library-missing')]
 
 
 # ---- CPU ---------------------------------------------------------------------------------------------------------------
@@ -167,41 +301,85 @@ def test_every_layer_names_its_kernel_without_a_gpu():
     assert all(ids[c]['conv1+pool1'] == 'stem_pool_f16<split2,f32in>' for c in ids if '-side' in c)
 
 
-def _gpu_tested_ids():
-    """Every kernel id a GPU test launches: the CONFIGS above (this file) and the layer-by-layer cases of test_f16_layerwise.py,
-    each at its real batch."""
-    from tests.test_f16_layerwise import CASES
+def _gpu_tested_ids(single_cases=None):
+    """Every kernel id a GPU test launches: the CONFIGS above (this file), the layer-by-layer cases of test_f16_layerwise.py, each
+    at its real batch, and the single launches."""
     out = {}
-    runs = [(c, s, n) for c, (s, n) in CONFIGS.items()]
-    runs += [(f'test_f16_layerwise[{i}]', c[0], c[2].get('batch', c[1]) if len(c) > 2 else c[1]) for i, c in enumerate(CASES)]
-    for who, spec, n in runs:
+    for who, spec, n in [(c, s, n) for c, (s, n) in CONFIGS.items()] + _layerwise_runs():
         for k in Engine(spec, None, 'f16', max_batch=n).layer_kernels(n):
             out.setdefault(k, who)
+    for p in _SINGLE_CASES if single_cases is None else single_cases:
+        out.setdefault(p.values[3], p.id)
     return out
+
+
+def _same_backbone(a, b):
+    """The layers in front of the head of two plans that differ in the head only: same names, same shapes, same fused forms."""
+    skip = ('name', 'out_offset', 'out2_offset', 'out_sub_offset')        # (slot offsets follow the head's size)
+    fields = [f for f, _ in _lib.MetroLayerInfo._fields_ if f not in skip]
+    la, lb = a.names.index('logits'), b.names.index('logits')
+    return la == lb and a.names == b.names and \
+        all(getattr(x, f) == getattr(y, f) for x, y in zip(a.infos[:la], b.infos[:lb]) for f in fields)
 
 
 def test_dispatch_closure():
     """The supported range of the f16 path is the grid
 
         proc_side 64, 96, ..., 512  x  ResNet-v2 50 / 101  x  stride 4 / 8 / 16 / 32  x  h36m / many19 / merged heads
-        x  batch 1, 8, 16, 32, 64, 128, 256
+        x  EVERY batch 1 .. 256
 
     (a dry run of the dispatch: no device).  Every kernel instantiation a plan of this grid dispatches must be launched by a
-    GPU-tested configuration -- CONFIGS, or a test_f16_layerwise case at its real batch -- so no shape of the range reaches a
-    kernel no test has held to the fp64 reference."""
+    GPU test -- a configuration of CONFIGS, a test_f16_layerwise case at its real batch, or a single launch -- so no shape of
+    the range reaches a kernel no test has held to the fp64 reference.  The batches are not sampled: which kernel a layer runs
+    on turns on tile counts against the 256 CUs, and two instantiations of this grid are reached at no power of two.
+
+    The scan is whole: 408 specs x 256 batches, one plan per spec.  The many19 and merged specs are asked for their head
+    layers only, after the assertion that every layer in front of their head equals h36m's (metro_plan_layer_kernel is per
+    layer).  Measured: 8 s on the build machine (24 s with every layer of every spec)."""
     tested = _gpu_tested_ids()
+    # one plan serves every batch: the ids it names are those of a plan made for exactly that batch
+    for cname, (spec, n) in CONFIGS.items():
+        assert DryRun(spec).kernels(n) == [k for _, _, k in dispatch_table(spec, n)], cname
     untested = {}
     for side in GRID_SIDES:
         for arch in GRID_ARCHS:
             for stride in GRID_STRIDES:
+                base = None
                 for ds in GRID_DATASETS:
-                    spec = ModelSpec(arch, stride, ds, proc_side=side)
+                    run = DryRun(ModelSpec(arch, stride, ds, proc_side=side))
+                    layers = None
+                    if base is None:
+                        base = run
+                    else:
+                        assert _same_backbone(base, run), f'rn{arch}-s{stride}-{ds} at proc_side {side}: backbone differs from {base.spec.dataset}\'s'
+                        layers = range(run.names.index('logits'), len(run.names))
                     for n in GRID_BATCHES:
-                        for k in Engine(spec, None, 'f16', max_batch=n).layer_kernels(n):
+                        for k in run.kernels(n, layers):
                             if k not in tested:
                                 untested.setdefault(k, f'rn{arch}-s{stride}-{ds} at proc_side {side}, batch {n}')
     assert not untested, 'dispatched by the supported grid but launched by no GPU test (first plan that reaches it):\n' + \
         '\n'.join(f'  {k}: {w}' for k, w in sorted(untested.items()))
+
+
+def test_pair_closure():
+    """One level below test_dispatch_closure: an instantiation's runtime arguments (K-loop length, halo, dilation, map side,
+    residual form, fused outputs) come from the layer, so an id that is right on one layer shape can be wrong on another
+    (the sub-grid 3x3 on a layer beyond its slab was).  Every (kernel id, layer shape) pair -- the shape is SHAPE_KEY of
+    MetroLayerInfo -- that the released models' crop side dispatches,
+
+        proc_side 256  x  ResNet-v2 50 / 101  x  stride 4 / 8 / 16 / 32  x  h36m / many19 / merged heads  x  every batch 1 .. 256,
+
+    must be LAUNCHED by a GPU case: the layer a configuration's case names (the first per id, not its whole plan), any layer of
+    a test_f16_layerwise case at its real batch, or a single launch.  The stated limit: other crop sides stay at the level of
+    ids (test_dispatch_closure) -- the whole grid has some 1 700 pairs, most of which differ in the map side only."""
+    universe = pair_universe()
+    tested = launched_pairs(_CASES, _SINGLE_CASES)
+    print(f'\n{len(universe)} (kernel id, layer shape) pairs at proc_side 256; {len(tested)} pairs launched by the GPU cases '
+          f'({len(_CASES)} configuration cases, {len(_layerwise_runs())} layer-by-layer cases, {len(_SINGLE_CASES)} single launches)')
+    missing = {pair: at for pair, at in universe.items() if pair not in tested}
+    assert not missing, 'dispatched at proc_side 256 but launched by no GPU case (kernel id: the smallest call that reaches the shape):\n' + \
+        '\n'.join(f'  {kid}: {spec_name(spec)}, batch {n}, {DryRun(spec, n).names[i]} {dict(zip(SHAPE_KEY, key))}'
+                  for (kid, key), (spec, n, i) in sorted(missing.items(), key=lambda kv: (kv[0][0], kv[1][1])))
 
 
 def test_every_kernel_has_a_nonfinite_case(lib):
@@ -274,6 +452,7 @@ def _close(got, ref, what, tol=2e-3):
     got = np.asarray(got, np.float64)
     assert np.isfinite(got).all(), what
     err, scale = np.abs(got - ref).max(), np.abs(ref).max()
+    print(f'\n[{what}] worst |d| / layer maximum {err / scale:.2e} (bar {tol:g})')
     assert err <= tol * scale, (what, err, scale)
 
 
@@ -282,6 +461,23 @@ def _close(got, ref, what, tol=2e-3):
 def test_production_dispatch_against_fp64_reference(lib, cuda, cname, layer, kid):
     assert cname is not None, f'libmetro_hip.so could not be loaded at collection time: {kid}'
     spec, n = CONFIGS[cname]
+    if dispatch_table(spec, n)[layer][1].name == b'softargmax' and kid == 'softargmax_finalize<acc32>':
+        pytest.skip('launched (and compared) together with the head: see the logits case of this configuration')
+    _launch(lib, cuda, cname, spec, n, layer, kid)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('spec,n,layer,kid', _SINGLE_CASES)
+def test_single_launch_against_fp64_reference(lib, cuda, spec, n, layer, kid):
+    """SINGLE_LAUNCHES and the (kernel id, layer shape) pairs of test_pair_closure that no other case launches: one launch each,
+    at the smallest call that brings the instantiation to that layer shape, held like the configurations' cases -- the entry
+    point launches what the plan names, fp64 reference on the same fp16 operands (2e-3 of the layer maximum for fp16 outputs,
+    2e-5 for fp32 ones, 2e-3 mm for poses), every position of the call carrying its twin's bits."""
+    assert spec is not None, f'libmetro_hip.so could not be loaded at collection time: {kid}'
+    _launch(lib, cuda, f'{spec_name(spec)}-b{n}', spec, n, layer, kid)
+
+
+def _launch(lib, cuda, cname, spec, n, layer, kid):
     _, li, kid2 = dispatch_table(spec, n)[layer]
     assert kid2 == kid
     name = li.name.decode()
@@ -292,8 +488,6 @@ def test_production_dispatch_against_fp64_reference(lib, cuda, cname, layer, kid
     assign = _assignment(n, f'{cname}/{name}')
     check(lib.metro_kernel_notes(1), 'metro_kernel_notes')
     try:
-        if name == 'softargmax' and kid == 'softargmax_finalize<acc32>':
-            pytest.skip('launched (and compared) together with the head: see the logits case of this configuration')
         if name == 'softargmax':
             _softargmax(lib, cuda, spec, assign, gen, rng, kid)
         elif name == 'conv1+pool1':
@@ -354,9 +548,10 @@ def _head(lib, cuda, spec, li, assign, gen, rng, dev, kid):
     ref = xin.reshape(-1, k) @ w.astype(np.float64).T + b.astype(np.float64)
     ref = ref.reshape(p, side, side, c)
     got = logits[:p].cpu().double().numpy()
-    assert np.abs(got - ref).max() <= 2e-5 * np.abs(ref).max(), np.abs(got - ref).max() / np.abs(ref).max()
     want = logits_to_output(H.oracle_spec(spec), ref).numpy()
     d = np.abs(poses[:p].cpu().numpy() - want).max()
+    print(f'\n[{kid}] logits: worst |d| / maximum {np.abs(got - ref).max() / np.abs(ref).max():.2e} (bar 2e-05); poses {d:.2e} mm (bar 0.002)')
+    assert np.abs(got - ref).max() <= 2e-5 * np.abs(ref).max(), np.abs(got - ref).max() / np.abs(ref).max()
     assert d <= 2e-3, f'{kid}: poses {d} mm from the exact soft-argmax of the exact logits'
 
 
@@ -384,6 +579,7 @@ def _softargmax(lib, cuda, spec, assign, gen, rng, kid):
     got = poses[:p].cpu().numpy()
     assert np.isfinite(got).all(), kid
     d = np.abs(got - want).max()
+    print(f'\n[{kid}] poses {d:.2e} mm (bar 0.002)')
     assert d <= 2e-3, f'{kid}: poses {d} mm from the exact soft-argmax of the same logits'
     # the planted peaks pull the joints off the centre: the comparison is not of two maps' centres
     assert np.abs(want).max() > 50.0, np.abs(want).max()
