@@ -13,13 +13,13 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.path.join(HERE, 'libmetro_hip.so')
-SOURCES = ['conv_igemm_f16_dma.hip', 'conv_gemm4w.hip', 'conv3x3_f16_slab.hip', 'conv3x3_c64.hip', 'conv_pw64.hip', 'conv_b1.hip', 'conv_pws.hip', 'head_f16.hip', 'stem_pool_f16.hip', 'conv_igemm_f64acc.hip', 'conv_igemm_f32.hip', 'pool_softargmax.hip', 'eval_metrics.hip', 'heads.hip', 'place_poses.hip', 'covariances.hip', 'triangulate.hip', 'match_views.hip', 'world_tracks.hip', 'smooth_tracks.hip', 'associate_tracks.hip', 'predict_boxes.hip', 'views.hip', 'look_at_boxes.hip', 'planner.cpp', 'executor.cpp', 'entries.cpp']
+SOURCES = ['conv_igemm_f16_dma.hip', 'conv_gemm4w.hip', 'conv3x3_f16_slab.hip', 'conv3x3_c64.hip', 'conv_pw64.hip', 'conv_b1.hip', 'conv_pws.hip', 'head_f16.hip', 'stem_pool_f16.hip', 'conv_igemm_f64acc.hip', 'conv_igemm_f32.hip', 'warp_crops.hip', 'pool_softargmax.hip', 'eval_metrics.hip', 'heads.hip', 'place_poses.hip', 'covariances.hip', 'triangulate.hip', 'match_views.hip', 'world_tracks.hip', 'smooth_tracks.hip', 'associate_tracks.hip', 'predict_boxes.hip', 'views.hip', 'look_at_boxes.hip', 'planner.cpp', 'executor.cpp', 'entries.cpp']
 EXPERIMENTAL_LIB_PATH = os.path.join(HERE, 'libmetro_experimental.so')
 EXPERIMENTAL_SOURCES = [os.path.join('experimental', f) for f in ('conv_gemm8p.hip', 'conv_gemm4d.hip', 'exp_abi.cpp')]
 EXPERIMENTAL_HEADERS = [os.path.join('experimental', 'metro_experimental.h')]
 PROBE_SRC = os.path.normpath(os.path.join(HERE, '..', 'tools', 'peak_probe.hip'))
 PROBE_LIB_PATH = os.path.normpath(os.path.join(HERE, '..', 'tools', 'libmetro_probe.so'))
-HEADERS = ['metro_common.h', 'plan.h', 'gfx950_prims.h', 'backproject.h', 'tri_ray.h', 'smooth_step.h', os.path.join('..', '..', 'include', 'metro_hip.h')]
+HEADERS = ['metro_common.h', 'plan.h', 'gfx950_prims.h', 'backproject.h', 'camera_math.h', 'tri_ray.h', 'smooth_step.h', os.path.join('..', '..', 'include', 'metro_hip.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-x', 'hip', '-Wall',
          '-Wno-unused-function'] + os.environ.get('METRO_EXTRA_HIPCC_FLAGS', '').split()
 

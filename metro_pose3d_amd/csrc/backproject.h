@@ -1,8 +1,7 @@
 // Device pieces of the reference's metric back-projection, shared by heads.hip (backproject_kernel) and place_poses.hip
 // (place_poses_kernel) so that both run the same operations in the same order:
-//   * crop_pixel: heatmap_to_image (reference src/model/volumetric.py:288-295): coords * last_receptive_center (+ stride // 2);
-//   * ray_through: matmul_joint_coords(inv_intrinsics, [u, v, 1]) (volumetric.py:221-222), evaluated ((k0 u + k1 v) + k2 1);
-//   * rays_and_delta_z: the rays of every head joint and delta_z = (z - z_root) * box_size (volumetric.py:175-177);
+//   * rays_and_delta_z: the rays of every head joint (crop_pixel and ray_through, camera_math.h) and
+//     delta_z = (z - z_root) * box_size (volumetric.py:175-177);
 //   * z_offset_by_bones: optimize_z_offset_by_bones_single (src/model/bone_length_based_backproj.py:38-62), whose
 //     scipy.optimize.least_squares(method='lm') is MINPACK lmder; `lmder1` restates lmder / qrfac / lmpar / qrsolv for one
 //     unknown in fp64, operation by operation (mode 2, diag = 1, ftol = xtol = gtol = 1e-8, factor = 100, maxfev = 100;
@@ -13,6 +12,7 @@
 #pragma once
 
 #include "metro_common.h"
+#include "camera_math.h"
 
 #pragma clang fp contract(off)
 
@@ -193,17 +193,6 @@ __device__ static double lmder1(const LmProblem& prob, double x0) {
     return x;
 }
 
-// heatmap_to_image (volumetric.py:288-295): coords * last_receptive_center (+ stride // 2)
-__device__ inline void crop_pixel(const float* c01j, float lrc, float half_off, float& u, float& v) {
-    u = c01j[0] * lrc; v = c01j[1] * lrc;
-    u = u + half_off; v = v + half_off;
-}
-
-// inv_intrinsics . [u, v, 1] (volumetric.py:221-222)
-__device__ inline void ray_through(const float* k, float u, float v, float* cam) {
-    for (int i = 0; i < 3; ++i) cam[i] = (k[i * 3 + 0] * u + k[i * 3 + 1] * v) + k[i * 3 + 2] * 1.0f;
-}
-
 // rays of the nj head joints of one pose through its virtual camera's K^-1 and delta_z (volumetric.py:173-177)
 __device__ inline void rays_and_delta_z(const float* c01, const float* k, int nj, float lrc, float half_off, float box,
                                         float (*cam)[3], float* dz) {
@@ -237,33 +226,6 @@ __device__ inline float z_offset_by_bones(const float (*cam)[3], const float* dz
     prob.c = c; prob.d = d; prob.e = e; prob.m = ne;
     prob.t = targets;
     return (float)lmder1(prob, 2000.0);
-}
-
-// det of a row-major fp32 3x3 evaluated in fp64: tf.linalg.det's sign is what to_orig_cam tests (volumetric.py:279-281)
-__host__ __device__ inline double det3_f64(const float* r) {
-    return (double)r[0] * ((double)r[4] * r[8] - (double)r[5] * r[7]) -
-           (double)r[1] * ((double)r[3] * r[8] - (double)r[5] * r[6]) +
-           (double)r[2] * ((double)r[3] * r[7] - (double)r[4] * r[6]);
-}
-
-// R . p, evaluated ((r0 p0 + r1 p1) + r2 p2) per row (matmul_joint_coords in to_orig_cam, volumetric.py:277-278)
-__device__ inline void rotate3(const float* r, const float* p, float* o) {
-    for (int i = 0; i < 3; ++i) o[i] = (r[i * 3 + 0] * p[0] + r[i * 3 + 1] * p[1]) + r[i * 3 + 2] * p[2];
-}
-
-// crop_pixel, ray_through and rotate3 on the same fp32 inputs with every product and sum in fp64, in the same order
-// (triangulate.hip, whose reference is an fp64 restatement of the fp32 records; __host__ too: its test runs them on the CPU)
-__host__ __device__ inline void crop_pixel_f64(const float* c01j, float lrc, float half_off, double& u, double& v) {
-    u = (double)c01j[0] * (double)lrc; v = (double)c01j[1] * (double)lrc;
-    u = u + (double)half_off; v = v + (double)half_off;
-}
-
-__host__ __device__ inline void ray_through_f64(const float* k, double u, double v, double* cam) {
-    for (int i = 0; i < 3; ++i) cam[i] = ((double)k[i * 3 + 0] * u + (double)k[i * 3 + 1] * v) + (double)k[i * 3 + 2] * 1.0;
-}
-
-__host__ __device__ inline void rotate3_f64(const float* r, const double* p, double* o) {
-    for (int i = 0; i < 3; ++i) o[i] = ((double)r[i * 3 + 0] * p[0] + (double)r[i * 3 + 1] * p[1]) + (double)r[i * 3 + 2] * p[2];
 }
 
 }  // namespace metro

@@ -12,7 +12,9 @@
 // the root-relative difference the poses are, and it stays in MeTRo's metric scale whatever scale recovery placed the poses.
 // One thread per (box, output joint); fp64 products of the fp32 inputs, one rounding to fp32 per output.
 #include "metro_common.h"
-#include "backproject.h"
+#include "camera_math.h"
+
+#pragma clang fp contract(off)
 
 namespace metro {
 
@@ -25,7 +27,7 @@ struct CovArgs {
     float* peak_out;                  // [n][n_out]
     int n, n_views, nj, n_out, coords;
     double sxy, sz;
-    int perm[HEAD_MAX];
+    int perm[METRO_MAX_JOINTS];
 };
 
 __global__ __launch_bounds__(64) void place_covariances_kernel(CovArgs a) {
@@ -37,12 +39,12 @@ __global__ __launch_bounds__(64) void place_covariances_kernel(CovArgs a) {
     for (int v = 0; v < a.n_views; ++v) {
         const size_t row = (size_t)box * a.n_views + v;
         const float* rot = nullptr;
-        bool mirrored = false;
+        bool flipped = false;
         if (a.coords != METRO_COORDS_CROP) {
             rot = a.coords == METRO_COORDS_CAMERA ? a.rec[row].rot_to_orig_cam : a.rec[row].rot_to_world;
-            mirrored = !(det3_f64(rot) > 0.0);
+            flipped = mirrored(rot);
         }
-        const int j = a.perm[mirrored ? a.mirror[r] : r];
+        const int j = a.perm[flipped ? a.mirror[r] : r];
         const float* c6 = a.cov01 + (row * a.nj + j) * 6;
         double c[3][3];
         c[0][0] = c6[0]; c[1][1] = c6[1]; c[2][2] = c6[2];
@@ -50,7 +52,7 @@ __global__ __launch_bounds__(64) void place_covariances_kernel(CovArgs a) {
         for (int i = 0; i < 3; ++i)
             for (int k = 0; k < 3; ++k) c[i][k] *= s[i] * s[k];
         if (rot != nullptr) {
-            double t[3][3];                                    // R C, then (R C) R^T
+            double t[3][3];            // R C, then (R C) R^T; written out: column by column through rotate3_f64 hipcc emits another kernel
             for (int i = 0; i < 3; ++i)
                 for (int k = 0; k < 3; ++k)
                     t[i][k] = ((double)rot[i * 3 + 0] * c[0][k] + (double)rot[i * 3 + 1] * c[1][k]) + (double)rot[i * 3 + 2] * c[2][k];
@@ -74,10 +76,9 @@ int launch_place_covariances(const float* cov01, const float* peak, const MetroP
     CovArgs a;
     a.cov01 = cov01; a.peak = peak; a.rec = rec; a.mirror = mirror; a.cov_out = cov_out; a.peak_out = peak_out;
     a.n = n; a.n_views = n_views; a.nj = spec.n_joints_head; a.n_out = spec.n_joints_out; a.coords = coords;
-    const SoftArgmaxArgs sa = make_softargmax_args(spec, n);
-    a.sxy = (double)sa.lrc * (double)spec.box_size_mm / (double)spec.proc_side;
+    a.sxy = (double)head_pixel_scale(spec).lrc * (double)spec.box_size_mm / (double)spec.proc_side;
     a.sz = (double)spec.box_size_mm;
-    for (int i = 0; i < HEAD_MAX; ++i) a.perm[i] = i < spec.n_joints_out ? spec.permutation[i] : 0;
+    head_permutation(spec, a.perm);
     const int total = n * spec.n_joints_out;
     hipLaunchKernelGGL(place_covariances_kernel, dim3((total + 63) / 64), dim3(64), 0, stream, a);
     return launch_status("place_covariances");

@@ -6,8 +6,8 @@
 //     (tfu3d.py:23-25) and export permutation (main.py:119-127).
 //   * to_orig_cam_kernel: rotation to the original camera with joints mirrored when det(R) <= 0
 //     (volumetric.py:277-281).
-// The ray, delta_z and z-offset pieces (MINPACK lmder restated for one unknown) live in backproject.h, shared with
-// place_poses.hip.  No FMA contraction anywhere in this file.
+// The ray, delta_z and z-offset pieces (MINPACK lmder restated for one unknown) come from backproject.h, the determinant and
+// the rotation from camera_math.h.  No FMA contraction anywhere in this file.
 // One thread per pose (E, J <= 64): the work is a few hundred flops per pose, the point is parity, not speed.
 #include "metro_common.h"
 #include "gfx950_prims.h"
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(64) void to_orig_cam_kernel(const float* __restrict
     const int j = threadIdx.x;
     if (img >= n || j >= nj) return;
     const float* r = rot + (size_t)img * 9;
-    const int src = det3_f64(r) > 0.0 ? j : mirror[j];
+    const int src = mirrored(r) ? mirror[j] : j;
     rotate3(r, x + ((size_t)img * nj + src) * 3, out + ((size_t)img * nj + j) * 3);
 }
 
@@ -70,13 +70,13 @@ int launch_backproject(const float* coords01, const float* inv_k, const double* 
     a.coords01 = coords01; a.inv_k = inv_k; a.targets = targets; a.root_z = root_z; a.edges = edges;
     a.out = out; a.z_out = z_out;
     a.n = n; a.nj = nj; a.ne = ne; a.per_pose_targets = per_pose_targets; a.mode = root_z != nullptr ? 1 : 0;
-    const int last = spec.proc_side - 1;
-    a.lrc = (float)(last - (last % spec.stride) - 1);
-    a.half_off = spec.centered_stride ? (float)(spec.stride / 2) : 0.0f;
+    const HeadPixelScale px = head_pixel_scale(spec);
+    a.lrc = (float)px.lrc; a.half_off = (float)px.half_off;
     a.box = spec.box_size_mm;
     a.root_relative = root_relative;
     a.n_out = permute ? spec.n_joints_out : nj;
-    for (int i = 0; i < HEAD_MAX; ++i) a.perm[i] = permute ? (i < spec.n_joints_out ? spec.permutation[i] : 0) : i;
+    if (permute) head_permutation(spec, a.perm);
+    else for (int i = 0; i < HEAD_MAX; ++i) a.perm[i] = i;          // head order out
     hipLaunchKernelGGL(backproject_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, a);
     return launch_status("backproject");
 }
@@ -93,11 +93,10 @@ __global__ __launch_bounds__(256) void heatmap_to_25d_kernel(const float* __rest
 }
 
 int launch_heatmap_to_25d(const float* coords01, float* out, int n, const MetroSpec& spec, hipStream_t stream) {
-    const int last = spec.proc_side - 1;
+    const HeadPixelScale px = head_pixel_scale(spec);
     const int total = n * spec.n_joints_head;
     hipLaunchKernelGGL(heatmap_to_25d_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, coords01, out, total,
-                       (float)(last - (last % spec.stride) - 1), spec.centered_stride ? (float)(spec.stride / 2) : 0.0f,
-                       spec.box_size_mm);
+                       (float)px.lrc, (float)px.half_off, spec.box_size_mm);
     return launch_status("heatmap_to_25d");
 }
 

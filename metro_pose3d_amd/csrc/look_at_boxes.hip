@@ -7,63 +7,21 @@
 //   without        preprocess.box_homography's axis-aligned square crop (a few fp64 operations and a cast: the host's bits).
 // One thread per box, every matrix in scalar registers: all array indices are compile-time constants after unrolling, so no
 // private array goes to scratch (cdna_hip_programming.md item 20; the code object's .private_segment_fixed_size is 0).
-// The 3x3 inverses are views.hip's closed forms (adjugate / determinant), not LAPACK's pivoted solves: the records agree with
-// the host's to a few fp32 ulp, not bit for bit (tests/test_gpu_device_geometry.py measures it).  The matrix products take the
-// order NumPy's BLAS (OpenBLAS' gemm kernels) takes on the host, a fused multiply-add chain a0 b0 -> +a1 b1 -> +a2 b2, except
-// the one-row fp32 product of the box centre (a gemv: every product rounded): camera_to_world adds the camera centre t (mm)
-// to a ray of depth 1 in fp32 and world_to_camera takes it off again, so one ulp of a world point is a visible share of the
-// ray, and the zoom inherits it.
+// The 3x3 inverses are closed forms (inv3, camera_math.h), not LAPACK's pivoted solves: the records agree with the host's to a
+// few fp32 ulp, not bit for bit (tests/test_gpu_device_geometry.py measures it).  The matrix products take the order NumPy's
+// BLAS (OpenBLAS' gemm kernels) takes on the host, a fused multiply-add chain a0 b0 -> +a1 b1 -> +a2 b2 (dot3_gemm, mm3_gemm),
+// except the homography behind the LAPACK solve, which has no gemm order to follow (mm3_rounded), and the one-row fp32 product
+// of the box centre (a gemv: every product rounded): camera_to_world adds the camera centre t (mm) to a ray of depth 1 in fp32
+// and world_to_camera takes it off again, so one ulp of a world point is a visible share of the ray, and the zoom inherits it.
 // No FMA contraction in this file: every fused multiply-add is written out.
 #include "metro_common.h"
+#include "camera_math.h"
 
 #pragma clang fp contract(off)
 
 namespace metro {
 
 namespace {
-
-// a0 b0 + a1 b1 + a2 b2 as the host's gemm kernels add it: fma(a2, b2, fma(a1, b1, a0 b0))
-__host__ __device__ inline float dot3(float a0, float a1, float a2, float b0, float b1, float b2) {
-    return fmaf(a2, b2, fmaf(a1, b1, a0 * b0));
-}
-__host__ __device__ inline double dot3(double a0, double a1, double a2, double b0, double b1, double b2) {
-    return fma(a2, b2, fma(a1, b1, a0 * b0));
-}
-
-// o = a b, row-major 3x3, in the element type T, each entry a gemm dot3
-template <typename T>
-__host__ __device__ inline void mm3(const T* a, const T* b, T* o) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) o[i * 3 + j] = dot3(a[i * 3 + 0], a[i * 3 + 1], a[i * 3 + 2], b[j], b[3 + j], b[6 + j]);
-}
-
-// o = a b with every product rounded, ((a_i0 b_0j + a_i1 b_1j) + a_i2 b_2j): the host's LAPACK solve has no gemm order to
-// follow, so the homography takes views.hip's form
-__host__ __device__ inline void mm3_plain(const double* a, const double* b, double* o) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) o[i * 3 + j] = (a[i * 3 + 0] * b[0 * 3 + j] + a[i * 3 + 1] * b[1 * 3 + j]) + a[i * 3 + 2] * b[2 * 3 + j];
-}
-
-// inverse of a row-major 3x3 in closed form, as views.hip's inv3
-__host__ __device__ inline void inv3d(const double* a, double* o) {
-    const double c00 = a[4] * a[8] - a[5] * a[7];
-    const double c01 = a[5] * a[6] - a[3] * a[8];
-    const double c02 = a[3] * a[7] - a[4] * a[6];
-    const double det = (a[0] * c00 + a[1] * c01) + a[2] * c02;
-    o[0] = c00 / det;
-    o[1] = (a[2] * a[7] - a[1] * a[8]) / det;
-    o[2] = (a[1] * a[5] - a[2] * a[4]) / det;
-    o[3] = c01 / det;
-    o[4] = (a[0] * a[8] - a[2] * a[6]) / det;
-    o[5] = (a[2] * a[3] - a[0] * a[5]) / det;
-    o[6] = c02 / det;
-    o[7] = (a[1] * a[6] - a[0] * a[7]) / det;
-    o[8] = (a[0] * a[4] - a[1] * a[3]) / det;
-}
 
 struct Vec3f { float x, y, z; };
 
@@ -93,8 +51,8 @@ __host__ __device__ inline Vec3f image_to_world(const MetroFrameCamera& c, doubl
     const float p0 = (float)x, p1 = (float)y, p2 = 1.f;
     const float* a = c.r_inv;
     if (gemm)
-        return {dot3(p0, p1, p2, a[0], a[1], a[2]) + c.t[0], dot3(p0, p1, p2, a[3], a[4], a[5]) + c.t[1],
-                dot3(p0, p1, p2, a[6], a[7], a[8]) + c.t[2]};
+        return {dot3_gemm(p0, p1, p2, a[0], a[1], a[2]) + c.t[0], dot3_gemm(p0, p1, p2, a[3], a[4], a[5]) + c.t[1],
+                dot3_gemm(p0, p1, p2, a[6], a[7], a[8]) + c.t[2]};
     return {((p0 * a[0] + p1 * a[1]) + p2 * a[2]) + c.t[0],
             ((p0 * a[3] + p1 * a[4]) + p2 * a[5]) + c.t[1],
             ((p0 * a[6] + p1 * a[7]) + p2 * a[8]) + c.t[2]};
@@ -146,7 +104,7 @@ __host__ __device__ inline void camera_record(const double* box, const MetroFram
     const double z0 = zf0, z1 = zf1, z2 = zf2;
     const double u0 = c.world_up[0], u1 = c.world_up[1], u2 = c.world_up[2];
     double x0 = z1 * u2 - z2 * u1, x1 = z2 * u0 - z0 * u2, x2 = z0 * u1 - z1 * u0;
-    const double nx = sqrt(dot3(x0, x1, x2, x0, x1, x2));
+    const double nx = sqrt(dot3_gemm(x0, x1, x2, x0, x1, x2));
     x0 = x0 / nx; x1 = x1 / nx; x2 = x2 / nx;
     const double y0 = z1 * x2 - z2 * x1, y1 = z2 * x0 - z0 * x2, y2 = z0 * x1 - z1 * x0;
     const float r[9] = {(float)x0, (float)x1, (float)x2, (float)y0, (float)y1, (float)y2, zf0, zf1, zf2};
@@ -161,9 +119,9 @@ __host__ __device__ inline void camera_record(const double* box, const MetroFram
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         const float d0 = ws[s].x - c.t[0], d1 = ws[s].y - c.t[1], d2 = ws[s].z - c.t[2];
-        const float q0 = dot3(d0, d1, d2, r[0], r[1], r[2]);
-        const float q1 = dot3(d0, d1, d2, r[3], r[4], r[5]);
-        const float q2 = dot3(d0, d1, d2, r[6], r[7], r[8]);
+        const float q0 = dot3_gemm(d0, d1, d2, r[0], r[1], r[2]);
+        const float q1 = dot3_gemm(d0, d1, d2, r[3], r[4], r[5]);
+        const float q2 = dot3_gemm(d0, d1, d2, r[6], r[7], r[8]);
         const double p0 = q0 / q2, p1 = q1 / q2;
         img[s] = tall ? fma(p1, k[4], p0 * k[3]) + k[5] : fma(p1, k[1], p0 * k[0]) + k[2];
     }
@@ -176,20 +134,20 @@ __host__ __device__ inline void camera_record(const double* box, const MetroFram
     double rd[9], inv_k[9];
 #pragma unroll
     for (int e = 0; e < 9; ++e) rd[e] = r[e];
-    inv3d(k, inv_k);
+    inv3(k, inv_k);
     float back[9];                                                      // orig.R @ virt.R.T in fp32
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j)
-            back[i * 3 + j] = dot3(c.r[i * 3 + 0], c.r[i * 3 + 1], c.r[i * 3 + 2], r[j * 3 + 0], r[j * 3 + 1], r[j * 3 + 2]);
+            back[i * 3 + j] = dot3_gemm(c.r[i * 3 + 0], c.r[i * 3 + 1], c.r[i * 3 + 2], r[j * 3 + 0], r[j * 3 + 1], r[j * 3 + 2]);
     o.has_camera = 1;
     if (!c.has_distortion) {
         // reproject_image_fast: solve(new.T, old.T).T = old_matrix inv(K R), K R in fp64, cast to fp32
         double nm[9], inv_nm[9], h[9];
-        mm3(k, rd, nm);
-        inv3d(nm, inv_nm);
-        mm3_plain(c.old_matrix, inv_nm, h);
+        mm3_gemm(k, rd, nm);
+        inv3(nm, inv_nm);
+        mm3_rounded(c.old_matrix, inv_nm, h);
         o.mode = METRO_WARP_HOMOGRAPHY;
 #pragma unroll
         for (int e = 0; e < 9; ++e) { o.homography[e] = (float)h[e]; o.partial[e] = 0.0; }
@@ -202,13 +160,13 @@ __host__ __device__ inline void camera_record(const double* box, const MetroFram
         // the second fp64
         double inv_r[9], pm[9], qd[9];
         float inv_rf[9], qf[9];
-        inv3d(rd, inv_r);
+        inv3(rd, inv_r);
 #pragma unroll
         for (int e = 0; e < 9; ++e) inv_rf[e] = (float)inv_r[e];
-        mm3(c.r, inv_rf, qf);
+        mm3_gemm(c.r, inv_rf, qf);
 #pragma unroll
         for (int e = 0; e < 9; ++e) qd[e] = qf[e];
-        mm3(qd, inv_k, pm);
+        mm3_gemm(qd, inv_k, pm);
         o.mode = METRO_WARP_DISTORTED;
 #pragma unroll
         for (int e = 0; e < 9; ++e) { o.partial[e] = pm[e]; o.homography[e] = 0.f; }

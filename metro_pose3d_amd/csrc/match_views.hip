@@ -28,7 +28,6 @@
 // centre fixes no depth, as frames.person_groups); the others own the crop rows i * n_views + v of their boxes in ascending
 // box order.  starts has n + 1 entries (persons >= n_persons: empty), rows n * n_views, those past starts[n] are -1.
 #include "metro_common.h"
-#include "backproject.h"
 #include "tri_ray.h"
 
 #pragma clang fp contract(off)
@@ -49,12 +48,8 @@ struct MatchArgs {
     int m, n, n_views, nj, n_out, weights, min_pairs;
     double min_sin2, clip;
     float lrc, half_off;
-    int perm[HEAD_MAX];
+    int perm[METRO_MAX_JOINTS];
 };
-
-__host__ __device__ inline double match_dot3(const double* x, const double* y) {
-    return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2];
-}
 
 // one unordered pair of boxes ia < ib: what a thread of the kernel runs, and what tests/test_match_views.py runs on the host
 __host__ __device__ inline void view_affinity_pair(const MatchArgs& a, int ia, int ib) {
@@ -68,17 +63,17 @@ __host__ __device__ inline void view_affinity_pair(const MatchArgs& a, int ia, i
         for (int v = 0; v < a.n_views; ++v) {
             for (int r = 0; r < a.n_out; ++r) {
                 if (!tri_ray(a, ia * a.n_views + v, r, ra) || !tri_ray(a, ib * a.n_views + v, r, rb)) continue;
-                const double c = match_dot3(ra.d, rb.d);
+                const double c = dot3_rounded(ra.d, rb.d);
                 const double sin2 = 1.0 - c * c;
                 if (!(sin2 >= a.min_sin2)) continue;
                 const double w0[3] = {ra.o[0] - rb.o[0], ra.o[1] - rb.o[1], ra.o[2] - rb.o[2]};
-                const double da = match_dot3(ra.d, w0), db = match_dot3(rb.d, w0);
+                const double da = dot3_rounded(ra.d, w0), db = dot3_rounded(rb.d, w0);
                 const double ta = (c * db - da) / sin2, tb = (db - c * da) / sin2;
                 double dist = a.clip;
                 if (ta > 0.0 && tb > 0.0) {
                     const double p[3] = {(w0[0] + ta * ra.d[0]) - tb * rb.d[0], (w0[1] + ta * ra.d[1]) - tb * rb.d[1],
                                          (w0[2] + ta * ra.d[2]) - tb * rb.d[2]};
-                    dist = sqrt(match_dot3(p, p));
+                    dist = sqrt(dot3_rounded(p, p));
                     if (!(dist <= a.clip)) dist = a.clip;
                 }
                 double w = 1.0;

@@ -397,6 +397,18 @@ struct SoftArgmaxArgs {
     int proc_side;
     int perm[METRO_MAX_JOINTS];
 };
+// What the spec fixes of a decode launch's arguments (host side).  The pixel scale of heatmap_to_image (reference
+// volumetric.py:288-295), as integers; a kernel that takes them as fp32 casts them.
+struct HeadPixelScale { int lrc, half_off; };
+inline HeadPixelScale head_pixel_scale(const MetroSpec& spec) {
+    const int last = spec.proc_side - 1;
+    return {last - (last % spec.stride) - 1,                    // last_receptive_center (:290-291)
+            spec.centered_stride ? spec.stride / 2 : 0};        // :293-294
+}
+// head joint of every exported joint (main.py:119-127), 0 behind n_joints_out
+inline void head_permutation(const MetroSpec& spec, int (&perm)[METRO_MAX_JOINTS]) {
+    for (int i = 0; i < METRO_MAX_JOINTS; ++i) perm[i] = i < spec.n_joints_out ? spec.permutation[i] : 0;
+}
 // Heat-map moments (metro_forward_moments and the kernel-level *_moments entries): `scratch` non-NULL selects the MOMENTS
 // instantiations, which write one record of six second central moments per (image, slab, joint) there (moments_scratch_bytes;
 // in the accumulator type of the launch) and fold them into cov01 fp32 [n][J_head][6] (xx, yy, zz, xy, xz, yz) and peak [n][J_head].

@@ -3,7 +3,7 @@
 // (src/data/data_loading.py:110-112 -> src/model/volumetric.py:171-216):
 //   * 3D, scale recovery `bone-lengths` / `true-root-depth`: heatmap_to_image (volumetric.py:288-295), rays through the
 //     virtual K^-1 (:221-222), delta_z, the per-pose z offset (bone_length_based_backproj.py:38-62, or the given root depth,
-//     :192-199) and back_project (:284-285) -- the arithmetic of heads.hip's backproject_kernel, from the same backproject.h;
+//     :192-199) and back_project (:284-285) -- backproject_kernel's arithmetic (heads.hip), from the same backproject.h;
 //     then the export permutation (main.py:119-127) and, for `camera` / `world`, to_orig_cam (:277-281: R x, joints mirrored
 //     when det R <= 0) plus cam_loc for `world` (:206-208).
 //   * 3D, `metro`: the engine's root-relative poses, rotated as metro_to_orig_cam does (no translation: they carry none).
@@ -47,23 +47,10 @@ struct PlaceArgs {
     int perm[HEAD_MAX];
 };
 
-// project_points (cameralib.py:375-397) in its statement order, fp32; K[:2,:2] . p + K[:2,2]
+// project_points (cameralib.py:375-397), fp32; K[:2,:2] . p + K[:2,2]
 __device__ inline void project_distorted(const MetroPlacement& r, const float* ray, float& x, float& y) {
-    const float* d = r.distortion;              // k1 k2 p1 p2 k3
     float px = ray[0] / ray[2], py = ray[1] / ray[2];
-    const float r2 = px * px + py * py;
-    const float r4 = r2 * r2;
-    float dist = d[0] * r2;
-    dist += d[1] * r4;
-    const float r6 = r4 * r2;
-    dist += d[4] * r6;
-    dist += 1.f;
-    dist += px * (2.f * d[3]);
-    dist += py * (2.f * d[2]);
-    px = px * dist;
-    px = px + r2 * d[3];
-    py = py * dist;
-    py = py + r2 * d[2];
+    distort_normalized(r.distortion, px, py);
     const float* K = r.intrinsics;              // K00 K01 K02 K10 K11 K12
     x = (K[0] * px + K[1] * py) + K[2];
     y = (K[3] * px + K[4] * py) + K[5];
@@ -76,14 +63,14 @@ __global__ __launch_bounds__(64) void place_poses_kernel(PlaceArgs a) {
     const float* c01 = a.coords01 + (size_t)img * a.nj * 3;
     float* o = a.out + (size_t)img * a.n_out * 3;
     const float* rot = a.coords == METRO_COORDS_CAMERA ? rec.rot_to_orig_cam : rec.rot_to_world;
-    const bool mirrored = a.coords != METRO_COORDS_CROP && !(det3_f64(rot) > 0.0);
+    const bool flipped = a.coords != METRO_COORDS_CROP && mirrored(rot);
     if (a.scale == METRO_SCALE_METRO) {
         const float* p = a.poses + (size_t)img * a.n_out * 3;
         for (int r = 0; r < a.n_out; ++r) {
             if (a.coords == METRO_COORDS_CROP) {
                 for (int t = 0; t < 3; ++t) o[r * 3 + t] = p[r * 3 + t];
             } else {
-                rotate3(rot, p + (mirrored ? a.mirror[r] : r) * 3, o + r * 3);
+                rotate3(rot, p + (flipped ? a.mirror[r] : r) * 3, o + r * 3);
             }
         }
     } else {
@@ -95,7 +82,7 @@ __global__ __launch_bounds__(64) void place_poses_kernel(PlaceArgs a) {
         if (a.z_out) a.z_out[img] = z_off;
         // back_project (volumetric.py:284-285) in output order; to_orig_cam reads the mirror joint's crop-frame position
         for (int r = 0; r < a.n_out; ++r) {
-            const int j = a.perm[mirrored ? a.mirror[r] : r];
+            const int j = a.perm[flipped ? a.mirror[r] : r];
             const float s = dz[j] + z_off;
             float x[3];
             for (int t = 0; t < 3; ++t) x[t] = cam[j][t] * s;
@@ -144,11 +131,10 @@ int launch_place_poses(const float* coords01, const float* poses, const MetroPla
     a.mirror = mirror; a.out = out; a.keypoints = keypoints; a.z_out = z_out;
     a.n = n; a.nj = spec.n_joints_head; a.ne = ne; a.n_out = spec.n_joints_out; a.per_pose_targets = per_pose_targets;
     a.scale = scale; a.coords = coords;
-    const int last = spec.proc_side - 1;
-    a.lrc = (float)(last - (last % spec.stride) - 1);
-    a.half_off = spec.centered_stride ? (float)(spec.stride / 2) : 0.0f;
+    const HeadPixelScale px = head_pixel_scale(spec);
+    a.lrc = (float)px.lrc; a.half_off = (float)px.half_off;
     a.box = spec.box_size_mm;
-    for (int i = 0; i < HEAD_MAX; ++i) a.perm[i] = i < spec.n_joints_out ? spec.permutation[i] : 0;
+    head_permutation(spec, a.perm);
     hipLaunchKernelGGL(place_poses_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, a);
     return launch_status("place_poses");
 }

@@ -13,8 +13,7 @@
 // one thread and a running count where the kernel has the ballots.  One thread per (frame, slot), every matrix in scalar
 // registers and every loop over P with constant bounds: nothing is indexed dynamically but global memory (no scratch).
 // World -> camera is Camera.world_to_camera, R (p - t), from the fp32 table entries in fp64; the pixel is project_points' fp32
-// chain in its statement order (place_poses.hip's project_distorted, here over a MetroFrameCamera); the margin and the box
-// are fp64.  No FMA contraction.
+// chain in its statement order; the margin and the box are fp64.  No FMA contraction.
 #include "metro_common.h"
 #include "smooth_step.h"
 
@@ -50,7 +49,9 @@ struct PredictArgs {
 // verdicts of a detection
 constexpr int DET_KEPT = 0, DET_SUPPRESSED = 1, DET_BAD = 2, DET_BAD_FRAME = 3;
 
-// project_points in its statement order, fp32 (place_poses.hip's project_distorted); without coefficients K (x/z, y/z, 1)
+// project_points (cameralib.py:375-397) in its statement order, fp32; without coefficients K (x/z, y/z, 1).  The chain is
+// distort_normalized's (camera_math.h), written out: through the call hipcc emits another instruction stream for
+// predict_boxes_kernel (same values, other schedule and registers), and a site is folded only where the kernel stays identical.
 __host__ __device__ inline void predict_project(const MetroFrameCamera& c, float x, float y, float z, float& u, float& v) {
     float px = x / z, py = y / z;
     if (c.has_distortion) {

@@ -1,12 +1,12 @@
 // The ray of one (crop row, output joint) through the crop's virtual camera, shared by triangulate.hip (the point nearest to
 // a person's rays) and match_views.hip (how close the rays of two boxes pass) so that both build it by the same operations in
 // the same order.  `Args` is the launch's argument struct; tri_ray reads its fields coords01 [m][nj][3], cov01 [m][nj][6]
-// (METRO_TRI_COVARIANCE only), rec [m], mirror [n_out], m, nj, n_out, weights, lrc, half_off and perm[HEAD_MAX], which
+// (METRO_TRI_COVARIANCE only), rec [m], mirror [n_out], m, nj, n_out, weights, lrc, half_off and perm[METRO_MAX_JOINTS], which
 // tri_ray_fields fills from the spec.
 #pragma once
 
 #include "metro_common.h"
-#include "backproject.h"
+#include "camera_math.h"
 
 #pragma clang fp contract(off)
 
@@ -23,8 +23,7 @@ template <class Args>
 __host__ __device__ inline bool tri_ray(const Args& a, int row, int r, TriRay& ray) {
     if ((unsigned)row >= (unsigned)a.m) return false;
     const MetroPlacement& rec = a.rec[row];
-    const bool mirrored = !(det3_f64(rec.rot_to_world) > 0.0);
-    const int ro = mirrored ? a.mirror[r] : r;
+    const int ro = mirrored(rec.rot_to_world) ? a.mirror[r] : r;
     if ((unsigned)ro >= (unsigned)a.n_out) return false;
     const int j = a.perm[ro];
     if ((unsigned)j >= (unsigned)a.nj) return false;
@@ -32,7 +31,7 @@ __host__ __device__ inline bool tri_ray(const Args& a, int row, int r, TriRay& r
     crop_pixel_f64(a.coords01 + ((size_t)row * a.nj + j) * 3, a.lrc, a.half_off, u, v);
     ray_through_f64(rec.inv_intrinsics, u, v, cam);
     rotate3_f64(rec.rot_to_world, cam, ray.d);
-    const double len = sqrt((ray.d[0] * ray.d[0] + ray.d[1] * ray.d[1]) + ray.d[2] * ray.d[2]);
+    const double len = sqrt(dot3_rounded(ray.d, ray.d));
     for (int t = 0; t < 3; ++t) {
         ray.d[t] = ray.d[t] / len;
         ray.o[t] = (double)rec.cam_loc[t];
@@ -49,14 +48,13 @@ __host__ __device__ inline bool tri_ray(const Args& a, int row, int r, TriRay& r
     return tri_finite3(ray.d) && tri_finite3(ray.o);
 }
 
-// the spec's part of the ray arguments (the pixel scale of heatmap_to_image, volumetric.py:288-295, as place_poses.hip)
+// the spec's part of the ray arguments
 template <class Args>
 inline void tri_ray_fields(Args& a, const MetroSpec& spec) {
     a.nj = spec.n_joints_head; a.n_out = spec.n_joints_out;
-    const int last = spec.proc_side - 1;
-    a.lrc = (float)(last - (last % spec.stride) - 1);
-    a.half_off = spec.centered_stride ? (float)(spec.stride / 2) : 0.0f;
-    for (int i = 0; i < HEAD_MAX; ++i) a.perm[i] = i < spec.n_joints_out ? spec.permutation[i] : 0;
+    const HeadPixelScale px = head_pixel_scale(spec);
+    a.lrc = (float)px.lrc; a.half_off = (float)px.half_off;
+    head_permutation(spec, a.perm);
 }
 
 }  // namespace metro

@@ -23,9 +23,8 @@
 // Cov = s^2 A^-1 with s^2 = sum |p|^2 / (2 k - 3), |p| the distances the residual sums and k the rays (two constraints per ray,
 // three unknowns); NaN where the joint is undetermined.  The plain kernel is compiled without the write.
 // One thread per (person, output joint); rays are recomputed in each pass rather than stored (a group has no upper size).
-// fp64 arithmetic on the fp32 inputs, no FMA contraction (backproject.h), one rounding to fp32 per output.
+// fp64 arithmetic on the fp32 inputs, no FMA contraction, one rounding to fp32 per output.
 #include "metro_common.h"
-#include "backproject.h"
 #include "tri_ray.h"
 
 #pragma clang fp contract(off)
@@ -46,7 +45,7 @@ struct TriArgs {
     int m, n_rows, n_persons, nj, n_out, weights;
     double min_det;
     float lrc, half_off;
-    int perm[HEAD_MAX];
+    int perm[METRO_MAX_JOINTS];
 };
 
 struct TriSystem { double a[6], b[3], sw; int cnt; };       // a: xx, yy, zz, xy, xz, yz of sum w (I - d d^T)

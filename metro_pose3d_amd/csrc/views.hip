@@ -3,7 +3,7 @@
 // (to_orig_cam, src/model/volumetric.py:277-281, with rot_to_orig_cam = orig.R virt.R^T, data_loading.py:110).
 //   expand  n per-box records -> n * V MetroCropWarp + MetroPlacement records on the device, one thread per (box, view), in
 //           fp64: the view camera (zoom, roll, flip applied to the look_at_box camera) and frames._frame_params' formulas with
-//           it, 3x3 inverses in closed form (adjugate / determinant).  The identity view copies the box's own records.
+//           it, 3x3 inverses in closed form (inv3, camera_math.h).  The identity view copies the box's own records.
 //   merge   the V placed views of each box -> one pose, keypoints, z offset and a per-joint spread, one thread per
 //           (box, joint), fp64 sums in view order.
 // Both are tiny next to the forward (a few hundred threads of scalar fp64); they exist so that the host packs one record per
@@ -11,41 +11,13 @@
 // No FMA contraction in this file: the expansion is compared with its host restatement (frames.view_params) to the ulp, and
 // n copies of one view must merge to that view's bits.
 #include "metro_common.h"
-#include "backproject.h"
+#include "camera_math.h"
 
 #pragma clang fp contract(off)
 
 namespace metro {
 
 struct ViewTable { MetroView v[METRO_MAX_VIEWS]; };
-
-// o = a b, row-major 3x3, each entry ((a_i0 b_0j + a_i1 b_1j) + a_i2 b_2j)
-__device__ inline void matmul3(const double* a, const double* b, double* o) {
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) o[i * 3 + j] = (a[i * 3 + 0] * b[0 * 3 + j] + a[i * 3 + 1] * b[1 * 3 + j]) + a[i * 3 + 2] * b[2 * 3 + j];
-}
-
-// inverse of a row-major 3x3 in closed form: the adjugate (cofactors transposed) divided by the determinant
-__device__ inline void inv3(const double* a, double* o) {
-    const double c00 = a[4] * a[8] - a[5] * a[7];
-    const double c01 = a[5] * a[6] - a[3] * a[8];
-    const double c02 = a[3] * a[7] - a[4] * a[6];
-    const double det = (a[0] * c00 + a[1] * c01) + a[2] * c02;
-    o[0] = c00 / det;
-    o[1] = (a[2] * a[7] - a[1] * a[8]) / det;
-    o[2] = (a[1] * a[5] - a[2] * a[4]) / det;
-    o[3] = c01 / det;
-    o[4] = (a[0] * a[8] - a[2] * a[6]) / det;
-    o[5] = (a[2] * a[3] - a[0] * a[5]) / det;
-    o[6] = c02 / det;
-    o[7] = (a[1] * a[6] - a[0] * a[7]) / det;
-    o[8] = (a[0] * a[4] - a[1] * a[3]) / det;
-}
-
-__device__ inline void transpose3(const double* a, double* o) {
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) o[i * 3 + j] = a[j * 3 + i];
-}
 
 __global__ __launch_bounds__(64) void expand_views_kernel(const MetroViewBase* __restrict__ bases, int n, ViewTable views,
                                                           int n_views, double half_side, MetroCropWarp* __restrict__ crops,
@@ -89,21 +61,21 @@ __global__ __launch_bounds__(64) void expand_views_kernel(const MetroViewBase* _
     k[0] *= v.zoom; k[1] *= v.zoom; k[3] *= v.zoom; k[4] *= v.zoom;
     const double cr = v.cos_roll, sr = v.sin_roll;
     const double rz_t[9] = {cr, sr, 0.0, -sr, cr, 0.0, 0.0, 0.0, 1.0};
-    matmul3(rz_t, r0, m);
+    mm3_rounded(rz_t, r0, m);
     for (int e = 0; e < 9; ++e) r[e] = (v.flip && e < 3) ? -m[e] : m[e];
     transpose3(r, rt);
     double new_matrix[9], inv_new[9], h[9];
-    matmul3(k, r, new_matrix);
+    mm3_rounded(k, r, new_matrix);
     if (!b.has_camera || b.mode == METRO_WARP_HOMOGRAPHY) {
         // homography = old_matrix inv(K R)  (frames._frame_params; cameras=None: the square crop's matrix times K_base inv(K R))
         inv3(new_matrix, inv_new);
         if (b.has_camera) {
-            matmul3(b.old_matrix, inv_new, h);
+            mm3_rounded(b.old_matrix, inv_new, h);
         } else {
             double g[9], h0[9];
-            matmul3(base_k, inv_new, g);
+            mm3_rounded(base_k, inv_new, g);
             for (int e = 0; e < 9; ++e) h0[e] = (double)b.homography[e];
-            matmul3(h0, g, h);
+            mm3_rounded(h0, g, h);
         }
         for (int e = 0; e < 9; ++e) { c.homography[e] = p.homography[e] = (float)h[e]; c.partial[e] = 0.0; }
     } else {
@@ -111,13 +83,13 @@ __global__ __launch_bounds__(64) void expand_views_kernel(const MetroViewBase* _
         double inv_r[9], inv_k[9], q[9], pm[9];
         inv3(r, inv_r);
         inv3(k, inv_k);
-        matmul3(b.orig_r, inv_r, q);
-        matmul3(q, inv_k, pm);
+        mm3_rounded(b.orig_r, inv_r, q);
+        mm3_rounded(q, inv_k, pm);
         for (int e = 0; e < 9; ++e) { c.partial[e] = pm[e]; c.homography[e] = p.homography[e] = 0.f; }
     }
     // the rotations back (data_loading.py:110-112): orig.R R^T (orig.R = I without a camera), R^T, inv(K) (0 without a camera)
     double back[9], inv_k[9];
-    if (b.has_camera) matmul3(b.orig_r, rt, back);
+    if (b.has_camera) mm3_rounded(b.orig_r, rt, back);
     else for (int e = 0; e < 9; ++e) back[e] = rt[e];
     if (b.has_camera) inv3(k, inv_k);
     for (int e = 0; e < 9; ++e) {
@@ -181,8 +153,8 @@ __global__ __launch_bounds__(256) void merge_views_kernel(MergeArgs a) {
         double sx = 0.0, sy = 0.0;
         int cnt = 0;
         for (int v = 0; v < V; ++v) {
-            const bool mirrored = !(det3_f64(a.rec[row0 + v].rot_to_orig_cam) > 0.0);
-            const float* kp = a.keypoints + ((row0 + v) * a.nj + (mirrored ? a.mirror[j] : j)) * 2;
+            const bool flipped = mirrored(a.rec[row0 + v].rot_to_orig_cam);
+            const float* kp = a.keypoints + ((row0 + v) * a.nj + (flipped ? a.mirror[j] : j)) * 2;
             const float x = kp[0], y = kp[1];
             if (__builtin_isfinite(x) && __builtin_isfinite(y)) {
                 sx += (double)x;

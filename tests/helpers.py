@@ -2,6 +2,8 @@
 from __future__ import annotations
 
 import ctypes as C
+import os
+import subprocess
 
 import numpy as np
 import torch
@@ -12,6 +14,24 @@ from metro_pose3d_amd._lib import check
 
 def ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+CSRC = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), 'csrc')
+
+
+def compile_for_host(tmp, name, sources, body) -> C.CDLL:
+    """The __host__ __device__ code of the csrc files `sources`, compiled for the host: `tmp`/`name`.hip includes them in
+    order, `body` (extern "C" wrappers around their functions) follows, and the shared object is opened.  The launchers in the
+    sources link against the library's helpers, so the library is loaded first."""
+    src = tmp / f'{name}.hip'
+    src.write_text(''.join(f'#include "{os.path.join(CSRC, f)}"\n' for f in sources) + body)
+    from metro_pose3d_amd.build import _hipcc
+    so = tmp / f'{name}.so'
+    pkg = os.path.dirname(_lib.LIB_PATH)
+    subprocess.check_call([_hipcc(), '--offload-arch=gfx950', '-O2', '-std=c++17', '-fPIC', '-shared', '-x', 'hip', str(src),
+                           '-o', str(so), '-L' + pkg, '-l:' + os.path.basename(_lib.LIB_PATH), '-Wl,-rpath,' + pkg])
+    _lib.load()
+    return C.CDLL(str(so))
 
 
 def conv_desc(n, h_in, c_in, h_out, c_out, k, stride=1, dil=1, pad=0, prologue=False, relu=False,

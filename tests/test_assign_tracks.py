@@ -7,7 +7,6 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ import torch
 from metro_pose3d_amd import _lib, frames as FR, heads as MH
 from tests import assign_tracks_ref as AR
 from tests import follow_tracks_ref as FT
+from tests.helpers import compile_for_host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = AR.CASES
@@ -164,9 +164,7 @@ def host_kernel(tmp_path_factory):
     (tests/test_follow_tracks.py's fixture with the optimal block between assoc_costs and assoc_births), the workgroup's LDS on
     the heap; smooth_tracks.hip's per-joint function for the state the smoothing launch leaves on the CSR the walk wrote."""
     tmp = tmp_path_factory.mktemp('host_assign_tracks')
-    src = tmp / 'host_assign_tracks.hip'
-    csrc = os.path.join(ROOT, 'metro_pose3d_amd', 'csrc')
-    src.write_text(f'#include "{os.path.join(csrc, "associate_tracks.hip")}"\n#include "{os.path.join(csrc, "smooth_tracks.hip")}"\n' + '''
+    dll = compile_for_host(tmp, 'host_assign_tracks', ['associate_tracks.hip', 'smooth_tracks.hip'], '''
 #include <memory>
 extern "C" void host_associate_tracks_optimal(const float* poses, const float* cov, const double* times, int n, const int* step_rows,
                                               int n_step_rows, const int* step_starts, int n_steps, int n_out, int measurement,
@@ -229,13 +227,6 @@ extern "C" void host_filter_tracks(const float* poses, const float* cov, const d
     for (int idx = 0; idx < n_tracks * n_out; ++idx) metro::smooth_track_joint(a, idx);
 }
 ''')
-    from metro_pose3d_amd.build import _hipcc
-    so = tmp / 'host_assign_tracks.so'
-    pkg = os.path.dirname(_lib.LIB_PATH)       # the launchers in the sources link against the library's helpers
-    subprocess.check_call([_hipcc(), '--offload-arch=gfx950', '-O2', '-std=c++17', '-fPIC', '-shared', '-x', 'hip', str(src),
-                           '-o', str(so), '-L' + pkg, '-l:' + os.path.basename(_lib.LIB_PATH), '-Wl,-rpath,' + pkg])
-    _lib.load()
-    dll = C.CDLL(str(so))
     fn, flt = dll.host_associate_tracks_optimal, dll.host_filter_tracks
     fn.restype = flt.restype = None
     P = C.c_void_p

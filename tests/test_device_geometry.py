@@ -11,6 +11,7 @@ import pytest
 from metro_pose3d_amd import _lib, frames as FR
 from metro_pose3d_amd.frames import Camera, estimate_pose_in_frames, locate_poses_in_frames, pack_frame_cameras
 from tests.test_frames import FIX, fixture_cameras
+from tests.helpers import compile_for_host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -78,8 +79,7 @@ def test_kernel_arithmetic_on_the_host_matches_pack_view_bases(tmp_path):
     """look_at_boxes.hip's per-box functions are __host__ __device__: compiled for the host from the same source, they are held
     to the bounds the GPU test holds the kernel to (fp32 fields within 4 column-scaled ulp, fp64 fields within 1e-6
     column-scaled, cameras=None bit-identical), on the fixture's cameras and boxes inside, across and outside the frame."""
-    src = tmp_path / 'host_look_at_boxes.hip'
-    src.write_text(f'#include "{os.path.join(ROOT, "metro_pose3d_amd", "csrc", "look_at_boxes.hip")}"\n' + '''
+    lib = compile_for_host(tmp_path, 'host_look_at_boxes', ['look_at_boxes.hip'], '''
 extern "C" void host_look_at_boxes(const double* boxes, const int32_t* fi, int n, const MetroFrameCamera* cams, int n_cameras,
                                    int side, MetroViewBase* out) {
     for (int i = 0; i < n; ++i) {
@@ -90,13 +90,6 @@ extern "C" void host_look_at_boxes(const double* boxes, const int32_t* fi, int n
     }
 }
 ''')
-    from metro_pose3d_amd.build import _hipcc
-    so = tmp_path / 'host_look_at_boxes.so'
-    pkg = os.path.dirname(_lib.LIB_PATH)       # the launcher in the source links against the library's helpers
-    subprocess.check_call([_hipcc(), '--offload-arch=gfx950', '-O2', '-std=c++17', '-fPIC', '-shared', '-x', 'hip', str(src),
-                           '-o', str(so), '-L' + pkg, '-l:' + os.path.basename(_lib.LIB_PATH), '-Wl,-rpath,' + pkg])
-    _lib.load()
-    lib = C.CDLL(str(so))
     d = np.load(FIX)
     boxes = np.concatenate([d['boxes'], [[-4000, 200, 300, 400], [1300, 1300, 150, 200], [-900, -900, 300, 300],
                                          [100, 100, 50, 400], [100, 100, 600, 80]]])

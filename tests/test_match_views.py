@@ -6,7 +6,6 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,6 +14,7 @@ import torch
 from metro_pose3d_amd import ModelSpec, _lib, frames as FR, heads as MH
 from tests import match_views_ref as MR
 from tests import triangulation_ref as TR
+from tests.helpers import compile_for_host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SPEC = ModelSpec(50, 32, 'h36m')
@@ -77,8 +77,7 @@ def host_kernel(tmp_path_factory):
     """match_views.hip's per-pair function and clustering steps are __host__ __device__: the source compiled for the host, one
     call per entry of the n x n index space where the launch has one thread, and the clustering steps run by one thread."""
     tmp = tmp_path_factory.mktemp('host_match_views')
-    src = tmp / 'host_match_views.hip'
-    src.write_text(f'#include "{os.path.join(ROOT, "metro_pose3d_amd", "csrc", "match_views.hip")}"\n' + '''
+    dll = compile_for_host(tmp, 'host_match_views', ['match_views.hip'], '''
 #include <vector>
 extern "C" void host_view_affinity(const float* coords01, const float* cov01, const MetroPlacement* rec, const MetroSpec* spec,
                                    const int* mirror, const int* frame_index, int n, int n_views, int weights, double min_sin2,
@@ -106,13 +105,6 @@ extern "C" void host_cluster_views(const float* cost, int n, int n_views, float 
     cluster_groups(a, label.data(), size.data(), pid.data(), 0, 1);
 }
 ''')
-    from metro_pose3d_amd.build import _hipcc
-    so = tmp / 'host_match_views.so'
-    pkg = os.path.dirname(_lib.LIB_PATH)       # the launchers in the source link against the library's helpers
-    subprocess.check_call([_hipcc(), '--offload-arch=gfx950', '-O2', '-std=c++17', '-fPIC', '-shared', '-x', 'hip', str(src),
-                           '-o', str(so), '-L' + pkg, '-l:' + os.path.basename(_lib.LIB_PATH), '-Wl,-rpath,' + pkg])
-    _lib.load()
-    dll = C.CDLL(str(so))
     aff, clu = dll.host_view_affinity, dll.host_cluster_views
     aff.restype = clu.restype = None
     aff.argtypes = [C.c_void_p] * 3 + [C.POINTER(_lib.MetroSpec), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double,

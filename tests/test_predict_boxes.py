@@ -10,7 +10,6 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -20,6 +19,7 @@ from metro_pose3d_amd import _lib, frames as FR, heads as MH
 from metro_pose3d_amd.camera import Camera
 from tests import predict_boxes_ref as PB
 from tests import track_smoothing_ref as TS
+from tests.helpers import compile_for_host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = PB.CASES
@@ -216,9 +216,7 @@ def host_kernel(tmp_path_factory):
     """predict_boxes.hip's steps are __host__ __device__ functions of one index: the source compiled for the host and run by one
     thread in the kernels' order, a running count where the workgroup has its ballots and per-wave sums."""
     tmp = tmp_path_factory.mktemp('host_predict_boxes')
-    src = tmp / 'host_predict_boxes.hip'
-    csrc = os.path.join(ROOT, 'metro_pose3d_amd', 'csrc')
-    src.write_text(f'#include "{os.path.join(csrc, "predict_boxes.hip")}"\n' + '''
+    fn = compile_for_host(tmp, 'host_predict_boxes', ['predict_boxes.hip'], '''
 extern "C" void host_predict_boxes(const double* state, const int* ids, int n_tracks, int n_out, const MetroFrameCamera* cameras,
                                    int n_cameras, const int* frame_sizes, const double* frame_times, int n_frames, int coords, double q,
                                    double max_age, double expand, double n_sigma, double max_sigma, double near, double min_side,
@@ -243,14 +241,7 @@ extern "C" void host_predict_boxes(const double* state, const int* ids, int n_tr
     counts[0] = at; counts[1] = n_predicted;
     counts[2] = tally[DET_SUPPRESSED]; counts[3] = tally[DET_BAD]; counts[4] = tally[DET_BAD_FRAME];
 }
-''')
-    from metro_pose3d_amd.build import _hipcc
-    so = tmp / 'host_predict_boxes.so'
-    pkg = os.path.dirname(_lib.LIB_PATH)       # the launcher in the source links against the library's helpers
-    subprocess.check_call([_hipcc(), '--offload-arch=gfx950', '-O2', '-std=c++17', '-fPIC', '-shared', '-x', 'hip', str(src),
-                           '-o', str(so), '-L' + pkg, '-l:' + os.path.basename(_lib.LIB_PATH), '-Wl,-rpath,' + pkg])
-    _lib.load()
-    fn = C.CDLL(str(so)).host_predict_boxes
+''').host_predict_boxes
     fn.restype = None
     fn.argtypes = _lib.SIGNATURES['metro_predict_boxes'][1][:-1]
 

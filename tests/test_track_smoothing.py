@@ -6,7 +6,6 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ import torch
 
 from metro_pose3d_amd import _lib, frames as FR, heads as MH
 from tests import track_smoothing_ref as TS
+from tests.helpers import compile_for_host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES, MODES, MEASUREMENTS = TS.CASES, TS.MODES, TS.MEASUREMENTS
@@ -95,8 +95,7 @@ def host_kernel(tmp_path_factory):
     """smooth_tracks.hip's per-joint function is __host__ __device__: the source compiled for the host, one call per (track,
     output joint) where the launch has one thread."""
     tmp = tmp_path_factory.mktemp('host_smooth_tracks')
-    src = tmp / 'host_smooth_tracks.hip'
-    src.write_text(f'#include "{os.path.join(ROOT, "metro_pose3d_amd", "csrc", "smooth_tracks.hip")}"\n' + '''
+    fn = compile_for_host(tmp, 'host_smooth_tracks', ['smooth_tracks.hip'], '''
 extern "C" void host_smooth_tracks(const float* poses, const float* cov, const double* times, int n, const int* rows, int n_rows,
                                    const int* starts, int n_tracks, int n_out, int mode, int measurement, double q, double r_floor,
                                    double cov_scale, double v0, double gate, double* state, double* ws, float* poses_out,
@@ -106,14 +105,7 @@ extern "C" void host_smooth_tracks(const float* poses, const float* cov, const d
                                                         used_out);
     for (int idx = 0; idx < n_tracks * n_out; ++idx) metro::smooth_track_joint(a, idx);
 }
-''')
-    from metro_pose3d_amd.build import _hipcc
-    so = tmp / 'host_smooth_tracks.so'
-    pkg = os.path.dirname(_lib.LIB_PATH)       # the launcher in the source links against the library's helpers
-    subprocess.check_call([_hipcc(), '--offload-arch=gfx950', '-O2', '-std=c++17', '-fPIC', '-shared', '-x', 'hip', str(src),
-                           '-o', str(so), '-L' + pkg, '-l:' + os.path.basename(_lib.LIB_PATH), '-Wl,-rpath,' + pkg])
-    _lib.load()
-    fn = C.CDLL(str(so)).host_smooth_tracks
+''').host_smooth_tracks
     fn.restype = None
     fn.argtypes = ([C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_double] * 5 + [C.c_void_p] * 6)
 

@@ -6,7 +6,6 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ import torch
 
 from metro_pose3d_amd import ModelSpec, _lib, frames as FR, heads as MH
 from tests import triangulation_ref as TR
+from tests.helpers import compile_for_host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SPEC = ModelSpec(50, 32, 'h36m')
@@ -218,8 +218,7 @@ def host_kernel(tmp_path_factory):
     """triangulate.hip's per-joint function is __host__ __device__: the source compiled for the host, one call per (person,
     output joint) where the launch has one thread."""
     tmp = tmp_path_factory.mktemp('host_triangulate')
-    src = tmp / 'host_triangulate.hip'
-    src.write_text(f'#include "{os.path.join(ROOT, "metro_pose3d_amd", "csrc", "triangulate.hip")}"\n' + '''
+    fn = compile_for_host(tmp, 'host_triangulate', ['triangulate.hip'], '''
 extern "C" void host_triangulate_joints(const float* coords01, const float* cov01, const MetroPlacement* rec, int m, const int* rows,
                                         int n_rows, const int* starts, int n_persons, const MetroSpec* spec, const int* mirror,
                                         int weights, double min_det, float* points, int* n_rays, float* residual) {
@@ -227,14 +226,7 @@ extern "C" void host_triangulate_joints(const float* coords01, const float* cov0
                                                   min_det, points, n_rays, residual);
     for (int idx = 0; idx < n_persons * spec->n_joints_out; ++idx) metro::triangulate_joint(a, idx);
 }
-''')
-    from metro_pose3d_amd.build import _hipcc
-    so = tmp / 'host_triangulate.so'
-    pkg = os.path.dirname(_lib.LIB_PATH)       # the launcher in the source links against the library's helpers
-    subprocess.check_call([_hipcc(), '--offload-arch=gfx950', '-O2', '-std=c++17', '-fPIC', '-shared', '-x', 'hip', str(src),
-                           '-o', str(so), '-L' + pkg, '-l:' + os.path.basename(_lib.LIB_PATH), '-Wl,-rpath,' + pkg])
-    _lib.load()
-    fn = C.CDLL(str(so)).host_triangulate_joints
+''').host_triangulate_joints
     fn.restype = None
     fn.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(_lib.MetroSpec), C.c_void_p,
                                       C.c_int, C.c_double] + [C.c_void_p] * 3

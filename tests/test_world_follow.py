@@ -6,7 +6,6 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,6 +16,7 @@ from tests import match_views_ref as MR
 from tests import track_smoothing_ref as TS
 from tests import triangulation_ref as TR
 from tests import world_follow_ref as WR
+from tests.helpers import compile_for_host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SPEC = ModelSpec(50, 32, 'h36m')
@@ -29,10 +29,7 @@ def host(tmp_path_factory):
     """The per-thread code of the three launches is __host__ __device__: the sources compiled for the host, one call where the
     launch has one thread."""
     tmp = tmp_path_factory.mktemp('host_world_follow')
-    src = tmp / 'host_world_follow.hip'
-    csrc = os.path.join(ROOT, 'metro_pose3d_amd', 'csrc')
-    src.write_text(''.join(f'#include "{os.path.join(csrc, f)}"\n' for f in ('triangulate.hip', 'match_views.hip', 'world_tracks.hip'))
-                   + '''
+    dll = compile_for_host(tmp, 'host_world_follow', ['triangulate.hip', 'match_views.hip', 'world_tracks.hip'], '''
 #include <vector>
 extern "C" void host_triangulate_cov(const float* coords01, const float* cov01, const MetroPlacement* rec, int m, const int* rows,
                                      int n_rows, const int* starts, int n_persons, const MetroSpec* spec, const int* mirror,
@@ -66,13 +63,6 @@ extern "C" void host_person_steps(const int* rows, int n_rows, const int* starts
     for (int t = 0; t < metro::PERSON_STEPS_THREADS; ++t) metro::person_steps_starts(a, step.data(), t, metro::PERSON_STEPS_THREADS);
 }
 ''')
-    from metro_pose3d_amd.build import _hipcc
-    so = tmp / 'host_world_follow.so'
-    pkg = os.path.dirname(_lib.LIB_PATH)       # the launchers in the sources link against the library's helpers
-    subprocess.check_call([_hipcc(), '--offload-arch=gfx950', '-O2', '-std=c++17', '-fPIC', '-shared', '-x', 'hip', str(src),
-                           '-o', str(so), '-L' + pkg, '-l:' + os.path.basename(_lib.LIB_PATH), '-Wl,-rpath,' + pkg])
-    _lib.load()
-    dll = C.CDLL(str(so))
     P = C.c_void_p
     tri, aff, stp = dll.host_triangulate_cov, dll.host_affinity_steps, dll.host_person_steps
     tri.restype = aff.restype = stp.restype = None
