@@ -159,7 +159,8 @@ double metro_plan_flops_per_image(const MetroPlan* plan);
 int  metro_plan_layer_kernel(const MetroPlan* plan, int32_t index, int32_t n, char* buf, int32_t buf_len);
 /* Test instrumentation for the single-kernel entry points below (thread-local): mode 0 off (default); 1 every launch on this
  * thread appends its kernel id to the string metro_last_kernel_id() returns; 2 DRY RUN -- entry points record the id and
- * return METRO_OK without launching.  Setting a mode clears the string. */
+ * return METRO_OK without launching.  Setting a mode clears the string, which holds 4 KiB -- every launch of a whole forward;
+ * one that did not fit ends in " ...". */
 int  metro_kernel_notes(int32_t mode);
 const char* metro_last_kernel_id(void);
 /* Binds the uploaded parameter blob (device pointer, metro_plan_param_bytes() long). */
@@ -644,7 +645,13 @@ int64_t metro_moments_scratch_bytes(const MetroSpec* spec, int32_t n);
  * that ALSO writes d_cov01_out fp32 [n, n_joints_head, 6] and d_peak_out fp32 [n, n_joints_head] (head joint order), from the
  * MOMENTS instantiations of the same head / soft-argmax launches: same launch count; poses, coords01 and status words have
  * the bits of those entries on the same input.  d_coords01_out may be NULL; d_cov01_out, d_peak_out and d_moments_scratch go
- * together (all NULL: the plain forward, eagerly).  Always plain launches: the hipGraph cache does not serve this entry. */
+ * together (all NULL: the plain forward, eagerly).  Always plain launches: the hipGraph cache does not serve this entry.
+ * Non-finite values (this entry and the two kernel-level ones below): a crop that reaches the soft-argmax with a NaN or +Inf
+ * logit is answered and flagged exactly as by the plain entries (poses, coords01 and status word keep those bits).  Its
+ * covariance is not a statistic of anything: the six d_cov01_out words and d_peak_out of every joint that has such a logit are
+ * NaN (the joint's normaliser is NaN and every word is divided by it) -- through the head a non-finite input element is a
+ * term of every channel of its pixel, so of every joint of the crop; the crop's other joints, and every other crop of the
+ * call, keep the bits of the call without the non-finite value (tests/test_gpu_heat_moments_closure.py). */
 int  metro_forward_moments(MetroPlan* plan, const void* d_images_nhwc, int32_t images_u8, int32_t n, float* d_poses_out,
                            float* d_coords01_out, float* d_cov01_out, float* d_peak_out, void* d_moments_scratch,
                            void* d_workspace, void* stream);

@@ -1,4 +1,6 @@
 // Executor of libmetro_hip.so: runs the layer list planner.cpp built -- one launch per layer, eagerly or as a captured hipGraph.
+#include <cstring>
+#include <string>
 #include <vector>
 
 #include "plan.h"
@@ -150,14 +152,16 @@ int metro_plan_layer_kernel(const MetroPlan* plan, int32_t index, int32_t n, cha
     METRO_CHECK_ARG(n > 0 && n <= plan->max_batch, "metro_plan_layer_kernel: batch %d outside [1, %d]", n, plan->max_batch);
     // dry run of the layer's dispatch: the leaf launcher records the instantiation it would launch and returns
     KernelNotes& kn = kernel_notes();
-    const KernelNotes saved = kn;
+    const int saved_mode = kn.mode;
+    const std::string saved_ids(kn.ids);              // what the string holds, not its 4 KiB: this entry is called a million times per scan
     kn.mode = 2; kn.ids[0] = 0;
     static const char fake = 0;                       // pointers are never dereferenced in a dry run (launch_status asserts it)
     float dummy_poses = 0.f;
     const int st = launch_layer(plan, &fake, index, reinterpret_cast<const float*>(&fake), n, &dummy_poses,
                                 const_cast<char*>(&fake), nullptr, false);
     snprintf(buf, (size_t)buf_len, "%s", kn.ids);
-    kn = saved;
+    kn.mode = saved_mode;
+    memcpy(kn.ids, saved_ids.c_str(), saved_ids.size() + 1);
     return st;
 }
 

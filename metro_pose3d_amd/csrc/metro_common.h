@@ -50,7 +50,7 @@ inline int tuning_knob(const char* name, int dflt) {
 // launch.  Off (the default) it is one thread-local load; mode 1 appends the id to a thread-local string
 // (metro_last_kernel_id); mode 2 is a DRY RUN: the id is recorded and the launcher returns METRO_OK without touching
 // the device (metro_plan_layer_kernel, and the coverage test in tests/test_kernel_coverage.py, work without a GPU).
-struct KernelNotes { int mode; char ids[1024]; };   // a string that did not fit ends in " ..." (tests assert against it)
+struct KernelNotes { int mode; char ids[4096]; };   // holds the ids of a whole forward; a string that did not fit ends in " ..." (tests assert against it)
 KernelNotes& kernel_notes();
 bool note_kernel(const char* fmt, ...) __attribute__((format(printf, 1, 2)));   // true = dry run: skip the launch
 
