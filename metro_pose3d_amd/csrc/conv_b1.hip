@@ -320,9 +320,12 @@ static thread_local int g_b1_force_classic = 0;
 void conv_b1_set_form(int classic) { g_b1_force_classic = classic; }
 bool classic_forms_forced() { return g_b1_force_classic != 0; }
 
-bool conv_b1_chain_preferred() {
+// the launches whose sum stays on chip (or is rebuilt), unless the classic form is asked for; the layer's shape is
+// conv_form_supported's, checked by the caller
+bool conv_b1_chain_supported(const MetroConvDesc& d, const ConvFused& f) {
     static const int enabled = tuning_knob("METRO_B1_SPLIT", 1);
-    return enabled != 0 && g_b1_force_classic == 0;
+    return (f.form == ConvForm::NextRebuild || (f.form == ConvForm::NextProj && f.rb.out_mode == 1)) && !f.rb.classic &&
+           enabled != 0 && g_b1_force_classic == 0 && b1_map_ok(d);
 }
 
 template <bool REB, int OUTM>
@@ -341,8 +344,8 @@ static int launch_b1(B1Args a, hipStream_t stream) {
     return launch_status("conv_b1_chain");
 }
 
-// d: the conv3 layer (1x1, 64 -> 256, no prologue, no residual tensor) of a NextProj / NextRebuild launch that conv_pw64 hands over
-// (whole 64-pixel tiles, map width a power of two >= 16); f.rb.out_mode 1 (NextProj) / 2 (NextRebuild) or 0
+// d: the conv3 layer (1x1, 64 -> 256, no prologue, no residual tensor) of a NextProj / NextRebuild launch that passes
+// conv_b1_chain_supported (whole 64-pixel tiles, map width a power of two >= 16); f.rb.out_mode 1 (NextProj) / 2 (NextRebuild) or 0
 int launch_conv_b1_chain(const MetroConvDesc& d, const void* in, const void* w, const float* bias, void* out, hipStream_t stream,
                          const ConvFused& f) {
     const ConvFuse2& f2 = f.next;

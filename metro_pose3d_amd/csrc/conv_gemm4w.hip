@@ -444,19 +444,25 @@ static int launch_g4_part(const ConvArgs& a, const half_t* in, const half_t* w, 
     return launch_status("conv_gemm4w");
 }
 
-int launch_conv_gemm4w(const MetroConvDesc& d, const void* in_, const void* w_, const float* bias, const void* ps_,
-                       const void* pb_, const void* res, void* out_, hipStream_t stream, const ConvSplit* split) {
+int launch_conv_gemm4w(const MetroConvDesc& d, const ConvOperands& o, hipStream_t stream, const ConvSplit* split) {
     if (!conv_gemm4w_shape_ok(d, split)) {
         set_error("conv_gemm4w: needs a 1x1 stride-1 fp16 layer with c_in %% 128 == 0 (<= 2048), c_out %% 256 == 0 and pixels %% 256 == 0 "
                   "(got c_in %d, c_out %d, %d x %d x %d pixels)", d.c_in, d.c_out, d.n, d.h_out, d.w_out);
         return METRO_ERR_UNSUPPORTED;
     }
     ConvArgs a = make_conv_args(d);
-    void* out2_ = nullptr;
+    half_t* out2 = nullptr;
     if (split != nullptr && split->split > 0) {
         a.split = split->split; a.c_out2 = split->c_out2; a.relu2 = split->relu2;
-        out2_ = split->out2;
+        out2 = static_cast<half_t*>(split->out2);
     }
+    const half_t* in = static_cast<const half_t*>(o.in);
+    const half_t* w = static_cast<const half_t*>(o.w);
+    const float* bias = o.bias;
+    const half_t* ps = static_cast<const half_t*>(o.pro_scale);
+    const half_t* pb = static_cast<const half_t*>(o.pro_shift);
+    const half_t* r = d.has_residual ? static_cast<const half_t*>(o.residual) : nullptr;
+    half_t* out = static_cast<half_t*>(o.out);
     const int tiles_m = d.c_out / g4::TM;
     const int tiles_n = a.m_total / g4::TN;
     // which part runs on which tile: everything on whole tiles; a lone layer with too few of them on half tiles; a pair whose
@@ -470,11 +476,8 @@ int launch_conv_gemm4w(const MetroConvDesc& d, const void* in_, const void* w_, 
         tm_whole = 0; tm_half = tiles_m;
     } else if ((long)tiles_m * tiles_n < 256 && g4_quarter_tiles_pay(tiles_m, a.m_total, d.c_in)) {
         if (note_kernel("conv_gemm4w<256x64%s>%s", d.has_prologue ? ",pro" : "", d.has_residual ? "+res" : "")) return METRO_OK;
-        const half_t* rq = d.has_residual ? static_cast<const half_t*>(res) : nullptr;
-        return d.has_prologue ? launch_g4_part<true, 1>(a, static_cast<const half_t*>(in_), static_cast<const half_t*>(w_), bias, static_cast<const half_t*>(ps_),
-                                                        static_cast<const half_t*>(pb_), rq, static_cast<half_t*>(out_), nullptr, 0, tiles_m, 1, stream)
-                              : launch_g4_part<false, 1>(a, static_cast<const half_t*>(in_), static_cast<const half_t*>(w_), bias, nullptr, nullptr, rq,
-                                                         static_cast<half_t*>(out_), nullptr, 0, tiles_m, 1, stream);
+        return d.has_prologue ? launch_g4_part<true, 1>(a, in, w, bias, ps, pb, r, out, nullptr, 0, tiles_m, 1, stream)
+                              : launch_g4_part<false, 1>(a, in, w, bias, nullptr, nullptr, r, out, nullptr, 0, tiles_m, 1, stream);
     }
     const char* pro_s = d.has_prologue ? ",pro" : "";
     const char* res_s = d.has_residual ? "+res" : "";
@@ -490,13 +493,6 @@ int launch_conv_gemm4w(const MetroConvDesc& d, const void* in_, const void* w_, 
     if (tm_half == 0 && mg_knob > 1 && (long)d.c_out * d.c_in * 2 > mg_min_w && 8 % mg_knob == 0 && tiles_m % mg_knob == 0 &&
         tiles_n % (8 / mg_knob) == 0)
         mgroups = mg_knob;
-    const half_t* in = static_cast<const half_t*>(in_);
-    const half_t* w = static_cast<const half_t*>(w_);
-    const half_t* ps = static_cast<const half_t*>(ps_);
-    const half_t* pb = static_cast<const half_t*>(pb_);
-    const half_t* r = d.has_residual ? static_cast<const half_t*>(res) : nullptr;
-    half_t* out = static_cast<half_t*>(out_);
-    half_t* out2 = static_cast<half_t*>(out2_);
     static const int mixed = tuning_knob("METRO_G4_MIXED", 1);
     if (mixed && tm_whole > 0 && tm_half > 0 && r == nullptr && d.has_prologue && ((long)tm_whole * tiles_n) % 8 == 0) {
         auto kern = conv_gemm4w_mixed_kernel<true>;

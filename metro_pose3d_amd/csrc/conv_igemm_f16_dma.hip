@@ -656,16 +656,18 @@ bool conv_f16_fuse2_supported(const MetroConvDesc& d, int c2) {
            d.out_dtype == METRO_F16 && d.in_dtype == METRO_F16 && d.h_in == d.h_out && d.w_in == d.w_out;
 }
 
-static int launch_fuse2(const ConvArgs& a, const half_t* in, const half_t* w, const float* bias, const half_t* res,
-                        void* out, const ConvFuse2& f, hipStream_t stream) {
+int launch_conv_fuse2(const MetroConvDesc& d, const ConvOperands& o, hipStream_t stream, const ConvFuse2& f) {
     using Cfg = DmaFuse256x64;
+    const half_t* res = d.has_residual ? static_cast<const half_t*>(o.residual) : nullptr;
     if (note_kernel("conv_igemm_f16_fuse2<256x64>%s", res ? "+res" : "")) return METRO_OK;
+    const ConvArgs a = make_conv_args(d);
     auto kern = conv_igemm_f16_fuse2_kernel<Cfg>;
     constexpr int lds = Cfg::MAIN_BYTES + 64 * Cfg::TM * 2 + 2 * Cfg::TM * 2;
     static PerDeviceInt attr_done;
     if (const int st = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds, attr_done, "conv_igemm_f16_fuse2")) return st;
     const int tiles_n = (a.m_total + Cfg::TN - 1) / Cfg::TN;
-    hipLaunchKernelGGL(kern, dim3(tiles_n), dim3(Cfg::NT), lds, stream, a, in, w, bias, res, out,
+    hipLaunchKernelGGL(kern, dim3(tiles_n), dim3(Cfg::NT), lds, stream, a, static_cast<const half_t*>(o.in), static_cast<const half_t*>(o.w),
+                       o.bias, res, o.out,
                        Fuse2Args{static_cast<const half_t*>(f.w2), f.bias2, static_cast<const half_t*>(f.scale2),
                                  static_cast<const half_t*>(f.shift2), static_cast<half_t*>(f.out2), f.c2});
     return launch_status("conv_igemm_f16_dma<fuse2>");
@@ -677,73 +679,30 @@ bool conv_f16_dma_supported(const MetroConvDesc& d) {
            (!d.has_residual || d.c_out % 8 == 0) && (d.in_pix_stride % 8 == 0 || !d.has_prologue);
 }
 
-bool conv_form_supported(const MetroConvDesc& d, const ConvFused& f) {
-    const ConvSplit& s = f.pair;
-    const ConvRebuild& rb = f.rb;
-    switch (f.form) {
-        case ConvForm::Plain:
-            return true;          // plain layers: launch_conv_f16's kernel predicates
-        case ConvForm::Pair:      // the ring kernel's pair, which holds every pair conv_pw64 and conv_gemm4w run
-            return d.kh == 1 && d.kw == 1 && d.stride == 1 && d.has_prologue && !d.has_residual && !d.relu && d.in_dtype == METRO_F16 &&
-                   d.out_dtype == METRO_F16 && d.c_in % 64 == 0 && s.split > 0 && s.c_out2 > 0 && s.split + s.c_out2 == d.c_out &&
-                   s.split % 256 == 0 && s.c_out2 % 8 == 0;
-        case ConvForm::Next:
-            return conv_f16_fuse2_supported(d, f.next.c2) || conv_pw64_supported(d, f);
-        case ConvForm::NextProj:  // out_mode 1: the sum only feeds the next conv1 in the launch
-            return conv_pw64_supported(d, f) && (rb.out_mode == 0 || rb.out_mode == 1);
-        case ConvForm::NextRebuild:   // out_mode 2: only the sub-sampled compact copy of the sum is stored
-            return conv_pw64_supported(d, f) &&
-                   (rb.out_mode == 0 || (rb.out_mode == 2 && rb.out_sub != nullptr && (rb.sub_off == 0 || rb.sub_off == 1) && rb.h_sub > 0 &&
-                                         rb.w_sub > 0));
-    }
-    return false;
-}
-
-// `f` has passed conv_form_supported (the planner, the C entries)
-int launch_conv_f16_dma(const MetroConvDesc& d, const void* in_, const void* w_, const float* bias,
-                        const void* ps_, const void* pb_, const void* res_, void* out, hipStream_t stream, const ConvFused& f) {
+// the configuration ladder: tile counts against the 256 CUs and the K depth pick the instantiation
+int launch_conv_ring(const MetroConvDesc& d, const ConvOperands& o, hipStream_t stream, const ConvSplit* split) {
     ConvArgs a = make_conv_args(d);
     void* out2 = nullptr;
-    switch (f.form) {
-        case ConvForm::NextProj:
-        case ConvForm::NextRebuild:       // the persistent kernel only
-            return launch_conv_pw64(d, in_, w_, bias, nullptr, nullptr, nullptr, out, stream, f);
-        case ConvForm::Next:
-            if (conv_pw64_supported(d, f)) return launch_conv_pw64(d, in_, w_, bias, ps_, pb_, res_, out, stream, f);
-            return launch_fuse2(a, static_cast<const half_t*>(in_), static_cast<const half_t*>(w_), bias,
-                                d.has_residual ? static_cast<const half_t*>(res_) : nullptr, out, f.next, stream);
-        case ConvForm::Pair:
-            if (conv_pw64_supported(d, f)) return launch_conv_pw64(d, in_, w_, bias, ps_, pb_, res_, out, stream, f);
-            if (conv_gemm4w_supported(d, &f.pair)) return launch_conv_gemm4w(d, in_, w_, bias, ps_, pb_, res_, out, stream, &f.pair);
-            a.split = f.pair.split; a.c_out2 = f.pair.c_out2; a.relu2 = f.pair.relu2;
-            out2 = f.pair.out2;
-            break;
-        case ConvForm::Plain:
-            if (conv_pws_supported(d)) return launch_conv_pws(d, in_, w_, bias, res_, out, stream);
-            if (conv_pw64_supported(d, f)) return launch_conv_pw64(d, in_, w_, bias, ps_, pb_, res_, out, stream, f);
-            // deep-K pre-activated 1x1 layers with at least one 256 x 256 tile per CU: the four-wave GEMM (128 x 128 wave tiles,
-            // register-staged operands, the pre-activation applied once per element on its way into LDS).  Two other forms of this
-            // GEMM (8-phase two-wave-group LDS-DMA, round 2; four waves with both operands by LDS-DMA, round 4) give the same bits and
-            // measured the same inside the forward: they live in csrc/experimental/ (libmetro_experimental.so), not in the product.
-            if (conv_gemm4w_supported(d, nullptr)) return launch_conv_gemm4w(d, in_, w_, bias, ps_, pb_, res_, out, stream, nullptr);
-            break;
+    if (split != nullptr) {
+        a.split = split->split; a.c_out2 = split->c_out2; a.relu2 = split->relu2;
+        out2 = split->out2;
     }
-    const half_t* in = static_cast<const half_t*>(in_);
-    const half_t* w = static_cast<const half_t*>(w_);
-    const half_t* ps = static_cast<const half_t*>(ps_);
-    const half_t* pb = static_cast<const half_t*>(pb_);
-    const half_t* res = d.has_residual ? static_cast<const half_t*>(res_) : nullptr;
+    const half_t* in = static_cast<const half_t*>(o.in);
+    const half_t* w = static_cast<const half_t*>(o.w);
+    const half_t* ps = static_cast<const half_t*>(o.pro_scale);
+    const half_t* pb = static_cast<const half_t*>(o.pro_shift);
+    const half_t* res = d.has_residual ? static_cast<const half_t*>(o.residual) : nullptr;
     const int out_f32 = d.out_dtype == METRO_F32;
     const bool pro = d.has_prologue != 0;
     const int tiles128 = (d.c_out + 127) / 128;
     // tuning knobs (A/B runs): K-steps up to which the 1-stage / 2-stage 128x128 configs are used
     static const int nk_s1 = tuning_knob("METRO_NK_S1", 2);
     static const int nk_s2 = tuning_knob("METRO_NK_S2", 8);
-#define METRO_DMA(CFG)                                                                               \
-    return pro ? launch_dma_cfg<CFG, true>(a, in, w, bias, ps, pb, res, out, out_f32, out2, stream)  \
-               : launch_dma_cfg<CFG, false>(a, in, w, bias, ps, pb, res, out, out_f32, out2, stream)
+#define METRO_DMA(CFG)                                                                                   \
+    return pro ? launch_dma_cfg<CFG, true>(a, in, w, o.bias, ps, pb, res, o.out, out_f32, out2, stream)  \
+               : launch_dma_cfg<CFG, false>(a, in, w, o.bias, ps, pb, res, o.out, out_f32, out2, stream)
     if (d.c_in <= 32 && !pro) {
-        return launch_dma_cfg<Dma64x128s3k32, false>(a, in, w, bias, ps, pb, res, out, out_f32, out2, stream);
+        return launch_dma_cfg<Dma64x128s3k32, false>(a, in, w, o.bias, ps, pb, res, o.out, out_f32, out2, stream);
     }
     const int nk = d.kh * d.kw * ((d.c_in + 63) / 64);
     // 64-cout tiles: narrow layers, and heads whose width wastes most of a second 128-tile (136 = 8*17)
@@ -773,17 +732,6 @@ int launch_conv_f16_dma(const MetroConvDesc& d, const void* in_, const void* w_,
     if (half_tiles && d.c_out % 64 == 0 && blocks128 >= 64 && blocks128 < 224 && a.split == 0) { METRO_DMA(Dma64x128s3); }
     METRO_DMA(Dma128x128s4);
 #undef METRO_DMA
-}
-
-// fp16 convolution dispatcher (metro_conv_f16 and every plain conv layer of the plan)
-int launch_conv_f16(const MetroConvDesc& d, const void* in, const void* w, const float* bias, const void* ps,
-                    const void* pb, const void* res, void* out, hipStream_t stream) {
-    if (conv3x3_c64_supported(d)) return launch_conv3x3_c64(d, in, w, bias, out, stream);
-    if (conv3x3_slab_supported(d)) return launch_conv3x3_slab(d, in, w, bias, out, stream);
-    if (conv_f16_dma_supported(d)) return launch_conv_f16_dma(d, in, w, bias, ps, pb, res, out, stream);
-    set_error("conv_f16: unsupported layer (c_in %d must be a multiple of 8 and <= 2048, in_pix_stride %d of 4 (8 with a "
-              "prologue), c_out %d of 4 (8 with a residual))", d.c_in, d.in_pix_stride, d.c_out);
-    return METRO_ERR_UNSUPPORTED;
 }
 
 }  // namespace metro

@@ -629,12 +629,6 @@ static bool pw_enabled() {
     return v != 0;
 }
 
-// the maps the rebuilt residual and conv_b1.hip's producer / consumer form are built for: whole 64-pixel tiles, width a power of
-// two >= 16 (the sub-sampled copy's pixel arithmetic)
-static bool b1_map_ok(const MetroConvDesc& d) {
-    return (d.h_out * d.w_out) % 64 == 0 && d.w_out >= 16 && (d.w_out & (d.w_out - 1)) == 0;
-}
-
 bool conv_pw64_supported(const MetroConvDesc& d, const ConvFused& f) {
     if (!pw_enabled()) return false;
     if (!(d.kh == 1 && d.kw == 1 && d.stride == 1 && d.pad_top == 0 && d.pad_left == 0 && d.in_pix_stride == d.c_in &&
@@ -695,21 +689,16 @@ static int launch_pw(Pw64Args a, hipStream_t stream) {
 }
 
 // `f` has passed conv_form_supported and conv_pw64_supported
-int launch_conv_pw64(const MetroConvDesc& d, const void* in, const void* w, const float* bias, const void* ps,
-                     const void* pb, const void* res, void* out, hipStream_t stream, const ConvFused& f) {
+int launch_conv_pw64(const MetroConvDesc& d, const ConvOperands& o, hipStream_t stream, const ConvFused& f) {
     const ConvRebuild& rb = f.rb;
-    // the launches whose sum stays on chip (or is rebuilt): the producer / consumer form, unless the classic one is asked for
-    if ((f.form == ConvForm::NextRebuild || (f.form == ConvForm::NextProj && rb.out_mode == 1)) && !rb.classic &&
-        conv_b1_chain_preferred() && b1_map_ok(d))
-        return launch_conv_b1_chain(d, in, w, bias, out, stream, f);
     Pw64Args a;
-    a.in = static_cast<const half_t*>(in);
-    a.w = static_cast<const half_t*>(w);
-    a.bias = bias;
-    a.pro_scale = static_cast<const half_t*>(ps);
-    a.pro_shift = static_cast<const half_t*>(pb);
-    a.residual = d.has_residual ? static_cast<const half_t*>(res) : nullptr;
-    a.out = static_cast<half_t*>(out);
+    a.in = static_cast<const half_t*>(o.in);
+    a.w = static_cast<const half_t*>(o.w);
+    a.bias = o.bias;
+    a.pro_scale = static_cast<const half_t*>(o.pro_scale);
+    a.pro_shift = static_cast<const half_t*>(o.pro_shift);
+    a.residual = d.has_residual ? static_cast<const half_t*>(o.residual) : nullptr;
+    a.out = static_cast<half_t*>(o.out);
     a.w2 = nullptr; a.bias2 = nullptr; a.scale2 = nullptr; a.shift2 = nullptr; a.out2 = nullptr;
     a.x_sc = nullptr; a.w_sc = nullptr; a.bias_sc = nullptr;
     a.in_b = nullptr; a.w_b = nullptr; a.bias_b = nullptr; a.out_sub = nullptr; a.sub_off = 0; a.h_sub = 0; a.w_sub = 0; a.lw_out = 0;
@@ -720,7 +709,7 @@ int launch_conv_pw64(const MetroConvDesc& d, const void* in, const void* w, cons
     a.h_out = d.h_out; a.w_out = d.w_out;
     const bool rsub = d.has_residual && d.res_stride == 2;
     if (f.form == ConvForm::Pair) {
-        a.w2 = a.w + (size_t)f.pair.split * d.c_in; a.bias2 = bias + f.pair.split; a.out2 = static_cast<half_t*>(f.pair.out2);
+        a.w2 = a.w + (size_t)f.pair.split * d.c_in; a.bias2 = a.bias + f.pair.split; a.out2 = static_cast<half_t*>(f.pair.out2);
         if (d.c_in == 256) return launch_pw<256, 8, true, false, 1, false, false, 512>(a, stream);
         return launch_pw<64, 4, true, false, 1>(a, stream);
     }

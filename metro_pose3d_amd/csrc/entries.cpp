@@ -92,8 +92,7 @@ int metro_conv_f16(const MetroConvDesc* d, const void* d_in, const void* d_w, co
     METRO_CHECK_ARG(d_in && d_w && d_bias && d_out, "conv_f16: NULL tensor pointer");
     METRO_CHECK_ARG(!d->has_prologue || (d_pro_scale && d_pro_shift), "conv_f16: prologue tensors missing");
     METRO_CHECK_ARG(!d->has_residual || d_residual, "conv_f16: residual tensor missing");
-    return launch_conv_f16(*d, d_in, d_w, d_bias, d_pro_scale, d_pro_shift, d_residual, d_out,
-                           static_cast<hipStream_t>(stream));
+    return launch_conv_f16(*d, {d_in, d_w, d_bias, d_pro_scale, d_pro_shift, d_residual, d_out}, static_cast<hipStream_t>(stream));
 }
 
 int metro_conv_f16_pair(const MetroConvDesc* d, const void* d_in, const void* d_w, const float* d_bias,
@@ -107,7 +106,7 @@ int metro_conv_f16_pair(const MetroConvDesc* d, const void* d_in, const void* d_
     f.pair = {split, d->c_out - split, 1, d_out2};
     METRO_CHECK_ARG(conv_form_supported(*d, f), "conv_f16_pair: fp16 1x1 stride-1 convolution with prologue, without residual / ReLU on the "
                     "first output, c_in %% 64; split %d of c_out %d (split %% 256, rest %% 8)", split, d->c_out);
-    return launch_conv_f16_dma(*d, d_in, d_w, d_bias, d_pro_scale, d_pro_shift, nullptr, d_out, static_cast<hipStream_t>(stream), f);
+    return launch_conv_f16(*d, {d_in, d_w, d_bias, d_pro_scale, d_pro_shift, nullptr, d_out}, static_cast<hipStream_t>(stream), f);
 }
 
 int metro_conv_f16_next(const MetroConvDesc* d, const void* d_in, const void* d_w, const float* d_bias,
@@ -123,7 +122,7 @@ int metro_conv_f16_next(const MetroConvDesc* d, const void* d_in, const void* d_
     f.next = {d_w2, d_bias2, d_scale2, d_shift2, d_out2, c2};
     METRO_CHECK_ARG(conv_form_supported(*d, f),
                     "conv_f16_next: built for 1x1 stride-1 64 -> 256 with c2 = 64 (block1) and 128 -> 512 with c2 = 128 (block2), fp16");
-    return launch_conv_f16_dma(*d, d_in, d_w, d_bias, nullptr, nullptr, d_residual, d_out, static_cast<hipStream_t>(stream), f);
+    return launch_conv_f16(*d, {d_in, d_w, d_bias, nullptr, nullptr, d_residual, d_out}, static_cast<hipStream_t>(stream), f);
 }
 
 int metro_conv_f16_conv1_conv2(const MetroConvDesc* d, const void* d_x, const void* d_w1, const float* d_bias1, const void* d_pro_scale,
@@ -153,7 +152,7 @@ int metro_conv_f16_next_proj(const MetroConvDesc* d, const void* d_in, const voi
     f.rb.out_mode = d_out == nullptr ? 1 : 0;          // d_out == NULL: the sum stays on chip (it only feeds the second GEMM)
     METRO_CHECK_ARG(conv_form_supported(*d, f), "conv_f16_next_proj: built for 1x1 stride-1 64 -> 256 without prologue / residual, "
                     "c2 = 64 (block1/unit_1), fp16");
-    return launch_conv_f16_dma(*d, d_in, d_w, d_bias, nullptr, nullptr, nullptr, d_out, static_cast<hipStream_t>(stream), f);
+    return launch_conv_f16(*d, {d_in, d_w, d_bias, nullptr, nullptr, nullptr, d_out}, static_cast<hipStream_t>(stream), f);
 }
 
 int metro_conv_f16_next_rebuild(const MetroConvDesc* d, const void* d_in, const void* d_w, const float* d_bias, const void* d_x,
@@ -180,7 +179,7 @@ int metro_conv_f16_next_rebuild(const MetroConvDesc* d, const void* d_in, const 
     }
     METRO_CHECK_ARG(conv_form_supported(*d, f), "conv_f16_next_rebuild: built for 1x1 stride-1 64 -> 256 without prologue / residual on maps "
                     "whose width is a power of two >= 16 and whose pixel count is a multiple of 64, c2 = 64 (block1/unit_2), fp16");
-    return launch_conv_f16_dma(*d, d_in, d_w, d_bias, nullptr, nullptr, nullptr, d_out, static_cast<hipStream_t>(stream), f);
+    return launch_conv_f16(*d, {d_in, d_w, d_bias, nullptr, nullptr, nullptr, d_out}, static_cast<hipStream_t>(stream), f);
 }
 
 int metro_conv_b1_form(int32_t classic) {
@@ -200,8 +199,8 @@ int metro_conv_f16_gemm4w(const MetroConvDesc* d, const void* d_in, const void* 
     METRO_CHECK_ARG(split >= 0 && split < d->c_out && (split == 0 || d_out2), "conv_f16_gemm4w: bad split %d / missing second output", split);
     ConvSplit sp;
     sp.split = split; sp.c_out2 = d->c_out - split; sp.relu2 = 1; sp.out2 = d_out2;
-    return launch_conv_gemm4w(*d, d_in, d_w, d_bias, d_pro_scale, d_pro_shift, d_residual, d_out,
-                              static_cast<hipStream_t>(stream), split > 0 ? &sp : nullptr);
+    return launch_conv_gemm4w(*d, {d_in, d_w, d_bias, d_pro_scale, d_pro_shift, d_residual, d_out}, static_cast<hipStream_t>(stream),
+                              split > 0 ? &sp : nullptr);
 }
 
 int metro_stem_pool_f16(const void* d_prepped, const void* d_w, const float* d_bias, void* d_out, int32_t n,

@@ -61,7 +61,7 @@ int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* 
                 }
                 case LayerForm::Plain:
                     if (p->fast)
-                        return launch_conv_f16(cd, in, w, bias, prm(L.main.scale), prm(L.main.shift), slot_ptr(L.res_slot), out, stream);
+                        return launch_conv_f16(cd, {in, w, bias, prm(L.main.scale), prm(L.main.shift), slot_ptr(L.res_slot), out}, stream);
                     if (p->spec.precision == METRO_PREC_F32M)
                         return launch_conv_f32m(cd, in, static_cast<const float*>(w), bias, fprm(L.main.scale), fprm(L.main.shift),
                                                 slot_ptr(L.res_slot), out, stream);
@@ -71,7 +71,7 @@ int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* 
                 case LayerForm::Pair:
                     f.form = ConvForm::Pair;
                     f.pair = {L.cd.c_out - L.c2, L.c2, 1, slot_ptr(L.out2_slot)};
-                    return launch_conv_f16_dma(cd, in, w, bias, prm(L.main.scale), prm(L.main.shift), nullptr, out, stream, f);
+                    return launch_conv_f16(cd, {in, w, bias, prm(L.main.scale), prm(L.main.shift), nullptr, out}, stream, f);
                 case LayerForm::Next:
                 case LayerForm::NextProj:
                 case LayerForm::NextRebuild:
@@ -87,7 +87,7 @@ int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* 
                     f.rb.out_mode = dump ? 0 : L.out_mode;
                     f.rb.classic = dump ? 1 : 0;
                     if (f.rb.out_mode == 2) { f.rb.out_sub = slot_ptr(L.sub_slot); f.rb.sub_off = L.sub_off; f.rb.h_sub = f.rb.w_sub = L.sub_side; }
-                    return launch_conv_f16_dma(cd, in, w, bias, nullptr, nullptr, slot_ptr(L.res_slot), out, stream, f);
+                    return launch_conv_f16(cd, {in, w, bias, nullptr, nullptr, slot_ptr(L.res_slot), out}, stream, f);
             }
             break;
         }

@@ -309,33 +309,52 @@ inline ConvArgs make_conv_args(const MetroConvDesc& d) {
 
 int validate_conv_desc(const MetroConvDesc* d);
 
-// kernel launchers implemented in the .hip files
-// fp16 convolution dispatcher: tap-reuse slab kernel for 3x3 stride-1 layers, the LDS-DMA ring kernel otherwise
-int launch_conv_f16(const MetroConvDesc& d, const void* in, const void* w, const float* bias,
-                    const void* pro_scale, const void* pro_shift, const void* residual, void* out,
-                    hipStream_t stream);
-// LDS-DMA ring kernel (coalesced epilogue); also the dispatcher of the fused forms, which reads `f.form` (checked)
-bool conv_f16_dma_supported(const MetroConvDesc& d);
-int launch_conv_f16_dma(const MetroConvDesc& d, const void* in, const void* w, const float* bias,
-                        const void* pro_scale, const void* pro_shift, const void* residual, void* out,
-                        hipStream_t stream, const ConvFused& f = ConvFused{});
+// the device tensors of one fp16 conv launch (a fused form's further tensors travel in its ConvFused)
+struct ConvOperands {
+    const void* in;
+    const void* w;
+    const float* bias;
+    const void* pro_scale;
+    const void* pro_shift;
+    const void* residual;
+    void* out;
+};
+
+// ---- fp16 convolution dispatch (conv_dispatch.cpp) ---------------------------------------------------------------------------
+// The kernel families of the product, and the one ordered rule "form f.form of layer d runs on family K".  None: no family runs it.
+enum class ConvKernel { C64, Slab, Pws, Pw64, B1Chain, Gemm4w, Fuse2, Ring, None };
+ConvKernel choose_conv_kernel(const MetroConvDesc& d, const ConvFused& f);
+// the dispatcher: one launch on the family choose_conv_kernel names (metro_conv_f16*, every fp16 conv layer of the plan);
+// a fused `f` has passed conv_form_supported (the planner, the C entries)
+int launch_conv_f16(const MetroConvDesc& d, const ConvOperands& o, hipStream_t stream, const ConvFused& f = ConvFused{});
 // whether `d` with the parts of `f` can run as one launch of form f.form: the one shape rule of each form (the pair's split, the
 // second GEMM's c2, the rebuilt residual's map and output mode), read by the planner, the C entries and the dispatch
 bool conv_form_supported(const MetroConvDesc& d, const ConvFused& f);
+
+// ---- kernel launchers implemented in the .hip files: each file launches its own kernels only ------------------------------------
+// LDS-DMA ring kernel, coalesced epilogue (conv_igemm_f16_dma.hip); `split`: the two outputs of a Pair, else NULL
+bool conv_f16_dma_supported(const MetroConvDesc& d);
+int launch_conv_ring(const MetroConvDesc& d, const ConvOperands& o, hipStream_t stream, const ConvSplit* split);
+// its one-K-step form with the next unit's conv1 as a second GEMM on the LDS-resident output tile (block1's Next launches)
 bool conv_f16_fuse2_supported(const MetroConvDesc& d, int c2);
+int launch_conv_fuse2(const MetroConvDesc& d, const ConvOperands& o, hipStream_t stream, const ConvFuse2& f);
 // 256 x 256 x 64 GEMM, four waves of 128 x 128, register-staged operands (conv_gemm4w.hip): the pre-activated deep-K 1x1 layers
 // (conv1, projection shortcut, shortcut + conv1 pair of blocks 3-4) with at least one tile per CU
 bool conv_gemm4w_shape_ok(const MetroConvDesc& d, const ConvSplit* split);      // what the kernel can run
 bool conv_gemm4w_supported(const MetroConvDesc& d, const ConvSplit* split);     // ... and when the dispatcher prefers it
-int launch_conv_gemm4w(const MetroConvDesc& d, const void* in, const void* w, const float* bias, const void* pro_scale,
-                       const void* pro_shift, const void* residual, void* out, hipStream_t stream, const ConvSplit* split);
+int launch_conv_gemm4w(const MetroConvDesc& d, const ConvOperands& o, hipStream_t stream, const ConvSplit* split);
 // persistent pipelined kernel for block1's 64-channel 1x1 convolutions and the conv3 layers of blocks 2-4 (conv_pw64.hip): whether it
 // runs `d` in form f.form with f's parts
 bool conv_pw64_supported(const MetroConvDesc& d, const ConvFused& f);
-int launch_conv_pw64(const MetroConvDesc& d, const void* in, const void* w, const float* bias, const void* pro_scale,
-                     const void* pro_shift, const void* residual, void* out, hipStream_t stream, const ConvFused& f);
-// producer / consumer form of the NextProj / NextRebuild launches of block1 whose sum stays on chip (conv_b1.hip)
-bool conv_b1_chain_preferred();
+int launch_conv_pw64(const MetroConvDesc& d, const ConvOperands& o, hipStream_t stream, const ConvFused& f);
+// the maps the rebuilt residual (conv_pw64.hip) and the producer / consumer form (conv_b1.hip) are built for: whole 64-pixel tiles,
+// width a power of two >= 16 (the sub-sampled copy's pixel arithmetic)
+inline bool b1_map_ok(const MetroConvDesc& d) {
+    return (d.h_out * d.w_out) % 64 == 0 && d.w_out >= 16 && (d.w_out & (d.w_out - 1)) == 0;
+}
+// producer / consumer form of the NextProj / NextRebuild launches of block1 whose sum stays on chip or is rebuilt (conv_b1.hip):
+// whether it is preferred for a launch that has passed conv_form_supported (the form, its output mode, rb.classic, the knob, the map)
+bool conv_b1_chain_supported(const MetroConvDesc& d, const ConvFused& f);
 void conv_b1_set_form(int classic);      // thread-local test switch: 1 = never dispatch it (nor conv_pws.hip's kernel)
 bool classic_forms_forced();
 // conv3 + shortcut of blocks 3-4 with the two waves of a SIMD half a tile apart (conv_pws.hip); same bits as conv_pw64's <k256|k512,wm8,res>

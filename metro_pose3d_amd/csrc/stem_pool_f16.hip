@@ -723,10 +723,8 @@ __device__ __forceinline__ void stem_pool_rows_body(const StemPoolArgs& a) {
 __global__ __launch_bounds__(sp2::NT, 2) void stem_pool_rows_kernel(StemPoolArgs a) { stem_pool_rows_body<false>(a); }
 __global__ __launch_bounds__(sp2::NT, 2) void stem_pool_rows_u8_kernel(StemPoolArgs a) { stem_pool_rows_body<true>(a); }
 
-static int sp_env_int(const char* name, int dflt) { return tuning_knob(name, dflt); }
-
 bool stem_pool_f16_supported(int side, int base_width) {
-    static const int enabled = sp_env_int("METRO_STEM_POOL", 1);
+    static const int enabled = tuning_knob("METRO_STEM_POOL", 1);
     return enabled && base_width == 64 && side % 32 == 0 && side >= 32;
 }
 
@@ -746,13 +744,13 @@ int launch_stem_pool_f16(const void* prepped, const void* w, const float* bias, 
     a.n_patches = n * ppr * ppr;
     a.img_f32 = nullptr;
     a.img_u8 = nullptr;
-    static const int split = sp_env_int("METRO_STEM_SPLIT", 2);
+    static const int split = tuning_knob("METRO_STEM_SPLIT", 2);
     if (split == 2) return launch_sp<2, IN_PREPPED>(a, stream);
     return launch_sp<1, IN_PREPPED>(a, stream);
 }
 
 bool stem_pool_f32in_supported(int side, int base_width) {
-    static const int enabled = sp_env_int("METRO_STEM_RAW", 1);
+    static const int enabled = tuning_knob("METRO_STEM_RAW", 1);
     return enabled && stem_pool_f16_supported(side, base_width);
 }
 
@@ -769,7 +767,7 @@ int launch_stem_pool_f32in(const float* images, const void* w, const float* bias
     a.n = n; a.side = side;
     const int ppr = side / 4 / sp::PP;
     a.n_patches = n * ppr * ppr;
-    static const int rows = sp_env_int("METRO_STEM_ROWS", 1);
+    static const int rows = tuning_knob("METRO_STEM_ROWS", 1);
     if (rows && side == sp2::SIDE) {
         if (note_kernel("stem_pool_f16<rows,f32in>")) return METRO_OK;
         static PerDeviceInt cap;
@@ -778,7 +776,7 @@ int launch_stem_pool_f32in(const float* images, const void* w, const float* bias
         hipLaunchKernelGGL(stem_pool_rows_kernel, dim3(n * (sp2::PS / sp2::PY)), dim3(sp2::NT), sp2::LDS_BYTES, stream, a);
         return launch_status("stem_pool_f16<rows>");
     }
-    static const int split = sp_env_int("METRO_STEM_RAW_SPLIT", 2);
+    static const int split = tuning_knob("METRO_STEM_RAW_SPLIT", 2);
     if (split == 1) return launch_sp<1, IN_F32>(a, stream);
     return launch_sp<2, IN_F32>(a, stream);
 }
@@ -802,7 +800,7 @@ int launch_stem_pool_u8in(const unsigned char* images, const void* w, const floa
     a.n = n; a.side = side;
     const int ppr = side / 4 / sp::PP;
     a.n_patches = n * ppr * ppr;
-    static const int rows = sp_env_int("METRO_STEM_ROWS", 1);
+    static const int rows = tuning_knob("METRO_STEM_ROWS", 1);
     if (rows && side == sp2::SIDE) {
         if (note_kernel("stem_pool_f16<rows,u8in>")) return METRO_OK;
         static PerDeviceInt cap;
@@ -811,7 +809,7 @@ int launch_stem_pool_u8in(const unsigned char* images, const void* w, const floa
         hipLaunchKernelGGL(stem_pool_rows_u8_kernel, dim3(n * (sp2::PS / sp2::PY)), dim3(sp2::NT), sp2::LDS_BYTES_U8, stream, a);
         return launch_status("stem_pool_f16<rows,u8in>");
     }
-    static const int split = sp_env_int("METRO_STEM_RAW_SPLIT", 2);
+    static const int split = tuning_knob("METRO_STEM_RAW_SPLIT", 2);
     if (split == 1) return launch_sp<1, IN_U8>(a, stream);
     return launch_sp<2, IN_U8>(a, stream);
 }

@@ -21,6 +21,9 @@ instantiation (a dry run of the dispatch, no device needed), so this file can
     not launch -- the list comes from the dry run over every call size 1 .. 256 that the two CPU closure tests make.
 """
 import ctypes as C
+import hashlib
+import json
+import os
 import zlib
 
 import numpy as np
@@ -380,6 +383,39 @@ def test_pair_closure():
     assert not missing, 'dispatched at proc_side 256 but launched by no GPU case (kernel id: the smallest call that reaches the shape):\n' + \
         '\n'.join(f'  {kid}: {spec_name(spec)}, batch {n}, {DryRun(spec, n).names[i]} {dict(zip(SHAPE_KEY, key))}'
                   for (kid, key), (spec, n, i) in sorted(missing.items(), key=lambda kv: (kv[0][0], kv[1][1])))
+
+
+def classic_dispatch_digests():
+    """{spec name: sha256 over the kernel id of every layer at every call size 1 .. 256} of PAIR_SPECS' default plans, dispatched
+    with the classic forms forced (metro_conv_b1_form(1))."""
+    lib = _lib.load()
+    runs = [DryRun(spec) for spec in PAIR_SPECS]
+    out = {}
+    check(lib.metro_conv_b1_form(1), 'metro_conv_b1_form')
+    try:
+        for run in runs:
+            h = hashlib.sha256()
+            for n in GRID_BATCHES:
+                h.update('\0'.join(run.kernels(n)).encode() + b'\n')
+            out[spec_name(run.spec)] = h.hexdigest()
+    finally:
+        lib.metro_conv_b1_form(0)
+    return out
+
+
+def test_classic_dispatch_reproduces_the_snapshot():
+    """tests/golden/plan_tables_v1.json (test_plan_snapshot.py) holds the default dispatch only.  The forms behind the test switch
+    metro_conv_b1_form(1) -- conv_pw64's single-role kernel in place of conv_b1_chain and conv_pws, the ring kernel's pair in
+    place of block2's weight-resident one -- are what the GPU tests compare the default kernels with bit for bit, so a change of
+    the dispatch must leave them where they were too.  tests/golden/classic_dispatch_v1.json was written by
+    classic_dispatch_digests() from the library of the commit BEFORE the dispatch moved into csrc/conv_dispatch.cpp
+    (METRO_HIP_LIB=<that library>); like the plan snapshot it is rewritten only with an intended change, from the commit before."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'classic_dispatch_v1.json')) as f:
+        golden = json.load(f)
+    got = classic_dispatch_digests()
+    assert sorted(got) == sorted(golden)
+    bad = [k for k in golden if got[k] != golden[k]]
+    assert not bad, f'classic dispatch of {bad} differs from tests/golden/classic_dispatch_v1.json'
 
 
 def test_every_kernel_has_a_nonfinite_case(lib):
