@@ -781,6 +781,42 @@ int  metro_person_steps(const int32_t* d_rows, int32_t n_rows, const int32_t* d_
                         int32_t* d_person_step_out, double* d_person_times_out, int32_t* d_step_rows_out,
                         int32_t* d_step_starts_out, void* stream);
 
+/* ---- persons that ONE camera sees: their time step, their box and the ray of every joint ----
+ * Nothing in the reference: its examples have one camera each and no world.  metro_cluster_views gives a person with one box
+ * an empty group, so metro_person_steps gives it no step and it never reaches the association.  These two launches bring it
+ * there as a RAY row (metro_associate_tracks_rays, further down).  The ABI version is unchanged: the entries are additions.
+ * metro_person_steps_labels: metro_person_steps without the cluster CSR, one workgroup of 128 threads, thread p = person p.
+ * d_person_index int32 [n_boxes], the person of every box as metro_cluster_views wrote it; d_n_persons int32 [1];
+ * n <= METRO_MATCH_MAX_BOXES the upper bound of the persons; d_box_step int32 [n_boxes]; d_step_times fp64 [n_steps] ascending.
+ * The step of person p < d_n_persons[0] is the smallest d_box_step[b] in [0, n_steps) over the boxes b with
+ * d_person_index[b] == p -- for a person with several boxes the value metro_person_steps gives, and a person with one box now
+ * has a step too; -1 for a person with no such box and for the persons >= d_n_persons[0].  A label outside [0, n) belongs to no
+ * person and a step outside [0, n_steps) is skipped: nothing is read through either.  d_person_step_out, d_person_times_out,
+ * d_step_rows_out and d_step_starts_out are metro_person_steps' four outputs, built from these steps by the same code.
+ * d_single_box_out int32 [n]: the box of a person that has exactly one box, whose step is valid; -1 for everyone else, the
+ * persons >= d_n_persons[0] included.  -1 before any launch for a negative size, n > METRO_MATCH_MAX_BOXES and, with n > 0, a NULL
+ * pointer (d_person_index and d_box_step only with n_boxes > 0, d_step_times only with n_steps > 0).  n == 0 launches nothing
+ * and returns 0.
+ * metro_person_rays: one thread per (person, output joint) in blocks of 64, fp64 arithmetic on the fp32 inputs.  d_coords01,
+ * d_cov01 (METRO_TRI_COVARIANCE only, else may be NULL), d_records, spec, d_mirror and weights as metro_triangulate_joints
+ * reads them, m = n * n_views crop rows, box-major; d_single_box int32 [n] as written above.  Per (p, r): with
+ * b = d_single_box[p] outside [0, n) there is no ray.  Otherwise over the usable rays (d_v, o_v, sigma2_v) of the rows
+ * b * n_views + v, built exactly as the triangulation builds them (the mirror joint of a flipped view; a non-finite ray is
+ * skipped): w_v = 1 (METRO_TRI_UNIFORM) or 1 / sigma2_v (METRO_TRI_COVARIANCE; a view whose w_v is not finite and positive is
+ * dropped); d = (sum w_v d_v) normalised; o = o_v of the first usable view (the views of a box share one optical centre);
+ * sigma2 = 1 / sum (1 / sigma2_v) with covariance weights, 0 with uniform ones.  No ray if no view is usable or the sum has
+ * zero or non-finite length.  d_rays_out fp64 [n, n_joints_out, 8]: o (3), d (3), sigma2, the number of views used; all eight
+ * NaN where there is no ray.  -1 before any launch for a NULL spec, joint counts out of range, unknown weights, a negative size,
+ * n > METRO_MATCH_MAX_BOXES, n_views outside [1, METRO_MAX_VIEWS], m != n * n_views and, with n > 0, a NULL pointer (d_cov01
+ * only with METRO_TRI_COVARIANCE).  n == 0 launches nothing and returns 0. */
+int  metro_person_steps_labels(const int32_t* d_person_index, const int32_t* d_n_persons, int32_t n, const int32_t* d_box_step,
+                               int32_t n_boxes, const double* d_step_times, int32_t n_steps, int32_t* d_person_step_out,
+                               double* d_person_times_out, int32_t* d_step_rows_out, int32_t* d_step_starts_out,
+                               int32_t* d_single_box_out, void* stream);
+int  metro_person_rays(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records, int32_t m,
+                       const MetroSpec* spec, const int32_t* d_mirror, int32_t weights, const int32_t* d_single_box, int32_t n,
+                       int32_t n_views, double* d_rays_out, void* stream);
+
 /* ---- poses of tracked persons smoothed over time: constant-velocity Kalman filter + Rauch-Tung-Striebel pass ----
  * Nothing in the reference: one example is one image.  One launch, one thread per (track, output joint), fp64 arithmetic on
  * the fp32 inputs, one rounding to fp32 per output.  J = spec->n_joints_out (nothing else of the spec is read).
@@ -912,6 +948,46 @@ int  metro_associate_tracks_optimal(const float* d_poses, const float* d_cov, co
                                     int32_t* d_next_id, void* d_workspace, int32_t* d_track_index_out, int32_t* d_track_id_out,
                                     float* d_cost_out, int32_t* d_rows_out, int32_t* d_starts_out, int32_t* d_n_new_out,
                                     int32_t* d_n_dropped_out, void* stream);
+
+/* ---- the same walk with RAY rows: a person one camera sees keeps feeding its track ----
+ * metro_associate_tracks_rays is metro_associate_tracks (assignment 0: the greedy step 2) or metro_associate_tracks_optimal
+ * (assignment 1: step 2') -- workspace, one launch of one workgroup, the cost matrix in LDS -- with these additions.
+ * d_poses and d_cov are WRITABLE; d_single_box int32 [n]: >= 0 marks row b as a RAY row (metro_person_steps_labels; the value
+ * itself is not read); d_rays fp64 [n, J, 8]: o (3), d (3, unit), sigma2, views per joint (metro_person_rays); depth_sigma_mm;
+ * d_ray_depth_out fp32 [n, J]; d_n_unplaced_out int32 [1].  A row that is no ray row is a POINT row and behaves exactly as
+ * there.  Of a ray row d_poses and d_cov are not read before the launch has written them; it differs as follows.
+ * 1. cost[t][b]: over the joints j whose working t_last[j] is not NaN and whose ray is finite (o, d and sigma2), with
+ *    p^ = p + dt v, dt as there: w = p^ - o, tau = d . w, dist_j = clip_mm if !(tau > 0) (behind the camera), else
+ *    min(|w - tau d|, clip_mm); cost = sqrt(mean dist_j^2), rounded once to fp32; +inf under the conditions there (min_joints,
+ *    max_age_s).  The cost is BLIND ALONG THE RAY: a slot anywhere on the rays costs 0, so of two tracks in line with the
+ *    camera either may be taken; a cost that knows the depth is left to a later version.
+ * 2. The assignment runs unchanged on the one matrix that holds both kinds of rows.
+ * 3. A ray row is never born: it has no depth.  Unassigned it is untracked and counted in d_n_unplaced_out, not in
+ *    d_n_dropped_out, which keeps its meaning.
+ * 3a. Place (new, between the births and the filter): per assigned ray row b and joint j whose slot joint has a state, whose
+ *    ray is finite and with tau > 0 -- tau from the same p^, on the working state before this step's filter:
+ *    z = o + tau d, the foot of the perpendicular from p^ onto the ray, and, in fp64,
+ *    R = sigma2 tau^2 (I - d d^T) + depth_sigma_mm^2 d d^T: tight across the ray, wide along it, the linearised (EKF) form of
+ *    a bearing measurement.  z goes to d_poses[b, j] and all nine entries of R to d_cov[b, j], each rounded once to fp32; tau
+ *    to d_ray_depth_out[b, j], which is NaN everywhere else.  A joint not placed keeps what d_poses and d_cov held (NaN from
+ *    the triangulation): the filter bridges it.
+ * 4. The filter is unchanged and reads the fp32 arrays it always reads.  So the contract survives: metro_smooth_tracks on
+ *    d_rows_out / d_starts_out and the d_poses and d_cov this launch leaves writes into d_state the working state, bit for bit.
+ *    A placed joint whose ROUNDED R (scaled and floored as there) is not positive definite is predict-only (used 0): the safe
+ *    outcome.
+ * -1 before any launch for whatever metro_associate_tracks refuses, a measurement other than METRO_SMOOTH_COVARIANCE (an
+ * isotropic R would ignore the ray's shape and pin the depth), an assignment other than 0 and 1, depth_sigma_mm not finite and
+ * > 0 and, with n, n_step_rows and n_steps all > 0, a NULL pointer, d_cov and the four new ones included.  The ABI version is
+ * unchanged: the entry is an addition. */
+int  metro_associate_tracks_rays(float* d_poses, float* d_cov, const double* d_times, int32_t n, const int32_t* d_step_rows,
+                                 int32_t n_step_rows, const int32_t* d_step_starts, int32_t n_steps, const MetroSpec* spec,
+                                 int32_t measurement, double q, double r_floor, double cov_scale, double v0, double gate,
+                                 float max_cost_mm, double clip_mm, int32_t min_joints, double max_age_s, double* d_state,
+                                 int32_t n_tracks, int32_t* d_ids, int32_t* d_next_id, void* d_workspace,
+                                 int32_t* d_track_index_out, int32_t* d_track_id_out, float* d_cost_out, int32_t* d_rows_out,
+                                 int32_t* d_starts_out, int32_t* d_n_new_out, int32_t* d_n_dropped_out, int32_t assignment,
+                                 const int32_t* d_single_box, const double* d_rays, double depth_sigma_mm,
+                                 float* d_ray_depth_out, int32_t* d_n_unplaced_out, void* stream);
 
 /* ---- next-frame person boxes from the track table: crops between the key frames of a detector ----
  * Nothing in the reference: one example is one image and its box is given.  Two launches on `stream`, no host work in

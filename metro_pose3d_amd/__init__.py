@@ -14,6 +14,8 @@ Public surface (mirrors reference inference.py):
         the boxes are assigned to tracks on the device, frame by frame, under ids that persist from call to call
     follow_world_poses_in_frames(frames, boxes, model_path, cameras, frame_index, timestamps) -> a calibrated rig's video:
         boxes matched across cameras per exposure, triangulated with covariance, followed and smoothed in the world
+    follow_rig_poses_in_frames(frames, boxes, model_path, cameras, frame_index, timestamps) -> the same, and a person only
+        one camera sees keeps feeding its track: its rays are matched to the tracks and update them across the ray
     predict_boxes_in_frames(tracks, cameras, frame_sizes, timestamps) -> the person boxes of the next frames from the
         table of tracks those two return (frame_sizes(frames): their sizes), for the frames a detector does not see
     Follower(model_path, cameras, world=False, assignment='greedy', ...) -> one of the two follow calls with its keywords
@@ -24,7 +26,7 @@ container (save_model / load_model) and batch sharding over the GPUs of a node (
 from metro_pose3d_amd.spec import ModelSpec  # noqa: F401
 from metro_pose3d_amd.modelfile import load_model, save_model  # noqa: F401
 
-__all__ = ['ModelSpec', 'load_model', 'save_model', 'Engine', 'estimate_pose', 'estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'predict_boxes_in_frames', 'frame_sizes', 'Follower', 'Camera']
+__all__ = ['ModelSpec', 'load_model', 'save_model', 'Engine', 'estimate_pose', 'estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'follow_rig_poses_in_frames', 'predict_boxes_in_frames', 'frame_sizes', 'Follower', 'Camera']
 
 
 def __getattr__(name):
@@ -35,7 +37,7 @@ def __getattr__(name):
     if name == 'estimate_pose':
         from metro_pose3d_amd.inference import estimate_pose
         return estimate_pose
-    if name in ('estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'predict_boxes_in_frames', 'frame_sizes', 'Follower', 'Camera'):
+    if name in ('estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'follow_rig_poses_in_frames', 'predict_boxes_in_frames', 'frame_sizes', 'Follower', 'Camera'):
         from metro_pose3d_amd import frames
         return getattr(frames, name)
     raise AttributeError(name)

@@ -198,6 +198,8 @@ SIGNATURES = {
     'metro_view_affinity_steps': (C.c_int, [_P, _P, _P, C.POINTER(MetroSpec), _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                             C.c_double, C.c_int32, _P, _P, _P]),
     'metro_person_steps': (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    'metro_person_steps_labels': (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    'metro_person_rays': (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(MetroSpec), _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
     'metro_cluster_views': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_float, _P, _P, _P, _P, _P]),
     'metro_smooth_tracks_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
     'metro_smooth_tracks': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.POINTER(MetroSpec), C.c_int32, C.c_int32,
@@ -209,6 +211,10 @@ SIGNATURES = {
     'metro_associate_tracks_optimal': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.POINTER(MetroSpec), C.c_int32,
                                                  C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float, C.c_double,
                                                  C.c_int32, C.c_double, _P, C.c_int32] + [_P] * 11),
+    'metro_associate_tracks_rays': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.POINTER(MetroSpec), C.c_int32,
+                                              C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float, C.c_double,
+                                              C.c_int32, C.c_double, _P, C.c_int32] + [_P] * 10 +
+                                    [C.c_int32, _P, _P, C.c_double, _P, _P, _P]),
     'metro_predict_boxes': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32] + [C.c_double] * 7 +
                             [C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_double] + [_P] * 10),
     'metro_last_error': (C.c_char_p, []),

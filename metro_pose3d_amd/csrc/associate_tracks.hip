@@ -630,4 +630,269 @@ int launch_associate_tracks_optimal(const float* poses, const float* cov, const 
     return launch_status("associate_tracks_optimal");
 }
 
+// ---- the same walk with RAY rows among the point rows (metro_associate_tracks_rays) ----
+// A row b with single_box[b] >= 0 is a person one camera sees: it has no point, but one ray per joint, rays[b][j] = o (3), d (3),
+// sigma2, views (metro_person_rays).  Point rows go through the steps above unchanged; for a ray row
+//   cost      per slot: the RMS over the joints of the distance of the predicted joint p^ = p + dt v from the ray, min(|w - tau d|,
+//             clip) with w = p^ - o, tau = d . w, and clip itself behind the camera (!(tau > 0)).  The cost is BLIND ALONG THE RAY:
+//             a track anywhere on the ray costs 0, so of two tracks in line with the camera either may be taken.
+//   births    never: a ray has no depth to start a state from.  Unassigned, the row is untracked and counted in n_unplaced, not
+//             in n_dropped.
+//   place     (new, between apply and filter) per assigned ray row and joint whose slot joint has a state, whose ray is finite
+//             and with tau > 0 from the same p^ on the working state before this step's filter: z = o + tau d, the foot of the
+//             perpendicular from p^ onto the ray, and R = sigma2 tau^2 (I - d d^T) + depth_sigma^2 d d^T -- tight across the ray,
+//             wide along it, the linearised (EKF) form of a bearing measurement -- each rounded once to fp32 into poses[b][j]
+//             and cov[b][j]; tau goes to ray_depth.  A joint not placed keeps the NaN the triangulation left.
+//   filter    unchanged: smooth_filter_row reads the fp32 arrays it always reads, so metro_smooth_tracks on the CSR and the
+//             arrays this launch wrote leaves the working state, bit for bit.  A placed joint whose ROUNDED R fails smooth_pd3
+//             is predict-only (used 0): the safe outcome.
+// AssocLds, AssocArgs and AssocOptLds keep their layout; the additions live in AssocRayArgs and AssocRayLds.
+
+constexpr int ASSOC_RAY_DOUBLES = 8;
+
+struct AssocRayArgs : AssocArgs {
+    float* poses_w;          // poses and
+    float* cov_w;            // cov, writable: the place step fills the ray rows
+    const int* single_box;   // [n] >= 0: the row is a ray row
+    const double* rays;      // [n][J][8]
+    double depth_var;        // depth_sigma_mm^2
+    float* ray_depth;        // [n][J]
+    int* n_unplaced;         // [1]
+};
+
+struct AssocRayLds {
+    int box_ray[ASSOC_MAX];                              // the position holds a ray row
+    int n_unplaced;
+};
+
+__host__ __device__ inline void assoc_ray_begin(const AssocRayArgs& a, AssocRayLds& r, int tid, int nt) {
+    const size_t total = (size_t)a.n * a.n_out;
+    for (size_t i = tid; i < total; i += nt) a.ray_depth[i] = __builtin_nanf("");
+    if (tid == 0) r.n_unplaced = 0;
+}
+
+// after assoc_step_boxes, by the same thread per position: which boxes are ray rows; such a row is never born
+__host__ __device__ inline void assoc_ray_step_boxes(const AssocRayArgs& a, AssocLds& l, AssocRayLds& r, int m, int tid, int nt) {
+    for (int k = tid; k < m; k += nt) {
+        const int row = l.box_row[k];
+        r.box_ray[k] = row >= 0 && a.single_box[row] >= 0;
+        if (r.box_ray[k]) l.box_any[k] = 0;
+    }
+}
+
+// false: no finite ray
+__host__ __device__ inline bool assoc_ray_load(const AssocRayArgs& a, int row, int j, const double*& ray) {
+    ray = a.rays + ((size_t)row * a.n_out + j) * ASSOC_RAY_DOUBLES;
+    bool fin = true;
+    for (int e = 0; e < 7; ++e) fin = fin && __builtin_isfinite(ray[e]);
+    return fin;
+}
+
+// the predicted joint against the ray: tau = d . (p^ - o) and the distance of p^ from the line
+__host__ __device__ inline void assoc_ray_foot(const double* st, const double* ray, double t_step, double& tau, double& dist) {
+    double dt = t_step - st[27];
+    if (!(dt > 0.0)) dt = 0.0;
+    const double w0 = (st[0] + dt * st[3]) - ray[0], w1 = (st[1] + dt * st[4]) - ray[1], w2 = (st[2] + dt * st[5]) - ray[2];
+    tau = (ray[3] * w0 + ray[4] * w1) + ray[5] * w2;
+    const double e0 = w0 - tau * ray[3], e1 = w1 - tau * ray[4], e2 = w2 - tau * ray[5];
+    dist = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
+}
+
+// the cost of slot `slot` continuing in ray row `row` at the step's time
+__host__ __device__ inline float assoc_ray_pair_cost(const AssocRayArgs& a, int slot, int row, double t_step) {
+    double sum = 0.0, seen = -__builtin_inf();
+    int cnt = 0;
+    for (int j = 0; j < a.n_out; ++j) {
+        const double* st = assoc_slot_state(a, a.ws, slot, j);
+        const double tl = st[27];
+        if (tl != tl) continue;
+        if (tl > seen) seen = tl;
+        const double* ray;
+        if (!assoc_ray_load(a, row, j, ray)) continue;
+        double tau, d;
+        assoc_ray_foot(st, ray, t_step, tau, d);
+        if (!(tau > 0.0) || !(d <= a.clip)) d = a.clip;
+        sum += d * d;
+        ++cnt;
+    }
+    if (cnt < a.min_joints || cnt < 1 || seen < t_step - a.max_age) return __builtin_inff();
+    return (float)sqrt(sum / (double)cnt);
+}
+
+// after assoc_costs, in its order (the same thread owns the same entry): the columns of the ray rows
+__host__ __device__ inline void assoc_ray_costs(const AssocRayArgs& a, AssocLds& l, const AssocRayLds& r, int m, double t_step, int tid,
+                                                int nt) {
+    const int dq = nt / m, dr = nt - dq * m;
+    int t = tid / m, k = tid - t * m;
+    while (t < a.n_tracks) {
+        if (r.box_ray[k]) l.c[t * ASSOC_LD + k] = assoc_ray_pair_cost(a, t, l.box_row[k], t_step);
+        t += dq;
+        k += dr;
+        if (k >= m) { k -= m; ++t; }
+    }
+}
+
+// after assoc_apply: an unassigned ray row is unplaced, not dropped
+__host__ __device__ inline void assoc_ray_count(AssocLds& l, AssocRayLds& r, int m, int tid) {
+    if (tid != 0) return;
+    int unplaced = 0;
+    for (int k = 0; k < m; ++k) unplaced += l.box_row[k] >= 0 && r.box_ray[k] && l.box_slot[k] < 0;
+    r.n_unplaced += unplaced;
+    l.n_dropped -= unplaced;
+}
+
+// every assigned ray row becomes a point measurement per joint, one (box, joint) per item
+__host__ __device__ inline void assoc_ray_place(const AssocRayArgs& a, const AssocLds& l, const AssocRayLds& r, int m, double t_step,
+                                                int tid, int nt) {
+    for (int i = tid; i < m * a.n_out; i += nt) {
+        const int k = i / a.n_out, j = i - k * a.n_out;
+        const int slot = l.box_slot[k], row = l.box_row[k];
+        if (!r.box_ray[k] || slot < 0 || row < 0) continue;
+        const double* st = assoc_slot_state(a, a.ws, slot, j);
+        if (st[27] != st[27]) continue;
+        const double* ray;
+        if (!assoc_ray_load(a, row, j, ray)) continue;
+        double tau, dist;
+        assoc_ray_foot(st, ray, t_step, tau, dist);
+        if (!(tau > 0.0)) continue;
+        const size_t at = (size_t)row * a.n_out + j;
+        const double lateral = ray[6] * (tau * tau);
+        for (int c = 0; c < 3; ++c) {
+            a.poses_w[at * 3 + c] = (float)(ray[c] + tau * ray[3 + c]);
+            for (int e = 0; e < 3; ++e) {
+                const double dd = ray[3 + c] * ray[3 + e];
+                a.cov_w[at * 9 + c * 3 + e] = (float)(lateral * ((c == e ? 1.0 : 0.0) - dd) + a.depth_var * dd);
+            }
+        }
+        a.ray_depth[at] = (float)tau;
+    }
+}
+
+__host__ __device__ inline void assoc_ray_finish(const AssocRayArgs& a, const AssocRayLds& r, int tid) {
+    if (tid == 0) a.n_unplaced[0] = r.n_unplaced;
+}
+
+template <bool OPTIMAL>
+__global__ __launch_bounds__(ASSOC_THREADS) void associate_tracks_rays_kernel(AssocRayArgs a) {
+    __shared__ AssocLds l;
+    __shared__ AssocRayLds r;
+    __shared__ AssocOptLds o;                              // referenced by the optimal instantiation only
+    __shared__ AssocCand wave_best[ASSOC_THREADS / 64];
+    __shared__ AssocCandD wave_best_d[2][ASSOC_THREADS / 64];
+    const int tid = threadIdx.x, nt = ASSOC_THREADS;
+    assoc_begin(a, l, tid, nt);
+    assoc_ray_begin(a, r, tid, nt);
+    __syncthreads();
+    double t_first = 0.0;
+    const bool have_first = assoc_first_time(a, t_first);
+    assoc_retire(a, l, have_first, t_first, tid, nt);
+    __syncthreads();
+    int turn = 0;
+    for (int s = 0; s < a.n_steps; ++s) {                  // every branch below is taken by all threads or by none
+        int lo, m;
+        double t_step;
+        assoc_step_range(a, s, lo, m);
+        if (!assoc_step_time(a, lo, m, t_step)) continue;
+        assoc_step_boxes(a, l, lo, m, tid, nt);
+        assoc_ray_step_boxes(a, l, r, m, tid, nt);
+        if constexpr (OPTIMAL) assoc_opt_begin(a, o, m, tid, nt);
+        __syncthreads();
+        assoc_costs(a, l, m, t_step, tid, nt);
+        assoc_ray_costs(a, l, r, m, t_step, tid, nt);
+        __syncthreads();
+        if constexpr (OPTIMAL) {
+            for (int k = 0; k < m; ++k) {
+                AssocPath p = assoc_opt_root(a, o, k, tid, nt);
+                for (int visit = 0; visit <= a.n_tracks && p.end == -2; ++visit) {
+                    AssocCandD best = assoc_opt_relax(a, l, o, p, tid, nt);
+                    for (int off = 32; off > 0; off >>= 1) {
+                        const AssocCandD other = {__shfl_xor(best.v, off), __shfl_xor(best.idx, off)};
+                        if (assoc_candd_less(other, best)) best = other;
+                    }
+                    if ((tid & 63) == 0) wave_best_d[turn][tid >> 6] = best;
+                    __syncthreads();
+                    best = wave_best_d[turn][0];
+                    for (int w = 1; w < ASSOC_THREADS / 64; ++w)
+                        if (assoc_candd_less(wave_best_d[turn][w], best)) best = wave_best_d[turn][w];
+                    turn ^= 1;
+                    assoc_opt_advance(a, o, p, best);      // the same value in every thread
+                }
+                assoc_opt_duals(a, o, p, k, tid, nt);
+                __syncthreads();                           // the duals read slot_box before the path rewrites it
+                assoc_opt_augment(a, o, p, k, tid);
+                __syncthreads();
+            }
+            assoc_opt_pairs(a, l, o, m, tid, nt);
+            __syncthreads();
+        } else {
+            const int rounds = a.n_tracks < m ? a.n_tracks : m;
+            for (int round = 0; round < rounds; ++round) {
+                AssocCand best = assoc_scan(l, a.n_tracks, m, tid, nt);
+                for (int off = 32; off > 0; off >>= 1) {
+                    const AssocCand other = {__shfl_xor(best.v, off), __shfl_xor(best.idx, off)};
+                    if (assoc_cand_less(other, best)) best = other;
+                }
+                if ((tid & 63) == 0) wave_best[tid >> 6] = best;
+                __syncthreads();
+                best = wave_best[0];
+                for (int w = 1; w < ASSOC_THREADS / 64; ++w)
+                    if (assoc_cand_less(wave_best[w], best)) best = wave_best[w];
+                if (!(best.v < a.max_cost)) break;         // the same value in every thread
+                assoc_strike(l, a.n_tracks, m, best, tid, nt);
+                __syncthreads();                           // also: wave_best is read before it is written again
+            }
+        }
+        assoc_births(a, l, m, tid, nt);
+        __syncthreads();
+        assoc_apply(a, l, m, tid, nt);
+        __syncthreads();
+        assoc_ray_count(l, r, m, tid);
+        assoc_ray_place(a, l, r, m, t_step, tid, nt);
+        __syncthreads();
+        assoc_filter(a, l, m, tid, nt);
+        __syncthreads();                                   // the working state and the box arrays, before the next step
+    }
+    assoc_starts(a, l, tid, nt);
+    __syncthreads();
+    for (int s = 0; s < a.n_steps; ++s) {
+        int lo, m;
+        assoc_step_range(a, s, lo, m);
+        if (m == 0) continue;
+        assoc_group_step(a, l, lo, m, tid, nt);
+        __syncthreads();
+    }
+    assoc_finish(a, l, tid, nt);
+    assoc_ray_finish(a, r, tid);
+}
+
+AssocRayArgs make_assoc_ray_args(const AssocArgs& base, float* poses, float* cov, const int* single_box, const double* rays,
+                                 double depth_sigma_mm, float* ray_depth, int* n_unplaced) {
+    AssocRayArgs a;
+    static_cast<AssocArgs&>(a) = base;
+    a.poses_w = poses; a.cov_w = cov; a.single_box = single_box; a.rays = rays;
+    a.depth_var = depth_sigma_mm * depth_sigma_mm; a.ray_depth = ray_depth; a.n_unplaced = n_unplaced;
+    return a;
+}
+
+int launch_associate_tracks_rays(float* poses, float* cov, const double* times, int n, const int* step_rows, int n_step_rows,
+                                 const int* step_starts, int n_steps, int n_out, int measurement, double q, double r_floor,
+                                 double cov_scale, double v0, double gate, float max_cost_mm, double clip_mm, int min_joints,
+                                 double max_age_s, double* state, int n_tracks, int* ids, int* next_id, void* workspace, int* track_index,
+                                 int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new, int* n_dropped,
+                                 int assignment, const int* single_box, const double* rays, double depth_sigma_mm, float* ray_depth,
+                                 int* n_unplaced, hipStream_t stream) {
+    if (note_kernel("%s", assignment ? "associate_tracks_rays_optimal" : "associate_tracks_rays")) return METRO_OK;
+    const AssocArgs base = make_assoc_args(poses, cov, times, n, step_rows, n_step_rows, step_starts, n_steps, n_out, measurement, q,
+                                           r_floor, cov_scale, v0, gate, max_cost_mm, clip_mm, min_joints, max_age_s, state, n_tracks,
+                                           ids, next_id, static_cast<double*>(workspace), track_index, track_id, cost_out, rows_out,
+                                           starts_out, n_new, n_dropped);
+    const AssocRayArgs a = make_assoc_ray_args(base, poses, cov, single_box, rays, depth_sigma_mm, ray_depth, n_unplaced);
+    if (assignment) {
+        hipLaunchKernelGGL(associate_tracks_rays_kernel<true>, dim3(1), dim3(ASSOC_THREADS), 0, stream, a);
+        return launch_status("associate_tracks_rays_optimal");
+    }
+    hipLaunchKernelGGL(associate_tracks_rays_kernel<false>, dim3(1), dim3(ASSOC_THREADS), 0, stream, a);
+    return launch_status("associate_tracks_rays");
+}
+
 }  // namespace metro

@@ -701,6 +701,44 @@ int metro_person_steps(const int32_t* d_rows, int32_t n_rows, const int32_t* d_s
                                static_cast<hipStream_t>(stream));
 }
 
+int metro_person_steps_labels(const int32_t* d_person_index, const int32_t* d_n_persons, int32_t n, const int32_t* d_box_step,
+                              int32_t n_boxes, const double* d_step_times, int32_t n_steps, int32_t* d_person_step_out,
+                              double* d_person_times_out, int32_t* d_step_rows_out, int32_t* d_step_starts_out,
+                              int32_t* d_single_box_out, void* stream) {
+    METRO_CHECK_ARG(n >= 0 && n_boxes >= 0 && n_steps >= 0, "person_steps_labels: negative size (persons %d, boxes %d, steps %d)", n,
+                    n_boxes, n_steps);
+    METRO_CHECK_ARG(n <= METRO_MATCH_MAX_BOXES, "person_steps_labels: %d persons (at most %d)", n, METRO_MATCH_MAX_BOXES);
+    if (n == 0) return METRO_OK;
+    METRO_CHECK_ARG(d_n_persons && d_person_step_out && d_person_times_out && d_step_rows_out && d_step_starts_out && d_single_box_out,
+                    "person_steps_labels: NULL n_persons / output pointer");
+    METRO_CHECK_ARG(n_boxes == 0 || (d_person_index && d_box_step), "person_steps_labels: %d boxes need person_index and box_step",
+                    n_boxes);
+    METRO_CHECK_ARG(n_steps == 0 || d_step_times, "person_steps_labels: %d steps need step_times", n_steps);
+    return launch_person_steps_labels(d_person_index, d_n_persons, n, d_box_step, n_boxes, d_step_times, n_steps, d_person_step_out,
+                                      d_person_times_out, d_step_rows_out, d_step_starts_out, d_single_box_out,
+                                      static_cast<hipStream_t>(stream));
+}
+
+int metro_person_rays(const float* d_coords01, const float* d_cov01, const MetroPlacement* d_records, int32_t m, const MetroSpec* spec,
+                      const int32_t* d_mirror, int32_t weights, const int32_t* d_single_box, int32_t n, int32_t n_views,
+                      double* d_rays_out, void* stream) {
+    METRO_CHECK_ARG(spec != nullptr, "person_rays: NULL spec");
+    METRO_CHECK_ARG(spec->n_joints_head >= 1 && spec->n_joints_head <= METRO_MAX_JOINTS && spec->n_joints_out >= 1 &&
+                        spec->n_joints_out <= METRO_MAX_JOINTS, "person_rays: joint counts out of range (<= %d)", METRO_MAX_JOINTS);
+    METRO_CHECK_ARG(weights == METRO_TRI_UNIFORM || weights == METRO_TRI_COVARIANCE,
+                    "person_rays: weights must be METRO_TRI_UNIFORM or METRO_TRI_COVARIANCE (got %d)", weights);
+    METRO_CHECK_ARG(n >= 0 && m >= 0, "person_rays: negative size (persons %d, crop rows %d)", n, m);
+    METRO_CHECK_ARG(n <= METRO_MATCH_MAX_BOXES, "person_rays: %d persons (at most %d)", n, METRO_MATCH_MAX_BOXES);
+    METRO_CHECK_ARG(n_views >= 1 && n_views <= METRO_MAX_VIEWS, "person_rays: %d views (1 to %d)", n_views, METRO_MAX_VIEWS);
+    METRO_CHECK_ARG((int64_t)m == (int64_t)n * n_views, "person_rays: %d crop rows are not %d boxes of %d views", m, n, n_views);
+    if (n == 0) return METRO_OK;
+    METRO_CHECK_ARG(d_coords01 && d_records && d_mirror && d_single_box && d_rays_out,
+                    "person_rays: NULL coords01 / records / mirror / single_box / rays_out pointer");
+    METRO_CHECK_ARG(weights != METRO_TRI_COVARIANCE || d_cov01, "person_rays: METRO_TRI_COVARIANCE reads cov01: NULL");
+    return launch_person_rays(d_coords01, d_cov01, d_records, m, *spec, d_mirror, weights, d_single_box, n, n_views, d_rays_out,
+                              static_cast<hipStream_t>(stream));
+}
+
 size_t metro_smooth_tracks_workspace_bytes(int32_t n_rows, int32_t n_joints_out) {
     return smooth_tracks_workspace_bytes(n_rows, n_joints_out);
 }
@@ -735,14 +773,10 @@ int metro_smooth_tracks(const float* d_poses, const float* d_cov, const double* 
                                 d_used_out, static_cast<hipStream_t>(stream));
 }
 
-// the argument checks of both association entries, then the launch of one
-static int associate_tracks_entry(bool optimal, const float* d_poses, const float* d_cov, const double* d_times, int32_t n,
-                                  const int32_t* d_step_rows, int32_t n_step_rows, const int32_t* d_step_starts, int32_t n_steps,
-                                  const MetroSpec* spec, int32_t measurement, double q, double r_floor, double cov_scale,
-                                  double v0, double gate, float max_cost_mm, double clip_mm, int32_t min_joints, double max_age_s,
-                                  double* d_state, int32_t n_tracks, int32_t* d_ids, int32_t* d_next_id, void* d_workspace,
-                                  int32_t* d_track_index_out, int32_t* d_track_id_out, float* d_cost_out, int32_t* d_rows_out,
-                                  int32_t* d_starts_out, int32_t* d_n_new_out, int32_t* d_n_dropped_out, void* stream) {
+// the checks of the sizes and numbers that all association entries share
+static int associate_tracks_numbers(int32_t n, int32_t n_step_rows, int32_t n_steps, const MetroSpec* spec, int32_t measurement, double q,
+                                    double r_floor, double cov_scale, double v0, double gate, float max_cost_mm, double clip_mm,
+                                    int32_t min_joints, double max_age_s, int32_t n_tracks) {
     METRO_CHECK_ARG(spec != nullptr, "associate_tracks: NULL spec");
     METRO_CHECK_ARG(spec->n_joints_out >= 1 && spec->n_joints_out <= METRO_MAX_JOINTS,
                     "associate_tracks: n_joints_out %d out of range [1, %d]", spec->n_joints_out, METRO_MAX_JOINTS);
@@ -762,6 +796,20 @@ static int associate_tracks_entry(bool optimal, const float* d_poses, const floa
     METRO_CHECK_ARG(max_age_s >= 0.0, "associate_tracks: max_age_s must be >= 0 (got %g)", max_age_s);
     METRO_CHECK_ARG(min_joints >= 1 && min_joints <= spec->n_joints_out, "associate_tracks: min_joints %d outside [1, %d]",
                     min_joints, spec->n_joints_out);
+    return METRO_OK;
+}
+
+// the argument checks of both association entries, then the launch of one
+static int associate_tracks_entry(bool optimal, const float* d_poses, const float* d_cov, const double* d_times, int32_t n,
+                                  const int32_t* d_step_rows, int32_t n_step_rows, const int32_t* d_step_starts, int32_t n_steps,
+                                  const MetroSpec* spec, int32_t measurement, double q, double r_floor, double cov_scale,
+                                  double v0, double gate, float max_cost_mm, double clip_mm, int32_t min_joints, double max_age_s,
+                                  double* d_state, int32_t n_tracks, int32_t* d_ids, int32_t* d_next_id, void* d_workspace,
+                                  int32_t* d_track_index_out, int32_t* d_track_id_out, float* d_cost_out, int32_t* d_rows_out,
+                                  int32_t* d_starts_out, int32_t* d_n_new_out, int32_t* d_n_dropped_out, void* stream) {
+    if (const int rc = associate_tracks_numbers(n, n_step_rows, n_steps, spec, measurement, q, r_floor, cov_scale, v0, gate, max_cost_mm,
+                                                clip_mm, min_joints, max_age_s, n_tracks))
+        return rc;
     if (n == 0 || n_step_rows == 0 || n_steps == 0) return METRO_OK;
     METRO_CHECK_ARG(d_poses && d_times && d_step_rows && d_step_starts && d_state && d_ids && d_next_id && d_workspace &&
                         d_track_index_out && d_track_id_out && d_cost_out && d_rows_out && d_starts_out && d_n_new_out &&
@@ -804,6 +852,39 @@ int metro_associate_tracks_optimal(const float* d_poses, const float* d_cov, con
                                   measurement, q, r_floor, cov_scale, v0, gate, max_cost_mm, clip_mm, min_joints, max_age_s, d_state,
                                   n_tracks, d_ids, d_next_id, d_workspace, d_track_index_out, d_track_id_out, d_cost_out, d_rows_out,
                                   d_starts_out, d_n_new_out, d_n_dropped_out, stream);
+}
+
+int metro_associate_tracks_rays(float* d_poses, float* d_cov, const double* d_times, int32_t n, const int32_t* d_step_rows,
+                                int32_t n_step_rows, const int32_t* d_step_starts, int32_t n_steps, const MetroSpec* spec,
+                                int32_t measurement, double q, double r_floor, double cov_scale, double v0, double gate,
+                                float max_cost_mm, double clip_mm, int32_t min_joints, double max_age_s, double* d_state,
+                                int32_t n_tracks, int32_t* d_ids, int32_t* d_next_id, void* d_workspace, int32_t* d_track_index_out,
+                                int32_t* d_track_id_out, float* d_cost_out, int32_t* d_rows_out, int32_t* d_starts_out,
+                                int32_t* d_n_new_out, int32_t* d_n_dropped_out, int32_t assignment, const int32_t* d_single_box,
+                                const double* d_rays, double depth_sigma_mm, float* d_ray_depth_out, int32_t* d_n_unplaced_out,
+                                void* stream) {
+    if (const int rc = associate_tracks_numbers(n, n_step_rows, n_steps, spec, measurement, q, r_floor, cov_scale, v0, gate, max_cost_mm,
+                                                clip_mm, min_joints, max_age_s, n_tracks))
+        return rc;
+    METRO_CHECK_ARG(measurement == METRO_SMOOTH_COVARIANCE,
+                    "associate_tracks_rays: measurement must be METRO_SMOOTH_COVARIANCE (an isotropic R ignores the ray's shape)");
+    METRO_CHECK_ARG(assignment == 0 || assignment == 1, "associate_tracks_rays: assignment must be 0 (greedy) or 1 (optimal), got %d",
+                    assignment);
+    METRO_CHECK_ARG(std::isfinite(depth_sigma_mm) && depth_sigma_mm > 0.0,
+                    "associate_tracks_rays: depth_sigma_mm must be finite and > 0 (got %g)", depth_sigma_mm);
+    METRO_CHECK_ARG((int64_t)n * spec->n_joints_out * 9 <= INT32_MAX, "associate_tracks_rays: %d pose rows overflow int32", n);
+    if (n == 0 || n_step_rows == 0 || n_steps == 0) return METRO_OK;
+    METRO_CHECK_ARG(d_poses && d_cov && d_times && d_step_rows && d_step_starts && d_state && d_ids && d_next_id && d_workspace &&
+                        d_track_index_out && d_track_id_out && d_cost_out && d_rows_out && d_starts_out && d_n_new_out &&
+                        d_n_dropped_out,
+                    "associate_tracks_rays: NULL poses / cov / times / steps / table / workspace / output pointer");
+    METRO_CHECK_ARG(d_single_box && d_rays && d_ray_depth_out && d_n_unplaced_out,
+                    "associate_tracks_rays: NULL single_box / rays / ray_depth_out / n_unplaced_out pointer");
+    return launch_associate_tracks_rays(d_poses, d_cov, d_times, n, d_step_rows, n_step_rows, d_step_starts, n_steps, spec->n_joints_out,
+                                        measurement, q, r_floor, cov_scale, v0, gate, max_cost_mm, clip_mm, min_joints, max_age_s,
+                                        d_state, n_tracks, d_ids, d_next_id, d_workspace, d_track_index_out, d_track_id_out, d_cost_out,
+                                        d_rows_out, d_starts_out, d_n_new_out, d_n_dropped_out, assignment, d_single_box, d_rays,
+                                        depth_sigma_mm, d_ray_depth_out, d_n_unplaced_out, static_cast<hipStream_t>(stream));
 }
 
 const char* metro_last_error(void) { return metro::get_error(); }

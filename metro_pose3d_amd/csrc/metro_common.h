@@ -491,6 +491,13 @@ int launch_cluster_views(const float* cost, int n, int n_views, float max_cost, 
 int launch_person_steps(const int* rows, int n_rows, const int* starts, const int* n_persons, int n, int n_views, const int* box_step,
                         int n_boxes, const double* step_times, int n_steps, int* person_step, double* person_times, int* step_rows,
                         int* step_starts, hipStream_t stream);
+// the same from the persons' labels, with a step for the persons one camera sees and their box (world_tracks.hip)
+int launch_person_steps_labels(const int* person_index, const int* n_persons, int n, const int* box_step, int n_boxes,
+                               const double* step_times, int n_steps, int* person_step, double* person_times, int* step_rows,
+                               int* step_starts, int* single_box, hipStream_t stream);
+// the ray of every joint of a person seen by one camera (person_rays.hip)
+int launch_person_rays(const float* coords01, const float* cov01, const MetroPlacement* rec, int m, const MetroSpec& spec,
+                       const int* mirror, int weights, const int* single_box, int n, int n_views, double* rays, hipStream_t stream);
 // tracked poses smoothed over time: Kalman filter + RTS pass per (track, joint) (smooth_tracks.hip)
 size_t smooth_tracks_workspace_bytes(int n_rows, int n_out);
 int launch_smooth_tracks(const float* poses, const float* cov, const double* times, int n, const int* rows, int n_rows,
@@ -512,6 +519,14 @@ int launch_associate_tracks_optimal(const float* poses, const float* cov, const 
                                     double max_age_s, double* state, int n_tracks, int* ids, int* next_id, void* workspace, int* track_index,
                                     int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new, int* n_dropped,
                                     hipStream_t stream);
+// the same walk, either assignment, with ray rows that are costed against the slots and placed as point measurements
+int launch_associate_tracks_rays(float* poses, float* cov, const double* times, int n, const int* step_rows, int n_step_rows,
+                                 const int* step_starts, int n_steps, int n_out, int measurement, double q, double r_floor,
+                                 double cov_scale, double v0, double gate, float max_cost_mm, double clip_mm, int min_joints,
+                                 double max_age_s, double* state, int n_tracks, int* ids, int* next_id, void* workspace, int* track_index,
+                                 int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new, int* n_dropped,
+                                 int assignment, const int* single_box, const double* rays, double depth_sigma_mm, float* ray_depth,
+                                 int* n_unplaced, hipStream_t stream);
 // per-box crop geometry of full frames (look_at_boxes.hip)
 int launch_look_at_boxes(const double* boxes, const int32_t* frame_index, int n, int n_frames, const MetroFrameCamera* cameras,
                          int n_cameras, int side, MetroViewBase* out, int32_t* status, hipStream_t stream);

@@ -89,4 +89,55 @@ int launch_person_steps(const int* rows, int n_rows, const int* starts, const in
     return launch_status("person_steps");
 }
 
+// ---- the same from the persons' labels alone (metro_person_steps_labels): a person with ONE box gets a step too ----
+// metro_cluster_views leaves the group of a person seen by one camera empty, so person_steps_kernel gives it no step.  Here
+// thread p walks person_index [n_boxes] itself: step[p] = the smallest valid box_step[b] over the boxes b with
+// person_index[b] == p (for a person with several boxes the value person_steps_assign finds in its group), and
+// single_box[p] = that box if the person has exactly one box and it has a valid step, else -1 (-1 also for p >= n_persons[0]).  A label outside [0, n) belongs to
+// nobody; a step outside [0, n_steps) is skipped.  Rank and starts are person_steps_kernel's own functions.
+struct PersonLabelsArgs : PersonStepsArgs {
+    const int* person_index;          // [n_boxes] the person of every box (metro_cluster_views)
+    int* single_box;                  // [n]
+};
+
+__host__ __device__ inline void person_labels_assign(const PersonLabelsArgs& a, int* step, int p) {
+    int best = -1, boxes = 0, box = -1;
+    if (p < a.n_persons[0]) {
+        for (int b = 0; b < a.n_boxes; ++b) {
+            if (a.person_index[b] != p) continue;
+            ++boxes;
+            const int s = a.box_step[b];
+            if ((unsigned)s >= (unsigned)a.n_steps) continue;
+            if (best < 0 || s < best) best = s;
+            box = b;
+        }
+    }
+    step[p] = best;
+    a.person_step[p] = best;
+    a.person_times[p] = best >= 0 ? a.step_times[best] : __builtin_nan("");
+    a.single_box[p] = boxes == 1 && best >= 0 ? box : -1;
+}
+
+__global__ __launch_bounds__(PERSON_STEPS_THREADS) void person_steps_labels_kernel(PersonLabelsArgs a) {
+    __shared__ int step[PERSON_STEPS_THREADS];
+    const int p = threadIdx.x;
+    if (p < a.n) person_labels_assign(a, step, p);
+    __syncthreads();
+    if (p < a.n) person_steps_rank(a, step, p);
+    person_steps_starts(a, step, p, PERSON_STEPS_THREADS);
+}
+
+int launch_person_steps_labels(const int* person_index, const int* n_persons, int n, const int* box_step, int n_boxes,
+                               const double* step_times, int n_steps, int* person_step, double* person_times, int* step_rows,
+                               int* step_starts, int* single_box, hipStream_t stream) {
+    if (note_kernel("person_steps_labels")) return METRO_OK;
+    PersonLabelsArgs a;
+    a.rows = nullptr; a.starts = nullptr; a.n_persons = n_persons; a.box_step = box_step; a.step_times = step_times;
+    a.person_step = person_step; a.person_times = person_times; a.step_rows = step_rows; a.step_starts = step_starts;
+    a.n = n; a.n_rows = 0; a.n_views = 1; a.n_boxes = n_boxes; a.n_steps = n_steps;
+    a.person_index = person_index; a.single_box = single_box;
+    hipLaunchKernelGGL(person_steps_labels_kernel, dim3(1), dim3(PERSON_STEPS_THREADS), 0, stream, a);
+    return launch_status("person_steps_labels");
+}
+
 }  // namespace metro

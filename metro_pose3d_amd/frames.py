@@ -50,6 +50,10 @@ the box centre, drops the lens distortion, squares the pixels and zooms so the b
                                           ids) and writes the CSR grouping on the device (time_steps: the CSR of the time
                                           steps; new_track_table: the tracks carried from call to call).  Nothing in the
                                           reference
+  follow_rig_poses_in_frames              follow_world_poses_in_frames (a calibrated rig's video followed in the world) in which
+                                          a person only ONE camera sees keeps feeding its track: metro_person_steps_labels,
+                                          metro_person_rays and metro_associate_tracks_rays cost its rays against the tracks
+                                          and place each joint on its ray as a measurement tight across the ray, wide along it
   predict_boxes_in_frames, frame_sizes    the boxes of the NEXT frames from the track table, for the frames between a
                                           detector's key frames: ONE metro_predict_boxes call advances every live track to
                                           each frame's time with the filter's own prediction, projects its joints through
@@ -1092,8 +1096,9 @@ def _world_poses(call: _Call, model_path, cameras, fi: np.ndarray, weights: str,
     metro_view_affinity and metro_cluster_views on the forward's outputs; the triangulation launch then runs over the upper
     bound of n persons and the count is read in the call's synchronisation.
     step_index (host int32 [n], with match): the affinity is gated by time step.  covariance: the triangulation launch also
-    writes the covariance of every joint.  then(spec, n_views, poses, covariance, rows, starts, n_persons): enqueued after the
-    triangulation, before the synchronisation, on the unsliced outputs over the n persons (with match and covariance)."""
+    writes the covariance of every joint.  then(spec, n_views, poses, covariance, rows, starts, n_persons, seen): enqueued after
+    the triangulation, before the synchronisation, on the unsliced outputs over the n persons (with match and covariance);
+    seen = (coords01, cov01, places, person_index), what the rays of a person one camera sees are built from."""
     from metro_pose3d_amd.heads import cluster_views, triangulate_joints, view_affinity_steps
     from metro_pose3d_amd.inference import _engine_for
     sk = _model_skeleton(model_path)
@@ -1127,7 +1132,8 @@ def _world_poses(call: _Call, model_path, cameras, fi: np.ndarray, weights: str,
         poses, n_rays, residual, *cov = triangulate_joints(coords01, cov01, places.reshape(-1), rows, starts, eng.spec, weights,
                                                            min_angle_deg, covariance)
         if covariance:
-            more = (cov[0], then(eng.spec, nv, poses, cov[0], rows, starts, n_persons) if then is not None else None)
+            seen = (coords01, cov01, places.reshape(-1), matched[0] if matched is not None else None)
+            more = (cov[0], then(eng.spec, nv, poses, cov[0], rows, starts, n_persons, seen) if then is not None else None)
         poses_v, keypoints_v = f32(m, sk.n_out, 3), f32(m, sk.n_out, 2)
         mirror = _upload(np.asarray(sk.out_mirror, np.int32), device)
         ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
@@ -1534,7 +1540,8 @@ def follow_world_poses_in_frames(frames, boxes, model_path, cameras, frame_index
     lives in one step: P counts persons per step.  With weights 'uniform' exactly meeting rays give a zero covariance;
     sigma_floor_mm keeps the measurement noise positive definite.
     A person seen by one camera only has NaN world joints and no step (person_step -1): it is in no step of the association,
-    stays untracked (track_index -1) and its track is bridged by the motion model until max_age_s.  A person seen by several
+    stays untracked (track_index -1) and its track is bridged by the motion model until max_age_s
+    (follow_rig_poses_in_frames is this call with such a person's rays fed to its track instead).  A person seen by several
     cameras none of whose joints could be triangulated is in its step, untracked and counted in n_dropped.
     One enqueue chain: match_poses_in_frames' own up to the forward, then, with no host work in between and all over the upper
     bound of n persons, metro_view_affinity_steps, metro_cluster_views, metro_triangulate_joints_cov, metro_person_steps,
@@ -1543,8 +1550,33 @@ def follow_world_poses_in_frames(frames, boxes, model_path, cameras, frame_index
     ValueError before any launch for more than 128 boxes or 64 frames, cameras=None, timestamps that are not finite or match
     neither frames nor boxes, capacity outside [1, 128], a tracks that is no table or has another joint count than the model,
     and whatever match_poses_in_frames and follow_poses_in_frames refuse of their keywords."""
-    from metro_pose3d_amd.heads import (MATCH_MAX_BOXES, associate_tracks, association_params, assignment_rule, matching_params,
-                                        person_steps, smooth_tracks, smoothing_params, triangulation_min_det)
+    return _follow_world(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity, match_max_cost_mm,
+                         match_clip_mm, match_min_joints, weights, min_angle_deg, max_cost_mm, clip_mm, min_joints, max_age_s, mode,
+                         measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, views, precision, check_finite,
+                         geometry, pixel_format, color_matrix, crop_dtype, assignment, 'skip', None)[0]
+
+
+SINGLE_VIEWS = ('rays', 'skip')
+
+
+def _follow_world(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity, match_max_cost_mm, match_clip_mm,
+                  match_min_joints, weights, min_angle_deg, max_cost_mm, clip_mm, min_joints, max_age_s, mode, measurement, accel_psd,
+                  sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, views, precision, check_finite, geometry, pixel_format,
+                  color_matrix, crop_dtype, assignment, single_view, ray_depth_sigma_mm):
+    """follow_world_poses_in_frames (single_view 'skip') and follow_rig_poses_in_frames -> (FollowedWorldPoses, None or
+    (single_view uint8 [P], ray_depth float32 [P, Jout], n_unplaced int32 [1]) of the 'rays' chain)."""
+    from metro_pose3d_amd.heads import (MATCH_MAX_BOXES, associate_tracks, associate_tracks_rays, association_params, assignment_rule,
+                                        matching_params, person_rays, person_steps, person_steps_labels, ray_depth_sigma,
+                                        smooth_tracks, smoothing_params, triangulation_min_det)
+    if not isinstance(single_view, str) or single_view not in SINGLE_VIEWS:
+        raise ValueError(f"single_view must be 'rays' or 'skip', got {single_view!r}")
+    with_rays = single_view == 'rays'
+    if ray_depth_sigma_mm is not None:
+        ray_depth_sigma(ray_depth_sigma_mm)
+    if with_rays:
+        if measurement == 'isotropic':
+            raise ValueError("single_view='rays' needs measurement='covariance': an isotropic R would ignore the ray's shape and "
+                             'pin the depth along it')
     assignment_rule(assignment)
     triangulation_min_det(weights, min_angle_deg)
     matching_params(match_clip_mm, match_min_joints, match_max_cost_mm)
@@ -1575,13 +1607,24 @@ def follow_world_poses_in_frames(frames, boxes, model_path, cameras, frame_index
     device = _call_device(call.boxes, call.frames)
     tracks = new_track_table(capacity, sk.n_out, device) if tracks is None else TrackTable(*tracks)
 
-    def then(spec, n_views, poses, cov, rows, starts, n_persons):
-        person_step, person_times, step_rows, step_starts = person_steps(rows, starts, n_persons, box_step, step_times, n_views)
-        found = associate_tracks(poses, cov, person_times, step_rows, step_starts, tracks.state, tracks.ids, tracks.next_id,
-                                 max_cost_mm, clip_mm, min_joints, max_age_s, measurement, accel_psd, sigma_floor_mm, cov_scale,
-                                 initial_speed_mm_s, gate, assignment)
+    def then(spec, n_views, poses, cov, rows, starts, n_persons, seen):
+        if with_rays:
+            coords01, cov01, places, labels = seen
+            person_step, person_times, step_rows, step_starts, single_box = person_steps_labels(labels, n_persons, box_step, step_times)
+            rays = person_rays(coords01, cov01, places, single_box, spec, n_views, weights)
+            found = associate_tracks_rays(poses, cov, person_times, step_rows, step_starts, tracks.state, tracks.ids, tracks.next_id,
+                                          single_box, rays, max_cost_mm, clip_mm, min_joints, max_age_s, accel_psd, sigma_floor_mm,
+                                          cov_scale, initial_speed_mm_s, gate, assignment, ray_depth_sigma_mm)
+            poses, cov = found.poses, found.covariance      # the triangulation's own stay as they are
+            extra = ((single_box >= 0).to(torch.uint8), found.ray_depth, found.n_unplaced)
+        else:
+            person_step, person_times, step_rows, step_starts = person_steps(rows, starts, n_persons, box_step, step_times, n_views)
+            found = associate_tracks(poses, cov, person_times, step_rows, step_starts, tracks.state, tracks.ids, tracks.next_id,
+                                     max_cost_mm, clip_mm, min_joints, max_age_s, measurement, accel_psd, sigma_floor_mm, cov_scale,
+                                     initial_speed_mm_s, gate, assignment)
+            extra = None
         return person_step, found, smooth_tracks(poses, cov, person_times, found.rows, found.starts, mode, measurement, accel_psd,
-                                                 sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, tracks.state)
+                                                 sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, tracks.state), extra
 
     match = (float(match_max_cost_mm), float(match_clip_mm), None if match_min_joints is None else int(match_min_joints))
     world, matched, (cov, followed) = _world_poses(call, model_path, cameras, fi, weights, min_angle_deg, match=match,
@@ -1592,11 +1635,78 @@ def follow_world_poses_in_frames(frames, boxes, model_path, cameras, frame_index
         f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=device)
         smoothed = SmoothedWorldPoses(f32(0, sk.n_out, 3), f32(0, sk.n_out, 3), f32(0, sk.n_out, 3, 3),
                                       torch.zeros((0, sk.n_out), dtype=torch.uint8, device=device), tracks.state)
-        return FollowedWorldPoses(*matched, world, cov, i32(0), i32(0), i32(0), f32(0), i32(1), i32(1), tracks, smoothed)
-    person_step, found, (poses, velocity, covariance, used) = followed
+        return FollowedWorldPoses(*matched, world, cov, i32(0), i32(0), i32(0), f32(0), i32(1), i32(1), tracks, smoothed), None
+    person_step, found, (poses, velocity, covariance, used), extra = followed
     smoothed = SmoothedWorldPoses(poses[:p], velocity[:p], covariance[:p], used[:p], tracks.state)
+    if extra is not None:
+        extra = (extra[0][:p], extra[1][:p], extra[2])
     return FollowedWorldPoses(*matched, world, cov, person_step[:p], found.track_index[:p], found.track_id[:p], found.cost[:p],
-                              found.n_new, found.n_dropped, tracks, smoothed)
+                              found.n_new, found.n_dropped, tracks, smoothed), extra
+
+
+class FollowedRigPoses(NamedTuple):
+    """What follow_rig_poses_in_frames returns: FollowedWorldPoses' fields in their order, then the single-view ones."""
+    person_index: torch.Tensor
+    cost: torch.Tensor
+    n_pairs: torch.Tensor
+    world: WorldPoses                    # the triangulated poses; NaN for a person one camera sees, placed or not
+    world_covariance: torch.Tensor
+    person_step: torch.Tensor            # int32 [P]: with single_view='rays' a person one camera sees has its step too
+    track_index: torch.Tensor
+    track_id: torch.Tensor
+    track_cost: torch.Tensor             # float32 [P] mm: for a person one camera sees, the RMS distance of the track's joints from its rays
+    n_new: torch.Tensor
+    n_dropped: torch.Tensor              # int32 [1]: persons SEVERAL cameras see left untracked
+    tracks: TrackTable
+    smoothed: SmoothedWorldPoses         # of a person one camera sees: the track's joints updated across the rays, bridged along them
+    single_view: torch.Tensor            # uint8 [P]: 1 where the person is seen by one camera and went into the association as rays
+    ray_depth: torch.Tensor              # float32 [P, Jout] mm: the depth along its ray at which a joint was placed, NaN elsewhere
+    n_unplaced: torch.Tensor             # int32 [1]: persons one camera sees that no track continued in (never born: no depth)
+
+
+def follow_rig_poses_in_frames(frames, boxes, model_path, cameras, frame_index, timestamps, tracks: Optional[TrackTable] = None,
+                               capacity: int = 64, match_max_cost_mm: float = 200.0, match_clip_mm: float = 500.0,
+                               match_min_joints: Optional[int] = None, weights: str = 'covariance', min_angle_deg: float = 2.0,
+                               max_cost_mm: float = 300.0, clip_mm: float = 600.0, min_joints: Optional[int] = None,
+                               max_age_s: float = 1.0, mode: str = 'smooth', measurement: str = 'covariance',
+                               accel_psd: float = 4e6, sigma_floor_mm: float = 1.0, cov_scale: float = 1.0,
+                               initial_speed_mm_s: float = 2000.0, gate=None, views=None, precision: Optional[str] = None,
+                               check_finite: Optional[bool] = None, geometry: str = 'auto', pixel_format: str = 'rgb',
+                               color_matrix: str = 'bt601', crop_dtype: str = 'float32', assignment: str = 'greedy',
+                               single_view: str = 'rays', ray_depth_sigma_mm: float = 1000.0) -> FollowedRigPoses:
+    """follow_world_poses_in_frames in which a person that only ONE camera sees keeps feeding its track -> FollowedRigPoses.
+    Every parameter up to `assignment` is follow_world_poses_in_frames', with its default.
+
+    There, such a person has NaN world joints and no step: its track coasts on the motion model while a camera looks straight at
+    the person, and after max_age_s it is retired and the person returns under a new id.  But one camera gives a ray per joint
+    and a lateral variance per ray, which pins the joint in two of three directions; the track's own prediction supplies the
+    third.  single_view='rays' (the default): the person gets its step (metro_person_steps_labels in place of
+    metro_person_steps) and its rays (metro_person_rays), and metro_associate_tracks_rays in place of the association entry
+    costs it against the tracks by the distance of their predicted joints from the rays, assigns it among the triangulated
+    persons under either rule, and places every joint at the foot of the perpendicular from the predicted joint onto its ray
+    with R = sigma2 tau^2 (I - d d^T) + ray_depth_sigma_mm^2 d d^T (heads.associate_tracks_rays has the model), which
+    metro_smooth_tracks, unchanged, then reads.  The association runs on copies of the triangulation's poses and covariance:
+    world.poses and world_covariance stay the triangulation's own, NaN for such a person; smoothed holds its updated joints.
+    The cost is blind along the ray, and such a person never STARTS a track (no depth): unassigned it is untracked and counted
+    in n_unplaced.  Still one synchronisation, and no host work after the forward.
+    single_view='skip': exactly the chain follow_world_poses_in_frames enqueues and its tensors; single_view all 0, ray_depth
+    NaN, n_unplaced 0.
+    ray_depth_sigma_mm = 1000 is a design choice, not a measurement (heads.associate_tracks_rays has the reasoning): large
+    against the predicted position variance along the ray, so the depth stays the motion model's; small enough that the fp32
+    rounding of R stays far below sigma_floor_mm^2.
+    ValueError before any launch for whatever follow_world_poses_in_frames refuses, an unknown single_view, ray_depth_sigma_mm
+    not finite and > 0, and measurement='isotropic' together with 'rays'."""
+    out, extra = _follow_world(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity, match_max_cost_mm,
+                               match_clip_mm, match_min_joints, weights, min_angle_deg, max_cost_mm, clip_mm, min_joints, max_age_s,
+                               mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, views, precision,
+                               check_finite, geometry, pixel_format, color_matrix, crop_dtype, assignment, single_view,
+                               ray_depth_sigma_mm)
+    if extra is None:
+        p, device = len(out.person_step), out.person_step.device
+        extra = (torch.zeros((p,), dtype=torch.uint8, device=device),
+                 torch.full((p, out.smoothed.poses.shape[1]), float('nan'), dtype=torch.float32, device=device),
+                 torch.zeros((1,), dtype=torch.int32, device=device))
+    return FollowedRigPoses(*out, *extra)
 
 
 # ---- the boxes of the next frames from the track table: crops between the key frames of a detector (metro_predict_boxes) ----
@@ -1689,6 +1799,8 @@ class Follower:
     coords='world', in the world) or follow_world_poses_in_frames (world=True: a calibrated rig) with the model, the
     cameras, the assignment rule and every keyword fixed at construction, and the table of tracks kept between calls.
 
+    Follower(..., world=True, single_view='rays' or 'skip'): follow_rig_poses_in_frames instead, in which a person one camera
+    sees keeps feeding its track; `keywords` then also takes ray_depth_sigma_mm.  Without single_view it is what it was.
     Follower(model_path, cameras, world=False, assignment='greedy', capacity=64, **keywords): `keywords` are those of the
     chosen call other than frames, boxes, model_path, cameras, frame_index, timestamps, tracks and capacity; an unknown name
     is a TypeError here, and the values are checked here by the calls' own validators (heads.association_params,
@@ -1699,14 +1811,21 @@ class Follower:
     .predict(frame_sizes, timestamps, **keywords) -> predict_boxes_in_frames on .tracks with the follower's cameras and
     coordinates.  .reset() drops the table: the next call starts new tracks from id 0."""
 
-    def __init__(self, model_path, cameras, world: bool = False, assignment: str = 'greedy', capacity: int = 64, **keywords):
+    def __init__(self, model_path, cameras, world: bool = False, assignment: str = 'greedy', capacity: int = 64,
+                 single_view: Optional[str] = None, **keywords):
         import inspect
-        from metro_pose3d_amd.heads import (association_params, assignment_rule, matching_params, smoothing_params,
+        from metro_pose3d_amd.heads import (association_params, assignment_rule, matching_params, ray_depth_sigma, smoothing_params,
                                             triangulation_min_det)
         if not isinstance(world, (bool, np.bool_)):
             raise ValueError(f'world must be True or False, got {world!r}')
-        params = inspect.signature(follow_world_poses_in_frames if world else follow_poses_in_frames).parameters
-        defaults = {k: p.default for k, p in params.items() if k not in _FOLLOWER_GIVEN}
+        if single_view is not None:
+            if not world:
+                raise ValueError('single_view belongs to a calibrated rig: it needs world=True')
+            if not isinstance(single_view, str) or single_view not in SINGLE_VIEWS:
+                raise ValueError(f"single_view must be 'rays' or 'skip', got {single_view!r}")
+        call = follow_poses_in_frames if not world else follow_world_poses_in_frames if single_view is None else follow_rig_poses_in_frames
+        params = inspect.signature(call).parameters
+        defaults = {k: p.default for k, p in params.items() if k not in _FOLLOWER_GIVEN + ('single_view',)}
         unknown = [k for k in keywords if k not in defaults]
         if unknown:
             raise TypeError(f"Follower(world={bool(world)}) got an unexpected keyword {unknown[0]!r}: it takes "
@@ -1722,15 +1841,23 @@ class Follower:
             triangulation_min_det(kw['weights'], kw['min_angle_deg'])
             if cameras is None:
                 raise ValueError('cameras: following in the world needs the calibrated cameras of the rig')
+            if single_view is not None:
+                ray_depth_sigma(kw['ray_depth_sigma_mm'])
+                if single_view == 'rays' and kw['measurement'] == 'isotropic':
+                    raise ValueError("single_view='rays' needs measurement='covariance'")
         elif kw['scale_recovery'] == 'metro':
             raise ValueError("scale_recovery='metro' returns root-relative poses, in which all persons coincide: following needs "
                              "absolute poses ('bone-lengths' or 'true-root-depth')")
         self.model_path, self.cameras, self.world = model_path, cameras, bool(world)
-        self.assignment, self.capacity, self.keywords = assignment, int(capacity), kw
+        self.assignment, self.capacity, self.keywords, self.single_view = assignment, int(capacity), kw, single_view
         self.tracks: Optional[TrackTable] = None
 
     def follow(self, frames, boxes, frame_index, timestamps):
-        if self.world:
+        if self.world and self.single_view is not None:
+            out = follow_rig_poses_in_frames(frames, boxes, self.model_path, self.cameras, frame_index, timestamps, tracks=self.tracks,
+                                             capacity=self.capacity, assignment=self.assignment, single_view=self.single_view,
+                                             **self.keywords)
+        elif self.world:
             out = follow_world_poses_in_frames(frames, boxes, self.model_path, self.cameras, frame_index, timestamps, tracks=self.tracks,
                                                capacity=self.capacity, assignment=self.assignment, **self.keywords)
         else:

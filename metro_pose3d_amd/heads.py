@@ -379,6 +379,83 @@ def person_steps(rows, starts, n_persons, box_step, step_times, n_views: int = 1
     return person_step, person_times, step_rows, step_starts
 
 
+def person_steps_labels(person_index, n_persons, box_step, step_times):
+    """person_steps from the persons' labels alone, one metro_person_steps_labels launch (one workgroup): a person ONE camera
+    sees gets a step too.  person_index [n] and n_persons [1]: cluster_views' labels and count, device tensors, n <= 128;
+    box_step [n] (ints or a tensor) and step_times [S] as person_steps reads them.
+    -> (person_step, person_times, step_rows, step_starts) as person_steps returns them -- for a person with several boxes the
+    same values -- and single_box int32 [n]: the box of a person that has exactly one box, and a valid step; -1 for everyone
+    else.  Labels and steps out of range are skipped.  (A function of its own: person_steps' parameter list is pinned.)"""
+    if not isinstance(person_index, torch.Tensor) or not isinstance(n_persons, torch.Tensor):
+        raise ValueError('person_index and n_persons must be the device tensors cluster_views returned')
+    if person_index.dim() != 1 or n_persons.numel() != 1:
+        raise ValueError(f'person_index must be [n] and n_persons hold one count, got {tuple(person_index.shape)} and {n_persons.numel()}')
+    n = int(person_index.numel())
+    if n > MATCH_MAX_BOXES:
+        raise ValueError(f'{n} persons: matching takes at most {MATCH_MAX_BOXES}')
+    dev = person_index.device
+    person_index, n_persons = _i32(person_index, dev), _i32(n_persons, dev).reshape(-1)
+    box_step = _i32(box_step, dev).reshape(-1)
+    if box_step.numel() != n:
+        raise ValueError(f'box_step must hold one value per box ({n}), got {box_step.numel()}')
+    if not isinstance(step_times, torch.Tensor):
+        step_times = torch.from_numpy(np.ascontiguousarray(np.asarray(step_times, np.float64).reshape(-1)))
+    step_times = step_times.to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+    n_steps = int(step_times.numel())
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    person_step, step_rows, step_starts, single_box = i32(n), i32(n), i32(n_steps + 1), i32(n)
+    person_times = torch.empty((n,), dtype=torch.float64, device=dev)
+    if n == 0:
+        step_starts.zero_()
+        return person_step, person_times, step_rows, step_starts, single_box
+    check(_lib.load().metro_person_steps_labels(_p(person_index), _p(n_persons), n, _p(box_step), n, _p(step_times), n_steps,
+                                                _p(person_step), _p(person_times), _p(step_rows), _p(step_starts), _p(single_box),
+                                                _stream(dev)), 'metro_person_steps_labels')
+    return person_step, person_times, step_rows, step_starts, single_box
+
+
+PERSON_RAY_DOUBLES = 8               # per (person, joint): o (3), d (3), sigma2, the number of views used
+
+
+def person_rays(coords01: torch.Tensor, cov01: Optional[torch.Tensor], places: torch.Tensor, single_box: torch.Tensor,
+                spec: ModelSpec, n_views: int = 1, weights: str = 'covariance') -> torch.Tensor:
+    """The ray of every joint of the persons one camera sees, one metro_person_rays launch.  coords01 [m,J_head,3], cov01
+    [m,J_head,6] (weights 'covariance') and `places` (m MetroPlacement records, uint8) as triangulate_joints reads them,
+    m = n * n_views crop rows, box-major; single_box int32 [n] on the device (person_steps_labels): the one box of person p,
+    -1 none.  -> rays float64 [n,Jout,8] on the device: the optical centre o (3) of the box's crops, the unit direction d (3) --
+    the views' directions averaged with weights 1 ('uniform') or 1 / sigma2_v ('covariance'), the mirror joint for a flipped
+    view --, sigma2 (the lateral variance of the ray in normalised image units, 1 / sum (1 / sigma2_v); 0 with 'uniform') and the
+    number of views used.  All eight NaN where there is no ray: single_box -1, or no usable view."""
+    triangulation_min_det(weights, 2.0)
+    nj, n_out = spec.skeleton.n_head, spec.skeleton.n_out
+    if not isinstance(coords01, torch.Tensor) or coords01.dim() != 3 or tuple(coords01.shape[1:]) != (nj, 3):
+        raise ValueError(f'coords01 must be a tensor [m,{nj},3], got {tuple(getattr(coords01, "shape", ()))}')
+    m = coords01.shape[0]
+    n_views = _check_n_views(n_views, m)
+    n = m // n_views
+    if n > MATCH_MAX_BOXES:
+        raise ValueError(f'{n} boxes: matching takes at most {MATCH_MAX_BOXES}')
+    if weights == 'covariance' and (cov01 is None or tuple(cov01.shape) != (m, nj, 6)):
+        raise ValueError(f"weights='covariance' needs cov01 [{m},{nj},6], got {None if cov01 is None else tuple(cov01.shape)}")
+    need = m * C.sizeof(_lib.MetroPlacement)
+    if not isinstance(places, torch.Tensor) or places.dtype != torch.uint8 or places.numel() != need:
+        raise ValueError(f'places must be a uint8 tensor of {m} MetroPlacement records ({need} bytes)')
+    if not isinstance(single_box, torch.Tensor) or single_box.numel() != n:
+        raise ValueError(f'single_box must be a device tensor of one value per person ({n})')
+    dev = coords01.device
+    rays = torch.empty((n, n_out, PERSON_RAY_DOUBLES), dtype=torch.float64, device=dev)
+    if n == 0:
+        return rays
+    single_box = _i32(single_box, dev).reshape(-1)
+    coords01, places = coords01.to(torch.float32).contiguous(), places.contiguous()
+    cov01 = cov01.to(torch.float32).contiguous() if weights == 'covariance' else None
+    cs = spec.to_c(1)
+    mirror = torch.from_numpy(np.asarray(spec.skeleton.out_mirror, dtype=np.int32)).to(dev)
+    check(_lib.load().metro_person_rays(_p(coords01), _p(cov01), _p(places), m, C.byref(cs), _p(mirror), TRI_WEIGHTS[weights],
+                                        _p(single_box), n, n_views, _p(rays), _stream(dev)), 'metro_person_rays')
+    return rays
+
+
 SMOOTH_MODES = {'filter': _lib.METRO_SMOOTH_FILTER, 'smooth': _lib.METRO_SMOOTH_RTS}
 SMOOTH_MEASUREMENTS = {'isotropic': _lib.METRO_SMOOTH_ISOTROPIC, 'covariance': _lib.METRO_SMOOTH_COVARIANCE}
 TRACK_STATE_DOUBLES = 28             # per (track, joint): x (6), the upper triangle of P (21), t_last
@@ -532,6 +609,73 @@ def associate_tracks(poses: torch.Tensor, covariance: Optional[torch.Tensor], ti
     prediction within a few frames; 600 mm keeps one wild joint from deciding a pair; one second bridges a short occlusion
     without handing a long-gone track's slot history to a newcomer; half the joints keeps a cost from resting on a few.
     -> AssociatedTracks; its rows / starts and `state` go to smooth_tracks unchanged.  No boxes or no steps: no launch."""
+    return _associate_tracks(poses, covariance, times, step_rows, step_starts, state, ids, next_id, max_cost_mm, clip_mm, min_joints,
+                             max_age_s, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, assignment, None)
+
+
+class RayAssociatedTracks(NamedTuple):
+    """What associate_tracks_rays returns, all on the device: AssociatedTracks' fields, then the additions."""
+    track_index: torch.Tensor
+    track_id: torch.Tensor
+    cost: torch.Tensor
+    rows: torch.Tensor
+    starts: torch.Tensor
+    n_new: torch.Tensor
+    n_dropped: torch.Tensor              # int32 [1]: POINT rows left untracked; an untracked ray row counts in n_unplaced
+    working_state: torch.Tensor
+    poses: torch.Tensor                  # float32 [n, J, 3]: a copy of the given poses with the placed joints of the ray rows written
+    covariance: torch.Tensor             # float32 [n, J, 9]: likewise, their R; both go to smooth_tracks with rows / starts
+    ray_depth: torch.Tensor              # float32 [n, J] mm: the depth tau along the ray at which a joint was placed, NaN elsewhere
+    n_unplaced: torch.Tensor             # int32 [1]: ray rows no track continued in (a ray row is never born)
+
+
+def ray_depth_sigma(ray_depth_sigma_mm) -> float:
+    """Checks `ray_depth_sigma_mm` of associate_tracks_rays and frames.follow_rig_poses_in_frames."""
+    if not _is_number(ray_depth_sigma_mm) or not np.isfinite(ray_depth_sigma_mm) or not ray_depth_sigma_mm > 0:
+        raise ValueError(f'ray_depth_sigma_mm must be a finite number > 0 (mm), got {ray_depth_sigma_mm!r}')
+    return float(ray_depth_sigma_mm)
+
+
+def associate_tracks_rays(poses: torch.Tensor, covariance: torch.Tensor, times, step_rows, step_starts, state: torch.Tensor,
+                          ids: torch.Tensor, next_id: torch.Tensor, single_box: torch.Tensor, rays: torch.Tensor,
+                          max_cost_mm: float = 300.0, clip_mm: float = 600.0, min_joints: Optional[int] = None,
+                          max_age_s: float = 1.0, accel_psd: float = 4e6, sigma_floor_mm: float = 1.0, cov_scale: float = 1.0,
+                          initial_speed_mm_s: float = 2000.0, gate: Optional[float] = None, assignment: str = 'greedy',
+                          ray_depth_sigma_mm: float = 1000.0) -> RayAssociatedTracks:
+    """associate_tracks with RAY rows among the boxes, one metro_associate_tracks_rays launch (include/metro_hip.h has the
+    model): row b with single_box[b] >= 0 (person_steps_labels) is a person one camera sees, with no pose but one ray per
+    joint, rays [n,J,8] (person_rays).  Every other row, the table and every other keyword are associate_tracks'; the
+    measurement is 'covariance' (an isotropic R would ignore the ray's shape and pin the depth along it).
+    A ray row costs a slot the RMS over the joints of the distance of the slot's predicted joint from the ray (clip_mm behind
+    the camera) -- blind along the ray --, competes with the point rows in the one assignment (either rule), is never born (no
+    depth to start from; unassigned it counts in n_unplaced), and once assigned each of its joints is PLACED: the pose becomes
+    the foot of the perpendicular from the predicted joint onto the ray, at depth tau, and its covariance
+    R = sigma2 tau^2 (I - d d^T) + ray_depth_sigma_mm^2 d d^T, tight across the ray and wide along it (the linearised form of
+    a bearing measurement), which the unchanged filter step then reads.  The launch works on copies of `poses` and
+    `covariance` and returns them: smooth_tracks on them with rows / starts leaves the working state in `state`, bit for bit.
+    ray_depth_sigma_mm = 1000 is a design choice, not a measurement: the placed point has no innovation along the ray, so the
+    along-ray variance only has to be large against the predicted P there (tens of mm) for the update to leave the depth to
+    the motion model -- at 1 m the gain along the ray is below 1e-2 -- and small enough that the fp32 rounding of R's entries
+    (one ulp at 1e6 mm^2 is 0.06 mm^2) stays far below sigma_floor_mm^2 and the lateral variance.
+    -> RayAssociatedTracks."""
+    depth_sigma = ray_depth_sigma(ray_depth_sigma_mm)
+    if not isinstance(poses, torch.Tensor) or poses.dim() != 3:
+        raise ValueError(f'poses must be a tensor [n,J,3], got {tuple(getattr(poses, "shape", ()))}')
+    n, nj = int(poses.shape[0]), int(poses.shape[1])
+    if not isinstance(single_box, torch.Tensor) or single_box.numel() != n:
+        raise ValueError(f'single_box must be a device tensor of one value per pose row ({n})')
+    if not isinstance(rays, torch.Tensor) or rays.dtype != torch.float64 or tuple(rays.shape) != (n, nj, PERSON_RAY_DOUBLES):
+        raise ValueError(f'rays must be a float64 tensor [{n},{nj},{PERSON_RAY_DOUBLES}] (person_rays), got '
+                         f'{tuple(getattr(rays, "shape", ()))}')
+    return _associate_tracks(poses, covariance, times, step_rows, step_starts, state, ids, next_id, max_cost_mm, clip_mm, min_joints,
+                             max_age_s, 'covariance', accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, assignment,
+                             (single_box, rays, depth_sigma))
+
+
+def _associate_tracks(poses, covariance, times, step_rows, step_starts, state, ids, next_id, max_cost_mm, clip_mm, min_joints, max_age_s,
+                      measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, assignment, rays):
+    """associate_tracks (rays None) and associate_tracks_rays (rays = (single_box, rays, depth sigma): the launch writes copies
+    of poses and covariance)."""
     assignment_rule(assignment)
     params = smoothing_params('filter', measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate)
     association_params(max_cost_mm, clip_mm, min_joints, max_age_s)
@@ -573,14 +717,31 @@ def associate_tracks(poses: torch.Tensor, covariance: Optional[torch.Tensor], ti
     if n == 0 or n_step_rows == 0 or n_starts == 1:        # nothing to decide: no launch
         track_index.fill_(-1), track_id.fill_(-1), rows.fill_(-1), cost.fill_(float('nan'))
         starts.zero_(), n_new.zero_(), n_dropped.zero_()
-        return AssociatedTracks(track_index, track_id, cost, rows, starts, n_new, n_dropped, state.clone())
+        found = AssociatedTracks(track_index, track_id, cost, rows, starts, n_new, n_dropped, state.clone())
+        if rays is None:
+            return found
+        return RayAssociatedTracks(*found, poses.to(torch.float32).clone(), covariance.to(torch.float32).reshape(n, nj, 9).clone(),
+                                   torch.full((n, nj), float('nan'), dtype=torch.float32, device=dev), i32(1).zero_())
     lib = _lib.load()
     times = times.to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
     step_rows, step_starts = _i32(step_rows, dev).reshape(-1), _i32(step_starts, dev).reshape(-1)
-    poses = poses.to(torch.float32).contiguous()
-    cov = covariance.to(torch.float32).reshape(n, nj, 9).contiguous() if with_cov else None
     ws = torch.empty(lib.metro_associate_tracks_workspace_bytes(n_tracks, nj), dtype=torch.uint8, device=dev)
     cs = _lib.MetroSpec(n_joints_out=nj)
+    if rays is not None:
+        poses = poses.to(torch.float32).clone(memory_format=torch.contiguous_format)
+        cov = covariance.to(torch.float32).reshape(n, nj, 9).clone(memory_format=torch.contiguous_format)
+        single_box, ray, depth_sigma = _i32(rays[0], dev).reshape(-1), rays[1].contiguous(), rays[2]
+        ray_depth, n_unplaced = torch.empty((n, nj), dtype=torch.float32, device=dev), i32(1)
+        check(lib.metro_associate_tracks_rays(_p(poses), _p(cov), _p(times), n, _p(step_rows), n_step_rows, _p(step_starts),
+                                              n_starts - 1, C.byref(cs), *params[1:], float(max_cost_mm), float(clip_mm),
+                                              int(min_joints), float(max_age_s), _p(state), n_tracks, _p(ids), _p(next_id), _p(ws),
+                                              _p(track_index), _p(track_id), _p(cost), _p(rows), _p(starts), _p(n_new), _p(n_dropped),
+                                              int(assignment == 'optimal'), _p(single_box), _p(ray), depth_sigma, _p(ray_depth),
+                                              _p(n_unplaced), _stream(dev)), 'metro_associate_tracks_rays')
+        return RayAssociatedTracks(track_index, track_id, cost, rows, starts, n_new, n_dropped,
+                                   ws.view(torch.float64).view(n_tracks, nj, TRACK_STATE_DOUBLES), poses, cov, ray_depth, n_unplaced)
+    poses = poses.to(torch.float32).contiguous()
+    cov = covariance.to(torch.float32).reshape(n, nj, 9).contiguous() if with_cov else None
     entry = 'metro_associate_tracks_optimal' if assignment == 'optimal' else 'metro_associate_tracks'
     check(getattr(lib, entry)(_p(poses), _p(cov), _p(times), n, _p(step_rows), n_step_rows, _p(step_starts), n_starts - 1,
                               C.byref(cs), *params[1:], float(max_cost_mm), float(clip_mm), int(min_joints), float(max_age_s),
