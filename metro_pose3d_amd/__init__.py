@@ -19,7 +19,9 @@ Public surface (mirrors reference inference.py):
     predict_boxes_in_frames(tracks, cameras, frame_sizes, timestamps) -> the person boxes of the next frames from the
         table of tracks those two return (frame_sizes(frames): their sizes), for the frames a detector does not see
     Follower(model_path, cameras, world=False, assignment='greedy', ...) -> one of the two follow calls with its keywords
-        and its table of tracks kept from call to call: .follow(frames, boxes, frame_index, timestamps), .predict(...)
+        and its table of tracks kept from call to call: .follow(frames, boxes, frame_index, timestamps), .predict(...);
+        with world=True, learn_bones=True it also learns every followed person's bone lengths on the device, and
+        .bone_lengths_for(track_index, fallback) hands them to locate_poses_in_frames(bone_lengths=...) as a CUDA tensor
 plus the pieces under it: ModelSpec, Engine (plan + forward over libmetro_hip.so), the model
 container (save_model / load_model) and batch sharding over the GPUs of a node (dist).
 """

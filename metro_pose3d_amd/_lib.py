@@ -215,6 +215,9 @@ SIGNATURES = {
                                               C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float, C.c_double,
                                               C.c_int32, C.c_double, _P, C.c_int32] + [_P] * 10 +
                                     [C.c_int32, _P, _P, C.c_double, _P, _P, _P]),
+    'metro_track_bone_lengths': (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, _P,
+                                           C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32] +
+                                 [_P] * 6),
     'metro_predict_boxes': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32] + [C.c_double] * 7 +
                             [C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_double] + [_P] * 10),
     'metro_last_error': (C.c_char_p, []),

@@ -887,6 +887,36 @@ int metro_associate_tracks_rays(float* d_poses, float* d_cov, const double* d_ti
                                         depth_sigma_mm, d_ray_depth_out, d_n_unplaced_out, static_cast<hipStream_t>(stream));
 }
 
+int metro_track_bone_lengths(const float* d_poses, const float* d_cov, int32_t n, const int32_t* d_rows, int32_t n_rows,
+                             const int32_t* d_starts, int32_t n_tracks, const int32_t* d_ids, int32_t n_joints_out,
+                             const int32_t* d_edges, const int32_t* d_edge_mirror, int32_t n_edges, const double* d_fallback,
+                             int32_t min_count, double gate, double r_floor, double cov_scale, double min_length_mm, int32_t debias,
+                             int32_t symmetric, double* d_stats, int32_t* d_bone_ids, double* d_lengths_out, double* d_sigma_out,
+                             uint8_t* d_known_out, void* stream) {
+    METRO_CHECK_ARG(n_joints_out >= 1 && n_joints_out <= METRO_MAX_JOINTS, "track_bone_lengths: n_joints_out %d out of range [1, %d]",
+                    n_joints_out, METRO_MAX_JOINTS);
+    METRO_CHECK_ARG(n_edges >= 1 && n_edges <= METRO_MAX_JOINTS, "track_bone_lengths: %d edges (1 to %d)", n_edges, METRO_MAX_JOINTS);
+    METRO_CHECK_ARG(n_tracks >= 1 && n_tracks <= METRO_ASSOC_MAX, "track_bone_lengths: %d track slots (1 to %d)", n_tracks,
+                    METRO_ASSOC_MAX);
+    METRO_CHECK_ARG(n >= 0 && n_rows >= 0, "track_bone_lengths: negative size (pose rows %d, group rows %d)", n, n_rows);
+    METRO_CHECK_ARG(min_count >= 1, "track_bone_lengths: min_count must be >= 1 (got %d)", min_count);
+    METRO_CHECK_ARG(gate >= 0.0 && std::isfinite(gate), "track_bone_lengths: gate must be finite and >= 0, 0 for none (got %g)", gate);
+    METRO_CHECK_ARG(r_floor > 0.0 && std::isfinite(r_floor), "track_bone_lengths: r_floor must be finite and > 0 (got %g)", r_floor);
+    METRO_CHECK_ARG(cov_scale >= 0.0 && std::isfinite(cov_scale), "track_bone_lengths: cov_scale must be finite and >= 0 (got %g)",
+                    cov_scale);
+    METRO_CHECK_ARG(min_length_mm >= 0.0 && std::isfinite(min_length_mm),
+                    "track_bone_lengths: min_length_mm must be finite and >= 0 (got %g)", min_length_mm);
+    METRO_CHECK_ARG(d_ids && d_edges && d_edge_mirror && d_stats && d_bone_ids && d_lengths_out && d_sigma_out && d_known_out,
+                    "track_bone_lengths: NULL ids / edges / edge_mirror / stats / bone_ids / output pointer");
+    METRO_CHECK_ARG(n_rows == 0 || n == 0 || (d_poses && d_rows && d_starts),
+                    "track_bone_lengths: %d group rows need poses, rows and starts", n_rows);
+    if (n == 0) n_rows = 0;             // no pose row to read: reset and read-out only
+    return launch_track_bone_lengths(d_poses, d_cov, n, d_rows, n_rows, d_starts, n_tracks, d_ids, n_joints_out, d_edges, d_edge_mirror,
+                                     n_edges, d_fallback, min_count, gate, r_floor, cov_scale, min_length_mm, debias != 0,
+                                     symmetric != 0, d_stats, d_bone_ids, d_lengths_out, d_sigma_out, d_known_out,
+                                     static_cast<hipStream_t>(stream));
+}
+
 const char* metro_last_error(void) { return metro::get_error(); }
 int32_t metro_abi_version(void) { return METRO_ABI_VERSION; }
 

@@ -527,6 +527,12 @@ int launch_associate_tracks_rays(float* poses, float* cov, const double* times, 
                                  int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new, int* n_dropped,
                                  int assignment, const int* single_box, const double* rays, double depth_sigma_mm, float* ray_depth,
                                  int* n_unplaced, hipStream_t stream);
+// the bone lengths of followed persons, accumulated per (track slot, skeleton edge) and read out (bone_lengths.hip)
+int launch_track_bone_lengths(const float* poses, const float* cov, int n, const int* rows, int n_rows, const int* starts, int n_tracks,
+                              const int* ids, int n_joints, const int* edges, const int* edge_mirror, int n_edges,
+                              const double* fallback, int min_count, double gate, double r_floor, double cov_scale, double min_length,
+                              int debias, int symmetric, double* stats, int* bone_ids, double* lengths_out, double* sigma_out,
+                              unsigned char* known_out, hipStream_t stream);
 // per-box crop geometry of full frames (look_at_boxes.hip)
 int launch_look_at_boxes(const double* boxes, const int32_t* frame_index, int n, int n_frames, const MetroFrameCamera* cameras,
                          int n_cameras, int side, MetroViewBase* out, int32_t* status, hipStream_t stream);

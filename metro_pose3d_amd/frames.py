@@ -838,8 +838,9 @@ def _model_skeleton(model_path):
     return sk
 
 
-def _placement_targets(scale_recovery, cameras, n, n_edges, bone_lengths, root_depth):
-    """Checks the scale-recovery arguments; returns (bone lengths float64 [E] or [n, E], per-pose flag, root depths float32 [n])."""
+def _placement_targets(scale_recovery, cameras, n, n_edges, bone_lengths, root_depth, device=None):
+    """Checks the scale-recovery arguments; returns (bone lengths float64 [E] or [n, E], per-pose flag, root depths float32 [n]).
+    A torch tensor as bone_lengths is device data: float64 [n, E], contiguous, on `device`; it is returned as it is, unread."""
     if scale_recovery not in SCALE_RECOVERY:
         raise ValueError(f"scale_recovery must be 'metro', 'bone-lengths' or 'true-root-depth', got {scale_recovery!r}")
     if scale_recovery == 'metro':
@@ -855,6 +856,14 @@ def _placement_targets(scale_recovery, cameras, n, n_edges, bone_lengths, root_d
         if bone_lengths is None:
             raise ValueError(f"scale_recovery='bone-lengths' needs bone_lengths in mm, [E] or [n, E] over the model's {n_edges} "
                              'head edges (spec.skeleton.head_edges); no default table ships with the package')
+        if isinstance(bone_lengths, torch.Tensor):
+            t = bone_lengths
+            if (not t.is_cuda or t.dtype != torch.float64 or tuple(t.shape) != (n, n_edges) or not t.is_contiguous()
+                    or (device is not None and t.device != device)):
+                raise ValueError(f'a tensor as bone_lengths must be a contiguous float64 CUDA tensor [{n}, {n_edges}] on the '
+                                 f"call's device (Follower.bone_lengths_for), got {t.dtype} {tuple(t.shape)} on {t.device}; host "
+                                 'values go in as arrays')
+            return t, 1, None
         b = np.asarray(bone_lengths, np.float64)
         if b.shape not in ((n_edges,), (n, n_edges)):
             raise ValueError(f'bone_lengths must be [{n_edges}] or [{n}, {n_edges}] (mm over spec.skeleton.head_edges), got {b.shape}')
@@ -886,7 +895,11 @@ def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=
       'metro'            root-relative poses: the bits of estimate_pose_in_frames(..., coords=coords); z_offset None;
       'bone-lengths'     needs cameras and bone_lengths in mm, [E] or [n, E] over spec.skeleton.head_edges: rays through each
                          crop's virtual camera, the reference's Levenberg-Marquardt z offset (metro_backproject_bone_lengths'
-                         arithmetic), back_project;
+                         arithmetic), back_project.  bone_lengths may also be a float64 CUDA tensor [n, E], contiguous and on
+                         the call's device (Follower.bone_lengths_for: each followed person's own learned skeleton): it goes to
+                         metro_place_poses as it is, repeated per view on the device, and its values are NOT read on the host --
+                         they must be finite and positive, which bone_lengths_for guarantees; any other tensor is a ValueError
+                         before any launch.  Host arrays keep their path and their bits;
       'true-root-depth'  needs cameras and root_depth [n] in mm: the root's z in the crop's virtual camera (the reference's
                          coords3d_true[:, -1, 2]).
     coords: 'crop' (the virtual camera), 'camera' (the original one: to_orig_cam, volumetric.py:204-205, 277-281) or 'world'
@@ -905,8 +918,8 @@ def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=
     merge, so a camera whose own R is improper (det R <= 0) has its keypoints swapped to the mirror joints with or without
     views, on host and on device boxes alike.  return_spread=True returns (FramePoses, spread [n, Jout]): per joint, the RMS
     3D distance in mm of the views from their mean (zeros with one view), a cheap agreement score.
-    geometry: 'host', 'device' or 'auto' as for estimate_pose_in_frames (bone_lengths and root_depth stay host data); a
-    device frame index outside [0, n_frames) raises ValueError, read together with the finite screen in the call's one
+    geometry: 'host', 'device' or 'auto' as for estimate_pose_in_frames (root_depth stays host data, bone_lengths unless given as
+    a CUDA tensor); a device frame index outside [0, n_frames) raises ValueError, read together with the finite screen in the call's one
     synchronisation.
     pixel_format, color_matrix: as for estimate_pose_in_frames ('bgr', 'nv12', 'i420' frames converted per tap in the warp,
     OpenCV's integer YUV rule, black border); crop_dtype 'float32' | 'uint8' likewise (the same bits from a quarter of the
@@ -919,8 +932,9 @@ def locate_poses_in_frames(frames, boxes, model_path, cameras=None, frame_index=
     call = _checked_call(frames, boxes, frame_index, coords, views, geometry, precision, check_finite, pixel_format,
                          color_matrix, crop_dtype)
     sk = _model_skeleton(model_path)
+    on_device = isinstance(bone_lengths, torch.Tensor) and bone_lengths.is_cuda
     targets, per_pose, root_z = _placement_targets(scale_recovery, cameras, len(call.boxes), len(sk.head_edges), bone_lengths,
-                                                   root_depth)
+                                                   root_depth, _call_device(call.boxes, call.frames) if on_device else None)
     res = _locate_poses_views(call, model_path, cameras, scale_recovery, targets, per_pose, root_z, coords, sk, return_uncertainty)
     return res if return_spread else res[0]
 
@@ -968,11 +982,14 @@ def _locate_poses_views(call: _Call, model_path, cameras, scale_recovery, target
                     torch.zeros((0, sk.n_out), dtype=torch.float32, device=device))
         crops, places = _warp_views(call.frames, cameras, call.boxes, call.fi, call.vs, eng.spec.proc_side, device, call.crop_dtype)
         rel, coords01, bad, *mom = _forward_coords01(eng, crops, call.check_finite, uncertainty)
-        if per_pose:                                    # per-box targets, repeated per view by index (box-major rows)
-            targets = np.repeat(targets, nv, axis=0)
+        if isinstance(targets, torch.Tensor):           # device bone lengths: unread, repeated per view on the device
+            d_targets = targets if nv == 1 else targets.repeat_interleave(nv, dim=0)
+        else:
+            if per_pose:                                # per-box targets, repeated per view by index (box-major rows)
+                targets = np.repeat(targets, nv, axis=0)
+            d_targets = _upload(targets, device) if targets is not None else None
         poses_v, keypoints_v, z_v = f32(m, sk.n_out, 3), f32(m, sk.n_out, 2), f32(m) if absolute else None
         mirror = _upload(np.asarray(sk.out_mirror, np.int32), device)
-        d_targets = _upload(targets, device) if targets is not None else None
         d_root = _upload(np.repeat(root_z, nv), device) if root_z is not None else None
         d_edges = _upload(np.asarray(sk.head_edges, np.int32).reshape(-1, 2), device) if targets is not None else None
         ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
@@ -1394,6 +1411,37 @@ def _check_track_table(tracks, capacity):
     del capacity
 
 
+class BoneTable(NamedTuple):
+    """The bone lengths a Follower(learn_bones=True) learns per track slot, on the device (new_bone_table)."""
+    stats: torch.Tensor                  # float64 [T, E, 4]: per slot and skeleton edge S0 = sum 1/v, S1 = sum l/v, count, rejected
+    ids: torch.Tensor                    # int32 [T]: the id of the track the slot's stats belong to (-1: nobody's)
+
+
+def new_bone_table(capacity: int, n_edges: int, device) -> BoneTable:
+    """An empty bone table for `capacity` (1 to 128) track slots and n_edges (1 to 64) skeleton edges: for
+    heads.track_bone_lengths next to new_track_table's table of the same capacity."""
+    from metro_pose3d_amd.heads import ASSOC_MAX, BONE_STAT_DOUBLES
+    if isinstance(capacity, (bool, np.bool_)) or not isinstance(capacity, (int, np.integer)) or not 1 <= capacity <= ASSOC_MAX:
+        raise ValueError(f'capacity must be an integer from 1 to {ASSOC_MAX} (track slots), got {capacity!r}')
+    if isinstance(n_edges, (bool, np.bool_)) or not isinstance(n_edges, (int, np.integer)) or not 1 <= n_edges <= _lib.METRO_MAX_JOINTS:
+        raise ValueError(f'n_edges must be an integer from 1 to {_lib.METRO_MAX_JOINTS} (skeleton edges), got {n_edges!r}')
+    return BoneTable(torch.zeros((int(capacity), int(n_edges), BONE_STAT_DOUBLES), dtype=torch.float64, device=device),
+                     torch.full((int(capacity),), -1, dtype=torch.int32, device=device))
+
+
+def _checked_bone_table(bones, tracks: TrackTable, sk) -> BoneTable:
+    from metro_pose3d_amd.heads import BONE_STAT_DOUBLES
+    shape = (len(tracks.ids), len(sk.edges), BONE_STAT_DOUBLES)
+    ok = (isinstance(bones, tuple) and len(bones) == 2 and all(isinstance(t, torch.Tensor) for t in bones)
+          and bones[0].dtype == torch.float64 and tuple(bones[0].shape) == shape and bones[0].is_contiguous()
+          and bones[1].dtype == torch.int32 and tuple(bones[1].shape) == shape[:1] and bones[1].is_contiguous()
+          and bones[0].device == tracks.ids.device and bones[1].device == tracks.ids.device)
+    if not ok:
+        raise ValueError(f'bones must be a BoneTable(stats float64 {list(shape)}, ids int32 [{shape[0]}]) on the device of the track '
+                         'table (new_bone_table, or the table of a previous call)')
+    return BoneTable(*bones)
+
+
 def follow_poses_in_frames(frames, boxes, model_path, cameras, frame_index, timestamps, tracks: Optional[TrackTable] = None,
                            capacity: int = 64, max_cost_mm: float = 300.0, clip_mm: float = 600.0,
                            min_joints: Optional[int] = None, max_age_s: float = 1.0, mode: str = 'smooth',
@@ -1562,12 +1610,15 @@ SINGLE_VIEWS = ('rays', 'skip')
 def _follow_world(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity, match_max_cost_mm, match_clip_mm,
                   match_min_joints, weights, min_angle_deg, max_cost_mm, clip_mm, min_joints, max_age_s, mode, measurement, accel_psd,
                   sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, views, precision, check_finite, geometry, pixel_format,
-                  color_matrix, crop_dtype, assignment, single_view, ray_depth_sigma_mm):
+                  color_matrix, crop_dtype, assignment, single_view, ray_depth_sigma_mm, bones=None):
     """follow_world_poses_in_frames (single_view 'skip') and follow_rig_poses_in_frames -> (FollowedWorldPoses, None or
-    (single_view uint8 [P], ray_depth float32 [P, Jout], n_unplaced int32 [1]) of the 'rays' chain)."""
+    (single_view uint8 [P], ray_depth float32 [P, Jout], n_unplaced int32 [1]) of the 'rays' chain, the bone table).
+    bones: None (nothing is learned: the chain is what it was), True (a fresh table) or the BoneTable of the previous call:
+    one metro_track_bone_lengths launch after the smoothing launch accumulates every followed person's bone lengths from the
+    triangulation's own poses and covariance."""
     from metro_pose3d_amd.heads import (MATCH_MAX_BOXES, associate_tracks, associate_tracks_rays, association_params, assignment_rule,
                                         matching_params, person_rays, person_steps, person_steps_labels, ray_depth_sigma,
-                                        smooth_tracks, smoothing_params, triangulation_min_det)
+                                        smooth_tracks, smoothing_params, track_bone_lengths, triangulation_min_det)
     if not isinstance(single_view, str) or single_view not in SINGLE_VIEWS:
         raise ValueError(f"single_view must be 'rays' or 'skip', got {single_view!r}")
     with_rays = single_view == 'rays'
@@ -1606,8 +1657,11 @@ def _follow_world(frames, boxes, model_path, cameras, frame_index, timestamps, t
         raise ValueError(f'tracks.state holds {tracks[0].shape[1]} joints, the model has {sk.n_out}')
     device = _call_device(call.boxes, call.frames)
     tracks = new_track_table(capacity, sk.n_out, device) if tracks is None else TrackTable(*tracks)
+    if bones is not None:
+        bones = new_bone_table(len(tracks.ids), len(sk.edges), device) if bones is True else _checked_bone_table(bones, tracks, sk)
 
     def then(spec, n_views, poses, cov, rows, starts, n_persons, seen):
+        own = (poses, cov)                                  # the triangulation's: NaN for a person one camera sees
         if with_rays:
             coords01, cov01, places, labels = seen
             person_step, person_times, step_rows, step_starts, single_box = person_steps_labels(labels, n_persons, box_step, step_times)
@@ -1623,8 +1677,12 @@ def _follow_world(frames, boxes, model_path, cameras, frame_index, timestamps, t
                                      max_cost_mm, clip_mm, min_joints, max_age_s, measurement, accel_psd, sigma_floor_mm, cov_scale,
                                      initial_speed_mm_s, gate, assignment)
             extra = None
-        return person_step, found, smooth_tracks(poses, cov, person_times, found.rows, found.starts, mode, measurement, accel_psd,
-                                                 sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, tracks.state), extra
+        smooth = smooth_tracks(poses, cov, person_times, found.rows, found.starts, mode, measurement, accel_psd, sigma_floor_mm,
+                               cov_scale, initial_speed_mm_s, gate, tracks.state)
+        if bones is not None:                               # the raw measurements, not the smoothed rows: those are correlated in time
+            track_bone_lengths(own[0], own[1] if measurement == 'covariance' else None, found.rows, found.starts, tracks.ids,
+                               bones.stats, bones.ids, sk.edges, sk.edge_mirror(), sigma_floor_mm=sigma_floor_mm, cov_scale=cov_scale)
+        return person_step, found, smooth, extra
 
     match = (float(match_max_cost_mm), float(match_clip_mm), None if match_min_joints is None else int(match_min_joints))
     world, matched, (cov, followed) = _world_poses(call, model_path, cameras, fi, weights, min_angle_deg, match=match,
@@ -1635,13 +1693,13 @@ def _follow_world(frames, boxes, model_path, cameras, frame_index, timestamps, t
         f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=device)
         smoothed = SmoothedWorldPoses(f32(0, sk.n_out, 3), f32(0, sk.n_out, 3), f32(0, sk.n_out, 3, 3),
                                       torch.zeros((0, sk.n_out), dtype=torch.uint8, device=device), tracks.state)
-        return FollowedWorldPoses(*matched, world, cov, i32(0), i32(0), i32(0), f32(0), i32(1), i32(1), tracks, smoothed), None
+        return FollowedWorldPoses(*matched, world, cov, i32(0), i32(0), i32(0), f32(0), i32(1), i32(1), tracks, smoothed), None, bones
     person_step, found, (poses, velocity, covariance, used), extra = followed
     smoothed = SmoothedWorldPoses(poses[:p], velocity[:p], covariance[:p], used[:p], tracks.state)
     if extra is not None:
         extra = (extra[0][:p], extra[1][:p], extra[2])
     return FollowedWorldPoses(*matched, world, cov, person_step[:p], found.track_index[:p], found.track_id[:p], found.cost[:p],
-                              found.n_new, found.n_dropped, tracks, smoothed), extra
+                              found.n_new, found.n_dropped, tracks, smoothed), extra, bones
 
 
 class FollowedRigPoses(NamedTuple):
@@ -1696,11 +1754,16 @@ def follow_rig_poses_in_frames(frames, boxes, model_path, cameras, frame_index, 
     rounding of R stays far below sigma_floor_mm^2.
     ValueError before any launch for whatever follow_world_poses_in_frames refuses, an unknown single_view, ray_depth_sigma_mm
     not finite and > 0, and measurement='isotropic' together with 'rays'."""
-    out, extra = _follow_world(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity, match_max_cost_mm,
-                               match_clip_mm, match_min_joints, weights, min_angle_deg, max_cost_mm, clip_mm, min_joints, max_age_s,
-                               mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, views, precision,
-                               check_finite, geometry, pixel_format, color_matrix, crop_dtype, assignment, single_view,
-                               ray_depth_sigma_mm)
+    out, extra, _ = _follow_world(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity, match_max_cost_mm,
+                                  match_clip_mm, match_min_joints, weights, min_angle_deg, max_cost_mm, clip_mm, min_joints, max_age_s,
+                                  mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, views, precision,
+                                  check_finite, geometry, pixel_format, color_matrix, crop_dtype, assignment, single_view,
+                                  ray_depth_sigma_mm)
+    return _rig_poses(out, extra)
+
+
+def _rig_poses(out: FollowedWorldPoses, extra) -> FollowedRigPoses:
+    """_follow_world's pair as FollowedRigPoses; extra None (the 'skip' chain): single_view all 0, ray_depth NaN, n_unplaced 0."""
     if extra is None:
         p, device = len(out.person_step), out.person_step.device
         extra = (torch.zeros((p,), dtype=torch.uint8, device=device),
@@ -1809,15 +1872,32 @@ class Follower:
     .follow(frames, boxes, frame_index, timestamps) -> FollowedPoses / FollowedWorldPoses of these boxes, continuing
     .tracks (None before the first call: a fresh table of `capacity` slots), which then is the table the call returned.
     .predict(frame_sizes, timestamps, **keywords) -> predict_boxes_in_frames on .tracks with the follower's cameras and
-    coordinates.  .reset() drops the table: the next call starts new tracks from id 0."""
+    coordinates.  .reset() drops the table: the next call starts new tracks from id 0.
+    Follower(..., world=True, learn_bones=True): every call also learns the bone lengths of the persons it follows, per track
+    slot, from their triangulated joints and covariance (one metro_track_bone_lengths launch at the end of the chain, still one
+    synchronisation; heads.track_bone_lengths has the estimator, run with its defaults and the follower's sigma_floor_mm and
+    cov_scale).  Every output of .follow is what it is without learn_bones, and without it the follower enqueues what it did.
+    world=False is refused: lengths learned from poses that bone lengths placed would only echo the table (learning under
+    'true-root-depth' is left out).  .bones is the BoneTable (None before the first call); .bone_lengths(fallback=None) ->
+    heads.BoneLengths of every slot, one read-out launch; .bone_lengths_for(track_index, fallback) -> float64 [n, E] on the
+    device, one row per entry of an int32 CUDA tensor of slots such as PredictedBoxes.track_index: the slot's learned lengths,
+    `fallback` (required: [E] finite and positive mm) for -1, for a slot outside the table and for every edge not yet known
+    -- so every value is finite and positive and the tensor goes straight into locate_poses_in_frames(bone_lengths=...): a rig
+    that has seen a person lets any one camera place that person with their own skeleton, with no host round trip.  Neither
+    synchronises.  .reset() also drops the bone table."""
 
     def __init__(self, model_path, cameras, world: bool = False, assignment: str = 'greedy', capacity: int = 64,
-                 single_view: Optional[str] = None, **keywords):
+                 single_view: Optional[str] = None, learn_bones: bool = False, **keywords):
         import inspect
         from metro_pose3d_amd.heads import (association_params, assignment_rule, matching_params, ray_depth_sigma, smoothing_params,
                                             triangulation_min_det)
         if not isinstance(world, (bool, np.bool_)):
             raise ValueError(f'world must be True or False, got {world!r}')
+        if not isinstance(learn_bones, (bool, np.bool_)):
+            raise ValueError(f'learn_bones must be True or False, got {learn_bones!r}')
+        if learn_bones and not world:
+            raise ValueError('learn_bones needs world=True: bone lengths are learned from triangulated poses; poses that bone '
+                             'lengths placed would only echo the table')
         if single_view is not None:
             if not world:
                 raise ValueError('single_view belongs to a calibrated rig: it needs world=True')
@@ -1851,9 +1931,20 @@ class Follower:
         self.model_path, self.cameras, self.world = model_path, cameras, bool(world)
         self.assignment, self.capacity, self.keywords, self.single_view = assignment, int(capacity), kw, single_view
         self.tracks: Optional[TrackTable] = None
+        self.learn_bones = bool(learn_bones)
+        self.bones: Optional[BoneTable] = None
 
     def follow(self, frames, boxes, frame_index, timestamps):
-        if self.world and self.single_view is not None:
+        if self.learn_bones:
+            kw = dict({'single_view': 'skip', 'ray_depth_sigma_mm': None}, **self.keywords)
+            if self.single_view is not None:
+                kw['single_view'] = self.single_view
+            out, extra, self.bones = _follow_world(frames, boxes, self.model_path, self.cameras, frame_index, timestamps, self.tracks,
+                                                   self.capacity, assignment=self.assignment,
+                                                   bones=True if self.bones is None else self.bones, **kw)
+            if self.single_view is not None:
+                out = _rig_poses(out, extra)
+        elif self.world and self.single_view is not None:
             out = follow_rig_poses_in_frames(frames, boxes, self.model_path, self.cameras, frame_index, timestamps, tracks=self.tracks,
                                              capacity=self.capacity, assignment=self.assignment, single_view=self.single_view,
                                              **self.keywords)
@@ -1874,5 +1965,40 @@ class Follower:
         coords = 'world' if self.world else self.keywords['coords']
         return predict_boxes_in_frames(self.tracks, self.cameras, frame_sizes, timestamps, coords=coords, **keywords)
 
+    def _bone_read_out(self, fallback, required: bool):
+        from metro_pose3d_amd.heads import bone_fallback, track_bone_lengths
+        bone_fallback(fallback, None, required)
+        if not self.learn_bones:
+            raise ValueError('this follower learns no bone lengths (learn_bones=True)')
+        sk = _model_skeleton(self.model_path)
+        fallback = bone_fallback(fallback, len(sk.edges), required)
+        if self.bones is None or self.tracks is None:
+            raise ValueError('no bone table yet (call follow first)')
+        with torch.cuda.device(self.bones.stats.device):
+            return track_bone_lengths(None, None, None, None, self.tracks.ids, self.bones.stats, self.bones.ids, sk.edges,
+                                      sk.edge_mirror(), fallback, sigma_floor_mm=self.keywords['sigma_floor_mm'],
+                                      cov_scale=self.keywords['cov_scale'])
+
+    def bone_lengths(self, fallback=None):
+        return self._bone_read_out(fallback, False)
+
+    def bone_lengths_for(self, track_index, fallback) -> torch.Tensor:
+        from metro_pose3d_amd.heads import bone_fallback
+        bone_fallback(fallback, None, True)
+        if (not isinstance(track_index, torch.Tensor) or not track_index.is_cuda or track_index.dtype != torch.int32
+                or track_index.dim() != 1):
+            raise ValueError('track_index must be an int32 CUDA tensor [n] of track slots (PredictedBoxes.track_index), got '
+                             f'{getattr(track_index, "dtype", type(track_index))} {tuple(getattr(track_index, "shape", ()))}')
+        table = self._bone_read_out(fallback, True).lengths               # unknown edges already hold the fallback
+        if track_index.device != table.device:
+            raise ValueError(f'track_index is on {track_index.device}, the bone table on {table.device}')
+        # row T of the padded table is the fallback itself (an unknown edge of ANY slot holds it): -1 and slots outside go there
+        n_tracks = table.shape[0]
+        slot = track_index.to(torch.int64)
+        slot = torch.where((slot >= 0) & (slot < n_tracks), slot, torch.full_like(slot, n_tracks))
+        row = _upload(bone_fallback(fallback, table.shape[1], True), table.device)
+        return torch.cat([table, row[None]], 0).index_select(0, slot).contiguous()
+
     def reset(self):
         self.tracks = None
+        self.bones = None

@@ -20,6 +20,9 @@ through the C ABI (csrc/heads.hip).  Names and argument meaning follow the refer
                             the frames' calibrated cameras, compacted on the device and fused with a detector's boxes
   smooth_tracks             poses of tracked persons over time: constant-velocity Kalman filter / RTS smoother per track and
                             joint, each row weighted by its heat-map covariance (nothing in the reference: one image each)
+  track_bone_lengths        the bone lengths of followed persons, learned per track slot from their triangulated joints: a
+                            covariance-weighted, noise-debiased, gated mean per skeleton edge (nothing in the reference: its
+                            tables come from its training data)
   backproject_bone_lengths  scale_recovery 'bone-lengths' / '-true'   volumetric.py:171-191,
                             optimize_z_offset_by_bones(_tensor)       src/model/bone_length_based_backproj.py:15-62
   backproject_root_depth    scale_recovery 'true-root-depth'          volumetric.py:192-199
@@ -749,6 +752,117 @@ def _associate_tracks(poses, covariance, times, step_rows, step_starts, state, i
                               _p(starts), _p(n_new), _p(n_dropped), _stream(dev)), entry)
     return AssociatedTracks(track_index, track_id, cost, rows, starts, n_new, n_dropped,
                             ws.view(torch.float64).view(n_tracks, nj, TRACK_STATE_DOUBLES))
+
+
+BONE_STAT_DOUBLES = 4                # per (track slot, edge): S0 = sum 1/v, S1 = sum l/v, count, rejected
+_BONE_EDGES = {}                     # (device, edges, edge_mirror) -> their device copies
+
+
+class BoneLengths(NamedTuple):
+    """What track_bone_lengths returns, all on the device."""
+    lengths: torch.Tensor                # float64 [T, E] mm: the learned length, the fallback (NaN without one) where it is not known
+    sigma: torch.Tensor                  # float64 [T, E] mm: the standard error the weights imply, NaN where it is not known
+    known: torch.Tensor                  # uint8 [T, E]: 1 where at least min_count rows (with the mirror bone's) were accepted
+
+
+def bone_length_params(min_count=8, gate=9.0, sigma_floor_mm=1.0, cov_scale=1.0, min_length_mm=1.0, debias=True, symmetric=True):
+    """Checks the estimator keywords of track_bone_lengths / frames.Follower(learn_bones=True); -> metro_track_bone_lengths'
+    (min_count, gate, r_floor, cov_scale, min_length_mm, debias, symmetric), gate None as 0."""
+    if isinstance(min_count, (bool, np.bool_)) or not isinstance(min_count, (int, np.integer)) or min_count < 1:
+        raise ValueError(f'min_count must be an integer >= 1, got {min_count!r}')
+    for name, flag in (('debias', debias), ('symmetric', symmetric)):
+        if not isinstance(flag, (bool, np.bool_)):
+            raise ValueError(f'{name} must be True or False, got {flag!r}')
+    return (int(min_count), 0.0 if gate is None else _positive('gate', gate, zero_ok=True), _positive('sigma_floor_mm', sigma_floor_mm),
+            _positive('cov_scale', cov_scale, zero_ok=True), _positive('min_length_mm', min_length_mm, zero_ok=True), int(debias),
+            int(symmetric))
+
+
+def bone_fallback(fallback, n_edges: Optional[int], required: bool = False) -> Optional[np.ndarray]:
+    """Checks a `fallback` table: host float64 [E] mm, finite and positive (None unless `required`; n_edges None: any E >= 1)."""
+    if fallback is None and not required:
+        return None
+    if fallback is None:
+        raise ValueError('fallback is required: [E] bone lengths in mm for unknown tracks and edges')
+    if isinstance(fallback, torch.Tensor):
+        fallback = fallback.detach().cpu().numpy()
+    f = np.asarray(fallback, np.float64)
+    if f.ndim != 1 or len(f) < 1 or (n_edges is not None and len(f) != n_edges) or not (np.isfinite(f).all() and (f > 0).all()):
+        raise ValueError(f"fallback must be [{'E' if n_edges is None else n_edges}] finite and positive bone lengths in mm, got "
+                         f'shape {f.shape}')
+    return np.ascontiguousarray(f)
+
+
+def track_bone_lengths(poses: Optional[torch.Tensor], covariance: Optional[torch.Tensor], rows, starts, ids: torch.Tensor,
+                       stats: torch.Tensor, bone_ids: torch.Tensor, edges, edge_mirror, fallback=None, min_count: int = 8,
+                       gate: Optional[float] = 9.0, sigma_floor_mm: float = 1.0, cov_scale: float = 1.0, min_length_mm: float = 1.0,
+                       debias: bool = True, symmetric: bool = True) -> BoneLengths:
+    """The bone lengths of followed persons, learned per track slot: one metro_track_bone_lengths launch on the current stream,
+    no synchronisation (include/metro_hip.h has the model and the reasoning).  poses [n,J,3] mm ABSOLUTE and covariance
+    [n,J,3,3] or [n,J,9] mm^2 (None: isotropic) on the device -- the triangulation's own world poses and covariance, NaN where
+    a joint could not be placed; rows / starts the CSR per slot associate_tracks* returned; ids int32 [T] the track table's ids
+    after that association.  edges [E,2] in output joint indices (Skeleton.edges), edge_mirror [E] (Skeleton.edge_mirror()).
+    The bone table (frames.new_bone_table), updated in place: stats float64 [T,E,4] = (S0, S1, count, rejected) and bone_ids
+    int32 [T]: a slot whose id differs from bone_ids forgets first.  Per slot, edge and listed row the length l of the bone,
+    corrected for the first-order bias of a noisy length (debias) to l^ = l - (tr C - u^T C u) / (2 l) with
+    C = cov_scale (C_a + C_b), enters a mean weighted by 1 / v, v = tr C / 3 + sigma_floor_mm^2, unless it lies further than
+    gate (a squared distance in units of v + 1/S0; None or 0: no gate) from the mean of at least min_count rows, which counts
+    it in `rejected`.  Read-out: with `symmetric` a bone is pooled with its mirror bone; with at least min_count rows
+    length = S1 / S0 and sigma = sqrt(1 / S0), known 1; else fallback [E] (NaN without one), known 0.
+    poses None (or no rows): reset and read-out only.  min_count = 8, gate = 9 (3 sigma, one degree of freedom),
+    min_length_mm = 1, sigma_floor_mm = 1 and cov_scale = 1 are design choices, not measurements.  -> BoneLengths."""
+    params = bone_length_params(min_count, gate, sigma_floor_mm, cov_scale, min_length_mm, debias, symmetric)
+    if (not isinstance(stats, torch.Tensor) or not stats.is_cuda or stats.dtype != torch.float64 or stats.dim() != 3
+            or stats.shape[2] != BONE_STAT_DOUBLES or not 1 <= stats.shape[0] <= ASSOC_MAX or not 1 <= stats.shape[1] <= _lib.METRO_MAX_JOINTS or not stats.is_contiguous()):
+        raise ValueError(f'stats must be a contiguous float64 CUDA tensor [T,E,{BONE_STAT_DOUBLES}] with 1 <= T <= {ASSOC_MAX} and '
+                         f'1 <= E <= {_lib.METRO_MAX_JOINTS} (frames.new_bone_table)')
+    dev, n_tracks, n_edges = stats.device, int(stats.shape[0]), int(stats.shape[1])
+    for name, t in (('ids', ids), ('bone_ids', bone_ids)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != dev or t.numel() != n_tracks or not t.is_contiguous():
+            raise ValueError(f'{name} must be a contiguous int32 tensor of {n_tracks} on {dev}')
+    fallback = bone_fallback(fallback, n_edges)
+    e = edges.detach().cpu().numpy() if isinstance(edges, torch.Tensor) else np.asarray(edges)
+    em = edge_mirror.detach().cpu().numpy() if isinstance(edge_mirror, torch.Tensor) else np.asarray(edge_mirror)
+    if e.shape != (n_edges, 2) or em.shape != (n_edges,):
+        raise ValueError(f'edges must be [{n_edges},2] and edge_mirror [{n_edges}], got {e.shape} and {em.shape}')
+    if poses is None:
+        n = nj = n_rows = 0
+    else:
+        if not isinstance(poses, torch.Tensor) or poses.dim() != 3 or poses.shape[2] != 3 or not 1 <= poses.shape[1] <= _lib.METRO_MAX_JOINTS:
+            raise ValueError(f'poses must be a tensor [n,J,3] with J <= {_lib.METRO_MAX_JOINTS}, got {tuple(getattr(poses, "shape", ()))}')
+        n, nj = int(poses.shape[0]), int(poses.shape[1])
+        if poses.device != dev:
+            raise ValueError(f'poses are on {poses.device}, the bone table on {dev}')
+        if covariance is not None and tuple(covariance.shape) not in ((n, nj, 3, 3), (n, nj, 9)):
+            raise ValueError(f'covariance must be [{n},{nj},3,3] or None, got {tuple(covariance.shape)}')
+        n_rows = int(rows.numel() if isinstance(rows, torch.Tensor) else np.asarray(rows).size)
+        n_starts = int(starts.numel() if isinstance(starts, torch.Tensor) else np.asarray(starts).size)
+        if n_starts != n_tracks + 1:
+            raise ValueError(f'starts must hold T + 1 = {n_tracks + 1} offsets, got {n_starts}')
+    from metro_pose3d_amd.frame_formats import _upload
+    lib = _lib.load()
+    e, em = np.ascontiguousarray(e, np.int32), np.ascontiguousarray(em, np.int32)
+    key = (str(dev), e.tobytes(), em.tobytes())
+    if key not in _BONE_EDGES:                              # a skeleton's two small tables: uploaded once per device
+        if len(_BONE_EDGES) >= 16:
+            _BONE_EDGES.clear()
+        _BONE_EDGES[key] = (_upload(e.reshape(-1), dev), _upload(em, dev))
+    d_edges, d_mirror = _BONE_EDGES[key]
+    d_fallback = _upload(fallback, dev) if fallback is not None else None
+    d_poses = d_cov = d_rows = d_starts = None
+    if n > 0 and n_rows > 0:
+        d_poses = poses.to(torch.float32).contiguous()
+        d_cov = covariance.to(torch.float32).reshape(n, nj, 9).contiguous() if covariance is not None else None
+        d_rows, d_starts = _i32(rows, dev).reshape(-1), _i32(starts, dev).reshape(-1)
+    else:
+        n = n_rows = 0
+    lengths = torch.empty((n_tracks, n_edges), dtype=torch.float64, device=dev)
+    sigma = torch.empty((n_tracks, n_edges), dtype=torch.float64, device=dev)
+    known = torch.empty((n_tracks, n_edges), dtype=torch.uint8, device=dev)
+    check(lib.metro_track_bone_lengths(_p(d_poses), _p(d_cov), n, _p(d_rows), n_rows, _p(d_starts), n_tracks, _p(ids), max(nj, 1),
+                                       _p(d_edges), _p(d_mirror), n_edges, _p(d_fallback), *params, _p(stats), _p(bone_ids),
+                                       _p(lengths), _p(sigma), _p(known), _stream(dev)), 'metro_track_bone_lengths')
+    return BoneLengths(lengths, sigma, known)
 
 
 PREDICT_MAX_DETECTIONS = _lib.METRO_PREDICT_MAX_DETECTIONS

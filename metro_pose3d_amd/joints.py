@@ -55,6 +55,15 @@ class Skeleton:
             raise ValueError(f'the mirror joints of {missing} are not among the exported joints')
         return tuple(position_of[mirror[h]] for h in self.permutation)
 
+    def edge_mirror(self) -> Tuple[int, ...]:
+        """Per edge (head_edges and edges share one order), the index of the edge made of its two joints' mirror joints
+        (head_mirror), in either orientation; -1 where that is the edge itself (a mid-line bone) or no edge: the partner
+        metro_track_bone_lengths pools a bone with."""
+        mirror = self.head_mirror
+        at = {frozenset(e): i for i, e in enumerate(self.head_edges)}
+        partner = (at.get(frozenset((mirror[a], mirror[b])), -1) for a, b in self.head_edges)
+        return tuple(-1 if p == i else p for i, p in enumerate(partner))
+
     @property
     def n_head(self) -> int:
         return len(self.head_names)
