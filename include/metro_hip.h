@@ -170,7 +170,13 @@ int  metro_plan_bind_params(MetroPlan* plan, const void* d_param_blob);
  *      architectures.resnet (architectures.py:24-35) -> net_output_to_heatmap_and_coords
  *      (volumetric.py:227-235) -> heatmap_to_metric (volumetric.py:303-306) -> root_relative
  *      (tfu3d.py:23-25) -> tf.gather(permutation) (main.py:127).
- *      d_images_nhwc: fp32 [n,256,256,3] in [0,1];  d_poses_out: fp32 [n,Jout,3] in mm. ---- */
+ *      d_images_nhwc: fp32 [n,256,256,3] in [0,1];  d_poses_out: fp32 [n,Jout,3] in mm.
+ *      The launch contract, for this and EVERY entry with a `stream` parameter (tests/test_gpu_streams.py holds each one to it
+ *      on a non-blocking side stream): all of the entry's work -- every kernel, every memset, the graph launch of a captured
+ *      forward -- is enqueued on `stream` and on no other stream; no entry synchronises, except metro_forward_status and
+ *      metro_forward_timed, which do so by contract.  A plan owns ONE workspace: consecutive calls on it that use different
+ *      streams must be ordered by the caller (an event of the first stream waited for on the second), as calls from
+ *      different threads must. ---- */
 int  metro_forward(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out,
                    void* d_workspace, void* stream);
 /* Small batches are launch-latency bound (45 dependent launches for ResNet-50 stride 16): forwards with

@@ -52,6 +52,27 @@ def _stream(dev) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
+_TABLES = {}                       # (device, dtype, shape, bytes) -> the device copy of a small constant table
+_TABLES_MAX = 64
+
+
+def _table(values, dtype, dev) -> torch.Tensor:
+    """A small constant table (a skeleton's mirror joints or edges, an index pattern) on the device.  Uploaded once per device
+    with a BLOCKING copy -- complete before any stream can read it, whichever stream is current now or at a later call -- and
+    kept: every later call uses the copy, launches no transfer and does not wait for its stream (a pageable upload per call
+    made the wrappers synchronise; tests/test_gpu_streams.py).  At most _TABLES_MAX tables are kept (the tables of a few
+    skeletons; callers may pass their own edges and mirror mappings): past that a table is uploaded, blocking, for the call
+    alone.  Nothing is ever dropped from the cache: a launch queued on some stream may still read it."""
+    a = np.ascontiguousarray(np.asarray(values, dtype))
+    key = (str(dev), a.dtype.str, a.shape, a.tobytes())
+    t = _TABLES.get(key)
+    if t is None:
+        t = torch.from_numpy(a).to(dev)
+        if len(_TABLES) < _TABLES_MAX:
+            _TABLES[key] = t
+    return t
+
+
 def _f32(x, dev, shape_tail) -> torch.Tensor:
     t = torch.as_tensor(x, dtype=torch.float32, device=dev).contiguous()
     if tuple(t.shape[1:]) != tuple(shape_tail):
@@ -77,7 +98,7 @@ def coords01_from_logits(logits: torch.Tensor, spec: ModelSpec, precise: int = 1
 
 def cov6_to_3x3(cov6: torch.Tensor) -> torch.Tensor:
     """[..., 6] (xx, yy, zz, xy, xz, yz) -> symmetric [..., 3, 3]."""
-    idx = torch.tensor([0, 3, 4, 3, 1, 5, 4, 5, 2], device=cov6.device)
+    idx = _table([0, 3, 4, 3, 1, 5, 4, 5, 2], np.int64, cov6.device)
     return cov6[..., idx].reshape(*cov6.shape[:-1], 3, 3)
 
 
@@ -131,7 +152,7 @@ def place_covariances(cov01: torch.Tensor, peak: torch.Tensor, spec: ModelSpec, 
     peak = peak.to(torch.float32).contiguous()
     n = cov01.shape[0] // n_views
     cs = spec.to_c(1)
-    mirror = torch.from_numpy(np.asarray(spec.skeleton.out_mirror, dtype=np.int32)).to(dev) if coords != 'crop' else None
+    mirror = _table(spec.skeleton.out_mirror, np.int32, dev) if coords != 'crop' else None
     out = torch.empty((n, spec.skeleton.n_out, 9), dtype=torch.float32, device=dev)
     pk = torch.empty((n, spec.skeleton.n_out), dtype=torch.float32, device=dev)
     check(lib.metro_place_covariances(_p(cov01), _p(peak), _p(records if coords != 'crop' else None), n, n_views, C.byref(cs),
@@ -200,7 +221,7 @@ def triangulate_joints(coords01: torch.Tensor, cov01: Optional[torch.Tensor], pl
     if n_persons == 0:
         return (points, n_rays, residual, cov) if return_covariance else (points, n_rays, residual)
     cs = spec.to_c(1)
-    mirror = torch.from_numpy(np.asarray(spec.skeleton.out_mirror, dtype=np.int32)).to(dev)
+    mirror = _table(spec.skeleton.out_mirror, np.int32, dev)
     if return_covariance:
         check(lib.metro_triangulate_joints_cov(_p(coords01), _p(cov01), _p(places), m, _p(rows), rows.numel(), _p(starts),
                                                n_persons, C.byref(cs), _p(mirror), TRI_WEIGHTS[weights], min_det, _p(points),
@@ -300,7 +321,7 @@ def _view_affinity(coords01, cov01, places, frame_index, step_index, spec, n_vie
     coords01, places = coords01.to(torch.float32).contiguous(), places.contiguous()
     cov01 = cov01.to(torch.float32).contiguous() if weights == 'covariance' else None
     cs = spec.to_c(1)
-    mirror = torch.from_numpy(np.asarray(spec.skeleton.out_mirror, dtype=np.int32)).to(dev)
+    mirror = _table(spec.skeleton.out_mirror, np.int32, dev)
     min_sin2 = float(np.sin(np.radians(float(min_angle_deg))) ** 2)
     if step_index is not None:
         si = _i32(step_index, dev).reshape(-1)
@@ -453,7 +474,7 @@ def person_rays(coords01: torch.Tensor, cov01: Optional[torch.Tensor], places: t
     coords01, places = coords01.to(torch.float32).contiguous(), places.contiguous()
     cov01 = cov01.to(torch.float32).contiguous() if weights == 'covariance' else None
     cs = spec.to_c(1)
-    mirror = torch.from_numpy(np.asarray(spec.skeleton.out_mirror, dtype=np.int32)).to(dev)
+    mirror = _table(spec.skeleton.out_mirror, np.int32, dev)
     check(_lib.load().metro_person_rays(_p(coords01), _p(cov01), _p(places), m, C.byref(cs), _p(mirror), TRI_WEIGHTS[weights],
                                         _p(single_box), n, n_views, _p(rays), _stream(dev)), 'metro_person_rays')
     return rays
@@ -755,7 +776,6 @@ def _associate_tracks(poses, covariance, times, step_rows, step_starts, state, i
 
 
 BONE_STAT_DOUBLES = 4                # per (track slot, edge): S0 = sum 1/v, S1 = sum l/v, count, rejected
-_BONE_EDGES = {}                     # (device, edges, edge_mirror) -> their device copies
 
 
 class BoneLengths(NamedTuple):
@@ -842,12 +862,9 @@ def track_bone_lengths(poses: Optional[torch.Tensor], covariance: Optional[torch
     from metro_pose3d_amd.frame_formats import _upload
     lib = _lib.load()
     e, em = np.ascontiguousarray(e, np.int32), np.ascontiguousarray(em, np.int32)
-    key = (str(dev), e.tobytes(), em.tobytes())
-    if key not in _BONE_EDGES:                              # a skeleton's two small tables: uploaded once per device
-        if len(_BONE_EDGES) >= 16:
-            _BONE_EDGES.clear()
-        _BONE_EDGES[key] = (_upload(e.reshape(-1), dev), _upload(em, dev))
-    d_edges, d_mirror = _BONE_EDGES[key]
+    # a skeleton's two small tables: uploaded once per device, complete before any stream reads them (_table) -- a non-blocking
+    # upload cached here was ordered on the stream of the first call only, and a later call on another stream could read it early
+    d_edges, d_mirror = _table(e.reshape(-1), np.int32, dev), _table(em, np.int32, dev)
     d_fallback = _upload(fallback, dev) if fallback is not None else None
     d_poses = d_cov = d_rows = d_starts = None
     if n > 0 and n_rows > 0:
@@ -1018,7 +1035,9 @@ def backproject_bone_lengths(coords01: torch.Tensor, inv_intrinsics, bone_length
                              edges: Optional[Sequence[Tuple[int, int]]] = None, root_relative: bool = False,
                              permute: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """coords01 [N,J,3] (head order) + inv_intrinsics [N,3,3] + target bone lengths [E] (dataset means) or [N,E]
-    (per pose) -> (coords3d_pred [N,J or Jout,3] mm in camera space, z_offset [N])."""
+    (per pose) -> (coords3d_pred [N,J or Jout,3] mm in camera space, z_offset [N]).  bone_lengths: host values, or a tensor,
+    which is used where it is (cast to float64 on the device of coords01): with coords01 and inv_intrinsics on the device too
+    the call uploads nothing and does not wait for its stream."""
     lib = _lib.load()
     dev = coords01.device
     c = _f32(coords01, dev, (spec.skeleton.n_head, 3))
@@ -1027,8 +1046,11 @@ def backproject_bone_lengths(coords01: torch.Tensor, inv_intrinsics, bone_length
     e = np.asarray(spec.skeleton.head_edges if edges is None else edges, dtype=np.int32).reshape(-1, 2)
     if e.size == 0 or e.min() < 0 or e.max() >= spec.skeleton.n_head:
         raise ValueError('edges must index head joints')
-    te = torch.from_numpy(np.ascontiguousarray(e)).to(dev)
-    t = torch.as_tensor(np.asarray(bone_lengths, dtype=np.float64), device=dev).contiguous()
+    te = _table(e, np.int32, dev)
+    if isinstance(bone_lengths, torch.Tensor):             # device-resident targets are used where they are: no upload, no wait
+        t = bone_lengths.to(device=dev, dtype=torch.float64).contiguous()
+    else:
+        t = torch.as_tensor(np.asarray(bone_lengths, dtype=np.float64), device=dev).contiguous()
     if t.shape not in ((len(e),), (n, len(e))):
         raise ValueError(f'bone_lengths must be [{len(e)}] or [{n},{len(e)}], got {tuple(t.shape)}')
     cs = spec.to_c(1)
@@ -1075,7 +1097,7 @@ def to_orig_cam(coords: torch.Tensor, rot_to_orig_cam, mirror_mapping: Sequence[
     m = np.asarray(mirror_mapping, dtype=np.int32)
     if m.shape != (nj,) or m.min() < 0 or m.max() >= nj:
         raise ValueError(f'mirror_mapping must be a permutation-like int array of length {nj}')
-    tm = torch.from_numpy(m).to(dev)
+    tm = _table(m, np.int32, dev)
     out = torch.empty_like(x)
     check(lib.metro_to_orig_cam(_p(x), _p(r), _p(tm), _p(out), n, nj, _stream(dev)), 'metro_to_orig_cam')
     return out
