@@ -163,6 +163,12 @@ int  metro_plan_layer_kernel(const MetroPlan* plan, int32_t index, int32_t n, ch
  * one that did not fit ends in " ...". */
 int  metro_kernel_notes(int32_t mode);
 const char* metro_last_kernel_id(void);
+/* The tile-walk schedule of the last PERSISTENT launch on this thread since metro_kernel_notes(1 | 2) -- a kernel whose grid is
+ * capped at CUs x resident blocks per CU and whose blocks walk several tiles (conv_pw64, conv_pws, conv_b1_chain, conv3x3_c64,
+ * stem_pool_f16<split*>):  out[0] the grid launched, out[1] the work items (pixel tiles x halves, or patches), out[2] the grid
+ * cap the launcher used, out[3] `halves` (blocks that share a pixel tile, one per slab of output channels; else 1).  All zero
+ * when no such launch was noted.  In a dry run (mode 2) no device is asked: out[0] is the uncapped grid and out[2] is 0. */
+int  metro_last_launch_schedule(int32_t out[4]);
 /* Binds the uploaded parameter blob (device pointer, metro_plan_param_bytes() long). */
 int  metro_plan_bind_params(MetroPlan* plan, const void* d_param_blob);
 

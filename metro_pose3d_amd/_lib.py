@@ -136,6 +136,7 @@ SIGNATURES = {
     'metro_plan_layer_kernel': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_char_p, C.c_int32]),
     'metro_kernel_notes': (C.c_int, [C.c_int32]),
     'metro_last_kernel_id': (C.c_char_p, []),
+    'metro_last_launch_schedule': (C.c_int, [C.POINTER(C.c_int32)]),
     'metro_plan_set_graph_max_batch': (C.c_int, [_P, C.c_int32]),
     'metro_forward': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
     'metro_forward_coords01': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),

@@ -239,7 +239,11 @@ int launch_conv3x3_c64(const MetroConvDesc& d, const void* in, const void* w, co
                        const ConvPre1* pre1) {
     if (!conv3x3_c64_supported(d)) { set_error("conv3x3_c64: unsupported layer"); return METRO_ERR_UNSUPPORTED; }
     const bool p1 = pre1 != nullptr && pre1->w1 != nullptr;
-    if (note_kernel(p1 ? "conv3x3_c64<pre1>" : "conv3x3_c64")) return METRO_OK;
+    if (note_kernel(p1 ? "conv3x3_c64<pre1>" : "conv3x3_c64")) {
+        const int work = (int)((long)d.n * d.h_out * d.w_out / c64::TN);
+        note_schedule(work, work, 0, 1);
+        return METRO_OK;
+    }
     C64Args a;
     a.in = static_cast<const half_t*>(in); a.w = static_cast<const half_t*>(w); a.bias = bias; a.out = static_cast<half_t*>(out);
     a.m_total = d.n * d.h_out * d.w_out; a.h = d.h_out; a.w_map = d.w_out; a.relu = d.relu;
@@ -257,6 +261,7 @@ int launch_conv3x3_c64(const MetroConvDesc& d, const void* in, const void* w, co
     // contiguous tile ranges per block: consecutive tiles share their halo rows through the L2 of one XCD
     a.tiles_per_block = (a.n_tiles + grid_cap - 1) / grid_cap;
     const int grid = (a.n_tiles + a.tiles_per_block - 1) / a.tiles_per_block;
+    note_schedule(grid, a.n_tiles, grid_cap, 1);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(c64::NT), c64::LDS_BYTES, stream, a);
     return launch_status("conv3x3_c64");
 }

@@ -363,13 +363,7 @@ __global__ __launch_bounds__(Cfg::NT) void conv3x3_f16_slab_kernel(
     const float* __restrict__ bias, half_t* __restrict__ out, int tiles_m, int halo, int sgd) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int nblk = gridDim.x;
-    int lid;
-    {
-        const int b = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = b & 7, idx = b >> 3;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int lid = xcd_block_lid(blockIdx.x, nblk);
     const int tile_n = lid / tiles_m;
     const int tile_m = lid % tiles_m;
     slab_tile<Cfg>(a, in, w, bias, out, halo, tile_n * Cfg::TN, tile_m * Cfg::TM, smem, threadIdx.x, sgd);

@@ -331,7 +331,10 @@ bool conv_b1_chain_supported(const MetroConvDesc& d, const ConvFused& f) {
 template <bool REB, int OUTM>
 static int launch_b1(B1Args a, hipStream_t stream) {
     if (note_kernel("conv_b1_chain<%s%s>", REB ? "rebuild" : "projsc", OUTM == 1 ? ",noout" : OUTM == 2 ? ",subout" : ""))
+    {
+        note_schedule(a.m_total / b1::TN, a.m_total / b1::TN, 0, 1);
         return METRO_OK;
+    }
     auto kern = conv_b1_chain_kernel<REB, OUTM>;
     constexpr int lds = b1::Lay<REB>::LDS;
     a.n_tiles = a.m_total / b1::TN;
@@ -340,6 +343,7 @@ static int launch_b1(B1Args a, hipStream_t stream) {
     if (const int st = ensure_dyn_lds_and_grid_cap(reinterpret_cast<const void*>(kern), b1::NT, lds, cap, "conv_b1_chain", 1, &grid_cap))
         return st;
     const int grid = a.n_tiles < grid_cap ? a.n_tiles : grid_cap;
+    note_schedule(grid, a.n_tiles, grid_cap, 1);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(b1::NT), lds, stream, a);
     return launch_status("conv_b1_chain");
 }

@@ -80,13 +80,7 @@ __device__ __forceinline__ void conv_dma_body(
 
     // XCD-aware (bijective) block -> tile map: the blocks of one XCD share pixel tiles in their L2
     const int nblk = gridDim.x;
-    int lid;
-    {
-        const int b = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = b & 7, idx = b >> 3;
-        lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int lid = xcd_block_lid(blockIdx.x, nblk);
     const int tile_n = lid / tiles_m;
     const int tile_m = lid % tiles_m;
     const int m0 = tile_n * Cfg::TN;

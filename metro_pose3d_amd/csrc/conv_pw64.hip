@@ -166,15 +166,9 @@ __global__ __launch_bounds__(pw::NT) void conv_pw64_kernel(Pw64Args a) {
     // SAME XCD (PMC: with consecutive block ids block4's conv3 fetched its input 8 times, 203 MB instead of 84 MB).
     const int halves = a.c_out / CB;
     const int G = gridDim.x / halves;                       // tile streams
-    int half, t;
-    if ((gridDim.x & 7) == 0 && ((gridDim.x >> 3) % halves) == 0) {
-        const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        half = j % halves;
-        t = xcd * ((gridDim.x >> 3) / halves) + j / halves;
-    } else {
-        half = blockIdx.x % halves;
-        t = blockIdx.x / halves;
-    }
+    const BlockStream bs_map = block_stream_map(blockIdx.x, gridDim.x, halves);
+    const int half = bs_map.half;
+    int t = bs_map.first;
     if (t >= a.n_tiles) return;
     a.w += (size_t)half * CB * K;
     a.bias += half * CB;
@@ -671,8 +665,11 @@ template <int K, int WM, bool PRO, bool RES, int MODE2, bool RSUB = false, bool 
 static int launch_pw(Pw64Args a, hipStream_t stream) {
     if (note_kernel("conv_pw64<k%d,wm%d%s%s%s%s%s%s%s%s>", K, WM, CB == 512 ? ",cb512" : "", PRO ? ",pro" : "", RES ? ",res" : "",
                     MODE2 == 1 ? ",pair" : MODE2 == 2 ? ",next" : "", RSUB ? ",ressub" : "", PSC ? ",projsc" : "", REB ? ",rebuild" : "",
-                    OUTM == 1 ? ",noout" : OUTM == 2 ? ",subout" : ""))
+                    OUTM == 1 ? ",noout" : OUTM == 2 ? ",subout" : "")) {
+        const int work = (a.m_total + pw::Lay<K, WM, CB>::TN - 1) / pw::Lay<K, WM, CB>::TN * (a.c_out / CB);
+        note_schedule(work, work, 0, a.c_out / CB);
         return METRO_OK;
+    }
     auto kern = conv_pw64_kernel<K, WM, PRO, RES, MODE2, RSUB, PSC, CB, REB, OUTM>;
     constexpr int lds = pw::lds_bytes<K, WM, RES, MODE2, PSC, CB, REB>();
     a.n_tiles = (a.m_total + pw::Lay<K, WM, CB>::TN - 1) / pw::Lay<K, WM, CB>::TN;
@@ -684,6 +681,7 @@ static int launch_pw(Pw64Args a, hipStream_t stream) {
     const int halves = a.c_out / CB;
     int grid = a.n_tiles * halves < grid_cap ? a.n_tiles * halves : grid_cap;
     grid -= grid % halves;
+    note_schedule(grid, a.n_tiles * halves, grid_cap, halves);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(pw::NT), lds, stream, a);
     return launch_status("conv_pw64");
 }

@@ -71,15 +71,8 @@ __global__ __launch_bounds__(pws::NT) void conv_pws_kernel(PwsArgs a) {
     // (blocks are dealt round-robin to the 8 XCDs), as in conv_pw64.hip
     const int halves = a.c_out / CB;
     const int G = gridDim.x / halves;                       // tile streams
-    int half, t0;
-    if ((gridDim.x & 7) == 0 && ((gridDim.x >> 3) % halves) == 0) {
-        const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        half = j % halves;
-        t0 = xcd * ((gridDim.x >> 3) / halves) + j / halves;
-    } else {
-        half = blockIdx.x % halves;
-        t0 = blockIdx.x / halves;
-    }
+    const BlockStream bs_map = block_stream_map(blockIdx.x, gridDim.x, halves);
+    const int half = bs_map.half, t0 = bs_map.first;
     if (t0 >= a.n_tiles) return;
     const int T = (a.n_tiles - t0 + G - 1) / G;             // tiles of this block: t0, t0 + G, ...
     const int ldo = a.c_out;
@@ -213,7 +206,11 @@ bool conv_pws_supported(const MetroConvDesc& d) {
 
 template <int K>
 static int launch_pws(PwsArgs a, hipStream_t stream) {
-    if (note_kernel("conv_pws<k%d,res>", K)) return METRO_OK;
+    if (note_kernel("conv_pws<k%d,res>", K)) {
+        const int work = a.m_total / pws::TN * (a.c_out / pws::CB);
+        note_schedule(work, work, 0, a.c_out / pws::CB);
+        return METRO_OK;
+    }
     auto kern = conv_pws_kernel<K>;
     constexpr int lds = pws::Lay<K>::LDS;
     a.n_tiles = a.m_total / pws::TN;
@@ -223,6 +220,7 @@ static int launch_pws(PwsArgs a, hipStream_t stream) {
     const int halves = a.c_out / pws::CB;
     int grid = a.n_tiles * halves < grid_cap ? a.n_tiles * halves : grid_cap;
     grid -= grid % halves;
+    note_schedule(grid, a.n_tiles * halves, grid_cap, halves);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(pws::NT), lds, stream, a);
     return launch_status("conv_pws");
 }

@@ -17,7 +17,7 @@ void set_error(const char* fmt, ...) {
 }
 const char* get_error() { return g_err; }
 
-static thread_local KernelNotes g_notes = {0, ""};
+static thread_local KernelNotes g_notes = {0, "", {0, 0, 0, 0}};
 KernelNotes& kernel_notes() { return g_notes; }
 bool note_kernel(const char* fmt, ...) {
     if (g_notes.mode == 0) return false;
@@ -74,9 +74,15 @@ int metro_kernel_notes(int32_t mode) {
     METRO_CHECK_ARG(mode >= 0 && mode <= 2, "metro_kernel_notes: mode must be 0 (off), 1 (record) or 2 (dry run)");
     KernelNotes& kn = kernel_notes();
     kn.mode = mode; kn.ids[0] = 0;
+    for (int i = 0; i < 4; ++i) kn.schedule[i] = 0;
     return METRO_OK;
 }
 const char* metro_last_kernel_id(void) { return kernel_notes().ids; }
+int metro_last_launch_schedule(int32_t out[4]) {
+    METRO_CHECK_ARG(out != nullptr, "metro_last_launch_schedule: out is NULL");
+    for (int i = 0; i < 4; ++i) out[i] = kernel_notes().schedule[i];
+    return METRO_OK;
+}
 
 int metro_conv_f16(const MetroConvDesc* d, const void* d_in, const void* d_w, const float* d_bias,
                    const void* d_pro_scale, const void* d_pro_shift, const void* d_residual,

@@ -50,9 +50,53 @@ inline int tuning_knob(const char* name, int dflt) {
 // launch.  Off (the default) it is one thread-local load; mode 1 appends the id to a thread-local string
 // (metro_last_kernel_id); mode 2 is a DRY RUN: the id is recorded and the launcher returns METRO_OK without touching
 // the device (metro_plan_layer_kernel, and the coverage test in tests/test_kernel_coverage.py, work without a GPU).
-struct KernelNotes { int mode; char ids[4096]; };   // holds the ids of a whole forward; a string that did not fit ends in " ..." (tests assert against it)
+struct KernelNotes {
+    int mode;
+    char ids[4096];       // holds the ids of a whole forward; a string that did not fit ends in " ..." (tests assert against it)
+    int32_t schedule[4];  // the last persistent launch's tile-walk schedule (note_schedule; metro_last_launch_schedule)
+};
 KernelNotes& kernel_notes();
 bool note_kernel(const char* fmt, ...) __attribute__((format(printf, 1, 2)));   // true = dry run: skip the launch
+// The schedule of a persistent launch -- a launcher that caps its grid with ensure_dyn_lds_and_grid_cap and lets a block walk several
+// tiles -- recorded right after the launcher has computed its grid: the grid launched, the work items (tiles x halves, or
+// patches), the grid cap (CUs x resident blocks per CU: known on the device only) and `halves` (blocks that share a tile, one per
+// output-channel slab; 1 where a block owns its tiles).  What a block's tile loop does -- buffer parity, counted waits, ramp and
+// drain -- follows from these four (tests/test_gpu_persistent_schedules.py: schedule_class).  Off (the default) this is one
+// thread-local load, like note_kernel.  A dry run reaches no device: its launchers record the uncapped grid and a cap of 0.
+inline void note_schedule(int grid, int work, int cap, int halves) {
+    KernelNotes& kn = kernel_notes();
+    if (kn.mode == 0) return;
+    kn.schedule[0] = grid; kn.schedule[1] = work; kn.schedule[2] = cap; kn.schedule[3] = halves;
+}
+
+// ---- block -> tile maps of the grids that deal their blocks round-robin to the 8 XCDs (one L2 each) -------------------------------
+// Integer arithmetic on blockIdx / gridDim only, __host__ __device__ so that tests/test_block_tile_maps.py walks them on the
+// host for every grid a device could ask for.
+// conv_pw64.hip / conv_pws.hip: `grid` = halves x G blocks serve G tile streams; block b works on the CB-channel slab `half` of the
+// tiles first, first + G, ...  The `halves` blocks that share a tile are placed on the SAME XCD (b & 7) wherever the grid splits
+// into eight equal runs of whole streams; otherwise consecutive blocks share a tile.
+struct BlockStream { int half, first; };
+// (block and grid keep the unsigned type of blockIdx.x / gridDim.x: the divisions by `halves` are the unsigned ones the kernels
+// were built with)
+__host__ __device__ __forceinline__ BlockStream block_stream_map(unsigned block, unsigned grid, int halves) {
+    BlockStream s;
+    if ((grid & 7) == 0 && ((grid >> 3) % halves) == 0) {
+        const int xcd = block & 7, j = block >> 3;
+        s.half = j % halves;
+        s.first = xcd * ((grid >> 3) / halves) + j / halves;
+    } else {
+        s.half = block % halves;
+        s.first = block / halves;
+    }
+    return s;
+}
+// conv_igemm_f16_dma.hip / conv3x3_f16_slab.hip: one tile per block; the blocks of one XCD get a contiguous run of tile ids
+// (bijective for any nblk: the first nblk & 7 XCDs hold one block more)
+__host__ __device__ __forceinline__ int xcd_block_lid(int block, int nblk) {
+    const int q = nblk >> 3, r = nblk & 7;
+    const int xcd = block & 7, idx = block >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
 
 // 16-byte activation store of an epilogue, in the form its translation unit chose with METRO_WT_STORES:
 //   0  plain: the line stays DIRTY in the writing XCD's L2 (the eight L2s are not coherent), and the release at the end of the

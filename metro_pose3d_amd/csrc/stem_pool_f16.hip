@@ -816,7 +816,10 @@ int launch_stem_pool_u8in(const unsigned char* images, const void* w, const floa
 
 template <int NSPLIT, int INPUT>
 static int launch_sp(const StemPoolArgs& a, hipStream_t stream) {
-    if (note_kernel("stem_pool_f16<split%d%s>", NSPLIT, INPUT == IN_F32 ? ",f32in" : INPUT == IN_U8 ? ",u8in" : "")) return METRO_OK;
+    if (note_kernel("stem_pool_f16<split%d%s>", NSPLIT, INPUT == IN_F32 ? ",f32in" : INPUT == IN_U8 ? ",u8in" : "")) {
+        note_schedule(a.n_patches, a.n_patches, 0, 1);
+        return METRO_OK;
+    }
     auto kern = stem_pool_f16_kernel<NSPLIT, INPUT>;
     constexpr int NT = 64 * sp::MG * NSPLIT;
     static PerDeviceInt cap;
@@ -824,6 +827,7 @@ static int launch_sp(const StemPoolArgs& a, hipStream_t stream) {
     if (const int st = ensure_dyn_lds_and_grid_cap(reinterpret_cast<const void*>(kern), NT, sp::LDS_BYTES, cap, "stem_pool_f16", 0, &grid_cap))
         return st;
     const int grid = a.n_patches < grid_cap ? a.n_patches : grid_cap;
+    note_schedule(grid, a.n_patches, grid_cap, 1);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), sp::LDS_BYTES, stream, a);
     return launch_status("stem_pool_f16");
 }

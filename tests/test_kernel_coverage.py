@@ -444,6 +444,51 @@ def test_every_kernel_has_a_nonfinite_case(lib):
     assert kernel_of('stem_pool_f16<rows,f32in>') != kernel_of('stem_pool_f16<split2,f32in>')
 
 
+# the launchers that cap their grid and let a block walk several tiles (metro_common.h: note_schedule)
+PERSISTENT_FAMILIES = ('conv_pw64<', 'conv_pws<', 'conv_b1_chain<', 'conv3x3_c64', 'stem_pool_f16<split')
+
+
+def test_every_persistent_instantiation_has_its_schedule_cases(lib):
+    """A persistent kernel keeps state from one tile to the next, so an instantiation is held not only at a shape but on every
+    tile-walk schedule its predicate admits (tests/test_gpu_persistent_schedules.py: ADMITTED, CASES).  Every id of the five
+    persistent families that pair_universe() or the grid of test_dispatch_closure dispatches (h36m heads: the backbones of the
+    other heads are the same, which test_dispatch_closure asserts) must have a case for each class of its row: a new persistent
+    instantiation cannot enter the plans without its schedules.  The rows' one shape claim -- whether the instantiation runs a
+    pixel count that is no multiple of its tile -- is put to the entry points by a dry run.
+    What this does and does not hold: CASES is generated from ADMITTED, so for an id that HAS a row the per-class lookup below
+    cannot fail; the live parts are the missing row (a new id), the ragged flag, and that the stem and conv_b1_chain rows are
+    the full lists of the module.  Whether a row names every schedule its kernel has is a matter of review, not of this test."""
+    from tests import test_gpu_persistent_schedules as PS
+    ids = {part for kid, _ in pair_universe() for part in kid.split(' & ')}
+    for side in GRID_SIDES:
+        for arch in GRID_ARCHS:
+            for stride in GRID_STRIDES:
+                run = DryRun(ModelSpec(arch, stride, 'h36m', proc_side=side))
+                layers = [i for i, name in enumerate(run.names) if name not in ('logits', 'softargmax')]
+                for n in GRID_BATCHES:
+                    ids.update(part for kid in run.kernels(n, layers) for part in kid.split(' & '))
+    persistent = sorted(k for k in ids if k.startswith(PERSISTENT_FAMILIES))
+    assert len(persistent) >= 15, persistent
+    have = {(inst.kid, cls) for inst, cls in PS.CASES}
+    missing = [(k, cls) for k in persistent for cls in PS.ADMITTED.get(k, ('<no row in ADMITTED>',)) if (k, cls) not in have]
+    assert not missing, 'persistent instantiations dispatched by the plans without a schedule case:\n' + '\n'.join(f'  {k}: {c}' for k, c in missing)
+    full = {'pw64': PS.STRIDED, 'pws': PS.STRIDED, 'b1': PS.NO_MAP, 'c64': PS.C64_CLASSES, 'stem': PS.STEM_CLASSES}
+    for inst in PS.INSTANCES:           # no row is trimmed: the family's whole list, the four sub-sampled variants for `two-three`
+        want = set(full[inst.family])
+        if 'subout' in inst.kid:
+            want = want - {'two-three'} | set(PS.SUBOUT)
+        assert set(PS.ADMITTED[inst.kid]) - {'ragged-late'} == want, inst.kid
+    for inst in PS.INSTANCES:
+        if inst.family in ('c64', 'stem'):
+            assert 'ragged-late' not in PS.ADMITTED[inst.kid]          # whole tiles by construction (map rows, patches)
+            continue
+        try:
+            (noted, _), _ = PS.dry_run(lib, inst, 'ragged-late', 256)
+        except ValueError:                                             # the entry refuses the shape
+            noted = []
+        assert (tuple(noted) == inst.before + (inst.kid,)) == ('ragged-late' in PS.ADMITTED[inst.kid]), (inst.kid, noted)
+
+
 @pytest.mark.parametrize('nb', [3, 8], ids=['64-pixel-tiles', '256-pixel-tiles'])
 def test_head_partials_slot_covers_large_heat_maps(lib, nb):
     """The one-launch head writes one fp32 record per (image, slab, joint): one per 64 pixels, and one per 32 pixels once the
