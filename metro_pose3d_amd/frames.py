@@ -638,19 +638,19 @@ def _warp_views(frames, cameras, boxes, fi, vs: Views, side: int, device: torch.
 
 def _synchronise(bad: Optional[torch.Tensor], boxes, also: Optional[torch.Tensor] = None):
     """The one read of a call, after everything is enqueued: the finite screen folded on the device (`bad`; None: not asked for)
-    and, for _DeviceBoxes, their frame status in one transfer -> the number of non-finite crops.  ValueError for a device
-    frame index outside its range.  Host boxes and no screen: nothing to read, no synchronisation.
+    and, for _DeviceBoxes, their frame status in one transfer.  ValueError for a device frame index outside its range.  Host
+    boxes and no screen: nothing to read, no synchronisation.
     also: one more device integer the caller needs on the host (the persons metro_cluster_views found), read in the same
-    transfer -> (the number of non-finite crops, that integer or None)."""
+    transfer.  -> (the number of non-finite crops, that integer or None)."""
     if also is None and not isinstance(boxes, _DeviceBoxes):
-        return int(bad.item()) if bad is not None else 0
+        return (int(bad.item()) if bad is not None else 0), None
     words = [t.reshape(-1)[:1].to(torch.int64) for t in (boxes.frame_status[0] if isinstance(boxes, _DeviceBoxes) else None, bad, also)
              if t is not None]
     words = torch.cat(words).tolist()
     if isinstance(boxes, _DeviceBoxes):
         _raise_on_bad_frames(words.pop(0), len(boxes), boxes.frame_status[1])
     n_bad = words.pop(0) if bad is not None else 0
-    return n_bad if also is None else (n_bad, words.pop(0))
+    return n_bad, (words.pop(0) if also is not None else None)
 
 
 class _Call(NamedTuple):
@@ -963,6 +963,28 @@ def _forward_coords01(eng, crops: torch.Tensor, check_finite: bool, moments: boo
     return (rel, coords01, bad, (cov01, peak)) if moments else (rel, coords01, bad)
 
 
+def _joint_names(sk) -> np.ndarray:
+    return np.array(sk.names_bytes(), dtype=object)
+
+
+def _place_poses(eng, coords01, rel, places, scale_recovery: str, coords: str, d_targets=None, per_pose: int = 0, root_z=None):
+    """One metro_place_poses launch over the m crop rows the forward wrote -> (poses [m, Jout, 3], keypoints [m, Jout, 2], z offsets
+    [m] or None in 'metro' mode, the mirror table on the device).  d_targets: bone lengths on the device; root_z: host float32 [m]."""
+    sk, m, device = eng.spec.skeleton, len(coords01), coords01.device
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
+    poses_v, keypoints_v, z_v = f32(m, sk.n_out, 3), f32(m, sk.n_out, 2), f32(m) if scale_recovery != 'metro' else None
+    mirror = _upload(np.asarray(sk.out_mirror, np.int32), device)
+    d_root = _upload(root_z, device) if root_z is not None else None
+    d_edges = _upload(np.asarray(sk.head_edges, np.int32).reshape(-1, 2), device) if d_targets is not None else None
+    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    check(_lib.load().metro_place_poses(ptr(coords01), ptr(rel), ptr(places), m, C.byref(eng.cspec), SCALE_RECOVERY[scale_recovery],
+                                        ptr(d_targets), per_pose, ptr(d_root), ptr(d_edges), len(sk.head_edges), ptr(mirror),
+                                        COORDS[coords], ptr(poses_v), ptr(keypoints_v), ptr(z_v), C.c_void_p(stream)),
+          'metro_place_poses')
+    return poses_v, keypoints_v, z_v, mirror
+
+
 def _locate_poses_views(call: _Call, model_path, cameras, scale_recovery, targets, per_pose, root_z, coords, sk,
                         uncertainty: bool = False):
     """-> (FramePoses, spread [n, Jout])."""
@@ -970,15 +992,14 @@ def _locate_poses_views(call: _Call, model_path, cameras, scale_recovery, target
     n, nv = len(call.boxes), len(call.vs.zoom)
     m = n * nv
     device = _call_device(call.boxes, call.frames)
-    names = np.empty(sk.n_out, dtype=object)
-    names[:] = sk.names_bytes()
-    absolute = scale_recovery != 'metro'
-    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
+    names = _joint_names(sk)
     with torch.cuda.device(device):
         eng = _engine_for(model_path, call.precision, device, max(m, 1))
         if n == 0:
+            f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
             unc = (f32(0, sk.n_out, 3, 3), f32(0, sk.n_out)) if uncertainty else (None, None)
-            return (FramePoses(f32(0, sk.n_out, 3), f32(0, sk.n_out, 2), f32(0) if absolute else None, sk.edges_array(), names, *unc),
+            return (FramePoses(f32(0, sk.n_out, 3), f32(0, sk.n_out, 2), f32(0) if scale_recovery != 'metro' else None,
+                               sk.edges_array(), names, *unc),
                     torch.zeros((0, sk.n_out), dtype=torch.float32, device=device))
         crops, places = _warp_views(call.frames, cameras, call.boxes, call.fi, call.vs, eng.spec.proc_side, device, call.crop_dtype)
         rel, coords01, bad, *mom = _forward_coords01(eng, crops, call.check_finite, uncertainty)
@@ -988,19 +1009,11 @@ def _locate_poses_views(call: _Call, model_path, cameras, scale_recovery, target
             if per_pose:                                # per-box targets, repeated per view by index (box-major rows)
                 targets = np.repeat(targets, nv, axis=0)
             d_targets = _upload(targets, device) if targets is not None else None
-        poses_v, keypoints_v, z_v = f32(m, sk.n_out, 3), f32(m, sk.n_out, 2), f32(m) if absolute else None
-        mirror = _upload(np.asarray(sk.out_mirror, np.int32), device)
-        d_root = _upload(np.repeat(root_z, nv), device) if root_z is not None else None
-        d_edges = _upload(np.asarray(sk.head_edges, np.int32).reshape(-1, 2), device) if targets is not None else None
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        check(_lib.load().metro_place_poses(ptr(coords01), ptr(rel), ptr(places), m, C.byref(eng.cspec), SCALE_RECOVERY[scale_recovery],
-                                            ptr(d_targets), per_pose, ptr(d_root), ptr(d_edges), len(sk.head_edges),
-                                            ptr(mirror), COORDS[coords], ptr(poses_v), ptr(keypoints_v), ptr(z_v),
-                                            C.c_void_p(stream)), 'metro_place_poses')
+        poses_v, keypoints_v, z_v, mirror = _place_poses(eng, coords01, rel, places, scale_recovery, coords, d_targets, per_pose,
+                                                         np.repeat(root_z, nv) if root_z is not None else None)
         poses, keypoints, z_offset, spread = _merge_views(poses_v, keypoints_v, z_v, places, mirror, n, nv, spread=True)
         unc = tuple(_place_covariances(eng.spec, mom[0][0], mom[0][1], places, coords, n, nv)) if uncertainty else (None, None)
-        _raise_on_non_finite(eng.spec, call.precision, _synchronise(bad, call.boxes), m)    # the call's one stream synchronisation
+        _raise_on_non_finite(eng.spec, call.precision, _synchronise(bad, call.boxes)[0], m)     # the call's one stream synchronisation
     return FramePoses(poses, keypoints, z_offset, sk.edges_array(), names, *unc), spread
 
 
@@ -1075,23 +1088,36 @@ def triangulate_poses_in_frames(frames, boxes, model_path, cameras, person_index
     screen; NonFiniteError).  No boxes: empty tensors, no launch.  ValueError before any launch for cameras=None or one Camera
     for several frames, a negative person index, index lengths other than the number of boxes, an unknown `weights`, and
     min_angle_deg outside (0, 90]."""
-    from metro_pose3d_amd.heads import triangulation_min_det
-    triangulation_min_det(weights, min_angle_deg)
-    n_boxes = _n_boxes(boxes)
-    pi = np.asarray(_host_array(person_index), np.int64).reshape(-1)
-    fi = np.asarray(_host_array(frame_index), np.int64).reshape(-1)
-    if len(pi) != n_boxes or len(fi) != n_boxes:
-        raise ValueError(f'person_index and frame_index must hold one value per box ({n_boxes}), got {len(pi)} and {len(fi)}')
+    from metro_pose3d_amd.heads import Triangulation
+    triangulation = Triangulation.checked(weights, min_angle_deg)
+    n_boxes, fi, pi = _box_frames(boxes, frame_index, person_index, 'person_index')
     if n_boxes and pi.min() < 0:
         raise ValueError(f'person_index must not be negative, got {pi.min()}')
     _check_rig(cameras, fi, n_boxes)
     call = _checked_call(frames, boxes, fi, 'world', views, geometry, precision, check_finite, pixel_format, color_matrix,
                          crop_dtype)
-    return _world_poses(call, model_path, cameras, fi, weights, min_angle_deg, person_index=pi)[0]
+    if len(call.boxes) == 0:
+        return _no_persons(_model_skeleton(model_path), _call_device(call.boxes, call.frames)).world
+    return _finish_world(call, _enqueue_world(call, model_path, cameras, fi, triangulation, person_index=pi))[0]
 
 
 def _n_boxes(boxes) -> int:
     return int(boxes.shape[0]) if isinstance(boxes, torch.Tensor) else len(np.asarray(boxes, np.float64).reshape(-1, 4))
+
+
+def _box_frames(boxes, frame_index, other_index=None, other: str = ''):
+    """(the number of boxes, frame_index as int64 [n]: None is frame 0), before any launch; with a second host index per box
+    (person_index, track_index; `other`: its name), that one as int64 [n] too."""
+    n_boxes = _n_boxes(boxes)
+    fi = np.zeros(n_boxes, np.int64) if frame_index is None else np.asarray(_host_array(frame_index), np.int64).reshape(-1)
+    if other_index is None:
+        if len(fi) != n_boxes:
+            raise ValueError(f'frame_index must hold one value per box ({n_boxes}), got {len(fi)}')
+        return n_boxes, fi
+    oi = np.asarray(_host_array(other_index), np.int64).reshape(-1)
+    if len(oi) != n_boxes or len(fi) != n_boxes:
+        raise ValueError(f'{other} and frame_index must hold one value per box ({n_boxes}), got {len(oi)} and {len(fi)}')
+    return n_boxes, fi, oi
 
 
 def _check_rig(cameras, fi: np.ndarray, n_boxes: int) -> None:
@@ -1105,68 +1131,86 @@ def _check_rig(cameras, fi: np.ndarray, n_boxes: int) -> None:
         raise ValueError(f'frame_index must lie in [0, {len(cameras)}) (one Camera per frame), got [{fi.min()}, {fi.max()}]')
 
 
-def _world_poses(call: _Call, model_path, cameras, fi: np.ndarray, weights: str, min_angle_deg: float, person_index=None,
-                 match=None, step_index=None, covariance: bool = False, then=None):
-    """The chain triangulate_poses_in_frames, match_poses_in_frames and follow_world_poses_in_frames share -> (WorldPoses,
-    None or (person_index, cost, n_pairs), None or (covariance [P, Jout, 9], what `then` returned)).  The persons' crop rows
-    come from the host (person_index: person_groups, uploaded) or, with match = (max_cost_mm, clip_mm, min_joints), from
-    metro_view_affinity and metro_cluster_views on the forward's outputs; the triangulation launch then runs over the upper
-    bound of n persons and the count is read in the call's synchronisation.
-    step_index (host int32 [n], with match): the affinity is gated by time step.  covariance: the triangulation launch also
-    writes the covariance of every joint.  then(spec, n_views, poses, covariance, rows, starts, n_persons, seen): enqueued after
-    the triangulation, before the synchronisation, on the unsliced outputs over the n persons (with match and covariance);
-    seen = (coords01, cov01, places, person_index), what the rays of a person one camera sees are built from."""
+class _WorldChain(NamedTuple):
+    """What _enqueue_world left on the stream: the device tensors of the chain up to the triangulation, unsliced (the per-person
+    ones over the upper bound of n persons when the persons were found on the device)."""
+    eng: object
+    n: int                               # boxes
+    nv: int                              # views per box
+    rel: torch.Tensor                    # the forward's root-relative poses [n V, Jout, 3]
+    coords01: torch.Tensor
+    cov01: Optional[torch.Tensor]        # the heat-map moments, weights 'covariance' only
+    places: torch.Tensor                 # MetroPlacement records uint8 [n V, 208]
+    rows: torch.Tensor                   # the persons' crop rows as a CSR,
+    starts: torch.Tensor                 # from the host (person_groups) or from metro_cluster_views
+    labels: Optional[torch.Tensor]       # metro_cluster_views' person of every box,
+    cost: Optional[torch.Tensor]         # the affinity's cost and
+    n_pairs: Optional[torch.Tensor]      # ray pairs, and
+    n_persons: Optional[torch.Tensor]    # the number of persons found int32 [1]; all four None with a host person_index
+    poses: torch.Tensor
+    n_rays: torch.Tensor
+    residual: torch.Tensor
+    covariance: Optional[torch.Tensor]   # [P, Jout, 9] of every triangulated joint, if asked for
+    bad: Optional[torch.Tensor]          # the finite screen folded on the device
+
+
+def _enqueue_world(call: _Call, model_path, cameras, fi: np.ndarray, triangulation, person_index=None, matching=None,
+                   step_index=None, covariance: bool = False) -> _WorldChain:
+    """The first half of the chain triangulate_poses_in_frames, match_poses_in_frames and the world follower share, for n >= 1
+    boxes: warp, forward, the persons' crop rows and ONE triangulation launch, nothing read back.  The rows come from the host
+    (person_index: person_groups, uploaded) or, with `matching` (heads.Matching), from metro_view_affinity and
+    metro_cluster_views on the forward's outputs; the triangulation launch then runs over the upper bound of n persons.
+    step_index (host int32 [n], with matching): the affinity is gated by time step.  covariance: the triangulation launch also
+    writes the covariance of every joint.  A caller enqueues what it adds on the record's tensors, then _finish_world."""
     from metro_pose3d_amd.heads import cluster_views, triangulate_joints, view_affinity_steps
     from metro_pose3d_amd.inference import _engine_for
-    sk = _model_skeleton(model_path)
     n, nv = len(call.boxes), len(call.vs.zoom)
-    m = n * nv
-    if match is not None and match[2] is not None and match[2] > sk.n_out:
-        raise ValueError(f'min_joints must be at most the {sk.n_out} output joints of the model, got {match[2]!r}')
     device = _call_device(call.boxes, call.frames)
-    names = np.empty(sk.n_out, dtype=object)
-    names[:] = sk.names_bytes()
-    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
-    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=device)
-    if n == 0:
-        return (WorldPoses(f32(0, sk.n_out, 3), i32(0, sk.n_out), f32(0, sk.n_out), f32(0, sk.n_out, 2), sk.edges_array(), names),
-                None if match is None else (i32(0), f32(0, 0), i32(0, 0)), (f32(0, sk.n_out, 9), None) if covariance else None)
-    moments = weights == 'covariance'
-    matched = n_persons = more = None
+    moments = triangulation.weights == 'covariance'
+    labels = cost = n_pairs = n_persons = None
     with torch.cuda.device(device):
-        eng = _engine_for(model_path, call.precision, device, m)
+        eng = _engine_for(model_path, call.precision, device, n * nv)
         crops, places = _warp_views(call.frames, cameras, call.boxes, call.fi, call.vs, eng.spec.proc_side, device, call.crop_dtype)
         rel, coords01, bad, *mom = _forward_coords01(eng, crops, call.check_finite, moments)
         cov01 = mom[0][0] if moments else None
-        if match is None:
+        if matching is None:
             rows, starts = (_upload(a, device) for a in person_groups(person_index, fi, nv))
         else:
             cost, n_pairs = view_affinity_steps(coords01, cov01, places.reshape(-1), _upload(fi.astype(np.int32), device),
                                                 None if step_index is None else _upload(np.asarray(step_index, np.int32), device),
-                                                eng.spec, nv, weights, min_angle_deg, match[1], match[2])
-            labels, n_persons, rows, starts = cluster_views(cost, match[0], nv)
-            matched = (labels, cost, n_pairs)
-        poses, n_rays, residual, *cov = triangulate_joints(coords01, cov01, places.reshape(-1), rows, starts, eng.spec, weights,
-                                                           min_angle_deg, covariance)
-        if covariance:
-            seen = (coords01, cov01, places.reshape(-1), matched[0] if matched is not None else None)
-            more = (cov[0], then(eng.spec, nv, poses, cov[0], rows, starts, n_persons, seen) if then is not None else None)
-        poses_v, keypoints_v = f32(m, sk.n_out, 3), f32(m, sk.n_out, 2)
-        mirror = _upload(np.asarray(sk.out_mirror, np.int32), device)
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        check(_lib.load().metro_place_poses(ptr(coords01), ptr(rel), ptr(places), m, C.byref(eng.cspec), SCALE_RECOVERY['metro'],
-                                            None, 0, None, None, len(sk.head_edges), ptr(mirror), COORDS['world'], ptr(poses_v),
-                                            ptr(keypoints_v), None, C.c_void_p(stream)), 'metro_place_poses')
-        keypoints = _merge_views(poses_v, keypoints_v, None, places, mirror, n, nv, spread=False)[1]
-        n_bad = _synchronise(bad, call.boxes, n_persons)                                    # the call's one stream synchronisation
-        if match is not None:
-            n_bad, count = n_bad
-            poses, n_rays, residual = poses[:count], n_rays[:count], residual[:count]
-            if covariance:
-                more = (more[0][:count], more[1])
-        _raise_on_non_finite(eng.spec, call.precision, n_bad, m)
-    return WorldPoses(poses, n_rays, residual, keypoints, sk.edges_array(), names), matched, more
+                                                eng.spec, nv, *triangulation, matching.clip_mm, matching.min_joints)
+            labels, n_persons, rows, starts = cluster_views(cost, matching.max_cost_mm, nv)
+        poses, n_rays, residual, *cov = triangulate_joints(coords01, cov01, places.reshape(-1), rows, starts, eng.spec, *triangulation,
+                                                           covariance)
+    return _WorldChain(eng, n, nv, rel, coords01, cov01, places, rows, starts, labels, cost, n_pairs, n_persons, poses, n_rays,
+                       residual, cov[0] if covariance else None, bad)
+
+
+def _finish_world(call: _Call, chain: _WorldChain):
+    """The second half: the keypoints by metro_place_poses and metro_merge_views, then the call's one stream synchronisation (the
+    finite screen, which also brings the number of persons found on the device) -> (WorldPoses sliced to the persons, their
+    number: None with a host person_index, where nothing is sliced).  NonFiniteError from the screen."""
+    sk = chain.eng.spec.skeleton
+    with torch.cuda.device(chain.coords01.device):
+        poses_v, keypoints_v, _, mirror = _place_poses(chain.eng, chain.coords01, chain.rel, chain.places, 'metro', 'world')
+        keypoints = _merge_views(poses_v, keypoints_v, None, chain.places, mirror, chain.n, chain.nv, spread=False)[1]
+        n_bad, count = _synchronise(chain.bad, call.boxes, chain.n_persons)
+        _raise_on_non_finite(chain.eng.spec, call.precision, n_bad, chain.n * chain.nv)
+    return WorldPoses(chain.poses[:count], chain.n_rays[:count], chain.residual[:count], keypoints, sk.edges_array(),
+                      _joint_names(sk)), count
+
+
+def _no_persons(sk, device) -> 'MatchedPoses':
+    """MatchedPoses, and in it the WorldPoses, of a call without boxes: empty tensors, no launch."""
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=device)
+    return MatchedPoses(i32(0), f32(0, 0), i32(0, 0), WorldPoses(f32(0, sk.n_out, 3), i32(0, sk.n_out), f32(0, sk.n_out), f32(0, sk.n_out, 2),
+                                                                 sk.edges_array(), _joint_names(sk)))
+
+
+def _check_min_joints(min_joints, sk) -> None:
+    if min_joints is not None and min_joints > sk.n_out:
+        raise ValueError(f'min_joints must be at most the {sk.n_out} output joints of the model, got {min_joints!r}')
 
 
 # ---- the same, with the persons found on the device: cross-view association (metro_view_affinity, metro_cluster_views) ----
@@ -1206,21 +1250,21 @@ def match_poses_in_frames(frames, boxes, model_path, cameras, frame_index, max_c
     found are empty); the call's one synchronisation stays the finite screen, which also brings the number of persons.
     ValueError before any launch for cameras=None or one Camera for several frames, a frame_index out of range or not one
     per box, more than 128 boxes, max_cost_mm, clip_mm, min_angle_deg or min_joints out of range and an unknown `weights`."""
-    from metro_pose3d_amd.heads import MATCH_MAX_BOXES, matching_params, triangulation_min_det
-    triangulation_min_det(weights, min_angle_deg)
-    matching_params(clip_mm, min_joints, max_cost_mm)
-    n_boxes = _n_boxes(boxes)
-    fi = np.asarray(_host_array(frame_index), np.int64).reshape(-1)
-    if len(fi) != n_boxes:
-        raise ValueError(f'frame_index must hold one value per box ({n_boxes}), got {len(fi)}')
+    from metro_pose3d_amd.heads import MATCH_MAX_BOXES, Matching, Triangulation
+    triangulation = Triangulation.checked(weights, min_angle_deg)
+    matching = Matching.checked(max_cost_mm, clip_mm, min_joints)
+    n_boxes, fi = _box_frames(boxes, frame_index)
     if n_boxes > MATCH_MAX_BOXES:
         raise ValueError(f'{n_boxes} boxes: matching takes at most {MATCH_MAX_BOXES} per call')
     _check_rig(cameras, fi, n_boxes)
     call = _checked_call(frames, boxes, fi, 'world', views, geometry, precision, check_finite, pixel_format, color_matrix,
                          crop_dtype)
-    world, matched, _ = _world_poses(call, model_path, cameras, fi, weights, min_angle_deg,
-                                     match=(float(max_cost_mm), float(clip_mm), None if min_joints is None else int(min_joints)))
-    return MatchedPoses(*matched, world)
+    sk = _model_skeleton(model_path)
+    _check_min_joints(matching.min_joints, sk)
+    if len(call.boxes) == 0:
+        return _no_persons(sk, _call_device(call.boxes, call.frames))
+    chain = _enqueue_world(call, model_path, cameras, fi, triangulation, matching=matching)
+    return MatchedPoses(chain.labels, chain.cost, chain.n_pairs, _finish_world(call, chain)[0])
 
 
 # ---- one camera over time: tracked poses smoothed by a Kalman filter / RTS pass (metro_smooth_tracks) ----
@@ -1318,13 +1362,10 @@ def track_poses_in_frames(frames, boxes, model_path, cameras, track_index, frame
     mode='filter' gives what one long call gives.  In mode 'smooth' a call smooths within itself; its last box per track is
     the filtered value.
     keypoints2d stay raw.keypoints2d: 2D smoothing is not offered."""
-    from metro_pose3d_amd.heads import TRACK_STATE_DOUBLES, smooth_tracks, smoothing_params
-    smoothing_params(mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate)
-    n_boxes = int(boxes.shape[0]) if isinstance(boxes, torch.Tensor) else len(np.asarray(boxes, np.float64).reshape(-1, 4))
-    ti = np.asarray(_host_array(track_index), np.int64).reshape(-1)
-    fi = np.zeros(n_boxes, np.int64) if frame_index is None else np.asarray(_host_array(frame_index), np.int64).reshape(-1)
-    if len(ti) != n_boxes or len(fi) != n_boxes:
-        raise ValueError(f'track_index and frame_index must hold one value per box ({n_boxes}), got {len(ti)} and {len(fi)}')
+    from metro_pose3d_amd.heads import TRACK_STATE_DOUBLES, Smoothing, _smooth_tracks
+    kw = locals()                                           # the keywords by name, for those handed on to locate_poses_in_frames
+    smoothing = Smoothing.checked(mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate)
+    n_boxes, fi, ti = _box_frames(boxes, frame_index, track_index, 'track_index')
     times = _box_times(timestamps, fi, n_boxes)
     rows, starts = track_groups(ti, times)
     n_tracks = len(starts) - 1
@@ -1334,16 +1375,13 @@ def track_poses_in_frames(frames, boxes, model_path, cameras, track_index, frame
             raise ValueError(f'state must be a contiguous float64 tensor [T, Jout, {TRACK_STATE_DOUBLES}] with T >= {n_tracks} '
                              '(new_track_state, or the state of a previous call)')
         starts = np.concatenate([starts, np.full(state.shape[0] - n_tracks, starts[-1], np.int32)])
-    raw = locate_poses_in_frames(frames, boxes, model_path, cameras=cameras, frame_index=frame_index, scale_recovery=scale_recovery,
-                                 bone_lengths=bone_lengths, root_depth=root_depth, coords=coords, precision=precision,
-                                 check_finite=check_finite, views=views, geometry=geometry, pixel_format=pixel_format,
-                                 color_matrix=color_matrix, crop_dtype=crop_dtype, return_uncertainty=True)
+    raw = locate_poses_in_frames(frames, boxes, model_path, cameras=cameras, frame_index=frame_index, return_uncertainty=True,
+                                 **{k: kw[k] for k in _LOCATE_OPTIONS})
     device = raw.poses.device
     if state is None:
         state = new_track_state(n_tracks, raw.poses.shape[1], device)
     with torch.cuda.device(device):
-        poses, velocity, covariance, used = smooth_tracks(raw.poses, raw.covariance, times, rows, starts, mode, measurement, accel_psd,
-                                                          sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, state)
+        poses, velocity, covariance, used = _smooth_tracks(raw.poses, raw.covariance, times, rows, starts, smoothing, state)
     return TrackPoses(poses, velocity, covariance, used, raw, state, raw.joint_edges, raw.joint_names)
 
 
@@ -1398,9 +1436,9 @@ def new_track_table(capacity: int, n_joints_out: int, device) -> TrackTable:
                       torch.zeros((1,), dtype=torch.int32, device=device))
 
 
-def _check_track_table(tracks, capacity):
+def _check_track_table(tracks):
     from metro_pose3d_amd.heads import ASSOC_MAX, TRACK_STATE_DOUBLES
-    ok = (isinstance(tracks, tuple) and len(tracks) == 3 and all(isinstance(t, torch.Tensor) for t in tracks)
+    ok =(isinstance(tracks, tuple) and len(tracks) == 3 and all(isinstance(t, torch.Tensor) for t in tracks)
           and tracks[0].dtype == torch.float64 and tracks[0].dim() == 3 and tracks[0].shape[2] == TRACK_STATE_DOUBLES
           and 1 <= tracks[0].shape[0] <= ASSOC_MAX and tracks[0].is_contiguous()
           and tracks[1].dtype == torch.int32 and tuple(tracks[1].shape) == (tracks[0].shape[0],) and tracks[1].is_contiguous()
@@ -1408,7 +1446,6 @@ def _check_track_table(tracks, capacity):
     if not ok:
         raise ValueError(f'tracks must be a TrackTable(state float64 [T, Jout, {TRACK_STATE_DOUBLES}], ids int32 [T], next_id int32 '
                          f'[1]) with 1 <= T <= {ASSOC_MAX} (new_track_table, or the table of a previous call)')
-    del capacity
 
 
 class BoneTable(NamedTuple):
@@ -1479,48 +1516,49 @@ def follow_poses_in_frames(frames, boxes, model_path, cameras, frame_index, time
     ValueError before any launch for more than 128 boxes on one timestamp, capacity outside [1, 128], a tracks that is no
     table, scale_recovery 'metro', max_cost_mm, clip_mm, min_joints or max_age_s out of range, and whatever
     track_poses_in_frames refuses."""
-    return _follow_poses(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity, max_cost_mm, clip_mm, min_joints,
-                         max_age_s, mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, scale_recovery,
-                         bone_lengths, root_depth, coords, precision, check_finite, views, geometry, pixel_format, color_matrix,
-                         crop_dtype, 'greedy')
+    return _follow_poses(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity,
+                         *_camera_groups(locals(), 'greedy'))
 
 
-def _follow_poses(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity, max_cost_mm, clip_mm, min_joints,
-                  max_age_s, mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, scale_recovery,
-                  bone_lengths, root_depth, coords, precision, check_finite, views, geometry, pixel_format, color_matrix, crop_dtype,
-                  assignment):
-    """follow_poses_in_frames with the assignment rule of heads.associate_tracks chosen ('greedy' there; Follower passes its own)."""
-    from metro_pose3d_amd.heads import associate_tracks, association_params, assignment_rule, smooth_tracks, smoothing_params
-    assignment_rule(assignment)
-    smoothing_params(mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate)
-    association_params(max_cost_mm, clip_mm, min_joints, max_age_s)
-    if scale_recovery == 'metro':
+_CALL_OPTIONS = ('views', 'geometry', 'precision', 'check_finite', 'pixel_format', 'color_matrix', 'crop_dtype')    # _checked_call's
+_LOCATE_OPTIONS = ('scale_recovery', 'bone_lengths', 'root_depth', 'coords') + _CALL_OPTIONS
+
+
+def _camera_groups(kw: dict, assignment):
+    """The keywords of follow_poses_in_frames (`kw` holds them by name: the call's locals(), or Follower's) checked once, here ->
+    (heads.Association, heads.Smoothing, the keywords handed on to locate_poses_in_frames)."""
+    from metro_pose3d_amd.heads import Association, Smoothing
+    association = Association.checked(kw['max_cost_mm'], kw['clip_mm'], kw['min_joints'], kw['max_age_s'], assignment)
+    smoothing = Smoothing.checked(*(kw[k] for k in Smoothing._fields))
+    if kw['scale_recovery'] == 'metro':
         raise ValueError("scale_recovery='metro' returns root-relative poses, in which all persons coincide: following needs "
                          "absolute poses ('bone-lengths' or 'true-root-depth')")
-    n_boxes = _n_boxes(boxes)
-    fi = np.zeros(n_boxes, np.int64) if frame_index is None else np.asarray(_host_array(frame_index), np.int64).reshape(-1)
-    if len(fi) != n_boxes:
-        raise ValueError(f'frame_index must hold one value per box ({n_boxes}), got {len(fi)}')
+    return association, smoothing, {k: kw[k] for k in _LOCATE_OPTIONS}
+
+
+def _check_tracks_or_capacity(tracks, capacity) -> None:
+    """A table to continue, or the capacity of a fresh one: checked before any launch."""
+    if tracks is None:
+        new_track_table(capacity, 1, 'cpu')
+    else:
+        _check_track_table(tracks)
+
+
+def _follow_poses(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity, association, smoothing, locate):
+    """follow_poses_in_frames on checked groups (heads.Association with its assignment rule -- 'greedy' there, Follower passes its
+    own -- and heads.Smoothing); locate: the keywords handed on to locate_poses_in_frames, none of them scale_recovery 'metro'."""
+    from metro_pose3d_amd.heads import _associate_tracks, _smooth_tracks
+    n_boxes, fi = _box_frames(boxes, frame_index)
     times = _box_times(timestamps, fi, n_boxes)
     step_rows, step_starts = time_steps(times)
-    if tracks is None:
-        new_track_table(capacity, 1, 'cpu')                 # the capacity check, before any launch
-    else:
-        _check_track_table(tracks, capacity)
-    raw = locate_poses_in_frames(frames, boxes, model_path, cameras=cameras, frame_index=frame_index, scale_recovery=scale_recovery,
-                                 bone_lengths=bone_lengths, root_depth=root_depth, coords=coords, precision=precision,
-                                 check_finite=check_finite, views=views, geometry=geometry, pixel_format=pixel_format,
-                                 color_matrix=color_matrix, crop_dtype=crop_dtype, return_uncertainty=True)
+    _check_tracks_or_capacity(tracks, capacity)
+    raw = locate_poses_in_frames(frames, boxes, model_path, cameras=cameras, frame_index=frame_index, return_uncertainty=True, **locate)
     device = raw.poses.device
-    if tracks is None:
-        tracks = new_track_table(capacity, raw.poses.shape[1], device)
-    tracks = TrackTable(*tracks)
+    tracks = new_track_table(capacity, raw.poses.shape[1], device) if tracks is None else TrackTable(*tracks)
     with torch.cuda.device(device):
-        found = associate_tracks(raw.poses, raw.covariance, times, step_rows, step_starts, tracks.state, tracks.ids, tracks.next_id,
-                                 max_cost_mm, clip_mm, min_joints, max_age_s, measurement, accel_psd, sigma_floor_mm, cov_scale,
-                                 initial_speed_mm_s, gate, assignment)
-        poses, velocity, covariance, used = smooth_tracks(raw.poses, raw.covariance, times, found.rows, found.starts, mode, measurement,
-                                                          accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, tracks.state)
+        found = _associate_tracks(raw.poses, raw.covariance, times, step_rows, step_starts, *tracks, association, smoothing)
+        poses, velocity, covariance, used = _smooth_tracks(raw.poses, raw.covariance, times, found.rows, found.starts, smoothing,
+                                                           tracks.state)
     smoothed = TrackPoses(poses, velocity, covariance, used, raw, tracks.state, raw.joint_edges, raw.joint_names)
     return FollowedPoses(found.track_index, found.track_id, found.cost, found.n_new, found.n_dropped, tracks, smoothed)
 
@@ -1598,45 +1636,43 @@ def follow_world_poses_in_frames(frames, boxes, model_path, cameras, frame_index
     ValueError before any launch for more than 128 boxes or 64 frames, cameras=None, timestamps that are not finite or match
     neither frames nor boxes, capacity outside [1, 128], a tracks that is no table or has another joint count than the model,
     and whatever match_poses_in_frames and follow_poses_in_frames refuse of their keywords."""
-    return _follow_world(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity, match_max_cost_mm,
-                         match_clip_mm, match_min_joints, weights, min_angle_deg, max_cost_mm, clip_mm, min_joints, max_age_s, mode,
-                         measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, views, precision, check_finite,
-                         geometry, pixel_format, color_matrix, crop_dtype, assignment, 'skip', None)[0]
+    return _follow_world(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity,
+                         *_world_groups(locals(), assignment, 'skip'))[0]
 
 
 SINGLE_VIEWS = ('rays', 'skip')
 
 
-def _follow_world(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity, match_max_cost_mm, match_clip_mm,
-                  match_min_joints, weights, min_angle_deg, max_cost_mm, clip_mm, min_joints, max_age_s, mode, measurement, accel_psd,
-                  sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, views, precision, check_finite, geometry, pixel_format,
-                  color_matrix, crop_dtype, assignment, single_view, ray_depth_sigma_mm, bones=None):
-    """follow_world_poses_in_frames (single_view 'skip') and follow_rig_poses_in_frames -> (FollowedWorldPoses, None or
-    (single_view uint8 [P], ray_depth float32 [P, Jout], n_unplaced int32 [1]) of the 'rays' chain, the bone table).
+def _world_groups(kw: dict, assignment, single_view):
+    """The keywords of follow_world_poses_in_frames / follow_rig_poses_in_frames (`kw` holds them by name: the call's locals(), or
+    Follower's) checked once, here -> (heads.Matching, heads.Triangulation, heads.Association -- with the ray depth sigma for
+    single_view 'rays' only --, heads.Smoothing, the keywords handed on to _checked_call)."""
+    from metro_pose3d_amd.heads import Association, Matching, Smoothing, Triangulation
+    if not isinstance(single_view, str) or single_view not in SINGLE_VIEWS:
+        raise ValueError(f"single_view must be 'rays' or 'skip', got {single_view!r}")
+    rays = single_view == 'rays'
+    association = Association.checked(kw['max_cost_mm'], kw['clip_mm'], kw['min_joints'], kw['max_age_s'], assignment,
+                                      kw.get('ray_depth_sigma_mm'), rays)
+    if rays and kw['measurement'] == 'isotropic':
+        raise ValueError("single_view='rays' needs measurement='covariance': an isotropic R would ignore the ray's shape and "
+                         'pin the depth along it')
+    triangulation = Triangulation.checked(kw['weights'], kw['min_angle_deg'])
+    matching = Matching.checked(kw['match_max_cost_mm'], kw['match_clip_mm'], kw['match_min_joints'])
+    smoothing = Smoothing.checked(*(kw[k] for k in Smoothing._fields))
+    return matching, triangulation, association, smoothing, {k: kw[k] for k in _CALL_OPTIONS}
+
+
+def _follow_world(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity, matching, triangulation, association,
+                  smoothing, call_options, bones=None):
+    """follow_world_poses_in_frames and follow_rig_poses_in_frames on checked groups (_world_groups) -> (FollowedWorldPoses, None
+    or (single_view uint8 [P], ray_depth float32 [P, Jout], n_unplaced int32 [1]) of the 'rays' chain -- the one whose association
+    holds a ray depth sigma --, the bone table).
     bones: None (nothing is learned: the chain is what it was), True (a fresh table) or the BoneTable of the previous call:
     one metro_track_bone_lengths launch after the smoothing launch accumulates every followed person's bone lengths from the
     triangulation's own poses and covariance."""
-    from metro_pose3d_amd.heads import (MATCH_MAX_BOXES, associate_tracks, associate_tracks_rays, association_params, assignment_rule,
-                                        matching_params, person_rays, person_steps, person_steps_labels, ray_depth_sigma,
-                                        smooth_tracks, smoothing_params, track_bone_lengths, triangulation_min_det)
-    if not isinstance(single_view, str) or single_view not in SINGLE_VIEWS:
-        raise ValueError(f"single_view must be 'rays' or 'skip', got {single_view!r}")
-    with_rays = single_view == 'rays'
-    if ray_depth_sigma_mm is not None:
-        ray_depth_sigma(ray_depth_sigma_mm)
-    if with_rays:
-        if measurement == 'isotropic':
-            raise ValueError("single_view='rays' needs measurement='covariance': an isotropic R would ignore the ray's shape and "
-                             'pin the depth along it')
-    assignment_rule(assignment)
-    triangulation_min_det(weights, min_angle_deg)
-    matching_params(match_clip_mm, match_min_joints, match_max_cost_mm)
-    smoothing_params(mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate)
-    association_params(max_cost_mm, clip_mm, min_joints, max_age_s)
-    n_boxes = _n_boxes(boxes)
-    fi = np.asarray(_host_array(frame_index), np.int64).reshape(-1)
-    if len(fi) != n_boxes:
-        raise ValueError(f'frame_index must hold one value per box ({n_boxes}), got {len(fi)}')
+    from metro_pose3d_amd.heads import (MATCH_MAX_BOXES, _associate_tracks, _smooth_tracks, person_rays, person_steps, person_steps_labels,
+                                        track_bone_lengths)
+    n_boxes, fi = _box_frames(boxes, frame_index)
     if n_boxes > MATCH_MAX_BOXES:
         raise ValueError(f'{n_boxes} boxes: matching takes at most {MATCH_MAX_BOXES} per call')
     if len(np.unique(fi)) > MAX_WORLD_FRAMES:
@@ -1644,62 +1680,50 @@ def _follow_world(frames, boxes, model_path, cameras, frame_index, timestamps, t
     _check_rig(cameras, fi, n_boxes)
     times = _box_times(timestamps, fi, n_boxes)
     step_times, box_step = np.unique(times, return_inverse=True)
-    if tracks is None:
-        new_track_table(capacity, 1, 'cpu')                 # the capacity check, before any launch
-    else:
-        _check_track_table(tracks, capacity)
-    call = _checked_call(frames, boxes, fi, 'world', views, geometry, precision, check_finite, pixel_format, color_matrix,
-                         crop_dtype)
+    _check_tracks_or_capacity(tracks, capacity)
+    call = _checked_call(frames, boxes, fi, 'world', **call_options)
     sk = _model_skeleton(model_path)
-    if min_joints is not None and min_joints > sk.n_out:
-        raise ValueError(f'min_joints must be at most the {sk.n_out} output joints of the model, got {min_joints!r}')
+    _check_min_joints(association.min_joints, sk)
     if tracks is not None and tracks[0].shape[1] != sk.n_out:
         raise ValueError(f'tracks.state holds {tracks[0].shape[1]} joints, the model has {sk.n_out}')
     device = _call_device(call.boxes, call.frames)
     tracks = new_track_table(capacity, sk.n_out, device) if tracks is None else TrackTable(*tracks)
     if bones is not None:
         bones = new_bone_table(len(tracks.ids), len(sk.edges), device) if bones is True else _checked_bone_table(bones, tracks, sk)
-
-    def then(spec, n_views, poses, cov, rows, starts, n_persons, seen):
-        own = (poses, cov)                                  # the triangulation's: NaN for a person one camera sees
-        if with_rays:
-            coords01, cov01, places, labels = seen
-            person_step, person_times, step_rows, step_starts, single_box = person_steps_labels(labels, n_persons, box_step, step_times)
-            rays = person_rays(coords01, cov01, places, single_box, spec, n_views, weights)
-            found = associate_tracks_rays(poses, cov, person_times, step_rows, step_starts, tracks.state, tracks.ids, tracks.next_id,
-                                          single_box, rays, max_cost_mm, clip_mm, min_joints, max_age_s, accel_psd, sigma_floor_mm,
-                                          cov_scale, initial_speed_mm_s, gate, assignment, ray_depth_sigma_mm)
-            poses, cov = found.poses, found.covariance      # the triangulation's own stay as they are
-            extra = ((single_box >= 0).to(torch.uint8), found.ray_depth, found.n_unplaced)
-        else:
-            person_step, person_times, step_rows, step_starts = person_steps(rows, starts, n_persons, box_step, step_times, n_views)
-            found = associate_tracks(poses, cov, person_times, step_rows, step_starts, tracks.state, tracks.ids, tracks.next_id,
-                                     max_cost_mm, clip_mm, min_joints, max_age_s, measurement, accel_psd, sigma_floor_mm, cov_scale,
-                                     initial_speed_mm_s, gate, assignment)
-            extra = None
-        smooth = smooth_tracks(poses, cov, person_times, found.rows, found.starts, mode, measurement, accel_psd, sigma_floor_mm,
-                               cov_scale, initial_speed_mm_s, gate, tracks.state)
-        if bones is not None:                               # the raw measurements, not the smoothed rows: those are correlated in time
-            track_bone_lengths(own[0], own[1] if measurement == 'covariance' else None, found.rows, found.starts, tracks.ids,
-                               bones.stats, bones.ids, sk.edges, sk.edge_mirror(), sigma_floor_mm=sigma_floor_mm, cov_scale=cov_scale)
-        return person_step, found, smooth, extra
-
-    match = (float(match_max_cost_mm), float(match_clip_mm), None if match_min_joints is None else int(match_min_joints))
-    world, matched, (cov, followed) = _world_poses(call, model_path, cameras, fi, weights, min_angle_deg, match=match,
-                                                   step_index=box_step, covariance=True, then=then)
-    p = len(world.poses)
-    if followed is None:                                    # no boxes: no launch
+    _check_min_joints(matching.min_joints, sk)
+    if len(call.boxes) == 0:                                # no boxes: no launch
         i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=device)
         f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=device)
         smoothed = SmoothedWorldPoses(f32(0, sk.n_out, 3), f32(0, sk.n_out, 3), f32(0, sk.n_out, 3, 3),
                                       torch.zeros((0, sk.n_out), dtype=torch.uint8, device=device), tracks.state)
-        return FollowedWorldPoses(*matched, world, cov, i32(0), i32(0), i32(0), f32(0), i32(1), i32(1), tracks, smoothed), None, bones
-    person_step, found, (poses, velocity, covariance, used), extra = followed
-    smoothed = SmoothedWorldPoses(poses[:p], velocity[:p], covariance[:p], used[:p], tracks.state)
+        return (FollowedWorldPoses(*_no_persons(sk, device), f32(0, sk.n_out, 9), i32(0), i32(0), i32(0), f32(0), i32(1), i32(1),
+                                   tracks, smoothed), None, bones)
+    chain = _enqueue_world(call, model_path, cameras, fi, triangulation, matching=matching, step_index=box_step, covariance=True)
+    places, extra = chain.places.reshape(-1), None
+    with torch.cuda.device(device):                         # between the triangulation and metro_place_poses, nothing read back
+        poses, cov = chain.poses, chain.covariance          # the triangulation's own: NaN for a person one camera sees
+        if association.ray_depth_sigma_mm is not None:
+            person_step, person_times, step_rows, step_starts, single_box = person_steps_labels(chain.labels, chain.n_persons, box_step,
+                                                                                                step_times)
+            rays = person_rays(chain.coords01, chain.cov01, places, single_box, chain.eng.spec, chain.nv, triangulation.weights)
+            found = _associate_tracks(poses, cov, person_times, step_rows, step_starts, *tracks, association, smoothing, (single_box, rays))
+            poses, cov = found.poses, found.covariance      # copies with the placed joints: the triangulation's own stay as they are
+            extra = ((single_box >= 0).to(torch.uint8), found.ray_depth, found.n_unplaced)
+        else:
+            person_step, person_times, step_rows, step_starts = person_steps(chain.rows, chain.starts, chain.n_persons, box_step,
+                                                                             step_times, chain.nv)
+            found = _associate_tracks(poses, cov, person_times, step_rows, step_starts, *tracks, association, smoothing)
+        smooth = _smooth_tracks(poses, cov, person_times, found.rows, found.starts, smoothing, tracks.state)
+        if bones is not None:                               # the raw measurements, not the smoothed rows: those are correlated in time
+            track_bone_lengths(chain.poses, chain.covariance if smoothing.measurement == 'covariance' else None, found.rows, found.starts,
+                               tracks.ids, bones.stats, bones.ids, sk.edges, sk.edge_mirror(), sigma_floor_mm=smoothing.sigma_floor_mm,
+                               cov_scale=smoothing.cov_scale)
+    world, p = _finish_world(call, chain)
     if extra is not None:
         extra = (extra[0][:p], extra[1][:p], extra[2])
-    return FollowedWorldPoses(*matched, world, cov, person_step[:p], found.track_index[:p], found.track_id[:p], found.cost[:p],
-                              found.n_new, found.n_dropped, tracks, smoothed), extra, bones
+    return (FollowedWorldPoses(chain.labels, chain.cost, chain.n_pairs, world, chain.covariance[:p], person_step[:p], found.track_index[:p],
+                               found.track_id[:p], found.cost[:p], found.n_new, found.n_dropped, tracks,
+                               SmoothedWorldPoses(*(t[:p] for t in smooth), tracks.state)), extra, bones)
 
 
 class FollowedRigPoses(NamedTuple):
@@ -1754,12 +1778,8 @@ def follow_rig_poses_in_frames(frames, boxes, model_path, cameras, frame_index, 
     rounding of R stays far below sigma_floor_mm^2.
     ValueError before any launch for whatever follow_world_poses_in_frames refuses, an unknown single_view, ray_depth_sigma_mm
     not finite and > 0, and measurement='isotropic' together with 'rays'."""
-    out, extra, _ = _follow_world(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity, match_max_cost_mm,
-                                  match_clip_mm, match_min_joints, weights, min_angle_deg, max_cost_mm, clip_mm, min_joints, max_age_s,
-                                  mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, views, precision,
-                                  check_finite, geometry, pixel_format, color_matrix, crop_dtype, assignment, single_view,
-                                  ray_depth_sigma_mm)
-    return _rig_poses(out, extra)
+    return _rig_poses(*_follow_world(frames, boxes, model_path, cameras, frame_index, timestamps, tracks, capacity,
+                                     *_world_groups(locals(), assignment, single_view))[:2])
 
 
 def _rig_poses(out: FollowedWorldPoses, extra) -> FollowedRigPoses:
@@ -1835,7 +1855,7 @@ def predict_boxes_in_frames(tracks: TrackTable, cameras, frame_sizes, timestamps
     if coords not in ('camera', 'world'):
         raise ValueError(f"coords must be 'camera' or 'world' (a crop has no calibrated camera of its own frame), got {coords!r}")
     prediction_params(expand, n_sigma, max_sigma_mm, min_joints, max_age_s, near_mm, min_side_px, iou_max, accel_psd)
-    _check_track_table(tracks, None)
+    _check_track_table(tracks)
     tracks = TrackTable(*tracks)
     if cameras is None:
         raise ValueError('cameras: predicting boxes needs calibrated cameras (one Camera, or one per frame)')
@@ -1889,8 +1909,6 @@ class Follower:
     def __init__(self, model_path, cameras, world: bool = False, assignment: str = 'greedy', capacity: int = 64,
                  single_view: Optional[str] = None, learn_bones: bool = False, **keywords):
         import inspect
-        from metro_pose3d_amd.heads import (association_params, assignment_rule, matching_params, ray_depth_sigma, smoothing_params,
-                                            triangulation_min_det)
         if not isinstance(world, (bool, np.bool_)):
             raise ValueError(f'world must be True or False, got {world!r}')
         if not isinstance(learn_bones, (bool, np.bool_)):
@@ -1898,11 +1916,8 @@ class Follower:
         if learn_bones and not world:
             raise ValueError('learn_bones needs world=True: bone lengths are learned from triangulated poses; poses that bone '
                              'lengths placed would only echo the table')
-        if single_view is not None:
-            if not world:
-                raise ValueError('single_view belongs to a calibrated rig: it needs world=True')
-            if not isinstance(single_view, str) or single_view not in SINGLE_VIEWS:
-                raise ValueError(f"single_view must be 'rays' or 'skip', got {single_view!r}")
+        if single_view is not None and not world:
+            raise ValueError('single_view belongs to a calibrated rig: it needs world=True')
         call = follow_poses_in_frames if not world else follow_world_poses_in_frames if single_view is None else follow_rig_poses_in_frames
         params = inspect.signature(call).parameters
         defaults = {k: p.default for k, p in params.items() if k not in _FOLLOWER_GIVEN + ('single_view',)}
@@ -1911,23 +1926,13 @@ class Follower:
             raise TypeError(f"Follower(world={bool(world)}) got an unexpected keyword {unknown[0]!r}: it takes "
                             f"{', '.join(defaults)}")
         kw = dict(defaults, **keywords)
-        assignment_rule(assignment)
         new_track_table(capacity, 1, 'cpu')                 # the capacity check
-        association_params(kw['max_cost_mm'], kw['clip_mm'], kw['min_joints'], kw['max_age_s'])
-        smoothing_params(kw['mode'], kw['measurement'], kw['accel_psd'], kw['sigma_floor_mm'], kw['cov_scale'],
-                         kw['initial_speed_mm_s'], kw['gate'])
-        if world:
-            matching_params(kw['match_clip_mm'], kw['match_min_joints'], kw['match_max_cost_mm'])
-            triangulation_min_det(kw['weights'], kw['min_angle_deg'])
+        if world:                                           # the option groups, checked here, once: follow() hands them on
+            self._groups = _world_groups(kw, assignment, 'skip' if single_view is None else single_view)
             if cameras is None:
                 raise ValueError('cameras: following in the world needs the calibrated cameras of the rig')
-            if single_view is not None:
-                ray_depth_sigma(kw['ray_depth_sigma_mm'])
-                if single_view == 'rays' and kw['measurement'] == 'isotropic':
-                    raise ValueError("single_view='rays' needs measurement='covariance'")
-        elif kw['scale_recovery'] == 'metro':
-            raise ValueError("scale_recovery='metro' returns root-relative poses, in which all persons coincide: following needs "
-                             "absolute poses ('bone-lengths' or 'true-root-depth')")
+        else:
+            self._groups = _camera_groups(kw, assignment)
         self.model_path, self.cameras, self.world = model_path, cameras, bool(world)
         self.assignment, self.capacity, self.keywords, self.single_view = assignment, int(capacity), kw, single_view
         self.tracks: Optional[TrackTable] = None
@@ -1935,25 +1940,14 @@ class Follower:
         self.bones: Optional[BoneTable] = None
 
     def follow(self, frames, boxes, frame_index, timestamps):
-        if self.learn_bones:
-            kw = dict({'single_view': 'skip', 'ray_depth_sigma_mm': None}, **self.keywords)
-            if self.single_view is not None:
-                kw['single_view'] = self.single_view
-            out, extra, self.bones = _follow_world(frames, boxes, self.model_path, self.cameras, frame_index, timestamps, self.tracks,
-                                                   self.capacity, assignment=self.assignment,
-                                                   bones=True if self.bones is None else self.bones, **kw)
+        given = (frames, boxes, self.model_path, self.cameras, frame_index, timestamps, self.tracks, self.capacity)
+        if self.world:
+            bones = (True if self.bones is None else self.bones) if self.learn_bones else None
+            out, extra, self.bones = _follow_world(*given, *self._groups, bones)
             if self.single_view is not None:
                 out = _rig_poses(out, extra)
-        elif self.world and self.single_view is not None:
-            out = follow_rig_poses_in_frames(frames, boxes, self.model_path, self.cameras, frame_index, timestamps, tracks=self.tracks,
-                                             capacity=self.capacity, assignment=self.assignment, single_view=self.single_view,
-                                             **self.keywords)
-        elif self.world:
-            out = follow_world_poses_in_frames(frames, boxes, self.model_path, self.cameras, frame_index, timestamps, tracks=self.tracks,
-                                               capacity=self.capacity, assignment=self.assignment, **self.keywords)
         else:
-            out = _follow_poses(frames, boxes, self.model_path, self.cameras, frame_index, timestamps, self.tracks, self.capacity,
-                                assignment=self.assignment, **self.keywords)
+            out = _follow_poses(*given, *self._groups)
         self.tracks = out.tracks
         return out
 

@@ -174,6 +174,17 @@ def triangulation_min_det(weights, min_angle_deg) -> float:
     return float(np.sin(np.radians(float(min_angle_deg))) ** 2 / 4.0)
 
 
+class Triangulation(NamedTuple):
+    """The triangulation keywords of the frames calls, checked once, where the group is built (`checked`)."""
+    weights: str
+    min_angle_deg: float
+
+    @classmethod
+    def checked(cls, weights, min_angle_deg) -> 'Triangulation':
+        triangulation_min_det(weights, min_angle_deg)
+        return cls(weights, min_angle_deg)
+
+
 def _i32(x, dev) -> torch.Tensor:
     if isinstance(x, torch.Tensor):
         return x.to(device=dev, dtype=torch.int32).contiguous()
@@ -217,20 +228,17 @@ def triangulate_joints(coords01: torch.Tensor, cov01: Optional[torch.Tensor], pl
     points = torch.empty((n_persons, n_out, 3), dtype=torch.float32, device=dev)
     n_rays = torch.empty((n_persons, n_out), dtype=torch.int32, device=dev)
     residual = torch.empty((n_persons, n_out), dtype=torch.float32, device=dev)
-    cov = torch.empty((n_persons, n_out, 9), dtype=torch.float32, device=dev) if return_covariance else None
+    out = (points, n_rays, residual)
+    if return_covariance:
+        out += (torch.empty((n_persons, n_out, 9), dtype=torch.float32, device=dev),)
     if n_persons == 0:
-        return (points, n_rays, residual, cov) if return_covariance else (points, n_rays, residual)
+        return out
     cs = spec.to_c(1)
     mirror = _table(spec.skeleton.out_mirror, np.int32, dev)
-    if return_covariance:
-        check(lib.metro_triangulate_joints_cov(_p(coords01), _p(cov01), _p(places), m, _p(rows), rows.numel(), _p(starts),
-                                               n_persons, C.byref(cs), _p(mirror), TRI_WEIGHTS[weights], min_det, _p(points),
-                                               _p(n_rays), _p(residual), _p(cov), _stream(dev)), 'metro_triangulate_joints_cov')
-        return points, n_rays, residual, cov
-    check(lib.metro_triangulate_joints(_p(coords01), _p(cov01), _p(places), m, _p(rows), rows.numel(), _p(starts),
-                                       n_persons, C.byref(cs), _p(mirror), TRI_WEIGHTS[weights], min_det, _p(points), _p(n_rays),
-                                       _p(residual), _stream(dev)), 'metro_triangulate_joints')
-    return points, n_rays, residual
+    entry = 'metro_triangulate_joints_cov' if return_covariance else 'metro_triangulate_joints'
+    check(getattr(lib, entry)(_p(coords01), _p(cov01), _p(places), m, _p(rows), rows.numel(), _p(starts), n_persons, C.byref(cs),
+                              _p(mirror), TRI_WEIGHTS[weights], min_det, *(_p(t) for t in out), _stream(dev)), entry)
+    return out
 
 
 MATCH_MAX_BOXES = _lib.METRO_MATCH_MAX_BOXES
@@ -250,12 +258,41 @@ def matching_params(clip_mm, min_joints, *max_cost_mm):
         raise ValueError(f'min_joints must be None or an integer >= 1, got {min_joints!r}')
 
 
+class Matching(NamedTuple):
+    """The cross-view matching keywords of the frames calls, checked once, where the group is built (`checked`)."""
+    max_cost_mm: float
+    clip_mm: float
+    min_joints: Optional[int]
+
+    @classmethod
+    def checked(cls, max_cost_mm, clip_mm, min_joints) -> 'Matching':
+        matching_params(clip_mm, min_joints, max_cost_mm)
+        return cls(float(max_cost_mm), float(clip_mm), None if min_joints is None else int(min_joints))
+
+
 def _check_n_views(n_views, rows: int) -> int:
     if isinstance(n_views, (bool, np.bool_)) or not isinstance(n_views, (int, np.integer)) or not 1 <= n_views <= _lib.METRO_MAX_VIEWS:
         raise ValueError(f'n_views must be an integer from 1 to {_lib.METRO_MAX_VIEWS}, got {n_views!r}')
     if rows % int(n_views):
         raise ValueError(f'{rows} rows are not a whole number of boxes of {n_views} views')
     return int(n_views)
+
+
+def _checked_crop_rows(coords01, cov01, places, spec, n_views, weights):
+    """What view_affinity* and person_rays check alike of the m = n * n_views crop rows -> (m, n_views, n)."""
+    nj = spec.skeleton.n_head
+    if not isinstance(coords01, torch.Tensor) or coords01.dim() != 3 or tuple(coords01.shape[1:]) != (nj, 3):
+        raise ValueError(f'coords01 must be a tensor [m,{nj},3], got {tuple(getattr(coords01, "shape", ()))}')
+    m = coords01.shape[0]
+    n_views = _check_n_views(n_views, m)
+    if m // n_views > MATCH_MAX_BOXES:
+        raise ValueError(f'{m // n_views} boxes: matching takes at most {MATCH_MAX_BOXES}')
+    if weights == 'covariance' and (cov01 is None or tuple(cov01.shape) != (m, nj, 6)):
+        raise ValueError(f"weights='covariance' needs cov01 [{m},{nj},6], got {None if cov01 is None else tuple(cov01.shape)}")
+    need = m * C.sizeof(_lib.MetroPlacement)
+    if not isinstance(places, torch.Tensor) or places.dtype != torch.uint8 or places.numel() != need:
+        raise ValueError(f'places must be a uint8 tensor of {m} MetroPlacement records ({need} bytes)')
+    return m, n_views, m // n_views
 
 
 def view_affinity(coords01: torch.Tensor, cov01: Optional[torch.Tensor], places: torch.Tensor, frame_index, spec: ModelSpec,
@@ -271,7 +308,7 @@ def view_affinity(coords01: torch.Tensor, cov01: Optional[torch.Tensor], places:
     each weighted ('covariance') by 1 / (sigma_a^2 t_a^2 + sigma_b^2 t_b^2), the heat-map variances carried to where the rays
     pass.  +inf on the diagonal, for two boxes on one frame (a person appears once per camera) and where fewer than
     min_joints * n_views ray pairs count (min_joints None: (Jout + 1) // 2).  At most 128 boxes."""
-    return _view_affinity(coords01, cov01, places, frame_index, None, spec, n_views, weights, min_angle_deg, clip_mm, min_joints)
+    return view_affinity_steps(coords01, cov01, places, frame_index, None, spec, n_views, weights, min_angle_deg, clip_mm, min_joints)
 
 
 def view_affinity_steps(coords01: torch.Tensor, cov01: Optional[torch.Tensor], places: torch.Tensor, frame_index, step_index,
@@ -281,36 +318,18 @@ def view_affinity_steps(coords01: torch.Tensor, cov01: Optional[torch.Tensor], p
     of each box, one exposure of the rig; two boxes of different steps cost +inf with n_pairs 0, as two boxes of one frame do;
     every other entry has view_affinity's bits.  step_index None is view_affinity.  (A function of its own: view_affinity's
     parameter list is pinned.)"""
-    return _view_affinity(coords01, cov01, places, frame_index, step_index, spec, n_views, weights, min_angle_deg, clip_mm, min_joints)
-
-
-def _view_affinity(coords01, cov01, places, frame_index, step_index, spec, n_views, weights, min_angle_deg, clip_mm, min_joints):
     triangulation_min_det(weights, min_angle_deg)
     matching_params(clip_mm, min_joints)
-    nj, n_out = spec.skeleton.n_head, spec.skeleton.n_out
-    if not isinstance(coords01, torch.Tensor) or coords01.dim() != 3 or tuple(coords01.shape[1:]) != (nj, 3):
-        raise ValueError(f'coords01 must be a tensor [m,{nj},3], got {tuple(getattr(coords01, "shape", ()))}')
-    m = coords01.shape[0]
-    n_views = _check_n_views(n_views, m)
-    n = m // n_views
-    if n > MATCH_MAX_BOXES:
-        raise ValueError(f'{n} boxes: matching takes at most {MATCH_MAX_BOXES}')
+    m, n_views, n = _checked_crop_rows(coords01, cov01, places, spec, n_views, weights)
+    n_out = spec.skeleton.n_out
     if min_joints is None:
         min_joints = (n_out + 1) // 2
     if min_joints > n_out:
         raise ValueError(f'min_joints must be at most the {n_out} output joints, got {min_joints!r}')
-    if weights == 'covariance' and (cov01 is None or tuple(cov01.shape) != (m, nj, 6)):
-        raise ValueError(f"weights='covariance' needs cov01 [{m},{nj},6], got {None if cov01 is None else tuple(cov01.shape)}")
-    need = m * C.sizeof(_lib.MetroPlacement)
-    if not isinstance(places, torch.Tensor) or places.dtype != torch.uint8 or places.numel() != need:
-        raise ValueError(f'places must be a uint8 tensor of {m} MetroPlacement records ({need} bytes)')
-    n_fi = int(frame_index.numel() if isinstance(frame_index, torch.Tensor) else np.asarray(frame_index).size)
-    if n_fi != n:
-        raise ValueError(f'frame_index must hold one value per box ({n}), got {n_fi}')
-    if step_index is not None:
-        n_si = int(step_index.numel() if isinstance(step_index, torch.Tensor) else np.asarray(step_index).size)
-        if n_si != n:
-            raise ValueError(f'step_index must hold one value per box ({n}), got {n_si}')
+    for name, index in (('frame_index', frame_index),) + ((('step_index', step_index),) if step_index is not None else ()):
+        size = int(index.numel() if isinstance(index, torch.Tensor) else np.asarray(index).size)
+        if size != n:
+            raise ValueError(f'{name} must hold one value per box ({n}), got {size}')
     dev = coords01.device
     cost = torch.empty((n, n), dtype=torch.float32, device=dev)
     n_pairs = torch.empty((n, n), dtype=torch.int32, device=dev)
@@ -323,15 +342,11 @@ def _view_affinity(coords01, cov01, places, frame_index, step_index, spec, n_vie
     cs = spec.to_c(1)
     mirror = _table(spec.skeleton.out_mirror, np.int32, dev)
     min_sin2 = float(np.sin(np.radians(float(min_angle_deg))) ** 2)
-    if step_index is not None:
-        si = _i32(step_index, dev).reshape(-1)
-        check(lib.metro_view_affinity_steps(_p(coords01), _p(cov01), _p(places), C.byref(cs), _p(mirror), _p(fi), _p(si), n, n_views,
-                                            TRI_WEIGHTS[weights], min_sin2, float(clip_mm), int(min_joints) * n_views, _p(cost),
-                                            _p(n_pairs), _stream(dev)), 'metro_view_affinity_steps')
-        return cost, n_pairs
-    check(lib.metro_view_affinity(_p(coords01), _p(cov01), _p(places), C.byref(cs), _p(mirror), _p(fi), n, n_views,
-                                  TRI_WEIGHTS[weights], min_sin2, float(clip_mm), int(min_joints) * n_views, _p(cost), _p(n_pairs),
-                                  _stream(dev)), 'metro_view_affinity')
+    si = _i32(step_index, dev).reshape(-1) if step_index is not None else None
+    entry, steps = ('metro_view_affinity', ()) if si is None else ('metro_view_affinity_steps', (_p(si),))
+    check(getattr(lib, entry)(_p(coords01), _p(cov01), _p(places), C.byref(cs), _p(mirror), _p(fi), *steps, n, n_views,
+                              TRI_WEIGHTS[weights], min_sin2, float(clip_mm), int(min_joints) * n_views, _p(cost), _p(n_pairs),
+                              _stream(dev)), entry)
     return cost, n_pairs
 
 
@@ -387,20 +402,24 @@ def person_steps(rows, starts, n_persons, box_step, step_times, n_views: int = 1
     dev = starts.device
     rows, starts, n_persons = _i32(rows, dev).reshape(-1), _i32(starts, dev).reshape(-1), _i32(n_persons, dev).reshape(-1)
     box_step = _i32(box_step, dev).reshape(-1)
+    step_times, out = _person_step_outputs(n, step_times, dev)
+    if n:
+        check(_lib.load().metro_person_steps(_p(rows), rows.numel(), _p(starts), _p(n_persons), n, n_views, _p(box_step), box_step.numel(),
+                                             _p(step_times), step_times.numel(), *(_p(t) for t in out), _stream(dev)), 'metro_person_steps')
+    return out
+
+
+def _person_step_outputs(n: int, step_times, dev):
+    """step_times [S] as a float64 device tensor, and what person_steps* write over n persons: (person_step, person_times, step_rows,
+    step_starts), step_starts zeroed where n = 0 leaves nothing to launch."""
     if not isinstance(step_times, torch.Tensor):
         step_times = torch.from_numpy(np.ascontiguousarray(np.asarray(step_times, np.float64).reshape(-1)))
     step_times = step_times.to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
-    n_steps = int(step_times.numel())
     i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
-    person_step, step_rows, step_starts = i32(n), i32(n), i32(n_steps + 1)
-    person_times = torch.empty((n,), dtype=torch.float64, device=dev)
+    out = (i32(n), torch.empty((n,), dtype=torch.float64, device=dev), i32(n), i32(step_times.numel() + 1))
     if n == 0:
-        step_starts.zero_()
-        return person_step, person_times, step_rows, step_starts
-    check(_lib.load().metro_person_steps(_p(rows), rows.numel(), _p(starts), _p(n_persons), n, n_views, _p(box_step), box_step.numel(),
-                                         _p(step_times), n_steps, _p(person_step), _p(person_times), _p(step_rows), _p(step_starts),
-                                         _stream(dev)), 'metro_person_steps')
-    return person_step, person_times, step_rows, step_starts
+        out[3].zero_()
+    return step_times, out
 
 
 def person_steps_labels(person_index, n_persons, box_step, step_times):
@@ -422,20 +441,12 @@ def person_steps_labels(person_index, n_persons, box_step, step_times):
     box_step = _i32(box_step, dev).reshape(-1)
     if box_step.numel() != n:
         raise ValueError(f'box_step must hold one value per box ({n}), got {box_step.numel()}')
-    if not isinstance(step_times, torch.Tensor):
-        step_times = torch.from_numpy(np.ascontiguousarray(np.asarray(step_times, np.float64).reshape(-1)))
-    step_times = step_times.to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
-    n_steps = int(step_times.numel())
-    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
-    person_step, step_rows, step_starts, single_box = i32(n), i32(n), i32(n_steps + 1), i32(n)
-    person_times = torch.empty((n,), dtype=torch.float64, device=dev)
-    if n == 0:
-        step_starts.zero_()
-        return person_step, person_times, step_rows, step_starts, single_box
-    check(_lib.load().metro_person_steps_labels(_p(person_index), _p(n_persons), n, _p(box_step), n, _p(step_times), n_steps,
-                                                _p(person_step), _p(person_times), _p(step_rows), _p(step_starts), _p(single_box),
-                                                _stream(dev)), 'metro_person_steps_labels')
-    return person_step, person_times, step_rows, step_starts, single_box
+    step_times, out = _person_step_outputs(n, step_times, dev)
+    out += (torch.empty((n,), dtype=torch.int32, device=dev),)                      # single_box
+    if n:
+        check(_lib.load().metro_person_steps_labels(_p(person_index), _p(n_persons), n, _p(box_step), n, _p(step_times), step_times.numel(),
+                                                    *(_p(t) for t in out), _stream(dev)), 'metro_person_steps_labels')
+    return out
 
 
 PERSON_RAY_DOUBLES = 8               # per (person, joint): o (3), d (3), sigma2, the number of views used
@@ -451,23 +462,11 @@ def person_rays(coords01: torch.Tensor, cov01: Optional[torch.Tensor], places: t
     view --, sigma2 (the lateral variance of the ray in normalised image units, 1 / sum (1 / sigma2_v); 0 with 'uniform') and the
     number of views used.  All eight NaN where there is no ray: single_box -1, or no usable view."""
     triangulation_min_det(weights, 2.0)
-    nj, n_out = spec.skeleton.n_head, spec.skeleton.n_out
-    if not isinstance(coords01, torch.Tensor) or coords01.dim() != 3 or tuple(coords01.shape[1:]) != (nj, 3):
-        raise ValueError(f'coords01 must be a tensor [m,{nj},3], got {tuple(getattr(coords01, "shape", ()))}')
-    m = coords01.shape[0]
-    n_views = _check_n_views(n_views, m)
-    n = m // n_views
-    if n > MATCH_MAX_BOXES:
-        raise ValueError(f'{n} boxes: matching takes at most {MATCH_MAX_BOXES}')
-    if weights == 'covariance' and (cov01 is None or tuple(cov01.shape) != (m, nj, 6)):
-        raise ValueError(f"weights='covariance' needs cov01 [{m},{nj},6], got {None if cov01 is None else tuple(cov01.shape)}")
-    need = m * C.sizeof(_lib.MetroPlacement)
-    if not isinstance(places, torch.Tensor) or places.dtype != torch.uint8 or places.numel() != need:
-        raise ValueError(f'places must be a uint8 tensor of {m} MetroPlacement records ({need} bytes)')
+    m, n_views, n = _checked_crop_rows(coords01, cov01, places, spec, n_views, weights)
     if not isinstance(single_box, torch.Tensor) or single_box.numel() != n:
         raise ValueError(f'single_box must be a device tensor of one value per person ({n})')
     dev = coords01.device
-    rays = torch.empty((n, n_out, PERSON_RAY_DOUBLES), dtype=torch.float64, device=dev)
+    rays = torch.empty((n, spec.skeleton.n_out, PERSON_RAY_DOUBLES), dtype=torch.float64, device=dev)
     if n == 0:
         return rays
     single_box = _i32(single_box, dev).reshape(-1)
@@ -504,6 +503,46 @@ def smoothing_params(mode, measurement, accel_psd, sigma_floor_mm, cov_scale, in
             _positive('initial_speed_mm_s', initial_speed_mm_s), 0.0 if gate is None else _positive('gate', gate))
 
 
+class Smoothing(NamedTuple):
+    """The smoothing keywords of smooth_tracks and the follow calls, checked once, where the group is built (`checked`, which
+    keeps the numbers as smoothing_params returns them: floats, gate None as 0)."""
+    mode: str
+    measurement: str
+    accel_psd: float
+    sigma_floor_mm: float
+    cov_scale: float
+    initial_speed_mm_s: float
+    gate: float
+
+    @classmethod
+    def checked(cls, mode, measurement, *numbers) -> 'Smoothing':
+        return cls(mode, measurement, *smoothing_params(mode, measurement, *numbers)[2:])
+
+    def params(self):
+        """metro_smooth_tracks' (mode, measurement, q, r_floor, cov_scale, v0, gate)."""
+        return (SMOOTH_MODES[self.mode], SMOOTH_MEASUREMENTS[self.measurement], *self[2:])
+
+
+def _checked_rows(poses, covariance, with_cov: bool, times, rows, starts, starts_name: str, groups: str):
+    """What smooth_tracks and _associate_tracks check alike: poses [n,J,3], the covariance a 'covariance' measurement needs, one
+    time per row and a CSR of at least one offset -> (n, J, times as a tensor, len(rows), len(starts))."""
+    if not isinstance(poses, torch.Tensor) or poses.dim() != 3 or poses.shape[2] != 3 or not 1 <= poses.shape[1] <= _lib.METRO_MAX_JOINTS:
+        raise ValueError(f'poses must be a tensor [n,J,3] with J <= {_lib.METRO_MAX_JOINTS}, got {tuple(getattr(poses, "shape", ()))}')
+    n, nj = int(poses.shape[0]), int(poses.shape[1])
+    if with_cov and (covariance is None or tuple(covariance.shape) not in ((n, nj, 3, 3), (n, nj, 9))):
+        raise ValueError(f"measurement='covariance' needs covariance [{n},{nj},3,3], got "
+                         f'{None if covariance is None else tuple(covariance.shape)}')
+    if not isinstance(times, torch.Tensor):
+        times = torch.from_numpy(np.ascontiguousarray(np.asarray(times, np.float64).reshape(-1)))
+    if times.numel() != n:
+        raise ValueError(f'times must hold one value per pose row ({n}), got {times.numel()}')
+    n_rows = int(rows.numel() if isinstance(rows, torch.Tensor) else np.asarray(rows).size)
+    n_starts = int(starts.numel() if isinstance(starts, torch.Tensor) else np.asarray(starts).size)
+    if n_starts < 1:
+        raise ValueError(f'{starts_name} must hold {groups} + 1 offsets ({groups} >= 0)')
+    return n, nj, times, n_rows, n_starts
+
+
 def smooth_tracks(poses: torch.Tensor, covariance: Optional[torch.Tensor], times, rows, starts, mode: str = 'smooth',
                   measurement: str = 'covariance', accel_psd: float = 4e6, sigma_floor_mm: float = 1.0, cov_scale: float = 1.0,
                   initial_speed_mm_s: float = 2000.0, gate: Optional[float] = None, state: Optional[torch.Tensor] = None):
@@ -524,24 +563,15 @@ def smooth_tracks(poses: torch.Tensor, covariance: Optional[torch.Tensor], times
     state: None, or a float64 [T,J,28] device tensor (frames.new_track_state) carried from call to call: a track whose slot
     holds a state continues from it, and every track with rows in this call gets the FILTER state of its last row written
     back in place (in both modes), so a stream cut into calls is filtered as one."""
-    params = smoothing_params(mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate)
-    if not isinstance(poses, torch.Tensor) or poses.dim() != 3 or poses.shape[2] != 3 or not 1 <= poses.shape[1] <= _lib.METRO_MAX_JOINTS:
-        raise ValueError(f'poses must be a tensor [n,J,3] with J <= {_lib.METRO_MAX_JOINTS}, got {tuple(getattr(poses, "shape", ()))}')
-    n, nj = int(poses.shape[0]), int(poses.shape[1])
-    with_cov = measurement == 'covariance'
-    if with_cov and (covariance is None or tuple(covariance.shape) not in ((n, nj, 3, 3), (n, nj, 9))):
-        raise ValueError(f"measurement='covariance' needs covariance [{n},{nj},3,3], got "
-                         f'{None if covariance is None else tuple(covariance.shape)}')
-    dev = poses.device
-    if not isinstance(times, torch.Tensor):
-        times = torch.from_numpy(np.ascontiguousarray(np.asarray(times, np.float64).reshape(-1)))
-    if times.numel() != n:
-        raise ValueError(f'times must hold one value per pose row ({n}), got {times.numel()}')
-    n_rows = int(rows.numel() if isinstance(rows, torch.Tensor) else np.asarray(rows).size)
-    n_starts = int(starts.numel() if isinstance(starts, torch.Tensor) else np.asarray(starts).size)
-    if n_starts < 1:
-        raise ValueError('starts must hold T + 1 offsets (T >= 0)')
-    n_tracks = n_starts - 1
+    return _smooth_tracks(poses, covariance, times, rows, starts,
+                          Smoothing.checked(mode, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate), state)
+
+
+def _smooth_tracks(poses, covariance, times, rows, starts, smoothing: Smoothing, state):
+    """smooth_tracks on a checked Smoothing group."""
+    params, with_cov = smoothing.params(), smoothing.measurement == 'covariance'
+    n, nj, times, n_rows, n_starts = _checked_rows(poses, covariance, with_cov, times, rows, starts, 'starts', 'T')
+    dev, n_tracks = poses.device, n_starts - 1
     if state is not None and (not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or state.device != dev
                               or tuple(state.shape) != (n_tracks, nj, TRACK_STATE_DOUBLES) or not state.is_contiguous()):
         raise ValueError(f'state must be a contiguous float64 tensor [{n_tracks},{nj},{TRACK_STATE_DOUBLES}] on {dev} '
@@ -560,7 +590,7 @@ def smooth_tracks(poses: torch.Tensor, covariance: Optional[torch.Tensor], times
         r = r + params[4] * (upper + upper.triu(1).transpose(-1, -2))
     cov_out = r.reshape(n, nj, 9).contiguous()
     used = torch.zeros((n, nj), dtype=torch.uint8, device=dev)
-    ws = torch.empty(lib.metro_smooth_tracks_workspace_bytes(n_rows, nj) if mode == 'smooth' else 0, dtype=torch.uint8, device=dev)
+    ws = torch.empty(lib.metro_smooth_tracks_workspace_bytes(n_rows, nj) if smoothing.mode == 'smooth' else 0, dtype=torch.uint8, device=dev)
     cs = _lib.MetroSpec(n_joints_out=nj)
     check(lib.metro_smooth_tracks(_p(poses), _p(cov), _p(times), n, _p(rows), n_rows, _p(starts), n_tracks, C.byref(cs), *params,
                                   _p(state), _p(ws), _p(out), _p(velocity), _p(cov_out), _p(used), _stream(dev)),
@@ -600,6 +630,26 @@ def assignment_rule(assignment):
         raise ValueError(f"assignment must be 'greedy' or 'optimal', got {assignment!r}")
 
 
+class Association(NamedTuple):
+    """The association keywords of associate_tracks* and the follow calls with the assignment rule, checked once, where the
+    group is built (`checked`: the ray depth sigma, then the rule, then the rest).  ray_depth_sigma_mm is kept for a chain with
+    ray rows (`rays`: associate_tracks_rays, single_view='rays') and None otherwise; given, it is checked either way."""
+    max_cost_mm: float
+    clip_mm: float
+    min_joints: Optional[int]
+    max_age_s: float
+    assignment: str
+    ray_depth_sigma_mm: Optional[float] = None
+
+    @classmethod
+    def checked(cls, max_cost_mm, clip_mm, min_joints, max_age_s, assignment, ray_depth_sigma_mm=None, rays=False) -> 'Association':
+        if rays or ray_depth_sigma_mm is not None:
+            ray_depth_sigma_mm = ray_depth_sigma(ray_depth_sigma_mm)
+        assignment_rule(assignment)
+        association_params(max_cost_mm, clip_mm, min_joints, max_age_s)
+        return cls(max_cost_mm, clip_mm, min_joints, max_age_s, assignment, ray_depth_sigma_mm if rays else None)
+
+
 def associate_tracks(poses: torch.Tensor, covariance: Optional[torch.Tensor], times, step_rows, step_starts, state: torch.Tensor,
                      ids: torch.Tensor, next_id: torch.Tensor, max_cost_mm: float = 300.0, clip_mm: float = 600.0,
                      min_joints: Optional[int] = None, max_age_s: float = 1.0, measurement: str = 'covariance',
@@ -633,8 +683,9 @@ def associate_tracks(poses: torch.Tensor, covariance: Optional[torch.Tensor], ti
     prediction within a few frames; 600 mm keeps one wild joint from deciding a pair; one second bridges a short occlusion
     without handing a long-gone track's slot history to a newcomer; half the joints keeps a cost from resting on a few.
     -> AssociatedTracks; its rows / starts and `state` go to smooth_tracks unchanged.  No boxes or no steps: no launch."""
-    return _associate_tracks(poses, covariance, times, step_rows, step_starts, state, ids, next_id, max_cost_mm, clip_mm, min_joints,
-                             max_age_s, measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, assignment, None)
+    return _associate_tracks(poses, covariance, times, step_rows, step_starts, state, ids, next_id,
+                             Association.checked(max_cost_mm, clip_mm, min_joints, max_age_s, assignment),
+                             Smoothing.checked('filter', measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate))
 
 
 class RayAssociatedTracks(NamedTuple):
@@ -691,38 +742,25 @@ def associate_tracks_rays(poses: torch.Tensor, covariance: torch.Tensor, times, 
     if not isinstance(rays, torch.Tensor) or rays.dtype != torch.float64 or tuple(rays.shape) != (n, nj, PERSON_RAY_DOUBLES):
         raise ValueError(f'rays must be a float64 tensor [{n},{nj},{PERSON_RAY_DOUBLES}] (person_rays), got '
                          f'{tuple(getattr(rays, "shape", ()))}')
-    return _associate_tracks(poses, covariance, times, step_rows, step_starts, state, ids, next_id, max_cost_mm, clip_mm, min_joints,
-                             max_age_s, 'covariance', accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, assignment,
-                             (single_box, rays, depth_sigma))
+    return _associate_tracks(poses, covariance, times, step_rows, step_starts, state, ids, next_id,
+                             Association.checked(max_cost_mm, clip_mm, min_joints, max_age_s, assignment)._replace(
+                                 ray_depth_sigma_mm=depth_sigma),
+                             Smoothing.checked('filter', 'covariance', accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate),
+                             (single_box, rays))
 
 
-def _associate_tracks(poses, covariance, times, step_rows, step_starts, state, ids, next_id, max_cost_mm, clip_mm, min_joints, max_age_s,
-                      measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate, assignment, rays):
-    """associate_tracks (rays None) and associate_tracks_rays (rays = (single_box, rays, depth sigma): the launch writes copies
-    of poses and covariance)."""
-    assignment_rule(assignment)
-    params = smoothing_params('filter', measurement, accel_psd, sigma_floor_mm, cov_scale, initial_speed_mm_s, gate)
-    association_params(max_cost_mm, clip_mm, min_joints, max_age_s)
-    if not isinstance(poses, torch.Tensor) or poses.dim() != 3 or poses.shape[2] != 3 or not 1 <= poses.shape[1] <= _lib.METRO_MAX_JOINTS:
-        raise ValueError(f'poses must be a tensor [n,J,3] with J <= {_lib.METRO_MAX_JOINTS}, got {tuple(getattr(poses, "shape", ()))}')
-    n, nj = int(poses.shape[0]), int(poses.shape[1])
+def _associate_tracks(poses, covariance, times, step_rows, step_starts, state, ids, next_id, association: Association,
+                      smoothing: Smoothing, rays=None):
+    """associate_tracks (rays None) and associate_tracks_rays (rays = (single_box, rays), the depth sigma the association's: the
+    launch writes copies of poses and covariance) on checked groups; the filter step reads `smoothing` without its mode."""
+    max_cost_mm, clip_mm, min_joints, max_age_s, assignment, depth_sigma = association
+    params, with_cov = smoothing.params(), smoothing.measurement == 'covariance'
+    n, nj, times, n_step_rows, n_starts = _checked_rows(poses, covariance, with_cov, times, step_rows, step_starts, 'step_starts', 'S')
     if min_joints is None:
         min_joints = (nj + 1) // 2
     if min_joints > nj:
         raise ValueError(f'min_joints must be at most the {nj} joints, got {min_joints!r}')
-    with_cov = measurement == 'covariance'
-    if with_cov and (covariance is None or tuple(covariance.shape) not in ((n, nj, 3, 3), (n, nj, 9))):
-        raise ValueError(f"measurement='covariance' needs covariance [{n},{nj},3,3], got "
-                         f'{None if covariance is None else tuple(covariance.shape)}')
     dev = poses.device
-    if not isinstance(times, torch.Tensor):
-        times = torch.from_numpy(np.ascontiguousarray(np.asarray(times, np.float64).reshape(-1)))
-    if times.numel() != n:
-        raise ValueError(f'times must hold one value per pose row ({n}), got {times.numel()}')
-    n_step_rows = int(step_rows.numel() if isinstance(step_rows, torch.Tensor) else np.asarray(step_rows).size)
-    n_starts = int(step_starts.numel() if isinstance(step_starts, torch.Tensor) else np.asarray(step_starts).size)
-    if n_starts < 1:
-        raise ValueError('step_starts must hold S + 1 offsets (S >= 0)')
     if not isinstance(step_starts, torch.Tensor):
         sizes = np.diff(np.asarray(step_starts, np.int64).reshape(-1))
         if len(sizes) and sizes.max() > ASSOC_MAX:
@@ -751,28 +789,24 @@ def _associate_tracks(poses, covariance, times, step_rows, step_starts, state, i
     step_rows, step_starts = _i32(step_rows, dev).reshape(-1), _i32(step_starts, dev).reshape(-1)
     ws = torch.empty(lib.metro_associate_tracks_workspace_bytes(n_tracks, nj), dtype=torch.uint8, device=dev)
     cs = _lib.MetroSpec(n_joints_out=nj)
+    found = AssociatedTracks(track_index, track_id, cost, rows, starts, n_new, n_dropped,
+                             ws.view(torch.float64).view(n_tracks, nj, TRACK_STATE_DOUBLES))
+    shared = (_p(times), n, _p(step_rows), n_step_rows, _p(step_starts), n_starts - 1, C.byref(cs), *params[1:], float(max_cost_mm),
+              float(clip_mm), int(min_joints), float(max_age_s), _p(state), n_tracks, _p(ids), _p(next_id), _p(ws),
+              *(_p(t) for t in found[:7]))                  # every entry's arguments between (poses, cov) and its own tail
     if rays is not None:
         poses = poses.to(torch.float32).clone(memory_format=torch.contiguous_format)
         cov = covariance.to(torch.float32).reshape(n, nj, 9).clone(memory_format=torch.contiguous_format)
-        single_box, ray, depth_sigma = _i32(rays[0], dev).reshape(-1), rays[1].contiguous(), rays[2]
+        single_box, ray = _i32(rays[0], dev).reshape(-1), rays[1].contiguous()
         ray_depth, n_unplaced = torch.empty((n, nj), dtype=torch.float32, device=dev), i32(1)
-        check(lib.metro_associate_tracks_rays(_p(poses), _p(cov), _p(times), n, _p(step_rows), n_step_rows, _p(step_starts),
-                                              n_starts - 1, C.byref(cs), *params[1:], float(max_cost_mm), float(clip_mm),
-                                              int(min_joints), float(max_age_s), _p(state), n_tracks, _p(ids), _p(next_id), _p(ws),
-                                              _p(track_index), _p(track_id), _p(cost), _p(rows), _p(starts), _p(n_new), _p(n_dropped),
-                                              int(assignment == 'optimal'), _p(single_box), _p(ray), depth_sigma, _p(ray_depth),
-                                              _p(n_unplaced), _stream(dev)), 'metro_associate_tracks_rays')
-        return RayAssociatedTracks(track_index, track_id, cost, rows, starts, n_new, n_dropped,
-                                   ws.view(torch.float64).view(n_tracks, nj, TRACK_STATE_DOUBLES), poses, cov, ray_depth, n_unplaced)
+        check(lib.metro_associate_tracks_rays(_p(poses), _p(cov), *shared, int(assignment == 'optimal'), _p(single_box), _p(ray),
+                                              depth_sigma, _p(ray_depth), _p(n_unplaced), _stream(dev)), 'metro_associate_tracks_rays')
+        return RayAssociatedTracks(*found, poses, cov, ray_depth, n_unplaced)
     poses = poses.to(torch.float32).contiguous()
     cov = covariance.to(torch.float32).reshape(n, nj, 9).contiguous() if with_cov else None
     entry = 'metro_associate_tracks_optimal' if assignment == 'optimal' else 'metro_associate_tracks'
-    check(getattr(lib, entry)(_p(poses), _p(cov), _p(times), n, _p(step_rows), n_step_rows, _p(step_starts), n_starts - 1,
-                              C.byref(cs), *params[1:], float(max_cost_mm), float(clip_mm), int(min_joints), float(max_age_s),
-                              _p(state), n_tracks, _p(ids), _p(next_id), _p(ws), _p(track_index), _p(track_id), _p(cost), _p(rows),
-                              _p(starts), _p(n_new), _p(n_dropped), _stream(dev)), entry)
-    return AssociatedTracks(track_index, track_id, cost, rows, starts, n_new, n_dropped,
-                            ws.view(torch.float64).view(n_tracks, nj, TRACK_STATE_DOUBLES))
+    check(getattr(lib, entry)(_p(poses), _p(cov), *shared, _stream(dev)), entry)
+    return found
 
 
 BONE_STAT_DOUBLES = 4                # per (track slot, edge): S0 = sum 1/v, S1 = sum l/v, count, rejected

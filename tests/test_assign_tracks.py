@@ -371,8 +371,6 @@ def test_follow_calls_take_the_rule_where_their_signature_allows():
     world = inspect.signature(FR.follow_world_poses_in_frames).parameters
     assert list(world)[-2:] == ['crop_dtype', 'assignment'] and world['assignment'].default == 'greedy'
     assert 'assignment' not in inspect.signature(FR.follow_poses_in_frames).parameters, 'its parameter list is pinned'
-    private = list(inspect.signature(FR._follow_poses).parameters)
-    assert private == list(inspect.signature(FR.follow_poses_in_frames).parameters) + ['assignment']
     from metro_pose3d_amd.camera import Camera
     cam = Camera(np.array([[500., 0, 4], [0, 500, 4], [0, 0, 1]]))
     frames = [np.zeros((8, 8, 3), np.uint8)] * 2
@@ -380,10 +378,10 @@ def test_follow_calls_take_the_rule_where_their_signature_allows():
         with pytest.raises(ValueError, match='assignment'):
             FR.follow_world_poses_in_frames(frames, [[0, 0, 4, 4], [1, 1, 4, 4]], 'no-such-model.npz', [cam, cam], (0, 1), (0.0, 0.0),
                                             assignment=bad)
+        with pytest.raises(ValueError, match='assignment'):     # the one road of a rule to one-camera following: the group, built
+            MH.Association.checked(300.0, 600.0, None, 1.0, bad)  # by Follower
         with pytest.raises(ValueError, match='assignment'):
-            FR._follow_poses(frames, [[0, 0, 4, 4]], 'no-such-model.npz', cam, (0,), (0.0,), None, 64, 300.0, 600.0, None, 1.0, 'smooth',
-                             'covariance', 4e6, 1.0, 1.0, 2000.0, None, 'true-root-depth', None, [3000.0], 'camera', None, None, None,
-                             'auto', 'rgb', 'bt601', 'float32', bad)
+            FR.Follower('no-such-model.npz', cam, assignment=bad)
 
 
 def test_follower_checks_its_keywords_at_construction():
