@@ -16,9 +16,13 @@
 // and then writes the CSR per slot that metro_smooth_tracks reads.  The cost matrix lives in LDS: 128 rows of 129 floats
 // (64.5 KiB of the CU's 160 KiB; the odd row stride keeps the column walk of the strike off a single bank).  The working
 // state lives in global memory and is exchanged only within the workgroup, across __syncthreads().
-// The steps below take (tid, nt): thread tid of nt covers the items tid, tid + nt, ...  The kernel calls them with its 256
-// threads and a workgroup barrier between steps; tests/test_follow_tracks.py runs the same steps on the host with one thread.
+// The steps below take (tid, nt): thread tid of nt covers the items tid, tid + nt, ...  Their order and the barriers between
+// them are written once, in assoc_walk at the end of the file, for both assignment rules, with and without ray rows, and for
+// whoever executes it: the kernel's 256 threads (AssocWorkgroup) or one thread on the host (tests/assoc_host.py, where
+// tests/test_follow_tracks.py, test_assign_tracks.py and test_single_view.py run this very walk).
 // fp64 arithmetic on the fp32 inputs, no FMA contraction.
+#include <type_traits>
+
 #include "metro_common.h"
 #include "smooth_step.h"
 
@@ -29,28 +33,6 @@ namespace metro {
 constexpr int ASSOC_MAX = METRO_ASSOC_MAX;               // boxes per step, and track slots
 constexpr int ASSOC_LD = ASSOC_MAX + 1;                  // row stride of the cost matrix, in floats
 constexpr int ASSOC_THREADS = 256;
-
-struct AssocArgs {
-    const float* poses;      // [n][J][3] mm, absolute
-    const float* cov;        // [n][J][9] mm^2 (METRO_SMOOTH_COVARIANCE)
-    const double* times;     // [n] s
-    const int* step_rows;    // [n_step_rows] indices into the n pose rows
-    const int* step_starts;  // [n_steps + 1]
-    double* state;           // [T][J][28]: only the retirement writes it
-    int* ids;                // [T]
-    int* next_id;            // [1]
-    double* ws;              // [T][J][28] working copy of the state
-    int* track_index;        // [n]
-    int* track_id;           // [n]
-    float* cost_out;         // [n]
-    int* rows_out;           // [n]
-    int* starts_out;         // [T + 1]
-    int* n_new;              // [1]
-    int* n_dropped;          // [1]
-    int n, n_step_rows, n_steps, n_tracks, n_out, measurement, min_joints;
-    double q, r2, cov_scale, v02, gate, clip, max_age;
-    float max_cost;
-};
 
 struct AssocCand { float v; int idx; };                  // idx = slot * ASSOC_LD + position: its order is (slot, position)'s
 
@@ -329,60 +311,6 @@ __host__ __device__ inline void assoc_finish(const AssocArgs& a, const AssocLds&
     }
 }
 
-__global__ __launch_bounds__(ASSOC_THREADS) void associate_tracks_kernel(AssocArgs a) {
-    __shared__ AssocLds l;
-    __shared__ AssocCand wave_best[ASSOC_THREADS / 64];
-    const int tid = threadIdx.x, nt = ASSOC_THREADS;
-    assoc_begin(a, l, tid, nt);
-    __syncthreads();
-    double t_first = 0.0;
-    const bool have_first = assoc_first_time(a, t_first);
-    assoc_retire(a, l, have_first, t_first, tid, nt);
-    __syncthreads();
-    for (int s = 0; s < a.n_steps; ++s) {                  // every branch below is taken by all threads or by none
-        int lo, m;
-        double t_step;
-        assoc_step_range(a, s, lo, m);
-        if (!assoc_step_time(a, lo, m, t_step)) continue;
-        assoc_step_boxes(a, l, lo, m, tid, nt);
-        __syncthreads();
-        assoc_costs(a, l, m, t_step, tid, nt);
-        __syncthreads();
-        const int rounds = a.n_tracks < m ? a.n_tracks : m;
-        for (int round = 0; round < rounds; ++round) {
-            AssocCand best = assoc_scan(l, a.n_tracks, m, tid, nt);
-            for (int off = 32; off > 0; off >>= 1) {
-                const AssocCand other = {__shfl_xor(best.v, off), __shfl_xor(best.idx, off)};
-                if (assoc_cand_less(other, best)) best = other;
-            }
-            if ((tid & 63) == 0) wave_best[tid >> 6] = best;
-            __syncthreads();
-            best = wave_best[0];
-            for (int w = 1; w < ASSOC_THREADS / 64; ++w)
-                if (assoc_cand_less(wave_best[w], best)) best = wave_best[w];
-            if (!(best.v < a.max_cost)) break;             // the same value in every thread
-            assoc_strike(l, a.n_tracks, m, best, tid, nt);
-            __syncthreads();                               // also: wave_best is read before it is written again
-        }
-        assoc_births(a, l, m, tid, nt);
-        __syncthreads();
-        assoc_apply(a, l, m, tid, nt);
-        __syncthreads();
-        assoc_filter(a, l, m, tid, nt);
-        __syncthreads();                                   // the working state and the box arrays, before the next step
-    }
-    assoc_starts(a, l, tid, nt);
-    __syncthreads();
-    for (int s = 0; s < a.n_steps; ++s) {
-        int lo, m;
-        assoc_step_range(a, s, lo, m);
-        if (m == 0) continue;
-        assoc_group_step(a, l, lo, m, tid, nt);
-        __syncthreads();
-    }
-    assoc_finish(a, l, tid, nt);
-}
-
 // ---- the optimal assignment (metro_associate_tracks_optimal): the block between assoc_costs and assoc_births ----
 // The one-to-one set of admissible pairs (c < max_cost) of the largest total gain sum (max_cost - c): the linear assignment
 // problem with one extra column of unlimited capacity at cost max_cost that means "unmatched".  Shortest augmenting paths
@@ -413,7 +341,7 @@ struct AssocPath {
     int end;                                             // -2: searching, -1: ended in the sink, >= 0: ended in this free slot
 };
 
-__host__ __device__ inline bool assoc_candd_less(const AssocCandD& x, const AssocCandD& y) {
+__host__ __device__ inline bool assoc_cand_less(const AssocCandD& x, const AssocCandD& y) {
     return x.v < y.v || (x.v == y.v && x.idx < y.idx);
 }
 
@@ -461,7 +389,7 @@ __host__ __device__ inline AssocCandD assoc_opt_relax(const AssocArgs& a, const 
             }
         }
         const AssocCandD x = {o.dist[t], t};
-        if (assoc_candd_less(x, best)) best = x;
+        if (assoc_cand_less(x, best)) best = x;
     }
     return best;
 }
@@ -515,121 +443,6 @@ __host__ __device__ inline void assoc_opt_pairs(const AssocArgs& a, AssocLds& l,
     }
 }
 
-__global__ __launch_bounds__(ASSOC_THREADS) void associate_tracks_optimal_kernel(AssocArgs a) {
-    __shared__ AssocLds l;
-    __shared__ AssocOptLds o;
-    __shared__ AssocCandD wave_best[2][ASSOC_THREADS / 64];   // two sets in turn: one barrier per visit
-    const int tid = threadIdx.x, nt = ASSOC_THREADS;
-    assoc_begin(a, l, tid, nt);
-    __syncthreads();
-    double t_first = 0.0;
-    const bool have_first = assoc_first_time(a, t_first);
-    assoc_retire(a, l, have_first, t_first, tid, nt);
-    __syncthreads();
-    int turn = 0;
-    for (int s = 0; s < a.n_steps; ++s) {                  // every branch below is taken by all threads or by none
-        int lo, m;
-        double t_step;
-        assoc_step_range(a, s, lo, m);
-        if (!assoc_step_time(a, lo, m, t_step)) continue;
-        assoc_step_boxes(a, l, lo, m, tid, nt);
-        assoc_opt_begin(a, o, m, tid, nt);
-        __syncthreads();
-        assoc_costs(a, l, m, t_step, tid, nt);
-        __syncthreads();
-        for (int k = 0; k < m; ++k) {
-            AssocPath p = assoc_opt_root(a, o, k, tid, nt);
-            for (int visit = 0; visit <= a.n_tracks && p.end == -2; ++visit) {
-                AssocCandD best = assoc_opt_relax(a, l, o, p, tid, nt);
-                for (int off = 32; off > 0; off >>= 1) {
-                    const AssocCandD other = {__shfl_xor(best.v, off), __shfl_xor(best.idx, off)};
-                    if (assoc_candd_less(other, best)) best = other;
-                }
-                if ((tid & 63) == 0) wave_best[turn][tid >> 6] = best;
-                __syncthreads();
-                best = wave_best[turn][0];
-                for (int w = 1; w < ASSOC_THREADS / 64; ++w)
-                    if (assoc_candd_less(wave_best[turn][w], best)) best = wave_best[turn][w];
-                turn ^= 1;
-                assoc_opt_advance(a, o, p, best);          // the same value in every thread
-            }
-            assoc_opt_duals(a, o, p, k, tid, nt);
-            __syncthreads();                               // the duals read slot_box before the path rewrites it
-            assoc_opt_augment(a, o, p, k, tid);
-            __syncthreads();
-        }
-        assoc_opt_pairs(a, l, o, m, tid, nt);
-        __syncthreads();
-        assoc_births(a, l, m, tid, nt);
-        __syncthreads();
-        assoc_apply(a, l, m, tid, nt);
-        __syncthreads();
-        assoc_filter(a, l, m, tid, nt);
-        __syncthreads();                                   // the working state and the box arrays, before the next step
-    }
-    assoc_starts(a, l, tid, nt);
-    __syncthreads();
-    for (int s = 0; s < a.n_steps; ++s) {
-        int lo, m;
-        assoc_step_range(a, s, lo, m);
-        if (m == 0) continue;
-        assoc_group_step(a, l, lo, m, tid, nt);
-        __syncthreads();
-    }
-    assoc_finish(a, l, tid, nt);
-}
-
-AssocArgs make_assoc_args(const float* poses, const float* cov, const double* times, int n, const int* step_rows, int n_step_rows,
-                          const int* step_starts, int n_steps, int n_out, int measurement, double q, double r_floor, double cov_scale,
-                          double v0, double gate, float max_cost_mm, double clip_mm, int min_joints, double max_age_s, double* state,
-                          int n_tracks, int* ids, int* next_id, double* ws, int* track_index, int* track_id, float* cost_out,
-                          int* rows_out, int* starts_out, int* n_new, int* n_dropped) {
-    AssocArgs a;
-    a.poses = poses; a.cov = cov; a.times = times; a.step_rows = step_rows; a.step_starts = step_starts;
-    a.state = state; a.ids = ids; a.next_id = next_id; a.ws = ws;
-    a.track_index = track_index; a.track_id = track_id; a.cost_out = cost_out; a.rows_out = rows_out; a.starts_out = starts_out;
-    a.n_new = n_new; a.n_dropped = n_dropped;
-    a.n = n; a.n_step_rows = n_step_rows; a.n_steps = n_steps; a.n_tracks = n_tracks; a.n_out = n_out;
-    a.measurement = measurement; a.min_joints = min_joints;
-    a.q = q; a.r2 = r_floor * r_floor; a.cov_scale = cov_scale; a.v02 = v0 * v0; a.gate = gate;
-    a.clip = clip_mm; a.max_age = max_age_s; a.max_cost = max_cost_mm;
-    return a;
-}
-
-size_t associate_tracks_workspace_bytes(int n_tracks, int n_out) {
-    return (size_t)(n_tracks > 0 ? n_tracks : 0) * (size_t)(n_out > 0 ? n_out : 0) * SMOOTH_STATE_DOUBLES * sizeof(double);
-}
-
-int launch_associate_tracks(const float* poses, const float* cov, const double* times, int n, const int* step_rows, int n_step_rows,
-                            const int* step_starts, int n_steps, int n_out, int measurement, double q, double r_floor,
-                            double cov_scale, double v0, double gate, float max_cost_mm, double clip_mm, int min_joints,
-                            double max_age_s, double* state, int n_tracks, int* ids, int* next_id, void* workspace, int* track_index,
-                            int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new, int* n_dropped,
-                            hipStream_t stream) {
-    if (note_kernel("associate_tracks")) return METRO_OK;
-    const AssocArgs a = make_assoc_args(poses, cov, times, n, step_rows, n_step_rows, step_starts, n_steps, n_out, measurement, q,
-                                        r_floor, cov_scale, v0, gate, max_cost_mm, clip_mm, min_joints, max_age_s, state, n_tracks,
-                                        ids, next_id, static_cast<double*>(workspace), track_index, track_id, cost_out, rows_out,
-                                        starts_out, n_new, n_dropped);
-    hipLaunchKernelGGL(associate_tracks_kernel, dim3(1), dim3(ASSOC_THREADS), 0, stream, a);
-    return launch_status("associate_tracks");
-}
-
-int launch_associate_tracks_optimal(const float* poses, const float* cov, const double* times, int n, const int* step_rows, int n_step_rows,
-                                    const int* step_starts, int n_steps, int n_out, int measurement, double q, double r_floor,
-                                    double cov_scale, double v0, double gate, float max_cost_mm, double clip_mm, int min_joints,
-                                    double max_age_s, double* state, int n_tracks, int* ids, int* next_id, void* workspace, int* track_index,
-                                    int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new, int* n_dropped,
-                                    hipStream_t stream) {
-    if (note_kernel("associate_tracks_optimal")) return METRO_OK;
-    const AssocArgs a = make_assoc_args(poses, cov, times, n, step_rows, n_step_rows, step_starts, n_steps, n_out, measurement, q,
-                                                r_floor, cov_scale, v0, gate, max_cost_mm, clip_mm, min_joints, max_age_s, state, n_tracks,
-                                                ids, next_id, static_cast<double*>(workspace), track_index, track_id, cost_out, rows_out,
-                                                starts_out, n_new, n_dropped);
-    hipLaunchKernelGGL(associate_tracks_optimal_kernel, dim3(1), dim3(ASSOC_THREADS), 0, stream, a);
-    return launch_status("associate_tracks_optimal");
-}
-
 // ---- the same walk with RAY rows among the point rows (metro_associate_tracks_rays) ----
 // A row b with single_box[b] >= 0 is a person one camera sees: it has no point, but one ray per joint, rays[b][j] = o (3), d (3),
 // sigma2, views (metro_person_rays).  Point rows go through the steps above unchanged; for a ray row
@@ -646,19 +459,10 @@ int launch_associate_tracks_optimal(const float* poses, const float* cov, const 
 //   filter    unchanged: smooth_filter_row reads the fp32 arrays it always reads, so metro_smooth_tracks on the CSR and the
 //             arrays this launch wrote leaves the working state, bit for bit.  A placed joint whose ROUNDED R fails smooth_pd3
 //             is predict-only (used 0): the safe outcome.
-// AssocLds, AssocArgs and AssocOptLds keep their layout; the additions live in AssocRayArgs and AssocRayLds.
+// AssocLds, AssocArgs and AssocOptLds keep their layout; the additions live in AssocRayArgs (metro_common.h) and AssocRayLds, and
+// a walk without ray rows (assoc_walk<.., false>) neither calls a step of this section nor touches an AssocRayLds.
 
 constexpr int ASSOC_RAY_DOUBLES = 8;
-
-struct AssocRayArgs : AssocArgs {
-    float* poses_w;          // poses and
-    float* cov_w;            // cov, writable: the place step fills the ray rows
-    const int* single_box;   // [n] >= 0: the row is a ray row
-    const double* rays;      // [n][J][8]
-    double depth_var;        // depth_sigma_mm^2
-    float* ray_depth;        // [n][J]
-    int* n_unplaced;         // [1]
-};
 
 struct AssocRayLds {
     int box_ray[ASSOC_MAX];                              // the position holds a ray row
@@ -772,127 +576,147 @@ __host__ __device__ inline void assoc_ray_finish(const AssocRayArgs& a, const As
     if (tid == 0) a.n_unplaced[0] = r.n_unplaced;
 }
 
-template <bool OPTIMAL>
-__global__ __launch_bounds__(ASSOC_THREADS) void associate_tracks_rays_kernel(AssocRayArgs a) {
-    __shared__ AssocLds l;
-    __shared__ AssocRayLds r;
-    __shared__ AssocOptLds o;                              // referenced by the optimal instantiation only
-    __shared__ AssocCand wave_best[ASSOC_THREADS / 64];
-    __shared__ AssocCandD wave_best_d[2][ASSOC_THREADS / 64];
-    const int tid = threadIdx.x, nt = ASSOC_THREADS;
+// ---- the walk: the order of the steps and the barriers between them, for every rule, with and without ray rows ----
+// A TEAM executes it: `tid` of `nt` for the steps, sync() where every member must have finished the step before, and least(x),
+// the smallest candidate any member holds (the same value in all of them).  search() marks where the search of one box starts;
+// only a team that counts the visits of a search does anything there.
+
+template <bool RAYS>
+using AssocWalkArgs = std::conditional_t<RAYS, AssocRayArgs, AssocArgs>;
+
+// `o` is touched under OPTIMAL only and `r` under RAYS only
+template <bool OPTIMAL, bool RAYS, class Team>
+__host__ __device__ inline void assoc_walk(const AssocWalkArgs<RAYS>& a, AssocLds& l, AssocOptLds& o, AssocRayLds& r, Team& team) {
+    const int tid = team.tid, nt = team.nt;
     assoc_begin(a, l, tid, nt);
-    assoc_ray_begin(a, r, tid, nt);
-    __syncthreads();
+    if constexpr (RAYS) assoc_ray_begin(a, r, tid, nt);
+    team.sync();
     double t_first = 0.0;
     const bool have_first = assoc_first_time(a, t_first);
     assoc_retire(a, l, have_first, t_first, tid, nt);
-    __syncthreads();
-    int turn = 0;
-    for (int s = 0; s < a.n_steps; ++s) {                  // every branch below is taken by all threads or by none
+    team.sync();
+    for (int s = 0; s < a.n_steps; ++s) {                  // every branch below is taken by all members or by none
         int lo, m;
         double t_step;
         assoc_step_range(a, s, lo, m);
         if (!assoc_step_time(a, lo, m, t_step)) continue;
         assoc_step_boxes(a, l, lo, m, tid, nt);
-        assoc_ray_step_boxes(a, l, r, m, tid, nt);
+        if constexpr (RAYS) assoc_ray_step_boxes(a, l, r, m, tid, nt);
         if constexpr (OPTIMAL) assoc_opt_begin(a, o, m, tid, nt);
-        __syncthreads();
+        team.sync();
         assoc_costs(a, l, m, t_step, tid, nt);
-        assoc_ray_costs(a, l, r, m, t_step, tid, nt);
-        __syncthreads();
+        if constexpr (RAYS) assoc_ray_costs(a, l, r, m, t_step, tid, nt);
+        team.sync();
         if constexpr (OPTIMAL) {
             for (int k = 0; k < m; ++k) {
+                team.search();
                 AssocPath p = assoc_opt_root(a, o, k, tid, nt);
                 for (int visit = 0; visit <= a.n_tracks && p.end == -2; ++visit) {
-                    AssocCandD best = assoc_opt_relax(a, l, o, p, tid, nt);
-                    for (int off = 32; off > 0; off >>= 1) {
-                        const AssocCandD other = {__shfl_xor(best.v, off), __shfl_xor(best.idx, off)};
-                        if (assoc_candd_less(other, best)) best = other;
-                    }
-                    if ((tid & 63) == 0) wave_best_d[turn][tid >> 6] = best;
-                    __syncthreads();
-                    best = wave_best_d[turn][0];
-                    for (int w = 1; w < ASSOC_THREADS / 64; ++w)
-                        if (assoc_candd_less(wave_best_d[turn][w], best)) best = wave_best_d[turn][w];
-                    turn ^= 1;
-                    assoc_opt_advance(a, o, p, best);      // the same value in every thread
+                    const AssocCandD best = team.least(assoc_opt_relax(a, l, o, p, tid, nt));
+                    assoc_opt_advance(a, o, p, best);
                 }
                 assoc_opt_duals(a, o, p, k, tid, nt);
-                __syncthreads();                           // the duals read slot_box before the path rewrites it
+                team.sync();                               // the duals read slot_box before the path rewrites it
                 assoc_opt_augment(a, o, p, k, tid);
-                __syncthreads();
+                team.sync();
             }
             assoc_opt_pairs(a, l, o, m, tid, nt);
-            __syncthreads();
+            team.sync();
         } else {
             const int rounds = a.n_tracks < m ? a.n_tracks : m;
             for (int round = 0; round < rounds; ++round) {
-                AssocCand best = assoc_scan(l, a.n_tracks, m, tid, nt);
-                for (int off = 32; off > 0; off >>= 1) {
-                    const AssocCand other = {__shfl_xor(best.v, off), __shfl_xor(best.idx, off)};
-                    if (assoc_cand_less(other, best)) best = other;
-                }
-                if ((tid & 63) == 0) wave_best[tid >> 6] = best;
-                __syncthreads();
-                best = wave_best[0];
-                for (int w = 1; w < ASSOC_THREADS / 64; ++w)
-                    if (assoc_cand_less(wave_best[w], best)) best = wave_best[w];
-                if (!(best.v < a.max_cost)) break;         // the same value in every thread
+                const AssocCand best = team.least(assoc_scan(l, a.n_tracks, m, tid, nt));
+                if (!(best.v < a.max_cost)) break;
                 assoc_strike(l, a.n_tracks, m, best, tid, nt);
-                __syncthreads();                           // also: wave_best is read before it is written again
+                team.sync();                               // also: least() may not be entered again before every member has read its result
             }
         }
         assoc_births(a, l, m, tid, nt);
-        __syncthreads();
+        team.sync();
         assoc_apply(a, l, m, tid, nt);
-        __syncthreads();
-        assoc_ray_count(l, r, m, tid);
-        assoc_ray_place(a, l, r, m, t_step, tid, nt);
-        __syncthreads();
+        team.sync();
+        if constexpr (RAYS) {
+            assoc_ray_count(l, r, m, tid);
+            assoc_ray_place(a, l, r, m, t_step, tid, nt);
+            team.sync();
+        }
         assoc_filter(a, l, m, tid, nt);
-        __syncthreads();                                   // the working state and the box arrays, before the next step
+        team.sync();                                       // the working state and the box arrays, before the next step
     }
     assoc_starts(a, l, tid, nt);
-    __syncthreads();
+    team.sync();
     for (int s = 0; s < a.n_steps; ++s) {
         int lo, m;
         assoc_step_range(a, s, lo, m);
         if (m == 0) continue;
         assoc_group_step(a, l, lo, m, tid, nt);
-        __syncthreads();
+        team.sync();
     }
     assoc_finish(a, l, tid, nt);
-    assoc_ray_finish(a, r, tid);
+    if constexpr (RAYS) assoc_ray_finish(a, r, tid);
 }
 
-AssocRayArgs make_assoc_ray_args(const AssocArgs& base, float* poses, float* cov, const int* single_box, const double* rays,
-                                 double depth_sigma_mm, float* ray_depth, int* n_unplaced) {
-    AssocRayArgs a;
-    static_cast<AssocArgs&>(a) = base;
-    a.poses_w = poses; a.cov_w = cov; a.single_box = single_box; a.rays = rays;
-    a.depth_var = depth_sigma_mm * depth_sigma_mm; a.ray_depth = ray_depth; a.n_unplaced = n_unplaced;
-    return a;
-}
+// The kernel's team: the workgroup.  least() is a 64-lane __shfl_xor ladder, then one candidate per wave through LDS and ONE
+// barrier.  The greedy rule has a single set of them: the barrier after assoc_strike is what keeps a wave from writing the next
+// round's candidate while another still reads this round's.  A visit of the optimal search has no other barrier, so its
+// candidates go through two sets in turn: a wave can be at most one visit ahead of the slowest, and writes the other set.
+template <bool OPTIMAL>
+struct AssocWaveBest { std::conditional_t<OPTIMAL, AssocCandD, AssocCand> of[OPTIMAL ? 2 : 1][ASSOC_THREADS / 64]; };
 
-int launch_associate_tracks_rays(float* poses, float* cov, const double* times, int n, const int* step_rows, int n_step_rows,
-                                 const int* step_starts, int n_steps, int n_out, int measurement, double q, double r_floor,
-                                 double cov_scale, double v0, double gate, float max_cost_mm, double clip_mm, int min_joints,
-                                 double max_age_s, double* state, int n_tracks, int* ids, int* next_id, void* workspace, int* track_index,
-                                 int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new, int* n_dropped,
-                                 int assignment, const int* single_box, const double* rays, double depth_sigma_mm, float* ray_depth,
-                                 int* n_unplaced, hipStream_t stream) {
-    if (note_kernel("%s", assignment ? "associate_tracks_rays_optimal" : "associate_tracks_rays")) return METRO_OK;
-    const AssocArgs base = make_assoc_args(poses, cov, times, n, step_rows, n_step_rows, step_starts, n_steps, n_out, measurement, q,
-                                           r_floor, cov_scale, v0, gate, max_cost_mm, clip_mm, min_joints, max_age_s, state, n_tracks,
-                                           ids, next_id, static_cast<double*>(workspace), track_index, track_id, cost_out, rows_out,
-                                           starts_out, n_new, n_dropped);
-    const AssocRayArgs a = make_assoc_ray_args(base, poses, cov, single_box, rays, depth_sigma_mm, ray_depth, n_unplaced);
-    if (assignment) {
-        hipLaunchKernelGGL(associate_tracks_rays_kernel<true>, dim3(1), dim3(ASSOC_THREADS), 0, stream, a);
-        return launch_status("associate_tracks_rays_optimal");
+template <bool OPTIMAL>
+struct AssocWorkgroup {
+    AssocWaveBest<OPTIMAL>& wave_best;                     // in LDS
+    const int tid;
+    static constexpr int nt = ASSOC_THREADS;
+    int turn = 0;
+
+    __device__ void sync() const { __syncthreads(); }
+    __device__ void search() const {}
+    template <class Cand>
+    __device__ Cand least(Cand best) {
+        for (int off = 32; off > 0; off >>= 1) {
+            const Cand other = {__shfl_xor(best.v, off), __shfl_xor(best.idx, off)};
+            if (assoc_cand_less(other, best)) best = other;
+        }
+        if ((tid & 63) == 0) wave_best.of[turn][tid >> 6] = best;
+        __syncthreads();
+        best = wave_best.of[turn][0];
+        for (int w = 1; w < ASSOC_THREADS / 64; ++w)
+            if (assoc_cand_less(wave_best.of[turn][w], best)) best = wave_best.of[turn][w];
+        if constexpr (OPTIMAL) turn ^= 1;
+        return best;
     }
-    hipLaunchKernelGGL(associate_tracks_rays_kernel<false>, dim3(1), dim3(ASSOC_THREADS), 0, stream, a);
-    return launch_status("associate_tracks_rays");
+};
+
+template <bool OPTIMAL, bool RAYS>
+__global__ __launch_bounds__(ASSOC_THREADS) void associate_tracks_kernel(AssocWalkArgs<RAYS> a) {
+    __shared__ AssocLds l;
+    __shared__ AssocOptLds o;                              // allocated where the walk touches them only:
+    __shared__ AssocRayLds r;                              // o with OPTIMAL, r with RAYS
+    __shared__ AssocWaveBest<OPTIMAL> wave_best;
+    AssocWorkgroup<OPTIMAL> team = {wave_best, (int)threadIdx.x};
+    assoc_walk<OPTIMAL, RAYS>(a, l, o, r, team);
+}
+
+size_t associate_tracks_workspace_bytes(int n_tracks, int n_out) {
+    return (size_t)(n_tracks > 0 ? n_tracks : 0) * (size_t)(n_out > 0 ? n_out : 0) * SMOOTH_STATE_DOUBLES * sizeof(double);
+}
+
+template <bool OPTIMAL, bool RAYS>
+static int launch_assoc(const AssocWalkArgs<RAYS>& a, const char* id, hipStream_t stream) {
+    if (note_kernel("%s", id)) return METRO_OK;
+    hipLaunchKernelGGL((associate_tracks_kernel<OPTIMAL, RAYS>), dim3(1), dim3(ASSOC_THREADS), 0, stream, a);
+    return launch_status(id);
+}
+
+int launch_associate_tracks(const AssocArgs& a, bool optimal, hipStream_t stream) {
+    return optimal ? launch_assoc<true, false>(a, "associate_tracks_optimal", stream)
+                   : launch_assoc<false, false>(a, "associate_tracks", stream);
+}
+
+int launch_associate_tracks_rays(const AssocRayArgs& a, bool optimal, hipStream_t stream) {
+    return optimal ? launch_assoc<true, true>(a, "associate_tracks_rays_optimal", stream)
+                   : launch_assoc<false, true>(a, "associate_tracks_rays", stream);
 }
 
 }  // namespace metro

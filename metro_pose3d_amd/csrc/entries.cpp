@@ -779,55 +779,48 @@ int metro_smooth_tracks(const float* d_poses, const float* d_cov, const double* 
                                 d_used_out, static_cast<hipStream_t>(stream));
 }
 
-// the checks of the sizes and numbers that all association entries share
-static int associate_tracks_numbers(int32_t n, int32_t n_step_rows, int32_t n_steps, const MetroSpec* spec, int32_t measurement, double q,
-                                    double r_floor, double cov_scale, double v0, double gate, float max_cost_mm, double clip_mm,
-                                    int32_t min_joints, double max_age_s, int32_t n_tracks) {
+// The association entries build their record first (make_assoc_args; n_out 0 stands for a NULL spec, which the first check
+// below turns away) and check it afterwards.
+// The checks of the sizes and numbers that all of them share; r_floor and v0 as given, the record holds their squares.
+static int associate_tracks_numbers(const AssocArgs& a, const MetroSpec* spec, double r_floor, double v0) {
     METRO_CHECK_ARG(spec != nullptr, "associate_tracks: NULL spec");
     METRO_CHECK_ARG(spec->n_joints_out >= 1 && spec->n_joints_out <= METRO_MAX_JOINTS,
                     "associate_tracks: n_joints_out %d out of range [1, %d]", spec->n_joints_out, METRO_MAX_JOINTS);
-    METRO_CHECK_ARG(measurement == METRO_SMOOTH_ISOTROPIC || measurement == METRO_SMOOTH_COVARIANCE,
-                    "associate_tracks: measurement must be METRO_SMOOTH_ISOTROPIC or METRO_SMOOTH_COVARIANCE (got %d)", measurement);
-    METRO_CHECK_ARG(n >= 0 && n_step_rows >= 0 && n_steps >= 0,
-                    "associate_tracks: negative size (pose rows %d, step rows %d, steps %d)", n, n_step_rows, n_steps);
-    METRO_CHECK_ARG(n_tracks >= 1 && n_tracks <= METRO_ASSOC_MAX, "associate_tracks: %d track slots (1 to %d)", n_tracks,
+    METRO_CHECK_ARG(a.measurement == METRO_SMOOTH_ISOTROPIC || a.measurement == METRO_SMOOTH_COVARIANCE,
+                    "associate_tracks: measurement must be METRO_SMOOTH_ISOTROPIC or METRO_SMOOTH_COVARIANCE (got %d)", a.measurement);
+    METRO_CHECK_ARG(a.n >= 0 && a.n_step_rows >= 0 && a.n_steps >= 0,
+                    "associate_tracks: negative size (pose rows %d, step rows %d, steps %d)", a.n, a.n_step_rows, a.n_steps);
+    METRO_CHECK_ARG(a.n_tracks >= 1 && a.n_tracks <= METRO_ASSOC_MAX, "associate_tracks: %d track slots (1 to %d)", a.n_tracks,
                     METRO_ASSOC_MAX);
-    METRO_CHECK_ARG(q > 0.0, "associate_tracks: q must be > 0 (got %g)", q);
+    METRO_CHECK_ARG(a.q > 0.0, "associate_tracks: q must be > 0 (got %g)", a.q);
     METRO_CHECK_ARG(r_floor > 0.0, "associate_tracks: r_floor must be > 0 (got %g)", r_floor);
     METRO_CHECK_ARG(v0 > 0.0, "associate_tracks: v0 must be > 0 (got %g)", v0);
-    METRO_CHECK_ARG(cov_scale >= 0.0, "associate_tracks: cov_scale must be >= 0 (got %g)", cov_scale);
-    METRO_CHECK_ARG(gate >= 0.0, "associate_tracks: gate must be >= 0, 0 for none (got %g)", gate);
-    METRO_CHECK_ARG(max_cost_mm > 0.0f, "associate_tracks: max_cost_mm must be > 0 (got %g)", (double)max_cost_mm);
-    METRO_CHECK_ARG(clip_mm > 0.0, "associate_tracks: clip_mm must be > 0 (got %g)", clip_mm);
-    METRO_CHECK_ARG(max_age_s >= 0.0, "associate_tracks: max_age_s must be >= 0 (got %g)", max_age_s);
-    METRO_CHECK_ARG(min_joints >= 1 && min_joints <= spec->n_joints_out, "associate_tracks: min_joints %d outside [1, %d]",
-                    min_joints, spec->n_joints_out);
+    METRO_CHECK_ARG(a.cov_scale >= 0.0, "associate_tracks: cov_scale must be >= 0 (got %g)", a.cov_scale);
+    METRO_CHECK_ARG(a.gate >= 0.0, "associate_tracks: gate must be >= 0, 0 for none (got %g)", a.gate);
+    METRO_CHECK_ARG(a.max_cost > 0.0f, "associate_tracks: max_cost_mm must be > 0 (got %g)", (double)a.max_cost);
+    METRO_CHECK_ARG(a.clip > 0.0, "associate_tracks: clip_mm must be > 0 (got %g)", a.clip);
+    METRO_CHECK_ARG(a.max_age >= 0.0, "associate_tracks: max_age_s must be >= 0 (got %g)", a.max_age);
+    METRO_CHECK_ARG(a.min_joints >= 1 && a.min_joints <= spec->n_joints_out, "associate_tracks: min_joints %d outside [1, %d]",
+                    a.min_joints, spec->n_joints_out);
     return METRO_OK;
 }
 
-// the argument checks of both association entries, then the launch of one
-static int associate_tracks_entry(bool optimal, const float* d_poses, const float* d_cov, const double* d_times, int32_t n,
-                                  const int32_t* d_step_rows, int32_t n_step_rows, const int32_t* d_step_starts, int32_t n_steps,
-                                  const MetroSpec* spec, int32_t measurement, double q, double r_floor, double cov_scale,
-                                  double v0, double gate, float max_cost_mm, double clip_mm, int32_t min_joints, double max_age_s,
-                                  double* d_state, int32_t n_tracks, int32_t* d_ids, int32_t* d_next_id, void* d_workspace,
-                                  int32_t* d_track_index_out, int32_t* d_track_id_out, float* d_cost_out, int32_t* d_rows_out,
-                                  int32_t* d_starts_out, int32_t* d_n_new_out, int32_t* d_n_dropped_out, void* stream) {
-    if (const int rc = associate_tracks_numbers(n, n_step_rows, n_steps, spec, measurement, q, r_floor, cov_scale, v0, gate, max_cost_mm,
-                                                clip_mm, min_joints, max_age_s, n_tracks))
-        return rc;
-    if (n == 0 || n_step_rows == 0 || n_steps == 0) return METRO_OK;
-    METRO_CHECK_ARG(d_poses && d_times && d_step_rows && d_step_starts && d_state && d_ids && d_next_id && d_workspace &&
-                        d_track_index_out && d_track_id_out && d_cost_out && d_rows_out && d_starts_out && d_n_new_out &&
-                        d_n_dropped_out,
-                    "associate_tracks: NULL poses / times / steps / table / workspace / output pointer");
-    METRO_CHECK_ARG(measurement != METRO_SMOOTH_COVARIANCE || d_cov,
+static bool associate_tracks_nothing_to_do(const AssocArgs& a) { return a.n == 0 || a.n_step_rows == 0 || a.n_steps == 0; }
+
+// every pointer of the record but the covariance
+static bool associate_tracks_pointers(const AssocArgs& a) {
+    return a.poses && a.times && a.step_rows && a.step_starts && a.state && a.ids && a.next_id && a.ws && a.track_index && a.track_id &&
+           a.cost_out && a.rows_out && a.starts_out && a.n_new && a.n_dropped;
+}
+
+// the argument checks of both association entries without ray rows, then the launch of one
+static int associate_tracks_entry(bool optimal, const AssocArgs& a, const MetroSpec* spec, double r_floor, double v0, void* stream) {
+    if (const int rc = associate_tracks_numbers(a, spec, r_floor, v0)) return rc;
+    if (associate_tracks_nothing_to_do(a)) return METRO_OK;
+    METRO_CHECK_ARG(associate_tracks_pointers(a), "associate_tracks: NULL poses / times / steps / table / workspace / output pointer");
+    METRO_CHECK_ARG(a.measurement != METRO_SMOOTH_COVARIANCE || a.cov,
                     "associate_tracks: METRO_SMOOTH_COVARIANCE reads the covariance: NULL");
-    const auto launch = optimal ? launch_associate_tracks_optimal : launch_associate_tracks;
-    return launch(d_poses, d_cov, d_times, n, d_step_rows, n_step_rows, d_step_starts, n_steps, spec->n_joints_out, measurement, q,
-                  r_floor, cov_scale, v0, gate, max_cost_mm, clip_mm, min_joints, max_age_s, d_state, n_tracks, d_ids, d_next_id,
-                  d_workspace, d_track_index_out, d_track_id_out, d_cost_out, d_rows_out, d_starts_out, d_n_new_out, d_n_dropped_out,
-                  static_cast<hipStream_t>(stream));
+    return launch_associate_tracks(a, optimal, static_cast<hipStream_t>(stream));
 }
 
 size_t metro_associate_tracks_workspace_bytes(int32_t n_tracks, int32_t n_joints_out) {
@@ -841,10 +834,12 @@ int metro_associate_tracks(const float* d_poses, const float* d_cov, const doubl
                            int32_t n_tracks, int32_t* d_ids, int32_t* d_next_id, void* d_workspace, int32_t* d_track_index_out,
                            int32_t* d_track_id_out, float* d_cost_out, int32_t* d_rows_out, int32_t* d_starts_out,
                            int32_t* d_n_new_out, int32_t* d_n_dropped_out, void* stream) {
-    return associate_tracks_entry(false, d_poses, d_cov, d_times, n, d_step_rows, n_step_rows, d_step_starts, n_steps, spec,
-                                  measurement, q, r_floor, cov_scale, v0, gate, max_cost_mm, clip_mm, min_joints, max_age_s, d_state,
-                                  n_tracks, d_ids, d_next_id, d_workspace, d_track_index_out, d_track_id_out, d_cost_out, d_rows_out,
-                                  d_starts_out, d_n_new_out, d_n_dropped_out, stream);
+    const AssocArgs a = make_assoc_args(d_poses, d_cov, d_times, n, d_step_rows, n_step_rows, d_step_starts, n_steps,
+                                        spec ? spec->n_joints_out : 0, measurement, q, r_floor, cov_scale, v0, gate, max_cost_mm,
+                                        clip_mm, min_joints, max_age_s, d_state, n_tracks, d_ids, d_next_id, d_workspace,
+                                        d_track_index_out, d_track_id_out, d_cost_out, d_rows_out, d_starts_out, d_n_new_out,
+                                        d_n_dropped_out);
+    return associate_tracks_entry(false, a, spec, r_floor, v0, stream);
 }
 
 int metro_associate_tracks_optimal(const float* d_poses, const float* d_cov, const double* d_times, int32_t n,
@@ -854,10 +849,12 @@ int metro_associate_tracks_optimal(const float* d_poses, const float* d_cov, con
                                    int32_t n_tracks, int32_t* d_ids, int32_t* d_next_id, void* d_workspace, int32_t* d_track_index_out,
                                    int32_t* d_track_id_out, float* d_cost_out, int32_t* d_rows_out, int32_t* d_starts_out,
                                    int32_t* d_n_new_out, int32_t* d_n_dropped_out, void* stream) {
-    return associate_tracks_entry(true, d_poses, d_cov, d_times, n, d_step_rows, n_step_rows, d_step_starts, n_steps, spec,
-                                  measurement, q, r_floor, cov_scale, v0, gate, max_cost_mm, clip_mm, min_joints, max_age_s, d_state,
-                                  n_tracks, d_ids, d_next_id, d_workspace, d_track_index_out, d_track_id_out, d_cost_out, d_rows_out,
-                                  d_starts_out, d_n_new_out, d_n_dropped_out, stream);
+    const AssocArgs a = make_assoc_args(d_poses, d_cov, d_times, n, d_step_rows, n_step_rows, d_step_starts, n_steps,
+                                        spec ? spec->n_joints_out : 0, measurement, q, r_floor, cov_scale, v0, gate, max_cost_mm,
+                                        clip_mm, min_joints, max_age_s, d_state, n_tracks, d_ids, d_next_id, d_workspace,
+                                        d_track_index_out, d_track_id_out, d_cost_out, d_rows_out, d_starts_out, d_n_new_out,
+                                        d_n_dropped_out);
+    return associate_tracks_entry(true, a, spec, r_floor, v0, stream);
 }
 
 int metro_associate_tracks_rays(float* d_poses, float* d_cov, const double* d_times, int32_t n, const int32_t* d_step_rows,
@@ -869,28 +866,27 @@ int metro_associate_tracks_rays(float* d_poses, float* d_cov, const double* d_ti
                                 int32_t* d_n_new_out, int32_t* d_n_dropped_out, int32_t assignment, const int32_t* d_single_box,
                                 const double* d_rays, double depth_sigma_mm, float* d_ray_depth_out, int32_t* d_n_unplaced_out,
                                 void* stream) {
-    if (const int rc = associate_tracks_numbers(n, n_step_rows, n_steps, spec, measurement, q, r_floor, cov_scale, v0, gate, max_cost_mm,
-                                                clip_mm, min_joints, max_age_s, n_tracks))
-        return rc;
-    METRO_CHECK_ARG(measurement == METRO_SMOOTH_COVARIANCE,
+    const AssocArgs base = make_assoc_args(d_poses, d_cov, d_times, n, d_step_rows, n_step_rows, d_step_starts, n_steps,
+                                           spec ? spec->n_joints_out : 0, measurement, q, r_floor, cov_scale, v0, gate, max_cost_mm,
+                                           clip_mm, min_joints, max_age_s, d_state, n_tracks, d_ids, d_next_id, d_workspace,
+                                           d_track_index_out, d_track_id_out, d_cost_out, d_rows_out, d_starts_out, d_n_new_out,
+                                           d_n_dropped_out);
+    const AssocRayArgs a = make_assoc_ray_args(base, d_poses, d_cov, d_single_box, d_rays, depth_sigma_mm, d_ray_depth_out,
+                                               d_n_unplaced_out);
+    if (const int rc = associate_tracks_numbers(a, spec, r_floor, v0)) return rc;
+    METRO_CHECK_ARG(a.measurement == METRO_SMOOTH_COVARIANCE,
                     "associate_tracks_rays: measurement must be METRO_SMOOTH_COVARIANCE (an isotropic R ignores the ray's shape)");
     METRO_CHECK_ARG(assignment == 0 || assignment == 1, "associate_tracks_rays: assignment must be 0 (greedy) or 1 (optimal), got %d",
                     assignment);
     METRO_CHECK_ARG(std::isfinite(depth_sigma_mm) && depth_sigma_mm > 0.0,
                     "associate_tracks_rays: depth_sigma_mm must be finite and > 0 (got %g)", depth_sigma_mm);
-    METRO_CHECK_ARG((int64_t)n * spec->n_joints_out * 9 <= INT32_MAX, "associate_tracks_rays: %d pose rows overflow int32", n);
-    if (n == 0 || n_step_rows == 0 || n_steps == 0) return METRO_OK;
-    METRO_CHECK_ARG(d_poses && d_cov && d_times && d_step_rows && d_step_starts && d_state && d_ids && d_next_id && d_workspace &&
-                        d_track_index_out && d_track_id_out && d_cost_out && d_rows_out && d_starts_out && d_n_new_out &&
-                        d_n_dropped_out,
+    METRO_CHECK_ARG((int64_t)a.n * a.n_out * 9 <= INT32_MAX, "associate_tracks_rays: %d pose rows overflow int32", a.n);
+    if (associate_tracks_nothing_to_do(a)) return METRO_OK;
+    METRO_CHECK_ARG(associate_tracks_pointers(a) && a.cov,
                     "associate_tracks_rays: NULL poses / cov / times / steps / table / workspace / output pointer");
-    METRO_CHECK_ARG(d_single_box && d_rays && d_ray_depth_out && d_n_unplaced_out,
+    METRO_CHECK_ARG(a.single_box && a.rays && a.ray_depth && a.n_unplaced,
                     "associate_tracks_rays: NULL single_box / rays / ray_depth_out / n_unplaced_out pointer");
-    return launch_associate_tracks_rays(d_poses, d_cov, d_times, n, d_step_rows, n_step_rows, d_step_starts, n_steps, spec->n_joints_out,
-                                        measurement, q, r_floor, cov_scale, v0, gate, max_cost_mm, clip_mm, min_joints, max_age_s,
-                                        d_state, n_tracks, d_ids, d_next_id, d_workspace, d_track_index_out, d_track_id_out, d_cost_out,
-                                        d_rows_out, d_starts_out, d_n_new_out, d_n_dropped_out, assignment, d_single_box, d_rays,
-                                        depth_sigma_mm, d_ray_depth_out, d_n_unplaced_out, static_cast<hipStream_t>(stream));
+    return launch_associate_tracks_rays(a, assignment == 1, static_cast<hipStream_t>(stream));
 }
 
 int metro_track_bone_lengths(const float* d_poses, const float* d_cov, int32_t n, const int32_t* d_rows, int32_t n_rows,

@@ -548,29 +548,72 @@ int launch_smooth_tracks(const float* poses, const float* cov, const double* tim
                          const int* starts, int n_tracks, int n_out, int mode, int measurement, double q, double r_floor,
                          double cov_scale, double v0, double gate, double* state, void* workspace, float* poses_out,
                          float* velocity_out, float* cov_out, unsigned char* used_out, hipStream_t stream);
-// which box of a video continues which track: one workgroup over the steps of the call (associate_tracks.hip)
-size_t associate_tracks_workspace_bytes(int n_tracks, int n_out);
-int launch_associate_tracks(const float* poses, const float* cov, const double* times, int n, const int* step_rows, int n_step_rows,
-                            const int* step_starts, int n_steps, int n_out, int measurement, double q, double r_floor,
-                            double cov_scale, double v0, double gate, float max_cost_mm, double clip_mm, int min_joints,
-                            double max_age_s, double* state, int n_tracks, int* ids, int* next_id, void* workspace, int* track_index,
-                            int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new, int* n_dropped,
-                            hipStream_t stream);
-// the same walk with the optimal assignment in place of the greedy one (associate_tracks.hip)
-int launch_associate_tracks_optimal(const float* poses, const float* cov, const double* times, int n, const int* step_rows, int n_step_rows,
-                                    const int* step_starts, int n_steps, int n_out, int measurement, double q, double r_floor,
-                                    double cov_scale, double v0, double gate, float max_cost_mm, double clip_mm, int min_joints,
-                                    double max_age_s, double* state, int n_tracks, int* ids, int* next_id, void* workspace, int* track_index,
-                                    int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new, int* n_dropped,
-                                    hipStream_t stream);
-// the same walk, either assignment, with ray rows that are costed against the slots and placed as point measurements
-int launch_associate_tracks_rays(float* poses, float* cov, const double* times, int n, const int* step_rows, int n_step_rows,
+// which box of a video continues which track: one workgroup over the steps of the call (associate_tracks.hip).  The arguments
+// travel as ONE record from the public entry to the kernel: the entry builds it (make_assoc_args), checks it and hands it on
+struct AssocArgs {
+    const float* poses;      // [n][J][3] mm, absolute
+    const float* cov;        // [n][J][9] mm^2 (METRO_SMOOTH_COVARIANCE)
+    const double* times;     // [n] s
+    const int* step_rows;    // [n_step_rows] indices into the n pose rows
+    const int* step_starts;  // [n_steps + 1]
+    double* state;           // [T][J][28]: only the retirement writes it
+    int* ids;                // [T]
+    int* next_id;            // [1]
+    double* ws;              // [T][J][28] working copy of the state
+    int* track_index;        // [n]
+    int* track_id;           // [n]
+    float* cost_out;         // [n]
+    int* rows_out;           // [n]
+    int* starts_out;         // [T + 1]
+    int* n_new;              // [1]
+    int* n_dropped;          // [1]
+    int n, n_step_rows, n_steps, n_tracks, n_out, measurement, min_joints;
+    double q, r2, cov_scale, v02, gate, clip, max_age;
+    float max_cost;
+};
+
+// the same walk with ray rows that are costed against the slots and placed as point measurements: what it reads and writes more
+struct AssocRayArgs : AssocArgs {
+    float* poses_w;          // poses and
+    float* cov_w;            // cov, writable: the place step fills the ray rows
+    const int* single_box;   // [n] >= 0: the row is a ray row
+    const double* rays;      // [n][J][8]
+    double depth_var;        // depth_sigma_mm^2
+    float* ray_depth;        // [n][J]
+    int* n_unplaced;         // [1]
+};
+
+// the records from the arguments of the public entries, in their order; r2, v02 and depth_var are formed here, once, in fp64
+inline AssocArgs make_assoc_args(const float* poses, const float* cov, const double* times, int n, const int* step_rows, int n_step_rows,
                                  const int* step_starts, int n_steps, int n_out, int measurement, double q, double r_floor,
                                  double cov_scale, double v0, double gate, float max_cost_mm, double clip_mm, int min_joints,
                                  double max_age_s, double* state, int n_tracks, int* ids, int* next_id, void* workspace, int* track_index,
-                                 int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new, int* n_dropped,
-                                 int assignment, const int* single_box, const double* rays, double depth_sigma_mm, float* ray_depth,
-                                 int* n_unplaced, hipStream_t stream);
+                                 int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new, int* n_dropped) {
+    AssocArgs a;
+    a.poses = poses; a.cov = cov; a.times = times; a.step_rows = step_rows; a.step_starts = step_starts;
+    a.state = state; a.ids = ids; a.next_id = next_id; a.ws = static_cast<double*>(workspace);
+    a.track_index = track_index; a.track_id = track_id; a.cost_out = cost_out; a.rows_out = rows_out; a.starts_out = starts_out;
+    a.n_new = n_new; a.n_dropped = n_dropped;
+    a.n = n; a.n_step_rows = n_step_rows; a.n_steps = n_steps; a.n_tracks = n_tracks; a.n_out = n_out;
+    a.measurement = measurement; a.min_joints = min_joints;
+    a.q = q; a.r2 = r_floor * r_floor; a.cov_scale = cov_scale; a.v02 = v0 * v0; a.gate = gate;
+    a.clip = clip_mm; a.max_age = max_age_s; a.max_cost = max_cost_mm;
+    return a;
+}
+
+inline AssocRayArgs make_assoc_ray_args(const AssocArgs& base, float* poses, float* cov, const int* single_box, const double* rays,
+                                        double depth_sigma_mm, float* ray_depth, int* n_unplaced) {
+    AssocRayArgs a;
+    static_cast<AssocArgs&>(a) = base;
+    a.poses_w = poses; a.cov_w = cov; a.single_box = single_box; a.rays = rays;
+    a.depth_var = depth_sigma_mm * depth_sigma_mm; a.ray_depth = ray_depth; a.n_unplaced = n_unplaced;
+    return a;
+}
+
+size_t associate_tracks_workspace_bytes(int n_tracks, int n_out);
+// the greedy assignment or the optimal one; kernel notes associate_tracks[_rays][_optimal]
+int launch_associate_tracks(const AssocArgs& a, bool optimal, hipStream_t stream);
+int launch_associate_tracks_rays(const AssocRayArgs& a, bool optimal, hipStream_t stream);
 // the bone lengths of followed persons, accumulated per (track slot, skeleton edge) and read out (bone_lengths.hip)
 int launch_track_bone_lengths(const float* poses, const float* cov, int n, const int* rows, int n_rows, const int* starts, int n_tracks,
                               const int* ids, int n_joints, const int* edges, const int* edge_mirror, int n_edges,

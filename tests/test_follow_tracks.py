@@ -1,5 +1,5 @@
 """Boxes assigned to tracks over video, without a GPU: the fp64 restatement the GPU tests compare against
-(tests/follow_tracks_ref.py) on known answers, a stream cut into calls, the kernel's own steps compiled for the host against
+(tests/follow_tracks_ref.py) on known answers, a stream cut into calls, the kernel's own walk compiled for the host against
 that restatement on every case, the margin that keeps every case away from a decision a last bit could flip, the argument
 checks of the Python surface that run before any device is touched, and the new C symbols in header, bindings and library with
 their invalid-argument returns."""
@@ -14,7 +14,7 @@ import torch
 
 from metro_pose3d_amd import _lib, frames as FR, heads as MH
 from tests import follow_tracks_ref as FT
-from tests.helpers import compile_for_host
+from tests.assoc_host import compile_walk
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = FT.CASES
@@ -165,96 +165,10 @@ def test_stream_cut_into_calls_gives_the_ids_and_states_of_one_call(stream_whole
 
 @pytest.fixture(scope='module')
 def host_kernel(tmp_path_factory):
-    """associate_tracks.hip's steps are __host__ __device__ functions of (tid, nt): the source compiled for the host and run by one
-    thread in the kernel's order, the workgroup's LDS on the heap.  smooth_tracks.hip's per-joint function comes along for the
-    state the smoothing launch leaves on the CSR the walk wrote."""
-    tmp = tmp_path_factory.mktemp('host_follow_tracks')
-    dll = compile_for_host(tmp, 'host_follow_tracks', ['associate_tracks.hip', 'smooth_tracks.hip'], '''
-#include <memory>
-extern "C" void host_associate_tracks(const float* poses, const float* cov, const double* times, int n, const int* step_rows,
-                                      int n_step_rows, const int* step_starts, int n_steps, int n_out, int measurement, double q,
-                                      double r_floor, double cov_scale, double v0, double gate, float max_cost, double clip,
-                                      int min_joints, double max_age, double* state, int n_tracks, int* ids, int* next_id, double* ws,
-                                      int* track_index, int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new,
-                                      int* n_dropped) {
-    using namespace metro;
-    const AssocArgs a = make_assoc_args(poses, cov, times, n, step_rows, n_step_rows, step_starts, n_steps, n_out, measurement, q,
-                                        r_floor, cov_scale, v0, gate, max_cost, clip, min_joints, max_age, state, n_tracks, ids,
-                                        next_id, ws, track_index, track_id, cost_out, rows_out, starts_out, n_new, n_dropped);
-    std::unique_ptr<AssocLds> lds(new AssocLds);
-    AssocLds& l = *lds;
-    assoc_begin(a, l, 0, 1);
-    double t_first = 0.0;
-    const bool have_first = assoc_first_time(a, t_first);
-    assoc_retire(a, l, have_first, t_first, 0, 1);
-    for (int s = 0; s < a.n_steps; ++s) {
-        int lo, m;
-        double t_step;
-        assoc_step_range(a, s, lo, m);
-        if (!assoc_step_time(a, lo, m, t_step)) continue;
-        assoc_step_boxes(a, l, lo, m, 0, 1);
-        assoc_costs(a, l, m, t_step, 0, 1);
-        const int rounds = a.n_tracks < m ? a.n_tracks : m;
-        for (int round = 0; round < rounds; ++round) {
-            const AssocCand best = assoc_scan(l, a.n_tracks, m, 0, 1);
-            if (!(best.v < a.max_cost)) break;
-            assoc_strike(l, a.n_tracks, m, best, 0, 1);
-        }
-        assoc_births(a, l, m, 0, 1);
-        assoc_apply(a, l, m, 0, 1);
-        assoc_filter(a, l, m, 0, 1);
-    }
-    assoc_starts(a, l, 0, 1);
-    for (int s = 0; s < a.n_steps; ++s) {
-        int lo, m;
-        assoc_step_range(a, s, lo, m);
-        if (m == 0) continue;
-        assoc_group_step(a, l, lo, m, 0, 1);
-    }
-    assoc_finish(a, l, 0, 1);
-}
-extern "C" void host_filter_tracks(const float* poses, const float* cov, const double* times, int n, const int* rows, int n_rows,
-                                   const int* starts, int n_tracks, int n_out, int measurement, double q, double r_floor,
-                                   double cov_scale, double v0, double gate, double* state, float* poses_out) {
-    const metro::SmoothArgs a = metro::make_smooth_args(poses, cov, times, n, rows, n_rows, starts, n_tracks, n_out, METRO_SMOOTH_FILTER,
-                                                        measurement, q, r_floor, cov_scale, v0, gate, state, nullptr, poses_out, nullptr,
-                                                        nullptr, nullptr);
-    for (int idx = 0; idx < n_tracks * n_out; ++idx) metro::smooth_track_joint(a, idx);
-}
-''')
-    fn, flt = dll.host_associate_tracks, dll.host_filter_tracks
-    fn.restype = flt.restype = None
-    P = C.c_void_p
-    fn.argtypes = [P, P, P, C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int] + [C.c_double] * 5 + [C.c_float, C.c_double, C.c_int,
-                                                                                                    C.c_double, P, C.c_int] + [P] * 10
-    flt.argtypes = [P, P, P, C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int] + [C.c_double] * 5 + [P, P]
-    ptr = lambda a: P(a.ctypes.data if a is not None else 0)
-
-    def run(c):
-        """-> the dict FT.compare reads, outputs pre-filled with the sentinel, plus `smoothed_state`: what the smoothing kernel's
-        code (filter mode) leaves in the table's state on the CSR the walk wrote."""
-        poses = np.ascontiguousarray(c['poses'], np.float32)
-        n, nj = poses.shape[:2]
-        cov = None if c['cov'] is None else np.ascontiguousarray(c['cov'], np.float32)
-        times = np.ascontiguousarray(c['times'], np.float64)
-        step_rows, step_starts = np.ascontiguousarray(c['step_rows'], np.int32), np.ascontiguousarray(c['step_starts'], np.int32)
-        state, ids, next_id = np.array(c['state'], np.float64), np.array(c['ids'], np.int32), np.array(c['next_id'], np.int32).reshape(1)
-        cap = len(ids)
-        ws = np.full((cap, nj, 28), float(FT.SENTINEL))
-        ints = lambda k: np.full(k, FT.SENTINEL, np.int32)
-        track_index, track_id, rows, starts, n_new, n_dropped = ints(n), ints(n), ints(n), ints(cap + 1), ints(1), ints(1)
-        cost = np.full(n, float(FT.SENTINEL), np.float32)
-        kind = MH.SMOOTH_MEASUREMENTS[c['measurement']]
-        fn(ptr(poses), ptr(cov), ptr(times), n, ptr(step_rows), len(step_rows), ptr(step_starts), len(step_starts) - 1, nj, kind, c['q'],
-           c['r_floor'], c['cov_scale'], c['v0'], c['gate'], c['max_cost'], c['clip'], c['min_joints'], c['max_age'], ptr(state), cap,
-           ptr(ids), ptr(next_id), ptr(ws), ptr(track_index), ptr(track_id), ptr(cost), ptr(rows), ptr(starts), ptr(n_new),
-           ptr(n_dropped))
-        smoothed, poses_out = state.copy(), np.empty((n, nj, 3), np.float32)
-        flt(ptr(poses), ptr(cov), ptr(times), n, ptr(rows), n, ptr(starts), cap, nj, kind, c['q'], c['r_floor'], c['cov_scale'], c['v0'],
-            c['gate'], ptr(smoothed), ptr(poses_out))
-        return dict(track_index=track_index, track_id=track_id, cost=cost, rows=rows, starts=starts, n_new=n_new, n_dropped=n_dropped,
-                    state=state, ids=ids, next_id=int(next_id[0]), working=ws, smoothed_state=smoothed)
-    return run
+    """associate_tracks.hip's walk, the function its kernels run, compiled for the host and run by one thread under the greedy
+    rule without ray rows (tests/assoc_host.py); the dict it returns carries `smoothed_state`, what the smoothing kernel's code
+    leaves in the table's state on the CSR the walk wrote."""
+    return compile_walk(tmp_path_factory.mktemp('host_follow_tracks'), 'host_follow_tracks')[1]
 
 
 @pytest.mark.parametrize('name', list(CASES))

@@ -11,12 +11,13 @@ import numpy as np
 import pytest
 
 from metro_pose3d_amd import ModelSpec, _lib, frames as FR, heads as MH
+from tests import assign_tracks_ref as AR
 from tests import follow_tracks_ref as FT
 from tests import single_view_ref as SV
 from tests import track_smoothing_ref as TS
 from tests import triangulation_ref as TR
 from tests import world_follow_ref as WR
-from tests.helpers import compile_for_host
+from tests.assoc_host import NO_RAY_ROW_CASES, assert_ray_walk_is_the_plain_walk, compile_walk, ptr, without_ray_rows
 from tests.test_world_follow import _exact_rays
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,11 +30,11 @@ RULES = ('greedy', 'optimal')
 @pytest.fixture(scope='module')
 def host(tmp_path_factory):
     """The per-thread code of the three launches compiled for the host and run by one thread: person_steps_labels_kernel's three
-    steps, person_ray per (person, joint), and the steps of associate_tracks_rays_kernel in its order (the workgroup's LDS on
-    the heap); smooth_tracks.hip's per-joint function for the state the smoothing launch leaves on what the walk wrote."""
+    steps, person_ray per (person, joint), and associate_tracks.hip's walk with ray rows, the function its kernels run
+    (tests/assoc_host.py, which also brings smooth_tracks.hip's per-joint function for the state the smoothing launch leaves on
+    what the walk wrote)."""
     tmp = tmp_path_factory.mktemp('host_single_view')
-    dll = compile_for_host(tmp, 'host_single_view', ['world_tracks.hip', 'person_rays.hip', 'associate_tracks.hip', 'smooth_tracks.hip'], '''
-#include <memory>
+    dll, associate = compile_walk(tmp, 'host_single_view', ['world_tracks.hip', 'person_rays.hip'], '''
 #include <vector>
 extern "C" void host_person_steps_labels(const int* person_index, const int* n_persons, int n, const int* box_step, int n_boxes,
                                          const double* step_times, int n_steps, int* person_step, double* person_times,
@@ -54,93 +55,12 @@ extern "C" void host_person_rays(const float* coords01, const float* cov01, cons
                                                                  n_views, rays);
     for (int idx = 0; idx < n * spec->n_joints_out; ++idx) metro::person_ray(a, idx);
 }
-extern "C" void host_associate_tracks_rays(float* poses, float* cov, const double* times, int n, const int* step_rows, int n_step_rows,
-                                           const int* step_starts, int n_steps, int n_out, double q, double r_floor, double cov_scale,
-                                           double v0, double gate, float max_cost, double clip, int min_joints, double max_age,
-                                           double* state, int n_tracks, int* ids, int* next_id, double* ws, int* track_index,
-                                           int* track_id, float* cost_out, int* rows_out, int* starts_out, int* n_new, int* n_dropped,
-                                           int assignment, const int* single_box, const double* rays, double depth_sigma,
-                                           float* ray_depth, int* n_unplaced) {
-    using namespace metro;
-    const AssocArgs base = make_assoc_args(poses, cov, times, n, step_rows, n_step_rows, step_starts, n_steps, n_out,
-                                           METRO_SMOOTH_COVARIANCE, q, r_floor, cov_scale, v0, gate, max_cost, clip, min_joints, max_age,
-                                           state, n_tracks, ids, next_id, ws, track_index, track_id, cost_out, rows_out, starts_out,
-                                           n_new, n_dropped);
-    const AssocRayArgs a = make_assoc_ray_args(base, poses, cov, single_box, rays, depth_sigma, ray_depth, n_unplaced);
-    std::unique_ptr<AssocLds> lds(new AssocLds);
-    std::unique_ptr<AssocOptLds> opt(new AssocOptLds);
-    std::unique_ptr<AssocRayLds> rl(new AssocRayLds);
-    AssocLds& l = *lds;
-    AssocOptLds& o = *opt;
-    AssocRayLds& r = *rl;
-    assoc_begin(a, l, 0, 1);
-    assoc_ray_begin(a, r, 0, 1);
-    double t_first = 0.0;
-    const bool have_first = assoc_first_time(a, t_first);
-    assoc_retire(a, l, have_first, t_first, 0, 1);
-    for (int s = 0; s < a.n_steps; ++s) {
-        int lo, m;
-        double t_step;
-        assoc_step_range(a, s, lo, m);
-        if (!assoc_step_time(a, lo, m, t_step)) continue;
-        assoc_step_boxes(a, l, lo, m, 0, 1);
-        assoc_ray_step_boxes(a, l, r, m, 0, 1);
-        assoc_costs(a, l, m, t_step, 0, 1);
-        assoc_ray_costs(a, l, r, m, t_step, 0, 1);
-        if (assignment) {
-            assoc_opt_begin(a, o, m, 0, 1);
-            for (int k = 0; k < m; ++k) {
-                AssocPath p = assoc_opt_root(a, o, k, 0, 1);
-                for (int visit = 0; visit <= a.n_tracks && p.end == -2; ++visit) {
-                    const AssocCandD best = assoc_opt_relax(a, l, o, p, 0, 1);
-                    assoc_opt_advance(a, o, p, best);
-                }
-                assoc_opt_duals(a, o, p, k, 0, 1);
-                assoc_opt_augment(a, o, p, k, 0);
-            }
-            assoc_opt_pairs(a, l, o, m, 0, 1);
-        } else {
-            const int rounds = a.n_tracks < m ? a.n_tracks : m;
-            for (int round = 0; round < rounds; ++round) {
-                const AssocCand best = assoc_scan(l, a.n_tracks, m, 0, 1);
-                if (!(best.v < a.max_cost)) break;
-                assoc_strike(l, a.n_tracks, m, best, 0, 1);
-            }
-        }
-        assoc_births(a, l, m, 0, 1);
-        assoc_apply(a, l, m, 0, 1);
-        assoc_ray_count(l, r, m, 0);
-        assoc_ray_place(a, l, r, m, t_step, 0, 1);
-        assoc_filter(a, l, m, 0, 1);
-    }
-    assoc_starts(a, l, 0, 1);
-    for (int s = 0; s < a.n_steps; ++s) {
-        int lo, m;
-        assoc_step_range(a, s, lo, m);
-        if (m == 0) continue;
-        assoc_group_step(a, l, lo, m, 0, 1);
-    }
-    assoc_finish(a, l, 0, 1);
-    assoc_ray_finish(a, r, 0);
-}
-extern "C" void host_filter_tracks(const float* poses, const float* cov, const double* times, int n, const int* rows, int n_rows,
-                                   const int* starts, int n_tracks, int n_out, int measurement, double q, double r_floor,
-                                   double cov_scale, double v0, double gate, double* state, float* poses_out, unsigned char* used) {
-    const metro::SmoothArgs a = metro::make_smooth_args(poses, cov, times, n, rows, n_rows, starts, n_tracks, n_out, METRO_SMOOTH_FILTER,
-                                                        measurement, q, r_floor, cov_scale, v0, gate, state, nullptr, poses_out, nullptr,
-                                                        nullptr, used);
-    for (int idx = 0; idx < n_tracks * n_out; ++idx) metro::smooth_track_joint(a, idx);
-}
 ''')
     P = C.c_void_p
-    stp, ray, walk, flt = dll.host_person_steps_labels, dll.host_person_rays, dll.host_associate_tracks_rays, dll.host_filter_tracks
-    stp.restype = ray.restype = walk.restype = flt.restype = None
+    stp, ray = dll.host_person_steps_labels, dll.host_person_rays
+    stp.restype = ray.restype = None
     stp.argtypes = [P, P, C.c_int, P, C.c_int, P, C.c_int, P, P, P, P, P]
     ray.argtypes = [P, P, P, C.c_int, C.POINTER(_lib.MetroSpec), P, C.c_int, P, C.c_int, C.c_int, P]
-    walk.argtypes = ([P, P, P, C.c_int, P, C.c_int, P, C.c_int, C.c_int] + [C.c_double] * 5 + [C.c_float, C.c_double, C.c_int, C.c_double,
-                     P, C.c_int] + [P] * 10 + [C.c_int, P, P, C.c_double, P, P])
-    flt.argtypes = [P, P, P, C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int] + [C.c_double] * 5 + [P, P, P]
-    ptr = lambda a: P(a.ctypes.data if a is not None else 0)
 
     def labels(c):
         n, n_steps = c['n'], len(c['step_times'])
@@ -163,32 +83,7 @@ extern "C" void host_filter_tracks(const float* poses, const float* cov, const d
             ptr(single), n, c['n_views'], ptr(out))
         return out
 
-    def associate(c, assignment='greedy'):
-        """-> the dict the comparison reads, outputs pre-filled with the sentinel, plus `smoothed_state` and `used` (what the
-        smoothing kernel's code leaves on the CSR and the arrays the walk wrote)."""
-        poses = np.array(c['poses'], np.float32)
-        n, nj = poses.shape[:2]
-        cov = np.array(c['cov'], np.float32).reshape(n, nj, 9)
-        times = np.ascontiguousarray(c['times'], np.float64)
-        step_rows, step_starts = np.ascontiguousarray(c['step_rows'], np.int32), np.ascontiguousarray(c['step_starts'], np.int32)
-        state, ids, next_id = np.array(c['state'], np.float64), np.array(c['ids'], np.int32), np.array(c['next_id'], np.int32).reshape(1)
-        single, ray_in = np.ascontiguousarray(c['single_box'], np.int32), np.ascontiguousarray(c['rays'], np.float64)
-        cap = len(ids)
-        ws = np.full((cap, nj, 28), float(FT.SENTINEL))
-        ints = lambda k: np.full(k, FT.SENTINEL, np.int32)
-        track_index, track_id, rows, starts, n_new, n_dropped, n_unplaced = ints(n), ints(n), ints(n), ints(cap + 1), ints(1), ints(1), ints(1)
-        cost, depth = np.full(n, float(FT.SENTINEL), np.float32), np.full((n, nj), float(FT.SENTINEL), np.float32)
-        walk(ptr(poses), ptr(cov), ptr(times), n, ptr(step_rows), len(step_rows), ptr(step_starts), len(step_starts) - 1, nj, c['q'],
-             c['r_floor'], c['cov_scale'], c['v0'], c['gate'], c['max_cost'], c['clip'], c['min_joints'], c['max_age'], ptr(state), cap,
-             ptr(ids), ptr(next_id), ptr(ws), ptr(track_index), ptr(track_id), ptr(cost), ptr(rows), ptr(starts), ptr(n_new),
-             ptr(n_dropped), int(assignment == 'optimal'), ptr(single), ptr(ray_in), float(c['depth_sigma']), ptr(depth), ptr(n_unplaced))
-        smoothed, poses_out, used = state.copy(), np.empty((n, nj, 3), np.float32), np.zeros((n, nj), np.uint8)
-        flt(ptr(poses), ptr(cov), ptr(times), n, ptr(rows), n, ptr(starts), cap, nj, _lib.METRO_SMOOTH_COVARIANCE, c['q'], c['r_floor'],
-            c['cov_scale'], c['v0'], c['gate'], ptr(smoothed), ptr(poses_out), ptr(used))
-        return dict(track_index=track_index, track_id=track_id, cost=cost, rows=rows, starts=starts, n_new=n_new, n_dropped=n_dropped,
-                    n_unplaced=n_unplaced, state=state, ids=ids, next_id=int(next_id[0]), working=ws, poses=poses, cov=cov,
-                    ray_depth=depth, smoothed_state=smoothed, used=used)
-    return labels, rays, associate
+    return labels, rays, lambda c, assignment='greedy': associate(c, assignment, ray_rows=True), associate
 
 
 # ---- the person steps from labels ---------------------------------------------------------------------------------------------
@@ -423,6 +318,13 @@ def test_walk_on_the_host_matches_the_restatement(host, name, assignment):
         assert got['n_new'][0] == 1 and placed.sum() == 17 and got['n_unplaced'][0] == 0
     elif name == 'T128-m128-j1-full-table':
         assert (got['ids'] >= 0).all() and got['n_unplaced'][0] == 0 and placed.sum() == 64
+
+
+@pytest.mark.parametrize('assignment', RULES)
+@pytest.mark.parametrize('name', NO_RAY_ROW_CASES)
+def test_walk_with_ray_rows_switched_on_and_no_ray_row_is_the_plain_walk(host, name, assignment):
+    c = AR.CASES[name]()
+    assert_ray_walk_is_the_plain_walk(host[2](without_ray_rows(c), assignment), host[3](c, assignment), c)
 
 
 # ---- what the feature is for ---------------------------------------------------------------------------------------------------
