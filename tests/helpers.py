@@ -153,6 +153,30 @@ def ref_conv_desc(d, x, w_ok, bias, pro=None, pro_round=np.float16, res=None):
     return y, a
 
 
+DYADIC_SCALES = (-1.5, -1.0, -0.5, 0.0, 0.5, 1.0, 1.5)
+
+
+def dyadic_conv_operands(rng, d, lim=8):
+    """Operands of MetroConvDesc `d` on which ANY summation order of a conv kernel with fp32 (or wider) accumulators gives the
+    exact result: inputs and weights integers / 8 in [-lim / 8, lim / 8], bias and residual integers / 64 in [-1, 1], prologue
+    scales from DYADIC_SCALES (negative and zero folded BN scales included), shifts integers / 8 in [-1, 1] -- every product is
+    a multiple of 2^-6 (2^-8 behind a prologue), so every partial sum is exact while it stays below 2^24 of that unit
+    (exact_sum_condition).  fp64 arrays (x, w, bias, pro or None, res or None); every value is exact in fp16 too."""
+    ints = lambda shape, m, q: rng.integers(-m, m + 1, shape).astype(np.float64) / q
+    x = ints((d.n, d.h_in, d.w_in, d.c_in), lim, 8)
+    w = ints((d.c_out, d.kh, d.kw, d.c_in), lim, 8)
+    b = ints(d.c_out, 64, 64)
+    pro = (rng.choice(DYADIC_SCALES, d.c_in), ints(d.c_in, 8, 8)) if d.has_prologue else None
+    res = ints((d.n, d.res_h, d.res_w, d.c_out), 64, 64) if d.has_residual else None
+    return x, w, b, pro, res
+
+
+def exact_sum_condition(a, prologue):
+    """Whether every partial sum of every output element is exact in fp32 on dyadic_conv_operands: a * 2^f < 2^24 for the
+    condition sums `a` of ref_conv_desc, f = the fractional bits of a product (6; 8 behind a prologue)."""
+    return bool((np.asarray(a) * 2.0 ** (8 if prologue else 6) < 2.0 ** 24).all())
+
+
 def run_conv_f16(lib, dev, d, x, w, bias, pro=None, res=None):
     """x, w, pro, res: numpy (cast to fp16); bias fp32.  Returns numpy of d.out_dtype."""
     tx = torch.from_numpy(np.ascontiguousarray(x.astype(np.float16))).to(dev)

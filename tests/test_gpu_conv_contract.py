@@ -204,7 +204,8 @@ def _input_ptr(t, off):
 
 
 def _check(got, y, a, d, u, out_round, res_abs=None, what=''):
-    """|got - y| <= out_round |y| (+ out_round / 2 |res|) + C_SUM u K a + floor, element by element (module docstring)."""
+    """|got - y| <= out_round |y| (+ out_round / 2 |res|) + C_SUM u K a + floor, element by element (module docstring).
+    Returns the worst |got - y| / bound (<= 1)."""
     got = np.asarray(got, np.float64)
     assert np.isfinite(got).all(), f'{what}: {int((~np.isfinite(got)).sum())} elements not written (or not finite)'
     k = d.kh * d.kw * d.c_in + 1
@@ -216,6 +217,7 @@ def _check(got, y, a, d, u, out_round, res_abs=None, what=''):
     worst = np.unravel_index(np.argmax(err / bound), err.shape)
     assert (err <= bound).all(), (f'{what}: {int((err > bound).sum())} of {err.size} elements out of bound; worst at {worst}: '
                                   f'got {got[worst]!r} want {y[worst]!r} bound {bound[worst]:.3g} (a {a[worst]:.3g})')
+    return float((err / bound).max())
 
 
 def _sampled(case, d, arrs):

@@ -537,9 +537,11 @@ def test_estimate_pose_shards_across_ranks(cuda, tmp_path, n):
 
 def test_f64_mode_is_shard_invariant(cuda, tmp_path):
     """"results must be bit-identical to the 1-GPU run".  In the f16 throughput mode that holds below the dispatch
-    thresholds only (tile shapes follow the crops per call); the PARITY mode runs one kernel configuration whatever the batch, so
-    the same 300 crops give the same bits as one call (chunks of 256 + 44), as five calls of 60, and as two ranks of 150 under
-    a process group (gloo on one GPU here; RCCL on a node)."""
+    thresholds only (tile shapes follow the crops per call).  In the PARITY mode the tile shape follows the batch too
+    (conv_igemm_f64acc: 64- or 128-cout tiles by the tile count, tests/test_parity_coverage.py), but not the order in which an
+    output element's products are summed (k ascending in groups of four on either tile), so the same 300 crops give the same
+    bits as one call (chunks of 256 + 44), as five calls of 60, and as two ranks of 150 under a process group (gloo on one GPU
+    here; RCCL on a node)."""
     import socket
     import torch.multiprocessing as mp
     from metro_pose3d_amd import inference as INF, save_model

@@ -396,7 +396,9 @@ def test_conv_f64acc(lib, cuda, case, variant, store):
 def test_conv_f32m(lib, cuda, case, variant):
     """The fp32-matrix-core kernel of the F32M mode (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulation in ascending
     k) on every conv shape, against fp64 on the same fp32 operands: what is left is fp32 accumulation, <= sqrt(K) ulps of the
-    layer maximum (bar 2e-5 relative: K <= 4608)."""
+    layer maximum (bar 2e-5 relative: K <= 4608).  That bar cannot see a dropped tap of a long K loop (one tap is ~1/K of an
+    element), so the cases with K >= 1152 also run dyadic operands (helpers.dyadic_conv_operands: every partial sum exact in
+    fp32, which is asserted from the reference's condition sums) and must give the exact result."""
     name, n, h_in, c_in, c_out, k, stride, dil, pad, h_out = case
     if variant == 'prologue' and (k != 1 or pad > 0):
         pytest.skip('prologue is defined for un-padded 1x1 convs only')
@@ -421,6 +423,20 @@ def test_conv_f32m(lib, cuda, case, variant):
     ref = H.ref_conv_nhwc(x, w, b, stride, dil, pad, h_out, pro=pro, relu=variant == 'relu_residual', res=res).numpy()
     assert np.isfinite(got).all()
     assert np.abs(got - ref).max() <= 2e-5 * np.abs(ref).max(), (np.abs(got - ref).max(), np.abs(ref).max())
+    if k * k * c_in >= 1152:
+        x, w, b, pro, res = H.dyadic_conv_operands(rng, d)
+        y, a = H.ref_conv_desc(d, x, w, b, pro=pro, pro_round=None, res=res)
+        assert H.exact_sum_condition(a, pro is not None)
+        t = [_dev(x, cuda, np.float32), _dev(w, cuda, np.float32), _dev(b, cuda, np.float32)]
+        ts = _dev(pro[0], cuda, np.float32) if pro else None
+        tsh = _dev(pro[1], cuda, np.float32) if pro else None
+        tr = _dev(res, cuda, np.float32) if res is not None else None
+        out.fill_(float('nan'))
+        check(lib.metro_conv_f32m(C.byref(d), H.ptr(t[0]), H.ptr(t[1]), H.ptr(t[2]), H.ptr(ts), H.ptr(tsh), H.ptr(tr), H.ptr(out), None),
+              'metro_conv_f32m (dyadic operands)')
+        torch.cuda.synchronize()
+        got = out.cpu().double().numpy()
+        assert np.isfinite(got).all() and np.array_equal(got, y), f'{int((got != y).sum())} of {y.size} elements differ from the exact result'
 
 
 def test_conv_f32m_stem_3ch(lib, cuda):

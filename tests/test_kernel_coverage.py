@@ -123,11 +123,11 @@ def dispatch_table(spec, n):
 class DryRun:
     """The dispatch of one spec at every batch up to max_batch from ONE plan (max_batch sizes the workspace slots and nothing else
     of a plan; test_dispatch_closure holds that against dispatch_table for every configuration).  kernels(n, layers): the ids of
-    the given layer indices (all by default)."""
+    the given layer indices (all by default).  `precision`: the plan's mode (tests/test_parity_coverage.py walks the parity modes)."""
 
-    def __init__(self, spec, max_batch=256):
+    def __init__(self, spec, max_batch=256, precision='f16'):
         self.spec = spec
-        self.eng = Engine(spec, None, 'f16', max_batch=max_batch)
+        self.eng = Engine(spec, None, precision, max_batch=max_batch)
         self.infos = self.eng.layer_infos()
         self.names = [li.name.decode() for li in self.infos]
         self.keys = [shape_key(li) for li in self.infos]
