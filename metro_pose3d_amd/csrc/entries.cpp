@@ -60,7 +60,16 @@ int validate_conv_desc(const MetroConvDesc* d) {
         METRO_CHECK_ARG((d->h_out - 1) * d->res_stride + d->res_offset < d->res_h &&
                             (d->w_out - 1) * d->res_stride + d->res_offset < d->res_w,
                         "conv desc: residual gather out of bounds");
+        METRO_CHECK_ARG((long)d->n * d->res_h * d->res_w < (1L << 31), "conv desc: too many residual pixels");
     }
+    return METRO_OK;
+}
+
+// The conv, stem and head kernels hold PIXEL indices (image x row x column) in int and widen to size_t before the channel count
+// goes in: a call fits while its pixel counts fit int32 -- element and byte counts may pass 2^32 (tests/test_gpu_large_address.py).
+// The head and stem grids put the image on a grid axis of at most 65 535 blocks.
+static int check_image_pixels(const char* who, int32_t n, int32_t side) {
+    METRO_CHECK_ARG(side > 0 && (int64_t)n * side * side <= INT32_MAX, "%s: %d images of side %d overflow the int32 pixel index", who, n, side);
     return METRO_OK;
 }
 
@@ -213,6 +222,7 @@ int metro_stem_pool_f16(const void* d_prepped, const void* d_w, const float* d_b
                         int32_t side, void* stream) {
     METRO_CHECK_ARG(d_prepped && d_w && d_bias && d_out, "stem_pool_f16: NULL tensor pointer");
     METRO_CHECK_ARG(n > 0, "stem_pool_f16: n = %d", n);
+    if (const int st = check_image_pixels("stem_pool_f16", n, side)) return st;
     METRO_CHECK_ARG(stem_pool_f16_supported(side, 64), "stem_pool_f16: side %d must be a multiple of 32 (and METRO_STEM_POOL != 0)", side);
     return launch_stem_pool_f16(d_prepped, d_w, d_bias, d_out, n, side, static_cast<hipStream_t>(stream));
 }
@@ -221,6 +231,7 @@ int metro_stem_pool_f32in(const float* d_images, const void* d_w, const float* d
                           int32_t side, void* stream) {
     METRO_CHECK_ARG(d_images && d_w && d_bias && d_out, "stem_pool_f32in: NULL tensor pointer");
     METRO_CHECK_ARG(n > 0, "stem_pool_f32in: n = %d", n);
+    if (const int st = check_image_pixels("stem_pool_f32in", n, side)) return st;
     METRO_CHECK_ARG(stem_pool_f32in_supported(side, 64), "stem_pool_f32in: side %d must be a multiple of 32 (and METRO_STEM_POOL / METRO_STEM_RAW != 0)", side);
     return launch_stem_pool_f32in(d_images, d_w, d_bias, d_out, n, side, static_cast<hipStream_t>(stream));
 }
@@ -229,6 +240,7 @@ int metro_stem_pool_u8in(const uint8_t* d_images, const void* d_w, const float* 
                          int32_t side, void* stream) {
     METRO_CHECK_ARG(d_images && d_w && d_bias && d_out, "stem_pool_u8in: NULL tensor pointer");
     METRO_CHECK_ARG(n > 0, "stem_pool_u8in: n = %d", n);
+    if (const int st = check_image_pixels("stem_pool_u8in", n, side)) return st;
     METRO_CHECK_ARG(stem_pool_f32in_supported(side, 64), "stem_pool_u8in: side %d must be a multiple of 32 (and METRO_STEM_POOL / METRO_STEM_RAW != 0)", side);
     return launch_stem_pool_u8in(d_images, d_w, d_bias, d_out, n, side, static_cast<hipStream_t>(stream));
 }
@@ -402,6 +414,8 @@ int metro_head_f16(const void* d_x, const void* d_w, const float* d_bias, const 
                         spec->n_joints_out <= METRO_MAX_JOINTS, "head_f16: joint counts out of range");
     METRO_CHECK_ARG((spec->depth * spec->n_joints_head) % 4 == 0, "head_f16: depth*n_joints_head must be a multiple of 4");
     const int side = spec->proc_side / spec->stride;
+    if (const int st = check_image_pixels("head_f16", n, side)) return st;
+    METRO_CHECK_ARG(n <= 65535, "head_f16: %d images exceed the grid's image axis (65535)", n);
     const SoftArgmaxArgs a = make_softargmax_args(*spec, n);
     int st = launch_head_f16(d_x, d_w, d_bias, d_pro_scale, d_pro_shift, n, c_in, spec->depth * spec->n_joints_head,
                              spec->n_joints_head, spec->depth, side, static_cast<float*>(d_partials), d_logits_out,
@@ -424,6 +438,8 @@ int metro_head_f16_moments(const void* d_x, const void* d_w, const float* d_bias
                         spec->n_joints_out <= METRO_MAX_JOINTS, "head_f16_moments: joint counts out of range");
     METRO_CHECK_ARG((spec->depth * spec->n_joints_head) % 4 == 0, "head_f16_moments: depth*n_joints_head must be a multiple of 4");
     const int side = spec->proc_side / spec->stride;
+    if (const int st = check_image_pixels("head_f16_moments", n, side)) return st;
+    METRO_CHECK_ARG(n <= 65535, "head_f16_moments: %d images exceed the grid's image axis (65535)", n);
     const SoftArgmaxArgs a = make_softargmax_args(*spec, n);
     MomentsOut mo;
     mo.scratch = d_moments_scratch; mo.cov01 = d_cov01_out; mo.peak = d_peak_out;

@@ -106,7 +106,8 @@ __host__ __device__ __forceinline__ int xcd_block_lid(int block, int nblk) {
 // A kernel file that ships write-through defines METRO_WT_STORES 1 above its includes (unless the command line set it:
 // tools/build_variant.sh <name> "-DMETRO_WT_STORES=0|1" <file>.hip flips one family); NOTES_dead_ends.md has the A/B per family.
 // Inline asm, not __builtin_amdgcn_raw_buffer_store_b128(.., aux 16), which hipcc would count: the builtin wants a wave-uniform
-// descriptor and a 32-bit offset, the 17 call sites hold per-lane 64-bit pointers into tensors of up to 537 MB, and a per-lane
+// descriptor and a 32-bit offset, the 17 call sites hold per-lane 64-bit pointers into tensors of up to 16 GiB (block4's output
+// at stride 4, crop side 512, 256 crops: 2^33 fp16 elements -- no 32-bit offset reaches across them), and a per-lane
 // descriptor costs a waterfall loop.  hipcc does not model the asm: `s_nop 1` keeps the data registers from being rewritten while
 // the store reads them, and the store is absent from the compiler's vmcnt bookkeeping -- compiler-placed waits count fewer
 // younger operations than there are (longer waits, never shorter); A CALLER WITH A HAND-COUNTED WAIT COUNTS THESE STORES ITSELF

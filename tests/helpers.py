@@ -302,24 +302,60 @@ def crop_assignment(n, p, seed):
     return a
 
 
-def lay_out_twins(base, assign):
-    """The batch base[assign]: [n, ...] from the p base images, a device tensor or a numpy array like `base`."""
+TWIN_CHUNK_ELEMENTS = 2 ** 28  # lay_out_twins / assert_twins gather and compare at most this many elements at a time (whole images)
+
+
+def _image_groups(n, per_image, chunk):
+    """(start, stop) runs of whole images with at most `chunk` elements each (one image where an image alone has more)."""
+    step = max(1, chunk // max(1, per_image))
+    return [(i, min(n, i + step)) for i in range(0, n, step)]
+
+
+def lay_out_twins(base, assign, chunk=TWIN_CHUNK_ELEMENTS):
+    """The batch base[assign]: [n, ...] from the p base images, a device tensor or a numpy array like `base`.  A device batch of
+    more than `chunk` elements is gathered in groups of whole images: no single gather spans 2^31 elements."""
     if isinstance(base, np.ndarray):
         return np.ascontiguousarray(base[assign])
-    return base[torch.as_tensor(assign, device=base.device)].contiguous()
+    idx = torch.as_tensor(assign, device=base.device)
+    per = base[0].numel()
+    if len(assign) * per <= chunk:
+        return base[idx].contiguous()
+    out = torch.empty((len(assign),) + tuple(base.shape[1:]), dtype=base.dtype, device=base.device)
+    for i, j in _image_groups(len(assign), per, chunk):
+        out[i:j] = base[idx[i:j]]
+    return out
 
 
-def assert_twins(out, assign, p, what):
-    """Every position of `out` [n, ...] carries the bits of its base image's first occurrence: out == out[:p][assign], one
-    gather on out's device (on the bit patterns of float tensors: NaN equals NaN)."""
+def assert_twins(out, assign, p, what, chunk=TWIN_CHUNK_ELEMENTS):
+    """Every position of `out` [n, ...] carries the bits of its base image's first occurrence: out == out[:p][assign], gathered
+    on out's device (on the bit patterns of float tensors: NaN equals NaN).  A tensor of more than `chunk` elements is gathered
+    and compared in groups of whole images -- the same comparison of every element and the same message, the first position that
+    differs -- so neither the copy nor the compare spans 2^31 elements (tensors beyond 4 GiB: tests/test_gpu_large_address.py)."""
     assert out.shape[0] == len(assign), (what, out.shape, len(assign))
     if out.is_floating_point():
         out = out.contiguous().view({2: torch.int16, 4: torch.int32, 8: torch.int64}[out.element_size()])
-    want = out[:p][torch.as_tensor(assign, device=out.device)]
-    if torch.equal(out, want):
-        return
-    i = int((out != want).reshape(len(assign), -1).any(dim=1).nonzero()[0])
-    raise AssertionError(f'{what}: position {i} of {len(assign)} differs from its twin, position {int(assign[i])} (base image {int(assign[i])})')
+    idx = torch.as_tensor(assign, device=out.device)
+    for lo, hi in _image_groups(len(assign), out[0].numel(), max(chunk, 1)):
+        part = out[lo:hi]
+        want = out[:p][idx[lo:hi]]
+        if torch.equal(part, want):
+            continue
+        i = lo + int((part != want).reshape(hi - lo, -1).any(dim=1).nonzero()[0])
+        raise AssertionError(f'{what}: position {i} of {len(assign)} differs from its twin, position {int(assign[i])} (base image {int(assign[i])})')
+
+
+def wrap_assignment(n, p, seed, wraps):
+    """crop_assignment(n, p, seed') with the seed stepped until, for every (first, distance) of `wraps`, some position
+    i >= first holds a different base image than position i - distance.  `first` is the first image that lies wholly beyond an
+    address boundary (2^31 or 2^32 bytes, 2^31 elements), `distance` the boundary in images: an access whose address wraps at the
+    boundary lands `distance` images lower, on ANOTHER image -- a wrapped load reads the wrong image, a wrapped store leaves NaN
+    above or overwrites a different image below.  crop_assignment itself promises only that some position differs per shift,
+    not one beyond `first`.  -> (assignment, seed used)."""
+    for step in range(1000):
+        a = crop_assignment(n, p, seed + step)
+        if all(d <= first < n and (a[first:] != a[first - d:n - d]).any() for first, d in wraps):
+            return a, seed + step
+    raise AssertionError(f'wrap_assignment({n}, {p}, {seed}, {wraps}): no seed gives every wrap a differing pair')
 
 
 def oracle_spec(spec):

@@ -126,3 +126,44 @@ def test_the_periodic_layout_passes_what_the_assignment_catches(n):
     a = H.crop_assignment(n, 4, 0)
     out = _output(a, 4)
     assert _caught(torch.roll(out, 4, 0), a, 4) and _caught(torch.roll(out, -4, 0), a, 4) and _caught(_swap_groups(out, 4, 0), a, 4)
+
+
+@pytest.mark.parametrize('chunk', [1, 5, 12, 35, 64])
+def test_the_chunked_twin_check_is_the_whole_one(chunk):
+    """Tensors beyond 2^31 elements are gathered and compared in groups of whole images (helpers.TWIN_CHUNK_ELEMENTS): with the
+    chunk forced down to a few elements (5 per image here) the layout is the same tensor, a right output passes, and every planted
+    swap or rotation is caught with the message of the one-piece check -- the first position that differs."""
+    n, p = 49, 4
+    a = H.crop_assignment(n, p, 5)
+    base = torch.from_numpy(np.random.default_rng(1).standard_normal((p, 5)).astype(np.float32))
+    assert torch.equal(H.lay_out_twins(base, a, chunk=chunk), H.lay_out_twins(base, a)) and H.lay_out_twins(base, a, chunk=chunk).is_contiguous()
+    out = _output(a, p)
+    H.assert_twins(out, a, p, 'as it should be', chunk=chunk)
+    planted = [torch.roll(out, s, 0) for s in (1, -1, 4, 16)] + [_swap_groups(out, g, k) for g in H.TWIN_GROUPS for k in (0, n // g - 2)]
+    last = out.clone()
+    last[n - 1, 4] += 1.0                  # one element of the last image
+    for bad in planted + [last]:
+        with pytest.raises(AssertionError) as whole:
+            H.assert_twins(bad, a, p, 'layer x')
+        with pytest.raises(AssertionError) as parts:
+            H.assert_twins(bad, a, p, 'layer x', chunk=chunk)
+        assert str(parts.value) == str(whole.value)
+
+
+@pytest.mark.parametrize('n,p,wraps', [(68, 4, [(64, 64), (32, 32)]), (132, 2, [(128, 128)]), (256, 4, [(128, 128), (255, 255)]), (207, 4, [(203, 1)])])
+def test_wrap_assignment_puts_different_images_a_wrap_apart(n, p, wraps):
+    a, seed = H.wrap_assignment(n, p, 11, wraps)
+    assert np.array_equal(a, H.crop_assignment(n, p, seed)) and seed >= 11
+    for first, d in wraps:
+        assert any(a[i] != a[i - d] for i in range(first, n))
+    # a store that wraps at the boundary: the images beyond `first` land `d` lower and their own slots keep the NaN prefill
+    first, d = wraps[0]
+    out = _output(a, p).nan_to_num(3.0)
+    wrapped = out.clone()
+    wrapped[first - d:n - d] = out[first:]
+    wrapped[first:] = float('nan')
+    assert _caught(wrapped, a, p)
+    # a load that wraps: the images beyond `first` are computed from the images `d` lower
+    wrapped = out.clone()
+    wrapped[first:] = out[first - d:n - d]
+    assert _caught(wrapped, a, p)

@@ -385,6 +385,261 @@ def test_pair_closure():
                   for (kid, key), (spec, n, i) in sorted(missing.items(), key=lambda kv: (kv[0][0], kv[1][1])))
 
 
+# ---- operands beyond 2^31 / 2^32 bytes and beyond 2^31 elements ------------------------------------------------------------------
+# class -> (unit, boundary): an operand is in the class when its size in that unit is BEYOND the boundary (strictly: a tensor of
+# exactly 2^32 bytes has no byte whose offset needs bit 32)
+LARGE_CLASSES = {'A': ('bytes', 2 ** 31), 'B': ('bytes', 2 ** 32), 'E': ('elements', 2 ** 31)}
+LARGE_ROLES = ('input', 'output', 'second output', 'residual', 'sub-sampled output', 'fp32 logits')
+LARGE_IMAGES_BEYOND = 4         # whole images a case puts beyond the boundary of every triple it is there for (fewer only at n = 256)
+DTYPE_BYTES = {_lib.METRO_F16: 2, _lib.METRO_F32: 4, _lib.METRO_F64: 8}
+
+
+def large_kernel_names(kid):
+    """The kernels of an id for the large-operand closure: kernel_of (tests/test_gpu_nonfinite_kernels.py) of every part of an
+    `a & b` id, with the form suffix behind the template arguments (+pair, +subgrid, +f32out, +res) kept."""
+    from tests.test_gpu_nonfinite_kernels import kernel_of
+    return sorted({kernel_of(part) + (part[part.rindex('>') + 1:] if '>' in part else '') for part in kid.split(' & ')})
+
+
+def operand_roles(infos, i, kid):
+    """{role: (elements per image, bytes per element)} of the tensors the launch of layer i touches that grow with the call size
+    (the roles of LARGE_ROLES; weights, the 64-channel side inputs of block1's rebuilt shortcuts, soft-argmax records and poses do
+    not reach 2^31 bytes at 256 crops).  The element size comes from the layer's dtypes: the stem reads the fp32 image, every other
+    layer what the layer in front stores (the plan's activation type; the two-launch soft-argmax the logits' type)."""
+    li = infos[i]
+    name = li.name.decode()
+    act = DTYPE_BYTES[infos[0].out_dtype]
+    out_b = DTYPE_BYTES[li.out_dtype]
+    px = li.h_out * li.w_out
+    if li.kind == _lib.LAYER_SOFTARGMAX:       # the finalize launch behind the one-launch head reads records, not logits
+        return {'input': (li.h_in * li.w_in * li.c_in, DTYPE_BYTES[infos[i - 1].out_dtype])} if 'softargmax_partial' in kid else {}
+    if name == 'conv1+pool1':                   # (h_in, c_in of this layer describe the padded slab; the image is 4 h_out wide, 3 channels)
+        return {'input': (16 * px * 3, 4), 'output': (px * li.c_out, out_b)}
+    roles = {'input': (li.h_in * li.w_in * li.c_in, 4 if name == 'conv1' else act)}
+    if name == 'logits' and kid.startswith('head_f16'):
+        roles['fp32 logits'] = (px * li.c_out, 4)          # what the single launch stores next to the poses (metro_forward keeps them on chip)
+        return roles
+    if li.kind != _lib.LAYER_CONV:
+        roles['output'] = (px * li.c_in if li.kind == _lib.LAYER_POOL else px * li.c_out, out_b)
+        return roles
+    if not li.fused_flags & _lib.FUSED_OUT_ON_CHIP:
+        roles['output'] = (px * li.c_out, out_b)
+    if li.out2_channels > 0 and not li.fused_flags & _lib.FUSED_CONV1_IN_FRONT:
+        roles['second output'] = (px * li.out2_channels, act)
+    if li.has_residual and not li.fused_flags & _lib.FUSED_REBUILT_SHORTCUT:
+        whole = li.res_stride == 1 or li.fused_flags & _lib.FUSED_COMPACT_SHORTCUT
+        roles['residual'] = ((px if whole else 4 * px) * li.c_out, out_b)
+    if li.out_sub_offset >= 0:
+        roles['sub-sampled output'] = (li.out_sub_side ** 2 * li.c_out, out_b)
+    return roles
+
+
+def images_beyond(n, per_image, bound):
+    """Whole images of a tensor of n images, per_image units each, that lie beyond `bound` units: image i does when i * per_image >= bound."""
+    return max(0, n - -(-bound // per_image))
+
+
+def large_triples(infos, i, kid, n):
+    """{(kernel, role, class): whole images beyond the class's boundary} of layer i at call size n; only operands IN the class."""
+    out = {}
+    for role, (elems, width) in operand_roles(infos, i, kid).items():
+        for cls, (unit, bound) in LARGE_CLASSES.items():
+            per = elems * width if unit == 'bytes' else elems
+            if n * per > bound:
+                for k in large_kernel_names(kid):
+                    out[(k, role, cls)] = images_beyond(n, per, bound)
+    return out
+
+
+_LARGE = {}
+
+
+def large_operand_scan(precision='f16'):
+    """[(multiply-accumulates, precision, spec, n, layer index, kernel id, {triple: images beyond})]: every (spec, n, layer) of the
+    supported grid (GRID_SIDES x GRID_ARCHS x GRID_STRIDES x GRID_DATASETS x GRID_BATCHES) with an operand beyond 2^31 bytes.
+    Operands grow with n: per spec the walk goes down from 256, asks only for the layers whose largest operand is beyond 2^31
+    bytes at that n, and stops at the first n with none (a spec whose plan has none at 256 costs one plan); the many19 and merged
+    specs are asked for their head layers only (test_dispatch_closure asserts that their backbones are h36m's)."""
+    if precision in _LARGE:
+        return _LARGE[precision]
+    found = []
+    for side in GRID_SIDES:
+        for arch in GRID_ARCHS:
+            for stride in GRID_STRIDES:
+                for ds in GRID_DATASETS:
+                    spec = ModelSpec(arch, stride, ds, proc_side=side)
+                    run = DryRun(spec, precision=precision)
+                    layers = range(0 if ds == GRID_DATASETS[0] else run.names.index('logits'), len(run.names))
+                    # the largest operand of a layer whatever kernel it gets (the head's fp32 logits, the two-launch soft-argmax's input)
+                    largest = {i: max(e * w for kid in ('', 'head_f16<', 'softargmax_partial<')
+                                      for e, w in operand_roles(run.infos, i, kid).values()) for i in layers}
+                    for n in reversed(GRID_BATCHES):
+                        ask = [i for i in layers if n * largest[i] > 2 ** 31]
+                        if not ask:
+                            break
+                        for i, kid in zip(ask, run.kernels(n, ask)):
+                            t = large_triples(run.infos, i, kid, n)
+                            if t:
+                                found.append((run.infos[i].flops_per_image / 2 * n, precision, spec, n, i, kid, t))
+    _LARGE[precision] = found
+    return found
+
+
+def large_universe(scan):
+    """Every triple the scan reaches."""
+    return {t for c in scan for t in c[6]}
+
+
+def _holds(n, images):
+    """Whether a launch at call size n holds a triple: LARGE_IMAGES_BEYOND whole images beyond the boundary, or the grid's largest call."""
+    return images >= LARGE_IMAGES_BEYOND or n == GRID_BATCHES[-1]
+
+
+def held_triples(n, triples):
+    return {t for t, images in triples.items() if _holds(n, images)}
+
+
+def large_address_cases(scan):
+    """The case list: [(precision, spec, n, layer index, kernel id, {triple: images beyond} the case is there for)].  For every
+    triple not yet held -- classes E, B, A in that order, one launch usually holds several roles and classes -- the (spec, n,
+    layer) with the fewest multiply-accumulates that holds it (fewest for a layer = its smallest n with LARGE_IMAGES_BEYOND images
+    beyond; ties: ResNet-50, the smaller stride and side); everything else that launch holds is then held.  A triple that no
+    point of the grid holds (its kernel leaves the layer before four images lie beyond) goes to the point with the most images
+    beyond."""
+    order = sorted(large_universe(scan), key=lambda t: ('EBA'.index(t[2]), t[0], t[1]))
+    cost = lambda c: (c[0], c[2].arch, c[2].stride, c[2].proc_side, c[2].dataset, c[1], c[3], c[4])
+    held, cases = set(), []
+    for t in order:
+        if t in held:
+            continue
+        at = [c for c in scan if t in c[6]]
+        good = [c for c in at if _holds(c[3], c[6][t])]
+        _, prec, spec, n, i, kid, triples = min(good, key=cost) if good else max(at, key=lambda c: (c[6][t], -c[0]))
+        mine = {u: k for u, k in triples.items() if (_holds(n, k) or u == t) and u not in held}
+        held.update(mine)
+        cases.append((prec, spec, n, i, kid, mine))
+    return cases
+
+
+# Base images of a large-address case: BASE_IMAGES while the fp64 reference of that many images stays within twice the heaviest
+# reference of the single launches above (block4's 3x3 on 64 x 64 maps, four images: 38.7 G multiply-accumulates), else 2
+LARGE_REFERENCE_MACS = 2 * 38.7e9
+
+
+def large_base_images(li):
+    return BASE_IMAGES if BASE_IMAGES * li.flops_per_image / 2 <= LARGE_REFERENCE_MACS else 2
+
+
+def large_case_id(prec, spec, n, name, kid):
+    return f'{prec}:{spec_name(spec)}-b{n}:{name}:{kid}'
+
+
+def _large_cases(precisions):
+    scan = [c for prec in precisions for c in large_operand_scan(prec)]
+    return [pytest.param(prec, spec, n, i, kid, mine, id=large_case_id(prec, spec, n, DryRun(spec, n, prec).names[i], kid))
+            for prec, spec, n, i, kid, mine in large_address_cases(scan)]
+
+
+def launched_large_triples(cases):
+    """{triple: case id} of what the large-address cases hold, from a dry run of each case's own (precision, spec, n, layer) --
+    not from what the case list says about itself: the triples with LARGE_IMAGES_BEYOND images beyond the boundary (or at the
+    largest call), and those with fewer that the case names as its own."""
+    out = {}
+    for c in cases:
+        prec, spec, n, i, kid, mine = c.values
+        run = DryRun(spec, n, prec)
+        assert run.kernels(n, [i]) == [kid], c.id
+        now = large_triples(run.infos, i, kid, n)
+        for t in held_triples(n, now) | {t for t in mine if t in now}:
+            out.setdefault(t, c.id)
+    return out
+
+
+def test_large_operand_closure():
+    """One level beside test_pair_closure: ADDRESSES.  Every other GPU case launches its large crop sides at small call sizes and
+    its large call sizes at side 256 -- no operand beyond 2^32 bytes or 2^31 elements -- while the supported grid reaches
+    activations of 16 GiB.  For every layer of every plan of the grid
+
+        proc_side 64 .. 512  x  ResNet-v2 50 / 101  x  stride 4 / 8 / 16 / 32  x  h36m / many19 / merged heads  x  every batch 1 .. 256
+
+    the size of each operand the launch touches (operand_roles: input, output, second output, residual with its own side,
+    sub-sampled output, the head's fp32 logits; element sizes from the layer's dtypes) is classed A (beyond 2^31 bytes), B (beyond
+    2^32 bytes), E (beyond 2^31 elements); every (kernel, role, class) triple reached -- kernel_of of
+    tests/test_gpu_nonfinite_kernels.py plus the form suffix, `a & b` ids split -- must be LAUNCHED by a case of
+    tests/test_gpu_large_address.py with that operand in that class and LARGE_IMAGES_BEYOND whole images beyond the boundary
+    (fewer only at 256 crops, or where no call size of the grid gives them: printed).  The case list is generated from the same
+    scan (large_address_cases); what the cases launch is recomputed here from each case's own dry run, so a case taken off the
+    list fails this test.
+    The parity modes ('f64', 'f32', 'f32m': the range of tests/test_parity_coverage.py, the same grid) reach class A too -- an
+    fp64 activation is four times the fp16 one -- so their triples are part of the universe and of the list.
+    Measured on the build machine: the f16 scan 2 s (47 triples, 15 cases), the three parity scans 18 s (34 triples, 10 cases);
+    the whole test 30 s."""
+    from tests.test_gpu_large_address import LARGE_CASES, PRECISIONS
+    assert all(c.values[1] is not None for c in LARGE_CASES), LARGE_CASES[0].values[4]
+    scan = [c for prec in PRECISIONS for c in large_operand_scan(prec)]
+    universe = large_universe(scan)
+    launched = launched_large_triples(LARGE_CASES)
+    holdable = {t for c in scan for t in held_triples(c[3], c[6])}
+    print(f'\n{len(universe)} (kernel, operand role, class) triples beyond 2^31 bytes over the grid, {len(LARGE_CASES)} large-address cases:')
+    for c in LARGE_CASES:
+        print(f'  {c.id}')
+        for t, images in sorted(c.values[5].items()):
+            print(f'      {t[0]}, {t[1]}, class {t[2]}: {images} images beyond' + ('' if t in holdable else '  (no call of the grid gives more)'))
+    assert {'A', 'B', 'E'} <= {t[2] for t in universe} and {t[1] for t in universe} <= set(LARGE_ROLES)
+    missing = sorted(t for t in universe if t not in launched)
+    assert not missing, 'reached by the supported grid but launched by no large-address case (kernel, operand role, class):\n' + \
+        '\n'.join(f'  {t}' for t in missing)
+    # launched with the images the issue asks for: a triple some call of the grid holds is held by a case, not merely touched
+    held = {t for c in LARGE_CASES for t in held_triples(c.values[2], large_triples(DryRun(c.values[1], c.values[2], c.values[0]).infos,
+                                                                                   c.values[3], c.values[4], c.values[2]))}
+    thin = sorted(holdable - held)
+    assert not thin, f'launched with fewer than {LARGE_IMAGES_BEYOND} images beyond the boundary although the grid gives them:\n' + \
+        '\n'.join(f'  {t}' for t in thin)
+    # the classes are strict: a tensor of exactly 2^32 bytes / 2^31 elements (block4 at stride 4, side 256, 256 crops) is in class A only
+    run = DryRun(ModelSpec(50, 4, 'h36m'))
+    i = run.names.index('block4/unit_1/conv3')
+    assert {t[1:] for t in large_triples(run.infos, i, run.kernels(256, [i])[0], 256)} == {('output', 'A'), ('residual', 'A')}
+    assert images_beyond(68, 2 ** 26, 2 ** 32) == 4 and images_beyond(65, 2 ** 26, 2 ** 32) == 1 and images_beyond(64, 2 ** 26, 2 ** 32) == 0
+
+
+def test_entries_refuse_calls_beyond_the_int32_pixel_index(lib):
+    """The conv, stem and head kernels hold pixel indices in int (elements and bytes in size_t): a call whose pixel count --
+    input, output, residual map, stem image, heat map -- does not fit int32 is refused with METRO_ERR_INVALID_ARG (ValueError)
+    instead of launched, and nothing inside the supported grid is refused.  Through the dry run: no device, no launch."""
+    one = C.c_void_p(256)                      # any non-NULL pointer: a dry run touches none
+    check(lib.metro_kernel_notes(2), 'metro_kernel_notes')
+    try:
+        # the largest maps of the grid pass: 256 crops of side 512 (stem), their 128 x 128 maps (conv with residual, head)
+        check(lib.metro_stem_pool_f32in(one, one, one, one, 256, 512, None), 'stem, grid maximum')
+        d = H.conv_desc(256, 128, 512, 128, 2048, 1, residual=True, res_h=128)
+        check(lib.metro_conv_f16(C.byref(d), one, one, one, None, None, one, one, None), 'conv, grid maximum')
+        spec = ModelSpec(50, 4, 'h36m', proc_side=512)
+        cs = spec.to_c(_lib.METRO_PREC_F16)
+        check(lib.metro_head_f16(one, one, one, one, one, 256, 2048, C.byref(cs), one, None, one, None), 'head, grid maximum')
+        assert lib.metro_last_kernel_id().decode().split(' & ')[:3] == ['stem_pool_f16<split2,f32in>', 'conv_pws<k512,res>', 'head_f16<144x256,k2>']
+        # 2^31 pixels: 8192 crops of side 512; 131 072 maps of 128 x 128
+        with pytest.raises(ValueError, match='overflow the int32 pixel index'):
+            check(lib.metro_stem_pool_f32in(one, one, one, one, 8192, 512, None), 'stem')
+        with pytest.raises(ValueError, match='overflow the int32 pixel index'):
+            check(lib.metro_stem_pool_u8in(one, one, one, one, 8192, 512, None), 'stem')
+        check(lib.metro_stem_pool_f32in(one, one, one, one, 8191, 512, None), 'stem, one crop below')
+        with pytest.raises(ValueError, match='overflow the int32 pixel index'):
+            check(lib.metro_head_f16(one, one, one, one, one, 131072, 2048, C.byref(cs), one, None, one, None), 'head')
+        small = ModelSpec(50, 32, 'h36m')     # an 8 x 8 heat map: the pixel index fits, the grid's image axis does not
+        cs2 = small.to_c(_lib.METRO_PREC_F16)
+        with pytest.raises(ValueError, match='image axis'):
+            check(lib.metro_head_f16(one, one, one, one, one, 65536, 2048, C.byref(cs2), one, None, one, None), 'head')
+        d = H.conv_desc(131072, 128, 512, 128, 2048, 1, residual=True, res_h=128)
+        with pytest.raises(ValueError, match='too many'):
+            check(lib.metro_conv_f16(C.byref(d), one, one, one, None, None, one, one, None), 'conv')
+        # a residual map larger than the output (the sub-sampled shortcut): its pixel count alone passes int32
+        d = H.conv_desc(40000, 128, 64, 128, 256, 1, residual=True, res_h=256, res_stride=2)
+        with pytest.raises(ValueError, match='too many residual pixels'):
+            check(lib.metro_conv_f16(C.byref(d), one, one, one, None, None, one, one, None), 'conv, residual map')
+    finally:
+        lib.metro_kernel_notes(0)
+
+
 def classic_dispatch_digests():
     """{spec name: sha256 over the kernel id of every layer at every call size 1 .. 256} of PAIR_SPECS' default plans, dispatched
     with the classic forms forced (metro_conv_b1_form(1))."""
@@ -515,9 +770,14 @@ def _assignment(n, what):
     return H.crop_assignment(n, min(BASE_IMAGES, n), zlib.crc32(what.encode()))
 
 
+def _base_images(assign):
+    """p of an assignment: every base image occurs (min(BASE_IMAGES, n) for _assignment's; a large-address case may use 2)."""
+    return int(np.max(assign)) + 1
+
+
 def _twins(gen, assign, shape, cuda, scale=1.0, relu=False):
     """fp16 [n, *shape] on the device with image i == base image assign[i], and the base images as numpy."""
-    p = min(BASE_IMAGES, len(assign))
+    p = _base_images(assign)
     base = torch.randn((p,) + tuple(shape), generator=gen, device=cuda, dtype=torch.float32) * scale
     if relu:
         base = base.clamp_min(0)
@@ -558,7 +818,9 @@ def test_single_launch_against_fp64_reference(lib, cuda, spec, n, layer, kid):
     _launch(lib, cuda, f'{spec_name(spec)}-b{n}', spec, n, layer, kid)
 
 
-def _launch(lib, cuda, cname, spec, n, layer, kid):
+def _launch(lib, cuda, cname, spec, n, layer, kid, assign=None):
+    """One launch of `layer` of the f16 plan of `spec` at call size n through its single-kernel entry point, held to the id the
+    plan names, to the twin layout and to the fp64 reference on the base images.  `assign`: the layout (default: _assignment)."""
     _, li, kid2 = dispatch_table(spec, n)[layer]
     assert kid2 == kid
     name = li.name.decode()
@@ -566,7 +828,9 @@ def _launch(lib, cuda, cname, spec, n, layer, kid):
     gen.manual_seed(zlib.crc32(f'{cname}/{name}'.encode()))
     rng = np.random.default_rng(zlib.crc32(f'{cname}/{name}/w'.encode()))
     dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(dt))).to(cuda)
-    assign = _assignment(n, f'{cname}/{name}')
+    if assign is None:
+        assign = _assignment(n, f'{cname}/{name}')
+    assert len(assign) == n
     check(lib.metro_kernel_notes(1), 'metro_kernel_notes')
     try:
         if name == 'softargmax':
@@ -584,7 +848,7 @@ def _launch(lib, cuda, cname, spec, n, layer, kid):
 def _stem(lib, cuda, li, assign, gen, rng, dev, kid):
     side = 4 * li.h_out
     n = len(assign)
-    p = min(BASE_IMAGES, n)
+    p = _base_images(assign)
     base = torch.rand((p, side, side, 3), generator=gen, device=cuda, dtype=torch.float32)
     img = H.lay_out_twins(base, assign)
     w = (rng.standard_normal((64, 7, 7, 3)) * np.sqrt(2.0 / 147)).astype(np.float16)
@@ -642,7 +906,7 @@ def _softargmax(lib, cuda, spec, assign, gen, rng, kid):
     from oracle.forward import logits_to_output
     side, j, dd = spec.heatmap_side, spec.skeleton.n_head, spec.depth
     n = len(assign)
-    p = min(BASE_IMAGES, n)
+    p = _base_images(assign)
     base = torch.randn((p, side, side, dd * j), generator=gen, device=cuda, dtype=torch.float32) * 4.0
     for i in range(p):
         for jj in range(j):

@@ -276,7 +276,7 @@ def _gaussian_set(key, d, np_in, np_w, np_act):
     return _REFS[types]
 
 
-def _conv(lib, cuda, li, n, kid, what):
+def _conv(lib, cuda, li, n, kid, what, assign=None):
     from tests.test_gpu_conv_contract import _check, _guarded, _guards_intact
     f32m = kid.startswith('conv_igemm_f32<')
     np_in = np.float64 if 'in64' in kid else np.float32
@@ -285,7 +285,9 @@ def _conv(lib, cuda, li, n, kid, what):
     assert f32m or f'act{np_act().itemsize * 8}' in kid, kid
     key = tuple(getattr(li, f) for f in SHAPE_KEY if f != 'out_dtype')          # (the modes share a layer shape's values)
     p = min(base_images(li), n)
-    assign = H.crop_assignment(n, p, zlib.crc32(what.encode()))
+    if assign is None:
+        assign = H.crop_assignment(n, p, zlib.crc32(what.encode()))
+    assert len(assign) == n and int(np.max(assign)) + 1 == p
     d = _desc(li, n, F64 if np_in is np.float64 else F32)
     dp = copy.copy(d)
     dp.n = p
@@ -328,10 +330,12 @@ def _conv(lib, cuda, li, n, kid, what):
     print(f'\n[parity] {what}: Gaussian set worst |err| / bound {ratio:.3f} (family {fam}: {RATIOS[fam]:.3f} so far)')
 
 
-def _pool(lib, cuda, li, n, kid, what):
+def _pool(lib, cuda, li, n, kid, what, assign=None):
     from tests.test_gpu_conv_contract import _guarded, _guards_intact
     p = min(4, n)
-    assign = H.crop_assignment(n, p, zlib.crc32(what.encode()))
+    if assign is None:
+        assign = H.crop_assignment(n, p, zlib.crc32(what.encode()))
+    assert len(assign) == n and int(np.max(assign)) + 1 == p
     tdt = torch.float64 if li.out_dtype == F64 else torch.float32
     gen = torch.Generator(device=cuda)
     gen.manual_seed(zlib.crc32(what.encode()))
@@ -356,7 +360,7 @@ def _pool(lib, cuda, li, n, kid, what):
     assert (want[p - 1, 0, :, ::2] == 0).all() and (want[p - 1, 1:, 1:, ::2] < 0).all()
 
 
-def _softargmax(lib, cuda, spec, n, kid, what):
+def _softargmax(lib, cuda, spec, n, kid, what, assign=None):
     """N(0, 4) logits plus one planted peak per (image, joint) at a random voxel (test_kernel_coverage._softargmax), in the
     type the mode stores its logits in."""
     from oracle.forward import logits_to_output
@@ -364,7 +368,9 @@ def _softargmax(lib, cuda, spec, n, kid, what):
     logits64 = 'logits64' in kid
     side, j, dd = spec.heatmap_side, spec.skeleton.n_head, spec.depth
     p = min(4, n)
-    assign = H.crop_assignment(n, p, zlib.crc32(what.encode()))
+    if assign is None:
+        assign = H.crop_assignment(n, p, zlib.crc32(what.encode()))
+    assert len(assign) == n and int(np.max(assign)) + 1 == p
     gen = torch.Generator(device=cuda)
     gen.manual_seed(zlib.crc32(what.encode()))
     rng = np.random.default_rng(zlib.crc32(what.encode()))
@@ -401,17 +407,23 @@ def _softargmax(lib, cuda, spec, n, kid, what):
 @pytest.mark.parametrize('prec,spec,n,layer,kid', _CASES)
 def test_parity_launch(lib, cuda, prec, spec, n, layer, kid):
     assert prec is not None, f'libmetro_hip.so could not be loaded at collection time: {kid}'
+    parity_launch(lib, cuda, prec, spec, n, layer, kid)
+
+
+def parity_launch(lib, cuda, prec, spec, n, layer, kid, assign=None):
+    """One launch of `layer` of the `prec` plan of `spec` at call size n, held as the module docstring says.  `assign`: the twin
+    layout (default: crop_assignment seeded by the case)."""
     eng = Engine(spec, None, prec, max_batch=n)
     li = eng.layer_infos()[layer]
     assert eng.layer_kernels(n)[layer] == kid
     what = f'{prec} {spec_name(spec)} b{n} {li.name.decode()} {kid}'
     if li.kind == _lib.LAYER_SOFTARGMAX:
-        _softargmax(lib, cuda, spec, n, kid, what)
+        _softargmax(lib, cuda, spec, n, kid, what, assign)
     elif li.kind == _lib.LAYER_POOL:
-        _pool(lib, cuda, li, n, kid, what)
+        _pool(lib, cuda, li, n, kid, what, assign)
     else:
         assert li.kind == _lib.LAYER_CONV and kid.startswith(CONV_FAMILIES), (li.kind, kid)
-        _conv(lib, cuda, li, n, kid, what)
+        _conv(lib, cuda, li, n, kid, what, assign)
 
 
 # ---- GPU: whole forwards ----------------------------------------------------------------------------------------------------
