@@ -13,7 +13,9 @@
 //   * weights stream per step (one tap, or one kernel row of three taps, of one chunk) through a 3- or
 //     4-deep LDS-DMA ring; the next chunk's slab is issued during the chunk's first step into the other
 //     slab buffer.  One raw s_barrier per step; waits are counted (s_waitcnt vmcnt(N)) over the merged
-//     in-order DMA stream.  SlabCfg holds the tile shape, chunk width, ring depth and taps per step.
+//     in-order DMA stream.  SlabCfg holds the tile shape, chunk width, ring depth and taps per step;
+//   * on maps (or sub-images) 16 pixels wide the side taps of a kernel row are the centre tap's fragment shifted by lanes (DPP
+//     row shifts with zero fill), one LDS read per kernel row instead of three (slab_tile: HS).
 // Covers the reference's conv2 call sites with stride 1: resnet_v2.py:130-132 via
 // resnet_utils.conv2d_same (SAME padding, rate r).  Post-conv BN+ReLU folded (bias + ReLU).
 // Below the tile: an EXPERIMENTAL launch that chains conv3 + shortcut behind it for block3 (four
@@ -26,6 +28,17 @@
 #endif
 #include "metro_common.h"
 #include "gfx950_prims.h"
+
+// The lane-shift form (slab_tile: HS; A/B of each switch in NOTES_dead_ends.md, "3x3 slab: horizontal taps by lane shifts").
+#ifndef METRO_SLAB_HSHIFT
+#define METRO_SLAB_HSHIFT 7    // which configurations take it on 16-wide maps: 1 = kernel-row steps (tps3), 2 = 128-cout tile, 4 = single-chunk tile; 0 = plain reads everywhere
+#endif
+#ifndef METRO_SLAB_HS_AHEAD
+#define METRO_SLAB_HS_AHEAD 1  // ... reads its weight fragments one k step ahead (the registers the smaller offset table frees pay for it)
+#endif
+#ifndef METRO_SLAB_HS_T3_2X4
+#define METRO_SLAB_HS_T3_2X4 1 // ... lays the waves of the kernel-row tile out 2 x 4 (32 cout x 64 pixels each) instead of 1 x 8
+#endif
 
 namespace metro {
 
@@ -72,8 +85,31 @@ struct SlabCfg {
     // the epilogue tile overlays slabs + zero area + weight ring (all idle by then)
 };
 
+// Pixel fragment of the side tap (dr, (TX - 1) * HS) from the centre tap's (dr, 0): lane l takes lane l - ds of its 16-lane DPP
+// row, zero where that lane is outside the row (bound_ctrl).  row_shr:n = 0x110 + n, row_shl:n = 0x100 + n.
+template <int HS, int TX>
+__device__ __forceinline__ half8_t slab_side_tap(const half8_t& centre) {
+    if constexpr (TX == 1) return centre;
+    else {
+        typedef int intx4 __attribute__((ext_vector_type(4)));
+        const intx4 c = __builtin_bit_cast(intx4, centre);
+        intx4 r;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r[e] = __builtin_amdgcn_update_dpp(0, c[e], (TX == 0 ? 0x110 : 0x100) + HS, 0xF, 0xF, true);
+        return __builtin_bit_cast(half8_t, r);
+    }
+}
+
 // One tile: cout [n0, n0 + TM) of pixels [m0, m0 + TN).
-template <class Cfg>
+// HS > 0 (the launcher: maps or sub-images 16 pixels wide, HS = the horizontal tap distance in pixels, 1 or 2): a pixel fragment's
+// lanes 0-15 and 16-31 (and 32-47, 48-63: the other k half) are one image row each -- tiles start at multiples of 256, fragments
+// at multiples of 32 -- so a 16-lane DPP row IS an image row and the side taps (dr, -d), (dr, +d) of a kernel row are the centre
+// tap's fragment shifted by d lanes with zero fill: the zero a shift brings in at x < d or x >= 16 - d is the zero the plain
+// form reads from the zero area.  One LDS read per kernel row instead of three; the MFMAs and their order are unchanged.
+// Fewer reads alone buy next to nothing (the wait per k step is the weight fragments' latency, not the read count); what they
+// buy is registers: the offset table shrinks from 9 to 3 entries per pixel fragment, and with PF = 1 the form spends them on a
+// second set of weight fragments, read one k step ahead of the MFMAs that use them (the plain 128-cout form spills if it does).
+template <class Cfg, int HS = 0, int PF = 0>
 __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __restrict__ in, const half_t* __restrict__ w,
                                           const float* __restrict__ bias, half_t* __restrict__ out, int halo, int m0, int n0,
                                           char* smem, int tid, int sgd) {
@@ -180,7 +216,9 @@ __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __res
     // TN == 512: four pixel tiles per wave would need 36 such registers next to 128 accumulators; there each pixel
     // tile keeps the offset of its centre row and a 9-bit validity mask, the tap displacement is a scalar.
     constexpr bool TABLE = Cfg::TN == 256;
-    int boff[TABLE ? Cfg::WN : 1][9];
+    static_assert(HS == 0 || TABLE, "lane-shift form: 256-pixel tiles");
+    constexpr int NTAB = HS ? 3 : 9;                            // HS: the centre tap of each kernel row (row validity included)
+    int boff[TABLE ? Cfg::WN : 1][NTAB];
     int bbase[Cfg::WN];
     unsigned bmask[Cfg::WN];
 #pragma unroll
@@ -196,7 +234,10 @@ __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __res
             const int dr = (tap / 3 - 1) * gdil, ds = (tap % 3 - 1) * gdil;
             const bool ok = m < a.m_total && (unsigned)(h + dr) < (unsigned)gh &&
                             (unsigned)(x + ds) < (unsigned)gw;
-            if constexpr (TABLE) boff[j][tap] = ok ? (halo + t + dr * gw + ds) * Cfg::ROW_BYTES : -1;
+            if constexpr (TABLE && HS == 0) boff[j][tap] = ok ? (halo + t + dr * gw + ds) * Cfg::ROW_BYTES : -1;
+            if constexpr (TABLE && HS != 0) {
+                if (tap % 3 == 1) boff[j][tap / 3] = ok ? (halo + t + dr * gw) * Cfg::ROW_BYTES : -1;
+            }
             bmask[j] |= ok ? 1u << tap : 0u;
         }
     }
@@ -239,7 +280,7 @@ __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __res
             int bo;
             bool ok;
             if constexpr (TABLE) {
-                bo = boff[j][TAP];
+                bo = boff[j][HS ? TAP / 3 : TAP];
                 ok = bo >= 0;
             } else {
                 const int toff = __builtin_amdgcn_readfirstlane((((TAP / 3 - 1) * gw + (TAP % 3 - 1)) * gdil) * Cfg::ROW_BYTES);
@@ -264,31 +305,61 @@ __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __res
     // One step = TPS taps of one chunk.  The taps, what gets issued and the wait count are compile-time, so each
     // step is straight-line code: ds_read_b128 + MFMA + its share of the DMA issue.  The ring slot is a constant
     // for the 3-deep ring (9 taps = 3 turns), a rotating scalar for deeper ones.
+    half8_t held[HS ? Cfg::WN : 1][NKK];                       // HS: the centre fragments of the current kernel row
     auto step = [&](auto tap_c, auto issue_slab_c, auto issue_w_c, auto wait_c, int slab_buf, int wslot) {
         constexpr int TAP0 = decltype(tap_c)::value;             // first tap of the step
         wait_vm_and_barrier<decltype(wait_c)::value>();
         const int islot = wslot == 0 ? WS - 1 : wslot - 1;     // slot of step q+WS-1 == slot of step q-1
+        unsigned pa[Cfg::TPS][Cfg::WM], pb[Cfg::TPS][Cfg::WN];
+        // the step's (tap, k step) pairs in order, q = tt * NKK + kk; PF = 1 reads the fragments of pair q + 1 before the MFMAs of
+        // pair q (every weight of the step has landed at the barrier, so the pipeline runs through the taps of a kernel-row step);
+        // the compiler sinks the early reads back behind the MFMAs unless the order is pinned
+        constexpr int NQ = Cfg::TPS * NKK;
+        half8_t af[PF + 1][Cfg::WM], bf[PF + 1][Cfg::WN];
+        auto fetch = [&](int q) {
+            const int tt = q / NKK, kk = q % NKK;
+            if (kk == 0) frag_addr(TAP0 + tt, tt, slab_buf, wslot, pa[tt], pb[tt]);
 #pragma unroll
-        for (int tt = 0; tt < Cfg::TPS; ++tt) {
-            unsigned pa[Cfg::WM], pb[Cfg::WN];
-            frag_addr(TAP0 + tt, tt, slab_buf, wslot, pa, pb);
+            for (int i = 0; i < Cfg::WM; ++i) af[q % (PF + 1)][i] = *reinterpret_cast<const half8_t*>(smem + (pa[tt][i] ^ (kk << 5)));
 #pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) {
-                half8_t af[Cfg::WM], bf[Cfg::WN];
-#pragma unroll
-                for (int i = 0; i < Cfg::WM; ++i) af[i] = *reinterpret_cast<const half8_t*>(smem + (pa[i] ^ (kk << 5)));
-#pragma unroll
-                for (int j = 0; j < Cfg::WN; ++j) bf[j] = *reinterpret_cast<const half8_t*>(smem + (pb[j] ^ (kk << 5)));
-#pragma unroll
-                for (int i = 0; i < Cfg::WM; ++i)
-#pragma unroll
-                    for (int j = 0; j < Cfg::WN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
-                if constexpr (decltype(issue_slab_c)::value) {
-                    if (tt == 0) issue_slab_part(slab_buf ^ 1, kk, kk == NKK - 1);
+            for (int j = 0; j < Cfg::WN; ++j) {
+                if constexpr (HS != 0) {
+                    // the row's first tap reads the centre fragment (pb: frag_addr maps every tap of a row to its centre);
+                    // with TPS == 1 it lives through the row's next two steps
+                    if ((TAP0 + tt) % 3 == 0) held[j][kk] = *reinterpret_cast<const half8_t*>(smem + (pb[tt][j] ^ (kk << 5)));
+                } else {
+                    bf[q % (PF + 1)][j] = *reinterpret_cast<const half8_t*>(smem + (pb[tt][j] ^ (kk << 5)));
                 }
-                if constexpr (decltype(issue_w_c)::value) issue_w_part(islot, (TAP0 + (WS - 1) * Cfg::TPS) % 9, kk, tt);
             }
+        };
+        if constexpr (PF != 0) fetch(0);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int tt = q / NKK, kk = q % NKK;
+            if constexpr (PF != 0) {
+                if (q + 1 < NQ) fetch(q + 1);
+                __builtin_amdgcn_sched_barrier(0);               // the pin: reads of q + 1 stay in front of the MFMAs of q
+            } else {
+                fetch(q);
+            }
+            half8_t bq[Cfg::WN];
+#pragma unroll
+            for (int j = 0; j < Cfg::WN; ++j) {
+                if constexpr (HS != 0)
+                    bq[j] = (TAP0 + tt) % 3 == 0 ? slab_side_tap<HS, 0>(held[j][kk])
+                          : (TAP0 + tt) % 3 == 1 ? slab_side_tap<HS, 1>(held[j][kk]) : slab_side_tap<HS, 2>(held[j][kk]);
+                else
+                    bq[j] = bf[q % (PF + 1)][j];
+            }
+#pragma unroll
+            for (int i = 0; i < Cfg::WM; ++i)
+#pragma unroll
+                for (int j = 0; j < Cfg::WN; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[q % (PF + 1)][i], bq[j], acc[i][j], 0, 0, 0);
+            if constexpr (decltype(issue_slab_c)::value) {
+                if (tt == 0) issue_slab_part(slab_buf ^ 1, kk, kk == NKK - 1);
+            }
+            if constexpr (decltype(issue_w_c)::value) issue_w_part(islot, (TAP0 + (WS - 1) * Cfg::TPS) % 9, kk, tt);
         }
     };
     auto chunk_main = [&](int slab_buf) {       // not the last chunk: slab(c+1) during the first step, W always
@@ -357,7 +428,7 @@ __device__ __forceinline__ void slab_tile(const ConvArgs& a, const half_t* __res
     }
 }
 
-template <class Cfg>
+template <class Cfg, int HS = 0>
 __global__ __launch_bounds__(Cfg::NT) void conv3x3_f16_slab_kernel(
     ConvArgs a, const half_t* __restrict__ in, const half_t* __restrict__ w,
     const float* __restrict__ bias, half_t* __restrict__ out, int tiles_m, int halo, int sgd) {
@@ -366,16 +437,13 @@ __global__ __launch_bounds__(Cfg::NT) void conv3x3_f16_slab_kernel(
     const int lid = xcd_block_lid(blockIdx.x, nblk);
     const int tile_n = lid / tiles_m;
     const int tile_m = lid % tiles_m;
-    slab_tile<Cfg>(a, in, w, bias, out, halo, tile_n * Cfg::TN, tile_m * Cfg::TM, smem, threadIdx.x, sgd);
+    slab_tile<Cfg, HS, HS != 0 && METRO_SLAB_HS_AHEAD>(a, in, w, bias, out, halo, tile_n * Cfg::TN, tile_m * Cfg::TM, smem, threadIdx.x, sgd);
 }
 
-template <class Cfg>
-static int launch_slab_cfg(const ConvArgs& a, const half_t* in, const half_t* w, const float* bias,
-                           half_t* out, int halo, hipStream_t stream, int sgd = 0) {
-    if (note_kernel("conv3x3_f16_slab<%dx%d,rows%d,bufs%d,tps%d,kc%d,ws%d>%s", Cfg::TM, Cfg::TN, Cfg::SLAB_ROWS, Cfg::SLAB_BUFS, Cfg::TPS,
-                    Cfg::KC, Cfg::W_STAGES, sgd ? "+subgrid" : ""))
-        return METRO_OK;
-    auto kern = conv3x3_f16_slab_kernel<Cfg>;
+template <class Cfg, int HS>
+static int launch_slab_kernel(const ConvArgs& a, const half_t* in, const half_t* w, const float* bias,
+                              half_t* out, int halo, hipStream_t stream, int sgd) {
+    auto kern = conv3x3_f16_slab_kernel<Cfg, HS>;
     static PerDeviceInt attr_done;
     if (const int st = ensure_dyn_lds(reinterpret_cast<const void*>(kern), Cfg::LDS_BYTES, attr_done, "conv3x3_f16_slab")) return st;
     const int tiles_m = (a.c_out + Cfg::TM - 1) / Cfg::TM;
@@ -383,6 +451,26 @@ static int launch_slab_cfg(const ConvArgs& a, const half_t* in, const half_t* w,
     hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(Cfg::NT), Cfg::LDS_BYTES, stream, a, in, w, bias,
                        out, tiles_m, halo, sgd);
     return launch_status("conv3x3_f16_slab");
+}
+
+// HSHIFT: this configuration takes the lane-shift form (slab_tile: HS) on 16-wide maps and sub-images.  The form is another
+// implementation of the same instantiation -- same tile, ring, steps and MFMA order, same bits -- so the kernel id does not name it.
+// HsCfg: the configuration the form runs on: Cfg, or the same tile and steps under another wave layout (the order of the MFMAs
+// of an accumulator does not depend on which wave holds it).
+template <class Cfg, bool HSHIFT = false, class HsCfg = Cfg>
+static int launch_slab_cfg(const ConvArgs& a, const half_t* in, const half_t* w, const float* bias,
+                           half_t* out, int halo, hipStream_t stream, int sgd = 0) {
+    if (note_kernel("conv3x3_f16_slab<%dx%d,rows%d,bufs%d,tps%d,kc%d,ws%d>%s", Cfg::TM, Cfg::TN, Cfg::SLAB_ROWS, Cfg::SLAB_BUFS, Cfg::TPS,
+                    Cfg::KC, Cfg::W_STAGES, sgd ? "+subgrid" : ""))
+        return METRO_OK;
+    if constexpr (HSHIFT) {
+        static_assert(HsCfg::TM == Cfg::TM && HsCfg::TN == Cfg::TN && HsCfg::SLAB_ROWS == Cfg::SLAB_ROWS && HsCfg::SLAB_BUFS == Cfg::SLAB_BUFS &&
+                      HsCfg::TPS == Cfg::TPS && HsCfg::KC == Cfg::KC && HsCfg::W_STAGES == Cfg::W_STAGES, "one kernel id");
+        const int gw = sgd ? a.w_out / sgd : a.w_out, gdil = sgd ? 1 : a.dil;      // as slab_tile
+        if (gw == 16 && gdil == 1) return launch_slab_kernel<HsCfg, 1>(a, in, w, bias, out, halo, stream, sgd);
+        if (gw == 16 && gdil == 2) return launch_slab_kernel<HsCfg, 2>(a, in, w, bias, out, halo, stream, sgd);
+    }
+    return launch_slab_kernel<Cfg, 0>(a, in, w, bias, out, halo, stream, sgd);
 }
 
 //                    WAVES_M WAVES_N WM WN slab rows        tile, LDS
@@ -401,9 +489,17 @@ using Slab64r320 = SlabCfg<1, 8, 2, 1, 320, 2, 1, 64, METRO_SLAB_WS64>;    //  6
 using Slab64r384 = SlabCfg<1, 8, 2, 1, 384>;
 using Slab64r512 = SlabCfg<1, 8, 2, 1, 512>;    // halo <= 128: 128 + 24 KiB
 using Slab64r320t3 = SlabCfg<1, 8, 2, 1, 320, 2, 3>;   // one kernel row per step: 80 + 72 KiB
+#if METRO_SLAB_HS_T3_2X4
+using Slab64r320t3hs = SlabCfg<2, 4, 1, 2, 320, 2, 3>; // the same tile for the lane-shift form, waves 2 x 4: 12 + 8 fragment reads per kernel row instead of 24 + 4
+#else
+using Slab64r320t3hs = Slab64r320t3;
+#endif
 using Slab64r384b1 = SlabCfg<1, 8, 2, 1, 384, 1>;  // single chunk (c_in == 64), halo <= 64: 48 + 24 KiB -> 2 blocks / CU
 using Slab64r320b1 = SlabCfg<1, 8, 2, 1, 320, 1>;
 using Slab128p512 = SlabCfg<2, 4, 2, 4, 640, 2, 1, 32, METRO_SLAB_WS512>;   // 128 cout x 512 px, 32-channel chunks, halo <= 64: 80 + 32 KiB (epilogue tile 136 KiB)
+
+// which configurations take the lane-shift form: bit 0 the kernel-row steps (tps3), bit 1 the 128-cout tile, bit 2 the single-chunk tile
+constexpr bool HS_T3 = (METRO_SLAB_HSHIFT & 1) != 0, HS_128 = (METRO_SLAB_HSHIFT & 2) != 0, HS_B1 = (METRO_SLAB_HSHIFT & 4) != 0;
 
 static bool slab_plain_ok(const MetroConvDesc& d) {
     // tiles are 256 consecutive pixels starting at column 0 (256 % W == 0): a tap (dr, ds<0) of a pixel
@@ -505,14 +601,14 @@ int launch_conv3x3_slab(const MetroConvDesc& d, const void* in_, const void* w_,
     const int sgd = slab_subgrid_rate(d);
     const int halo = slab_halo(d, sgd);
     switch (slab_pick(d, halo, sgd)) {
-        case SP_64R320B1: return launch_slab_cfg<Slab64r320b1>(a, in, w, bias, out, halo, stream, sgd);
+        case SP_64R320B1: return launch_slab_cfg<Slab64r320b1, HS_B1>(a, in, w, bias, out, halo, stream, sgd);
         case SP_64R384B1: return launch_slab_cfg<Slab64r384b1>(a, in, w, bias, out, halo, stream, sgd);
-        case SP_64R320T3: return launch_slab_cfg<Slab64r320t3>(a, in, w, bias, out, halo, stream, sgd);
+        case SP_64R320T3: return launch_slab_cfg<Slab64r320t3, HS_T3, Slab64r320t3hs>(a, in, w, bias, out, halo, stream, sgd);
         case SP_64R320: return launch_slab_cfg<Slab64r320>(a, in, w, bias, out, halo, stream, sgd);
         case SP_64R384: return launch_slab_cfg<Slab64r384>(a, in, w, bias, out, halo, stream, sgd);
         case SP_64R512: return launch_slab_cfg<Slab64r512>(a, in, w, bias, out, halo, stream, sgd);
         case SP_128P512: return launch_slab_cfg<Slab128p512>(a, in, w, bias, out, halo, stream, sgd);
-        case SP_128R320: return launch_slab_cfg<Slab128r320>(a, in, w, bias, out, halo, stream, sgd);
+        case SP_128R320: return launch_slab_cfg<Slab128r320, HS_128>(a, in, w, bias, out, halo, stream, sgd);
         case SP_128R384: return launch_slab_cfg<Slab128r384>(a, in, w, bias, out, halo, stream, sgd);
     }
     set_error("conv3x3_f16_slab: no configuration");

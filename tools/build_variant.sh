@@ -3,6 +3,7 @@
 #   tools/build_variant.sh <name> "<flags>" file1.hip file2.hip ...   ->  metro_pose3d_amd/ab/libmetro_<name>.so
 #   tools/build_variant.sh agpr_slab "-DMETRO_AGPR_ACC=1" conv3x3_f16_slab.hip
 #   tools/build_variant.sh plain_slab "-DMETRO_WT_STORES=0" conv3x3_f16_slab.hip      (the store form of one family: metro_common.h)
+#   tools/build_variant.sh slab_plain_reads "-DMETRO_SLAB_HSHIFT=0" conv3x3_f16_slab.hip   (the slab kernel without its lane-shift form)
 # then: tools/ab_libs.sh 64 3 metro_pose3d_amd/libmetro_hip.so metro_pose3d_amd/ab/libmetro_agpr_slab.so
 set -e
 name=$1; flags=$2; shift 2
