@@ -200,6 +200,34 @@ int  metro_forward_status(const MetroPlan* plan, const void* d_workspace, int32_
  * several forwards (more crops than the plan's max_batch) can fold them on the device after each one and synchronise ONCE.  The
  * words are those of the LAST forward on this workspace: valid until the next metro_forward on it, on the same stream only. */
 int64_t metro_plan_status_offset(const MetroPlan* plan);
+/* ---- per-joint heat-map marginals, bound to the plan ----
+ * Every joint's output is a softmax distribution p over its S x S x D volume (S = proc_side / stride; the heat-map
+ * net_output_to_heatmap_and_coords returns next to the coordinates, reference volumetric.py:227-235).  With output buffers bound,
+ * every forward entry -- metro_forward, metro_forward_coords01, metro_forward_u8, metro_forward_moments, in every precision;
+ * metro_forward_timed and a metro_forward_upto that runs the whole plan too, outside the timed layers -- also writes, for crop i < n and OUTPUT joint r (head joint permutation[r]), on the stream it is given:
+ *   d_xy_out fp32 [max_n, n_joints_out, S, S]:  xy[i, r, y, x] = sum_d p[y, x, d]
+ *   d_z_out  fp32 [max_n, n_joints_out, D]:     z[i, r, d]     = sum_{y, x} p[y, x, d]
+ * Their expectations on the soft-argmax grids (fp32 linspace(0,1,.)) are the coords01 of the same call.  Rows n .. max_n - 1 are
+ * not touched.  Optional forward outputs are added this way: buffers bound to the plan, written by the existing entries -- no
+ * new launching entry, neither function has a stream parameter.
+ * Binding is HOST state: a forward reads the pointers when it enqueues, so rebinding (or unbinding: all three pointers NULL and
+ * max_n 0) between two enqueues needs no synchronisation; the buffers must stay alive until the forwards enqueued while they
+ * were bound have run.  Anything but the unbind call is checked in full: three non-NULL pointers, the scratch 16-byte aligned,
+ * max_n in [1, the plan's max_batch].  d_scratch: metro_plan_heatmaps_scratch_bytes(plan, max_n) bytes (-1 for a bad argument);
+ * on f16 plans whose head keeps the logits on chip it receives them as fp32 (the head kernels' layer-dump store), else the
+ * logits are read from the workspace.
+ * While bound: a forward with n > max_n returns METRO_ERR_INVALID_ARG before any launch; forwards make PLAIN launches -- the
+ * hipGraph cache (metro_plan_set_graph_max_batch) does not serve them, as it does not serve metro_forward_u8; three launches
+ * follow the finalize launch (heat_partial, heat_fold, heat_xy: csrc/heat_marginals.hip).  Poses, coords01, covariance, peak
+ * and status words keep the bits of the unbound call.  Unbound, a forward enqueues exactly the kernels it always did.
+ * Arithmetic: per-joint maximum and normaliser first, then p = exp(l - max) / sum.  All sums (tile sums of exponentials, their
+ * folds, the sums over D and over pixels) are fp32 on f16 plans and fp64 on f32, f32m and f64 plans, in a fixed order; each
+ * output is rounded to fp32 once.
+ * Non-finite values: a joint one of whose logits is NaN or +Inf gets NaN in all its rows of both outputs (its normaliser is
+ * NaN); the crop's other joints and every other crop are not affected by it, and the crop's pose, status word and
+ * METRO_ERR_NONFINITE are those of the unbound call.  A -Inf logit is a voxel of weight zero, as in the soft-argmax. */
+int64_t metro_plan_heatmaps_scratch_bytes(const MetroPlan* plan, int32_t max_n);
+int  metro_plan_bind_heatmaps(MetroPlan* plan, float* d_xy_out, float* d_z_out, void* d_scratch, int32_t max_n);
 /* Same, stopping after layer `last_layer` (inclusive) so tests can read that layer's output at
  * MetroLayerInfo.out_offset in the workspace.  d_poses_out may be NULL if the finalize layer
  * is not reached. */

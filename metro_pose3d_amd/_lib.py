@@ -143,6 +143,8 @@ SIGNATURES = {
     'metro_forward_u8': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     'metro_forward_status': (C.c_int, [_P, _P, C.c_int32, _P, C.POINTER(C.c_int32)]),
     'metro_plan_status_offset': (C.c_int64, [_P]),
+    'metro_plan_heatmaps_scratch_bytes': (C.c_int64, [_P, C.c_int32]),
+    'metro_plan_bind_heatmaps': (C.c_int, [_P, _P, _P, _P, C.c_int32]),
     'metro_forward_upto': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32]),
     'metro_forward_timed': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_float)]),
     'metro_conv_f16': (C.c_int, [C.POINTER(MetroConvDesc), _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -14,8 +14,9 @@ namespace {
 // `coords01` (optional): the finalize launch also writes the soft-argmax coordinates in [0,1] there (metro_forward_coords01).
 // `images_u8` (metro_forward_u8): `images` points to uint8 crops; the layer that reads them runs the uint8 form of its kernel.
 // `mo` (metro_forward_moments): its scratch selects the MOMENTS instantiations of the head / soft-argmax launches.
+// `head_logits` (a forward with heat-map buffers bound): where the one-launch head also writes its fp32 logits, as for a dump.
 int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* images, int n, float* poses, char* ws, hipStream_t stream, bool dump,
-                 float* coords01 = nullptr, bool images_u8 = false, const MomentsOut& mo = MomentsOut{}) {
+                 float* coords01 = nullptr, bool images_u8 = false, const MomentsOut& mo = MomentsOut{}, float* head_logits = nullptr) {
     const Layer& L = p->layers[li];
     auto slot_ptr = [&](int slot) -> void* {
         if (slot == S_IMAGES) return const_cast<float*>(images);
@@ -41,7 +42,7 @@ int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* 
             ConvFused f;
             switch (L.form) {
                 case LayerForm::Head: {
-                    float* logits_dump = dump ? static_cast<float*>(out) : nullptr;
+                    float* logits_dump = dump ? static_cast<float*>(out) : head_logits;
                     return launch_head_f16(in, w, bias, prm(L.main.scale), prm(L.main.shift), n, L.cd.c_in, L.cd.c_out, p->spec.n_joints_head,
                                            p->spec.depth, L.cd.h_in, static_cast<float*>(slot_ptr(S_PART)), logits_dump, stream,
                                            static_cast<float*>(mo.scratch));
@@ -116,6 +117,13 @@ int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_
     char* ws = static_cast<char*>(ws_);
     const int nl = (int)p->layers.size();
     if (last_layer < 0 || last_layer >= nl) last_layer = nl - 1;
+    // heat-map buffers bound (metro_plan_bind_heatmaps): a forward that runs the whole plan also writes the marginals
+    const bool heat = p->heat.scratch != nullptr && last_layer == nl - 1;
+    const int side = p->spec.proc_side / p->spec.stride;
+    METRO_CHECK_ARG(!heat || n <= p->heat.max_n, "batch %d exceeds the %d crops the bound heat-map buffers hold (metro_plan_bind_heatmaps)",
+                    n, p->heat.max_n);
+    float* head_logits = heat && p->head_fused
+        ? heat_marginals_scratch_logits(p->heat.scratch, p->heat.max_n, side, p->spec.n_joints_head, p->spec.depth) : nullptr;
 
     std::vector<hipEvent_t> ev;
     if (ms_out) {
@@ -125,9 +133,13 @@ int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_
     int st = METRO_OK;
     for (int li = 0; li <= last_layer && st == METRO_OK; ++li) {
         if (ms_out) METRO_HIP_CHECK(hipEventRecord(ev[2 * li], stream));
-        st = launch_layer(p, p->d_params, li, images, n, poses, ws, stream, li == last_layer && li + 1 < nl, coords01, images_u8, mo);
+        st = launch_layer(p, p->d_params, li, images, n, poses, ws, stream, li == last_layer && li + 1 < nl, coords01, images_u8, mo, head_logits);
         if (ms_out) METRO_HIP_CHECK(hipEventRecord(ev[2 * li + 1], stream));
     }
+    if (heat && st == METRO_OK)
+        st = launch_heat_marginals(head_logits ? head_logits : static_cast<void*>(ws + p->slot_offset[S_LOGITS]),
+                                   p->spec.precision == METRO_PREC_F32M ? 1 : p->spec.precision, n, p->heat.max_n, p->spec, p->heat.scratch,
+                                   p->heat.xy, p->heat.z, stream);
     if (ms_out) {
         if (st == METRO_OK) {
             METRO_HIP_CHECK(hipEventSynchronize(ev.back()));
@@ -176,6 +188,27 @@ int metro_plan_bind_params(MetroPlan* plan, const void* d_param_blob) {
     return METRO_OK;
 }
 
+int64_t metro_plan_heatmaps_scratch_bytes(const MetroPlan* plan, int32_t max_n) {
+    if (plan == nullptr || max_n < 1 || max_n > plan->max_batch) return -1;
+    return heat_marginals_scratch_bytes(max_n, plan->spec.proc_side / plan->spec.stride, plan->spec.n_joints_head, plan->spec.depth,
+                                        plan->head_fused);
+}
+
+int metro_plan_bind_heatmaps(MetroPlan* plan, float* d_xy_out, float* d_z_out, void* d_scratch, int32_t max_n) {
+    METRO_CHECK_ARG(plan != nullptr, "metro_plan_bind_heatmaps: plan is NULL");
+    if (d_xy_out == nullptr && d_z_out == nullptr && d_scratch == nullptr && max_n == 0) {       // unbind
+        plan->heat.xy = plan->heat.z = nullptr; plan->heat.scratch = nullptr; plan->heat.max_n = 0;
+        return METRO_OK;
+    }
+    METRO_CHECK_ARG(d_xy_out != nullptr && d_z_out != nullptr && d_scratch != nullptr,
+                    "metro_plan_bind_heatmaps: xy_out, z_out and the scratch go together (all three, or all NULL with max_n 0 to unbind)");
+    METRO_CHECK_ARG(max_n >= 1 && max_n <= plan->max_batch, "metro_plan_bind_heatmaps: max_n %d outside [1, %d]", max_n, plan->max_batch);
+    METRO_CHECK_ARG(((uintptr_t)d_scratch & 15) == 0 && ((uintptr_t)d_xy_out & 3) == 0 && ((uintptr_t)d_z_out & 3) == 0,
+                    "metro_plan_bind_heatmaps: the scratch must be 16-byte aligned, the outputs 4-byte aligned");
+    plan->heat.xy = d_xy_out; plan->heat.z = d_z_out; plan->heat.scratch = d_scratch; plan->heat.max_n = max_n;
+    return METRO_OK;
+}
+
 int metro_plan_set_graph_max_batch(MetroPlan* plan, int32_t max_batch_for_graphs) {
     METRO_CHECK_ARG(plan != nullptr && max_batch_for_graphs >= 0, "metro_plan_set_graph_max_batch: bad argument");
     plan->graph_max_batch = max_batch_for_graphs;
@@ -185,7 +218,8 @@ int metro_plan_set_graph_max_batch(MetroPlan* plan, int32_t max_batch_for_graphs
 static int forward_impl(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out, float* d_coords01,
                         void* d_workspace, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (plan == nullptr || n > plan->graph_max_batch || n < 1)
+    // heat-map buffers bound: plain launches, the captured forwards do not write them
+    if (plan == nullptr || n > plan->graph_max_batch || n < 1 || plan->heat.scratch != nullptr)
         return run_layers(plan, d_images_nhwc, n, d_poses_out, d_workspace, stream, -1, nullptr, d_coords01);
     // small batches are launch-latency bound (57 dependent launches): replay a captured hipGraph
     GraphEntry* hit = nullptr;

@@ -492,6 +492,13 @@ int launch_softargmax(const void* logits, const SoftArgmaxArgs& a, int precise, 
 int launch_softargmax_finalize(const float* partials, const SoftArgmaxArgs& a, int slabs, float* poses_out,
                                hipStream_t stream, float* coords01_out = nullptr, int32_t* status = nullptr,
                                const MomentsOut& mo = MomentsOut{});
+// Heat-map marginals of a bound forward (heat_marginals.hip): xy [n][J_out][S][S] and z [n][J_out][D] from the logits
+// (fp32, or fp64 with precise == 2; precise as launch_softargmax).  `scratch`: heat_marginals_scratch_bytes(max_n, ...) bytes;
+// with_logits plans (the one-launch head) also keep the head's fp32 logits there, at heat_marginals_scratch_logits.
+int64_t heat_marginals_scratch_bytes(int n, int side, int n_joints_head, int depth, bool with_logits);
+float* heat_marginals_scratch_logits(void* scratch, int max_n, int side, int n_joints_head, int depth);
+int launch_heat_marginals(const void* logits, int precise, int n, int max_n, const MetroSpec& spec, void* scratch, float* xy_out,
+                          float* z_out, hipStream_t stream);
 // the volumetric head in one launch (head_f16.hip): postnorm prologue + logits GEMM + per-joint softmax statistics
 bool head_f16_supported(int c_in, int c_head, int n_joints, int depth, int side);
 int head_f16_slabs(int side);               // records per image the partials slot must hold

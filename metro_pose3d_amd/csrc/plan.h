@@ -70,4 +70,7 @@ struct MetroPlan {
     int64_t workspace_bytes = 0, param_bytes = 0;
     const char* d_params = nullptr;
     double flops_per_image = 0.0;
+    // metro_plan_bind_heatmaps: host state a forward reads when it enqueues (scratch == nullptr: nothing bound)
+    struct { float* xy = nullptr; float* z = nullptr; void* scratch = nullptr; int max_n = 0; } heat;
+    bool head_fused = false;             // the logits stay on chip (LayerForm::Head)
 };

@@ -481,6 +481,7 @@ int build_plan(MetroPlan* p) {
     // fp16 mode: the logits stay on chip (volumetric.py:227-235 starts in the GEMM's epilogue)
     const bool head_fused = fast && head_f16_supported(cur_c, c_head, sp.n_joints_head, sp.depth, cur_side);
     if (head_fused) logits.form = LayerForm::Head;
+    p->head_fused = head_fused;
     p->layers.push_back(logits);
 
     // ---- soft-argmax + decode ---------------------------------------------------------------

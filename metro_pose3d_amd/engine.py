@@ -88,6 +88,8 @@ class Engine:
         self._ws = None
         self._u8_f32 = None
         self._moments = None
+        self._heat = None
+        self.heat_chunk = None       # crops per forward of a call with heat-map outputs (None: from HEAT_SCRATCH_CAP)
         if params is not None:
             if device is None:
                 if not torch.cuda.is_available():
@@ -187,9 +189,50 @@ class Engine:
                                               C.c_void_p(stream)), 'metro_images_u8_to_f32')
         return out
 
+    def heat_shapes(self, n: int):
+        """Shapes of the heat-map marginals of n crops: xy (n, Jout, S, S) and z (n, Jout, D)."""
+        s, j = self.spec.heatmap_side, self.spec.skeleton.n_out
+        return (n, j, s, s), (n, j, self.spec.depth)
+
+    def _heat_chunk(self) -> int:
+        """Crops per bound forward: `heat_chunk` if set, else as many as keep the scratch within HEAT_SCRATCH_CAP bytes."""
+        if self.heat_chunk is not None:
+            return max(1, min(int(self.heat_chunk), self.max_batch))
+        k = self.max_batch
+        while k > 1 and int(self.lib.metro_plan_heatmaps_scratch_bytes(self._plan, k)) > self.HEAT_SCRATCH_CAP:
+            k = (k + 1) // 2
+        return k
+
+    def _forward_heat(self, images, out, coords01, cov01, peak, heat_xy, heat_z) -> torch.Tensor:
+        """forward() with heat-map buffers: binds them to the plan chunk by chunk (host state, read at enqueue), runs the plain
+        forward on each chunk and unbinds.  The status words of every chunk are put back so that status_words(n) is the call's."""
+        n, k = images.shape[0], self._heat_chunk()
+        nb = int(self.lib.metro_plan_heatmaps_scratch_bytes(self._plan, k))
+        if self._heat is None or self._heat.numel() < nb:
+            self._heat = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        part = lambda t, i, m: None if t is None else t[i:i + m]
+        words = []
+        try:
+            for i in range(0, n, k):
+                m = min(k, n - i)
+                check(self.lib.metro_plan_bind_heatmaps(self._plan, C.c_void_p(heat_xy[i:i + m].data_ptr()),
+                                                        C.c_void_p(heat_z[i:i + m].data_ptr()), C.c_void_p(self._heat.data_ptr()), k),
+                      'metro_plan_bind_heatmaps')
+                self.forward(images[i:i + m], out[i:i + m], part(coords01, i, m), part(cov01, i, m), part(peak, i, m))
+                if n > k:
+                    words.append(self.status_words(m).clone())
+        finally:
+            check(self.lib.metro_plan_bind_heatmaps(self._plan, None, None, None, 0), 'metro_plan_bind_heatmaps')
+        if words:
+            self.status_words(n).copy_(torch.cat(words))
+        return out
+
+    HEAT_SCRATCH_CAP = 1 << 30
+
     def forward(self, images: torch.Tensor, out: Optional[torch.Tensor] = None,
                 coords01: Optional[torch.Tensor] = None, cov01: Optional[torch.Tensor] = None,
-                peak: Optional[torch.Tensor] = None) -> torch.Tensor:
+                peak: Optional[torch.Tensor] = None, heat_xy: Optional[torch.Tensor] = None,
+                heat_z: Optional[torch.Tensor] = None) -> torch.Tensor:
         """images fp32 [n,256,256,3] on the plan's device -> poses fp32 [n,Jout,3] (mm).  Enqueued
         on torch's current stream; no synchronisation.  `coords01`: an fp32 [n, J_head, 3] device tensor that also receives
         the soft-argmax coordinates in [0,1] (head order; metro_forward_coords01: the same poses, from the same launches).
@@ -199,19 +242,33 @@ class Engine:
         covariance (xx, yy, zz, xy, xz, yz in the units of coords01) and peak probability, head order -- the spread of the
         joint's own softmax distribution in the crop's virtual-camera axes, not of the root-relative pose
         (metro_forward_moments: the same launch count, the same poses and coords01).  With both None the call goes to the
-        entries it always went to."""
+        entries it always went to.
+        `heat_xy` / `heat_z` (together): fp32 [n, Jout, S, S] and [n, Jout, D] device tensors (heat_shapes) that receive every
+        output joint's heat-map marginals, xy[i, r, y, x] = sum_d p and z[i, r, d] = sum_{y,x} p of its softmax volume
+        (metro_plan_bind_heatmaps: the same entries write them from the logits of the same forward; every other output keeps
+        its bits).  The engine owns the scratch (the one-launch head's fp32 logits: S * S * D * J_head * 4 bytes a crop).  Only
+        where that would pass HEAT_SCRATCH_CAP for max_batch crops -- or where `heat_chunk` is set -- the call is made of
+        forwards of at most that many crops each; the kernels a forward dispatches follow its batch, so all outputs are then
+        those of Engine.forward on those chunks, which need not be the bits of one forward of all n crops."""
         images = self._check_images(images)
         n = images.shape[0]
         if (cov01 is None) != (peak is None):
             raise ValueError('cov01 and peak go together: pass both or neither')
+        if (heat_xy is None) != (heat_z is None):
+            raise ValueError('heat_xy and heat_z go together: pass both or neither')
         if cov01 is not None:
             self._check_out('cov01', cov01, (n, self.spec.skeleton.n_head, 6))
             self._check_out('peak', peak, (n, self.spec.skeleton.n_head))
+        if heat_xy is not None:
+            self._check_out('heat_xy', heat_xy, self.heat_shapes(n)[0])
+            self._check_out('heat_z', heat_z, self.heat_shapes(n)[1])
         if out is None:
             out = torch.empty((n, self.spec.skeleton.n_out, 3), dtype=torch.float32, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         if coords01 is not None:
             self._check_coords01(coords01, n)
+        if heat_xy is not None:
+            return self._forward_heat(images, out, coords01, cov01, peak, heat_xy, heat_z)
         if cov01 is not None:
             u8 = images.dtype == torch.uint8 and self.precision == 'f16'
             if images.dtype == torch.uint8 and not u8:

@@ -100,8 +100,15 @@ class PoseUncertainty(NamedTuple):
     peak: torch.Tensor           # float32 [n, Jout]: its largest voxel probability, in (0, 1]
 
 
+class Heatmaps(NamedTuple):
+    """Per-joint heat-map marginals (estimate_pose(..., return_heatmaps=True)), output joint order: every joint's softmax
+    distribution p over its S x S x D volume, summed over depth and over the image plane."""
+    xy: torch.Tensor             # float32 [n, Jout, S, S]: xy[i, r, y, x] = sum_d p[y, x, d]
+    z: torch.Tensor              # float32 [n, Jout, D]:    z[i, r, d] = sum_{y,x} p[y, x, d]
+
+
 def estimate_pose(images_tensor, model_path, precision: Optional[str] = None, check_finite: Optional[bool] = None,
-                  shard: Optional[bool] = None, group=None, return_uncertainty: bool = False):
+                  shard: Optional[bool] = None, group=None, return_uncertainty: bool = False, return_heatmaps: bool = False):
     """images [N,256,256,3] float32 in [0,1] -> (poses [N,Jout,3] mm, joint_edges, joint_names).
 
     return_uncertainty=True adds a fourth element, PoseUncertainty(covariance [N,Jout,3,3] mm^2, peak [N,Jout]): every joint's
@@ -111,6 +118,13 @@ def estimate_pose(images_tensor, model_path, precision: Optional[str] = None, ch
     part of heatmap_to_metric -- not the covariance of the root-relative difference the poses are.  Computed by the same
     launches as the poses (metro_forward_moments: the logits never reach HBM), which stay bit for bit those of the plain
     call; sharded calls gather it with the poses in the same collective.
+
+    return_heatmaps=True appends Heatmaps(xy [N,Jout,S,S], z [N,Jout,D]) (after the uncertainty when both are asked): the
+    marginals of every joint's softmax volume, the heat-map the reference's net_output_to_heatmap_and_coords returns next to
+    the coordinates.  The mean and covariance of a two-peaked joint (left / right confusion, a second person in the crop) say
+    only "between" and "wide"; the map shows both peaks.  Written by the same forwards from their own logits
+    (metro_plan_bind_heatmaps); the poses and the uncertainty keep their bits, uint8 crops and every precision are served, and
+    sharded calls gather the maps with the poses in the same collective.
 
     uint8 images (RGB bytes, as a JPEG decoder or the crop warp leaves them) are accepted as they are: byte b stands for the
     float32 value b / 255 (normalize01, reference improc.py:56-61) and the result has the bits of the float32 call on those
@@ -139,14 +153,14 @@ def estimate_pose(images_tensor, model_path, precision: Optional[str] = None, ch
     the collective.  The screen reads the words of the immediately preceding forward on the engine's workspace and stream: one
     caller per cached engine at a time (an Engine is not thread-safe, like the C plan it wraps)."""
     res = _estimate_pose(images_tensor, model_path, precision, check_finite, shard, group,
-                         'placed' if return_uncertainty else None)
-    return res if return_uncertainty else res[:3]
+                         'placed' if return_uncertainty else None, heatmaps=bool(return_heatmaps))
+    return res[:3] + ((res[3],) if return_uncertainty else ()) + ((res[4],) if return_heatmaps else ())
 
 
-def _estimate_pose(images_tensor, model_path, precision, check_finite, shard, group, uncertainty):
+def _estimate_pose(images_tensor, model_path, precision, check_finite, shard, group, uncertainty, heatmaps=False):
     """estimate_pose's body -> (poses, joint_edges, joint_names, uncertainty): None, PoseUncertainty ('placed'), or, for the
     frames chain, which rotates and averages them itself, the forward's own (cov01 [N,J_head,6], peak [N,J_head]) ('head':
-    local calls only)."""
+    local calls only).  `heatmaps`: a fifth element, Heatmaps."""
     if precision is None:
         precision = os.environ.get('METRO_PRECISION', 'f16')
     if check_finite is None:
@@ -177,13 +191,15 @@ def _estimate_pose(images_tensor, model_path, precision, check_finite, shard, gr
     # collective), a wrong image shape (ValueError on every rank alike), or a sticky HIP error after which no device tensor can
     # be allocated under backend `nccl` (the process group's own timeout ends the other ranks).
     status, err, eng, poses, n_out = 0, None, None, None, None
-    cov01 = peak = None
-    width = 13 if uncertainty == 'placed' else 3          # gathered row: pose (3) + covariance (9) + peak (1)
+    cov01 = peak = heat_xy = heat_z = None
+    width = 13 if uncertainty == 'placed' else 3          # gathered row: pose (3) + covariance (9) + peak (1) [+ xy (S * S) + z (D)]
+    heat_dims = None                                      # (S, D) once the spec is known
     with (torch.cuda.device(device) if device.type == 'cuda' else contextlib.nullcontext()):
         try:
             eng = _engine_for(model_path, precision, device, max(end - begin, 1))
             s = eng.spec.proc_side
             n_out = eng.spec.skeleton.n_out
+            heat_dims = (eng.spec.heatmap_side, eng.spec.depth)
             if images_tensor.dim() != 4 or tuple(images_tensor.shape[1:]) != (s, s, 3):
                 raise _ShapeError(f'images must be NHWC [N,{s},{s},3] (reference main.py:109-110), got '
                                   f'{tuple(images_tensor.shape)}')
@@ -192,13 +208,17 @@ def _estimate_pose(images_tensor, model_path, precision, check_finite, shard, gr
             if uncertainty:
                 cov01 = torch.empty((end - begin, eng.spec.skeleton.n_head, 6), dtype=torch.float32, device=device)
                 peak = torch.empty((end - begin, eng.spec.skeleton.n_head), dtype=torch.float32, device=device)
+            if heatmaps:
+                xy_shape, z_shape = eng.heat_shapes(end - begin)
+                heat_xy = torch.empty(xy_shape, dtype=torch.float32, device=device)
+                heat_z = torch.empty(z_shape, dtype=torch.float32, device=device)
             bad = None
             for i in range(0, end - begin, eng.max_batch):
                 k = min(eng.max_batch, end - begin - i)
-                if uncertainty:
-                    eng.forward(images[i:i + k], out=poses[i:i + k], cov01=cov01[i:i + k], peak=peak[i:i + k])
-                else:
-                    eng.forward(images[i:i + k], out=poses[i:i + k])
+                kw = dict(cov01=cov01[i:i + k], peak=peak[i:i + k]) if uncertainty else {}
+                if heatmaps:
+                    kw.update(heat_xy=heat_xy[i:i + k], heat_z=heat_z[i:i + k])
+                eng.forward(images[i:i + k], out=poses[i:i + k], **kw)
                 if check_finite:       # folded on the device after every chunk: ONE synchronisation per call, below
                     cnt = eng.status_words(k).ne(0).sum()
                     bad = cnt if bad is None else bad + cnt
@@ -209,6 +229,8 @@ def _estimate_pose(images_tensor, model_path, precision, check_finite, shard, gr
                 else:
                     cov, pk = poses.new_empty((0, n_out, 3, 3)), poses.new_empty((0, n_out))
                 poses = torch.cat([poses, cov.reshape(-1, n_out, 9), pk[..., None]], dim=2)
+            if heatmaps:
+                poses = torch.cat([poses, heat_xy.reshape(end - begin, n_out, heat_dims[0] ** 2), heat_z], dim=2)
             if bad is not None:
                 status = int(bad.item())                                 # the call's one stream synchronisation
         except _ShapeError:
@@ -220,7 +242,10 @@ def _estimate_pose(images_tensor, model_path, precision, check_finite, shard, gr
                 if err is not None:
                     # join with a FRESH tensor that only carries the status row: `poses` may be unallocated or hold garbage
                     if n_out is None:
-                        n_out = load_model(model_path)[0].skeleton.n_out       # raises if the file is unreadable (every rank alike)
+                        spec = load_model(model_path)[0]                        # raises if the file is unreadable (every rank alike)
+                        n_out, heat_dims = spec.skeleton.n_out, (spec.heatmap_side, spec.depth)
+                    if heatmaps:
+                        width += heat_dims[0] * heat_dims[0] + heat_dims[1]
                     on_host = torch.distributed.get_backend(group) != 'nccl'
                     poses = torch.zeros((end - begin, n_out, width), dtype=torch.float32, device='cpu' if on_host else device)
                 poses, statuses = _gather_shards(poses, n, group, status)
@@ -242,12 +267,21 @@ def _estimate_pose(images_tensor, model_path, precision, check_finite, shard, gr
     sk = eng.spec.skeleton
     names = np.empty(sk.n_out, dtype=object)
     names[:] = sk.names_bytes()
+    heat = None
+    if heatmaps:
+        side, depth = heat_dims
+        base = 13 if uncertainty == 'placed' else 3
+        heat = Heatmaps(poses[..., base:base + side * side].reshape(-1, sk.n_out, side, side).contiguous(),
+                        poses[..., base + side * side:].contiguous())
+        poses = poses[..., :base]
     unc = None
     if uncertainty == 'placed':
         unc = PoseUncertainty(poses[..., 3:12].reshape(-1, sk.n_out, 3, 3).contiguous(), poses[..., 12].contiguous())
         poses = poses[..., :3].contiguous()
     elif uncertainty == 'head':
         unc = (cov01, peak)
+    if heatmaps:
+        return poses.contiguous(), sk.edges_array(), names, unc, heat
     return poses, sk.edges_array(), names, unc
 
 
@@ -309,8 +343,13 @@ def main(argv=None):
     parser.add_argument('--uncertainty', action='store_true',
                         help='also print, per joint, the standard deviations in mm of its heat-map along the three axes and its '
                              'peak probability')
+    parser.add_argument('--heatmaps', type=str, default=None, metavar='OUT.npz',
+                        help='also write every joint\'s heat-map marginals of the crop call to this .npz: xy [1,J,S,S] and '
+                             'z [1,J,D] (output joint order), next to the poses and the joint names')
     opts = parser.parse_args(argv)
     if opts.frame:
+        if opts.heatmaps:
+            parser.error('--heatmaps goes with the crop call (--image), not with --frame')
         return _main_frame(opts)
     if opts.crop_dtype:
         parser.error('--crop-dtype goes with --frame')
@@ -324,9 +363,13 @@ def main(argv=None):
         from metro_pose3d_amd.synth import make_images
         img = make_images(1)[0]
     images = torch.from_numpy(img[None])
-    poses, edges, names, *unc = estimate_pose(images, opts.model_path, precision=opts.precision,
-                                              return_uncertainty=opts.uncertainty)
+    poses, edges, names, *more = estimate_pose(images, opts.model_path, precision=opts.precision,
+                                               return_uncertainty=opts.uncertainty, return_heatmaps=bool(opts.heatmaps))
+    unc = more[:1] if opts.uncertainty else []
     poses = poses.cpu().numpy()
+    if opts.heatmaps:
+        np.savez(opts.heatmaps, xy=more[-1].xy.cpu().numpy(), z=more[-1].z.cpu().numpy(), poses=poses,
+                 joint_names=np.array([nm.decode() for nm in names]))
     tails = _uncertainty_columns(unc[0], 0) if unc else [''] * len(names)
     for name, p, tail in zip(names, poses[0], tails):
         print(f'{name.decode():>10s}  {p[0]:9.2f} {p[1]:9.2f} {p[2]:9.2f}{tail}')
