@@ -228,6 +228,50 @@ int64_t metro_plan_status_offset(const MetroPlan* plan);
  * METRO_ERR_NONFINITE are those of the unbound call.  A -Inf logit is a voxel of weight zero, as in the soft-argmax. */
 int64_t metro_plan_heatmaps_scratch_bytes(const MetroPlan* plan, int32_t max_n);
 int  metro_plan_bind_heatmaps(MetroPlan* plan, float* d_xy_out, float* d_z_out, void* d_scratch, int32_t max_n);
+/* ---- per-joint heat-map modes, bound to the plan ----
+ * The mean and covariance of a two-peaked joint say only "between" and "wide", and the marginals above are a picture.  The modes
+ * are numbers a consumer can act on: the K places the joint may be, how much probability each holds and how tight each is.  With
+ * mode buffers bound, every forward entry (the list above) also writes them on the stream it is given, from the logits of the
+ * same forward; the logits never pass through the host.  Definition, for crop i < n and head joint j:
+ *   l[y, x, d] = logits[i, y, x, d * J + j], v = (y * S + x) * D + d the voxel's linear index, p = exp(l - M_j) / S_j the joint's
+ *   softmax, as the marginals form it.  Parameters: k modes per joint, 1 <= k <= METRO_MAX_MODES, and the window radius,
+ *   0 <= radius <= METRO_MAX_MODE_RADIUS.
+ *   Neighbours of v: the voxels inside the volume that differ from it by at most 1 in each of y, x and d (up to 26).
+ *   Candidates: v is one if l[v] is finite and, for every neighbour u, l[u] < l[v] or (l[u] == l[v] and u > v).  A plateau has one
+ *   candidate, its lowest index; a -Inf voxel is never a candidate.
+ *   Selection: the candidates in order of decreasing l, ties by increasing v; a candidate with max(|dy|, |dx|, |dd|) <= 2 radius to
+ *   a mode already selected is skipped (so the windows of a joint's modes are disjoint and its masses sum to at most 1); stop at
+ *   k modes.  The comparisons are on the logits as stored (fp32; fp64 on f64 plans), never on probabilities: the selected
+ *   voxels are exact in every precision.
+ *   Per mode, with W the voxels within `radius` of the mode in every axis, clipped to the volume:  mass = sum_W p;  peak = p[v];
+ *   coords01 = sum_W p g / mass, g the soft-argmax's own grid (fp32 linspace(0,1,S) for x and y, linspace(0,1,D) for z, order
+ *   x, y, z);  cov01 = the six central second moments of p over W about coords01, divided by mass, in the order (xx, yy, zz, xy,
+ *   xz, yz) and units of metro_forward_moments' cov01.
+ *   Fewer than k modes: the missing ones have voxel -1, mass 0, and NaN in peak, coords01 and cov01.
+ *   Non-finite logits: a joint with a NaN or +Inf logit has, for all k modes, voxel -1 and NaN in every float; no other joint and no
+ *   other crop is affected (the marginals' rule).
+ *   Sums: fp32 on f16 plans, fp64 on f32, f32m and f64 plans, in a fixed order, no atomics; each output is rounded to fp32 once.
+ * Outputs, in OUTPUT joint order (row r, head joint permutation[r]); rows n .. max_n - 1 are not touched:
+ *   d_voxel_out int32 [max_n, n_joints_out, k]
+ *   d_stats_out fp32  [max_n, n_joints_out, k, 11]: mass, peak, coords01 (3), cov01 (6)
+ * Binding is HOST state: a forward reads the pointers when it enqueues, so rebinding (or unbinding: all three pointers NULL and
+ * max_n = k = radius = 0) between two enqueues needs no synchronisation; the buffers must stay alive until the forwards enqueued
+ * while they were bound have run.  Anything but the unbind call is checked in full: three non-NULL pointers, the scratch 16-byte
+ * and the outputs 4-byte aligned, max_n in [1, the plan's max_batch], k and radius in their ranges.  d_scratch:
+ * metro_plan_modes_scratch_bytes(plan, max_n) bytes (-1 for a bad argument); on f16 plans whose head keeps the logits on chip it
+ * receives them as fp32 (the head kernels' layer-dump store), else the logits are read from the workspace.
+ * While bound: a forward with n > max_n returns METRO_ERR_INVALID_ARG before any launch; forwards make PLAIN launches (the
+ * hipGraph cache does not serve them); one launch (heat_modes: csrc/heat_modes.hip) follows the finalize launch, and the three
+ * marginal launches when those are bound.  Heat-maps and modes may be bound together: the head's one fp32 logits store then goes
+ * to the heat-map scratch and the modes read it there; each output is bit for bit what it is when bound alone.  A shape whose
+ * volume does not fit the kernel's LDS (S * S * D flag bytes and three y-rows of logits in 64 KB) returns METRO_ERR_UNSUPPORTED.
+ * Poses, coords01, covariance, peak and status words keep the bits of the unbound call.  Unbound, a forward enqueues exactly the
+ * kernels it always did. */
+#define METRO_MAX_MODES 8
+#define METRO_MAX_MODE_RADIUS 3
+int64_t metro_plan_modes_scratch_bytes(const MetroPlan* plan, int32_t max_n);
+int  metro_plan_bind_modes(MetroPlan* plan, int32_t* d_voxel_out, float* d_stats_out, void* d_scratch,
+                           int32_t max_n, int32_t k, int32_t radius);
 /* Same, stopping after layer `last_layer` (inclusive) so tests can read that layer's output at
  * MetroLayerInfo.out_offset in the workspace.  d_poses_out may be NULL if the finalize layer
  * is not reached. */

@@ -93,6 +93,8 @@ class MetroPlacement(C.Structure):
 
 
 METRO_MAX_VIEWS = 32
+METRO_MAX_MODES = 8            # metro_plan_bind_modes: modes per joint
+METRO_MAX_MODE_RADIUS = 3
 METRO_TRI_UNIFORM, METRO_TRI_COVARIANCE = 0, 1
 METRO_MATCH_MAX_BOXES = 128
 METRO_SMOOTH_FILTER, METRO_SMOOTH_RTS = 0, 1
@@ -145,6 +147,8 @@ SIGNATURES = {
     'metro_plan_status_offset': (C.c_int64, [_P]),
     'metro_plan_heatmaps_scratch_bytes': (C.c_int64, [_P, C.c_int32]),
     'metro_plan_bind_heatmaps': (C.c_int, [_P, _P, _P, _P, C.c_int32]),
+    'metro_plan_modes_scratch_bytes': (C.c_int64, [_P, C.c_int32]),
+    'metro_plan_bind_modes': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
     'metro_forward_upto': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32]),
     'metro_forward_timed': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_float)]),
     'metro_conv_f16': (C.c_int, [C.POINTER(MetroConvDesc), _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -14,7 +14,7 @@ namespace {
 // `coords01` (optional): the finalize launch also writes the soft-argmax coordinates in [0,1] there (metro_forward_coords01).
 // `images_u8` (metro_forward_u8): `images` points to uint8 crops; the layer that reads them runs the uint8 form of its kernel.
 // `mo` (metro_forward_moments): its scratch selects the MOMENTS instantiations of the head / soft-argmax launches.
-// `head_logits` (a forward with heat-map buffers bound): where the one-launch head also writes its fp32 logits, as for a dump.
+// `head_logits` (a forward with heat-map or mode buffers bound): where the one-launch head also writes its fp32 logits, as for a dump.
 int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* images, int n, float* poses, char* ws, hipStream_t stream, bool dump,
                  float* coords01 = nullptr, bool images_u8 = false, const MomentsOut& mo = MomentsOut{}, float* head_logits = nullptr) {
     const Layer& L = p->layers[li];
@@ -122,8 +122,15 @@ int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_
     const int side = p->spec.proc_side / p->spec.stride;
     METRO_CHECK_ARG(!heat || n <= p->heat.max_n, "batch %d exceeds the %d crops the bound heat-map buffers hold (metro_plan_bind_heatmaps)",
                     n, p->heat.max_n);
-    float* head_logits = heat && p->head_fused
-        ? heat_marginals_scratch_logits(p->heat.scratch, p->heat.max_n, side, p->spec.n_joints_head, p->spec.depth) : nullptr;
+    // mode buffers bound (metro_plan_bind_modes): the same; the head's one logits store goes to the heat-map scratch when both are bound
+    const bool modes = p->modes.scratch != nullptr && last_layer == nl - 1;
+    METRO_CHECK_ARG(!modes || n <= p->modes.max_n, "batch %d exceeds the %d crops the bound mode buffers hold (metro_plan_bind_modes)",
+                    n, p->modes.max_n);
+    float* head_logits = nullptr;
+    if (heat && p->head_fused)
+        head_logits = heat_marginals_scratch_logits(p->heat.scratch, p->heat.max_n, side, p->spec.n_joints_head, p->spec.depth);
+    else if (modes && p->head_fused)
+        head_logits = static_cast<float*>(p->modes.scratch);
 
     std::vector<hipEvent_t> ev;
     if (ms_out) {
@@ -140,6 +147,10 @@ int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_
         st = launch_heat_marginals(head_logits ? head_logits : static_cast<void*>(ws + p->slot_offset[S_LOGITS]),
                                    p->spec.precision == METRO_PREC_F32M ? 1 : p->spec.precision, n, p->heat.max_n, p->spec, p->heat.scratch,
                                    p->heat.xy, p->heat.z, stream);
+    if (modes && st == METRO_OK)
+        st = launch_heat_modes(head_logits ? head_logits : static_cast<void*>(ws + p->slot_offset[S_LOGITS]),
+                               p->spec.precision == METRO_PREC_F32M ? 1 : p->spec.precision, n, p->modes.max_n, p->spec, p->modes.k,
+                               p->modes.radius, p->modes.voxel, p->modes.stats, stream);
     if (ms_out) {
         if (st == METRO_OK) {
             METRO_HIP_CHECK(hipEventSynchronize(ev.back()));
@@ -209,6 +220,34 @@ int metro_plan_bind_heatmaps(MetroPlan* plan, float* d_xy_out, float* d_z_out, v
     return METRO_OK;
 }
 
+int64_t metro_plan_modes_scratch_bytes(const MetroPlan* plan, int32_t max_n) {
+    if (plan == nullptr || max_n < 1 || max_n > plan->max_batch) return -1;
+    return heat_modes_scratch_bytes(max_n, plan->spec.proc_side / plan->spec.stride, plan->spec.n_joints_head, plan->spec.depth,
+                                    plan->head_fused);
+}
+
+int metro_plan_bind_modes(MetroPlan* plan, int32_t* d_voxel_out, float* d_stats_out, void* d_scratch, int32_t max_n, int32_t k,
+                          int32_t radius) {
+    METRO_CHECK_ARG(plan != nullptr, "metro_plan_bind_modes: plan is NULL");
+    if (d_voxel_out == nullptr && d_stats_out == nullptr && d_scratch == nullptr && max_n == 0 && k == 0 && radius == 0) {      // unbind
+        plan->modes.voxel = nullptr; plan->modes.stats = nullptr; plan->modes.scratch = nullptr;
+        plan->modes.max_n = plan->modes.k = plan->modes.radius = 0;
+        return METRO_OK;
+    }
+    METRO_CHECK_ARG(d_voxel_out != nullptr && d_stats_out != nullptr && d_scratch != nullptr,
+                    "metro_plan_bind_modes: voxel_out, stats_out and the scratch go together (all three, or all NULL with max_n, k and "
+                    "radius 0 to unbind)");
+    METRO_CHECK_ARG(max_n >= 1 && max_n <= plan->max_batch, "metro_plan_bind_modes: max_n %d outside [1, %d]", max_n, plan->max_batch);
+    METRO_CHECK_ARG(k >= 1 && k <= METRO_MAX_MODES, "metro_plan_bind_modes: k %d outside [1, %d]", k, METRO_MAX_MODES);
+    METRO_CHECK_ARG(radius >= 0 && radius <= METRO_MAX_MODE_RADIUS, "metro_plan_bind_modes: radius %d outside [0, %d]", radius,
+                    METRO_MAX_MODE_RADIUS);
+    METRO_CHECK_ARG(((uintptr_t)d_scratch & 15) == 0 && ((uintptr_t)d_voxel_out & 3) == 0 && ((uintptr_t)d_stats_out & 3) == 0,
+                    "metro_plan_bind_modes: the scratch must be 16-byte aligned, the outputs 4-byte aligned");
+    plan->modes.voxel = d_voxel_out; plan->modes.stats = d_stats_out; plan->modes.scratch = d_scratch;
+    plan->modes.max_n = max_n; plan->modes.k = k; plan->modes.radius = radius;
+    return METRO_OK;
+}
+
 int metro_plan_set_graph_max_batch(MetroPlan* plan, int32_t max_batch_for_graphs) {
     METRO_CHECK_ARG(plan != nullptr && max_batch_for_graphs >= 0, "metro_plan_set_graph_max_batch: bad argument");
     plan->graph_max_batch = max_batch_for_graphs;
@@ -218,8 +257,8 @@ int metro_plan_set_graph_max_batch(MetroPlan* plan, int32_t max_batch_for_graphs
 static int forward_impl(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out, float* d_coords01,
                         void* d_workspace, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    // heat-map buffers bound: plain launches, the captured forwards do not write them
-    if (plan == nullptr || n > plan->graph_max_batch || n < 1 || plan->heat.scratch != nullptr)
+    // heat-map or mode buffers bound: plain launches, the captured forwards do not write them
+    if (plan == nullptr || n > plan->graph_max_batch || n < 1 || plan->heat.scratch != nullptr || plan->modes.scratch != nullptr)
         return run_layers(plan, d_images_nhwc, n, d_poses_out, d_workspace, stream, -1, nullptr, d_coords01);
     // small batches are launch-latency bound (57 dependent launches): replay a captured hipGraph
     GraphEntry* hit = nullptr;

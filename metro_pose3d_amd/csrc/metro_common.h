@@ -499,6 +499,11 @@ int64_t heat_marginals_scratch_bytes(int n, int side, int n_joints_head, int dep
 float* heat_marginals_scratch_logits(void* scratch, int max_n, int side, int n_joints_head, int depth);
 int launch_heat_marginals(const void* logits, int precise, int n, int max_n, const MetroSpec& spec, void* scratch, float* xy_out,
                           float* z_out, hipStream_t stream);
+// Heat-map modes of a bound forward (heat_modes.hip): voxel [n][J_out][k] and stats [n][J_out][k][11] from the logits (as above).
+// The kernel needs no scratch; with_logits plans keep the head's fp32 logits in the bound scratch, from its first byte.
+int64_t heat_modes_scratch_bytes(int n, int side, int n_joints_head, int depth, bool with_logits);
+int launch_heat_modes(const void* logits, int precise, int n, int max_n, const MetroSpec& spec, int k, int radius, int32_t* voxel_out,
+                      float* stats_out, hipStream_t stream);
 // the volumetric head in one launch (head_f16.hip): postnorm prologue + logits GEMM + per-joint softmax statistics
 bool head_f16_supported(int c_in, int c_head, int n_joints, int depth, int side);
 int head_f16_slabs(int side);               // records per image the partials slot must hold

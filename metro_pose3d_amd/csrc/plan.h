@@ -72,5 +72,7 @@ struct MetroPlan {
     double flops_per_image = 0.0;
     // metro_plan_bind_heatmaps: host state a forward reads when it enqueues (scratch == nullptr: nothing bound)
     struct { float* xy = nullptr; float* z = nullptr; void* scratch = nullptr; int max_n = 0; } heat;
+    // metro_plan_bind_modes: the same (heat_modes.hip)
+    struct { int32_t* voxel = nullptr; float* stats = nullptr; void* scratch = nullptr; int max_n = 0, k = 0, radius = 0; } modes;
     bool head_fused = false;             // the logits stay on chip (LayerForm::Head)
 };

@@ -89,6 +89,7 @@ class Engine:
         self._u8_f32 = None
         self._moments = None
         self._heat = None
+        self._modes = None
         self.heat_chunk = None       # crops per forward of a call with heat-map outputs (None: from HEAT_SCRATCH_CAP)
         if params is not None:
             if device is None:
@@ -228,6 +229,54 @@ class Engine:
         return out
 
     HEAT_SCRATCH_CAP = 1 << 30
+
+    MODE_STATS = 11          # mass, peak, coords01 (x, y, z), cov01 (xx, yy, zz, xy, xz, yz)
+
+    def forward_modes(self, images: torch.Tensor, k: int = 2, radius: int = 1, out: Optional[torch.Tensor] = None,
+                      coords01: Optional[torch.Tensor] = None, cov01: Optional[torch.Tensor] = None,
+                      peak: Optional[torch.Tensor] = None, heat_xy: Optional[torch.Tensor] = None,
+                      heat_z: Optional[torch.Tensor] = None):
+        """forward() that also returns every output joint's heat-map modes -> (poses, voxel int32 [n, Jout, k], stats fp32
+        [n, Jout, k, 11]): the k places the joint may be (local maxima of its logits, none within 2 * radius voxels of another
+        in every axis, by decreasing logit), `voxel` their linear index (y * S + x) * D + d or -1 for a missing mode, `stats`
+        per mode the mass, peak, coords01 (x, y, z) and cov01 (xx, yy, zz, xy, xz, yz) of the joint's softmax over the window
+        of `radius` voxels around it (metro_plan_bind_modes, include/metro_hip.h, holds the definition).  Binds the two
+        outputs to the plan chunk by chunk (host state, read at enqueue), calls forward() with the other arguments and
+        unbinds; every other output keeps the bits forward() gives it.  The engine owns the scratch; the call is made of
+        several forwards by the rule of the heat-map outputs (HEAT_SCRATCH_CAP, heat_chunk)."""
+        images = self._check_images(images)
+        n, nj = images.shape[0], self.spec.skeleton.n_out
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _lib.METRO_MAX_MODES:
+            raise ValueError(f'k must be an int in [1, {_lib.METRO_MAX_MODES}], got {k!r}')
+        if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= _lib.METRO_MAX_MODE_RADIUS:
+            raise ValueError(f'radius must be an int in [0, {_lib.METRO_MAX_MODE_RADIUS}], got {radius!r}')
+        if out is None:
+            out = torch.empty((n, nj, 3), dtype=torch.float32, device=self.device)
+        else:
+            self._check_out('out', out, (n, nj, 3))
+        voxel = torch.empty((n, nj, k), dtype=torch.int32, device=self.device)
+        stats = torch.empty((n, nj, k, self.MODE_STATS), dtype=torch.float32, device=self.device)
+        step = self._heat_chunk()
+        nb = int(self.lib.metro_plan_modes_scratch_bytes(self._plan, step))
+        if self._modes is None or self._modes.numel() < nb:
+            self._modes = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        part = lambda t, i, m: None if t is None else t[i:i + m]
+        words = []
+        try:
+            for i in range(0, n, step):
+                m = min(step, n - i)
+                check(self.lib.metro_plan_bind_modes(self._plan, C.c_void_p(voxel[i:i + m].data_ptr()),
+                                                     C.c_void_p(stats[i:i + m].data_ptr()), C.c_void_p(self._modes.data_ptr()),
+                                                     step, k, radius), 'metro_plan_bind_modes')
+                self.forward(images[i:i + m], out[i:i + m], part(coords01, i, m), part(cov01, i, m), part(peak, i, m),
+                             part(heat_xy, i, m), part(heat_z, i, m))
+                if n > step:
+                    words.append(self.status_words(m).clone())
+        finally:
+            check(self.lib.metro_plan_bind_modes(self._plan, None, None, None, 0, 0, 0), 'metro_plan_bind_modes')
+        if words:
+            self.status_words(n).copy_(torch.cat(words))
+        return out, voxel, stats
 
     def forward(self, images: torch.Tensor, out: Optional[torch.Tensor] = None,
                 coords01: Optional[torch.Tensor] = None, cov01: Optional[torch.Tensor] = None,

@@ -285,6 +285,107 @@ def _estimate_pose(images_tensor, model_path, precision, check_finite, shard, gr
     return poses, sk.edges_array(), names, unc
 
 
+class Modes(NamedTuple):
+    """Per-joint heat-map modes (estimate_pose_modes), output joint order: the K places a joint may be, how much probability
+    each holds and how tight each is.  A missing mode (fewer than K local maxima far enough apart) has voxel -1, mass 0 and NaN
+    elsewhere; a joint with a NaN or +Inf logit has voxel -1 and NaN everywhere."""
+    poses: torch.Tensor          # float32 [n, Jout, K, 3] mm, in the frame of the call's own poses (relative to the root's MEAN)
+    covariance: torch.Tensor     # float32 [n, Jout, K, 3, 3] mm^2: of the joint's softmax over the mode's window, about its mean
+    mass: torch.Tensor           # float32 [n, Jout, K]: the probability inside the window; a joint's masses sum to at most 1
+    peak: torch.Tensor           # float32 [n, Jout, K]: the probability of the mode's own voxel
+    voxel: torch.Tensor          # int32 [n, Jout, K]: its linear index (y * S + x) * D + d, or -1
+
+
+def modes_to_metric(spec, stats: torch.Tensor, coords01: torch.Tensor, voxel: torch.Tensor) -> Modes:
+    """Engine.forward_modes' stats [n, Jout, K, 11] and voxel, and the same call's coords01 [n, J_head, 3] -> Modes.  Positions:
+    heatmap_to_metric (reference volumetric.py:288-306) of the mode's coords01 minus that of the root joint's mean (the last head
+    joint, tfu3d.py:23-25), so the plain pose is the mass-weighted blend of a joint's modes when they hold all the mass.
+    Covariances: diag(s) Cov01 diag(s) with the linear part of heatmap_to_metric, the scaling of
+    heads.place_covariances(..., coords='crop').  fp64 arithmetic on the fp32 inputs, one rounding per output."""
+    from metro_pose3d_amd.heads import cov6_to_3x3
+    last = spec.proc_side - 1
+    lrc, half = float(last - last % spec.stride - 1), float(spec.stride // 2)
+    box, side = float(spec.box_size_mm), float(spec.proc_side)
+
+    def metric(c):
+        return torch.cat([(c[..., :2] * lrc + half) * box / side, c[..., 2:] * box], dim=-1)
+    st = stats.double()
+    root = metric(coords01.double()[:, -1])                                                # [n, 3]
+    s = torch.tensor([lrc * box / side, lrc * box / side, box], dtype=torch.float64, device=stats.device)
+    cov = cov6_to_3x3(st[..., 5:]) * (s[:, None] * s[None, :])
+    return Modes((metric(st[..., 2:5]) - root[:, None, None, :]).float(), cov.float(), stats[..., 0].contiguous(),
+                 stats[..., 1].contiguous(), voxel)
+
+
+def estimate_pose_modes(images_tensor, model_path, k: int = 2, radius: int = 1, precision: Optional[str] = None,
+                        check_finite: Optional[bool] = None, return_uncertainty: bool = False, return_heatmaps: bool = False,
+                        *, shard: Optional[bool] = None):
+    """estimate_pose that also returns every joint's heat-map modes: estimate_pose's tuple (with the PoseUncertainty and the
+    Heatmaps where asked), and Modes appended last.  For a two-peaked joint (left / right confusion, a second person in the
+    crop) the pose lies between the peaks and at neither; the modes are the k places the joint may be -- local maxima of its
+    logits, none within 2 * radius voxels of another -- each with its probability mass, position and covariance over the window
+    of `radius` voxels around it (metro_plan_bind_modes; Engine.forward_modes).  Written by the same forwards from their own
+    logits; poses, uncertainty and heat-maps keep the bits estimate_pose gives them; uint8 crops and every precision are
+    served.  A local call: sharded calls do not return modes (shard=True raises ValueError)."""
+    if shard:
+        raise ValueError('estimate_pose_modes: sharded calls do not return modes (shard must be None or False)')
+    for name, v, hi in (('k', k, _lib.METRO_MAX_MODES), ('radius', radius, _lib.METRO_MAX_MODE_RADIUS)):
+        if isinstance(v, bool) or not isinstance(v, int) or not (1 if name == 'k' else 0) <= v <= hi:
+            raise ValueError(f'{name} must be an int in [{1 if name == "k" else 0}, {hi}], got {v!r}')
+    if precision is None:
+        precision = os.environ.get('METRO_PRECISION', 'f16')
+    if check_finite is None:
+        check_finite = os.environ.get('METRO_CHECK_FINITE', '1') != '0'
+    if isinstance(images_tensor, np.ndarray):
+        images_tensor = torch.from_numpy(images_tensor)
+    if not isinstance(images_tensor, torch.Tensor):
+        raise ValueError(f'images must be a torch.Tensor or numpy array, got {type(images_tensor)}')
+    if images_tensor.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f'images must be float32 in [0,1] (reference inference.py:18) or uint8 RGB bytes, got {images_tensor.dtype}')
+    device = _resolve_device(images_tensor)
+    n = int(images_tensor.shape[0]) if images_tensor.dim() == 4 else 0
+    with torch.cuda.device(device):
+        eng = _engine_for(model_path, precision, device, max(n, 1))
+        sk, s = eng.spec.skeleton, eng.spec.proc_side
+        if images_tensor.dim() != 4 or tuple(images_tensor.shape[1:]) != (s, s, 3):
+            raise _ShapeError(f'images must be NHWC [N,{s},{s},3] (reference main.py:109-110), got {tuple(images_tensor.shape)}')
+        images = images_tensor.to(device, non_blocking=True).contiguous()
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
+        poses, coords01 = f32(n, sk.n_out, 3), f32(n, sk.n_head, 3)
+        cov01, peak = (f32(n, sk.n_head, 6), f32(n, sk.n_head)) if return_uncertainty else (None, None)
+        heat_xy, heat_z = (f32(*eng.heat_shapes(n)[0]), f32(*eng.heat_shapes(n)[1])) if return_heatmaps else (None, None)
+        part = lambda t, i, m: None if t is None else t[i:i + m]
+        voxels, stats, bad = [], [], None
+        for i in range(0, n, eng.max_batch):
+            m = min(eng.max_batch, n - i)
+            _, vx, st = eng.forward_modes(images[i:i + m], k, radius, poses[i:i + m], coords01[i:i + m], part(cov01, i, m),
+                                          part(peak, i, m), part(heat_xy, i, m), part(heat_z, i, m))
+            voxels.append(vx)
+            stats.append(st)
+            if check_finite:       # folded on the device after every chunk: one synchronisation per call, below
+                cnt = eng.status_words(m).ne(0).sum()
+                bad = cnt if bad is None else bad + cnt
+        if bad is not None and int(bad.item()):
+            raise _lib.NonFiniteError(
+                f'{eng.spec.arch_name} stride {eng.spec.stride} in precision {precision!r}: {int(bad.item())} crops reached the '
+                f'soft-argmax with non-finite statistics' +
+                (' (fp16 storage overflows at 65504: run this model with precision f32m or f64)' if precision == 'f16' else ''))
+        res = [poses, sk.edges_array(), None]
+        names = np.empty(sk.n_out, dtype=object)
+        names[:] = sk.names_bytes()
+        res[2] = names
+        if return_uncertainty:
+            from metro_pose3d_amd.heads import place_covariances
+            res.append(PoseUncertainty(*place_covariances(cov01, peak, eng.spec)) if n else
+                       PoseUncertainty(poses.new_empty((0, sk.n_out, 3, 3)), poses.new_empty((0, sk.n_out))))
+        if return_heatmaps:
+            res.append(Heatmaps(heat_xy, heat_z))
+        vx = torch.cat(voxels) if voxels else torch.empty((0, sk.n_out, k), dtype=torch.int32, device=device)
+        st = torch.cat(stats) if stats else f32(0, sk.n_out, k, Engine.MODE_STATS)
+        res.append(modes_to_metric(eng.spec, st, coords01, vx))
+    return tuple(res)
+
+
 def visualize_pose(image, coords, edges):
     """Stick-figure plot like reference inference.py:46-76 (matplotlib optional)."""
     import matplotlib
@@ -346,10 +447,22 @@ def main(argv=None):
     parser.add_argument('--heatmaps', type=str, default=None, metavar='OUT.npz',
                         help='also write every joint\'s heat-map marginals of the crop call to this .npz: xy [1,J,S,S] and '
                              'z [1,J,D] (output joint order), next to the poses and the joint names')
+    parser.add_argument('--modes', type=str, default=None, metavar='K[,R]',
+                        help='also print, per joint, its heat-map modes that hold a mass of at least 0.05: up to K places the '
+                             'joint may be (window radius R voxels, default 1), each with its mass and position in mm')
     opts = parser.parse_args(argv)
+    modes_kr = None
+    if opts.modes:
+        try:
+            modes_kr = [int(v) for v in opts.modes.split(',')]
+            modes_kr = (modes_kr[0], modes_kr[1] if len(modes_kr) > 1 else 1)
+            if len(opts.modes.split(',')) > 2:
+                raise ValueError(opts.modes)
+        except (ValueError, IndexError):
+            parser.error(f'--modes takes K or K,R (integers), got {opts.modes!r}')
     if opts.frame:
-        if opts.heatmaps:
-            parser.error('--heatmaps goes with the crop call (--image), not with --frame')
+        if opts.heatmaps or opts.modes:
+            parser.error('--heatmaps and --modes go with the crop call (--image), not with --frame')
         return _main_frame(opts)
     if opts.crop_dtype:
         parser.error('--crop-dtype goes with --frame')
@@ -363,8 +476,13 @@ def main(argv=None):
         from metro_pose3d_amd.synth import make_images
         img = make_images(1)[0]
     images = torch.from_numpy(img[None])
-    poses, edges, names, *more = estimate_pose(images, opts.model_path, precision=opts.precision,
-                                               return_uncertainty=opts.uncertainty, return_heatmaps=bool(opts.heatmaps))
+    modes = None
+    if modes_kr:
+        poses, edges, names, *more, modes = estimate_pose_modes(images, opts.model_path, modes_kr[0], modes_kr[1], precision=opts.precision,
+                                                                return_uncertainty=opts.uncertainty, return_heatmaps=bool(opts.heatmaps))
+    else:
+        poses, edges, names, *more = estimate_pose(images, opts.model_path, precision=opts.precision,
+                                                   return_uncertainty=opts.uncertainty, return_heatmaps=bool(opts.heatmaps))
     unc = more[:1] if opts.uncertainty else []
     poses = poses.cpu().numpy()
     if opts.heatmaps:
@@ -373,6 +491,11 @@ def main(argv=None):
     tails = _uncertainty_columns(unc[0], 0) if unc else [''] * len(names)
     for name, p, tail in zip(names, poses[0], tails):
         print(f'{name.decode():>10s}  {p[0]:9.2f} {p[1]:9.2f} {p[2]:9.2f}{tail}')
+    if modes is not None:
+        mass, at = modes.mass[0].cpu().numpy(), modes.poses[0].cpu().numpy()
+        for r, name in enumerate(names):
+            for i in np.flatnonzero(mass[r] >= 0.05):
+                print(f'{name.decode():>10s}  mode {i}: mass {mass[r, i]:.3f} at {at[r, i, 0]:9.2f} {at[r, i, 1]:9.2f} {at[r, i, 2]:9.2f}')
     if opts.plot:
         visualize_pose(img, poses[0], edges).savefig(opts.plot)
 
