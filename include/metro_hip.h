@@ -272,6 +272,49 @@ int  metro_plan_bind_heatmaps(MetroPlan* plan, float* d_xy_out, float* d_z_out, 
 int64_t metro_plan_modes_scratch_bytes(const MetroPlan* plan, int32_t max_n);
 int  metro_plan_bind_modes(MetroPlan* plan, int32_t* d_voxel_out, float* d_stats_out, void* d_scratch,
                            int32_t max_n, int32_t k, int32_t radius);
+/* ---- per-joint heat-map posterior under a Gaussian prior, bound to the plan ----
+ * Moments, marginals and modes describe what the net believes on its own.  This lets the caller tell the forward what it already
+ * knows (a tracker's prediction, the previous frame's pose, another camera's ray): a Gaussian prior is multiplied into the joint's
+ * softmax before the expectation, so the posterior mean is taken from the peak that agrees with the prior, the posterior
+ * covariance is that peak's, and the evidence is the probability the heat-map gives to the prior's region -- the quantity a
+ * tracker gates a measurement with.  Exact over the whole S x S x D volume.  With prior buffers bound, every forward entry (the
+ * list above) also writes the posterior on the stream it is given, from the logits of the same forward.  Definition, for crop
+ * i < n, output joint r and head joint j = permutation[r]:
+ *   l[v] = logits[i, y, x, d * J + j] over the voxels v = (y * S + x) * D + d;  g(v) = (gx[x], gy[y], gz[d]) the soft-argmax's own
+ *   fp32 grids (fp32 linspace(0,1,S) for x and y, linspace(0,1,D) for z; a grid of one point is 0).
+ *   Input   d_prior fp32 [max_n, n_joints_out, 9], OUTPUT joint order: per row mu (x, y, z, in coords01 units) and the precision
+ *           L (xx, yy, zz, xy, xz, yz: the order of cov01, units of 1 / coords01^2).  L must be symmetric positive semi-definite
+ *           and may be singular: a zero row and column means "no knowledge along that axis" (callers use this for z, whose absolute
+ *           heat-map position the model does not pin).  The device does not check definiteness.
+ *   Energy     q(v) = -1/2 (g(v) - mu)^T L (g(v) - mu)
+ *   Posterior  w[v] = l[v] + q(v),  M' = max w,  p'[v] = exp(w[v] - M') / S',  S' = sum exp(w - M')
+ *   Output  d_post_out fp32 [max_n, n_joints_out, 11], the layout of the mode stats with the mass slot replaced:
+ *           log_evidence = (M' - M) + ln(S' / S), M and S the joint's plain maximum and normaliser, both sums formed by the same
+ *             code in the same order (= ln sum_v p[v] exp(q(v)); <= 0 for a positive semi-definite L);
+ *           peak' = max p';  coords01' = sum p' g (x, y, z);  cov01' = the six central second moments of p' about coords01', in the
+ *           order (xx, yy, zz, xy, xz, yz).  Rows n .. max_n - 1 are not touched.
+ *   Special rows: a zero L gives log_evidence exactly 0.0 and the plain distribution's statistics in the other ten values.  A NaN in
+ *   the joint's mu or L, a NaN or +Inf logit, or a non-finite M' gives NaN in all 11 values of that joint only; a -Inf logit is a
+ *   voxel of weight zero.  No other joint and no other crop is affected; the crop's pose, status word and METRO_ERR_NONFINITE are
+ *   those of the unbound call.
+ *   Sums: fp32 on f16 plans, fp64 on f32, f32m and f64 plans (the logits are read as fp64 on f64 plans); q is evaluated in the
+ *   accumulator type; fixed order, no atomics; each output is rounded to fp32 once.  The central moments are formed about the
+ *   posterior mean, not as E[g^2] - E[g]^2.
+ * Binding is HOST state: a forward reads the pointers when it enqueues, so rebinding (or unbinding: all three pointers NULL and
+ * max_n = 0) between two enqueues needs no synchronisation; the buffers must stay alive until the forwards enqueued while they
+ * were bound have run.  Anything but the unbind call is checked in full: three non-NULL pointers, the scratch 16-byte and the
+ * others 4-byte aligned, max_n in [1, the plan's max_batch].  d_scratch: metro_plan_prior_scratch_bytes(plan, max_n) bytes (-1 for
+ * a bad argument); on f16 plans whose head keeps the logits on chip it receives them as fp32, else the logits are read from the
+ * workspace.
+ * While bound: a forward with n > max_n returns METRO_ERR_INVALID_ARG before any launch; forwards make PLAIN launches (the
+ * hipGraph cache does not serve them); one launch (heat_posterior: csrc/heat_posterior.hip) follows the finalize launch, the three
+ * marginal launches and the modes launch when those are bound.  All three may be bound together: the head's one fp32 logits
+ * store goes to the heat-map scratch if heat-maps are bound, else to the modes scratch, else to this one, and the others read
+ * the logits there; each output is bit for bit what it is when bound alone.  A shape the kernel cannot serve (more than 2^24
+ * voxels a joint) returns METRO_ERR_UNSUPPORTED.  Poses, coords01, covariance, peak and status words keep the bits of the unbound
+ * call.  Unbound, a forward enqueues exactly the kernels it always did. */
+int64_t metro_plan_prior_scratch_bytes(const MetroPlan* plan, int32_t max_n);
+int  metro_plan_bind_prior(MetroPlan* plan, const float* d_prior, float* d_post_out, void* d_scratch, int32_t max_n);
 /* Same, stopping after layer `last_layer` (inclusive) so tests can read that layer's output at
  * MetroLayerInfo.out_offset in the workspace.  d_poses_out may be NULL if the finalize layer
  * is not reached. */

@@ -5,6 +5,8 @@ Public surface (mirrors reference inference.py):
         [, PoseUncertainty with return_uncertainty=True][, Heatmaps (per-joint xy and z marginals) with return_heatmaps=True]
     estimate_pose_modes(images, model_path, k=2, radius=1) -> the same, and Modes last: the k places each joint may be, with the
         probability mass, position (mm) and covariance of each
+    estimate_pose_posterior(images, model_path, prior_positions, prior_precision) -> the same, and Posterior last: each joint's
+        heat-map times a Gaussian prior (pose_prior: mm -> prior rows) -- posterior position, covariance and log-evidence
     estimate_pose_in_frames(frames, boxes, model_path, cameras=...) -> the same from uint8 frames + person boxes (frames.py)
     locate_poses_in_frames(frames, boxes, model_path, cameras=..., bone_lengths=...) -> absolute poses + 2D frame keypoints
     triangulate_poses_in_frames(frames, boxes, model_path, cameras, person_index, frame_index) -> world poses of persons seen
@@ -31,7 +33,7 @@ container (save_model / load_model) and batch sharding over the GPUs of a node (
 from metro_pose3d_amd.spec import ModelSpec  # noqa: F401
 from metro_pose3d_amd.modelfile import load_model, save_model  # noqa: F401
 
-__all__ = ['ModelSpec', 'load_model', 'save_model', 'Engine', 'estimate_pose', 'Heatmaps', 'estimate_pose_modes', 'Modes', 'estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'follow_rig_poses_in_frames', 'predict_boxes_in_frames', 'frame_sizes', 'Follower', 'Camera']
+__all__ = ['ModelSpec', 'load_model', 'save_model', 'Engine', 'estimate_pose', 'Heatmaps', 'estimate_pose_modes', 'Modes', 'estimate_pose_posterior', 'Posterior', 'pose_prior', 'posterior_to_metric', 'estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'follow_rig_poses_in_frames', 'predict_boxes_in_frames', 'frame_sizes', 'Follower', 'Camera']
 
 
 def __getattr__(name):
@@ -45,7 +47,7 @@ def __getattr__(name):
     if name == 'Heatmaps':
         from metro_pose3d_amd.inference import Heatmaps
         return Heatmaps
-    if name in ('estimate_pose_modes', 'Modes'):
+    if name in ('estimate_pose_modes', 'Modes', 'estimate_pose_posterior', 'Posterior', 'pose_prior', 'posterior_to_metric'):
         from metro_pose3d_amd import inference
         return getattr(inference, name)
     if name in ('estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'follow_rig_poses_in_frames', 'predict_boxes_in_frames', 'frame_sizes', 'Follower', 'Camera'):

@@ -149,6 +149,8 @@ SIGNATURES = {
     'metro_plan_bind_heatmaps': (C.c_int, [_P, _P, _P, _P, C.c_int32]),
     'metro_plan_modes_scratch_bytes': (C.c_int64, [_P, C.c_int32]),
     'metro_plan_bind_modes': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
+    'metro_plan_prior_scratch_bytes': (C.c_int64, [_P, C.c_int32]),
+    'metro_plan_bind_prior': (C.c_int, [_P, _P, _P, _P, C.c_int32]),
     'metro_forward_upto': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32]),
     'metro_forward_timed': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_float)]),
     'metro_conv_f16': (C.c_int, [C.POINTER(MetroConvDesc), _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -14,7 +14,7 @@ namespace {
 // `coords01` (optional): the finalize launch also writes the soft-argmax coordinates in [0,1] there (metro_forward_coords01).
 // `images_u8` (metro_forward_u8): `images` points to uint8 crops; the layer that reads them runs the uint8 form of its kernel.
 // `mo` (metro_forward_moments): its scratch selects the MOMENTS instantiations of the head / soft-argmax launches.
-// `head_logits` (a forward with heat-map or mode buffers bound): where the one-launch head also writes its fp32 logits, as for a dump.
+// `head_logits` (a forward with heat-map, mode or prior buffers bound): where the one-launch head also writes its fp32 logits, as for a dump.
 int launch_layer(const MetroPlan* p, const char* d_params, int li, const float* images, int n, float* poses, char* ws, hipStream_t stream, bool dump,
                  float* coords01 = nullptr, bool images_u8 = false, const MomentsOut& mo = MomentsOut{}, float* head_logits = nullptr) {
     const Layer& L = p->layers[li];
@@ -126,11 +126,17 @@ int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_
     const bool modes = p->modes.scratch != nullptr && last_layer == nl - 1;
     METRO_CHECK_ARG(!modes || n <= p->modes.max_n, "batch %d exceeds the %d crops the bound mode buffers hold (metro_plan_bind_modes)",
                     n, p->modes.max_n);
+    // prior buffers bound (metro_plan_bind_prior): the same; the logits store goes to the heat-map scratch, else to the modes', else here
+    const bool prior = p->prior.scratch != nullptr && last_layer == nl - 1;
+    METRO_CHECK_ARG(!prior || n <= p->prior.max_n, "batch %d exceeds the %d crops the bound prior buffers hold (metro_plan_bind_prior)",
+                    n, p->prior.max_n);
     float* head_logits = nullptr;
     if (heat && p->head_fused)
         head_logits = heat_marginals_scratch_logits(p->heat.scratch, p->heat.max_n, side, p->spec.n_joints_head, p->spec.depth);
     else if (modes && p->head_fused)
         head_logits = static_cast<float*>(p->modes.scratch);
+    else if (prior && p->head_fused)
+        head_logits = static_cast<float*>(p->prior.scratch);
 
     std::vector<hipEvent_t> ev;
     if (ms_out) {
@@ -151,6 +157,10 @@ int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_
         st = launch_heat_modes(head_logits ? head_logits : static_cast<void*>(ws + p->slot_offset[S_LOGITS]),
                                p->spec.precision == METRO_PREC_F32M ? 1 : p->spec.precision, n, p->modes.max_n, p->spec, p->modes.k,
                                p->modes.radius, p->modes.voxel, p->modes.stats, stream);
+    if (prior && st == METRO_OK)
+        st = launch_heat_posterior(head_logits ? head_logits : static_cast<void*>(ws + p->slot_offset[S_LOGITS]),
+                                   p->spec.precision == METRO_PREC_F32M ? 1 : p->spec.precision, n, p->prior.max_n, p->spec, p->prior.prior,
+                                   p->prior.post, stream);
     if (ms_out) {
         if (st == METRO_OK) {
             METRO_HIP_CHECK(hipEventSynchronize(ev.back()));
@@ -248,6 +258,27 @@ int metro_plan_bind_modes(MetroPlan* plan, int32_t* d_voxel_out, float* d_stats_
     return METRO_OK;
 }
 
+int64_t metro_plan_prior_scratch_bytes(const MetroPlan* plan, int32_t max_n) {
+    if (plan == nullptr || max_n < 1 || max_n > plan->max_batch) return -1;
+    return heat_posterior_scratch_bytes(max_n, plan->spec.proc_side / plan->spec.stride, plan->spec.n_joints_head, plan->spec.depth,
+                                        plan->head_fused);
+}
+
+int metro_plan_bind_prior(MetroPlan* plan, const float* d_prior, float* d_post_out, void* d_scratch, int32_t max_n) {
+    METRO_CHECK_ARG(plan != nullptr, "metro_plan_bind_prior: plan is NULL");
+    if (d_prior == nullptr && d_post_out == nullptr && d_scratch == nullptr && max_n == 0) {       // unbind
+        plan->prior.prior = nullptr; plan->prior.post = nullptr; plan->prior.scratch = nullptr; plan->prior.max_n = 0;
+        return METRO_OK;
+    }
+    METRO_CHECK_ARG(d_prior != nullptr && d_post_out != nullptr && d_scratch != nullptr,
+                    "metro_plan_bind_prior: prior, post_out and the scratch go together (all three, or all NULL with max_n 0 to unbind)");
+    METRO_CHECK_ARG(max_n >= 1 && max_n <= plan->max_batch, "metro_plan_bind_prior: max_n %d outside [1, %d]", max_n, plan->max_batch);
+    METRO_CHECK_ARG(((uintptr_t)d_scratch & 15) == 0 && ((uintptr_t)d_prior & 3) == 0 && ((uintptr_t)d_post_out & 3) == 0,
+                    "metro_plan_bind_prior: the scratch must be 16-byte aligned, the prior and the output 4-byte aligned");
+    plan->prior.prior = d_prior; plan->prior.post = d_post_out; plan->prior.scratch = d_scratch; plan->prior.max_n = max_n;
+    return METRO_OK;
+}
+
 int metro_plan_set_graph_max_batch(MetroPlan* plan, int32_t max_batch_for_graphs) {
     METRO_CHECK_ARG(plan != nullptr && max_batch_for_graphs >= 0, "metro_plan_set_graph_max_batch: bad argument");
     plan->graph_max_batch = max_batch_for_graphs;
@@ -257,8 +288,9 @@ int metro_plan_set_graph_max_batch(MetroPlan* plan, int32_t max_batch_for_graphs
 static int forward_impl(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out, float* d_coords01,
                         void* d_workspace, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    // heat-map or mode buffers bound: plain launches, the captured forwards do not write them
-    if (plan == nullptr || n > plan->graph_max_batch || n < 1 || plan->heat.scratch != nullptr || plan->modes.scratch != nullptr)
+    // heat-map, mode or prior buffers bound: plain launches, the captured forwards do not write them
+    if (plan == nullptr || n > plan->graph_max_batch || n < 1 || plan->heat.scratch != nullptr || plan->modes.scratch != nullptr ||
+        plan->prior.scratch != nullptr)
         return run_layers(plan, d_images_nhwc, n, d_poses_out, d_workspace, stream, -1, nullptr, d_coords01);
     // small batches are launch-latency bound (57 dependent launches): replay a captured hipGraph
     GraphEntry* hit = nullptr;

@@ -504,6 +504,12 @@ int launch_heat_marginals(const void* logits, int precise, int n, int max_n, con
 int64_t heat_modes_scratch_bytes(int n, int side, int n_joints_head, int depth, bool with_logits);
 int launch_heat_modes(const void* logits, int precise, int n, int max_n, const MetroSpec& spec, int k, int radius, int32_t* voxel_out,
                       float* stats_out, hipStream_t stream);
+// Heat-map posterior under a Gaussian prior of a bound forward (heat_posterior.hip): post [n][J_out][11] from the logits (as above)
+// and the prior rows [n][J_out][9].  The kernel needs no scratch; with_logits plans keep the head's fp32 logits in the bound
+// scratch, from its first byte.
+int64_t heat_posterior_scratch_bytes(int n, int side, int n_joints_head, int depth, bool with_logits);
+int launch_heat_posterior(const void* logits, int precise, int n, int max_n, const MetroSpec& spec, const float* prior, float* post_out,
+                          hipStream_t stream);
 // the volumetric head in one launch (head_f16.hip): postnorm prologue + logits GEMM + per-joint softmax statistics
 bool head_f16_supported(int c_in, int c_head, int n_joints, int depth, int side);
 int head_f16_slabs(int side);               // records per image the partials slot must hold

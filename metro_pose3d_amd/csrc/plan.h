@@ -74,5 +74,7 @@ struct MetroPlan {
     struct { float* xy = nullptr; float* z = nullptr; void* scratch = nullptr; int max_n = 0; } heat;
     // metro_plan_bind_modes: the same (heat_modes.hip)
     struct { int32_t* voxel = nullptr; float* stats = nullptr; void* scratch = nullptr; int max_n = 0, k = 0, radius = 0; } modes;
+    // metro_plan_bind_prior: the same (heat_posterior.hip)
+    struct { const float* prior = nullptr; float* post = nullptr; void* scratch = nullptr; int max_n = 0; } prior;
     bool head_fused = false;             // the logits stay on chip (LayerForm::Head)
 };

@@ -90,6 +90,7 @@ class Engine:
         self._moments = None
         self._heat = None
         self._modes = None
+        self._prior = None
         self.heat_chunk = None       # crops per forward of a call with heat-map outputs (None: from HEAT_SCRATCH_CAP)
         if params is not None:
             if device is None:
@@ -277,6 +278,57 @@ class Engine:
         if words:
             self.status_words(n).copy_(torch.cat(words))
         return out, voxel, stats
+
+    POST_STATS = 11          # log_evidence, peak', coords01' (x, y, z), cov01' (xx, yy, zz, xy, xz, yz)
+    PRIOR_WORDS = 9          # mu (x, y, z), precision (xx, yy, zz, xy, xz, yz), in coords01 units
+
+    def forward_posterior(self, images: torch.Tensor, prior: torch.Tensor, out: Optional[torch.Tensor] = None,
+                          coords01: Optional[torch.Tensor] = None, cov01: Optional[torch.Tensor] = None,
+                          peak: Optional[torch.Tensor] = None, heat_xy: Optional[torch.Tensor] = None,
+                          heat_z: Optional[torch.Tensor] = None):
+        """forward() that also returns every output joint's heat-map posterior under a Gaussian prior -> (poses, post fp32
+        [n, Jout, 11]).  `prior` fp32 [n, Jout, 9] on the plan's device, output joint order: per joint mu (x, y, z in coords01
+        units) and the precision (xx, yy, zz, xy, xz, yz; positive semi-definite, may be singular, all zero: no knowledge).
+        `post` per joint: log_evidence, and the peak, coords01 (x, y, z) and cov01 (xx, yy, zz, xy, xz, yz) of the joint's
+        softmax times the prior, over the whole volume (metro_plan_bind_prior, include/metro_hip.h, holds the definition).
+        Binds prior and output to the plan chunk by chunk (host state, read at enqueue), calls forward() with the other
+        arguments and unbinds; every other output keeps the bits forward() gives it.  The engine owns the scratch; the call is
+        made of several forwards by the rule of the heat-map outputs (HEAT_SCRATCH_CAP, heat_chunk)."""
+        images = self._check_images(images)
+        n, nj = images.shape[0], self.spec.skeleton.n_out
+        if not isinstance(prior, torch.Tensor) or prior.dtype != torch.float32 or tuple(prior.shape) != (n, nj, self.PRIOR_WORDS):
+            raise ValueError(f'prior must be a float32 tensor [{n}, {nj}, {self.PRIOR_WORDS}] (mu x, y, z; precision xx, yy, zz, xy, '
+                             f'xz, yz), got {tuple(prior.shape) if isinstance(prior, torch.Tensor) else type(prior)}'
+                             f'{" of " + str(prior.dtype) if isinstance(prior, torch.Tensor) else ""}')
+        if prior.device != self.device:
+            raise ValueError(f'prior is on {prior.device}, the plan is on {self.device}')
+        prior = prior.contiguous()
+        if out is None:
+            out = torch.empty((n, nj, 3), dtype=torch.float32, device=self.device)
+        else:
+            self._check_out('out', out, (n, nj, 3))
+        post = torch.empty((n, nj, self.POST_STATS), dtype=torch.float32, device=self.device)
+        step = self._heat_chunk()
+        nb = int(self.lib.metro_plan_prior_scratch_bytes(self._plan, step))
+        if self._prior is None or self._prior.numel() < nb:
+            self._prior = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        part = lambda t, i, m: None if t is None else t[i:i + m]
+        words = []
+        try:
+            for i in range(0, n, step):
+                m = min(step, n - i)
+                check(self.lib.metro_plan_bind_prior(self._plan, C.c_void_p(prior[i:i + m].data_ptr()),
+                                                     C.c_void_p(post[i:i + m].data_ptr()), C.c_void_p(self._prior.data_ptr()), step),
+                      'metro_plan_bind_prior')
+                self.forward(images[i:i + m], out[i:i + m], part(coords01, i, m), part(cov01, i, m), part(peak, i, m),
+                             part(heat_xy, i, m), part(heat_z, i, m))
+                if n > step:
+                    words.append(self.status_words(m).clone())
+        finally:
+            check(self.lib.metro_plan_bind_prior(self._plan, None, None, None, 0), 'metro_plan_bind_prior')
+        if words:
+            self.status_words(n).copy_(torch.cat(words))
+        return out, post
 
     def forward(self, images: torch.Tensor, out: Optional[torch.Tensor] = None,
                 coords01: Optional[torch.Tensor] = None, cov01: Optional[torch.Tensor] = None,

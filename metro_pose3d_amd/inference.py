@@ -386,6 +386,176 @@ def estimate_pose_modes(images_tensor, model_path, k: int = 2, radius: int = 1, 
     return tuple(res)
 
 
+class Posterior(NamedTuple):
+    """Per-joint heat-map posterior under a Gaussian prior (estimate_pose_posterior), output joint order: the joint's softmax
+    times the prior, over the whole volume.  A joint with a NaN in its prior row or a NaN / +Inf logit is NaN everywhere."""
+    poses: torch.Tensor          # float32 [n, Jout, 3] mm: `positions` minus the posterior root's position
+    positions: torch.Tensor      # float32 [n, Jout, 3] mm: heatmap_to_metric of the posterior mean, un-rooted (crop-metric frame)
+    covariance: torch.Tensor     # float32 [n, Jout, 3, 3] mm^2: of the posterior, about its mean
+    log_evidence: torch.Tensor   # float32 [n, Jout]: ln of the probability the heat-map gives to the prior's region (<= 0)
+    peak: torch.Tensor           # float32 [n, Jout]: the largest posterior probability of a voxel
+
+
+def _metric_map(spec):
+    """heatmap_to_metric (reference volumetric.py:288-306) as mm = a * coords01 + b per axis: (a [3], b [3]), Python floats."""
+    last = spec.proc_side - 1
+    lrc, half = float(last - last % spec.stride - 1), float(spec.stride // 2)
+    box, side = float(spec.box_size_mm), float(spec.proc_side)
+    return (lrc * box / side, lrc * box / side, box), (half * box / side, half * box / side, 0.0)
+
+
+def _check_prior_arrays(positions, precision, n=None):
+    """Shapes and dtypes of a prior in mm: positions [n, Jout, 3] and precision [n, Jout, 3, 3], both NumPy arrays or both torch
+    tensors of a float type; HOST arrays are also checked for symmetry and for being positive semi-definite (CUDA tensors are
+    not read).  -> (positions, precision) as float64 torch tensors on the inputs' device."""
+    if isinstance(positions, np.ndarray):
+        positions = torch.from_numpy(positions)
+    if isinstance(precision, np.ndarray):
+        precision = torch.from_numpy(precision)
+    for name, t in (('prior positions', positions), ('prior precision', precision)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f'{name} must be a torch.Tensor or numpy array, got {type(t)}')
+        if not t.dtype.is_floating_point:
+            raise ValueError(f'{name} must be of a float type, got {t.dtype}')
+    if positions.dim() != 3 or positions.shape[-1] != 3:
+        raise ValueError(f'prior positions must be [n, Jout, 3] (mm), got {tuple(positions.shape)}')
+    if tuple(precision.shape) != tuple(positions.shape) + (3,):
+        raise ValueError(f'prior precision must be {tuple(positions.shape) + (3,)} (1/mm^2, one symmetric 3 x 3 matrix per joint), '
+                         f'got {tuple(precision.shape)}')
+    if n is not None and positions.shape[0] != n:
+        raise ValueError(f'the prior holds {positions.shape[0]} crops, the images {n}')
+    if precision.device != positions.device:
+        raise ValueError(f'prior positions are on {positions.device}, the precision on {precision.device}')
+    positions, precision = positions.double(), precision.double()
+    if not precision.is_cuda and precision.numel():
+        lam = precision.numpy()
+        ok = np.isfinite(lam).all(axis=(-1, -2))          # a NaN row is the caller's way to poison a joint: passed on
+        size = np.abs(lam).max(axis=(-1, -2), initial=0.0)
+        skew = np.abs(lam - np.swapaxes(lam, -1, -2)).max(axis=(-1, -2))
+        if (ok & (skew > 1e-9 * size)).any():
+            i = np.argwhere(ok & (skew > 1e-9 * size))[0]
+            raise ValueError(f'prior precision of crop {i[0]}, joint {i[1]} is not symmetric')
+        low = np.linalg.eigvalsh(np.where(ok[..., None, None], 0.5 * (lam + np.swapaxes(lam, -1, -2)), 0.0))[..., 0]
+        if (low < -1e-9 * size).any():
+            i = np.argwhere(low < -1e-9 * size)[0]
+            raise ValueError(f'prior precision of crop {i[0]}, joint {i[1]} is not positive semi-definite (lowest eigenvalue {low[tuple(i)]:g})')
+    return positions, precision
+
+
+def pose_prior(spec, positions_mm, precision_mm) -> torch.Tensor:
+    """A Gaussian prior in mm -> the prior rows Engine.forward_posterior takes, float32 [n, Jout, 9] on the inputs' device:
+    positions_mm [n, Jout, 3] in the crop-metric frame of Posterior.positions (un-rooted), precision_mm [n, Jout, 3, 3] in
+    1/mm^2 (symmetric positive semi-definite; singular and zero matrices are fine: no knowledge along those axes).  The inverse
+    of the linear map of posterior_to_metric: mu = (mm - b) / a per axis and L01 = diag(a) Lmm diag(a), words (xx, yy, zz, xy,
+    xz, yz).  fp64 arithmetic, one rounding per value.  Host arrays are checked for symmetry and definiteness; CUDA tensors
+    are not read."""
+    pos, lam = _check_prior_arrays(positions_mm, precision_mm)
+    a, b = _metric_map(spec)
+    a = torch.tensor(a, dtype=torch.float64, device=pos.device)
+    b = torch.tensor(b, dtype=torch.float64, device=pos.device)
+    mu = (pos - b) / a
+    l01 = lam * (a[:, None] * a[None, :])
+    words = [l01[..., 0, 0], l01[..., 1, 1], l01[..., 2, 2], l01[..., 0, 1], l01[..., 0, 2], l01[..., 1, 2]]
+    return torch.cat([mu, torch.stack(words, -1)], -1).float().contiguous()
+
+
+def posterior_to_metric(spec, post: torch.Tensor, coords01: Optional[torch.Tensor] = None) -> Posterior:
+    """Engine.forward_posterior's post [n, Jout, 11] -> Posterior.  Positions: heatmap_to_metric (reference volumetric.py:288-306)
+    of the posterior mean.  Poses: positions minus the posterior root's -- the output row of the root head joint (the last head
+    joint, tfu3d.py:23-25); a skeleton whose output order does not carry it (the merged one) takes the root's plain mean from the
+    same call's coords01 [n, J_head, 3], which must then be given.  Covariances: diag(a) Cov01 diag(a), the scaling of
+    modes_to_metric.  fp64 arithmetic on the fp32 inputs, one rounding per output."""
+    from metro_pose3d_amd.heads import cov6_to_3x3
+    sk = spec.skeleton
+    a, b = _metric_map(spec)
+    a = torch.tensor(a, dtype=torch.float64, device=post.device)
+    b = torch.tensor(b, dtype=torch.float64, device=post.device)
+    if post.dim() != 3 or tuple(post.shape[1:]) != (sk.n_out, Engine.POST_STATS):
+        raise ValueError(f'post must be [n, {sk.n_out}, {Engine.POST_STATS}], got {tuple(post.shape)}')
+    pd = post.double()
+    positions = pd[..., 2:5] * a + b
+    perm = list(sk.permutation)
+    if sk.n_head - 1 in perm:
+        root = positions[:, perm.index(sk.n_head - 1)]
+    elif coords01 is not None:
+        root = coords01.double()[:, -1] * a + b
+    else:
+        raise ValueError('the output joints of this skeleton do not carry the root head joint: pass the same call\'s coords01')
+    cov = cov6_to_3x3(pd[..., 5:]) * (a[:, None] * a[None, :])
+    return Posterior((positions - root[:, None, :]).float(), positions.float(), cov.float(), post[..., 0].contiguous(),
+                     post[..., 1].contiguous())
+
+
+def estimate_pose_posterior(images_tensor, model_path, prior_positions, prior_precision, precision: Optional[str] = None,
+                            check_finite: Optional[bool] = None, return_uncertainty: bool = False, return_heatmaps: bool = False,
+                            *, shard: Optional[bool] = None):
+    """estimate_pose that also returns every joint's heat-map posterior under a Gaussian prior: estimate_pose's tuple (with the
+    PoseUncertainty and the Heatmaps where asked), and Posterior appended last.  The prior is what the caller already knows -- a
+    tracker's prediction, the previous frame's pose: prior_positions [n, Jout, 3] in mm, in the crop-metric frame of
+    Posterior.positions, and prior_precision [n, Jout, 3, 3] in 1/mm^2 (positive semi-definite; a zero row and column: no
+    knowledge along that axis; see pose_prior).  For a two-peaked joint the plain pose lies between the peaks; the posterior
+    mean is taken from the peak that agrees with the prior, its covariance is that peak's, and exp(log_evidence) is the
+    probability the heat-map gives to the prior's region (metro_plan_bind_prior; Engine.forward_posterior).  Written by the same
+    forwards from their own logits; poses, uncertainty and heat-maps keep the bits estimate_pose gives them; uint8 crops and
+    every precision are served.  A local call: sharded calls do not return posteriors (shard=True raises ValueError)."""
+    if shard:
+        raise ValueError('estimate_pose_posterior: sharded calls do not return posteriors (shard must be None or False)')
+    if precision is None:
+        precision = os.environ.get('METRO_PRECISION', 'f16')
+    if check_finite is None:
+        check_finite = os.environ.get('METRO_CHECK_FINITE', '1') != '0'
+    if isinstance(images_tensor, np.ndarray):
+        images_tensor = torch.from_numpy(images_tensor)
+    if not isinstance(images_tensor, torch.Tensor):
+        raise ValueError(f'images must be a torch.Tensor or numpy array, got {type(images_tensor)}')
+    if images_tensor.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f'images must be float32 in [0,1] (reference inference.py:18) or uint8 RGB bytes, got {images_tensor.dtype}')
+    n = int(images_tensor.shape[0]) if images_tensor.dim() == 4 else 0
+    _check_prior_arrays(prior_positions, prior_precision, n if images_tensor.dim() == 4 else None)
+    device = _resolve_device(images_tensor)
+    with torch.cuda.device(device):
+        eng = _engine_for(model_path, precision, device, max(n, 1))
+        sk, s = eng.spec.skeleton, eng.spec.proc_side
+        if images_tensor.dim() != 4 or tuple(images_tensor.shape[1:]) != (s, s, 3):
+            raise _ShapeError(f'images must be NHWC [N,{s},{s},3] (reference main.py:109-110), got {tuple(images_tensor.shape)}')
+        prior = pose_prior(eng.spec, prior_positions, prior_precision)
+        if prior.shape[1] != sk.n_out:
+            raise ValueError(f'the prior holds {prior.shape[1]} joints, the model returns {sk.n_out}')
+        prior = prior.to(device, non_blocking=True)
+        images = images_tensor.to(device, non_blocking=True).contiguous()
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
+        poses, coords01 = f32(n, sk.n_out, 3), f32(n, sk.n_head, 3)
+        cov01, peak = (f32(n, sk.n_head, 6), f32(n, sk.n_head)) if return_uncertainty else (None, None)
+        heat_xy, heat_z = (f32(*eng.heat_shapes(n)[0]), f32(*eng.heat_shapes(n)[1])) if return_heatmaps else (None, None)
+        part = lambda t, i, m: None if t is None else t[i:i + m]
+        posts, bad = [], None
+        for i in range(0, n, eng.max_batch):
+            m = min(eng.max_batch, n - i)
+            _, po = eng.forward_posterior(images[i:i + m], prior[i:i + m], poses[i:i + m], coords01[i:i + m], part(cov01, i, m),
+                                          part(peak, i, m), part(heat_xy, i, m), part(heat_z, i, m))
+            posts.append(po)
+            if check_finite:       # folded on the device after every chunk: one synchronisation per call, below
+                cnt = eng.status_words(m).ne(0).sum()
+                bad = cnt if bad is None else bad + cnt
+        if bad is not None and int(bad.item()):
+            raise _lib.NonFiniteError(
+                f'{eng.spec.arch_name} stride {eng.spec.stride} in precision {precision!r}: {int(bad.item())} crops reached the '
+                f'soft-argmax with non-finite statistics' +
+                (' (fp16 storage overflows at 65504: run this model with precision f32m or f64)' if precision == 'f16' else ''))
+        names = np.empty(sk.n_out, dtype=object)
+        names[:] = sk.names_bytes()
+        res = [poses, sk.edges_array(), names]
+        if return_uncertainty:
+            from metro_pose3d_amd.heads import place_covariances
+            res.append(PoseUncertainty(*place_covariances(cov01, peak, eng.spec)) if n else
+                       PoseUncertainty(poses.new_empty((0, sk.n_out, 3, 3)), poses.new_empty((0, sk.n_out))))
+        if return_heatmaps:
+            res.append(Heatmaps(heat_xy, heat_z))
+        po = torch.cat(posts) if posts else f32(0, sk.n_out, Engine.POST_STATS)
+        res.append(posterior_to_metric(eng.spec, po, coords01))
+    return tuple(res)
+
+
 def visualize_pose(image, coords, edges):
     """Stick-figure plot like reference inference.py:46-76 (matplotlib optional)."""
     import matplotlib
@@ -450,6 +620,10 @@ def main(argv=None):
     parser.add_argument('--modes', type=str, default=None, metavar='K[,R]',
                         help='also print, per joint, its heat-map modes that hold a mass of at least 0.05: up to K places the '
                              'joint may be (window radius R voxels, default 1), each with its mass and position in mm')
+    parser.add_argument('--prior', type=str, default=None, metavar='PRIOR.npz',
+                        help='also print, per joint, its heat-map posterior under the Gaussian prior of this .npz (arrays '
+                             '`positions` [Jout,3] mm, crop-metric frame, and `precision` [Jout,3,3] 1/mm^2): the posterior '
+                             'position, its standard deviations and exp(log_evidence)')
     opts = parser.parse_args(argv)
     modes_kr = None
     if opts.modes:
@@ -461,8 +635,8 @@ def main(argv=None):
         except (ValueError, IndexError):
             parser.error(f'--modes takes K or K,R (integers), got {opts.modes!r}')
     if opts.frame:
-        if opts.heatmaps or opts.modes:
-            parser.error('--heatmaps and --modes go with the crop call (--image), not with --frame')
+        if opts.heatmaps or opts.modes or opts.prior:
+            parser.error('--heatmaps, --modes and --prior go with the crop call (--image), not with --frame')
         return _main_frame(opts)
     if opts.crop_dtype:
         parser.error('--crop-dtype goes with --frame')
@@ -476,8 +650,17 @@ def main(argv=None):
         from metro_pose3d_amd.synth import make_images
         img = make_images(1)[0]
     images = torch.from_numpy(img[None])
-    modes = None
-    if modes_kr:
+    modes = posterior = None
+    if opts.prior:
+        if modes_kr:
+            parser.error('--prior and --modes are two calls: give one of them')
+        with np.load(opts.prior) as f:
+            prior_pos, prior_lam = np.asarray(f['positions'], np.float64), np.asarray(f['precision'], np.float64)
+        prior_pos = prior_pos[None] if prior_pos.ndim == 2 else prior_pos
+        prior_lam = prior_lam[None] if prior_lam.ndim == 3 else prior_lam
+        poses, edges, names, *more, posterior = estimate_pose_posterior(images, opts.model_path, prior_pos, prior_lam, precision=opts.precision,
+                                                                        return_uncertainty=opts.uncertainty, return_heatmaps=bool(opts.heatmaps))
+    elif modes_kr:
         poses, edges, names, *more, modes = estimate_pose_modes(images, opts.model_path, modes_kr[0], modes_kr[1], precision=opts.precision,
                                                                 return_uncertainty=opts.uncertainty, return_heatmaps=bool(opts.heatmaps))
     else:
@@ -496,6 +679,12 @@ def main(argv=None):
         for r, name in enumerate(names):
             for i in np.flatnonzero(mass[r] >= 0.05):
                 print(f'{name.decode():>10s}  mode {i}: mass {mass[r, i]:.3f} at {at[r, i, 0]:9.2f} {at[r, i, 1]:9.2f} {at[r, i, 2]:9.2f}')
+    if posterior is not None:
+        at, ev = posterior.positions[0].cpu().numpy(), np.exp(posterior.log_evidence[0].double().cpu().numpy())
+        sd = np.sqrt(np.maximum(np.diagonal(posterior.covariance[0].cpu().numpy(), axis1=-2, axis2=-1), 0.0))
+        for r, name in enumerate(names):
+            print(f'{name.decode():>10s}  posterior at {at[r, 0]:9.2f} {at[r, 1]:9.2f} {at[r, 2]:9.2f}   sd {sd[r, 0]:7.2f} {sd[r, 1]:7.2f} '
+                  f'{sd[r, 2]:7.2f} mm   evidence {ev[r]:6.4f}')
     if opts.plot:
         visualize_pose(img, poses[0], edges).savefig(opts.plot)
 
