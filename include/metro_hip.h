@@ -791,6 +791,25 @@ int  metro_head_f16_moments(const void* d_x, const void* d_w, const float* d_bia
 int  metro_softargmax01_moments(const void* d_logits, int32_t n, const MetroSpec* spec, int32_t precise, void* d_scratch,
                                 void* d_moments_scratch, float* d_coords01_out, float* d_cov01_out, float* d_peak_out,
                                 void* stream);
+/* The kernels behind metro_plan_bind_heatmaps, metro_plan_bind_modes and metro_plan_bind_prior on the caller's own logits
+ * (kernel-level entries for the tests and heads.marginals_from_logits / modes_from_logits / posterior_from_logits): the launchers
+ * the bound forwards call, with max_n = n.  d_logits: device NHWC [n, S, S, D * J], S = proc_side / stride; precise 0: fp32
+ * logits, fp32 sums (what f16 plans run); 1: fp32 logits, fp64 sums (f32, f32m); 2: fp64 logits and sums (f64).  Outputs,
+ * definitions, arithmetic and non-finite rules are those of the bound forms above, word for word, in OUTPUT joint order
+ * (spec->n_joints_out rows, head joint spec->permutation[r]); d_prior is the bound form's input [n, n_joints_out, 9].
+ * d_scratch (marginals only): metro_heat_marginals_scratch_bytes(spec, n) bytes (-1 for a bad argument), 16-byte aligned -- the
+ * tile and joint records alone, no copy of the logits.  Checked before any launch: non-NULL pointers, the logits aligned to
+ * their element, the scratch to 16 and every other pointer to 4 bytes, 1 <= n <= 65535, both joint counts in
+ * [1, METRO_MAX_JOINTS], depth >= 1, stride >= 1 and proc_side / stride >= 1, k and radius in the ranges of
+ * metro_plan_bind_modes (METRO_ERR_INVALID_ARG); a shape the kernel cannot serve returns METRO_ERR_UNSUPPORTED as the bound
+ * forward does.  All work is enqueued on `stream`. */
+int64_t metro_heat_marginals_scratch_bytes(const MetroSpec* spec, int32_t n);
+int  metro_heat_marginals(const void* d_logits, int32_t n, const MetroSpec* spec, int32_t precise, void* d_scratch,
+                          float* d_xy_out, float* d_z_out, void* stream);
+int  metro_heat_modes(const void* d_logits, int32_t n, const MetroSpec* spec, int32_t precise, int32_t k, int32_t radius,
+                      int32_t* d_voxel_out, float* d_stats_out, void* stream);
+int  metro_heat_posterior(const void* d_logits, int32_t n, const MetroSpec* spec, int32_t precise, const float* d_prior,
+                          float* d_post_out, void* stream);
 /* Covariances in mm^2, output joint order, requested coordinates, one launch, one thread per (box, output joint).
  * d_cov01 / d_peak: [n * n_views, n_joints_head, 6] / [n * n_views, n_joints_head] (box-major rows i * n_views + v).
  * Gathers spec->permutation; Cov_mm = diag(s) Cov01 diag(s) with the linear part of heatmap_to_metric,

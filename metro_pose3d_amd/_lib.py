@@ -197,6 +197,10 @@ SIGNATURES = {
     'metro_forward_moments': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     'metro_head_f16_moments': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(MetroSpec)] + [_P] * 8),
     'metro_softargmax01_moments': (C.c_int, [_P, C.c_int32, C.POINTER(MetroSpec), C.c_int32, _P, _P, _P, _P, _P, _P]),
+    'metro_heat_marginals_scratch_bytes': (C.c_int64, [C.POINTER(MetroSpec), C.c_int32]),
+    'metro_heat_marginals': (C.c_int, [_P, C.c_int32, C.POINTER(MetroSpec), C.c_int32, _P, _P, _P, _P]),
+    'metro_heat_modes': (C.c_int, [_P, C.c_int32, C.POINTER(MetroSpec), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    'metro_heat_posterior': (C.c_int, [_P, C.c_int32, C.POINTER(MetroSpec), C.c_int32, _P, _P, _P]),
     'metro_place_covariances': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(MetroSpec), _P, C.c_int32, _P, _P, _P]),
     'metro_triangulate_joints': (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.POINTER(MetroSpec), _P, C.c_int32,
                                            C.c_double, _P, _P, _P, _P]),

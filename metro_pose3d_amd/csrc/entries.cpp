@@ -465,6 +465,65 @@ int metro_softargmax01_moments(const void* d_logits, int32_t n, const MetroSpec*
     return launch_softargmax(d_logits, a, precise, d_partials, nullptr, static_cast<hipStream_t>(stream), d_coords01_out, nullptr, mo);
 }
 
+// The three heat-map kernels on the caller's logits: what the bound forwards launch (executor.cpp), with max_n = n.
+constexpr int64_t MD_ENTRY_MAX_VOXELS = 64 * 1024;      // one flag byte a voxel: more than the LDS holds
+static bool heat_aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+static int check_heat_args(const char* who, const void* d_logits, int32_t n, const MetroSpec* spec, int32_t precise) {
+    METRO_CHECK_ARG(d_logits != nullptr && spec != nullptr, "%s: NULL logits or spec", who);
+    METRO_CHECK_ARG(precise >= 0 && precise <= 2, "%s: precise must be 0, 1 or 2 (got %d)", who, precise);
+    METRO_CHECK_ARG(heat_aligned(d_logits, precise == 2 ? 8 : 4), "%s: the logits must be aligned to their element", who);
+    METRO_CHECK_ARG(n >= 1 && n <= 65535, "%s: %d crops outside [1, 65535] (the grid's crop axis)", who, n);
+    METRO_CHECK_ARG(spec->n_joints_head >= 1 && spec->n_joints_head <= METRO_MAX_JOINTS && spec->n_joints_out >= 1 &&
+                        spec->n_joints_out <= METRO_MAX_JOINTS, "%s: joint counts out of range (1 to %d)", who, METRO_MAX_JOINTS);
+    METRO_CHECK_ARG(spec->depth >= 1 && spec->stride >= 1 && spec->proc_side / spec->stride >= 1,
+                    "%s: depth, stride and proc_side / stride must be at least 1", who);
+    for (int r = 0; r < spec->n_joints_out; ++r)
+        METRO_CHECK_ARG(spec->permutation[r] >= 0 && spec->permutation[r] < spec->n_joints_head,
+                        "%s: permutation[%d] = %d is no head joint", who, r, spec->permutation[r]);
+    return METRO_OK;
+}
+
+int64_t metro_heat_marginals_scratch_bytes(const MetroSpec* spec, int32_t n) {
+    if (spec == nullptr || n < 1 || n > 65535 || spec->n_joints_head < 1 || spec->n_joints_head > METRO_MAX_JOINTS || spec->depth < 1 ||
+        spec->stride < 1 || spec->proc_side / spec->stride < 1)
+        return -1;
+    return heat_marginals_scratch_bytes(n, spec->proc_side / spec->stride, spec->n_joints_head, spec->depth, false);
+}
+
+int metro_heat_marginals(const void* d_logits, int32_t n, const MetroSpec* spec, int32_t precise, void* d_scratch, float* d_xy_out,
+                         float* d_z_out, void* stream) {
+    if (const int st = check_heat_args("heat_marginals", d_logits, n, spec, precise)) return st;
+    METRO_CHECK_ARG(d_scratch && d_xy_out && d_z_out, "heat_marginals: NULL scratch or output pointer");
+    METRO_CHECK_ARG(heat_aligned(d_scratch, 16) && heat_aligned(d_xy_out, 4) && heat_aligned(d_z_out, 4),
+                    "heat_marginals: the scratch must be 16-byte and the outputs 4-byte aligned");
+    const int side = spec->proc_side / spec->stride;
+    METRO_CHECK_ARG((int64_t)side * side <= INT32_MAX / METRO_MAX_JOINTS, "heat_marginals: a map of side %d overflows the int32 row index", side);
+    return launch_heat_marginals(d_logits, precise, n, n, *spec, d_scratch, d_xy_out, d_z_out, static_cast<hipStream_t>(stream));
+}
+
+int metro_heat_modes(const void* d_logits, int32_t n, const MetroSpec* spec, int32_t precise, int32_t k, int32_t radius,
+                     int32_t* d_voxel_out, float* d_stats_out, void* stream) {
+    if (const int st = check_heat_args("heat_modes", d_logits, n, spec, precise)) return st;
+    METRO_CHECK_ARG(d_voxel_out && d_stats_out, "heat_modes: NULL output pointer");
+    METRO_CHECK_ARG(heat_aligned(d_voxel_out, 4) && heat_aligned(d_stats_out, 4), "heat_modes: the outputs must be 4-byte aligned");
+    METRO_CHECK_ARG(k >= 1 && k <= METRO_MAX_MODES, "heat_modes: k %d outside [1, %d]", k, METRO_MAX_MODES);
+    METRO_CHECK_ARG(radius >= 0 && radius <= METRO_MAX_MODE_RADIUS, "heat_modes: radius %d outside [0, %d]", radius, METRO_MAX_MODE_RADIUS);
+    const int side = spec->proc_side / spec->stride;
+    if ((int64_t)side * side * spec->depth > MD_ENTRY_MAX_VOXELS) {           // md_flag_bytes in int; no such volume fits the LDS anyway
+        set_error("heat_modes: a %d x %d x %d volume does not fit the kernel's LDS", side, side, spec->depth);
+        return METRO_ERR_UNSUPPORTED;
+    }
+    return launch_heat_modes(d_logits, precise, n, n, *spec, k, radius, d_voxel_out, d_stats_out, static_cast<hipStream_t>(stream));
+}
+
+int metro_heat_posterior(const void* d_logits, int32_t n, const MetroSpec* spec, int32_t precise, const float* d_prior,
+                         float* d_post_out, void* stream) {
+    if (const int st = check_heat_args("heat_posterior", d_logits, n, spec, precise)) return st;
+    METRO_CHECK_ARG(d_prior && d_post_out, "heat_posterior: NULL prior or output pointer");
+    METRO_CHECK_ARG(heat_aligned(d_prior, 4) && heat_aligned(d_post_out, 4), "heat_posterior: the prior and the output must be 4-byte aligned");
+    return launch_heat_posterior(d_logits, precise, n, n, *spec, d_prior, d_post_out, static_cast<hipStream_t>(stream));
+}
+
 int metro_place_covariances(const float* d_cov01, const float* d_peak, const MetroPlacement* d_records, int32_t n, int32_t n_views,
                             const MetroSpec* spec, const int32_t* d_mirror, int32_t coords, float* d_cov_out, float* d_peak_out,
                             void* stream) {

@@ -125,6 +125,63 @@ def moments_from_logits(logits: torch.Tensor, spec: ModelSpec, precise: int = 1)
     return c01, cov6_to_3x3(cov), peak
 
 
+def _heat_logits(logits: torch.Tensor, spec: ModelSpec, precise: int) -> torch.Tensor:
+    if logits.dim() != 4 or logits.shape[0] < 1 or tuple(logits.shape[1:]) != (spec.heatmap_side, spec.heatmap_side, spec.n_head_channels):
+        raise ValueError(f'logits must be [N,{spec.heatmap_side},{spec.heatmap_side},{spec.n_head_channels}]')
+    if precise not in (0, 1, 2):
+        raise ValueError(f'precise must be 0, 1 or 2, got {precise!r}')
+    return logits.to(torch.float64 if precise == 2 else torch.float32).contiguous()
+
+
+def marginals_from_logits(logits: torch.Tensor, spec: ModelSpec, precise: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp32 (precise 0/1) or fp64 (precise 2) NHWC logits [N,S,S,D*J] -> (xy [N,Jout,S,S], z [N,Jout,D]): the heat-map marginals
+    of a forward with bound heat-map buffers (metro_plan_bind_heatmaps), from the caller's logits, output joint order."""
+    lib = _lib.load()
+    logits = _heat_logits(logits, spec, precise)
+    n, nj, side, dev = logits.shape[0], spec.skeleton.n_out, spec.heatmap_side, logits.device
+    cs = spec.to_c(int(precise))
+    scratch = torch.empty(lib.metro_heat_marginals_scratch_bytes(C.byref(cs), n), dtype=torch.uint8, device=dev)
+    xy = torch.empty((n, nj, side, side), dtype=torch.float32, device=dev)
+    z = torch.empty((n, nj, spec.depth), dtype=torch.float32, device=dev)
+    check(lib.metro_heat_marginals(_p(logits), n, C.byref(cs), int(precise), _p(scratch), _p(xy), _p(z), _stream(dev)),
+          'metro_heat_marginals')
+    return xy, z
+
+
+def modes_from_logits(logits: torch.Tensor, spec: ModelSpec, k: int = 2, radius: int = 1,
+                      precise: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Logits as above -> (voxel int32 [N,Jout,k], stats [N,Jout,k,11]: mass, peak, coords01, cov01): the heat-map modes of a
+    forward with bound mode buffers (metro_plan_bind_modes), from the caller's logits, output joint order."""
+    lib = _lib.load()
+    logits = _heat_logits(logits, spec, precise)
+    for name, v, lo, hi in (('k', k, 1, _lib.METRO_MAX_MODES), ('radius', radius, 0, _lib.METRO_MAX_MODE_RADIUS)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f'{name} must be an int in [{lo}, {hi}], got {v!r}')
+    n, nj, dev = logits.shape[0], spec.skeleton.n_out, logits.device
+    cs = spec.to_c(int(precise))
+    voxel = torch.empty((n, nj, k), dtype=torch.int32, device=dev)
+    stats = torch.empty((n, nj, k, 11), dtype=torch.float32, device=dev)
+    check(lib.metro_heat_modes(_p(logits), n, C.byref(cs), int(precise), k, radius, _p(voxel), _p(stats), _stream(dev)),
+          'metro_heat_modes')
+    return voxel, stats
+
+
+def posterior_from_logits(logits: torch.Tensor, prior: torch.Tensor, spec: ModelSpec, precise: int = 1) -> torch.Tensor:
+    """Logits as above and prior rows [N,Jout,9] (mu, precision) -> post [N,Jout,11]: the heat-map posterior of a forward with
+    bound prior buffers (metro_plan_bind_prior), from the caller's logits, output joint order."""
+    lib = _lib.load()
+    logits = _heat_logits(logits, spec, precise)
+    n, nj, dev = logits.shape[0], spec.skeleton.n_out, logits.device
+    if tuple(prior.shape) != (n, nj, 9):
+        raise ValueError(f'prior must be [{n},{nj},9], got {tuple(prior.shape)}')
+    prior = prior.to(device=dev, dtype=torch.float32).contiguous()
+    cs = spec.to_c(int(precise))
+    post = torch.empty((n, nj, 11), dtype=torch.float32, device=dev)
+    check(lib.metro_heat_posterior(_p(logits), n, C.byref(cs), int(precise), _p(prior), _p(post), _stream(dev)),
+          'metro_heat_posterior')
+    return post
+
+
 _COORDS = {'crop': _lib.METRO_COORDS_CROP, 'camera': _lib.METRO_COORDS_CAMERA, 'world': _lib.METRO_COORDS_WORLD}
 
 

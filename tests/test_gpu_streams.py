@@ -257,6 +257,22 @@ def _softargmax01_moments(ctx, which):
     return MH.moments_from_logits(ctx.up(_logits(which)), H36M, 1)
 
 
+@case('metro_heat_marginals')
+def _heat_marginals(ctx, which):
+    return MH.marginals_from_logits(ctx.up(_logits(which)), H36M, 1)
+
+
+@case('metro_heat_modes')
+def _heat_modes(ctx, which):
+    return MH.modes_from_logits(ctx.up(_logits(which)), H36M, 2, 1, 1)
+
+
+@case('metro_heat_posterior')
+def _heat_posterior(ctx, which):
+    from tests.test_gpu_heat_posterior import make_prior
+    return MH.posterior_from_logits(ctx.up(_logits(which)), make_prior(2, H36M.skeleton.n_out, ctx.dev, seed=3 + int(which == 'B')), H36M, 1)
+
+
 case('metro_head_f16')(_nf_problem('_build_head', (H36M, 1), ['x']))
 
 

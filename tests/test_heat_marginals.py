@@ -139,6 +139,8 @@ extern "C" int host_heat_marginals(const void* logits, int precise, int n, int s
     else walk<double, double>(static_cast<const double*>(logits), n, side, J, D, perm, n_out, xy, z);
     return metro::hm_tiles(side * side);
 }
+extern "C" int host_tile_pixels(int pixels) { return metro::hm_tile_pixels(pixels); }
+extern "C" int host_chunk_pixels(int pixels, int C, int acc_bytes) { return metro::hm_chunk_pixels(pixels, C, acc_bytes); }
 '''
 SIDES = (2, 3, 7, 16, 24)
 HEADS = ((17, 8), (19, 8), (53, 8), (17, 4), (1, 4))

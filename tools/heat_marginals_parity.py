@@ -3,11 +3,13 @@
   host/<accumulator, logits>     heat_marginals.hip's arithmetic compiled for the host (tests/test_heat_marginals.py)
   gpu/<precision>/<head>         the bound forward against the logits of the same forward (tests/test_gpu_heat_marginals.py)
   gpu/f64/golden-oracle          precision 'f64' end to end against the fp64 oracle's logits
+  gpu/<accumulator, logits>      the kernel-level entry on the crafted volumes of tests/test_gpu_heat_volumes.py
 The tests assert heat_marginals_ref.GATE (4) times these figures.  The reference is always the restatement or the oracle.
 
-    python tools/heat_marginals_parity.py [--host-only]
+    python tools/heat_marginals_parity.py [--host-only | --volumes-only]
 
-Without a GPU (or with --host-only) the gpu/ keys of an existing file are kept as they are."""
+Without a GPU (or with --host-only) the gpu/ keys of an existing file are kept as they are; --volumes-only measures the
+gpu/<accumulator, logits> keys alone and keeps every other key."""
 import json
 import os
 import pathlib
@@ -24,18 +26,22 @@ def main(argv):
     rec = {'worst': {}, 'smallest_voxels': {}}
     if os.path.exists(HR.PARITY):
         rec = HR.recorded()
+    volumes_only = '--volumes-only' in argv
     with tempfile.TemporaryDirectory() as tmp:
         import ctypes as C
-        dll = TH.compile_for_host(pathlib.Path(tmp), 'host_heat_marginals', ['heat_marginals.hip'], TH.HOST_BODY)
-        dll.host_heat_marginals.restype = C.c_int
-        dll.host_heat_marginals.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                            C.c_void_p]
-        for key, (a, r) in TH.host_deviations(dll).items():
+        dll = None if volumes_only else TH.compile_for_host(pathlib.Path(tmp), 'host_heat_marginals', ['heat_marginals.hip'], TH.HOST_BODY)
+        if dll is not None:
+            dll.host_heat_marginals.restype = C.c_int
+            dll.host_heat_marginals.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_void_p]
+        for key, (a, r) in (TH.host_deviations(dll) if dll is not None else {}).items():
             rec['worst'][key] = {'abs': a, 'rel': r}
             rec['smallest_voxels'][key] = min(s * s * d for s in TH.SIDES for _, d in TH.HEADS)
     if '--host-only' not in argv and torch.cuda.is_available():
-        from tests import test_gpu_heat_marginals as TG
-        for key, (a, r, voxels) in TG.gpu_deviations(torch.device('cuda', 0)).items():
+        from tests import test_gpu_heat_marginals as TG, test_gpu_heat_volumes as TV
+        found = {} if volumes_only else TG.gpu_deviations(torch.device('cuda', 0))
+        found.update(TV.gpu_deviations(torch.device('cuda', 0), 'marginals'))
+        for key, (a, r, voxels) in found.items():
             rec['worst'][key] = {'abs': a, 'rel': r}
             rec['smallest_voxels'][key] = voxels
         rec['device'] = torch.cuda.get_device_name(0)
