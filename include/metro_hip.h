@@ -315,6 +315,72 @@ int  metro_plan_bind_modes(MetroPlan* plan, int32_t* d_voxel_out, float* d_stats
  * call.  Unbound, a forward enqueues exactly the kernels it always did. */
 int64_t metro_plan_prior_scratch_bytes(const MetroPlan* plan, int32_t max_n);
 int  metro_plan_bind_prior(MetroPlan* plan, const float* d_prior, float* d_post_out, void* d_scratch, int32_t max_n);
+/* ---- the prior of the posterior above from the track table, bound to the plan ----
+ * metro_plan_bind_prior takes prior rows in heat-map units of one particular crop, a frame no caller has a pose in.  A tracked
+ * joint lives in the camera or the world, in mm, with a covariance (the [T, n_joints_out, 28] constant-velocity table of
+ * metro_associate_tracks / metro_smooth_tracks).  While this is bound, every forward entry (the list above) first writes the
+ * prior rows itself, one launch (track_priors: csrc/track_priors.hip) behind the finalize launch -- and behind the marginal and
+ * modes launches when those are bound -- and then runs the heat_posterior launch of metro_plan_bind_prior on the rows it wrote.
+ * No launching entry is added.  Definition, for crop row i < n and output joint r, fp64 on the stored inputs:
+ *   1. Slot.  s = d_slot[i].  No prior (reason 1) if s is outside [0, capacity).
+ *   2. Source joint.  q = r, or d_mirror[r] where the row's record has det(rot) <= 0 (a flipped test-time view; rot is
+ *      rot_to_world for a world table, else rot_to_orig_cam; metro_merge_views' rule).  No prior (reason 2) if the state
+ *      d_state[s, q] holds none (t_last NaN) or q lies outside the skeleton.
+ *   3. Time.  t = d_times[i]; a non-finite t: no prior (reason 6).  t - t_last > max_age_s: no prior (reason 3).
+ *   4. Prediction.  The constant-velocity prediction of metro_smooth_tracks over dt = max(t - t_last, 0) with q = accel_psd: x
+ *      and P.  C = cov_scale P_pos + sigma_floor_mm^2 I.
+ *   5. Into the crop's virtual camera.  World table: c = rot_to_world^T (x - cam_loc); camera table: c = rot_to_orig_cam^T x.
+ *      C_c = R^T C R.  A non-finite c: no prior (reason 6).  c.z < near_mm: no prior (reason 4).
+ *   6. Pixel.  K = inv(inv_intrinsics) in closed form, fp64 from the fp32 record; (u, v) = the first two rows of K on
+ *      (c.x / c.z, c.y / c.z, 1) (a camera matrix ends in (0, 0, 1)), with the 2x3 Jacobian of that map.
+ *   7. Heat-map units.  mu_xy = ((u, v) - half_stride) / last_receptive_center, the inverse of heatmap_to_image
+ *      (volumetric.py:288-295); the Jacobian is divided by last_receptive_center.  A non-finite mu: no prior (reason 6).
+ *   8. xy precision.  Sigma = J C_c J^T (2x2), L_xy = Sigma^-1 by cofactors.  A non-finite or non-positive determinant: no prior
+ *      (reason 5).
+ *   9. Depth.  The model pins z only relative to the root (volumetric.py:52-56).  METRO_TRACK_PRIOR_DEPTH_NONE: the z row and
+ *      column of L are 0 and mu_z = 0.  METRO_TRACK_PRIOR_DEPTH_ROOT, for every output joint but the root's (head joint
+ *      n_joints_head - 1), when steps 2 to 5 give a point c_root, C_c,root for the root joint of the same slot at the same t:
+ *        mu_z = coords01[i, n_joints_head - 1, 2] + (c.z - c_root.z) / box_size_mm,   L_zz = box_size_mm^2 / (C_c[2,2] + C_c,root[2,2]),
+ *      coords01 the plain soft-argmax output of the same forward; the xz and yz words are 0.  The root's own row, and a joint
+ *      whose root gives no point, have the zero z block.  The z term ignores the correlation of z with the projected xy (a
+ *      joint's depth error also moves its pixel) and the correlation between a joint and its root (the table keeps the joints
+ *      as independent filters); it is anchored at the plain root mean, not at the root's posterior.
+ *   Outputs, rows n .. max_n - 1 untouched:
+ *     d_prior_out  fp32 [max_n, n_joints_out, 9]: mu x, y, z; L xx, yy, zz, xy, xz, yz -- metro_plan_bind_prior's layout, each
+ *                  word rounded to fp32 once; nine zeros where there is no prior, for which the posterior has log_evidence
+ *                  exactly 0 and the plain statistics (its special row);
+ *     d_reason_out int32 [max_n, n_joints_out]: 0 prior given, 1 no slot, 2 no state, 3 too old, 4 behind or too near the
+ *                  camera, 5 covariance not invertible, 6 non-finite input;
+ *     d_post_out   fp32 [max_n, n_joints_out, 11]: metro_plan_bind_prior's output under d_prior_out.
+ * Inputs, all DEVICE memory read when the forward runs: d_state fp64 [capacity, n_joints_out, 28]; d_slot int32 [max_n];
+ * d_times fp64 [max_n]; d_records max_n MetroPlacement; d_mirror int32 [n_joints_out].  `params` is HOST memory, copied at bind
+ * time.  d_scratch: metro_plan_prior_scratch_bytes(plan, max_n) bytes.
+ * Binding is HOST state, as for the binds above; unbind with every pointer NULL and capacity = max_n = 0.  Anything else is
+ * checked in full and returns METRO_ERR_INVALID_ARG: a NULL pointer, the scratch not 16-byte, d_state and d_times not 8-byte or
+ * another pointer not 4-byte aligned, max_n outside [1, the plan's max_batch], capacity outside [1, METRO_ASSOC_MAX], coords
+ * other than METRO_COORDS_CAMERA / METRO_COORDS_WORLD, depth other than the two modes, a negative or non-finite parameter,
+ * DEPTH_ROOT on a skeleton whose output order does not carry head joint n_joints_head - 1, and binding while
+ * metro_plan_bind_prior is bound (metro_plan_bind_prior likewise refuses while this is bound: one prior per forward).
+ * While bound: a forward with n > max_n, or a forward entry called without a coords01 output while DEPTH_ROOT is bound, returns
+ * METRO_ERR_INVALID_ARG before any launch; forwards make PLAIN launches; the head's one fp32 logits store goes to the heat-map
+ * scratch, else to the modes', else to this one.  Poses, coords01, covariance, peak, status words, heat-maps and modes keep the
+ * bits of the unbound call.  Unbound, a forward enqueues exactly the kernels it always did. */
+#define METRO_TRACK_PRIOR_DEPTH_NONE 0
+#define METRO_TRACK_PRIOR_DEPTH_ROOT 1
+typedef struct MetroTrackPrior {
+    int32_t coords;             /* METRO_COORDS_CAMERA or METRO_COORDS_WORLD: the frame of the track table                 */
+    int32_t depth;              /* METRO_TRACK_PRIOR_DEPTH_*                                                                */
+    double accel_psd;           /* q of the constant-velocity model, mm^2 / s^3 (metro_smooth_tracks)                      */
+    double max_age_s;           /* a state older than this at the row's time gives no prior                                */
+    double near_mm;             /* a joint nearer than this to the crop's camera plane gives no prior                      */
+    double sigma_floor_mm;      /* added in quadrature to every axis of the predicted position                             */
+    double cov_scale;           /* factor on the predicted position covariance                                             */
+} MetroTrackPrior;              /* 48 bytes */
+struct MetroPlacement;          /* defined below, with metro_place_poses */
+int  metro_plan_bind_track_prior(MetroPlan* plan, const double* d_state, int32_t capacity, const int32_t* d_slot,
+                                 const double* d_times, const struct MetroPlacement* d_records, const int32_t* d_mirror,
+                                 const MetroTrackPrior* params, float* d_prior_out, int32_t* d_reason_out, float* d_post_out,
+                                 void* d_scratch, int32_t max_n);
 /* Same, stopping after layer `last_layer` (inclusive) so tests can read that layer's output at
  * MetroLayerInfo.out_offset in the workspace.  d_poses_out may be NULL if the finalize layer
  * is not reached. */

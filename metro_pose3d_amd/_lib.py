@@ -117,6 +117,14 @@ class MetroFrameCamera(C.Structure):
                 ('old_matrix', C.c_double * 9)]
 
 
+class MetroTrackPrior(C.Structure):
+    _fields_ = [('coords', C.c_int32), ('depth', C.c_int32), ('accel_psd', C.c_double), ('max_age_s', C.c_double),
+                ('near_mm', C.c_double), ('sigma_floor_mm', C.c_double), ('cov_scale', C.c_double)]
+
+
+METRO_TRACK_PRIOR_DEPTH_NONE, METRO_TRACK_PRIOR_DEPTH_ROOT = 0, 1
+
+
 class MetroView(C.Structure):
     _fields_ = [('cos_roll', C.c_double), ('sin_roll', C.c_double), ('zoom', C.c_double), ('flip', C.c_int32),
                 ('reserved', C.c_int32)]
@@ -151,6 +159,8 @@ SIGNATURES = {
     'metro_plan_bind_modes': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
     'metro_plan_prior_scratch_bytes': (C.c_int64, [_P, C.c_int32]),
     'metro_plan_bind_prior': (C.c_int, [_P, _P, _P, _P, C.c_int32]),
+    'metro_plan_bind_track_prior': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, C.POINTER(MetroTrackPrior), _P, _P, _P, _P,
+                                              C.c_int32]),
     'metro_forward_upto': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32]),
     'metro_forward_timed': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_float)]),
     'metro_conv_f16': (C.c_int, [C.POINTER(MetroConvDesc), _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -130,6 +130,13 @@ int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_
     const bool prior = p->prior.scratch != nullptr && last_layer == nl - 1;
     METRO_CHECK_ARG(!prior || n <= p->prior.max_n, "batch %d exceeds the %d crops the bound prior buffers hold (metro_plan_bind_prior)",
                     n, p->prior.max_n);
+    // a track table bound (metro_plan_bind_track_prior): the prior rows are written behind the finalize launch, the posterior follows
+    const bool track = p->track.scratch != nullptr && last_layer == nl - 1;
+    METRO_CHECK_ARG(!track || n <= p->track.max_n, "batch %d exceeds the %d crops the bound track-prior buffers hold (metro_plan_bind_track_prior)",
+                    n, p->track.max_n);
+    METRO_CHECK_ARG(!track || p->track.params.depth != METRO_TRACK_PRIOR_DEPTH_ROOT || coords01 != nullptr,
+                    "METRO_TRACK_PRIOR_DEPTH_ROOT is bound (metro_plan_bind_track_prior): the forward needs a coords01 output "
+                    "(metro_forward_coords01, metro_forward_u8 or metro_forward_moments with one)");
     float* head_logits = nullptr;
     if (heat && p->head_fused)
         head_logits = heat_marginals_scratch_logits(p->heat.scratch, p->heat.max_n, side, p->spec.n_joints_head, p->spec.depth);
@@ -137,6 +144,8 @@ int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_
         head_logits = static_cast<float*>(p->modes.scratch);
     else if (prior && p->head_fused)
         head_logits = static_cast<float*>(p->prior.scratch);
+    else if (track && p->head_fused)
+        head_logits = static_cast<float*>(p->track.scratch);
 
     std::vector<hipEvent_t> ev;
     if (ms_out) {
@@ -161,6 +170,13 @@ int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_
         st = launch_heat_posterior(head_logits ? head_logits : static_cast<void*>(ws + p->slot_offset[S_LOGITS]),
                                    p->spec.precision == METRO_PREC_F32M ? 1 : p->spec.precision, n, p->prior.max_n, p->spec, p->prior.prior,
                                    p->prior.post, stream);
+    if (track && st == METRO_OK)
+        st = launch_track_priors(p->track.state, p->track.capacity, p->track.slot, p->track.times, p->track.records, p->track.mirror,
+                                 p->track.params, coords01, n, p->spec, p->track.prior, p->track.reason, stream);
+    if (track && st == METRO_OK)
+        st = launch_heat_posterior(head_logits ? head_logits : static_cast<void*>(ws + p->slot_offset[S_LOGITS]),
+                                   p->spec.precision == METRO_PREC_F32M ? 1 : p->spec.precision, n, p->track.max_n, p->spec, p->track.prior,
+                                   p->track.post, stream);
     if (ms_out) {
         if (st == METRO_OK) {
             METRO_HIP_CHECK(hipEventSynchronize(ev.back()));
@@ -270,12 +286,51 @@ int metro_plan_bind_prior(MetroPlan* plan, const float* d_prior, float* d_post_o
         plan->prior.prior = nullptr; plan->prior.post = nullptr; plan->prior.scratch = nullptr; plan->prior.max_n = 0;
         return METRO_OK;
     }
+    METRO_CHECK_ARG(plan->track.scratch == nullptr, "metro_plan_bind_prior: a track table is bound (metro_plan_bind_track_prior): one prior per forward");
     METRO_CHECK_ARG(d_prior != nullptr && d_post_out != nullptr && d_scratch != nullptr,
                     "metro_plan_bind_prior: prior, post_out and the scratch go together (all three, or all NULL with max_n 0 to unbind)");
     METRO_CHECK_ARG(max_n >= 1 && max_n <= plan->max_batch, "metro_plan_bind_prior: max_n %d outside [1, %d]", max_n, plan->max_batch);
     METRO_CHECK_ARG(((uintptr_t)d_scratch & 15) == 0 && ((uintptr_t)d_prior & 3) == 0 && ((uintptr_t)d_post_out & 3) == 0,
                     "metro_plan_bind_prior: the scratch must be 16-byte aligned, the prior and the output 4-byte aligned");
     plan->prior.prior = d_prior; plan->prior.post = d_post_out; plan->prior.scratch = d_scratch; plan->prior.max_n = max_n;
+    return METRO_OK;
+}
+
+int metro_plan_bind_track_prior(MetroPlan* plan, const double* d_state, int32_t capacity, const int32_t* d_slot, const double* d_times,
+                                const MetroPlacement* d_records, const int32_t* d_mirror, const MetroTrackPrior* params, float* d_prior_out,
+                                int32_t* d_reason_out, float* d_post_out, void* d_scratch, int32_t max_n) {
+    METRO_CHECK_ARG(plan != nullptr, "metro_plan_bind_track_prior: plan is NULL");
+    if (!d_state && !d_slot && !d_times && !d_records && !d_mirror && !d_prior_out && !d_reason_out && !d_post_out && !d_scratch &&
+        capacity == 0 && max_n == 0) {                                                                // unbind
+        plan->track = {};
+        return METRO_OK;
+    }
+    METRO_CHECK_ARG(plan->prior.scratch == nullptr, "metro_plan_bind_track_prior: prior rows are bound (metro_plan_bind_prior): one prior per forward");
+    METRO_CHECK_ARG(d_state && d_slot && d_times && d_records && d_mirror && params && d_prior_out && d_reason_out && d_post_out && d_scratch,
+                    "metro_plan_bind_track_prior: the state, slots, times, records, mirror table, parameters, the three outputs and the "
+                    "scratch go together (all of them, or all NULL with capacity and max_n 0 to unbind)");
+    METRO_CHECK_ARG(max_n >= 1 && max_n <= plan->max_batch, "metro_plan_bind_track_prior: max_n %d outside [1, %d]", max_n, plan->max_batch);
+    METRO_CHECK_ARG(capacity >= 1 && capacity <= METRO_ASSOC_MAX, "metro_plan_bind_track_prior: capacity %d outside [1, %d]", capacity,
+                    METRO_ASSOC_MAX);
+    METRO_CHECK_ARG(((uintptr_t)d_scratch & 15) == 0 && ((uintptr_t)d_state & 7) == 0 && ((uintptr_t)d_times & 7) == 0 &&
+                        ((uintptr_t)d_slot & 3) == 0 && ((uintptr_t)d_records & 3) == 0 && ((uintptr_t)d_mirror & 3) == 0 &&
+                        ((uintptr_t)d_prior_out & 3) == 0 && ((uintptr_t)d_reason_out & 3) == 0 && ((uintptr_t)d_post_out & 3) == 0,
+                    "metro_plan_bind_track_prior: the scratch must be 16-byte aligned, the state and the times 8-byte, the others 4-byte");
+    METRO_CHECK_ARG(params->coords == METRO_COORDS_CAMERA || params->coords == METRO_COORDS_WORLD,
+                    "metro_plan_bind_track_prior: coords must be METRO_COORDS_CAMERA or METRO_COORDS_WORLD (got %d)", params->coords);
+    METRO_CHECK_ARG(params->depth == METRO_TRACK_PRIOR_DEPTH_NONE || params->depth == METRO_TRACK_PRIOR_DEPTH_ROOT,
+                    "metro_plan_bind_track_prior: depth must be METRO_TRACK_PRIOR_DEPTH_NONE or _ROOT (got %d)", params->depth);
+    const double values[5] = {params->accel_psd, params->max_age_s, params->near_mm, params->sigma_floor_mm, params->cov_scale};
+    static const char* const names[5] = {"accel_psd", "max_age_s", "near_mm", "sigma_floor_mm", "cov_scale"};
+    for (int i = 0; i < 5; ++i)
+        METRO_CHECK_ARG(__builtin_isfinite(values[i]) && values[i] >= 0.0, "metro_plan_bind_track_prior: %s must be finite and >= 0 (got %g)",
+                        names[i], values[i]);
+    METRO_CHECK_ARG(params->depth != METRO_TRACK_PRIOR_DEPTH_ROOT || track_prior_root_out(plan->spec) >= 0,
+                    "metro_plan_bind_track_prior: METRO_TRACK_PRIOR_DEPTH_ROOT needs the root (head joint %d) in the output order",
+                    plan->spec.n_joints_head - 1);
+    plan->track.state = d_state; plan->track.slot = d_slot; plan->track.times = d_times; plan->track.records = d_records;
+    plan->track.mirror = d_mirror; plan->track.prior = d_prior_out; plan->track.reason = d_reason_out; plan->track.post = d_post_out;
+    plan->track.scratch = d_scratch; plan->track.capacity = capacity; plan->track.max_n = max_n; plan->track.params = *params;
     return METRO_OK;
 }
 
@@ -288,9 +343,9 @@ int metro_plan_set_graph_max_batch(MetroPlan* plan, int32_t max_batch_for_graphs
 static int forward_impl(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out, float* d_coords01,
                         void* d_workspace, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    // heat-map, mode or prior buffers bound: plain launches, the captured forwards do not write them
+    // heat-map, mode, prior or track-prior buffers bound: plain launches, the captured forwards do not write them
     if (plan == nullptr || n > plan->graph_max_batch || n < 1 || plan->heat.scratch != nullptr || plan->modes.scratch != nullptr ||
-        plan->prior.scratch != nullptr)
+        plan->prior.scratch != nullptr || plan->track.scratch != nullptr)
         return run_layers(plan, d_images_nhwc, n, d_poses_out, d_workspace, stream, -1, nullptr, d_coords01);
     // small batches are launch-latency bound (57 dependent launches): replay a captured hipGraph
     GraphEntry* hit = nullptr;

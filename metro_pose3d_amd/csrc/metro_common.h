@@ -510,6 +510,12 @@ int launch_heat_modes(const void* logits, int precise, int n, int max_n, const M
 int64_t heat_posterior_scratch_bytes(int n, int side, int n_joints_head, int depth, bool with_logits);
 int launch_heat_posterior(const void* logits, int precise, int n, int max_n, const MetroSpec& spec, const float* prior, float* post_out,
                           hipStream_t stream);
+// The prior rows of a forward with a track table bound (track_priors.hip): prior [n][J_out][9] and reason [n][J_out] from the
+// table's states, the rows' slots, times and placement records; coords01 is the forward's own (read with DEPTH_ROOT only).
+int track_prior_root_out(const MetroSpec& spec);      // the output joint of head joint J_head - 1, -1: not in the output order
+int launch_track_priors(const double* state, int capacity, const int* slot, const double* times, const MetroPlacement* rec,
+                        const int* mirror, const MetroTrackPrior& params, const float* coords01, int n, const MetroSpec& spec,
+                        float* prior_out, int* reason_out, hipStream_t stream);
 // the volumetric head in one launch (head_f16.hip): postnorm prologue + logits GEMM + per-joint softmax statistics
 bool head_f16_supported(int c_in, int c_head, int n_joints, int depth, int side);
 int head_f16_slabs(int side);               // records per image the partials slot must hold

@@ -76,5 +76,13 @@ struct MetroPlan {
     struct { int32_t* voxel = nullptr; float* stats = nullptr; void* scratch = nullptr; int max_n = 0, k = 0, radius = 0; } modes;
     // metro_plan_bind_prior: the same (heat_posterior.hip)
     struct { const float* prior = nullptr; float* post = nullptr; void* scratch = nullptr; int max_n = 0; } prior;
-    bool head_fused = false;             // the logits stay on chip (LayerForm::Head)
+    // metro_plan_bind_track_prior: the same (track_priors.hip writes `prior`, heat_posterior.hip reads it); params is a copy
+    struct {
+        const double* state = nullptr; const int32_t* slot = nullptr; const double* times = nullptr;
+        const MetroPlacement* records = nullptr; const int32_t* mirror = nullptr;
+        float* prior = nullptr; int32_t* reason = nullptr; float* post = nullptr; void* scratch = nullptr;
+        int capacity = 0, max_n = 0;
+        MetroTrackPrior params{};
+    } track;
+    bool head_fused = false;            // the logits stay on chip (LayerForm::Head)
 };

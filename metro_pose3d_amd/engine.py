@@ -330,6 +330,82 @@ class Engine:
             self.status_words(n).copy_(torch.cat(words))
         return out, post
 
+    def forward_track_posterior(self, images: torch.Tensor, state: torch.Tensor, slot: torch.Tensor, times: torch.Tensor,
+                                records: torch.Tensor, mirror: torch.Tensor, coords: str, depth: str = 'none',
+                                accel_psd: float = 4e6, max_age_s: float = 1.0, near_mm: float = 100.0,
+                                sigma_floor_mm: float = 30.0, cov_scale: float = 1.0, out: Optional[torch.Tensor] = None,
+                                coords01: Optional[torch.Tensor] = None, cov01: Optional[torch.Tensor] = None,
+                                peak: Optional[torch.Tensor] = None, heat_xy: Optional[torch.Tensor] = None,
+                                heat_z: Optional[torch.Tensor] = None):
+        """forward_posterior() whose prior rows the forward writes itself, from a track table -> (poses, post fp32 [n, Jout, 11],
+        prior fp32 [n, Jout, 9], reason int32 [n, Jout]).  All on the plan's device, contiguous, read when the forward runs:
+        state float64 [T, Jout, 28], the constant-velocity table of the follow calls (frames.TrackTable.state), 1 <= T <= 128;
+        slot int32 [n], the table slot of every crop (-1 or outside the table: no prior); times float64 [n], the crops' exposure
+        times in seconds on the clock of the table; records uint8 [n, 208], the crops' MetroPlacement records
+        (frames.pack_placements, or what the view expansion wrote); mirror int32 [Jout], the output-order mirror joints.
+        coords 'camera' or 'world': the frame the table lives in.  depth, accel_psd, max_age_s, near_mm, sigma_floor_mm and
+        cov_scale: heads.track_prior_params, which holds their meaning and says of the defaults that they are design choices,
+        not measurements.  Per crop and output joint the track's state is advanced to the crop's time, projected through the
+        crop's virtual camera and written as the prior row `prior` (nine zeros and a reason word other than 0 where the track
+        gives none: `post` is then the plain distribution's, log_evidence exactly 0); `post` is forward_posterior's under
+        those rows (metro_plan_bind_track_prior, include/metro_hip.h, holds the definition).  Binds chunk by chunk by the rule
+        of forward_posterior and unbinds; every other output keeps the bits forward() gives it.  depth='root' reads the
+        forward's own coords01: one is allocated when none is passed."""
+        from metro_pose3d_amd.heads import ASSOC_MAX, TRACK_STATE_DOUBLES, track_prior_params
+        images = self._check_images(images)
+        n, nj = images.shape[0], self.spec.skeleton.n_out
+        params = track_prior_params(coords, depth, accel_psd, max_age_s, near_mm, sigma_floor_mm, cov_scale)
+        rec_bytes = C.sizeof(_lib.MetroPlacement)
+
+        def given(name, t, dtype, shape, what):
+            if (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != self.device
+                    or not t.is_contiguous()):
+                raise ValueError(f'{name} must be a contiguous {str(dtype).replace("torch.", "")} {list(shape)} tensor on {self.device} '
+                                 f'({what}), got {getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))}')
+        if not isinstance(state, torch.Tensor) or state.dim() != 3 or not 1 <= state.shape[0] <= ASSOC_MAX:
+            raise ValueError(f'state must be a float64 tensor [T, {nj}, {TRACK_STATE_DOUBLES}] with 1 <= T <= {ASSOC_MAX} '
+                             f'(frames.TrackTable.state), got {tuple(getattr(state, "shape", ()))}')
+        given('state', state, torch.float64, (state.shape[0], nj, TRACK_STATE_DOUBLES), 'frames.TrackTable.state')
+        given('slot', slot, torch.int32, (n,), 'the table slot of every crop')
+        given('times', times, torch.float64, (n,), 'the exposure time of every crop, seconds')
+        given('records', records, torch.uint8, (n, rec_bytes), 'the MetroPlacement record of every crop')
+        given('mirror', mirror, torch.int32, (nj,), 'the output-order mirror joints')
+        if records.data_ptr() % 4:
+            records = records.clone()
+        if out is None:
+            out = torch.empty((n, nj, 3), dtype=torch.float32, device=self.device)
+        else:
+            self._check_out('out', out, (n, nj, 3))
+        if depth == 'root' and coords01 is None:
+            coords01 = torch.empty((n, self.spec.skeleton.n_head, 3), dtype=torch.float32, device=self.device)
+        post = torch.empty((n, nj, self.POST_STATS), dtype=torch.float32, device=self.device)
+        prior = torch.empty((n, nj, self.PRIOR_WORDS), dtype=torch.float32, device=self.device)
+        reason = torch.empty((n, nj), dtype=torch.int32, device=self.device)
+        step = self._heat_chunk()
+        nb = int(self.lib.metro_plan_prior_scratch_bytes(self._plan, step))
+        if self._prior is None or self._prior.numel() < nb:
+            self._prior = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        part = lambda t, i, m: None if t is None else t[i:i + m]
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        words = []
+        try:
+            for i in range(0, n, step):
+                m = min(step, n - i)
+                check(self.lib.metro_plan_bind_track_prior(self._plan, ptr(state), int(state.shape[0]), ptr(slot[i:i + m]),
+                                                           ptr(times[i:i + m]), ptr(records[i:i + m]), ptr(mirror), C.byref(params),
+                                                           ptr(prior[i:i + m]), ptr(reason[i:i + m]), ptr(post[i:i + m]),
+                                                           ptr(self._prior), step), 'metro_plan_bind_track_prior')
+                self.forward(images[i:i + m], out[i:i + m], part(coords01, i, m), part(cov01, i, m), part(peak, i, m),
+                             part(heat_xy, i, m), part(heat_z, i, m))
+                if n > step:
+                    words.append(self.status_words(m).clone())
+        finally:
+            check(self.lib.metro_plan_bind_track_prior(self._plan, None, 0, None, None, None, None, None, None, None, None, None, 0),
+                  'metro_plan_bind_track_prior')
+        if words:
+            self.status_words(n).copy_(torch.cat(words))
+        return out, post, prior, reason
+
     def forward(self, images: torch.Tensor, out: Optional[torch.Tensor] = None,
                 coords01: Optional[torch.Tensor] = None, cov01: Optional[torch.Tensor] = None,
                 peak: Optional[torch.Tensor] = None, heat_xy: Optional[torch.Tensor] = None,

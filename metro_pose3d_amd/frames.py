@@ -60,6 +60,11 @@ the box centre, drops the lens distortion, squares the pixels and zooms so the b
                                           the frame's calibrated camera and writes one box per (frame, track), compacted on
                                           the device and fused with whatever boxes a detector did give; the rows go into the
                                           calls above as they are.  Nothing in the reference
+  locate_tracked_poses_in_frames          locate_poses_in_frames between those key frames with each person's own track as the
+                                          prior of each crop's heat-maps (metro_plan_bind_track_prior: the forward writes the
+                                          prior rows from the track table and the posterior behind them): plain and posterior
+                                          poses from the same launches, the posterior covariance and, per joint, the
+                                          log-evidence a tracker gates with.  Nothing in the reference
   Follower                                one followed stream: follow_poses_in_frames or follow_world_poses_in_frames with the
                                           keywords checked once, the assignment rule chosen ('greedy', or 'optimal':
                                           metro_associate_tracks_optimal) and the table of tracks kept between calls
@@ -985,9 +990,33 @@ def _place_poses(eng, coords01, rel, places, scale_recovery: str, coords: str, d
     return poses_v, keypoints_v, z_v, mirror
 
 
+def _forward_tracked(eng, crops: torch.Tensor, check_finite: bool, places, nv: int, state, slots, times, prior: dict):
+    """_forward_coords01 with the track prior bound (Engine.forward_track_posterior) -> (rel, coords01, bad, post [m, Jout, 11],
+    reason [m, Jout]); slots and times hold one value per box and are repeated per view here, on the device."""
+    sk = eng.spec.skeleton
+    m = len(crops)
+    rel = torch.empty((m, sk.n_out, 3), dtype=torch.float32, device=crops.device)
+    coords01 = torch.empty((m, sk.n_head, 3), dtype=torch.float32, device=crops.device)
+    mirror = _upload(np.asarray(sk.out_mirror, np.int32), crops.device)
+    if nv > 1:
+        slots, times = slots.repeat_interleave(nv), times.repeat_interleave(nv)
+    posts, reasons, bad = [], [], None
+    for i in range(0, m, eng.max_batch):
+        k = min(eng.max_batch, m - i)
+        _, post, _, reason = eng.forward_track_posterior(crops[i:i + k], state, slots[i:i + k], times[i:i + k], places[i:i + k], mirror,
+                                                         out=rel[i:i + k], coords01=coords01[i:i + k], **prior)
+        posts.append(post)
+        reasons.append(reason)
+        if check_finite:
+            cnt = eng.status_words(k).ne(0).sum()
+            bad = cnt if bad is None else bad + cnt
+    return rel, coords01, bad, torch.cat(posts), torch.cat(reasons)
+
+
 def _locate_poses_views(call: _Call, model_path, cameras, scale_recovery, targets, per_pose, root_z, coords, sk,
-                        uncertainty: bool = False):
-    """-> (FramePoses, spread [n, Jout])."""
+                        uncertainty: bool = False, tracked=None):
+    """-> (FramePoses, spread [n, Jout]); tracked (the table's state, a slot and a time per box on the device, the prior keywords):
+    (TrackedFramePoses, spread of the plain poses) from the same chain with the track prior bound."""
     from metro_pose3d_amd.inference import _engine_for
     n, nv = len(call.boxes), len(call.vs.zoom)
     m = n * nv
@@ -998,22 +1027,35 @@ def _locate_poses_views(call: _Call, model_path, cameras, scale_recovery, target
         if n == 0:
             f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
             unc = (f32(0, sk.n_out, 3, 3), f32(0, sk.n_out)) if uncertainty else (None, None)
-            return (FramePoses(f32(0, sk.n_out, 3), f32(0, sk.n_out, 2), f32(0) if scale_recovery != 'metro' else None,
-                               sk.edges_array(), names, *unc),
-                    torch.zeros((0, sk.n_out), dtype=torch.float32, device=device))
+            empty = FramePoses(f32(0, sk.n_out, 3), f32(0, sk.n_out, 2), f32(0) if scale_recovery != 'metro' else None,
+                               sk.edges_array(), names, *unc)
+            if tracked is not None:
+                nv0 = (0, nv, sk.n_out)
+                empty = TrackedFramePoses(empty, empty, f32(0, sk.n_out, 3, 3), f32(*nv0), f32(*nv0),
+                                          torch.zeros(nv0, dtype=torch.int32, device=device))
+            return empty, torch.zeros((0, sk.n_out), dtype=torch.float32, device=device)
         crops, places = _warp_views(call.frames, cameras, call.boxes, call.fi, call.vs, eng.spec.proc_side, device, call.crop_dtype)
-        rel, coords01, bad, *mom = _forward_coords01(eng, crops, call.check_finite, uncertainty)
+        if tracked is not None:
+            rel, coords01, bad, post, reason = _forward_tracked(eng, crops, call.check_finite, places, nv, *tracked)
+        else:
+            rel, coords01, bad, *mom = _forward_coords01(eng, crops, call.check_finite, uncertainty)
         if isinstance(targets, torch.Tensor):           # device bone lengths: unread, repeated per view on the device
             d_targets = targets if nv == 1 else targets.repeat_interleave(nv, dim=0)
         else:
             if per_pose:                                # per-box targets, repeated per view by index (box-major rows)
                 targets = np.repeat(targets, nv, axis=0)
             d_targets = _upload(targets, device) if targets is not None else None
-        poses_v, keypoints_v, z_v, mirror = _place_poses(eng, coords01, rel, places, scale_recovery, coords, d_targets, per_pose,
-                                                         np.repeat(root_z, nv) if root_z is not None else None)
+        root_rows = np.repeat(root_z, nv) if root_z is not None else None
+        poses_v, keypoints_v, z_v, mirror = _place_poses(eng, coords01, rel, places, scale_recovery, coords, d_targets, per_pose, root_rows)
         poses, keypoints, z_offset, spread = _merge_views(poses_v, keypoints_v, z_v, places, mirror, n, nv, spread=True)
         unc = tuple(_place_covariances(eng.spec, mom[0][0], mom[0][1], places, coords, n, nv)) if uncertainty else (None, None)
+        if tracked is not None:
+            plain = FramePoses(poses, keypoints, z_offset, sk.edges_array(), names)
+            both = _tracked_frame_poses(eng, plain, post, reason, coords01, places, scale_recovery, coords, d_targets, per_pose,
+                                        root_rows, n, nv)
         _raise_on_non_finite(eng.spec, call.precision, _synchronise(bad, call.boxes)[0], m)     # the call's one stream synchronisation
+    if tracked is not None:
+        return both, spread
     return FramePoses(poses, keypoints, z_offset, sk.edges_array(), names, *unc), spread
 
 
@@ -1872,6 +1914,147 @@ def predict_boxes_in_frames(tracks: TrackTable, cameras, frame_sizes, timestamps
                           rows.n_joints[:n], n_predicted, n_suppressed, n_bad, rows.dense_boxes, rows.dense_joints)
 
 
+# ---- the tracks as the prior of the crops' heat-map posterior: predict -> locate between key frames (metro_plan_bind_track_prior) ----
+
+class TrackedFramePoses(NamedTuple):
+    """What locate_tracked_poses_in_frames returns; every tensor on the call's device."""
+    plain: FramePoses                    # locate_poses_in_frames' result for these boxes, bit for bit
+    posterior: FramePoses                # the same placement and merge on the posterior means (covariance and peak None)
+    posterior_covariance: torch.Tensor   # float32 [n, Jout, 3, 3] mm^2 in the requested coords, views averaged
+    log_evidence: torch.Tensor           # float32 [n, V, Jout]: per view row, unmerged; exactly 0 where reason != 0
+    peak: torch.Tensor                   # float32 [n, V, Jout]: the largest posterior probability of a voxel
+    reason: torch.Tensor                 # int32 [n, V, Jout]: 0 prior given, else why not (heads.REASONS)
+
+
+def _device_slots(track_index, n: int, device: torch.device) -> torch.Tensor:
+    """track_index (host integers or a CUDA integer tensor, one per box) -> int32 [n] on the device, without a synchronisation."""
+    if isinstance(track_index, torch.Tensor) and track_index.is_cuda:
+        if track_index.device != device:
+            raise ValueError(f'track_index is on {track_index.device}, the call runs on {device}')
+        if track_index.is_floating_point() or track_index.is_complex() or track_index.dtype == torch.bool:
+            raise ValueError(f'track_index must hold integers, got {track_index.dtype}')
+        if track_index.numel() != n:
+            raise ValueError(f'track_index must hold {n} values (one per box), got {track_index.numel()}')
+        ti = track_index.reshape(n)
+        if ti.dtype != torch.int32:             # out-of-range values stay out of range through the cast
+            ti = ti.to(torch.int64).clamp(-1, _lib.METRO_ASSOC_MAX).to(torch.int32)
+        return ti.contiguous()
+    ti = np.asarray(_host_array(track_index)).reshape(-1)
+    if ti.dtype.kind not in 'iu' or len(ti) != n:
+        raise ValueError(f'track_index must hold {n} integers (one per box; -1: no track), got {ti.dtype} [{len(ti)}]')
+    return _upload(np.clip(ti.astype(np.int64), -1, _lib.METRO_ASSOC_MAX).astype(np.int32), device)
+
+
+def _device_times(timestamps, frame_index, n: int, device: torch.device) -> torch.Tensor:
+    """timestamps (host data: one per box, or one per frame looked up through frame_index) -> float64 [n] on the device.  A
+    host frame index is looked up on the host (_box_times, with its checks); a CUDA one on the device, clamped to the table
+    (the call's frame check reports an index outside it)."""
+    if isinstance(frame_index, torch.Tensor) and frame_index.is_cuda:
+        ts = np.asarray(_host_array(timestamps), np.float64).reshape(-1)
+        if not np.isfinite(ts).all() or len(ts) == 0:
+            raise ValueError('timestamps must be finite (seconds), one per box or one per frame')
+        d_ts = _upload(ts, device)
+        if len(ts) == n:
+            return d_ts
+        return d_ts.index_select(0, frame_index.reshape(-1).to(torch.int64).clamp(0, len(ts) - 1)).contiguous()
+    fi = np.zeros(n, np.int64) if frame_index is None else np.asarray(_host_array(frame_index), np.int64).reshape(-1)
+    if len(fi) != n:
+        raise ValueError(f'frame_index must hold one value per box ({n}), got {len(fi)}')
+    return _upload(np.ascontiguousarray(_box_times(timestamps, fi, n)), device)
+
+
+def locate_tracked_poses_in_frames(frames, boxes, model_path, cameras, tracks: TrackTable, track_index, frame_index, timestamps,
+                                   table_coords: str = 'camera', depth: str = 'none', accel_psd: float = 4e6,
+                                   max_age_s: float = 1.0, near_mm: float = 100.0, sigma_floor_mm: float = 30.0,
+                                   cov_scale: float = 1.0, scale_recovery: str = 'bone-lengths', bone_lengths=None,
+                                   root_depth=None, coords: str = 'camera', precision: Optional[str] = None,
+                                   check_finite: Optional[bool] = None, views=None, geometry: str = 'auto',
+                                   pixel_format: str = 'rgb', color_matrix: str = 'bt601',
+                                   crop_dtype: str = 'float32') -> TrackedFramePoses:
+    """locate_poses_in_frames with each person's own track as the prior of each crop's heat-maps -> TrackedFramePoses(plain,
+    posterior, posterior_covariance, log_evidence, peak, reason).  Between the key frames of a detector, predict_boxes_in_frames
+    says where to cut the crops; this call also tells the network's read-out where the track expects every joint: a two-peaked
+    joint (a left/right swap, a second person in the crop) resolves to the peak the track agrees with, and exp(log_evidence)
+    is the probability the heat-map gives to the track's region -- the value a tracker gates a measurement with.
+
+    frames, boxes, cameras, frame_index and every keyword from scale_recovery on are locate_poses_in_frames'; cameras must be
+    calibrated (a prior is projected through the crop's virtual camera).  tracks: the TrackTable a follow_* call returned,
+    read, never written.  track_index [n]: the table slot of each box, host integers or a CUDA integer tensor (-1, or a slot
+    outside the table: no prior for that box); timestamps: seconds on the clock of the table, host data, one per box or one
+    per frame looked up through frame_index.  boxes, frame_index and track_index may be the CUDA tensors of PredictedBoxes
+    as they are.  table_coords: 'camera' or 'world', the frame the table lives in (follow_poses_in_frames' coords;
+    'world' for follow_world_poses_in_frames); it need not be `coords`, the frame of the poses returned.
+    depth, accel_psd, max_age_s, near_mm, sigma_floor_mm, cov_scale: heads.track_prior_params.  The defaults sigma_floor_mm =
+    30, cov_scale = 1, near_mm = 100 and depth = 'none' are design choices, not measurements (the reasoning is there);
+    max_age_s and accel_psd are the follow_* calls' own and should be theirs.
+    One enqueue chain and ONE synchronisation, locate_poses_in_frames' own with the track prior bound to the forward
+    (Engine.forward_track_posterior: one more small launch, which writes the prior rows of every crop row from the table --
+    track_index and the times repeated per view on the device, a flipped view reading the mirror joints -- and the posterior
+    launch).  `plain` is locate_poses_in_frames' result, bit for bit.  `posterior` is placed by the same metro_place_poses and
+    metro_merge_views launches on a head-order copy of coords01 whose output joints are replaced by the posterior means (head
+    joints the output order does not carry keep their plain mean; scale_recovery 'metro' roots the posterior means as
+    inference.posterior_to_metric does).  posterior_covariance is the posterior's covariance in `coords`, by
+    metro_place_covariances as FramePoses.covariance.  log_evidence, peak and reason stay per view row.
+    Limits: the prior is only as good as the track -- a track that follows the wrong person pulls the posterior to that
+    person, and log_evidence is the figure to gate on; xy rests on the heatmap_to_image convention every keypoint here rests
+    on; z (depth='root') is anchored at the plain root mean of the same forward; sharded calls are not served.
+    ValueError before any launch for cameras=None, a tracks that is no table or whose joints are not the model's, table_coords
+    other than 'camera' / 'world', any keyword out of range, and whatever locate_poses_in_frames refuses."""
+    from metro_pose3d_amd.heads import track_prior_params
+    call = _checked_call(frames, boxes, frame_index, coords, views, geometry, precision, check_finite, pixel_format,
+                         color_matrix, crop_dtype)
+    if table_coords not in ('camera', 'world'):
+        raise ValueError(f"table_coords must be 'camera' or 'world' (the frame the track table lives in), got {table_coords!r}")
+    prior = dict(coords=table_coords, depth=depth, accel_psd=accel_psd, max_age_s=max_age_s, near_mm=near_mm,
+                 sigma_floor_mm=sigma_floor_mm, cov_scale=cov_scale)
+    track_prior_params(**prior)
+    if cameras is None:
+        raise ValueError('cameras: a track prior is projected through the crop\'s virtual camera and needs calibrated cameras')
+    _check_track_table(tracks)
+    tracks = TrackTable(*tracks)
+    sk = _model_skeleton(model_path)
+    if tracks.state.shape[1] != sk.n_out:
+        raise ValueError(f'the track table holds {tracks.state.shape[1]} joints, the model returns {sk.n_out}')
+    on_device = isinstance(bone_lengths, torch.Tensor) and bone_lengths.is_cuda
+    n = len(call.boxes)
+    targets, per_pose, root_z = _placement_targets(scale_recovery, cameras, n, len(sk.head_edges), bone_lengths, root_depth,
+                                                   _call_device(call.boxes, call.frames) if on_device else None)
+    device = _call_device(call.boxes, call.frames)
+    if tracks.state.device != device:
+        raise ValueError(f'the track table is on {tracks.state.device}, the call runs on {device}')
+    with torch.cuda.device(device):
+        slots = _device_slots(track_index, n, device)
+        d_fi = call.boxes.device_fi if isinstance(call.boxes, _DeviceBoxes) and call.boxes.device_fi is not None else \
+            (call.boxes.host_fi if isinstance(call.boxes, _DeviceBoxes) else call.fi)
+        times = _device_times(timestamps, d_fi, n, device)
+    return _locate_poses_views(call, model_path, cameras, scale_recovery, targets, per_pose, root_z, coords, sk, False,
+                               tracked=(tracks.state, slots, times, prior))[0]
+
+
+def _tracked_frame_poses(eng, plain: FramePoses, post, reason, coords01, places, scale_recovery, coords, d_targets, per_pose, root_z,
+                         n: int, nv: int) -> TrackedFramePoses:
+    """The posterior half of locate_tracked_poses_in_frames, enqueued behind the plain half: the same placement, merge and
+    covariance launches on the posterior's means and covariances."""
+    from metro_pose3d_amd.heads import place_covariances
+    from metro_pose3d_amd.inference import posterior_to_metric
+    sk = eng.spec.skeleton
+    device = post.device
+    perm = _upload(np.asarray(sk.permutation, np.int64), device)
+    c01 = coords01.clone()
+    c01.index_copy_(1, perm, post[..., 2:5].contiguous())
+    rel = posterior_to_metric(eng.spec, post, coords01).poses.contiguous() if scale_recovery == 'metro' else None
+    poses_v, keypoints_v, z_v, mirror = _place_poses(eng, c01, rel, places, scale_recovery, coords, d_targets, per_pose, root_z)
+    poses, keypoints, z_offset, _ = _merge_views(poses_v, keypoints_v, z_v, places, mirror, n, nv, spread=False)
+    cov_head = torch.zeros((n * nv, sk.n_head, 6), dtype=torch.float32, device=device)
+    cov_head.index_copy_(1, perm, post[..., 5:11].contiguous())
+    peak_head = torch.zeros((n * nv, sk.n_head), dtype=torch.float32, device=device)
+    peak_head.index_copy_(1, perm, post[..., 1].contiguous())
+    cov = place_covariances(cov_head, peak_head, eng.spec, coords, places.reshape(-1) if coords != 'crop' else None, nv)[0]
+    posterior = FramePoses(poses, keypoints, z_offset, plain.joint_edges, plain.joint_names)
+    return TrackedFramePoses(plain, posterior, cov, post[..., 0].reshape(n, nv, sk.n_out).contiguous(),
+                             post[..., 1].reshape(n, nv, sk.n_out).contiguous(), reason.view(n, nv, sk.n_out))
+
+
 # ---- one object per followed stream: the keywords checked once, the table of tracks carried from call to call ----
 
 _FOLLOWER_GIVEN = ('frames', 'boxes', 'model_path', 'cameras', 'frame_index', 'timestamps', 'tracks', 'capacity', 'assignment')
@@ -1958,6 +2141,28 @@ class Follower:
             raise TypeError("Follower.predict: coords is the follower's own")
         coords = 'world' if self.world else self.keywords['coords']
         return predict_boxes_in_frames(self.tracks, self.cameras, frame_sizes, timestamps, coords=coords, **keywords)
+
+    def locate(self, frames, boxes, track_index, frame_index, timestamps, **keywords) -> TrackedFramePoses:
+        """locate_tracked_poses_in_frames on .tracks with the follower's model, cameras, table coordinates, accel_psd, max_age_s
+        and locate keywords (scale_recovery, bone_lengths, root_depth, coords, views, ...); `keywords` override those and take
+        depth, near_mm, sigma_floor_mm and cov_scale.  boxes, frame_index and track_index may be .predict's CUDA tensors."""
+        if self.tracks is None:
+            raise ValueError('Follower.locate: no table of tracks yet (call follow first)')
+        if 'table_coords' in keywords:
+            raise TypeError("Follower.locate: table_coords is the follower's own")
+        table_coords = 'world' if self.world else self.keywords['coords']
+        if table_coords not in ('camera', 'world'):
+            raise ValueError(f"Follower.locate: the follower's tracks live in {table_coords!r} coordinates; a track prior needs a "
+                             "table in 'camera' or 'world' coordinates")
+        import inspect
+        params = inspect.signature(locate_tracked_poses_in_frames).parameters
+        kw = {k: self.keywords[k] for k in ('accel_psd', 'max_age_s') + _LOCATE_OPTIONS if k in self.keywords and k in params}
+        unknown = [k for k in keywords if k not in params or k in _FOLLOWER_GIVEN + ('track_index',)]
+        if unknown:
+            raise TypeError(f'Follower.locate got an unexpected keyword {unknown[0]!r}')
+        kw.update(keywords)
+        return locate_tracked_poses_in_frames(frames, boxes, self.model_path, self.cameras, self.tracks, track_index, frame_index,
+                                              timestamps, table_coords=table_coords, **kw)
 
     def _bone_read_out(self, fallback, required: bool):
         from metro_pose3d_amd.heads import bone_fallback, track_bone_lengths

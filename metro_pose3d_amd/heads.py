@@ -18,6 +18,8 @@ through the C ABI (csrc/heads.hip).  Names and argument meaning follow the refer
                             CSR grouping smooth_tracks reads, one workgroup
   predict_boxes             next-frame person boxes from the track table: the filter's prediction of every live track through
                             the frames' calibrated cameras, compacted on the device and fused with a detector's boxes
+  track_prior_params        the options of the track-predicted heat-map prior (Engine.forward_track_posterior,
+                            frames.locate_tracked_poses_in_frames), checked
   smooth_tracks             poses of tracked persons over time: constant-velocity Kalman filter / RTS smoother per track and
                             joint, each row weighted by its heat-map covariance (nothing in the reference: one image each)
   track_bone_lengths        the bone lengths of followed persons, learned per track slot from their triangulated joints: a
@@ -1007,6 +1009,39 @@ def prediction_params(expand, n_sigma, max_sigma_mm, min_joints, max_age_s, near
     return (_finite('accel_psd', accel_psd, 0, False), _finite('max_age_s', max_age_s, 0, True), _finite('expand', expand, 1, True),
             _finite('n_sigma', n_sigma, 0, True), _finite('max_sigma_mm', max_sigma_mm, 0, True), _finite('near_mm', near_mm, 0, False),
             _finite('min_side_px', min_side_px, 0, True)), _finite('iou_max', iou_max, 0, False, 1)
+
+
+TRACK_PRIOR_DEPTH = {'none': _lib.METRO_TRACK_PRIOR_DEPTH_NONE, 'root': _lib.METRO_TRACK_PRIOR_DEPTH_ROOT}
+REASONS = ('prior given', 'no slot', 'no state', 'too old', 'behind or too near the camera', 'covariance not invertible',
+           'non-finite input')                     # the reason words metro_plan_bind_track_prior writes, by value
+
+
+def track_prior_params(coords='camera', depth='none', accel_psd=4e6, max_age_s=1.0, near_mm=100.0, sigma_floor_mm=30.0,
+                       cov_scale=1.0) -> '_lib.MetroTrackPrior':
+    """Checks the keywords of Engine.forward_track_posterior / frames.locate_tracked_poses_in_frames; -> the MetroTrackPrior
+    record metro_plan_bind_track_prior copies.  coords: 'camera' or 'world', the frame of the track table ('crop' is refused: a
+    crop's own camera differs from box to box, no table lives in it); depth: 'none' (no knowledge along z) or 'root' (z
+    relative to the root, anchored at the root's plain coords01 z of the same forward); accel_psd > 0 and max_age_s >= 0 are the
+    follow_* calls' own and should be theirs; near_mm > 0; sigma_floor_mm >= 0; cov_scale >= 0, and not both zero.
+    The defaults sigma_floor_mm = 30, cov_scale = 1, near_mm = 100 and depth = 'none' are design choices, not measurements: a
+    filter that has seen a joint a hundred times reports millimetres, less than a heat-map voxel and less than what a constant-
+    velocity model misses of a limb that turns, and 30 mm (about one voxel of a 2.2 m box at S = 64) keeps such a prior from
+    overruling the image; the predicted covariance is taken at face value; nothing nearer than 100 mm is a person in front of
+    a lens (predict_boxes' rule); and z stays out of the prior unless asked for, because its anchor is the plain root mean."""
+    if coords not in ('camera', 'world'):
+        raise ValueError(f"coords must be 'camera' or 'world' (the frame of the track table; no table lives in a crop's), got {coords!r}")
+    if depth not in TRACK_PRIOR_DEPTH:
+        raise ValueError(f"depth must be 'none' or 'root', got {depth!r}")
+    p = _lib.MetroTrackPrior()
+    p.coords, p.depth = _COORDS[coords], TRACK_PRIOR_DEPTH[depth]
+    p.accel_psd = _finite('accel_psd', accel_psd, 0, False)
+    p.max_age_s = _finite('max_age_s', max_age_s, 0, True)
+    p.near_mm = _finite('near_mm', near_mm, 0, False)
+    p.sigma_floor_mm = _finite('sigma_floor_mm', sigma_floor_mm, 0, True)
+    p.cov_scale = _finite('cov_scale', cov_scale, 0, True)
+    if p.sigma_floor_mm == 0.0 and p.cov_scale == 0.0:
+        raise ValueError('sigma_floor_mm and cov_scale are both 0: every prior would have a singular covariance')
+    return p
 
 
 def predict_boxes(state: torch.Tensor, ids: torch.Tensor, cameras, frame_sizes, times, coords: str = 'camera', detections=None,
