@@ -381,6 +381,72 @@ int  metro_plan_bind_track_prior(MetroPlan* plan, const double* d_state, int32_t
                                  const double* d_times, const struct MetroPlacement* d_records, const int32_t* d_mirror,
                                  const MetroTrackPrior* params, float* d_prior_out, int32_t* d_reason_out, float* d_post_out,
                                  void* d_scratch, int32_t max_n);
+/* ---- a person's heat-maps from several cameras, fused on a grid of world points, bound to the plan ----
+ * Nothing in the reference (its examples have one camera each).  metro_triangulate_joints reduces every crop to the mean of its
+ * heat-map before the cameras meet; the mean of a two-peaked joint lies between the peaks and bends that camera's ray.  The
+ * exact multi-view answer keeps the distributions: the product of the cameras' xy marginals along their rays, evaluated on a
+ * grid of world points.  A wrong peak in one camera finds no partner in the others and vanishes from the product.  With TWO
+ * cameras the wrong peak's ray still meets the other camera's ray and nothing resolves it: that is inherent, three views are
+ * needed.  The bilinear probabilities are a coarser model than the soft-argmax, so on clean heat-maps the triangulated point
+ * is the better one: the fusion is returned beside it and replaces nothing.
+ * While this is bound, every forward entry (the list above) ends with the launch view_fusion (csrc/view_fusion.hip), one
+ * workgroup per (person, output joint), behind the marginal launches (and every other bound launch) of the same forward, and
+ * -- with d_centres NULL -- first with the launch of metro_triangulate_joints on the forward's own coords01 and cov01, the
+ * bound CSR, records, mirror table, weights and min_det, whose points go to d_centres_out, bit for bit what that entry gives
+ * on the same inputs (its n_rays and residual pass through d_info_out and d_stats_out, which view_fusion then overwrites).
+ * With d_centres given (a track's prediction, say) those are copied to d_centres_out and no triangulation runs.  No launching
+ * entry is added.  Definition, for person p < n_persons and output joint r, n the forward's crops; fp64 arithmetic on the
+ * stored fp32 inputs, each output rounded to fp32 once:
+ *   Grid.     X[a,b,c] = centre + (g[a], g[b], g[c]), g[i] = -extent_mm / 2 + i extent_mm / (G - 1), the axes world x, y, z; the
+ *             point's index is v = (a G + b) G + c.  A centre that is not finite: NaN in every float output, rows used 0, edge 0.
+ *   Rows.     The person's group is d_rows[d_starts[p] : d_starts[p + 1]] with metro_triangulate_joints' clamping.  Row i uses
+ *             the map d_xy[i, flipped ? d_mirror[r] : r], flipped = !(det rot_to_world > 0) (metro_place_poses' rule).
+ *   Skipped.  A row outside [0, n); a row whose record has a non-finite inv_intrinsics, rot_to_world or cam_loc entry; a row
+ *             whose mirror joint lies outside the skeleton; a row whose map has a non-finite cell (the marginals' NaN rule
+ *             for a bad joint).  Skipped rows are not counted.
+ *   Project.  c = rot_to_world^T (X - cam_loc); K = inv(inv_intrinsics) in closed form; (u, v) = the first two rows of K on
+ *             (c.x / c.z, c.y / c.z, 1); m = ((u, v) - half_stride) / last_receptive_center, the inverse of heatmap_to_image;
+ *             f = m (S - 1).
+ *   Sample.   If c.z > near_mm and 0 <= f.x, f.y <= S - 1: x0 = min(floor(f.x), S - 2), likewise y0, p the bilinear value of
+ *             the four cells (never above the map's largest cell), l = ln max(p, floor).  Otherwise l = ln floor.
+ *   Energy.   E[v] = (1 / n_views) sum over the used rows of l, in row order.
+ *   Softmax.  M = max E at the lowest v among equals; w = exp(E - M) / sum exp(E - M).
+ *   Outputs:
+ *     d_points_out  fp32 [n_persons, n_joints_out, 3]: sum w X, world mm;
+ *     d_cov_out     fp32 [n_persons, n_joints_out, 9]: the central second moments of X under w, mm^2, row-major symmetric 3x3
+ *                   (the layout metro_smooth_tracks reads);
+ *     d_stats_out   fp32 [n_persons, n_joints_out, 2]: max w, and agreement = M - (1 / n_views) sum over the used rows of
+ *                   ln max(largest cell of the row's map, floor): <= 0, near 0 when all cameras' peaks meet in one point;
+ *     d_info_out    int32 [n_persons, n_joints_out, 2]: the rows used, and edge = 1 when the point of M has an index 0 or G - 1
+ *                   on some axis (the cube was too small);
+ *     d_centres_out fp32 [n_persons, n_joints_out, 3]: the centres used.
+ *   A group with no usable row has NaN in points, cov and stats, and (0, 0) in info.
+ * Inputs, all DEVICE memory read when the forward runs: d_xy fp32 [max_n, n_joints_out, S, S], S the heat-map side -- in the
+ * product the very buffer metro_plan_bind_heatmaps writes, but any buffer will do and the heat-map binding is not required;
+ * d_records max_n MetroPlacement; d_rows int32 [n_rows]; d_starts int32 [n_persons + 1]; d_mirror int32 [n_joints_out];
+ * d_centres fp32 [n_persons, n_joints_out, 3] or NULL.  `params` is HOST memory, copied at bind time.
+ * Binding is HOST state, as for the binds above; unbind with every pointer NULL and n_rows = n_persons = max_n = 0.  Anything
+ * else is checked in full and returns METRO_ERR_INVALID_ARG: a NULL pointer other than d_centres, a pointer not 4-byte
+ * aligned, max_n outside [1, the plan's max_batch], n_rows or n_persons negative, grid outside [2, 16], n_views < 1, weights
+ * other than METRO_TRI_UNIFORM / METRO_TRI_COVARIANCE, extent_mm not finite and > 0, floor outside (0, 1), near_mm not finite
+ * and >= 0, min_det not finite, and a plan whose heat-map side is below 2.
+ * While bound: a forward with n > max_n -- and, with d_centres NULL, a forward entry without a coords01 output, or under
+ * METRO_TRI_COVARIANCE without a cov01 output -- returns METRO_ERR_INVALID_ARG before any launch; forwards make PLAIN launches
+ * (the hipGraph cache does not serve them).  Every other output keeps the bits of the unbound call.  Unbound, a forward
+ * enqueues exactly the kernels it always did. */
+typedef struct MetroViewFusion {
+    int32_t grid;               /* G points per axis, 2..16                                                                */
+    int32_t n_views;            /* V >= 1: the rows per camera (test-time views); a row counts 1 / V                       */
+    int32_t weights;            /* METRO_TRI_UNIFORM or METRO_TRI_COVARIANCE, of the internal triangulation                */
+    double extent_mm;           /* the cube's side, > 0 (at offset 16)                                                     */
+    double floor;               /* the least probability a row gives a point, in (0, 1)                                    */
+    double near_mm;             /* a point nearer than this to a camera's plane takes the floor there, >= 0                */
+    double min_det;             /* of the internal triangulation (metro_triangulate_joints)                                */
+} MetroViewFusion;              /* 48 bytes; copied at bind */
+int  metro_plan_bind_view_fusion(MetroPlan* plan, const float* d_xy, const struct MetroPlacement* d_records, const int32_t* d_rows,
+                                 int32_t n_rows, const int32_t* d_starts, int32_t n_persons, const int32_t* d_mirror,
+                                 const float* d_centres, const MetroViewFusion* params, float* d_points_out, float* d_cov_out,
+                                 float* d_stats_out, int32_t* d_info_out, float* d_centres_out, int32_t max_n);
 /* Same, stopping after layer `last_layer` (inclusive) so tests can read that layer's output at
  * MetroLayerInfo.out_offset in the workspace.  d_poses_out may be NULL if the finalize layer
  * is not reached. */

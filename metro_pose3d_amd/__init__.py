@@ -26,6 +26,9 @@ Public surface (mirrors reference inference.py):
     locate_tracked_poses_in_frames(frames, boxes, model_path, cameras, tracks, track_index, frame_index, timestamps) ->
         locate_poses_in_frames with each person's own track as the prior of each crop's heat-maps: the plain poses, the
         posterior poses and covariance, and per joint the log-evidence a tracker gates with (Follower.locate)
+    fuse_poses_in_frames(frames, boxes, model_path, cameras, person_index, frame_index) -> triangulate_poses_in_frames
+        and, beside it, every person's heat-maps fused over its cameras on a grid of world points: a wrong peak in one
+        camera finds no partner in the others (FusedPoses: the triangulation bit for bit, the fused poses, covariance, ...)
     Follower(model_path, cameras, world=False, assignment='greedy', ...) -> one of the two follow calls with its keywords
         and its table of tracks kept from call to call: .follow(frames, boxes, frame_index, timestamps), .predict(...),
         .locate(frames, boxes, track_index, frame_index, timestamps);
@@ -37,7 +40,7 @@ container (save_model / load_model) and batch sharding over the GPUs of a node (
 from metro_pose3d_amd.spec import ModelSpec  # noqa: F401
 from metro_pose3d_amd.modelfile import load_model, save_model  # noqa: F401
 
-__all__ = ['ModelSpec', 'load_model', 'save_model', 'Engine', 'estimate_pose', 'Heatmaps', 'estimate_pose_modes', 'Modes', 'estimate_pose_posterior', 'Posterior', 'pose_prior', 'posterior_to_metric', 'estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'follow_rig_poses_in_frames', 'predict_boxes_in_frames', 'locate_tracked_poses_in_frames', 'frame_sizes', 'Follower', 'Camera']
+__all__ = ['ModelSpec', 'load_model', 'save_model', 'Engine', 'estimate_pose', 'Heatmaps', 'estimate_pose_modes', 'Modes', 'estimate_pose_posterior', 'Posterior', 'pose_prior', 'posterior_to_metric', 'estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'follow_rig_poses_in_frames', 'predict_boxes_in_frames', 'locate_tracked_poses_in_frames', 'fuse_poses_in_frames', 'FusedPoses', 'frame_sizes', 'Follower', 'Camera']
 
 
 def __getattr__(name):
@@ -54,7 +57,7 @@ def __getattr__(name):
     if name in ('estimate_pose_modes', 'Modes', 'estimate_pose_posterior', 'Posterior', 'pose_prior', 'posterior_to_metric'):
         from metro_pose3d_amd import inference
         return getattr(inference, name)
-    if name in ('estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'follow_rig_poses_in_frames', 'predict_boxes_in_frames', 'locate_tracked_poses_in_frames', 'frame_sizes', 'Follower', 'Camera'):
+    if name in ('estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'follow_rig_poses_in_frames', 'predict_boxes_in_frames', 'locate_tracked_poses_in_frames', 'fuse_poses_in_frames', 'FusedPoses', 'frame_sizes', 'Follower', 'Camera'):
         from metro_pose3d_amd import frames
         return getattr(frames, name)
     raise AttributeError(name)

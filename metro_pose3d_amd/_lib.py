@@ -125,6 +125,11 @@ class MetroTrackPrior(C.Structure):
 METRO_TRACK_PRIOR_DEPTH_NONE, METRO_TRACK_PRIOR_DEPTH_ROOT = 0, 1
 
 
+class MetroViewFusion(C.Structure):
+    _fields_ = [('grid', C.c_int32), ('n_views', C.c_int32), ('weights', C.c_int32), ('extent_mm', C.c_double),
+                ('floor', C.c_double), ('near_mm', C.c_double), ('min_det', C.c_double)]
+
+
 class MetroView(C.Structure):
     _fields_ = [('cos_roll', C.c_double), ('sin_roll', C.c_double), ('zoom', C.c_double), ('flip', C.c_int32),
                 ('reserved', C.c_int32)]
@@ -161,6 +166,8 @@ SIGNATURES = {
     'metro_plan_bind_prior': (C.c_int, [_P, _P, _P, _P, C.c_int32]),
     'metro_plan_bind_track_prior': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, C.POINTER(MetroTrackPrior), _P, _P, _P, _P,
                                               C.c_int32]),
+    'metro_plan_bind_view_fusion': (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(MetroViewFusion), _P, _P, _P,
+                                              _P, _P, C.c_int32]),
     'metro_forward_upto': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32]),
     'metro_forward_timed': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_float)]),
     'metro_conv_f16': (C.c_int, [C.POINTER(MetroConvDesc), _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -137,6 +137,17 @@ int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_
     METRO_CHECK_ARG(!track || p->track.params.depth != METRO_TRACK_PRIOR_DEPTH_ROOT || coords01 != nullptr,
                     "METRO_TRACK_PRIOR_DEPTH_ROOT is bound (metro_plan_bind_track_prior): the forward needs a coords01 output "
                     "(metro_forward_coords01, metro_forward_u8 or metro_forward_moments with one)");
+    // a view fusion bound (metro_plan_bind_view_fusion): the last launches of the forward; without the caller's centres the
+    // triangulation reads this forward's own coords01 (and cov01 under METRO_TRI_COVARIANCE)
+    const bool fusion = p->fusion.points != nullptr && last_layer == nl - 1;
+    METRO_CHECK_ARG(!fusion || n <= p->fusion.max_n, "batch %d exceeds the %d crops the bound view-fusion buffers hold (metro_plan_bind_view_fusion)",
+                    n, p->fusion.max_n);
+    METRO_CHECK_ARG(!fusion || p->fusion.centres != nullptr || coords01 != nullptr,
+                    "a view fusion without centres is bound (metro_plan_bind_view_fusion): the forward needs a coords01 output "
+                    "(metro_forward_coords01, metro_forward_u8 or metro_forward_moments with one)");
+    METRO_CHECK_ARG(!fusion || p->fusion.centres != nullptr || p->fusion.params.weights != METRO_TRI_COVARIANCE || mo.cov01 != nullptr,
+                    "a view fusion without centres is bound with METRO_TRI_COVARIANCE (metro_plan_bind_view_fusion): the forward needs "
+                    "a cov01 output (metro_forward_moments with one)");
     float* head_logits = nullptr;
     if (heat && p->head_fused)
         head_logits = heat_marginals_scratch_logits(p->heat.scratch, p->heat.max_n, side, p->spec.n_joints_head, p->spec.depth);
@@ -177,6 +188,16 @@ int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_
         st = launch_heat_posterior(head_logits ? head_logits : static_cast<void*>(ws + p->slot_offset[S_LOGITS]),
                                    p->spec.precision == METRO_PREC_F32M ? 1 : p->spec.precision, n, p->track.max_n, p->spec, p->track.prior,
                                    p->track.post, stream);
+    // the triangulation's n_rays and residual pass through info and stats, which the fusion launch overwrites
+    if (fusion && p->fusion.centres == nullptr && p->fusion.n_persons > 0 && st == METRO_OK)
+        st = launch_triangulate_joints(coords01, p->fusion.params.weights == METRO_TRI_COVARIANCE ? mo.cov01 : nullptr, p->fusion.records, n,
+                                       p->fusion.rows, p->fusion.n_rows, p->fusion.starts, p->fusion.n_persons, p->spec, p->fusion.mirror,
+                                       p->fusion.params.weights, p->fusion.params.min_det, p->fusion.centres_out, p->fusion.info,
+                                       p->fusion.stats, nullptr, stream);
+    if (fusion && st == METRO_OK)
+        st = launch_view_fusion(p->fusion.xy, p->fusion.records, p->fusion.rows, p->fusion.n_rows, p->fusion.starts, p->fusion.n_persons,
+                                p->fusion.mirror, p->fusion.centres, p->fusion.params, n, p->spec, p->fusion.points, p->fusion.cov,
+                                p->fusion.stats, p->fusion.info, p->fusion.centres_out, stream);
     if (ms_out) {
         if (st == METRO_OK) {
             METRO_HIP_CHECK(hipEventSynchronize(ev.back()));
@@ -334,6 +355,47 @@ int metro_plan_bind_track_prior(MetroPlan* plan, const double* d_state, int32_t 
     return METRO_OK;
 }
 
+int metro_plan_bind_view_fusion(MetroPlan* plan, const float* d_xy, const MetroPlacement* d_records, const int32_t* d_rows, int32_t n_rows,
+                                const int32_t* d_starts, int32_t n_persons, const int32_t* d_mirror, const float* d_centres,
+                                const MetroViewFusion* params, float* d_points_out, float* d_cov_out, float* d_stats_out,
+                                int32_t* d_info_out, float* d_centres_out, int32_t max_n) {
+    METRO_CHECK_ARG(plan != nullptr, "metro_plan_bind_view_fusion: plan is NULL");
+    if (!d_xy && !d_records && !d_rows && !d_starts && !d_mirror && !d_centres && !params && !d_points_out && !d_cov_out && !d_stats_out &&
+        !d_info_out && !d_centres_out && n_rows == 0 && n_persons == 0 && max_n == 0) {               // unbind
+        plan->fusion = {};
+        return METRO_OK;
+    }
+    METRO_CHECK_ARG(d_xy && d_records && d_rows && d_starts && d_mirror && params && d_points_out && d_cov_out && d_stats_out && d_info_out &&
+                        d_centres_out,
+                    "metro_plan_bind_view_fusion: the marginals, records, rows, starts, mirror table, parameters and the five outputs go "
+                    "together (all of them, or all NULL with n_rows, n_persons and max_n 0 to unbind); only d_centres may be NULL");
+    METRO_CHECK_ARG(max_n >= 1 && max_n <= plan->max_batch, "metro_plan_bind_view_fusion: max_n %d outside [1, %d]", max_n, plan->max_batch);
+    METRO_CHECK_ARG(n_rows >= 0 && n_persons >= 0, "metro_plan_bind_view_fusion: negative size (n_rows %d, n_persons %d)", n_rows, n_persons);
+    METRO_CHECK_ARG((int64_t)n_persons * plan->spec.n_joints_out <= (int64_t)0x7fffffff / 9,
+                    "metro_plan_bind_view_fusion: n_persons %d overflows int32", n_persons);
+    METRO_CHECK_ARG((((uintptr_t)d_xy | (uintptr_t)d_records | (uintptr_t)d_rows | (uintptr_t)d_starts | (uintptr_t)d_mirror |
+                      (uintptr_t)d_centres | (uintptr_t)d_points_out | (uintptr_t)d_cov_out | (uintptr_t)d_stats_out | (uintptr_t)d_info_out |
+                      (uintptr_t)d_centres_out) & 3) == 0,
+                    "metro_plan_bind_view_fusion: every pointer must be 4-byte aligned");
+    METRO_CHECK_ARG(params->grid >= 2 && params->grid <= 16, "metro_plan_bind_view_fusion: grid %d outside [2, 16]", params->grid);
+    METRO_CHECK_ARG(params->n_views >= 1, "metro_plan_bind_view_fusion: n_views must be >= 1 (got %d)", params->n_views);
+    METRO_CHECK_ARG(params->weights == METRO_TRI_UNIFORM || params->weights == METRO_TRI_COVARIANCE,
+                    "metro_plan_bind_view_fusion: weights must be METRO_TRI_UNIFORM or METRO_TRI_COVARIANCE (got %d)", params->weights);
+    METRO_CHECK_ARG(__builtin_isfinite(params->extent_mm) && params->extent_mm > 0.0,
+                    "metro_plan_bind_view_fusion: extent_mm must be finite and > 0 (got %g)", params->extent_mm);
+    METRO_CHECK_ARG(params->floor > 0.0 && params->floor < 1.0, "metro_plan_bind_view_fusion: floor must lie in (0, 1) (got %g)", params->floor);
+    METRO_CHECK_ARG(__builtin_isfinite(params->near_mm) && params->near_mm >= 0.0,
+                    "metro_plan_bind_view_fusion: near_mm must be finite and >= 0 (got %g)", params->near_mm);
+    METRO_CHECK_ARG(__builtin_isfinite(params->min_det), "metro_plan_bind_view_fusion: min_det must be finite (got %g)", params->min_det);
+    METRO_CHECK_ARG(plan->spec.stride > 0 && plan->spec.proc_side / plan->spec.stride >= 2,
+                    "metro_plan_bind_view_fusion: the heat-map side must be at least 2 (a bilinear value needs four cells)");
+    plan->fusion.xy = d_xy; plan->fusion.records = d_records; plan->fusion.rows = d_rows; plan->fusion.starts = d_starts;
+    plan->fusion.mirror = d_mirror; plan->fusion.centres = d_centres; plan->fusion.points = d_points_out; plan->fusion.cov = d_cov_out;
+    plan->fusion.stats = d_stats_out; plan->fusion.info = d_info_out; plan->fusion.centres_out = d_centres_out;
+    plan->fusion.n_rows = n_rows; plan->fusion.n_persons = n_persons; plan->fusion.max_n = max_n; plan->fusion.params = *params;
+    return METRO_OK;
+}
+
 int metro_plan_set_graph_max_batch(MetroPlan* plan, int32_t max_batch_for_graphs) {
     METRO_CHECK_ARG(plan != nullptr && max_batch_for_graphs >= 0, "metro_plan_set_graph_max_batch: bad argument");
     plan->graph_max_batch = max_batch_for_graphs;
@@ -343,9 +405,9 @@ int metro_plan_set_graph_max_batch(MetroPlan* plan, int32_t max_batch_for_graphs
 static int forward_impl(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out, float* d_coords01,
                         void* d_workspace, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    // heat-map, mode, prior or track-prior buffers bound: plain launches, the captured forwards do not write them
+    // heat-map, mode, prior, track-prior or view-fusion buffers bound: plain launches, the captured forwards do not write them
     if (plan == nullptr || n > plan->graph_max_batch || n < 1 || plan->heat.scratch != nullptr || plan->modes.scratch != nullptr ||
-        plan->prior.scratch != nullptr || plan->track.scratch != nullptr)
+        plan->prior.scratch != nullptr || plan->track.scratch != nullptr || plan->fusion.points != nullptr)
         return run_layers(plan, d_images_nhwc, n, d_poses_out, d_workspace, stream, -1, nullptr, d_coords01);
     // small batches are launch-latency bound (57 dependent launches): replay a captured hipGraph
     GraphEntry* hit = nullptr;

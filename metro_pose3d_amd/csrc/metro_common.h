@@ -516,6 +516,11 @@ int track_prior_root_out(const MetroSpec& spec);      // the output joint of hea
 int launch_track_priors(const double* state, int capacity, const int* slot, const double* times, const MetroPlacement* rec,
                         const int* mirror, const MetroTrackPrior& params, const float* coords01, int n, const MetroSpec& spec,
                         float* prior_out, int* reason_out, hipStream_t stream);
+// The fused world joints of a forward with a view fusion bound (view_fusion.hip): per (person, output joint) the softmax of the
+// rows' log marginals over a cube of world points around centres (NULL: centres_out, as the triangulation launch wrote it).
+int launch_view_fusion(const float* xy, const MetroPlacement* rec, const int* rows, int n_rows, const int* starts, int n_persons,
+                       const int* mirror, const float* centres, const MetroViewFusion& params, int n, const MetroSpec& spec,
+                       float* points, float* cov, float* stats, int* info, float* centres_out, hipStream_t stream);
 // the volumetric head in one launch (head_f16.hip): postnorm prologue + logits GEMM + per-joint softmax statistics
 bool head_f16_supported(int c_in, int c_head, int n_joints, int depth, int side);
 int head_f16_slabs(int side);               // records per image the partials slot must hold

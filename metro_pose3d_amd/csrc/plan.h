@@ -84,5 +84,14 @@ struct MetroPlan {
         int capacity = 0, max_n = 0;
         MetroTrackPrior params{};
     } track;
+    // metro_plan_bind_view_fusion: the same (view_fusion.hip, behind triangulate.hip's launch when `centres` is NULL); bound
+    // while `points` is set
+    struct {
+        const float* xy = nullptr; const MetroPlacement* records = nullptr; const int32_t* rows = nullptr;
+        const int32_t* starts = nullptr; const int32_t* mirror = nullptr; const float* centres = nullptr;
+        float* points = nullptr; float* cov = nullptr; float* stats = nullptr; int32_t* info = nullptr; float* centres_out = nullptr;
+        int n_rows = 0, n_persons = 0, max_n = 0;
+        MetroViewFusion params{};
+    } fusion;
     bool head_fused = false;            // the logits stay on chip (LayerForm::Head)
 };

@@ -406,6 +406,81 @@ class Engine:
             self.status_words(n).copy_(torch.cat(words))
         return out, post, prior, reason
 
+    def forward_view_fusion(self, images: torch.Tensor, places: torch.Tensor, rows: torch.Tensor, starts: torch.Tensor,
+                            n_persons: int, mirror: torch.Tensor, fusion, weights: str = 'covariance', min_angle_deg: float = 2.0,
+                            centres: Optional[torch.Tensor] = None, n_views: int = 1, out: Optional[torch.Tensor] = None,
+                            coords01: Optional[torch.Tensor] = None, cov01: Optional[torch.Tensor] = None,
+                            peak: Optional[torch.Tensor] = None, heat_xy: Optional[torch.Tensor] = None,
+                            heat_z: Optional[torch.Tensor] = None):
+        """forward() whose heat-map marginals are fused over the cameras of every person, on a grid of world points ->
+        (poses, coords01, fused points fp32 [P, Jout, 3] world mm, cov fp32 [P, Jout, 9] mm^2, stats fp32 [P, Jout, 2]: the
+        largest weight and the agreement, info int32 [P, Jout, 2]: rows used and edge, centres fp32 [P, Jout, 3]).  All on the
+        plan's device, contiguous, read when the forward runs: places uint8 [n, 208], the crops' MetroPlacement records; rows
+        int32 [R] and starts int32 [n_persons + 1], the CSR heads.triangulate_joints reads (frames.person_groups); mirror int32
+        [Jout], the output-order mirror joints; fusion: heads.fusion_params(...), which holds the keywords' meaning and says of
+        the defaults that they are design choices; n_views: the rows per camera, a row counts 1 / n_views.
+        centres None: the cube of every joint is centred on its triangulated point -- heads.triangulate_joints' launch on this
+        forward's coords01 (and cov01 with weights 'covariance', allocated here when not passed), with `weights` and
+        `min_angle_deg`; `centres` is that launch's points bit for bit.  centres fp32 [P, Jout, 3] (a track's prediction, say):
+        used as they are, returned as a copy.  metro_plan_bind_view_fusion (include/metro_hip.h) holds the definition.
+        Binds the heat-maps (heat_xy, heat_z: allocated when not passed) and the fusion together and unbinds after the enqueue;
+        every other output keeps the bits forward() gives it.  A person's rows must share one forward: ValueError where the
+        call would be split (n above the chunk of bound forwards, `heat_chunk`)."""
+        images = self._check_images(images)
+        n, sk = images.shape[0], self.spec.skeleton
+        nj = sk.n_out
+        params = fusion.record(weights, min_angle_deg, n_views)
+        step = self._heat_chunk()
+        if n > step:
+            raise ValueError(f'{n} crops would be split into forwards of {step} (heat_chunk): a person\'s rows must share one forward')
+        if isinstance(n_persons, (bool, np.bool_)) or not isinstance(n_persons, (int, np.integer)) or n_persons < 0:
+            raise ValueError(f'n_persons must be an integer >= 0, got {n_persons!r}')
+        n_persons = int(n_persons)
+        rec_bytes = C.sizeof(_lib.MetroPlacement)
+
+        def given(name, t, dtype, shape, what):
+            if (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != self.device
+                    or not t.is_contiguous()):
+                raise ValueError(f'{name} must be a contiguous {str(dtype).replace("torch.", "")} {list(shape)} tensor on {self.device} '
+                                 f'({what}), got {getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))}')
+        given('places', places, torch.uint8, (n, rec_bytes), 'the MetroPlacement record of every crop')
+        if not isinstance(rows, torch.Tensor) or rows.dim() != 1:
+            raise ValueError(f'rows must be an int32 tensor [R] (frames.person_groups), got {tuple(getattr(rows, "shape", ()))}')
+        given('rows', rows, torch.int32, (rows.numel(),), 'the crop rows of the persons')
+        given('starts', starts, torch.int32, (n_persons + 1,), 'the first row of every person, and the end')
+        given('mirror', mirror, torch.int32, (nj,), 'the output-order mirror joints')
+        if centres is not None:
+            given('centres', centres, torch.float32, (n_persons, nj, 3), 'the centre of the cube of every joint, world mm')
+        if places.data_ptr() % 4:
+            places = places.clone()
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        if out is None:
+            out = f32(n, nj, 3)
+        else:
+            self._check_out('out', out, (n, nj, 3))
+        if coords01 is None:
+            coords01 = f32(n, sk.n_head, 3)
+        if centres is None and weights == 'covariance' and cov01 is None and peak is None:
+            cov01, peak = f32(n, sk.n_head, 6), f32(n, sk.n_head)
+        if (heat_xy is None) != (heat_z is None):
+            raise ValueError('heat_xy and heat_z go together: pass both or neither')
+        if heat_xy is None:
+            heat_xy, heat_z = (f32(*s) for s in self.heat_shapes(n))
+        points, cov, stats, centres_out = f32(n_persons, nj, 3), f32(n_persons, nj, 9), f32(n_persons, nj, 2), f32(n_persons, nj, 3)
+        info = torch.empty((n_persons, nj, 2), dtype=torch.int32, device=self.device)
+        # an empty tensor has no address: any aligned one stands for it, nothing is read or written through it
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t.numel() else self._ws.data_ptr())
+        try:
+            check(self.lib.metro_plan_bind_view_fusion(self._plan, ptr(heat_xy), ptr(places), ptr(rows), int(rows.numel()), ptr(starts),
+                                                       n_persons, ptr(mirror), ptr(centres) if centres is not None else None,
+                                                       C.byref(params), ptr(points), ptr(cov), ptr(stats), ptr(info), ptr(centres_out),
+                                                       step), 'metro_plan_bind_view_fusion')
+            self.forward(images, out, coords01, cov01, peak, heat_xy, heat_z)
+        finally:
+            check(self.lib.metro_plan_bind_view_fusion(self._plan, None, None, None, 0, None, 0, None, None, None, None, None, None, None,
+                                                       None, 0), 'metro_plan_bind_view_fusion')
+        return out, coords01, points, cov, stats, info, centres_out
+
     def forward(self, images: torch.Tensor, out: Optional[torch.Tensor] = None,
                 coords01: Optional[torch.Tensor] = None, cov01: Optional[torch.Tensor] = None,
                 peak: Optional[torch.Tensor] = None, heat_xy: Optional[torch.Tensor] = None,

@@ -1143,6 +1143,66 @@ def triangulate_poses_in_frames(frames, boxes, model_path, cameras, person_index
     return _finish_world(call, _enqueue_world(call, model_path, cameras, fi, triangulation, person_index=pi))[0]
 
 
+class FusedPoses(NamedTuple):
+    """What fuse_poses_in_frames returns."""
+    world: WorldPoses                    # triangulate_poses_in_frames' own, bit for bit
+    poses: torch.Tensor                  # float32 [P, Jout, 3] world mm: the mean of the fused distribution; NaN where no row was usable
+    covariance: torch.Tensor             # float32 [P, Jout, 3, 3] mm^2: its central second moments
+    peak: torch.Tensor                   # float32 [P, Jout]: the largest weight of a grid point
+    agreement: torch.Tensor              # float32 [P, Jout] <= 0: near 0 when all cameras' peaks meet in one point
+    n_rows: torch.Tensor                 # int32 [P, Jout]: the crop rows used
+    edge: torch.Tensor                   # int32 [P, Jout]: 1 where the heaviest grid point lies on the cube's surface (cube too small)
+
+
+def fuse_poses_in_frames(frames, boxes, model_path, cameras, person_index, frame_index, weights: str = 'covariance',
+                         min_angle_deg: float = 2.0, views=None, precision: Optional[str] = None,
+                         check_finite: Optional[bool] = None, geometry: str = 'auto', pixel_format: str = 'rgb',
+                         color_matrix: str = 'bt601', crop_dtype: str = 'float32', grid: int = 16, extent_mm: float = 1200.0,
+                         floor: float = 1e-6, near_mm: float = 100.0) -> FusedPoses:
+    """triangulate_poses_in_frames that also fuses every person's heat-maps over its cameras -> FusedPoses(world, poses
+    [P, Jout, 3], covariance [P, Jout, 3, 3], peak, agreement, n_rows, edge).  Parameters as triangulate_poses_in_frames, plus the
+    fusion's: grid, extent_mm, floor, near_mm (heads.fusion_params, which says of their defaults that they are design choices).
+
+    The triangulation reduces every crop to the mean of its heat-map before the cameras meet; the mean of a two-peaked joint (a
+    left / right swap, a second person in the crop) lies between the peaks and bends that camera's ray, and covariance weights
+    only dilute the error.  The fusion keeps the distributions: on a cube of grid^3 world points of side extent_mm around every
+    triangulated joint, each crop row gives a point the bilinear value of the joint's xy marginal at the point's projection
+    (at least `floor`; a flipped view gives its mirror joint's), and the product of the rows -- with views=V each counting 1 / V
+    -- is normalised over the cube.  A wrong peak in one camera finds no partner in the others and vanishes from the product.
+    `poses` is the mean of that distribution, `covariance` its second moments, `peak` its largest weight; `agreement` <= 0 is
+    the log of how far the best point falls short of all cameras' highest cells meeting there; `edge` says the cube was too
+    small.  With TWO cameras a wrong peak's ray still meets the other camera's ray and nothing resolves it: that is inherent.
+    On clean heat-maps the triangulated point is the better one (the bilinear probabilities are a coarser model than the
+    soft-argmax): `world` is triangulate_poses_in_frames' result bit for bit, and the fusion stands beside it.  A joint the
+    triangulation leaves undetermined has no centre: NaN, n_rows 0.
+    One enqueue chain, triangulate_poses_in_frames' with the heat-maps and the fusion bound to its forward (the marginal
+    launches, the centres' triangulation and view_fusion follow it), and the call's one synchronisation.  A known redundancy: the
+    joints are triangulated twice on the same inputs, once inside the bound forward for the centres (its n_rays and residual
+    are not kept) and once by triangulate_poses_in_frames' own launch for `world` (19 us a call as measured); that keeps
+    `world` bit for bit with no further buffer bound.  All crop rows share
+    ONE forward: ValueError where n V boxes-times-views exceed it.  ValueError before any launch as for
+    triangulate_poses_in_frames, and for a fusion keyword out of range."""
+    from metro_pose3d_amd.heads import Triangulation, fusion_params
+    fusion = fusion_params(grid, extent_mm, floor, near_mm)
+    triangulation = Triangulation.checked(weights, min_angle_deg)
+    n_boxes, fi, pi = _box_frames(boxes, frame_index, person_index, 'person_index')
+    if n_boxes and pi.min() < 0:
+        raise ValueError(f'person_index must not be negative, got {pi.min()}')
+    _check_rig(cameras, fi, n_boxes)
+    call = _checked_call(frames, boxes, fi, 'world', views, geometry, precision, check_finite, pixel_format, color_matrix,
+                         crop_dtype)
+    if len(call.boxes) == 0:
+        sk, device = _model_skeleton(model_path), _call_device(call.boxes, call.frames)
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=device)
+        return FusedPoses(_no_persons(sk, device).world, f32(0, sk.n_out, 3), f32(0, sk.n_out, 3, 3), f32(0, sk.n_out), f32(0, sk.n_out),
+                          i32(0, sk.n_out), i32(0, sk.n_out))
+    chain = _enqueue_world(call, model_path, cameras, fi, triangulation, person_index=pi, fusion=fusion)
+    world = _finish_world(call, chain)[0]
+    points, cov, stats, info, _ = chain.fused
+    return FusedPoses(world, points, cov.view(cov.shape[0], cov.shape[1], 3, 3), stats[..., 0], stats[..., 1], info[..., 0], info[..., 1])
+
+
 def _n_boxes(boxes) -> int:
     return int(boxes.shape[0]) if isinstance(boxes, torch.Tensor) else len(np.asarray(boxes, np.float64).reshape(-1, 4))
 
@@ -1194,16 +1254,35 @@ class _WorldChain(NamedTuple):
     residual: torch.Tensor
     covariance: Optional[torch.Tensor]   # [P, Jout, 9] of every triangulated joint, if asked for
     bad: Optional[torch.Tensor]          # the finite screen folded on the device
+    fused: Optional[tuple] = None        # with `fusion`: Engine.forward_view_fusion's (points, cov, stats, info, centres)
+
+
+def _forward_fused(eng, crops: torch.Tensor, check_finite: bool, moments: bool, places, rows, starts, nv: int, triangulation, fusion):
+    """_forward_coords01 as ONE forward with the heat-maps and the view fusion bound (Engine.forward_view_fusion) -> (rel,
+    coords01, bad, (cov01, peak) or None, (points, cov, stats, info, centres))."""
+    sk, m = eng.spec.skeleton, len(crops)
+    if m > eng.max_batch:
+        raise ValueError(f'{m} crop rows exceed the {eng.max_batch} of one forward: a person\'s rows must share one forward')
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=crops.device)
+    mom = (f32(m, sk.n_head, 6), f32(m, sk.n_head)) if moments else (None, None)
+    mirror = _upload(np.asarray(sk.out_mirror, np.int32), crops.device)
+    rel, coords01, *fused = eng.forward_view_fusion(crops, places.reshape(m, -1), rows, starts, int(starts.numel()) - 1, mirror, fusion,
+                                                    triangulation.weights, triangulation.min_angle_deg, n_views=nv, cov01=mom[0],
+                                                    peak=mom[1])
+    bad = eng.status_words(m).ne(0).sum() if check_finite else None
+    return rel, coords01, bad, mom if moments else None, tuple(fused)
 
 
 def _enqueue_world(call: _Call, model_path, cameras, fi: np.ndarray, triangulation, person_index=None, matching=None,
-                   step_index=None, covariance: bool = False) -> _WorldChain:
+                   step_index=None, covariance: bool = False, fusion=None) -> _WorldChain:
     """The first half of the chain triangulate_poses_in_frames, match_poses_in_frames and the world follower share, for n >= 1
     boxes: warp, forward, the persons' crop rows and ONE triangulation launch, nothing read back.  The rows come from the host
     (person_index: person_groups, uploaded) or, with `matching` (heads.Matching), from metro_view_affinity and
     metro_cluster_views on the forward's outputs; the triangulation launch then runs over the upper bound of n persons.
     step_index (host int32 [n], with matching): the affinity is gated by time step.  covariance: the triangulation launch also
-    writes the covariance of every joint.  A caller enqueues what it adds on the record's tensors, then _finish_world."""
+    writes the covariance of every joint.  fusion (heads.Fusion, with person_index): the forward is ONE call with the heat-maps
+    and the view fusion bound, whose outputs ride in the record's `fused`; the triangulation launch stays as it is.  A caller
+    enqueues what it adds on the record's tensors, then _finish_world."""
     from metro_pose3d_amd.heads import cluster_views, triangulate_joints, view_affinity_steps
     from metro_pose3d_amd.inference import _engine_for
     n, nv = len(call.boxes), len(call.vs.zoom)
@@ -1213,11 +1292,19 @@ def _enqueue_world(call: _Call, model_path, cameras, fi: np.ndarray, triangulati
     with torch.cuda.device(device):
         eng = _engine_for(model_path, call.precision, device, n * nv)
         crops, places = _warp_views(call.frames, cameras, call.boxes, call.fi, call.vs, eng.spec.proc_side, device, call.crop_dtype)
-        rel, coords01, bad, *mom = _forward_coords01(eng, crops, call.check_finite, moments)
-        cov01 = mom[0][0] if moments else None
+        fused = None
+        if fusion is not None and matching is not None:
+            raise ValueError('the view fusion reads the persons\' rows in the forward: persons found on the device (matching) are out of scope')
         if matching is None:
             rows, starts = (_upload(a, device) for a in person_groups(person_index, fi, nv))
+        if fusion is not None:                                 # the fusion reads the persons' rows in the forward: host rows only
+            rel, coords01, bad, mom, fused = _forward_fused(eng, crops, call.check_finite, moments, places, rows, starts, nv, triangulation,
+                                                            fusion)
+            mom = [mom]
         else:
+            rel, coords01, bad, *mom = _forward_coords01(eng, crops, call.check_finite, moments)
+        cov01 = mom[0][0] if moments else None
+        if matching is not None:
             cost, n_pairs = view_affinity_steps(coords01, cov01, places.reshape(-1), _upload(fi.astype(np.int32), device),
                                                 None if step_index is None else _upload(np.asarray(step_index, np.int32), device),
                                                 eng.spec, nv, *triangulation, matching.clip_mm, matching.min_joints)
@@ -1225,7 +1312,7 @@ def _enqueue_world(call: _Call, model_path, cameras, fi: np.ndarray, triangulati
         poses, n_rays, residual, *cov = triangulate_joints(coords01, cov01, places.reshape(-1), rows, starts, eng.spec, *triangulation,
                                                            covariance)
     return _WorldChain(eng, n, nv, rel, coords01, cov01, places, rows, starts, labels, cost, n_pairs, n_persons, poses, n_rays,
-                       residual, cov[0] if covariance else None, bad)
+                       residual, cov[0] if covariance else None, bad, fused)
 
 
 def _finish_world(call: _Call, chain: _WorldChain):

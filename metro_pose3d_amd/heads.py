@@ -20,6 +20,8 @@ through the C ABI (csrc/heads.hip).  Names and argument meaning follow the refer
                             the frames' calibrated cameras, compacted on the device and fused with a detector's boxes
   track_prior_params        the options of the track-predicted heat-map prior (Engine.forward_track_posterior,
                             frames.locate_tracked_poses_in_frames), checked
+  fusion_params             the options of the view fusion (Engine.forward_view_fusion, frames.fuse_poses_in_frames), checked:
+                            Fusion, whose record() is the MetroViewFusion metro_plan_bind_view_fusion copies
   smooth_tracks             poses of tracked persons over time: constant-velocity Kalman filter / RTS smoother per track and
                             joint, each row weighted by its heat-map covariance (nothing in the reference: one image each)
   track_bone_lengths        the bone lengths of followed persons, learned per track slot from their triangulated joints: a
@@ -1042,6 +1044,48 @@ def track_prior_params(coords='camera', depth='none', accel_psd=4e6, max_age_s=1
     if p.sigma_floor_mm == 0.0 and p.cov_scale == 0.0:
         raise ValueError('sigma_floor_mm and cov_scale are both 0: every prior would have a singular covariance')
     return p
+
+
+FUSION_MAX_GRID = 16
+
+
+class Fusion(NamedTuple):
+    """The view-fusion keywords of Engine.forward_view_fusion / frames.fuse_poses_in_frames, checked (fusion_params)."""
+    grid: int
+    extent_mm: float
+    floor: float
+    near_mm: float
+
+    def record(self, weights: str, min_angle_deg: float, n_views: int = 1) -> '_lib.MetroViewFusion':
+        """The MetroViewFusion record metro_plan_bind_view_fusion copies, with the keywords of the internal triangulation and
+        the rows per camera (test-time views: a row counts 1 / n_views)."""
+        if isinstance(n_views, (bool, np.bool_)) or not isinstance(n_views, (int, np.integer)) or n_views < 1:
+            raise ValueError(f'n_views must be an integer >= 1, got {n_views!r}')
+        p = _lib.MetroViewFusion()
+        p.min_det = triangulation_min_det(weights, min_angle_deg)          # checks both
+        p.grid, p.n_views, p.weights = int(self.grid), int(n_views), TRI_WEIGHTS[weights]
+        p.extent_mm, p.floor, p.near_mm = float(self.extent_mm), float(self.floor), float(self.near_mm)
+        return p
+
+
+def fusion_params(grid=16, extent_mm=1200.0, floor=1e-6, near_mm=100.0) -> Fusion:
+    """Checks the keywords of Engine.forward_view_fusion / frames.fuse_poses_in_frames; -> Fusion.  grid: the points per axis
+    of the cube of world points, an integer in [2, 16] (16^3 fp64 energies are the 32 KB of LDS the kernel keeps them in);
+    extent_mm > 0: the cube's side, around the joint's triangulated point (or the centre the caller gives); floor in (0, 1): the
+    least probability a camera gives a point -- what a point outside its map, behind it or on an empty cell counts, so that
+    one camera that misses a joint cannot veto it; near_mm >= 0: a point nearer than this to a camera's plane takes the floor
+    there.
+    The defaults grid = 16, extent_mm = 1200, floor = 1e-6 and near_mm = 100 are design choices, not measurements: a 1.2 m cube
+    in steps of 80 mm holds a wrong peak a few heat-map cells away at a person's distance (the `edge` output says when it did
+    not); 1e-6 is far below a cell of any peaked 64 x 64 map and far above fp32's underflow; nothing nearer than 100 mm is a
+    person in front of a lens (predict_boxes' rule).  One level only: a second, smaller grid around the first one's mode cut
+    the distribution and biased its mean."""
+    if isinstance(grid, (bool, np.bool_)) or not isinstance(grid, (int, np.integer)) or not 2 <= grid <= FUSION_MAX_GRID:
+        raise ValueError(f'grid must be an integer in [2, {FUSION_MAX_GRID}], got {grid!r}')
+    floor = _finite('floor', floor, 0, False, 1)
+    if floor >= 1.0:
+        raise ValueError(f'floor must lie in (0, 1), got {floor!r}')
+    return Fusion(int(grid), _finite('extent_mm', extent_mm, 0, False), floor, _finite('near_mm', near_mm, 0, True))
 
 
 def predict_boxes(state: torch.Tensor, ids: torch.Tensor, cameras, frame_sizes, times, coords: str = 'camera', detections=None,
