@@ -447,6 +447,63 @@ int  metro_plan_bind_view_fusion(MetroPlan* plan, const float* d_xy, const struc
                                  int32_t n_rows, const int32_t* d_starts, int32_t n_persons, const int32_t* d_mirror,
                                  const float* d_centres, const MetroViewFusion* params, float* d_points_out, float* d_cov_out,
                                  float* d_stats_out, int32_t* d_info_out, float* d_centres_out, int32_t max_n);
+/* ---- which heat-map mode every joint is in, decided by the person's bone lengths: tree inference per crop, bound to the plan ----
+ * Nothing in the reference (it reduces every heat-map to its mean, volumetric.py:227-235).  metro_plan_bind_modes gives per
+ * joint the k places it may be; every entry above treats the joints of one person as independent.  The skeleton ties them
+ * together: of a wrist's two peaks only one is a forearm's length from the elbow.  The skeletons of all three datasets are
+ * trees, so "which mode of every joint" is exact inference on a tree per crop.
+ * While this is bound, every forward entry (the list above) enqueues the launch skeleton_modes (csrc/skeleton_modes.hip), one
+ * workgroup of 64 lanes per crop row, behind heat_modes of the same forward (behind the finalize launch where modes are not
+ * bound).  No launching entry is added.  Definition, for crop row i < n, n the forward's crops; fp64 arithmetic on the stored
+ * fp32 inputs in a fixed order, each output rounded to fp32 once:
+ *   Present.    Mode k of output joint r is present if voxel[i, r, k] >= 0, its mass is finite and > 0 and its coords01 and
+ *               cov01 are finite.  A joint with no present mode is DEAD; all of its edges are cut.
+ *   Unary.      w[r, k] = mass / (the sum of the joint's present masses, in mode order).
+ *   Geometry.   x[r, k] = scale_mm * coords01 (per axis), C[r, k] = diag(scale_mm) Cov01 diag(scale_mm).
+ *   Known edge. Edge e = (p, q) is known for the row if lengths[i, e] = L is finite and > 0 and both joints are alive.
+ *   Pair.       For present modes ka of p and kb of q on a known edge: d = x[q, kb] - x[p, ka], l = |d|, u = d / l,
+ *               s = max(0, u^T (C[p, ka] + C[q, kb]) u) (a third of the trace where l < min_length_mm or l = 0),
+ *               v0 = sigma_mm^2 + (sigma_rel L)^2, v = v0 + cov_scale s,
+ *               ln psi = -(l - L)^2 / (2 v) - 1/2 ln(v / v0)  (<= 0: a Gaussian likelihood of the bone length, normalised so that
+ *               a sharp, exact pair scores 0).
+ *   Component.  A maximal set of alive joints joined by known edges.  Over its assignments k, P(k) ~ prod w prod psi.
+ *   Outputs (rows n .. max_n - 1 are not touched):
+ *     d_prob_out   fp32 [max_n, n_joints_out, k]: the exact marginal of every mode; 0 for an absent mode of an alive joint,
+ *                  NaN for a dead joint; the unaries w themselves in a component of one joint;
+ *     d_choice_out int32 [max_n, n_joints_out]: the MAP assignment, by max-product with back-tracking from the component's
+ *                  lowest-numbered joint, the lowest index among equals at every step; -1 for a dead joint;
+ *     d_info_out   fp32 [max_n, n_joints_out, 2]: log_evidence = ln sum_k prod w prod psi of the joint's component (<= 0,
+ *                  exactly 0.0 for a component without a known edge) and log_map = ln P(the MAP assignment); NaN for a dead joint;
+ *     d_coords01_sel_out fp32 [max_n, n_joints_head, 3] or NULL: the forward's coords01 with head joint permutation[r]
+ *                  replaced by the chosen mode's coords01 for every alive output joint r (of output joints that share a head
+ *                  joint the last); dead joints and head joints outside the output order keep the plain mean.
+ *   No other crop, and no joint other than a dead one, is affected by a NaN.
+ * It can only choose among the modes heat_modes found; lengths are compared in MeTRo's metric scale (heatmap_to_metric's linear
+ * part, which `scale_mm` is); the covariance of a mode is its window's; a skeleton with a cycle is refused.  The defaults of
+ * the host side -- sigma_mm 20, sigma_rel 0, cov_scale 1, min_length_mm 1 -- are design choices, not measurements.
+ * Inputs, all DEVICE memory read when the forward runs: d_voxel int32 [max_n, n_joints_out, k] and d_stats fp32 [max_n,
+ * n_joints_out, k, 11] in metro_plan_bind_modes' layout -- in the product the very buffers that binding writes, but any buffers
+ * will do and the modes binding is not required; d_lengths fp64 [max_n, n_edges], mm.  h_edges int32 [n_edges, 2] (output-joint
+ * indices) and `params` are HOST memory, copied at bind time with the rooted schedule derived from the edges.
+ * Binding is HOST state, as for the binds above; there is no scratch; unbind with every pointer NULL and k = n_edges = max_n = 0.
+ * Anything else is checked in full and returns METRO_ERR_INVALID_ARG: a NULL pointer other than d_coords01_sel_out (h_edges may
+ * be NULL with n_edges 0), d_lengths not 8-byte or another pointer not 4-byte aligned, max_n outside [1, the plan's max_batch],
+ * k outside [1, METRO_MAX_MODES], n_edges outside [0, 63], an edge with a joint outside [0, n_joints_out), a self-edge or an
+ * edge that closes a cycle (the message names the edge), scale_mm or sigma_mm not finite and > 0, sigma_rel, cov_scale or
+ * min_length_mm not finite and >= 0.
+ * While bound: a forward with n > max_n, and a forward entry without a coords01 output while d_coords01_sel_out is bound,
+ * return METRO_ERR_INVALID_ARG before any launch; forwards make PLAIN launches (the hipGraph cache does not serve them).  Every
+ * other output keeps the bits of the unbound call.  Unbound, a forward enqueues exactly the kernels it always did. */
+typedef struct MetroSkeletonModes {
+    double scale_mm[3];         /* mm per coords01 unit (x, y, z): the linear part of heatmap_to_metric, > 0                */
+    double sigma_mm;            /* sd of a bone's length, > 0                                                              */
+    double sigma_rel;           /* and the part of it that grows with the length, >= 0                                     */
+    double cov_scale;           /* how much of the modes' own covariance along the bone widens the likelihood, >= 0        */
+    double min_length_mm;       /* below this distance the bone has no direction: a third of the trace is used, >= 0       */
+} MetroSkeletonModes;           /* 56 bytes; copied at bind */
+int  metro_plan_bind_skeleton_modes(MetroPlan* plan, const int32_t* d_voxel, const float* d_stats, int32_t k, const double* d_lengths,
+                                    const int32_t* h_edges, int32_t n_edges, const MetroSkeletonModes* params, float* d_prob_out,
+                                    int32_t* d_choice_out, float* d_info_out, float* d_coords01_sel_out, int32_t max_n);
 /* Same, stopping after layer `last_layer` (inclusive) so tests can read that layer's output at
  * MetroLayerInfo.out_offset in the workspace.  d_poses_out may be NULL if the finalize layer
  * is not reached. */

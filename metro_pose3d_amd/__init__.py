@@ -26,6 +26,10 @@ Public surface (mirrors reference inference.py):
     locate_tracked_poses_in_frames(frames, boxes, model_path, cameras, tracks, track_index, frame_index, timestamps) ->
         locate_poses_in_frames with each person's own track as the prior of each crop's heat-maps: the plain poses, the
         posterior poses and covariance, and per joint the log-evidence a tracker gates with (Follower.locate)
+    estimate_pose_skeleton(images, model_path, bone_lengths, k=2, radius=1) -> estimate_pose_modes and, last, SkeletonModes:
+        which mode every joint is in under the person's bone lengths (exact inference on the skeleton tree), the marginals,
+        the evidence; locate_skeleton_poses_in_frames(frames, boxes, model_path, cameras, bone_lengths, frame_index) -> the
+        same choice in locate_poses_in_frames' chain (SkeletonFramePoses: plain bit for bit, and the selected poses beside it)
     fuse_poses_in_frames(frames, boxes, model_path, cameras, person_index, frame_index) -> triangulate_poses_in_frames
         and, beside it, every person's heat-maps fused over its cameras on a grid of world points: a wrong peak in one
         camera finds no partner in the others (FusedPoses: the triangulation bit for bit, the fused poses, covariance, ...)
@@ -40,7 +44,7 @@ container (save_model / load_model) and batch sharding over the GPUs of a node (
 from metro_pose3d_amd.spec import ModelSpec  # noqa: F401
 from metro_pose3d_amd.modelfile import load_model, save_model  # noqa: F401
 
-__all__ = ['ModelSpec', 'load_model', 'save_model', 'Engine', 'estimate_pose', 'Heatmaps', 'estimate_pose_modes', 'Modes', 'estimate_pose_posterior', 'Posterior', 'pose_prior', 'posterior_to_metric', 'estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'follow_rig_poses_in_frames', 'predict_boxes_in_frames', 'locate_tracked_poses_in_frames', 'fuse_poses_in_frames', 'FusedPoses', 'frame_sizes', 'Follower', 'Camera']
+__all__ = ['ModelSpec', 'load_model', 'save_model', 'Engine', 'estimate_pose', 'Heatmaps', 'estimate_pose_modes', 'Modes', 'estimate_pose_skeleton', 'SkeletonModes', 'estimate_pose_posterior', 'Posterior', 'pose_prior', 'posterior_to_metric', 'estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'follow_rig_poses_in_frames', 'predict_boxes_in_frames', 'locate_tracked_poses_in_frames', 'locate_skeleton_poses_in_frames', 'SkeletonFramePoses', 'fuse_poses_in_frames', 'FusedPoses', 'frame_sizes', 'Follower', 'Camera']
 
 
 def __getattr__(name):
@@ -54,10 +58,10 @@ def __getattr__(name):
     if name == 'Heatmaps':
         from metro_pose3d_amd.inference import Heatmaps
         return Heatmaps
-    if name in ('estimate_pose_modes', 'Modes', 'estimate_pose_posterior', 'Posterior', 'pose_prior', 'posterior_to_metric'):
+    if name in ('estimate_pose_modes', 'Modes', 'estimate_pose_skeleton', 'SkeletonModes', 'estimate_pose_posterior', 'Posterior', 'pose_prior', 'posterior_to_metric'):
         from metro_pose3d_amd import inference
         return getattr(inference, name)
-    if name in ('estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'follow_rig_poses_in_frames', 'predict_boxes_in_frames', 'locate_tracked_poses_in_frames', 'fuse_poses_in_frames', 'FusedPoses', 'frame_sizes', 'Follower', 'Camera'):
+    if name in ('estimate_pose_in_frames', 'locate_poses_in_frames', 'triangulate_poses_in_frames', 'match_poses_in_frames', 'track_poses_in_frames', 'follow_poses_in_frames', 'follow_world_poses_in_frames', 'follow_rig_poses_in_frames', 'predict_boxes_in_frames', 'locate_tracked_poses_in_frames', 'locate_skeleton_poses_in_frames', 'SkeletonFramePoses', 'fuse_poses_in_frames', 'FusedPoses', 'frame_sizes', 'Follower', 'Camera'):
         from metro_pose3d_amd import frames
         return getattr(frames, name)
     raise AttributeError(name)

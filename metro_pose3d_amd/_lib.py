@@ -130,6 +130,11 @@ class MetroViewFusion(C.Structure):
                 ('floor', C.c_double), ('near_mm', C.c_double), ('min_det', C.c_double)]
 
 
+class MetroSkeletonModes(C.Structure):
+    _fields_ = [('scale_mm', C.c_double * 3), ('sigma_mm', C.c_double), ('sigma_rel', C.c_double), ('cov_scale', C.c_double),
+                ('min_length_mm', C.c_double)]
+
+
 class MetroView(C.Structure):
     _fields_ = [('cos_roll', C.c_double), ('sin_roll', C.c_double), ('zoom', C.c_double), ('flip', C.c_int32),
                 ('reserved', C.c_int32)]
@@ -168,6 +173,8 @@ SIGNATURES = {
                                               C.c_int32]),
     'metro_plan_bind_view_fusion': (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(MetroViewFusion), _P, _P, _P,
                                               _P, _P, C.c_int32]),
+    'metro_plan_bind_skeleton_modes': (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, C.c_int32, C.POINTER(MetroSkeletonModes), _P, _P, _P, _P,
+                                                 C.c_int32]),
     'metro_forward_upto': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32]),
     'metro_forward_timed': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.POINTER(C.c_float)]),
     'metro_conv_f16': (C.c_int, [C.POINTER(MetroConvDesc), _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -148,6 +148,13 @@ int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_
     METRO_CHECK_ARG(!fusion || p->fusion.centres != nullptr || p->fusion.params.weights != METRO_TRI_COVARIANCE || mo.cov01 != nullptr,
                     "a view fusion without centres is bound with METRO_TRI_COVARIANCE (metro_plan_bind_view_fusion): the forward needs "
                     "a cov01 output (metro_forward_moments with one)");
+    // a skeleton bound (metro_plan_bind_skeleton_modes): one launch behind the modes', on whatever mode buffers it was given
+    const bool skel = p->skel.prob != nullptr && last_layer == nl - 1;
+    METRO_CHECK_ARG(!skel || n <= p->skel.max_n, "batch %d exceeds the %d crops the bound skeleton buffers hold (metro_plan_bind_skeleton_modes)",
+                    n, p->skel.max_n);
+    METRO_CHECK_ARG(!skel || p->skel.coords01_sel == nullptr || coords01 != nullptr,
+                    "a coords01_sel output is bound (metro_plan_bind_skeleton_modes): the forward needs a coords01 output "
+                    "(metro_forward_coords01, metro_forward_u8 or metro_forward_moments with one)");
     float* head_logits = nullptr;
     if (heat && p->head_fused)
         head_logits = heat_marginals_scratch_logits(p->heat.scratch, p->heat.max_n, side, p->spec.n_joints_head, p->spec.depth);
@@ -177,6 +184,10 @@ int run_layers(MetroPlan* p, const float* images, int n, float* poses, void* ws_
         st = launch_heat_modes(head_logits ? head_logits : static_cast<void*>(ws + p->slot_offset[S_LOGITS]),
                                p->spec.precision == METRO_PREC_F32M ? 1 : p->spec.precision, n, p->modes.max_n, p->spec, p->modes.k,
                                p->modes.radius, p->modes.voxel, p->modes.stats, stream);
+    if (skel && st == METRO_OK)
+        st = launch_skeleton_modes(p->skel.voxel, p->skel.stats, p->skel.k, p->skel.lengths, p->skel.edges, p->skel.n_edges, p->skel.parent,
+                                   p->skel.parent_edge, p->skel.params, coords01, n, p->skel.max_n, p->spec, p->skel.prob, p->skel.choice,
+                                   p->skel.info, p->skel.coords01_sel, stream);
     if (prior && st == METRO_OK)
         st = launch_heat_posterior(head_logits ? head_logits : static_cast<void*>(ws + p->slot_offset[S_LOGITS]),
                                    p->spec.precision == METRO_PREC_F32M ? 1 : p->spec.precision, n, p->prior.max_n, p->spec, p->prior.prior,
@@ -396,6 +407,52 @@ int metro_plan_bind_view_fusion(MetroPlan* plan, const float* d_xy, const MetroP
     return METRO_OK;
 }
 
+int metro_plan_bind_skeleton_modes(MetroPlan* plan, const int32_t* d_voxel, const float* d_stats, int32_t k, const double* d_lengths,
+                                   const int32_t* h_edges, int32_t n_edges, const MetroSkeletonModes* params, float* d_prob_out,
+                                   int32_t* d_choice_out, float* d_info_out, float* d_coords01_sel_out, int32_t max_n) {
+    METRO_CHECK_ARG(plan != nullptr, "metro_plan_bind_skeleton_modes: plan is NULL");
+    if (!d_voxel && !d_stats && !d_lengths && !h_edges && !params && !d_prob_out && !d_choice_out && !d_info_out && !d_coords01_sel_out &&
+        k == 0 && n_edges == 0 && max_n == 0) {                                                       // unbind
+        plan->skel = {};
+        return METRO_OK;
+    }
+    METRO_CHECK_ARG(d_voxel && d_stats && d_lengths && params && d_prob_out && d_choice_out && d_info_out,
+                    "metro_plan_bind_skeleton_modes: the modes' voxel and stats, the lengths, the parameters and the three outputs go "
+                    "together (all of them, or all NULL with k, n_edges and max_n 0 to unbind); only d_coords01_sel_out may be NULL");
+    METRO_CHECK_ARG(max_n >= 1 && max_n <= plan->max_batch, "metro_plan_bind_skeleton_modes: max_n %d outside [1, %d]", max_n, plan->max_batch);
+    METRO_CHECK_ARG(k >= 1 && k <= METRO_MAX_MODES, "metro_plan_bind_skeleton_modes: k %d outside [1, %d]", k, METRO_MAX_MODES);
+    METRO_CHECK_ARG(n_edges >= 0 && n_edges <= 63, "metro_plan_bind_skeleton_modes: n_edges %d outside [0, 63]", n_edges);
+    METRO_CHECK_ARG(n_edges == 0 || h_edges != nullptr, "metro_plan_bind_skeleton_modes: h_edges is NULL with n_edges %d", n_edges);
+    METRO_CHECK_ARG(((uintptr_t)d_lengths & 7) == 0 &&
+                        (((uintptr_t)d_voxel | (uintptr_t)d_stats | (uintptr_t)d_prob_out | (uintptr_t)d_choice_out | (uintptr_t)d_info_out |
+                          (uintptr_t)d_coords01_sel_out) & 3) == 0,
+                    "metro_plan_bind_skeleton_modes: the lengths must be 8-byte aligned, the other pointers 4-byte aligned");
+    METRO_CHECK_ARG(plan->spec.n_joints_out >= 1 && plan->spec.n_joints_out <= METRO_MAX_JOINTS,
+                    "metro_plan_bind_skeleton_modes: %d output joints outside [1, %d]", plan->spec.n_joints_out, METRO_MAX_JOINTS);
+    signed char parent[METRO_MAX_JOINTS] = {}, parent_edge[METRO_MAX_JOINTS] = {};
+    const char* why = "";
+    const int bad = skeleton_schedule(h_edges, n_edges, plan->spec.n_joints_out, parent, parent_edge, &why);
+    METRO_CHECK_ARG(bad < 0, "metro_plan_bind_skeleton_modes: edge %d (%d, %d) %s; the plan has %d output joints", bad, h_edges[2 * bad],
+                    h_edges[2 * bad + 1], why, plan->spec.n_joints_out);
+    for (int i = 0; i < 3; ++i)
+        METRO_CHECK_ARG(__builtin_isfinite(params->scale_mm[i]) && params->scale_mm[i] > 0.0,
+                        "metro_plan_bind_skeleton_modes: scale_mm[%d] must be finite and > 0 (got %g)", i, params->scale_mm[i]);
+    METRO_CHECK_ARG(__builtin_isfinite(params->sigma_mm) && params->sigma_mm > 0.0,
+                    "metro_plan_bind_skeleton_modes: sigma_mm must be finite and > 0 (got %g)", params->sigma_mm);
+    const double values[3] = {params->sigma_rel, params->cov_scale, params->min_length_mm};
+    static const char* const names[3] = {"sigma_rel", "cov_scale", "min_length_mm"};
+    for (int i = 0; i < 3; ++i)
+        METRO_CHECK_ARG(__builtin_isfinite(values[i]) && values[i] >= 0.0, "metro_plan_bind_skeleton_modes: %s must be finite and >= 0 (got %g)",
+                        names[i], values[i]);
+    plan->skel = {};
+    plan->skel.voxel = d_voxel; plan->skel.stats = d_stats; plan->skel.lengths = d_lengths; plan->skel.prob = d_prob_out;
+    plan->skel.choice = d_choice_out; plan->skel.info = d_info_out; plan->skel.coords01_sel = d_coords01_sel_out;
+    plan->skel.k = k; plan->skel.n_edges = n_edges; plan->skel.max_n = max_n; plan->skel.params = *params;
+    if (n_edges > 0) memcpy(plan->skel.edges, h_edges, sizeof(int32_t) * 2 * (size_t)n_edges);
+    memcpy(plan->skel.parent, parent, sizeof(parent)); memcpy(plan->skel.parent_edge, parent_edge, sizeof(parent_edge));
+    return METRO_OK;
+}
+
 int metro_plan_set_graph_max_batch(MetroPlan* plan, int32_t max_batch_for_graphs) {
     METRO_CHECK_ARG(plan != nullptr && max_batch_for_graphs >= 0, "metro_plan_set_graph_max_batch: bad argument");
     plan->graph_max_batch = max_batch_for_graphs;
@@ -405,9 +462,9 @@ int metro_plan_set_graph_max_batch(MetroPlan* plan, int32_t max_batch_for_graphs
 static int forward_impl(MetroPlan* plan, const float* d_images_nhwc, int32_t n, float* d_poses_out, float* d_coords01,
                         void* d_workspace, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    // heat-map, mode, prior, track-prior or view-fusion buffers bound: plain launches, the captured forwards do not write them
+    // heat-map, mode, prior, track-prior, view-fusion or skeleton buffers bound: plain launches, the captured forwards do not write them
     if (plan == nullptr || n > plan->graph_max_batch || n < 1 || plan->heat.scratch != nullptr || plan->modes.scratch != nullptr ||
-        plan->prior.scratch != nullptr || plan->track.scratch != nullptr || plan->fusion.points != nullptr)
+        plan->prior.scratch != nullptr || plan->track.scratch != nullptr || plan->fusion.points != nullptr || plan->skel.prob != nullptr)
         return run_layers(plan, d_images_nhwc, n, d_poses_out, d_workspace, stream, -1, nullptr, d_coords01);
     // small batches are launch-latency bound (57 dependent launches): replay a captured hipGraph
     GraphEntry* hit = nullptr;

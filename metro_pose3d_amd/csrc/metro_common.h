@@ -521,6 +521,14 @@ int launch_track_priors(const double* state, int capacity, const int* slot, cons
 int launch_view_fusion(const float* xy, const MetroPlacement* rec, const int* rows, int n_rows, const int* starts, int n_persons,
                        const int* mirror, const float* centres, const MetroViewFusion& params, int n, const MetroSpec& spec,
                        float* points, float* cov, float* stats, int* info, float* centres_out, hipStream_t stream);
+// The mode of every joint chosen by bone lengths, of a forward with a skeleton bound (skeleton_modes.hip): per crop row exact
+// inference on the forest `edges` rooted by skeleton_schedule (every component at its lowest-numbered joint; returns the first
+// bad edge and says why, or -1).
+int skeleton_schedule(const int32_t* edges, int n_edges, int n_joints, signed char* parent, signed char* parent_edge, const char** why);
+int launch_skeleton_modes(const int32_t* voxel, const float* stats, int k, const double* lengths, const int32_t* edges, int n_edges,
+                          const signed char* parent, const signed char* parent_edge, const MetroSkeletonModes& params,
+                          const float* coords01, int n, int max_n, const MetroSpec& spec, float* prob, int32_t* choice, float* info,
+                          float* coords01_sel, hipStream_t stream);
 // the volumetric head in one launch (head_f16.hip): postnorm prologue + logits GEMM + per-joint softmax statistics
 bool head_f16_supported(int c_in, int c_head, int n_joints, int depth, int side);
 int head_f16_slabs(int side);               // records per image the partials slot must hold

@@ -93,5 +93,15 @@ struct MetroPlan {
         int n_rows = 0, n_persons = 0, max_n = 0;
         MetroViewFusion params{};
     } fusion;
+    // metro_plan_bind_skeleton_modes: the same (skeleton_modes.hip, behind heat_modes.hip's launch); bound while `prob` is set;
+    // edges, params and the rooted schedule are copies
+    struct {
+        const int32_t* voxel = nullptr; const float* stats = nullptr; const double* lengths = nullptr;
+        float* prob = nullptr; int32_t* choice = nullptr; float* info = nullptr; float* coords01_sel = nullptr;
+        int k = 0, n_edges = 0, max_n = 0;
+        int32_t edges[2 * 63] = {};
+        signed char parent[METRO_MAX_JOINTS] = {}, parent_edge[METRO_MAX_JOINTS] = {};
+        MetroSkeletonModes params{};
+    } skel;
     bool head_fused = false;            // the logits stay on chip (LayerForm::Head)
 };

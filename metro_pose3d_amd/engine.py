@@ -481,6 +481,78 @@ class Engine:
                                                        None, 0), 'metro_plan_bind_view_fusion')
         return out, coords01, points, cov, stats, info, centres_out
 
+    def forward_skeleton_modes(self, images: torch.Tensor, lengths: torch.Tensor, k: int = 2, radius: int = 1, edges=None,
+                               sigma_mm: float = 20.0, sigma_rel: float = 0.0, cov_scale: float = 1.0, min_length_mm: float = 1.0,
+                               out: Optional[torch.Tensor] = None, coords01: Optional[torch.Tensor] = None,
+                               cov01: Optional[torch.Tensor] = None, peak: Optional[torch.Tensor] = None,
+                               heat_xy: Optional[torch.Tensor] = None, heat_z: Optional[torch.Tensor] = None):
+        """forward_modes() whose modes are chosen among by the person's bone lengths -> (poses, voxel int32 [n, Jout, k], stats
+        fp32 [n, Jout, k, 11], choice int32 [n, Jout]: the mode of every joint in the most probable assignment of the whole
+        skeleton (-1: a joint without a usable mode), prob fp32 [n, Jout, k]: the marginal of every mode, info fp32 [n, Jout, 2]:
+        (log_evidence, log_map) of the joint's component, coords01_sel fp32 [n, J_head, 3]: coords01 with the chosen modes'
+        means in place of the plain ones).  lengths: float64 [n, E] in mm on the plan's device, contiguous, read when the forward
+        runs (Follower.bone_lengths_for's tensor as it is); NaN or <= 0: that bone is unknown for that crop.  edges: [E, 2]
+        output-joint indices, a forest (default: the skeleton's own edges).  The likelihood of a pair of modes on a bone is a
+        Gaussian of the distance between their means in heatmap_to_metric's scale (heads.skeleton_mode_params holds the
+        keywords' meaning and says of the defaults that they are design choices; metro_plan_bind_skeleton_modes,
+        include/metro_hip.h, holds the definition).  Binds the modes and the skeleton together, chunk by chunk, and unbinds
+        after the enqueue; every other output keeps the bits forward_modes() gives it."""
+        from metro_pose3d_amd.heads import skeleton_edges, skeleton_mode_params
+        from metro_pose3d_amd.inference import _metric_map
+        images = self._check_images(images)
+        n, sk = images.shape[0], self.spec.skeleton
+        nj = sk.n_out
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _lib.METRO_MAX_MODES:
+            raise ValueError(f'k must be an int in [1, {_lib.METRO_MAX_MODES}], got {k!r}')
+        if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= _lib.METRO_MAX_MODE_RADIUS:
+            raise ValueError(f'radius must be an int in [0, {_lib.METRO_MAX_MODE_RADIUS}], got {radius!r}')
+        e = skeleton_edges(sk.edges_array() if edges is None else edges, nj)
+        ne = len(e)
+        params = skeleton_mode_params(_metric_map(self.spec)[0], sigma_mm, sigma_rel, cov_scale, min_length_mm)
+        if (not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.float64 or tuple(lengths.shape) != (n, ne)
+                or lengths.device != self.device or not lengths.is_contiguous()):
+            raise ValueError(f'lengths must be a contiguous float64 [{n}, {ne}] tensor on {self.device} (mm, one row per crop), got '
+                             f'{getattr(lengths, "dtype", type(lengths))} {tuple(getattr(lengths, "shape", ()))}')
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        if out is None:
+            out = f32(n, nj, 3)
+        else:
+            self._check_out('out', out, (n, nj, 3))
+        if coords01 is None:
+            coords01 = f32(n, sk.n_head, 3)
+        voxel = torch.empty((n, nj, k), dtype=torch.int32, device=self.device)
+        stats = f32(n, nj, k, self.MODE_STATS)
+        choice = torch.empty((n, nj), dtype=torch.int32, device=self.device)
+        prob, info, sel = f32(n, nj, k), f32(n, nj, 2), f32(n, sk.n_head, 3)
+        step = self._heat_chunk()
+        nb = int(self.lib.metro_plan_modes_scratch_bytes(self._plan, step))
+        if self._modes is None or self._modes.numel() < nb:
+            self._modes = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        part = lambda t, i, m: None if t is None else t[i:i + m]
+        # an empty tensor has no address: any aligned one stands for it, nothing is read or written through it
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t.numel() else self._ws.data_ptr())
+        words = []
+        try:
+            for i in range(0, n, step):
+                m = min(step, n - i)
+                check(self.lib.metro_plan_bind_modes(self._plan, ptr(voxel[i:i + m]), ptr(stats[i:i + m]), C.c_void_p(self._modes.data_ptr()),
+                                                     step, k, radius), 'metro_plan_bind_modes')
+                check(self.lib.metro_plan_bind_skeleton_modes(self._plan, ptr(voxel[i:i + m]), ptr(stats[i:i + m]), k, ptr(lengths[i:i + m]),
+                                                              e.ctypes.data_as(C.c_void_p) if ne else None, ne, C.byref(params),
+                                                              ptr(prob[i:i + m]), ptr(choice[i:i + m]), ptr(info[i:i + m]),
+                                                              ptr(sel[i:i + m]), step), 'metro_plan_bind_skeleton_modes')
+                self.forward(images[i:i + m], out[i:i + m], coords01[i:i + m], part(cov01, i, m), part(peak, i, m),
+                             part(heat_xy, i, m), part(heat_z, i, m))
+                if n > step:
+                    words.append(self.status_words(m).clone())
+        finally:
+            check(self.lib.metro_plan_bind_skeleton_modes(self._plan, None, None, 0, None, None, 0, None, None, None, None, None, 0),
+                  'metro_plan_bind_skeleton_modes')
+            check(self.lib.metro_plan_bind_modes(self._plan, None, None, None, 0, 0, 0), 'metro_plan_bind_modes')
+        if words:
+            self.status_words(n).copy_(torch.cat(words))
+        return out, voxel, stats, choice, prob, info, sel
+
     def forward(self, images: torch.Tensor, out: Optional[torch.Tensor] = None,
                 coords01: Optional[torch.Tensor] = None, cov01: Optional[torch.Tensor] = None,
                 peak: Optional[torch.Tensor] = None, heat_xy: Optional[torch.Tensor] = None,

@@ -1013,10 +1013,47 @@ def _forward_tracked(eng, crops: torch.Tensor, check_finite: bool, places, nv: i
     return rel, coords01, bad, torch.cat(posts), torch.cat(reasons)
 
 
+def _view_edge_columns(vs: Views, sk) -> np.ndarray:
+    """int64 [V, E]: the bone-length column view v reads for edge e -- e itself, or in a flipped view (which shows every joint
+    where its mirror joint is) Skeleton.edge_mirror()[e], -1 keeping the column."""
+    straight = np.arange(len(sk.edges), dtype=np.int64)
+    mirror = np.asarray(sk.edge_mirror(), np.int64).reshape(-1)
+    flipped = np.where(mirror >= 0, mirror, straight)
+    return np.stack([flipped if f else straight for f in vs.flip]).reshape(len(vs.flip), len(straight))
+
+
+def _view_bone_rows(lengths: torch.Tensor, vs: Views, sk) -> torch.Tensor:
+    """Bone lengths float64 [n, E] on the device -> [n V, E], one row per view row (box-major), unread: repeated per view, a
+    flipped view's columns gathered through _view_edge_columns -- the flips are host-known."""
+    cols = _upload(_view_edge_columns(vs, sk), lengths.device)
+    return lengths[:, cols].reshape(-1, lengths.shape[1]).contiguous()
+
+
+def _forward_skeleton(eng, crops: torch.Tensor, check_finite: bool, vs: Views, lengths, k, radius, options: dict):
+    """_forward_coords01 with the modes and the skeleton bound (Engine.forward_skeleton_modes) -> (rel, coords01, bad, coords01_sel
+    [m, Jhead, 3], choice [m, Jout], prob [m, Jout, k], info [m, Jout, 2]); lengths float64 [n, E] on the device, one row per box."""
+    sk = eng.spec.skeleton
+    m = len(crops)
+    rel = torch.empty((m, sk.n_out, 3), dtype=torch.float32, device=crops.device)
+    coords01 = torch.empty((m, sk.n_head, 3), dtype=torch.float32, device=crops.device)
+    rows = _view_bone_rows(lengths, vs, sk)
+    parts, bad = [], None
+    for i in range(0, m, eng.max_batch):
+        c = min(eng.max_batch, m - i)
+        parts.append(eng.forward_skeleton_modes(crops[i:i + c], rows[i:i + c], k, radius, out=rel[i:i + c], coords01=coords01[i:i + c],
+                                                **options)[3:])
+        if check_finite:
+            cnt = eng.status_words(c).ne(0).sum()
+            bad = cnt if bad is None else bad + cnt
+    choice, prob, info, sel = (torch.cat(t) for t in zip(*parts))
+    return rel, coords01, bad, sel, choice, prob, info
+
+
 def _locate_poses_views(call: _Call, model_path, cameras, scale_recovery, targets, per_pose, root_z, coords, sk,
-                        uncertainty: bool = False, tracked=None):
+                        uncertainty: bool = False, tracked=None, skeleton=None):
     """-> (FramePoses, spread [n, Jout]); tracked (the table's state, a slot and a time per box on the device, the prior keywords):
-    (TrackedFramePoses, spread of the plain poses) from the same chain with the track prior bound."""
+    (TrackedFramePoses, spread of the plain poses) from the same chain with the track prior bound; skeleton (bone lengths [n, E]
+    on the device, k, radius, the options): (SkeletonFramePoses, spread of the plain poses) with the modes and the skeleton bound."""
     from metro_pose3d_amd.inference import _engine_for
     n, nv = len(call.boxes), len(call.vs.zoom)
     m = n * nv
@@ -1033,10 +1070,16 @@ def _locate_poses_views(call: _Call, model_path, cameras, scale_recovery, target
                 nv0 = (0, nv, sk.n_out)
                 empty = TrackedFramePoses(empty, empty, f32(0, sk.n_out, 3, 3), f32(*nv0), f32(*nv0),
                                           torch.zeros(nv0, dtype=torch.int32, device=device))
+            if skeleton is not None:
+                nv0 = (0, nv, sk.n_out)
+                empty = SkeletonFramePoses(empty, empty, torch.zeros(nv0, dtype=torch.int32, device=device), f32(*nv0, skeleton[1]),
+                                           f32(*nv0), f32(*nv0))
             return empty, torch.zeros((0, sk.n_out), dtype=torch.float32, device=device)
         crops, places = _warp_views(call.frames, cameras, call.boxes, call.fi, call.vs, eng.spec.proc_side, device, call.crop_dtype)
         if tracked is not None:
             rel, coords01, bad, post, reason = _forward_tracked(eng, crops, call.check_finite, places, nv, *tracked)
+        elif skeleton is not None:
+            rel, coords01, bad, sel, choice, prob, info = _forward_skeleton(eng, crops, call.check_finite, call.vs, *skeleton)
         else:
             rel, coords01, bad, *mom = _forward_coords01(eng, crops, call.check_finite, uncertainty)
         if isinstance(targets, torch.Tensor):           # device bone lengths: unread, repeated per view on the device
@@ -1053,8 +1096,12 @@ def _locate_poses_views(call: _Call, model_path, cameras, scale_recovery, target
             plain = FramePoses(poses, keypoints, z_offset, sk.edges_array(), names)
             both = _tracked_frame_poses(eng, plain, post, reason, coords01, places, scale_recovery, coords, d_targets, per_pose,
                                         root_rows, n, nv)
+        if skeleton is not None:
+            plain = FramePoses(poses, keypoints, z_offset, sk.edges_array(), names)
+            both = _skeleton_frame_poses(eng, plain, sel, choice, prob, info, places, scale_recovery, coords, d_targets, per_pose,
+                                         root_rows, n, nv)
         _raise_on_non_finite(eng.spec, call.precision, _synchronise(bad, call.boxes)[0], m)     # the call's one stream synchronisation
-    if tracked is not None:
+    if tracked is not None or skeleton is not None:
         return both, spread
     return FramePoses(poses, keypoints, z_offset, sk.edges_array(), names, *unc), spread
 
@@ -2142,6 +2189,93 @@ def _tracked_frame_poses(eng, plain: FramePoses, post, reason, coords01, places,
                              post[..., 1].reshape(n, nv, sk.n_out).contiguous(), reason.view(n, nv, sk.n_out))
 
 
+class SkeletonFramePoses(NamedTuple):
+    """locate_skeleton_poses_in_frames: `plain` is locate_poses_in_frames' result bit for bit; `selected` the same placement of
+    the heat-map modes the person's bone lengths choose; the rest stays per view row ([n, V, ...], V = 1 without views)."""
+    plain: FramePoses
+    selected: FramePoses
+    choice: torch.Tensor         # int32 [n, V, Jout]: the joint's mode in the most probable assignment of the skeleton, -1: none usable
+    prob: torch.Tensor           # float32 [n, V, Jout, K]: the marginal probability of every mode under the skeleton
+    log_evidence: torch.Tensor   # float32 [n, V, Jout]: ln of the probability the modes give to the bone lengths (<= 0), per component
+    log_map: torch.Tensor        # float32 [n, V, Jout]: ln of the probability of the chosen assignment of the joint's component
+
+
+def locate_skeleton_poses_in_frames(frames, boxes, model_path, cameras, bone_lengths, frame_index=None, k: int = 2, radius: int = 1,
+                                    sigma_mm: float = 20.0, sigma_rel: float = 0.0, cov_scale: float = 1.0,
+                                    min_length_mm: float = 1.0, scale_recovery: str = 'bone-lengths', root_depth=None,
+                                    coords: str = 'camera', precision: Optional[str] = None, check_finite: Optional[bool] = None,
+                                    views=None, geometry: str = 'auto', pixel_format: str = 'rgb', color_matrix: str = 'bt601',
+                                    crop_dtype: str = 'float32') -> SkeletonFramePoses:
+    """locate_poses_in_frames that also chooses among every joint's heat-map modes by the person's bone lengths ->
+    SkeletonFramePoses(plain, selected, choice, prob, log_evidence, log_map).  A wrist's heat-map with two peaks (a left / right
+    swap, a second person in the crop) has its mean between them, and its heavier peak may be the wrong one; only one of them is a
+    forearm's length from the elbow.  From one camera and one frame, without a track, that is what can tell them apart.
+
+    frames, boxes, cameras, frame_index and every keyword from scale_recovery on are locate_poses_in_frames'.  bone_lengths: mm
+    over skeleton.edges (the order of head_edges), [E] or [n, E], host values or a float64 CUDA tensor [n, E], contiguous, on the
+    call's device (Follower.bone_lengths_for's tensor as it is: never read on the host).  They choose the modes and, under
+    scale_recovery 'bone-lengths', also place both poses, so they must then be finite and positive; under 'metro' and
+    'true-root-depth' a NaN (or a value <= 0) says that a bone is unknown.  k, radius: the modes (estimate_pose_modes); sigma_mm,
+    sigma_rel, cov_scale, min_length_mm: heads.skeleton_mode_params, which says of the defaults that they are design choices.
+    One enqueue chain and ONE synchronisation, locate_poses_in_frames' own with the modes and the skeleton bound to the forward
+    (Engine.forward_skeleton_modes: the modes launch and one more small launch).  The lengths are repeated per view on the
+    device; a flipped view shows every joint where its mirror joint is, so its columns are gathered through
+    Skeleton.edge_mirror().  `plain` is locate_poses_in_frames' result, bit for bit.  `selected` is placed by the same
+    metro_place_poses and metro_merge_views launches on coords01_sel, the forward's coords01 with the chosen modes' means in
+    place of the plain ones (scale_recovery 'metro' roots them as inference.skeleton_to_metric does).  choice, prob and both logs
+    stay per view row.
+    Limits: it can only choose among the modes heat_modes found; lengths are compared in MeTRo's metric scale (the linear part of
+    heatmap_to_metric), which is not the scale bone lengths place the pose in; sharded calls are not served.
+    ValueError before any launch for a bad k, radius or option, bone lengths of another shape, dtype or device, and whatever
+    locate_poses_in_frames refuses."""
+    from metro_pose3d_amd.heads import skeleton_mode_params
+    call = _checked_call(frames, boxes, frame_index, coords, views, geometry, precision, check_finite, pixel_format,
+                         color_matrix, crop_dtype)
+    for name, v, lo, hi in (('k', k, 1, _lib.METRO_MAX_MODES), ('radius', radius, 0, _lib.METRO_MAX_MODE_RADIUS)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f'{name} must be an int in [{lo}, {hi}], got {v!r}')
+    options = dict(sigma_mm=sigma_mm, sigma_rel=sigma_rel, cov_scale=cov_scale, min_length_mm=min_length_mm)
+    skeleton_mode_params((1.0, 1.0, 1.0), **options)
+    sk = _model_skeleton(model_path)
+    n, n_edges = len(call.boxes), len(sk.edges)
+    device = _call_device(call.boxes, call.frames)
+    if bone_lengths is None:
+        raise ValueError(f'bone_lengths is required: mm over the model\'s {n_edges} edges (skeleton.edges), [E] or [n, E]')
+    if isinstance(bone_lengths, torch.Tensor) and bone_lengths.is_cuda:
+        t = bone_lengths
+        if t.dtype != torch.float64 or tuple(t.shape) != (n, n_edges) or not t.is_contiguous() or t.device != device:
+            raise ValueError(f'a CUDA tensor as bone_lengths must be a contiguous float64 [{n}, {n_edges}] tensor on the call\'s device '
+                             f'(Follower.bone_lengths_for), got {t.dtype} {tuple(t.shape)} on {t.device}')
+        place_with = t
+    else:
+        b = np.asarray(bone_lengths.numpy() if isinstance(bone_lengths, torch.Tensor) else bone_lengths, np.float64)
+        if b.shape not in ((n_edges,), (n, n_edges)):
+            raise ValueError(f'bone_lengths must be [{n_edges}] or [{n}, {n_edges}] (mm over skeleton.edges), got {b.shape}')
+        place_with = np.ascontiguousarray(b)
+    placed = scale_recovery == 'bone-lengths'
+    targets, per_pose, root_z = _placement_targets(scale_recovery, cameras, n, len(sk.head_edges), place_with if placed else None,
+                                                   root_depth, device if isinstance(place_with, torch.Tensor) else None)
+    with torch.cuda.device(device):
+        rows = place_with if isinstance(place_with, torch.Tensor) else \
+            _upload(np.array(np.broadcast_to(place_with, (n, n_edges)), np.float64), device)
+    return _locate_poses_views(call, model_path, cameras, scale_recovery, targets, per_pose, root_z, coords, sk, False,
+                               skeleton=(rows, k, radius, options))[0]
+
+
+def _skeleton_frame_poses(eng, plain: FramePoses, sel, choice, prob, info, places, scale_recovery, coords, d_targets, per_pose, root_z,
+                          n: int, nv: int) -> SkeletonFramePoses:
+    """The selected half of locate_skeleton_poses_in_frames, enqueued behind the plain half: the same placement and merge launches
+    on coords01_sel."""
+    from metro_pose3d_amd.inference import skeleton_to_metric
+    sk = eng.spec.skeleton
+    rel = skeleton_to_metric(eng.spec, sel).contiguous() if scale_recovery == 'metro' else None
+    poses_v, keypoints_v, z_v, mirror = _place_poses(eng, sel, rel, places, scale_recovery, coords, d_targets, per_pose, root_z)
+    poses, keypoints, z_offset, _ = _merge_views(poses_v, keypoints_v, z_v, places, mirror, n, nv, spread=False)
+    selected = FramePoses(poses, keypoints, z_offset, plain.joint_edges, plain.joint_names)
+    return SkeletonFramePoses(plain, selected, choice.view(n, nv, sk.n_out), prob.view(n, nv, sk.n_out, -1),
+                              info[..., 0].reshape(n, nv, sk.n_out).contiguous(), info[..., 1].reshape(n, nv, sk.n_out).contiguous())
+
+
 # ---- one object per followed stream: the keywords checked once, the table of tracks carried from call to call ----
 
 _FOLLOWER_GIVEN = ('frames', 'boxes', 'model_path', 'cameras', 'frame_index', 'timestamps', 'tracks', 'capacity', 'assignment')
@@ -2250,6 +2384,17 @@ class Follower:
         kw.update(keywords)
         return locate_tracked_poses_in_frames(frames, boxes, self.model_path, self.cameras, self.tracks, track_index, frame_index,
                                               timestamps, table_coords=table_coords, **kw)
+
+    def locate_skeleton(self, frames, boxes, track_index, frame_index, fallback, **keywords) -> SkeletonFramePoses:
+        """locate_skeleton_poses_in_frames on .bone_lengths_for(track_index, fallback): every box's heat-map modes chosen among,
+        and both poses placed, by the followed person's own learned skeleton (`fallback` [E] mm for -1, for a slot outside the
+        table and for every edge not yet known).  Needs learn_bones=True; track_index: an int32 CUDA tensor of slots such as
+        PredictedBoxes.track_index; `keywords` are that call's (k, radius, sigma_mm, ..., scale_recovery, coords, views, ...).  No
+        host round trip: the lengths are never read on the host."""
+        if 'bone_lengths' in keywords:
+            raise TypeError("Follower.locate_skeleton: bone_lengths are the follower's own")
+        lengths = self.bone_lengths_for(track_index, fallback)
+        return locate_skeleton_poses_in_frames(frames, boxes, self.model_path, self.cameras, lengths, frame_index, **keywords)
 
     def _bone_read_out(self, fallback, required: bool):
         from metro_pose3d_amd.heads import bone_fallback, track_bone_lengths

@@ -22,6 +22,8 @@ through the C ABI (csrc/heads.hip).  Names and argument meaning follow the refer
                             frames.locate_tracked_poses_in_frames), checked
   fusion_params             the options of the view fusion (Engine.forward_view_fusion, frames.fuse_poses_in_frames), checked:
                             Fusion, whose record() is the MetroViewFusion metro_plan_bind_view_fusion copies
+  skeleton_mode_params      the options of the choice among heat-map modes by bone lengths (Engine.forward_skeleton_modes,
+                            estimate_pose_skeleton), checked: the MetroSkeletonModes metro_plan_bind_skeleton_modes copies
   smooth_tracks             poses of tracked persons over time: constant-velocity Kalman filter / RTS smoother per track and
                             joint, each row weighted by its heat-map covariance (nothing in the reference: one image each)
   track_bone_lengths        the bone lengths of followed persons, learned per track slot from their triangulated joints: a
@@ -1086,6 +1088,48 @@ def fusion_params(grid=16, extent_mm=1200.0, floor=1e-6, near_mm=100.0) -> Fusio
     if floor >= 1.0:
         raise ValueError(f'floor must lie in (0, 1), got {floor!r}')
     return Fusion(int(grid), _finite('extent_mm', extent_mm, 0, False), floor, _finite('near_mm', near_mm, 0, True))
+
+
+SKELETON_MAX_EDGES = 63
+
+
+def skeleton_mode_params(scale_mm, sigma_mm=20.0, sigma_rel=0.0, cov_scale=1.0, min_length_mm=1.0) -> '_lib.MetroSkeletonModes':
+    """Checks the keywords of Engine.forward_skeleton_modes / estimate_pose_skeleton; -> the MetroSkeletonModes record
+    metro_plan_bind_skeleton_modes copies.  scale_mm: three finite numbers > 0, mm per coords01 unit (the linear part of
+    heatmap_to_metric); sigma_mm > 0: the sd of a bone's length; sigma_rel >= 0: the part of it that grows with the length
+    (sd^2 = sigma_mm^2 + (sigma_rel L)^2); cov_scale >= 0: how much of the two modes' own covariance along the bone widens the
+    likelihood; min_length_mm >= 0: two modes nearer than this have no direction, a third of the covariance's trace is used.
+    The defaults sigma_mm = 20, sigma_rel = 0, cov_scale = 1 and min_length_mm = 1 are design choices, not measurements: 20 mm
+    is a few per cent of a limb and well below the distance between two peaks a heat-map can tell apart (one stride-16 voxel is
+    about 130 mm); the modes' covariances are taken at face value; 1 mm is bone_lengths' own floor."""
+    s = tuple(scale_mm) if isinstance(scale_mm, (tuple, list, np.ndarray)) else ()
+    if len(s) != 3:
+        raise ValueError(f'scale_mm must be three numbers (mm per coords01 unit in x, y, z), got {scale_mm!r}')
+    p = _lib.MetroSkeletonModes()
+    for i, v in enumerate(s):
+        p.scale_mm[i] = _finite(f'scale_mm[{i}]', v, 0, False)
+    p.sigma_mm = _finite('sigma_mm', sigma_mm, 0, False)
+    p.sigma_rel, p.cov_scale = _finite('sigma_rel', sigma_rel, 0, True), _finite('cov_scale', cov_scale, 0, True)
+    p.min_length_mm = _finite('min_length_mm', min_length_mm, 0, True)
+    return p
+
+
+def skeleton_edges(edges, n_joints: int) -> np.ndarray:
+    """Checks the edges of a skeleton binding: -> int32 [E, 2], E <= 63, output-joint indices in [0, n_joints), no self-edge, no
+    cycle (a forest: metro_plan_bind_skeleton_modes refuses anything else, this names the edge first)."""
+    e = np.asarray(edges.detach().cpu().numpy() if isinstance(edges, torch.Tensor) else edges)
+    if e.size == 0:
+        return np.zeros((0, 2), np.int32)
+    if e.ndim != 2 or e.shape[1] != 2 or e.dtype.kind not in 'iu' or len(e) > SKELETON_MAX_EDGES:
+        raise ValueError(f'edges must be integers [E, 2] with E <= {SKELETON_MAX_EDGES}, got {e.dtype} {e.shape}')
+    comp = list(range(n_joints))
+    for i, (a, b) in enumerate(e.tolist()):
+        if not (0 <= a < n_joints and 0 <= b < n_joints) or a == b:
+            raise ValueError(f'edge {i} ({a}, {b}) must join two different joints in [0, {n_joints})')
+        if comp[a] == comp[b]:
+            raise ValueError(f'edge {i} ({a}, {b}) closes a cycle: the skeleton must be a forest')
+        comp = [comp[a] if c == comp[b] else c for c in comp]
+    return np.ascontiguousarray(e, np.int32)
 
 
 def predict_boxes(state: torch.Tensor, ids: torch.Tensor, cameras, frame_sizes, times, coords: str = 'camera', detections=None,

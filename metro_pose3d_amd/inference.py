@@ -386,6 +386,115 @@ def estimate_pose_modes(images_tensor, model_path, k: int = 2, radius: int = 1, 
     return tuple(res)
 
 
+class SkeletonModes(NamedTuple):
+    """The choice among every joint's heat-map modes by the person's bone lengths (estimate_pose_skeleton), output joint order.
+    A joint without a usable mode (a NaN or +Inf logit) has choice -1, NaN in prob and both logs, and keeps its plain pose."""
+    poses: torch.Tensor          # float32 [n, Jout, 3] mm: the chosen modes' positions minus the chosen root's
+    choice: torch.Tensor         # int32 [n, Jout]: the joint's mode in the most probable assignment of the whole skeleton
+    prob: torch.Tensor           # float32 [n, Jout, K]: the marginal probability of every mode under the skeleton
+    log_evidence: torch.Tensor   # float32 [n, Jout]: ln of the probability the modes give to the bone lengths (<= 0), per component
+    log_map: torch.Tensor        # float32 [n, Jout]: ln of the probability of the chosen assignment of the joint's component
+
+
+def skeleton_to_metric(spec, coords01_sel: torch.Tensor) -> torch.Tensor:
+    """Engine.forward_skeleton_modes' coords01_sel [n, J_head, 3] -> the selected poses float32 [n, Jout, 3] in mm:
+    heatmap_to_metric (reference volumetric.py:288-306) of the chosen modes' means minus that of the root -- the chosen root
+    where the output order carries the root head joint (the last one, tfu3d.py:23-25), else its plain mean, which coords01_sel
+    holds there (posterior_to_metric's rule).  fp64 arithmetic on the fp32 input, one rounding per output."""
+    sk = spec.skeleton
+    a, b = _metric_map(spec)
+    a = torch.tensor(a, dtype=torch.float64, device=coords01_sel.device)
+    b = torch.tensor(b, dtype=torch.float64, device=coords01_sel.device)
+    if coords01_sel.dim() != 3 or tuple(coords01_sel.shape[1:]) != (sk.n_head, 3):
+        raise ValueError(f'coords01_sel must be [n, {sk.n_head}, 3], got {tuple(coords01_sel.shape)}')
+    positions = coords01_sel.double() * a + b
+    perm = torch.tensor(list(sk.permutation), dtype=torch.int64, device=coords01_sel.device)
+    return (positions[:, perm] - positions[:, -1:]).float()
+
+
+def _bone_length_rows(bone_lengths, n: int, n_edges: int, device) -> torch.Tensor:
+    """bone_lengths [E] or [n, E], NumPy or tensor, mm -> float64 [n, E] on `device`, contiguous.  The values are not read: NaN
+    (or <= 0) is the caller's way to say that a bone is unknown."""
+    t = torch.from_numpy(np.asarray(bone_lengths)) if not isinstance(bone_lengths, torch.Tensor) else bone_lengths
+    if t.dtype.is_complex or t.dtype == torch.bool or t.dim() not in (1, 2) or t.shape[-1] != n_edges or (t.dim() == 2 and t.shape[0] != n):
+        raise ValueError(f'bone_lengths must be numbers [{n_edges}] or [{n}, {n_edges}] (mm, in skeleton.edges order; NaN: unknown), got '
+                         f'{t.dtype} {tuple(t.shape)}')
+    t = t.to(device=device, dtype=torch.float64, non_blocking=True)
+    return (t[None].expand(n, n_edges) if t.dim() == 1 else t).contiguous()
+
+
+def estimate_pose_skeleton(images_tensor, model_path, bone_lengths, k: int = 2, radius: int = 1, sigma_mm: float = 20.0,
+                           sigma_rel: float = 0.0, cov_scale: float = 1.0, min_length_mm: float = 1.0,
+                           precision: Optional[str] = None, check_finite: Optional[bool] = None, return_uncertainty: bool = False,
+                           return_heatmaps: bool = False, *, shard: Optional[bool] = None):
+    """estimate_pose_modes that also chooses among every joint's modes by the person's bone lengths: estimate_pose's tuple (with
+    the PoseUncertainty and the Heatmaps where asked), then Modes, then SkeletonModes.  A wrist's heat-map with two peaks (a
+    left / right swap, a second person in the crop) has its mean between them and its heavier peak may be the wrong one; only
+    one of the two is a forearm's length from the elbow.  bone_lengths: [E] or [n, E] in mm, NumPy or tensor, in skeleton.edges
+    order (a person's own: Follower.bone_lengths_for; NaN: that bone is unknown).  The skeleton is a tree, so the most probable
+    assignment of a mode to every joint and every mode's marginal are exact, one small launch per forward behind the modes'
+    (metro_plan_bind_skeleton_modes; Engine.forward_skeleton_modes, which holds the other keywords).  It can only choose among
+    the modes found, and lengths are compared in MeTRo's metric scale.  Poses, uncertainty, heat-maps and modes keep the bits
+    estimate_pose_modes gives them; uint8 crops and every precision are served.  A local call: shard=True raises ValueError."""
+    if shard:
+        raise ValueError('estimate_pose_skeleton: sharded calls do not choose modes (shard must be None or False)')
+    if precision is None:
+        precision = os.environ.get('METRO_PRECISION', 'f16')
+    if check_finite is None:
+        check_finite = os.environ.get('METRO_CHECK_FINITE', '1') != '0'
+    if isinstance(images_tensor, np.ndarray):
+        images_tensor = torch.from_numpy(images_tensor)
+    if not isinstance(images_tensor, torch.Tensor):
+        raise ValueError(f'images must be a torch.Tensor or numpy array, got {type(images_tensor)}')
+    if images_tensor.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f'images must be float32 in [0,1] (reference inference.py:18) or uint8 RGB bytes, got {images_tensor.dtype}')
+    device = _resolve_device(images_tensor)
+    n = int(images_tensor.shape[0]) if images_tensor.dim() == 4 else 0
+    with torch.cuda.device(device):
+        eng = _engine_for(model_path, precision, device, max(n, 1))
+        sk, s = eng.spec.skeleton, eng.spec.proc_side
+        if images_tensor.dim() != 4 or tuple(images_tensor.shape[1:]) != (s, s, 3):
+            raise _ShapeError(f'images must be NHWC [N,{s},{s},3] (reference main.py:109-110), got {tuple(images_tensor.shape)}')
+        lengths = _bone_length_rows(bone_lengths, n, len(sk.edges), device)
+        images = images_tensor.to(device, non_blocking=True).contiguous()
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
+        poses, coords01 = f32(n, sk.n_out, 3), f32(n, sk.n_head, 3)
+        cov01, peak = (f32(n, sk.n_head, 6), f32(n, sk.n_head)) if return_uncertainty else (None, None)
+        heat_xy, heat_z = (f32(*eng.heat_shapes(n)[0]), f32(*eng.heat_shapes(n)[1])) if return_heatmaps else (None, None)
+        part = lambda t, i, m: None if t is None else t[i:i + m]
+        parts, bad = [], None
+        for i in range(0, n, eng.max_batch):
+            m = min(eng.max_batch, n - i)
+            parts.append(eng.forward_skeleton_modes(images[i:i + m], lengths[i:i + m], k, radius, None, sigma_mm, sigma_rel, cov_scale,
+                                                    min_length_mm, poses[i:i + m], coords01[i:i + m], part(cov01, i, m),
+                                                    part(peak, i, m), part(heat_xy, i, m), part(heat_z, i, m))[1:])
+            if check_finite:       # folded on the device after every chunk: one synchronisation per call, below
+                cnt = eng.status_words(m).ne(0).sum()
+                bad = cnt if bad is None else bad + cnt
+        if bad is not None and int(bad.item()):
+            raise _lib.NonFiniteError(
+                f'{eng.spec.arch_name} stride {eng.spec.stride} in precision {precision!r}: {int(bad.item())} crops reached the '
+                f'soft-argmax with non-finite statistics' +
+                (' (fp16 storage overflows at 65504: run this model with precision f32m or f64)' if precision == 'f16' else ''))
+        names = np.empty(sk.n_out, dtype=object)
+        names[:] = sk.names_bytes()
+        res = [poses, sk.edges_array(), names]
+        if return_uncertainty:
+            from metro_pose3d_amd.heads import place_covariances
+            res.append(PoseUncertainty(*place_covariances(cov01, peak, eng.spec)) if n else
+                       PoseUncertainty(poses.new_empty((0, sk.n_out, 3, 3)), poses.new_empty((0, sk.n_out))))
+        if return_heatmaps:
+            res.append(Heatmaps(heat_xy, heat_z))
+        if parts:
+            vx, st, choice, prob, info, sel = (torch.cat(t) for t in zip(*parts))
+        else:
+            vx, choice = (torch.empty(sh, dtype=torch.int32, device=device) for sh in ((0, sk.n_out, k), (0, sk.n_out)))
+            st, prob, info, sel = f32(0, sk.n_out, k, Engine.MODE_STATS), f32(0, sk.n_out, k), f32(0, sk.n_out, 2), f32(0, sk.n_head, 3)
+        res.append(modes_to_metric(eng.spec, st, coords01, vx))
+        res.append(SkeletonModes(skeleton_to_metric(eng.spec, sel), choice, prob, info[..., 0].contiguous(), info[..., 1].contiguous()))
+    return tuple(res)
+
+
 class Posterior(NamedTuple):
     """Per-joint heat-map posterior under a Gaussian prior (estimate_pose_posterior), output joint order: the joint's softmax
     times the prior, over the whole volume.  A joint with a NaN in its prior row or a NaN / +Inf logit is NaN everywhere."""
@@ -620,6 +729,9 @@ def main(argv=None):
     parser.add_argument('--modes', type=str, default=None, metavar='K[,R]',
                         help='also print, per joint, its heat-map modes that hold a mass of at least 0.05: up to K places the '
                              'joint may be (window radius R voxels, default 1), each with its mass and position in mm')
+    parser.add_argument('--skeleton', type=str, default=None, metavar='BONES.npy',
+                        help='with --modes: choose among every joint\'s modes by these bone lengths ([E] mm over the skeleton\'s '
+                             'edges, NaN: unknown); prints the joints whose choice is not mode 0, their marginals and the evidence')
     parser.add_argument('--prior', type=str, default=None, metavar='PRIOR.npz',
                         help='also print, per joint, its heat-map posterior under the Gaussian prior of this .npz (arrays '
                              '`positions` [Jout,3] mm, crop-metric frame, and `precision` [Jout,3,3] 1/mm^2): the posterior '
@@ -635,8 +747,8 @@ def main(argv=None):
         except (ValueError, IndexError):
             parser.error(f'--modes takes K or K,R (integers), got {opts.modes!r}')
     if opts.frame:
-        if opts.heatmaps or opts.modes or opts.prior:
-            parser.error('--heatmaps, --modes and --prior go with the crop call (--image), not with --frame')
+        if opts.heatmaps or opts.modes or opts.prior or opts.skeleton:
+            parser.error('--heatmaps, --modes, --skeleton and --prior go with the crop call (--image), not with --frame')
         return _main_frame(opts)
     if opts.crop_dtype:
         parser.error('--crop-dtype goes with --frame')
@@ -650,7 +762,9 @@ def main(argv=None):
         from metro_pose3d_amd.synth import make_images
         img = make_images(1)[0]
     images = torch.from_numpy(img[None])
-    modes = posterior = None
+    modes = posterior = chosen = None
+    if opts.skeleton and not modes_kr:
+        parser.error('--skeleton chooses among modes: it needs --modes K[,R]')
     if opts.prior:
         if modes_kr:
             parser.error('--prior and --modes are two calls: give one of them')
@@ -660,6 +774,13 @@ def main(argv=None):
         prior_lam = prior_lam[None] if prior_lam.ndim == 3 else prior_lam
         poses, edges, names, *more, posterior = estimate_pose_posterior(images, opts.model_path, prior_pos, prior_lam, precision=opts.precision,
                                                                         return_uncertainty=opts.uncertainty, return_heatmaps=bool(opts.heatmaps))
+    elif modes_kr and opts.skeleton:
+        try:
+            poses, edges, names, *more, modes, chosen = estimate_pose_skeleton(
+                images, opts.model_path, np.load(opts.skeleton), modes_kr[0], modes_kr[1], precision=opts.precision,
+                return_uncertainty=opts.uncertainty, return_heatmaps=bool(opts.heatmaps))
+        except ValueError as e:
+            raise SystemExit(str(e))
     elif modes_kr:
         poses, edges, names, *more, modes = estimate_pose_modes(images, opts.model_path, modes_kr[0], modes_kr[1], precision=opts.precision,
                                                                 return_uncertainty=opts.uncertainty, return_heatmaps=bool(opts.heatmaps))
@@ -679,6 +800,15 @@ def main(argv=None):
         for r, name in enumerate(names):
             for i in np.flatnonzero(mass[r] >= 0.05):
                 print(f'{name.decode():>10s}  mode {i}: mass {mass[r, i]:.3f} at {at[r, i, 0]:9.2f} {at[r, i, 1]:9.2f} {at[r, i, 2]:9.2f}')
+    if chosen is not None:
+        choice, prob = chosen.choice[0].cpu().numpy(), chosen.prob[0].cpu().numpy()
+        ev, at = chosen.log_evidence[0].cpu().numpy(), chosen.poses[0].cpu().numpy()
+        moved = np.flatnonzero(choice > 0)
+        print(f'skeleton: {len(moved)} of {len(names)} joints are not in their first mode')
+        for r in moved:
+            marginals = ' '.join(f'{v:.3f}' for v in prob[r])
+            print(f'{names[r].decode():>10s}  mode {choice[r]}: marginals {marginals}   log evidence {ev[r]:8.3f}   selected pose '
+                  f'{at[r, 0]:9.2f} {at[r, 1]:9.2f} {at[r, 2]:9.2f}')
     if posterior is not None:
         at, ev = posterior.positions[0].cpu().numpy(), np.exp(posterior.log_evidence[0].double().cpu().numpy())
         sd = np.sqrt(np.maximum(np.diagonal(posterior.covariance[0].cpu().numpy(), axis1=-2, axis2=-1), 0.0))
